@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- frames/sec of the meterelf hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the untimed preheat, the K timed steps, the
+result line (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds of one timed step, ...).
+Everything else -- the per-kernel and single-lane passes behind `roofline` / `kernel_ms`, the per-step event times and
+the blocks listed below -- runs with --full only (--only / --skip choose among those blocks).
+
+--dump-outputs DIR writes what the timed region's LAST step computed, the records a caller of melf_process_batch_dev
+receives for that batch (rank 0's), one float64 array per record field: DIR/<field>.npy (pos / angle: frames x dials).
+The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 With --gpus N > 1 and no torchrun environment the script launches its own N ranks
 (`python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD process; the parent never touches
@@ -13,7 +22,7 @@ Consecutive steps rotate over --nbuf (default 4) DISTINCT batches (3.8 GB of fra
 never what the previous step left in the 256 MB Infinity Cache.  Each rank owns one GPU and its own batches (weak
 scaling); the only collectives are set-up ones (RCCL broadcast of the calibration blob) and the timing barrier.
 
-Objects on the line besides the contract's fields:
+Objects on the line besides the contract's fields (rccl_ranks on every line, the others with --full only):
   roofline       dominant kernel of the step (k_match), timed by the dispatch's own start/stop stamps
                  (hipExtLaunchKernelGGL) on the stream it runs on, over the timed region
   single_lane    the same K steps on ONE caller stream without the hint (every kernel behind the previous one): the launches roofline /
@@ -28,9 +37,10 @@ Objects on the line besides the contract's fields:
   host_fed       the host-pointer entry point (frames in host memory, PCIe inclusive) -- never `value`
   jpeg_decode    the same path fed with JPEG files (decode on the GPU)
   rccl_ranks     all_reduce(1) over the nccl (= RCCL) backend: number of ranks that took part
-Every timed block runs untimed launches first (`untimed_preheat_steps` / `untimed_preheat_launches` on the line: 300 steps in
-front of the headline, 60 ms of launches in front of the fused-mask and config-5 blocks): the chip's clocks settle 20-30 ms after
-a load begins (tools/fused_first_launches.py), and W + K launches right behind a buffer allocation sit inside that.
+Every timed region, the headline's of a plain run included, runs untimed launches first (`untimed_preheat_steps` /
+`untimed_preheat_launches` on the line: 300 steps in front of the headline, 60 ms of launches in front of the fused-mask and
+config-5 blocks): the chip's clocks settle 20-30 ms after a load begins (tools/fused_first_launches.py), and W + K launches right
+behind a buffer allocation sit inside that.
 """
 import argparse
 import glob
@@ -428,23 +438,25 @@ def full_path_block(env, pfile, sample_dir, seed, steps, warmup, B, nbuf, sustai
         return timed_steps(env, ctx, frames, B, nbuf, H, W, d_results, k, nstreams=nstreams)
 
     run(max(warmup, 1))
-    # 1. a few steps with every kernel bracketed by events (informational per-kernel times) ...
-    ctx.set_profiling(1)
-    ctx.timings()
-    run(max(3, nbuf))
-    kt_all = ctx.timings()
-    # 2. ... the same K steps on one lane with stamps on the dominant kernel only (the dispatch's own start / stop events: ~10 us
-    # of idle time around that kernel per step), pre-heated: the event read-back above leaves the GPU idle for
-    # a moment and the first launches after a pause run at a lower clock
-    ctx.set_profiling(2)
     ns = env.args.streams
     preheat = env.args.preheat
-    run(max(preheat, warmup, 2))
-    ctx.timings()
-    (elapsed1, recs1) = run(steps)
-    kt = ctx.timings()
-    (elapsed1_max, _p1) = max_over_ranks(env, elapsed1)
-    # 3. the timed region
+    full = env.args.full
+    if full:
+        # 1. a few steps with every kernel bracketed by events (informational per-kernel times) ...
+        ctx.set_profiling(1)
+        ctx.timings()
+        run(max(3, nbuf))
+        kt_all = ctx.timings()
+        # 2. ... the same K steps on one lane with stamps on the dominant kernel only (the dispatch's own start / stop events: ~10 us
+        # of idle time around that kernel per step), pre-heated: the event read-back above leaves the GPU idle for
+        # a moment and the first launches after a pause run at a lower clock
+        ctx.set_profiling(2)
+        run(max(preheat, warmup, 2))
+        ctx.timings()
+        (elapsed1, recs1) = run(steps)
+        kt = ctx.timings()
+        (elapsed1_max, _p1) = max_over_ranks(env, elapsed1)
+    # 3. the timed region (a plain run: the only pass after the warm-up)
     ctx.set_profiling(0)
     resident = two_lanes and ns == 1 and env.args.mode == 'resident'
     ns_timed = 2 if (two_lanes and ns == 1 and not resident) else ns
@@ -452,14 +464,20 @@ def full_path_block(env, pfile, sample_dir, seed, steps, warmup, B, nbuf, sustai
     run(max(preheat, warmup, 2), ns_timed)
     (elapsed, recs) = run(steps, ns_timed)
     (elapsed_max, per_rank) = max_over_ranks(env, elapsed)
-    # per-step distribution: the same K steps again, an event after each (this rank's; single stream)
-    step_ms = step_event_times(env, ctx, frames, B, nbuf, H, W, d_results, max(steps, 20))
+    # the last timed step (i = steps - 1) wrote record slice (steps - 1) % nbuf, the records of batch (steps - 1) % nbuf
+    last = (steps - 1) % nbuf
     out = {'ctx': ctx, 'P': P, 'H': H, 'W': W, 'frames': frames, 'recs': recs, 'elapsed': elapsed_max,
-           'per_rank_ms': [round(t / steps * 1e3, 4) for t in per_rank], 'kt': kt, 'kt_all': kt_all,
-           'roofline': match_roofline(P, H, W, kt, B * steps, traffic.get(label + ':k_match'))}
+           'per_rank_ms': [round(t / steps * 1e3, 4) for t in per_rank], 'last_step_recs': recs[last * B:(last + 1) * B]}
     out['mode'] = ('one melf_process_batch_dev call per step on one caller stream with melf_ctx_set_frames_resident (the library alternates its two lanes)' if resident else
                    'one melf_process_batch_dev call per step, consecutive steps on %d caller stream(s)%s'
                    % (ns_timed, ' (the context runs them on its two lanes)' if ns_timed > 1 else ''))
+    out['match_layout'] = ctx.last_match()
+    if not full:
+        ctx.set_frames_resident(False)
+        return out
+    # per-step distribution: the same K steps again, an event after each (this rank's; single stream)
+    step_ms = step_event_times(env, ctx, frames, B, nbuf, H, W, d_results, max(steps, 20))
+    out.update({'kt': kt, 'kt_all': kt_all, 'roofline': match_roofline(P, H, W, kt, B * steps, traffic.get(label + ':k_match'))})
     out['single_lane'] = {'ms_per_step': round(elapsed1_max / steps * 1e3, 4), 'frames_per_s': round(env.world * B * steps / elapsed1_max, 1), 'steps': steps,
                           'what': 'the same K steps as K melf_process_batch_dev calls on one stream: every kernel behind the previous one (the '
                                   'step is the sum of its kernels); these are the launches `roofline` and `kernel_ms` describe',
@@ -976,6 +994,16 @@ def jpeg_block(ctx, sample_dir, H, W, traffic=None):
             'decoded_frames_equal_libjpeg_turbo': same, 'files_ok': int((jstatus == 0).sum())}
 
 
+def dump_outputs(d, recs, ndials):
+    """--dump-outputs: the records of the timed region's last step (one batch, this rank's), one float64 array per field (exact for
+    every field: i4 / u4 / f4 / f8); pos and angle keep the params' dials only."""
+    from meterelf_amd import _hip
+    os.makedirs(d, exist_ok=True)
+    for name in _hip.RESULT_DTYPE.names:
+        a = recs[name][:, :ndials] if recs[name].ndim == 2 else recs[name]
+        np.save(os.path.join(d, name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def dry_run(args):
     """Launch / rendezvous / collective plumbing without a GPU (CI): no step is run, nothing is measured."""
     import torch
@@ -1027,8 +1055,11 @@ def main():
     ap.add_argument('--mode', default='two_streams', choices=['two_streams', 'resident'], help='how the timed regions drive the two lanes: consecutive steps on two caller '
                     'streams, or one caller stream with melf_ctx_set_frames_resident')
     ap.add_argument('--preheat', type=int, default=300, help='untimed steps run immediately before the timed region (clock settling)')
-    ap.add_argument('--skip', default='', help='comma list of blocks to skip: ' + ','.join(ALL_BLOCKS))
-    ap.add_argument('--only', default='', help='comma list of extra blocks to run (default: all)')
+    ap.add_argument('--full', action='store_true', help='everything besides the headline: the per-kernel / single-lane passes (roofline, '
+                    'kernel_ms), the per-step event times and the extra blocks ' + ','.join(ALL_BLOCKS))
+    ap.add_argument('--skip', default='', help='with --full: comma list of blocks to skip: ' + ','.join(ALL_BLOCKS))
+    ap.add_argument('--only', default='', help='with --full: comma list of extra blocks to run (default: all)')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR', help='write the records of the last timed step as DIR/<field>.npy (float64)')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'], help='process-group backend (nccl = RCCL)')
     ap.add_argument('--share-gpu', action='store_true', help='rehearsal: ranks share the visible GPUs (gloo backend only)')
     ap.add_argument('--dry-run', action='store_true', help='launcher / collective rehearsal without a GPU; measures nothing')
@@ -1036,6 +1067,8 @@ def main():
     args = ap.parse_args()
     if args.ceiling_child:
         return ceiling_child_main(args.ceiling_child)
+    if (args.only or args.skip) and not args.full:
+        ap.error('--only / --skip choose among the blocks of --full')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         raise SystemExit(launch_ranks(args))
@@ -1045,7 +1078,7 @@ def main():
     if args.dry_run:
         return dry_run(args)
 
-    blocks = set(ALL_BLOCKS)
+    blocks = set(ALL_BLOCKS) if args.full else set()
     if args.only:
         blocks = set(x for x in args.only.split(',') if x)
     blocks -= set(x for x in args.skip.split(',') if x)
@@ -1059,7 +1092,7 @@ def main():
         one = torch.ones(1, dtype=torch.int32, device=env.device if env.backend == 'nccl' else 'cpu')
         env.dist.all_reduce(one)
         rccl_ranks = int(one.item()) if env.backend == 'nccl' else None
-    traffic = Traffic()
+    traffic = Traffic() if args.full else None
     single = world == 1
 
     # ---- headline: BASELINE config 3 ----
@@ -1071,11 +1104,14 @@ def main():
                            two_stream_s=1.0 if 'twostream' in blocks else 0.0)
     (ctx, P, H, W, B) = (full['ctx'], full['P'], full['H'], full['W'], args.batch)
     n_ok = int((full['recs'][:B]['status'] == 0).sum())
-    roofline = full['roofline']
-    roofline['k_dials_avg_launch_ms'] = full['kernel_ms'].get('k_dials')
-    roofline['k_prep_avg_launch_ms'] = full['kernel_ms'].get('k_lplane')
-    roofline_dials = dials_roofline(full['kernel_ms'], traffic, main_label)
-    roofline_prep = prep_roofline(full['P'], full['H'], full['W'], full['kernel_ms'], traffic, main_label, args.batch)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, full['last_step_recs'], int(P.ndials))
+    if args.full:
+        roofline = full['roofline']
+        roofline['k_dials_avg_launch_ms'] = full['kernel_ms'].get('k_dials')
+        roofline['k_prep_avg_launch_ms'] = full['kernel_ms'].get('k_lplane')
+        roofline_dials = dials_roofline(full['kernel_ms'], traffic, main_label)
+        roofline_prep = prep_roofline(full['P'], full['H'], full['W'], full['kernel_ms'], traffic, main_label, args.batch)
 
     fused = None
     if 'fused' in blocks:
@@ -1128,12 +1164,18 @@ def main():
                        'global_batch': B * world, 'parallelism': 'dp%d' % world, 'frames_read_ok_batch0': n_ok,
                        'untimed_preheat_steps': args.preheat, 'mode': full['mode']},
             'per_rank_ms_per_step': full['per_rank_ms'], 'rccl_ranks': rccl_ranks, 'backend': env.backend,
-            'kernel_ms': full['kernel_ms'], 'step_events': full.get('step_events'), 'match_layout': full.get('match_layout'),
-            'roofline': roofline, 'roofline_dials': roofline_dials, 'roofline_prep': roofline_prep, 'sustained': full.get('sustained'), 'two_streams': full.get('two_streams'),
-            'single_lane': full.get('single_lane'), 'resident_hint': full.get('resident_hint'),
-            'cpu_baseline': full.get('cpu'),
-            'fused_mask': fused, 'config4': cfg4, 'config5': cfg5, 'host_fed': hostfed, 'jpeg_decode': jpeg,
+            'match_layout': full.get('match_layout'), 'full': args.full,
         }
+        if args.full:
+            line.update({
+                'kernel_ms': full['kernel_ms'], 'step_events': full.get('step_events'),
+                'roofline': roofline, 'roofline_dials': roofline_dials, 'roofline_prep': roofline_prep, 'sustained': full.get('sustained'),
+                'two_streams': full.get('two_streams'), 'single_lane': full.get('single_lane'), 'resident_hint': full.get('resident_hint'),
+                'cpu_baseline': full.get('cpu'),
+                'fused_mask': fused, 'config4': cfg4, 'config5': cfg5, 'host_fed': hostfed, 'jpeg_decode': jpeg,
+            })
+        if args.dump_outputs:
+            line['dumped_outputs'] = args.dump_outputs
         print(json.dumps(line))
         sys.stdout.flush()
     if env.dist is not None:

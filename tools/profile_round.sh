@@ -10,7 +10,7 @@
 #       config5  fused mask, 1080p, B=512
 #       jpeg     1024 fixture files
 #     -> traffic.json: bytes per launch for bench.py, stamped with the hash of the kernel sources they were measured on
-#  2. rocprofv3 --kernel-trace --stats of the bench command on one lane and without its two_streams blocks (`--skip twostream --no-resident-hint`:
+#  2. rocprofv3 --kernel-trace --stats of the bench command on one lane and without its two_streams blocks (`--full --skip twostream --no-resident-hint`:
 #     launches that share the chip with another stream's kernels have stretched durations and would blur the per-kernel
 #     averages the roofline lines are checked against) -> bench_kernel_stats.csv + the JSON line of that run
 #  3. one --kernel-trace --stats run PER WORKLOAD whose roofline the line quotes, so that every roofline.frac can be
@@ -127,7 +127,7 @@ stats() {  # name, command...
   echo "stats $name done" >> $OUT/progress.txt
 }
 # (--no-resident-hint: every timed region on ONE caller stream, so that no launch of the trace shares the chip with another lane's kernels)
-stats bench python3 bench.py --skip twostream --no-resident-hint
+stats bench python3 bench.py --full --skip twostream --no-resident-hint
 mv $OUT/bench_kernel_stats_bench.csv $OUT/bench_kernel_stats.csv
 mv $OUT/bench_stdout.txt $OUT/bench_under_rocprof.json; mv $OUT/bench_stderr.txt $OUT/bench_under_rocprof.err
 stats config2 python3 tools/run_stage.py fused --iters 60 --hw 640x480 --batch 256 --nbuf 4 --profiling 0

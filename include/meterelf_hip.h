@@ -147,6 +147,31 @@ int melf_process_batch(melf_ctx* ctx, const uint8_t* frames_host, int n, int H, 
 int melf_process_batch_dev(melf_ctx* ctx, const void* d_frames, int n, int H, int W,
                            size_t frame_stride, void* d_results, melf_result* out_host, void* stream);
 
+/* ---- the same path for the frames callers have: RGB, BGRA / BGRx, RGBA / RGBx, padded rows ---------------
+ * What get_bgr_image + _crop_meter would have read (meterelf/_image.py:46-55) from the packed BGR frame made of each
+ * frame: the records are byte-identical to melf_process_batch(_dev) on that frame, without the conversion pass.  The
+ * kernels read the layout in place; only the meter_rect crop is ever read.
+ * Frame f's row y starts at frames + f * frame_stride + y * row_pitch.  The last row of the last frame needs no padding:
+ * the buffer must hold (n - 1) * frame_stride + (H - 1) * row_pitch + W * bytes per pixel bytes.  The 4-byte formats need
+ * a 4-byte aligned base, row_pitch and frame_stride; the 3-byte formats take any alignment.  An unknown format, a pitch
+ * or stride too small, a misaligned 4-byte layout or a NULL descriptor return MELF_ERR_INVALID before anything runs.
+ * melf_process_stream_dev, the fused full-frame mask (melf_hls_inrange_close*), melf_aligned_average and the JPEG entry
+ * points take packed BGR only. */
+enum { MELF_PIX_BGR = 0, MELF_PIX_RGB = 1, MELF_PIX_BGRA = 2, MELF_PIX_RGBA = 3 };
+typedef struct melf_frames {
+    int32_t pixel_format;  /* MELF_PIX_*; the 4th byte of BGRA / RGBA is ignored                          */
+    int32_t n, H, W;
+    int64_t row_pitch;     /* bytes between rows, >= W * bytes per pixel                                 */
+    int64_t frame_stride;  /* bytes between frames, >= (H - 1) * row_pitch + W * bytes per pixel          */
+} melf_frames;
+/* Host frames, as melf_process_batch: only the crop rows (ccols * bytes per pixel, read at the caller's pitch) are
+ * packed into the pinned staging buffers and cross PCIe. */
+int melf_process_frames(melf_ctx* ctx, const void* frames_host, const melf_frames* f, melf_result* out_host);
+/* Frames in HBM, exactly as melf_process_batch_dev: the same lanes, melf_ctx_set_frames_resident, caller streams,
+ * and NULL d_results / out_host semantics. */
+int melf_process_frames_dev(melf_ctx* ctx, const void* d_frames, const melf_frames* f, void* d_results,
+                            melf_result* out_host, void* stream);
+
 /* ---- stage entry points (parity tests and roofline runs) ----------------- */
 
 /* convert_to_hls (meterelf/_utils.py:100-102): cvtColor(BGR2HLS_FULL) + uint8

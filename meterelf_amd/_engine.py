@@ -144,6 +144,34 @@ class MeterReader:
         """Full camera frames (N, H, W, 3) BGR -> records."""
         return self.ctx.process_batch(frames)
 
+    def read_frame_views(self, frames, pixel_format: str = 'bgr', out=None):
+        """Full camera frames in the layout the caller has -> records, equal to read_frames() of the packed BGR frames made from
+        them (melf_process_frames*).  frames: (N, H, W, C) uint8, a numpy array / torch CPU tensor (host path) or a torch tensor
+        on this reader's GPU (enqueued on torch.cuda.current_stream); pixel_format 'bgr', 'rgb' (C = 3), 'bgra', 'rgba' (C = 4,
+        the 4th byte ignored); padded rows and frames and rgba[..., :3]-style views are read in place (_hip.frames_view).
+        out: a uint8 device tensor (N, RESULT_DTYPE.itemsize) on the same GPU that receives the records without synchronising
+        the stream (device frames only); returns it.  Otherwise returns the records."""
+        v = _hip.frames_view(frames, pixel_format)
+        if not v.on_device:
+            if out is not None:
+                raise ValueError('out= takes the records of device frames only')
+            return self.ctx.process_frames(v.ptr, v.pixel_format, v.n, v.H, v.W, v.row_pitch, v.frame_stride)
+        import torch
+        if v.device != self.device:
+            raise ValueError('frames are on cuda:%s, the reader on cuda:%d' % (v.device, self.device))
+        stream = torch.cuda.current_stream(self.device)
+        if out is None:
+            return self.ctx.process_frames_dev(v.ptr, v.pixel_format, v.n, v.H, v.W, v.row_pitch, v.frame_stride,
+                                               stream=stream.cuda_stream)
+        if (not _hip._is_torch(out) or out.dtype != torch.uint8 or out.device != v.array.device or not out.is_contiguous()
+                or tuple(out.shape) != (v.n, _hip.RESULT_DTYPE.itemsize)):
+            raise ValueError('out must be a contiguous uint8 tensor of shape (%d, %d) on %s' % (v.n, _hip.RESULT_DTYPE.itemsize, v.array.device))
+        if v.copied:
+            v.array.record_stream(stream)   # the packed copy lives until the stream has passed the call's kernels
+        self.ctx.process_frames_dev(v.ptr, v.pixel_format, v.n, v.H, v.W, v.row_pitch, v.frame_stride, d_results_ptr=out.data_ptr(),
+                                    want_host=False, stream=stream.cuda_stream)
+        return out
+
     def read_crops(self, crops: np.ndarray) -> np.ndarray:
         """Already meter_rect-cropped images (the reference's bgr_image injection)."""
         (_n, h, w, _c) = crops.shape

@@ -6,6 +6,7 @@ MI355X is visible, everything here raises.
 import ctypes as C
 import os
 import sys
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -60,6 +61,16 @@ class MelfMatchInfo(C.Structure):
                 ('tiles', C.c_int32), ('reserved', C.c_int32 * 6)]
 
 
+class MelfFrames(C.Structure):
+    _fields_ = [('pixel_format', C.c_int32), ('n', C.c_int32), ('H', C.c_int32), ('W', C.c_int32),
+                ('row_pitch', C.c_int64), ('frame_stride', C.c_int64)]
+
+
+# pixel layouts of melf_process_frames* (MELF_PIX_*); the 4th byte of BGRA / RGBA (BGRx / RGBx) is ignored
+PIX_BGR, PIX_RGB, PIX_BGRA, PIX_RGBA = 0, 1, 2, 3
+PIX_CODES = {'bgr': PIX_BGR, 'rgb': PIX_RGB, 'bgra': PIX_BGRA, 'rgba': PIX_RGBA, 'bgrx': PIX_BGRA, 'rgbx': PIX_RGBA}
+PIX_BYTES = {PIX_BGR: 3, PIX_RGB: 3, PIX_BGRA: 4, PIX_RGBA: 4}
+
 MATCH_KERNEL_NAMES = ('dot4', 'mfma', 'gen')
 
 RESULT_DTYPE = np.dtype([('status', '<i4'), ('match_x', '<i4'), ('match_y', '<i4'), ('failed_dial', '<i4'),
@@ -79,6 +90,7 @@ EXPORTS = [
     'melf_last_error', 'melf_abi_version', 'melf_device_count', 'melf_build_dial_masks',
     'melf_blob_size', 'melf_blob_pack', 'melf_blob_params', 'melf_ctx_create', 'melf_ctx_create_bcast', 'melf_ctx_destroy',
     'melf_ctx_params', 'melf_ctx_sync', 'melf_ctx_get_masks', 'melf_process_batch', 'melf_process_batch_dev', 'melf_process_stream_dev',
+    'melf_process_frames', 'melf_process_frames_dev',
     'melf_bgr2hls', 'melf_hls_inrange_close', 'melf_hls_inrange_close_dev', 'melf_match_ccoeff',
     'melf_read_dials', 'melf_aligned_average', 'melf_inrange', 'melf_ctx_fused_table_ties', 'melf_ctx_set_frames_resident', 'melf_ctx_last_match', 'melf_match_layout_query', 'melf_match_gen_plan_query', 'melf_ctx_set_profiling', 'melf_ctx_timings', 'melf_kernel_name',
     'melf_jpeg_probe', 'melf_jpeg_probe_batch', 'melf_jpeg_decode_batch', 'melf_jpeg_clean_segment', 'melf_jpeg_process_batch',
@@ -117,6 +129,8 @@ def lib():
     L.melf_ctx_sync.argtypes = [vp]
     L.melf_process_batch.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp]
     L.melf_process_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp]
+    L.melf_process_frames.argtypes = [vp, vp, C.POINTER(MelfFrames), vp]
+    L.melf_process_frames_dev.argtypes = [vp, vp, C.POINTER(MelfFrames), vp, vp, vp]
     L.melf_process_stream_dev.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, vp]
     L.melf_bgr2hls.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp]
     L.melf_hls_inrange_close.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
@@ -165,6 +179,110 @@ def device_count():
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+class FramesView(NamedTuple):
+    """How the kernels read a batch of frames in place (frames_view)."""
+    ptr: int            # address of frame 0, row 0, pixel 0
+    on_device: bool     # True: a torch tensor on a GPU (ptr is a device address)
+    device: Optional[int]   # that GPU's index (None for host memory)
+    pixel_format: int   # PIX_*
+    n: int
+    H: int
+    W: int
+    row_pitch: int      # bytes between rows
+    frame_stride: int   # bytes between frames
+    extent: int         # bytes read from ptr: (n - 1) * frame_stride + (H - 1) * row_pitch + W * bytes per pixel
+    copied: bool        # the layout could not be described and the frames were copied once to a packed array
+    array: object       # what ptr points into (the caller's array, or the copy): keep it alive while the call runs
+
+
+def _is_torch(x):
+    return type(x).__module__.split('.')[0] == 'torch'
+
+
+def _owner_span(a, is_torch):
+    """(start, end) of the memory that `a`'s storage owns: the bytes a view may read beyond its own elements."""
+    if is_torch:
+        st = a.untyped_storage()
+        return st.data_ptr(), st.data_ptr() + st.nbytes()
+    root = a
+    while isinstance(root.base, np.ndarray):
+        root = root.base
+    lo = hi = root.ctypes.data
+    for (k, st) in zip(root.shape, root.strides):
+        if k == 0:
+            return lo, lo
+        if st < 0:
+            lo += (k - 1) * st
+        else:
+            hi += (k - 1) * st
+    return lo, hi + root.itemsize
+
+
+def frames_view(frames, pixel_format='bgr'):
+    """Describes an (N, H, W, C) uint8 numpy array or torch tensor as melf_process_frames* read it -- the one place that maps an
+    array's layout to pointer, pixel format, row pitch and frame stride.  pixel_format: the order of the array's channels,
+    'bgr' / 'rgb' for C = 3, 'bgra' / 'rgba' (or 'bgrx' / 'rgbx') for C = 4.  A 3-channel view whose pixels are 4 bytes apart
+    (rgba[..., :3]) is read as the 4-byte format of the same order; padded rows and frames (frames[:, :, :w], frames[::2]) are
+    read in place.  A layout the kernels cannot read -- a channel stride other than 1, negative or odd strides, a misaligned
+    4-byte layout -- is copied once to a packed array (FramesView.copied).  Not uint8, or C not 3 / 4: ValueError."""
+    is_torch = _is_torch(frames)
+    if is_torch:
+        if str(frames.dtype) != 'torch.uint8':
+            raise ValueError('frames must be uint8, not %s' % frames.dtype)
+        shape = tuple(frames.shape)
+        strides = tuple(frames.stride())          # elements = bytes for uint8
+        ptr = frames.data_ptr()
+        on_device = frames.device.type == 'cuda'
+        device = frames.device.index if on_device else None
+    else:
+        frames = np.asarray(frames)
+        if frames.dtype != np.uint8:
+            raise ValueError('frames must be uint8, not %s' % frames.dtype)
+        shape = frames.shape
+        strides = frames.strides
+        ptr = frames.ctypes.data
+        (on_device, device) = (False, None)
+    if len(shape) != 4 or shape[3] not in (3, 4):
+        raise ValueError('frames must be (N, H, W, 3) or (N, H, W, 4), not %s' % (shape,))
+    fmt = str(pixel_format).lower()
+    if fmt not in PIX_CODES or (shape[3] == 3) != (PIX_BYTES[PIX_CODES[fmt]] == 3):
+        raise ValueError('pixel_format %r does not name the %d channels of the frames' % (pixel_format, shape[3]))
+    code = PIX_CODES[fmt]
+    (n, H, W, ch) = shape
+    (fs, rp, ps, cs) = strides
+    if ch == 3 and ps == 4 and cs == 1:
+        code = PIX_BGRA if code == PIX_BGR else PIX_RGBA   # a 3-channel view of 4-byte pixels: read the 4-byte format
+    bpp = PIX_BYTES[code]
+    # strides of dimensions of size 1 are never stepped over: make them what a packed array has
+    if W == 1:
+        ps = bpp
+    if H == 1:
+        rp = W * bpp
+    if n == 1:
+        fs = (H - 1) * rp + W * bpp
+    extent = (n - 1) * fs + (H - 1) * rp + W * bpp if n else 0
+    ok = (cs == 1 and ps == bpp and rp >= W * bpp and fs >= (H - 1) * rp + W * bpp and rp <= 2 ** 31 - 1)
+    if ok and bpp == 4:
+        ok = (ptr | rp | fs) % 4 == 0
+    if ok and n and bpp == 4 and ch == 3:
+        # the ignored 4th byte of the last pixel lies behind the view's own bytes: it must belong to the same memory
+        (lo, hi) = _owner_span(frames, is_torch)
+        ok = lo <= ptr and ptr + extent <= hi
+    if not ok:
+        # a fresh allocation (aligned) even where the array is contiguous already (a misaligned 4-byte layout)
+        if is_torch:
+            import torch
+            frames = frames.clone(memory_format=torch.contiguous_format)
+        else:
+            frames = np.array(frames, order='C', copy=True)
+        code = PIX_CODES[fmt]
+        bpp = PIX_BYTES[code]
+        (rp, fs) = (W * bpp, H * W * bpp)
+        ptr = frames.data_ptr() if is_torch else frames.ctypes.data
+        extent = n * fs
+    return FramesView(int(ptr), on_device, device, code, n, H, W, int(rp), int(fs), int(extent), not ok, frames)
 
 
 def jpeg_probe(data):
@@ -366,6 +484,23 @@ class Context:
         check(self._L.melf_process_batch_dev(
             self._h, C.c_void_p(d_frames_ptr), n, H, W, frame_stride or H * W * 3,
             C.c_void_p(d_results_ptr) if d_results_ptr else None,
+            _ptr(out) if want_host else None, C.c_void_p(stream) if stream else None))
+        return out
+
+    def process_frames(self, frames_ptr, pixel_format, n, H, W, row_pitch, frame_stride):
+        """Host frames in any PIX_* layout (melf_process_frames; frames_view describes an array) -> records."""
+        out = np.zeros(n, RESULT_DTYPE)
+        f = MelfFrames(pixel_format, n, H, W, row_pitch, frame_stride)
+        check(self._L.melf_process_frames(self._h, C.c_void_p(frames_ptr), C.byref(f), _ptr(out)))
+        return out
+
+    def process_frames_dev(self, d_frames_ptr, pixel_format, n, H, W, row_pitch, frame_stride, d_results_ptr=None, want_host=True,
+                           stream=None):
+        """Frames in HBM in any PIX_* layout (melf_process_frames_dev, as process_batch_dev).  Returns records when want_host."""
+        out = np.zeros(n, RESULT_DTYPE) if want_host else None
+        f = MelfFrames(pixel_format, n, H, W, row_pitch, frame_stride)
+        check(self._L.melf_process_frames_dev(
+            self._h, C.c_void_p(d_frames_ptr), C.byref(f), C.c_void_p(d_results_ptr) if d_results_ptr else None,
             _ptr(out) if want_host else None, C.c_void_p(stream) if stream else None))
         return out
 

@@ -27,10 +27,12 @@ __device__ inline bool better(float v, int i, float bv, int bi)
     return i != INT_MAX && (bi == INT_MAX || v > bv || (v == bv && i < bi));
 }
 
-template <bool FROM_BGR>
-__global__ __launch_bounds__(256) void k_match(MatchSrc src, MatchGeom g, const uint32_t* __restrict__ tplT,
-                                               int rh, int rw, int nrb, float* __restrict__ result_map,
-                                               MatchPartial* __restrict__ partials, int nparts)
+// The body of k_match and k_match_px4.  PX: 1 = packed single-channel u8 images, 3 = 3-byte pixels (BGR / RGB: L = (max + min) / 2
+// does not depend on the channel order), 4 = 4-byte pixels (BGRA / RGBA, 4-byte aligned, the 4th byte ignored).
+template <int PX>
+__device__ __forceinline__ void match_tile(MatchSrc src, MatchGeom g, const uint32_t* __restrict__ tplT,
+                                           int rh, int rw, int nrb, float* __restrict__ result_map,
+                                           MatchPartial* __restrict__ partials, int nparts)
 {
     constexpr int R = MATCH_R;
     extern __shared__ uint32_t lds[];
@@ -55,9 +57,12 @@ __global__ __launch_bounds__(256) void k_match(MatchSrc src, MatchGeom g, const 
                     const int x = xb + c4 * 4 + k;
                     uint32_t v = 0;
                     if (x < src.cols) {
-                        if (FROM_BGR) {
+                        if (PX == 3) {
                             const uint8_t* p = prow + (size_t)(src.x0 + x) * 3;
                             v = (uint32_t)hls_lightness(p[0], p[1], p[2]);
+                        } else if (PX == 4) {
+                            const uint32_t px = *(const uint32_t*)(prow + (size_t)(src.x0 + x) * 4);
+                            v = (uint32_t)hls_lightness(px & 255, (px >> 8) & 255, (px >> 16) & 255);
                         } else {
                             v = prow[src.x0 + x];
                         }
@@ -141,6 +146,22 @@ __global__ __launch_bounds__(256) void k_match(MatchSrc src, MatchGeom g, const 
     }
 }
 
+template <bool FROM_BGR>
+__global__ __launch_bounds__(256) void k_match(MatchSrc src, MatchGeom g, const uint32_t* __restrict__ tplT,
+                                               int rh, int rw, int nrb, float* __restrict__ result_map,
+                                               MatchPartial* __restrict__ partials, int nparts)
+{
+    match_tile<FROM_BGR ? 3 : 1>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts);
+}
+
+// BGRA / RGBA frames (melf_process_frames*)
+__global__ __launch_bounds__(256) void k_match_px4(MatchSrc src, MatchGeom g, const uint32_t* __restrict__ tplT,
+                                                   int rh, int rw, int nrb, float* __restrict__ result_map,
+                                                   MatchPartial* __restrict__ partials, int nparts)
+{
+    match_tile<4>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts);
+}
+
 int match_parts(const MatchGeom& g, int rows, int cols)
 {
     const int rh = rows - g.th + 1, rw = cols - g.tw + 1;
@@ -149,7 +170,7 @@ int match_parts(const MatchGeom& g, int rows, int cols)
     return nrb * ncb;
 }
 
-void launch_match(const MatchSrc& src, bool from_bgr, int n, const MatchGeom& g, const uint32_t* d_tplT,
+void launch_match(const MatchSrc& src, int pix, int n, const MatchGeom& g, const uint32_t* d_tplT,
                   float* d_result_map, MatchPartial* d_partials, int* nparts_out, hipStream_t stream)
 {
     const int rh = src.rows - g.th + 1, rw = src.cols - g.tw + 1;
@@ -158,11 +179,14 @@ void launch_match(const MatchSrc& src, bool from_bgr, int n, const MatchGeom& g,
     if (nparts_out) *nparts_out = nparts;
     const size_t shmem = (size_t)g.lds_rows * g.ldsw * sizeof(uint32_t);
     dim3 grid(nparts, n), block(256);
-    if (from_bgr)
-        hipLaunchKernelGGL(k_match<true>, grid, block, shmem, stream, src, g, d_tplT, rh, rw, nrb, d_result_map,
+    if (pix == PIX_PLANE)
+        hipLaunchKernelGGL(k_match<false>, grid, block, shmem, stream, src, g, d_tplT, rh, rw, nrb, d_result_map,
+                           d_partials, nparts);
+    else if (pix_bytes(pix) == 4)
+        hipLaunchKernelGGL(k_match_px4, grid, block, shmem, stream, src, g, d_tplT, rh, rw, nrb, d_result_map,
                            d_partials, nparts);
     else
-        hipLaunchKernelGGL(k_match<false>, grid, block, shmem, stream, src, g, d_tplT, rh, rw, nrb, d_result_map,
+        hipLaunchKernelGGL(k_match<true>, grid, block, shmem, stream, src, g, d_tplT, rh, rw, nrb, d_result_map,
                            d_partials, nparts);
 }
 

@@ -1034,15 +1034,15 @@ static int gen_entry(melf_ctx* c, int rows, int cols, int n, melf_ctx::GenEntry*
 
 // prep + match of m images on stream ls with lane bl's work buffers; *parts / *nparts: per-frame (max, first arg-max)
 // partials for the consumer (k_dials or the host fold of melf_match_ccoeff)
-static int run_match_impl(melf_ctx* c, const MatchSrc& ms, bool from_bgr, int m, int bl, hipStream_t ls, float* d_map,
+static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int bl, hipStream_t ls, float* d_map,
                           MatchPartial** parts, int* nparts, TimedEvent& ev);
-static int run_match(melf_ctx* c, const MatchSrc& ms, bool from_bgr, int m, int bl, hipStream_t ls, float* d_map,
+static int run_match(melf_ctx* c, const MatchSrc& ms, int pix, int m, int bl, hipStream_t ls, float* d_map,
                      MatchPartial** parts, int* nparts)
 {
     TimedEvent ev;
     ev.kernel = MELF_K_MATCH;
     ev.start = ev.stop = nullptr;
-    const int rc = run_match_impl(c, ms, from_bgr, m, bl, ls, d_map, parts, nparts, ev);
+    const int rc = run_match_impl(c, ms, pix, m, bl, ls, d_map, parts, nparts, ev);
     if (rc == MELF_SUCCESS && ev.start && ev.stop) {
         c->events.push_back(ev);
     } else {   // nothing was launched with them (an allocation failed on the way)
@@ -1051,7 +1051,7 @@ static int run_match(melf_ctx* c, const MatchSrc& ms, bool from_bgr, int m, int 
     }
     return rc;
 }
-static int run_match_impl(melf_ctx* c, const MatchSrc& ms, bool from_bgr, int m, int bl, hipStream_t ls, float* d_map,
+static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int bl, hipStream_t ls, float* d_map,
                           MatchPartial** parts, int* nparts, TimedEvent& ev)
 {
     const melf_params& P = c->P;
@@ -1076,7 +1076,7 @@ static int run_match_impl(melf_ctx* c, const MatchSrc& ms, bool from_bgr, int m,
         *parts = c->d_lpart[bl];
         {
             KernelTimer t(c, MELF_K_LPLANE, ls);
-            launch_mfma_prep(ms, from_bgr, m, pl, P.th, P.tw, c->d_lg[bl], c->d_rsum[bl], ls);
+            launch_mfma_prep(ms, pix, m, pl, P.th, P.tw, c->d_lg[bl], c->d_rsum[bl], ls);
         }
         info.rows_per_wave = pl.rb; info.full_waves = pl.na; info.pair_waves = 2 * pl.np;
         info.waves = pl.nparts * pl.groups; info.tiles = pl.ntiles;
@@ -1094,7 +1094,7 @@ static int run_match_impl(melf_ctx* c, const MatchSrc& ms, bool from_bgr, int m,
         *parts = c->d_lpart[bl];
         {
             KernelTimer t(c, MELF_K_LPLANE, ls);
-            launch_match_prep(ms, from_bgr, m, pl.groups, pl.rows_pad, pl.nkb, pl.rwp, P.tw, c->d_lg[bl], c->d_rsum[bl], ls);
+            launch_match_prep(ms, pix, m, pl.groups, pl.rows_pad, pl.nkb, pl.rwp, P.tw, c->d_lg[bl], c->d_rsum[bl], ls);
         }
         const GenDev& dev = ge->dev;
         fill_gen_info(&info, pl);
@@ -1104,7 +1104,7 @@ static int run_match_impl(melf_ctx* c, const MatchSrc& ms, bool from_bgr, int m,
         if (int rc = grow(&c->d_lpart[bl], &c->lpart_cap[bl], (size_t)m * *nparts)) return rc;
         *parts = c->d_lpart[bl];
         KernelTimer t(c, MELF_K_MATCH, ls);
-        launch_match(ms, from_bgr, m, c->mg, c->d_tplT, d_map, *parts, nullptr, ls);
+        launch_match(ms, pix, m, c->mg, c->d_tplT, d_map, *parts, nullptr, ls);
         info.tiles = *nparts;
     }
     if (trace)
@@ -1118,9 +1118,32 @@ static int run_match_impl(melf_ctx* c, const MatchSrc& ms, bool from_bgr, int m,
 static const int MAX_FRAMES_PER_LAUNCH = 32768;
 
 // rect (optional): {x0, y0, x1, y1} of the meter crop inside the H x W frames instead of the context's meter_rect
-// (the host-fed path uploads only the crop: its "frames" are the crops themselves)
+// (the host-fed path uploads only the crop: its "frames" are the crops themselves); row_stride: bytes between rows
+// (0 = packed); pix: the frames' pixel layout (MELF_PIX_*)
 static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
-                            void* d_results, melf_result* out_host, hipStream_t st, const int* rect = nullptr, int row_stride = 0);
+                            void* d_results, melf_result* out_host, hipStream_t st, const int* rect = nullptr, int row_stride = 0,
+                            int pix = MELF_PIX_BGR);
+
+// The checks of a melf_frames descriptor (melf_process_frames*); n == 0 passes
+static int check_frames(const void* frames, const melf_frames* f)
+{
+    if (!f) return fail(MELF_ERR_INVALID, "frame descriptor is NULL");
+    if (f->pixel_format < MELF_PIX_BGR || f->pixel_format > MELF_PIX_RGBA) return fail(MELF_ERR_INVALID, "unknown pixel_format");
+    if (f->n < 0 || f->H <= 0 || f->W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
+    const int64_t bpp = pix_bytes(f->pixel_format);
+    if (f->row_pitch < (int64_t)f->W * bpp) return fail(MELF_ERR_INVALID, "row_pitch smaller than a row");
+    if (f->row_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "row_pitch too large");
+    if (f->frame_stride < (int64_t)(f->H - 1) * f->row_pitch + (int64_t)f->W * bpp)
+        return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
+    if (f->n == 0) return MELF_SUCCESS;
+    if (!frames) return fail(MELF_ERR_INVALID, "frames pointer is NULL");
+    if (bpp == 4 && (((uintptr_t)frames | (uint64_t)f->row_pitch | (uint64_t)f->frame_stride) & 3))
+        return fail(MELF_ERR_INVALID, "4-byte pixel formats need a 4-byte aligned base, row_pitch and frame_stride");
+    return MELF_SUCCESS;
+}
+
+static int batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride, int row_stride, int pix,
+                     void* d_results, melf_result* out_host, void* stream_);
 
 extern "C" int melf_process_batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
                                       void* d_results, melf_result* out_host, void* stream_)
@@ -1130,6 +1153,23 @@ extern "C" int melf_process_batch_dev(melf_ctx* c, const void* d_frames, int n, 
     if (n == 0) return MELF_SUCCESS;
     if (!d_frames) return fail(MELF_ERR_INVALID, "d_frames is NULL");
     if (frame_stride < (size_t)H * W * 3) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
+    return batch_dev(c, d_frames, n, H, W, frame_stride, W * 3, MELF_PIX_BGR, d_results, out_host, stream_);
+}
+
+extern "C" int melf_process_frames_dev(melf_ctx* c, const void* d_frames, const melf_frames* f, void* d_results, melf_result* out_host,
+                                       void* stream_)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    if (int rc = check_frames(d_frames, f)) return rc;
+    if (f->n == 0) return MELF_SUCCESS;
+    return batch_dev(c, d_frames, f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch, f->pixel_format, d_results, out_host,
+                     stream_);
+}
+
+// melf_process_batch_dev / melf_process_frames_dev after their argument checks: the lane logic
+static int batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride, int row_stride, int pix,
+                     void* d_results, melf_result* out_host, void* stream_)
+{
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream_;  // NULL = the null (legacy default) stream, as everywhere in HIP
     if (c->frames_resident && c->lanes == 1 && n <= MAX_FRAMES_PER_LAUNCH) {
@@ -1142,7 +1182,7 @@ extern "C" int melf_process_batch_dev(melf_ctx* c, const void* d_frames, int n, 
         c->active_lane = lane;
         c->order_stream = st;
         c->order_valid = true;
-        const int rc = process_batch_on(c, d_frames, n, H, W, frame_stride, d_results, nullptr, ls);
+        const int rc = process_batch_on(c, d_frames, n, H, W, frame_stride, d_results, nullptr, ls, nullptr, row_stride, pix);
         c->order_valid = false;
         if (rc) return rc;
         HIP_TRY(hipEventRecord(c->ev_join[lane], ls));
@@ -1159,13 +1199,17 @@ extern "C" int melf_process_batch_dev(melf_ctx* c, const void* d_frames, int n, 
     } else if (int rc = acquire_lane(c, st, &c->active_lane)) {
         return rc;
     }
-    return process_batch_on(c, d_frames, n, H, W, frame_stride, d_results, out_host, st);
+    return process_batch_on(c, d_frames, n, H, W, frame_stride, d_results, out_host, st, nullptr, row_stride, pix);
 }
 
 static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
-                            void* d_results, melf_result* out_host, hipStream_t st, const int* rect, int row_stride)
+                            void* d_results, melf_result* out_host, hipStream_t st, const int* rect, int row_stride, int pix)
 {
-    if (row_stride <= 0) row_stride = W * 3;  // packed rows unless the caller's rows are padded (host-fed crops)
+    const int bpp = pix_bytes(pix);
+    if (row_stride <= 0) row_stride = W * bpp;  // packed rows unless the caller's rows are padded (host-fed crops, pitched frames)
+    // what the kernels may read of the last frame: its rows as far as they reach (the last row of a pitched buffer needs no
+    // padding); the host-fed crops keep their staging pitch and spare bytes behind every crop
+    const size_t last_frame = rect ? (size_t)H * row_stride : (size_t)(H - 1) * row_stride + (size_t)W * bpp;
     const melf_params& P = c->P;
     // numpy slicing img[y0:y1, x0:x1] clamps to the image (meterelf/_image.py:54-55)
     const int rx0 = rect ? rect[0] : P.rect_x0, ry0 = rect ? rect[1] : P.rect_y0;
@@ -1203,14 +1247,14 @@ static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int
             MatchSrc ms;
             ms.base = base; ms.frame_stride = frame_stride; ms.row_stride = row_stride;
             ms.x0 = x0; ms.y0 = y0; ms.rows = crows; ms.cols = ccols;
-            ms.readable = (size_t)(m - 1) * frame_stride + (size_t)H * row_stride;
+            ms.readable = (size_t)(m - 1) * frame_stride + last_frame;
             int nparts = 0;
             MatchPartial* parts = nullptr;
-            if (int rc = run_match(c, ms, true, m, bl, ls, nullptr, &parts, &nparts)) return rc;
+            if (int rc = run_match(c, ms, pix, m, bl, ls, nullptr, &parts, &nparts)) return rc;
             DialsSrc ds;
             ds.base = base; ds.frame_stride = frame_stride; ds.row_stride = row_stride;
             ds.x0 = x0; ds.y0 = y0; ds.crop_rows = crows; ds.crop_cols = ccols;
-            ds.readable = (size_t)(m - 1) * frame_stride + (size_t)H * row_stride;
+            ds.readable = (size_t)(m - 1) * frame_stride + last_frame;
             if (c->order_valid) {
                 // resident mode: prep and match above ran unordered with the caller's stream (they touch only the frames
                 // and the lane's buffers); the kernel that writes the caller's records waits for everything that stream
@@ -1221,7 +1265,7 @@ static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int
             }
             {
                 KernelTimer t(c, MELF_K_DIALS, ls);
-                launch_dials(ds, false, m, P, c->d_geom, c->d_rowmasks, parts, nparts, rw, res_dev + g0, ls, c->ws_max);
+                launch_dials(ds, pix, m, P, c->d_geom, c->d_rowmasks, parts, nparts, rw, res_dev + g0, ls, c->ws_max);
             }
             HIP_TRY(hipGetLastError());
         }
@@ -1283,6 +1327,11 @@ extern "C" int melf_process_stream_dev(melf_ctx* c, const void* d_frames, int nb
 // frames are packed (on the host pool's threads) into one of two pinned staging buffers, copied by DMA on a copy
 // stream and processed on the context's stream, so that packing chunk k+1, the copy of chunk k and the kernels of
 // chunk k-1 overlap.  The kernels see the crops as frames of crop size with the rect at the origin.
+// The pixel layouts of melf_process_frames go the same way: the crop rows are packed as they are (ccols * bytes per pixel, read at
+// the caller's row pitch), the kernels read the layout.
+static int batch_host(melf_ctx* c, const uint8_t* frames_host, int n, int H, int W, size_t frame_stride, size_t row_pitch, int pix,
+                      melf_result* out_host);
+
 extern "C" int melf_process_batch(melf_ctx* c, const uint8_t* frames_host, int n, int H, int W, size_t frame_stride,
                                   melf_result* out_host)
 {
@@ -1290,6 +1339,23 @@ extern "C" int melf_process_batch(melf_ctx* c, const uint8_t* frames_host, int n
     if (n == 0) return MELF_SUCCESS;
     if (!frames_host || !out_host || n < 0 || H <= 0 || W <= 0) return fail(MELF_ERR_INVALID, "bad argument");
     if (frame_stride < (size_t)H * W * 3) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
+    return batch_host(c, frames_host, n, H, W, frame_stride, (size_t)W * 3, MELF_PIX_BGR, out_host);
+}
+
+extern "C" int melf_process_frames(melf_ctx* c, const void* frames_host, const melf_frames* f, melf_result* out_host)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    if (int rc = check_frames(frames_host, f)) return rc;
+    if (f->n == 0) return MELF_SUCCESS;
+    if (!out_host) return fail(MELF_ERR_INVALID, "out_host is NULL");
+    return batch_host(c, (const uint8_t*)frames_host, f->n, f->H, f->W, (size_t)f->frame_stride, (size_t)f->row_pitch, f->pixel_format,
+                      out_host);
+}
+
+static int batch_host(melf_ctx* c, const uint8_t* frames_host, int n, int H, int W, size_t frame_stride, size_t row_pitch, int pix,
+                      melf_result* out_host)
+{
+    const int bpp = pix_bytes(pix);
     HIP_TRY(hipSetDevice(c->device));
     pool_use_device(c->device);
     const melf_params& P = c->P;
@@ -1298,7 +1364,7 @@ extern "C" int melf_process_batch(melf_ctx* c, const uint8_t* frames_host, int n
     const int crows = y1 - y0, ccols = x1 - x0;
     if (x0 < 0 || y0 < 0 || crows < P.th || ccols < P.tw)
         return fail(MELF_ERR_INVALID, "meter_rect crop is smaller than the dials template (cv2.matchTemplate would assert)");
-    const size_t row_bytes = (size_t)ccols * 3;
+    const size_t row_bytes = (size_t)ccols * bpp;
     // crop rows at a 64-byte pitch, so that the host side can pack them with streaming (non-temporal) 16-byte stores:
     // a plain memcpy into the staging buffer reads every destination line before writing it, a third of the pack's
     // memory traffic; + 128 spare bytes per crop (the prep kernel's aligned 100-byte windows reach past the last pixel)
@@ -1329,7 +1395,7 @@ extern "C" int melf_process_batch(melf_ctx* c, const uint8_t* frames_host, int n
     double pack_ms = 0;
     const auto t_begin = std::chrono::steady_clock::now();
     const int rect[4] = {0, 0, ccols, crows};
-    const uint8_t* frames_end = frames_host + (size_t)(n - 1) * frame_stride + (size_t)H * W * 3;
+    const uint8_t* frames_end = frames_host + (size_t)(n - 1) * frame_stride + (size_t)(H - 1) * row_pitch + (size_t)W * bpp;
     int k = 0;
     for (int f0 = 0; f0 < n; f0 += chunk, ++k) {
         const int m = n - f0 < chunk ? n - f0 : chunk;
@@ -1341,9 +1407,9 @@ extern "C" int melf_process_batch(melf_ctx* c, const uint8_t* frames_host, int n
         const int rblocks = (crows + 31) / 32;
         host_pool().run(m * rblocks, [&](int item) {
             const int i = item / rblocks, r0 = (item - i * rblocks) * 32, r1 = r0 + 32 < crows ? r0 + 32 : crows;
-            const uint8_t* src = frames_host + (size_t)(f0 + i) * frame_stride + ((size_t)(y0 + r0) * W + x0) * 3;
+            const uint8_t* src = frames_host + (size_t)(f0 + i) * frame_stride + (size_t)(y0 + r0) * row_pitch + (size_t)x0 * bpp;
             uint8_t* dst = pin + (size_t)i * crop_stride + (size_t)r0 * pitch;
-            for (int y = r0; y < r1; ++y, src += (size_t)W * 3, dst += pitch) {
+            for (int y = r0; y < r1; ++y, src += row_pitch, dst += pitch) {
                 if (src + pitch <= frames_end) {  // whole 64-byte pitch from the source row (the tail bytes are never looked at)
                     for (size_t o = 0; o < pitch; o += 16)
                         _mm_stream_si128((__m128i*)(dst + o), _mm_loadu_si128((const __m128i*)(src + o)));
@@ -1358,7 +1424,7 @@ extern "C" int melf_process_batch(melf_ctx* c, const uint8_t* frames_host, int n
         HIP_TRY(hipMemcpyAsync(d_chunk, pin, (size_t)m * crop_stride, hipMemcpyHostToDevice, c->copy_stream));
         HIP_TRY(hipEventRecord(c->ev_h2d[b], c->copy_stream));
         HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_h2d[b], 0));
-        if (int rc = process_batch_on(c, d_chunk, m, crows, ccols, crop_stride, c->d_results + f0, nullptr, c->stream, rect, (int)pitch))
+        if (int rc = process_batch_on(c, d_chunk, m, crows, ccols, crop_stride, c->d_results + f0, nullptr, c->stream, rect, (int)pitch, pix))
             return rc;
     }
     HIP_TRY(hipMemcpyAsync(out_host, c->d_results, (size_t)n * sizeof(melf_result), hipMemcpyDeviceToHost, c->stream));
@@ -1484,7 +1550,7 @@ extern "C" int melf_match_ccoeff(melf_ctx* c, const uint8_t* images_host, int n,
     ms.readable = (size_t)n * rows * cols;
     int nparts = 0;
     MatchPartial* d_parts = nullptr;
-    if (int rc = run_match(c, ms, false, n, 0, c->stream, result_map ? (float*)c->d_stage_out : nullptr, &d_parts, &nparts)) return rc;
+    if (int rc = run_match(c, ms, PIX_PLANE, n, 0, c->stream, result_map ? (float*)c->d_stage_out : nullptr, &d_parts, &nparts)) return rc;
     HIP_TRY(hipGetLastError());
     std::vector<MatchPartial> parts((size_t)n * nparts);
     HIP_TRY(hipMemcpyAsync(parts.data(), d_parts, parts.size() * sizeof(MatchPartial), hipMemcpyDeviceToHost, c->stream));
@@ -1521,7 +1587,7 @@ extern "C" int melf_read_dials(melf_ctx* c, const uint8_t* dials_hls_host, int n
     ds.readable = (size_t)n * per;
     {
         KernelTimer t(c, MELF_K_DIALS, c->stream);
-        launch_dials(ds, true, n, P, c->d_geom, c->d_rowmasks, nullptr, 0, 1, c->d_results, c->stream, c->ws_max);
+        launch_dials(ds, PIX_PLANE, n, P, c->d_geom, c->d_rowmasks, nullptr, 0, 1, c->d_results, c->stream, c->ws_max);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_host, c->d_results, (size_t)n * sizeof(melf_result), hipMemcpyDeviceToHost, c->stream));
@@ -1697,7 +1763,7 @@ static thread_local std::function<void()>* tl_jpeg_enqueued = nullptr;
 // overlapped: another call's kernels may still be running (melf_jpeg_process_files_begin, two calls in flight): nothing
 // here waits for the context's stream; what protects a ring slot is its own pair of events, across calls as within one.
 static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
-                            void* d_results, melf_result* out_host, hipStream_t st, const int* rect, int row_stride);
+                            void* d_results, melf_result* out_host, hipStream_t st, const int* rect, int row_stride, int pix);
 // What a caller inside the library may already have of the files it hands to the decode path (the file-name entry points
 // do): the parsed headers + Huffman decode data (of file index[k] of that parse for the call's file k), and the pinned buffer
 // the files' bytes lie in.

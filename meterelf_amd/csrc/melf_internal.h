@@ -20,6 +20,11 @@ inline const char* diag_env(const char* name) { return getenv(name); }
 inline const char* diag_env(const char*) { return nullptr; }
 #endif
 
+// Pixel layout of the images the reading kernels take: MELF_PIX_* (include/meterelf_hip.h) for camera frames, PIX_PLANE for
+// the stage entry points' packed single-channel images (melf_match_ccoeff) and HLS dials crops (melf_read_dials).
+constexpr int PIX_PLANE = -1;
+inline int pix_bytes(int pix) { return pix == MELF_PIX_BGRA || pix == MELF_PIX_RGBA ? 4 : 3; }
+
 // ---- K2: template match -----------------------------------------------------
 // One partial (max, first-argmax) per workgroup tile of the correlation map.
 struct MatchPartial {
@@ -42,7 +47,7 @@ struct MatchGeom {
     double tmean;      // cv::mean(template) = sum * (1.0 / N)
 };
 
-// source description for K2: either packed single-channel u8 images or BGR frames
+// source description for K2: either packed single-channel u8 images or camera frames (BGR, RGB, BGRA, RGBA: the launch's pix)
 struct MatchSrc {
     const uint8_t* base;
     size_t frame_stride;  // bytes between consecutive images/frames
@@ -52,7 +57,7 @@ struct MatchSrc {
     size_t readable;      // bytes from `base` the caller guarantees readable: (images - 1) * frame_stride + the last image's rows
 };
 
-void launch_match(const MatchSrc& src, bool from_bgr, int n, const MatchGeom& g, const uint32_t* d_tplT,
+void launch_match(const MatchSrc& src, int pix, int n, const MatchGeom& g, const uint32_t* d_tplT,
                   float* d_result_map, MatchPartial* d_partials, int* nparts_out, hipStream_t stream);
 int match_parts(const MatchGeom& g, int rows, int cols);
 
@@ -67,7 +72,7 @@ bool mfma_match_ok(int th, int tw, int rows, int cols);
 MfmaPlan mfma_plan(int th, int tw, int rows, int cols, int nframes);
 size_t mfma_atab_bytes(int th);
 void mfma_build_atab(const uint8_t* templ, int th, int tw, int8_t* atab);
-void launch_mfma_prep(const MatchSrc& src, bool from_bgr, int n, const MfmaPlan& p, int th, int tw, int8_t* d_lg,
+void launch_mfma_prep(const MatchSrc& src, int pix, int n, const MfmaPlan& p, int th, int tw, int8_t* d_lg,
                       uint16_t* d_r, hipStream_t stream);
 // launch_mfma_match: d_ws = the row-window sums R in epilogue order (k_prep_lplane); the waves add them up
 void launch_mfma_match(int n, const MfmaPlan& p, int th, int tw, long tsum, double tmean, const int8_t* d_atab,
@@ -105,7 +110,7 @@ void launch_gen_match(int n, const GenPlan& p, int rows, int th, int tw, long ts
                       hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 // prep for either matrix-core kernel: Lg (fragment order) and the row-window sums R in the match waves' epilogue order
 // (pairs > 0: the tuned kernel's paired-operand row layout, see k_prep_lplane)
-void launch_match_prep(const MatchSrc& src, bool from_bgr, int n, int groups, int rows_pad, int nkb, int rwp, int tw, int8_t* d_lg,
+void launch_match_prep(const MatchSrc& src, int pix, int n, int groups, int rows_pad, int nkb, int rwp, int tw, int8_t* d_lg,
                        uint16_t* d_r, hipStream_t stream, int pairs = 0);
 
 // ---- K3: per-dial reading ---------------------------------------------------
@@ -116,7 +121,7 @@ struct DialGeom {
 };
 
 struct DialsSrc {
-    const uint8_t* base;   // BGR frames or packed HLS dials crops
+    const uint8_t* base;   // camera frames (the launch's pix) or packed HLS dials crops
     size_t frame_stride;
     int row_stride;        // bytes
     int x0, y0;            // origin of the meter crop inside the frame (BGR mode)
@@ -124,7 +129,7 @@ struct DialsSrc {
     size_t readable;       // bytes from `base` the caller guarantees readable: (frames - 1) * frame_stride + the last frame's rows
 };
 
-void launch_dials(const DialsSrc& src, bool from_hls, int n, const melf_params& P, const DialGeom* d_geom,
+void launch_dials(const DialsSrc& src, int pix, int n, const melf_params& P, const DialGeom* d_geom,
                   const uint64_t* d_rowmasks /* [ndials][3][64] */, const MatchPartial* d_partials,
                   int nparts, int rw, melf_result* d_results, hipStream_t stream, int ws_max /* largest DialGeom::ws */);
 

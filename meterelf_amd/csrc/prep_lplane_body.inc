@@ -1,0 +1,161 @@
+// The body of k_prep_lplane and k_lplane_px4 (k_match_mfma.hip), included by both kernels: everything but the pixel loads is
+// shared, and each kernel compiles to what one kernel body gives (a force-inlined function shared by them changed the register
+// allocation of the existing instantiations).  In scope: the kernel's arguments and
+//   PX  1 = packed single-channel u8 images, 3 = 3-byte pixels (BGR / RGB: L = (max + min) / 2 does not depend on the channel
+//       order), 4 = 4-byte pixels (BGRA / RGBA, base, rows and frames 4-byte aligned, the 4th byte ignored): 32 pixels are 128
+//       bytes, eight aligned 16-byte loads, no gather.
+    constexpr int PB = PX == 4 ? 4 : 3;         // bytes per pixel of the frame reads
+    constexpr int WIN = PX == 4 ? 128 : 100;    // bytes a lane's 32-pixel load window spans
+    __shared__ __attribute__((aligned(16))) uint32_t tile[8 * 2 * 32 * 4];  // [kb][h][n][16 B], one chunk of 8 blocks
+    extern __shared__ int16_t pre_dyn[];                                    // [32][nkb * 32 + 8]: inclusive prefix of L' per frame (mod 2^16)
+    const int pstride = nkb * 32 + 8;
+    const int y = blockIdx.x, grp = blockIdx.y;
+    const int t = threadIdx.x, n = t >> 3, kl = t & 7;
+    const int f = grp * 32 + n;
+    int carry = 0;  // prefix of the blocks before this chunk (per frame, same in its 8 lanes)
+    // (wave-uniform, once) every 100-byte gather window of this row, in every frame of the group, ends inside the caller's buffer -- all
+    // rows but the last few of the last frame; the per-lane pointer test below then never runs (as the branch condition of every
+    // thread it cost 10 % of the kernel: profiles/r06/prep_bisect.txt)
+    const bool rows_safe = (size_t)min(grp * 32 + 31, nframes - 1) * src.frame_stride + (size_t)(src.y0 + y) * src.row_stride +
+                           (size_t)(src.x0 + 32 * (nkb - 1)) * PB + WIN <= src.readable;
+    u32x4m* out = (u32x4m*)(Lg + ((size_t)grp * rows_pad + y) * (size_t)nkb * 1024);
+    for (int kc = 0; kc < nkb; kc += 8) {
+        const int kb = kc + kl;
+        uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // 32 output bytes (L' = 0 <=> pad)
+        const bool live = kb < nkb && f < nframes && y < src.rows && kb * 32 < src.cols;  // uniform per wave except ragged tails
+        if (live) {
+            const uint8_t* prow = src.base + (size_t)f * src.frame_stride + (size_t)(src.y0 + y) * src.row_stride;
+            const int xbeg = kb * 32;
+            const int npx = min(32, src.cols - xbeg);  // < 32 only in the last block: masked below, not branched on
+            if (PX == 3) {
+                const size_t o = (size_t)(src.x0 + xbeg) * 3;
+                const uint8_t* p = prow + o;
+                const int mis = (int)((size_t)p & 3);
+                // 25 aligned dwords cover the 96 bytes of 32 pixels at any byte alignment; the window may
+                // reach past the crop (never used: masked) but must stay inside the caller's buffer
+                if (rows_safe || (size_t)f * src.frame_stride + (size_t)(src.y0 + y) * src.row_stride + o + 100 <= src.readable) {
+                    const uint32_t* q = (const uint32_t*)(p - mis);
+                    uint32_t d[25];
+#pragma unroll
+                    for (int i = 0; i < 25; ++i) d[i] = q[i];
+                    uint32_t a[24];
+#pragma unroll
+                    for (int i = 0; i < 24; ++i) a[i] = __builtin_amdgcn_alignbit(d[i + 1], d[i], (uint32_t)mis * 8u);
+#pragma unroll
+                    for (int k = 0; k < 32; ++k) {
+                        const int j = (3 * k) >> 2, sh = ((3 * k) & 3) * 8;
+                        const uint32_t px = sh <= 8 ? (a[j] >> sh) : __builtin_amdgcn_alignbit(a[j + 1 < 24 ? j + 1 : 23], a[j], sh);
+                        const int L = hls_lightness_fast(px & 255, (px >> 8) & 255, (px >> 16) & 255);
+                        w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
+                    }
+                    // (The last block's columns beyond the image keep whatever the gather found there -- pixels of the same frame.  No map
+                    // position inside the map reaches them: x + j <= cols - 1 for x < rw, and the window sums stop at column cols - 1 too;
+                    // the positions that do are thrown away by the match kernels.  Masking them cost 40 issue slots per wave and row.)
+                } else {  // last bytes of the frame buffer: byte loads
+                    for (int k = 0; k < npx; ++k) {
+                        const int L = hls_lightness(p[3 * k], p[3 * k + 1], p[3 * k + 2]);
+                        w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
+                    }
+                }
+            } else if (PX == 4) {
+                const size_t o = (size_t)(src.x0 + xbeg) * 4;
+                const uint8_t* p = prow + o;
+                // (as above: the last block's window may reach past the crop, never past the caller's buffer)
+                if (rows_safe || (size_t)f * src.frame_stride + (size_t)(src.y0 + y) * src.row_stride + o + 128 <= src.readable) {
+                    const u32x4a4* q = (const u32x4a4*)p;
+                    u32x4a4 d[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) d[i] = q[i];
+#pragma unroll
+                    for (int k = 0; k < 32; ++k) {
+                        const uint32_t px = d[k >> 2][k & 3];
+                        const int L = hls_lightness_fast(px & 255, (px >> 8) & 255, (px >> 16) & 255);
+                        w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
+                    }
+                } else {  // last bytes of the frame buffer: one dword per pixel
+                    for (int k = 0; k < npx; ++k) {
+                        const uint32_t px = ((const uint32_t*)p)[k];
+                        const int L = hls_lightness(px & 255, (px >> 8) & 255, (px >> 16) & 255);
+                        w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
+                    }
+                }
+            } else {
+                const uint8_t* p = prow + src.x0 + xbeg;
+                for (int k = 0; k < npx; ++k) w[k >> 2] |= (uint32_t)(((int)p[k] - 128) & 255) << ((k & 3) * 8);
+            }
+        }
+        if (kc) __syncthreads();  // the previous chunk's tile has been written out
+        // fragment-order image of the row (plain: the paired operands are put together when the row leaves, below)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            u32x4m v = {w[4 * h], w[4 * h + 1], w[4 * h + 2], w[4 * h + 3]};
+            *(u32x4m*)(tile + ((kl * 2 + h) * 32 + n) * 4) = v;
+        }
+        // inclusive prefix sums of L' along the row: the block's total (four signed bytes per v_dot4), a scan of the totals over the
+        // frame's 8 lanes, then the 32 running sums are produced and stored pair by pair (nothing but the running sum stays live)
+        int run = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) run = __builtin_amdgcn_sdot4((int)w[j], 0x01010101, run, false);
+        int off = run;  // inclusive scan of block totals over lanes with equal t >> 3
+#pragma unroll
+        for (int dlt = 1; dlt < 8; dlt <<= 1) {
+            const int o2 = __shfl_up(off, dlt, 8);
+            if (kl >= dlt) off += o2;
+        }
+        const int chunk_total = __shfl(off, 7, 8);
+        off += carry - run;  // exclusive, including the earlier chunks
+        carry += chunk_total;
+        if (kb < nkb) {
+            int acc = off;
+#pragma unroll
+            for (int k = 0; k < 32; k += 2) {
+                acc += (int)(int8_t)((w[k >> 2] >> ((k & 3) * 8)) & 255u);
+                const uint32_t lo16 = (uint32_t)acc & 0xffffu;
+                acc += (int)(int8_t)((w[k >> 2] >> (((k + 1) & 3) * 8)) & 255u);
+                *(uint32_t*)&pre_dyn[n * pstride + kb * 32 + k] = lo16 | ((uint32_t)acc << 16);
+            }
+        }
+        __syncthreads();
+        const int nb = min(8, nkb - kc);
+        if (pairs == 0) {
+            for (int i = t; i < nb * 64; i += 256) out[kc * 64 + i] = *(const u32x4m*)(tile + i * 4);
+        } else {
+            // (nkb <= 8: one chunk)  output piece i = 1 KiB slot i >> 6, lane i & 63.  Slots 2 p, 2 p + 1: dwords 0-3 / 4-7 of P_p -- two
+            // dwords of block p's fragment and two of block p + 6's, interleaved by 16-bit pairs; slots 2 pairs ..: blocks pairs .. 5
+            for (int i = t; i < nb * 64; i += 256) {
+                const int slot = i >> 6, li = i & 63;
+                u32x4m v;
+                if (slot < 2 * pairs) {   // (uniform per wave)
+                    const int p = slot >> 1, hl = slot & 1;
+                    const uint2 lo2 = *(const uint2*)(tile + (p * 64 + li) * 4 + 2 * hl), hi2 = *(const uint2*)(tile + ((p + 6) * 64 + li) * 4 + 2 * hl);
+                    v.x = __builtin_amdgcn_perm(hi2.x, lo2.x, 0x05040100u); v.y = __builtin_amdgcn_perm(hi2.x, lo2.x, 0x07060302u);
+                    v.z = __builtin_amdgcn_perm(hi2.y, lo2.y, 0x05040100u); v.w = __builtin_amdgcn_perm(hi2.y, lo2.y, 0x07060302u);
+                } else {
+                    v = *(const u32x4m*)(tile + ((slot - pairs) * 64 + li) * 4);
+                }
+                out[i] = v;
+            }
+        }
+    }
+    // window sums: R[x] = P[x + tw - 1] - P[x - 1] + 128 tw   (P = inclusive prefix of L - 128, modulo 2^16:
+    // the window sum itself is below 2^16 for tw <= 257)
+    if (y < src.rows) {
+        uint16_t* ro = R + (((size_t)grp * src.rows + y) * rwp) * 32;
+        const int bias = tw * 128;
+        const int pmax = nkb * 32 - 1;
+        const int ln = t & 63, nn = ln & 31, hh = ln >> 5;
+        for (int kk = t >> 6; kk < rwp / 16; kk += 4) {   // 1 KiB pieces, four per pass of the workgroup
+            const int xb = kk >> 1, e0 = 8 * (kk & 1);
+            uint32_t o[4];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int e = e0 + q;
+                const int x = 32 * xb + (e & 3) + 8 * (e >> 2) + 4 * hh;
+                const int hi = (int)pre_dyn[nn * pstride + min(x + tw - 1, pmax)], lo = x > 0 ? (int)pre_dyn[nn * pstride + min(x - 1, pmax)] : 0;
+                const uint32_t v = (uint32_t)(hi - lo + bias) & 0xffffu;
+                if (q & 1) o[q >> 1] |= v << 16; else o[q >> 1] = v;
+            }
+            u32x4m ov = {o[0], o[1], o[2], o[3]};
+            *(u32x4m*)(ro + ((size_t)kk * 64 + ln) * 8) = ov;
+        }
+    }

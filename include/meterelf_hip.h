@@ -156,7 +156,7 @@ int melf_process_batch_dev(melf_ctx* ctx, const void* d_frames, int n, int H, in
  * a 4-byte aligned base, row_pitch and frame_stride; the 3-byte formats take any alignment.  An unknown format, a pitch
  * or stride too small, a misaligned 4-byte layout or a NULL descriptor return MELF_ERR_INVALID before anything runs.
  * melf_process_stream_dev, the fused full-frame mask (melf_hls_inrange_close*), melf_aligned_average and the JPEG entry
- * points take packed BGR only. */
+ * points take packed BGR only; YUV 4:2:0 frames have their own descriptor and entry points (melf_process_yuv*, below). */
 enum { MELF_PIX_BGR = 0, MELF_PIX_RGB = 1, MELF_PIX_BGRA = 2, MELF_PIX_RGBA = 3 };
 typedef struct melf_frames {
     int32_t pixel_format;  /* MELF_PIX_*; the 4th byte of BGRA / RGBA is ignored                          */
@@ -171,6 +171,43 @@ int melf_process_frames(melf_ctx* ctx, const void* frames_host, const melf_frame
  * and NULL d_results / out_host semantics. */
 int melf_process_frames_dev(melf_ctx* ctx, const void* d_frames, const melf_frames* f, void* d_results,
                             melf_result* out_host, void* stream);
+
+/* ---- the same path for YUV 4:2:0 video frames: NV12 (hardware decoders, capture stacks), I420 / YV12 (software decoders) ----
+ * The records are byte-identical to melf_process_batch(_dev) on the packed BGR frame that the conversion below makes of each
+ * frame (the constants of cv2.cvtColor(COLOR_YUV2BGR_NV12 / _I420): BT.601, limited range), without a conversion pass: the
+ * kernels read the planes in place, and only the meter_rect crop of them.  In integers, >> arithmetic:
+ *     chroma: the nearest sample, no interpolation: pixel (x, y) uses U[y >> 1][x >> 1], V[y >> 1][x >> 1]
+ *     yy = max(Y - 16, 0) * 1220542          u = U - 128          v = V - 128
+ *     R = clamp((yy + (1 << 19) + 1673527 * v)              >> 20, 0, 255)
+ *     G = clamp((yy + (1 << 19) -  852492 * v - 409993 * u) >> 20, 0, 255)
+ *     B = clamp((yy + (1 << 19) + 2116026 * u)              >> 20, 0, 255)
+ * Frame f starts at frames + f * frame_stride; its Y row y at + y * y_pitch (W bytes), its chroma row y >> 1 at
+ * + u_offset / v_offset + (y >> 1) * c_pitch: NV12 W bytes U V U V .. (v_offset == u_offset + 1), I420 W / 2 bytes per plane.
+ * YV12 is I420 with the two offsets exchanged.  The buffer must hold every plane of every frame up to the last sample of its
+ * last row, and nothing behind that: no load of the kernels reaches past it.  Odd H or W, a pitch or stride too small, a chroma
+ * plane that overlaps the Y plane, an unknown format or matrix or a NULL descriptor return MELF_ERR_INVALID before anything is
+ * launched or copied. */
+enum { MELF_YUV_NV12 = 0, MELF_YUV_I420 = 1 };
+enum { MELF_YUV_BT601_LIMITED = 0 };            /* the only matrix; anything else: MELF_ERR_INVALID */
+typedef struct melf_yuv_frames {
+    int32_t format, matrix;
+    int32_t n, H, W;                            /* H and W even                                           */
+    int32_t reserved;
+    int64_t y_pitch;                            /* bytes between Y rows, >= W                             */
+    int64_t c_pitch;                            /* bytes between chroma rows: >= W (NV12), >= W / 2 (I420) */
+    int64_t u_offset, v_offset;                 /* from a frame's first byte to its U / V samples;
+                                                   NV12: v_offset == u_offset + 1, u_offset even          */
+    int64_t frame_stride;                       /* bytes between frames                                   */
+} melf_yuv_frames;
+/* Host frames, as melf_process_batch: only the Y rows of the crop and the chroma rows under it cross PCIe (packed into the
+ * pinned staging buffers as small frames of the same format); no byte is converted on the CPU. */
+int melf_process_yuv(melf_ctx* ctx, const void* frames_host, const melf_yuv_frames* f, melf_result* out_host);
+/* Frames in HBM, exactly as melf_process_frames_dev: the same lanes, melf_ctx_set_frames_resident, caller streams, and NULL
+ * d_results / out_host semantics. */
+int melf_process_yuv_dev(melf_ctx* ctx, const void* d_frames, const melf_yuv_frames* f, void* d_results, melf_result* out_host,
+                         void* stream);
+/* Stage entry point (parity tests, and a debug view for callers): the conversion alone, n packed H x W x 3 BGR frames out. */
+int melf_yuv_to_bgr(melf_ctx* ctx, const void* frames_host, const melf_yuv_frames* f, uint8_t* bgr_out_host);
 
 /* ---- stage entry points (parity tests and roofline runs) ----------------- */
 

@@ -71,6 +71,19 @@ PIX_BGR, PIX_RGB, PIX_BGRA, PIX_RGBA = 0, 1, 2, 3
 PIX_CODES = {'bgr': PIX_BGR, 'rgb': PIX_RGB, 'bgra': PIX_BGRA, 'rgba': PIX_RGBA, 'bgrx': PIX_BGRA, 'rgbx': PIX_RGBA}
 PIX_BYTES = {PIX_BGR: 3, PIX_RGB: 3, PIX_BGRA: 4, PIX_RGBA: 4}
 
+
+
+class MelfYuvFrames(C.Structure):
+    _fields_ = [('format', C.c_int32), ('matrix', C.c_int32), ('n', C.c_int32), ('H', C.c_int32), ('W', C.c_int32),
+                ('reserved', C.c_int32), ('y_pitch', C.c_int64), ('c_pitch', C.c_int64), ('u_offset', C.c_int64),
+                ('v_offset', C.c_int64), ('frame_stride', C.c_int64)]
+
+
+# YUV 4:2:0 layouts of melf_process_yuv* (MELF_YUV_*); 'yv12' is I420 with the two chroma planes exchanged
+YUV_NV12, YUV_I420 = 0, 1
+YUV_BT601_LIMITED = 0
+YUV_CODES = {'nv12': YUV_NV12, 'i420': YUV_I420, 'yv12': YUV_I420}
+
 MATCH_KERNEL_NAMES = ('dot4', 'mfma', 'gen')
 
 RESULT_DTYPE = np.dtype([('status', '<i4'), ('match_x', '<i4'), ('match_y', '<i4'), ('failed_dial', '<i4'),
@@ -90,7 +103,7 @@ EXPORTS = [
     'melf_last_error', 'melf_abi_version', 'melf_device_count', 'melf_build_dial_masks',
     'melf_blob_size', 'melf_blob_pack', 'melf_blob_params', 'melf_ctx_create', 'melf_ctx_create_bcast', 'melf_ctx_destroy',
     'melf_ctx_params', 'melf_ctx_sync', 'melf_ctx_get_masks', 'melf_process_batch', 'melf_process_batch_dev', 'melf_process_stream_dev',
-    'melf_process_frames', 'melf_process_frames_dev',
+    'melf_process_frames', 'melf_process_frames_dev', 'melf_process_yuv', 'melf_process_yuv_dev', 'melf_yuv_to_bgr',
     'melf_bgr2hls', 'melf_hls_inrange_close', 'melf_hls_inrange_close_dev', 'melf_match_ccoeff',
     'melf_read_dials', 'melf_aligned_average', 'melf_inrange', 'melf_ctx_fused_table_ties', 'melf_ctx_set_frames_resident', 'melf_ctx_last_match', 'melf_match_layout_query', 'melf_match_gen_plan_query', 'melf_ctx_set_profiling', 'melf_ctx_timings', 'melf_kernel_name',
     'melf_jpeg_probe', 'melf_jpeg_probe_batch', 'melf_jpeg_decode_batch', 'melf_jpeg_clean_segment', 'melf_jpeg_process_batch',
@@ -131,6 +144,9 @@ def lib():
     L.melf_process_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, vp]
     L.melf_process_frames.argtypes = [vp, vp, C.POINTER(MelfFrames), vp]
     L.melf_process_frames_dev.argtypes = [vp, vp, C.POINTER(MelfFrames), vp, vp, vp]
+    L.melf_process_yuv.argtypes = [vp, vp, C.POINTER(MelfYuvFrames), vp]
+    L.melf_process_yuv_dev.argtypes = [vp, vp, C.POINTER(MelfYuvFrames), vp, vp, vp]
+    L.melf_yuv_to_bgr.argtypes = [vp, vp, C.POINTER(MelfYuvFrames), vp]
     L.melf_process_stream_dev.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, vp]
     L.melf_bgr2hls.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp]
     L.melf_hls_inrange_close.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
@@ -283,6 +299,87 @@ def frames_view(frames, pixel_format='bgr'):
         ptr = frames.data_ptr() if is_torch else frames.ctypes.data
         extent = n * fs
     return FramesView(int(ptr), on_device, device, code, n, H, W, int(rp), int(fs), int(extent), not ok, frames)
+
+
+class YuvFramesView(NamedTuple):
+    """How the kernels read a batch of YUV 4:2:0 frames in place (yuv_frames_view)."""
+    ptr: int            # address of frame 0's first Y sample
+    on_device: bool     # True: a torch tensor on a GPU (ptr is a device address)
+    device: Optional[int]
+    format: int         # YUV_NV12 / YUV_I420
+    n: int
+    H: int
+    W: int
+    y_pitch: int        # bytes between Y rows
+    c_pitch: int        # bytes between chroma rows
+    u_offset: int       # bytes from a frame's first byte to its U / V samples
+    v_offset: int
+    frame_stride: int   # bytes between frames
+    extent: int         # bytes read from ptr: every plane of every frame up to the last sample of its last row
+    copied: bool        # the layout could not be described and the frames were copied once to a packed array
+    array: object       # what ptr points into (the caller's array, or the copy): keep it alive while the call runs
+
+    def descriptor(self):
+        return MelfYuvFrames(self.format, YUV_BT601_LIMITED, self.n, self.H, self.W, 0, self.y_pitch, self.c_pitch, self.u_offset,
+                             self.v_offset, self.frame_stride)
+
+
+def yuv_frames_view(frames, pixel_format='nv12'):
+    """Describes the conventional (N, H * 3 // 2, W) uint8 array of YUV 4:2:0 frames (numpy array or torch tensor) as
+    melf_process_yuv* read it: rows 0 .. H - 1 are Y; 'nv12': rows H .. H * 3 // 2 - 1 are the interleaved U V rows; 'i420': the
+    H * W // 4 bytes behind the Y rows are the U plane (rows of W // 2), the next H * W // 4 the V plane; 'yv12': V first.
+    'nv12' honours the row stride and the frame stride in place (frames[:, :, :w], frames[::2], frames[a:b]); the planar formats
+    are read in place when the rows are contiguous (row stride == W: their chroma rows are half rows of the array), otherwise the
+    frames are copied once to a packed array (YuvFramesView.copied), as is any layout with an element stride other than 1 or
+    negative strides.  Not uint8, not three-dimensional, an odd H or W, or an unknown format: ValueError."""
+    is_torch = _is_torch(frames)
+    if is_torch:
+        if str(frames.dtype) != 'torch.uint8':
+            raise ValueError('frames must be uint8, not %s' % frames.dtype)
+        shape = tuple(frames.shape)
+        strides = tuple(frames.stride())          # elements = bytes for uint8
+        ptr = frames.data_ptr()
+        on_device = frames.device.type == 'cuda'
+        device = frames.device.index if on_device else None
+    else:
+        frames = np.asarray(frames)
+        if frames.dtype != np.uint8:
+            raise ValueError('frames must be uint8, not %s' % frames.dtype)
+        shape = frames.shape
+        strides = frames.strides
+        ptr = frames.ctypes.data
+        (on_device, device) = (False, None)
+    fmt = str(pixel_format).lower()
+    if fmt not in YUV_CODES:
+        raise ValueError('pixel_format %r is not a YUV 4:2:0 layout (nv12, i420, yv12)' % (pixel_format,))
+    if len(shape) != 3 or shape[1] % 3 != 0 or (shape[1] // 3 * 2) % 2 != 0 or shape[1] == 0 or shape[2] == 0 or shape[2] % 2 != 0:
+        raise ValueError('YUV 4:2:0 frames must be (N, H * 3 // 2, W) with even H and W, not %s' % (shape,))
+    code = YUV_CODES[fmt]
+    (n, rows, W) = shape
+    H = rows // 3 * 2
+    (fs, rp, es) = strides
+    if n == 1:
+        fs = rows * rp if rp > 0 else 0
+    planar = code == YUV_I420
+    ok = es == 1 and rp >= W and fs >= (rows - 1) * rp + W and rp <= 2 ** 31 - 1 and (not planar or rp == W)
+    if not ok:
+        if is_torch:
+            import torch
+            frames = frames.clone(memory_format=torch.contiguous_format)
+        else:
+            frames = np.array(frames, order='C', copy=True)
+        (rp, fs) = (W, rows * W)
+        ptr = frames.data_ptr() if is_torch else frames.ctypes.data
+    if planar:
+        (c_pitch, first, second) = (W // 2, H * W, H * W + (H // 2) * (W // 2))
+        (u_off, v_off) = (second, first) if fmt == 'yv12' else (first, second)
+        last = second + (H // 2) * (W // 2)
+    else:
+        (c_pitch, u_off, v_off) = (rp, H * rp, H * rp + 1)
+        last = (rows - 1) * rp + W
+    extent = (n - 1) * fs + last if n else 0
+    return YuvFramesView(int(ptr), on_device, device, code, n, H, W, int(rp), int(c_pitch), int(u_off), int(v_off), int(fs), int(extent),
+                         not ok, frames)
 
 
 def jpeg_probe(data):
@@ -502,6 +599,26 @@ class Context:
         check(self._L.melf_process_frames_dev(
             self._h, C.c_void_p(d_frames_ptr), C.byref(f), C.c_void_p(d_results_ptr) if d_results_ptr else None,
             _ptr(out) if want_host else None, C.c_void_p(stream) if stream else None))
+        return out
+
+    def process_yuv(self, frames_ptr, desc):
+        """Host YUV 4:2:0 frames (melf_process_yuv; desc: a MelfYuvFrames, e.g. yuv_frames_view(...).descriptor()) -> records."""
+        out = np.zeros(desc.n, RESULT_DTYPE)
+        check(self._L.melf_process_yuv(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
+        return out
+
+    def process_yuv_dev(self, d_frames_ptr, desc, d_results_ptr=None, want_host=True, stream=None):
+        """YUV 4:2:0 frames in HBM (melf_process_yuv_dev, as process_frames_dev).  Returns records when want_host."""
+        out = np.zeros(desc.n, RESULT_DTYPE) if want_host else None
+        check(self._L.melf_process_yuv_dev(
+            self._h, C.c_void_p(d_frames_ptr), C.byref(desc), C.c_void_p(d_results_ptr) if d_results_ptr else None,
+            _ptr(out) if want_host else None, C.c_void_p(stream) if stream else None))
+        return out
+
+    def yuv_to_bgr(self, frames_ptr, desc):
+        """The conversion alone (melf_yuv_to_bgr): host YUV 4:2:0 frames -> (n, H, W, 3) BGR."""
+        out = np.empty((desc.n, desc.H, desc.W, 3), np.uint8)
+        check(self._L.melf_yuv_to_bgr(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
         return out
 
     # --- stages ---

@@ -288,9 +288,27 @@ __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_v
 #include "k_dials_body.inc"
 }
 
+// NV12 / I420 frames (melf_process_yuv*): src describes the Y plane, yuv the chroma planes; PLANAR: separate U and V planes
+// (I420, YV12) instead of interleaved pairs (NV12).  Past its loads the body is the one of 4-byte B G R pixels.
+#define MELF_YUV_BODY
+template <bool PLANAR, int NR>
+__global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_vgpr(DIALS_VGPRS))) void k_yneedle(DialsSrc src, YuvPlanes yuv, melf_params P,
+                                                                const DialGeom* __restrict__ geom,
+                                                                const uint64_t* __restrict__ rowmasks,
+                                                                const MatchPartial* __restrict__ partials,
+                                                                int nparts, int rw, melf_result* __restrict__ results)
+{
+    constexpr bool FROM_HLS = false;
+    constexpr int PB = 4;
+    constexpr bool RT_ORDER = false;
+    const uint32_t bsel = 0u;
+#include "k_dials_body.inc"
+}
+#undef MELF_YUV_BODY
+
 void launch_dials(const DialsSrc& src, int pix, int n, const melf_params& P, const DialGeom* d_geom,
                   const uint64_t* d_rowmasks, const MatchPartial* d_partials, int nparts, int rw,
-                  melf_result* d_results, hipStream_t stream, int ws_max)
+                  melf_result* d_results, hipStream_t stream, int ws_max, const YuvPlanes* yuv)
 {
     dim3 grid(n), block(64 * P.ndials);
     const size_t shmem = (size_t)P.ndials * DIAL_LDS_BYTES;
@@ -318,11 +336,26 @@ void launch_dials(const DialsSrc& src, int pix, int n, const melf_params& P, con
         case 56: MELF_NEEDLES_LAUNCH(BPP, 56); break;        \
         default: MELF_NEEDLES_LAUNCH(BPP, 64); break;        \
     }
+#define MELF_YNEEDLE_LAUNCH(PL, NRV) \
+    hipLaunchKernelGGL((k_yneedle<PL, NRV>), grid, block, shmem, stream, src, *yuv, P, d_geom, d_rowmasks, d_partials, nparts, rw, d_results)
+#define MELF_YNEEDLE_NR(PL)                                  \
+    switch (nr) {                                            \
+        case 32: MELF_YNEEDLE_LAUNCH(PL, 32); break;         \
+        case 40: MELF_YNEEDLE_LAUNCH(PL, 40); break;         \
+        case 48: MELF_YNEEDLE_LAUNCH(PL, 48); break;         \
+        case 52: MELF_YNEEDLE_LAUNCH(PL, 52); break;         \
+        case 56: MELF_YNEEDLE_LAUNCH(PL, 56); break;         \
+        default: MELF_YNEEDLE_LAUNCH(PL, 64); break;         \
+    }
     const int swap_rb = pix == MELF_PIX_RGB || pix == MELF_PIX_RGBA;
-    if (pix == PIX_PLANE) { MELF_DIALS_NR(true) }
+    if (pix == PIX_NV12) { MELF_YNEEDLE_NR(false) }
+    else if (pix == PIX_I420) { MELF_YNEEDLE_NR(true) }
+    else if (pix == PIX_PLANE) { MELF_DIALS_NR(true) }
     else if (pix == MELF_PIX_BGR) { MELF_DIALS_NR(false) }
     else if (pix == MELF_PIX_RGB) { MELF_NEEDLES_NR(3) }
     else { MELF_NEEDLES_NR(4) }
+#undef MELF_YNEEDLE_NR
+#undef MELF_YNEEDLE_LAUNCH
 #undef MELF_NEEDLES_NR
 #undef MELF_NEEDLES_LAUNCH
 #undef MELF_DIALS_NR

@@ -8,6 +8,10 @@
 //             compile-time byte selectors.  Every pixel leaves its load through a byte permute into B G R order, so that hls_pixel
 //             and the prefilter see what they see for a BGR frame: the records are those of the BGR frame made from the caller's;
 //   NR        window rows whose pixels a lane requests up front (the largest dial window of the context, rounded up to 8).
+// With MELF_YUV_BODY defined by the including kernel (k_yneedle): NV12 (PLANAR false) / I420 (PLANAR true) frames, src the Y plane,
+// `yuv` the chroma planes.  Every load fetches Y and the chroma under it and leaves as a B G R dword (melf_device.h: yuv_bgr), which
+// is what the rest of the body sees with PB = 4: the core pixel and the exact path's column pixel by byte loads, the window's four
+// pixels per lane as one Y dword and the (at most three) chroma pairs under it, at any parity of the window's origin.
     [[maybe_unused]] const uint32_t csel = bsel ? 0x0c000102u : 0x0c020100u;   // pixel -> B G R in bytes 0..2 (RT_ORDER)
     auto bgr = [&](uint32_t px) -> uint32_t {
         if constexpr (RT_ORDER) return __builtin_amdgcn_perm(0u, px, csel);
@@ -87,11 +91,29 @@
     const int ylast = ws - 1;   // wave-uniform
     const bool tail = !FROM_HLS && hls_scalar_tail(mx + Xl, src.crop_cols);
     const size_t rstride = FROM_HLS ? (size_t)P.tw * 3 : (size_t)src.row_stride;
+#ifdef MELF_YUV_BODY
+    const int fx_m = src.x0 + mx, fy_m = src.y0 + my;   // the match position in the frame
+    const int cp_u = __builtin_amdgcn_readfirstlane(yuv.c_pitch);
+    const uint8_t* const uplane = frame + (size_t)yuv.u_off;
+    const uint8_t* const vplane = frame + (size_t)yuv.v_off;
+    // pixel (X, Y) of the dials crop as a B G R dword: three byte loads
+    auto yuv_px = [&](int X, int Y) -> uint32_t {
+        const int fx = fx_m + X, fy = fy_m + Y;
+        const size_t co = (size_t)(fy >> 1) * (size_t)cp_u + (size_t)(PLANAR ? fx >> 1 : fx & ~1);
+        const int yv = frame[(size_t)fy * rstride + (size_t)fx];
+        return yuv_bgr(yv, yuv_chroma(uplane[co], vplane[co]));
+    };
+#else
     const uint8_t* const origin = FROM_HLS ? frame : frame + (size_t)(src.y0 + my) * src.row_stride + (size_t)(src.x0 + mx) * PB;
+#endif
     const int coreX = G.core_x - 2 + lane % 5, coreY = G.core_y - 2 + (lane < 25 ? lane / 5 : 0);
     const bool corevalid = lane < 25 && coreX >= 0 && coreX < P.tw && coreY >= 0 && coreY < P.th;
+#ifdef MELF_YUV_BODY
+    const uint32_t corepx = yuv_px(min(max(coreX, 0), P.tw - 1), min(max(coreY, 0), P.th - 1));
+#else
     const uint32_t corepx = bgr(load_px<PB>(origin + (size_t)min(max(coreY, 0), P.th - 1) * rstride + (size_t)min(max(coreX, 0), P.tw - 1) * PB, src.base));
     const PxColumn pcol = px_column_of<PB>(origin + (size_t)Xc * PB, src.base);   // (the exact path's loads: one pixel per lane and row)
+#endif
     const int th1 = __builtin_amdgcn_readfirstlane(P.th - 1);
     const int rs_u = __builtin_amdgcn_readfirstlane((int)rstride);  // uniform: the row offsets below are scalar products
     // The window for the integer test, round 5: a lane fetches FOUR pixels of a row as one aligned 16-byte load (the 12 bytes and
@@ -107,10 +129,65 @@
     // the last load ends inside the frames' buffer; otherwise every pixel takes the exact path below
     const uint8_t* const buf_end = src.base + src.readable;   // (not frames x stride: the last frame of a padded-stride buffer may end earlier)
     // (4-byte pixels: a lane's four are one aligned 16-byte load, nothing beyond them)
+#ifdef MELF_YUV_BODY
+    // YUV: a lane's four pixels are one Y dword (inside its row: the pieces lie inside the crop) and the chroma pairs under them, one
+    // 8-byte (NV12) / two 4-byte (I420) loads that start at the first pair or, near the crop's right edge, as far left of it as keeps
+    // them inside the chroma row of the crop (xlim: the crop's right edge, rounded up to a whole pair); the shift is undone below.
+    // Any alignment (unaligned global loads); nothing is read outside the rows of the planes.
+    (void)buf_end;
+    const int xlim = (src.x0 + src.crop_cols + 1) & ~1;
+    const bool quads = wx0 >= 0 && wx0 + 4 * npiece <= P.tw && xlim >= 8;
+    const int fx0 = fx_m + wx0 + 4 * min(pc, npiece - 1);   // the lane's first pixel in the frame
+    const int cstart = PLANAR ? min(fx0 >> 1, (xlim >> 1) - 4) : min(fx0 & ~1, xlim - 8);   // first chroma byte loaded
+    const uint32_t cshift = (uint32_t)((PLANAR ? fx0 >> 1 : fx0 & ~1) - cstart) * 8u;       // bits to the lane's first pair
+    const bool fodd = fx0 & 1;
+    // the four pixels as B G R dwords from what was loaded: {Y dword, chroma, chroma, -}
+    auto yuv_quad = [&](const u32x4v r) -> u32x4v {
+        uint32_t cu, cv;   // U / V of the three pairs in bytes 0..2
+        if constexpr (PLANAR) {
+            cu = r.y >> cshift; cv = r.z >> cshift;
+        } else {
+            const uint64_t c = (((uint64_t)r.z << 32) | r.y) >> cshift;   // U0 V0 U1 V1 U2 V2
+            const uint32_t lo = (uint32_t)c, hi = (uint32_t)(c >> 32);
+            cu = __builtin_amdgcn_perm(hi, lo, 0x0c040200u); cv = __builtin_amdgcn_perm(hi, lo, 0x0c050301u);
+        }
+        const YuvChroma c0 = yuv_chroma(cu & 255, cv & 255), c1 = yuv_chroma((cu >> 8) & 255, (cv >> 8) & 255),
+                        c2 = yuv_chroma((cu >> 16) & 255, (cv >> 16) & 255);
+        // pixel j sits on pair (j + fodd) >> 1
+        u32x4v o;
+        o.x = yuv_bgr(r.x & 255, c0);
+        o.y = yuv_bgr((r.x >> 8) & 255, fodd ? c1 : c0);
+        o.z = yuv_bgr((r.x >> 16) & 255, c1);
+        o.w = yuv_bgr(r.x >> 24, fodd ? c2 : c1);
+        return o;
+    };
+#else
     const bool quads = !FROM_HLS && ((uintptr_t)src.base & 3) == 0 && wx0 >= 0 && wx0 + 4 * npiece <= P.tw &&
                        origin + (size_t)th1 * rstride + (size_t)(wx0 + 4 * npiece) * PB + (PB == 4 ? 0 : 4) <= buf_end;
+#endif
     u32x4v raw[NG];
     uint32_t mshift = 0;   // bytes between a load's aligned address and its first pixel (0..3), two bits per load
+#ifdef MELF_YUV_BODY
+    if (quads) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const int fy = fy_m + min(max(wy0 + min(4 * g + rg, ylast), 0), th1);
+            uint32_t yd;
+            __builtin_memcpy(&yd, frame + (size_t)fy * (size_t)rs_u + (size_t)fx0, 4);
+            const size_t co = (size_t)(fy >> 1) * (size_t)cp_u + (size_t)cstart;
+            if constexpr (PLANAR) {
+                uint32_t ud, vd;
+                __builtin_memcpy(&ud, uplane + co, 4);
+                __builtin_memcpy(&vd, vplane + co, 4);
+                raw[g] = u32x4v{yd, ud, vd, 0u};
+            } else {
+                uint32_t cd[2];
+                __builtin_memcpy(cd, uplane + co, 8);
+                raw[g] = u32x4v{yd, cd[0], cd[1], 0u};
+            }
+        }
+    }
+#else
     if (quads) {
         const uint8_t* const lane0 = origin + (size_t)(wx0 + 4 * min(pc, npiece - 1)) * PB;
 #pragma unroll
@@ -125,6 +202,7 @@
             }
         }
     }
+#endif
     __builtin_amdgcn_sched_barrier(0);
     FSTAMPD(9);    // every pixel requested
 #ifdef MELF_DIALS_STAMP
@@ -157,7 +235,11 @@
 #pragma unroll
             for (int k = 0; k < 16; ++k) {
                 const int Y = min(max(wy0 + min(yc + k, ylast), 0), th1);
+#ifdef MELF_YUV_BODY
+                pxe[k] = yuv_px(Xc, Y);
+#else
                 pxe[k] = bgr(load_px3_row(pcol, (size_t)((int64_t)Y * rs_u)));
+#endif
             }
 #pragma unroll
             for (int k = 0; k < 16; ++k) {
@@ -202,6 +284,9 @@
         if (quads) {
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
+#ifdef MELF_YUV_BODY
+                raw[g] = yuv_quad(raw[g]);   // from here on: one B G R pixel per dword, as for 4-byte pixels
+#endif
                 // the lane's 12 bytes: B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3  (4-byte pixels: raw[g] holds one pixel per dword)
                 uint32_t e0 = 0, e1 = 0, e2 = 0;
                 if constexpr (PB == 3) {

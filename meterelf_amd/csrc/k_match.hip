@@ -28,11 +28,13 @@ __device__ inline bool better(float v, int i, float bv, int bi)
 }
 
 // The body of k_match and k_match_px4.  PX: 1 = packed single-channel u8 images, 3 = 3-byte pixels (BGR / RGB: L = (max + min) / 2
-// does not depend on the channel order), 4 = 4-byte pixels (BGRA / RGBA, 4-byte aligned, the 4th byte ignored).
-template <int PX>
+// does not depend on the channel order), 4 = 4-byte pixels (BGRA / RGBA, 4-byte aligned, the 4th byte ignored); 20 / 21 = NV12 /
+// I420 frames (src: the Y plane, yuv: the chroma planes; a Y byte and the chroma pair under it per pixel, byte loads).
+struct NoYuv {};
+template <int PX, class YUV = NoYuv>
 __device__ __forceinline__ void match_tile(MatchSrc src, MatchGeom g, const uint32_t* __restrict__ tplT,
                                            int rh, int rw, int nrb, float* __restrict__ result_map,
-                                           MatchPartial* __restrict__ partials, int nparts)
+                                           MatchPartial* __restrict__ partials, int nparts, YUV yuv = YUV{})
 {
     constexpr int R = MATCH_R;
     extern __shared__ uint32_t lds[];
@@ -49,6 +51,12 @@ __device__ __forceinline__ void match_tile(MatchSrc src, MatchGeom g, const uint
     for (int row = wave; row < g.lds_rows; row += MATCH_WAVES) {
         const int y = yb + row;
         const uint8_t* prow = img + (size_t)(src.y0 + y) * src.row_stride;
+        [[maybe_unused]] const uint8_t* urow = nullptr;
+        [[maybe_unused]] const uint8_t* vrow = nullptr;
+        if constexpr (PX == 20 || PX == 21) {
+            urow = img + (size_t)yuv.u_off + (size_t)((src.y0 + y) >> 1) * (size_t)yuv.c_pitch;
+            vrow = img + (size_t)yuv.v_off + (size_t)((src.y0 + y) >> 1) * (size_t)yuv.c_pitch;
+        }
         for (int c4 = lane; c4 < g.ldsw; c4 += 64) {
             uint32_t packed = 0;
             if (y < src.rows) {
@@ -57,7 +65,11 @@ __device__ __forceinline__ void match_tile(MatchSrc src, MatchGeom g, const uint
                     const int x = xb + c4 * 4 + k;
                     uint32_t v = 0;
                     if (x < src.cols) {
-                        if (PX == 3) {
+                        if constexpr (PX == 20 || PX == 21) {
+                            const int cx = (src.x0 + x) >> 1, ci = PX == 20 ? 2 * cx : cx;
+                            const YuvChroma c = yuv_chroma(urow[ci], vrow[ci]);
+                            v = (uint32_t)yuv_lightness(prow[src.x0 + x], yuv_cmax(c), yuv_cmin(c));
+                        } else if (PX == 3) {
                             const uint8_t* p = prow + (size_t)(src.x0 + x) * 3;
                             v = (uint32_t)hls_lightness(p[0], p[1], p[2]);
                         } else if (PX == 4) {
@@ -162,6 +174,15 @@ __global__ __launch_bounds__(256) void k_match_px4(MatchSrc src, MatchGeom g, co
     match_tile<4>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts);
 }
 
+// NV12 / I420 frames (melf_process_yuv*)
+template <bool PLANAR>
+__global__ __launch_bounds__(256) void k_match_yuv(MatchSrc src, YuvPlanes yuv, MatchGeom g, const uint32_t* __restrict__ tplT,
+                                                   int rh, int rw, int nrb, float* __restrict__ result_map,
+                                                   MatchPartial* __restrict__ partials, int nparts)
+{
+    match_tile<PLANAR ? 21 : 20, YuvPlanes>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts, yuv);
+}
+
 int match_parts(const MatchGeom& g, int rows, int cols)
 {
     const int rh = rows - g.th + 1, rw = cols - g.tw + 1;
@@ -171,7 +192,7 @@ int match_parts(const MatchGeom& g, int rows, int cols)
 }
 
 void launch_match(const MatchSrc& src, int pix, int n, const MatchGeom& g, const uint32_t* d_tplT,
-                  float* d_result_map, MatchPartial* d_partials, int* nparts_out, hipStream_t stream)
+                  float* d_result_map, MatchPartial* d_partials, int* nparts_out, hipStream_t stream, const YuvPlanes* yuv)
 {
     const int rh = src.rows - g.th + 1, rw = src.cols - g.tw + 1;
     const int nrb = (rh + MATCH_RBLK - 1) / MATCH_RBLK, ncb = (rw + MATCH_CBLK - 1) / MATCH_CBLK;
@@ -179,7 +200,13 @@ void launch_match(const MatchSrc& src, int pix, int n, const MatchGeom& g, const
     if (nparts_out) *nparts_out = nparts;
     const size_t shmem = (size_t)g.lds_rows * g.ldsw * sizeof(uint32_t);
     dim3 grid(nparts, n), block(256);
-    if (pix == PIX_PLANE)
+    if (pix == PIX_NV12)
+        hipLaunchKernelGGL(k_match_yuv<false>, grid, block, shmem, stream, src, *yuv, g, d_tplT, rh, rw, nrb, d_result_map,
+                           d_partials, nparts);
+    else if (pix == PIX_I420)
+        hipLaunchKernelGGL(k_match_yuv<true>, grid, block, shmem, stream, src, *yuv, g, d_tplT, rh, rw, nrb, d_result_map,
+                           d_partials, nparts);
+    else if (pix == PIX_PLANE)
         hipLaunchKernelGGL(k_match<false>, grid, block, shmem, stream, src, g, d_tplT, rh, rw, nrb, d_result_map,
                            d_partials, nparts);
     else if (pix_bytes(pix) == 4)

@@ -82,6 +82,18 @@ __global__ __launch_bounds__(256) void k_lplane_px4(MatchSrc src, int nframes, i
 #include "prep_lplane_body.inc"
 }
 
+// NV12 / I420 frames (melf_process_yuv*): src is the Y plane, yuv the chroma planes; PLANAR: separate U and V planes (I420, YV12)
+// instead of interleaved U V pairs (NV12).  L comes straight from Y, U, V (melf_device.h: yuv_lightness); no BGR pixel is formed.
+#define MELF_YUV_BODY
+template <bool PLANAR>
+__global__ __launch_bounds__(256) void k_lplane_yuv(MatchSrc src, YuvPlanes yuv, int nframes, int nkb, int rows_pad, int tw, int rwp, int pairs,
+                                                    int8_t* __restrict__ Lg, uint16_t* __restrict__ R)
+{
+    constexpr int PX = PLANAR ? 21 : 20;
+#include "prep_lplane_body.inc"
+}
+#undef MELF_YUV_BODY
+
 // ---------------------------------------------------------------------------
 // k_match_mfma
 // ---------------------------------------------------------------------------
@@ -764,7 +776,7 @@ void mfma_build_atab(const uint8_t* templ, int th, int tw, int8_t* atab)
 }
 
 void launch_match_prep(const MatchSrc& src, int pix, int n, int groups, int rows_pad, int nkb, int rwp, int tw, int8_t* d_lg,
-                       uint16_t* d_r, hipStream_t stream, int pairs)
+                       uint16_t* d_r, hipStream_t stream, int pairs, const YuvPlanes* yuv)
 {
     dim3 grid(rows_pad, groups), block(256);
     const size_t pre_bytes = (size_t)32 * (nkb * 32 + 8) * sizeof(int16_t);
@@ -775,18 +787,22 @@ void launch_match_prep(const MatchSrc& src, int pix, int n, int groups, int rows
         (void)hipFuncSetAttribute((const void*)k_prep_lplane<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute((const void*)k_prep_lplane<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute((const void*)k_lplane_px4, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_lplane_yuv<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_lplane_yuv<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         attr_set[dev] = true;
     }
-    if (pix == PIX_PLANE) hipLaunchKernelGGL((k_prep_lplane<false>), grid, block, pre_bytes, stream, src, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    if (pix == PIX_NV12) hipLaunchKernelGGL((k_lplane_yuv<false>), grid, block, pre_bytes, stream, src, *yuv, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    else if (pix == PIX_I420) hipLaunchKernelGGL((k_lplane_yuv<true>), grid, block, pre_bytes, stream, src, *yuv, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    else if (pix == PIX_PLANE) hipLaunchKernelGGL((k_prep_lplane<false>), grid, block, pre_bytes, stream, src, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else if (pix_bytes(pix) == 4) hipLaunchKernelGGL(k_lplane_px4, grid, block, pre_bytes, stream, src, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else hipLaunchKernelGGL((k_prep_lplane<true>), grid, block, pre_bytes, stream, src, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
 }
 
 void launch_mfma_prep(const MatchSrc& src, int pix, int n, const MfmaPlan& p, int th, int tw, int8_t* d_lg,
-                      uint16_t* d_r, hipStream_t stream)
+                      uint16_t* d_r, hipStream_t stream, const YuvPlanes* yuv)
 {
     (void)th;
-    launch_match_prep(src, pix, n, p.groups, p.rows_pad, p.nkb, 64, tw, d_lg, d_r, stream, p.nxb);   // one paired operand per column block
+    launch_match_prep(src, pix, n, p.groups, p.rows_pad, p.nkb, 64, tw, d_lg, d_r, stream, p.nxb, yuv);   // one paired operand per column block
 }
 
 template <int NXB, int RB, int KS>

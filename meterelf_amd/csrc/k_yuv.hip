@@ -1,0 +1,47 @@
+// YUV 4:2:0 -> BGR alone: the stage kernel behind melf_yuv_to_bgr (include/meterelf_hip.h), what
+// cv2.cvtColor(COLOR_YUV2BGR_NV12 / _I420) makes of a decoder's frame before the reference's get_bgr_image hands it on
+// (meterelf/_image.py:46-51).  The arithmetic is melf_device.h's yuv_chroma / yuv_bgr, the functions the reading kernels
+// (k_lplane_yuv, k_match_yuv, k_yneedle) convert with in place: this kernel pins it for every (Y, U, V).
+//
+// Mapping: one thread per 2 x 2 block of pixels, which shares one chroma pair: two byte loads of chroma, two 2-byte loads of
+// Y, two 6-byte rows of B G R out.  A parity and debugging aid, not a hot path: the hot path never forms the BGR frame.
+#include "melf_device.h"
+#include "melf_internal.h"
+
+namespace melf {
+
+template <bool PLANAR>
+__global__ __launch_bounds__(256) void k_yuv2bgr(const uint8_t* __restrict__ src, int H, int W, int y_pitch, size_t frame_stride,
+                                                 YuvPlanes yuv, uint8_t* __restrict__ dst)
+{
+    const int bx = blockIdx.x * blockDim.x + threadIdx.x, by = blockIdx.y, f = blockIdx.z;
+    if (bx >= (W >> 1) || by >= (H >> 1)) return;
+    const uint8_t* frame = src + (size_t)f * frame_stride;
+    const size_t co = (size_t)by * (size_t)yuv.c_pitch + (size_t)(PLANAR ? bx : 2 * bx);
+    const YuvChroma c = yuv_chroma(frame[(size_t)yuv.u_off + co], frame[(size_t)yuv.v_off + co]);
+    uint8_t* out = dst + ((size_t)f * H + 2 * by) * (size_t)W * 3 + (size_t)bx * 6;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const uint8_t* yrow = frame + (size_t)(2 * by + r) * (size_t)y_pitch + 2 * bx;
+        const uint32_t p0 = yuv_bgr(yrow[0], c), p1 = yuv_bgr(yrow[1], c);
+        uint8_t* o = out + (size_t)r * W * 3;
+        o[0] = (uint8_t)p0; o[1] = (uint8_t)(p0 >> 8); o[2] = (uint8_t)(p0 >> 16);
+        o[3] = (uint8_t)p1; o[4] = (uint8_t)(p1 >> 8); o[5] = (uint8_t)(p1 >> 16);
+    }
+}
+
+void launch_yuv2bgr(const uint8_t* d_src, int pix, int n, int H, int W, int y_pitch, size_t frame_stride, const YuvPlanes& yuv,
+                    uint8_t* d_dst, hipStream_t stream)
+{
+    // at most 65 535 frames per launch (grid z)
+    for (int f0 = 0; f0 < n; f0 += 65535) {
+        const int m = n - f0 < 65535 ? n - f0 : 65535;
+        dim3 grid(((W >> 1) + 255) / 256, H >> 1, m), block(256);
+        const uint8_t* s = d_src + (size_t)f0 * frame_stride;
+        uint8_t* d = d_dst + (size_t)f0 * H * W * 3;
+        if (pix == PIX_I420) hipLaunchKernelGGL(k_yuv2bgr<true>, grid, block, 0, stream, s, H, W, y_pitch, frame_stride, yuv, d);
+        else hipLaunchKernelGGL(k_yuv2bgr<false>, grid, block, 0, stream, s, H, W, y_pitch, frame_stride, yuv, d);
+    }
+}
+
+}  // namespace melf

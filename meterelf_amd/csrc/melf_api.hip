@@ -1029,14 +1029,14 @@ static int gen_entry(melf_ctx* c, int rows, int cols, int n, melf_ctx::GenEntry*
 // prep + match of m images on stream ls with lane bl's work buffers; *parts / *nparts: per-frame (max, first arg-max)
 // partials for the consumer (k_dials or the host fold of melf_match_ccoeff)
 static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int bl, hipStream_t ls, float* d_map,
-                          MatchPartial** parts, int* nparts, TimedEvent& ev);
+                          MatchPartial** parts, int* nparts, TimedEvent& ev, const YuvPlanes* yuv);
 static int run_match(melf_ctx* c, const MatchSrc& ms, int pix, int m, int bl, hipStream_t ls, float* d_map,
-                     MatchPartial** parts, int* nparts)
+                     MatchPartial** parts, int* nparts, const YuvPlanes* yuv = nullptr /* pix_yuv(pix): the chroma planes */)
 {
     TimedEvent ev;
     ev.kernel = MELF_K_MATCH;
     ev.start = ev.stop = nullptr;
-    const int rc = run_match_impl(c, ms, pix, m, bl, ls, d_map, parts, nparts, ev);
+    const int rc = run_match_impl(c, ms, pix, m, bl, ls, d_map, parts, nparts, ev, yuv);
     if (rc == MELF_SUCCESS && ev.start && ev.stop) {
         c->events.push_back(ev);
     } else {   // nothing was launched with them (an allocation failed on the way)
@@ -1046,7 +1046,7 @@ static int run_match(melf_ctx* c, const MatchSrc& ms, int pix, int m, int bl, hi
     return rc;
 }
 static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int bl, hipStream_t ls, float* d_map,
-                          MatchPartial** parts, int* nparts, TimedEvent& ev)
+                          MatchPartial** parts, int* nparts, TimedEvent& ev, const YuvPlanes* yuv)
 {
     const melf_params& P = c->P;
     const int kind = pick_match_kind(c, ms.rows, ms.cols, m);
@@ -1070,7 +1070,7 @@ static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int b
         *parts = c->d_lpart[bl];
         {
             KernelTimer t(c, MELF_K_LPLANE, ls);
-            launch_mfma_prep(ms, pix, m, pl, P.th, P.tw, c->d_lg[bl], c->d_rsum[bl], ls);
+            launch_mfma_prep(ms, pix, m, pl, P.th, P.tw, c->d_lg[bl], c->d_rsum[bl], ls, yuv);
         }
         info.rows_per_wave = pl.rb; info.full_waves = pl.na; info.pair_waves = 2 * pl.np;
         info.waves = pl.nparts * pl.groups; info.tiles = pl.ntiles;
@@ -1088,7 +1088,7 @@ static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int b
         *parts = c->d_lpart[bl];
         {
             KernelTimer t(c, MELF_K_LPLANE, ls);
-            launch_match_prep(ms, pix, m, pl.groups, pl.rows_pad, pl.nkb, pl.rwp, P.tw, c->d_lg[bl], c->d_rsum[bl], ls);
+            launch_match_prep(ms, pix, m, pl.groups, pl.rows_pad, pl.nkb, pl.rwp, P.tw, c->d_lg[bl], c->d_rsum[bl], ls, 0, yuv);
         }
         const GenDev& dev = ge->dev;
         fill_gen_info(&info, pl);
@@ -1098,7 +1098,7 @@ static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int b
         if (int rc = grow(&c->d_lpart[bl], &c->lpart_cap[bl], (size_t)m * *nparts)) return rc;
         *parts = c->d_lpart[bl];
         KernelTimer t(c, MELF_K_MATCH, ls);
-        launch_match(ms, pix, m, c->mg, c->d_tplT, d_map, *parts, nullptr, ls);
+        launch_match(ms, pix, m, c->mg, c->d_tplT, d_map, *parts, nullptr, ls, yuv);
         info.tiles = *nparts;
     }
     if (trace)
@@ -1113,10 +1113,11 @@ static const int MAX_FRAMES_PER_LAUNCH = 32768;
 
 // rect (optional): {x0, y0, x1, y1} of the meter crop inside the H x W frames instead of the context's meter_rect
 // (the host-fed path uploads only the crop: its "frames" are the crops themselves); row_stride: bytes between rows
-// (0 = packed); pix: the frames' pixel layout (MELF_PIX_*)
+// (0 = packed); pix: the frames' pixel layout (MELF_PIX_*, or PIX_NV12 / PIX_I420: d_frames, frame_stride and row_stride then describe
+// the Y plane, yuv the chroma planes, yuv_extent = the bytes of a frame up to the last sample of its last plane)
 static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
                             void* d_results, melf_result* out_host, hipStream_t st, const int* rect = nullptr, int row_stride = 0,
-                            int pix = MELF_PIX_BGR);
+                            int pix = MELF_PIX_BGR, const YuvPlanes* yuv = nullptr, size_t yuv_extent = 0);
 
 // The checks of a melf_frames descriptor (melf_process_frames*); n == 0 passes
 static int check_frames(const void* frames, const melf_frames* f)
@@ -1137,7 +1138,7 @@ static int check_frames(const void* frames, const melf_frames* f)
 }
 
 static int batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride, int row_stride, int pix,
-                     void* d_results, melf_result* out_host, void* stream_);
+                     void* d_results, melf_result* out_host, void* stream_, const YuvPlanes* yuv = nullptr, size_t yuv_extent = 0);
 
 extern "C" int melf_process_batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
                                       void* d_results, melf_result* out_host, void* stream_)
@@ -1160,9 +1161,50 @@ extern "C" int melf_process_frames_dev(melf_ctx* c, const void* d_frames, const 
                      stream_);
 }
 
-// melf_process_batch_dev / melf_process_frames_dev after their argument checks: the lane logic
+// The checks of a melf_yuv_frames descriptor (melf_process_yuv*, melf_yuv_to_bgr); n == 0 passes.  *pix: PIX_NV12 / PIX_I420,
+// *yp: the chroma planes, *extent: the bytes of one frame up to the last sample of its last plane.
+static int check_yuv(const void* frames, const melf_yuv_frames* f, int* pix, YuvPlanes* yp, size_t* extent)
+{
+    if (!f) return fail(MELF_ERR_INVALID, "YUV frame descriptor is NULL");
+    if (f->format != MELF_YUV_NV12 && f->format != MELF_YUV_I420) return fail(MELF_ERR_INVALID, "unknown YUV format");
+    if (f->matrix != MELF_YUV_BT601_LIMITED) return fail(MELF_ERR_INVALID, "unknown YUV matrix (BT.601 limited range only)");
+    if (f->n < 0 || f->H <= 0 || f->W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
+    if ((f->H | f->W) & 1) return fail(MELF_ERR_INVALID, "YUV 4:2:0 frames need an even height and width");
+    if (f->H > 131070) return fail(MELF_ERR_INVALID, "frame too high");
+    const bool nv12 = f->format == MELF_YUV_NV12;
+    const int64_t cw = nv12 ? f->W : f->W / 2;   // bytes of a chroma row
+    if (f->y_pitch < f->W || f->y_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "y_pitch smaller than a row (or too large)");
+    if (f->c_pitch < cw || f->c_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "c_pitch smaller than a chroma row (or too large)");
+    const int64_t y_end = (int64_t)(f->H - 1) * f->y_pitch + f->W;
+    const int64_t c_len = (int64_t)(f->H / 2 - 1) * f->c_pitch + (nv12 ? cw - 1 : cw);   // samples of one of U, V from its offset
+    if (f->u_offset < y_end || f->v_offset < y_end) return fail(MELF_ERR_INVALID, "a chroma plane overlaps the Y plane");
+    if (nv12 && (f->v_offset != f->u_offset + 1 || (f->u_offset & 1)))
+        return fail(MELF_ERR_INVALID, "NV12 needs v_offset == u_offset + 1 and an even u_offset");
+    const int64_t c_end = (f->u_offset > f->v_offset ? f->u_offset : f->v_offset) + c_len;
+    if (f->frame_stride < c_end) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
+    *pix = nv12 ? PIX_NV12 : PIX_I420;
+    yp->u_off = f->u_offset; yp->v_off = f->v_offset; yp->c_pitch = (int)f->c_pitch; yp->pad = 0;
+    *extent = (size_t)c_end;
+    if (f->n == 0) return MELF_SUCCESS;
+    if (!frames) return fail(MELF_ERR_INVALID, "frames pointer is NULL");
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_process_yuv_dev(melf_ctx* c, const void* d_frames, const melf_yuv_frames* f, void* d_results, melf_result* out_host,
+                                    void* stream_)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    int pix = 0;
+    YuvPlanes yp;
+    size_t extent = 0;
+    if (int rc = check_yuv(d_frames, f, &pix, &yp, &extent)) return rc;
+    if (f->n == 0) return MELF_SUCCESS;
+    return batch_dev(c, d_frames, f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->y_pitch, pix, d_results, out_host, stream_, &yp, extent);
+}
+
+// melf_process_batch_dev / melf_process_frames_dev / melf_process_yuv_dev after their argument checks: the lane logic
 static int batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride, int row_stride, int pix,
-                     void* d_results, melf_result* out_host, void* stream_)
+                     void* d_results, melf_result* out_host, void* stream_, const YuvPlanes* yuv, size_t yuv_extent)
 {
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream_;  // NULL = the null (legacy default) stream, as everywhere in HIP
@@ -1176,7 +1218,7 @@ static int batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, siz
         c->active_lane = lane;
         c->order_stream = st;
         c->order_valid = true;
-        const int rc = process_batch_on(c, d_frames, n, H, W, frame_stride, d_results, nullptr, ls, nullptr, row_stride, pix);
+        const int rc = process_batch_on(c, d_frames, n, H, W, frame_stride, d_results, nullptr, ls, nullptr, row_stride, pix, yuv, yuv_extent);
         c->order_valid = false;
         if (rc) return rc;
         HIP_TRY(hipEventRecord(c->ev_join[lane], ls));
@@ -1189,17 +1231,18 @@ static int batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, siz
         return MELF_SUCCESS;
     }
     if (int rc = acquire_lane(c, st, &c->active_lane)) return rc;
-    return process_batch_on(c, d_frames, n, H, W, frame_stride, d_results, out_host, st, nullptr, row_stride, pix);
+    return process_batch_on(c, d_frames, n, H, W, frame_stride, d_results, out_host, st, nullptr, row_stride, pix, yuv, yuv_extent);
 }
 
 static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
-                            void* d_results, melf_result* out_host, hipStream_t st, const int* rect, int row_stride, int pix)
+                            void* d_results, melf_result* out_host, hipStream_t st, const int* rect, int row_stride, int pix,
+                            const YuvPlanes* yuv, size_t yuv_extent)
 {
-    const int bpp = pix_bytes(pix);
+    const int bpp = yuv ? 1 : pix_bytes(pix);
     if (row_stride <= 0) row_stride = W * bpp;  // packed rows unless the caller's rows are padded (host-fed crops, pitched frames)
     // what the kernels may read of the last frame: its rows as far as they reach (the last row of a pitched buffer needs no
     // padding); the host-fed crops keep their staging pitch and spare bytes behind every crop
-    const size_t last_frame = rect ? (size_t)H * row_stride : (size_t)(H - 1) * row_stride + (size_t)W * bpp;
+    const size_t last_frame = yuv ? yuv_extent : (rect ? (size_t)H * row_stride : (size_t)(H - 1) * row_stride + (size_t)W * bpp);
     const melf_params& P = c->P;
     // numpy slicing img[y0:y1, x0:x1] clamps to the image (meterelf/_image.py:54-55)
     const int rx0 = rect ? rect[0] : P.rect_x0, ry0 = rect ? rect[1] : P.rect_y0;
@@ -1226,7 +1269,7 @@ static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int
         ms.readable = (size_t)(m - 1) * frame_stride + last_frame;
         int nparts = 0;
         MatchPartial* parts = nullptr;
-        if (int rc = run_match(c, ms, pix, m, bl, st, nullptr, &parts, &nparts)) return rc;
+        if (int rc = run_match(c, ms, pix, m, bl, st, nullptr, &parts, &nparts, yuv)) return rc;
         DialsSrc ds;
         ds.base = base; ds.frame_stride = frame_stride; ds.row_stride = row_stride;
         ds.x0 = x0; ds.y0 = y0; ds.crop_rows = crows; ds.crop_cols = ccols;
@@ -1241,7 +1284,7 @@ static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int
         }
         {
             KernelTimer t(c, MELF_K_DIALS, st);
-            launch_dials(ds, pix, m, P, c->d_geom, c->d_rowmasks, parts, nparts, rw, res_dev + f0, st, c->ws_max);
+            launch_dials(ds, pix, m, P, c->d_geom, c->d_rowmasks, parts, nparts, rw, res_dev + f0, st, c->ws_max, yuv);
         }
         HIP_TRY(hipGetLastError());
     }
@@ -1401,7 +1444,124 @@ static int batch_host(melf_ctx* c, const uint8_t* frames_host, int n, int H, int
     return MELF_SUCCESS;
 }
 
+// YUV 4:2:0 host frames: the same pipeline.  What crosses PCIe per frame is a small frame of the same format: the Y rows of the
+// crop with its origin rounded down (and its far corner up) to even, and the chroma rows under them, each plane at a 64-byte
+// pitch in the staging buffer; the kernels read it with the rectangle shifted by the rounding (0 or 1 pixel each way).  Rows are
+// copied as they are: no byte is converted on the CPU.
+static int batch_host_yuv(melf_ctx* c, const uint8_t* frames_host, const melf_yuv_frames* f, int pix, const YuvPlanes& yp, melf_result* out_host)
+{
+    const int n = f->n, H = f->H, W = f->W;
+    const bool nv12 = pix == PIX_NV12;
+    HIP_TRY(hipSetDevice(c->device));
+    pool_use_device(c->device);
+    const melf_params& P = c->P;
+    const int x0 = P.rect_x0 < W ? P.rect_x0 : W, x1 = P.rect_x1 < W ? P.rect_x1 : W;
+    const int y0 = P.rect_y0 < H ? P.rect_y0 : H, y1 = P.rect_y1 < H ? P.rect_y1 : H;
+    const int crows = y1 - y0, ccols = x1 - x0;
+    if (x0 < 0 || y0 < 0 || crows < P.th || ccols < P.tw)
+        return fail(MELF_ERR_INVALID, "meter_rect crop is smaller than the dials template (cv2.matchTemplate would assert)");
+    const int ex0 = x0 & ~1, ey0 = y0 & ~1;
+    const int sw = ((x1 + 1) & ~1) - ex0, sh = ((y1 + 1) & ~1) - ey0;   // the small frame (even, inside the frame: H and W are even)
+    const size_t ypitch = ((size_t)sw + 63) & ~(size_t)63;
+    const size_t cbytes = nv12 ? (size_t)sw : (size_t)sw / 2;            // bytes of a chroma row
+    const size_t cpitch = (cbytes + 63) & ~(size_t)63;
+    YuvPlanes sp;
+    sp.u_off = (int64_t)((size_t)sh * ypitch);
+    sp.v_off = nv12 ? sp.u_off + 1 : sp.u_off + (int64_t)((size_t)(sh / 2) * cpitch);
+    sp.c_pitch = (int)cpitch; sp.pad = 0;
+    // + 128 spare bytes per small frame (the prep kernel's aligned windows reach past the last sample)
+    const size_t crop_stride = (size_t)sh * ypitch + (size_t)(sh / 2) * cpitch * (nv12 ? 1 : 2) + 128;
+    const int chunk = 128;  // frames per pipeline stage (a multiple of the 32-frame MFMA group)
+    const size_t pin_need = (size_t)(n < chunk ? n : chunk) * crop_stride;
+    if (!c->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    for (int b = 0; b < 2; ++b) {
+        if (!c->ev_h2d[b]) HIP_TRY(hipEventCreateWithFlags(&c->ev_h2d[b], hipEventDisableTiming));
+        if (c->pin_cap[b] < pin_need && (b == 0 || n > chunk)) {
+            if (c->h_pin[b]) { HIP_TRY(hipStreamSynchronize(c->copy_stream)); HIP_TRY(hipHostFree(c->h_pin[b])); }
+            c->h_pin[b] = nullptr;
+            c->pin_cap[b] = 0;
+            HIP_TRY(hipHostMalloc((void**)&c->h_pin[b], pin_need, hipHostMallocDefault));
+            c->pin_cap[b] = pin_need;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the previous call's kernels may still read d_crops
+    if (int rc = grow(&c->d_crops, &c->crops_cap, (size_t)n * crop_stride)) return rc;
+    if (int rc = grow(&c->d_results, &c->results_cap, (size_t)n)) return rc;
+    if (int rc = acquire_lane(c, c->stream, &c->active_lane)) return rc;
+    const int rect[4] = {x0 - ex0, y0 - ey0, x0 - ex0 + ccols, y0 - ey0 + crows};
+    int k = 0;
+    for (int f0 = 0; f0 < n; f0 += chunk, ++k) {
+        const int m = n - f0 < chunk ? n - f0 : chunk;
+        const int b = k & 1;
+        if (k >= 2) HIP_TRY(hipEventSynchronize(c->ev_h2d[b]));  // the copy that last read this staging buffer is done
+        uint8_t* pin = c->h_pin[b];
+        // work items: the Y rows of a frame in blocks of 32, and its chroma rows as one more
+        const int rblocks = (sh + 31) / 32;
+        host_pool().run(m * (rblocks + 1), [&](int item) {
+            const int i = item / (rblocks + 1), part = item - i * (rblocks + 1);
+            const uint8_t* frame = frames_host + (size_t)(f0 + i) * (size_t)f->frame_stride;
+            uint8_t* small = pin + (size_t)i * crop_stride;
+            if (part < rblocks) {
+                const int r0 = part * 32, r1 = r0 + 32 < sh ? r0 + 32 : sh;
+                for (int y = r0; y < r1; ++y)
+                    memcpy(small + (size_t)y * ypitch, frame + (size_t)(ey0 + y) * (size_t)f->y_pitch + ex0, (size_t)sw);
+            } else {
+                const size_t cx = nv12 ? (size_t)ex0 : (size_t)ex0 / 2;
+                for (int y = 0; y < sh / 2; ++y) {
+                    const size_t so = (size_t)(ey0 / 2 + y) * (size_t)f->c_pitch + cx;
+                    memcpy(small + (size_t)sp.u_off + (size_t)y * cpitch, frame + (size_t)f->u_offset + so, cbytes);
+                    if (!nv12) memcpy(small + (size_t)sp.v_off + (size_t)y * cpitch, frame + (size_t)f->v_offset + so, cbytes);
+                }
+            }
+        });
+        uint8_t* d_chunk = c->d_crops + (size_t)f0 * crop_stride;
+        HIP_TRY(hipMemcpyAsync(d_chunk, pin, (size_t)m * crop_stride, hipMemcpyHostToDevice, c->copy_stream));
+        HIP_TRY(hipEventRecord(c->ev_h2d[b], c->copy_stream));
+        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_h2d[b], 0));
+        if (int rc = process_batch_on(c, d_chunk, m, sh, sw, crop_stride, c->d_results + f0, nullptr, c->stream, rect, (int)ypitch, pix, &sp,
+                                      crop_stride))
+            return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(out_host, c->d_results, (size_t)n * sizeof(melf_result), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    (void)yp;
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_process_yuv(melf_ctx* c, const void* frames_host, const melf_yuv_frames* f, melf_result* out_host)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    int pix = 0;
+    YuvPlanes yp;
+    size_t extent = 0;
+    if (int rc = check_yuv(frames_host, f, &pix, &yp, &extent)) return rc;
+    if (f->n == 0) return MELF_SUCCESS;
+    if (!out_host) return fail(MELF_ERR_INVALID, "out_host is NULL");
+    return batch_host_yuv(c, (const uint8_t*)frames_host, f, pix, yp, out_host);
+}
+
 // ---------------------------------------------------------- stage entries ----
+extern "C" int melf_yuv_to_bgr(melf_ctx* c, const void* frames_host, const melf_yuv_frames* f, uint8_t* bgr_out_host)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    int pix = 0;
+    YuvPlanes yp;
+    size_t extent = 0;
+    if (int rc = check_yuv(frames_host, f, &pix, &yp, &extent)) return rc;
+    if (f->n == 0) return MELF_SUCCESS;
+    if (!bgr_out_host) return fail(MELF_ERR_INVALID, "bgr_out_host is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t in_bytes = (size_t)(f->n - 1) * (size_t)f->frame_stride + extent, out_bytes = (size_t)f->n * f->H * f->W * 3;
+    if (int rc = grow(&c->d_stage_in, &c->stage_in_cap, in_bytes)) return rc;
+    if (int rc = grow(&c->d_stage_out, &c->stage_out_cap, out_bytes)) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_stage_in, frames_host, in_bytes, hipMemcpyHostToDevice, c->stream));
+    launch_yuv2bgr(c->d_stage_in, pix, f->n, f->H, f->W, (int)f->y_pitch, (size_t)f->frame_stride, yp, c->d_stage_out, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(bgr_out_host, c->d_stage_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MELF_SUCCESS;
+}
+
 extern "C" int melf_bgr2hls(melf_ctx* c, const uint8_t* src_host, int rows, int cols, size_t row_stride, uint8_t* dst_host)
 {
     if (!c || !src_host || !dst_host || rows <= 0 || cols <= 0 || row_stride < (size_t)cols * 3)
@@ -1728,7 +1888,8 @@ static thread_local std::function<void()>* tl_jpeg_enqueued = nullptr;
 // overlapped: another call's kernels may still be running (melf_jpeg_process_files_begin, two calls in flight): nothing
 // here waits for the context's stream; what protects a ring slot is its own pair of events, across calls as within one.
 static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
-                            void* d_results, melf_result* out_host, hipStream_t st, const int* rect, int row_stride, int pix);
+                            void* d_results, melf_result* out_host, hipStream_t st, const int* rect, int row_stride, int pix,
+                            const YuvPlanes* yuv, size_t yuv_extent);
 // What a caller inside the library may already have of the files it hands to the decode path (the file-name entry points
 // do): the parsed headers + Huffman decode data (of file index[k] of that parse for the call's file k), and the pinned buffer
 // the files' bytes lie in.

@@ -86,6 +86,56 @@ __host__ __device__ inline void hls_pixel(int b8, int g8, int r8, bool scalar_ta
     S = sat_u8_rne(s * 255.f);
 }
 
+// ---- YUV 4:2:0 -> BGR (melf_process_yuv*, include/meterelf_hip.h: BT.601 limited range, the integer constants of
+// cv2.cvtColor(COLOR_YUV2BGR_NV12 / _I420), nearest chroma sample).  The one statement of the arithmetic: every kernel that
+// reads YUV frames goes through these.  All products fit 24-bit multiplies (|u|, |v| <= 128, Y - 16 <= 239, constants < 2^22)
+// and every sum 32 bits (|sum| < 2^30).
+__host__ __device__ inline int yuv_mul24(int a, int b)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    return __mul24(a, b);
+#else
+    return a * b;
+#endif
+}
+// The chroma terms of a sample pair, rounding constant included: what is added to the luma term per channel.
+struct YuvChroma {
+    int r, g, b;
+};
+__host__ __device__ inline YuvChroma yuv_chroma(int U, int V)
+{
+    const int u = U - 128, v = V - 128;
+    YuvChroma c;
+    c.r = yuv_mul24(v, 1673527) + (1 << 19);
+    c.g = yuv_mul24(v, -852492) + yuv_mul24(u, -409993) + (1 << 19);
+    c.b = yuv_mul24(u, 2116026) + (1 << 19);
+    return c;
+}
+__host__ __device__ inline int yuv_luma(int Y) { return yuv_mul24(Y > 16 ? Y - 16 : 0, 1220542); }
+__host__ __device__ inline int yuv_clamp8(int s)
+{
+    const int v = s >> 20;
+    return v < 0 ? 0 : (v > 255 ? 255 : v);
+}
+// the pixel as B | G << 8 | R << 16: what a load of a BGR frame's pixel gives
+__host__ __device__ inline uint32_t yuv_bgr(int Y, const YuvChroma& c)
+{
+    const int yy = yuv_luma(Y);
+    return (uint32_t)yuv_clamp8(yy + c.b) | (uint32_t)yuv_clamp8(yy + c.g) << 8 | (uint32_t)yuv_clamp8(yy + c.r) << 16;
+}
+// L = (max + min) / 2 needs the largest and the smallest channel only, and shift and clamp are monotone: they are those of the
+// largest and the smallest sum.  cmax / cmin: the largest / smallest chroma term of the pair (yuv_chroma).  The value of
+// hls_lightness_fast(B, G, R).
+__host__ __device__ inline int yuv_lightness(int Y, int cmax, int cmin)
+{
+    const int yy = yuv_luma(Y);
+    const float inv255 = 1.f / 255.f;
+    const float vmax = (float)yuv_clamp8(yy + cmax) * inv255, vmin = (float)yuv_clamp8(yy + cmin) * inv255;
+    return (int)rintf((vmax + vmin) * 127.5f);
+}
+__host__ __device__ inline int yuv_cmax(const YuvChroma& c) { return c.r > c.g ? (c.r > c.b ? c.r : c.b) : (c.g > c.b ? c.g : c.b); }
+__host__ __device__ inline int yuv_cmin(const YuvChroma& c) { return c.r < c.g ? (c.r < c.b ? c.r : c.b) : (c.g < c.b ? c.g : c.b); }
+
 #ifdef __HIPCC__
 // ---- wave64 helpers -------------------------------------------------------
 // Wave-wide reductions and scans on the DPP path (GFX9 row shifts + row broadcasts): six VALU steps and no LDS round

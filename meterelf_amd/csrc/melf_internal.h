@@ -24,6 +24,15 @@ inline const char* diag_env(const char*) { return nullptr; }
 // the stage entry points' packed single-channel images (melf_match_ccoeff) and HLS dials crops (melf_read_dials).
 constexpr int PIX_PLANE = -1;
 inline int pix_bytes(int pix) { return pix == MELF_PIX_BGRA || pix == MELF_PIX_RGBA ? 4 : 3; }
+// YUV 4:2:0 frames (melf_process_yuv*): the launch's pix, beside the MELF_PIX_* codes.  The Y plane is described like a
+// single-channel image (base, frame_stride, row_stride of MatchSrc / DialsSrc), the chroma planes by YuvPlanes.
+constexpr int PIX_NV12 = 16, PIX_I420 = 17;
+inline bool pix_yuv(int pix) { return pix == PIX_NV12 || pix == PIX_I420; }
+struct YuvPlanes {
+    int64_t u_off, v_off;  // bytes from a frame's first byte to its U / V samples (NV12: v_off == u_off + 1)
+    int c_pitch;           // bytes between chroma rows
+    int pad;
+};
 
 // ---- K2: template match -----------------------------------------------------
 // One partial (max, first-argmax) per workgroup tile of the correlation map.
@@ -58,7 +67,8 @@ struct MatchSrc {
 };
 
 void launch_match(const MatchSrc& src, int pix, int n, const MatchGeom& g, const uint32_t* d_tplT,
-                  float* d_result_map, MatchPartial* d_partials, int* nparts_out, hipStream_t stream);
+                  float* d_result_map, MatchPartial* d_partials, int* nparts_out, hipStream_t stream,
+                  const YuvPlanes* yuv = nullptr /* pix_yuv(pix) */);
 int match_parts(const MatchGeom& g, int rows, int cols);
 
 // ---- K2 on the matrix cores (k_match_mfma.hip) --------------------------------
@@ -73,7 +83,7 @@ MfmaPlan mfma_plan(int th, int tw, int rows, int cols, int nframes);
 size_t mfma_atab_bytes(int th);
 void mfma_build_atab(const uint8_t* templ, int th, int tw, int8_t* atab);
 void launch_mfma_prep(const MatchSrc& src, int pix, int n, const MfmaPlan& p, int th, int tw, int8_t* d_lg,
-                      uint16_t* d_r, hipStream_t stream);
+                      uint16_t* d_r, hipStream_t stream, const YuvPlanes* yuv = nullptr);
 // launch_mfma_match: d_ws = the row-window sums R in epilogue order (k_prep_lplane); the waves add them up
 void launch_mfma_match(int n, const MfmaPlan& p, int th, int tw, long tsum, double tmean, const int8_t* d_atab,
                        const int8_t* d_lg, const uint32_t* d_ws, float* d_result_map, MatchPartial* d_partials,
@@ -111,7 +121,7 @@ void launch_gen_match(int n, const GenPlan& p, int rows, int th, int tw, long ts
 // prep for either matrix-core kernel: Lg (fragment order) and the row-window sums R in the match waves' epilogue order
 // (pairs > 0: the tuned kernel's paired-operand row layout, see k_prep_lplane)
 void launch_match_prep(const MatchSrc& src, int pix, int n, int groups, int rows_pad, int nkb, int rwp, int tw, int8_t* d_lg,
-                       uint16_t* d_r, hipStream_t stream, int pairs = 0);
+                       uint16_t* d_r, hipStream_t stream, int pairs = 0, const YuvPlanes* yuv = nullptr);
 
 // ---- K3: per-dial reading ---------------------------------------------------
 struct DialGeom {
@@ -131,7 +141,8 @@ struct DialsSrc {
 
 void launch_dials(const DialsSrc& src, int pix, int n, const melf_params& P, const DialGeom* d_geom,
                   const uint64_t* d_rowmasks /* [ndials][3][64] */, const MatchPartial* d_partials,
-                  int nparts, int rw, melf_result* d_results, hipStream_t stream, int ws_max /* largest DialGeom::ws */);
+                  int nparts, int rw, melf_result* d_results, hipStream_t stream, int ws_max /* largest DialGeom::ws */,
+                  const YuvPlanes* yuv = nullptr /* pix_yuv(pix) */);
 
 // ---- K1b / HLS --------------------------------------------------------------
 void launch_bgr2hls(const uint8_t* d_src, int rows, int cols, size_t row_stride, int hue_shift,
@@ -159,6 +170,11 @@ void launch_fused_mask_lut(const uint8_t* d_frames, int n, int H, int W, int hue
 // measurement aid: bare 3:1 stream over the caller's buffers (bench.py's stream_ceiling); returns the bytes moved
 size_t launch_stream_probe(const void* d_in, size_t in_bytes, void* d_out, int chunks_per_block, uint32_t* d_tables, hipStream_t stream,
                            hipEvent_t ev_start, hipEvent_t ev_stop);
+
+// ---- k_yuv.hip: the YUV 4:2:0 -> BGR conversion alone (melf_yuv_to_bgr) ----
+// n frames: Y plane at d_src (y_pitch, frame_stride), chroma planes per YuvPlanes; d_dst: n packed H x W x 3 BGR frames
+void launch_yuv2bgr(const uint8_t* d_src, int pix, int n, int H, int W, int y_pitch, size_t frame_stride, const YuvPlanes& yuv,
+                    uint8_t* d_dst, hipStream_t stream);
 
 // ---- calibration stage kernels ------------------------------------------------
 void launch_aligned_average(const uint8_t* d_frames, int n, size_t frame_stride, int row_stride, int x0, int y0, int rows,

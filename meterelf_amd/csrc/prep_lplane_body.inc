@@ -4,6 +4,10 @@
 //   PX  1 = packed single-channel u8 images, 3 = 3-byte pixels (BGR / RGB: L = (max + min) / 2 does not depend on the channel
 //       order), 4 = 4-byte pixels (BGRA / RGBA, base, rows and frames 4-byte aligned, the 4th byte ignored): 32 pixels are 128
 //       bytes, eight aligned 16-byte loads, no gather.
+//   With MELF_YUV_BODY defined by the including kernel (k_lplane_yuv): PX 20 = NV12, 21 = I420 frames, the chroma planes in `yuv`
+//       (YuvPlanes); src describes the Y plane.  A lane's window starts at the EVEN pixel at or left of its first one: 34 Y bytes and
+//       the 17 chroma pairs under them (NV12 34 interleaved bytes, I420 17 + 17), as aligned dwords; an odd crop origin costs the
+//       one pixel of overlap (the 34 results are shifted by a byte at the end), not a second code path.
     constexpr int PB = PX == 4 ? 4 : 3;         // bytes per pixel of the frame reads
     constexpr int WIN = PX == 4 ? 128 : 100;    // bytes a lane's 32-pixel load window spans
     __shared__ __attribute__((aligned(16))) uint32_t tile[8 * 2 * 32 * 4];  // [kb][h][n][16 B], one chunk of 8 blocks
@@ -16,8 +20,19 @@
     // (wave-uniform, once) every 100-byte gather window of this row, in every frame of the group, ends inside the caller's buffer -- all
     // rows but the last few of the last frame; the per-lane pointer test below then never runs (as the branch condition of every
     // thread it cost 10 % of the kernel: profiles/r06/prep_bisect.txt)
+#ifdef MELF_YUV_BODY
+    (void)PB; (void)WIN;
+    // (the same for the three windows of a YUV lane: 40 bytes from the Y sample and from the chroma samples of its even pixel)
+    const int xodd = src.x0 & 1;
+    const size_t yuv_last = (size_t)min(grp * 32 + 31, nframes - 1) * src.frame_stride;
+    const size_t yuv_crow = (size_t)((src.y0 + y) >> 1) * (size_t)yuv.c_pitch;
+    const int yuv_xlast = (src.x0 & ~1) + 32 * (nkb - 1);
+    const bool rows_safe = yuv_last + (size_t)(src.y0 + y) * src.row_stride + (size_t)yuv_xlast + 40 <= src.readable &&
+                           yuv_last + (size_t)max(yuv.u_off, yuv.v_off) + yuv_crow + (size_t)(PX == 20 ? yuv_xlast : yuv_xlast >> 1) + 40 <= src.readable;
+#else
     const bool rows_safe = (size_t)min(grp * 32 + 31, nframes - 1) * src.frame_stride + (size_t)(src.y0 + y) * src.row_stride +
                            (size_t)(src.x0 + 32 * (nkb - 1)) * PB + WIN <= src.readable;
+#endif
     u32x4m* out = (u32x4m*)(Lg + ((size_t)grp * rows_pad + y) * (size_t)nkb * 1024);
     for (int kc = 0; kc < nkb; kc += 8) {
         const int kb = kc + kl;
@@ -27,6 +42,88 @@
             const uint8_t* prow = src.base + (size_t)f * src.frame_stride + (size_t)(src.y0 + y) * src.row_stride;
             const int xbeg = kb * 32;
             const int npx = min(32, src.cols - xbeg);  // < 32 only in the last block: masked below, not branched on
+#ifdef MELF_YUV_BODY
+            if (PX == 20 || PX == 21) {
+                constexpr bool NV12 = PX == 20;
+                const int xs = (src.x0 + xbeg) & ~1;   // the window's first pixel (even)
+                const size_t fo = (size_t)f * src.frame_stride;
+                const size_t yo = fo + (size_t)(src.y0 + y) * src.row_stride + (size_t)xs;
+                const size_t uo = fo + (size_t)yuv.u_off + yuv_crow + (size_t)(NV12 ? xs : xs >> 1);
+                const size_t vo = fo + (size_t)yuv.v_off + yuv_crow + (size_t)(xs >> 1);   // (I420 only)
+                // 10 aligned dwords cover 34 bytes (+ 3 of misalignment), 6 the 17 bytes of an I420 chroma row's share; the windows
+                // may reach past the crop (never used: masked) but must stay inside the caller's buffer
+                if (rows_safe || (yo + 40 <= src.readable && uo + (NV12 ? 40 : 24) <= src.readable && (NV12 || vo + 24 <= src.readable))) {
+                    uint32_t ya[9], ua[9], va[5];
+                    {
+                        const uint8_t* p = src.base + yo;
+                        const uint32_t mis = (uint32_t)((size_t)p & 3);
+                        const uint32_t* q = (const uint32_t*)(p - mis);
+                        uint32_t d[10];
+#pragma unroll
+                        for (int i = 0; i < 10; ++i) d[i] = q[i];
+#pragma unroll
+                        for (int i = 0; i < 9; ++i) ya[i] = __builtin_amdgcn_alignbit(d[i + 1], d[i], mis * 8u);
+                    }
+                    if (NV12) {
+                        const uint8_t* p = src.base + uo;
+                        const uint32_t mis = (uint32_t)((size_t)p & 3);
+                        const uint32_t* q = (const uint32_t*)(p - mis);
+                        uint32_t d[10];
+#pragma unroll
+                        for (int i = 0; i < 10; ++i) d[i] = q[i];
+#pragma unroll
+                        for (int i = 0; i < 9; ++i) ua[i] = __builtin_amdgcn_alignbit(d[i + 1], d[i], mis * 8u);
+                    } else {
+                        const uint8_t* pu = src.base + uo;
+                        const uint8_t* pv = src.base + vo;
+                        const uint32_t misu = (uint32_t)((size_t)pu & 3), misv = (uint32_t)((size_t)pv & 3);
+                        const uint32_t* qu = (const uint32_t*)(pu - misu);
+                        const uint32_t* qv = (const uint32_t*)(pv - misv);
+                        uint32_t du[6], dv[6];
+#pragma unroll
+                        for (int i = 0; i < 6; ++i) { du[i] = qu[i]; dv[i] = qv[i]; }
+#pragma unroll
+                        for (int i = 0; i < 5; ++i) {
+                            ua[i] = __builtin_amdgcn_alignbit(du[i + 1], du[i], misu * 8u);
+                            va[i] = __builtin_amdgcn_alignbit(dv[i + 1], dv[i], misv * 8u);
+                        }
+                    }
+                    uint32_t wl[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // L' of the window's 34 pixels
+#pragma unroll
+                    for (int j = 0; j < 17; ++j) {
+                        int U, V;
+                        if (NV12) {
+                            U = (int)((ua[j >> 1] >> ((j & 1) * 16)) & 255u);
+                            V = (int)((ua[j >> 1] >> ((j & 1) * 16 + 8)) & 255u);
+                        } else {
+                            U = (int)((ua[j >> 2] >> ((j & 3) * 8)) & 255u);
+                            V = (int)((va[j >> 2] >> ((j & 3) * 8)) & 255u);
+                        }
+                        const YuvChroma c = yuv_chroma(U, V);
+                        const int cmax = yuv_cmax(c), cmin = yuv_cmin(c);
+#pragma unroll
+                        for (int q2 = 0; q2 < 2; ++q2) {
+                            const int k = 2 * j + q2;
+                            const int L = yuv_lightness((int)((ya[k >> 2] >> ((k & 3) * 8)) & 255u), cmax, cmin);
+                            wl[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
+                        }
+                    }
+                    // the lane's 32 pixels start at byte xodd of the window
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) w[i] = __builtin_amdgcn_alignbit(wl[i + 1], wl[i], (uint32_t)xodd * 8u);
+                } else {  // last bytes of the frame buffer: byte loads
+                    const uint8_t* py = src.base + fo + (size_t)(src.y0 + y) * src.row_stride + (size_t)(src.x0 + xbeg);
+                    const uint8_t* pu = src.base + fo + (size_t)yuv.u_off + yuv_crow;
+                    const uint8_t* pv = src.base + fo + (size_t)yuv.v_off + yuv_crow;
+                    for (int k = 0; k < npx; ++k) {
+                        const int cx = (src.x0 + xbeg + k) >> 1;
+                        const YuvChroma c = yuv_chroma(pu[NV12 ? 2 * cx : cx], pv[NV12 ? 2 * cx : cx]);
+                        const int L = yuv_lightness(py[k], yuv_cmax(c), yuv_cmin(c));
+                        w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
+                    }
+                }
+            } else
+#endif
             if (PX == 3) {
                 const size_t o = (size_t)(src.x0 + xbeg) * 3;
                 const uint8_t* p = prow + o;

@@ -245,6 +245,22 @@ int melf_stream_probe_dev(melf_ctx* ctx, const void* d_in, size_t in_bytes, void
  * pixels with the exact float path; results are identical either way. */
 int melf_ctx_fused_table_ties(const melf_ctx* ctx, int* count);
 
+/* Which kernel body the fused stage (melf_hls_inrange_close*) runs for this context's needle bounds, and the three
+ * numbers the choice was made from.  Builds the tables on first use, like melf_ctx_fused_table_ties.  Every output
+ * pointer may be NULL.
+ *   variant         0 / 1 / 2: one hue sector (maximum r / g / b), bit tables; 3: any sectors; 4: any sectors, rounding ties
+ *                   re-evaluated with the float path; 6 / 7 / 8: one hue sector r / g / b, interval tables.  It is what the
+ *                   table kernel k_fused_mask_lut is instantiated with AFTER MELF_FUSED_VARIANT has been applied.
+ *   active_sectors  bit c set: hue sector c (0 = r, 1 = g, 2 = b) has an in-range table entry
+ *   noniv[c]        rows of sector c's tables whose set bits are not one contiguous run (0: interval tables possible)
+ *   last_launch     what this context's most recent fused-mask launch ran: [0] the variant, or -1 for the float-path
+ *                   kernel k_fused_mask (W % 16 != 0, a buffer that is not 16-byte aligned, MELF_FORCE_GENERIC_MASK=1),
+ *                   or -2 if nothing has been launched yet; [1] the work-queue slot of that launch, -1 when its segments
+ *                   were split statically over the workgroups.  A call of more frames than one launch takes reports its last
+ *                   piece.  The two values are plain fields written by every launch, without synchronisation: they mean
+ *                   something only right after the caller's own launch, with no other thread launching on the context. */
+int melf_ctx_fused_variant(const melf_ctx* ctx, int* variant, int* active_sectors, int noniv[3], int last_launch[2]);
+
 /* match_template (meterelf/_utils.py:91-97): TM_CCOEFF of n single-channel u8
  * images (rows x cols, packed) against the context's template + minMaxLoc.
  * result_map (optional) receives n*(rows-th+1)*(cols-tw+1) float32. */

@@ -105,7 +105,7 @@ EXPORTS = [
     'melf_ctx_params', 'melf_ctx_sync', 'melf_ctx_get_masks', 'melf_process_batch', 'melf_process_batch_dev', 'melf_process_stream_dev',
     'melf_process_frames', 'melf_process_frames_dev', 'melf_process_yuv', 'melf_process_yuv_dev', 'melf_yuv_to_bgr',
     'melf_bgr2hls', 'melf_hls_inrange_close', 'melf_hls_inrange_close_dev', 'melf_match_ccoeff',
-    'melf_read_dials', 'melf_aligned_average', 'melf_inrange', 'melf_ctx_fused_table_ties', 'melf_ctx_set_frames_resident', 'melf_ctx_last_match', 'melf_match_layout_query', 'melf_match_gen_plan_query', 'melf_ctx_set_profiling', 'melf_ctx_timings', 'melf_kernel_name',
+    'melf_read_dials', 'melf_aligned_average', 'melf_inrange', 'melf_ctx_fused_table_ties', 'melf_ctx_fused_variant', 'melf_ctx_set_frames_resident', 'melf_ctx_last_match', 'melf_match_layout_query', 'melf_match_gen_plan_query', 'melf_ctx_set_profiling', 'melf_ctx_timings', 'melf_kernel_name',
     'melf_jpeg_probe', 'melf_jpeg_probe_batch', 'melf_jpeg_decode_batch', 'melf_jpeg_clean_segment', 'melf_jpeg_process_batch',
     'melf_jpeg_process_files', 'melf_jpeg_process_files_begin', 'melf_jpeg_process_files_end', 'melf_jpeg_files_in_flight_max', 'melf_ctx_files_stats', 'melf_files_open_probe',
 ]
@@ -158,6 +158,7 @@ def lib():
     L.melf_aligned_average.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp, C.c_int, C.c_int, vp]
     L.melf_inrange.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp]
     L.melf_ctx_fused_table_ties.argtypes = [vp, C.POINTER(C.c_int)]
+    L.melf_ctx_fused_variant.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.melf_ctx_set_profiling.argtypes = [vp, C.c_int]
     L.melf_ctx_last_match.argtypes = [vp, C.POINTER(MelfMatchInfo)]
     L.melf_match_layout_query.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(MelfMatchInfo)]
@@ -707,6 +708,15 @@ class Context:
         n = C.c_int(0)
         check(self._L.melf_ctx_fused_table_ties(self._h, C.byref(n)))
         return n.value
+
+    def fused_variant(self):
+        """Which fused-mask kernel body this context's needle bounds select, from what, and what the last launch ran
+        (include/meterelf_hip.h, melf_ctx_fused_variant): last_body -1 = the float-path kernel, -2 = no launch yet;
+        last_queue_slot -1 = static split."""
+        (v, a) = (C.c_int(0), C.c_int(0))
+        (noniv, last) = ((C.c_int * 3)(), (C.c_int * 2)())
+        check(self._L.melf_ctx_fused_variant(self._h, C.byref(v), C.byref(a), noniv, last))
+        return dict(variant=v.value, active_sectors=a.value, noniv=tuple(noniv), last_body=last[0], last_queue_slot=last[1])
 
     # --- measurement ---
     def jpeg_decode(self, files, H, W):

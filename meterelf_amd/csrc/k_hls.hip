@@ -166,6 +166,9 @@ __global__ __launch_bounds__(256) void k_fused_mask(const uint8_t* __restrict__ 
 // an out-of-range H was seen (2 bits).  01 = in, 10 = out, 11 = depends on the
 // triple: the main kernel then re-evaluates that pixel with the exact float path.
 // Entry index = case * 65536 + diff^2 + diff + num  (sum_{d<diff}(2d+1) = diff^2).
+// (A census over all 2^24 triples has since shown that the exception never happens: H is a function of the entry alone, no entry
+// is ever 11 for any bounds or hue shift, and the tie variant is reached only when forced -- DESIGN.md section 4, "Which of the
+// nine fused-mask bodies runs"; tests/test_fused_census.py.)
 // ---------------------------------------------------------------------------
 constexpr int HUE2_DWORDS = 3 * 65536 * 2 / 32;  // 12288 (48 KiB): 2 bits per entry (seen in / seen out)
 constexpr int LS_DWORDS = 65536 / 32;            // 2048  (8 KiB)
@@ -772,8 +775,9 @@ bool fused_mask_lut_ok(const void* d_frames, const void* d_masks, int H, int W)
 static thread_local hipEvent_t g_fused_ev_start = nullptr, g_fused_ev_stop = nullptr;
 void fused_mask_timing_events(hipEvent_t start, hipEvent_t stop) { g_fused_ev_start = start; g_fused_ev_stop = stop; }
 
+// Returns the work-queue slot the launch took, -1 for the static split.
 template <int V, int T, int PF, int WPS>
-static void launch_lut_t(const uint8_t* d_frames, int n, int H, int W, int hue_shift, const Bounds& B,
+static int launch_lut_t(const uint8_t* d_frames, int n, int H, int W, int hue_shift, const Bounds& B,
                          uint32_t* d_tables, uint8_t* d_masks, hipStream_t stream)
 {
     const int G16 = W >> 4, wpr = (W + 31) >> 5;
@@ -799,6 +803,7 @@ static void launch_lut_t(const uint8_t* d_frames, int n, int H, int W, int hue_s
     // workgroup) measure the same either way and keep the static split.
     constexpr bool queue_shape = PF == 1 && T == 1024;
     uint32_t* wq = nullptr;
+    int wq_slot = -1;
     if (queue_shape) {
         // the fewest passes that make a segment of >= 64 KB of pixels with the 4 halo rows at most a quarter of its own rows
         // (1080p: 3 passes = 20 rows, 115 KB; 640 x 480: 2 passes = 46 rows, 88 KB -- measured best of P = 2 .. 5 for both);
@@ -821,6 +826,7 @@ static void launch_lut_t(const uint8_t* d_frames, int n, int H, int W, int hue_s
             seg_rows = dr;
             segs = ds;
             wq = d_tables + FUSED_TABLE_DWORDS + 16 * qslot;
+            wq_slot = qslot;
         }
     }
     const long total = (long)n * segs;
@@ -845,12 +851,13 @@ static void launch_lut_t(const uint8_t* d_frames, int n, int H, int W, int hue_s
             hipExtLaunchKernelGGL((k_fused_mask_lut<V, T, PF, WPS, 1>), dim3(grid), dim3(T), shmem, stream, g_fused_ev_start, g_fused_ev_stop, 0, d_frames,
                                   n, H, W, hue_shift, B, d_tables, d_masks, segs, seg_rows, NB, wq);
             g_fused_ev_start = g_fused_ev_stop = nullptr;
-            return;
+            return wq_slot;
         }
     }
     hipExtLaunchKernelGGL((k_fused_mask_lut<V, T, PF, WPS>), dim3(grid), dim3(T), shmem, stream, g_fused_ev_start, g_fused_ev_stop, 0, d_frames,
                           n, H, W, hue_shift, B, d_tables, d_masks, segs, seg_rows, NB, (uint32_t*)nullptr);
     g_fused_ev_start = g_fused_ev_stop = nullptr;
+    return -1;
 }
 
 // ONE launch shape per variant (what production runs and the parity tests cover):
@@ -861,31 +868,32 @@ static void launch_lut_t(const uint8_t* d_frames, int n, int H, int W, int hue_s
 //     launch against 0.100 / 0.110 for 512 threads x 6 waves per SIMD, which spilled);
 //   generic with tie re-evaluation (4): 512 threads, no prefetch (the tie path needs more than 80 registers).
 template <int V>
-static void launch_lut_v(const uint8_t* d_frames, int n, int H, int W, int hue_shift, const Bounds& B,
+static int launch_lut_v(const uint8_t* d_frames, int n, int H, int W, int hue_shift, const Bounds& B,
                          uint32_t* d_tables, uint8_t* d_masks, hipStream_t stream)
 {
-    if constexpr (V >= 6) launch_lut_t<V, 1024, 1, 8>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream);
-    else if constexpr (V == 4) launch_lut_t<V, 512, 0, 4>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream);
-    else launch_lut_t<V, 1024, 1, 4>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream);
+    if constexpr (V >= 6) return launch_lut_t<V, 1024, 1, 8>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream);
+    else if constexpr (V == 4) return launch_lut_t<V, 512, 0, 4>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream);
+    else return launch_lut_t<V, 1024, 1, 4>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream);
 }
 
 // variant: 0/1/2 single sector r/g/b (bit tables), 3 generic, 4 generic with tie re-evaluation,
 //          6/7/8 single sector r/g/b with interval tables
-void launch_fused_mask_lut(const uint8_t* d_frames, int n, int H, int W, int hue_shift, const int lo[3],
+// returns the launch's work-queue slot, -1 for the static split
+int launch_fused_mask_lut(const uint8_t* d_frames, int n, int H, int W, int hue_shift, const int lo[3],
                            const int hi[3], uint32_t* d_tables, int variant, uint8_t* d_masks,
                            hipStream_t stream)
 {
     Bounds B;
     for (int c = 0; c < 3; ++c) { B.lo[c] = lo[c]; B.hi[c] = hi[c]; }
     switch (variant) {
-        case 0: launch_lut_v<0>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream); break;
-        case 1: launch_lut_v<1>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream); break;
-        case 2: launch_lut_v<2>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream); break;
-        case 3: launch_lut_v<3>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream); break;
-        case 6: launch_lut_v<6>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream); break;
-        case 7: launch_lut_v<7>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream); break;
-        case 8: launch_lut_v<8>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream); break;
-        default: launch_lut_v<4>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream); break;
+        case 0: return launch_lut_v<0>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream);
+        case 1: return launch_lut_v<1>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream);
+        case 2: return launch_lut_v<2>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream);
+        case 3: return launch_lut_v<3>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream);
+        case 6: return launch_lut_v<6>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream);
+        case 7: return launch_lut_v<7>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream);
+        case 8: return launch_lut_v<8>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream);
+        default: return launch_lut_v<4>(d_frames, n, H, W, hue_shift, B, d_tables, d_masks, stream);
     }
 }
 

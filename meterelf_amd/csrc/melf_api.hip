@@ -255,6 +255,9 @@ struct melf_ctx {
     int fused_ambiguous = 0;             // hue-table entries whose answer depends on float32 rounding of the triple
     int fused_active_sectors = 0;        // bit c: hue sector c (max = r/g/b) has in-range entries
     int fused_variant = 3;
+    int fused_noniv[3] = {0, 0, 0};      // per hue sector: table rows whose set bits are not one contiguous run
+    int fused_last_body = -2;            // the most recent fused-mask launch: variant, -1 = k_fused_mask (float path), -2 = none yet
+    int fused_last_slot = -1;            // ... and its work-queue slot, -1 = static split
     hipStream_t stream = nullptr;
     // workspaces (grown on demand)
     melf_result* d_results = nullptr;
@@ -566,10 +569,12 @@ static int ensure_fused_tables(melf_ctx* c)
     }
     c->fused_ambiguous = (int)namb;
     c->fused_active_sectors = (int)active;
+    for (int k = 0; k < 3; ++k) c->fused_noniv[k] = (int)noniv[k];
     // kernel variant: ties -> 4; exactly one hue sector can be in range -> 0/1/2; otherwise 3
     c->fused_variant = namb > 0 ? 4 : (active == 1 ? 0 : (active == 2 ? 1 : (active == 4 ? 2 : 3)));
     if (c->fused_variant < 3 && noniv[c->fused_variant] == 0) c->fused_variant += 6;  // single sector, every row one contiguous run: interval tables
-    if (const char* ev = getenv("MELF_FUSED_VARIANT")) {  // tests: "generic" = 3, "ties" = 4
+    if (const char* ev = getenv("MELF_FUSED_VARIANT")) {  // tests: "generic" = 3, "ties" = 4, "bits" = 6 / 7 / 8 -> 0 / 1 / 2 (by data,
+                                                          // 4 and 0 / 1 / 2 are never chosen: DESIGN.md section 4, "Which of the nine ...")
         if (!strcmp(ev, "generic") && namb == 0) c->fused_variant = 3;
         if (!strcmp(ev, "bits") && c->fused_variant >= 6) c->fused_variant -= 6;  // single-sector bit tables
         if (!strcmp(ev, "ties")) c->fused_variant = 4;
@@ -834,6 +839,19 @@ extern "C" int melf_ctx_fused_table_ties(const melf_ctx* c_, int* count)
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = ensure_fused_tables(c)) return rc;
     *count = c->fused_ambiguous;
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_ctx_fused_variant(const melf_ctx* c_, int* variant, int* active_sectors, int noniv[3], int last_launch[2])
+{
+    if (!c_) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    melf_ctx* c = const_cast<melf_ctx*>(c_);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ensure_fused_tables(c)) return rc;
+    if (variant) *variant = c->fused_variant;
+    if (active_sectors) *active_sectors = c->fused_active_sectors;
+    if (noniv) for (int k = 0; k < 3; ++k) noniv[k] = c->fused_noniv[k];
+    if (last_launch) { last_launch[0] = c->fused_last_body; last_launch[1] = c->fused_last_slot; }
     return MELF_SUCCESS;
 }
 
@@ -1606,12 +1624,15 @@ extern "C" int melf_hls_inrange_close_dev(melf_ctx* c, const void* d_frames, int
                 HIP_TRY(hipEventCreateWithFlags(&ev.stop, hipEventDisableSystemFence));
                 fused_mask_timing_events(ev.start, ev.stop);
             }
-            launch_fused_mask_lut(fin, m, H, W, c->P.hue_shift, c->P.needle_lo, c->P.needle_hi, c->d_fused_tables,
-                                  c->fused_variant, fout, st);
+            c->fused_last_slot = launch_fused_mask_lut(fin, m, H, W, c->P.hue_shift, c->P.needle_lo, c->P.needle_hi, c->d_fused_tables,
+                                                       c->fused_variant, fout, st);
+            c->fused_last_body = c->fused_variant;
             if (ev.start) c->events.push_back(ev);
         } else {
             KernelTimer t(c, MELF_K_FUSED_MASK, st);
             launch_fused_mask(fin, m, H, W, c->P.hue_shift, c->P.needle_lo, c->P.needle_hi, fout, st);
+            c->fused_last_body = -1;
+            c->fused_last_slot = -1;
         }
     }
     HIP_TRY(hipGetLastError());

@@ -161,8 +161,10 @@ def test_fused_mask_other_kernel_variants(env, monkeypatch, variant):
     try:
         p = reader.ctx.params
         assert reader.ctx.fused_table_ties() == 0
+        assert reader.ctx.fused_variant()['variant'] == {'generic': 3, 'ties': 4}[variant]
         frames = _blobby(np.random.default_rng(4), 2, 96, 160)
         got = reader.ctx.hls_inrange_close(frames)
+        assert reader.ctx.fused_variant()['last_body'] == {'generic': 3, 'ties': 4}[variant]
         for f in range(2):
             assert np.array_equal(got[f], po.hls_inrange_close(frames[f], p.hue_shift, list(p.needle_lo), list(p.needle_hi)))
     finally:
@@ -194,6 +196,11 @@ def test_fused_mask_other_bounds(env, tmp_path, needle):
     try:
         p = reader.ctx.params
         (lo, hi) = (list(p.needle_lo), list(p.needle_hi))
+        # the variant the CPU census predicts for these bounds (tests/fused_census.py)
+        from tests import fused_census as fc
+        (census,) = [b for b in fc.BOUNDS.values() if b['needle'] == needle]
+        assert (tuple(lo), tuple(hi)) == (census['lo'], census['hi'])
+        assert reader.ctx.fused_variant()['variant'] == census['variant']
         rng = np.random.default_rng(needle['h'])
         frames = np.concatenate([rng.integers(0, 256, size=(2, 64, 256, 3), dtype=np.uint8), _blobby(rng, 1, 64, 256)])
         got = reader.ctx.hls_inrange_close(frames)

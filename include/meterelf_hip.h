@@ -156,7 +156,8 @@ int melf_process_batch_dev(melf_ctx* ctx, const void* d_frames, int n, int H, in
  * a 4-byte aligned base, row_pitch and frame_stride; the 3-byte formats take any alignment.  An unknown format, a pitch
  * or stride too small, a misaligned 4-byte layout or a NULL descriptor return MELF_ERR_INVALID before anything runs.
  * melf_process_stream_dev, the fused full-frame mask (melf_hls_inrange_close*), melf_aligned_average and the JPEG entry
- * points take packed BGR only; YUV 4:2:0 frames have their own descriptor and entry points (melf_process_yuv*, below). */
+ * points take packed BGR only; YUV 4:2:0 frames and packed YUV 4:2:2 frames have their own descriptors and entry points
+ * (melf_process_yuv*, melf_process_yuv422*, below). */
 enum { MELF_PIX_BGR = 0, MELF_PIX_RGB = 1, MELF_PIX_BGRA = 2, MELF_PIX_RGBA = 3 };
 typedef struct melf_frames {
     int32_t pixel_format;  /* MELF_PIX_*; the 4th byte of BGRA / RGBA is ignored                          */
@@ -208,6 +209,38 @@ int melf_process_yuv_dev(melf_ctx* ctx, const void* d_frames, const melf_yuv_fra
                          void* stream);
 /* Stage entry point (parity tests, and a debug view for callers): the conversion alone, n packed H x W x 3 BGR frames out. */
 int melf_yuv_to_bgr(melf_ctx* ctx, const void* frames_host, const melf_yuv_frames* f, uint8_t* bgr_out_host);
+
+/* ---- the same path for packed YUV 4:2:2 frames: YUYV / YUY2 (UVC webcams, V4L2), UYVY (SDI / HDMI capture cards), YVYU ----
+ * The records are byte-identical to melf_process_batch(_dev) on the packed BGR frame that the conversion makes of each frame
+ * (cv2.cvtColor(COLOR_YUV2BGR_YUY2 / _UYVY / _YVYU): the integer formulas and constants above, BT.601, limited range), which
+ * replaces the BGR copy of every frame such a caller had to write: that frame is never formed, the kernels read the
+ * macropixels in place, and only the meter_rect crop of them.
+ *     chroma: the two pixels of a macropixel share its U and V; no interpolation, no vertical subsampling
+ * Frame f starts at frames + f * frame_stride, its row y at + y * row_pitch: W / 2 macropixels of 4 bytes, two pixels each, in
+ * the byte order of the format.  Pixel (x, y) has its Y in the macropixel at + 4 * (x >> 1) and uses that macropixel's U and V.
+ * The base pointer, row_pitch and frame_stride must be 4-byte aligned (as for the 4-byte RGB formats): a macropixel is then one
+ * aligned dword.  The buffer must hold (n - 1) * frame_stride + (H - 1) * row_pitch + 2 * W bytes, and nothing behind that: no
+ * load of the kernels reaches past it.  An odd W, a pitch or stride too small, a misaligned base, pitch or stride, an unknown
+ * format or matrix, H or W <= 0, n < 0, a NULL descriptor or NULL frames return MELF_ERR_INVALID (melf_last_error says which)
+ * before anything is launched or copied; n == 0 passes. */
+enum { MELF_YUV422_YUYV = 0, MELF_YUV422_UYVY = 1, MELF_YUV422_YVYU = 2 };   /* bytes of a macropixel: Y0 U Y1 V / U Y0 V Y1 / Y0 V Y1 U */
+typedef struct melf_yuv422_frames {
+    int32_t format, matrix;                     /* MELF_YUV422_*; matrix: MELF_YUV_BT601_LIMITED only     */
+    int32_t n, H, W;                            /* W even, H any                                          */
+    int32_t reserved;
+    int64_t row_pitch;                          /* bytes between rows, >= 2 * W                           */
+    int64_t frame_stride;                       /* bytes between frames                                   */
+} melf_yuv422_frames;
+/* Host frames, as melf_process_yuv: only the crop crosses PCIe, packed into the pinned staging buffers as a small frame of the
+ * same format (its x origin rounded down and its far corner up to a whole macropixel, every row of the crop: no vertical
+ * rounding); no byte is converted or reordered on the CPU. */
+int melf_process_yuv422(melf_ctx* ctx, const void* frames_host, const melf_yuv422_frames* f, melf_result* out_host);
+/* Frames in HBM, exactly as melf_process_yuv_dev: the same lanes, melf_ctx_set_frames_resident, caller streams, and NULL
+ * d_results / out_host semantics. */
+int melf_process_yuv422_dev(melf_ctx* ctx, const void* d_frames, const melf_yuv422_frames* f, void* d_results, melf_result* out_host,
+                            void* stream);
+/* Stage entry point (parity tests, and a debug view for callers): the conversion alone, n packed H x W x 3 BGR frames out. */
+int melf_yuv422_to_bgr(melf_ctx* ctx, const void* frames_host, const melf_yuv422_frames* f, uint8_t* bgr_out_host);
 
 /* ---- stage entry points (parity tests and roofline runs) ----------------- */
 

@@ -199,6 +199,34 @@ class MeterReader:
         self.ctx.process_yuv_dev(v.ptr, desc, d_results_ptr=out.data_ptr(), want_host=False, stream=stream.cuda_stream)
         return out
 
+    def read_yuv422_frames(self, frames, pixel_format: str = 'yuyv', out=None):
+        """Packed YUV 4:2:2 frames (UVC / V4L2 YUYV, capture-card UYVY, YVYU) -> records, equal to read_frames() of the packed BGR
+        frames that the BT.601 limited-range conversion of include/meterelf_hip.h makes of them (melf_process_yuv422*); the
+        macropixels are read in place, no conversion pass.  frames: the conventional (N, H, W, 2) uint8 array, a numpy array /
+        torch CPU tensor (host path) or a torch tensor on this reader's GPU (enqueued on torch.cuda.current_stream); pixel_format
+        'yuyv' (or 'yuy2'), 'uyvy' or 'yvyu' (_hip.yuv422_frames_view says which layouts are read in place).  out: a uint8 device
+        tensor (N, RESULT_DTYPE.itemsize) on the same GPU that receives the records without synchronising the stream (device
+        frames only); returns it.  Otherwise returns the records."""
+        v = _hip.yuv422_frames_view(frames, pixel_format)
+        desc = v.descriptor()
+        if not v.on_device:
+            if out is not None:
+                raise ValueError('out= takes the records of device frames only')
+            return self.ctx.process_yuv422(v.ptr, desc)
+        import torch
+        if v.device != self.device:
+            raise ValueError('frames are on cuda:%s, the reader on cuda:%d' % (v.device, self.device))
+        stream = torch.cuda.current_stream(self.device)
+        if out is None:
+            return self.ctx.process_yuv422_dev(v.ptr, desc, stream=stream.cuda_stream)
+        if (not _hip._is_torch(out) or out.dtype != torch.uint8 or out.device != v.array.device or not out.is_contiguous()
+                or tuple(out.shape) != (v.n, _hip.RESULT_DTYPE.itemsize)):
+            raise ValueError('out must be a contiguous uint8 tensor of shape (%d, %d) on %s' % (v.n, _hip.RESULT_DTYPE.itemsize, v.array.device))
+        if v.copied:
+            v.array.record_stream(stream)   # the packed copy lives until the stream has passed the call's kernels
+        self.ctx.process_yuv422_dev(v.ptr, desc, d_results_ptr=out.data_ptr(), want_host=False, stream=stream.cuda_stream)
+        return out
+
     def read_crops(self, crops: np.ndarray) -> np.ndarray:
         """Already meter_rect-cropped images (the reference's bgr_image injection)."""
         (_n, h, w, _c) = crops.shape

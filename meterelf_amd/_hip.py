@@ -84,6 +84,17 @@ YUV_NV12, YUV_I420 = 0, 1
 YUV_BT601_LIMITED = 0
 YUV_CODES = {'nv12': YUV_NV12, 'i420': YUV_I420, 'yv12': YUV_I420}
 
+
+
+class MelfYuv422Frames(C.Structure):
+    _fields_ = [('format', C.c_int32), ('matrix', C.c_int32), ('n', C.c_int32), ('H', C.c_int32), ('W', C.c_int32),
+                ('reserved', C.c_int32), ('row_pitch', C.c_int64), ('frame_stride', C.c_int64)]
+
+
+# packed YUV 4:2:2 layouts of melf_process_yuv422* (MELF_YUV422_*): the bytes of a macropixel; 'yuy2' is YUYV's other name
+YUV422_YUYV, YUV422_UYVY, YUV422_YVYU = 0, 1, 2
+YUV422_CODES = {'yuyv': YUV422_YUYV, 'yuy2': YUV422_YUYV, 'uyvy': YUV422_UYVY, 'yvyu': YUV422_YVYU}
+
 MATCH_KERNEL_NAMES = ('dot4', 'mfma', 'gen')
 
 RESULT_DTYPE = np.dtype([('status', '<i4'), ('match_x', '<i4'), ('match_y', '<i4'), ('failed_dial', '<i4'),
@@ -104,6 +115,7 @@ EXPORTS = [
     'melf_blob_size', 'melf_blob_pack', 'melf_blob_params', 'melf_ctx_create', 'melf_ctx_create_bcast', 'melf_ctx_destroy',
     'melf_ctx_params', 'melf_ctx_sync', 'melf_ctx_get_masks', 'melf_process_batch', 'melf_process_batch_dev', 'melf_process_stream_dev',
     'melf_process_frames', 'melf_process_frames_dev', 'melf_process_yuv', 'melf_process_yuv_dev', 'melf_yuv_to_bgr',
+    'melf_process_yuv422', 'melf_process_yuv422_dev', 'melf_yuv422_to_bgr',
     'melf_bgr2hls', 'melf_hls_inrange_close', 'melf_hls_inrange_close_dev', 'melf_match_ccoeff',
     'melf_read_dials', 'melf_aligned_average', 'melf_inrange', 'melf_ctx_fused_table_ties', 'melf_ctx_fused_variant', 'melf_ctx_set_frames_resident', 'melf_ctx_last_match', 'melf_match_layout_query', 'melf_match_gen_plan_query', 'melf_ctx_set_profiling', 'melf_ctx_timings', 'melf_kernel_name',
     'melf_jpeg_probe', 'melf_jpeg_probe_batch', 'melf_jpeg_decode_batch', 'melf_jpeg_clean_segment', 'melf_jpeg_process_batch',
@@ -147,6 +159,9 @@ def lib():
     L.melf_process_yuv.argtypes = [vp, vp, C.POINTER(MelfYuvFrames), vp]
     L.melf_process_yuv_dev.argtypes = [vp, vp, C.POINTER(MelfYuvFrames), vp, vp, vp]
     L.melf_yuv_to_bgr.argtypes = [vp, vp, C.POINTER(MelfYuvFrames), vp]
+    L.melf_process_yuv422.argtypes = [vp, vp, C.POINTER(MelfYuv422Frames), vp]
+    L.melf_process_yuv422_dev.argtypes = [vp, vp, C.POINTER(MelfYuv422Frames), vp, vp, vp]
+    L.melf_yuv422_to_bgr.argtypes = [vp, vp, C.POINTER(MelfYuv422Frames), vp]
     L.melf_process_stream_dev.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, vp]
     L.melf_bgr2hls.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp]
     L.melf_hls_inrange_close.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
@@ -381,6 +396,78 @@ def yuv_frames_view(frames, pixel_format='nv12'):
     extent = (n - 1) * fs + last if n else 0
     return YuvFramesView(int(ptr), on_device, device, code, n, H, W, int(rp), int(c_pitch), int(u_off), int(v_off), int(fs), int(extent),
                          not ok, frames)
+
+
+class Yuv422FramesView(NamedTuple):
+    """How the kernels read a batch of packed YUV 4:2:2 frames in place (yuv422_frames_view)."""
+    ptr: int            # address of frame 0's first macropixel
+    on_device: bool     # True: a torch tensor on a GPU (ptr is a device address)
+    device: Optional[int]
+    format: int         # YUV422_YUYV / YUV422_UYVY / YUV422_YVYU
+    n: int
+    H: int
+    W: int
+    row_pitch: int      # bytes between rows
+    frame_stride: int   # bytes between frames
+    extent: int         # bytes read from ptr: (n - 1) * frame_stride + (H - 1) * row_pitch + 2 * W
+    copied: bool        # the layout could not be described and the frames were copied once to a packed array
+    array: object       # what ptr points into (the caller's array, or the copy): keep it alive while the call runs
+
+    def descriptor(self):
+        return MelfYuv422Frames(self.format, YUV_BT601_LIMITED, self.n, self.H, self.W, 0, self.row_pitch, self.frame_stride)
+
+
+def yuv422_frames_view(frames, pixel_format='yuyv'):
+    """Describes the conventional (N, H, W, 2) uint8 array of packed YUV 4:2:2 frames (numpy array or torch tensor) as
+    melf_process_yuv422* read it: the two bytes of pixel x are bytes 2 x, 2 x + 1 of its row, 'yuyv' (or 'yuy2'): Y0 U Y1 V per
+    pair of pixels, 'uyvy': U Y0 V Y1, 'yvyu': Y0 V Y1 U.  The row stride and the frame stride are honoured in place
+    (frames[:, :, :w], frames[::2], frames[a:b]).  A layout the descriptor cannot express -- an element or pixel stride other
+    than 1 / 2, a base, row stride or frame stride that is not a multiple of 4, negative strides -- is copied once to a packed
+    array (Yuv422FramesView.copied).  Not uint8, not four-dimensional, a last dimension other than 2, an odd or zero W, a zero
+    H, or an unknown format name: ValueError."""
+    is_torch = _is_torch(frames)
+    if is_torch:
+        if str(frames.dtype) != 'torch.uint8':
+            raise ValueError('frames must be uint8, not %s' % frames.dtype)
+        shape = tuple(frames.shape)
+        strides = tuple(frames.stride())          # elements = bytes for uint8
+        ptr = frames.data_ptr()
+        on_device = frames.device.type == 'cuda'
+        device = frames.device.index if on_device else None
+    else:
+        frames = np.asarray(frames)
+        if frames.dtype != np.uint8:
+            raise ValueError('frames must be uint8, not %s' % frames.dtype)
+        shape = frames.shape
+        strides = frames.strides
+        ptr = frames.ctypes.data
+        (on_device, device) = (False, None)
+    fmt = str(pixel_format).lower()
+    if fmt not in YUV422_CODES:
+        raise ValueError('pixel_format %r is not a packed YUV 4:2:2 layout (yuyv / yuy2, uyvy, yvyu)' % (pixel_format,))
+    if len(shape) != 4 or shape[3] != 2 or shape[1] == 0 or shape[2] == 0 or shape[2] % 2 != 0:
+        raise ValueError('packed YUV 4:2:2 frames must be (N, H, W, 2) with an even W, not %s' % (shape,))
+    code = YUV422_CODES[fmt]
+    (n, H, W, _two) = shape
+    (fs, rp, ps, es) = strides
+    # strides of dimensions of size 1 are never stepped over: make them what a packed array has
+    if H == 1:
+        rp = W * 2
+    if n == 1:
+        fs = (H - 1) * rp + W * 2 if rp > 0 else 0
+        fs += -fs % 4
+    ok = (es == 1 and ps == 2 and rp >= W * 2 and fs >= (H - 1) * rp + W * 2 and rp <= 2 ** 31 - 1 and (ptr | rp | fs) % 4 == 0)
+    if not ok:
+        # a fresh allocation (aligned) even where the array is contiguous already (a misaligned base)
+        if is_torch:
+            import torch
+            frames = frames.clone(memory_format=torch.contiguous_format)
+        else:
+            frames = np.array(frames, order='C', copy=True)
+        (rp, fs) = (W * 2, H * W * 2)
+        ptr = frames.data_ptr() if is_torch else frames.ctypes.data
+    extent = (n - 1) * fs + (H - 1) * rp + W * 2 if n else 0
+    return Yuv422FramesView(int(ptr), on_device, device, code, n, H, W, int(rp), int(fs), int(extent), not ok, frames)
 
 
 def jpeg_probe(data):
@@ -620,6 +707,27 @@ class Context:
         """The conversion alone (melf_yuv_to_bgr): host YUV 4:2:0 frames -> (n, H, W, 3) BGR."""
         out = np.empty((desc.n, desc.H, desc.W, 3), np.uint8)
         check(self._L.melf_yuv_to_bgr(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
+        return out
+
+    def process_yuv422(self, frames_ptr, desc):
+        """Host packed YUV 4:2:2 frames (melf_process_yuv422; desc: a MelfYuv422Frames, e.g. yuv422_frames_view(...).descriptor())
+        -> records."""
+        out = np.zeros(desc.n, RESULT_DTYPE)
+        check(self._L.melf_process_yuv422(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
+        return out
+
+    def process_yuv422_dev(self, d_frames_ptr, desc, d_results_ptr=None, want_host=True, stream=None):
+        """Packed YUV 4:2:2 frames in HBM (melf_process_yuv422_dev, as process_frames_dev).  Returns records when want_host."""
+        out = np.zeros(desc.n, RESULT_DTYPE) if want_host else None
+        check(self._L.melf_process_yuv422_dev(
+            self._h, C.c_void_p(d_frames_ptr), C.byref(desc), C.c_void_p(d_results_ptr) if d_results_ptr else None,
+            _ptr(out) if want_host else None, C.c_void_p(stream) if stream else None))
+        return out
+
+    def yuv422_to_bgr(self, frames_ptr, desc):
+        """The conversion alone (melf_yuv422_to_bgr): host packed YUV 4:2:2 frames -> (n, H, W, 3) BGR."""
+        out = np.empty((desc.n, desc.H, desc.W, 3), np.uint8)
+        check(self._L.melf_yuv422_to_bgr(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
         return out
 
     # --- stages ---

@@ -306,6 +306,24 @@ __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_v
 }
 #undef MELF_YUV_BODY
 
+// Packed YUV 4:2:2 frames (melf_process_yuv422*): two pixels per aligned macropixel dword; psel: the byte permute that brings the
+// frames' order (YUYV, UYVY, YVYU) to Y0 U Y1 V, a runtime value, so that the formats share the NR instantiations.
+#define MELF_P422_BODY
+template <int NR>
+__global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_vgpr(DIALS_VGPRS))) void k_p422_needle(DialsSrc src, uint32_t psel, melf_params P,
+                                                                const DialGeom* __restrict__ geom,
+                                                                const uint64_t* __restrict__ rowmasks,
+                                                                const MatchPartial* __restrict__ partials,
+                                                                int nparts, int rw, melf_result* __restrict__ results)
+{
+    constexpr bool FROM_HLS = false;
+    constexpr int PB = 4;
+    constexpr bool RT_ORDER = false;
+    const uint32_t bsel = 0u;
+#include "k_dials_body.inc"
+}
+#undef MELF_P422_BODY
+
 void launch_dials(const DialsSrc& src, int pix, int n, const melf_params& P, const DialGeom* d_geom,
                   const uint64_t* d_rowmasks, const MatchPartial* d_partials, int nparts, int rw,
                   melf_result* d_results, hipStream_t stream, int ws_max, const YuvPlanes* yuv)
@@ -347,13 +365,26 @@ void launch_dials(const DialsSrc& src, int pix, int n, const melf_params& P, con
         case 56: MELF_YNEEDLE_LAUNCH(PL, 56); break;         \
         default: MELF_YNEEDLE_LAUNCH(PL, 64); break;         \
     }
+#define MELF_P422_NEEDLE_LAUNCH(NRV) \
+    hipLaunchKernelGGL((k_p422_needle<NRV>), grid, block, shmem, stream, src, p422_sel(pix), P, d_geom, d_rowmasks, d_partials, nparts, rw, d_results)
     const int swap_rb = pix == MELF_PIX_RGB || pix == MELF_PIX_RGBA;
-    if (pix == PIX_NV12) { MELF_YNEEDLE_NR(false) }
+    if (pix_p422(pix)) {
+        switch (nr) {
+            case 32: MELF_P422_NEEDLE_LAUNCH(32); break;
+            case 40: MELF_P422_NEEDLE_LAUNCH(40); break;
+            case 48: MELF_P422_NEEDLE_LAUNCH(48); break;
+            case 52: MELF_P422_NEEDLE_LAUNCH(52); break;
+            case 56: MELF_P422_NEEDLE_LAUNCH(56); break;
+            default: MELF_P422_NEEDLE_LAUNCH(64); break;
+        }
+    }
+    else if (pix == PIX_NV12) { MELF_YNEEDLE_NR(false) }
     else if (pix == PIX_I420) { MELF_YNEEDLE_NR(true) }
     else if (pix == PIX_PLANE) { MELF_DIALS_NR(true) }
     else if (pix == MELF_PIX_BGR) { MELF_DIALS_NR(false) }
     else if (pix == MELF_PIX_RGB) { MELF_NEEDLES_NR(3) }
     else { MELF_NEEDLES_NR(4) }
+#undef MELF_P422_NEEDLE_LAUNCH
 #undef MELF_YNEEDLE_NR
 #undef MELF_YNEEDLE_LAUNCH
 #undef MELF_NEEDLES_NR

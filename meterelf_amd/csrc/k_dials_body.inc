@@ -12,6 +12,9 @@
 // `yuv` the chroma planes.  Every load fetches Y and the chroma under it and leaves as a B G R dword (melf_device.h: yuv_bgr), which
 // is what the rest of the body sees with PB = 4: the core pixel and the exact path's column pixel by byte loads, the window's four
 // pixels per lane as one Y dword and the (at most three) chroma pairs under it, at any parity of the window's origin.
+// With MELF_P422_BODY defined instead (k_p422_needle): packed YUV 4:2:2 frames (melf_process_yuv422*), two pixels per aligned
+// macropixel dword, its byte order the runtime permute selector psel (-> Y0 U Y1 V).  A lane's four window pixels lie in two or
+// three consecutive macropixels: three dwords per lane and row, and from there on one B G R dword per pixel as above.
     [[maybe_unused]] const uint32_t csel = bsel ? 0x0c000102u : 0x0c020100u;   // pixel -> B G R in bytes 0..2 (RT_ORDER)
     auto bgr = [&](uint32_t px) -> uint32_t {
         if constexpr (RT_ORDER) return __builtin_amdgcn_perm(0u, px, csel);
@@ -103,12 +106,20 @@
         const int yv = frame[(size_t)fy * rstride + (size_t)fx];
         return yuv_bgr(yv, yuv_chroma(uplane[co], vplane[co]));
     };
+#elif defined(MELF_P422_BODY)
+    const int fx_m = src.x0 + mx, fy_m = src.y0 + my;   // the match position in the frame
+    // pixel (X, Y) of the dials crop as a B G R dword: its macropixel, one aligned dword load
+    auto yuv_px = [&](int X, int Y) -> uint32_t {
+        const int fx = fx_m + X, fy = fy_m + Y;
+        const uint32_t c = __builtin_amdgcn_perm(0u, *(const uint32_t*)(frame + (size_t)fy * rstride + (size_t)(fx >> 1) * 4), psel);
+        return yuv_bgr((int)((fx & 1 ? c >> 16 : c) & 255u), yuv_chroma((int)((c >> 8) & 255u), (int)(c >> 24)));
+    };
 #else
     const uint8_t* const origin = FROM_HLS ? frame : frame + (size_t)(src.y0 + my) * src.row_stride + (size_t)(src.x0 + mx) * PB;
 #endif
     const int coreX = G.core_x - 2 + lane % 5, coreY = G.core_y - 2 + (lane < 25 ? lane / 5 : 0);
     const bool corevalid = lane < 25 && coreX >= 0 && coreX < P.tw && coreY >= 0 && coreY < P.th;
-#ifdef MELF_YUV_BODY
+#if defined(MELF_YUV_BODY) || defined(MELF_P422_BODY)
     const uint32_t corepx = yuv_px(min(max(coreX, 0), P.tw - 1), min(max(coreY, 0), P.th - 1));
 #else
     const uint32_t corepx = bgr(load_px<PB>(origin + (size_t)min(max(coreY, 0), P.th - 1) * rstride + (size_t)min(max(coreX, 0), P.tw - 1) * PB, src.base));
@@ -161,6 +172,34 @@
         o.w = yuv_bgr(r.x >> 24, fodd ? c2 : c1);
         return o;
     };
+#elif defined(MELF_P422_BODY)
+    // 4:2:2: a lane's four pixels lie in the macropixels (fx0 >> 1) .. (fx0 + 3) >> 1, two of them (fx0 even) or three (odd).  Three
+    // aligned dwords per lane and row, from the first macropixel or, at the crop's right edge, from one further left, so that the
+    // third stays inside the row (mlim: the macropixels up to the crop's right edge; the frame's width is even, so the row holds
+    // them all).  Only an even fx0 can be moved (its third dword is the spare one); the move is undone below.
+    (void)buf_end;
+    const int mlim = (src.x0 + src.crop_cols + 1) >> 1;
+    const bool quads = wx0 >= 0 && wx0 + 4 * npiece <= P.tw && mlim >= 3;
+    const int fx0 = fx_m + wx0 + 4 * min(pc, npiece - 1);   // the lane's first pixel in the frame
+    const int mstart = min(fx0 >> 1, mlim - 3);             // first macropixel loaded
+    const bool mshifted = (fx0 >> 1) != mstart;
+    const bool fodd = fx0 & 1;
+    // the four pixels as B G R dwords from the three macropixels loaded
+    auto yuv_quad = [&](const u32x4v r) -> u32x4v {
+        const uint32_t ma = __builtin_amdgcn_perm(0u, mshifted ? r.y : r.x, psel), mb = __builtin_amdgcn_perm(0u, mshifted ? r.z : r.y, psel),
+                       mc = __builtin_amdgcn_perm(0u, r.z, psel);   // Y0 U Y1 V each
+        const YuvChroma c0 = yuv_chroma((int)((ma >> 8) & 255u), (int)(ma >> 24)), c1 = yuv_chroma((int)((mb >> 8) & 255u), (int)(mb >> 24)),
+                        c2 = yuv_chroma((int)((mc >> 8) & 255u), (int)(mc >> 24));
+        const uint32_t y4 = __builtin_amdgcn_perm(mb, ma, 0x06040200u);                  // Y of the pixels of ma, mb
+        const uint32_t yd = fodd ? __builtin_amdgcn_perm(mc, y4, 0x04030201u) : y4;      // Y of the lane's four
+        // pixel j sits on macropixel (j + fodd) >> 1
+        u32x4v o;
+        o.x = yuv_bgr((int)(yd & 255u), c0);
+        o.y = yuv_bgr((int)((yd >> 8) & 255u), fodd ? c1 : c0);
+        o.z = yuv_bgr((int)((yd >> 16) & 255u), c1);
+        o.w = yuv_bgr((int)(yd >> 24), fodd ? c2 : c1);
+        return o;
+    };
 #else
     const bool quads = !FROM_HLS && ((uintptr_t)src.base & 3) == 0 && wx0 >= 0 && wx0 + 4 * npiece <= P.tw &&
                        origin + (size_t)th1 * rstride + (size_t)(wx0 + 4 * npiece) * PB + (PB == 4 ? 0 : 4) <= buf_end;
@@ -185,6 +224,16 @@
                 __builtin_memcpy(cd, uplane + co, 8);
                 raw[g] = u32x4v{yd, cd[0], cd[1], 0u};
             }
+        }
+    }
+#elif defined(MELF_P422_BODY)
+    if (quads) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const int fy = fy_m + min(max(wy0 + min(4 * g + rg, ylast), 0), th1);
+            uint32_t md[3];
+            __builtin_memcpy(md, (const uint32_t*)(frame + (size_t)fy * (size_t)rs_u) + mstart, 12);
+            raw[g] = u32x4v{md[0], md[1], md[2], 0u};
         }
     }
 #else
@@ -235,7 +284,7 @@
 #pragma unroll
             for (int k = 0; k < 16; ++k) {
                 const int Y = min(max(wy0 + min(yc + k, ylast), 0), th1);
-#ifdef MELF_YUV_BODY
+#if defined(MELF_YUV_BODY) || defined(MELF_P422_BODY)
                 pxe[k] = yuv_px(Xc, Y);
 #else
                 pxe[k] = bgr(load_px3_row(pcol, (size_t)((int64_t)Y * rs_u)));
@@ -284,7 +333,7 @@
         if (quads) {
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
-#ifdef MELF_YUV_BODY
+#if defined(MELF_YUV_BODY) || defined(MELF_P422_BODY)
                 raw[g] = yuv_quad(raw[g]);   // from here on: one B G R pixel per dword, as for 4-byte pixels
 #endif
                 // the lane's 12 bytes: B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3  (4-byte pixels: raw[g] holds one pixel per dword)

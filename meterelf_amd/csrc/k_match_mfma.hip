@@ -94,6 +94,17 @@ __global__ __launch_bounds__(256) void k_lplane_yuv(MatchSrc src, YuvPlanes yuv,
 }
 #undef MELF_YUV_BODY
 
+// Packed YUV 4:2:2 frames (melf_process_yuv422*): two pixels per aligned macropixel dword; psel: the byte permute that brings the
+// frames' order (YUYV, UYVY, YVYU) to Y0 U Y1 V, a runtime value: one instantiation.  L straight from Y, U, V as above.
+#define MELF_P422_BODY
+__global__ __launch_bounds__(256) void k_p422_lplane(MatchSrc src, uint32_t psel, int nframes, int nkb, int rows_pad, int tw, int rwp, int pairs,
+                                                     int8_t* __restrict__ Lg, uint16_t* __restrict__ R)
+{
+    constexpr int PX = 22;
+#include "prep_lplane_body.inc"
+}
+#undef MELF_P422_BODY
+
 // ---------------------------------------------------------------------------
 // k_match_mfma
 // ---------------------------------------------------------------------------
@@ -789,9 +800,11 @@ void launch_match_prep(const MatchSrc& src, int pix, int n, int groups, int rows
         (void)hipFuncSetAttribute((const void*)k_lplane_px4, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute((const void*)k_lplane_yuv<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute((const void*)k_lplane_yuv<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_p422_lplane, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         attr_set[dev] = true;
     }
-    if (pix == PIX_NV12) hipLaunchKernelGGL((k_lplane_yuv<false>), grid, block, pre_bytes, stream, src, *yuv, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    if (pix_p422(pix)) hipLaunchKernelGGL(k_p422_lplane, grid, block, pre_bytes, stream, src, p422_sel(pix), n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    else if (pix == PIX_NV12) hipLaunchKernelGGL((k_lplane_yuv<false>), grid, block, pre_bytes, stream, src, *yuv, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else if (pix == PIX_I420) hipLaunchKernelGGL((k_lplane_yuv<true>), grid, block, pre_bytes, stream, src, *yuv, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else if (pix == PIX_PLANE) hipLaunchKernelGGL((k_prep_lplane<false>), grid, block, pre_bytes, stream, src, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else if (pix_bytes(pix) == 4) hipLaunchKernelGGL(k_lplane_px4, grid, block, pre_bytes, stream, src, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);

@@ -44,4 +44,35 @@ void launch_yuv2bgr(const uint8_t* d_src, int pix, int n, int H, int W, int y_pi
     }
 }
 
+// Packed YUV 4:2:2 -> BGR alone: the stage kernel behind melf_yuv422_to_bgr, what cv2.cvtColor(COLOR_YUV2BGR_YUY2 / _UYVY / _YVYU)
+// makes of a capture frame.  One thread per macropixel: one aligned dword in, permuted to Y0 U Y1 V by the runtime selector the
+// reading kernels (k_p422_lplane, k_p422_match, k_p422_needle) use, two B G R pixels out.  This kernel pins the fetch and the
+// arithmetic for every (Y, U, V) at both pixels of a macropixel; like k_yuv2bgr it is no hot path.
+__global__ __launch_bounds__(256) void k_p422_to_bgr(const uint8_t* __restrict__ src, int H, int W, int row_pitch, size_t frame_stride,
+                                                     uint32_t psel, uint8_t* __restrict__ dst)
+{
+    const int bx = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.z;
+    if (bx >= (W >> 1)) return;
+    for (int y = blockIdx.y; y < H; y += gridDim.y) {
+        const uint32_t m = __builtin_amdgcn_perm(0u, *(const uint32_t*)(src + (size_t)f * frame_stride + (size_t)y * (size_t)row_pitch + (size_t)bx * 4), psel);
+        const YuvChroma c = yuv_chroma((int)((m >> 8) & 255u), (int)(m >> 24));
+        const uint32_t p0 = yuv_bgr((int)(m & 255u), c), p1 = yuv_bgr((int)((m >> 16) & 255u), c);
+        uint8_t* o = dst + ((size_t)f * H + y) * (size_t)W * 3 + (size_t)bx * 6;
+        o[0] = (uint8_t)p0; o[1] = (uint8_t)(p0 >> 8); o[2] = (uint8_t)(p0 >> 16);
+        o[3] = (uint8_t)p1; o[4] = (uint8_t)(p1 >> 8); o[5] = (uint8_t)(p1 >> 16);
+    }
+}
+
+void launch_p422_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int row_pitch, size_t frame_stride, uint8_t* d_dst,
+                        hipStream_t stream)
+{
+    // at most 65 535 frames per launch (grid z); a workgroup row takes every 65 535th image row (grid y)
+    for (int f0 = 0; f0 < n; f0 += 65535) {
+        const int m = n - f0 < 65535 ? n - f0 : 65535;
+        dim3 grid(((W >> 1) + 255) / 256, H < 65535 ? H : 65535, m), block(256);
+        hipLaunchKernelGGL(k_p422_to_bgr, grid, block, 0, stream, d_src + (size_t)f0 * frame_stride, H, W, row_pitch, frame_stride,
+                           p422_sel(pix), d_dst + (size_t)f0 * H * W * 3);
+    }
+}
+
 }  // namespace melf

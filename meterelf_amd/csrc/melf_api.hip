@@ -1132,7 +1132,8 @@ static const int MAX_FRAMES_PER_LAUNCH = 32768;
 // rect (optional): {x0, y0, x1, y1} of the meter crop inside the H x W frames instead of the context's meter_rect
 // (the host-fed path uploads only the crop: its "frames" are the crops themselves); row_stride: bytes between rows
 // (0 = packed); pix: the frames' pixel layout (MELF_PIX_*, or PIX_NV12 / PIX_I420: d_frames, frame_stride and row_stride then describe
-// the Y plane, yuv the chroma planes, yuv_extent = the bytes of a frame up to the last sample of its last plane)
+// the Y plane, yuv the chroma planes, yuv_extent = the bytes of a frame up to the last sample of its last plane; or PIX_YUYV /
+// PIX_UYVY / PIX_YVYU: packed 4:2:2 frames of 2 bytes per pixel, W even, everything 4-byte aligned)
 static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
                             void* d_results, melf_result* out_host, hipStream_t st, const int* rect = nullptr, int row_stride = 0,
                             int pix = MELF_PIX_BGR, const YuvPlanes* yuv = nullptr, size_t yuv_extent = 0);
@@ -1220,7 +1221,41 @@ extern "C" int melf_process_yuv_dev(melf_ctx* c, const void* d_frames, const mel
     return batch_dev(c, d_frames, f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->y_pitch, pix, d_results, out_host, stream_, &yp, extent);
 }
 
-// melf_process_batch_dev / melf_process_frames_dev / melf_process_yuv_dev after their argument checks: the lane logic
+// The checks of a melf_yuv422_frames descriptor (melf_process_yuv422*, melf_yuv422_to_bgr); n == 0 passes.  *pix: PIX_YUYV /
+// PIX_UYVY / PIX_YVYU.
+static int check_yuv422(const void* frames, const melf_yuv422_frames* f, int* pix)
+{
+    if (!f) return fail(MELF_ERR_INVALID, "YUV 4:2:2 frame descriptor is NULL");
+    if (f->format != MELF_YUV422_YUYV && f->format != MELF_YUV422_UYVY && f->format != MELF_YUV422_YVYU)
+        return fail(MELF_ERR_INVALID, "unknown YUV 4:2:2 format");
+    if (f->matrix != MELF_YUV_BT601_LIMITED) return fail(MELF_ERR_INVALID, "unknown YUV matrix (BT.601 limited range only)");
+    if (f->n < 0 || f->H <= 0 || f->W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
+    if (f->W & 1) return fail(MELF_ERR_INVALID, "YUV 4:2:2 frames need an even width");
+    if (f->row_pitch < (int64_t)f->W * 2) return fail(MELF_ERR_INVALID, "row_pitch smaller than a row");
+    if (f->row_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "row_pitch too large");
+    if (f->frame_stride < (int64_t)(f->H - 1) * f->row_pitch + (int64_t)f->W * 2)
+        return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
+    if (((uint64_t)f->row_pitch | (uint64_t)f->frame_stride) & 3)
+        return fail(MELF_ERR_INVALID, "YUV 4:2:2 frames need a 4-byte aligned row_pitch and frame_stride");
+    *pix = f->format == MELF_YUV422_UYVY ? PIX_UYVY : (f->format == MELF_YUV422_YVYU ? PIX_YVYU : PIX_YUYV);
+    if (f->n == 0) return MELF_SUCCESS;
+    if (!frames) return fail(MELF_ERR_INVALID, "frames pointer is NULL");
+    if ((uintptr_t)frames & 3) return fail(MELF_ERR_INVALID, "YUV 4:2:2 frames need a 4-byte aligned base");
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_process_yuv422_dev(melf_ctx* c, const void* d_frames, const melf_yuv422_frames* f, void* d_results,
+                                       melf_result* out_host, void* stream_)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    int pix = 0;
+    if (int rc = check_yuv422(d_frames, f, &pix)) return rc;
+    if (f->n == 0) return MELF_SUCCESS;
+    return batch_dev(c, d_frames, f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch, pix, d_results, out_host, stream_);
+}
+
+// melf_process_batch_dev / melf_process_frames_dev / melf_process_yuv_dev / melf_process_yuv422_dev after their argument checks:
+// the lane logic
 static int batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride, int row_stride, int pix,
                      void* d_results, melf_result* out_host, void* stream_, const YuvPlanes* yuv, size_t yuv_extent)
 {
@@ -1256,7 +1291,7 @@ static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int
                             void* d_results, melf_result* out_host, hipStream_t st, const int* rect, int row_stride, int pix,
                             const YuvPlanes* yuv, size_t yuv_extent)
 {
-    const int bpp = yuv ? 1 : pix_bytes(pix);
+    const int bpp = yuv ? 1 : (pix_p422(pix) ? 2 : pix_bytes(pix));
     if (row_stride <= 0) row_stride = W * bpp;  // packed rows unless the caller's rows are padded (host-fed crops, pitched frames)
     // what the kernels may read of the last frame: its rows as far as they reach (the last row of a pitched buffer needs no
     // padding); the host-fed crops keep their staging pitch and spare bytes behind every crop
@@ -1558,7 +1593,104 @@ extern "C" int melf_process_yuv(melf_ctx* c, const void* frames_host, const melf
     return batch_host_yuv(c, (const uint8_t*)frames_host, f, pix, yp, out_host);
 }
 
+// Packed YUV 4:2:2 host frames: the same pipeline.  What crosses PCIe per frame is a small frame of the same format: the rows of
+// the crop (no vertical rounding: every row has its own chroma), its x origin rounded down and its far corner up to even, i.e.
+// to whole macropixels, at a 64-byte pitch in the staging buffer; the kernels read it with the rectangle shifted by the rounding
+// (0 or 1 pixel).  Rows are copied as they are: no byte is converted or reordered on the CPU.
+static int batch_host_p422(melf_ctx* c, const uint8_t* frames_host, const melf_yuv422_frames* f, int pix, melf_result* out_host)
+{
+    const int n = f->n, H = f->H, W = f->W;
+    HIP_TRY(hipSetDevice(c->device));
+    pool_use_device(c->device);
+    const melf_params& P = c->P;
+    const int x0 = P.rect_x0 < W ? P.rect_x0 : W, x1 = P.rect_x1 < W ? P.rect_x1 : W;
+    const int y0 = P.rect_y0 < H ? P.rect_y0 : H, y1 = P.rect_y1 < H ? P.rect_y1 : H;
+    const int crows = y1 - y0, ccols = x1 - x0;
+    if (x0 < 0 || y0 < 0 || crows < P.th || ccols < P.tw)
+        return fail(MELF_ERR_INVALID, "meter_rect crop is smaller than the dials template (cv2.matchTemplate would assert)");
+    const int ex0 = x0 & ~1;
+    const int sw = ((x1 + 1) & ~1) - ex0;   // the small frame's width (even, inside the frame: W is even)
+    const size_t rbytes = (size_t)sw * 2;
+    const size_t pitch = (rbytes + 63) & ~(size_t)63;
+    // + 128 spare bytes per small frame (the prep kernel's aligned windows reach past the last sample)
+    const size_t crop_stride = (size_t)crows * pitch + 128;
+    const int chunk = 128;  // frames per pipeline stage (a multiple of the 32-frame MFMA group)
+    const size_t pin_need = (size_t)(n < chunk ? n : chunk) * crop_stride;
+    if (!c->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    for (int b = 0; b < 2; ++b) {
+        if (!c->ev_h2d[b]) HIP_TRY(hipEventCreateWithFlags(&c->ev_h2d[b], hipEventDisableTiming));
+        if (c->pin_cap[b] < pin_need && (b == 0 || n > chunk)) {
+            if (c->h_pin[b]) { HIP_TRY(hipStreamSynchronize(c->copy_stream)); HIP_TRY(hipHostFree(c->h_pin[b])); }
+            c->h_pin[b] = nullptr;
+            c->pin_cap[b] = 0;
+            HIP_TRY(hipHostMalloc((void**)&c->h_pin[b], pin_need, hipHostMallocDefault));
+            c->pin_cap[b] = pin_need;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the previous call's kernels may still read d_crops
+    if (int rc = grow(&c->d_crops, &c->crops_cap, (size_t)n * crop_stride)) return rc;
+    if (int rc = grow(&c->d_results, &c->results_cap, (size_t)n)) return rc;
+    if (int rc = acquire_lane(c, c->stream, &c->active_lane)) return rc;
+    const int rect[4] = {x0 - ex0, 0, x0 - ex0 + ccols, crows};
+    int k = 0;
+    for (int f0 = 0; f0 < n; f0 += chunk, ++k) {
+        const int m = n - f0 < chunk ? n - f0 : chunk;
+        const int b = k & 1;
+        if (k >= 2) HIP_TRY(hipEventSynchronize(c->ev_h2d[b]));  // the copy that last read this staging buffer is done
+        uint8_t* pin = c->h_pin[b];
+        // work items: the rows of a frame in blocks of 32
+        const int rblocks = (crows + 31) / 32;
+        host_pool().run(m * rblocks, [&](int item) {
+            const int i = item / rblocks, part = item - i * rblocks;
+            const uint8_t* frame = frames_host + (size_t)(f0 + i) * (size_t)f->frame_stride;
+            uint8_t* small = pin + (size_t)i * crop_stride;
+            const int r0 = part * 32, r1 = r0 + 32 < crows ? r0 + 32 : crows;
+            for (int y = r0; y < r1; ++y)
+                memcpy(small + (size_t)y * pitch, frame + (size_t)(y0 + y) * (size_t)f->row_pitch + (size_t)ex0 * 2, rbytes);
+        });
+        uint8_t* d_chunk = c->d_crops + (size_t)f0 * crop_stride;
+        HIP_TRY(hipMemcpyAsync(d_chunk, pin, (size_t)m * crop_stride, hipMemcpyHostToDevice, c->copy_stream));
+        HIP_TRY(hipEventRecord(c->ev_h2d[b], c->copy_stream));
+        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_h2d[b], 0));
+        if (int rc = process_batch_on(c, d_chunk, m, crows, sw, crop_stride, c->d_results + f0, nullptr, c->stream, rect, (int)pitch, pix))
+            return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(out_host, c->d_results, (size_t)n * sizeof(melf_result), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_process_yuv422(melf_ctx* c, const void* frames_host, const melf_yuv422_frames* f, melf_result* out_host)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    int pix = 0;
+    if (int rc = check_yuv422(frames_host, f, &pix)) return rc;
+    if (f->n == 0) return MELF_SUCCESS;
+    if (!out_host) return fail(MELF_ERR_INVALID, "out_host is NULL");
+    return batch_host_p422(c, (const uint8_t*)frames_host, f, pix, out_host);
+}
+
 // ---------------------------------------------------------- stage entries ----
+extern "C" int melf_yuv422_to_bgr(melf_ctx* c, const void* frames_host, const melf_yuv422_frames* f, uint8_t* bgr_out_host)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    int pix = 0;
+    if (int rc = check_yuv422(frames_host, f, &pix)) return rc;
+    if (f->n == 0) return MELF_SUCCESS;
+    if (!bgr_out_host) return fail(MELF_ERR_INVALID, "bgr_out_host is NULL");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t in_bytes = (size_t)(f->n - 1) * (size_t)f->frame_stride + (size_t)(f->H - 1) * (size_t)f->row_pitch + (size_t)f->W * 2;
+    const size_t out_bytes = (size_t)f->n * f->H * f->W * 3;
+    if (int rc = grow(&c->d_stage_in, &c->stage_in_cap, in_bytes)) return rc;
+    if (int rc = grow(&c->d_stage_out, &c->stage_out_cap, out_bytes)) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_stage_in, frames_host, in_bytes, hipMemcpyHostToDevice, c->stream));
+    launch_p422_to_bgr(c->d_stage_in, pix, f->n, f->H, f->W, (int)f->row_pitch, (size_t)f->frame_stride, c->d_stage_out, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(bgr_out_host, c->d_stage_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MELF_SUCCESS;
+}
+
 extern "C" int melf_yuv_to_bgr(melf_ctx* c, const void* frames_host, const melf_yuv_frames* f, uint8_t* bgr_out_host)
 {
     if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");

@@ -33,6 +33,12 @@ struct YuvPlanes {
     int c_pitch;           // bytes between chroma rows
     int pad;
 };
+// Packed YUV 4:2:2 frames (melf_process_yuv422*): the launch's pix.  Two pixels per 4-byte macropixel; base, frame_stride and
+// row_stride (bytes, all 4-byte aligned) describe the frames as for any packed layout, x0 and cols count pixels.  The formats
+// differ in a byte permute only, which the kernels take as a runtime value (v_perm_b32 selector): macropixel -> Y0 U Y1 V.
+constexpr int PIX_YUYV = 24, PIX_UYVY = 25, PIX_YVYU = 26;
+inline bool pix_p422(int pix) { return pix >= PIX_YUYV && pix <= PIX_YVYU; }
+inline uint32_t p422_sel(int pix) { return pix == PIX_UYVY ? 0x02030001u : (pix == PIX_YVYU ? 0x01020300u : 0x03020100u); }
 
 // ---- K2: template match -----------------------------------------------------
 // One partial (max, first-argmax) per workgroup tile of the correlation map.
@@ -176,6 +182,10 @@ size_t launch_stream_probe(const void* d_in, size_t in_bytes, void* d_out, int c
 // n frames: Y plane at d_src (y_pitch, frame_stride), chroma planes per YuvPlanes; d_dst: n packed H x W x 3 BGR frames
 void launch_yuv2bgr(const uint8_t* d_src, int pix, int n, int H, int W, int y_pitch, size_t frame_stride, const YuvPlanes& yuv,
                     uint8_t* d_dst, hipStream_t stream);
+
+// the same for packed YUV 4:2:2 (melf_yuv422_to_bgr): n frames at d_src (row_pitch, frame_stride), pix PIX_YUYV / _UYVY / _YVYU
+void launch_p422_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int row_pitch, size_t frame_stride, uint8_t* d_dst,
+                        hipStream_t stream);
 
 // ---- calibration stage kernels ------------------------------------------------
 void launch_aligned_average(const uint8_t* d_frames, int n, size_t frame_stride, int row_stride, int x0, int y0, int rows,

@@ -8,6 +8,9 @@
 //       (YuvPlanes); src describes the Y plane.  A lane's window starts at the EVEN pixel at or left of its first one: 34 Y bytes and
 //       the 17 chroma pairs under them (NV12 34 interleaved bytes, I420 17 + 17), as aligned dwords; an odd crop origin costs the
 //       one pixel of overlap (the 34 results are shifted by a byte at the end), not a second code path.
+//   With MELF_P422_BODY defined instead (k_p422_lplane): PX 22 = packed YUV 4:2:2 frames, two pixels per aligned 4-byte macropixel,
+//       its byte order the runtime permute selector psel (-> Y0 U Y1 V).  The same even-pixel window is 17 consecutive aligned
+//       dwords, each with both Y samples and the chroma pair: no gather, no chroma loads; the odd origin as above.
     constexpr int PB = PX == 4 ? 4 : 3;         // bytes per pixel of the frame reads
     constexpr int WIN = PX == 4 ? 128 : 100;    // bytes a lane's 32-pixel load window spans
     __shared__ __attribute__((aligned(16))) uint32_t tile[8 * 2 * 32 * 4];  // [kb][h][n][16 B], one chunk of 8 blocks
@@ -29,6 +32,12 @@
     const int yuv_xlast = (src.x0 & ~1) + 32 * (nkb - 1);
     const bool rows_safe = yuv_last + (size_t)(src.y0 + y) * src.row_stride + (size_t)yuv_xlast + 40 <= src.readable &&
                            yuv_last + (size_t)max(yuv.u_off, yuv.v_off) + yuv_crow + (size_t)(PX == 20 ? yuv_xlast : yuv_xlast >> 1) + 40 <= src.readable;
+#elif defined(MELF_P422_BODY)
+    (void)PB; (void)WIN;
+    // (the same for the 68-byte window of a 4:2:2 lane: 17 macropixels from the one of its even pixel)
+    const int xodd = src.x0 & 1;
+    const bool rows_safe = (size_t)min(grp * 32 + 31, nframes - 1) * src.frame_stride + (size_t)(src.y0 + y) * src.row_stride +
+                           (size_t)((src.x0 & ~1) + 32 * (nkb - 1)) * 2 + 68 <= src.readable;
 #else
     const bool rows_safe = (size_t)min(grp * 32 + 31, nframes - 1) * src.frame_stride + (size_t)(src.y0 + y) * src.row_stride +
                            (size_t)(src.x0 + 32 * (nkb - 1)) * PB + WIN <= src.readable;
@@ -119,6 +128,39 @@
                         const int cx = (src.x0 + xbeg + k) >> 1;
                         const YuvChroma c = yuv_chroma(pu[NV12 ? 2 * cx : cx], pv[NV12 ? 2 * cx : cx]);
                         const int L = yuv_lightness(py[k], yuv_cmax(c), yuv_cmin(c));
+                        w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
+                    }
+                }
+            } else
+#elif defined(MELF_P422_BODY)
+            if (PX == 22) {
+                const int xs = (src.x0 + xbeg) & ~1;   // the window's first pixel (even)
+                const size_t o = (size_t)xs * 2;
+                // the window may reach past the crop and the row (never used: masked) but must stay inside the caller's buffer
+                if (rows_safe || (size_t)f * src.frame_stride + (size_t)(src.y0 + y) * src.row_stride + o + 68 <= src.readable) {
+                    const u32x4a4* q = (const u32x4a4*)(prow + o);
+                    u32x4a4 d[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) d[i] = q[i];
+                    const uint32_t d16 = ((const uint32_t*)(prow + o))[16];
+                    uint32_t wl[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // L' of the window's 34 pixels
+#pragma unroll
+                    for (int j = 0; j < 17; ++j) {
+                        const uint32_t m = __builtin_amdgcn_perm(0u, j < 16 ? d[j >> 2][j & 3] : d16, psel);   // Y0 U Y1 V
+                        const YuvChroma c = yuv_chroma((int)((m >> 8) & 255u), (int)(m >> 24));
+                        const int cmax = yuv_cmax(c), cmin = yuv_cmin(c);
+                        const int L0 = yuv_lightness((int)(m & 255u), cmax, cmin), L1 = yuv_lightness((int)((m >> 16) & 255u), cmax, cmin);
+                        wl[j >> 1] |= ((uint32_t)((L0 - 128) & 255) | (uint32_t)((L1 - 128) & 255) << 8) << ((j & 1) * 16);
+                    }
+                    // the lane's 32 pixels start at byte xodd of the window
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) w[i] = __builtin_amdgcn_alignbit(wl[i + 1], wl[i], (uint32_t)xodd * 8u);
+                } else {  // last bytes of the frame buffer: one macropixel per pixel, inside the row
+                    for (int k = 0; k < npx; ++k) {
+                        const int fx = src.x0 + xbeg + k;
+                        const uint32_t m = __builtin_amdgcn_perm(0u, ((const uint32_t*)prow)[fx >> 1], psel);
+                        const YuvChroma c = yuv_chroma((int)((m >> 8) & 255u), (int)(m >> 24));
+                        const int L = yuv_lightness((int)((fx & 1 ? m >> 16 : m) & 255u), yuv_cmax(c), yuv_cmin(c));
                         w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
                     }
                 }

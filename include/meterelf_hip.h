@@ -157,7 +157,7 @@ int melf_process_batch_dev(melf_ctx* ctx, const void* d_frames, int n, int H, in
  * or stride too small, a misaligned 4-byte layout or a NULL descriptor return MELF_ERR_INVALID before anything runs.
  * melf_process_stream_dev, the fused full-frame mask (melf_hls_inrange_close*), melf_aligned_average and the JPEG entry
  * points take packed BGR only; YUV 4:2:0 frames and packed YUV 4:2:2 frames have their own descriptors and entry points
- * (melf_process_yuv*, melf_process_yuv422*, below). */
+ * (melf_process_yuv*, melf_process_yuv422*, below), and so have planar RGB frames (melf_process_planes*, below). */
 enum { MELF_PIX_BGR = 0, MELF_PIX_RGB = 1, MELF_PIX_BGRA = 2, MELF_PIX_RGBA = 3 };
 typedef struct melf_frames {
     int32_t pixel_format;  /* MELF_PIX_*; the 4th byte of BGRA / RGBA is ignored                          */
@@ -241,6 +241,38 @@ int melf_process_yuv422_dev(melf_ctx* ctx, const void* d_frames, const melf_yuv4
                             void* stream);
 /* Stage entry point (parity tests, and a debug view for callers): the conversion alone, n packed H x W x 3 BGR frames out. */
 int melf_yuv422_to_bgr(melf_ctx* ctx, const void* frames_host, const melf_yuv422_frames* f, uint8_t* bgr_out_host);
+
+/* ---- the same path for planar, channels-first frames: (N, 3, H, W) uint8 as torch's decoders and pre-processing pipelines
+ * hold them, ffmpeg's gbrp, rgb24 split into planes ----
+ * The records are byte-identical to melf_process_batch(_dev) on the packed BGR frame whose pixel (x, y) is
+ * (B[y][x], G[y][x], R[y][x]); that frame is never formed: the kernels read the three planes in place, and only the meter_rect
+ * crop of them.  No colour conversion is involved.
+ * Frame f starts at frames + f * frame_stride; row y of its B / G / R plane at + b_offset / g_offset / r_offset + y * row_pitch,
+ * W bytes.  The three offsets give the channel order and there is no format code: RGB planes of P bytes each are r_offset = 0,
+ * g_offset = P, b_offset = 2 P, BGR planes the reverse, ffmpeg's gbrp G, B, R; a 4-plane RGBA / RGBx tensor names three of its
+ * four planes and the fourth is never looked at.  Planes are bytes: any alignment of the base, the offsets, row_pitch and
+ * frame_stride is taken.  The buffer must hold every named plane of every frame up to the last sample of its last row,
+ * (n - 1) * frame_stride + max(offset) + (H - 1) * row_pitch + W bytes, and need hold nothing behind that nor before the base:
+ * no load of the kernels reaches outside it.  H or W <= 0, n < 0, a NULL descriptor or NULL frames, reserved != 0, a negative
+ * offset, row_pitch < W or > 2^31 - 1, two planes closer together than (H - 1) * row_pitch + W (overlapping) or a frame_stride
+ * smaller than the span of one frame's planes return MELF_ERR_INVALID (melf_last_error says which) before anything is launched
+ * or copied; n == 0 passes.
+ * melf_process_stream_dev, the fused full-frame mask, melf_aligned_average and the JPEG entry points stay packed BGR only. */
+typedef struct melf_planar_frames {
+    int32_t n, H, W;
+    int32_t reserved;                           /* 0                                                      */
+    int64_t b_offset, g_offset, r_offset;       /* bytes from a frame's first byte to the first sample of
+                                                   its B / G / R plane, >= 0                              */
+    int64_t row_pitch;                          /* bytes between rows of a plane (the same for the three), >= W */
+    int64_t frame_stride;                       /* bytes between frames                                   */
+} melf_planar_frames;
+/* Host frames, as melf_process_frames: only the crop crosses PCIe -- the crop's rows of the three planes, packed into the pinned
+ * staging buffers as a small planar frame, which the kernels read; no byte is interleaved on the CPU. */
+int melf_process_planes(melf_ctx* ctx, const void* frames_host, const melf_planar_frames* f, melf_result* out_host);
+/* Frames in HBM, exactly as melf_process_frames_dev: the same lanes, melf_ctx_set_frames_resident, caller streams, and NULL
+ * d_results / out_host semantics. */
+int melf_process_planes_dev(melf_ctx* ctx, const void* d_frames, const melf_planar_frames* f, void* d_results, melf_result* out_host,
+                            void* stream);
 
 /* ---- stage entry points (parity tests and roofline runs) ----------------- */
 

@@ -150,7 +150,8 @@ class MeterReader:
         on this reader's GPU (enqueued on torch.cuda.current_stream); pixel_format 'bgr', 'rgb' (C = 3), 'bgra', 'rgba' (C = 4,
         the 4th byte ignored); padded rows and frames and rgba[..., :3]-style views are read in place (_hip.frames_view).
         out: a uint8 device tensor (N, RESULT_DTYPE.itemsize) on the same GPU that receives the records without synchronising
-        the stream (device frames only); returns it.  Otherwise returns the records."""
+        the stream (device frames only); returns it.  Otherwise returns the records.
+        Channels-first (N, C, H, W) frames: read_planar_frames reads them in place; a permuted view of them is copied here."""
         v = _hip.frames_view(frames, pixel_format)
         if not v.on_device:
             if out is not None:
@@ -225,6 +226,33 @@ class MeterReader:
         if v.copied:
             v.array.record_stream(stream)   # the packed copy lives until the stream has passed the call's kernels
         self.ctx.process_yuv422_dev(v.ptr, desc, d_results_ptr=out.data_ptr(), want_host=False, stream=stream.cuda_stream)
+        return out
+
+    def read_planar_frames(self, frames, channel_order: str = 'rgb', out=None):
+        """Planar, channels-first frames (N, 3, H, W) / (N, 4, H, W) uint8 -> records, equal to read_frames() of the packed BGR
+        frames with the same samples (melf_process_planes*); the planes are read in place, no interleaved copy is made.  frames: a
+        numpy array / torch CPU tensor (host path) or a torch tensor on this reader's GPU (enqueued on torch.cuda.current_stream);
+        channel_order names the planes present: 'rgb', 'bgr', 'gbr', 'rgba', 'rgbx', 'bgra' or 'bgrx' (_hip.planar_frames_view says
+        which layouts are read in place).  out: a uint8 device tensor (N, RESULT_DTYPE.itemsize) on the same GPU that receives the
+        records without synchronising the stream (device frames only); returns it.  Otherwise returns the records."""
+        v = _hip.planar_frames_view(frames, channel_order)
+        desc = v.descriptor()
+        if not v.on_device:
+            if out is not None:
+                raise ValueError('out= takes the records of device frames only')
+            return self.ctx.process_planes(v.ptr, desc)
+        import torch
+        if v.device != self.device:
+            raise ValueError('frames are on cuda:%s, the reader on cuda:%d' % (v.device, self.device))
+        stream = torch.cuda.current_stream(self.device)
+        if out is None:
+            return self.ctx.process_planes_dev(v.ptr, desc, stream=stream.cuda_stream)
+        if (not _hip._is_torch(out) or out.dtype != torch.uint8 or out.device != v.array.device or not out.is_contiguous()
+                or tuple(out.shape) != (v.n, _hip.RESULT_DTYPE.itemsize)):
+            raise ValueError('out must be a contiguous uint8 tensor of shape (%d, %d) on %s' % (v.n, _hip.RESULT_DTYPE.itemsize, v.array.device))
+        if v.copied:
+            v.array.record_stream(stream)   # the packed copy lives until the stream has passed the call's kernels
+        self.ctx.process_planes_dev(v.ptr, desc, d_results_ptr=out.data_ptr(), want_host=False, stream=stream.cuda_stream)
         return out
 
     def read_crops(self, crops: np.ndarray) -> np.ndarray:

@@ -95,6 +95,16 @@ class MelfYuv422Frames(C.Structure):
 YUV422_YUYV, YUV422_UYVY, YUV422_YVYU = 0, 1, 2
 YUV422_CODES = {'yuyv': YUV422_YUYV, 'yuy2': YUV422_YUYV, 'uyvy': YUV422_UYVY, 'yvyu': YUV422_YVYU}
 
+
+
+class MelfPlanarFrames(C.Structure):
+    _fields_ = [('n', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('reserved', C.c_int32), ('b_offset', C.c_int64),
+                ('g_offset', C.c_int64), ('r_offset', C.c_int64), ('row_pitch', C.c_int64), ('frame_stride', C.c_int64)]
+
+
+# plane orders of planar_frames_view: the planes present in an (N, C, H, W) array, in the array's order; 'a' / 'x' is never read
+PLANAR_ORDERS = ('rgb', 'bgr', 'gbr', 'rgba', 'rgbx', 'bgra', 'bgrx')
+
 MATCH_KERNEL_NAMES = ('dot4', 'mfma', 'gen')
 
 RESULT_DTYPE = np.dtype([('status', '<i4'), ('match_x', '<i4'), ('match_y', '<i4'), ('failed_dial', '<i4'),
@@ -115,7 +125,7 @@ EXPORTS = [
     'melf_blob_size', 'melf_blob_pack', 'melf_blob_params', 'melf_ctx_create', 'melf_ctx_create_bcast', 'melf_ctx_destroy',
     'melf_ctx_params', 'melf_ctx_sync', 'melf_ctx_get_masks', 'melf_process_batch', 'melf_process_batch_dev', 'melf_process_stream_dev',
     'melf_process_frames', 'melf_process_frames_dev', 'melf_process_yuv', 'melf_process_yuv_dev', 'melf_yuv_to_bgr',
-    'melf_process_yuv422', 'melf_process_yuv422_dev', 'melf_yuv422_to_bgr',
+    'melf_process_yuv422', 'melf_process_yuv422_dev', 'melf_yuv422_to_bgr', 'melf_process_planes', 'melf_process_planes_dev',
     'melf_bgr2hls', 'melf_hls_inrange_close', 'melf_hls_inrange_close_dev', 'melf_match_ccoeff',
     'melf_read_dials', 'melf_aligned_average', 'melf_inrange', 'melf_ctx_fused_table_ties', 'melf_ctx_fused_variant', 'melf_ctx_set_frames_resident', 'melf_ctx_last_match', 'melf_match_layout_query', 'melf_match_gen_plan_query', 'melf_ctx_set_profiling', 'melf_ctx_timings', 'melf_kernel_name',
     'melf_jpeg_probe', 'melf_jpeg_probe_batch', 'melf_jpeg_decode_batch', 'melf_jpeg_clean_segment', 'melf_jpeg_process_batch',
@@ -162,6 +172,8 @@ def lib():
     L.melf_process_yuv422.argtypes = [vp, vp, C.POINTER(MelfYuv422Frames), vp]
     L.melf_process_yuv422_dev.argtypes = [vp, vp, C.POINTER(MelfYuv422Frames), vp, vp, vp]
     L.melf_yuv422_to_bgr.argtypes = [vp, vp, C.POINTER(MelfYuv422Frames), vp]
+    L.melf_process_planes.argtypes = [vp, vp, C.POINTER(MelfPlanarFrames), vp]
+    L.melf_process_planes_dev.argtypes = [vp, vp, C.POINTER(MelfPlanarFrames), vp, vp, vp]
     L.melf_process_stream_dev.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, vp]
     L.melf_bgr2hls.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp]
     L.melf_hls_inrange_close.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
@@ -470,6 +482,88 @@ def yuv422_frames_view(frames, pixel_format='yuyv'):
     return Yuv422FramesView(int(ptr), on_device, device, code, n, H, W, int(rp), int(fs), int(extent), not ok, frames)
 
 
+class PlanarFramesView(NamedTuple):
+    """How the kernels read a batch of planar (channels-first) frames in place (planar_frames_view)."""
+    ptr: int            # address of frame 0's first plane
+    on_device: bool     # True: a torch tensor on a GPU (ptr is a device address)
+    device: Optional[int]
+    n: int
+    H: int
+    W: int
+    b_offset: int       # bytes from a frame's first byte to the first sample of its B / G / R plane
+    g_offset: int
+    r_offset: int
+    row_pitch: int      # bytes between rows of a plane
+    frame_stride: int   # bytes between frames
+    extent: int         # bytes read from ptr: (n - 1) * frame_stride + max(offset) + (H - 1) * row_pitch + W
+    copied: bool        # the layout could not be described and the frames were copied once to a packed (N, 3, H, W) array
+    array: object       # what ptr points into (the caller's array, or the copy): keep it alive while the call runs
+
+    def descriptor(self):
+        return MelfPlanarFrames(self.n, self.H, self.W, 0, self.b_offset, self.g_offset, self.r_offset, self.row_pitch, self.frame_stride)
+
+
+def planar_frames_view(frames, channel_order='rgb'):
+    """Describes an (N, C, H, W) uint8 numpy array or torch tensor (channels first: what torch's decoders and pre-processing
+    pipelines hold, ffmpeg's gbrp) as melf_process_planes* read it.  channel_order names the planes present, in the array's order:
+    'rgb', 'bgr' or 'gbr' for C = 3, 'rgba' / 'rgbx' / 'bgra' / 'bgrx' for C = 4 (the 4th plane is never read).  Read in place: a
+    unit stride along W, a row stride >= W, a plane stride that keeps the planes apart, any frame stride that holds a frame's
+    planes -- contiguous NCHW, x[:, :3] of a 4-plane tensor, x[..., :h, :w], x[::2]; a channel order other than the caller's is
+    a matter of channel_order, not of x[:, [2, 1, 0]].  Anything else -- a W stride other than 1 (a permuted NHWC tensor:
+    frames_view reads those), negative strides, overlapping planes -- is copied once to a packed (N, 3, H, W) array
+    (PlanarFramesView.copied).  Not uint8, not four-dimensional, a zero H or W, or a channel_order that does not name the array's C
+    planes: ValueError."""
+    is_torch = _is_torch(frames)
+    if is_torch:
+        if str(frames.dtype) != 'torch.uint8':
+            raise ValueError('frames must be uint8, not %s' % frames.dtype)
+        shape = tuple(frames.shape)
+        strides = tuple(frames.stride())          # elements = bytes for uint8
+        ptr = frames.data_ptr()
+        on_device = frames.device.type == 'cuda'
+        device = frames.device.index if on_device else None
+    else:
+        frames = np.asarray(frames)
+        if frames.dtype != np.uint8:
+            raise ValueError('frames must be uint8, not %s' % frames.dtype)
+        shape = frames.shape
+        strides = frames.strides
+        ptr = frames.ctypes.data
+        (on_device, device) = (False, None)
+    order = str(channel_order).lower()
+    if order not in PLANAR_ORDERS:
+        raise ValueError('channel_order %r is not one of %s' % (channel_order, ', '.join(PLANAR_ORDERS)))
+    if len(shape) != 4 or shape[1] not in (3, 4) or shape[2] == 0 or shape[3] == 0:
+        raise ValueError('planar frames must be (N, 3, H, W) or (N, 4, H, W), not %s' % (shape,))
+    if shape[1] != len(order):
+        raise ValueError('channel_order %r does not name the %d planes of the frames' % (channel_order, shape[1]))
+    (n, _c, H, W) = shape
+    (fs, ps, rp, es) = strides
+    (ib, ig, ir) = (order.index('b'), order.index('g'), order.index('r'))
+    # strides of dimensions of size 1 are never stepped over: make them what a packed array has
+    if W == 1:
+        es = 1
+    if H == 1:
+        rp = W
+    span = (H - 1) * rp + W                       # bytes of one plane, first to last sample
+    if n == 1:
+        fs = max(ib, ig, ir) * ps + span if ps >= 0 else 0
+    ok = es == 1 and W <= rp <= 2 ** 31 - 1 and ps >= span and fs >= max(ib, ig, ir) * ps + span
+    if not ok:
+        # the three colour planes, packed, in the caller's order (they are the first three of every order)
+        if is_torch:
+            import torch
+            frames = frames[:, :3].clone(memory_format=torch.contiguous_format)
+        else:
+            frames = np.array(frames[:, :3], order='C', copy=True)
+        (rp, ps, fs) = (W, H * W, 3 * H * W)
+        span = H * W
+        ptr = frames.data_ptr() if is_torch else frames.ctypes.data
+    extent = (n - 1) * fs + max(ib, ig, ir) * ps + span if n else 0
+    return PlanarFramesView(int(ptr), on_device, device, n, H, W, int(ib * ps), int(ig * ps), int(ir * ps), int(rp), int(fs), int(extent),
+                            not ok, frames)
+
+
 def jpeg_probe(data):
     """(H, W, supported, reason) of a JPEG file's bytes; header parse only, no GPU."""
     L = lib()
@@ -728,6 +822,20 @@ class Context:
         """The conversion alone (melf_yuv422_to_bgr): host packed YUV 4:2:2 frames -> (n, H, W, 3) BGR."""
         out = np.empty((desc.n, desc.H, desc.W, 3), np.uint8)
         check(self._L.melf_yuv422_to_bgr(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
+        return out
+
+    def process_planes(self, frames_ptr, desc):
+        """Host planar frames (melf_process_planes; desc: a MelfPlanarFrames, e.g. planar_frames_view(...).descriptor()) -> records."""
+        out = np.zeros(desc.n, RESULT_DTYPE)
+        check(self._L.melf_process_planes(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
+        return out
+
+    def process_planes_dev(self, d_frames_ptr, desc, d_results_ptr=None, want_host=True, stream=None):
+        """Planar frames in HBM (melf_process_planes_dev, as process_frames_dev).  Returns records when want_host."""
+        out = np.zeros(desc.n, RESULT_DTYPE) if want_host else None
+        check(self._L.melf_process_planes_dev(
+            self._h, C.c_void_p(d_frames_ptr), C.byref(desc), C.c_void_p(d_results_ptr) if d_results_ptr else None,
+            _ptr(out) if want_host else None, C.c_void_p(stream) if stream else None))
         return out
 
     # --- stages ---

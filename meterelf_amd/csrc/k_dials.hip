@@ -324,9 +324,27 @@ __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_v
 }
 #undef MELF_P422_BODY
 
+// Planar frames (melf_process_planes*): the B, G and R planes at `planes` in a frame.  Past its loads the body is the one of 4-byte
+// B G R pixels.
+#define MELF_PLANAR_BODY
+template <int NR>
+__global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_vgpr(DIALS_VGPRS))) void k_planar_needle(DialsSrc src, PlanarPlanes planes, melf_params P,
+                                                                const DialGeom* __restrict__ geom,
+                                                                const uint64_t* __restrict__ rowmasks,
+                                                                const MatchPartial* __restrict__ partials,
+                                                                int nparts, int rw, melf_result* __restrict__ results)
+{
+    constexpr bool FROM_HLS = false;
+    constexpr int PB = 4;
+    constexpr bool RT_ORDER = false;
+    const uint32_t bsel = 0u;
+#include "k_dials_body.inc"
+}
+#undef MELF_PLANAR_BODY
+
 void launch_dials(const DialsSrc& src, int pix, int n, const melf_params& P, const DialGeom* d_geom,
                   const uint64_t* d_rowmasks, const MatchPartial* d_partials, int nparts, int rw,
-                  melf_result* d_results, hipStream_t stream, int ws_max, const YuvPlanes* yuv)
+                  melf_result* d_results, hipStream_t stream, int ws_max, const YuvPlanes* yuv, const PlanarPlanes* planes)
 {
     dim3 grid(n), block(64 * P.ndials);
     const size_t shmem = (size_t)P.ndials * DIAL_LDS_BYTES;
@@ -367,8 +385,20 @@ void launch_dials(const DialsSrc& src, int pix, int n, const melf_params& P, con
     }
 #define MELF_P422_NEEDLE_LAUNCH(NRV) \
     hipLaunchKernelGGL((k_p422_needle<NRV>), grid, block, shmem, stream, src, p422_sel(pix), P, d_geom, d_rowmasks, d_partials, nparts, rw, d_results)
+#define MELF_PLANAR_NEEDLE_LAUNCH(NRV) \
+    hipLaunchKernelGGL((k_planar_needle<NRV>), grid, block, shmem, stream, src, *planes, P, d_geom, d_rowmasks, d_partials, nparts, rw, d_results)
     const int swap_rb = pix == MELF_PIX_RGB || pix == MELF_PIX_RGBA;
-    if (pix_p422(pix)) {
+    if (pix == PIX_PLANAR) {
+        switch (nr) {
+            case 32: MELF_PLANAR_NEEDLE_LAUNCH(32); break;
+            case 40: MELF_PLANAR_NEEDLE_LAUNCH(40); break;
+            case 48: MELF_PLANAR_NEEDLE_LAUNCH(48); break;
+            case 52: MELF_PLANAR_NEEDLE_LAUNCH(52); break;
+            case 56: MELF_PLANAR_NEEDLE_LAUNCH(56); break;
+            default: MELF_PLANAR_NEEDLE_LAUNCH(64); break;
+        }
+    }
+    else if (pix_p422(pix)) {
         switch (nr) {
             case 32: MELF_P422_NEEDLE_LAUNCH(32); break;
             case 40: MELF_P422_NEEDLE_LAUNCH(40); break;
@@ -384,6 +414,7 @@ void launch_dials(const DialsSrc& src, int pix, int n, const melf_params& P, con
     else if (pix == MELF_PIX_BGR) { MELF_DIALS_NR(false) }
     else if (pix == MELF_PIX_RGB) { MELF_NEEDLES_NR(3) }
     else { MELF_NEEDLES_NR(4) }
+#undef MELF_PLANAR_NEEDLE_LAUNCH
 #undef MELF_P422_NEEDLE_LAUNCH
 #undef MELF_YNEEDLE_NR
 #undef MELF_YNEEDLE_LAUNCH

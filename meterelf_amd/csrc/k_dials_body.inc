@@ -15,6 +15,10 @@
 // With MELF_P422_BODY defined instead (k_p422_needle): packed YUV 4:2:2 frames (melf_process_yuv422*), two pixels per aligned
 // macropixel dword, its byte order the runtime permute selector psel (-> Y0 U Y1 V).  A lane's four window pixels lie in two or
 // three consecutive macropixels: three dwords per lane and row, and from there on one B G R dword per pixel as above.
+// With MELF_PLANAR_BODY defined instead (k_planar_needle): planar frames (melf_process_planes*), the B, G and R planes at `planes`
+// (PlanarPlanes) in a frame, any byte alignment.  The core pixel and the exact path's column pixel are three byte loads; a lane's
+// four window pixels are one unaligned dword per plane (inside the crop's row of its plane: the pieces lie inside the crop), turned
+// into four B G R dwords by six v_perm_b32 where the prefilter picks them up: from there on as above, at any byte phase.
     [[maybe_unused]] const uint32_t csel = bsel ? 0x0c000102u : 0x0c020100u;   // pixel -> B G R in bytes 0..2 (RT_ORDER)
     auto bgr = [&](uint32_t px) -> uint32_t {
         if constexpr (RT_ORDER) return __builtin_amdgcn_perm(0u, px, csel);
@@ -114,6 +118,16 @@
         const uint32_t c = __builtin_amdgcn_perm(0u, *(const uint32_t*)(frame + (size_t)fy * rstride + (size_t)(fx >> 1) * 4), psel);
         return yuv_bgr((int)((fx & 1 ? c >> 16 : c) & 255u), yuv_chroma((int)((c >> 8) & 255u), (int)(c >> 24)));
     };
+#elif defined(MELF_PLANAR_BODY)
+    const int fx_m = src.x0 + mx, fy_m = src.y0 + my;   // the match position in the frame
+    const uint8_t* const bplane = frame + (size_t)planes.b_off;
+    const uint8_t* const gplane = frame + (size_t)planes.g_off;
+    const uint8_t* const rplane = frame + (size_t)planes.r_off;
+    // pixel (X, Y) of the dials crop as a B G R dword: three byte loads
+    auto planar_px = [&](int X, int Y) -> uint32_t {
+        const size_t o = (size_t)(fy_m + Y) * rstride + (size_t)(fx_m + X);
+        return (uint32_t)bplane[o] | (uint32_t)gplane[o] << 8 | (uint32_t)rplane[o] << 16;
+    };
 #else
     const uint8_t* const origin = FROM_HLS ? frame : frame + (size_t)(src.y0 + my) * src.row_stride + (size_t)(src.x0 + mx) * PB;
 #endif
@@ -121,6 +135,8 @@
     const bool corevalid = lane < 25 && coreX >= 0 && coreX < P.tw && coreY >= 0 && coreY < P.th;
 #if defined(MELF_YUV_BODY) || defined(MELF_P422_BODY)
     const uint32_t corepx = yuv_px(min(max(coreX, 0), P.tw - 1), min(max(coreY, 0), P.th - 1));
+#elif defined(MELF_PLANAR_BODY)
+    const uint32_t corepx = planar_px(min(max(coreX, 0), P.tw - 1), min(max(coreY, 0), P.th - 1));
 #else
     const uint32_t corepx = bgr(load_px<PB>(origin + (size_t)min(max(coreY, 0), P.th - 1) * rstride + (size_t)min(max(coreX, 0), P.tw - 1) * PB, src.base));
     const PxColumn pcol = px_column_of<PB>(origin + (size_t)Xc * PB, src.base);   // (the exact path's loads: one pixel per lane and row)
@@ -200,6 +216,22 @@
         o.w = yuv_bgr((int)(yd >> 24), fodd ? c2 : c1);
         return o;
     };
+#elif defined(MELF_PLANAR_BODY)
+    // planar: a lane's four pixels are four consecutive bytes of each plane's row, inside the crop (and so inside the frame's row):
+    // nothing is read outside the planes' samples, whatever the alignment
+    (void)buf_end;
+    const bool quads = wx0 >= 0 && wx0 + 4 * npiece <= P.tw;
+    const int fx0 = fx_m + wx0 + 4 * min(pc, npiece - 1);   // the lane's first pixel in the frame
+    // the four pixels as B G R dwords from the three plane dwords {B0 B1 B2 B3, G0 G1 G2 G3, R0 R1 R2 R3}
+    auto planar_quad = [&](const u32x4v r) -> u32x4v {
+        const uint32_t t01 = __builtin_amdgcn_perm(r.y, r.x, 0x05010400u), t23 = __builtin_amdgcn_perm(r.y, r.x, 0x07030602u);   // B0 G0 B1 G1, B2 G2 B3 G3
+        u32x4v o;
+        o.x = __builtin_amdgcn_perm(r.z, t01, 0x0c040100u);
+        o.y = __builtin_amdgcn_perm(r.z, t01, 0x0c050302u);
+        o.z = __builtin_amdgcn_perm(r.z, t23, 0x0c060100u);
+        o.w = __builtin_amdgcn_perm(r.z, t23, 0x0c070302u);
+        return o;
+    };
 #else
     const bool quads = !FROM_HLS && ((uintptr_t)src.base & 3) == 0 && wx0 >= 0 && wx0 + 4 * npiece <= P.tw &&
                        origin + (size_t)th1 * rstride + (size_t)(wx0 + 4 * npiece) * PB + (PB == 4 ? 0 : 4) <= buf_end;
@@ -234,6 +266,19 @@
             uint32_t md[3];
             __builtin_memcpy(md, (const uint32_t*)(frame + (size_t)fy * (size_t)rs_u) + mstart, 12);
             raw[g] = u32x4v{md[0], md[1], md[2], 0u};
+        }
+    }
+#elif defined(MELF_PLANAR_BODY)
+    if (quads) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const int fy = fy_m + min(max(wy0 + min(4 * g + rg, ylast), 0), th1);
+            const size_t o = (size_t)fy * (size_t)rs_u + (size_t)fx0;
+            uint32_t bd, gd, rd;
+            __builtin_memcpy(&bd, bplane + o, 4);
+            __builtin_memcpy(&gd, gplane + o, 4);
+            __builtin_memcpy(&rd, rplane + o, 4);
+            raw[g] = u32x4v{bd, gd, rd, 0u};
         }
     }
 #else
@@ -286,6 +331,8 @@
                 const int Y = min(max(wy0 + min(yc + k, ylast), 0), th1);
 #if defined(MELF_YUV_BODY) || defined(MELF_P422_BODY)
                 pxe[k] = yuv_px(Xc, Y);
+#elif defined(MELF_PLANAR_BODY)
+                pxe[k] = planar_px(Xc, Y);
 #else
                 pxe[k] = bgr(load_px3_row(pcol, (size_t)((int64_t)Y * rs_u)));
 #endif
@@ -335,6 +382,8 @@
             for (int g = 0; g < NG; ++g) {
 #if defined(MELF_YUV_BODY) || defined(MELF_P422_BODY)
                 raw[g] = yuv_quad(raw[g]);   // from here on: one B G R pixel per dword, as for 4-byte pixels
+#elif defined(MELF_PLANAR_BODY)
+                raw[g] = planar_quad(raw[g]);   // (the same)
 #endif
                 // the lane's 12 bytes: B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3  (4-byte pixels: raw[g] holds one pixel per dword)
                 uint32_t e0 = 0, e1 = 0, e2 = 0;

@@ -30,7 +30,8 @@ __device__ inline bool better(float v, int i, float bv, int bi)
 // The body of k_match and k_match_px4.  PX: 1 = packed single-channel u8 images, 3 = 3-byte pixels (BGR / RGB: L = (max + min) / 2
 // does not depend on the channel order), 4 = 4-byte pixels (BGRA / RGBA, 4-byte aligned, the 4th byte ignored); 20 / 21 = NV12 /
 // I420 frames (src: the Y plane, yuv: the chroma planes; a Y byte and the chroma pair under it per pixel, byte loads); 22 = packed
-// YUV 4:2:2 frames (yuv: P422Sel, the byte permute to Y0 U Y1 V; a pixel's macropixel as one aligned dword load).
+// YUV 4:2:2 frames (yuv: P422Sel, the byte permute to Y0 U Y1 V; a pixel's macropixel as one aligned dword load); 23 = planar
+// frames (melf_process_planes*; yuv: PlanarPlanes, where the B, G and R planes start in a frame; three byte loads per pixel).
 struct NoYuv {};
 struct P422Sel { uint32_t sel; };
 template <int PX, class YUV = NoYuv>
@@ -76,6 +77,9 @@ __device__ __forceinline__ void match_tile(MatchSrc src, MatchGeom g, const uint
                             const uint32_t m = __builtin_amdgcn_perm(0u, *(const uint32_t*)(prow + (size_t)(fx >> 1) * 4), yuv.sel);
                             const YuvChroma c = yuv_chroma((int)((m >> 8) & 255u), (int)(m >> 24));
                             v = (uint32_t)yuv_lightness((int)((fx & 1 ? m >> 16 : m) & 255u), yuv_cmax(c), yuv_cmin(c));
+                        } else if constexpr (PX == 23) {
+                            const uint8_t* p = prow + (size_t)(src.x0 + x);
+                            v = (uint32_t)hls_lightness(p[yuv.b_off], p[yuv.g_off], p[yuv.r_off]);
                         } else if (PX == 3) {
                             const uint8_t* p = prow + (size_t)(src.x0 + x) * 3;
                             v = (uint32_t)hls_lightness(p[0], p[1], p[2]);
@@ -198,6 +202,14 @@ __global__ __launch_bounds__(256) void k_p422_match(MatchSrc src, uint32_t psel,
     match_tile<22, P422Sel>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts, P422Sel{psel});
 }
 
+// planar frames (melf_process_planes*): the dot4 matcher with three byte loads per pixel, one from each plane
+__global__ __launch_bounds__(256) void k_planar_match(MatchSrc src, PlanarPlanes planes, MatchGeom g, const uint32_t* __restrict__ tplT,
+                                                      int rh, int rw, int nrb, float* __restrict__ result_map,
+                                                      MatchPartial* __restrict__ partials, int nparts)
+{
+    match_tile<23, PlanarPlanes>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts, planes);
+}
+
 int match_parts(const MatchGeom& g, int rows, int cols)
 {
     const int rh = rows - g.th + 1, rw = cols - g.tw + 1;
@@ -207,7 +219,8 @@ int match_parts(const MatchGeom& g, int rows, int cols)
 }
 
 void launch_match(const MatchSrc& src, int pix, int n, const MatchGeom& g, const uint32_t* d_tplT,
-                  float* d_result_map, MatchPartial* d_partials, int* nparts_out, hipStream_t stream, const YuvPlanes* yuv)
+                  float* d_result_map, MatchPartial* d_partials, int* nparts_out, hipStream_t stream, const YuvPlanes* yuv,
+                  const PlanarPlanes* planes)
 {
     const int rh = src.rows - g.th + 1, rw = src.cols - g.tw + 1;
     const int nrb = (rh + MATCH_RBLK - 1) / MATCH_RBLK, ncb = (rw + MATCH_CBLK - 1) / MATCH_CBLK;
@@ -215,7 +228,10 @@ void launch_match(const MatchSrc& src, int pix, int n, const MatchGeom& g, const
     if (nparts_out) *nparts_out = nparts;
     const size_t shmem = (size_t)g.lds_rows * g.ldsw * sizeof(uint32_t);
     dim3 grid(nparts, n), block(256);
-    if (pix_p422(pix))
+    if (pix == PIX_PLANAR)
+        hipLaunchKernelGGL(k_planar_match, grid, block, shmem, stream, src, *planes, g, d_tplT, rh, rw, nrb, d_result_map,
+                           d_partials, nparts);
+    else if (pix_p422(pix))
         hipLaunchKernelGGL(k_p422_match, grid, block, shmem, stream, src, p422_sel(pix), g, d_tplT, rh, rw, nrb, d_result_map,
                            d_partials, nparts);
     else if (pix == PIX_NV12)

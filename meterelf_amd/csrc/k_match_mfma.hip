@@ -105,6 +105,18 @@ __global__ __launch_bounds__(256) void k_p422_lplane(MatchSrc src, uint32_t psel
 }
 #undef MELF_P422_BODY
 
+// Planar frames (melf_process_planes*): three planes of one byte per sample, `planes` where they start in a frame.  A lane's 32
+// pixels are 32 consecutive bytes in each plane: nine aligned dwords and v_alignbit at the plane's own byte phase, then L from the
+// largest and the smallest of a pixel's three bytes as for BGR.
+#define MELF_PLANAR_BODY
+__global__ __launch_bounds__(256) void k_planar_lplane(MatchSrc src, PlanarPlanes planes, int nframes, int nkb, int rows_pad, int tw, int rwp, int pairs,
+                                                       int8_t* __restrict__ Lg, uint16_t* __restrict__ R)
+{
+    constexpr int PX = 23;
+#include "prep_lplane_body.inc"
+}
+#undef MELF_PLANAR_BODY
+
 // ---------------------------------------------------------------------------
 // k_match_mfma
 // ---------------------------------------------------------------------------
@@ -787,7 +799,7 @@ void mfma_build_atab(const uint8_t* templ, int th, int tw, int8_t* atab)
 }
 
 void launch_match_prep(const MatchSrc& src, int pix, int n, int groups, int rows_pad, int nkb, int rwp, int tw, int8_t* d_lg,
-                       uint16_t* d_r, hipStream_t stream, int pairs, const YuvPlanes* yuv)
+                       uint16_t* d_r, hipStream_t stream, int pairs, const YuvPlanes* yuv, const PlanarPlanes* planes)
 {
     dim3 grid(rows_pad, groups), block(256);
     const size_t pre_bytes = (size_t)32 * (nkb * 32 + 8) * sizeof(int16_t);
@@ -801,9 +813,11 @@ void launch_match_prep(const MatchSrc& src, int pix, int n, int groups, int rows
         (void)hipFuncSetAttribute((const void*)k_lplane_yuv<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute((const void*)k_lplane_yuv<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute((const void*)k_p422_lplane, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_planar_lplane, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         attr_set[dev] = true;
     }
-    if (pix_p422(pix)) hipLaunchKernelGGL(k_p422_lplane, grid, block, pre_bytes, stream, src, p422_sel(pix), n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    if (pix == PIX_PLANAR) hipLaunchKernelGGL(k_planar_lplane, grid, block, pre_bytes, stream, src, *planes, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    else if (pix_p422(pix)) hipLaunchKernelGGL(k_p422_lplane, grid, block, pre_bytes, stream, src, p422_sel(pix), n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else if (pix == PIX_NV12) hipLaunchKernelGGL((k_lplane_yuv<false>), grid, block, pre_bytes, stream, src, *yuv, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else if (pix == PIX_I420) hipLaunchKernelGGL((k_lplane_yuv<true>), grid, block, pre_bytes, stream, src, *yuv, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else if (pix == PIX_PLANE) hipLaunchKernelGGL((k_prep_lplane<false>), grid, block, pre_bytes, stream, src, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
@@ -812,10 +826,10 @@ void launch_match_prep(const MatchSrc& src, int pix, int n, int groups, int rows
 }
 
 void launch_mfma_prep(const MatchSrc& src, int pix, int n, const MfmaPlan& p, int th, int tw, int8_t* d_lg,
-                      uint16_t* d_r, hipStream_t stream, const YuvPlanes* yuv)
+                      uint16_t* d_r, hipStream_t stream, const YuvPlanes* yuv, const PlanarPlanes* planes)
 {
     (void)th;
-    launch_match_prep(src, pix, n, p.groups, p.rows_pad, p.nkb, 64, tw, d_lg, d_r, stream, p.nxb, yuv);   // one paired operand per column block
+    launch_match_prep(src, pix, n, p.groups, p.rows_pad, p.nkb, 64, tw, d_lg, d_r, stream, p.nxb, yuv, planes);   // one paired operand per column block
 }
 
 template <int NXB, int RB, int KS>

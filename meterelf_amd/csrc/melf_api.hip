@@ -1047,14 +1047,15 @@ static int gen_entry(melf_ctx* c, int rows, int cols, int n, melf_ctx::GenEntry*
 // prep + match of m images on stream ls with lane bl's work buffers; *parts / *nparts: per-frame (max, first arg-max)
 // partials for the consumer (k_dials or the host fold of melf_match_ccoeff)
 static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int bl, hipStream_t ls, float* d_map,
-                          MatchPartial** parts, int* nparts, TimedEvent& ev, const YuvPlanes* yuv);
+                          MatchPartial** parts, int* nparts, TimedEvent& ev, const YuvPlanes* yuv, const PlanarPlanes* planes);
 static int run_match(melf_ctx* c, const MatchSrc& ms, int pix, int m, int bl, hipStream_t ls, float* d_map,
-                     MatchPartial** parts, int* nparts, const YuvPlanes* yuv = nullptr /* pix_yuv(pix): the chroma planes */)
+                     MatchPartial** parts, int* nparts, const YuvPlanes* yuv = nullptr /* pix_yuv(pix): the chroma planes */,
+                     const PlanarPlanes* planes = nullptr /* PIX_PLANAR: the three planes */)
 {
     TimedEvent ev;
     ev.kernel = MELF_K_MATCH;
     ev.start = ev.stop = nullptr;
-    const int rc = run_match_impl(c, ms, pix, m, bl, ls, d_map, parts, nparts, ev, yuv);
+    const int rc = run_match_impl(c, ms, pix, m, bl, ls, d_map, parts, nparts, ev, yuv, planes);
     if (rc == MELF_SUCCESS && ev.start && ev.stop) {
         c->events.push_back(ev);
     } else {   // nothing was launched with them (an allocation failed on the way)
@@ -1064,7 +1065,7 @@ static int run_match(melf_ctx* c, const MatchSrc& ms, int pix, int m, int bl, hi
     return rc;
 }
 static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int bl, hipStream_t ls, float* d_map,
-                          MatchPartial** parts, int* nparts, TimedEvent& ev, const YuvPlanes* yuv)
+                          MatchPartial** parts, int* nparts, TimedEvent& ev, const YuvPlanes* yuv, const PlanarPlanes* planes)
 {
     const melf_params& P = c->P;
     const int kind = pick_match_kind(c, ms.rows, ms.cols, m);
@@ -1088,7 +1089,7 @@ static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int b
         *parts = c->d_lpart[bl];
         {
             KernelTimer t(c, MELF_K_LPLANE, ls);
-            launch_mfma_prep(ms, pix, m, pl, P.th, P.tw, c->d_lg[bl], c->d_rsum[bl], ls, yuv);
+            launch_mfma_prep(ms, pix, m, pl, P.th, P.tw, c->d_lg[bl], c->d_rsum[bl], ls, yuv, planes);
         }
         info.rows_per_wave = pl.rb; info.full_waves = pl.na; info.pair_waves = 2 * pl.np;
         info.waves = pl.nparts * pl.groups; info.tiles = pl.ntiles;
@@ -1106,7 +1107,7 @@ static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int b
         *parts = c->d_lpart[bl];
         {
             KernelTimer t(c, MELF_K_LPLANE, ls);
-            launch_match_prep(ms, pix, m, pl.groups, pl.rows_pad, pl.nkb, pl.rwp, P.tw, c->d_lg[bl], c->d_rsum[bl], ls, 0, yuv);
+            launch_match_prep(ms, pix, m, pl.groups, pl.rows_pad, pl.nkb, pl.rwp, P.tw, c->d_lg[bl], c->d_rsum[bl], ls, 0, yuv, planes);
         }
         const GenDev& dev = ge->dev;
         fill_gen_info(&info, pl);
@@ -1116,7 +1117,7 @@ static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int b
         if (int rc = grow(&c->d_lpart[bl], &c->lpart_cap[bl], (size_t)m * *nparts)) return rc;
         *parts = c->d_lpart[bl];
         KernelTimer t(c, MELF_K_MATCH, ls);
-        launch_match(ms, pix, m, c->mg, c->d_tplT, d_map, *parts, nullptr, ls, yuv);
+        launch_match(ms, pix, m, c->mg, c->d_tplT, d_map, *parts, nullptr, ls, yuv, planes);
         info.tiles = *nparts;
     }
     if (trace)
@@ -1133,10 +1134,12 @@ static const int MAX_FRAMES_PER_LAUNCH = 32768;
 // (the host-fed path uploads only the crop: its "frames" are the crops themselves); row_stride: bytes between rows
 // (0 = packed); pix: the frames' pixel layout (MELF_PIX_*, or PIX_NV12 / PIX_I420: d_frames, frame_stride and row_stride then describe
 // the Y plane, yuv the chroma planes, yuv_extent = the bytes of a frame up to the last sample of its last plane; or PIX_YUYV /
-// PIX_UYVY / PIX_YVYU: packed 4:2:2 frames of 2 bytes per pixel, W even, everything 4-byte aligned)
+// PIX_UYVY / PIX_YVYU: packed 4:2:2 frames of 2 bytes per pixel, W even, everything 4-byte aligned; or PIX_PLANAR: d_frames,
+// frame_stride and row_stride describe a frame and the rows of its planes, planes where they start, yuv_extent as for YUV)
 static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
                             void* d_results, melf_result* out_host, hipStream_t st, const int* rect = nullptr, int row_stride = 0,
-                            int pix = MELF_PIX_BGR, const YuvPlanes* yuv = nullptr, size_t yuv_extent = 0);
+                            int pix = MELF_PIX_BGR, const YuvPlanes* yuv = nullptr, size_t yuv_extent = 0,
+                            const PlanarPlanes* planes = nullptr);
 
 // The checks of a melf_frames descriptor (melf_process_frames*); n == 0 passes
 static int check_frames(const void* frames, const melf_frames* f)
@@ -1157,7 +1160,8 @@ static int check_frames(const void* frames, const melf_frames* f)
 }
 
 static int batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride, int row_stride, int pix,
-                     void* d_results, melf_result* out_host, void* stream_, const YuvPlanes* yuv = nullptr, size_t yuv_extent = 0);
+                     void* d_results, melf_result* out_host, void* stream_, const YuvPlanes* yuv = nullptr, size_t yuv_extent = 0,
+                     const PlanarPlanes* planes = nullptr);
 
 extern "C" int melf_process_batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
                                       void* d_results, melf_result* out_host, void* stream_)
@@ -1254,10 +1258,52 @@ extern "C" int melf_process_yuv422_dev(melf_ctx* c, const void* d_frames, const 
     return batch_dev(c, d_frames, f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch, pix, d_results, out_host, stream_);
 }
 
-// melf_process_batch_dev / melf_process_frames_dev / melf_process_yuv_dev / melf_process_yuv422_dev after their argument checks:
-// the lane logic
+// The checks of a melf_planar_frames descriptor (melf_process_planes*); n == 0 passes.  *pl: the planes, *extent: the bytes of one
+// frame up to the last sample of its last plane.
+static int check_planes(const void* frames, const melf_planar_frames* f, PlanarPlanes* pl, size_t* extent)
+{
+    if (!f) return fail(MELF_ERR_INVALID, "planar frame descriptor is NULL");
+    if (f->n < 0 || f->H <= 0 || f->W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
+    if (f->reserved != 0) return fail(MELF_ERR_INVALID, "reserved field of the planar frame descriptor is not 0");
+    if (f->b_offset < 0 || f->g_offset < 0 || f->r_offset < 0) return fail(MELF_ERR_INVALID, "negative plane offset");
+    if (f->row_pitch < f->W) return fail(MELF_ERR_INVALID, "row_pitch smaller than a row");
+    if (f->row_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "row_pitch too large");
+    const int64_t span = (int64_t)(f->H - 1) * f->row_pitch + f->W;   // bytes of one plane, first to last sample
+    const int64_t off[3] = {f->b_offset, f->g_offset, f->r_offset};
+    int64_t hi = 0;
+    for (int a = 0; a < 3; ++a) {
+        if (off[a] > INT64_MAX - span) return fail(MELF_ERR_INVALID, "plane offset too large");
+        if (off[a] > hi) hi = off[a];
+        for (int b = a + 1; b < 3; ++b) {
+            const int64_t lo2 = off[a] < off[b] ? off[a] : off[b], hi2 = off[a] < off[b] ? off[b] : off[a];
+            if (hi2 - lo2 < span) return fail(MELF_ERR_INVALID, "two planes overlap");
+        }
+    }
+    if (f->frame_stride < hi + span) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
+    pl->b_off = f->b_offset; pl->g_off = f->g_offset; pl->r_off = f->r_offset;
+    *extent = (size_t)(hi + span);
+    if (f->n == 0) return MELF_SUCCESS;
+    if (!frames) return fail(MELF_ERR_INVALID, "frames pointer is NULL");
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_process_planes_dev(melf_ctx* c, const void* d_frames, const melf_planar_frames* f, void* d_results,
+                                       melf_result* out_host, void* stream_)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    PlanarPlanes pl;
+    size_t extent = 0;
+    if (int rc = check_planes(d_frames, f, &pl, &extent)) return rc;
+    if (f->n == 0) return MELF_SUCCESS;
+    return batch_dev(c, d_frames, f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch, PIX_PLANAR, d_results, out_host, stream_,
+                     nullptr, extent, &pl);
+}
+
+// melf_process_batch_dev / melf_process_frames_dev / melf_process_yuv_dev / melf_process_yuv422_dev / melf_process_planes_dev after
+// their argument checks: the lane logic
 static int batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride, int row_stride, int pix,
-                     void* d_results, melf_result* out_host, void* stream_, const YuvPlanes* yuv, size_t yuv_extent)
+                     void* d_results, melf_result* out_host, void* stream_, const YuvPlanes* yuv, size_t yuv_extent,
+                     const PlanarPlanes* planes)
 {
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream_;  // NULL = the null (legacy default) stream, as everywhere in HIP
@@ -1271,7 +1317,7 @@ static int batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, siz
         c->active_lane = lane;
         c->order_stream = st;
         c->order_valid = true;
-        const int rc = process_batch_on(c, d_frames, n, H, W, frame_stride, d_results, nullptr, ls, nullptr, row_stride, pix, yuv, yuv_extent);
+        const int rc = process_batch_on(c, d_frames, n, H, W, frame_stride, d_results, nullptr, ls, nullptr, row_stride, pix, yuv, yuv_extent, planes);
         c->order_valid = false;
         if (rc) return rc;
         HIP_TRY(hipEventRecord(c->ev_join[lane], ls));
@@ -1284,18 +1330,18 @@ static int batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, siz
         return MELF_SUCCESS;
     }
     if (int rc = acquire_lane(c, st, &c->active_lane)) return rc;
-    return process_batch_on(c, d_frames, n, H, W, frame_stride, d_results, out_host, st, nullptr, row_stride, pix, yuv, yuv_extent);
+    return process_batch_on(c, d_frames, n, H, W, frame_stride, d_results, out_host, st, nullptr, row_stride, pix, yuv, yuv_extent, planes);
 }
 
 static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
                             void* d_results, melf_result* out_host, hipStream_t st, const int* rect, int row_stride, int pix,
-                            const YuvPlanes* yuv, size_t yuv_extent)
+                            const YuvPlanes* yuv, size_t yuv_extent, const PlanarPlanes* planes)
 {
-    const int bpp = yuv ? 1 : (pix_p422(pix) ? 2 : pix_bytes(pix));
+    const int bpp = yuv || planes ? 1 : (pix_p422(pix) ? 2 : pix_bytes(pix));
     if (row_stride <= 0) row_stride = W * bpp;  // packed rows unless the caller's rows are padded (host-fed crops, pitched frames)
     // what the kernels may read of the last frame: its rows as far as they reach (the last row of a pitched buffer needs no
     // padding); the host-fed crops keep their staging pitch and spare bytes behind every crop
-    const size_t last_frame = yuv ? yuv_extent : (rect ? (size_t)H * row_stride : (size_t)(H - 1) * row_stride + (size_t)W * bpp);
+    const size_t last_frame = yuv || planes ? yuv_extent : (rect ? (size_t)H * row_stride : (size_t)(H - 1) * row_stride + (size_t)W * bpp);
     const melf_params& P = c->P;
     // numpy slicing img[y0:y1, x0:x1] clamps to the image (meterelf/_image.py:54-55)
     const int rx0 = rect ? rect[0] : P.rect_x0, ry0 = rect ? rect[1] : P.rect_y0;
@@ -1322,7 +1368,7 @@ static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int
         ms.readable = (size_t)(m - 1) * frame_stride + last_frame;
         int nparts = 0;
         MatchPartial* parts = nullptr;
-        if (int rc = run_match(c, ms, pix, m, bl, st, nullptr, &parts, &nparts, yuv)) return rc;
+        if (int rc = run_match(c, ms, pix, m, bl, st, nullptr, &parts, &nparts, yuv, planes)) return rc;
         DialsSrc ds;
         ds.base = base; ds.frame_stride = frame_stride; ds.row_stride = row_stride;
         ds.x0 = x0; ds.y0 = y0; ds.crop_rows = crows; ds.crop_cols = ccols;
@@ -1337,7 +1383,7 @@ static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int
         }
         {
             KernelTimer t(c, MELF_K_DIALS, st);
-            launch_dials(ds, pix, m, P, c->d_geom, c->d_rowmasks, parts, nparts, rw, res_dev + f0, st, c->ws_max, yuv);
+            launch_dials(ds, pix, m, P, c->d_geom, c->d_rowmasks, parts, nparts, rw, res_dev + f0, st, c->ws_max, yuv, planes);
         }
         HIP_TRY(hipGetLastError());
     }
@@ -1668,6 +1714,84 @@ extern "C" int melf_process_yuv422(melf_ctx* c, const void* frames_host, const m
     if (f->n == 0) return MELF_SUCCESS;
     if (!out_host) return fail(MELF_ERR_INVALID, "out_host is NULL");
     return batch_host_p422(c, (const uint8_t*)frames_host, f, pix, out_host);
+}
+
+// Planar host frames: the same pipeline.  What crosses PCIe per frame is a small planar frame: the crop's rows of the B, the G and
+// the R plane, one plane after the other at a 64-byte pitch in the staging buffer, which the kernels read with the rectangle at
+// its origin.  Rows are copied as they are: no byte is interleaved or reordered on the CPU.
+static int batch_host_planes(melf_ctx* c, const uint8_t* frames_host, const melf_planar_frames* f, melf_result* out_host)
+{
+    const int n = f->n, H = f->H, W = f->W;
+    HIP_TRY(hipSetDevice(c->device));
+    pool_use_device(c->device);
+    const melf_params& P = c->P;
+    const int x0 = P.rect_x0 < W ? P.rect_x0 : W, x1 = P.rect_x1 < W ? P.rect_x1 : W;
+    const int y0 = P.rect_y0 < H ? P.rect_y0 : H, y1 = P.rect_y1 < H ? P.rect_y1 : H;
+    const int crows = y1 - y0, ccols = x1 - x0;
+    if (x0 < 0 || y0 < 0 || crows < P.th || ccols < P.tw)
+        return fail(MELF_ERR_INVALID, "meter_rect crop is smaller than the dials template (cv2.matchTemplate would assert)");
+    const size_t pitch = ((size_t)ccols + 63) & ~(size_t)63;
+    const size_t plane = (size_t)crows * pitch;
+    PlanarPlanes sp;
+    sp.b_off = 0; sp.g_off = (int64_t)plane; sp.r_off = (int64_t)(2 * plane);
+    // + 128 spare bytes per small frame (the prep kernel's aligned windows reach past the last sample)
+    const size_t crop_stride = 3 * plane + 128;
+    const int chunk = 128;  // frames per pipeline stage (a multiple of the 32-frame MFMA group)
+    const size_t pin_need = (size_t)(n < chunk ? n : chunk) * crop_stride;
+    if (!c->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+    for (int b = 0; b < 2; ++b) {
+        if (!c->ev_h2d[b]) HIP_TRY(hipEventCreateWithFlags(&c->ev_h2d[b], hipEventDisableTiming));
+        if (c->pin_cap[b] < pin_need && (b == 0 || n > chunk)) {
+            if (c->h_pin[b]) { HIP_TRY(hipStreamSynchronize(c->copy_stream)); HIP_TRY(hipHostFree(c->h_pin[b])); }
+            c->h_pin[b] = nullptr;
+            c->pin_cap[b] = 0;
+            HIP_TRY(hipHostMalloc((void**)&c->h_pin[b], pin_need, hipHostMallocDefault));
+            c->pin_cap[b] = pin_need;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));  // the previous call's kernels may still read d_crops
+    if (int rc = grow(&c->d_crops, &c->crops_cap, (size_t)n * crop_stride)) return rc;
+    if (int rc = grow(&c->d_results, &c->results_cap, (size_t)n)) return rc;
+    if (int rc = acquire_lane(c, c->stream, &c->active_lane)) return rc;
+    const int rect[4] = {0, 0, ccols, crows};
+    const int64_t src_off[3] = {f->b_offset, f->g_offset, f->r_offset};
+    int k = 0;
+    for (int f0 = 0; f0 < n; f0 += chunk, ++k) {
+        const int m = n - f0 < chunk ? n - f0 : chunk;
+        const int b = k & 1;
+        if (k >= 2) HIP_TRY(hipEventSynchronize(c->ev_h2d[b]));  // the copy that last read this staging buffer is done
+        uint8_t* pin = c->h_pin[b];
+        // work items: the crop's rows of one plane of a frame in blocks of 32
+        const int rblocks = (crows + 31) / 32;
+        host_pool().run(m * 3 * rblocks, [&](int item) {
+            const int i = item / (3 * rblocks), rest = item - i * 3 * rblocks, p = rest / rblocks, part = rest - p * rblocks;
+            const uint8_t* src = frames_host + (size_t)(f0 + i) * (size_t)f->frame_stride + (size_t)src_off[p] + (size_t)x0;
+            uint8_t* dst = pin + (size_t)i * crop_stride + (size_t)p * plane;
+            const int r0 = part * 32, r1 = r0 + 32 < crows ? r0 + 32 : crows;
+            for (int y = r0; y < r1; ++y) memcpy(dst + (size_t)y * pitch, src + (size_t)(y0 + y) * (size_t)f->row_pitch, (size_t)ccols);
+        });
+        uint8_t* d_chunk = c->d_crops + (size_t)f0 * crop_stride;
+        HIP_TRY(hipMemcpyAsync(d_chunk, pin, (size_t)m * crop_stride, hipMemcpyHostToDevice, c->copy_stream));
+        HIP_TRY(hipEventRecord(c->ev_h2d[b], c->copy_stream));
+        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_h2d[b], 0));
+        if (int rc = process_batch_on(c, d_chunk, m, crows, ccols, crop_stride, c->d_results + f0, nullptr, c->stream, rect, (int)pitch,
+                                      PIX_PLANAR, nullptr, crop_stride, &sp))
+            return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(out_host, c->d_results, (size_t)n * sizeof(melf_result), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_process_planes(melf_ctx* c, const void* frames_host, const melf_planar_frames* f, melf_result* out_host)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    PlanarPlanes pl;
+    size_t extent = 0;
+    if (int rc = check_planes(frames_host, f, &pl, &extent)) return rc;
+    if (f->n == 0) return MELF_SUCCESS;
+    if (!out_host) return fail(MELF_ERR_INVALID, "out_host is NULL");
+    return batch_host_planes(c, (const uint8_t*)frames_host, f, out_host);
 }
 
 // ---------------------------------------------------------- stage entries ----
@@ -2042,7 +2166,7 @@ static thread_local std::function<void()>* tl_jpeg_enqueued = nullptr;
 // here waits for the context's stream; what protects a ring slot is its own pair of events, across calls as within one.
 static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
                             void* d_results, melf_result* out_host, hipStream_t st, const int* rect, int row_stride, int pix,
-                            const YuvPlanes* yuv, size_t yuv_extent);
+                            const YuvPlanes* yuv, size_t yuv_extent, const PlanarPlanes* planes);
 // What a caller inside the library may already have of the files it hands to the decode path (the file-name entry points
 // do): the parsed headers + Huffman decode data (of file index[k] of that parse for the call's file k), and the pinned buffer
 // the files' bytes lie in.

@@ -39,6 +39,14 @@ struct YuvPlanes {
 constexpr int PIX_YUYV = 24, PIX_UYVY = 25, PIX_YVYU = 26;
 inline bool pix_p422(int pix) { return pix >= PIX_YUYV && pix <= PIX_YVYU; }
 inline uint32_t p422_sel(int pix) { return pix == PIX_UYVY ? 0x02030001u : (pix == PIX_YVYU ? 0x01020300u : 0x03020100u); }
+// Planar frames (melf_process_planes*): the launch's pix.  Three planes of one byte per sample; base, frame_stride and row_stride
+// (bytes, any alignment) describe a frame and the rows of each of its planes, PlanarPlanes where the planes start inside a frame
+// (which gives the channel order), x0 and cols count pixels.  `readable` counts from base to the last sample of the last frame's
+// last plane: no load may start before base or end behind base + readable.
+constexpr int PIX_PLANAR = 32;
+struct PlanarPlanes {
+    int64_t b_off, g_off, r_off;  // bytes from a frame's first byte to the first sample of its B / G / R plane
+};
 
 // ---- K2: template match -----------------------------------------------------
 // One partial (max, first-argmax) per workgroup tile of the correlation map.
@@ -74,7 +82,7 @@ struct MatchSrc {
 
 void launch_match(const MatchSrc& src, int pix, int n, const MatchGeom& g, const uint32_t* d_tplT,
                   float* d_result_map, MatchPartial* d_partials, int* nparts_out, hipStream_t stream,
-                  const YuvPlanes* yuv = nullptr /* pix_yuv(pix) */);
+                  const YuvPlanes* yuv = nullptr /* pix_yuv(pix) */, const PlanarPlanes* planes = nullptr /* PIX_PLANAR */);
 int match_parts(const MatchGeom& g, int rows, int cols);
 
 // ---- K2 on the matrix cores (k_match_mfma.hip) --------------------------------
@@ -89,7 +97,7 @@ MfmaPlan mfma_plan(int th, int tw, int rows, int cols, int nframes);
 size_t mfma_atab_bytes(int th);
 void mfma_build_atab(const uint8_t* templ, int th, int tw, int8_t* atab);
 void launch_mfma_prep(const MatchSrc& src, int pix, int n, const MfmaPlan& p, int th, int tw, int8_t* d_lg,
-                      uint16_t* d_r, hipStream_t stream, const YuvPlanes* yuv = nullptr);
+                      uint16_t* d_r, hipStream_t stream, const YuvPlanes* yuv = nullptr, const PlanarPlanes* planes = nullptr);
 // launch_mfma_match: d_ws = the row-window sums R in epilogue order (k_prep_lplane); the waves add them up
 void launch_mfma_match(int n, const MfmaPlan& p, int th, int tw, long tsum, double tmean, const int8_t* d_atab,
                        const int8_t* d_lg, const uint32_t* d_ws, float* d_result_map, MatchPartial* d_partials,
@@ -127,7 +135,8 @@ void launch_gen_match(int n, const GenPlan& p, int rows, int th, int tw, long ts
 // prep for either matrix-core kernel: Lg (fragment order) and the row-window sums R in the match waves' epilogue order
 // (pairs > 0: the tuned kernel's paired-operand row layout, see k_prep_lplane)
 void launch_match_prep(const MatchSrc& src, int pix, int n, int groups, int rows_pad, int nkb, int rwp, int tw, int8_t* d_lg,
-                       uint16_t* d_r, hipStream_t stream, int pairs = 0, const YuvPlanes* yuv = nullptr);
+                       uint16_t* d_r, hipStream_t stream, int pairs = 0, const YuvPlanes* yuv = nullptr,
+                       const PlanarPlanes* planes = nullptr);
 
 // ---- K3: per-dial reading ---------------------------------------------------
 struct DialGeom {
@@ -148,7 +157,7 @@ struct DialsSrc {
 void launch_dials(const DialsSrc& src, int pix, int n, const melf_params& P, const DialGeom* d_geom,
                   const uint64_t* d_rowmasks /* [ndials][3][64] */, const MatchPartial* d_partials,
                   int nparts, int rw, melf_result* d_results, hipStream_t stream, int ws_max /* largest DialGeom::ws */,
-                  const YuvPlanes* yuv = nullptr /* pix_yuv(pix) */);
+                  const YuvPlanes* yuv = nullptr /* pix_yuv(pix) */, const PlanarPlanes* planes = nullptr /* PIX_PLANAR */);
 
 // ---- K1b / HLS --------------------------------------------------------------
 void launch_bgr2hls(const uint8_t* d_src, int rows, int cols, size_t row_stride, int hue_shift,

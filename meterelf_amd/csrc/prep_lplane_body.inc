@@ -11,6 +11,11 @@
 //   With MELF_P422_BODY defined instead (k_p422_lplane): PX 22 = packed YUV 4:2:2 frames, two pixels per aligned 4-byte macropixel,
 //       its byte order the runtime permute selector psel (-> Y0 U Y1 V).  The same even-pixel window is 17 consecutive aligned
 //       dwords, each with both Y samples and the chroma pair: no gather, no chroma loads; the odd origin as above.
+//   With MELF_PLANAR_BODY defined instead (k_planar_lplane): PX 23 = planar frames (melf_process_planes*), the B, G and R planes at
+//       `planes` (PlanarPlanes) in a frame, any byte alignment.  A lane's 32 pixels are 32 consecutive bytes of each plane: nine
+//       aligned dwords per plane, shifted by v_alignbit at that plane's own byte phase (the three phases differ when offsets and
+//       pitch are arbitrary).  The aligned window reaches up to 3 bytes to the left of the lane's first sample and up to 35 behind it:
+//       it must not start before the caller's base nor end behind the buffer, or the lane takes byte loads.
     constexpr int PB = PX == 4 ? 4 : 3;         // bytes per pixel of the frame reads
     constexpr int WIN = PX == 4 ? 128 : 100;    // bytes a lane's 32-pixel load window spans
     __shared__ __attribute__((aligned(16))) uint32_t tile[8 * 2 * 32 * 4];  // [kb][h][n][16 B], one chunk of 8 blocks
@@ -38,6 +43,15 @@
     const int xodd = src.x0 & 1;
     const bool rows_safe = (size_t)min(grp * 32 + 31, nframes - 1) * src.frame_stride + (size_t)(src.y0 + y) * src.row_stride +
                            (size_t)((src.x0 & ~1) + 32 * (nkb - 1)) * 2 + 68 <= src.readable;
+#elif defined(MELF_PLANAR_BODY)
+    (void)PB; (void)WIN;
+    // (the same for the three 36-byte windows of a planar lane, and for their first dword: with a base that is not 4-byte aligned
+    // the aligned window of the very first samples of the buffer would start before it)
+    const uint32_t pl_bm = (uint32_t)((size_t)src.base & 3);
+    const size_t pl_row = (size_t)(src.y0 + y) * src.row_stride + (size_t)src.x0;
+    const size_t pl_lo = (size_t)min(min(planes.b_off, planes.g_off), planes.r_off), pl_hi = (size_t)max(max(planes.b_off, planes.g_off), planes.r_off);
+    const bool rows_safe = (pl_bm == 0 || (size_t)grp * 32 * src.frame_stride + pl_lo + pl_row >= 3) &&
+                           (size_t)min(grp * 32 + 31, nframes - 1) * src.frame_stride + pl_hi + pl_row + (size_t)(32 * (nkb - 1)) + 36 <= src.readable;
 #else
     const bool rows_safe = (size_t)min(grp * 32 + 31, nframes - 1) * src.frame_stride + (size_t)(src.y0 + y) * src.row_stride +
                            (size_t)(src.x0 + 32 * (nkb - 1)) * PB + WIN <= src.readable;
@@ -161,6 +175,43 @@
                         const uint32_t m = __builtin_amdgcn_perm(0u, ((const uint32_t*)prow)[fx >> 1], psel);
                         const YuvChroma c = yuv_chroma((int)((m >> 8) & 255u), (int)(m >> 24));
                         const int L = yuv_lightness((int)((fx & 1 ? m >> 16 : m) & 255u), yuv_cmax(c), yuv_cmin(c));
+                        w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
+                    }
+                }
+            } else
+#elif defined(MELF_PLANAR_BODY)
+            if (PX == 23) {
+                // the lane's first sample in each plane, from the caller's base, and its byte phase there
+                const size_t o = (size_t)f * src.frame_stride + (size_t)(src.y0 + y) * src.row_stride + (size_t)(src.x0 + xbeg);
+                const size_t ob = o + (size_t)planes.b_off, og = o + (size_t)planes.g_off, orr = o + (size_t)planes.r_off;
+                const uint32_t mb = (pl_bm + (uint32_t)ob) & 3u, mg = (pl_bm + (uint32_t)og) & 3u, mr = (pl_bm + (uint32_t)orr) & 3u;
+                // nine aligned dwords per plane cover its 32 bytes at any phase; the windows may reach past the crop and the row (never
+                // used: masked) but must stay inside the caller's buffer, at its first bytes as well as at its last
+                if (rows_safe || (ob >= mb && og >= mg && orr >= mr && ob - mb + 36 <= src.readable && og - mg + 36 <= src.readable &&
+                                  orr - mr + 36 <= src.readable)) {
+                    const uint32_t* qb = (const uint32_t*)(src.base + (ob - mb));
+                    const uint32_t* qg = (const uint32_t*)(src.base + (og - mg));
+                    const uint32_t* qr = (const uint32_t*)(src.base + (orr - mr));
+                    uint32_t db[9], dg[9], dr[9];
+#pragma unroll
+                    for (int i = 0; i < 9; ++i) { db[i] = qb[i]; dg[i] = qg[i]; dr[i] = qr[i]; }
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        // four pixels: their B, G and R samples, one dword each
+                        const uint32_t B = __builtin_amdgcn_alignbit(db[i + 1], db[i], mb * 8u), G = __builtin_amdgcn_alignbit(dg[i + 1], dg[i], mg * 8u),
+                                       Rr = __builtin_amdgcn_alignbit(dr[i + 1], dr[i], mr * 8u);
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) {
+                            const int L = hls_lightness_fast((B >> (8 * k)) & 255, (G >> (8 * k)) & 255, (Rr >> (8 * k)) & 255);
+                            w[i] |= (uint32_t)((L - 128) & 255) << (8 * k);
+                        }
+                    }
+                } else {  // first / last bytes of the frame buffer: byte loads, the crop's own samples only
+                    const uint8_t* pb = src.base + ob;
+                    const uint8_t* pg = src.base + og;
+                    const uint8_t* pr = src.base + orr;
+                    for (int k = 0; k < npx; ++k) {
+                        const int L = hls_lightness(pb[k], pg[k], pr[k]);
                         w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
                     }
                 }

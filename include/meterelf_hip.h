@@ -175,13 +175,33 @@ int melf_process_frames_dev(melf_ctx* ctx, const void* d_frames, const melf_fram
 
 /* ---- the same path for YUV 4:2:0 video frames: NV12 (hardware decoders, capture stacks), I420 / YV12 (software decoders) ----
  * The records are byte-identical to melf_process_batch(_dev) on the packed BGR frame that the conversion below makes of each
- * frame (the constants of cv2.cvtColor(COLOR_YUV2BGR_NV12 / _I420): BT.601, limited range), without a conversion pass: the
- * kernels read the planes in place, and only the meter_rect crop of them.  In integers, >> arithmetic:
+ * frame, without a conversion pass: the kernels read the planes in place, and only the meter_rect crop of them.  In integers,
+ * >> arithmetic, with the offset and the five coefficients of the descriptor's matrix:
  *     chroma: the nearest sample, no interpolation: pixel (x, y) uses U[y >> 1][x >> 1], V[y >> 1][x >> 1]
- *     yy = max(Y - 16, 0) * 1220542          u = U - 128          v = V - 128
- *     R = clamp((yy + (1 << 19) + 1673527 * v)              >> 20, 0, 255)
- *     G = clamp((yy + (1 << 19) -  852492 * v - 409993 * u) >> 20, 0, 255)
- *     B = clamp((yy + (1 << 19) + 2116026 * u)              >> 20, 0, 255)
+ *     yy = max(Y - YOFF, 0) * CY             u = U - 128          v = V - 128
+ *     R = clamp((yy + (1 << 19) + CRV * v)           >> 20, 0, 255)
+ *     G = clamp((yy + (1 << 19) + CGV * v + CGU * u) >> 20, 0, 255)
+ *     B = clamp((yy + (1 << 19) + CBU * u)           >> 20, 0, 255)
+ *
+ *     code  matrix                    YOFF       CY      CRV      CGV      CGU      CBU
+ *       0   MELF_YUV_BT601_LIMITED      16  1220542  1673527  -852492  -409993  2116026
+ *       2   MELF_YUV_BT601_FULL          0  1048576  1470104  -748826  -360853  1858077
+ *       3   MELF_YUV_BT709_LIMITED      16  1220945  1879825  -558796  -223607  2215014
+ *       4   MELF_YUV_BT709_FULL          0  1048576  1651297  -490864  -196424  1945738
+ * Frames as they come from: 0 cv2.cvtColor(COLOR_YUV2BGR_NV12 / _I420 / _YUY2 ..), SD video; 2 MJPEG webcams and phone cameras
+ * (JFIF; ffmpeg's yuvj420p / yuvj422p, raw UVC); 3 H.264 / HEVC of HD cameras out of a hardware decoder; 4 screen and capture
+ * pipelines.
+ *
+ * Code 1 is never assigned and stays MELF_ERR_INVALID (it was the one rejected code callers tested against while code 0 was the
+ * only matrix).  Row 0 keeps the three-decimal constants of cv2 bit for bit.  Rows 2 - 4 are round(2^20 c) of the standards'
+ * exact coefficients: with Kr, Kb = 0.299, 0.114 (BT.601) or 0.2126, 0.0722 (BT.709) and Kg = 1 - Kr - Kb, c is 2 (1 - Kr) for
+ * CRV, 2 (1 - Kb) for CBU, -Kb 2 (1 - Kb) / Kg for CGU, -Kr 2 (1 - Kr) / Kg for CGV and 1 for CY; limited range scales the
+ * chroma coefficients by 255 / 224 and CY by 255 / 219.  Over all 2^24 (Y, U, V) every product fits a 24-bit multiply, every sum
+ * stays below 2^30 in magnitude, and every channel is within 1 of the float64 conversion rounded half up and clipped (8 924
+ * triples differ from it at all under code 2, 1 315 under code 3, none under code 4).  Code 2 is the JFIF matrix but not
+ * libjpeg's tables bit for bit: libjpeg rounds the chroma terms separately at 16 bits, and 8 332 triples differ by 1 (the JPEG
+ * entry points below decode with libjpeg's own arithmetic and are not affected by any of this).
+ * Out of scope: BT.2020, 10-bit formats, interpolated chroma, chroma siting, 4:4:4 and planar 4:2:2 layouts.
  * Frame f starts at frames + f * frame_stride; its Y row y at + y * y_pitch (W bytes), its chroma row y >> 1 at
  * + u_offset / v_offset + (y >> 1) * c_pitch: NV12 W bytes U V U V .. (v_offset == u_offset + 1), I420 W / 2 bytes per plane.
  * YV12 is I420 with the two offsets exchanged.  The buffer must hold every plane of every frame up to the last sample of its
@@ -189,7 +209,8 @@ int melf_process_frames_dev(melf_ctx* ctx, const void* d_frames, const melf_fram
  * plane that overlaps the Y plane, an unknown format or matrix or a NULL descriptor return MELF_ERR_INVALID before anything is
  * launched or copied. */
 enum { MELF_YUV_NV12 = 0, MELF_YUV_I420 = 1 };
-enum { MELF_YUV_BT601_LIMITED = 0 };            /* the only matrix; anything else: MELF_ERR_INVALID */
+enum { MELF_YUV_BT601_LIMITED = 0, MELF_YUV_BT601_FULL = 2, MELF_YUV_BT709_LIMITED = 3, MELF_YUV_BT709_FULL = 4 };
+                                                /* matrix; anything else, 1 included: MELF_ERR_INVALID    */
 typedef struct melf_yuv_frames {
     int32_t format, matrix;
     int32_t n, H, W;                            /* H and W even                                           */
@@ -212,8 +233,9 @@ int melf_yuv_to_bgr(melf_ctx* ctx, const void* frames_host, const melf_yuv_frame
 
 /* ---- the same path for packed YUV 4:2:2 frames: YUYV / YUY2 (UVC webcams, V4L2), UYVY (SDI / HDMI capture cards), YVYU ----
  * The records are byte-identical to melf_process_batch(_dev) on the packed BGR frame that the conversion makes of each frame
- * (cv2.cvtColor(COLOR_YUV2BGR_YUY2 / _UYVY / _YVYU): the integer formulas and constants above, BT.601, limited range), which
- * replaces the BGR copy of every frame such a caller had to write: that frame is never formed, the kernels read the
+ * (the integer formulas above under the descriptor's matrix, any of the four; MELF_YUV_BT601_LIMITED is
+ * cv2.cvtColor(COLOR_YUV2BGR_YUY2 / _UYVY / _YVYU)), which replaces the BGR copy of every frame such a caller had to write: that
+ * frame is never formed, the kernels read the
  * macropixels in place, and only the meter_rect crop of them.
  *     chroma: the two pixels of a macropixel share its U and V; no interpolation, no vertical subsampling
  * Frame f starts at frames + f * frame_stride, its row y at + y * row_pitch: W / 2 macropixels of 4 bytes, two pixels each, in
@@ -225,7 +247,7 @@ int melf_yuv_to_bgr(melf_ctx* ctx, const void* frames_host, const melf_yuv_frame
  * before anything is launched or copied; n == 0 passes. */
 enum { MELF_YUV422_YUYV = 0, MELF_YUV422_UYVY = 1, MELF_YUV422_YVYU = 2 };   /* bytes of a macropixel: Y0 U Y1 V / U Y0 V Y1 / Y0 V Y1 U */
 typedef struct melf_yuv422_frames {
-    int32_t format, matrix;                     /* MELF_YUV422_*; matrix: MELF_YUV_BT601_LIMITED only     */
+    int32_t format, matrix;                     /* MELF_YUV422_*; matrix: MELF_YUV_BT* as above           */
     int32_t n, H, W;                            /* W even, H any                                          */
     int32_t reserved;
     int64_t row_pitch;                          /* bytes between rows, >= 2 * W                           */

@@ -173,14 +173,18 @@ class MeterReader:
                                     want_host=False, stream=stream.cuda_stream)
         return out
 
-    def read_yuv_frames(self, frames, pixel_format: str = 'nv12', out=None):
-        """YUV 4:2:0 video frames -> records, equal to read_frames() of the packed BGR frames that the BT.601 limited-range
-        conversion of include/meterelf_hip.h makes of them (melf_process_yuv*); the planes are read in place, no conversion pass.
+    def read_yuv_frames(self, frames, pixel_format: str = 'nv12', matrix='bt601', out=None):
+        """YUV 4:2:0 video frames -> records, equal to read_frames() of the packed BGR frames that the integer conversion of
+        include/meterelf_hip.h makes of them under `matrix` (melf_process_yuv*); the planes are read in place, no conversion pass.
+        matrix: what the frames are encoded with, a name of _hip.YUV_MATRIX_CODES or a code -- 'bt709' for H.264 / HEVC of an HD IP
+        camera as a hardware decoder leaves it in NV12; 'bt601-full' for MJPEG webcams and phone cameras decoded by ffmpeg (yuvj420p)
+        or delivered raw over UVC; 'bt709-full' for screen and capture pipelines; 'bt601' (the default: limited range, what
+        cv2.cvtColor(COLOR_YUV2BGR_NV12) assumes).  The wrong matrix shifts hue and lightness, which is what the dials are read from.
         frames: the conventional (N, H * 3 // 2, W) uint8 array, a numpy array / torch CPU tensor (host path) or a torch tensor on
         this reader's GPU (enqueued on torch.cuda.current_stream); pixel_format 'nv12', 'i420' or 'yv12' (_hip.yuv_frames_view says
         which layouts are read in place).  out: a uint8 device tensor (N, RESULT_DTYPE.itemsize) on the same GPU that receives the
         records without synchronising the stream (device frames only); returns it.  Otherwise returns the records."""
-        v = _hip.yuv_frames_view(frames, pixel_format)
+        v = _hip.yuv_frames_view(frames, pixel_format, matrix)
         desc = v.descriptor()
         if not v.on_device:
             if out is not None:
@@ -200,15 +204,17 @@ class MeterReader:
         self.ctx.process_yuv_dev(v.ptr, desc, d_results_ptr=out.data_ptr(), want_host=False, stream=stream.cuda_stream)
         return out
 
-    def read_yuv422_frames(self, frames, pixel_format: str = 'yuyv', out=None):
+    def read_yuv422_frames(self, frames, pixel_format: str = 'yuyv', matrix='bt601', out=None):
         """Packed YUV 4:2:2 frames (UVC / V4L2 YUYV, capture-card UYVY, YVYU) -> records, equal to read_frames() of the packed BGR
-        frames that the BT.601 limited-range conversion of include/meterelf_hip.h makes of them (melf_process_yuv422*); the
-        macropixels are read in place, no conversion pass.  frames: the conventional (N, H, W, 2) uint8 array, a numpy array /
-        torch CPU tensor (host path) or a torch tensor on this reader's GPU (enqueued on torch.cuda.current_stream); pixel_format
+        frames that the integer conversion of include/meterelf_hip.h makes of them under `matrix` (melf_process_yuv422*); the
+        macropixels are read in place, no conversion pass.  matrix as for read_yuv_frames: 'bt601-full' for MJPEG webcams and phone
+        cameras (ffmpeg's yuvj422p, raw UVC), 'bt709' for HD capture cards and decoders, 'bt709-full' for screen and capture
+        pipelines, 'bt601' (the default) limited range as cv2 assumes.  frames: the conventional (N, H, W, 2) uint8 array, a numpy
+        array / torch CPU tensor (host path) or a torch tensor on this reader's GPU (enqueued on torch.cuda.current_stream); pixel_format
         'yuyv' (or 'yuy2'), 'uyvy' or 'yvyu' (_hip.yuv422_frames_view says which layouts are read in place).  out: a uint8 device
         tensor (N, RESULT_DTYPE.itemsize) on the same GPU that receives the records without synchronising the stream (device
         frames only); returns it.  Otherwise returns the records."""
-        v = _hip.yuv422_frames_view(frames, pixel_format)
+        v = _hip.yuv422_frames_view(frames, pixel_format, matrix)
         desc = v.descriptor()
         if not v.on_device:
             if out is not None:

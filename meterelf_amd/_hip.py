@@ -81,9 +81,14 @@ class MelfYuvFrames(C.Structure):
 
 # YUV 4:2:0 layouts of melf_process_yuv* (MELF_YUV_*); 'yv12' is I420 with the two chroma planes exchanged
 YUV_NV12, YUV_I420 = 0, 1
-YUV_BT601_LIMITED = 0
+# colour conversion of YUV frames, 4:2:0 and 4:2:2 alike (MELF_YUV_BT*, include/meterelf_hip.h has the coefficients); 1 is never
+# assigned.
+# Which sources produce which: 'bt709' (limited range) H.264 / HEVC of an HD camera as a hardware decoder leaves it in NV12;
+# 'bt601-full' MJPEG webcams and phone cameras (JFIF: ffmpeg's yuvj420p / yuvj422p, raw UVC); 'bt709-full' screen and capture
+# pipelines; 'bt601' (limited range) what cv2.cvtColor(COLOR_YUV2BGR_*) assumes, SD video.
+YUV_BT601_LIMITED, YUV_BT601_FULL, YUV_BT709_LIMITED, YUV_BT709_FULL = 0, 2, 3, 4
+YUV_MATRIX_CODES = {'bt601': YUV_BT601_LIMITED, 'bt601-full': YUV_BT601_FULL, 'bt709': YUV_BT709_LIMITED, 'bt709-full': YUV_BT709_FULL}
 YUV_CODES = {'nv12': YUV_NV12, 'i420': YUV_I420, 'yv12': YUV_I420}
-
 
 
 class MelfYuv422Frames(C.Structure):
@@ -329,6 +334,21 @@ def frames_view(frames, pixel_format='bgr'):
     return FramesView(int(ptr), on_device, device, code, n, H, W, int(rp), int(fs), int(extent), not ok, frames)
 
 
+def yuv_matrix_code(matrix):
+    """The MELF_YUV_BT* code of a matrix given by name (YUV_MATRIX_CODES) or by code; anything else: ValueError."""
+    if isinstance(matrix, str):
+        code = YUV_MATRIX_CODES.get(matrix.lower())
+    else:
+        try:
+            code = int(matrix) if int(matrix) == matrix and int(matrix) in YUV_MATRIX_CODES.values() else None
+        except (TypeError, ValueError):
+            code = None
+    if code is None:
+        raise ValueError('matrix %r is not a YUV matrix (%s, or a code out of %s)'
+                         % (matrix, ', '.join(YUV_MATRIX_CODES), sorted(YUV_MATRIX_CODES.values())))
+    return code
+
+
 class YuvFramesView(NamedTuple):
     """How the kernels read a batch of YUV 4:2:0 frames in place (yuv_frames_view)."""
     ptr: int            # address of frame 0's first Y sample
@@ -346,20 +366,25 @@ class YuvFramesView(NamedTuple):
     extent: int         # bytes read from ptr: every plane of every frame up to the last sample of its last row
     copied: bool        # the layout could not be described and the frames were copied once to a packed array
     array: object       # what ptr points into (the caller's array, or the copy): keep it alive while the call runs
+    matrix: int = YUV_BT601_LIMITED   # YUV_BT* code of the colour conversion
 
     def descriptor(self):
-        return MelfYuvFrames(self.format, YUV_BT601_LIMITED, self.n, self.H, self.W, 0, self.y_pitch, self.c_pitch, self.u_offset,
+        return MelfYuvFrames(self.format, self.matrix, self.n, self.H, self.W, 0, self.y_pitch, self.c_pitch, self.u_offset,
                              self.v_offset, self.frame_stride)
 
 
-def yuv_frames_view(frames, pixel_format='nv12'):
+def yuv_frames_view(frames, pixel_format='nv12', matrix='bt601'):
     """Describes the conventional (N, H * 3 // 2, W) uint8 array of YUV 4:2:0 frames (numpy array or torch tensor) as
     melf_process_yuv* read it: rows 0 .. H - 1 are Y; 'nv12': rows H .. H * 3 // 2 - 1 are the interleaved U V rows; 'i420': the
     H * W // 4 bytes behind the Y rows are the U plane (rows of W // 2), the next H * W // 4 the V plane; 'yv12': V first.
     'nv12' honours the row stride and the frame stride in place (frames[:, :, :w], frames[::2], frames[a:b]); the planar formats
     are read in place when the rows are contiguous (row stride == W: their chroma rows are half rows of the array), otherwise the
     frames are copied once to a packed array (YuvFramesView.copied), as is any layout with an element stride other than 1 or
-    negative strides.  Not uint8, not three-dimensional, an odd H or W, or an unknown format: ValueError."""
+    negative strides.  matrix: the frames' colour conversion, a name of YUV_MATRIX_CODES or a YUV_BT* code: 'bt601' (limited range,
+    cv2's convention), 'bt709' (H.264 / HEVC of an HD camera out of a hardware decoder), 'bt601-full' (MJPEG webcams and phone
+    cameras: ffmpeg's yuvj420p, raw UVC), 'bt709-full' (screen and capture pipelines).  Not uint8, not three-dimensional, an odd H
+    or W, an unknown format or an unknown matrix: ValueError."""
+    mcode = yuv_matrix_code(matrix)
     is_torch = _is_torch(frames)
     if is_torch:
         if str(frames.dtype) != 'torch.uint8':
@@ -407,7 +432,7 @@ def yuv_frames_view(frames, pixel_format='nv12'):
         last = (rows - 1) * rp + W
     extent = (n - 1) * fs + last if n else 0
     return YuvFramesView(int(ptr), on_device, device, code, n, H, W, int(rp), int(c_pitch), int(u_off), int(v_off), int(fs), int(extent),
-                         not ok, frames)
+                         not ok, frames, mcode)
 
 
 class Yuv422FramesView(NamedTuple):
@@ -424,19 +449,22 @@ class Yuv422FramesView(NamedTuple):
     extent: int         # bytes read from ptr: (n - 1) * frame_stride + (H - 1) * row_pitch + 2 * W
     copied: bool        # the layout could not be described and the frames were copied once to a packed array
     array: object       # what ptr points into (the caller's array, or the copy): keep it alive while the call runs
+    matrix: int = YUV_BT601_LIMITED   # YUV_BT* code of the colour conversion
 
     def descriptor(self):
-        return MelfYuv422Frames(self.format, YUV_BT601_LIMITED, self.n, self.H, self.W, 0, self.row_pitch, self.frame_stride)
+        return MelfYuv422Frames(self.format, self.matrix, self.n, self.H, self.W, 0, self.row_pitch, self.frame_stride)
 
 
-def yuv422_frames_view(frames, pixel_format='yuyv'):
+def yuv422_frames_view(frames, pixel_format='yuyv', matrix='bt601'):
     """Describes the conventional (N, H, W, 2) uint8 array of packed YUV 4:2:2 frames (numpy array or torch tensor) as
     melf_process_yuv422* read it: the two bytes of pixel x are bytes 2 x, 2 x + 1 of its row, 'yuyv' (or 'yuy2'): Y0 U Y1 V per
     pair of pixels, 'uyvy': U Y0 V Y1, 'yvyu': Y0 V Y1 U.  The row stride and the frame stride are honoured in place
     (frames[:, :, :w], frames[::2], frames[a:b]).  A layout the descriptor cannot express -- an element or pixel stride other
     than 1 / 2, a base, row stride or frame stride that is not a multiple of 4, negative strides -- is copied once to a packed
-    array (Yuv422FramesView.copied).  Not uint8, not four-dimensional, a last dimension other than 2, an odd or zero W, a zero
-    H, or an unknown format name: ValueError."""
+    array (Yuv422FramesView.copied).  matrix: the frames' colour conversion as for yuv_frames_view, a name of YUV_MATRIX_CODES or a
+    YUV_BT* code (raw UVC webcams deliver 'bt601-full', HD capture cards 'bt709').  Not uint8, not four-dimensional, a last dimension
+    other than 2, an odd or zero W, a zero H, an unknown format name or an unknown matrix: ValueError."""
+    mcode = yuv_matrix_code(matrix)
     is_torch = _is_torch(frames)
     if is_torch:
         if str(frames.dtype) != 'torch.uint8':
@@ -479,7 +507,7 @@ def yuv422_frames_view(frames, pixel_format='yuyv'):
         (rp, fs) = (W * 2, H * W * 2)
         ptr = frames.data_ptr() if is_torch else frames.ctypes.data
     extent = (n - 1) * fs + (H - 1) * rp + W * 2 if n else 0
-    return Yuv422FramesView(int(ptr), on_device, device, code, n, H, W, int(rp), int(fs), int(extent), not ok, frames)
+    return Yuv422FramesView(int(ptr), on_device, device, code, n, H, W, int(rp), int(fs), int(extent), not ok, frames, mcode)
 
 
 class PlanarFramesView(NamedTuple):

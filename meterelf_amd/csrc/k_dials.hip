@@ -289,10 +289,11 @@ __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_v
 }
 
 // NV12 / I420 frames (melf_process_yuv*): src describes the Y plane, yuv the chroma planes; PLANAR: separate U and V planes
-// (I420, YV12) instead of interleaved pairs (NV12).  Past its loads the body is the one of 4-byte B G R pixels.
+// (I420, YV12) instead of interleaved pairs (NV12).  Past its loads the body is the one of 4-byte B G R pixels.  ymat: the frames'
+// colour conversion, the same for every lane (SGPRs), so that the matrices share the NR instantiations.
 #define MELF_YUV_BODY
 template <bool PLANAR, int NR>
-__global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_vgpr(DIALS_VGPRS))) void k_yneedle(DialsSrc src, YuvPlanes yuv, melf_params P,
+__global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_vgpr(DIALS_VGPRS))) void k_yneedle(DialsSrc src, YuvPlanes yuv, YuvMatrix ymat, melf_params P,
                                                                 const DialGeom* __restrict__ geom,
                                                                 const uint64_t* __restrict__ rowmasks,
                                                                 const MatchPartial* __restrict__ partials,
@@ -310,7 +311,7 @@ __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_v
 // frames' order (YUYV, UYVY, YVYU) to Y0 U Y1 V, a runtime value, so that the formats share the NR instantiations.
 #define MELF_P422_BODY
 template <int NR>
-__global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_vgpr(DIALS_VGPRS))) void k_p422_needle(DialsSrc src, uint32_t psel, melf_params P,
+__global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_vgpr(DIALS_VGPRS))) void k_p422_needle(DialsSrc src, uint32_t psel, YuvMatrix ymat, melf_params P,
                                                                 const DialGeom* __restrict__ geom,
                                                                 const uint64_t* __restrict__ rowmasks,
                                                                 const MatchPartial* __restrict__ partials,
@@ -344,7 +345,8 @@ __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_v
 
 void launch_dials(const DialsSrc& src, int pix, int n, const melf_params& P, const DialGeom* d_geom,
                   const uint64_t* d_rowmasks, const MatchPartial* d_partials, int nparts, int rw,
-                  melf_result* d_results, hipStream_t stream, int ws_max, const YuvPlanes* yuv, const PlanarPlanes* planes)
+                  melf_result* d_results, hipStream_t stream, int ws_max, const YuvPlanes* yuv, const PlanarPlanes* planes,
+                  const YuvMatrix* ymat)
 {
     dim3 grid(n), block(64 * P.ndials);
     const size_t shmem = (size_t)P.ndials * DIAL_LDS_BYTES;
@@ -373,7 +375,7 @@ void launch_dials(const DialsSrc& src, int pix, int n, const melf_params& P, con
         default: MELF_NEEDLES_LAUNCH(BPP, 64); break;        \
     }
 #define MELF_YNEEDLE_LAUNCH(PL, NRV) \
-    hipLaunchKernelGGL((k_yneedle<PL, NRV>), grid, block, shmem, stream, src, *yuv, P, d_geom, d_rowmasks, d_partials, nparts, rw, d_results)
+    hipLaunchKernelGGL((k_yneedle<PL, NRV>), grid, block, shmem, stream, src, *yuv, *ymat, P, d_geom, d_rowmasks, d_partials, nparts, rw, d_results)
 #define MELF_YNEEDLE_NR(PL)                                  \
     switch (nr) {                                            \
         case 32: MELF_YNEEDLE_LAUNCH(PL, 32); break;         \
@@ -384,7 +386,7 @@ void launch_dials(const DialsSrc& src, int pix, int n, const melf_params& P, con
         default: MELF_YNEEDLE_LAUNCH(PL, 64); break;         \
     }
 #define MELF_P422_NEEDLE_LAUNCH(NRV) \
-    hipLaunchKernelGGL((k_p422_needle<NRV>), grid, block, shmem, stream, src, p422_sel(pix), P, d_geom, d_rowmasks, d_partials, nparts, rw, d_results)
+    hipLaunchKernelGGL((k_p422_needle<NRV>), grid, block, shmem, stream, src, p422_sel(pix), *ymat, P, d_geom, d_rowmasks, d_partials, nparts, rw, d_results)
 #define MELF_PLANAR_NEEDLE_LAUNCH(NRV) \
     hipLaunchKernelGGL((k_planar_needle<NRV>), grid, block, shmem, stream, src, *planes, P, d_geom, d_rowmasks, d_partials, nparts, rw, d_results)
     const int swap_rb = pix == MELF_PIX_RGB || pix == MELF_PIX_RGBA;

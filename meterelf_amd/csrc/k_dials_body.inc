@@ -9,7 +9,8 @@
 //             and the prefilter see what they see for a BGR frame: the records are those of the BGR frame made from the caller's;
 //   NR        window rows whose pixels a lane requests up front (the largest dial window of the context, rounded up to 8).
 // With MELF_YUV_BODY defined by the including kernel (k_yneedle): NV12 (PLANAR false) / I420 (PLANAR true) frames, src the Y plane,
-// `yuv` the chroma planes.  Every load fetches Y and the chroma under it and leaves as a B G R dword (melf_device.h: yuv_bgr), which
+// `yuv` the chroma planes.  Every load fetches Y and the chroma under it and leaves as a B G R dword (melf_device.h: yuv_bgr, under
+// the launch's matrix ymat), which
 // is what the rest of the body sees with PB = 4: the core pixel and the exact path's column pixel by byte loads, the window's four
 // pixels per lane as one Y dword and the (at most three) chroma pairs under it, at any parity of the window's origin.
 // With MELF_P422_BODY defined instead (k_p422_needle): packed YUV 4:2:2 frames (melf_process_yuv422*), two pixels per aligned
@@ -108,7 +109,7 @@
         const int fx = fx_m + X, fy = fy_m + Y;
         const size_t co = (size_t)(fy >> 1) * (size_t)cp_u + (size_t)(PLANAR ? fx >> 1 : fx & ~1);
         const int yv = frame[(size_t)fy * rstride + (size_t)fx];
-        return yuv_bgr(yv, yuv_chroma(uplane[co], vplane[co]));
+        return yuv_bgr(yv, yuv_chroma<false>(uplane[co], vplane[co], ymat), ymat);
     };
 #elif defined(MELF_P422_BODY)
     const int fx_m = src.x0 + mx, fy_m = src.y0 + my;   // the match position in the frame
@@ -116,7 +117,7 @@
     auto yuv_px = [&](int X, int Y) -> uint32_t {
         const int fx = fx_m + X, fy = fy_m + Y;
         const uint32_t c = __builtin_amdgcn_perm(0u, *(const uint32_t*)(frame + (size_t)fy * rstride + (size_t)(fx >> 1) * 4), psel);
-        return yuv_bgr((int)((fx & 1 ? c >> 16 : c) & 255u), yuv_chroma((int)((c >> 8) & 255u), (int)(c >> 24)));
+        return yuv_bgr((int)((fx & 1 ? c >> 16 : c) & 255u), yuv_chroma<false>((int)((c >> 8) & 255u), (int)(c >> 24), ymat), ymat);
     };
 #elif defined(MELF_PLANAR_BODY)
     const int fx_m = src.x0 + mx, fy_m = src.y0 + my;   // the match position in the frame
@@ -178,14 +179,14 @@
             const uint32_t lo = (uint32_t)c, hi = (uint32_t)(c >> 32);
             cu = __builtin_amdgcn_perm(hi, lo, 0x0c040200u); cv = __builtin_amdgcn_perm(hi, lo, 0x0c050301u);
         }
-        const YuvChroma c0 = yuv_chroma(cu & 255, cv & 255), c1 = yuv_chroma((cu >> 8) & 255, (cv >> 8) & 255),
-                        c2 = yuv_chroma((cu >> 16) & 255, (cv >> 16) & 255);
+        const YuvChroma c0 = yuv_chroma<false>(cu & 255, cv & 255, ymat), c1 = yuv_chroma<false>((cu >> 8) & 255, (cv >> 8) & 255, ymat),
+                        c2 = yuv_chroma<false>((cu >> 16) & 255, (cv >> 16) & 255, ymat);
         // pixel j sits on pair (j + fodd) >> 1
         u32x4v o;
-        o.x = yuv_bgr(r.x & 255, c0);
-        o.y = yuv_bgr((r.x >> 8) & 255, fodd ? c1 : c0);
-        o.z = yuv_bgr((r.x >> 16) & 255, c1);
-        o.w = yuv_bgr(r.x >> 24, fodd ? c2 : c1);
+        o.x = yuv_bgr(r.x & 255, c0, ymat);
+        o.y = yuv_bgr((r.x >> 8) & 255, fodd ? c1 : c0, ymat);
+        o.z = yuv_bgr((r.x >> 16) & 255, c1, ymat);
+        o.w = yuv_bgr(r.x >> 24, fodd ? c2 : c1, ymat);
         return o;
     };
 #elif defined(MELF_P422_BODY)
@@ -204,16 +205,16 @@
     auto yuv_quad = [&](const u32x4v r) -> u32x4v {
         const uint32_t ma = __builtin_amdgcn_perm(0u, mshifted ? r.y : r.x, psel), mb = __builtin_amdgcn_perm(0u, mshifted ? r.z : r.y, psel),
                        mc = __builtin_amdgcn_perm(0u, r.z, psel);   // Y0 U Y1 V each
-        const YuvChroma c0 = yuv_chroma((int)((ma >> 8) & 255u), (int)(ma >> 24)), c1 = yuv_chroma((int)((mb >> 8) & 255u), (int)(mb >> 24)),
-                        c2 = yuv_chroma((int)((mc >> 8) & 255u), (int)(mc >> 24));
+        const YuvChroma c0 = yuv_chroma<false>((int)((ma >> 8) & 255u), (int)(ma >> 24), ymat), c1 = yuv_chroma<false>((int)((mb >> 8) & 255u), (int)(mb >> 24), ymat),
+                        c2 = yuv_chroma<false>((int)((mc >> 8) & 255u), (int)(mc >> 24), ymat);
         const uint32_t y4 = __builtin_amdgcn_perm(mb, ma, 0x06040200u);                  // Y of the pixels of ma, mb
         const uint32_t yd = fodd ? __builtin_amdgcn_perm(mc, y4, 0x04030201u) : y4;      // Y of the lane's four
         // pixel j sits on macropixel (j + fodd) >> 1
         u32x4v o;
-        o.x = yuv_bgr((int)(yd & 255u), c0);
-        o.y = yuv_bgr((int)((yd >> 8) & 255u), fodd ? c1 : c0);
-        o.z = yuv_bgr((int)((yd >> 16) & 255u), c1);
-        o.w = yuv_bgr((int)(yd >> 24), fodd ? c2 : c1);
+        o.x = yuv_bgr((int)(yd & 255u), c0, ymat);
+        o.y = yuv_bgr((int)((yd >> 8) & 255u), fodd ? c1 : c0, ymat);
+        o.z = yuv_bgr((int)((yd >> 16) & 255u), c1, ymat);
+        o.w = yuv_bgr((int)(yd >> 24), fodd ? c2 : c1, ymat);
         return o;
     };
 #elif defined(MELF_PLANAR_BODY)

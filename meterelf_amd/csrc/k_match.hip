@@ -37,7 +37,8 @@ struct P422Sel { uint32_t sel; };
 template <int PX, class YUV = NoYuv>
 __device__ __forceinline__ void match_tile(MatchSrc src, MatchGeom g, const uint32_t* __restrict__ tplT,
                                            int rh, int rw, int nrb, float* __restrict__ result_map,
-                                           MatchPartial* __restrict__ partials, int nparts, YUV yuv = YUV{})
+                                           MatchPartial* __restrict__ partials, int nparts, YUV yuv = YUV{},
+                                           [[maybe_unused]] YuvMatrix mx = YuvMatrix{} /* PX 20 .. 22: the frames' colour conversion */)
 {
     constexpr int R = MATCH_R;
     extern __shared__ uint32_t lds[];
@@ -70,13 +71,13 @@ __device__ __forceinline__ void match_tile(MatchSrc src, MatchGeom g, const uint
                     if (x < src.cols) {
                         if constexpr (PX == 20 || PX == 21) {
                             const int cx = (src.x0 + x) >> 1, ci = PX == 20 ? 2 * cx : cx;
-                            const YuvChroma c = yuv_chroma(urow[ci], vrow[ci]);
-                            v = (uint32_t)yuv_lightness(prow[src.x0 + x], yuv_cmax(c), yuv_cmin(c));
+                            const YuvChroma c = yuv_chroma(urow[ci], vrow[ci], mx);
+                            v = (uint32_t)yuv_lightness(prow[src.x0 + x], yuv_cmax(c), yuv_cmin(c), mx);
                         } else if constexpr (PX == 22) {
                             const int fx = src.x0 + x;
                             const uint32_t m = __builtin_amdgcn_perm(0u, *(const uint32_t*)(prow + (size_t)(fx >> 1) * 4), yuv.sel);
-                            const YuvChroma c = yuv_chroma((int)((m >> 8) & 255u), (int)(m >> 24));
-                            v = (uint32_t)yuv_lightness((int)((fx & 1 ? m >> 16 : m) & 255u), yuv_cmax(c), yuv_cmin(c));
+                            const YuvChroma c = yuv_chroma((int)((m >> 8) & 255u), (int)(m >> 24), mx);
+                            v = (uint32_t)yuv_lightness((int)((fx & 1 ? m >> 16 : m) & 255u), yuv_cmax(c), yuv_cmin(c), mx);
                         } else if constexpr (PX == 23) {
                             const uint8_t* p = prow + (size_t)(src.x0 + x);
                             v = (uint32_t)hls_lightness(p[yuv.b_off], p[yuv.g_off], p[yuv.r_off]);
@@ -185,21 +186,21 @@ __global__ __launch_bounds__(256) void k_match_px4(MatchSrc src, MatchGeom g, co
     match_tile<4>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts);
 }
 
-// NV12 / I420 frames (melf_process_yuv*)
+// NV12 / I420 frames (melf_process_yuv*); mx: the frames' colour conversion (wave-uniform: SGPRs)
 template <bool PLANAR>
-__global__ __launch_bounds__(256) void k_match_yuv(MatchSrc src, YuvPlanes yuv, MatchGeom g, const uint32_t* __restrict__ tplT,
+__global__ __launch_bounds__(256) void k_match_yuv(MatchSrc src, YuvPlanes yuv, YuvMatrix mx, MatchGeom g, const uint32_t* __restrict__ tplT,
                                                    int rh, int rw, int nrb, float* __restrict__ result_map,
                                                    MatchPartial* __restrict__ partials, int nparts)
 {
-    match_tile<PLANAR ? 21 : 20, YuvPlanes>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts, yuv);
+    match_tile<PLANAR ? 21 : 20, YuvPlanes>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts, yuv, mx);
 }
 
 // packed YUV 4:2:2 frames (melf_process_yuv422*); psel: macropixel -> Y0 U Y1 V
-__global__ __launch_bounds__(256) void k_p422_match(MatchSrc src, uint32_t psel, MatchGeom g, const uint32_t* __restrict__ tplT,
+__global__ __launch_bounds__(256) void k_p422_match(MatchSrc src, uint32_t psel, YuvMatrix mx, MatchGeom g, const uint32_t* __restrict__ tplT,
                                                     int rh, int rw, int nrb, float* __restrict__ result_map,
                                                     MatchPartial* __restrict__ partials, int nparts)
 {
-    match_tile<22, P422Sel>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts, P422Sel{psel});
+    match_tile<22, P422Sel>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts, P422Sel{psel}, mx);
 }
 
 // planar frames (melf_process_planes*): the dot4 matcher with three byte loads per pixel, one from each plane
@@ -220,7 +221,7 @@ int match_parts(const MatchGeom& g, int rows, int cols)
 
 void launch_match(const MatchSrc& src, int pix, int n, const MatchGeom& g, const uint32_t* d_tplT,
                   float* d_result_map, MatchPartial* d_partials, int* nparts_out, hipStream_t stream, const YuvPlanes* yuv,
-                  const PlanarPlanes* planes)
+                  const PlanarPlanes* planes, const YuvMatrix* mx)
 {
     const int rh = src.rows - g.th + 1, rw = src.cols - g.tw + 1;
     const int nrb = (rh + MATCH_RBLK - 1) / MATCH_RBLK, ncb = (rw + MATCH_CBLK - 1) / MATCH_CBLK;
@@ -232,13 +233,13 @@ void launch_match(const MatchSrc& src, int pix, int n, const MatchGeom& g, const
         hipLaunchKernelGGL(k_planar_match, grid, block, shmem, stream, src, *planes, g, d_tplT, rh, rw, nrb, d_result_map,
                            d_partials, nparts);
     else if (pix_p422(pix))
-        hipLaunchKernelGGL(k_p422_match, grid, block, shmem, stream, src, p422_sel(pix), g, d_tplT, rh, rw, nrb, d_result_map,
+        hipLaunchKernelGGL(k_p422_match, grid, block, shmem, stream, src, p422_sel(pix), *mx, g, d_tplT, rh, rw, nrb, d_result_map,
                            d_partials, nparts);
     else if (pix == PIX_NV12)
-        hipLaunchKernelGGL(k_match_yuv<false>, grid, block, shmem, stream, src, *yuv, g, d_tplT, rh, rw, nrb, d_result_map,
+        hipLaunchKernelGGL(k_match_yuv<false>, grid, block, shmem, stream, src, *yuv, *mx, g, d_tplT, rh, rw, nrb, d_result_map,
                            d_partials, nparts);
     else if (pix == PIX_I420)
-        hipLaunchKernelGGL(k_match_yuv<true>, grid, block, shmem, stream, src, *yuv, g, d_tplT, rh, rw, nrb, d_result_map,
+        hipLaunchKernelGGL(k_match_yuv<true>, grid, block, shmem, stream, src, *yuv, *mx, g, d_tplT, rh, rw, nrb, d_result_map,
                            d_partials, nparts);
     else if (pix == PIX_PLANE)
         hipLaunchKernelGGL(k_match<false>, grid, block, shmem, stream, src, g, d_tplT, rh, rw, nrb, d_result_map,

@@ -84,9 +84,10 @@ __global__ __launch_bounds__(256) void k_lplane_px4(MatchSrc src, int nframes, i
 
 // NV12 / I420 frames (melf_process_yuv*): src is the Y plane, yuv the chroma planes; PLANAR: separate U and V planes (I420, YV12)
 // instead of interleaved U V pairs (NV12).  L comes straight from Y, U, V (melf_device.h: yuv_lightness); no BGR pixel is formed.
+// mx: the frames' colour conversion, the same for every lane (SGPRs): one instantiation serves every matrix.
 #define MELF_YUV_BODY
 template <bool PLANAR>
-__global__ __launch_bounds__(256) void k_lplane_yuv(MatchSrc src, YuvPlanes yuv, int nframes, int nkb, int rows_pad, int tw, int rwp, int pairs,
+__global__ __launch_bounds__(256) void k_lplane_yuv(MatchSrc src, YuvPlanes yuv, YuvMatrix mx, int nframes, int nkb, int rows_pad, int tw, int rwp, int pairs,
                                                     int8_t* __restrict__ Lg, uint16_t* __restrict__ R)
 {
     constexpr int PX = PLANAR ? 21 : 20;
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(256) void k_lplane_yuv(MatchSrc src, YuvPlanes yuv,
 // Packed YUV 4:2:2 frames (melf_process_yuv422*): two pixels per aligned macropixel dword; psel: the byte permute that brings the
 // frames' order (YUYV, UYVY, YVYU) to Y0 U Y1 V, a runtime value: one instantiation.  L straight from Y, U, V as above.
 #define MELF_P422_BODY
-__global__ __launch_bounds__(256) void k_p422_lplane(MatchSrc src, uint32_t psel, int nframes, int nkb, int rows_pad, int tw, int rwp, int pairs,
+__global__ __launch_bounds__(256) void k_p422_lplane(MatchSrc src, uint32_t psel, YuvMatrix mx, int nframes, int nkb, int rows_pad, int tw, int rwp, int pairs,
                                                      int8_t* __restrict__ Lg, uint16_t* __restrict__ R)
 {
     constexpr int PX = 22;
@@ -799,7 +800,8 @@ void mfma_build_atab(const uint8_t* templ, int th, int tw, int8_t* atab)
 }
 
 void launch_match_prep(const MatchSrc& src, int pix, int n, int groups, int rows_pad, int nkb, int rwp, int tw, int8_t* d_lg,
-                       uint16_t* d_r, hipStream_t stream, int pairs, const YuvPlanes* yuv, const PlanarPlanes* planes)
+                       uint16_t* d_r, hipStream_t stream, int pairs, const YuvPlanes* yuv, const PlanarPlanes* planes,
+                       const YuvMatrix* mx)
 {
     dim3 grid(rows_pad, groups), block(256);
     const size_t pre_bytes = (size_t)32 * (nkb * 32 + 8) * sizeof(int16_t);
@@ -817,19 +819,19 @@ void launch_match_prep(const MatchSrc& src, int pix, int n, int groups, int rows
         attr_set[dev] = true;
     }
     if (pix == PIX_PLANAR) hipLaunchKernelGGL(k_planar_lplane, grid, block, pre_bytes, stream, src, *planes, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
-    else if (pix_p422(pix)) hipLaunchKernelGGL(k_p422_lplane, grid, block, pre_bytes, stream, src, p422_sel(pix), n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
-    else if (pix == PIX_NV12) hipLaunchKernelGGL((k_lplane_yuv<false>), grid, block, pre_bytes, stream, src, *yuv, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
-    else if (pix == PIX_I420) hipLaunchKernelGGL((k_lplane_yuv<true>), grid, block, pre_bytes, stream, src, *yuv, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    else if (pix_p422(pix)) hipLaunchKernelGGL(k_p422_lplane, grid, block, pre_bytes, stream, src, p422_sel(pix), *mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    else if (pix == PIX_NV12) hipLaunchKernelGGL((k_lplane_yuv<false>), grid, block, pre_bytes, stream, src, *yuv, *mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    else if (pix == PIX_I420) hipLaunchKernelGGL((k_lplane_yuv<true>), grid, block, pre_bytes, stream, src, *yuv, *mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else if (pix == PIX_PLANE) hipLaunchKernelGGL((k_prep_lplane<false>), grid, block, pre_bytes, stream, src, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else if (pix_bytes(pix) == 4) hipLaunchKernelGGL(k_lplane_px4, grid, block, pre_bytes, stream, src, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else hipLaunchKernelGGL((k_prep_lplane<true>), grid, block, pre_bytes, stream, src, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
 }
 
 void launch_mfma_prep(const MatchSrc& src, int pix, int n, const MfmaPlan& p, int th, int tw, int8_t* d_lg,
-                      uint16_t* d_r, hipStream_t stream, const YuvPlanes* yuv, const PlanarPlanes* planes)
+                      uint16_t* d_r, hipStream_t stream, const YuvPlanes* yuv, const PlanarPlanes* planes, const YuvMatrix* mx)
 {
     (void)th;
-    launch_match_prep(src, pix, n, p.groups, p.rows_pad, p.nkb, 64, tw, d_lg, d_r, stream, p.nxb, yuv, planes);   // one paired operand per column block
+    launch_match_prep(src, pix, n, p.groups, p.rows_pad, p.nkb, 64, tw, d_lg, d_r, stream, p.nxb, yuv, planes, mx);   // one paired operand per column block
 }
 
 template <int NXB, int RB, int KS>

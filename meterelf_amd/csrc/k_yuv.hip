@@ -1,7 +1,7 @@
-// YUV 4:2:0 -> BGR alone: the stage kernel behind melf_yuv_to_bgr (include/meterelf_hip.h), what
-// cv2.cvtColor(COLOR_YUV2BGR_NV12 / _I420) makes of a decoder's frame before the reference's get_bgr_image hands it on
-// (meterelf/_image.py:46-51).  The arithmetic is melf_device.h's yuv_chroma / yuv_bgr, the functions the reading kernels
-// (k_lplane_yuv, k_match_yuv, k_yneedle) convert with in place: this kernel pins it for every (Y, U, V).
+// YUV 4:2:0 -> BGR alone: the stage kernel behind melf_yuv_to_bgr (include/meterelf_hip.h), under the descriptor's matrix (mx;
+// MELF_YUV_BT601_LIMITED: what cv2.cvtColor(COLOR_YUV2BGR_NV12 / _I420) makes of a decoder's frame) before the reference's
+// get_bgr_image hands it on (meterelf/_image.py:46-51).  The arithmetic is melf_device.h's yuv_chroma / yuv_bgr, the functions the
+// reading kernels (k_lplane_yuv, k_match_yuv, k_yneedle) convert with in place: this kernel pins it for every (Y, U, V).
 //
 // Mapping: one thread per 2 x 2 block of pixels, which shares one chroma pair: two byte loads of chroma, two 2-byte loads of
 // Y, two 6-byte rows of B G R out.  A parity and debugging aid, not a hot path: the hot path never forms the BGR frame.
@@ -12,18 +12,18 @@ namespace melf {
 
 template <bool PLANAR>
 __global__ __launch_bounds__(256) void k_yuv2bgr(const uint8_t* __restrict__ src, int H, int W, int y_pitch, size_t frame_stride,
-                                                 YuvPlanes yuv, uint8_t* __restrict__ dst)
+                                                 YuvPlanes yuv, YuvMatrix mx, uint8_t* __restrict__ dst)
 {
     const int bx = blockIdx.x * blockDim.x + threadIdx.x, by = blockIdx.y, f = blockIdx.z;
     if (bx >= (W >> 1) || by >= (H >> 1)) return;
     const uint8_t* frame = src + (size_t)f * frame_stride;
     const size_t co = (size_t)by * (size_t)yuv.c_pitch + (size_t)(PLANAR ? bx : 2 * bx);
-    const YuvChroma c = yuv_chroma(frame[(size_t)yuv.u_off + co], frame[(size_t)yuv.v_off + co]);
+    const YuvChroma c = yuv_chroma(frame[(size_t)yuv.u_off + co], frame[(size_t)yuv.v_off + co], mx);
     uint8_t* out = dst + ((size_t)f * H + 2 * by) * (size_t)W * 3 + (size_t)bx * 6;
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         const uint8_t* yrow = frame + (size_t)(2 * by + r) * (size_t)y_pitch + 2 * bx;
-        const uint32_t p0 = yuv_bgr(yrow[0], c), p1 = yuv_bgr(yrow[1], c);
+        const uint32_t p0 = yuv_bgr(yrow[0], c, mx), p1 = yuv_bgr(yrow[1], c, mx);
         uint8_t* o = out + (size_t)r * W * 3;
         o[0] = (uint8_t)p0; o[1] = (uint8_t)(p0 >> 8); o[2] = (uint8_t)(p0 >> 16);
         o[3] = (uint8_t)p1; o[4] = (uint8_t)(p1 >> 8); o[5] = (uint8_t)(p1 >> 16);
@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void k_yuv2bgr(const uint8_t* __restrict__ src
 }
 
 void launch_yuv2bgr(const uint8_t* d_src, int pix, int n, int H, int W, int y_pitch, size_t frame_stride, const YuvPlanes& yuv,
-                    uint8_t* d_dst, hipStream_t stream)
+                    const YuvMatrix& mx, uint8_t* d_dst, hipStream_t stream)
 {
     // at most 65 535 frames per launch (grid z)
     for (int f0 = 0; f0 < n; f0 += 65535) {
@@ -39,8 +39,8 @@ void launch_yuv2bgr(const uint8_t* d_src, int pix, int n, int H, int W, int y_pi
         dim3 grid(((W >> 1) + 255) / 256, H >> 1, m), block(256);
         const uint8_t* s = d_src + (size_t)f0 * frame_stride;
         uint8_t* d = d_dst + (size_t)f0 * H * W * 3;
-        if (pix == PIX_I420) hipLaunchKernelGGL(k_yuv2bgr<true>, grid, block, 0, stream, s, H, W, y_pitch, frame_stride, yuv, d);
-        else hipLaunchKernelGGL(k_yuv2bgr<false>, grid, block, 0, stream, s, H, W, y_pitch, frame_stride, yuv, d);
+        if (pix == PIX_I420) hipLaunchKernelGGL(k_yuv2bgr<true>, grid, block, 0, stream, s, H, W, y_pitch, frame_stride, yuv, mx, d);
+        else hipLaunchKernelGGL(k_yuv2bgr<false>, grid, block, 0, stream, s, H, W, y_pitch, frame_stride, yuv, mx, d);
     }
 }
 
@@ -49,29 +49,29 @@ void launch_yuv2bgr(const uint8_t* d_src, int pix, int n, int H, int W, int y_pi
 // reading kernels (k_p422_lplane, k_p422_match, k_p422_needle) use, two B G R pixels out.  This kernel pins the fetch and the
 // arithmetic for every (Y, U, V) at both pixels of a macropixel; like k_yuv2bgr it is no hot path.
 __global__ __launch_bounds__(256) void k_p422_to_bgr(const uint8_t* __restrict__ src, int H, int W, int row_pitch, size_t frame_stride,
-                                                     uint32_t psel, uint8_t* __restrict__ dst)
+                                                     uint32_t psel, YuvMatrix mx, uint8_t* __restrict__ dst)
 {
     const int bx = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.z;
     if (bx >= (W >> 1)) return;
     for (int y = blockIdx.y; y < H; y += gridDim.y) {
         const uint32_t m = __builtin_amdgcn_perm(0u, *(const uint32_t*)(src + (size_t)f * frame_stride + (size_t)y * (size_t)row_pitch + (size_t)bx * 4), psel);
-        const YuvChroma c = yuv_chroma((int)((m >> 8) & 255u), (int)(m >> 24));
-        const uint32_t p0 = yuv_bgr((int)(m & 255u), c), p1 = yuv_bgr((int)((m >> 16) & 255u), c);
+        const YuvChroma c = yuv_chroma((int)((m >> 8) & 255u), (int)(m >> 24), mx);
+        const uint32_t p0 = yuv_bgr((int)(m & 255u), c, mx), p1 = yuv_bgr((int)((m >> 16) & 255u), c, mx);
         uint8_t* o = dst + ((size_t)f * H + y) * (size_t)W * 3 + (size_t)bx * 6;
         o[0] = (uint8_t)p0; o[1] = (uint8_t)(p0 >> 8); o[2] = (uint8_t)(p0 >> 16);
         o[3] = (uint8_t)p1; o[4] = (uint8_t)(p1 >> 8); o[5] = (uint8_t)(p1 >> 16);
     }
 }
 
-void launch_p422_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int row_pitch, size_t frame_stride, uint8_t* d_dst,
-                        hipStream_t stream)
+void launch_p422_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int row_pitch, size_t frame_stride, const YuvMatrix& mx,
+                        uint8_t* d_dst, hipStream_t stream)
 {
     // at most 65 535 frames per launch (grid z); a workgroup row takes every 65 535th image row (grid y)
     for (int f0 = 0; f0 < n; f0 += 65535) {
         const int m = n - f0 < 65535 ? n - f0 : 65535;
         dim3 grid(((W >> 1) + 255) / 256, H < 65535 ? H : 65535, m), block(256);
         hipLaunchKernelGGL(k_p422_to_bgr, grid, block, 0, stream, d_src + (size_t)f0 * frame_stride, H, W, row_pitch, frame_stride,
-                           p422_sel(pix), d_dst + (size_t)f0 * H * W * 3);
+                           p422_sel(pix), mx, d_dst + (size_t)f0 * H * W * 3);
     }
 }
 

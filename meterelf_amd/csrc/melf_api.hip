@@ -1047,15 +1047,17 @@ static int gen_entry(melf_ctx* c, int rows, int cols, int n, melf_ctx::GenEntry*
 // prep + match of m images on stream ls with lane bl's work buffers; *parts / *nparts: per-frame (max, first arg-max)
 // partials for the consumer (k_dials or the host fold of melf_match_ccoeff)
 static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int bl, hipStream_t ls, float* d_map,
-                          MatchPartial** parts, int* nparts, TimedEvent& ev, const YuvPlanes* yuv, const PlanarPlanes* planes);
+                          MatchPartial** parts, int* nparts, TimedEvent& ev, const YuvPlanes* yuv, const PlanarPlanes* planes,
+                          const YuvMatrix* mx);
 static int run_match(melf_ctx* c, const MatchSrc& ms, int pix, int m, int bl, hipStream_t ls, float* d_map,
                      MatchPartial** parts, int* nparts, const YuvPlanes* yuv = nullptr /* pix_yuv(pix): the chroma planes */,
-                     const PlanarPlanes* planes = nullptr /* PIX_PLANAR: the three planes */)
+                     const PlanarPlanes* planes = nullptr /* PIX_PLANAR: the three planes */,
+                     const YuvMatrix* mx = nullptr /* pix_yuv(pix), pix_p422(pix): the frames' colour conversion */)
 {
     TimedEvent ev;
     ev.kernel = MELF_K_MATCH;
     ev.start = ev.stop = nullptr;
-    const int rc = run_match_impl(c, ms, pix, m, bl, ls, d_map, parts, nparts, ev, yuv, planes);
+    const int rc = run_match_impl(c, ms, pix, m, bl, ls, d_map, parts, nparts, ev, yuv, planes, mx);
     if (rc == MELF_SUCCESS && ev.start && ev.stop) {
         c->events.push_back(ev);
     } else {   // nothing was launched with them (an allocation failed on the way)
@@ -1065,7 +1067,8 @@ static int run_match(melf_ctx* c, const MatchSrc& ms, int pix, int m, int bl, hi
     return rc;
 }
 static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int bl, hipStream_t ls, float* d_map,
-                          MatchPartial** parts, int* nparts, TimedEvent& ev, const YuvPlanes* yuv, const PlanarPlanes* planes)
+                          MatchPartial** parts, int* nparts, TimedEvent& ev, const YuvPlanes* yuv, const PlanarPlanes* planes,
+                          const YuvMatrix* mx)
 {
     const melf_params& P = c->P;
     const int kind = pick_match_kind(c, ms.rows, ms.cols, m);
@@ -1089,7 +1092,7 @@ static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int b
         *parts = c->d_lpart[bl];
         {
             KernelTimer t(c, MELF_K_LPLANE, ls);
-            launch_mfma_prep(ms, pix, m, pl, P.th, P.tw, c->d_lg[bl], c->d_rsum[bl], ls, yuv, planes);
+            launch_mfma_prep(ms, pix, m, pl, P.th, P.tw, c->d_lg[bl], c->d_rsum[bl], ls, yuv, planes, mx);
         }
         info.rows_per_wave = pl.rb; info.full_waves = pl.na; info.pair_waves = 2 * pl.np;
         info.waves = pl.nparts * pl.groups; info.tiles = pl.ntiles;
@@ -1107,7 +1110,7 @@ static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int b
         *parts = c->d_lpart[bl];
         {
             KernelTimer t(c, MELF_K_LPLANE, ls);
-            launch_match_prep(ms, pix, m, pl.groups, pl.rows_pad, pl.nkb, pl.rwp, P.tw, c->d_lg[bl], c->d_rsum[bl], ls, 0, yuv, planes);
+            launch_match_prep(ms, pix, m, pl.groups, pl.rows_pad, pl.nkb, pl.rwp, P.tw, c->d_lg[bl], c->d_rsum[bl], ls, 0, yuv, planes, mx);
         }
         const GenDev& dev = ge->dev;
         fill_gen_info(&info, pl);
@@ -1117,7 +1120,7 @@ static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int b
         if (int rc = grow(&c->d_lpart[bl], &c->lpart_cap[bl], (size_t)m * *nparts)) return rc;
         *parts = c->d_lpart[bl];
         KernelTimer t(c, MELF_K_MATCH, ls);
-        launch_match(ms, pix, m, c->mg, c->d_tplT, d_map, *parts, nullptr, ls, yuv, planes);
+        launch_match(ms, pix, m, c->mg, c->d_tplT, d_map, *parts, nullptr, ls, yuv, planes, mx);
         info.tiles = *nparts;
     }
     if (trace)
@@ -1135,11 +1138,12 @@ static const int MAX_FRAMES_PER_LAUNCH = 32768;
 // (0 = packed); pix: the frames' pixel layout (MELF_PIX_*, or PIX_NV12 / PIX_I420: d_frames, frame_stride and row_stride then describe
 // the Y plane, yuv the chroma planes, yuv_extent = the bytes of a frame up to the last sample of its last plane; or PIX_YUYV /
 // PIX_UYVY / PIX_YVYU: packed 4:2:2 frames of 2 bytes per pixel, W even, everything 4-byte aligned; or PIX_PLANAR: d_frames,
-// frame_stride and row_stride describe a frame and the rows of its planes, planes where they start, yuv_extent as for YUV)
+// frame_stride and row_stride describe a frame and the rows of its planes, planes where they start, yuv_extent as for YUV);
+// mx: the colour conversion of YUV frames, 4:2:0 and 4:2:2 (the descriptor's matrix: yuv_matrix())
 static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
                             void* d_results, melf_result* out_host, hipStream_t st, const int* rect = nullptr, int row_stride = 0,
                             int pix = MELF_PIX_BGR, const YuvPlanes* yuv = nullptr, size_t yuv_extent = 0,
-                            const PlanarPlanes* planes = nullptr);
+                            const PlanarPlanes* planes = nullptr, const YuvMatrix* mx = nullptr);
 
 // The checks of a melf_frames descriptor (melf_process_frames*); n == 0 passes
 static int check_frames(const void* frames, const melf_frames* f)
@@ -1161,7 +1165,7 @@ static int check_frames(const void* frames, const melf_frames* f)
 
 static int batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride, int row_stride, int pix,
                      void* d_results, melf_result* out_host, void* stream_, const YuvPlanes* yuv = nullptr, size_t yuv_extent = 0,
-                     const PlanarPlanes* planes = nullptr);
+                     const PlanarPlanes* planes = nullptr, const YuvMatrix* mx = nullptr);
 
 extern "C" int melf_process_batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
                                       void* d_results, melf_result* out_host, void* stream_)
@@ -1185,12 +1189,14 @@ extern "C" int melf_process_frames_dev(melf_ctx* c, const void* d_frames, const 
 }
 
 // The checks of a melf_yuv_frames descriptor (melf_process_yuv*, melf_yuv_to_bgr); n == 0 passes.  *pix: PIX_NV12 / PIX_I420,
-// *yp: the chroma planes, *extent: the bytes of one frame up to the last sample of its last plane.
-static int check_yuv(const void* frames, const melf_yuv_frames* f, int* pix, YuvPlanes* yp, size_t* extent)
+// *yp: the chroma planes, *mx: the colour conversion of the descriptor's matrix code,
+// *extent: the bytes of one frame up to the last sample of its last plane.
+static int check_yuv(const void* frames, const melf_yuv_frames* f, int* pix, YuvPlanes* yp, const YuvMatrix** mx, size_t* extent)
 {
     if (!f) return fail(MELF_ERR_INVALID, "YUV frame descriptor is NULL");
     if (f->format != MELF_YUV_NV12 && f->format != MELF_YUV_I420) return fail(MELF_ERR_INVALID, "unknown YUV format");
-    if (f->matrix != MELF_YUV_BT601_LIMITED) return fail(MELF_ERR_INVALID, "unknown YUV matrix (BT.601 limited range only)");
+    if (!(*mx = yuv_matrix(f->matrix)))
+        return fail(MELF_ERR_INVALID, "unknown YUV matrix (accepted: 0 BT.601 limited, 2 BT.601 full, 3 BT.709 limited, 4 BT.709 full)");
     if (f->n < 0 || f->H <= 0 || f->W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
     if ((f->H | f->W) & 1) return fail(MELF_ERR_INVALID, "YUV 4:2:0 frames need an even height and width");
     if (f->H > 131070) return fail(MELF_ERR_INVALID, "frame too high");
@@ -1219,20 +1225,22 @@ extern "C" int melf_process_yuv_dev(melf_ctx* c, const void* d_frames, const mel
     if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
     int pix = 0;
     YuvPlanes yp;
+    const YuvMatrix* mx = nullptr;
     size_t extent = 0;
-    if (int rc = check_yuv(d_frames, f, &pix, &yp, &extent)) return rc;
+    if (int rc = check_yuv(d_frames, f, &pix, &yp, &mx, &extent)) return rc;
     if (f->n == 0) return MELF_SUCCESS;
-    return batch_dev(c, d_frames, f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->y_pitch, pix, d_results, out_host, stream_, &yp, extent);
+    return batch_dev(c, d_frames, f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->y_pitch, pix, d_results, out_host, stream_, &yp, extent, nullptr, mx);
 }
 
 // The checks of a melf_yuv422_frames descriptor (melf_process_yuv422*, melf_yuv422_to_bgr); n == 0 passes.  *pix: PIX_YUYV /
-// PIX_UYVY / PIX_YVYU.
-static int check_yuv422(const void* frames, const melf_yuv422_frames* f, int* pix)
+// PIX_UYVY / PIX_YVYU, *mx: the colour conversion of the descriptor's matrix code.
+static int check_yuv422(const void* frames, const melf_yuv422_frames* f, int* pix, const YuvMatrix** mx)
 {
     if (!f) return fail(MELF_ERR_INVALID, "YUV 4:2:2 frame descriptor is NULL");
     if (f->format != MELF_YUV422_YUYV && f->format != MELF_YUV422_UYVY && f->format != MELF_YUV422_YVYU)
         return fail(MELF_ERR_INVALID, "unknown YUV 4:2:2 format");
-    if (f->matrix != MELF_YUV_BT601_LIMITED) return fail(MELF_ERR_INVALID, "unknown YUV matrix (BT.601 limited range only)");
+    if (!(*mx = yuv_matrix(f->matrix)))
+        return fail(MELF_ERR_INVALID, "unknown YUV matrix (accepted: 0 BT.601 limited, 2 BT.601 full, 3 BT.709 limited, 4 BT.709 full)");
     if (f->n < 0 || f->H <= 0 || f->W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
     if (f->W & 1) return fail(MELF_ERR_INVALID, "YUV 4:2:2 frames need an even width");
     if (f->row_pitch < (int64_t)f->W * 2) return fail(MELF_ERR_INVALID, "row_pitch smaller than a row");
@@ -1253,9 +1261,11 @@ extern "C" int melf_process_yuv422_dev(melf_ctx* c, const void* d_frames, const 
 {
     if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
     int pix = 0;
-    if (int rc = check_yuv422(d_frames, f, &pix)) return rc;
+    const YuvMatrix* mx = nullptr;
+    if (int rc = check_yuv422(d_frames, f, &pix, &mx)) return rc;
     if (f->n == 0) return MELF_SUCCESS;
-    return batch_dev(c, d_frames, f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch, pix, d_results, out_host, stream_);
+    return batch_dev(c, d_frames, f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch, pix, d_results, out_host, stream_, nullptr, 0,
+                     nullptr, mx);
 }
 
 // The checks of a melf_planar_frames descriptor (melf_process_planes*); n == 0 passes.  *pl: the planes, *extent: the bytes of one
@@ -1303,7 +1313,7 @@ extern "C" int melf_process_planes_dev(melf_ctx* c, const void* d_frames, const 
 // their argument checks: the lane logic
 static int batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride, int row_stride, int pix,
                      void* d_results, melf_result* out_host, void* stream_, const YuvPlanes* yuv, size_t yuv_extent,
-                     const PlanarPlanes* planes)
+                     const PlanarPlanes* planes, const YuvMatrix* mx)
 {
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream_;  // NULL = the null (legacy default) stream, as everywhere in HIP
@@ -1317,7 +1327,7 @@ static int batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, siz
         c->active_lane = lane;
         c->order_stream = st;
         c->order_valid = true;
-        const int rc = process_batch_on(c, d_frames, n, H, W, frame_stride, d_results, nullptr, ls, nullptr, row_stride, pix, yuv, yuv_extent, planes);
+        const int rc = process_batch_on(c, d_frames, n, H, W, frame_stride, d_results, nullptr, ls, nullptr, row_stride, pix, yuv, yuv_extent, planes, mx);
         c->order_valid = false;
         if (rc) return rc;
         HIP_TRY(hipEventRecord(c->ev_join[lane], ls));
@@ -1330,12 +1340,12 @@ static int batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, siz
         return MELF_SUCCESS;
     }
     if (int rc = acquire_lane(c, st, &c->active_lane)) return rc;
-    return process_batch_on(c, d_frames, n, H, W, frame_stride, d_results, out_host, st, nullptr, row_stride, pix, yuv, yuv_extent, planes);
+    return process_batch_on(c, d_frames, n, H, W, frame_stride, d_results, out_host, st, nullptr, row_stride, pix, yuv, yuv_extent, planes, mx);
 }
 
 static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
                             void* d_results, melf_result* out_host, hipStream_t st, const int* rect, int row_stride, int pix,
-                            const YuvPlanes* yuv, size_t yuv_extent, const PlanarPlanes* planes)
+                            const YuvPlanes* yuv, size_t yuv_extent, const PlanarPlanes* planes, const YuvMatrix* mx)
 {
     const int bpp = yuv || planes ? 1 : (pix_p422(pix) ? 2 : pix_bytes(pix));
     if (row_stride <= 0) row_stride = W * bpp;  // packed rows unless the caller's rows are padded (host-fed crops, pitched frames)
@@ -1368,7 +1378,7 @@ static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int
         ms.readable = (size_t)(m - 1) * frame_stride + last_frame;
         int nparts = 0;
         MatchPartial* parts = nullptr;
-        if (int rc = run_match(c, ms, pix, m, bl, st, nullptr, &parts, &nparts, yuv, planes)) return rc;
+        if (int rc = run_match(c, ms, pix, m, bl, st, nullptr, &parts, &nparts, yuv, planes, mx)) return rc;
         DialsSrc ds;
         ds.base = base; ds.frame_stride = frame_stride; ds.row_stride = row_stride;
         ds.x0 = x0; ds.y0 = y0; ds.crop_rows = crows; ds.crop_cols = ccols;
@@ -1383,7 +1393,7 @@ static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int
         }
         {
             KernelTimer t(c, MELF_K_DIALS, st);
-            launch_dials(ds, pix, m, P, c->d_geom, c->d_rowmasks, parts, nparts, rw, res_dev + f0, st, c->ws_max, yuv, planes);
+            launch_dials(ds, pix, m, P, c->d_geom, c->d_rowmasks, parts, nparts, rw, res_dev + f0, st, c->ws_max, yuv, planes, mx);
         }
         HIP_TRY(hipGetLastError());
     }
@@ -1546,8 +1556,9 @@ static int batch_host(melf_ctx* c, const uint8_t* frames_host, int n, int H, int
 // YUV 4:2:0 host frames: the same pipeline.  What crosses PCIe per frame is a small frame of the same format: the Y rows of the
 // crop with its origin rounded down (and its far corner up) to even, and the chroma rows under them, each plane at a 64-byte
 // pitch in the staging buffer; the kernels read it with the rectangle shifted by the rounding (0 or 1 pixel each way).  Rows are
-// copied as they are: no byte is converted on the CPU.
-static int batch_host_yuv(melf_ctx* c, const uint8_t* frames_host, const melf_yuv_frames* f, int pix, const YuvPlanes& yp, melf_result* out_host)
+// copied as they are: no byte is converted on the CPU, and the small frames keep the caller's matrix (mx).
+static int batch_host_yuv(melf_ctx* c, const uint8_t* frames_host, const melf_yuv_frames* f, int pix, const YuvPlanes& yp,
+                          const YuvMatrix* mx, melf_result* out_host)
 {
     const int n = f->n, H = f->H, W = f->W;
     const bool nv12 = pix == PIX_NV12;
@@ -1618,7 +1629,7 @@ static int batch_host_yuv(melf_ctx* c, const uint8_t* frames_host, const melf_yu
         HIP_TRY(hipEventRecord(c->ev_h2d[b], c->copy_stream));
         HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_h2d[b], 0));
         if (int rc = process_batch_on(c, d_chunk, m, sh, sw, crop_stride, c->d_results + f0, nullptr, c->stream, rect, (int)ypitch, pix, &sp,
-                                      crop_stride))
+                                      crop_stride, nullptr, mx))
             return rc;
     }
     HIP_TRY(hipMemcpyAsync(out_host, c->d_results, (size_t)n * sizeof(melf_result), hipMemcpyDeviceToHost, c->stream));
@@ -1632,18 +1643,21 @@ extern "C" int melf_process_yuv(melf_ctx* c, const void* frames_host, const melf
     if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
     int pix = 0;
     YuvPlanes yp;
+    const YuvMatrix* mx = nullptr;
     size_t extent = 0;
-    if (int rc = check_yuv(frames_host, f, &pix, &yp, &extent)) return rc;
+    if (int rc = check_yuv(frames_host, f, &pix, &yp, &mx, &extent)) return rc;
     if (f->n == 0) return MELF_SUCCESS;
     if (!out_host) return fail(MELF_ERR_INVALID, "out_host is NULL");
-    return batch_host_yuv(c, (const uint8_t*)frames_host, f, pix, yp, out_host);
+    return batch_host_yuv(c, (const uint8_t*)frames_host, f, pix, yp, mx, out_host);
 }
 
 // Packed YUV 4:2:2 host frames: the same pipeline.  What crosses PCIe per frame is a small frame of the same format: the rows of
 // the crop (no vertical rounding: every row has its own chroma), its x origin rounded down and its far corner up to even, i.e.
 // to whole macropixels, at a 64-byte pitch in the staging buffer; the kernels read it with the rectangle shifted by the rounding
-// (0 or 1 pixel).  Rows are copied as they are: no byte is converted or reordered on the CPU.
-static int batch_host_p422(melf_ctx* c, const uint8_t* frames_host, const melf_yuv422_frames* f, int pix, melf_result* out_host)
+// (0 or 1 pixel).  Rows are copied as they are: no byte is converted or reordered on the CPU, and the small frames keep the
+// caller's matrix (mx).
+static int batch_host_p422(melf_ctx* c, const uint8_t* frames_host, const melf_yuv422_frames* f, int pix, const YuvMatrix* mx,
+                           melf_result* out_host)
 {
     const int n = f->n, H = f->H, W = f->W;
     HIP_TRY(hipSetDevice(c->device));
@@ -1698,7 +1712,8 @@ static int batch_host_p422(melf_ctx* c, const uint8_t* frames_host, const melf_y
         HIP_TRY(hipMemcpyAsync(d_chunk, pin, (size_t)m * crop_stride, hipMemcpyHostToDevice, c->copy_stream));
         HIP_TRY(hipEventRecord(c->ev_h2d[b], c->copy_stream));
         HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_h2d[b], 0));
-        if (int rc = process_batch_on(c, d_chunk, m, crows, sw, crop_stride, c->d_results + f0, nullptr, c->stream, rect, (int)pitch, pix))
+        if (int rc = process_batch_on(c, d_chunk, m, crows, sw, crop_stride, c->d_results + f0, nullptr, c->stream, rect, (int)pitch, pix, nullptr, 0,
+                                      nullptr, mx))
             return rc;
     }
     HIP_TRY(hipMemcpyAsync(out_host, c->d_results, (size_t)n * sizeof(melf_result), hipMemcpyDeviceToHost, c->stream));
@@ -1710,10 +1725,11 @@ extern "C" int melf_process_yuv422(melf_ctx* c, const void* frames_host, const m
 {
     if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
     int pix = 0;
-    if (int rc = check_yuv422(frames_host, f, &pix)) return rc;
+    const YuvMatrix* mx = nullptr;
+    if (int rc = check_yuv422(frames_host, f, &pix, &mx)) return rc;
     if (f->n == 0) return MELF_SUCCESS;
     if (!out_host) return fail(MELF_ERR_INVALID, "out_host is NULL");
-    return batch_host_p422(c, (const uint8_t*)frames_host, f, pix, out_host);
+    return batch_host_p422(c, (const uint8_t*)frames_host, f, pix, mx, out_host);
 }
 
 // Planar host frames: the same pipeline.  What crosses PCIe per frame is a small planar frame: the crop's rows of the B, the G and
@@ -1799,7 +1815,8 @@ extern "C" int melf_yuv422_to_bgr(melf_ctx* c, const void* frames_host, const me
 {
     if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
     int pix = 0;
-    if (int rc = check_yuv422(frames_host, f, &pix)) return rc;
+    const YuvMatrix* mx = nullptr;
+    if (int rc = check_yuv422(frames_host, f, &pix, &mx)) return rc;
     if (f->n == 0) return MELF_SUCCESS;
     if (!bgr_out_host) return fail(MELF_ERR_INVALID, "bgr_out_host is NULL");
     HIP_TRY(hipSetDevice(c->device));
@@ -1808,7 +1825,7 @@ extern "C" int melf_yuv422_to_bgr(melf_ctx* c, const void* frames_host, const me
     if (int rc = grow(&c->d_stage_in, &c->stage_in_cap, in_bytes)) return rc;
     if (int rc = grow(&c->d_stage_out, &c->stage_out_cap, out_bytes)) return rc;
     HIP_TRY(hipMemcpyAsync(c->d_stage_in, frames_host, in_bytes, hipMemcpyHostToDevice, c->stream));
-    launch_p422_to_bgr(c->d_stage_in, pix, f->n, f->H, f->W, (int)f->row_pitch, (size_t)f->frame_stride, c->d_stage_out, c->stream);
+    launch_p422_to_bgr(c->d_stage_in, pix, f->n, f->H, f->W, (int)f->row_pitch, (size_t)f->frame_stride, *mx, c->d_stage_out, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(bgr_out_host, c->d_stage_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1820,8 +1837,9 @@ extern "C" int melf_yuv_to_bgr(melf_ctx* c, const void* frames_host, const melf_
     if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
     int pix = 0;
     YuvPlanes yp;
+    const YuvMatrix* mx = nullptr;
     size_t extent = 0;
-    if (int rc = check_yuv(frames_host, f, &pix, &yp, &extent)) return rc;
+    if (int rc = check_yuv(frames_host, f, &pix, &yp, &mx, &extent)) return rc;
     if (f->n == 0) return MELF_SUCCESS;
     if (!bgr_out_host) return fail(MELF_ERR_INVALID, "bgr_out_host is NULL");
     HIP_TRY(hipSetDevice(c->device));
@@ -1829,7 +1847,7 @@ extern "C" int melf_yuv_to_bgr(melf_ctx* c, const void* frames_host, const melf_
     if (int rc = grow(&c->d_stage_in, &c->stage_in_cap, in_bytes)) return rc;
     if (int rc = grow(&c->d_stage_out, &c->stage_out_cap, out_bytes)) return rc;
     HIP_TRY(hipMemcpyAsync(c->d_stage_in, frames_host, in_bytes, hipMemcpyHostToDevice, c->stream));
-    launch_yuv2bgr(c->d_stage_in, pix, f->n, f->H, f->W, (int)f->y_pitch, (size_t)f->frame_stride, yp, c->d_stage_out, c->stream);
+    launch_yuv2bgr(c->d_stage_in, pix, f->n, f->H, f->W, (int)f->y_pitch, (size_t)f->frame_stride, yp, *mx, c->d_stage_out, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(bgr_out_host, c->d_stage_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2166,7 +2184,7 @@ static thread_local std::function<void()>* tl_jpeg_enqueued = nullptr;
 // here waits for the context's stream; what protects a ring slot is its own pair of events, across calls as within one.
 static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
                             void* d_results, melf_result* out_host, hipStream_t st, const int* rect, int row_stride, int pix,
-                            const YuvPlanes* yuv, size_t yuv_extent, const PlanarPlanes* planes);
+                            const YuvPlanes* yuv, size_t yuv_extent, const PlanarPlanes* planes, const YuvMatrix* mx);
 // What a caller inside the library may already have of the files it hands to the decode path (the file-name entry points
 // do): the parsed headers + Huffman decode data (of file index[k] of that parse for the call's file k), and the pinned buffer
 // the files' bytes lie in.

@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "melf_internal.h"   // YuvMatrix
+
 namespace melf {
 
 // OpenCV converts each row in blocks of 256 px; inside a block the first
@@ -86,49 +88,66 @@ __host__ __device__ inline void hls_pixel(int b8, int g8, int r8, bool scalar_ta
     S = sat_u8_rne(s * 255.f);
 }
 
-// ---- YUV 4:2:0 -> BGR (melf_process_yuv*, include/meterelf_hip.h: BT.601 limited range, the integer constants of
-// cv2.cvtColor(COLOR_YUV2BGR_NV12 / _I420), nearest chroma sample).  The one statement of the arithmetic: every kernel that
-// reads YUV frames goes through these.  All products fit 24-bit multiplies (|u|, |v| <= 128, Y - 16 <= 239, constants < 2^22)
-// and every sum 32 bits (|sum| < 2^30).
-__host__ __device__ inline int yuv_mul24(int a, int b)
-{
-#ifdef __HIP_DEVICE_COMPILE__
-    return __mul24(a, b);
-#else
-    return a * b;
-#endif
-}
+// ---- YUV -> BGR (melf_process_yuv*, melf_process_yuv422*, include/meterelf_hip.h: the integer conversion, nearest chroma
+// sample).  The one statement of the arithmetic: every kernel that reads YUV frames goes through these, the host too.  The offset
+// and the five coefficients of the frames' matrix (MELF_YUV_BT601_LIMITED: the constants of cv2.cvtColor(COLOR_YUV2BGR_NV12 /
+// _I420 / _YUY2 ..)) are a launch's YuvMatrix: a by-value kernel argument, the same for every lane, so each coefficient is the
+// one scalar operand a v_mul_i32_i24 takes, where a compiled-in constant was its one literal.  No branch on the matrix or on the
+// range: full range is max(Y - 0, 0).  For every matrix of melf_internal.h's yuv_matrix() all products fit 24-bit multiplies
+// (|u|, |v| <= 128, Y - yoff <= 255, coefficients < 2^22 + 2^18 in magnitude) and every sum 32 bits (|sum| < 2^30).
+//
+// yuv_mul24: sample x coefficient.  The sample's range is known where it is made (a byte, minus 128 or the offset); the coefficient
+// is sign-extended from 24 bits, once per wave on the scalar unit, which tells the compiler that the product is one v_mul_i32_i24 /
+// v_mad_i32_i24 with the coefficient as its scalar operand (and changes no value: the coefficients fit 24 bits).
+__host__ __device__ inline int yuv_mul24(int a, int coef) { return a * ((int)((uint32_t)coef << 8) >> 8); }
 // The chroma terms of a sample pair, rounding constant included: what is added to the luma term per channel.
 struct YuvChroma {
     int r, g, b;
 };
-__host__ __device__ inline YuvChroma yuv_chroma(int U, int V)
+// TWO_MADS (device): G as two dependent v_mad_i32_i24, what the compiler made of compiled-in coefficients; left to itself with
+// runtime coefficients it adds the two products and the constant with a third instruction.  The dial readers pass false: there
+// the opaque instruction cost them registers (101 -> 113 VGPRs, past k_dials' count) for 0.3 % of their instructions.
+// The two forms give the same value only while the coefficient fits a signed 24-bit operand: the instruction reads the low 24
+// bits of mx.cgu as they are, without the sign extension yuv_mul24 applies first (|coef| < 2^23: melf_internal.h asserts it for
+// every matrix of the table).  The stage kernels pin the instruction form for all 2^24 (Y, U, V), the whole-path tests the other.
+template <bool TWO_MADS = true>
+__host__ __device__ inline YuvChroma yuv_chroma(int U, int V, const YuvMatrix& mx)
 {
     const int u = U - 128, v = V - 128;
     YuvChroma c;
-    c.r = yuv_mul24(v, 1673527) + (1 << 19);
-    c.g = yuv_mul24(v, -852492) + yuv_mul24(u, -409993) + (1 << 19);
-    c.b = yuv_mul24(u, 2116026) + (1 << 19);
+    c.r = yuv_mul24(v, mx.crv) + (1 << 19);
+#ifdef __HIP_DEVICE_COMPILE__
+    if constexpr (TWO_MADS) {
+        asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(c.g) : "v"(u), "s"(mx.cgu), "v"(yuv_mul24(v, mx.cgv) + (1 << 19)));
+    } else
+#endif
+        c.g = yuv_mul24(v, mx.cgv) + yuv_mul24(u, mx.cgu) + (1 << 19);
+    c.b = yuv_mul24(u, mx.cbu) + (1 << 19);
     return c;
 }
-__host__ __device__ inline int yuv_luma(int Y) { return yuv_mul24(Y > 16 ? Y - 16 : 0, 1220542); }
+// max(Y - yoff, 0) as an unsigned saturating subtraction: one v_sub_u32 with clamp, which also picks Y's byte out of its dword
+__host__ __device__ inline int yuv_luma(int Y, const YuvMatrix& mx)
+{
+    const uint32_t y = (uint32_t)Y, o = (uint32_t)mx.yoff;
+    return yuv_mul24((int)(y > o ? y - o : 0u), mx.cy);
+}
 __host__ __device__ inline int yuv_clamp8(int s)
 {
     const int v = s >> 20;
     return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 // the pixel as B | G << 8 | R << 16: what a load of a BGR frame's pixel gives
-__host__ __device__ inline uint32_t yuv_bgr(int Y, const YuvChroma& c)
+__host__ __device__ inline uint32_t yuv_bgr(int Y, const YuvChroma& c, const YuvMatrix& mx)
 {
-    const int yy = yuv_luma(Y);
+    const int yy = yuv_luma(Y, mx);
     return (uint32_t)yuv_clamp8(yy + c.b) | (uint32_t)yuv_clamp8(yy + c.g) << 8 | (uint32_t)yuv_clamp8(yy + c.r) << 16;
 }
 // L = (max + min) / 2 needs the largest and the smallest channel only, and shift and clamp are monotone: they are those of the
-// largest and the smallest sum.  cmax / cmin: the largest / smallest chroma term of the pair (yuv_chroma).  The value of
-// hls_lightness_fast(B, G, R).
-__host__ __device__ inline int yuv_lightness(int Y, int cmax, int cmin)
+// largest and the smallest sum, whatever the coefficients: the luma term is common to the three channels.  cmax / cmin: the
+// largest / smallest chroma term of the pair (yuv_chroma).  The value of hls_lightness_fast(B, G, R).
+__host__ __device__ inline int yuv_lightness(int Y, int cmax, int cmin, const YuvMatrix& mx)
 {
-    const int yy = yuv_luma(Y);
+    const int yy = yuv_luma(Y, mx);
     const float inv255 = 1.f / 255.f;
     const float vmax = (float)yuv_clamp8(yy + cmax) * inv255, vmin = (float)yuv_clamp8(yy + cmin) * inv255;
     return (int)rintf((vmax + vmin) * 127.5f);

@@ -33,6 +33,43 @@ struct YuvPlanes {
     int c_pitch;           // bytes between chroma rows
     int pad;
 };
+// The colour conversion of YUV frames, 4:2:0 and 4:2:2 alike: the offset and the five coefficients of melf_device.h's yuv_chroma /
+// yuv_luma (include/meterelf_hip.h states the formula).  A by-value kernel argument of every kernel that converts, the same for
+// every lane: the compiler keeps it in SGPRs.  The four constants below are the single statement of the numbers: row 0 the
+// three-decimal constants of cv2, the others round(2^20 c) of the standards' exact coefficients (derivation: include/meterelf_hip.h).
+struct YuvMatrix {
+    int yoff;                 // 16 (limited range) or 0 (full range)
+    int cy;                   // luma gain
+    int crv, cgv, cgu, cbu;   // R from v; G from v and from u; B from u
+};
+// Every coefficient fits a signed 24-bit operand (|c| < 2^23): the kernels multiply with v_mul_i32_i24 / v_mad_i32_i24, which read
+// the low 24 bits of an operand as a signed number, and yuv_chroma's two forms of the G term (melf_device.h) stay equal only then.
+constexpr bool yuv_matrix_fits24(const YuvMatrix& m)
+{
+    constexpr int lim = 1 << 23;
+    return (m.yoff == 0 || m.yoff == 16) && m.cy > -lim && m.cy < lim && m.crv > -lim && m.crv < lim && m.cgv > -lim && m.cgv < lim &&
+           m.cgu > -lim && m.cgu < lim && m.cbu > -lim && m.cbu < lim;
+}
+constexpr YuvMatrix YUV_BT601_LIMITED_MATRIX = {16, 1220542, 1673527, -852492, -409993, 2116026};
+constexpr YuvMatrix YUV_BT601_FULL_MATRIX = {0, 1048576, 1470104, -748826, -360853, 1858077};
+constexpr YuvMatrix YUV_BT709_LIMITED_MATRIX = {16, 1220945, 1879825, -558796, -223607, 2215014};
+constexpr YuvMatrix YUV_BT709_FULL_MATRIX = {0, 1048576, 1651297, -490864, -196424, 1945738};
+static_assert(yuv_matrix_fits24(YUV_BT601_LIMITED_MATRIX) && yuv_matrix_fits24(YUV_BT601_FULL_MATRIX) &&
+                  yuv_matrix_fits24(YUV_BT709_LIMITED_MATRIX) && yuv_matrix_fits24(YUV_BT709_FULL_MATRIX),
+              "a YUV coefficient does not fit the 24-bit multiply");
+// the matrix of a descriptor's code (MELF_YUV_BT*); NULL: not a code (1 is never assigned)
+inline const YuvMatrix* yuv_matrix(int code)
+{
+    static const YuvMatrix table[4] = {YUV_BT601_LIMITED_MATRIX, YUV_BT601_FULL_MATRIX, YUV_BT709_LIMITED_MATRIX,
+                                       YUV_BT709_FULL_MATRIX};
+    switch (code) {
+    case MELF_YUV_BT601_LIMITED: return &table[0];
+    case MELF_YUV_BT601_FULL: return &table[1];
+    case MELF_YUV_BT709_LIMITED: return &table[2];
+    case MELF_YUV_BT709_FULL: return &table[3];
+    default: return nullptr;
+    }
+}
 // Packed YUV 4:2:2 frames (melf_process_yuv422*): the launch's pix.  Two pixels per 4-byte macropixel; base, frame_stride and
 // row_stride (bytes, all 4-byte aligned) describe the frames as for any packed layout, x0 and cols count pixels.  The formats
 // differ in a byte permute only, which the kernels take as a runtime value (v_perm_b32 selector): macropixel -> Y0 U Y1 V.
@@ -82,7 +119,8 @@ struct MatchSrc {
 
 void launch_match(const MatchSrc& src, int pix, int n, const MatchGeom& g, const uint32_t* d_tplT,
                   float* d_result_map, MatchPartial* d_partials, int* nparts_out, hipStream_t stream,
-                  const YuvPlanes* yuv = nullptr /* pix_yuv(pix) */, const PlanarPlanes* planes = nullptr /* PIX_PLANAR */);
+                  const YuvPlanes* yuv = nullptr /* pix_yuv(pix) */, const PlanarPlanes* planes = nullptr /* PIX_PLANAR */,
+                  const YuvMatrix* mx = nullptr /* pix_yuv(pix) or pix_p422(pix): required */);
 int match_parts(const MatchGeom& g, int rows, int cols);
 
 // ---- K2 on the matrix cores (k_match_mfma.hip) --------------------------------
@@ -97,7 +135,8 @@ MfmaPlan mfma_plan(int th, int tw, int rows, int cols, int nframes);
 size_t mfma_atab_bytes(int th);
 void mfma_build_atab(const uint8_t* templ, int th, int tw, int8_t* atab);
 void launch_mfma_prep(const MatchSrc& src, int pix, int n, const MfmaPlan& p, int th, int tw, int8_t* d_lg,
-                      uint16_t* d_r, hipStream_t stream, const YuvPlanes* yuv = nullptr, const PlanarPlanes* planes = nullptr);
+                      uint16_t* d_r, hipStream_t stream, const YuvPlanes* yuv = nullptr, const PlanarPlanes* planes = nullptr,
+                      const YuvMatrix* mx = nullptr);
 // launch_mfma_match: d_ws = the row-window sums R in epilogue order (k_prep_lplane); the waves add them up
 void launch_mfma_match(int n, const MfmaPlan& p, int th, int tw, long tsum, double tmean, const int8_t* d_atab,
                        const int8_t* d_lg, const uint32_t* d_ws, float* d_result_map, MatchPartial* d_partials,
@@ -136,7 +175,7 @@ void launch_gen_match(int n, const GenPlan& p, int rows, int th, int tw, long ts
 // (pairs > 0: the tuned kernel's paired-operand row layout, see k_prep_lplane)
 void launch_match_prep(const MatchSrc& src, int pix, int n, int groups, int rows_pad, int nkb, int rwp, int tw, int8_t* d_lg,
                        uint16_t* d_r, hipStream_t stream, int pairs = 0, const YuvPlanes* yuv = nullptr,
-                       const PlanarPlanes* planes = nullptr);
+                       const PlanarPlanes* planes = nullptr, const YuvMatrix* mx = nullptr);
 
 // ---- K3: per-dial reading ---------------------------------------------------
 struct DialGeom {
@@ -157,7 +196,8 @@ struct DialsSrc {
 void launch_dials(const DialsSrc& src, int pix, int n, const melf_params& P, const DialGeom* d_geom,
                   const uint64_t* d_rowmasks /* [ndials][3][64] */, const MatchPartial* d_partials,
                   int nparts, int rw, melf_result* d_results, hipStream_t stream, int ws_max /* largest DialGeom::ws */,
-                  const YuvPlanes* yuv = nullptr /* pix_yuv(pix) */, const PlanarPlanes* planes = nullptr /* PIX_PLANAR */);
+                  const YuvPlanes* yuv = nullptr /* pix_yuv(pix) */, const PlanarPlanes* planes = nullptr /* PIX_PLANAR */,
+                  const YuvMatrix* mx = nullptr /* pix_yuv(pix) or pix_p422(pix): required */);
 
 // ---- K1b / HLS --------------------------------------------------------------
 void launch_bgr2hls(const uint8_t* d_src, int rows, int cols, size_t row_stride, int hue_shift,
@@ -188,13 +228,14 @@ size_t launch_stream_probe(const void* d_in, size_t in_bytes, void* d_out, int c
                            hipEvent_t ev_start, hipEvent_t ev_stop);
 
 // ---- k_yuv.hip: the YUV 4:2:0 -> BGR conversion alone (melf_yuv_to_bgr) ----
-// n frames: Y plane at d_src (y_pitch, frame_stride), chroma planes per YuvPlanes; d_dst: n packed H x W x 3 BGR frames
+// n frames: Y plane at d_src (y_pitch, frame_stride), chroma planes per YuvPlanes, converted under mx; d_dst: n packed H x W x 3
+// BGR frames
 void launch_yuv2bgr(const uint8_t* d_src, int pix, int n, int H, int W, int y_pitch, size_t frame_stride, const YuvPlanes& yuv,
-                    uint8_t* d_dst, hipStream_t stream);
+                    const YuvMatrix& mx, uint8_t* d_dst, hipStream_t stream);
 
 // the same for packed YUV 4:2:2 (melf_yuv422_to_bgr): n frames at d_src (row_pitch, frame_stride), pix PIX_YUYV / _UYVY / _YVYU
-void launch_p422_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int row_pitch, size_t frame_stride, uint8_t* d_dst,
-                        hipStream_t stream);
+void launch_p422_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int row_pitch, size_t frame_stride, const YuvMatrix& mx,
+                        uint8_t* d_dst, hipStream_t stream);
 
 // ---- calibration stage kernels ------------------------------------------------
 void launch_aligned_average(const uint8_t* d_frames, int n, size_t frame_stride, int row_stride, int x0, int y0, int rows,

@@ -122,12 +122,12 @@
                             U = (int)((ua[j >> 2] >> ((j & 3) * 8)) & 255u);
                             V = (int)((va[j >> 2] >> ((j & 3) * 8)) & 255u);
                         }
-                        const YuvChroma c = yuv_chroma(U, V);
+                        const YuvChroma c = yuv_chroma(U, V, mx);
                         const int cmax = yuv_cmax(c), cmin = yuv_cmin(c);
 #pragma unroll
                         for (int q2 = 0; q2 < 2; ++q2) {
                             const int k = 2 * j + q2;
-                            const int L = yuv_lightness((int)((ya[k >> 2] >> ((k & 3) * 8)) & 255u), cmax, cmin);
+                            const int L = yuv_lightness((int)((ya[k >> 2] >> ((k & 3) * 8)) & 255u), cmax, cmin, mx);
                             wl[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
                         }
                     }
@@ -140,8 +140,8 @@
                     const uint8_t* pv = src.base + fo + (size_t)yuv.v_off + yuv_crow;
                     for (int k = 0; k < npx; ++k) {
                         const int cx = (src.x0 + xbeg + k) >> 1;
-                        const YuvChroma c = yuv_chroma(pu[NV12 ? 2 * cx : cx], pv[NV12 ? 2 * cx : cx]);
-                        const int L = yuv_lightness(py[k], yuv_cmax(c), yuv_cmin(c));
+                        const YuvChroma c = yuv_chroma(pu[NV12 ? 2 * cx : cx], pv[NV12 ? 2 * cx : cx], mx);
+                        const int L = yuv_lightness(py[k], yuv_cmax(c), yuv_cmin(c), mx);
                         w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
                     }
                 }
@@ -161,9 +161,9 @@
 #pragma unroll
                     for (int j = 0; j < 17; ++j) {
                         const uint32_t m = __builtin_amdgcn_perm(0u, j < 16 ? d[j >> 2][j & 3] : d16, psel);   // Y0 U Y1 V
-                        const YuvChroma c = yuv_chroma((int)((m >> 8) & 255u), (int)(m >> 24));
+                        const YuvChroma c = yuv_chroma((int)((m >> 8) & 255u), (int)(m >> 24), mx);
                         const int cmax = yuv_cmax(c), cmin = yuv_cmin(c);
-                        const int L0 = yuv_lightness((int)(m & 255u), cmax, cmin), L1 = yuv_lightness((int)((m >> 16) & 255u), cmax, cmin);
+                        const int L0 = yuv_lightness((int)(m & 255u), cmax, cmin, mx), L1 = yuv_lightness((int)((m >> 16) & 255u), cmax, cmin, mx);
                         wl[j >> 1] |= ((uint32_t)((L0 - 128) & 255) | (uint32_t)((L1 - 128) & 255) << 8) << ((j & 1) * 16);
                     }
                     // the lane's 32 pixels start at byte xodd of the window
@@ -173,8 +173,8 @@
                     for (int k = 0; k < npx; ++k) {
                         const int fx = src.x0 + xbeg + k;
                         const uint32_t m = __builtin_amdgcn_perm(0u, ((const uint32_t*)prow)[fx >> 1], psel);
-                        const YuvChroma c = yuv_chroma((int)((m >> 8) & 255u), (int)(m >> 24));
-                        const int L = yuv_lightness((int)((fx & 1 ? m >> 16 : m) & 255u), yuv_cmax(c), yuv_cmin(c));
+                        const YuvChroma c = yuv_chroma((int)((m >> 8) & 255u), (int)(m >> 24), mx);
+                        const int L = yuv_lightness((int)((fx & 1 ? m >> 16 : m) & 255u), yuv_cmax(c), yuv_cmin(c), mx);
                         w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
                     }
                 }

@@ -1,6 +1,10 @@
 // Baseline JPEG decode on the GPU: replaces the host decode behind
 // cv2.imread (meterelf/_image.py:49) for the files the meter cameras write -- baseline sequential
-// DCT, 8 bit, Huffman, one interleaved scan, YCbCr 4:2:0 / 4:2:2 / 4:4:4 or greyscale.
+// DCT, 8 bit, Huffman, one interleaved scan, YCbCr 4:2:0 / 4:2:2 / 4:4:4 or greyscale.  Within that: SOF0 or SOF1, Huffman
+// table ids 0 and 1 in any assignment to the components, quantisation tables 0..3 with 8- or 16-bit entries, any component
+// ids, any order and packing of the header segments.  Everything else is reported unsupported (the caller's host decoder
+// takes it), including a file that refers to a Huffman table it does not define (libjpeg-turbo falls back to the Annex K
+// tables there) or to one libjpeg rejects (over-subscribed, using the all-ones code, a DC category above 15).
 //
 // The result must be the bytes libjpeg(-turbo) produces with its defaults (what cv2.imread and
 // Pillow both use): JDCT_ISLOW inverse DCT, "fancy" triangle-filter chroma upsampling, the
@@ -83,6 +87,26 @@ static int exif_orientation(const uint8_t* t, int n)
         }
     }
     return 0;
+}
+
+// What libjpeg checks when it builds the decoding table of a Huffman table the scan refers to (jdhuff, derived tables): the
+// canonical code counter must stay below 2^l after the codes of every length l in use -- an over-subscribed code set fails
+// that, and so does a complete one, whose last code is all ones -- and a DC table may only hold the categories 0..15.  A
+// table that fails makes libjpeg refuse the file; the kernels would decode something from it, so it is refused here too.
+static const char* huff_spec_flaw(const HuffSpec& t, const bool dc)
+{
+    int last = 0;
+    for (int l = 1; l <= 16; ++l) if (t.bits[l]) last = l;
+    long code = 0;
+    for (int l = 1; l <= last; ++l) {
+        code += t.bits[l];
+        if (code >= (1L << l)) return "Huffman table over-subscribed or using the all-ones code (libjpeg rejects it)";
+        code <<= 1;
+    }
+    if (dc)
+        for (int i = 0; i < t.nvals; ++i)
+            if (t.vals[i] > 15) return "DC Huffman table with a category above 15 (libjpeg rejects it)";
+    return nullptr;
 }
 
 static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h)
@@ -207,6 +231,8 @@ done:
     for (int c = 0; c < h.ncomp && !h.why; ++c) {
         if (!h.qt_set[h.tq[c]]) h.why = "missing quantisation table";
         else if (!h.dc[h.td[c]].set || !h.ac[h.ta[c]].set) h.why = "missing Huffman table";
+        else if (const char* flaw = huff_spec_flaw(h.dc[h.td[c]], true)) h.why = flaw;
+        else if (const char* flaw_ac = huff_spec_flaw(h.ac[h.ta[c]], false)) h.why = flaw_ac;
     }
     return 0;
 }

@@ -144,6 +144,27 @@ class MeterReader:
         """Full camera frames (N, H, W, 3) BGR -> records."""
         return self.ctx.process_batch(frames)
 
+    def _read_view(self, v, out, host_call, dev_call):
+        """What the read_*_frames methods share once the frames are described (v: a *FramesView): host frames -> host_call();
+        frames on this reader's GPU -> dev_call(...) on torch.cuda.current_stream, the records into out where one is given."""
+        if not v.on_device:
+            if out is not None:
+                raise ValueError('out= takes the records of device frames only')
+            return host_call()
+        import torch
+        if v.device != self.device:
+            raise ValueError('frames are on cuda:%s, the reader on cuda:%d' % (v.device, self.device))
+        stream = torch.cuda.current_stream(self.device)
+        if out is None:
+            return dev_call(stream=stream.cuda_stream)
+        if (not _hip._is_torch(out) or out.dtype != torch.uint8 or out.device != v.array.device or not out.is_contiguous()
+                or tuple(out.shape) != (v.n, _hip.RESULT_DTYPE.itemsize)):
+            raise ValueError('out must be a contiguous uint8 tensor of shape (%d, %d) on %s' % (v.n, _hip.RESULT_DTYPE.itemsize, v.array.device))
+        if v.copied:
+            v.array.record_stream(stream)   # the packed copy lives until the stream has passed the call's kernels
+        dev_call(d_results_ptr=out.data_ptr(), want_host=False, stream=stream.cuda_stream)
+        return out
+
     def read_frame_views(self, frames, pixel_format: str = 'bgr', out=None):
         """Full camera frames in the layout the caller has -> records, equal to read_frames() of the packed BGR frames made from
         them (melf_process_frames*).  frames: (N, H, W, C) uint8, a numpy array / torch CPU tensor (host path) or a torch tensor
@@ -153,25 +174,9 @@ class MeterReader:
         the stream (device frames only); returns it.  Otherwise returns the records.
         Channels-first (N, C, H, W) frames: read_planar_frames reads them in place; a permuted view of them is copied here."""
         v = _hip.frames_view(frames, pixel_format)
-        if not v.on_device:
-            if out is not None:
-                raise ValueError('out= takes the records of device frames only')
-            return self.ctx.process_frames(v.ptr, v.pixel_format, v.n, v.H, v.W, v.row_pitch, v.frame_stride)
-        import torch
-        if v.device != self.device:
-            raise ValueError('frames are on cuda:%s, the reader on cuda:%d' % (v.device, self.device))
-        stream = torch.cuda.current_stream(self.device)
-        if out is None:
-            return self.ctx.process_frames_dev(v.ptr, v.pixel_format, v.n, v.H, v.W, v.row_pitch, v.frame_stride,
-                                               stream=stream.cuda_stream)
-        if (not _hip._is_torch(out) or out.dtype != torch.uint8 or out.device != v.array.device or not out.is_contiguous()
-                or tuple(out.shape) != (v.n, _hip.RESULT_DTYPE.itemsize)):
-            raise ValueError('out must be a contiguous uint8 tensor of shape (%d, %d) on %s' % (v.n, _hip.RESULT_DTYPE.itemsize, v.array.device))
-        if v.copied:
-            v.array.record_stream(stream)   # the packed copy lives until the stream has passed the call's kernels
-        self.ctx.process_frames_dev(v.ptr, v.pixel_format, v.n, v.H, v.W, v.row_pitch, v.frame_stride, d_results_ptr=out.data_ptr(),
-                                    want_host=False, stream=stream.cuda_stream)
-        return out
+        geom = (v.pixel_format, v.n, v.H, v.W, v.row_pitch, v.frame_stride)
+        return self._read_view(v, out, lambda: self.ctx.process_frames(v.ptr, *geom),
+                               lambda **kw: self.ctx.process_frames_dev(v.ptr, *geom, **kw))
 
     def read_yuv_frames(self, frames, pixel_format: str = 'nv12', matrix='bt601', out=None):
         """YUV 4:2:0 video frames -> records, equal to read_frames() of the packed BGR frames that the integer conversion of
@@ -186,23 +191,7 @@ class MeterReader:
         records without synchronising the stream (device frames only); returns it.  Otherwise returns the records."""
         v = _hip.yuv_frames_view(frames, pixel_format, matrix)
         desc = v.descriptor()
-        if not v.on_device:
-            if out is not None:
-                raise ValueError('out= takes the records of device frames only')
-            return self.ctx.process_yuv(v.ptr, desc)
-        import torch
-        if v.device != self.device:
-            raise ValueError('frames are on cuda:%s, the reader on cuda:%d' % (v.device, self.device))
-        stream = torch.cuda.current_stream(self.device)
-        if out is None:
-            return self.ctx.process_yuv_dev(v.ptr, desc, stream=stream.cuda_stream)
-        if (not _hip._is_torch(out) or out.dtype != torch.uint8 or out.device != v.array.device or not out.is_contiguous()
-                or tuple(out.shape) != (v.n, _hip.RESULT_DTYPE.itemsize)):
-            raise ValueError('out must be a contiguous uint8 tensor of shape (%d, %d) on %s' % (v.n, _hip.RESULT_DTYPE.itemsize, v.array.device))
-        if v.copied:
-            v.array.record_stream(stream)   # the packed copy lives until the stream has passed the call's kernels
-        self.ctx.process_yuv_dev(v.ptr, desc, d_results_ptr=out.data_ptr(), want_host=False, stream=stream.cuda_stream)
-        return out
+        return self._read_view(v, out, lambda: self.ctx.process_yuv(v.ptr, desc), lambda **kw: self.ctx.process_yuv_dev(v.ptr, desc, **kw))
 
     def read_yuv422_frames(self, frames, pixel_format: str = 'yuyv', matrix='bt601', out=None):
         """Packed YUV 4:2:2 frames (UVC / V4L2 YUYV, capture-card UYVY, YVYU) -> records, equal to read_frames() of the packed BGR
@@ -216,23 +205,7 @@ class MeterReader:
         frames only); returns it.  Otherwise returns the records."""
         v = _hip.yuv422_frames_view(frames, pixel_format, matrix)
         desc = v.descriptor()
-        if not v.on_device:
-            if out is not None:
-                raise ValueError('out= takes the records of device frames only')
-            return self.ctx.process_yuv422(v.ptr, desc)
-        import torch
-        if v.device != self.device:
-            raise ValueError('frames are on cuda:%s, the reader on cuda:%d' % (v.device, self.device))
-        stream = torch.cuda.current_stream(self.device)
-        if out is None:
-            return self.ctx.process_yuv422_dev(v.ptr, desc, stream=stream.cuda_stream)
-        if (not _hip._is_torch(out) or out.dtype != torch.uint8 or out.device != v.array.device or not out.is_contiguous()
-                or tuple(out.shape) != (v.n, _hip.RESULT_DTYPE.itemsize)):
-            raise ValueError('out must be a contiguous uint8 tensor of shape (%d, %d) on %s' % (v.n, _hip.RESULT_DTYPE.itemsize, v.array.device))
-        if v.copied:
-            v.array.record_stream(stream)   # the packed copy lives until the stream has passed the call's kernels
-        self.ctx.process_yuv422_dev(v.ptr, desc, d_results_ptr=out.data_ptr(), want_host=False, stream=stream.cuda_stream)
-        return out
+        return self._read_view(v, out, lambda: self.ctx.process_yuv422(v.ptr, desc), lambda **kw: self.ctx.process_yuv422_dev(v.ptr, desc, **kw))
 
     def read_planar_frames(self, frames, channel_order: str = 'rgb', out=None):
         """Planar, channels-first frames (N, 3, H, W) / (N, 4, H, W) uint8 -> records, equal to read_frames() of the packed BGR
@@ -243,23 +216,7 @@ class MeterReader:
         records without synchronising the stream (device frames only); returns it.  Otherwise returns the records."""
         v = _hip.planar_frames_view(frames, channel_order)
         desc = v.descriptor()
-        if not v.on_device:
-            if out is not None:
-                raise ValueError('out= takes the records of device frames only')
-            return self.ctx.process_planes(v.ptr, desc)
-        import torch
-        if v.device != self.device:
-            raise ValueError('frames are on cuda:%s, the reader on cuda:%d' % (v.device, self.device))
-        stream = torch.cuda.current_stream(self.device)
-        if out is None:
-            return self.ctx.process_planes_dev(v.ptr, desc, stream=stream.cuda_stream)
-        if (not _hip._is_torch(out) or out.dtype != torch.uint8 or out.device != v.array.device or not out.is_contiguous()
-                or tuple(out.shape) != (v.n, _hip.RESULT_DTYPE.itemsize)):
-            raise ValueError('out must be a contiguous uint8 tensor of shape (%d, %d) on %s' % (v.n, _hip.RESULT_DTYPE.itemsize, v.array.device))
-        if v.copied:
-            v.array.record_stream(stream)   # the packed copy lives until the stream has passed the call's kernels
-        self.ctx.process_planes_dev(v.ptr, desc, d_results_ptr=out.data_ptr(), want_host=False, stream=stream.cuda_stream)
-        return out
+        return self._read_view(v, out, lambda: self.ctx.process_planes(v.ptr, desc), lambda **kw: self.ctx.process_planes_dev(v.ptr, desc, **kw))
 
     def read_crops(self, crops: np.ndarray) -> np.ndarray:
         """Already meter_rect-cropped images (the reference's bgr_image injection)."""

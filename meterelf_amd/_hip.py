@@ -269,6 +269,32 @@ def _owner_span(a, is_torch):
     return lo, hi + root.itemsize
 
 
+def _unwrap(frames):
+    """(frames, is_torch, shape, strides, ptr, on_device, device) of a uint8 torch tensor or of what np.asarray makes of anything
+    else; strides in bytes, device: the GPU's index of a tensor on one.  Not uint8: ValueError."""
+    if _is_torch(frames):
+        if str(frames.dtype) != 'torch.uint8':
+            raise ValueError('frames must be uint8, not %s' % frames.dtype)
+        on_device = frames.device.type == 'cuda'
+        return (frames, True, tuple(frames.shape), tuple(frames.stride()),          # elements = bytes for uint8
+                frames.data_ptr(), on_device, frames.device.index if on_device else None)
+    frames = np.asarray(frames)
+    if frames.dtype != np.uint8:
+        raise ValueError('frames must be uint8, not %s' % frames.dtype)
+    return (frames, False, frames.shape, frames.strides, frames.ctypes.data, False, None)
+
+
+def _packed_copy(frames, is_torch):
+    """(copy, its address): the frames copied once to a packed array -- a fresh allocation (aligned) even where they are contiguous
+    already."""
+    if is_torch:
+        import torch
+        frames = frames.clone(memory_format=torch.contiguous_format)
+        return frames, frames.data_ptr()
+    frames = np.array(frames, order='C', copy=True)
+    return frames, frames.ctypes.data
+
+
 def frames_view(frames, pixel_format='bgr'):
     """Describes an (N, H, W, C) uint8 numpy array or torch tensor as melf_process_frames* read it -- the one place that maps an
     array's layout to pointer, pixel format, row pitch and frame stride.  pixel_format: the order of the array's channels,
@@ -276,23 +302,7 @@ def frames_view(frames, pixel_format='bgr'):
     (rgba[..., :3]) is read as the 4-byte format of the same order; padded rows and frames (frames[:, :, :w], frames[::2]) are
     read in place.  A layout the kernels cannot read -- a channel stride other than 1, negative or odd strides, a misaligned
     4-byte layout -- is copied once to a packed array (FramesView.copied).  Not uint8, or C not 3 / 4: ValueError."""
-    is_torch = _is_torch(frames)
-    if is_torch:
-        if str(frames.dtype) != 'torch.uint8':
-            raise ValueError('frames must be uint8, not %s' % frames.dtype)
-        shape = tuple(frames.shape)
-        strides = tuple(frames.stride())          # elements = bytes for uint8
-        ptr = frames.data_ptr()
-        on_device = frames.device.type == 'cuda'
-        device = frames.device.index if on_device else None
-    else:
-        frames = np.asarray(frames)
-        if frames.dtype != np.uint8:
-            raise ValueError('frames must be uint8, not %s' % frames.dtype)
-        shape = frames.shape
-        strides = frames.strides
-        ptr = frames.ctypes.data
-        (on_device, device) = (False, None)
+    (frames, is_torch, shape, strides, ptr, on_device, device) = _unwrap(frames)
     if len(shape) != 4 or shape[3] not in (3, 4):
         raise ValueError('frames must be (N, H, W, 3) or (N, H, W, 4), not %s' % (shape,))
     fmt = str(pixel_format).lower()
@@ -320,16 +330,10 @@ def frames_view(frames, pixel_format='bgr'):
         (lo, hi) = _owner_span(frames, is_torch)
         ok = lo <= ptr and ptr + extent <= hi
     if not ok:
-        # a fresh allocation (aligned) even where the array is contiguous already (a misaligned 4-byte layout)
-        if is_torch:
-            import torch
-            frames = frames.clone(memory_format=torch.contiguous_format)
-        else:
-            frames = np.array(frames, order='C', copy=True)
+        (frames, ptr) = _packed_copy(frames, is_torch)   # also where the array is contiguous already (a misaligned 4-byte layout)
         code = PIX_CODES[fmt]
         bpp = PIX_BYTES[code]
         (rp, fs) = (W * bpp, H * W * bpp)
-        ptr = frames.data_ptr() if is_torch else frames.ctypes.data
         extent = n * fs
     return FramesView(int(ptr), on_device, device, code, n, H, W, int(rp), int(fs), int(extent), not ok, frames)
 
@@ -385,23 +389,7 @@ def yuv_frames_view(frames, pixel_format='nv12', matrix='bt601'):
     cameras: ffmpeg's yuvj420p, raw UVC), 'bt709-full' (screen and capture pipelines).  Not uint8, not three-dimensional, an odd H
     or W, an unknown format or an unknown matrix: ValueError."""
     mcode = yuv_matrix_code(matrix)
-    is_torch = _is_torch(frames)
-    if is_torch:
-        if str(frames.dtype) != 'torch.uint8':
-            raise ValueError('frames must be uint8, not %s' % frames.dtype)
-        shape = tuple(frames.shape)
-        strides = tuple(frames.stride())          # elements = bytes for uint8
-        ptr = frames.data_ptr()
-        on_device = frames.device.type == 'cuda'
-        device = frames.device.index if on_device else None
-    else:
-        frames = np.asarray(frames)
-        if frames.dtype != np.uint8:
-            raise ValueError('frames must be uint8, not %s' % frames.dtype)
-        shape = frames.shape
-        strides = frames.strides
-        ptr = frames.ctypes.data
-        (on_device, device) = (False, None)
+    (frames, is_torch, shape, strides, ptr, on_device, device) = _unwrap(frames)
     fmt = str(pixel_format).lower()
     if fmt not in YUV_CODES:
         raise ValueError('pixel_format %r is not a YUV 4:2:0 layout (nv12, i420, yv12)' % (pixel_format,))
@@ -416,13 +404,8 @@ def yuv_frames_view(frames, pixel_format='nv12', matrix='bt601'):
     planar = code == YUV_I420
     ok = es == 1 and rp >= W and fs >= (rows - 1) * rp + W and rp <= 2 ** 31 - 1 and (not planar or rp == W)
     if not ok:
-        if is_torch:
-            import torch
-            frames = frames.clone(memory_format=torch.contiguous_format)
-        else:
-            frames = np.array(frames, order='C', copy=True)
+        (frames, ptr) = _packed_copy(frames, is_torch)
         (rp, fs) = (W, rows * W)
-        ptr = frames.data_ptr() if is_torch else frames.ctypes.data
     if planar:
         (c_pitch, first, second) = (W // 2, H * W, H * W + (H // 2) * (W // 2))
         (u_off, v_off) = (second, first) if fmt == 'yv12' else (first, second)
@@ -465,23 +448,7 @@ def yuv422_frames_view(frames, pixel_format='yuyv', matrix='bt601'):
     YUV_BT* code (raw UVC webcams deliver 'bt601-full', HD capture cards 'bt709').  Not uint8, not four-dimensional, a last dimension
     other than 2, an odd or zero W, a zero H, an unknown format name or an unknown matrix: ValueError."""
     mcode = yuv_matrix_code(matrix)
-    is_torch = _is_torch(frames)
-    if is_torch:
-        if str(frames.dtype) != 'torch.uint8':
-            raise ValueError('frames must be uint8, not %s' % frames.dtype)
-        shape = tuple(frames.shape)
-        strides = tuple(frames.stride())          # elements = bytes for uint8
-        ptr = frames.data_ptr()
-        on_device = frames.device.type == 'cuda'
-        device = frames.device.index if on_device else None
-    else:
-        frames = np.asarray(frames)
-        if frames.dtype != np.uint8:
-            raise ValueError('frames must be uint8, not %s' % frames.dtype)
-        shape = frames.shape
-        strides = frames.strides
-        ptr = frames.ctypes.data
-        (on_device, device) = (False, None)
+    (frames, is_torch, shape, strides, ptr, on_device, device) = _unwrap(frames)
     fmt = str(pixel_format).lower()
     if fmt not in YUV422_CODES:
         raise ValueError('pixel_format %r is not a packed YUV 4:2:2 layout (yuyv / yuy2, uyvy, yvyu)' % (pixel_format,))
@@ -498,14 +465,8 @@ def yuv422_frames_view(frames, pixel_format='yuyv', matrix='bt601'):
         fs += -fs % 4
     ok = (es == 1 and ps == 2 and rp >= W * 2 and fs >= (H - 1) * rp + W * 2 and rp <= 2 ** 31 - 1 and (ptr | rp | fs) % 4 == 0)
     if not ok:
-        # a fresh allocation (aligned) even where the array is contiguous already (a misaligned base)
-        if is_torch:
-            import torch
-            frames = frames.clone(memory_format=torch.contiguous_format)
-        else:
-            frames = np.array(frames, order='C', copy=True)
+        (frames, ptr) = _packed_copy(frames, is_torch)   # also where the array is contiguous already (a misaligned base)
         (rp, fs) = (W * 2, H * W * 2)
-        ptr = frames.data_ptr() if is_torch else frames.ctypes.data
     extent = (n - 1) * fs + (H - 1) * rp + W * 2 if n else 0
     return Yuv422FramesView(int(ptr), on_device, device, code, n, H, W, int(rp), int(fs), int(extent), not ok, frames, mcode)
 
@@ -541,23 +502,7 @@ def planar_frames_view(frames, channel_order='rgb'):
     frames_view reads those), negative strides, overlapping planes -- is copied once to a packed (N, 3, H, W) array
     (PlanarFramesView.copied).  Not uint8, not four-dimensional, a zero H or W, or a channel_order that does not name the array's C
     planes: ValueError."""
-    is_torch = _is_torch(frames)
-    if is_torch:
-        if str(frames.dtype) != 'torch.uint8':
-            raise ValueError('frames must be uint8, not %s' % frames.dtype)
-        shape = tuple(frames.shape)
-        strides = tuple(frames.stride())          # elements = bytes for uint8
-        ptr = frames.data_ptr()
-        on_device = frames.device.type == 'cuda'
-        device = frames.device.index if on_device else None
-    else:
-        frames = np.asarray(frames)
-        if frames.dtype != np.uint8:
-            raise ValueError('frames must be uint8, not %s' % frames.dtype)
-        shape = frames.shape
-        strides = frames.strides
-        ptr = frames.ctypes.data
-        (on_device, device) = (False, None)
+    (frames, is_torch, shape, strides, ptr, on_device, device) = _unwrap(frames)
     order = str(channel_order).lower()
     if order not in PLANAR_ORDERS:
         raise ValueError('channel_order %r is not one of %s' % (channel_order, ', '.join(PLANAR_ORDERS)))
@@ -579,14 +524,9 @@ def planar_frames_view(frames, channel_order='rgb'):
     ok = es == 1 and W <= rp <= 2 ** 31 - 1 and ps >= span and fs >= max(ib, ig, ir) * ps + span
     if not ok:
         # the three colour planes, packed, in the caller's order (they are the first three of every order)
-        if is_torch:
-            import torch
-            frames = frames[:, :3].clone(memory_format=torch.contiguous_format)
-        else:
-            frames = np.array(frames[:, :3], order='C', copy=True)
+        (frames, ptr) = _packed_copy(frames[:, :3], is_torch)
         (rp, ps, fs) = (W, H * W, 3 * H * W)
         span = H * W
-        ptr = frames.data_ptr() if is_torch else frames.ctypes.data
     extent = (n - 1) * fs + max(ib, ig, ir) * ps + span if n else 0
     return PlanarFramesView(int(ptr), on_device, device, n, H, W, int(ib * ps), int(ig * ps), int(ir * ps), int(rp), int(fs), int(extent),
                             not ok, frames)
@@ -794,36 +734,36 @@ class Context:
             _ptr(out) if want_host else None, C.c_void_p(stream) if stream else None))
         return out
 
+    def _host(self, entry, frames_ptr, desc):
+        """A descriptor-taking host entry point (melf_process_frames / _yuv / _yuv422 / _planes) -> records."""
+        out = np.zeros(desc.n, RESULT_DTYPE)
+        check(entry(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
+        return out
+
+    def _dev(self, entry, d_frames_ptr, desc, d_results_ptr, want_host, stream):
+        """Its *_dev form: frames in HBM (device pointer as int), as process_batch_dev.  Returns records when want_host."""
+        out = np.zeros(desc.n, RESULT_DTYPE) if want_host else None
+        check(entry(self._h, C.c_void_p(d_frames_ptr), C.byref(desc), C.c_void_p(d_results_ptr) if d_results_ptr else None,
+                    _ptr(out) if want_host else None, C.c_void_p(stream) if stream else None))
+        return out
+
     def process_frames(self, frames_ptr, pixel_format, n, H, W, row_pitch, frame_stride):
         """Host frames in any PIX_* layout (melf_process_frames; frames_view describes an array) -> records."""
-        out = np.zeros(n, RESULT_DTYPE)
-        f = MelfFrames(pixel_format, n, H, W, row_pitch, frame_stride)
-        check(self._L.melf_process_frames(self._h, C.c_void_p(frames_ptr), C.byref(f), _ptr(out)))
-        return out
+        return self._host(self._L.melf_process_frames, frames_ptr, MelfFrames(pixel_format, n, H, W, row_pitch, frame_stride))
 
     def process_frames_dev(self, d_frames_ptr, pixel_format, n, H, W, row_pitch, frame_stride, d_results_ptr=None, want_host=True,
                            stream=None):
         """Frames in HBM in any PIX_* layout (melf_process_frames_dev, as process_batch_dev).  Returns records when want_host."""
-        out = np.zeros(n, RESULT_DTYPE) if want_host else None
-        f = MelfFrames(pixel_format, n, H, W, row_pitch, frame_stride)
-        check(self._L.melf_process_frames_dev(
-            self._h, C.c_void_p(d_frames_ptr), C.byref(f), C.c_void_p(d_results_ptr) if d_results_ptr else None,
-            _ptr(out) if want_host else None, C.c_void_p(stream) if stream else None))
-        return out
+        return self._dev(self._L.melf_process_frames_dev, d_frames_ptr, MelfFrames(pixel_format, n, H, W, row_pitch, frame_stride),
+                         d_results_ptr, want_host, stream)
 
     def process_yuv(self, frames_ptr, desc):
         """Host YUV 4:2:0 frames (melf_process_yuv; desc: a MelfYuvFrames, e.g. yuv_frames_view(...).descriptor()) -> records."""
-        out = np.zeros(desc.n, RESULT_DTYPE)
-        check(self._L.melf_process_yuv(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
-        return out
+        return self._host(self._L.melf_process_yuv, frames_ptr, desc)
 
     def process_yuv_dev(self, d_frames_ptr, desc, d_results_ptr=None, want_host=True, stream=None):
         """YUV 4:2:0 frames in HBM (melf_process_yuv_dev, as process_frames_dev).  Returns records when want_host."""
-        out = np.zeros(desc.n, RESULT_DTYPE) if want_host else None
-        check(self._L.melf_process_yuv_dev(
-            self._h, C.c_void_p(d_frames_ptr), C.byref(desc), C.c_void_p(d_results_ptr) if d_results_ptr else None,
-            _ptr(out) if want_host else None, C.c_void_p(stream) if stream else None))
-        return out
+        return self._dev(self._L.melf_process_yuv_dev, d_frames_ptr, desc, d_results_ptr, want_host, stream)
 
     def yuv_to_bgr(self, frames_ptr, desc):
         """The conversion alone (melf_yuv_to_bgr): host YUV 4:2:0 frames -> (n, H, W, 3) BGR."""
@@ -834,17 +774,11 @@ class Context:
     def process_yuv422(self, frames_ptr, desc):
         """Host packed YUV 4:2:2 frames (melf_process_yuv422; desc: a MelfYuv422Frames, e.g. yuv422_frames_view(...).descriptor())
         -> records."""
-        out = np.zeros(desc.n, RESULT_DTYPE)
-        check(self._L.melf_process_yuv422(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
-        return out
+        return self._host(self._L.melf_process_yuv422, frames_ptr, desc)
 
     def process_yuv422_dev(self, d_frames_ptr, desc, d_results_ptr=None, want_host=True, stream=None):
         """Packed YUV 4:2:2 frames in HBM (melf_process_yuv422_dev, as process_frames_dev).  Returns records when want_host."""
-        out = np.zeros(desc.n, RESULT_DTYPE) if want_host else None
-        check(self._L.melf_process_yuv422_dev(
-            self._h, C.c_void_p(d_frames_ptr), C.byref(desc), C.c_void_p(d_results_ptr) if d_results_ptr else None,
-            _ptr(out) if want_host else None, C.c_void_p(stream) if stream else None))
-        return out
+        return self._dev(self._L.melf_process_yuv422_dev, d_frames_ptr, desc, d_results_ptr, want_host, stream)
 
     def yuv422_to_bgr(self, frames_ptr, desc):
         """The conversion alone (melf_yuv422_to_bgr): host packed YUV 4:2:2 frames -> (n, H, W, 3) BGR."""
@@ -854,17 +788,11 @@ class Context:
 
     def process_planes(self, frames_ptr, desc):
         """Host planar frames (melf_process_planes; desc: a MelfPlanarFrames, e.g. planar_frames_view(...).descriptor()) -> records."""
-        out = np.zeros(desc.n, RESULT_DTYPE)
-        check(self._L.melf_process_planes(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
-        return out
+        return self._host(self._L.melf_process_planes, frames_ptr, desc)
 
     def process_planes_dev(self, d_frames_ptr, desc, d_results_ptr=None, want_host=True, stream=None):
         """Planar frames in HBM (melf_process_planes_dev, as process_frames_dev).  Returns records when want_host."""
-        out = np.zeros(desc.n, RESULT_DTYPE) if want_host else None
-        check(self._L.melf_process_planes_dev(
-            self._h, C.c_void_p(d_frames_ptr), C.byref(desc), C.c_void_p(d_results_ptr) if d_results_ptr else None,
-            _ptr(out) if want_host else None, C.c_void_p(stream) if stream else None))
-        return out
+        return self._dev(self._L.melf_process_planes_dev, d_frames_ptr, desc, d_results_ptr, want_host, stream)
 
     # --- stages ---
     def process_stream_dev(self, d_frames_ptr, nbatches, batch_stride, n, H, W, d_results_ptr, results_stride, frame_stride=None,

@@ -24,6 +24,8 @@
 #include <limits.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "melf_device.h"
 #include "melf_internal.h"
 
@@ -343,87 +345,44 @@ __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_v
 }
 #undef MELF_PLANAR_BODY
 
-void launch_dials(const DialsSrc& src, int pix, int n, const melf_params& P, const DialGeom* d_geom,
+// f(std::integral_constant<int, NR>) for the instantiated NR that holds ws_max window rows
+template <class F>
+static void with_nr(int ws_max, F&& f)
+{
+    if (ws_max <= 32) f(std::integral_constant<int, 32>{});
+    else if (ws_max <= 40) f(std::integral_constant<int, 40>{});
+    else if (ws_max <= 48) f(std::integral_constant<int, 48>{});
+    else if (ws_max <= 52) f(std::integral_constant<int, 52>{});
+    else if (ws_max <= 56) f(std::integral_constant<int, 56>{});
+    else f(std::integral_constant<int, 64>{});
+}
+
+void launch_dials(const DialsSrc& src, const FrameLayout& lay, int n, const melf_params& P, const DialGeom* d_geom,
                   const uint64_t* d_rowmasks, const MatchPartial* d_partials, int nparts, int rw,
-                  melf_result* d_results, hipStream_t stream, int ws_max, const YuvPlanes* yuv, const PlanarPlanes* planes,
-                  const YuvMatrix* ymat)
+                  melf_result* d_results, hipStream_t stream, int ws_max)
 {
     dim3 grid(n), block(64 * P.ndials);
     const size_t shmem = (size_t)P.ndials * DIAL_LDS_BYTES;
-    const int nr = ws_max <= 32 ? 32 : (ws_max <= 40 ? 40 : (ws_max <= 48 ? 48 : (ws_max <= 52 ? 52 : (ws_max <= 56 ? 56 : 64))));
-#define MELF_DIALS_LAUNCH(HLS, NRV) \
-    hipLaunchKernelGGL((k_dials<HLS, NRV>), grid, block, shmem, stream, src, P, d_geom, d_rowmasks, d_partials, nparts, rw, d_results)
-#define MELF_DIALS_NR(HLS)                                   \
-    switch (nr) {                                            \
-        case 32: MELF_DIALS_LAUNCH(HLS, 32); break;          \
-        case 40: MELF_DIALS_LAUNCH(HLS, 40); break;          \
-        case 48: MELF_DIALS_LAUNCH(HLS, 48); break;          \
-        case 52: MELF_DIALS_LAUNCH(HLS, 52); break;          \
-        case 56: MELF_DIALS_LAUNCH(HLS, 56); break;          \
-        default: MELF_DIALS_LAUNCH(HLS, 64); break;          \
-    }
-#define MELF_NEEDLES_LAUNCH(BPP, NRV)                                                                                          \
-    hipLaunchKernelGGL((k_needles<BPP, NRV>), grid, block, shmem, stream, src, P, d_geom, d_rowmasks, d_partials, nparts, rw, d_results, \
-                       swap_rb)
-#define MELF_NEEDLES_NR(BPP)                                 \
-    switch (nr) {                                            \
-        case 32: MELF_NEEDLES_LAUNCH(BPP, 32); break;        \
-        case 40: MELF_NEEDLES_LAUNCH(BPP, 40); break;        \
-        case 48: MELF_NEEDLES_LAUNCH(BPP, 48); break;        \
-        case 52: MELF_NEEDLES_LAUNCH(BPP, 52); break;        \
-        case 56: MELF_NEEDLES_LAUNCH(BPP, 56); break;        \
-        default: MELF_NEEDLES_LAUNCH(BPP, 64); break;        \
-    }
-#define MELF_YNEEDLE_LAUNCH(PL, NRV) \
-    hipLaunchKernelGGL((k_yneedle<PL, NRV>), grid, block, shmem, stream, src, *yuv, *ymat, P, d_geom, d_rowmasks, d_partials, nparts, rw, d_results)
-#define MELF_YNEEDLE_NR(PL)                                  \
-    switch (nr) {                                            \
-        case 32: MELF_YNEEDLE_LAUNCH(PL, 32); break;         \
-        case 40: MELF_YNEEDLE_LAUNCH(PL, 40); break;         \
-        case 48: MELF_YNEEDLE_LAUNCH(PL, 48); break;         \
-        case 52: MELF_YNEEDLE_LAUNCH(PL, 52); break;         \
-        case 56: MELF_YNEEDLE_LAUNCH(PL, 56); break;         \
-        default: MELF_YNEEDLE_LAUNCH(PL, 64); break;         \
-    }
-#define MELF_P422_NEEDLE_LAUNCH(NRV) \
-    hipLaunchKernelGGL((k_p422_needle<NRV>), grid, block, shmem, stream, src, p422_sel(pix), *ymat, P, d_geom, d_rowmasks, d_partials, nparts, rw, d_results)
-#define MELF_PLANAR_NEEDLE_LAUNCH(NRV) \
-    hipLaunchKernelGGL((k_planar_needle<NRV>), grid, block, shmem, stream, src, *planes, P, d_geom, d_rowmasks, d_partials, nparts, rw, d_results)
-    const int swap_rb = pix == MELF_PIX_RGB || pix == MELF_PIX_RGBA;
-    if (pix == PIX_PLANAR) {
-        switch (nr) {
-            case 32: MELF_PLANAR_NEEDLE_LAUNCH(32); break;
-            case 40: MELF_PLANAR_NEEDLE_LAUNCH(40); break;
-            case 48: MELF_PLANAR_NEEDLE_LAUNCH(48); break;
-            case 52: MELF_PLANAR_NEEDLE_LAUNCH(52); break;
-            case 56: MELF_PLANAR_NEEDLE_LAUNCH(56); break;
-            default: MELF_PLANAR_NEEDLE_LAUNCH(64); break;
-        }
-    }
-    else if (pix_p422(pix)) {
-        switch (nr) {
-            case 32: MELF_P422_NEEDLE_LAUNCH(32); break;
-            case 40: MELF_P422_NEEDLE_LAUNCH(40); break;
-            case 48: MELF_P422_NEEDLE_LAUNCH(48); break;
-            case 52: MELF_P422_NEEDLE_LAUNCH(52); break;
-            case 56: MELF_P422_NEEDLE_LAUNCH(56); break;
-            default: MELF_P422_NEEDLE_LAUNCH(64); break;
-        }
-    }
-    else if (pix == PIX_NV12) { MELF_YNEEDLE_NR(false) }
-    else if (pix == PIX_I420) { MELF_YNEEDLE_NR(true) }
-    else if (pix == PIX_PLANE) { MELF_DIALS_NR(true) }
-    else if (pix == MELF_PIX_BGR) { MELF_DIALS_NR(false) }
-    else if (pix == MELF_PIX_RGB) { MELF_NEEDLES_NR(3) }
-    else { MELF_NEEDLES_NR(4) }
-#undef MELF_PLANAR_NEEDLE_LAUNCH
-#undef MELF_P422_NEEDLE_LAUNCH
-#undef MELF_YNEEDLE_NR
-#undef MELF_YNEEDLE_LAUNCH
-#undef MELF_NEEDLES_NR
-#undef MELF_NEEDLES_LAUNCH
-#undef MELF_DIALS_NR
-#undef MELF_DIALS_LAUNCH
+    const int pix = lay.pix;
+    with_nr(ws_max, [&](auto nr) {
+        constexpr int NR = decltype(nr)::value;
+        // lead: a kernel family's own arguments, which stand between src and P
+        auto go = [&](auto kernel, auto... lead) {
+            hipLaunchKernelGGL(kernel, grid, block, shmem, stream, src, lead..., P, d_geom, d_rowmasks, d_partials, nparts, rw, d_results);
+        };
+        auto go_needles = [&](auto kernel) {
+            const int swap_rb = pix == MELF_PIX_RGB || pix == MELF_PIX_RGBA;
+            hipLaunchKernelGGL(kernel, grid, block, shmem, stream, src, P, d_geom, d_rowmasks, d_partials, nparts, rw, d_results, swap_rb);
+        };
+        if (pix == PIX_PLANAR) go(k_planar_needle<NR>, lay.planes);
+        else if (pix_p422(pix)) go(k_p422_needle<NR>, p422_sel(pix), *lay.mx);
+        else if (pix == PIX_NV12) go(k_yneedle<false, NR>, lay.yuv, *lay.mx);
+        else if (pix == PIX_I420) go(k_yneedle<true, NR>, lay.yuv, *lay.mx);
+        else if (pix == PIX_PLANE) go(k_dials<true, NR>);
+        else if (pix == MELF_PIX_BGR) go(k_dials<false, NR>);
+        else if (pix == MELF_PIX_RGB) go_needles(k_needles<3, NR>);
+        else go_needles(k_needles<4, NR>);
+    });
 }
 
 }  // namespace melf

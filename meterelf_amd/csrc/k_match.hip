@@ -219,10 +219,10 @@ int match_parts(const MatchGeom& g, int rows, int cols)
     return nrb * ncb;
 }
 
-void launch_match(const MatchSrc& src, int pix, int n, const MatchGeom& g, const uint32_t* d_tplT,
-                  float* d_result_map, MatchPartial* d_partials, int* nparts_out, hipStream_t stream, const YuvPlanes* yuv,
-                  const PlanarPlanes* planes, const YuvMatrix* mx)
+void launch_match(const MatchSrc& src, const FrameLayout& lay, int n, const MatchGeom& g, const uint32_t* d_tplT,
+                  float* d_result_map, MatchPartial* d_partials, int* nparts_out, hipStream_t stream)
 {
+    const int pix = lay.pix;
     const int rh = src.rows - g.th + 1, rw = src.cols - g.tw + 1;
     const int nrb = (rh + MATCH_RBLK - 1) / MATCH_RBLK, ncb = (rw + MATCH_CBLK - 1) / MATCH_CBLK;
     const int nparts = nrb * ncb;
@@ -230,16 +230,16 @@ void launch_match(const MatchSrc& src, int pix, int n, const MatchGeom& g, const
     const size_t shmem = (size_t)g.lds_rows * g.ldsw * sizeof(uint32_t);
     dim3 grid(nparts, n), block(256);
     if (pix == PIX_PLANAR)
-        hipLaunchKernelGGL(k_planar_match, grid, block, shmem, stream, src, *planes, g, d_tplT, rh, rw, nrb, d_result_map,
+        hipLaunchKernelGGL(k_planar_match, grid, block, shmem, stream, src, lay.planes, g, d_tplT, rh, rw, nrb, d_result_map,
                            d_partials, nparts);
     else if (pix_p422(pix))
-        hipLaunchKernelGGL(k_p422_match, grid, block, shmem, stream, src, p422_sel(pix), *mx, g, d_tplT, rh, rw, nrb, d_result_map,
+        hipLaunchKernelGGL(k_p422_match, grid, block, shmem, stream, src, p422_sel(pix), *lay.mx, g, d_tplT, rh, rw, nrb, d_result_map,
                            d_partials, nparts);
     else if (pix == PIX_NV12)
-        hipLaunchKernelGGL(k_match_yuv<false>, grid, block, shmem, stream, src, *yuv, *mx, g, d_tplT, rh, rw, nrb, d_result_map,
+        hipLaunchKernelGGL(k_match_yuv<false>, grid, block, shmem, stream, src, lay.yuv, *lay.mx, g, d_tplT, rh, rw, nrb, d_result_map,
                            d_partials, nparts);
     else if (pix == PIX_I420)
-        hipLaunchKernelGGL(k_match_yuv<true>, grid, block, shmem, stream, src, *yuv, *mx, g, d_tplT, rh, rw, nrb, d_result_map,
+        hipLaunchKernelGGL(k_match_yuv<true>, grid, block, shmem, stream, src, lay.yuv, *lay.mx, g, d_tplT, rh, rw, nrb, d_result_map,
                            d_partials, nparts);
     else if (pix == PIX_PLANE)
         hipLaunchKernelGGL(k_match<false>, grid, block, shmem, stream, src, g, d_tplT, rh, rw, nrb, d_result_map,

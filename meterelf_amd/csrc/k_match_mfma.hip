@@ -799,10 +799,10 @@ void mfma_build_atab(const uint8_t* templ, int th, int tw, int8_t* atab)
     }
 }
 
-void launch_match_prep(const MatchSrc& src, int pix, int n, int groups, int rows_pad, int nkb, int rwp, int tw, int8_t* d_lg,
-                       uint16_t* d_r, hipStream_t stream, int pairs, const YuvPlanes* yuv, const PlanarPlanes* planes,
-                       const YuvMatrix* mx)
+void launch_match_prep(const MatchSrc& src, const FrameLayout& lay, int n, int groups, int rows_pad, int nkb, int rwp, int tw,
+                       int8_t* d_lg, uint16_t* d_r, hipStream_t stream, int pairs)
 {
+    const int pix = lay.pix;
     dim3 grid(rows_pad, groups), block(256);
     const size_t pre_bytes = (size_t)32 * (nkb * 32 + 8) * sizeof(int16_t);
     int dev = 0;
@@ -818,20 +818,20 @@ void launch_match_prep(const MatchSrc& src, int pix, int n, int groups, int rows
         (void)hipFuncSetAttribute((const void*)k_planar_lplane, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         attr_set[dev] = true;
     }
-    if (pix == PIX_PLANAR) hipLaunchKernelGGL(k_planar_lplane, grid, block, pre_bytes, stream, src, *planes, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
-    else if (pix_p422(pix)) hipLaunchKernelGGL(k_p422_lplane, grid, block, pre_bytes, stream, src, p422_sel(pix), *mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
-    else if (pix == PIX_NV12) hipLaunchKernelGGL((k_lplane_yuv<false>), grid, block, pre_bytes, stream, src, *yuv, *mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
-    else if (pix == PIX_I420) hipLaunchKernelGGL((k_lplane_yuv<true>), grid, block, pre_bytes, stream, src, *yuv, *mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    if (pix == PIX_PLANAR) hipLaunchKernelGGL(k_planar_lplane, grid, block, pre_bytes, stream, src, lay.planes, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    else if (pix_p422(pix)) hipLaunchKernelGGL(k_p422_lplane, grid, block, pre_bytes, stream, src, p422_sel(pix), *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    else if (pix == PIX_NV12) hipLaunchKernelGGL((k_lplane_yuv<false>), grid, block, pre_bytes, stream, src, lay.yuv, *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    else if (pix == PIX_I420) hipLaunchKernelGGL((k_lplane_yuv<true>), grid, block, pre_bytes, stream, src, lay.yuv, *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else if (pix == PIX_PLANE) hipLaunchKernelGGL((k_prep_lplane<false>), grid, block, pre_bytes, stream, src, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else if (pix_bytes(pix) == 4) hipLaunchKernelGGL(k_lplane_px4, grid, block, pre_bytes, stream, src, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else hipLaunchKernelGGL((k_prep_lplane<true>), grid, block, pre_bytes, stream, src, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
 }
 
-void launch_mfma_prep(const MatchSrc& src, int pix, int n, const MfmaPlan& p, int th, int tw, int8_t* d_lg,
-                      uint16_t* d_r, hipStream_t stream, const YuvPlanes* yuv, const PlanarPlanes* planes, const YuvMatrix* mx)
+void launch_mfma_prep(const MatchSrc& src, const FrameLayout& lay, int n, const MfmaPlan& p, int th, int tw, int8_t* d_lg,
+                      uint16_t* d_r, hipStream_t stream)
 {
     (void)th;
-    launch_match_prep(src, pix, n, p.groups, p.rows_pad, p.nkb, 64, tw, d_lg, d_r, stream, p.nxb, yuv, planes, mx);   // one paired operand per column block
+    launch_match_prep(src, lay, n, p.groups, p.rows_pad, p.nkb, 64, tw, d_lg, d_r, stream, p.nxb);   // one paired operand per column block
 }
 
 template <int NXB, int RB, int KS>

@@ -264,7 +264,7 @@ struct melf_ctx {
     size_t results_cap = 0;
     uint8_t* d_stage_in = nullptr;
     size_t stage_in_cap = 0;
-    // host-fed path (melf_process_batch): two pinned staging buffers, a copy stream and the packed crops in HBM
+    // host-fed path (stage_host_frames): two pinned staging buffers, a copy stream and the staged frames in HBM
     uint8_t* h_pin[2] = {nullptr, nullptr};
     size_t pin_cap[2] = {0, 0};
     hipEvent_t ev_h2d[2] = {nullptr, nullptr};
@@ -1046,18 +1046,15 @@ static int gen_entry(melf_ctx* c, int rows, int cols, int n, melf_ctx::GenEntry*
 
 // prep + match of m images on stream ls with lane bl's work buffers; *parts / *nparts: per-frame (max, first arg-max)
 // partials for the consumer (k_dials or the host fold of melf_match_ccoeff)
-static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int bl, hipStream_t ls, float* d_map,
-                          MatchPartial** parts, int* nparts, TimedEvent& ev, const YuvPlanes* yuv, const PlanarPlanes* planes,
-                          const YuvMatrix* mx);
-static int run_match(melf_ctx* c, const MatchSrc& ms, int pix, int m, int bl, hipStream_t ls, float* d_map,
-                     MatchPartial** parts, int* nparts, const YuvPlanes* yuv = nullptr /* pix_yuv(pix): the chroma planes */,
-                     const PlanarPlanes* planes = nullptr /* PIX_PLANAR: the three planes */,
-                     const YuvMatrix* mx = nullptr /* pix_yuv(pix), pix_p422(pix): the frames' colour conversion */)
+static int run_match_impl(melf_ctx* c, const MatchSrc& ms, const FrameLayout& lay, int m, int bl, hipStream_t ls, float* d_map,
+                          MatchPartial** parts, int* nparts, TimedEvent& ev);
+static int run_match(melf_ctx* c, const MatchSrc& ms, const FrameLayout& lay, int m, int bl, hipStream_t ls, float* d_map,
+                     MatchPartial** parts, int* nparts)
 {
     TimedEvent ev;
     ev.kernel = MELF_K_MATCH;
     ev.start = ev.stop = nullptr;
-    const int rc = run_match_impl(c, ms, pix, m, bl, ls, d_map, parts, nparts, ev, yuv, planes, mx);
+    const int rc = run_match_impl(c, ms, lay, m, bl, ls, d_map, parts, nparts, ev);
     if (rc == MELF_SUCCESS && ev.start && ev.stop) {
         c->events.push_back(ev);
     } else {   // nothing was launched with them (an allocation failed on the way)
@@ -1066,9 +1063,8 @@ static int run_match(melf_ctx* c, const MatchSrc& ms, int pix, int m, int bl, hi
     }
     return rc;
 }
-static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int bl, hipStream_t ls, float* d_map,
-                          MatchPartial** parts, int* nparts, TimedEvent& ev, const YuvPlanes* yuv, const PlanarPlanes* planes,
-                          const YuvMatrix* mx)
+static int run_match_impl(melf_ctx* c, const MatchSrc& ms, const FrameLayout& lay, int m, int bl, hipStream_t ls, float* d_map,
+                          MatchPartial** parts, int* nparts, TimedEvent& ev)
 {
     const melf_params& P = c->P;
     const int kind = pick_match_kind(c, ms.rows, ms.cols, m);
@@ -1092,7 +1088,7 @@ static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int b
         *parts = c->d_lpart[bl];
         {
             KernelTimer t(c, MELF_K_LPLANE, ls);
-            launch_mfma_prep(ms, pix, m, pl, P.th, P.tw, c->d_lg[bl], c->d_rsum[bl], ls, yuv, planes, mx);
+            launch_mfma_prep(ms, lay, m, pl, P.th, P.tw, c->d_lg[bl], c->d_rsum[bl], ls);
         }
         info.rows_per_wave = pl.rb; info.full_waves = pl.na; info.pair_waves = 2 * pl.np;
         info.waves = pl.nparts * pl.groups; info.tiles = pl.ntiles;
@@ -1110,7 +1106,7 @@ static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int b
         *parts = c->d_lpart[bl];
         {
             KernelTimer t(c, MELF_K_LPLANE, ls);
-            launch_match_prep(ms, pix, m, pl.groups, pl.rows_pad, pl.nkb, pl.rwp, P.tw, c->d_lg[bl], c->d_rsum[bl], ls, 0, yuv, planes, mx);
+            launch_match_prep(ms, lay, m, pl.groups, pl.rows_pad, pl.nkb, pl.rwp, P.tw, c->d_lg[bl], c->d_rsum[bl], ls);
         }
         const GenDev& dev = ge->dev;
         fill_gen_info(&info, pl);
@@ -1120,7 +1116,7 @@ static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int b
         if (int rc = grow(&c->d_lpart[bl], &c->lpart_cap[bl], (size_t)m * *nparts)) return rc;
         *parts = c->d_lpart[bl];
         KernelTimer t(c, MELF_K_MATCH, ls);
-        launch_match(ms, pix, m, c->mg, c->d_tplT, d_map, *parts, nullptr, ls, yuv, planes, mx);
+        launch_match(ms, lay, m, c->mg, c->d_tplT, d_map, *parts, nullptr, ls);
         info.tiles = *nparts;
     }
     if (trace)
@@ -1133,29 +1129,61 @@ static int run_match_impl(melf_ctx* c, const MatchSrc& ms, int pix, int m, int b
 // ------------------------------------------------------------ full path ----
 static const int MAX_FRAMES_PER_LAUNCH = 32768;
 
-// rect (optional): {x0, y0, x1, y1} of the meter crop inside the H x W frames instead of the context's meter_rect
-// (the host-fed path uploads only the crop: its "frames" are the crops themselves); row_stride: bytes between rows
-// (0 = packed); pix: the frames' pixel layout (MELF_PIX_*, or PIX_NV12 / PIX_I420: d_frames, frame_stride and row_stride then describe
-// the Y plane, yuv the chroma planes, yuv_extent = the bytes of a frame up to the last sample of its last plane; or PIX_YUYV /
-// PIX_UYVY / PIX_YVYU: packed 4:2:2 frames of 2 bytes per pixel, W even, everything 4-byte aligned; or PIX_PLANAR: d_frames,
-// frame_stride and row_stride describe a frame and the rows of its planes, planes where they start, yuv_extent as for YUV);
-// mx: the colour conversion of YUV frames, 4:2:0 and 4:2:2 (the descriptor's matrix: yuv_matrix())
-static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
-                            void* d_results, melf_result* out_host, hipStream_t st, const int* rect = nullptr, int row_stride = 0,
-                            int pix = MELF_PIX_BGR, const YuvPlanes* yuv = nullptr, size_t yuv_extent = 0,
-                            const PlanarPlanes* planes = nullptr, const YuvMatrix* mx = nullptr);
-
-// The checks of a melf_frames descriptor (melf_process_frames*); n == 0 passes
-static int check_frames(const void* frames, const melf_frames* f)
+// A batch of frames as an entry point's checks leave it: n frames of H x W pixels, frame_stride bytes apart, their rows (of the
+// packed pixels, of the Y plane, of every plane) row_stride bytes apart, everything else in the layout
+struct FrameBatch {
+    int n, H, W;
+    size_t frame_stride;
+    int row_stride;
+    FrameLayout lay;
+};
+// packed BGR frames with packed rows: melf_process_batch*, melf_process_stream_dev, the decoded JPEG frames
+static FrameBatch bgr_batch(int n, int H, int W, size_t frame_stride)
 {
+    return FrameBatch{n, H, W, frame_stride, W * 3, FrameLayout::packed(MELF_PIX_BGR, (size_t)H * W * 3)};
+}
+
+// The meter crop of H x W frames: r = {x0, y0, x1, y1} (NULL: the context's meter_rect) clamped to the frame as numpy slicing
+// img[y0:y1, x0:x1] clamps (meterelf/_image.py:54-55)
+struct Crop {
+    int x0, y0, x1, y1, rows, cols;
+};
+static int meter_crop(const melf_params& P, const int* r, int H, int W, Crop* cr)
+{
+    const int rx0 = r ? r[0] : P.rect_x0, ry0 = r ? r[1] : P.rect_y0;
+    const int rx1 = r ? r[2] : P.rect_x1, ry1 = r ? r[3] : P.rect_y1;
+    cr->x0 = rx0 < W ? rx0 : W; cr->x1 = rx1 < W ? rx1 : W;
+    cr->y0 = ry0 < H ? ry0 : H; cr->y1 = ry1 < H ? ry1 : H;
+    cr->rows = cr->y1 - cr->y0; cr->cols = cr->x1 - cr->x0;
+    if (cr->x0 < 0 || cr->y0 < 0 || cr->rows < P.th || cr->cols < P.tw)
+        return fail(MELF_ERR_INVALID, "meter_rect crop is smaller than the dials template (cv2.matchTemplate would assert)");
+    return MELF_SUCCESS;
+}
+
+// The reading path over frames in HBM, on stream st with the active lane's work buffers.  rect (optional): {x0, y0, x1, y1} of the
+// meter crop inside the frames instead of the context's meter_rect (the host-fed path uploads only the crop: its "frames" are
+// the staged crops).
+static int process_batch_on(melf_ctx* c, const void* d_frames, const FrameBatch& b, void* d_results, melf_result* out_host,
+                            hipStream_t st, const int* rect = nullptr);
+// the entry points on frames in HBM after their argument checks: the lane logic
+static int batch_dev(melf_ctx* c, const void* d_frames, const FrameBatch& b, void* d_results, melf_result* out_host, void* stream_);
+
+// The four descriptor checks (the C ABI's melf_*_frames): every entry point that takes the descriptor starts with its check, which
+// leaves the batch in *b; n == 0 passes whatever the frames pointer.
+
+// melf_frames (melf_process_frames*)
+static int check_frames(const melf_ctx* c, const void* frames, const melf_frames* f, FrameBatch* b)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
     if (!f) return fail(MELF_ERR_INVALID, "frame descriptor is NULL");
     if (f->pixel_format < MELF_PIX_BGR || f->pixel_format > MELF_PIX_RGBA) return fail(MELF_ERR_INVALID, "unknown pixel_format");
     if (f->n < 0 || f->H <= 0 || f->W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
     const int64_t bpp = pix_bytes(f->pixel_format);
     if (f->row_pitch < (int64_t)f->W * bpp) return fail(MELF_ERR_INVALID, "row_pitch smaller than a row");
     if (f->row_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "row_pitch too large");
-    if (f->frame_stride < (int64_t)(f->H - 1) * f->row_pitch + (int64_t)f->W * bpp)
-        return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
+    const int64_t extent = (int64_t)(f->H - 1) * f->row_pitch + (int64_t)f->W * bpp;   // the last row of a pitched buffer needs no padding
+    if (f->frame_stride < extent) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
+    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch, FrameLayout::packed(f->pixel_format, (size_t)extent)};
     if (f->n == 0) return MELF_SUCCESS;
     if (!frames) return fail(MELF_ERR_INVALID, "frames pointer is NULL");
     if (bpp == 4 && (((uintptr_t)frames | (uint64_t)f->row_pitch | (uint64_t)f->frame_stride) & 3))
@@ -1163,39 +1191,15 @@ static int check_frames(const void* frames, const melf_frames* f)
     return MELF_SUCCESS;
 }
 
-static int batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride, int row_stride, int pix,
-                     void* d_results, melf_result* out_host, void* stream_, const YuvPlanes* yuv = nullptr, size_t yuv_extent = 0,
-                     const PlanarPlanes* planes = nullptr, const YuvMatrix* mx = nullptr);
-
-extern "C" int melf_process_batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
-                                      void* d_results, melf_result* out_host, void* stream_)
+// melf_yuv_frames (melf_process_yuv*, melf_yuv_to_bgr): base, frame_stride and row_stride describe the Y plane; the extent reaches
+// to the last sample of the frame's last plane
+static int check_yuv(const melf_ctx* c, const void* frames, const melf_yuv_frames* f, FrameBatch* b)
 {
     if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    if (n < 0 || H <= 0 || W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
-    if (n == 0) return MELF_SUCCESS;
-    if (!d_frames) return fail(MELF_ERR_INVALID, "d_frames is NULL");
-    if (frame_stride < (size_t)H * W * 3) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
-    return batch_dev(c, d_frames, n, H, W, frame_stride, W * 3, MELF_PIX_BGR, d_results, out_host, stream_);
-}
-
-extern "C" int melf_process_frames_dev(melf_ctx* c, const void* d_frames, const melf_frames* f, void* d_results, melf_result* out_host,
-                                       void* stream_)
-{
-    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    if (int rc = check_frames(d_frames, f)) return rc;
-    if (f->n == 0) return MELF_SUCCESS;
-    return batch_dev(c, d_frames, f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch, f->pixel_format, d_results, out_host,
-                     stream_);
-}
-
-// The checks of a melf_yuv_frames descriptor (melf_process_yuv*, melf_yuv_to_bgr); n == 0 passes.  *pix: PIX_NV12 / PIX_I420,
-// *yp: the chroma planes, *mx: the colour conversion of the descriptor's matrix code,
-// *extent: the bytes of one frame up to the last sample of its last plane.
-static int check_yuv(const void* frames, const melf_yuv_frames* f, int* pix, YuvPlanes* yp, const YuvMatrix** mx, size_t* extent)
-{
     if (!f) return fail(MELF_ERR_INVALID, "YUV frame descriptor is NULL");
     if (f->format != MELF_YUV_NV12 && f->format != MELF_YUV_I420) return fail(MELF_ERR_INVALID, "unknown YUV format");
-    if (!(*mx = yuv_matrix(f->matrix)))
+    const YuvMatrix* mx = yuv_matrix(f->matrix);
+    if (!mx)
         return fail(MELF_ERR_INVALID, "unknown YUV matrix (accepted: 0 BT.601 limited, 2 BT.601 full, 3 BT.709 limited, 4 BT.709 full)");
     if (f->n < 0 || f->H <= 0 || f->W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
     if ((f->H | f->W) & 1) return fail(MELF_ERR_INVALID, "YUV 4:2:0 frames need an even height and width");
@@ -1211,67 +1215,44 @@ static int check_yuv(const void* frames, const melf_yuv_frames* f, int* pix, Yuv
         return fail(MELF_ERR_INVALID, "NV12 needs v_offset == u_offset + 1 and an even u_offset");
     const int64_t c_end = (f->u_offset > f->v_offset ? f->u_offset : f->v_offset) + c_len;
     if (f->frame_stride < c_end) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
-    *pix = nv12 ? PIX_NV12 : PIX_I420;
-    yp->u_off = f->u_offset; yp->v_off = f->v_offset; yp->c_pitch = (int)f->c_pitch; yp->pad = 0;
-    *extent = (size_t)c_end;
+    const YuvPlanes yp = {f->u_offset, f->v_offset, (int)f->c_pitch, 0};
+    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->y_pitch,
+                    FrameLayout::yuv420(nv12 ? PIX_NV12 : PIX_I420, yp, *mx, (size_t)c_end)};
     if (f->n == 0) return MELF_SUCCESS;
     if (!frames) return fail(MELF_ERR_INVALID, "frames pointer is NULL");
     return MELF_SUCCESS;
 }
 
-extern "C" int melf_process_yuv_dev(melf_ctx* c, const void* d_frames, const melf_yuv_frames* f, void* d_results, melf_result* out_host,
-                                    void* stream_)
+// melf_yuv422_frames (melf_process_yuv422*, melf_yuv422_to_bgr)
+static int check_yuv422(const melf_ctx* c, const void* frames, const melf_yuv422_frames* f, FrameBatch* b)
 {
     if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    int pix = 0;
-    YuvPlanes yp;
-    const YuvMatrix* mx = nullptr;
-    size_t extent = 0;
-    if (int rc = check_yuv(d_frames, f, &pix, &yp, &mx, &extent)) return rc;
-    if (f->n == 0) return MELF_SUCCESS;
-    return batch_dev(c, d_frames, f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->y_pitch, pix, d_results, out_host, stream_, &yp, extent, nullptr, mx);
-}
-
-// The checks of a melf_yuv422_frames descriptor (melf_process_yuv422*, melf_yuv422_to_bgr); n == 0 passes.  *pix: PIX_YUYV /
-// PIX_UYVY / PIX_YVYU, *mx: the colour conversion of the descriptor's matrix code.
-static int check_yuv422(const void* frames, const melf_yuv422_frames* f, int* pix, const YuvMatrix** mx)
-{
     if (!f) return fail(MELF_ERR_INVALID, "YUV 4:2:2 frame descriptor is NULL");
     if (f->format != MELF_YUV422_YUYV && f->format != MELF_YUV422_UYVY && f->format != MELF_YUV422_YVYU)
         return fail(MELF_ERR_INVALID, "unknown YUV 4:2:2 format");
-    if (!(*mx = yuv_matrix(f->matrix)))
+    const YuvMatrix* mx = yuv_matrix(f->matrix);
+    if (!mx)
         return fail(MELF_ERR_INVALID, "unknown YUV matrix (accepted: 0 BT.601 limited, 2 BT.601 full, 3 BT.709 limited, 4 BT.709 full)");
     if (f->n < 0 || f->H <= 0 || f->W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
     if (f->W & 1) return fail(MELF_ERR_INVALID, "YUV 4:2:2 frames need an even width");
     if (f->row_pitch < (int64_t)f->W * 2) return fail(MELF_ERR_INVALID, "row_pitch smaller than a row");
     if (f->row_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "row_pitch too large");
-    if (f->frame_stride < (int64_t)(f->H - 1) * f->row_pitch + (int64_t)f->W * 2)
-        return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
+    const int64_t extent = (int64_t)(f->H - 1) * f->row_pitch + (int64_t)f->W * 2;
+    if (f->frame_stride < extent) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
     if (((uint64_t)f->row_pitch | (uint64_t)f->frame_stride) & 3)
         return fail(MELF_ERR_INVALID, "YUV 4:2:2 frames need a 4-byte aligned row_pitch and frame_stride");
-    *pix = f->format == MELF_YUV422_UYVY ? PIX_UYVY : (f->format == MELF_YUV422_YVYU ? PIX_YVYU : PIX_YUYV);
+    const int pix = f->format == MELF_YUV422_UYVY ? PIX_UYVY : (f->format == MELF_YUV422_YVYU ? PIX_YVYU : PIX_YUYV);
+    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch, FrameLayout::yuv422(pix, *mx, (size_t)extent)};
     if (f->n == 0) return MELF_SUCCESS;
     if (!frames) return fail(MELF_ERR_INVALID, "frames pointer is NULL");
     if ((uintptr_t)frames & 3) return fail(MELF_ERR_INVALID, "YUV 4:2:2 frames need a 4-byte aligned base");
     return MELF_SUCCESS;
 }
 
-extern "C" int melf_process_yuv422_dev(melf_ctx* c, const void* d_frames, const melf_yuv422_frames* f, void* d_results,
-                                       melf_result* out_host, void* stream_)
+// melf_planar_frames (melf_process_planes*): the extent reaches to the last sample of the frame's last plane
+static int check_planes(const melf_ctx* c, const void* frames, const melf_planar_frames* f, FrameBatch* b)
 {
     if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    int pix = 0;
-    const YuvMatrix* mx = nullptr;
-    if (int rc = check_yuv422(d_frames, f, &pix, &mx)) return rc;
-    if (f->n == 0) return MELF_SUCCESS;
-    return batch_dev(c, d_frames, f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch, pix, d_results, out_host, stream_, nullptr, 0,
-                     nullptr, mx);
-}
-
-// The checks of a melf_planar_frames descriptor (melf_process_planes*); n == 0 passes.  *pl: the planes, *extent: the bytes of one
-// frame up to the last sample of its last plane.
-static int check_planes(const void* frames, const melf_planar_frames* f, PlanarPlanes* pl, size_t* extent)
-{
     if (!f) return fail(MELF_ERR_INVALID, "planar frame descriptor is NULL");
     if (f->n < 0 || f->H <= 0 || f->W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
     if (f->reserved != 0) return fail(MELF_ERR_INVALID, "reserved field of the planar frame descriptor is not 0");
@@ -1284,40 +1265,71 @@ static int check_planes(const void* frames, const melf_planar_frames* f, PlanarP
     for (int a = 0; a < 3; ++a) {
         if (off[a] > INT64_MAX - span) return fail(MELF_ERR_INVALID, "plane offset too large");
         if (off[a] > hi) hi = off[a];
-        for (int b = a + 1; b < 3; ++b) {
-            const int64_t lo2 = off[a] < off[b] ? off[a] : off[b], hi2 = off[a] < off[b] ? off[b] : off[a];
+        for (int k = a + 1; k < 3; ++k) {
+            const int64_t lo2 = off[a] < off[k] ? off[a] : off[k], hi2 = off[a] < off[k] ? off[k] : off[a];
             if (hi2 - lo2 < span) return fail(MELF_ERR_INVALID, "two planes overlap");
         }
     }
     if (f->frame_stride < hi + span) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
-    pl->b_off = f->b_offset; pl->g_off = f->g_offset; pl->r_off = f->r_offset;
-    *extent = (size_t)(hi + span);
+    const PlanarPlanes pl = {f->b_offset, f->g_offset, f->r_offset};
+    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch, FrameLayout::planar(pl, (size_t)(hi + span))};
     if (f->n == 0) return MELF_SUCCESS;
     if (!frames) return fail(MELF_ERR_INVALID, "frames pointer is NULL");
     return MELF_SUCCESS;
 }
 
+extern "C" int melf_process_batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
+                                      void* d_results, melf_result* out_host, void* stream_)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    if (n < 0 || H <= 0 || W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
+    if (n == 0) return MELF_SUCCESS;
+    if (!d_frames) return fail(MELF_ERR_INVALID, "d_frames is NULL");
+    if (frame_stride < (size_t)H * W * 3) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
+    return batch_dev(c, d_frames, bgr_batch(n, H, W, frame_stride), d_results, out_host, stream_);
+}
+
+extern "C" int melf_process_frames_dev(melf_ctx* c, const void* d_frames, const melf_frames* f, void* d_results, melf_result* out_host,
+                                       void* stream_)
+{
+    FrameBatch b;
+    if (int rc = check_frames(c, d_frames, f, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return batch_dev(c, d_frames, b, d_results, out_host, stream_);
+}
+
+extern "C" int melf_process_yuv_dev(melf_ctx* c, const void* d_frames, const melf_yuv_frames* f, void* d_results, melf_result* out_host,
+                                    void* stream_)
+{
+    FrameBatch b;
+    if (int rc = check_yuv(c, d_frames, f, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return batch_dev(c, d_frames, b, d_results, out_host, stream_);
+}
+
+extern "C" int melf_process_yuv422_dev(melf_ctx* c, const void* d_frames, const melf_yuv422_frames* f, void* d_results,
+                                       melf_result* out_host, void* stream_)
+{
+    FrameBatch b;
+    if (int rc = check_yuv422(c, d_frames, f, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return batch_dev(c, d_frames, b, d_results, out_host, stream_);
+}
+
 extern "C" int melf_process_planes_dev(melf_ctx* c, const void* d_frames, const melf_planar_frames* f, void* d_results,
                                        melf_result* out_host, void* stream_)
 {
-    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    PlanarPlanes pl;
-    size_t extent = 0;
-    if (int rc = check_planes(d_frames, f, &pl, &extent)) return rc;
-    if (f->n == 0) return MELF_SUCCESS;
-    return batch_dev(c, d_frames, f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch, PIX_PLANAR, d_results, out_host, stream_,
-                     nullptr, extent, &pl);
+    FrameBatch b;
+    if (int rc = check_planes(c, d_frames, f, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return batch_dev(c, d_frames, b, d_results, out_host, stream_);
 }
 
-// melf_process_batch_dev / melf_process_frames_dev / melf_process_yuv_dev / melf_process_yuv422_dev / melf_process_planes_dev after
-// their argument checks: the lane logic
-static int batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride, int row_stride, int pix,
-                     void* d_results, melf_result* out_host, void* stream_, const YuvPlanes* yuv, size_t yuv_extent,
-                     const PlanarPlanes* planes, const YuvMatrix* mx)
+static int batch_dev(melf_ctx* c, const void* d_frames, const FrameBatch& b, void* d_results, melf_result* out_host, void* stream_)
 {
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream_;  // NULL = the null (legacy default) stream, as everywhere in HIP
-    if (c->frames_resident && n <= MAX_FRAMES_PER_LAUNCH) {
+    if (c->frames_resident && b.n <= MAX_FRAMES_PER_LAUNCH) {
         // frames promised complete: the call runs on the next lane's own stream, beside the previous call's kernels on the
         // other lane; only its dials kernel (which writes the records) waits for the caller's stream (process_batch_on)
         const int lane = c->resident_next_lane;
@@ -1327,41 +1339,33 @@ static int batch_dev(melf_ctx* c, const void* d_frames, int n, int H, int W, siz
         c->active_lane = lane;
         c->order_stream = st;
         c->order_valid = true;
-        const int rc = process_batch_on(c, d_frames, n, H, W, frame_stride, d_results, nullptr, ls, nullptr, row_stride, pix, yuv, yuv_extent, planes, mx);
+        const int rc = process_batch_on(c, d_frames, b, d_results, nullptr, ls);
         c->order_valid = false;
         if (rc) return rc;
         HIP_TRY(hipEventRecord(c->ev_join[lane], ls));
         HIP_TRY(hipStreamWaitEvent(st, c->ev_join[lane], 0));   // what the caller enqueues next sees the records
         if (out_host) {
             const melf_result* res_dev = d_results ? (const melf_result*)d_results : c->d_results;
-            HIP_TRY(hipMemcpyAsync(out_host, res_dev, (size_t)n * sizeof(melf_result), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(out_host, res_dev, (size_t)b.n * sizeof(melf_result), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
         }
         return MELF_SUCCESS;
     }
     if (int rc = acquire_lane(c, st, &c->active_lane)) return rc;
-    return process_batch_on(c, d_frames, n, H, W, frame_stride, d_results, out_host, st, nullptr, row_stride, pix, yuv, yuv_extent, planes, mx);
+    return process_batch_on(c, d_frames, b, d_results, out_host, st);
 }
 
-static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
-                            void* d_results, melf_result* out_host, hipStream_t st, const int* rect, int row_stride, int pix,
-                            const YuvPlanes* yuv, size_t yuv_extent, const PlanarPlanes* planes, const YuvMatrix* mx)
+static int process_batch_on(melf_ctx* c, const void* d_frames, const FrameBatch& b, void* d_results, melf_result* out_host,
+                            hipStream_t st, const int* rect)
 {
-    const int bpp = yuv || planes ? 1 : (pix_p422(pix) ? 2 : pix_bytes(pix));
-    if (row_stride <= 0) row_stride = W * bpp;  // packed rows unless the caller's rows are padded (host-fed crops, pitched frames)
-    // what the kernels may read of the last frame: its rows as far as they reach (the last row of a pitched buffer needs no
-    // padding); the host-fed crops keep their staging pitch and spare bytes behind every crop
-    const size_t last_frame = yuv || planes ? yuv_extent : (rect ? (size_t)H * row_stride : (size_t)(H - 1) * row_stride + (size_t)W * bpp);
     const melf_params& P = c->P;
-    // numpy slicing img[y0:y1, x0:x1] clamps to the image (meterelf/_image.py:54-55)
-    const int rx0 = rect ? rect[0] : P.rect_x0, ry0 = rect ? rect[1] : P.rect_y0;
-    const int rx1 = rect ? rect[2] : P.rect_x1, ry1 = rect ? rect[3] : P.rect_y1;
-    const int x0 = rx0 < W ? rx0 : W, x1 = rx1 < W ? rx1 : W;
-    const int y0 = ry0 < H ? ry0 : H, y1 = ry1 < H ? ry1 : H;
-    const int crows = y1 - y0, ccols = x1 - x0;
-    if (x0 < 0 || y0 < 0 || crows < P.th || ccols < P.tw)
-        return fail(MELF_ERR_INVALID, "meter_rect crop is smaller than the dials template (cv2.matchTemplate would assert)");
-    const int rw = ccols - P.tw + 1;
+    const FrameLayout& lay = b.lay;
+    const int n = b.n;
+    const size_t frame_stride = b.frame_stride;
+    const int row_stride = b.row_stride;
+    Crop cr;
+    if (int rc = meter_crop(P, rect, b.H, b.W, &cr)) return rc;
+    const int rw = cr.cols - P.tw + 1;
     melf_result* res_dev = (melf_result*)d_results;
     if (!res_dev) {
         if (int rc = grow(&c->d_results, &c->results_cap, (size_t)n)) return rc;
@@ -1374,15 +1378,15 @@ static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int
         const uint8_t* base = (const uint8_t*)d_frames + (size_t)f0 * frame_stride;
         MatchSrc ms;
         ms.base = base; ms.frame_stride = frame_stride; ms.row_stride = row_stride;
-        ms.x0 = x0; ms.y0 = y0; ms.rows = crows; ms.cols = ccols;
-        ms.readable = (size_t)(m - 1) * frame_stride + last_frame;
+        ms.x0 = cr.x0; ms.y0 = cr.y0; ms.rows = cr.rows; ms.cols = cr.cols;
+        ms.readable = (size_t)(m - 1) * frame_stride + lay.extent;
         int nparts = 0;
         MatchPartial* parts = nullptr;
-        if (int rc = run_match(c, ms, pix, m, bl, st, nullptr, &parts, &nparts, yuv, planes, mx)) return rc;
+        if (int rc = run_match(c, ms, lay, m, bl, st, nullptr, &parts, &nparts)) return rc;
         DialsSrc ds;
         ds.base = base; ds.frame_stride = frame_stride; ds.row_stride = row_stride;
-        ds.x0 = x0; ds.y0 = y0; ds.crop_rows = crows; ds.crop_cols = ccols;
-        ds.readable = (size_t)(m - 1) * frame_stride + last_frame;
+        ds.x0 = cr.x0; ds.y0 = cr.y0; ds.crop_rows = cr.rows; ds.crop_cols = cr.cols;
+        ds.readable = ms.readable;
         if (c->order_valid) {
             // resident mode: prep and match above ran unordered with the caller's stream (they touch only the frames
             // and the lane's buffers); the kernel that writes the caller's records waits for everything that stream
@@ -1393,7 +1397,7 @@ static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int
         }
         {
             KernelTimer t(c, MELF_K_DIALS, st);
-            launch_dials(ds, pix, m, P, c->d_geom, c->d_rowmasks, parts, nparts, rw, res_dev + f0, st, c->ws_max, yuv, planes, mx);
+            launch_dials(ds, lay, m, P, c->d_geom, c->d_rowmasks, parts, nparts, rw, res_dev + f0, st, c->ws_max);
         }
         HIP_TRY(hipGetLastError());
     }
@@ -1421,7 +1425,7 @@ extern "C" int melf_process_stream_dev(melf_ctx* c, const void* d_frames, int nb
     if (nbatches == 1 || n > MAX_FRAMES_PER_LAUNCH)  // nothing to overlap / too large for one set of lane buffers
     {
         for (int b = 0; b < nbatches; ++b)
-            if (int rc = process_batch_on(c, (const uint8_t*)d_frames + (size_t)b * batch_stride, n, H, W, frame_stride,
+            if (int rc = process_batch_on(c, (const uint8_t*)d_frames + (size_t)b * batch_stride, bgr_batch(n, H, W, frame_stride),
                                           (melf_result*)d_results + (size_t)b * results_stride, nullptr, st))
                 return rc;
         return MELF_SUCCESS;
@@ -1432,7 +1436,7 @@ extern "C" int melf_process_stream_dev(melf_ctx* c, const void* d_frames, int nb
     int rc = MELF_SUCCESS;
     for (int b = 0; b < nbatches && rc == MELF_SUCCESS; ++b) {
         c->active_lane = b % melf_ctx::NLANES;
-        rc = process_batch_on(c, (const uint8_t*)d_frames + (size_t)b * batch_stride, n, H, W, frame_stride,
+        rc = process_batch_on(c, (const uint8_t*)d_frames + (size_t)b * batch_stride, bgr_batch(n, H, W, frame_stride),
                               (melf_result*)d_results + (size_t)b * results_stride, nullptr, c->lane_stream[c->active_lane]);
     }
     c->active_lane = saved;
@@ -1447,50 +1451,32 @@ extern "C" int melf_process_stream_dev(melf_ctx* c, const void* d_frames, int nb
 // reads the meter_rect crop, so only the crop crosses PCIe -- 187 500 of a 640x480 frame's 921 600 bytes.  Chunks of
 // frames are packed (on the host pool's threads) into one of two pinned staging buffers, copied by DMA on a copy
 // stream and processed on the context's stream, so that packing chunk k+1, the copy of chunk k and the kernels of
-// chunk k-1 overlap.  The kernels see the crops as frames of crop size with the rect at the origin.
-// The pixel layouts of melf_process_frames go the same way: the crop rows are packed as they are (ccols * bytes per pixel, read at
-// the caller's row pitch), the kernels read the layout.
-static int batch_host(melf_ctx* c, const uint8_t* frames_host, int n, int H, int W, size_t frame_stride, size_t row_pitch, int pix,
-                      melf_result* out_host);
+// chunk k-1 overlap.  The kernels see the staged frames as frames of their own, with the rect where the plan says.
+// Every format goes this way (stage_host_frames); a format brings its plan and its packer: what a staged frame looks like, and
+// the rows of the caller's frame that go into it -- copied as they are, no byte is converted or reordered on the CPU.
+struct StagePlan {
+    FrameBatch staged;   // the staged frames as the kernels read them (n: set per chunk); frame_stride: bytes of a staged frame,
+                         // rows at a 64-byte pitch, + 128 spare bytes (the prep kernel's aligned windows reach past the last sample)
+    int rect[4];         // the meter crop inside a staged frame
+    int items;           // the packer's work items per frame
+};
 
-extern "C" int melf_process_batch(melf_ctx* c, const uint8_t* frames_host, int n, int H, int W, size_t frame_stride,
-                                  melf_result* out_host)
+// What every host entry point needs after its descriptor's checks: somewhere for the records, and a meter crop the template fits
+static int host_crop(const melf_ctx* c, const FrameBatch& b, const melf_result* out_host, Crop* cr)
 {
-    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    if (n == 0) return MELF_SUCCESS;
-    if (!frames_host || !out_host || n < 0 || H <= 0 || W <= 0) return fail(MELF_ERR_INVALID, "bad argument");
-    if (frame_stride < (size_t)H * W * 3) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
-    return batch_host(c, frames_host, n, H, W, frame_stride, (size_t)W * 3, MELF_PIX_BGR, out_host);
-}
-
-extern "C" int melf_process_frames(melf_ctx* c, const void* frames_host, const melf_frames* f, melf_result* out_host)
-{
-    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    if (int rc = check_frames(frames_host, f)) return rc;
-    if (f->n == 0) return MELF_SUCCESS;
     if (!out_host) return fail(MELF_ERR_INVALID, "out_host is NULL");
-    return batch_host(c, (const uint8_t*)frames_host, f->n, f->H, f->W, (size_t)f->frame_stride, (size_t)f->row_pitch, f->pixel_format,
-                      out_host);
+    return meter_crop(c->P, nullptr, b.H, b.W, cr);
 }
 
-static int batch_host(melf_ctx* c, const uint8_t* frames_host, int n, int H, int W, size_t frame_stride, size_t row_pitch, int pix,
-                      melf_result* out_host)
+// pack(frame, staged, item): writes work item `item` (0 .. sp.items - 1) of the caller's frame at `frame` into its staged frame
+// at `staged`; runs on the host pool's threads.  A template parameter, so that the packer is inlined into the pool's work item.
+template <class Pack>
+static int stage_host_frames(melf_ctx* c, const uint8_t* frames_host, int n, size_t frame_stride, const StagePlan& sp,
+                             melf_result* out_host, const Pack& pack)
 {
-    const int bpp = pix_bytes(pix);
     HIP_TRY(hipSetDevice(c->device));
     pool_use_device(c->device);
-    const melf_params& P = c->P;
-    const int x0 = P.rect_x0 < W ? P.rect_x0 : W, x1 = P.rect_x1 < W ? P.rect_x1 : W;
-    const int y0 = P.rect_y0 < H ? P.rect_y0 : H, y1 = P.rect_y1 < H ? P.rect_y1 : H;
-    const int crows = y1 - y0, ccols = x1 - x0;
-    if (x0 < 0 || y0 < 0 || crows < P.th || ccols < P.tw)
-        return fail(MELF_ERR_INVALID, "meter_rect crop is smaller than the dials template (cv2.matchTemplate would assert)");
-    const size_t row_bytes = (size_t)ccols * bpp;
-    // crop rows at a 64-byte pitch, so that the host side can pack them with streaming (non-temporal) 16-byte stores:
-    // a plain memcpy into the staging buffer reads every destination line before writing it, a third of the pack's
-    // memory traffic; + 128 spare bytes per crop (the prep kernel's aligned 100-byte windows reach past the last pixel)
-    const size_t pitch = (row_bytes + 63) & ~(size_t)63;
-    const size_t crop_stride = (size_t)crows * pitch + 128;
+    const size_t crop_stride = sp.staged.frame_stride;
     const int chunk = 128;  // frames per pipeline stage (a multiple of the 32-frame MFMA group)
     const size_t pin_need = (size_t)(n < chunk ? n : chunk) * crop_stride;
     if (!c->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
@@ -1511,8 +1497,7 @@ static int batch_host(melf_ctx* c, const uint8_t* frames_host, int n, int H, int
     static const bool trace = diag_env("MELF_HOSTFED_TRACE") != nullptr;
     double pack_ms = 0;
     const auto t_begin = std::chrono::steady_clock::now();
-    const int rect[4] = {0, 0, ccols, crows};
-    const uint8_t* frames_end = frames_host + (size_t)(n - 1) * frame_stride + (size_t)(H - 1) * row_pitch + (size_t)W * bpp;
+    FrameBatch staged = sp.staged;
     int k = 0;
     for (int f0 = 0; f0 < n; f0 += chunk, ++k) {
         const int m = n - f0 < chunk ? n - f0 : chunk;
@@ -1520,338 +1505,218 @@ static int batch_host(melf_ctx* c, const uint8_t* frames_host, int n, int H, int
         if (k >= 2) HIP_TRY(hipEventSynchronize(c->ev_h2d[b]));  // the copy that last read this staging buffer is done
         uint8_t* pin = c->h_pin[b];
         const auto tp0 = std::chrono::steady_clock::now();
-        // work items of 32 crop rows: a chunk of 128 frames gives a 16-thread pool ~1000 items
-        const int rblocks = (crows + 31) / 32;
-        host_pool().run(m * rblocks, [&](int item) {
-            const int i = item / rblocks, r0 = (item - i * rblocks) * 32, r1 = r0 + 32 < crows ? r0 + 32 : crows;
-            const uint8_t* src = frames_host + (size_t)(f0 + i) * frame_stride + (size_t)(y0 + r0) * row_pitch + (size_t)x0 * bpp;
-            uint8_t* dst = pin + (size_t)i * crop_stride + (size_t)r0 * pitch;
-            for (int y = r0; y < r1; ++y, src += row_pitch, dst += pitch) {
-                if (src + pitch <= frames_end) {  // whole 64-byte pitch from the source row (the tail bytes are never looked at)
-                    for (size_t o = 0; o < pitch; o += 16)
-                        _mm_stream_si128((__m128i*)(dst + o), _mm_loadu_si128((const __m128i*)(src + o)));
-                } else {
-                    memcpy(dst, src, row_bytes);
-                }
-            }
-            _mm_sfence();
+        const int items = sp.items;   // of 32 rows or so: a chunk of 128 frames gives a 16-thread pool ~1000 of them
+        host_pool().run(m * items, [&](int item) {
+            const int i = item / items;
+            pack(frames_host + (size_t)(f0 + i) * frame_stride, pin + (size_t)i * crop_stride, item - i * items);
         });
         pack_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count();
         uint8_t* d_chunk = c->d_crops + (size_t)f0 * crop_stride;
         HIP_TRY(hipMemcpyAsync(d_chunk, pin, (size_t)m * crop_stride, hipMemcpyHostToDevice, c->copy_stream));
         HIP_TRY(hipEventRecord(c->ev_h2d[b], c->copy_stream));
         HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_h2d[b], 0));
-        if (int rc = process_batch_on(c, d_chunk, m, crows, ccols, crop_stride, c->d_results + f0, nullptr, c->stream, rect, (int)pitch, pix))
-            return rc;
+        staged.n = m;
+        if (int rc = process_batch_on(c, d_chunk, staged, c->d_results + f0, nullptr, c->stream, sp.rect)) return rc;
     }
     HIP_TRY(hipMemcpyAsync(out_host, c->d_results, (size_t)n * sizeof(melf_result), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (trace)
-        fprintf(stderr, "[melf host-fed] n=%d crop %dx%d: %.2f ms in all, %.2f ms of it packing (%d pool threads), %.1f MB over PCIe\n", n, ccols,
-                crows, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(), pack_ms,
+        fprintf(stderr, "[melf host-fed] n=%d crop %dx%d: %.2f ms in all, %.2f ms of it packing (%d pool threads), %.1f MB over PCIe\n", n,
+                sp.rect[2] - sp.rect[0], sp.rect[3] - sp.rect[1],
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(), pack_ms,
                 host_pool().size() + 1, (double)n * crop_stride / 1e6);
     return MELF_SUCCESS;
 }
 
-// YUV 4:2:0 host frames: the same pipeline.  What crosses PCIe per frame is a small frame of the same format: the Y rows of the
-// crop with its origin rounded down (and its far corner up) to even, and the chroma rows under them, each plane at a 64-byte
-// pitch in the staging buffer; the kernels read it with the rectangle shifted by the rounding (0 or 1 pixel each way).  Rows are
-// copied as they are: no byte is converted on the CPU, and the small frames keep the caller's matrix (mx).
-static int batch_host_yuv(melf_ctx* c, const uint8_t* frames_host, const melf_yuv_frames* f, int pix, const YuvPlanes& yp,
-                          const YuvMatrix* mx, melf_result* out_host)
+static size_t pitch64(size_t row_bytes) { return (row_bytes + 63) & ~(size_t)63; }
+
+// The pixel layouts of melf_process_batch / melf_process_frames: the staged frame is the crop, its rows (cols * bytes per pixel, read
+// at the caller's row pitch) packed as they are
+static int host_packed(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host)
 {
-    const int n = f->n, H = f->H, W = f->W;
-    const bool nv12 = pix == PIX_NV12;
-    HIP_TRY(hipSetDevice(c->device));
-    pool_use_device(c->device);
-    const melf_params& P = c->P;
-    const int x0 = P.rect_x0 < W ? P.rect_x0 : W, x1 = P.rect_x1 < W ? P.rect_x1 : W;
-    const int y0 = P.rect_y0 < H ? P.rect_y0 : H, y1 = P.rect_y1 < H ? P.rect_y1 : H;
-    const int crows = y1 - y0, ccols = x1 - x0;
-    if (x0 < 0 || y0 < 0 || crows < P.th || ccols < P.tw)
-        return fail(MELF_ERR_INVALID, "meter_rect crop is smaller than the dials template (cv2.matchTemplate would assert)");
-    const int ex0 = x0 & ~1, ey0 = y0 & ~1;
-    const int sw = ((x1 + 1) & ~1) - ex0, sh = ((y1 + 1) & ~1) - ey0;   // the small frame (even, inside the frame: H and W are even)
-    const size_t ypitch = ((size_t)sw + 63) & ~(size_t)63;
-    const size_t cbytes = nv12 ? (size_t)sw : (size_t)sw / 2;            // bytes of a chroma row
-    const size_t cpitch = (cbytes + 63) & ~(size_t)63;
-    YuvPlanes sp;
-    sp.u_off = (int64_t)((size_t)sh * ypitch);
-    sp.v_off = nv12 ? sp.u_off + 1 : sp.u_off + (int64_t)((size_t)(sh / 2) * cpitch);
-    sp.c_pitch = (int)cpitch; sp.pad = 0;
-    // + 128 spare bytes per small frame (the prep kernel's aligned windows reach past the last sample)
-    const size_t crop_stride = (size_t)sh * ypitch + (size_t)(sh / 2) * cpitch * (nv12 ? 1 : 2) + 128;
-    const int chunk = 128;  // frames per pipeline stage (a multiple of the 32-frame MFMA group)
-    const size_t pin_need = (size_t)(n < chunk ? n : chunk) * crop_stride;
-    if (!c->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    for (int b = 0; b < 2; ++b) {
-        if (!c->ev_h2d[b]) HIP_TRY(hipEventCreateWithFlags(&c->ev_h2d[b], hipEventDisableTiming));
-        if (c->pin_cap[b] < pin_need && (b == 0 || n > chunk)) {
-            if (c->h_pin[b]) { HIP_TRY(hipStreamSynchronize(c->copy_stream)); HIP_TRY(hipHostFree(c->h_pin[b])); }
-            c->h_pin[b] = nullptr;
-            c->pin_cap[b] = 0;
-            HIP_TRY(hipHostMalloc((void**)&c->h_pin[b], pin_need, hipHostMallocDefault));
-            c->pin_cap[b] = pin_need;
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));  // the previous call's kernels may still read d_crops
-    if (int rc = grow(&c->d_crops, &c->crops_cap, (size_t)n * crop_stride)) return rc;
-    if (int rc = grow(&c->d_results, &c->results_cap, (size_t)n)) return rc;
-    if (int rc = acquire_lane(c, c->stream, &c->active_lane)) return rc;
-    const int rect[4] = {x0 - ex0, y0 - ey0, x0 - ex0 + ccols, y0 - ey0 + crows};
-    int k = 0;
-    for (int f0 = 0; f0 < n; f0 += chunk, ++k) {
-        const int m = n - f0 < chunk ? n - f0 : chunk;
-        const int b = k & 1;
-        if (k >= 2) HIP_TRY(hipEventSynchronize(c->ev_h2d[b]));  // the copy that last read this staging buffer is done
-        uint8_t* pin = c->h_pin[b];
-        // work items: the Y rows of a frame in blocks of 32, and its chroma rows as one more
-        const int rblocks = (sh + 31) / 32;
-        host_pool().run(m * (rblocks + 1), [&](int item) {
-            const int i = item / (rblocks + 1), part = item - i * (rblocks + 1);
-            const uint8_t* frame = frames_host + (size_t)(f0 + i) * (size_t)f->frame_stride;
-            uint8_t* small = pin + (size_t)i * crop_stride;
-            if (part < rblocks) {
-                const int r0 = part * 32, r1 = r0 + 32 < sh ? r0 + 32 : sh;
-                for (int y = r0; y < r1; ++y)
-                    memcpy(small + (size_t)y * ypitch, frame + (size_t)(ey0 + y) * (size_t)f->y_pitch + ex0, (size_t)sw);
+    Crop cr;
+    if (int rc = host_crop(c, b, out_host, &cr)) return rc;
+    const int pix = b.lay.pix, bpp = pix_bytes(pix), crows = cr.rows;
+    const size_t row_pitch = (size_t)b.row_stride, row_bytes = (size_t)cr.cols * bpp, x_off = (size_t)cr.x0 * bpp;
+    // crop rows at a 64-byte pitch, so that the host side can pack them with streaming (non-temporal) 16-byte stores:
+    // a plain memcpy into the staging buffer reads every destination line before writing it, a third of the pack's
+    // memory traffic
+    const size_t pitch = pitch64(row_bytes);
+    const StagePlan sp = {{0, crows, cr.cols, crows * pitch + 128, (int)pitch, FrameLayout::packed(pix, crows * pitch)},
+                          {0, 0, cr.cols, crows}, (crows + 31) / 32};
+    const uint8_t* frames_end = frames_host + (size_t)(b.n - 1) * b.frame_stride + b.lay.extent;
+    const int y0 = cr.y0;
+    return stage_host_frames(c, frames_host, b.n, b.frame_stride, sp, out_host, [=](const uint8_t* frame, uint8_t* staged, int part) {
+        const int r0 = part * 32, r1 = r0 + 32 < crows ? r0 + 32 : crows;
+        const uint8_t* src = frame + (size_t)(y0 + r0) * row_pitch + x_off;
+        uint8_t* dst = staged + (size_t)r0 * pitch;
+        for (int y = r0; y < r1; ++y, src += row_pitch, dst += pitch) {
+            if (src + pitch <= frames_end) {  // whole 64-byte pitch from the source row (the tail bytes are never looked at)
+                for (size_t o = 0; o < pitch; o += 16)
+                    _mm_stream_si128((__m128i*)(dst + o), _mm_loadu_si128((const __m128i*)(src + o)));
             } else {
-                const size_t cx = nv12 ? (size_t)ex0 : (size_t)ex0 / 2;
-                for (int y = 0; y < sh / 2; ++y) {
-                    const size_t so = (size_t)(ey0 / 2 + y) * (size_t)f->c_pitch + cx;
-                    memcpy(small + (size_t)sp.u_off + (size_t)y * cpitch, frame + (size_t)f->u_offset + so, cbytes);
-                    if (!nv12) memcpy(small + (size_t)sp.v_off + (size_t)y * cpitch, frame + (size_t)f->v_offset + so, cbytes);
-                }
+                memcpy(dst, src, row_bytes);
             }
-        });
-        uint8_t* d_chunk = c->d_crops + (size_t)f0 * crop_stride;
-        HIP_TRY(hipMemcpyAsync(d_chunk, pin, (size_t)m * crop_stride, hipMemcpyHostToDevice, c->copy_stream));
-        HIP_TRY(hipEventRecord(c->ev_h2d[b], c->copy_stream));
-        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_h2d[b], 0));
-        if (int rc = process_batch_on(c, d_chunk, m, sh, sw, crop_stride, c->d_results + f0, nullptr, c->stream, rect, (int)ypitch, pix, &sp,
-                                      crop_stride, nullptr, mx))
-            return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(out_host, c->d_results, (size_t)n * sizeof(melf_result), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    (void)yp;
-    return MELF_SUCCESS;
+        }
+        _mm_sfence();
+    });
+}
+
+// YUV 4:2:0: the staged frame is a small frame of the same format, the Y rows of the crop with its origin rounded down (and its
+// far corner up) to even and the chroma rows under them; the kernels read it with the rectangle shifted by the rounding (0 or 1
+// pixel each way), under the caller's matrix.  Work items: the Y rows in blocks of 32, and the chroma rows as one more.
+static int host_yuv(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host)
+{
+    Crop cr;
+    if (int rc = host_crop(c, b, out_host, &cr)) return rc;
+    const bool nv12 = b.lay.pix == PIX_NV12;
+    const YuvPlanes src_planes = b.lay.yuv;
+    const size_t y_pitch = (size_t)b.row_stride;
+    const int ex0 = cr.x0 & ~1, ey0 = cr.y0 & ~1;
+    const int sw = ((cr.x1 + 1) & ~1) - ex0, sh = ((cr.y1 + 1) & ~1) - ey0;   // the small frame (even, inside the frame: H and W are even)
+    const size_t ypitch = pitch64((size_t)sw);
+    const size_t cbytes = nv12 ? (size_t)sw : (size_t)sw / 2;            // bytes of a chroma row
+    const size_t cpitch = pitch64(cbytes);
+    YuvPlanes sy;
+    sy.u_off = (int64_t)((size_t)sh * ypitch);
+    sy.v_off = nv12 ? sy.u_off + 1 : sy.u_off + (int64_t)((size_t)(sh / 2) * cpitch);
+    sy.c_pitch = (int)cpitch; sy.pad = 0;
+    const size_t crop_stride = (size_t)sh * ypitch + (size_t)(sh / 2) * cpitch * (nv12 ? 1 : 2) + 128;
+    const int rblocks = (sh + 31) / 32;
+    const StagePlan sp = {{0, sh, sw, crop_stride, (int)ypitch, FrameLayout::yuv420(b.lay.pix, sy, *b.lay.mx, crop_stride)},
+                          {cr.x0 - ex0, cr.y0 - ey0, cr.x0 - ex0 + cr.cols, cr.y0 - ey0 + cr.rows}, rblocks + 1};
+    return stage_host_frames(c, frames_host, b.n, b.frame_stride, sp, out_host, [=](const uint8_t* frame, uint8_t* small, int part) {
+        if (part < rblocks) {
+            const int r0 = part * 32, r1 = r0 + 32 < sh ? r0 + 32 : sh;
+            for (int y = r0; y < r1; ++y) memcpy(small + (size_t)y * ypitch, frame + (size_t)(ey0 + y) * y_pitch + ex0, (size_t)sw);
+        } else {
+            const size_t cx = nv12 ? (size_t)ex0 : (size_t)ex0 / 2;
+            for (int y = 0; y < sh / 2; ++y) {
+                const size_t so = (size_t)(ey0 / 2 + y) * (size_t)src_planes.c_pitch + cx;
+                memcpy(small + (size_t)sy.u_off + (size_t)y * cpitch, frame + (size_t)src_planes.u_off + so, cbytes);
+                if (!nv12) memcpy(small + (size_t)sy.v_off + (size_t)y * cpitch, frame + (size_t)src_planes.v_off + so, cbytes);
+            }
+        }
+    });
+}
+
+// Packed YUV 4:2:2: the staged frame is a small frame of the same format, the rows of the crop (no vertical rounding: every row
+// has its own chroma), its x origin rounded down and its far corner up to even, i.e. to whole macropixels; the kernels read it
+// with the rectangle shifted by the rounding (0 or 1 pixel), under the caller's matrix.  Work items: the rows in blocks of 32.
+static int host_p422(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host)
+{
+    Crop cr;
+    if (int rc = host_crop(c, b, out_host, &cr)) return rc;
+    const int crows = cr.rows, y0 = cr.y0, ex0 = cr.x0 & ~1;
+    const int sw = ((cr.x1 + 1) & ~1) - ex0;   // the small frame's width (even, inside the frame: W is even)
+    const size_t row_pitch = (size_t)b.row_stride, rbytes = (size_t)sw * 2;
+    const size_t pitch = pitch64(rbytes);
+    const StagePlan sp = {{0, crows, sw, crows * pitch + 128, (int)pitch, FrameLayout::yuv422(b.lay.pix, *b.lay.mx, crows * pitch)},
+                          {cr.x0 - ex0, 0, cr.x0 - ex0 + cr.cols, crows}, (crows + 31) / 32};
+    return stage_host_frames(c, frames_host, b.n, b.frame_stride, sp, out_host, [=](const uint8_t* frame, uint8_t* small, int part) {
+        const int r0 = part * 32, r1 = r0 + 32 < crows ? r0 + 32 : crows;
+        for (int y = r0; y < r1; ++y) memcpy(small + (size_t)y * pitch, frame + (size_t)(y0 + y) * row_pitch + (size_t)ex0 * 2, rbytes);
+    });
+}
+
+// Planar: the staged frame is a small planar frame, the crop's rows of the B, the G and the R plane, one plane after the other,
+// which the kernels read with the rectangle at its origin.  Work items: the crop's rows of one plane in blocks of 32.
+static int host_planes(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host)
+{
+    Crop cr;
+    if (int rc = host_crop(c, b, out_host, &cr)) return rc;
+    const int crows = cr.rows, ccols = cr.cols, x0 = cr.x0, y0 = cr.y0;
+    const size_t row_pitch = (size_t)b.row_stride, pitch = pitch64((size_t)ccols), plane = (size_t)crows * pitch;
+    const size_t crop_stride = 3 * plane + 128;
+    const PlanarPlanes in_frame = {0, (int64_t)plane, (int64_t)(2 * plane)};
+    const int rblocks = (crows + 31) / 32;
+    const StagePlan sp = {{0, crows, ccols, crop_stride, (int)pitch, FrameLayout::planar(in_frame, crop_stride)}, {0, 0, ccols, crows}, 3 * rblocks};
+    const int64_t src_off[3] = {b.lay.planes.b_off, b.lay.planes.g_off, b.lay.planes.r_off};
+    return stage_host_frames(c, frames_host, b.n, b.frame_stride, sp, out_host, [=](const uint8_t* frame, uint8_t* small, int item) {
+        const int p = item / rblocks, part = item - p * rblocks;
+        const uint8_t* src = frame + (size_t)src_off[p] + (size_t)x0;
+        uint8_t* dst = small + (size_t)p * plane;
+        const int r0 = part * 32, r1 = r0 + 32 < crows ? r0 + 32 : crows;
+        for (int y = r0; y < r1; ++y) memcpy(dst + (size_t)y * pitch, src + (size_t)(y0 + y) * row_pitch, (size_t)ccols);
+    });
+}
+
+extern "C" int melf_process_batch(melf_ctx* c, const uint8_t* frames_host, int n, int H, int W, size_t frame_stride,
+                                  melf_result* out_host)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    if (n == 0) return MELF_SUCCESS;
+    if (!frames_host || !out_host || n < 0 || H <= 0 || W <= 0) return fail(MELF_ERR_INVALID, "bad argument");
+    if (frame_stride < (size_t)H * W * 3) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
+    return host_packed(c, frames_host, bgr_batch(n, H, W, frame_stride), out_host);
+}
+
+extern "C" int melf_process_frames(melf_ctx* c, const void* frames_host, const melf_frames* f, melf_result* out_host)
+{
+    FrameBatch b;
+    if (int rc = check_frames(c, frames_host, f, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return host_packed(c, (const uint8_t*)frames_host, b, out_host);
 }
 
 extern "C" int melf_process_yuv(melf_ctx* c, const void* frames_host, const melf_yuv_frames* f, melf_result* out_host)
 {
-    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    int pix = 0;
-    YuvPlanes yp;
-    const YuvMatrix* mx = nullptr;
-    size_t extent = 0;
-    if (int rc = check_yuv(frames_host, f, &pix, &yp, &mx, &extent)) return rc;
-    if (f->n == 0) return MELF_SUCCESS;
-    if (!out_host) return fail(MELF_ERR_INVALID, "out_host is NULL");
-    return batch_host_yuv(c, (const uint8_t*)frames_host, f, pix, yp, mx, out_host);
-}
-
-// Packed YUV 4:2:2 host frames: the same pipeline.  What crosses PCIe per frame is a small frame of the same format: the rows of
-// the crop (no vertical rounding: every row has its own chroma), its x origin rounded down and its far corner up to even, i.e.
-// to whole macropixels, at a 64-byte pitch in the staging buffer; the kernels read it with the rectangle shifted by the rounding
-// (0 or 1 pixel).  Rows are copied as they are: no byte is converted or reordered on the CPU, and the small frames keep the
-// caller's matrix (mx).
-static int batch_host_p422(melf_ctx* c, const uint8_t* frames_host, const melf_yuv422_frames* f, int pix, const YuvMatrix* mx,
-                           melf_result* out_host)
-{
-    const int n = f->n, H = f->H, W = f->W;
-    HIP_TRY(hipSetDevice(c->device));
-    pool_use_device(c->device);
-    const melf_params& P = c->P;
-    const int x0 = P.rect_x0 < W ? P.rect_x0 : W, x1 = P.rect_x1 < W ? P.rect_x1 : W;
-    const int y0 = P.rect_y0 < H ? P.rect_y0 : H, y1 = P.rect_y1 < H ? P.rect_y1 : H;
-    const int crows = y1 - y0, ccols = x1 - x0;
-    if (x0 < 0 || y0 < 0 || crows < P.th || ccols < P.tw)
-        return fail(MELF_ERR_INVALID, "meter_rect crop is smaller than the dials template (cv2.matchTemplate would assert)");
-    const int ex0 = x0 & ~1;
-    const int sw = ((x1 + 1) & ~1) - ex0;   // the small frame's width (even, inside the frame: W is even)
-    const size_t rbytes = (size_t)sw * 2;
-    const size_t pitch = (rbytes + 63) & ~(size_t)63;
-    // + 128 spare bytes per small frame (the prep kernel's aligned windows reach past the last sample)
-    const size_t crop_stride = (size_t)crows * pitch + 128;
-    const int chunk = 128;  // frames per pipeline stage (a multiple of the 32-frame MFMA group)
-    const size_t pin_need = (size_t)(n < chunk ? n : chunk) * crop_stride;
-    if (!c->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    for (int b = 0; b < 2; ++b) {
-        if (!c->ev_h2d[b]) HIP_TRY(hipEventCreateWithFlags(&c->ev_h2d[b], hipEventDisableTiming));
-        if (c->pin_cap[b] < pin_need && (b == 0 || n > chunk)) {
-            if (c->h_pin[b]) { HIP_TRY(hipStreamSynchronize(c->copy_stream)); HIP_TRY(hipHostFree(c->h_pin[b])); }
-            c->h_pin[b] = nullptr;
-            c->pin_cap[b] = 0;
-            HIP_TRY(hipHostMalloc((void**)&c->h_pin[b], pin_need, hipHostMallocDefault));
-            c->pin_cap[b] = pin_need;
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));  // the previous call's kernels may still read d_crops
-    if (int rc = grow(&c->d_crops, &c->crops_cap, (size_t)n * crop_stride)) return rc;
-    if (int rc = grow(&c->d_results, &c->results_cap, (size_t)n)) return rc;
-    if (int rc = acquire_lane(c, c->stream, &c->active_lane)) return rc;
-    const int rect[4] = {x0 - ex0, 0, x0 - ex0 + ccols, crows};
-    int k = 0;
-    for (int f0 = 0; f0 < n; f0 += chunk, ++k) {
-        const int m = n - f0 < chunk ? n - f0 : chunk;
-        const int b = k & 1;
-        if (k >= 2) HIP_TRY(hipEventSynchronize(c->ev_h2d[b]));  // the copy that last read this staging buffer is done
-        uint8_t* pin = c->h_pin[b];
-        // work items: the rows of a frame in blocks of 32
-        const int rblocks = (crows + 31) / 32;
-        host_pool().run(m * rblocks, [&](int item) {
-            const int i = item / rblocks, part = item - i * rblocks;
-            const uint8_t* frame = frames_host + (size_t)(f0 + i) * (size_t)f->frame_stride;
-            uint8_t* small = pin + (size_t)i * crop_stride;
-            const int r0 = part * 32, r1 = r0 + 32 < crows ? r0 + 32 : crows;
-            for (int y = r0; y < r1; ++y)
-                memcpy(small + (size_t)y * pitch, frame + (size_t)(y0 + y) * (size_t)f->row_pitch + (size_t)ex0 * 2, rbytes);
-        });
-        uint8_t* d_chunk = c->d_crops + (size_t)f0 * crop_stride;
-        HIP_TRY(hipMemcpyAsync(d_chunk, pin, (size_t)m * crop_stride, hipMemcpyHostToDevice, c->copy_stream));
-        HIP_TRY(hipEventRecord(c->ev_h2d[b], c->copy_stream));
-        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_h2d[b], 0));
-        if (int rc = process_batch_on(c, d_chunk, m, crows, sw, crop_stride, c->d_results + f0, nullptr, c->stream, rect, (int)pitch, pix, nullptr, 0,
-                                      nullptr, mx))
-            return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(out_host, c->d_results, (size_t)n * sizeof(melf_result), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return MELF_SUCCESS;
+    FrameBatch b;
+    if (int rc = check_yuv(c, frames_host, f, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return host_yuv(c, (const uint8_t*)frames_host, b, out_host);
 }
 
 extern "C" int melf_process_yuv422(melf_ctx* c, const void* frames_host, const melf_yuv422_frames* f, melf_result* out_host)
 {
-    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    int pix = 0;
-    const YuvMatrix* mx = nullptr;
-    if (int rc = check_yuv422(frames_host, f, &pix, &mx)) return rc;
-    if (f->n == 0) return MELF_SUCCESS;
-    if (!out_host) return fail(MELF_ERR_INVALID, "out_host is NULL");
-    return batch_host_p422(c, (const uint8_t*)frames_host, f, pix, mx, out_host);
-}
-
-// Planar host frames: the same pipeline.  What crosses PCIe per frame is a small planar frame: the crop's rows of the B, the G and
-// the R plane, one plane after the other at a 64-byte pitch in the staging buffer, which the kernels read with the rectangle at
-// its origin.  Rows are copied as they are: no byte is interleaved or reordered on the CPU.
-static int batch_host_planes(melf_ctx* c, const uint8_t* frames_host, const melf_planar_frames* f, melf_result* out_host)
-{
-    const int n = f->n, H = f->H, W = f->W;
-    HIP_TRY(hipSetDevice(c->device));
-    pool_use_device(c->device);
-    const melf_params& P = c->P;
-    const int x0 = P.rect_x0 < W ? P.rect_x0 : W, x1 = P.rect_x1 < W ? P.rect_x1 : W;
-    const int y0 = P.rect_y0 < H ? P.rect_y0 : H, y1 = P.rect_y1 < H ? P.rect_y1 : H;
-    const int crows = y1 - y0, ccols = x1 - x0;
-    if (x0 < 0 || y0 < 0 || crows < P.th || ccols < P.tw)
-        return fail(MELF_ERR_INVALID, "meter_rect crop is smaller than the dials template (cv2.matchTemplate would assert)");
-    const size_t pitch = ((size_t)ccols + 63) & ~(size_t)63;
-    const size_t plane = (size_t)crows * pitch;
-    PlanarPlanes sp;
-    sp.b_off = 0; sp.g_off = (int64_t)plane; sp.r_off = (int64_t)(2 * plane);
-    // + 128 spare bytes per small frame (the prep kernel's aligned windows reach past the last sample)
-    const size_t crop_stride = 3 * plane + 128;
-    const int chunk = 128;  // frames per pipeline stage (a multiple of the 32-frame MFMA group)
-    const size_t pin_need = (size_t)(n < chunk ? n : chunk) * crop_stride;
-    if (!c->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    for (int b = 0; b < 2; ++b) {
-        if (!c->ev_h2d[b]) HIP_TRY(hipEventCreateWithFlags(&c->ev_h2d[b], hipEventDisableTiming));
-        if (c->pin_cap[b] < pin_need && (b == 0 || n > chunk)) {
-            if (c->h_pin[b]) { HIP_TRY(hipStreamSynchronize(c->copy_stream)); HIP_TRY(hipHostFree(c->h_pin[b])); }
-            c->h_pin[b] = nullptr;
-            c->pin_cap[b] = 0;
-            HIP_TRY(hipHostMalloc((void**)&c->h_pin[b], pin_need, hipHostMallocDefault));
-            c->pin_cap[b] = pin_need;
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));  // the previous call's kernels may still read d_crops
-    if (int rc = grow(&c->d_crops, &c->crops_cap, (size_t)n * crop_stride)) return rc;
-    if (int rc = grow(&c->d_results, &c->results_cap, (size_t)n)) return rc;
-    if (int rc = acquire_lane(c, c->stream, &c->active_lane)) return rc;
-    const int rect[4] = {0, 0, ccols, crows};
-    const int64_t src_off[3] = {f->b_offset, f->g_offset, f->r_offset};
-    int k = 0;
-    for (int f0 = 0; f0 < n; f0 += chunk, ++k) {
-        const int m = n - f0 < chunk ? n - f0 : chunk;
-        const int b = k & 1;
-        if (k >= 2) HIP_TRY(hipEventSynchronize(c->ev_h2d[b]));  // the copy that last read this staging buffer is done
-        uint8_t* pin = c->h_pin[b];
-        // work items: the crop's rows of one plane of a frame in blocks of 32
-        const int rblocks = (crows + 31) / 32;
-        host_pool().run(m * 3 * rblocks, [&](int item) {
-            const int i = item / (3 * rblocks), rest = item - i * 3 * rblocks, p = rest / rblocks, part = rest - p * rblocks;
-            const uint8_t* src = frames_host + (size_t)(f0 + i) * (size_t)f->frame_stride + (size_t)src_off[p] + (size_t)x0;
-            uint8_t* dst = pin + (size_t)i * crop_stride + (size_t)p * plane;
-            const int r0 = part * 32, r1 = r0 + 32 < crows ? r0 + 32 : crows;
-            for (int y = r0; y < r1; ++y) memcpy(dst + (size_t)y * pitch, src + (size_t)(y0 + y) * (size_t)f->row_pitch, (size_t)ccols);
-        });
-        uint8_t* d_chunk = c->d_crops + (size_t)f0 * crop_stride;
-        HIP_TRY(hipMemcpyAsync(d_chunk, pin, (size_t)m * crop_stride, hipMemcpyHostToDevice, c->copy_stream));
-        HIP_TRY(hipEventRecord(c->ev_h2d[b], c->copy_stream));
-        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_h2d[b], 0));
-        if (int rc = process_batch_on(c, d_chunk, m, crows, ccols, crop_stride, c->d_results + f0, nullptr, c->stream, rect, (int)pitch,
-                                      PIX_PLANAR, nullptr, crop_stride, &sp))
-            return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(out_host, c->d_results, (size_t)n * sizeof(melf_result), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return MELF_SUCCESS;
+    FrameBatch b;
+    if (int rc = check_yuv422(c, frames_host, f, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return host_p422(c, (const uint8_t*)frames_host, b, out_host);
 }
 
 extern "C" int melf_process_planes(melf_ctx* c, const void* frames_host, const melf_planar_frames* f, melf_result* out_host)
 {
-    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    PlanarPlanes pl;
-    size_t extent = 0;
-    if (int rc = check_planes(frames_host, f, &pl, &extent)) return rc;
-    if (f->n == 0) return MELF_SUCCESS;
-    if (!out_host) return fail(MELF_ERR_INVALID, "out_host is NULL");
-    return batch_host_planes(c, (const uint8_t*)frames_host, f, out_host);
+    FrameBatch b;
+    if (int rc = check_planes(c, frames_host, f, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return host_planes(c, (const uint8_t*)frames_host, b, out_host);
 }
 
 // ---------------------------------------------------------- stage entries ----
-extern "C" int melf_yuv422_to_bgr(melf_ctx* c, const void* frames_host, const melf_yuv422_frames* f, uint8_t* bgr_out_host)
+// melf_yuv_to_bgr / melf_yuv422_to_bgr after their checks: the frames up, the conversion kernel alone, n packed H x W BGR frames down
+static int to_bgr(melf_ctx* c, const void* frames_host, const FrameBatch& b, uint8_t* bgr_out_host)
 {
-    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    int pix = 0;
-    const YuvMatrix* mx = nullptr;
-    if (int rc = check_yuv422(frames_host, f, &pix, &mx)) return rc;
-    if (f->n == 0) return MELF_SUCCESS;
     if (!bgr_out_host) return fail(MELF_ERR_INVALID, "bgr_out_host is NULL");
     HIP_TRY(hipSetDevice(c->device));
-    const size_t in_bytes = (size_t)(f->n - 1) * (size_t)f->frame_stride + (size_t)(f->H - 1) * (size_t)f->row_pitch + (size_t)f->W * 2;
-    const size_t out_bytes = (size_t)f->n * f->H * f->W * 3;
+    const size_t in_bytes = (size_t)(b.n - 1) * b.frame_stride + b.lay.extent, out_bytes = (size_t)b.n * b.H * b.W * 3;
     if (int rc = grow(&c->d_stage_in, &c->stage_in_cap, in_bytes)) return rc;
     if (int rc = grow(&c->d_stage_out, &c->stage_out_cap, out_bytes)) return rc;
     HIP_TRY(hipMemcpyAsync(c->d_stage_in, frames_host, in_bytes, hipMemcpyHostToDevice, c->stream));
-    launch_p422_to_bgr(c->d_stage_in, pix, f->n, f->H, f->W, (int)f->row_pitch, (size_t)f->frame_stride, *mx, c->d_stage_out, c->stream);
+    if (pix_yuv(b.lay.pix))
+        launch_yuv2bgr(c->d_stage_in, b.lay.pix, b.n, b.H, b.W, b.row_stride, b.frame_stride, b.lay.yuv, *b.lay.mx, c->d_stage_out, c->stream);
+    else
+        launch_p422_to_bgr(c->d_stage_in, b.lay.pix, b.n, b.H, b.W, b.row_stride, b.frame_stride, *b.lay.mx, c->d_stage_out, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(bgr_out_host, c->d_stage_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return MELF_SUCCESS;
+}
+
+extern "C" int melf_yuv422_to_bgr(melf_ctx* c, const void* frames_host, const melf_yuv422_frames* f, uint8_t* bgr_out_host)
+{
+    FrameBatch b;
+    if (int rc = check_yuv422(c, frames_host, f, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return to_bgr(c, frames_host, b, bgr_out_host);
 }
 
 extern "C" int melf_yuv_to_bgr(melf_ctx* c, const void* frames_host, const melf_yuv_frames* f, uint8_t* bgr_out_host)
 {
-    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    int pix = 0;
-    YuvPlanes yp;
-    const YuvMatrix* mx = nullptr;
-    size_t extent = 0;
-    if (int rc = check_yuv(frames_host, f, &pix, &yp, &mx, &extent)) return rc;
-    if (f->n == 0) return MELF_SUCCESS;
-    if (!bgr_out_host) return fail(MELF_ERR_INVALID, "bgr_out_host is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t in_bytes = (size_t)(f->n - 1) * (size_t)f->frame_stride + extent, out_bytes = (size_t)f->n * f->H * f->W * 3;
-    if (int rc = grow(&c->d_stage_in, &c->stage_in_cap, in_bytes)) return rc;
-    if (int rc = grow(&c->d_stage_out, &c->stage_out_cap, out_bytes)) return rc;
-    HIP_TRY(hipMemcpyAsync(c->d_stage_in, frames_host, in_bytes, hipMemcpyHostToDevice, c->stream));
-    launch_yuv2bgr(c->d_stage_in, pix, f->n, f->H, f->W, (int)f->y_pitch, (size_t)f->frame_stride, yp, *mx, c->d_stage_out, c->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(bgr_out_host, c->d_stage_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return MELF_SUCCESS;
+    FrameBatch b;
+    if (int rc = check_yuv(c, frames_host, f, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return to_bgr(c, frames_host, b, bgr_out_host);
 }
 
 extern "C" int melf_bgr2hls(melf_ctx* c, const uint8_t* src_host, int rows, int cols, size_t row_stride, uint8_t* dst_host)
@@ -1970,7 +1835,7 @@ extern "C" int melf_match_ccoeff(melf_ctx* c, const uint8_t* images_host, int n,
     ms.readable = (size_t)n * rows * cols;
     int nparts = 0;
     MatchPartial* d_parts = nullptr;
-    if (int rc = run_match(c, ms, PIX_PLANE, n, 0, c->stream, result_map ? (float*)c->d_stage_out : nullptr, &d_parts, &nparts)) return rc;
+    if (int rc = run_match(c, ms, FrameLayout::plane(ms.frame_stride), n, 0, c->stream, result_map ? (float*)c->d_stage_out : nullptr, &d_parts, &nparts)) return rc;
     HIP_TRY(hipGetLastError());
     std::vector<MatchPartial> parts((size_t)n * nparts);
     HIP_TRY(hipMemcpyAsync(parts.data(), d_parts, parts.size() * sizeof(MatchPartial), hipMemcpyDeviceToHost, c->stream));
@@ -2007,7 +1872,7 @@ extern "C" int melf_read_dials(melf_ctx* c, const uint8_t* dials_hls_host, int n
     ds.readable = (size_t)n * per;
     {
         KernelTimer t(c, MELF_K_DIALS, c->stream);
-        launch_dials(ds, PIX_PLANE, n, P, c->d_geom, c->d_rowmasks, nullptr, 0, 1, c->d_results, c->stream, c->ws_max);
+        launch_dials(ds, FrameLayout::plane(per), n, P, c->d_geom, c->d_rowmasks, nullptr, 0, 1, c->d_results, c->stream, c->ws_max);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_host, c->d_results, (size_t)n * sizeof(melf_result), hipMemcpyDeviceToHost, c->stream));
@@ -2182,9 +2047,6 @@ static thread_local std::function<void()>* tl_jpeg_enqueued = nullptr;
 // status in h_status (pinned) once the context's stream has passed the point this function leaves it at.
 // overlapped: another call's kernels may still be running (melf_jpeg_process_files_begin, two calls in flight): nothing
 // here waits for the context's stream; what protects a ring slot is its own pair of events, across calls as within one.
-static int process_batch_on(melf_ctx* c, const void* d_frames, int n, int H, int W, size_t frame_stride,
-                            void* d_results, melf_result* out_host, hipStream_t st, const int* rect, int row_stride, int pix,
-                            const YuvPlanes* yuv, size_t yuv_extent, const PlanarPlanes* planes, const YuvMatrix* mx);
 // What a caller inside the library may already have of the files it hands to the decode path (the file-name entry points
 // do): the parsed headers + Huffman decode data (of file index[k] of that parse for the call's file k), and the pinned buffer
 // the files' bytes lie in.
@@ -2367,7 +2229,7 @@ static int jpeg_process_batch_from(melf_ctx* c, const uint8_t* const* data, cons
     if (rc == MELF_SUCCESS) {
         rc = acquire_lane(c, c->stream, &c->active_lane);
         if (rc == MELF_SUCCESS)
-            rc = process_batch_on(c, c->d_jframes[cs], n, H, W, (size_t)H * W * 3, c->d_jresults[cs], nullptr, c->stream, nullptr, 0);
+            rc = process_batch_on(c, c->d_jframes[cs], bgr_batch(n, H, W, (size_t)H * W * 3), c->d_jresults[cs], nullptr, c->stream);
     }
     if (rc != MELF_SUCCESS) {
         (void)hipDeviceSynchronize();   // nothing of the aborted pipeline may outlive the call

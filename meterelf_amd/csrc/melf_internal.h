@@ -85,6 +85,29 @@ struct PlanarPlanes {
     int64_t b_off, g_off, r_off;  // bytes from a frame's first byte to the first sample of its B / G / R plane
 };
 
+// How the frames of one launch lie in memory, beside the base, the strides and the rectangle of MatchSrc / DialsSrc: the pixel
+// layout and what goes with it.  Host side only: the launchers hand the kernels the members by value.  Made by the makers below
+// and by nothing else, so that which member means something for which pix is settled where the value is made, not at every use.
+struct FrameLayout {
+    int pix;
+    YuvPlanes yuv;         // pix_yuv(pix): the chroma planes
+    PlanarPlanes planes;   // PIX_PLANAR: where the three planes start
+    const YuvMatrix* mx;   // pix_yuv(pix), pix_p422(pix): the frames' colour conversion, never NULL there
+    size_t extent;         // bytes a kernel may read of the LAST frame, from its first byte (the others: frame_stride)
+
+    static FrameLayout packed(int pix /* MELF_PIX_* */, size_t extent) { return FrameLayout{pix, {}, {}, nullptr, extent}; }
+    static FrameLayout yuv420(int pix /* PIX_NV12, PIX_I420 */, const YuvPlanes& yp, const YuvMatrix& mx, size_t extent)
+    {
+        return FrameLayout{pix, yp, {}, &mx, extent};
+    }
+    static FrameLayout yuv422(int pix /* PIX_YUYV, PIX_UYVY, PIX_YVYU */, const YuvMatrix& mx, size_t extent)
+    {
+        return FrameLayout{pix, {}, {}, &mx, extent};
+    }
+    static FrameLayout planar(const PlanarPlanes& pl, size_t extent) { return FrameLayout{PIX_PLANAR, {}, pl, nullptr, extent}; }
+    static FrameLayout plane(size_t extent) { return FrameLayout{PIX_PLANE, {}, {}, nullptr, extent}; }
+};
+
 // ---- K2: template match -----------------------------------------------------
 // One partial (max, first-argmax) per workgroup tile of the correlation map.
 struct MatchPartial {
@@ -117,10 +140,8 @@ struct MatchSrc {
     size_t readable;      // bytes from `base` the caller guarantees readable: (images - 1) * frame_stride + the last image's rows
 };
 
-void launch_match(const MatchSrc& src, int pix, int n, const MatchGeom& g, const uint32_t* d_tplT,
-                  float* d_result_map, MatchPartial* d_partials, int* nparts_out, hipStream_t stream,
-                  const YuvPlanes* yuv = nullptr /* pix_yuv(pix) */, const PlanarPlanes* planes = nullptr /* PIX_PLANAR */,
-                  const YuvMatrix* mx = nullptr /* pix_yuv(pix) or pix_p422(pix): required */);
+void launch_match(const MatchSrc& src, const FrameLayout& lay, int n, const MatchGeom& g, const uint32_t* d_tplT,
+                  float* d_result_map, MatchPartial* d_partials, int* nparts_out, hipStream_t stream);
 int match_parts(const MatchGeom& g, int rows, int cols);
 
 // ---- K2 on the matrix cores (k_match_mfma.hip) --------------------------------
@@ -134,9 +155,8 @@ bool mfma_match_ok(int th, int tw, int rows, int cols);
 MfmaPlan mfma_plan(int th, int tw, int rows, int cols, int nframes);
 size_t mfma_atab_bytes(int th);
 void mfma_build_atab(const uint8_t* templ, int th, int tw, int8_t* atab);
-void launch_mfma_prep(const MatchSrc& src, int pix, int n, const MfmaPlan& p, int th, int tw, int8_t* d_lg,
-                      uint16_t* d_r, hipStream_t stream, const YuvPlanes* yuv = nullptr, const PlanarPlanes* planes = nullptr,
-                      const YuvMatrix* mx = nullptr);
+void launch_mfma_prep(const MatchSrc& src, const FrameLayout& lay, int n, const MfmaPlan& p, int th, int tw, int8_t* d_lg,
+                      uint16_t* d_r, hipStream_t stream);
 // launch_mfma_match: d_ws = the row-window sums R in epilogue order (k_prep_lplane); the waves add them up
 void launch_mfma_match(int n, const MfmaPlan& p, int th, int tw, long tsum, double tmean, const int8_t* d_atab,
                        const int8_t* d_lg, const uint32_t* d_ws, float* d_result_map, MatchPartial* d_partials,
@@ -173,9 +193,8 @@ void launch_gen_match(int n, const GenPlan& p, int rows, int th, int tw, long ts
                       hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 // prep for either matrix-core kernel: Lg (fragment order) and the row-window sums R in the match waves' epilogue order
 // (pairs > 0: the tuned kernel's paired-operand row layout, see k_prep_lplane)
-void launch_match_prep(const MatchSrc& src, int pix, int n, int groups, int rows_pad, int nkb, int rwp, int tw, int8_t* d_lg,
-                       uint16_t* d_r, hipStream_t stream, int pairs = 0, const YuvPlanes* yuv = nullptr,
-                       const PlanarPlanes* planes = nullptr, const YuvMatrix* mx = nullptr);
+void launch_match_prep(const MatchSrc& src, const FrameLayout& lay, int n, int groups, int rows_pad, int nkb, int rwp, int tw,
+                       int8_t* d_lg, uint16_t* d_r, hipStream_t stream, int pairs = 0);
 
 // ---- K3: per-dial reading ---------------------------------------------------
 struct DialGeom {
@@ -184,6 +203,7 @@ struct DialGeom {
     int32_t core_x, core_y;  // int(cx), int(cy): centre of the 5x5 colour core
 };
 
+// (MatchSrc under other field names: one struct would rename every kernel's mangled symbol and touch both .inc bodies -- not done)
 struct DialsSrc {
     const uint8_t* base;   // camera frames (the launch's pix) or packed HLS dials crops
     size_t frame_stride;
@@ -193,11 +213,9 @@ struct DialsSrc {
     size_t readable;       // bytes from `base` the caller guarantees readable: (frames - 1) * frame_stride + the last frame's rows
 };
 
-void launch_dials(const DialsSrc& src, int pix, int n, const melf_params& P, const DialGeom* d_geom,
+void launch_dials(const DialsSrc& src, const FrameLayout& lay, int n, const melf_params& P, const DialGeom* d_geom,
                   const uint64_t* d_rowmasks /* [ndials][3][64] */, const MatchPartial* d_partials,
-                  int nparts, int rw, melf_result* d_results, hipStream_t stream, int ws_max /* largest DialGeom::ws */,
-                  const YuvPlanes* yuv = nullptr /* pix_yuv(pix) */, const PlanarPlanes* planes = nullptr /* PIX_PLANAR */,
-                  const YuvMatrix* mx = nullptr /* pix_yuv(pix) or pix_p422(pix): required */);
+                  int nparts, int rw, melf_result* d_results, hipStream_t stream, int ws_max /* largest DialGeom::ws */);
 
 // ---- K1b / HLS --------------------------------------------------------------
 void launch_bgr2hls(const uint8_t* d_src, int rows, int cols, size_t row_stride, int hue_shift,

@@ -157,7 +157,8 @@ int melf_process_batch_dev(melf_ctx* ctx, const void* d_frames, int n, int H, in
  * or stride too small, a misaligned 4-byte layout or a NULL descriptor return MELF_ERR_INVALID before anything runs.
  * melf_process_stream_dev, the fused full-frame mask (melf_hls_inrange_close*), melf_aligned_average and the JPEG entry
  * points take packed BGR only; YUV 4:2:0 frames and packed YUV 4:2:2 frames have their own descriptors and entry points
- * (melf_process_yuv*, melf_process_yuv422*, below), and so have planar RGB frames (melf_process_planes*, below). */
+ * (melf_process_yuv*, melf_process_yuv422*, below), planar and semi-planar YUV of the other subsamplings too
+ * (melf_process_yuv_planar*), and so have planar RGB frames (melf_process_planes*, below). */
 enum { MELF_PIX_BGR = 0, MELF_PIX_RGB = 1, MELF_PIX_BGRA = 2, MELF_PIX_RGBA = 3 };
 typedef struct melf_frames {
     int32_t pixel_format;  /* MELF_PIX_*; the 4th byte of BGRA / RGBA is ignored                          */
@@ -201,7 +202,8 @@ int melf_process_frames_dev(melf_ctx* ctx, const void* d_frames, const melf_fram
  * triples differ from it at all under code 2, 1 315 under code 3, none under code 4).  Code 2 is the JFIF matrix but not
  * libjpeg's tables bit for bit: libjpeg rounds the chroma terms separately at 16 bits, and 8 332 triples differ by 1 (the JPEG
  * entry points below decode with libjpeg's own arithmetic and are not affected by any of this).
- * Out of scope: BT.2020, 10-bit formats, interpolated chroma, chroma siting, 4:4:4 and planar 4:2:2 layouts.
+ * Out of scope: BT.2020, 10-bit formats, interpolated chroma, chroma siting, planes in separate allocations.  (4:2:2, 4:4:4 and 4:4:0
+ * planes and NV21: melf_process_yuv_planar*, below.)
  * Frame f starts at frames + f * frame_stride; its Y row y at + y * y_pitch (W bytes), its chroma row y >> 1 at
  * + u_offset / v_offset + (y >> 1) * c_pitch: NV12 W bytes U V U V .. (v_offset == u_offset + 1), I420 W / 2 bytes per plane.
  * YV12 is I420 with the two offsets exchanged.  The buffer must hold every plane of every frame up to the last sample of its
@@ -263,6 +265,52 @@ int melf_process_yuv422_dev(melf_ctx* ctx, const void* d_frames, const melf_yuv4
                             void* stream);
 /* Stage entry point (parity tests, and a debug view for callers): the conversion alone, n packed H x W x 3 BGR frames out. */
 int melf_yuv422_to_bgr(melf_ctx* ctx, const void* frames_host, const melf_yuv422_frames* f, uint8_t* bgr_out_host);
+
+/* ---- the same path for planar and semi-planar YUV frames of any 8-bit chroma subsampling: what software JPEG / MJPEG decoders
+ * leave of a webcam's 4:2:2 (I422, ffmpeg's yuv422p / yuvj422p), screen capture and high-quality JPEG of 4:4:4 (I444, NV24), Rockchip
+ * and V4L2 decoders (NV16), Android's camera API (NV21) ----
+ * The contract of melf_process_yuv*: the records are byte-identical to melf_process_batch(_dev) on the packed BGR frame that the
+ * integer conversion above makes of each frame under the descriptor's matrix (any of the four; code 1 stays invalid).  That frame
+ * is never formed: the kernels read the planes in place, and only the meter_rect crop of them.
+ *     chroma: the nearest sample, no interpolation: pixel (x, y) uses U[y >> sub_y][x >> sub_x], V[y >> sub_y][x >> sub_x]
+ * One general descriptor instead of a format code.  Frame f starts at frames + f * frame_stride; its Y row y at + y * y_pitch (W
+ * bytes); U of pixel (x, y) is the byte at + u_offset + (y >> sub_y) * c_pitch + (x >> sub_x) * c_step, V the same from v_offset.
+ *     sub_x, sub_y  log2 of the chroma subsampling: 4:4:4 (0, 0)   4:2:2 (1, 0)   4:2:0 (1, 1)   4:4:0 (0, 1)
+ *     c_step        1: planar, U and V in planes of their own; 2: semi-planar, U and V interleaved in one plane: the two offsets are
+ *                   adjacent, and which is the lower says which byte of a pair comes first
+ *     4:2:2  I422 / yuv422p / yuvj422p (c_step 1, U first), YV16 (V first), NV16 (c_step 2, U first), NV61 (V first)
+ *     4:4:4  I444 / yuv444p / yuvj444p, YV24, NV24, NV42            4:4:0  I440 / yuvj440p
+ *     4:2:0  NV21 (c_step 2, V first); NV12, I420 and YV12 can be described as well and give the records of melf_process_yuv*
+ * Planes are bytes: any alignment of the base, the offsets, the pitches and frame_stride is taken.  The buffer must hold every
+ * plane of every frame up to the last sample of its last row, and need hold nothing behind that nor before the base: no load of
+ * the kernels reaches outside it.  MELF_ERR_INVALID (melf_last_error says which) before anything is launched or copied for: a NULL
+ * descriptor or NULL frames; reserved != 0; sub_x or sub_y outside {0, 1}; c_step outside {1, 2}; c_step 2 with offsets that are not
+ * adjacent; an odd W with sub_x, an odd H with sub_y; H or W <= 0, n < 0 (n == 0 passes); a negative offset; an unknown matrix;
+ * y_pitch < W; c_pitch smaller than a chroma row ((W >> sub_x) * c_step bytes); a pitch > 2^31 - 1; a chroma plane closer to the
+ * other than its span (overlapping) or starting inside the Y plane's span; a frame_stride smaller than the span of one frame. */
+typedef struct melf_yuv_planar_frames {
+    int32_t matrix;                             /* MELF_YUV_BT* as above                                  */
+    int32_t n, H, W;                            /* W even if sub_x, H even if sub_y                       */
+    int32_t sub_x, sub_y;                       /* log2 chroma subsampling, 0 or 1 each                   */
+    int32_t c_step;                             /* bytes from one sample of a chroma plane to the next in
+                                                   its row: 1 planar, 2 semi-planar                       */
+    int32_t reserved;                           /* 0                                                      */
+    int64_t y_pitch;                            /* bytes between Y rows, >= W                             */
+    int64_t c_pitch;                            /* bytes between chroma rows, >= (W >> sub_x) * c_step    */
+    int64_t u_offset, v_offset;                 /* from a frame's first byte to its first U / V sample;
+                                                   c_step 2: |u_offset - v_offset| == 1                   */
+    int64_t frame_stride;                       /* bytes between frames                                   */
+} melf_yuv_planar_frames;
+/* Host frames, as melf_process_yuv: only the crop crosses PCIe, packed into the pinned staging buffers as a small frame of the same
+ * layout (its origin rounded down and its far corner up to whole chroma blocks of 1 << sub_x by 1 << sub_y pixels: the Y rows of
+ * that rectangle and the chroma rows under them); no byte is converted or reordered on the CPU. */
+int melf_process_yuv_planar(melf_ctx* ctx, const void* frames_host, const melf_yuv_planar_frames* f, melf_result* out_host);
+/* Frames in HBM, exactly as melf_process_yuv_dev: the same lanes, melf_ctx_set_frames_resident, caller streams, and NULL
+ * d_results / out_host semantics. */
+int melf_process_yuv_planar_dev(melf_ctx* ctx, const void* d_frames, const melf_yuv_planar_frames* f, void* d_results,
+                                melf_result* out_host, void* stream);
+/* Stage entry point (parity tests, and a debug view for callers): the conversion alone, n packed H x W x 3 BGR frames out. */
+int melf_yuv_planar_to_bgr(melf_ctx* ctx, const void* frames_host, const melf_yuv_planar_frames* f, uint8_t* bgr_out_host);
 
 /* ---- the same path for planar, channels-first frames: (N, 3, H, W) uint8 as torch's decoders and pre-processing pipelines
  * hold them, ffmpeg's gbrp, rgb24 split into planes ----

@@ -207,6 +207,23 @@ class MeterReader:
         desc = v.descriptor()
         return self._read_view(v, out, lambda: self.ctx.process_yuv422(v.ptr, desc), lambda **kw: self.ctx.process_yuv422_dev(v.ptr, desc, **kw))
 
+    def read_yuv_planar_frames(self, frames, pixel_format: str = 'i422', matrix='bt601', out=None):
+        """Planar and semi-planar YUV frames of the other chroma subsamplings -- 4:2:2 as software MJPEG decoders leave a webcam's
+        frames ('i422': ffmpeg's yuv422p / yuvj422p; 'yv16'; 'nv16' / 'nv61' of Rockchip and V4L2 decoders), 4:4:4 of screen capture
+        and high-quality JPEG ('i444', 'yv24', 'nv24', 'nv42'), 4:4:0 ('i440'), and Android's 'nv21' -- -> records, equal to
+        read_frames() of the packed BGR frames that the integer conversion of include/meterelf_hip.h makes of them under `matrix`
+        with the nearest chroma sample (melf_process_yuv_planar*); the planes are read in place, no conversion pass.  'nv12', 'i420'
+        and 'yv12' are taken too and give read_yuv_frames' records.  matrix as for read_yuv_frames ('bt601-full' for yuvj422p /
+        yuvj444p).  frames: the raw-video (N, rows, W) uint8 array, rows = 2 H (4:2:2, 4:4:0), 3 H (4:4:4) or 3 H / 2 (4:2:0), for
+        'i444' / 'yv24' also (N, 3, H, W); a numpy array / torch CPU tensor (host path) or a torch tensor on this reader's GPU
+        (enqueued on torch.cuda.current_stream); _hip.yuv_planar_frames_view says which layouts are read in place.  out: a uint8
+        device tensor (N, RESULT_DTYPE.itemsize) on the same GPU that receives the records without synchronising the stream (device
+        frames only); returns it.  Otherwise returns the records."""
+        v = _hip.yuv_planar_frames_view(frames, pixel_format, matrix)
+        desc = v.descriptor()
+        return self._read_view(v, out, lambda: self.ctx.process_yuv_planar(v.ptr, desc),
+                               lambda **kw: self.ctx.process_yuv_planar_dev(v.ptr, desc, **kw))
+
     def read_planar_frames(self, frames, channel_order: str = 'rgb', out=None):
         """Planar, channels-first frames (N, 3, H, W) / (N, 4, H, W) uint8 -> records, equal to read_frames() of the packed BGR
         frames with the same samples (melf_process_planes*); the planes are read in place, no interleaved copy is made.  frames: a

@@ -102,6 +102,22 @@ YUV422_CODES = {'yuyv': YUV422_YUYV, 'yuy2': YUV422_YUYV, 'uyvy': YUV422_UYVY, '
 
 
 
+class MelfYuvPlanarFrames(C.Structure):
+    _fields_ = [('matrix', C.c_int32), ('n', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('sub_x', C.c_int32),
+                ('sub_y', C.c_int32), ('c_step', C.c_int32), ('reserved', C.c_int32), ('y_pitch', C.c_int64),
+                ('c_pitch', C.c_int64), ('u_offset', C.c_int64), ('v_offset', C.c_int64), ('frame_stride', C.c_int64)]
+
+
+# planar and semi-planar YUV layouts of melf_process_yuv_planar* by name: (sub_x, sub_y, c_step, V before U).  sub_x, sub_y: log2 of
+# the chroma subsampling; c_step 1: U and V in planes of their own, 2: interleaved pairs in one plane.
+YUV_PLANAR_FORMATS = {
+    'i422': (1, 0, 1, False), 'yv16': (1, 0, 1, True), 'nv16': (1, 0, 2, False), 'nv61': (1, 0, 2, True),
+    'i444': (0, 0, 1, False), 'yv24': (0, 0, 1, True), 'nv24': (0, 0, 2, False), 'nv42': (0, 0, 2, True),
+    'i440': (0, 1, 1, False),
+    'nv21': (1, 1, 2, True), 'nv12': (1, 1, 2, False), 'i420': (1, 1, 1, False), 'yv12': (1, 1, 1, True),
+}
+
+
 class MelfPlanarFrames(C.Structure):
     _fields_ = [('n', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('reserved', C.c_int32), ('b_offset', C.c_int64),
                 ('g_offset', C.c_int64), ('r_offset', C.c_int64), ('row_pitch', C.c_int64), ('frame_stride', C.c_int64)]
@@ -131,6 +147,7 @@ EXPORTS = [
     'melf_ctx_params', 'melf_ctx_sync', 'melf_ctx_get_masks', 'melf_process_batch', 'melf_process_batch_dev', 'melf_process_stream_dev',
     'melf_process_frames', 'melf_process_frames_dev', 'melf_process_yuv', 'melf_process_yuv_dev', 'melf_yuv_to_bgr',
     'melf_process_yuv422', 'melf_process_yuv422_dev', 'melf_yuv422_to_bgr', 'melf_process_planes', 'melf_process_planes_dev',
+    'melf_process_yuv_planar', 'melf_process_yuv_planar_dev', 'melf_yuv_planar_to_bgr',
     'melf_bgr2hls', 'melf_hls_inrange_close', 'melf_hls_inrange_close_dev', 'melf_match_ccoeff',
     'melf_read_dials', 'melf_aligned_average', 'melf_inrange', 'melf_ctx_fused_table_ties', 'melf_ctx_fused_variant', 'melf_ctx_set_frames_resident', 'melf_ctx_last_match', 'melf_match_layout_query', 'melf_match_gen_plan_query', 'melf_ctx_set_profiling', 'melf_ctx_timings', 'melf_kernel_name',
     'melf_jpeg_probe', 'melf_jpeg_probe_batch', 'melf_jpeg_decode_batch', 'melf_jpeg_clean_segment', 'melf_jpeg_process_batch',
@@ -177,6 +194,9 @@ def lib():
     L.melf_process_yuv422.argtypes = [vp, vp, C.POINTER(MelfYuv422Frames), vp]
     L.melf_process_yuv422_dev.argtypes = [vp, vp, C.POINTER(MelfYuv422Frames), vp, vp, vp]
     L.melf_yuv422_to_bgr.argtypes = [vp, vp, C.POINTER(MelfYuv422Frames), vp]
+    L.melf_process_yuv_planar.argtypes = [vp, vp, C.POINTER(MelfYuvPlanarFrames), vp]
+    L.melf_process_yuv_planar_dev.argtypes = [vp, vp, C.POINTER(MelfYuvPlanarFrames), vp, vp, vp]
+    L.melf_yuv_planar_to_bgr.argtypes = [vp, vp, C.POINTER(MelfYuvPlanarFrames), vp]
     L.melf_process_planes.argtypes = [vp, vp, C.POINTER(MelfPlanarFrames), vp]
     L.melf_process_planes_dev.argtypes = [vp, vp, C.POINTER(MelfPlanarFrames), vp, vp, vp]
     L.melf_process_stream_dev.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, vp]
@@ -471,6 +491,107 @@ def yuv422_frames_view(frames, pixel_format='yuyv', matrix='bt601'):
     return Yuv422FramesView(int(ptr), on_device, device, code, n, H, W, int(rp), int(fs), int(extent), not ok, frames, mcode)
 
 
+class YuvPlanarFramesView(NamedTuple):
+    """How the kernels read a batch of planar / semi-planar YUV frames in place (yuv_planar_frames_view)."""
+    ptr: int            # address of frame 0's first Y sample
+    on_device: bool     # True: a torch tensor on a GPU (ptr is a device address)
+    device: Optional[int]
+    n: int
+    H: int
+    W: int
+    sub_x: int          # log2 of the chroma subsampling
+    sub_y: int
+    c_step: int         # bytes between the samples of a chroma plane: 1 planar, 2 semi-planar
+    y_pitch: int        # bytes between Y rows
+    c_pitch: int        # bytes between chroma rows
+    u_offset: int       # bytes from a frame's first byte to its first U / V sample
+    v_offset: int
+    frame_stride: int   # bytes between frames
+    extent: int         # bytes read from ptr: every plane of every frame up to the last sample of its last row
+    copied: bool        # the layout could not be described and the frames were copied once to a packed array
+    array: object       # what ptr points into (the caller's array, or the copy): keep it alive while the call runs
+    matrix: int = YUV_BT601_LIMITED   # YUV_BT* code of the colour conversion
+
+    def descriptor(self):
+        return MelfYuvPlanarFrames(self.matrix, self.n, self.H, self.W, self.sub_x, self.sub_y, self.c_step, 0, self.y_pitch,
+                                   self.c_pitch, self.u_offset, self.v_offset, self.frame_stride)
+
+
+def yuv_planar_frames_view(frames, pixel_format='i422', matrix='bt601'):
+    """Describes the raw-video (N, rows, W) uint8 array of planar / semi-planar YUV frames (numpy array or torch tensor) as
+    melf_process_yuv_planar* read it.  pixel_format, a name of YUV_PLANAR_FORMATS: 4:2:2 'i422' (yuv422p / yuvj422p), 'yv16', 'nv16',
+    'nv61' (rows = 2 H); 4:4:4 'i444' (yuv444p / yuvj444p), 'yv24', 'nv24', 'nv42' (rows = 3 H); 4:4:0 'i440' (rows = 2 H); 4:2:0
+    'nv21', 'nv12', 'i420', 'yv12' (rows = 3 H / 2).  Rows 0 .. H - 1 are Y; behind them the U plane and then the V plane ('yv..': V
+    first), H >> sub_y rows of W >> sub_x bytes each, or one plane of interleaved U V pairs ('nv16', 'nv24', 'nv12'; V U: 'nv61',
+    'nv42', 'nv21').  For 'i444' / 'yv24' an (N, 3, H, W) array is taken as well (planes Y U V / Y V U).  The frame stride is
+    honoured in place (frames[::2], frames[a:b]); a row-padded view (frames[:, :, :w]) where a chroma row is one row of the array:
+    the semi-planar 4:2:x formats, 'i440', and 'i444' / 'yv24' in either shape.  Anything else -- padded rows of a layout whose chroma
+    rows are half or double rows of the array, an element stride other than 1, negative strides -- is copied once to a packed array
+    (YuvPlanarFramesView.copied).  matrix as for yuv_frames_view.  Not uint8, a shape that is not that of the format, an odd W (H)
+    where the chroma is subsampled horizontally (vertically), an unknown format or an unknown matrix: ValueError."""
+    mcode = yuv_matrix_code(matrix)
+    (frames, is_torch, shape, strides, ptr, on_device, device) = _unwrap(frames)
+    fmt = str(pixel_format).lower()
+    if fmt not in YUV_PLANAR_FORMATS:
+        raise ValueError('pixel_format %r is not a planar / semi-planar YUV layout (%s)' % (pixel_format, ', '.join(YUV_PLANAR_FORMATS)))
+    (sx, sy, step, vfirst) = YUV_PLANAR_FORMATS[fmt]
+    if len(shape) == 4 and (sx, sy, step) == (0, 0, 1):
+        # (N, 3, H, W): three whole planes, Y first
+        if shape[1] != 3 or shape[2] == 0 or shape[3] == 0:
+            raise ValueError('planar 4:4:4 frames must be (N, 3 * H, W) or (N, 3, H, W), not %s' % (shape,))
+        (n, _c, H, W) = shape
+        (fs, ps, rp, es) = strides
+        if W == 1:
+            es = 1
+        if H == 1:
+            rp = W
+        span = (H - 1) * rp + W
+        if n == 1:
+            fs = 2 * ps + span if ps >= 0 else 0
+        ok = es == 1 and W <= rp <= 2 ** 31 - 1 and ps >= span and fs >= 2 * ps + span
+        if not ok:
+            (frames, ptr) = _packed_copy(frames, is_torch)
+            (rp, ps, fs) = (W, H * W, 3 * H * W)
+            span = H * W
+        (first, second) = (ps, 2 * ps)
+        (u_off, v_off) = (second, first) if vfirst else (first, second)
+        extent = (n - 1) * fs + 2 * ps + span if n else 0
+        return YuvPlanarFramesView(int(ptr), on_device, device, n, H, W, 0, 0, 1, int(rp), int(rp), int(u_off), int(v_off), int(fs),
+                                   int(extent), not ok, frames, mcode)
+    blocks = (1 << sx) * (1 << sy)                    # pixels per chroma sample: rows = H * (blocks + 2) / blocks
+    bad = len(shape) != 3 or shape[1] == 0 or shape[2] == 0 or (shape[1] * blocks) % (blocks + 2) != 0
+    if not bad:
+        (n, rows, W) = shape
+        H = rows * blocks // (blocks + 2)
+        bad = (sx and W % 2) or (sy and H % 2)
+    if bad:
+        raise ValueError('%s frames must be (N, H * %d // %d, W)%s, not %s'
+                         % (fmt, blocks + 2, blocks, ' with an even W' * sx + ' with an even H' * sy, shape))
+    (fs, rp, es) = strides
+    (cw, ch) = ((W >> sx) * step, H >> sy)            # bytes of a chroma row (semi-planar: of both), chroma rows
+    if W == 1:
+        es = 1
+    if n == 1:
+        fs = rows * rp if rp > 0 else 0
+    whole_rows = cw == W                              # a chroma row is one row of the array: padded rows can be described
+    ok = es == 1 and W <= rp <= 2 ** 31 - 1 and fs >= (rows - 1) * rp + W and (whole_rows or rp == W)
+    if not ok:
+        (frames, ptr) = _packed_copy(frames, is_torch)
+        (rp, fs) = (W, rows * W)
+    c_pitch = rp if whole_rows else cw
+    first = H * rp
+    if step == 2:
+        (u_off, v_off) = (first + 1, first) if vfirst else (first, first + 1)
+        last = first + (ch - 1) * c_pitch + cw
+    else:
+        second = first + ch * c_pitch
+        (u_off, v_off) = (second, first) if vfirst else (first, second)
+        last = second + (ch - 1) * c_pitch + cw
+    extent = (n - 1) * fs + last if n else 0
+    return YuvPlanarFramesView(int(ptr), on_device, device, n, H, W, sx, sy, step, int(rp), int(c_pitch), int(u_off), int(v_off), int(fs),
+                               int(extent), not ok, frames, mcode)
+
+
 class PlanarFramesView(NamedTuple):
     """How the kernels read a batch of planar (channels-first) frames in place (planar_frames_view)."""
     ptr: int            # address of frame 0's first plane
@@ -735,7 +856,7 @@ class Context:
         return out
 
     def _host(self, entry, frames_ptr, desc):
-        """A descriptor-taking host entry point (melf_process_frames / _yuv / _yuv422 / _planes) -> records."""
+        """A descriptor-taking host entry point (melf_process_frames / _yuv / _yuv422 / _yuv_planar / _planes) -> records."""
         out = np.zeros(desc.n, RESULT_DTYPE)
         check(entry(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
         return out
@@ -784,6 +905,21 @@ class Context:
         """The conversion alone (melf_yuv422_to_bgr): host packed YUV 4:2:2 frames -> (n, H, W, 3) BGR."""
         out = np.empty((desc.n, desc.H, desc.W, 3), np.uint8)
         check(self._L.melf_yuv422_to_bgr(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
+        return out
+
+    def process_yuv_planar(self, frames_ptr, desc):
+        """Host planar / semi-planar YUV frames (melf_process_yuv_planar; desc: a MelfYuvPlanarFrames, e.g.
+        yuv_planar_frames_view(...).descriptor()) -> records."""
+        return self._host(self._L.melf_process_yuv_planar, frames_ptr, desc)
+
+    def process_yuv_planar_dev(self, d_frames_ptr, desc, d_results_ptr=None, want_host=True, stream=None):
+        """Planar / semi-planar YUV frames in HBM (melf_process_yuv_planar_dev, as process_frames_dev).  Returns records when want_host."""
+        return self._dev(self._L.melf_process_yuv_planar_dev, d_frames_ptr, desc, d_results_ptr, want_host, stream)
+
+    def yuv_planar_to_bgr(self, frames_ptr, desc):
+        """The conversion alone (melf_yuv_planar_to_bgr): host planar / semi-planar YUV frames -> (n, H, W, 3) BGR."""
+        out = np.empty((desc.n, desc.H, desc.W, 3), np.uint8)
+        check(self._L.melf_yuv_planar_to_bgr(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
         return out
 
     def process_planes(self, frames_ptr, desc):

@@ -327,6 +327,25 @@ __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_v
 }
 #undef MELF_P422_BODY
 
+// Planar / semi-planar YUV frames of any subsampling (melf_process_yuv_planar*): src describes the Y plane, yuv the chroma.  One
+// instantiation per form of the chroma fetch (SUBX: log2 of the horizontal subsampling, CSTEP: bytes between the samples of a
+// chroma plane) and NR; sub_y, the order of a pair's bytes and the matrix are runtime, wave-uniform values.
+#define MELF_YUVP_BODY
+template <int SUBX, int CSTEP, int NR>
+__global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_vgpr(DIALS_VGPRS))) void k_yp_needle(DialsSrc src, YuvPlanarPlanes yuv, YuvMatrix ymat, melf_params P,
+                                                                const DialGeom* __restrict__ geom,
+                                                                const uint64_t* __restrict__ rowmasks,
+                                                                const MatchPartial* __restrict__ partials,
+                                                                int nparts, int rw, melf_result* __restrict__ results)
+{
+    constexpr bool FROM_HLS = false;
+    constexpr int PB = 4;
+    constexpr bool RT_ORDER = false;
+    const uint32_t bsel = 0u;
+#include "k_dials_body.inc"
+}
+#undef MELF_YUVP_BODY
+
 // Planar frames (melf_process_planes*): the B, G and R planes at `planes` in a frame.  Past its loads the body is the one of 4-byte
 // B G R pixels.
 #define MELF_PLANAR_BODY
@@ -374,7 +393,12 @@ void launch_dials(const DialsSrc& src, const FrameLayout& lay, int n, const melf
             const int swap_rb = pix == MELF_PIX_RGB || pix == MELF_PIX_RGBA;
             hipLaunchKernelGGL(kernel, grid, block, shmem, stream, src, P, d_geom, d_rowmasks, d_partials, nparts, rw, d_results, swap_rb);
         };
-        if (pix == PIX_PLANAR) go(k_planar_needle<NR>, lay.planes);
+        if (pix == PIX_YUVP) {
+            const YuvPlanarPlanes& yp = lay.yuvp;
+            if (yp.sub_x == 0) { if (yp.c_step == 1) go(k_yp_needle<0, 1, NR>, yp, *lay.mx); else go(k_yp_needle<0, 2, NR>, yp, *lay.mx); }
+            else { if (yp.c_step == 1) go(k_yp_needle<1, 1, NR>, yp, *lay.mx); else go(k_yp_needle<1, 2, NR>, yp, *lay.mx); }
+        }
+        else if (pix == PIX_PLANAR) go(k_planar_needle<NR>, lay.planes);
         else if (pix_p422(pix)) go(k_p422_needle<NR>, p422_sel(pix), *lay.mx);
         else if (pix == PIX_NV12) go(k_yneedle<false, NR>, lay.yuv, *lay.mx);
         else if (pix == PIX_I420) go(k_yneedle<true, NR>, lay.yuv, *lay.mx);

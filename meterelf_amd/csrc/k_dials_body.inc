@@ -20,6 +20,12 @@
 // (PlanarPlanes) in a frame, any byte alignment.  The core pixel and the exact path's column pixel are three byte loads; a lane's
 // four window pixels are one unaligned dword per plane (inside the crop's row of its plane: the pieces lie inside the crop), turned
 // into four B G R dwords by six v_perm_b32 where the prefilter picks them up: from there on as above, at any byte phase.
+// With MELF_YUVP_BODY defined instead (k_yp_needle): planar / semi-planar YUV frames of any subsampling (melf_process_yuv_planar*),
+// src the Y plane, `yuv` the chroma (YuvPlanarPlanes), any byte alignment; SUBX (0, 1) and CSTEP (1, 2) are compile-time: the four
+// forms of the chroma fetch.  As for k_yneedle a lane's four window pixels are one Y dword and the chroma under it: CSTEP 1 one
+// unaligned dword of each plane (SUBX 1: the three samples the four pixels can touch, SUBX 0: their four), CSTEP 2 one 8-byte load
+// of interleaved pairs (three or four of them), split by two v_perm_b32 whose selectors the order of a pair's bytes exchanges; sub_y
+// is the scalar shift of the chroma row.  Nothing is read outside the crop's rows of the planes.
     [[maybe_unused]] const uint32_t csel = bsel ? 0x0c000102u : 0x0c020100u;   // pixel -> B G R in bytes 0..2 (RT_ORDER)
     auto bgr = [&](uint32_t px) -> uint32_t {
         if constexpr (RT_ORDER) return __builtin_amdgcn_perm(0u, px, csel);
@@ -111,6 +117,19 @@
         const int yv = frame[(size_t)fy * rstride + (size_t)fx];
         return yuv_bgr(yv, yuv_chroma<false>(uplane[co], vplane[co], ymat), ymat);
     };
+#elif defined(MELF_YUVP_BODY)
+    const int fx_m = src.x0 + mx, fy_m = src.y0 + my;   // the match position in the frame
+    const int cp_u = __builtin_amdgcn_readfirstlane(yuv.c_pitch);
+    const uint32_t sy_u = (uint32_t)__builtin_amdgcn_readfirstlane(yuv.sub_y);
+    const uint8_t* const uplane = frame + (size_t)yuv.u_off;
+    const uint8_t* const vplane = frame + (size_t)yuv.v_off;
+    // pixel (X, Y) of the dials crop as a B G R dword: three byte loads
+    auto yuv_px = [&](int X, int Y) -> uint32_t {
+        const int fx = fx_m + X, fy = fy_m + Y;
+        const size_t co = (size_t)(fy >> sy_u) * (size_t)cp_u + (size_t)((fx >> SUBX) * CSTEP);
+        const int yv = frame[(size_t)fy * rstride + (size_t)fx];
+        return yuv_bgr(yv, yuv_chroma<false>(uplane[co], vplane[co], ymat), ymat);
+    };
 #elif defined(MELF_P422_BODY)
     const int fx_m = src.x0 + mx, fy_m = src.y0 + my;   // the match position in the frame
     // pixel (X, Y) of the dials crop as a B G R dword: its macropixel, one aligned dword load
@@ -134,7 +153,7 @@
 #endif
     const int coreX = G.core_x - 2 + lane % 5, coreY = G.core_y - 2 + (lane < 25 ? lane / 5 : 0);
     const bool corevalid = lane < 25 && coreX >= 0 && coreX < P.tw && coreY >= 0 && coreY < P.th;
-#if defined(MELF_YUV_BODY) || defined(MELF_P422_BODY)
+#if defined(MELF_YUV_BODY) || defined(MELF_P422_BODY) || defined(MELF_YUVP_BODY)
     const uint32_t corepx = yuv_px(min(max(coreX, 0), P.tw - 1), min(max(coreY, 0), P.th - 1));
 #elif defined(MELF_PLANAR_BODY)
     const uint32_t corepx = planar_px(min(max(coreX, 0), P.tw - 1), min(max(coreY, 0), P.th - 1));
@@ -187,6 +206,49 @@
         o.y = yuv_bgr((r.x >> 8) & 255, fodd ? c1 : c0, ymat);
         o.z = yuv_bgr((r.x >> 16) & 255, c1, ymat);
         o.w = yuv_bgr(r.x >> 24, fodd ? c2 : c1, ymat);
+        return o;
+    };
+#elif defined(MELF_YUVP_BODY)
+    // A lane's four pixels are one Y dword (inside its row: the pieces lie inside the crop) and the chroma under them.  SUBX 1: the
+    // pairs (fx0 >> 1) .. (fx0 + 3) >> 1, two or three of them, in a load of four samples that starts at the first or, near the
+    // crop's right edge, as far left of it as keeps the load inside the chroma row of the crop (xlim: the crop's right edge, rounded
+    // up to a whole pair); the shift is undone below.  SUBX 0: the four samples of the four pixels, inside the crop like the Y dword.
+    // CSTEP 2: the samples are interleaved pairs, read from the lower of the two offsets.  Any alignment (unaligned global loads).
+    (void)buf_end;
+    const int xlim = (src.x0 + src.crop_cols + 1) & ~1;
+    const bool quads = wx0 >= 0 && wx0 + 4 * npiece <= P.tw && (SUBX == 0 || xlim >= 8);
+    const int fx0 = fx_m + wx0 + 4 * min(pc, npiece - 1);   // the lane's first pixel in the frame
+    const int cstart = SUBX ? min(fx0 >> 1, (xlim >> 1) - 4) : fx0;                     // first chroma sample loaded
+    const uint32_t cshift = SUBX ? (uint32_t)((fx0 >> 1) - cstart) * 8u * CSTEP : 0u;   // bits to the lane's first sample
+    const bool fodd = fx0 & 1;
+    const bool vfirst = yuv.v_off < yuv.u_off;   // CSTEP 2: V before U in a pair (wave-uniform)
+    const uint8_t* const cplane = vfirst ? vplane : uplane;
+    const uint32_t usel = vfirst ? 0x07050301u : 0x06040200u, vsel = vfirst ? 0x06040200u : 0x07050301u;
+    // the four pixels as B G R dwords from what was loaded: {Y dword, chroma, chroma, -}
+    auto yuv_quad = [&](const u32x4v r) -> u32x4v {
+        uint32_t cu, cv;   // U / V of the samples in bytes 0 ..
+        if constexpr (CSTEP == 1) {
+            cu = r.y >> cshift; cv = r.z >> cshift;
+        } else {
+            const uint64_t c = (((uint64_t)r.z << 32) | r.y) >> cshift;   // the pairs from the lane's first on
+            const uint32_t lo = (uint32_t)c, hi = (uint32_t)(c >> 32);
+            cu = __builtin_amdgcn_perm(hi, lo, usel); cv = __builtin_amdgcn_perm(hi, lo, vsel);
+        }
+        const YuvChroma c0 = yuv_chroma<false>(cu & 255, cv & 255, ymat), c1 = yuv_chroma<false>((cu >> 8) & 255, (cv >> 8) & 255, ymat),
+                        c2 = yuv_chroma<false>((cu >> 16) & 255, (cv >> 16) & 255, ymat);
+        u32x4v o;
+        if constexpr (SUBX) {   // pixel j sits on pair (j + fodd) >> 1
+            o.x = yuv_bgr(r.x & 255, c0, ymat);
+            o.y = yuv_bgr((r.x >> 8) & 255, fodd ? c1 : c0, ymat);
+            o.z = yuv_bgr((r.x >> 16) & 255, c1, ymat);
+            o.w = yuv_bgr(r.x >> 24, fodd ? c2 : c1, ymat);
+        } else {                // a sample per pixel
+            const YuvChroma c3 = yuv_chroma<false>(cu >> 24, cv >> 24, ymat);
+            o.x = yuv_bgr(r.x & 255, c0, ymat);
+            o.y = yuv_bgr((r.x >> 8) & 255, c1, ymat);
+            o.z = yuv_bgr((r.x >> 16) & 255, c2, ymat);
+            o.w = yuv_bgr(r.x >> 24, c3, ymat);
+        }
         return o;
     };
 #elif defined(MELF_P422_BODY)
@@ -255,6 +317,26 @@
             } else {
                 uint32_t cd[2];
                 __builtin_memcpy(cd, uplane + co, 8);
+                raw[g] = u32x4v{yd, cd[0], cd[1], 0u};
+            }
+        }
+    }
+#elif defined(MELF_YUVP_BODY)
+    if (quads) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const int fy = fy_m + min(max(wy0 + min(4 * g + rg, ylast), 0), th1);
+            uint32_t yd;
+            __builtin_memcpy(&yd, frame + (size_t)fy * (size_t)rs_u + (size_t)fx0, 4);
+            const size_t co = (size_t)(fy >> sy_u) * (size_t)cp_u + (size_t)(cstart * CSTEP);
+            if constexpr (CSTEP == 1) {
+                uint32_t ud, vd;
+                __builtin_memcpy(&ud, uplane + co, 4);
+                __builtin_memcpy(&vd, vplane + co, 4);
+                raw[g] = u32x4v{yd, ud, vd, 0u};
+            } else {
+                uint32_t cd[2];
+                __builtin_memcpy(cd, cplane + co, 8);
                 raw[g] = u32x4v{yd, cd[0], cd[1], 0u};
             }
         }
@@ -330,7 +412,7 @@
 #pragma unroll
             for (int k = 0; k < 16; ++k) {
                 const int Y = min(max(wy0 + min(yc + k, ylast), 0), th1);
-#if defined(MELF_YUV_BODY) || defined(MELF_P422_BODY)
+#if defined(MELF_YUV_BODY) || defined(MELF_P422_BODY) || defined(MELF_YUVP_BODY)
                 pxe[k] = yuv_px(Xc, Y);
 #elif defined(MELF_PLANAR_BODY)
                 pxe[k] = planar_px(Xc, Y);
@@ -381,7 +463,7 @@
         if (quads) {
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
-#if defined(MELF_YUV_BODY) || defined(MELF_P422_BODY)
+#if defined(MELF_YUV_BODY) || defined(MELF_P422_BODY) || defined(MELF_YUVP_BODY)
                 raw[g] = yuv_quad(raw[g]);   // from here on: one B G R pixel per dword, as for 4-byte pixels
 #elif defined(MELF_PLANAR_BODY)
                 raw[g] = planar_quad(raw[g]);   // (the same)

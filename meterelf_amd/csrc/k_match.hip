@@ -31,14 +31,16 @@ __device__ inline bool better(float v, int i, float bv, int bi)
 // does not depend on the channel order), 4 = 4-byte pixels (BGRA / RGBA, 4-byte aligned, the 4th byte ignored); 20 / 21 = NV12 /
 // I420 frames (src: the Y plane, yuv: the chroma planes; a Y byte and the chroma pair under it per pixel, byte loads); 22 = packed
 // YUV 4:2:2 frames (yuv: P422Sel, the byte permute to Y0 U Y1 V; a pixel's macropixel as one aligned dword load); 23 = planar
-// frames (melf_process_planes*; yuv: PlanarPlanes, where the B, G and R planes start in a frame; three byte loads per pixel).
+// frames (melf_process_planes*; yuv: PlanarPlanes, where the B, G and R planes start in a frame; three byte loads per pixel);
+// 24 = planar / semi-planar YUV of any subsampling (melf_process_yuv_planar*; yuv: YuvPlanarPlanes; a Y byte and the chroma bytes
+// at (y >> sub_y, x >> sub_x) per pixel, byte loads: the shifts and the sample step are wave-uniform scalars).
 struct NoYuv {};
 struct P422Sel { uint32_t sel; };
 template <int PX, class YUV = NoYuv>
 __device__ __forceinline__ void match_tile(MatchSrc src, MatchGeom g, const uint32_t* __restrict__ tplT,
                                            int rh, int rw, int nrb, float* __restrict__ result_map,
                                            MatchPartial* __restrict__ partials, int nparts, YUV yuv = YUV{},
-                                           [[maybe_unused]] YuvMatrix mx = YuvMatrix{} /* PX 20 .. 22: the frames' colour conversion */)
+                                           [[maybe_unused]] YuvMatrix mx = YuvMatrix{} /* PX 20 .. 22, 24: the frames' colour conversion */)
 {
     constexpr int R = MATCH_R;
     extern __shared__ uint32_t lds[];
@@ -61,6 +63,10 @@ __device__ __forceinline__ void match_tile(MatchSrc src, MatchGeom g, const uint
             urow = img + (size_t)yuv.u_off + (size_t)((src.y0 + y) >> 1) * (size_t)yuv.c_pitch;
             vrow = img + (size_t)yuv.v_off + (size_t)((src.y0 + y) >> 1) * (size_t)yuv.c_pitch;
         }
+        if constexpr (PX == 24) {
+            urow = img + (size_t)yuv.u_off + (size_t)((src.y0 + y) >> yuv.sub_y) * (size_t)yuv.c_pitch;
+            vrow = img + (size_t)yuv.v_off + (size_t)((src.y0 + y) >> yuv.sub_y) * (size_t)yuv.c_pitch;
+        }
         for (int c4 = lane; c4 < g.ldsw; c4 += 64) {
             uint32_t packed = 0;
             if (y < src.rows) {
@@ -71,6 +77,10 @@ __device__ __forceinline__ void match_tile(MatchSrc src, MatchGeom g, const uint
                     if (x < src.cols) {
                         if constexpr (PX == 20 || PX == 21) {
                             const int cx = (src.x0 + x) >> 1, ci = PX == 20 ? 2 * cx : cx;
+                            const YuvChroma c = yuv_chroma(urow[ci], vrow[ci], mx);
+                            v = (uint32_t)yuv_lightness(prow[src.x0 + x], yuv_cmax(c), yuv_cmin(c), mx);
+                        } else if constexpr (PX == 24) {
+                            const int ci = ((src.x0 + x) >> yuv.sub_x) << (yuv.c_step - 1);
                             const YuvChroma c = yuv_chroma(urow[ci], vrow[ci], mx);
                             v = (uint32_t)yuv_lightness(prow[src.x0 + x], yuv_cmax(c), yuv_cmin(c), mx);
                         } else if constexpr (PX == 22) {
@@ -211,6 +221,14 @@ __global__ __launch_bounds__(256) void k_planar_match(MatchSrc src, PlanarPlanes
     match_tile<23, PlanarPlanes>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts, planes);
 }
 
+// planar / semi-planar YUV of any subsampling (melf_process_yuv_planar*): the dot4 matcher with a Y byte and two chroma bytes per pixel
+__global__ __launch_bounds__(256) void k_yp_match(MatchSrc src, YuvPlanarPlanes yuv, YuvMatrix mx, MatchGeom g, const uint32_t* __restrict__ tplT,
+                                                    int rh, int rw, int nrb, float* __restrict__ result_map,
+                                                    MatchPartial* __restrict__ partials, int nparts)
+{
+    match_tile<24, YuvPlanarPlanes>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts, yuv, mx);
+}
+
 int match_parts(const MatchGeom& g, int rows, int cols)
 {
     const int rh = rows - g.th + 1, rw = cols - g.tw + 1;
@@ -229,7 +247,10 @@ void launch_match(const MatchSrc& src, const FrameLayout& lay, int n, const Matc
     if (nparts_out) *nparts_out = nparts;
     const size_t shmem = (size_t)g.lds_rows * g.ldsw * sizeof(uint32_t);
     dim3 grid(nparts, n), block(256);
-    if (pix == PIX_PLANAR)
+    if (pix == PIX_YUVP)
+        hipLaunchKernelGGL(k_yp_match, grid, block, shmem, stream, src, lay.yuvp, *lay.mx, g, d_tplT, rh, rw, nrb, d_result_map,
+                           d_partials, nparts);
+    else if (pix == PIX_PLANAR)
         hipLaunchKernelGGL(k_planar_match, grid, block, shmem, stream, src, lay.planes, g, d_tplT, rh, rw, nrb, d_result_map,
                            d_partials, nparts);
     else if (pix_p422(pix))

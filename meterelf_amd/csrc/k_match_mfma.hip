@@ -118,6 +118,35 @@ __global__ __launch_bounds__(256) void k_planar_lplane(MatchSrc src, PlanarPlane
 }
 #undef MELF_PLANAR_BODY
 
+// NB consecutive bytes from byte o of the buffer at `base` (o - m >= 0: the caller has checked it; m = the byte phase of base + o),
+// as aligned dwords shifted into place by v_alignbit: out holds the bytes from its byte 0 on.  (NB + 3) / 4 + 1 dwords are loaded
+// where the last output dword can need a byte of it, one fewer where it cannot (NB % 4 == 1).
+template <int NB>
+__device__ __forceinline__ void load_window(const uint8_t* base, size_t o, uint32_t m, uint32_t (&out)[(NB + 3) / 4])
+{
+    constexpr int ND = (NB + 3) / 4, NL = (NB + 6) / 4;
+    const uint32_t* q = (const uint32_t*)(base + (o - m));
+    uint32_t d[NL];
+#pragma unroll
+    for (int i = 0; i < NL; ++i) d[i] = q[i];
+#pragma unroll
+    for (int i = 0; i < ND; ++i) out[i] = __builtin_amdgcn_alignbit(d[i + 1 < NL ? i + 1 : i], d[i], m * 8u);
+}
+
+// Planar / semi-planar YUV frames of any subsampling (melf_process_yuv_planar*): src is the Y plane, yuv the chroma.  One
+// instantiation per form of the chroma fetch: SUBX = log2 of the horizontal subsampling, CSTEP = bytes between the samples of a
+// chroma plane (2: interleaved pairs); sub_y and the order of a pair's bytes are runtime, wave-uniform values.  L straight from
+// Y, U, V as in k_lplane_yuv.
+#define MELF_YUVP_BODY
+template <int SUBX, int CSTEP>
+__global__ __launch_bounds__(256) void k_yp_lplane(MatchSrc src, YuvPlanarPlanes yuv, YuvMatrix mx, int nframes, int nkb, int rows_pad, int tw, int rwp, int pairs,
+                                                     int8_t* __restrict__ Lg, uint16_t* __restrict__ R)
+{
+    constexpr int PX = 24;
+#include "prep_lplane_body.inc"
+}
+#undef MELF_YUVP_BODY
+
 // ---------------------------------------------------------------------------
 // k_match_mfma
 // ---------------------------------------------------------------------------
@@ -816,9 +845,19 @@ void launch_match_prep(const MatchSrc& src, const FrameLayout& lay, int n, int g
         (void)hipFuncSetAttribute((const void*)k_lplane_yuv<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute((const void*)k_p422_lplane, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute((const void*)k_planar_lplane, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_yp_lplane<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_yp_lplane<0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_yp_lplane<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_yp_lplane<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         attr_set[dev] = true;
     }
-    if (pix == PIX_PLANAR) hipLaunchKernelGGL(k_planar_lplane, grid, block, pre_bytes, stream, src, lay.planes, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    if (pix == PIX_YUVP) {
+        const YuvPlanarPlanes& yp = lay.yuvp;
+        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, pre_bytes, stream, src, yp, *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r); };
+        if (yp.sub_x == 0) { if (yp.c_step == 1) go(k_yp_lplane<0, 1>); else go(k_yp_lplane<0, 2>); }
+        else { if (yp.c_step == 1) go(k_yp_lplane<1, 1>); else go(k_yp_lplane<1, 2>); }
+    }
+    else if (pix == PIX_PLANAR) hipLaunchKernelGGL(k_planar_lplane, grid, block, pre_bytes, stream, src, lay.planes, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else if (pix_p422(pix)) hipLaunchKernelGGL(k_p422_lplane, grid, block, pre_bytes, stream, src, p422_sel(pix), *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else if (pix == PIX_NV12) hipLaunchKernelGGL((k_lplane_yuv<false>), grid, block, pre_bytes, stream, src, lay.yuv, *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else if (pix == PIX_I420) hipLaunchKernelGGL((k_lplane_yuv<true>), grid, block, pre_bytes, stream, src, lay.yuv, *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);

@@ -75,4 +75,36 @@ void launch_p422_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int 
     }
 }
 
+// Planar / semi-planar YUV of any subsampling -> BGR alone: the stage kernel behind melf_yuv_planar_to_bgr.  One thread per pixel:
+// its Y byte and the chroma bytes at (y >> sub_y, x >> sub_x), the address formula of include/meterelf_hip.h as it stands (sub_x,
+// sub_y and c_step are runtime scalars here), three bytes out.  This kernel pins the addressing and the arithmetic for every
+// (Y, U, V) at every position inside a chroma block; like k_yuv2bgr it is no hot path.
+__global__ __launch_bounds__(256) void k_yp_to_bgr(const uint8_t* __restrict__ src, int H, int W, int y_pitch, size_t frame_stride,
+                                                     YuvPlanarPlanes yp, YuvMatrix mx, uint8_t* __restrict__ dst)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.z;
+    if (x >= W) return;
+    const uint8_t* frame = src + (size_t)f * frame_stride;
+    const size_t cx = (size_t)(x >> yp.sub_x) * (size_t)yp.c_step;
+    for (int y = blockIdx.y; y < H; y += gridDim.y) {
+        const size_t co = (size_t)(y >> yp.sub_y) * (size_t)yp.c_pitch + cx;
+        const YuvChroma c = yuv_chroma(frame[(size_t)yp.u_off + co], frame[(size_t)yp.v_off + co], mx);
+        const uint32_t p = yuv_bgr(frame[(size_t)y * (size_t)y_pitch + (size_t)x], c, mx);
+        uint8_t* o = dst + (((size_t)f * H + y) * (size_t)W + (size_t)x) * 3;
+        o[0] = (uint8_t)p; o[1] = (uint8_t)(p >> 8); o[2] = (uint8_t)(p >> 16);
+    }
+}
+
+void launch_yuvp_to_bgr(const uint8_t* d_src, int n, int H, int W, int y_pitch, size_t frame_stride, const YuvPlanarPlanes& yp,
+                        const YuvMatrix& mx, uint8_t* d_dst, hipStream_t stream)
+{
+    // at most 65 535 frames per launch (grid z); a workgroup row takes every 65 535th image row (grid y)
+    for (int f0 = 0; f0 < n; f0 += 65535) {
+        const int m = n - f0 < 65535 ? n - f0 : 65535;
+        dim3 grid((W + 255) / 256, H < 65535 ? H : 65535, m), block(256);
+        hipLaunchKernelGGL(k_yp_to_bgr, grid, block, 0, stream, d_src + (size_t)f0 * frame_stride, H, W, y_pitch, frame_stride, yp, mx,
+                           d_dst + (size_t)f0 * H * W * 3);
+    }
+}
+
 }  // namespace melf

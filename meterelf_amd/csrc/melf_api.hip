@@ -1168,7 +1168,7 @@ static int process_batch_on(melf_ctx* c, const void* d_frames, const FrameBatch&
 // the entry points on frames in HBM after their argument checks: the lane logic
 static int batch_dev(melf_ctx* c, const void* d_frames, const FrameBatch& b, void* d_results, melf_result* out_host, void* stream_);
 
-// The four descriptor checks (the C ABI's melf_*_frames): every entry point that takes the descriptor starts with its check, which
+// The five descriptor checks (the C ABI's melf_*_frames): every entry point that takes the descriptor starts with its check, which
 // leaves the batch in *b; n == 0 passes whatever the frames pointer.
 
 // melf_frames (melf_process_frames*)
@@ -1249,6 +1249,47 @@ static int check_yuv422(const melf_ctx* c, const void* frames, const melf_yuv422
     return MELF_SUCCESS;
 }
 
+// melf_yuv_planar_frames (melf_process_yuv_planar*, melf_yuv_planar_to_bgr): base, frame_stride and row_stride describe the Y plane;
+// the extent reaches to the last sample of the frame's last plane
+static int check_yuv_planar(const melf_ctx* c, const void* frames, const melf_yuv_planar_frames* f, FrameBatch* b)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    if (!f) return fail(MELF_ERR_INVALID, "planar YUV frame descriptor is NULL");
+    if (f->reserved != 0) return fail(MELF_ERR_INVALID, "reserved field of the planar YUV frame descriptor is not 0");
+    if ((f->sub_x != 0 && f->sub_x != 1) || (f->sub_y != 0 && f->sub_y != 1))
+        return fail(MELF_ERR_INVALID, "sub_x and sub_y must be 0 or 1 (log2 of the chroma subsampling)");
+    if (f->c_step != 1 && f->c_step != 2) return fail(MELF_ERR_INVALID, "c_step must be 1 (planar) or 2 (semi-planar)");
+    const YuvMatrix* mx = yuv_matrix(f->matrix);
+    if (!mx)
+        return fail(MELF_ERR_INVALID, "unknown YUV matrix (accepted: 0 BT.601 limited, 2 BT.601 full, 3 BT.709 limited, 4 BT.709 full)");
+    if (f->n < 0 || f->H <= 0 || f->W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
+    if (f->sub_x && (f->W & 1)) return fail(MELF_ERR_INVALID, "horizontally subsampled chroma (sub_x) needs an even width");
+    if (f->sub_y && (f->H & 1)) return fail(MELF_ERR_INVALID, "vertically subsampled chroma (sub_y) needs an even height");
+    if (f->u_offset < 0 || f->v_offset < 0) return fail(MELF_ERR_INVALID, "negative chroma offset");
+    const bool semi = f->c_step == 2;
+    if (semi && f->u_offset - f->v_offset != 1 && f->v_offset - f->u_offset != 1)
+        return fail(MELF_ERR_INVALID, "c_step 2 (semi-planar) needs adjacent u_offset and v_offset");
+    if (f->y_pitch < f->W || f->y_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "y_pitch smaller than a row (or too large)");
+    const int64_t cw = (int64_t)(f->W >> f->sub_x) * f->c_step, ch = f->H >> f->sub_y;   // bytes of a chroma row (semi-planar: of both), rows
+    if (f->c_pitch < cw || f->c_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "c_pitch smaller than a chroma row (or too large)");
+    const int64_t y_end = (int64_t)(f->H - 1) * f->y_pitch + f->W;
+    const int64_t c_lo = f->u_offset < f->v_offset ? f->u_offset : f->v_offset, c_hi = f->u_offset < f->v_offset ? f->v_offset : f->u_offset;
+    const int64_t c_len = (ch - 1) * f->c_pitch + (semi ? cw - 1 : cw);   // bytes from a plane's offset to its last sample
+    if (c_hi > INT64_MAX - c_len) return fail(MELF_ERR_INVALID, "chroma offset too large");
+    // (by spans, first to last sample: chroma kept inside the Y rows' padding, or U and V rows side by side in one pitch, do not
+    // overlap sample by sample but are not taken -- the header states the span rule)
+    if (c_lo < y_end) return fail(MELF_ERR_INVALID, "a chroma offset lies inside the Y plane's span (first to last sample): spans may not overlap");
+    if (!semi && c_hi - c_lo < c_len)
+        return fail(MELF_ERR_INVALID, "the spans (first to last sample) of the two chroma planes overlap: U and V rows sharing one pitch are not taken");
+    const int64_t c_end = c_hi + c_len;
+    if (f->frame_stride < c_end) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
+    const YuvPlanarPlanes yp = {f->u_offset, f->v_offset, (int)f->c_pitch, f->sub_x, f->sub_y, f->c_step};
+    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->y_pitch, FrameLayout::yuv_planar(yp, *mx, (size_t)c_end)};
+    if (f->n == 0) return MELF_SUCCESS;
+    if (!frames) return fail(MELF_ERR_INVALID, "frames pointer is NULL");
+    return MELF_SUCCESS;
+}
+
 // melf_planar_frames (melf_process_planes*): the extent reaches to the last sample of the frame's last plane
 static int check_planes(const melf_ctx* c, const void* frames, const melf_planar_frames* f, FrameBatch* b)
 {
@@ -1312,6 +1353,15 @@ extern "C" int melf_process_yuv422_dev(melf_ctx* c, const void* d_frames, const 
 {
     FrameBatch b;
     if (int rc = check_yuv422(c, d_frames, f, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return batch_dev(c, d_frames, b, d_results, out_host, stream_);
+}
+
+extern "C" int melf_process_yuv_planar_dev(melf_ctx* c, const void* d_frames, const melf_yuv_planar_frames* f, void* d_results,
+                                           melf_result* out_host, void* stream_)
+{
+    FrameBatch b;
+    if (int rc = check_yuv_planar(c, d_frames, f, &b)) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return batch_dev(c, d_frames, b, d_results, out_host, stream_);
 }
@@ -1619,6 +1669,60 @@ static int host_p422(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& 
     });
 }
 
+// Planar / semi-planar YUV of any subsampling: the staged frame is a small frame of the same layout -- the same subsampling, sample
+// step and order of U and V --, the Y rows of the crop with its origin rounded down (and its far corner up) to whole chroma blocks
+// (1 << sub_x by 1 << sub_y) and the chroma rows under them; the kernels read it with the rectangle shifted by the rounding (0 or 1
+// pixel each way), under the caller's matrix.  Work items: the Y rows in blocks of 32, and the chroma rows as one more.
+static int host_yuv_planar(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host)
+{
+    Crop cr;
+    if (int rc = host_crop(c, b, out_host, &cr)) return rc;
+    const YuvPlanarPlanes src_planes = b.lay.yuvp;
+    const int sx = src_planes.sub_x, sy = src_planes.sub_y, step = src_planes.c_step;
+    const bool semi = step == 2;
+    const size_t y_pitch = (size_t)b.row_stride;
+    const int bx = 1 << sx, by = 1 << sy;
+    const int ex0 = cr.x0 & ~(bx - 1), ey0 = cr.y0 & ~(by - 1);
+    // the small frame (whole blocks, inside the frame: W and H are whole blocks)
+    const int sw = ((cr.x1 + bx - 1) & ~(bx - 1)) - ex0, sh = ((cr.y1 + by - 1) & ~(by - 1)) - ey0;
+    const int crows = sh >> sy;                                      // chroma rows of the small frame
+    const size_t ypitch = pitch64((size_t)sw);
+    const size_t cbytes = (size_t)(sw >> sx) * (size_t)step;         // bytes of a chroma row (semi-planar: of both)
+    const size_t cpitch = pitch64(cbytes);
+    const size_t c0 = (size_t)sh * ypitch;                           // the first chroma byte of the small frame
+    const int64_t src_lo = src_planes.u_off < src_planes.v_off ? src_planes.u_off : src_planes.v_off;
+    YuvPlanarPlanes sp_planes = src_planes;
+    sp_planes.c_pitch = (int)cpitch;
+    if (semi) {
+        sp_planes.u_off = (int64_t)c0 + (src_planes.u_off - src_lo);
+        sp_planes.v_off = (int64_t)c0 + (src_planes.v_off - src_lo);
+    } else {
+        sp_planes.u_off = (int64_t)c0;
+        sp_planes.v_off = (int64_t)(c0 + (size_t)crows * cpitch);
+    }
+    const size_t crop_stride = c0 + (size_t)crows * cpitch * (semi ? 1 : 2) + 128;
+    const int rblocks = (sh + 31) / 32;
+    const StagePlan sp = {{0, sh, sw, crop_stride, (int)ypitch, FrameLayout::yuv_planar(sp_planes, *b.lay.mx, crop_stride)},
+                          {cr.x0 - ex0, cr.y0 - ey0, cr.x0 - ex0 + cr.cols, cr.y0 - ey0 + cr.rows}, rblocks + 1};
+    return stage_host_frames(c, frames_host, b.n, b.frame_stride, sp, out_host, [=](const uint8_t* frame, uint8_t* small, int part) {
+        if (part < rblocks) {
+            const int r0 = part * 32, r1 = r0 + 32 < sh ? r0 + 32 : sh;
+            for (int y = r0; y < r1; ++y) memcpy(small + (size_t)y * ypitch, frame + (size_t)(ey0 + y) * y_pitch + ex0, (size_t)sw);
+        } else {
+            const size_t cx = (size_t)(ex0 >> sx) * (size_t)step;
+            for (int y = 0; y < crows; ++y) {
+                const size_t so = (size_t)((ey0 >> sy) + y) * (size_t)src_planes.c_pitch + cx;
+                if (semi) {
+                    memcpy(small + c0 + (size_t)y * cpitch, frame + (size_t)src_lo + so, cbytes);
+                } else {
+                    memcpy(small + (size_t)sp_planes.u_off + (size_t)y * cpitch, frame + (size_t)src_planes.u_off + so, cbytes);
+                    memcpy(small + (size_t)sp_planes.v_off + (size_t)y * cpitch, frame + (size_t)src_planes.v_off + so, cbytes);
+                }
+            }
+        }
+    });
+}
+
 // Planar: the staged frame is a small planar frame, the crop's rows of the B, the G and the R plane, one plane after the other,
 // which the kernels read with the rectangle at its origin.  Work items: the crop's rows of one plane in blocks of 32.
 static int host_planes(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host)
@@ -1675,6 +1779,14 @@ extern "C" int melf_process_yuv422(melf_ctx* c, const void* frames_host, const m
     return host_p422(c, (const uint8_t*)frames_host, b, out_host);
 }
 
+extern "C" int melf_process_yuv_planar(melf_ctx* c, const void* frames_host, const melf_yuv_planar_frames* f, melf_result* out_host)
+{
+    FrameBatch b;
+    if (int rc = check_yuv_planar(c, frames_host, f, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return host_yuv_planar(c, (const uint8_t*)frames_host, b, out_host);
+}
+
 extern "C" int melf_process_planes(melf_ctx* c, const void* frames_host, const melf_planar_frames* f, melf_result* out_host)
 {
     FrameBatch b;
@@ -1684,7 +1796,7 @@ extern "C" int melf_process_planes(melf_ctx* c, const void* frames_host, const m
 }
 
 // ---------------------------------------------------------- stage entries ----
-// melf_yuv_to_bgr / melf_yuv422_to_bgr after their checks: the frames up, the conversion kernel alone, n packed H x W BGR frames down
+// melf_yuv_to_bgr / melf_yuv422_to_bgr / melf_yuv_planar_to_bgr after their checks: the frames up, the conversion kernel alone, n packed H x W BGR frames down
 static int to_bgr(melf_ctx* c, const void* frames_host, const FrameBatch& b, uint8_t* bgr_out_host)
 {
     if (!bgr_out_host) return fail(MELF_ERR_INVALID, "bgr_out_host is NULL");
@@ -1693,7 +1805,9 @@ static int to_bgr(melf_ctx* c, const void* frames_host, const FrameBatch& b, uin
     if (int rc = grow(&c->d_stage_in, &c->stage_in_cap, in_bytes)) return rc;
     if (int rc = grow(&c->d_stage_out, &c->stage_out_cap, out_bytes)) return rc;
     HIP_TRY(hipMemcpyAsync(c->d_stage_in, frames_host, in_bytes, hipMemcpyHostToDevice, c->stream));
-    if (pix_yuv(b.lay.pix))
+    if (b.lay.pix == PIX_YUVP)
+        launch_yuvp_to_bgr(c->d_stage_in, b.n, b.H, b.W, b.row_stride, b.frame_stride, b.lay.yuvp, *b.lay.mx, c->d_stage_out, c->stream);
+    else if (pix_yuv(b.lay.pix))
         launch_yuv2bgr(c->d_stage_in, b.lay.pix, b.n, b.H, b.W, b.row_stride, b.frame_stride, b.lay.yuv, *b.lay.mx, c->d_stage_out, c->stream);
     else
         launch_p422_to_bgr(c->d_stage_in, b.lay.pix, b.n, b.H, b.W, b.row_stride, b.frame_stride, *b.lay.mx, c->d_stage_out, c->stream);
@@ -1707,6 +1821,14 @@ extern "C" int melf_yuv422_to_bgr(melf_ctx* c, const void* frames_host, const me
 {
     FrameBatch b;
     if (int rc = check_yuv422(c, frames_host, f, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return to_bgr(c, frames_host, b, bgr_out_host);
+}
+
+extern "C" int melf_yuv_planar_to_bgr(melf_ctx* c, const void* frames_host, const melf_yuv_planar_frames* f, uint8_t* bgr_out_host)
+{
+    FrameBatch b;
+    if (int rc = check_yuv_planar(c, frames_host, f, &b)) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return to_bgr(c, frames_host, b, bgr_out_host);
 }

@@ -84,6 +84,19 @@ constexpr int PIX_PLANAR = 32;
 struct PlanarPlanes {
     int64_t b_off, g_off, r_off;  // bytes from a frame's first byte to the first sample of its B / G / R plane
 };
+// Planar and semi-planar YUV frames of any of the four chroma subsamplings (melf_process_yuv_planar*): the launch's pix.  The Y
+// plane is described like a single-channel image (base, frame_stride, row_stride of MatchSrc / DialsSrc, any byte alignment), the
+// chroma by YuvPlanarPlanes: U of pixel (x, y) at frame + u_off + (y >> sub_y) * c_pitch + (x >> sub_x) * c_step, V the same from
+// v_off.  c_step 2: the two are the bytes of one interleaved pair (|u_off - v_off| == 1; which comes first is a runtime, wave-uniform
+// matter).  A by-value kernel argument of its own: YuvPlanes and the kernels that take it stay as they are.  The hot kernels are
+// instantiated per (sub_x, c_step) -- the four forms of the chroma fetch -- and take sub_y as the runtime shift of the chroma row.
+constexpr int PIX_YUVP = 40;
+struct YuvPlanarPlanes {
+    int64_t u_off, v_off;  // bytes from a frame's first byte to its first U / V sample
+    int c_pitch;           // bytes between chroma rows
+    int sub_x, sub_y;      // log2 of the chroma subsampling, 0 or 1 each
+    int c_step;            // bytes from one sample of a chroma plane to the next in its row: 1 planar, 2 semi-planar
+};
 
 // How the frames of one launch lie in memory, beside the base, the strides and the rectangle of MatchSrc / DialsSrc: the pixel
 // layout and what goes with it.  Host side only: the launchers hand the kernels the members by value.  Made by the makers below
@@ -92,8 +105,9 @@ struct FrameLayout {
     int pix;
     YuvPlanes yuv;         // pix_yuv(pix): the chroma planes
     PlanarPlanes planes;   // PIX_PLANAR: where the three planes start
-    const YuvMatrix* mx;   // pix_yuv(pix), pix_p422(pix): the frames' colour conversion, never NULL there
+    const YuvMatrix* mx;   // pix_yuv(pix), pix_p422(pix), PIX_YUVP: the frames' colour conversion, never NULL there
     size_t extent;         // bytes a kernel may read of the LAST frame, from its first byte (the others: frame_stride)
+    YuvPlanarPlanes yuvp;  // PIX_YUVP: the chroma planes and their subsampling (mx: the conversion, as above)
 
     static FrameLayout packed(int pix /* MELF_PIX_* */, size_t extent) { return FrameLayout{pix, {}, {}, nullptr, extent}; }
     static FrameLayout yuv420(int pix /* PIX_NV12, PIX_I420 */, const YuvPlanes& yp, const YuvMatrix& mx, size_t extent)
@@ -103,6 +117,10 @@ struct FrameLayout {
     static FrameLayout yuv422(int pix /* PIX_YUYV, PIX_UYVY, PIX_YVYU */, const YuvMatrix& mx, size_t extent)
     {
         return FrameLayout{pix, {}, {}, &mx, extent};
+    }
+    static FrameLayout yuv_planar(const YuvPlanarPlanes& yp, const YuvMatrix& mx, size_t extent)
+    {
+        return FrameLayout{PIX_YUVP, {}, {}, &mx, extent, yp};
     }
     static FrameLayout planar(const PlanarPlanes& pl, size_t extent) { return FrameLayout{PIX_PLANAR, {}, pl, nullptr, extent}; }
     static FrameLayout plane(size_t extent) { return FrameLayout{PIX_PLANE, {}, {}, nullptr, extent}; }
@@ -250,6 +268,10 @@ size_t launch_stream_probe(const void* d_in, size_t in_bytes, void* d_out, int c
 // BGR frames
 void launch_yuv2bgr(const uint8_t* d_src, int pix, int n, int H, int W, int y_pitch, size_t frame_stride, const YuvPlanes& yuv,
                     const YuvMatrix& mx, uint8_t* d_dst, hipStream_t stream);
+
+// the same for planar / semi-planar YUV of any subsampling (melf_yuv_planar_to_bgr): the Y plane at d_src (y_pitch, frame_stride)
+void launch_yuvp_to_bgr(const uint8_t* d_src, int n, int H, int W, int y_pitch, size_t frame_stride, const YuvPlanarPlanes& yp,
+                        const YuvMatrix& mx, uint8_t* d_dst, hipStream_t stream);
 
 // the same for packed YUV 4:2:2 (melf_yuv422_to_bgr): n frames at d_src (row_pitch, frame_stride), pix PIX_YUYV / _UYVY / _YVYU
 void launch_p422_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int row_pitch, size_t frame_stride, const YuvMatrix& mx,

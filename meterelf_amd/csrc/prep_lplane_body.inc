@@ -16,6 +16,13 @@
 //       aligned dwords per plane, shifted by v_alignbit at that plane's own byte phase (the three phases differ when offsets and
 //       pitch are arbitrary).  The aligned window reaches up to 3 bytes to the left of the lane's first sample and up to 35 behind it:
 //       it must not start before the caller's base nor end behind the buffer, or the lane takes byte loads.
+//   With MELF_YUVP_BODY defined instead (k_yp_lplane): PX 24 = planar / semi-planar YUV frames of any subsampling
+//       (melf_process_yuv_planar*), the chroma in `yuv` (YuvPlanarPlanes), any byte alignment; SUBX (0, 1) and CSTEP (1, 2) are
+//       compile-time: the four forms of the chroma fetch.  The even-pixel window of 34 Y bytes as for PX 20 / 21; the chroma under it
+//       is 34 >> SUBX samples: CSTEP 1 that many bytes of each plane, at each plane's own byte phase (load_window, k_match_mfma.hip:
+//       aligned dwords and v_alignbit, as for PX 23), CSTEP 2 twice as many interleaved bytes from the lower of the two offsets, one
+//       runtime v_perm_b32 per dword putting U before V.  sub_y is the scalar shift of the chroma row.  No window may start before
+//       the caller's base nor end behind the buffer, or the lane takes byte loads of the crop's own samples.
     constexpr int PB = PX == 4 ? 4 : 3;         // bytes per pixel of the frame reads
     constexpr int WIN = PX == 4 ? 128 : 100;    // bytes a lane's 32-pixel load window spans
     __shared__ __attribute__((aligned(16))) uint32_t tile[8 * 2 * 32 * 4];  // [kb][h][n][16 B], one chunk of 8 blocks
@@ -43,6 +50,25 @@
     const int xodd = src.x0 & 1;
     const bool rows_safe = (size_t)min(grp * 32 + 31, nframes - 1) * src.frame_stride + (size_t)(src.y0 + y) * src.row_stride +
                            (size_t)((src.x0 & ~1) + 32 * (nkb - 1)) * 2 + 68 <= src.readable;
+#elif defined(MELF_YUVP_BODY)
+    (void)PB; (void)WIN;
+    // (the same for the windows of a lane of these frames: 40 bytes from the Y sample of its even pixel, CB + 3 bytes rounded up to
+    // dwords from its first chroma sample in each plane (CSTEP 1) or in the interleaved plane (CSTEP 2) -- and for their first dword:
+    // with a base that is not 4-byte aligned the aligned window of the buffer's very first samples would start before it)
+    constexpr int NC = 34 >> SUBX;                   // chroma samples under a window
+    constexpr int CB = NC * CSTEP;                   // bytes of a chroma window
+    constexpr int CWIN = (CB + 6) / 4 * 4;           // bytes its aligned dwords span
+    const int xodd = src.x0 & 1;
+    const uint32_t yp_bm = (uint32_t)((size_t)src.base & 3);
+    const bool yp_swap = yuv.v_off < yuv.u_off;      // CSTEP 2: V before U in a pair (NV21, NV61, NV42)
+    const size_t yp_c0 = (size_t)min(yuv.u_off, yuv.v_off), yp_c1 = (size_t)max(yuv.u_off, yuv.v_off);
+    const size_t yp_first = (size_t)grp * 32 * src.frame_stride, yp_last = (size_t)min(grp * 32 + 31, nframes - 1) * src.frame_stride;
+    const size_t yp_yrow = (size_t)(src.y0 + y) * src.row_stride;
+    const size_t yp_crow = (size_t)((src.y0 + y) >> yuv.sub_y) * (size_t)yuv.c_pitch;
+    const int yp_x0 = src.x0 & ~1, yp_xlast = yp_x0 + 32 * (nkb - 1);
+    const bool rows_safe = (yp_bm == 0 || (yp_first + yp_yrow + (size_t)yp_x0 >= 3 && yp_first + yp_c0 + yp_crow + (size_t)((yp_x0 >> SUBX) * CSTEP) >= 3)) &&
+                           yp_last + yp_yrow + (size_t)yp_xlast + 40 <= src.readable &&
+                           yp_last + (CSTEP == 2 ? yp_c0 : yp_c1) + yp_crow + (size_t)((yp_xlast >> SUBX) * CSTEP) + CWIN <= src.readable;
 #elif defined(MELF_PLANAR_BODY)
     (void)PB; (void)WIN;
     // (the same for the three 36-byte windows of a planar lane, and for their first dword: with a base that is not 4-byte aligned
@@ -175,6 +201,66 @@
                         const uint32_t m = __builtin_amdgcn_perm(0u, ((const uint32_t*)prow)[fx >> 1], psel);
                         const YuvChroma c = yuv_chroma((int)((m >> 8) & 255u), (int)(m >> 24), mx);
                         const int L = yuv_lightness((int)((fx & 1 ? m >> 16 : m) & 255u), yuv_cmax(c), yuv_cmin(c), mx);
+                        w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
+                    }
+                }
+            } else
+#elif defined(MELF_YUVP_BODY)
+            if (PX == 24) {
+                const int xs = (src.x0 + xbeg) & ~1;   // the window's first pixel (even)
+                const size_t fo = (size_t)f * src.frame_stride;
+                const size_t yo = fo + yp_yrow + (size_t)xs;
+                const size_t cx = (size_t)((xs >> SUBX) * CSTEP);
+                const size_t uo = fo + (CSTEP == 2 ? yp_c0 : (size_t)yuv.u_off) + yp_crow + cx;   // CSTEP 2: the interleaved window
+                const size_t vo = fo + (size_t)yuv.v_off + yp_crow + cx;                          // (CSTEP 1 only)
+                const uint32_t my = (yp_bm + (uint32_t)yo) & 3u, mu = (yp_bm + (uint32_t)uo) & 3u, mv = (yp_bm + (uint32_t)vo) & 3u;
+                // the windows may reach past the crop and the row (never used: masked) but must stay inside the caller's buffer, at its
+                // first bytes as well as at its last
+                if (rows_safe || (yo >= my && uo >= mu && yo - my + 40 <= src.readable && uo - mu + CWIN <= src.readable &&
+                                  (CSTEP == 2 || (vo >= mv && vo - mv + CWIN <= src.readable)))) {
+                    uint32_t ya[9], ua[(NC + 3) / 4], va[(NC + 3) / 4];   // Y, U, V of the window, a sample per byte
+                    load_window<34>(src.base, yo, my, ya);
+                    if constexpr (CSTEP == 2) {
+                        uint32_t ca[(CB + 3) / 4];
+                        load_window<CB>(src.base, uo, mu, ca);
+                        // pairs -> U0 U1 V0 V1 per dword, then the U halves and the V halves of two dwords together
+                        const uint32_t sel = yp_swap ? 0x02000301u : 0x03010200u;
+#pragma unroll
+                        for (int i = 0; i < (CB + 3) / 4; ++i) ca[i] = __builtin_amdgcn_perm(0u, ca[i], sel);
+#pragma unroll
+                        for (int i = 0; i < (NC + 3) / 4; ++i) {
+                            const uint32_t lo = ca[2 * i], hi = 2 * i + 1 < (CB + 3) / 4 ? ca[2 * i + 1] : 0u;
+                            ua[i] = __builtin_amdgcn_perm(hi, lo, 0x05040100u);
+                            va[i] = __builtin_amdgcn_perm(hi, lo, 0x07060302u);
+                        }
+                    } else {
+                        load_window<CB>(src.base, uo, mu, ua);
+                        load_window<CB>(src.base, vo, mv, va);
+                    }
+                    uint32_t wl[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // L' of the window's 34 pixels
+#pragma unroll
+                    for (int j = 0; j < NC; ++j) {
+                        const int U = (int)((ua[j >> 2] >> ((j & 3) * 8)) & 255u), V = (int)((va[j >> 2] >> ((j & 3) * 8)) & 255u);
+                        const YuvChroma c = yuv_chroma(U, V, mx);
+                        const int cmax = yuv_cmax(c), cmin = yuv_cmin(c);
+#pragma unroll
+                        for (int q2 = 0; q2 < (SUBX ? 2 : 1); ++q2) {
+                            const int k = SUBX ? 2 * j + q2 : j;
+                            const int L = yuv_lightness((int)((ya[k >> 2] >> ((k & 3) * 8)) & 255u), cmax, cmin, mx);
+                            wl[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
+                        }
+                    }
+                    // the lane's 32 pixels start at byte xodd of the window
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) w[i] = __builtin_amdgcn_alignbit(wl[i + 1], wl[i], (uint32_t)xodd * 8u);
+                } else {  // first / last bytes of the frame buffer: byte loads, the crop's own samples only
+                    const uint8_t* py = src.base + fo + yp_yrow + (size_t)(src.x0 + xbeg);
+                    const uint8_t* pu = src.base + fo + (size_t)yuv.u_off + yp_crow;
+                    const uint8_t* pv = src.base + fo + (size_t)yuv.v_off + yp_crow;
+                    for (int k = 0; k < npx; ++k) {
+                        const int ci = ((src.x0 + xbeg + k) >> SUBX) * CSTEP;
+                        const YuvChroma c = yuv_chroma(pu[ci], pv[ci], mx);
+                        const int L = yuv_lightness(py[k], yuv_cmax(c), yuv_cmin(c), mx);
                         w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
                     }
                 }

@@ -530,6 +530,26 @@ typedef struct {
     int32_t reserved[6];
 } melf_match_info;
 int melf_ctx_last_match(const melf_ctx* ctx, melf_match_info* out);
+/* Which dial-reader kernel the context's most recent launch ran: the kernel family that reads the frames' layout and NR, the
+ * window rows a lane requests up front -- one of 32, 40, 48, 52, 56, 64, the smallest that holds ws_max, the context's largest
+ * dial window (2 R + 5 rows).  Twelve families times six NR: tests assert the pair, so that every instantiation production can
+ * pick is known to have been the one a parity test launched.  family is -1 and nr 0 before the first launch; a call of more
+ * frames than one launch takes reports its last piece.  Plain fields written by every launch, as for melf_ctx_fused_variant's
+ * last_launch.  Every output pointer may be NULL. */
+enum { MELF_DIALS_HLS = 0,            /* k_dials<true>: packed HLS dials crops (melf_read_dials)            */
+       MELF_DIALS_BGR = 1,            /* k_dials<false>: packed B G R                                       */
+       MELF_DIALS_PACKED3 = 2,        /* k_needles<3>: packed R G B                                         */
+       MELF_DIALS_PACKED4 = 3,        /* k_needles<4>: B G R A / R G B A                                    */
+       MELF_DIALS_NV12 = 4,           /* k_yneedle<false>: melf_process_yuv*, NV12                          */
+       MELF_DIALS_I420 = 5,           /* k_yneedle<true>: melf_process_yuv*, I420 / YV12                    */
+       MELF_DIALS_P422 = 6,           /* k_p422_needle: packed 4:2:2                                        */
+       MELF_DIALS_YP_SUB0_STEP1 = 7,  /* k_yp_needle<0, 1>: melf_process_yuv_planar*, sub_x 0, planar       */
+       MELF_DIALS_YP_SUB0_STEP2 = 8,  /* k_yp_needle<0, 2>: ... sub_x 0, interleaved pairs                  */
+       MELF_DIALS_YP_SUB1_STEP1 = 9,  /* k_yp_needle<1, 1>: ... sub_x 1, planar                             */
+       MELF_DIALS_YP_SUB1_STEP2 = 10, /* k_yp_needle<1, 2>: ... sub_x 1, interleaved pairs                  */
+       MELF_DIALS_PLANAR = 11,        /* k_planar_needle: melf_process_planes*                              */
+       MELF_DIALS_FAMILIES = 12 };
+int melf_ctx_last_dials(const melf_ctx* ctx, int* nr, int* family, int* ws_max);
 /* The tuned kernel's wave layout for a template / searched-image shape and a batch of n images, without a GPU or a
  * context (host logic; kernel = MELF_MATCH_KERNEL_MFMA when the shape belongs to the tuned kernel's class, else the
  * kernel that takes it).  reserved[0] = padded template rows, reserved[1] = L-plane rows per frame group. */

@@ -138,6 +138,10 @@ class HipError(RuntimeError):
     pass
 
 
+# MELF_DIALS_* of include/meterelf_hip.h, by value: the dial reader's kernel families (melf_ctx_last_dials)
+DIALS_FAMILIES = ('hls', 'bgr', 'packed3', 'packed4', 'nv12', 'i420', 'p422', 'yp_sub0_step1', 'yp_sub0_step2', 'yp_sub1_step1',
+                  'yp_sub1_step2', 'planar')
+
 # every symbol include/meterelf_hip.h declares for the product library; DIAG_EXPORTS: what its `#ifdef MELF_DIAG` part adds (the
 # diagnostic build, make -C meterelf_amd/csrc diag, loaded through MELF_LIB_PATH)
 DIAG_EXPORTS = ['melf_stream_probe_dev']
@@ -149,7 +153,7 @@ EXPORTS = [
     'melf_process_yuv422', 'melf_process_yuv422_dev', 'melf_yuv422_to_bgr', 'melf_process_planes', 'melf_process_planes_dev',
     'melf_process_yuv_planar', 'melf_process_yuv_planar_dev', 'melf_yuv_planar_to_bgr',
     'melf_bgr2hls', 'melf_hls_inrange_close', 'melf_hls_inrange_close_dev', 'melf_match_ccoeff',
-    'melf_read_dials', 'melf_aligned_average', 'melf_inrange', 'melf_ctx_fused_table_ties', 'melf_ctx_fused_variant', 'melf_ctx_set_frames_resident', 'melf_ctx_last_match', 'melf_match_layout_query', 'melf_match_gen_plan_query', 'melf_ctx_set_profiling', 'melf_ctx_timings', 'melf_kernel_name',
+    'melf_read_dials', 'melf_aligned_average', 'melf_inrange', 'melf_ctx_fused_table_ties', 'melf_ctx_fused_variant', 'melf_ctx_set_frames_resident', 'melf_ctx_last_match', 'melf_ctx_last_dials', 'melf_match_layout_query', 'melf_match_gen_plan_query', 'melf_ctx_set_profiling', 'melf_ctx_timings', 'melf_kernel_name',
     'melf_jpeg_probe', 'melf_jpeg_probe_batch', 'melf_jpeg_decode_batch', 'melf_jpeg_clean_segment', 'melf_jpeg_process_batch',
     'melf_jpeg_process_files', 'melf_jpeg_process_files_begin', 'melf_jpeg_process_files_end', 'melf_jpeg_files_in_flight_max', 'melf_ctx_files_stats', 'melf_files_open_probe',
 ]
@@ -213,6 +217,7 @@ def lib():
     L.melf_ctx_fused_variant.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.melf_ctx_set_profiling.argtypes = [vp, C.c_int]
     L.melf_ctx_last_match.argtypes = [vp, C.POINTER(MelfMatchInfo)]
+    L.melf_ctx_last_dials.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.melf_match_layout_query.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(MelfMatchInfo)]
     L.melf_match_gen_plan_query.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(MelfMatchInfo), vp, C.c_int,
                                             C.POINTER(C.c_int32)]
@@ -1103,6 +1108,13 @@ class Context:
         mi = MelfMatchInfo()
         check(self._L.melf_ctx_last_match(self._h, C.byref(mi)))
         return _match_info_dict(mi)
+
+    def last_dials(self):
+        """The dial-reader kernel of the most recent launch (melf_ctx_last_dials): dict with 'family' (a name of DIALS_FAMILIES,
+        None before the first launch), 'nr' (window rows a lane requests up front) and 'ws_max' (the context's largest window)."""
+        (nr, fam, ws) = (C.c_int(0), C.c_int(0), C.c_int(0))
+        check(self._L.melf_ctx_last_dials(self._h, C.byref(nr), C.byref(fam), C.byref(ws)))
+        return dict(family=DIALS_FAMILIES[fam.value] if fam.value >= 0 else None, nr=nr.value, ws_max=ws.value)
 
     def set_profiling(self, on):
         check(self._L.melf_ctx_set_profiling(self._h, int(on)))  # False/0 off, True/1 every kernel, 2 only k_match

@@ -376,15 +376,17 @@ static void with_nr(int ws_max, F&& f)
     else f(std::integral_constant<int, 64>{});
 }
 
-void launch_dials(const DialsSrc& src, const FrameLayout& lay, int n, const melf_params& P, const DialGeom* d_geom,
-                  const uint64_t* d_rowmasks, const MatchPartial* d_partials, int nparts, int rw,
-                  melf_result* d_results, hipStream_t stream, int ws_max)
+DialsLaunch launch_dials(const DialsSrc& src, const FrameLayout& lay, int n, const melf_params& P, const DialGeom* d_geom,
+                         const uint64_t* d_rowmasks, const MatchPartial* d_partials, int nparts, int rw,
+                         melf_result* d_results, hipStream_t stream, int ws_max)
 {
+    DialsLaunch ran = {0, -1};   // host-side note of the instantiation picked below (melf_ctx_last_dials)
     dim3 grid(n), block(64 * P.ndials);
     const size_t shmem = (size_t)P.ndials * DIAL_LDS_BYTES;
     const int pix = lay.pix;
     with_nr(ws_max, [&](auto nr) {
         constexpr int NR = decltype(nr)::value;
+        ran.nr = NR;
         // lead: a kernel family's own arguments, which stand between src and P
         auto go = [&](auto kernel, auto... lead) {
             hipLaunchKernelGGL(kernel, grid, block, shmem, stream, src, lead..., P, d_geom, d_rowmasks, d_partials, nparts, rw, d_results);
@@ -395,18 +397,24 @@ void launch_dials(const DialsSrc& src, const FrameLayout& lay, int n, const melf
         };
         if (pix == PIX_YUVP) {
             const YuvPlanarPlanes& yp = lay.yuvp;
-            if (yp.sub_x == 0) { if (yp.c_step == 1) go(k_yp_needle<0, 1, NR>, yp, *lay.mx); else go(k_yp_needle<0, 2, NR>, yp, *lay.mx); }
-            else { if (yp.c_step == 1) go(k_yp_needle<1, 1, NR>, yp, *lay.mx); else go(k_yp_needle<1, 2, NR>, yp, *lay.mx); }
+            if (yp.sub_x == 0) {
+                if (yp.c_step == 1) { ran.family = MELF_DIALS_YP_SUB0_STEP1; go(k_yp_needle<0, 1, NR>, yp, *lay.mx); }
+                else { ran.family = MELF_DIALS_YP_SUB0_STEP2; go(k_yp_needle<0, 2, NR>, yp, *lay.mx); }
+            } else {
+                if (yp.c_step == 1) { ran.family = MELF_DIALS_YP_SUB1_STEP1; go(k_yp_needle<1, 1, NR>, yp, *lay.mx); }
+                else { ran.family = MELF_DIALS_YP_SUB1_STEP2; go(k_yp_needle<1, 2, NR>, yp, *lay.mx); }
+            }
         }
-        else if (pix == PIX_PLANAR) go(k_planar_needle<NR>, lay.planes);
-        else if (pix_p422(pix)) go(k_p422_needle<NR>, p422_sel(pix), *lay.mx);
-        else if (pix == PIX_NV12) go(k_yneedle<false, NR>, lay.yuv, *lay.mx);
-        else if (pix == PIX_I420) go(k_yneedle<true, NR>, lay.yuv, *lay.mx);
-        else if (pix == PIX_PLANE) go(k_dials<true, NR>);
-        else if (pix == MELF_PIX_BGR) go(k_dials<false, NR>);
-        else if (pix == MELF_PIX_RGB) go_needles(k_needles<3, NR>);
-        else go_needles(k_needles<4, NR>);
+        else if (pix == PIX_PLANAR) { ran.family = MELF_DIALS_PLANAR; go(k_planar_needle<NR>, lay.planes); }
+        else if (pix_p422(pix)) { ran.family = MELF_DIALS_P422; go(k_p422_needle<NR>, p422_sel(pix), *lay.mx); }
+        else if (pix == PIX_NV12) { ran.family = MELF_DIALS_NV12; go(k_yneedle<false, NR>, lay.yuv, *lay.mx); }
+        else if (pix == PIX_I420) { ran.family = MELF_DIALS_I420; go(k_yneedle<true, NR>, lay.yuv, *lay.mx); }
+        else if (pix == PIX_PLANE) { ran.family = MELF_DIALS_HLS; go(k_dials<true, NR>); }
+        else if (pix == MELF_PIX_BGR) { ran.family = MELF_DIALS_BGR; go(k_dials<false, NR>); }
+        else if (pix == MELF_PIX_RGB) { ran.family = MELF_DIALS_PACKED3; go_needles(k_needles<3, NR>); }
+        else { ran.family = MELF_DIALS_PACKED4; go_needles(k_needles<4, NR>); }
     });
+    return ran;
 }
 
 }  // namespace melf

@@ -345,6 +345,7 @@ struct melf_ctx {
     hipEvent_t ev_order = nullptr;
     std::vector<TimedEvent> events;
     melf_match_info last_match = {};     // what run_match launched last (melf_ctx_last_match)
+    DialsLaunch last_dials = {0, -1};    // what launch_dials launched last (melf_ctx_last_dials); family -1: nothing yet
     double acc_ms[MELF_K_COUNT] = {0};
     int64_t acc_n[MELF_K_COUNT] = {0};
 };
@@ -944,6 +945,15 @@ extern "C" int melf_ctx_last_match(const melf_ctx* c, melf_match_info* out)
     return MELF_SUCCESS;
 }
 
+extern "C" int melf_ctx_last_dials(const melf_ctx* c, int* nr, int* family, int* ws_max)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    if (nr) *nr = c->last_dials.nr;
+    if (family) *family = c->last_dials.family;
+    if (ws_max) *ws_max = c->ws_max;
+    return MELF_SUCCESS;
+}
+
 extern "C" int melf_ctx_set_profiling(melf_ctx* c, int on)
 {
     if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
@@ -1447,7 +1457,7 @@ static int process_batch_on(melf_ctx* c, const void* d_frames, const FrameBatch&
         }
         {
             KernelTimer t(c, MELF_K_DIALS, st);
-            launch_dials(ds, lay, m, P, c->d_geom, c->d_rowmasks, parts, nparts, rw, res_dev + f0, st, c->ws_max);
+            c->last_dials = launch_dials(ds, lay, m, P, c->d_geom, c->d_rowmasks, parts, nparts, rw, res_dev + f0, st, c->ws_max);
         }
         HIP_TRY(hipGetLastError());
     }
@@ -1994,7 +2004,7 @@ extern "C" int melf_read_dials(melf_ctx* c, const uint8_t* dials_hls_host, int n
     ds.readable = (size_t)n * per;
     {
         KernelTimer t(c, MELF_K_DIALS, c->stream);
-        launch_dials(ds, FrameLayout::plane(per), n, P, c->d_geom, c->d_rowmasks, nullptr, 0, 1, c->d_results, c->stream, c->ws_max);
+        c->last_dials = launch_dials(ds, FrameLayout::plane(per), n, P, c->d_geom, c->d_rowmasks, nullptr, 0, 1, c->d_results, c->stream, c->ws_max);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_host, c->d_results, (size_t)n * sizeof(melf_result), hipMemcpyDeviceToHost, c->stream));

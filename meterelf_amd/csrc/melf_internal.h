@@ -231,9 +231,13 @@ struct DialsSrc {
     size_t readable;       // bytes from `base` the caller guarantees readable: (frames - 1) * frame_stride + the last frame's rows
 };
 
-void launch_dials(const DialsSrc& src, const FrameLayout& lay, int n, const melf_params& P, const DialGeom* d_geom,
-                  const uint64_t* d_rowmasks /* [ndials][3][64] */, const MatchPartial* d_partials,
-                  int nparts, int rw, melf_result* d_results, hipStream_t stream, int ws_max /* largest DialGeom::ws */);
+// which instantiation a launch_dials call picked: its NR (window rows requested up front) and its kernel family (MELF_DIALS_*)
+struct DialsLaunch {
+    int nr, family;
+};
+DialsLaunch launch_dials(const DialsSrc& src, const FrameLayout& lay, int n, const melf_params& P, const DialGeom* d_geom,
+                         const uint64_t* d_rowmasks /* [ndials][3][64] */, const MatchPartial* d_partials,
+                         int nparts, int rw, melf_result* d_results, hipStream_t stream, int ws_max /* largest DialGeom::ws */);
 
 // ---- K1b / HLS --------------------------------------------------------------
 void launch_bgr2hls(const uint8_t* d_src, int rows, int cols, size_t row_stride, int hue_shift,

@@ -28,6 +28,7 @@
 
 #include "melf_device.h"
 #include "melf_internal.h"
+#include "melf_frame_src.h"
 
 namespace melf {
 
@@ -133,43 +134,8 @@ constexpr int RING_CAP_REGS = 1024;   // ... beyond the LDS cache: angles in reg
 constexpr int DIAL_LDS_BYTES = 5120;
 static_assert(DIAL_LIST_CAP * 4 + DIAL_LIST_CAP * 2 <= 4608 && RING_CAP * 8 + RING_CAP * 2 <= DIAL_LDS_BYTES, "dial LDS layout");
 
-// Three bytes of a packed 3-channel pixel with ONE (unaligned) dword load instead of three byte loads: the
-// dword starts one byte early (so it never runs past the buffer's end) except at the buffer's very first pixel.
-// The top byte of the result is unspecified (every user looks at bytes 0..2 only).
-__device__ __forceinline__ uint32_t load_px3(const uint8_t* p, const uint8_t* buffer_start)
-{
-    const uint32_t back = p == buffer_start ? 0u : 1u;
-    uint32_t v;
-    __builtin_memcpy(&v, p - back, 4);
-    return v >> (8u * back);
-}
-
-// The same for a lane's COLUMN of pixels, col + row_off for wave-uniform row offsets: the address arithmetic of
-// load_px3 (a 64-bit multiply-add, a 64-bit compare against the buffer's start, a select) cost ten issue slots per window
-// row and lane, a tenth of the kernel's vector instructions.  Here the direction is fixed per LANE: the dword starts one
-// byte early, except in the lane whose column begins at the buffer's first byte, which reads forward in every row (one
-// byte into its right-hand neighbour: inside the buffer, rows being at least two pixels wide -- melf_ctx_create refuses
-// a one-pixel-wide template).  Per row: one 64-bit add, the load, one shift.
-struct PxColumn {
-    const uint8_t* first;  // col - 1, or col in the lane at the buffer's start
-    uint32_t shift;        // 8, or 0 there
-};
-__device__ __forceinline__ PxColumn px_column(const uint8_t* col, const uint8_t* buffer_start)
-{
-    const bool at_start = col == buffer_start;
-    return PxColumn{at_start ? col : col - 1, at_start ? 0u : 8u};
-}
-__device__ __forceinline__ uint32_t load_px3_row(const PxColumn& c, size_t row_off)
-{
-    asm("" : "+s"(row_off));  // the offset stays a scalar product: otherwise the compiler folds it into one 64-bit vector multiply-add per row
-    uint32_t v;
-    __builtin_memcpy(&v, c.first + row_off, 4);
-    return v >> c.shift;
-}
-
 // packed 16-bit arithmetic on two values per register (v_pk_*_u16)
 typedef unsigned short u16x2v __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b)
 {
     return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u16x2v, a), __builtin_bit_cast(u16x2v, b)));
@@ -246,20 +212,6 @@ extern "C" __attribute__((visibility("default"))) int melf_debug_dials_fine(uint
 // a register-capped match wave of the other caller stream; that variant is gone, and at 128 nothing spills and -- since round 4,
 // tests/test_host_logic.py reads the code object's notes -- the kernel has no private segment at all.)
 constexpr int DIALS_VGPRS = 64;
-// One pixel of the frame: three bytes through load_px3, four as one aligned dword (the 4th byte is never looked at).
-template <int PB>
-__device__ __forceinline__ uint32_t load_px(const uint8_t* p, const uint8_t* buffer_start)
-{
-    if constexpr (PB == 4) return *(const uint32_t*)p;
-    else return load_px3(p, buffer_start);
-}
-template <int PB>
-__device__ __forceinline__ PxColumn px_column_of(const uint8_t* col, const uint8_t* buffer_start)
-{
-    if constexpr (PB == 4) return PxColumn{col, 0u};   // aligned 4-byte pixels: the dword is the pixel
-    else return px_column(col, buffer_start);
-}
-
 // NR: window rows whose pixels a lane requests up front (the largest dial window of the context, rounded up to 8)
 template <bool FROM_HLS, int NR>
 __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_vgpr(DIALS_VGPRS))) void k_dials(DialsSrc src, melf_params P,
@@ -268,9 +220,7 @@ __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_v
                                                               const MatchPartial* __restrict__ partials,
                                                               int nparts, int rw, melf_result* __restrict__ results)
 {
-    constexpr int PB = 3;
-    constexpr bool RT_ORDER = false;
-    const uint32_t bsel = 0u;
+    using Src = DialPacked<3, false, FROM_HLS>; const typename Src::Args sargs{0u};
 #include "k_dials_body.inc"
 }
 
@@ -283,17 +233,13 @@ __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_v
                                                                 const MatchPartial* __restrict__ partials,
                                                                 int nparts, int rw, melf_result* __restrict__ results, int swap_rb)
 {
-    constexpr bool FROM_HLS = false;
-    constexpr int PB = BPP;
-    constexpr bool RT_ORDER = true;
-    const uint32_t bsel = swap_rb ? 0x00020002u : 0u;
+    using Src = DialPacked<BPP, true>; const typename Src::Args sargs{swap_rb ? 0x00020002u : 0u};
 #include "k_dials_body.inc"
 }
 
 // NV12 / I420 frames (melf_process_yuv*): src describes the Y plane, yuv the chroma planes; PLANAR: separate U and V planes
 // (I420, YV12) instead of interleaved pairs (NV12).  Past its loads the body is the one of 4-byte B G R pixels.  ymat: the frames'
 // colour conversion, the same for every lane (SGPRs), so that the matrices share the NR instantiations.
-#define MELF_YUV_BODY
 template <bool PLANAR, int NR>
 __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_vgpr(DIALS_VGPRS))) void k_yneedle(DialsSrc src, YuvPlanes yuv, YuvMatrix ymat, melf_params P,
                                                                 const DialGeom* __restrict__ geom,
@@ -301,17 +247,12 @@ __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_v
                                                                 const MatchPartial* __restrict__ partials,
                                                                 int nparts, int rw, melf_result* __restrict__ results)
 {
-    constexpr bool FROM_HLS = false;
-    constexpr int PB = 4;
-    constexpr bool RT_ORDER = false;
-    const uint32_t bsel = 0u;
+    using Src = DialYuv420<PLANAR>; const typename Src::Args sargs{yuv, ymat};
 #include "k_dials_body.inc"
 }
-#undef MELF_YUV_BODY
 
 // Packed YUV 4:2:2 frames (melf_process_yuv422*): two pixels per aligned macropixel dword; psel: the byte permute that brings the
 // frames' order (YUYV, UYVY, YVYU) to Y0 U Y1 V, a runtime value, so that the formats share the NR instantiations.
-#define MELF_P422_BODY
 template <int NR>
 __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_vgpr(DIALS_VGPRS))) void k_p422_needle(DialsSrc src, uint32_t psel, YuvMatrix ymat, melf_params P,
                                                                 const DialGeom* __restrict__ geom,
@@ -319,18 +260,13 @@ __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_v
                                                                 const MatchPartial* __restrict__ partials,
                                                                 int nparts, int rw, melf_result* __restrict__ results)
 {
-    constexpr bool FROM_HLS = false;
-    constexpr int PB = 4;
-    constexpr bool RT_ORDER = false;
-    const uint32_t bsel = 0u;
+    using Src = DialP422; const Src::Args sargs{psel, ymat};
 #include "k_dials_body.inc"
 }
-#undef MELF_P422_BODY
 
 // Planar / semi-planar YUV frames of any subsampling (melf_process_yuv_planar*): src describes the Y plane, yuv the chroma.  One
 // instantiation per form of the chroma fetch (SUBX: log2 of the horizontal subsampling, CSTEP: bytes between the samples of a
 // chroma plane) and NR; sub_y, the order of a pair's bytes and the matrix are runtime, wave-uniform values.
-#define MELF_YUVP_BODY
 template <int SUBX, int CSTEP, int NR>
 __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_vgpr(DIALS_VGPRS))) void k_yp_needle(DialsSrc src, YuvPlanarPlanes yuv, YuvMatrix ymat, melf_params P,
                                                                 const DialGeom* __restrict__ geom,
@@ -338,17 +274,12 @@ __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_v
                                                                 const MatchPartial* __restrict__ partials,
                                                                 int nparts, int rw, melf_result* __restrict__ results)
 {
-    constexpr bool FROM_HLS = false;
-    constexpr int PB = 4;
-    constexpr bool RT_ORDER = false;
-    const uint32_t bsel = 0u;
+    using Src = DialYuvPlanar<SUBX, CSTEP>; const typename Src::Args sargs{yuv, ymat};
 #include "k_dials_body.inc"
 }
-#undef MELF_YUVP_BODY
 
 // Planar frames (melf_process_planes*): the B, G and R planes at `planes` in a frame.  Past its loads the body is the one of 4-byte
 // B G R pixels.
-#define MELF_PLANAR_BODY
 template <int NR>
 __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_vgpr(DIALS_VGPRS))) void k_planar_needle(DialsSrc src, PlanarPlanes planes, melf_params P,
                                                                 const DialGeom* __restrict__ geom,
@@ -356,13 +287,9 @@ __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_v
                                                                 const MatchPartial* __restrict__ partials,
                                                                 int nparts, int rw, melf_result* __restrict__ results)
 {
-    constexpr bool FROM_HLS = false;
-    constexpr int PB = 4;
-    constexpr bool RT_ORDER = false;
-    const uint32_t bsel = 0u;
+    using Src = DialPlanarRgb; const Src::Args sargs{planes};
 #include "k_dials_body.inc"
 }
-#undef MELF_PLANAR_BODY
 
 // f(std::integral_constant<int, NR>) for the instantiated NR that holds ws_max window rows
 template <class F>

@@ -1,36 +1,12 @@
-// The body of the dial reader (k_dials.hip): included as the body of k_dials (BGR frames / HLS dials crops) and of k_needles (the
-// other pixel layouts of melf_process_frames*), so that both compile to what one kernel body gives -- a force-inlined function
-// shared by them changed the register allocation of the existing k_dials instantiations (101 -> 115 VGPRs).
-// In scope: the kernel's arguments (src, P, geom, rowmasks, partials, nparts, rw, results) and
-//   FROM_HLS  packed HLS dials crops (melf_read_dials) instead of camera frames;
-//   PB        bytes per pixel in memory: 3, or 4 (base, rows and frames 4-byte aligned, the 4th byte ignored);
-//   RT_ORDER  the channel order is the runtime selector bsel (0: B G R, 0x00020002: R G B) -- k_needles; k_dials reads B G R with
-//             compile-time byte selectors.  Every pixel leaves its load through a byte permute into B G R order, so that hls_pixel
-//             and the prefilter see what they see for a BGR frame: the records are those of the BGR frame made from the caller's;
-//   NR        window rows whose pixels a lane requests up front (the largest dial window of the context, rounded up to 8).
-// With MELF_YUV_BODY defined by the including kernel (k_yneedle): NV12 (PLANAR false) / I420 (PLANAR true) frames, src the Y plane,
-// `yuv` the chroma planes.  Every load fetches Y and the chroma under it and leaves as a B G R dword (melf_device.h: yuv_bgr, under
-// the launch's matrix ymat), which
-// is what the rest of the body sees with PB = 4: the core pixel and the exact path's column pixel by byte loads, the window's four
-// pixels per lane as one Y dword and the (at most three) chroma pairs under it, at any parity of the window's origin.
-// With MELF_P422_BODY defined instead (k_p422_needle): packed YUV 4:2:2 frames (melf_process_yuv422*), two pixels per aligned
-// macropixel dword, its byte order the runtime permute selector psel (-> Y0 U Y1 V).  A lane's four window pixels lie in two or
-// three consecutive macropixels: three dwords per lane and row, and from there on one B G R dword per pixel as above.
-// With MELF_PLANAR_BODY defined instead (k_planar_needle): planar frames (melf_process_planes*), the B, G and R planes at `planes`
-// (PlanarPlanes) in a frame, any byte alignment.  The core pixel and the exact path's column pixel are three byte loads; a lane's
-// four window pixels are one unaligned dword per plane (inside the crop's row of its plane: the pieces lie inside the crop), turned
-// into four B G R dwords by six v_perm_b32 where the prefilter picks them up: from there on as above, at any byte phase.
-// With MELF_YUVP_BODY defined instead (k_yp_needle): planar / semi-planar YUV frames of any subsampling (melf_process_yuv_planar*),
-// src the Y plane, `yuv` the chroma (YuvPlanarPlanes), any byte alignment; SUBX (0, 1) and CSTEP (1, 2) are compile-time: the four
-// forms of the chroma fetch.  As for k_yneedle a lane's four window pixels are one Y dword and the chroma under it: CSTEP 1 one
-// unaligned dword of each plane (SUBX 1: the three samples the four pixels can touch, SUBX 0: their four), CSTEP 2 one 8-byte load
-// of interleaved pairs (three or four of them), split by two v_perm_b32 whose selectors the order of a pair's bytes exchanges; sub_y
-// is the scalar shift of the chroma row.  Nothing is read outside the crop's rows of the planes.
-    [[maybe_unused]] const uint32_t csel = bsel ? 0x0c000102u : 0x0c020100u;   // pixel -> B G R in bytes 0..2 (RT_ORDER)
-    auto bgr = [&](uint32_t px) -> uint32_t {
-        if constexpr (RT_ORDER) return __builtin_amdgcn_perm(0u, px, csel);
-        else return px;
-    };
+// The body of the dial reader (k_dials.hip), written once against the dial-source interface of melf_frame_src.h and included as
+// the body of every dial kernel.  In scope: the kernel's arguments (src, P, geom, rowmasks, partials, nparts, rw, results) and
+//   Src    the kernel's frame source type, sargs its Src::Args (the kernel's own arguments of that layout);
+//   NR     window rows whose pixels a lane requests up front (the largest dial window of the context, rounded up to 8).
+// Textual, so that every kernel compiles to what one kernel body gives.  As one __device__ __forceinline__ function template over
+// <Src, NR>, called by every wrapper (tried over the sources, device code only), all 72 kernels went from 101 VGPRs (k_dials<true,
+// NR>: 100) to 115, accum_offset 104 (100) to 116, none with a private segment: no descriptor was the included form's, so the body
+// stays an #include (profiles/frame_sources/device_code_diff.txt).
+    constexpr int PB = Src::PB;
     __shared__ int s_status[MELF_MAX_DIALS];
     __shared__ double s_pos[MELF_MAX_DIALS], s_angle[MELF_MAX_DIALS];
     extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];  // DIAL_LDS_BYTES per dial
@@ -53,7 +29,7 @@
     // ---- minMaxLoc over the K2 partials; DialsNotFoundError check (_image.py:62-64) ----
     int mx = 0, my = 0;
     float mv = 0.f;
-    if (!FROM_HLS) {
+    if (!Src::FROM_HLS) {
         // every wave folds the partials itself (a few dozen entries): no LDS hand-off, no workgroup barrier
         float bv = 0.f;
         int bi = INT_MAX;
@@ -103,283 +79,26 @@
     const bool colvalid = lane < ws && Xl >= 0 && Xl < P.tw;
     const int Xc = min(max(wx0 + min(lane, ws - 1), 0), P.tw - 1);
     const int ylast = ws - 1;   // wave-uniform
-    const bool tail = !FROM_HLS && hls_scalar_tail(mx + Xl, src.crop_cols);
-    const size_t rstride = FROM_HLS ? (size_t)P.tw * 3 : (size_t)src.row_stride;
-#ifdef MELF_YUV_BODY
-    const int fx_m = src.x0 + mx, fy_m = src.y0 + my;   // the match position in the frame
-    const int cp_u = __builtin_amdgcn_readfirstlane(yuv.c_pitch);
-    const uint8_t* const uplane = frame + (size_t)yuv.u_off;
-    const uint8_t* const vplane = frame + (size_t)yuv.v_off;
-    // pixel (X, Y) of the dials crop as a B G R dword: three byte loads
-    auto yuv_px = [&](int X, int Y) -> uint32_t {
-        const int fx = fx_m + X, fy = fy_m + Y;
-        const size_t co = (size_t)(fy >> 1) * (size_t)cp_u + (size_t)(PLANAR ? fx >> 1 : fx & ~1);
-        const int yv = frame[(size_t)fy * rstride + (size_t)fx];
-        return yuv_bgr(yv, yuv_chroma<false>(uplane[co], vplane[co], ymat), ymat);
-    };
-#elif defined(MELF_YUVP_BODY)
-    const int fx_m = src.x0 + mx, fy_m = src.y0 + my;   // the match position in the frame
-    const int cp_u = __builtin_amdgcn_readfirstlane(yuv.c_pitch);
-    const uint32_t sy_u = (uint32_t)__builtin_amdgcn_readfirstlane(yuv.sub_y);
-    const uint8_t* const uplane = frame + (size_t)yuv.u_off;
-    const uint8_t* const vplane = frame + (size_t)yuv.v_off;
-    // pixel (X, Y) of the dials crop as a B G R dword: three byte loads
-    auto yuv_px = [&](int X, int Y) -> uint32_t {
-        const int fx = fx_m + X, fy = fy_m + Y;
-        const size_t co = (size_t)(fy >> sy_u) * (size_t)cp_u + (size_t)((fx >> SUBX) * CSTEP);
-        const int yv = frame[(size_t)fy * rstride + (size_t)fx];
-        return yuv_bgr(yv, yuv_chroma<false>(uplane[co], vplane[co], ymat), ymat);
-    };
-#elif defined(MELF_P422_BODY)
-    const int fx_m = src.x0 + mx, fy_m = src.y0 + my;   // the match position in the frame
-    // pixel (X, Y) of the dials crop as a B G R dword: its macropixel, one aligned dword load
-    auto yuv_px = [&](int X, int Y) -> uint32_t {
-        const int fx = fx_m + X, fy = fy_m + Y;
-        const uint32_t c = __builtin_amdgcn_perm(0u, *(const uint32_t*)(frame + (size_t)fy * rstride + (size_t)(fx >> 1) * 4), psel);
-        return yuv_bgr((int)((fx & 1 ? c >> 16 : c) & 255u), yuv_chroma<false>((int)((c >> 8) & 255u), (int)(c >> 24), ymat), ymat);
-    };
-#elif defined(MELF_PLANAR_BODY)
-    const int fx_m = src.x0 + mx, fy_m = src.y0 + my;   // the match position in the frame
-    const uint8_t* const bplane = frame + (size_t)planes.b_off;
-    const uint8_t* const gplane = frame + (size_t)planes.g_off;
-    const uint8_t* const rplane = frame + (size_t)planes.r_off;
-    // pixel (X, Y) of the dials crop as a B G R dword: three byte loads
-    auto planar_px = [&](int X, int Y) -> uint32_t {
-        const size_t o = (size_t)(fy_m + Y) * rstride + (size_t)(fx_m + X);
-        return (uint32_t)bplane[o] | (uint32_t)gplane[o] << 8 | (uint32_t)rplane[o] << 16;
-    };
-#else
-    const uint8_t* const origin = FROM_HLS ? frame : frame + (size_t)(src.y0 + my) * src.row_stride + (size_t)(src.x0 + mx) * PB;
-#endif
+    const Src FS(src, sargs, P, frame, mx, my);
+    const bool tail = !Src::FROM_HLS && hls_scalar_tail(mx + Xl, src.crop_cols);
     const int coreX = G.core_x - 2 + lane % 5, coreY = G.core_y - 2 + (lane < 25 ? lane / 5 : 0);
     const bool corevalid = lane < 25 && coreX >= 0 && coreX < P.tw && coreY >= 0 && coreY < P.th;
-#if defined(MELF_YUV_BODY) || defined(MELF_P422_BODY) || defined(MELF_YUVP_BODY)
-    const uint32_t corepx = yuv_px(min(max(coreX, 0), P.tw - 1), min(max(coreY, 0), P.th - 1));
-#elif defined(MELF_PLANAR_BODY)
-    const uint32_t corepx = planar_px(min(max(coreX, 0), P.tw - 1), min(max(coreY, 0), P.th - 1));
-#else
-    const uint32_t corepx = bgr(load_px<PB>(origin + (size_t)min(max(coreY, 0), P.th - 1) * rstride + (size_t)min(max(coreX, 0), P.tw - 1) * PB, src.base));
-    const PxColumn pcol = px_column_of<PB>(origin + (size_t)Xc * PB, src.base);   // (the exact path's loads: one pixel per lane and row)
-#endif
+    const uint32_t corepx = FS.px(min(max(coreX, 0), P.tw - 1), min(max(coreY, 0), P.th - 1));
+    const auto xcol = FS.column(Xc);   // (the exact path's loads: one pixel per lane and row)
     const int th1 = __builtin_amdgcn_readfirstlane(P.th - 1);
-    const int rs_u = __builtin_amdgcn_readfirstlane((int)rstride);  // uniform: the row offsets below are scalar products
-    // The window for the integer test, round 5: a lane fetches FOUR pixels of a row as one aligned 16-byte load (the 12 bytes and
-    // what the alignment adds), sixteen lanes a row, four rows per instruction -- NR / 4 loads per wave instead of NR.  Until then
-    // a lane fetched its column's pixel of every row as an unaligned dword: the texture addresser took 12 cycles per such
-    // instruction, and the 784 of a CU's sixteen waves were issued over the launch's first 4.6 us with nothing else to do
-    // (tools/dials_clock.py: "pixels requested" 9 700 cycles; 4 200 for a wave alone on its SIMD).
+    const int rs_u = __builtin_amdgcn_readfirstlane((int)FS.rstride);  // uniform: the row offsets below are scalar products
+    // The window for the integer test: a lane requests FOUR pixels of a row, sixteen lanes a row, four rows per group.
     constexpr int NG = NR / 4;
     static_assert(NR % 4 == 0, "window rows come in groups of four");
     const int rg = lane >> 4, pc = lane & 15;
     const int npiece = (ws + 3) >> 2;   // wave-uniform: 12-byte pieces of a window row
-    // wave-uniform: every piece lies inside the crop's rows (no column clamping: a lane's four pixels stay four neighbours) and
-    // the last load ends inside the frames' buffer; otherwise every pixel takes the exact path below
-    const uint8_t* const buf_end = src.base + src.readable;   // (not frames x stride: the last frame of a padded-stride buffer may end earlier)
-    // (4-byte pixels: a lane's four are one aligned 16-byte load, nothing beyond them)
-#ifdef MELF_YUV_BODY
-    // YUV: a lane's four pixels are one Y dword (inside its row: the pieces lie inside the crop) and the chroma pairs under them, one
-    // 8-byte (NV12) / two 4-byte (I420) loads that start at the first pair or, near the crop's right edge, as far left of it as keeps
-    // them inside the chroma row of the crop (xlim: the crop's right edge, rounded up to a whole pair); the shift is undone below.
-    // Any alignment (unaligned global loads); nothing is read outside the rows of the planes.
-    (void)buf_end;
-    const int xlim = (src.x0 + src.crop_cols + 1) & ~1;
-    const bool quads = wx0 >= 0 && wx0 + 4 * npiece <= P.tw && xlim >= 8;
-    const int fx0 = fx_m + wx0 + 4 * min(pc, npiece - 1);   // the lane's first pixel in the frame
-    const int cstart = PLANAR ? min(fx0 >> 1, (xlim >> 1) - 4) : min(fx0 & ~1, xlim - 8);   // first chroma byte loaded
-    const uint32_t cshift = (uint32_t)((PLANAR ? fx0 >> 1 : fx0 & ~1) - cstart) * 8u;       // bits to the lane's first pair
-    const bool fodd = fx0 & 1;
-    // the four pixels as B G R dwords from what was loaded: {Y dword, chroma, chroma, -}
-    auto yuv_quad = [&](const u32x4v r) -> u32x4v {
-        uint32_t cu, cv;   // U / V of the three pairs in bytes 0..2
-        if constexpr (PLANAR) {
-            cu = r.y >> cshift; cv = r.z >> cshift;
-        } else {
-            const uint64_t c = (((uint64_t)r.z << 32) | r.y) >> cshift;   // U0 V0 U1 V1 U2 V2
-            const uint32_t lo = (uint32_t)c, hi = (uint32_t)(c >> 32);
-            cu = __builtin_amdgcn_perm(hi, lo, 0x0c040200u); cv = __builtin_amdgcn_perm(hi, lo, 0x0c050301u);
-        }
-        const YuvChroma c0 = yuv_chroma<false>(cu & 255, cv & 255, ymat), c1 = yuv_chroma<false>((cu >> 8) & 255, (cv >> 8) & 255, ymat),
-                        c2 = yuv_chroma<false>((cu >> 16) & 255, (cv >> 16) & 255, ymat);
-        // pixel j sits on pair (j + fodd) >> 1
-        u32x4v o;
-        o.x = yuv_bgr(r.x & 255, c0, ymat);
-        o.y = yuv_bgr((r.x >> 8) & 255, fodd ? c1 : c0, ymat);
-        o.z = yuv_bgr((r.x >> 16) & 255, c1, ymat);
-        o.w = yuv_bgr(r.x >> 24, fodd ? c2 : c1, ymat);
-        return o;
-    };
-#elif defined(MELF_YUVP_BODY)
-    // A lane's four pixels are one Y dword (inside its row: the pieces lie inside the crop) and the chroma under them.  SUBX 1: the
-    // pairs (fx0 >> 1) .. (fx0 + 3) >> 1, two or three of them, in a load of four samples that starts at the first or, near the
-    // crop's right edge, as far left of it as keeps the load inside the chroma row of the crop (xlim: the crop's right edge, rounded
-    // up to a whole pair); the shift is undone below.  SUBX 0: the four samples of the four pixels, inside the crop like the Y dword.
-    // CSTEP 2: the samples are interleaved pairs, read from the lower of the two offsets.  Any alignment (unaligned global loads).
-    (void)buf_end;
-    const int xlim = (src.x0 + src.crop_cols + 1) & ~1;
-    const bool quads = wx0 >= 0 && wx0 + 4 * npiece <= P.tw && (SUBX == 0 || xlim >= 8);
-    const int fx0 = fx_m + wx0 + 4 * min(pc, npiece - 1);   // the lane's first pixel in the frame
-    const int cstart = SUBX ? min(fx0 >> 1, (xlim >> 1) - 4) : fx0;                     // first chroma sample loaded
-    const uint32_t cshift = SUBX ? (uint32_t)((fx0 >> 1) - cstart) * 8u * CSTEP : 0u;   // bits to the lane's first sample
-    const bool fodd = fx0 & 1;
-    const bool vfirst = yuv.v_off < yuv.u_off;   // CSTEP 2: V before U in a pair (wave-uniform)
-    const uint8_t* const cplane = vfirst ? vplane : uplane;
-    const uint32_t usel = vfirst ? 0x07050301u : 0x06040200u, vsel = vfirst ? 0x06040200u : 0x07050301u;
-    // the four pixels as B G R dwords from what was loaded: {Y dword, chroma, chroma, -}
-    auto yuv_quad = [&](const u32x4v r) -> u32x4v {
-        uint32_t cu, cv;   // U / V of the samples in bytes 0 ..
-        if constexpr (CSTEP == 1) {
-            cu = r.y >> cshift; cv = r.z >> cshift;
-        } else {
-            const uint64_t c = (((uint64_t)r.z << 32) | r.y) >> cshift;   // the pairs from the lane's first on
-            const uint32_t lo = (uint32_t)c, hi = (uint32_t)(c >> 32);
-            cu = __builtin_amdgcn_perm(hi, lo, usel); cv = __builtin_amdgcn_perm(hi, lo, vsel);
-        }
-        const YuvChroma c0 = yuv_chroma<false>(cu & 255, cv & 255, ymat), c1 = yuv_chroma<false>((cu >> 8) & 255, (cv >> 8) & 255, ymat),
-                        c2 = yuv_chroma<false>((cu >> 16) & 255, (cv >> 16) & 255, ymat);
-        u32x4v o;
-        if constexpr (SUBX) {   // pixel j sits on pair (j + fodd) >> 1
-            o.x = yuv_bgr(r.x & 255, c0, ymat);
-            o.y = yuv_bgr((r.x >> 8) & 255, fodd ? c1 : c0, ymat);
-            o.z = yuv_bgr((r.x >> 16) & 255, c1, ymat);
-            o.w = yuv_bgr(r.x >> 24, fodd ? c2 : c1, ymat);
-        } else {                // a sample per pixel
-            const YuvChroma c3 = yuv_chroma<false>(cu >> 24, cv >> 24, ymat);
-            o.x = yuv_bgr(r.x & 255, c0, ymat);
-            o.y = yuv_bgr((r.x >> 8) & 255, c1, ymat);
-            o.z = yuv_bgr((r.x >> 16) & 255, c2, ymat);
-            o.w = yuv_bgr(r.x >> 24, c3, ymat);
-        }
-        return o;
-    };
-#elif defined(MELF_P422_BODY)
-    // 4:2:2: a lane's four pixels lie in the macropixels (fx0 >> 1) .. (fx0 + 3) >> 1, two of them (fx0 even) or three (odd).  Three
-    // aligned dwords per lane and row, from the first macropixel or, at the crop's right edge, from one further left, so that the
-    // third stays inside the row (mlim: the macropixels up to the crop's right edge; the frame's width is even, so the row holds
-    // them all).  Only an even fx0 can be moved (its third dword is the spare one); the move is undone below.
-    (void)buf_end;
-    const int mlim = (src.x0 + src.crop_cols + 1) >> 1;
-    const bool quads = wx0 >= 0 && wx0 + 4 * npiece <= P.tw && mlim >= 3;
-    const int fx0 = fx_m + wx0 + 4 * min(pc, npiece - 1);   // the lane's first pixel in the frame
-    const int mstart = min(fx0 >> 1, mlim - 3);             // first macropixel loaded
-    const bool mshifted = (fx0 >> 1) != mstart;
-    const bool fodd = fx0 & 1;
-    // the four pixels as B G R dwords from the three macropixels loaded
-    auto yuv_quad = [&](const u32x4v r) -> u32x4v {
-        const uint32_t ma = __builtin_amdgcn_perm(0u, mshifted ? r.y : r.x, psel), mb = __builtin_amdgcn_perm(0u, mshifted ? r.z : r.y, psel),
-                       mc = __builtin_amdgcn_perm(0u, r.z, psel);   // Y0 U Y1 V each
-        const YuvChroma c0 = yuv_chroma<false>((int)((ma >> 8) & 255u), (int)(ma >> 24), ymat), c1 = yuv_chroma<false>((int)((mb >> 8) & 255u), (int)(mb >> 24), ymat),
-                        c2 = yuv_chroma<false>((int)((mc >> 8) & 255u), (int)(mc >> 24), ymat);
-        const uint32_t y4 = __builtin_amdgcn_perm(mb, ma, 0x06040200u);                  // Y of the pixels of ma, mb
-        const uint32_t yd = fodd ? __builtin_amdgcn_perm(mc, y4, 0x04030201u) : y4;      // Y of the lane's four
-        // pixel j sits on macropixel (j + fodd) >> 1
-        u32x4v o;
-        o.x = yuv_bgr((int)(yd & 255u), c0, ymat);
-        o.y = yuv_bgr((int)((yd >> 8) & 255u), fodd ? c1 : c0, ymat);
-        o.z = yuv_bgr((int)((yd >> 16) & 255u), c1, ymat);
-        o.w = yuv_bgr((int)(yd >> 24), fodd ? c2 : c1, ymat);
-        return o;
-    };
-#elif defined(MELF_PLANAR_BODY)
-    // planar: a lane's four pixels are four consecutive bytes of each plane's row, inside the crop (and so inside the frame's row):
-    // nothing is read outside the planes' samples, whatever the alignment
-    (void)buf_end;
-    const bool quads = wx0 >= 0 && wx0 + 4 * npiece <= P.tw;
-    const int fx0 = fx_m + wx0 + 4 * min(pc, npiece - 1);   // the lane's first pixel in the frame
-    // the four pixels as B G R dwords from the three plane dwords {B0 B1 B2 B3, G0 G1 G2 G3, R0 R1 R2 R3}
-    auto planar_quad = [&](const u32x4v r) -> u32x4v {
-        const uint32_t t01 = __builtin_amdgcn_perm(r.y, r.x, 0x05010400u), t23 = __builtin_amdgcn_perm(r.y, r.x, 0x07030602u);   // B0 G0 B1 G1, B2 G2 B3 G3
-        u32x4v o;
-        o.x = __builtin_amdgcn_perm(r.z, t01, 0x0c040100u);
-        o.y = __builtin_amdgcn_perm(r.z, t01, 0x0c050302u);
-        o.z = __builtin_amdgcn_perm(r.z, t23, 0x0c060100u);
-        o.w = __builtin_amdgcn_perm(r.z, t23, 0x0c070302u);
-        return o;
-    };
-#else
-    const bool quads = !FROM_HLS && ((uintptr_t)src.base & 3) == 0 && wx0 >= 0 && wx0 + 4 * npiece <= P.tw &&
-                       origin + (size_t)th1 * rstride + (size_t)(wx0 + 4 * npiece) * PB + (PB == 4 ? 0 : 4) <= buf_end;
-#endif
+    auto W = FS.window(wx0, npiece, pc, th1, rs_u, P.tw);
+    const bool quads = W.quads;   // wave-uniform; otherwise every pixel takes the exact path below
     u32x4v raw[NG];
-    uint32_t mshift = 0;   // bytes between a load's aligned address and its first pixel (0..3), two bits per load
-#ifdef MELF_YUV_BODY
     if (quads) {
 #pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const int fy = fy_m + min(max(wy0 + min(4 * g + rg, ylast), 0), th1);
-            uint32_t yd;
-            __builtin_memcpy(&yd, frame + (size_t)fy * (size_t)rs_u + (size_t)fx0, 4);
-            const size_t co = (size_t)(fy >> 1) * (size_t)cp_u + (size_t)cstart;
-            if constexpr (PLANAR) {
-                uint32_t ud, vd;
-                __builtin_memcpy(&ud, uplane + co, 4);
-                __builtin_memcpy(&vd, vplane + co, 4);
-                raw[g] = u32x4v{yd, ud, vd, 0u};
-            } else {
-                uint32_t cd[2];
-                __builtin_memcpy(cd, uplane + co, 8);
-                raw[g] = u32x4v{yd, cd[0], cd[1], 0u};
-            }
-        }
+        for (int g = 0; g < NG; ++g) raw[g] = W.request(g, min(max(wy0 + min(4 * g + rg, ylast), 0), th1));
     }
-#elif defined(MELF_YUVP_BODY)
-    if (quads) {
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const int fy = fy_m + min(max(wy0 + min(4 * g + rg, ylast), 0), th1);
-            uint32_t yd;
-            __builtin_memcpy(&yd, frame + (size_t)fy * (size_t)rs_u + (size_t)fx0, 4);
-            const size_t co = (size_t)(fy >> sy_u) * (size_t)cp_u + (size_t)(cstart * CSTEP);
-            if constexpr (CSTEP == 1) {
-                uint32_t ud, vd;
-                __builtin_memcpy(&ud, uplane + co, 4);
-                __builtin_memcpy(&vd, vplane + co, 4);
-                raw[g] = u32x4v{yd, ud, vd, 0u};
-            } else {
-                uint32_t cd[2];
-                __builtin_memcpy(cd, cplane + co, 8);
-                raw[g] = u32x4v{yd, cd[0], cd[1], 0u};
-            }
-        }
-    }
-#elif defined(MELF_P422_BODY)
-    if (quads) {
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const int fy = fy_m + min(max(wy0 + min(4 * g + rg, ylast), 0), th1);
-            uint32_t md[3];
-            __builtin_memcpy(md, (const uint32_t*)(frame + (size_t)fy * (size_t)rs_u) + mstart, 12);
-            raw[g] = u32x4v{md[0], md[1], md[2], 0u};
-        }
-    }
-#elif defined(MELF_PLANAR_BODY)
-    if (quads) {
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const int fy = fy_m + min(max(wy0 + min(4 * g + rg, ylast), 0), th1);
-            const size_t o = (size_t)fy * (size_t)rs_u + (size_t)fx0;
-            uint32_t bd, gd, rd;
-            __builtin_memcpy(&bd, bplane + o, 4);
-            __builtin_memcpy(&gd, gplane + o, 4);
-            __builtin_memcpy(&rd, rplane + o, 4);
-            raw[g] = u32x4v{bd, gd, rd, 0u};
-        }
-    }
-#else
-    if (quads) {
-        const uint8_t* const lane0 = origin + (size_t)(wx0 + 4 * min(pc, npiece - 1)) * PB;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const int Y = min(max(wy0 + min(4 * g + rg, ylast), 0), th1);
-            const uint8_t* const a = lane0 + (size_t)Y * (size_t)rs_u;
-            if constexpr (PB == 4) {
-                raw[g] = *(const u32x4v*)a;
-            } else {
-                mshift |= ((uint32_t)(uintptr_t)a & 3u) << (2 * g);
-                raw[g] = *(const u32x4v*)((uintptr_t)a & ~(uintptr_t)3);
-            }
-        }
-    }
-#endif
     __builtin_amdgcn_sched_barrier(0);
     FSTAMPD(9);    // every pixel requested
 #ifdef MELF_DIALS_STAMP
@@ -390,7 +109,7 @@
     // get_dial_color (_reading.py:154-160): mean of the 5x5 core, Python round()
     int sh = 0, sl = 0, ss = 0, cnt = 0;
     if (corevalid) {
-        if (FROM_HLS) { sh = corepx & 255; sl = (corepx >> 8) & 255; ss = (corepx >> 16) & 255; }
+        if (Src::FROM_HLS) { sh = corepx & 255; sl = (corepx >> 8) & 255; ss = (corepx >> 16) & 255; }
         else hls_pixel(corepx & 255, (corepx >> 8) & 255, (corepx >> 16) & 255, hls_scalar_tail(mx + coreX, src.crop_cols), P.hue_shift, sh, sl, ss);
         cnt = 1;
     }
@@ -412,13 +131,7 @@
 #pragma unroll
             for (int k = 0; k < 16; ++k) {
                 const int Y = min(max(wy0 + min(yc + k, ylast), 0), th1);
-#if defined(MELF_YUV_BODY) || defined(MELF_P422_BODY) || defined(MELF_YUVP_BODY)
-                pxe[k] = yuv_px(Xc, Y);
-#elif defined(MELF_PLANAR_BODY)
-                pxe[k] = planar_px(Xc, Y);
-#else
-                pxe[k] = bgr(load_px3_row(pcol, (size_t)((int64_t)Y * rs_u)));
-#endif
+                pxe[k] = FS.col_px(xcol, Y, rs_u);
             }
 #pragma unroll
             for (int k = 0; k < 16; ++k) {
@@ -428,7 +141,7 @@
                 if (valid) {
                     int H, L, S;
                     const uint32_t px = pxe[k];
-                    if (FROM_HLS) { H = px & 255; L = (px >> 8) & 255; S = (px >> 16) & 255; }
+                    if (Src::FROM_HLS) { H = px & 255; L = (px >> 8) & 255; S = (px >> 16) & 255; }
                     else hls_pixel(px & 255, (px >> 8) & 255, (px >> 16) & 255, tail, P.hue_shift, H, L, S);
                     in = H >= loh && H <= hih && L >= lol && L <= hil && S >= los && S <= his;
                 }
@@ -437,7 +150,7 @@
             }
         }
     };
-    if (FROM_HLS) {
+    if (Src::FROM_HLS) {
         exact_rows();
     } else {
         // Two steps.  (1) An integer test that can only err towards "maybe" picks candidates: with
@@ -463,28 +176,18 @@
         if (quads) {
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
-#if defined(MELF_YUV_BODY) || defined(MELF_P422_BODY) || defined(MELF_YUVP_BODY)
-                raw[g] = yuv_quad(raw[g]);   // from here on: one B G R pixel per dword, as for 4-byte pixels
-#elif defined(MELF_PLANAR_BODY)
-                raw[g] = planar_quad(raw[g]);   // (the same)
-#endif
-                // the lane's 12 bytes: B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3  (4-byte pixels: raw[g] holds one pixel per dword)
-                uint32_t e0 = 0, e1 = 0, e2 = 0;
-                if constexpr (PB == 3) {
-                    const uint32_t ms = (mshift >> (2 * g)) & 3u;
-                    e0 = __builtin_amdgcn_alignbyte(raw[g].y, raw[g].x, ms);
-                    e1 = __builtin_amdgcn_alignbyte(raw[g].z, raw[g].y, ms);
-                    e2 = __builtin_amdgcn_alignbyte(raw[g].w, raw[g].z, ms);
-                }
+                // PB 4: one B G R pixel per dword; PB 3: the lane's 12 bytes  B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3  in x, y, z
+                const u32x4v q4 = W.unpack(g, raw[g]);
+                const uint32_t e0 = q4.x, e1 = q4.y, e2 = q4.z;
                 const int y = 4 * g + rg, Y = wy0 + y;
                 const uint64_t rowb = __builtin_amdgcn_ballot_w64((y < ws) & (Y >= 0) & (Y < P.th));
                 // channel order: R G B swaps the selectors of B and R (the byte of B moves up by two, that of R down by two)
-                const uint32_t sb = RT_ORDER ? bsel : 0u;
+                const uint32_t sb = FS.sb();
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {   // pixels (0, 1), then (2, 3): two per instruction, as packed 16-bit halves
                     uint32_t B2, G2, R2;
                     if constexpr (PB == 4) {
-                        const uint32_t lo = h ? raw[g].z : raw[g].x, hi = h ? raw[g].w : raw[g].y;
+                        const uint32_t lo = h ? q4.z : q4.x, hi = h ? q4.w : q4.y;
                         B2 = __builtin_amdgcn_perm(hi, lo, 0x0c040c00u + sb);
                         G2 = __builtin_amdgcn_perm(hi, lo, 0x0c050c01u);
                         R2 = __builtin_amdgcn_perm(hi, lo, 0x0c060c02u - sb);
@@ -510,9 +213,9 @@
                             if (cand && slot < DIAL_LIST_CAP) {
                                 list_pos[slot] = (uint16_t)(y << 6 | (4 * pc + j));
                                 if constexpr (PB == 4)
-                                    list_px[slot] = bgr(j == 0 ? raw[g].x : (j == 1 ? raw[g].y : (j == 2 ? raw[g].z : raw[g].w)));
+                                    list_px[slot] = FS.bgr(j == 0 ? q4.x : (j == 1 ? q4.y : (j == 2 ? q4.z : q4.w)));
                                 else
-                                    list_px[slot] = bgr(j == 0 ? e0 : (j == 1 ? __builtin_amdgcn_alignbyte(e1, e0, 3) : (j == 2 ? __builtin_amdgcn_alignbyte(e2, e1, 2) : e2 >> 8)));
+                                    list_px[slot] = FS.bgr(j == 0 ? e0 : (j == 1 ? __builtin_amdgcn_alignbyte(e1, e0, 3) : (j == 2 ? __builtin_amdgcn_alignbyte(e2, e1, 2) : e2 >> 8)));
                             }
                             total += __popcll(cb);
                         }

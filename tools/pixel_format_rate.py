@@ -8,7 +8,10 @@ Rows: packed BGR through the old entry point; BGR, RGB, BGRA, RGBA through the n
 converts the same batch from RGBA / RGB to packed BGR (what a caller did before the new entry point).  Every row has its own copy
 of the frames, so that the timed region rotates over more than 256 MB (a 1024-frame batch is 0.94 GB in BGR, 1.26 GB in BGRA)
 as bench.py's does; the rows take turns, K steps each, in an order that rotates from round to round, R rounds, after W untimed
-steps of every row.  Prints a table (median ms per step over the rounds and its ratio to the old entry point's)."""
+steps of every row.  Prints a table (median ms per step over the rounds and its ratio to the old entry point's) and, for the rows
+that run the library's kernels, the prep and the dial kernel's own time per launch (every kernel bracketed by events,
+melf_ctx_set_profiling); a last row gives the dial kernel of melf_read_dials on the same number of HLS crops (host-fed: no step
+time).  MELF_LIB_PATH selects the library, so that two builds can be compared."""
 import argparse
 import glob
 import os
@@ -99,6 +102,25 @@ for r in range(args.rounds):
         e1.record(stream)
         e1.synchronize()
         times[name].append(e0.elapsed_time(e1) / args.steps)
+# per-kernel times: every kernel bracketed by events
+kern = {}
+ctx.set_profiling(1)
+for (name, fn) in rows[:5]:
+    for _ in range(4):
+        fn()
+    torch.cuda.synchronize()
+    ctx.timings()
+    for _ in range(8):
+        fn()
+    torch.cuda.synchronize()
+    kern[name] = {k: (ms / max(cnt, 1)) for (k, (ms, cnt)) in ctx.timings().items() if cnt}
+hls = np.random.default_rng(5).integers(0, 256, (B, ctx.params.th, ctx.params.tw, 3), dtype=np.uint8)
+ctx.read_dials(hls)
+ctx.timings()
+for _ in range(4):
+    ctx.read_dials(hls)
+kern['HLS crops, melf_read_dials'] = {k: (ms / max(cnt, 1)) for (k, (ms, cnt)) in ctx.timings().items() if cnt}
+ctx.set_profiling(0)
 old = float(np.median(times[rows[0][0]]))
 print('%d-frame steps, %dx%d, %d rounds x %d steps (median ms per step; spread = min..max of the rounds)' % (B, W, H, args.rounds, args.steps))
 print('| %-45s | %8s | %15s | %7s |' % ('row', 'ms/step', 'spread', 'vs old'))
@@ -106,5 +128,9 @@ print('|%s|%s|%s|%s|' % ('-' * 47, '-' * 10, '-' * 17, '-' * 9))
 for (name, _fn) in rows:
     t = times[name]
     print('| %-45s | %8.4f | %6.4f..%6.4f | %6.3fx |' % (name, float(np.median(t)), min(t), max(t), float(np.median(t)) / old))
+print('| %-45s | %11s | %10s |' % ('row', 'k_lplane ms', 'k_dials ms'))
+print('|%s|%s|%s|' % ('-' * 47, '-' * 13, '-' * 12))
+for (name, k) in kern.items():
+    print('| %-45s | %11.4f | %10.4f |' % (name, k.get('k_lplane', 0.0), k.get('k_dials', 0.0)))
 ctx.sync()
 ctx.close()

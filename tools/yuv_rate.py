@@ -85,6 +85,11 @@ streams = [torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)]
 view = _hip.yuv_frames_view(nv12[:B], 'nv12')
 desc = view.descriptor()
 yuv_batch_bytes = B * view.frame_stride
+# the same frames as I420 (U plane, then V plane behind the Y rows): the planar kernels' times
+i420 = nv12.clone()
+i420[:, H:] = torch.cat([nv12[:, H:, 0::2].reshape(N, -1), nv12[:, H:, 1::2].reshape(N, -1)], dim=1).reshape(N, H // 2, W)
+view_p = _hip.yuv_frames_view(i420[:B], 'i420')
+desc_p = view_p.descriptor()
 
 
 def step_bgr(i, stream):
@@ -106,13 +111,21 @@ def run(fn, steps, nstreams=2):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
-rows = [('BGR, melf_process_batch_dev', step_bgr), ('NV12, melf_process_yuv_dev', step_nv12)]
+def step_i420(i, stream):
+    k = i % NB
+    ctx.process_yuv_dev(i420.data_ptr() + k * B * view_p.frame_stride, desc_p, d_results_ptr=d_res.data_ptr() + k * B * rsz, want_host=False, stream=stream)
+
+
+rows = [('BGR, melf_process_batch_dev', step_bgr), ('NV12, melf_process_yuv_dev', step_nv12), ('I420, melf_process_yuv_dev', step_i420)]
 # the same records, byte for byte
 run(step_bgr, NB)
 ref = d_res.clone()
 d_res.zero_()
 run(step_nv12, NB)
 assert torch.equal(d_res, ref), 'NV12 records differ from the BGR records'
+d_res.zero_()
+run(step_i420, NB)
+assert torch.equal(d_res, ref), 'I420 records differ from the BGR records'
 ok = int((ref.cpu().numpy().view(_hip.RESULT_DTYPE)['status'] == _hip.FRAME_OK).sum())
 print('frames read: %d of %d; NV12 records == BGR records' % (ok, N))
 print('match kernel: %s' % ctx.last_match()['kernel'])
@@ -140,7 +153,7 @@ P = ctx.params
 (cr, cc) = (y1 - y0, x1 - x0)
 crow = ((y1 - 1) >> 1) - (y0 >> 1) + 1
 cbytes = (((x1 - 1) >> 1) - (x0 >> 1) + 1) * 2
-alg = {'BGR': cr * cc * 3, 'NV12': cr * cc + crow * cbytes}
+alg = {'BGR': cr * cc * 3, 'NV12': cr * cc + crow * cbytes, 'I420': cr * cc + crow * cbytes}
 old = float(np.median(times[rows[0][0]]))
 print('%d-frame steps, %dx%d, %d batches in rotation (BGR %.2f GB, NV12 %.2f GB), two caller streams, %d rounds x %d steps'
       % (B, W, H, NB, bgr.numel() / 1e9, nv12.numel() / 1e9, args.rounds, args.steps))

@@ -37,11 +37,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from meterelf_amd import _hip  # noqa: E402
-from tests import test_pixel_formats as pf  # noqa: E402
-from tests import test_planar_frames as pl  # noqa: E402
-from tests import test_yuv422_frames as y422  # noqa: E402
-from tests import test_yuv_frames as y420  # noqa: E402
-from tests import test_yuv_planar_frames as yp  # noqa: E402
+from tests import frame_cases as fc  # noqa: E402
 from tests.test_gpu_parity import POS_TOL, REJECTED, _compare_records  # noqa: E402
 
 SD = 'sample-images1'
@@ -178,7 +174,7 @@ def _streak(frame, ox, oy, angle, colour):
 
 @functools.lru_cache(maxsize=None)
 def sweep_frames():
-    """The first twelve same-sized good fixture frames, shifted and with +-2 noise (test_pixel_formats._synth; its constant frame
+    """The first twelve same-sized good fixture frames, shifted and with +-2 noise (frame_cases.synth; its constant frame
     is given a slot of its own and dropped).  The fixture's needle of dial 1 ends at radius 21, so every second frame gets a
     streak of the dial's own colour from the needle into the rings beyond, 0.02 turn off the needle's angle: without it the rows
     that only the larger NR classes hold would not bear on any reading (test_outer_rows_bear_on_the_reading)."""
@@ -189,7 +185,7 @@ def sweep_frames():
     shapes = [f.shape for f in frames]
     twelve = [f for f in frames if f.shape == max(set(shapes), key=shapes.count)][:NFRAMES]
     assert len(twelve) == NFRAMES
-    out = np.delete(pf._synth(twelve[:4] + [twelve[0]] + twelve[4:], NFRAMES + 1, 11), 4, axis=0)
+    out = np.delete(fc.synth(twelve[:4] + [twelve[0]] + twelve[4:], NFRAMES + 1, 11), 4, axis=0)
     assert out.shape == (NFRAMES, 640, 480, 3)
     ores = po.process_frames(out, _oparams(_fixture_data(), 'fixture'))
     (cx, cy) = _fixture_data()['needle_data'][1]['center']
@@ -406,15 +402,15 @@ def _converted(bgr, key):
         _CONVERTED['frames'] = bgr
     if key not in _CONVERTED:
         if key == '420':
-            (Y, U, V) = y420.bgr_to_yuv420(bgr)
-            _CONVERTED[key] = (Y, U, V, y420.yuv420_to_bgr(Y, U, V))
+            (Y, U, V) = fc.F420.from_bgr(bgr)
+            _CONVERTED[key] = (Y, U, V, fc.F420.bgr_of(Y, U, V))
         elif key == '422':
-            (Y, U, V) = y422.bgr_to_yuv422(bgr)
-            _CONVERTED[key] = (Y, U, V, y422.yuv422_to_bgr(Y, U, V))
+            (Y, U, V) = fc.F422.from_bgr(bgr)
+            _CONVERTED[key] = (Y, U, V, fc.F422.bgr_of(Y, U, V))
         else:
             assert key == '444'
-            (Y, U, V) = yp.bgr_to_yuv(bgr, 0, 0)
-            _CONVERTED[key] = (Y, U, V, yp.yuv_planar_to_bgr(Y, U, V, 0, 0))
+            (Y, U, V) = fc.bgr_to_yuv(bgr, 0, 0)
+            _CONVERTED[key] = (Y, U, V, fc.yuv_to_bgr(Y, U, V, 0, 0))
     return _CONVERTED[key]
 
 
@@ -440,44 +436,46 @@ def _run_families(c, bgr, rng, families, want_match_x=None):
 
     for (fmt, family) in (('rgb', 'packed3'), ('bgra', 'packed4'), ('rgba', 'packed4')):
         if family in families:
-            (arr, f) = pf.to_layout(bgr, fmt, 5, rng)
+            (arr, f) = fc.to_layout(bgr, fmt, 5, rng)
             check(family, fmt, want_of('bgr'), lambda: c.reader.read_frame_views(arr, f),
-                  lambda: pf._read_dev(ctx, _hip.frames_view(arr, f)))
+                  lambda: fc.read_packed_dev(ctx, _hip.frames_view(arr, f)))
     for fmt in ('nv12', 'i420'):
         if fmt in families:
             (Y, U, V, _b) = _converted(bgr, '420')
-            v = _hip.yuv_frames_view(y420.conventional(Y, U, V, fmt, 10 if fmt == 'nv12' else 0, rng), fmt)
+            v = _hip.yuv_frames_view(fc.conventional420(Y, U, V, fmt, 10 if fmt == 'nv12' else 0, rng), fmt)
             check(fmt, fmt, want_of('420'), lambda: ctx.process_yuv(v.ptr, v.descriptor()),
-                  lambda: _dev(lambda: y420.DevBuf(v.ptr, v.extent), lambda d: ctx.process_yuv_dev(d, v.descriptor())))
+                  lambda: _dev(lambda: fc.DevBuf(v.ptr, v.extent), lambda d: ctx.process_yuv_dev(d, v.descriptor())))
     if 'p422' in families:
         (Y, U, V, _b) = _converted(bgr, '422')
         for fmt in ('yuyv', 'uyvy'):
-            v = _hip.yuv422_frames_view(y422.conventional(Y, U, V, fmt, 6, rng), fmt)
+            v = _hip.yuv422_frames_view(fc.conventional422(Y, U, V, fmt, 6, rng), fmt)
             check('p422', fmt, want_of('422'), lambda: ctx.process_yuv422(v.ptr, v.descriptor()),
-                  lambda: _dev(lambda: y422.DevBuf(v.ptr, v.extent), lambda d: ctx.process_yuv422_dev(d, v.descriptor())))
+                  lambda: _dev(lambda: fc.DevBuf(v.ptr, v.extent), lambda d: ctx.process_yuv422_dev(d, v.descriptor())))
     for (fmt, family) in (('i422', 'yp_sub1_step1'), ('nv16', 'yp_sub1_step2'), ('i444', 'yp_sub0_step1'), ('nv24', 'yp_sub0_step2')):
         if family in families:
-            (sx, sy, step, _vf) = yp.FORMATS[fmt]
+            (sx, sy, step, _vf) = fc.YUV_PLANAR_FORMATS[fmt]
             assert (sx, sy, step) == (int(family[6]), 0, int(family[-1]))
-            # (4:2:2: the forward conversion and the restatement of the packed formats' module give the same frames as this
-            # module's -- test_forward_conversions_agree -- so the planar formats share their expected records)
+            # (4:2:2: packed and planar formats are made by one forward conversion and expected from one restatement,
+            # tests/frame_cases.py's, at (sub_x, sub_y) = (1, 0) -- so the planar formats share their expected records)
             key = '422' if sx else '444'
             (Y, U, V, _b) = _converted(bgr, key)
-            v = _hip.yuv_planar_frames_view(yp.conventional(Y, U, V, fmt, 0, rng), fmt)
+            v = _hip.yuv_planar_frames_view(fc.conventional_yuv_planar(Y, U, V, fmt, 0, rng), fmt)
             check(family, fmt, want_of(key), lambda: ctx.process_yuv_planar(v.ptr, v.descriptor()),
-                  lambda: _dev(lambda: y420.DevBuf(v.ptr, v.extent), lambda d: ctx.process_yuv_planar_dev(d, v.descriptor())))
+                  lambda: _dev(lambda: fc.DevBuf(v.ptr, v.extent), lambda d: ctx.process_yuv_planar_dev(d, v.descriptor())))
     if 'planar' in families:
-        v = _hip.planar_frames_view(pl.to_planes(bgr, 'rgb', rng), 'rgb')
+        v = _hip.planar_frames_view(fc.to_planes(bgr, 'rgb', rng), 'rgb')
         check('planar', 'rgb planes', want_of('bgr'), lambda: ctx.process_planes(v.ptr, v.descriptor()),
-              lambda: _dev(lambda: pl.DevBuf(v.ptr, v.extent), lambda d: ctx.process_planes_dev(d, v.descriptor())))
+              lambda: _dev(lambda: fc.DevBuf.at_end(v.ptr, v.extent), lambda d: ctx.process_planes_dev(d, v.descriptor())))
 
 
 def test_forward_conversions_agree():
-    """_run_families shares one set of expected records between the packed and the planar 4:2:2 formats."""
+    """_run_families shares one set of expected records between the packed and the planar 4:2:2 formats.  Both families' input
+    and expected frames now come from one function each (frame_cases.bgr_to_yuv, yuv_to_bgr), so this only holds the 4:2:2 record
+    to (sub_x, sub_y) = (1, 0): the packed family's converters are those functions at that subsampling."""
     bgr = np.ascontiguousarray(sweep_frames()[:1, 200:264, 100:164])
-    (a, b) = (y422.bgr_to_yuv422(bgr), yp.bgr_to_yuv(bgr, 1, 0))
+    (a, b) = (fc.F422.from_bgr(bgr), fc.bgr_to_yuv(bgr, 1, 0))
     assert all(np.array_equal(p, q) for (p, q) in zip(a, b))
-    assert np.array_equal(y422.yuv422_to_bgr(*a), yp.yuv_planar_to_bgr(*b, 1, 0))
+    assert np.array_equal(fc.F422.bgr_of(*a), fc.yuv_to_bgr(*b, 1, 0))
 
 
 def _sweep_one(r_max):
@@ -492,7 +490,7 @@ def _sweep_one(r_max):
         # (a) packed BGR, host-fed and from device memory, against the oracle
         recs = c.read_bgr(bgr)
         _compare_records(recs, ores, tag='r%d' % r_max)
-        dev = _dev(lambda: y420.DevBuf(bgr.ctypes.data, bgr.nbytes), lambda d: c.ctx.process_batch_dev(d, NFRAMES, *bgr.shape[1:3]))
+        dev = _dev(lambda: fc.DevBuf(bgr.ctypes.data, bgr.nbytes), lambda d: c.ctx.process_batch_dev(d, NFRAMES, *bgr.shape[1:3]))
         c.ran('bgr')
         assert dev.tobytes() == recs.tobytes()
         # (b) the oracle's HLS crops of the same frames

@@ -23,8 +23,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from meterelf_amd import _hip  # noqa: E402
-from tests import test_pixel_formats as t_pix, test_planar_frames as t_planar, test_yuv422_frames as t_422, test_yuv_frames as t_420  # noqa: E402
-from tests.test_pixel_formats import env  # noqa: E402,F401  (the module-scoped readers + fixture frames)
+from tests import frame_cases as fc  # noqa: E402
+from tests.frame_cases import env  # noqa: E402,F401  (the module-scoped readers + fixture frames)
 
 N, CHUNK, H, W, NVAR = 257, 128, 410, 300, 32
 CASES = ('bgr', 'bgra', 'nv12', 'i420', 'yuyv', 'planar')
@@ -56,22 +56,22 @@ def _layout(case, var, pick):
         arr = var[pick]
         return arr, None, None
     if case == 'bgra':
-        (arr, fmt) = t_pix.to_layout(var, 'bgra')
+        (arr, fmt) = fc.to_layout(var, 'bgra')
         arr = arr[pick]
         return arr, (lambda a: _hip.frames_view(a, fmt)), None
     if case in ('nv12', 'i420'):
-        arr = t_420.conventional(*t_420.bgr_to_yuv420(var), case)[pick]
+        arr = fc.conventional420(*fc.F420.from_bgr(var), case)[pick]
         return arr, (lambda a: _hip.yuv_frames_view(a, case)), ctx_calls['yuv']
     if case == 'yuyv':
-        arr = t_422.conventional(*t_422.bgr_to_yuv422(var), case)[pick]
+        arr = fc.conventional422(*fc.F422.from_bgr(var), case)[pick]
         return arr, (lambda a: _hip.yuv422_frames_view(a, case)), ctx_calls['yuv422']
-    arr = t_planar.to_planes(var, 'rgb')[pick]
+    arr = fc.to_planes(var, 'rgb')[pick]
     return arr, (lambda a: _hip.planar_frames_view(a, 'rgb')), ctx_calls['planes']
 
 
 def _host_and_dev(ctx, case, arr, view, calls):
     """Records of the host entry point and of the *_dev entry point for the same bytes."""
-    hip = t_pix._hip_rt()
+    hip = fc.hip_rt()
     d = C.c_void_p()
     if case == 'bgr':   # the packed-BGR entry points take no descriptor
         (ptr, extent) = (arr.ctypes.data, arr.nbytes)

@@ -6,12 +6,12 @@ The contract: the records of a frame in any layout are byte-identical to read_fr
 header, frames_view's mapping of numpy arrays and torch CPU tensors, the new kernels' code-object notes.  GPU tests: records
 against the BGR path on the fixtures, with every match kernel, at 1080p, at the frame edges, over lanes and streams.
 
-Device frames without torch come from the HIP runtime the library is bound to (tests.helpers.hip_runtime).  The torch path of
-read_frame_views runs in a child process that imports torch before the package, as a torch program does (bench.py): a process
-that loaded the library first holds a second HIP runtime once torch loads its own, and torch's streams would be foreign to it.
+The helpers these tests share with the other frame formats' -- the readers, device buffers, frame synthesis, the torch child
+process -- are in tests/frame_cases.py.  The bodies here stay the file's own: packed pixels go through frames_view and
+process_frames' argument list, not through a descriptor as the other families do.
 """
 import ctypes as C
-import glob
+import functools
 import os
 import subprocess
 import sys
@@ -26,22 +26,10 @@ if ROOT not in sys.path:
 
 from meterelf_amd import _hip  # noqa: E402
 
+from tests import frame_cases as fc  # noqa: E402
+from tests.frame_cases import env, read_packed_dev as _read_dev, to_layout  # noqa: E402,F401
+
 FORMATS = ('bgr', 'rgb', 'bgra', 'rgba')
-ORDER = {'bgr': [0, 1, 2], 'rgb': [2, 1, 0], 'bgra': [0, 1, 2], 'rgba': [2, 1, 0]}
-
-
-def to_layout(bgr, fmt, pad=0, rng=None, view3=False):
-    """The frames `bgr` (N, H, W, 3) in layout `fmt`, rows padded by `pad` pixels (a [:, :, :W] view of a wider array), the 4th
-    byte random; view3: a 4-byte layout handed over as its 3-channel view (rgba[..., :3])."""
-    rng = rng if rng is not None else np.random.default_rng(0)
-    (n, H, W, _) = bgr.shape
-    ch = 4 if fmt in ('bgra', 'rgba') else 3
-    full = rng.integers(0, 256, size=(n, H, W + pad, ch), dtype=np.uint8)
-    full[:, :, :W, :3] = bgr[..., ORDER[fmt]]
-    out = full[:, :, :W]
-    if view3 and ch == 4:
-        return out[..., :3], fmt[:3]
-    return out, fmt
 
 
 # ------------------------------------------------------------------------------------------------------------- CPU ---------
@@ -140,48 +128,6 @@ def test_new_kernels_metadata():
 
 
 # ------------------------------------------------------------------------------------------------------------- GPU ---------
-@pytest.fixture(scope='module')
-def env():
-    if _hip.device_count() < 1:
-        pytest.fail('GPU tests need an MI355X: no HIP device visible (no CPU fallback exists)')
-    from meterelf_amd import MeterReader, _params
-    from meterelf_amd._image import imread_bgr
-    out = {}
-    for sd in ('sample-images1', 'sample-images2'):
-        params = _params.load(os.path.join(GOLDEN, sd, 'params.yml'))
-        frames = [imread_bgr(f) for f in sorted(glob.glob(os.path.join(GOLDEN, sd, '*.jpg')))]
-        out[sd] = dict(params=params, frames=frames, reader=MeterReader(params))
-    yield out
-    for e in out.values():
-        e['reader'].close()
-
-
-class DevBuf:
-    """Device copy of the bytes [ptr, ptr + extent) of a host array, allocated to exactly that size."""
-
-    def __init__(self, v):
-        self.hip = _hip_rt()
-        self.d = C.c_void_p()
-        assert self.hip.hipMalloc(C.byref(self.d), C.c_size_t(max(v.extent, 1))) == 0
-        assert self.hip.hipMemcpy(self.d, C.c_void_p(v.ptr), C.c_size_t(v.extent), 1) == 0
-
-    def free(self):
-        self.hip.hipFree(self.d)
-
-
-def _hip_rt():
-    from tests.helpers import hip_runtime
-    return hip_runtime()
-
-
-def _read_dev(ctx, v, **kw):
-    buf = DevBuf(v)
-    try:
-        return ctx.process_frames_dev(buf.d.value, v.pixel_format, v.n, v.H, v.W, v.row_pitch, v.frame_stride, **kw)
-    finally:
-        buf.free()
-
-
 def _check_all_layouts(reader, bgr, tag, rng):
     want = reader.read_frames(bgr).tobytes()
     for fmt in FORMATS:
@@ -212,29 +158,12 @@ def test_fixture_frames_every_layout(env, sd, count):
     assert e['reader'].read_frame_views(arr, f).tobytes() == e['reader'].read_frames(bgr).tobytes()
 
 
-def _synth(frames, n, seed):
-    """n shifted + noisy fixture frames, every 9th a constant frame (Dials not found)."""
-    rng = np.random.default_rng(seed)
-    shapes = [f.shape for f in frames]
-    base = [f for f in frames if f.shape == max(set(shapes), key=shapes.count)]   # the fixture's frame size
-    out = np.empty((n,) + base[0].shape, np.uint8)
-    for i in range(n):
-        if i % 9 == 4:
-            out[i] = 128
-            continue
-        (dx, dy) = rng.integers(-8, 9, size=2)
-        img = np.roll(base[i % len(base)], (int(dy), int(dx)), axis=(0, 1)).astype(np.int16)
-        img += rng.integers(-2, 3, size=img.shape).astype(np.int16)
-        out[i] = np.clip(img, 0, 255).astype(np.uint8)
-    return out
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize('kind,kernel', [('fast', 'mfma'), ('gen', 'gen'), ('dot4', 'dot4')])
 def test_each_match_kernel(env, monkeypatch, kind, kernel):
     from meterelf_amd import MeterReader
     e = env['sample-images1']
-    bgr = _synth(e['frames'], 256, 5)
+    bgr = fc.synth(e['frames'], 256, 5)
     monkeypatch.setenv('MELF_MATCH', kind)
     r = MeterReader(e['params'])
     try:
@@ -297,7 +226,7 @@ def test_frame_edges_and_batch_sizes(env):
     e = env['sample-images1']
     reader = e['reader']
     rng = np.random.default_rng(11)
-    src = _synth(e['frames'], 70, 3)
+    src = fc.synth(e['frames'], 70, 3)
     assert (reader.read_frames(src)['status'] == _hip.FRAME_OK).sum() > 40
     for (H, W) in ((410, 300), (400, 290)):
         bgr = np.ascontiguousarray(src[:12, :H, :W])
@@ -315,49 +244,28 @@ def test_frame_edges_and_batch_sizes(env):
 
 
 @pytest.mark.gpu
-def test_resident_lanes_two_streams(env):
+def test_resident_lanes_two_streams(env):  # noqa: F811
     """melf_ctx_set_frames_resident(1) and two caller streams: every call's records equal a single synchronous call's."""
     from meterelf_amd import MeterReader
     e = env['sample-images2']
-    hip = _hip_rt()
-    src = _synth(e['frames'], 96, 21)
-    rsz = _hip.RESULT_DTYPE.itemsize
+    src = fc.synth(e['frames'], 96, 21)
     r = MeterReader(e['params'])
     bufs = []
-    streams = [C.c_void_p(), C.c_void_p()]
-    d_res = C.c_void_p()
     try:
         want = r.read_frames(src)
         assert (want['status'] == _hip.FRAME_OK).sum() > 48
-        views = []
+        calls = []
         for (k, fmt) in enumerate(FORMATS):
             (arr, f) = to_layout(src, fmt, 4 * k, np.random.default_rng(k))
             v = _hip.frames_view(arr, f)
-            bufs.append(DevBuf(v))
-            views.append(v)
-        for s in streams:
-            assert hip.hipStreamCreate(C.byref(s)) == 0
-        assert hip.hipMalloc(C.byref(d_res), C.c_size_t(8 * len(src) * rsz)) == 0
-        r.ctx.set_frames_resident(True)
-        for i in range(8):   # formats in turn, streams alternating, each call its own records
-            v = views[i % 4]
-            r.ctx.process_frames_dev(bufs[i % 4].d.value, v.pixel_format, v.n, v.H, v.W, v.row_pitch, v.frame_stride,
-                                     d_results_ptr=d_res.value + i * len(src) * rsz, want_host=False, stream=streams[i % 2].value)
-        r.ctx.sync()
-        got = np.zeros(8 * len(src), _hip.RESULT_DTYPE)
-        assert hip.hipMemcpy(C.c_void_p(got.ctypes.data), d_res, C.c_size_t(got.nbytes), 2) == 0
-        for i in range(8):
-            assert got[i * len(src):(i + 1) * len(src)].tobytes() == want.tobytes(), i
-        r.ctx.set_frames_resident(False)
+            bufs.append(fc.DevBuf(v.ptr, v.extent))
+            calls.append((functools.partial(r.ctx.process_frames_dev, bufs[-1].d.value, v.pixel_format, v.n, v.H, v.W, v.row_pitch,
+                                            v.frame_stride), want.tobytes()))
+        fc.resident_calls(r, len(src), calls, 8, lambda i: i % 4)   # formats in turn, streams alternating, each call its own records
     finally:
         r.close()
         for b in bufs:
             b.free()
-        if d_res.value:
-            hip.hipFree(d_res)
-        for s in streams:
-            if s.value:
-                hip.hipStreamDestroy(s)
 
 
 @pytest.mark.gpu
@@ -368,10 +276,11 @@ def test_argument_errors_launch_nothing(env):
     bgr = np.stack(e['frames'][2:6])
     (n, H, W, _) = bgr.shape
     bgra = np.zeros((n, H, W, 4), np.uint8)
-    buf = DevBuf(_hip.frames_view(bgra, 'bgra'))
+    view = _hip.frames_view(bgra, 'bgra')
+    buf = fc.DevBuf(view.ptr, view.extent)
     try:
         ctx.set_profiling(1)
-        before = {k: cnt for (k, (_ms, cnt)) in ctx.timings().items()}
+        before = fc.launch_counts(ctx)
         out = np.zeros(n, _hip.RESULT_DTYPE)
         F = _hip.MelfFrames
         bad = [
@@ -394,11 +303,11 @@ def test_argument_errors_launch_nothing(env):
                 assert L.melf_last_error().decode()
         assert L.melf_process_frames_dev(ctx._h, C.c_void_p(buf.d.value), None, None, _hip._ptr(out), None) == -1
         assert L.melf_process_frames(ctx._h, C.c_void_p(bgra.ctypes.data), None, _hip._ptr(out)) == -1
-        assert {k: cnt for (k, (_ms, cnt)) in ctx.timings().items()} == before
+        assert fc.launch_counts(ctx) == before
         # a good descriptor runs
         good = F(_hip.PIX_BGRA, n, H, W, W * 4, H * W * 4)
         assert L.melf_process_frames_dev(ctx._h, C.c_void_p(buf.d.value), C.byref(good), None, _hip._ptr(out), None) == 0
-        assert {k: cnt for (k, (_ms, cnt)) in ctx.timings().items()} != before
+        assert fc.launch_counts(ctx) != before
     finally:
         ctx.set_profiling(0)
         buf.free()
@@ -406,75 +315,5 @@ def test_argument_errors_launch_nothing(env):
 
 @pytest.mark.gpu
 def test_torch_tensors_in_a_torch_process():
-    """read_frame_views with torch tensors, in a child process that imports torch first (see the module docstring)."""
-    env = dict(os.environ)
-    env['PYTHONPATH'] = ROOT + os.pathsep + env.get('PYTHONPATH', '')
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), 'torch'], env=env, cwd=ROOT, stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=900)
-    assert p.returncode == 0 and b'torch path ok' in p.stdout, (p.returncode, p.stdout[-3000:], p.stderr[-3000:])
-
-
-def _torch_main():
-    import torch  # before the package loads the library: one HIP runtime in the process
-    from meterelf_amd import MeterReader, _params
-    from meterelf_amd._image import imread_bgr
-    params = _params.load(os.path.join(GOLDEN, 'sample-images1', 'params.yml'))
-    files = sorted(glob.glob(os.path.join(GOLDEN, 'sample-images1', '*.jpg')))
-    frames = [imread_bgr(f) for f in files]
-    bgr = _synth(frames, 128, 9)
-    reader = MeterReader(params, device=0)
-    dev = torch.device('cuda', 0)
-    want = reader.read_frames(bgr)
-    assert (want['status'] == _hip.FRAME_OK).sum() > 64
-    rsz = _hip.RESULT_DTYPE.itemsize
-    rng = np.random.default_rng(1)
-    for fmt in FORMATS:
-        for pad in (0, 11):
-            (arr, f) = to_layout(bgr, fmt, pad, rng)
-            full = torch.from_numpy(arr.base).to(dev)
-            t = full[:, :, :bgr.shape[2]]
-            assert not _hip.frames_view(t, f).copied
-            assert reader.read_frame_views(t, f).tobytes() == want.tobytes(), (fmt, pad)
-            # host tensors take the host path
-            assert reader.read_frame_views(torch.from_numpy(np.ascontiguousarray(arr)), f).tobytes() == want.tobytes(), (fmt, pad)
-            # out=: records into a device tensor on the current stream, nothing synchronised
-            out = torch.empty((len(bgr), rsz), dtype=torch.uint8, device=dev)
-            assert reader.read_frame_views(t, f, out=out) is out
-            torch.cuda.synchronize()
-            assert out.cpu().numpy().tobytes() == want.tobytes(), (fmt, pad, 'out')
-    # a 3-channel view of RGBA pixels, and a buffer of exactly the descriptor's extent (torch.as_strided)
-    (arr, f) = to_layout(bgr, 'rgba', 6, rng, view3=True)
-    v = _hip.frames_view(arr, f)
-    flat = torch.from_numpy(np.frombuffer((C.c_uint8 * v.extent).from_address(v.ptr), np.uint8).copy()).to(dev)
-    t = torch.as_strided(flat, arr.shape, (v.frame_stride, v.row_pitch, 4, 1))
-    assert _hip.frames_view(t, f).pixel_format == _hip.PIX_RGBA
-    assert reader.read_frame_views(t, f).tobytes() == want.tobytes()
-    # resident frames, two caller streams, out= on each
-    reader.ctx.set_frames_resident(True)
-    (sa, sb) = (torch.cuda.Stream(dev), torch.cuda.Stream(dev))
-    outs = []
-    tb = torch.from_numpy(to_layout(bgr, 'bgra', 3, rng)[0].base).to(dev)[:, :, :bgr.shape[2]]
-    torch.cuda.synchronize()
-    for i in range(6):
-        with torch.cuda.stream(sa if i % 2 == 0 else sb):
-            o = torch.empty((len(bgr), rsz), dtype=torch.uint8, device=dev)
-            reader.read_frame_views(tb, 'bgra', out=o)
-            outs.append(o)
-    torch.cuda.synchronize()
-    for o in outs:
-        assert o.cpu().numpy().tobytes() == want.tobytes()
-    reader.ctx.set_frames_resident(False)
-    # a tensor on another device than the reader's is an error
-    if torch.cuda.device_count() > 1:
-        try:
-            reader.read_frame_views(t.to(torch.device('cuda', 1)), f)
-            raise AssertionError('a frame tensor on another GPU was accepted')
-        except ValueError:
-            pass
-    reader.ctx.sync()
-    reader.close()
-    print('torch path ok')
-
-
-if __name__ == '__main__' and sys.argv[1:] == ['torch']:
-    _torch_main()
+    """read_frame_views with torch tensors, in a child process that imports torch first (tests/frame_cases.py says why)."""
+    fc.run_torch_child('packed')

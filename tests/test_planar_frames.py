@@ -4,18 +4,18 @@ MeterReader.read_planar_frames).
 
 The contract: the records of a planar frame are byte-identical to read_frames() of the packed BGR frame whose pixel (x, y) is
 (B[y][x], G[y][x], R[y][x]).  No colour conversion is involved, so the same records are also held against the CPU oracle on that
-BGR frame, under the rules of tests/test_gpu_parity.py (_compare_records: status, match position, float32 match value bit-exact,
-positions and angles to 1e-9, the digits).
+BGR frame, under the rules of tests/test_gpu_parity.py (its _compare_records: status, match position, float32 match value
+bit-exact, positions and angles to 1e-9, the digits).
 
 CPU tests: the descriptor against the header, planar_frames_view's mapping of numpy arrays and torch CPU tensors, the exported
 symbols, the new kernels' code-object notes.  GPU tests: the fixtures as RGB, BGR and GBR planes, every match kernel, plane
 offsets and pitches that put the three planes at every byte phase relative to each other and to the base, meter_rect at every
 parity and at the frame's edges, 4-plane tensors, batch sizes, random bytes, 1080p with six dials, resident lanes on two caller
-streams, rejected descriptors, torch tensors (in a child process that imports torch first: tests/test_pixel_formats.py says why).
+streams, rejected descriptors, torch tensors (in a child process that imports torch first: tests/frame_cases.py says why).
 Every device buffer has exactly the descriptor's extent and ends where its allocation ends.
 """
 import ctypes as C
-import glob
+import functools
 import os
 import shutil
 import subprocess
@@ -31,48 +31,11 @@ if ROOT not in sys.path:
 
 from meterelf_amd import _hip  # noqa: E402
 
-ORDERS3 = ('rgb', 'bgr', 'gbr')
-POS_TOL = 1e-9   # tests/test_gpu_parity.py
+from tests import frame_cases as fc  # noqa: E402
+from tests.frame_cases import PLANAR, env, extent_planes as _desc_extent, pitched_planes as pitched, to_planes  # noqa: E402,F401
 
-
-def to_planes(bgr, order, rng=None):
-    """(n, H, W, 3) BGR -> the (n, C, H, W) array whose planes are in `order`; a 4th plane ('a' / 'x') is random."""
-    rng = rng if rng is not None else np.random.default_rng(0)
-    (n, H, W, _c) = bgr.shape
-    out = rng.integers(0, 256, size=(n, len(order), H, W), dtype=np.uint8)
-    for (k, ch) in enumerate(order):
-        if ch in 'bgr':
-            out[:, k] = bgr[..., 'bgr'.index(ch)]
-    return out
-
-
-def pitched(bgr, order='rgb', row_pad=0, gaps=(0, 0, 0), stride_pad=0, rng=None):
-    """A byte buffer of exactly the descriptor's extent: the three planes in `order`, rows row_pad bytes longer than W, gaps[k]
-    bytes in front of plane k (gaps[0]: from the frame's first byte), stride_pad bytes behind a frame's last sample; random
-    filling.  Returns (buffer, MelfPlanarFrames)."""
-    rng = rng if rng is not None else np.random.default_rng(0)
-    (n, H, W, _c) = bgr.shape
-    rp = W + row_pad
-    span = (H - 1) * rp + W
-    off = {}
-    at = 0
-    for (k, ch) in enumerate(order):
-        at += gaps[k]
-        off[ch] = at
-        at += span
-    fs = at + stride_pad
-    buf = rng.integers(0, 256, size=(n - 1) * fs + at, dtype=np.uint8)
-    for ch in 'bgr':
-        plane = bgr[..., 'bgr'.index(ch)]
-        for f in range(n):
-            dst = np.lib.stride_tricks.as_strided(buf[f * fs + off[ch]:], shape=(H, W), strides=(rp, 1))
-            dst[...] = plane[f]
-    desc = _hip.MelfPlanarFrames(n, H, W, 0, off['b'], off['g'], off['r'], rp, fs)
-    return buf, desc
-
-
-def _desc_extent(d):
-    return (d.n - 1) * d.frame_stride + max(d.b_offset, d.g_offset, d.r_offset) + (d.H - 1) * d.row_pitch + d.W
+ORDERS3 = PLANAR.formats
+DevBuf = fc.DevBuf.at_end   # every device buffer of this file ends where its allocation ends
 
 
 # ------------------------------------------------------------------------------------------------------------- CPU ---------
@@ -244,97 +207,16 @@ def test_planar_kernels_metadata():
 
 
 # ------------------------------------------------------------------------------------------------------------- GPU ---------
-@pytest.fixture(scope='module')
-def env():
-    if _hip.device_count() < 1:
-        pytest.fail('GPU tests need an MI355X: no HIP device visible (no CPU fallback exists)')
-    from meterelf_amd import MeterReader, _params
-    from meterelf_amd._image import imread_bgr
-    out = {}
-    for sd in ('sample-images1', 'sample-images2'):
-        pfile = os.path.join(GOLDEN, sd, 'params.yml')
-        params = _params.load(pfile)
-        frames = [imread_bgr(f) for f in sorted(glob.glob(os.path.join(GOLDEN, sd, '*.jpg')))]
-        out[sd] = dict(pfile=pfile, params=params, frames=frames, reader=MeterReader(params))
-    yield out
-    for e in out.values():
-        e['reader'].close()
-
-
-def _hip_rt():
-    from tests.helpers import hip_runtime
-    return hip_runtime()
-
-
-class DevBuf:
-    """Device copy of `nbytes` bytes at host address `ptr`: exactly that many bytes, ending where the allocation (a whole number
-    of 4 KiB pages) ends.  phase 0..3: the copy's address has that residue modulo 4 instead, as close to the allocation's end as
-    that allows (at most 3 bytes of it left behind the copy)."""
-
-    def __init__(self, ptr, nbytes, phase=None):
-        self.hip = _hip_rt()
-        self.base = C.c_void_p()
-        alloc = (nbytes + 3 + 4095) // 4096 * 4096
-        assert self.hip.hipMalloc(C.byref(self.base), C.c_size_t(alloc)) == 0
-        at = alloc - nbytes
-        if phase is not None:
-            at -= (self.base.value + at - phase) % 4
-        assert at >= 0
-        self.d = C.c_void_p(self.base.value + at)
-        assert self.hip.hipMemcpy(self.d, C.c_void_p(ptr), C.c_size_t(nbytes), 1) == 0
-
-    def free(self):
-        self.hip.hipFree(self.base)
-
-
-def _read_both(reader, ptr, desc, extent, phase=None):
-    """Records of the host path and of the device path (a device buffer of exactly `extent` bytes)."""
-    assert extent == _desc_extent(desc)
-    host = reader.ctx.process_planes(ptr, desc)
-    buf = DevBuf(ptr, extent, phase)
-    try:
-        dev = reader.ctx.process_planes_dev(buf.d.value, desc)
-    finally:
-        buf.free()
-    return host, dev
+_read_both = functools.partial(fc.read_both, PLANAR)
 
 
 def _check_orders(reader, bgr, tag, rng, orders=ORDERS3, want=None):
     """Every order, as an (N, C, H, W) array and as a pitched buffer with odd gaps, host and device, against read_frames."""
-    if want is None:
-        want = reader.read_frames(bgr)
-    wb = want.tobytes()
-    for (k, order) in enumerate(orders):
-        arr = to_planes(bgr, order, rng)
-        assert reader.read_planar_frames(arr, order).tobytes() == wb, (tag, order, 'reader')
-        v = _hip.planar_frames_view(arr, order)
-        assert not v.copied
-        (host, dev) = _read_both(reader, v.ptr, v.descriptor(), v.extent)
-        assert host.tobytes() == wb, (tag, order, 'host')
-        assert dev.tobytes() == wb, (tag, order, 'device')
-        (buf, desc) = pitched(bgr, order[:3], row_pad=5 + k, gaps=(k, 1 + k, 6 - k), stride_pad=7 + k, rng=rng)
-        (host, dev) = _read_both(reader, buf.ctypes.data, desc, buf.nbytes)
-        assert host.tobytes() == wb, (tag, order, 'pitched host')
-        assert dev.tobytes() == wb, (tag, order, 'pitched device')
-    return want
+    return fc.check_formats(PLANAR, reader, (bgr,), tag, rng, orders, want)
 
 
-def _compare_records(recs, ores, ndials=4, tag=''):
-    """tests/test_gpu_parity.py's rules for the whole path."""
-    for i in range(len(recs)):
-        (r, o) = (recs[i], ores[i])
-        assert int(r['status']) == o.status, (tag, i, int(r['status']), o.status)
-        assert (int(r['match_x']), int(r['match_y'])) == (o.match_x, o.match_y), (tag, i)
-        assert float(r['match_val']) == o.match_val, (tag, i)  # float32, bit-exact
-        if o.status == 0:
-            assert np.allclose(r['pos'][:ndials], list(o.pos)[:ndials], rtol=0, atol=POS_TOL), (tag, i)
-            assert np.allclose(r['angle'][:ndials], list(o.angle)[:ndials], rtol=0, atol=POS_TOL), (tag, i)
-            assert abs(float(r['value']) - o.value) < 1e-8, (tag, i)
-            assert int(float(r['value'])) == int(o.value), (tag, i)  # the three dial digits
-        elif o.status == 2:
-            assert int(r['failed_dial']) == o.failed_dial, (tag, i)
-        elif o.status == 3:
-            assert int(r['unreadable_mask']) == o.unreadable_mask, (tag, i)
+def _check_source(reader, src, tag, rng, **kw):
+    return _check_orders(reader, *src, tag, rng, **kw)
 
 
 @pytest.mark.gpu
@@ -342,6 +224,7 @@ def _compare_records(recs, ores, ndials=4, tag=''):
 def test_fixture_frames(env, sd, count):
     """The fixture frames as RGB, BGR and GBR planes: byte-identical to read_frames of the BGR frames, and equal to the oracle."""
     from oracle import pyoracle as po
+    from tests.test_gpu_parity import _compare_records
     e = env[sd]
     assert len(e['frames']) == count
     oparams = po.Params(e['pfile'])
@@ -363,48 +246,12 @@ def test_fixture_frames(env, sd, count):
     assert ok == ok_bgr and ok > 0   # the equality is one of readings, not of failures
 
 
-def _synth(frames, n, seed):
-    """n shifted + noisy fixture frames, every 9th a constant frame (Dials not found): as tests/test_pixel_formats.py."""
-    rng = np.random.default_rng(seed)
-    shapes = [f.shape for f in frames]
-    base = [f for f in frames if f.shape == max(set(shapes), key=shapes.count)]
-    out = np.empty((n,) + base[0].shape, np.uint8)
-    for i in range(n):
-        if i % 9 == 4:
-            out[i] = 128
-            continue
-        (dx, dy) = rng.integers(-8, 9, size=2)
-        img = np.roll(base[i % len(base)], (int(dy), int(dx)), axis=(0, 1)).astype(np.int16)
-        img += rng.integers(-2, 3, size=img.shape).astype(np.int16)
-        out[i] = np.clip(img, 0, 255).astype(np.uint8)
-    return out
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize('kind,kernel', [('fast', 'mfma'), ('gen', 'gen'), ('dot4', 'dot4')])
-def test_each_match_kernel(env, monkeypatch, kind, kernel):
-    from meterelf_amd import MeterReader
-    e = env['sample-images1']
-    bgr = _synth(e['frames'], 256, 5)
-    monkeypatch.setenv('MELF_MATCH', kind)
-    r = MeterReader(e['params'])
-    try:
-        want = r.read_frames(bgr)
-        assert r.ctx.last_match()['kernel'] == kernel
-        assert (want['status'] == _hip.FRAME_DIALS_NOT_FOUND).sum() >= 28 and (want['status'] == _hip.FRAME_OK).sum() >= 128
-        rng = np.random.default_rng(7)
-        for (k, order) in enumerate(ORDERS3):
-            (buf, desc) = pitched(bgr, order, row_pad=3, gaps=(1, 2, 1), stride_pad=9 + k, rng=rng)
-            assert r.ctx.process_planes(buf.ctypes.data, desc).tobytes() == want.tobytes(), (kind, order, 'host')
-            assert r.ctx.last_match()['kernel'] == kernel
-            dbuf = DevBuf(buf.ctypes.data, buf.nbytes)
-            try:
-                assert r.ctx.process_planes_dev(dbuf.d.value, desc).tobytes() == want.tobytes(), (kind, order, 'device')
-            finally:
-                dbuf.free()
-            assert r.ctx.last_match()['kernel'] == kernel
-    finally:
-        r.close()
+def test_each_match_kernel(env, monkeypatch, kind, kernel):  # noqa: F811
+    layout = fc.as_pitched(PLANAR, lambda k: dict(row_pad=3, gaps=(1, 2, 1), stride_pad=9 + k))
+    fc.each_match_kernel(env['sample-images1'], monkeypatch, kind, kernel, [(PLANAR, ORDERS3, layout)], n=256, seed=5, rng_seed=7,
+                         min_not_found=28, min_ok=128)
 
 
 @pytest.mark.gpu
@@ -415,7 +262,7 @@ def test_plane_phases(env, monkeypatch, kind):
     kernel and every phase of the dial reader's unaligned dwords."""
     from meterelf_amd import MeterReader
     e = env['sample-images1']
-    bgr = _synth(e['frames'], 12, 17)
+    bgr = fc.synth(e['frames'], 12, 17)
     monkeypatch.setenv('MELF_MATCH', kind)
     r = MeterReader(e['params'])
     try:
@@ -443,41 +290,16 @@ def test_plane_phases(env, monkeypatch, kind):
         r.close()
 
 
-def _params_with_rect(tmp_path, sd, rect, tag):
-    import yaml
-    from meterelf_amd import _params
-    src = os.path.join(GOLDEN, sd)
-    with open(os.path.join(src, 'params.yml')) as fp:
-        data = yaml.safe_load(fp)
-    data['meter_rect'] = {'top_left': [rect[0], rect[1]], 'bottom_right': [rect[2], rect[3]]}
-    d = tmp_path / tag
-    d.mkdir()
-    with open(d / 'params.yml', 'w') as fp:
-        yaml.safe_dump(data, fp)
-    shutil.copy(os.path.join(src, 'dials_gray.png'), d / 'dials_gray.png')
-    return _params.load(str(d / 'params.yml'))
-
-
 @pytest.mark.gpu
-def test_odd_geometry(env, tmp_path):
+def test_odd_geometry(env, tmp_path):  # noqa: F811
     """meter_rect (50, 160)-(300, 410) moved to all four parities of (x0, y0), and given sizes of all four parities; the frames
     are shifted by as much, so that the meter stays inside."""
-    from meterelf_amd import MeterReader
-    e = env['sample-images1']
-    src = _synth(e['frames'], 40, 3)
-    rng = np.random.default_rng(13)
     cases = ((0, 0, 0, 0), (1, 0, 0, 0), (0, 1, 0, 0), (1, 1, 0, 0),       # origins at the four parities of (x, y), even sizes
              (0, 0, -1, 0), (0, 0, 0, -1), (0, 0, -1, -1),                  # sizes at the other three parities
              (1, 1, -1, -1), (1, 0, 1, 1), (3, 5, 1, 1), (2, 3, 2, 1))
-    for (k, (dx, dy, dw, dh)) in enumerate(cases):
-        params = _params_with_rect(tmp_path, 'sample-images1', (50 + dx, 160 + dy, 300 + dx + dw, 410 + dy + dh), 'odd%d' % k)
-        bgr = np.roll(src, (dy, dx), axis=(1, 2))
-        r = MeterReader(params)
-        try:
-            want = _check_orders(r, bgr, (dx, dy, dw, dh), rng, orders=(ORDERS3[k % 3], ORDERS3[(k + 1) % 3]))
-            assert (want['status'] == _hip.FRAME_OK).sum() > 20, (dx, dy, dw, dh)
-        finally:
-            r.close()
+    fc.odd_geometry(PLANAR, env['sample-images1'], tmp_path, cases,
+                    lambda r, src, tag, rng, k: _check_source(r, src, tag, rng, orders=(ORDERS3[k % 3], ORDERS3[(k + 1) % 3])),
+                    n=40, seed=3, rng_seed=13, min_ok=20)
 
 
 @pytest.mark.gpu
@@ -490,15 +312,12 @@ def test_frame_edges_and_batch_sizes(env, tmp_path):
     e = env['sample-images1']
     reader = e['reader']
     rng = np.random.default_rng(11)
-    src = _synth(e['frames'], 131, 3)
-    for (H, W) in ((410, 300), (399, 290), (405, 297)):
-        bgr = np.ascontiguousarray(src[:12, :H, :W])
-        want = _check_orders(reader, bgr, (H, W), rng)
-        assert (want['status'] == _hip.FRAME_OK).sum() >= 6, (H, W)
+    src = fc.synth(e['frames'], 131, 3)
+    fc.frame_edges(PLANAR, reader, src, rng, 12, ((410, 300), (399, 290), (405, 297)), _check_source, min_ok=6)
     # the crop in the frame's top left corner, and filling the frame
     for (k, (y1, x1)) in enumerate(((480, 640), (410, 300))):
         bgr = np.ascontiguousarray(src[:12, 160:y1, 50:x1])
-        r = MeterReader(_params_with_rect(tmp_path, 'sample-images1', (0, 0, 250, 250), 'corner%d' % k))
+        r = MeterReader(fc.params_with_rect(tmp_path, 'sample-images1', (0, 0, 250, 250), 'corner%d' % k))
         try:
             want = _check_orders(r, bgr, ('corner', y1, x1), rng)
             assert (want['status'] == _hip.FRAME_OK).sum() >= 6
@@ -510,10 +329,8 @@ def test_frame_edges_and_batch_sizes(env, tmp_path):
                     assert host.tobytes() == want.tobytes() and dev.tobytes() == want.tobytes(), (y1, x1, phase, order)
         finally:
             r.close()
-    want = reader.read_frames(src)
-    assert (want['status'] == _hip.FRAME_OK).sum() > 80
-    for (k, n) in enumerate((1, 31, 32, 33, 131)):
-        _check_orders(reader, src[:n], n, rng, orders=(ORDERS3[k % 3],), want=want[:n])
+    fc.batch_sizes(PLANAR, reader, src, rng, (1, 31, 32, 33, 131), lambda k: (ORDERS3[k % 3],),
+                   lambda r, src_, tag, rng_, formats, want: _check_source(r, src_, tag, rng_, orders=formats, want=want), min_ok=80)
 
 
 @pytest.mark.gpu
@@ -523,7 +340,7 @@ def test_four_plane_tensors(env):
     e = env['sample-images1']
     reader = e['reader']
     rng = np.random.default_rng(41)
-    bgr = _synth(e['frames'], 24, 8)
+    bgr = fc.synth(e['frames'], 24, 8)
     want = reader.read_frames(bgr)
     assert (want['status'] == _hip.FRAME_OK).sum() >= 12
     for order in ('rgba', 'rgbx', 'bgra', 'bgrx'):
@@ -610,48 +427,11 @@ def test_1080p_six_dials_padded(env, tmp_path):
 
 
 @pytest.mark.gpu
-def test_resident_lanes_two_streams(env):
+def test_resident_lanes_two_streams(env):  # noqa: F811
     """melf_ctx_set_frames_resident(1) and two caller streams, layouts alternating: every call's records equal a synchronous call's."""
-    from meterelf_amd import MeterReader
-    e = env['sample-images2']
-    hip = _hip_rt()
-    bgr = _synth(e['frames'], 96, 21)
-    rsz = _hip.RESULT_DTYPE.itemsize
-    r = MeterReader(e['params'])
-    bufs = []
-    streams = [C.c_void_p(), C.c_void_p()]
-    d_res = C.c_void_p()
-    try:
-        want = r.read_frames(bgr)
-        assert (want['status'] == _hip.FRAME_OK).sum() > 48
-        descs = []
-        for (k, order) in enumerate(('rgb', 'bgr', 'gbr', 'rgb')):
-            (buf, desc) = pitched(bgr, order, row_pad=k, gaps=(k, 1, 2), stride_pad=3 * k, rng=np.random.default_rng(k))
-            bufs.append(DevBuf(buf.ctypes.data, buf.nbytes))
-            descs.append(desc)
-            assert r.ctx.process_planes_dev(bufs[-1].d.value, desc).tobytes() == want.tobytes(), order   # the synchronous call
-        for s in streams:
-            assert hip.hipStreamCreate(C.byref(s)) == 0
-        assert hip.hipMalloc(C.byref(d_res), C.c_size_t(8 * len(bgr) * rsz)) == 0
-        r.ctx.set_frames_resident(True)
-        for i in range(8):
-            r.ctx.process_planes_dev(bufs[i % 4].d.value, descs[i % 4], d_results_ptr=d_res.value + i * len(bgr) * rsz, want_host=False,
-                                     stream=streams[i % 2].value)
-        r.ctx.sync()
-        got = np.zeros(8 * len(bgr), _hip.RESULT_DTYPE)
-        assert hip.hipMemcpy(C.c_void_p(got.ctypes.data), d_res, C.c_size_t(got.nbytes), 2) == 0
-        for i in range(8):
-            assert got[i * len(bgr):(i + 1) * len(bgr)].tobytes() == want.tobytes(), i
-        r.ctx.set_frames_resident(False)
-    finally:
-        r.close()
-        for b in bufs:
-            b.free()
-        if d_res.value:
-            hip.hipFree(d_res)
-        for s in streams:
-            if s.value:
-                hip.hipStreamDestroy(s)
+    fc.resident_lanes_two_streams(PLANAR, env['sample-images2'], ('rgb', 'bgr', 'gbr', 'rgb'),
+                                  lambda k: dict(row_pad=k, gaps=(k, 1, 2), stride_pad=3 * k), n=96, seed=21, min_ok=48,
+                                  keep_host=False)
 
 
 @pytest.mark.gpu
@@ -666,7 +446,7 @@ def test_argument_errors_launch_nothing(env):
     buf = DevBuf(host.ctypes.data, host.nbytes)
     try:
         ctx.set_profiling(1)
-        before = {k: cnt for (k, (_ms, cnt)) in ctx.timings().items()}
+        before = fc.launch_counts(ctx)
         out = np.zeros(n, _hip.RESULT_DTYPE)
         F = _hip.MelfPlanarFrames
         bad = [
@@ -708,10 +488,10 @@ def test_argument_errors_launch_nothing(env):
         empty = F(0, H, W, 0, 0, P, 2 * P, W, 3 * P)
         assert L.melf_process_planes_dev(ctx._h, None, C.byref(empty), None, None, None) == 0
         assert L.melf_process_planes(ctx._h, None, C.byref(empty), None) == 0
-        assert {k: cnt for (k, (_ms, cnt)) in ctx.timings().items()} == before
+        assert fc.launch_counts(ctx) == before
         # a good descriptor runs; planes that touch without overlapping are good
         assert L.melf_process_planes_dev(ctx._h, C.c_void_p(buf.d.value), C.byref(good), None, _hip._ptr(out), None) == 0
-        assert {k: cnt for (k, (_ms, cnt)) in ctx.timings().items()} != before
+        assert fc.launch_counts(ctx) != before
         assert out.tobytes() == e['reader'].read_frames(bgr).tobytes()
     finally:
         ctx.set_profiling(0)
@@ -721,84 +501,4 @@ def test_argument_errors_launch_nothing(env):
 @pytest.mark.gpu
 def test_torch_tensors_in_a_torch_process():
     """read_planar_frames with torch tensors, in a child process that imports torch first."""
-    env = dict(os.environ)
-    env['PYTHONPATH'] = ROOT + os.pathsep + env.get('PYTHONPATH', '')
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), 'torch'], env=env, cwd=ROOT, stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=900)
-    assert p.returncode == 0 and b'torch planar path ok' in p.stdout, (p.returncode, p.stdout[-3000:], p.stderr[-3000:])
-
-
-def _torch_main():
-    import torch  # before the package loads the library: one HIP runtime in the process
-    from meterelf_amd import MeterReader, _params
-    from meterelf_amd._image import imread_bgr
-    params = _params.load(os.path.join(GOLDEN, 'sample-images1', 'params.yml'))
-    files = sorted(glob.glob(os.path.join(GOLDEN, 'sample-images1', '*.jpg')))
-    frames = [imread_bgr(f) for f in files]
-    bgr = _synth(frames, 128, 9)
-    reader = MeterReader(params, device=0)
-    dev = torch.device('cuda', 0)
-    want = reader.read_frames(bgr)
-    assert (want['status'] == _hip.FRAME_OK).sum() > 64
-    rsz = _hip.RESULT_DTYPE.itemsize
-    rng = np.random.default_rng(1)
-    (n, H, W, _c) = bgr.shape
-    for order in ('rgb', 'bgr', 'gbr', 'rgba', 'bgrx'):
-        t = torch.from_numpy(to_planes(bgr, order, rng)).to(dev)
-        assert t.is_contiguous() and not _hip.planar_frames_view(t, order).copied
-        assert reader.read_planar_frames(t, order).tobytes() == want.tobytes(), order
-        # host tensors take the host path
-        assert reader.read_planar_frames(t.cpu(), order).tobytes() == want.tobytes(), order
-        # out=: records into a device tensor on the current stream, nothing synchronised
-        out = torch.empty((n, rsz), dtype=torch.uint8, device=dev)
-        assert reader.read_planar_frames(t, order, out=out) is out
-        torch.cuda.synchronize()
-        assert out.cpu().numpy().tobytes() == want.tobytes(), (order, 'out')
-    # the NCHW batch a torch pipeline holds: what the interleaved route gives, without the interleaved copy
-    t = torch.from_numpy(to_planes(bgr, 'rgb')).to(dev)
-    assert _hip.frames_view(t.permute(0, 2, 3, 1), 'rgb').copied            # today's route copies (unchanged)
-    assert reader.read_frame_views(t.permute(0, 2, 3, 1), 'rgb').tobytes() == want.tobytes()
-    # x[:, :3] of a 4-plane tensor, every other frame, a crop of a larger tensor: in place
-    t4 = torch.from_numpy(to_planes(bgr, 'rgba', rng)).to(dev)
-    assert not _hip.planar_frames_view(t4[:, :3], 'rgb').copied
-    assert reader.read_planar_frames(t4[:, :3], 'rgb').tobytes() == want.tobytes()
-    assert not _hip.planar_frames_view(t[::2], 'rgb').copied
-    assert reader.read_planar_frames(t[::2], 'rgb').tobytes() == want[::2].tobytes()
-    big = torch.randint(0, 256, (n, 3, H + 3, W + 5), dtype=torch.uint8, device=dev)
-    big[:, :, 2:2 + H, 1:1 + W] = t
-    view = big[:, :, 2:2 + H, 1:1 + W]
-    v = _hip.planar_frames_view(view, 'rgb')
-    assert not v.copied and v.row_pitch == W + 5 and v.ptr == big.data_ptr() + 2 * (W + 5) + 1
-    assert reader.read_planar_frames(view, 'rgb').tobytes() == want.tobytes()
-    # a permuted NHWC tensor goes through one packed copy, with out= too
-    nhwc = torch.from_numpy(np.ascontiguousarray(bgr[..., ::-1])).to(dev)
-    assert _hip.planar_frames_view(nhwc.permute(0, 3, 1, 2), 'rgb').copied
-    out = torch.empty((n, rsz), dtype=torch.uint8, device=dev)
-    reader.read_planar_frames(nhwc.permute(0, 3, 1, 2), 'rgb', out=out)
-    torch.cuda.synchronize()
-    assert out.cpu().numpy().tobytes() == want.tobytes()
-    with pytest.raises(ValueError):
-        reader.read_planar_frames(t.cpu(), 'rgb', out=out)   # out= takes device frames only
-    with pytest.raises(ValueError):
-        reader.read_planar_frames(t, 'rgba')
-    # resident frames, two caller streams, out= on each
-    reader.ctx.set_frames_resident(True)
-    (sa, sb) = (torch.cuda.Stream(dev), torch.cuda.Stream(dev))
-    outs = []
-    torch.cuda.synchronize()
-    for i in range(6):
-        with torch.cuda.stream(sa if i % 2 == 0 else sb):
-            o = torch.empty((n, rsz), dtype=torch.uint8, device=dev)
-            reader.read_planar_frames(view if i % 3 else t4, 'rgb' if i % 3 else 'rgba', out=o)
-            outs.append(o)
-    torch.cuda.synchronize()
-    for o in outs:
-        assert o.cpu().numpy().tobytes() == want.tobytes()
-    reader.ctx.set_frames_resident(False)
-    reader.ctx.sync()
-    reader.close()
-    print('torch planar path ok')
-
-
-if __name__ == '__main__' and sys.argv[1:] == ['torch']:
-    _torch_main()
+    fc.run_torch_child('planar')

@@ -13,19 +13,19 @@ limited range), in integers, >> arithmetic:
 
     bytes of a macropixel (pixels 2 k, 2 k + 1 of a row):  yuyv: Y0 U Y1 V    uyvy: U Y0 V Y1    yvyu: Y0 V Y1 U
 
-yuv422_to_bgr below is its numpy restatement (U and V repeated twice along x): the expected side of every comparison.
-bgr_to_yuv422 (float BT.601 limited-range RGB -> YUV, the mean of each horizontal pixel pair for chroma, round half up, clip) only
-makes test input from the BGR fixtures; nothing is compared against it.
+yuv_to_bgr(Y, U, V, 1, 0) of tests/frame_cases.py is its numpy restatement (yuv422_to_bgr here; U and V repeated twice along x):
+the expected side of every comparison.  bgr_to_yuv422 (float BT.601 limited-range RGB -> YUV, the mean of each horizontal pixel
+pair for chroma, round half up, clip) only makes test input from the BGR fixtures; nothing is compared against it.
 
 CPU tests: the descriptor against the header, yuv422_frames_view's mapping of numpy arrays and torch CPU tensors, the restatement
 against hand-derived triples and byte positions, the new kernels' code-object notes.  GPU tests: the conversion kernel for all
 2^24 triples at both pixels of a macropixel, records against the BGR path of the converted frames on the fixtures, with every
 match kernel, at every parity of the crop, at the frame edges, at 1080p, over lanes and streams, with torch tensors (in a child
-process that imports torch first: tests/test_pixel_formats.py says why).  Every device buffer has exactly the descriptor's
+process that imports torch first: tests/frame_cases.py says why).  Every device buffer has exactly the descriptor's
 extent: a load past it is a fault.
 """
 import ctypes as C
-import glob
+import functools
 import os
 import shutil
 import subprocess
@@ -40,86 +40,12 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from meterelf_amd import _hip  # noqa: E402
+from tests import frame_cases as fc  # noqa: E402
+from tests.frame_cases import DevBuf, F422, conventional422 as conventional, env, pitched422 as pitched  # noqa: E402,F401
 
-FORMATS = ('yuyv', 'uyvy', 'yvyu')
-
-
-# ------------------------------------------------------------------------------------------------- the conversion, restated ---
-def yuv422_to_bgr(Y, U, V):
-    """Y (..., H, W), U and V (..., H, W / 2) uint8 -> (..., H, W, 3) uint8 BGR: the module docstring's arithmetic."""
-    yy = np.maximum(Y.astype(np.int32) - 16, 0) * 1220542 + (1 << 19)
-    u = np.repeat(U.astype(np.int32) - 128, 2, axis=-1)
-    v = np.repeat(V.astype(np.int32) - 128, 2, axis=-1)
-    out = np.empty(Y.shape + (3,), np.uint8)
-    out[..., 2] = np.clip((yy + 1673527 * v) >> 20, 0, 255)
-    out[..., 1] = np.clip((yy - 852492 * v - 409993 * u) >> 20, 0, 255)
-    out[..., 0] = np.clip((yy + 2116026 * u) >> 20, 0, 255)
-    return out
-
-
-def bgr_to_yuv422(bgr):
-    """Test input only: (..., H, W, 3) BGR -> Y (..., H, W), U, V (..., H, W / 2): float BT.601 limited range, the mean of each
-    horizontal pixel pair for chroma, round half up, clip."""
-    f = bgr.astype(np.float64)
-    (b, g, r) = (f[..., 0], f[..., 1], f[..., 2])
-    y = 16.0 + (65.481 * r + 128.553 * g + 24.966 * b) / 255.0
-    u = 128.0 + (-37.797 * r - 74.203 * g + 112.0 * b) / 255.0
-    v = 128.0 + (112.0 * r - 93.786 * g - 18.214 * b) / 255.0
-
-    def mean2(p):
-        return (p[..., 0::2] + p[..., 1::2]) / 2.0
-
-    def q(p):
-        return np.clip(np.floor(p + 0.5), 0, 255).astype(np.uint8)
-    return q(y), q(mean2(u)), q(mean2(v))
-
-
-def fill422(out, Y, U, V, fmt):
-    """Writes the samples into out (..., H, W, 2) in layout fmt."""
-    if fmt == 'yuyv':
-        out[..., 0] = Y
-        out[..., 0::2, 1] = U
-        out[..., 1::2, 1] = V
-    elif fmt == 'uyvy':
-        out[..., 1] = Y
-        out[..., 0::2, 0] = U
-        out[..., 1::2, 0] = V
-    else:
-        assert fmt == 'yvyu'
-        out[..., 0] = Y
-        out[..., 0::2, 1] = V
-        out[..., 1::2, 1] = U
-    return out
-
-
-def conventional(Y, U, V, fmt, pad=0, rng=None):
-    """The (N, H, W, 2) array of the samples in layout fmt; pad > 0: a [:, :, :W] view of an array whose rows are pad pixels
-    longer (random filling; pad even, so that the rows stay 4-byte aligned)."""
-    rng = rng if rng is not None else np.random.default_rng(0)
-    (n, H, W) = Y.shape
-    assert pad % 2 == 0
-    full = rng.integers(0, 256, size=(n, H, W + pad, 2), dtype=np.uint8)
-    return fill422(full[:, :, :W], Y, U, V, fmt)
-
-
-def pitched(Y, U, V, fmt, row_pad=0, stride_pad=0, rng=None):
-    """A byte buffer of exactly the descriptor's extent with padded rows and a padded frame stride: (buffer, MelfYuv422Frames).
-    row_pad, stride_pad: bytes, multiples of 4."""
-    rng = rng if rng is not None else np.random.default_rng(0)
-    (n, H, W) = Y.shape
-    assert row_pad % 4 == 0 and stride_pad % 4 == 0
-    rp = 2 * W + row_pad
-    end = (H - 1) * rp + 2 * W
-    fs = end + stride_pad
-    buf = rng.integers(0, 256, size=(n - 1) * fs + end, dtype=np.uint8)
-    assert buf.ctypes.data % 4 == 0
-    packed = fill422(np.empty((n, H, W, 2), np.uint8), Y, U, V, fmt).reshape(n, H, 2 * W)
-    for f in range(n):
-        for y in range(H):
-            o = f * fs + y * rp
-            buf[o:o + 2 * W] = packed[f, y]
-    desc = _hip.MelfYuv422Frames(_hip.YUV422_CODES[fmt], _hip.YUV_BT601_LIMITED, n, H, W, 0, rp, fs)
-    return buf, desc
+FORMATS = F422.formats
+yuv422_to_bgr = F422.bgr_of        # the conversion above, restated (tests/frame_cases.py: yuv_to_bgr)
+bgr_to_yuv422 = F422.from_bgr      # test input only
 
 
 # ------------------------------------------------------------------------------------------------------------- CPU ---------
@@ -314,74 +240,16 @@ def test_yuv422_kernels_metadata():
 
 
 # ------------------------------------------------------------------------------------------------------------- GPU ---------
-@pytest.fixture(scope='module')
-def env():
-    if _hip.device_count() < 1:
-        pytest.fail('GPU tests need an MI355X: no HIP device visible (no CPU fallback exists)')
-    from meterelf_amd import MeterReader, _params
-    from meterelf_amd._image import imread_bgr
-    out = {}
-    for sd in ('sample-images1', 'sample-images2'):
-        params = _params.load(os.path.join(GOLDEN, sd, 'params.yml'))
-        frames = [imread_bgr(f) for f in sorted(glob.glob(os.path.join(GOLDEN, sd, '*.jpg')))]
-        out[sd] = dict(params=params, frames=frames, reader=MeterReader(params))
-    yield out
-    for e in out.values():
-        e['reader'].close()
-
-
-def _hip_rt():
-    from tests.helpers import hip_runtime
-    return hip_runtime()
-
-
-class DevBuf:
-    """Device copy of `nbytes` bytes at host address `ptr`, allocated to exactly that size."""
-
-    def __init__(self, ptr, nbytes):
-        self.hip = _hip_rt()
-        self.d = C.c_void_p()
-        assert self.hip.hipMalloc(C.byref(self.d), C.c_size_t(max(nbytes, 1))) == 0
-        assert self.hip.hipMemcpy(self.d, C.c_void_p(ptr), C.c_size_t(nbytes), 1) == 0
-
-    def free(self):
-        self.hip.hipFree(self.d)
-
-
-def _desc_extent(d):
-    return (d.n - 1) * d.frame_stride + (d.H - 1) * d.row_pitch + 2 * d.W
-
-
-def _read_both(reader, ptr, desc, extent):
-    """Records of the host path and of the device path (a device buffer of exactly `extent` bytes)."""
-    assert extent == _desc_extent(desc)
-    host = reader.ctx.process_yuv422(ptr, desc)
-    buf = DevBuf(ptr, extent)
-    try:
-        dev = reader.ctx.process_yuv422_dev(buf.d.value, desc)
-    finally:
-        buf.free()
-    return host, dev
+_read_both = functools.partial(fc.read_both, F422)
 
 
 def _check_formats(reader, Y, U, V, tag, rng, formats=FORMATS, want=None):
     """Every format, conventional and pitched, host and device, against read_frames of the converted frames."""
-    if want is None:
-        want = reader.read_frames(yuv422_to_bgr(Y, U, V))
-    wb = want.tobytes()
-    for fmt in formats:
-        arr = conventional(Y, U, V, fmt, 0, rng)
-        assert reader.read_yuv422_frames(arr, fmt).tobytes() == wb, (tag, fmt, 'reader')
-        v = _hip.yuv422_frames_view(arr, fmt)
-        assert not v.copied
-        (host, dev) = _read_both(reader, v.ptr, v.descriptor(), v.extent)
-        assert host.tobytes() == wb, (tag, fmt, 'host')
-        assert dev.tobytes() == wb, (tag, fmt, 'device')
-        (buf, desc) = pitched(Y, U, V, fmt, row_pad=12, stride_pad=20, rng=rng)
-        (host, dev) = _read_both(reader, buf.ctypes.data, desc, buf.nbytes)
-        assert host.tobytes() == wb, (tag, fmt, 'pitched host')
-        assert dev.tobytes() == wb, (tag, fmt, 'pitched device')
-    return want
+    return fc.check_formats(F422, reader, (Y, U, V), tag, rng, formats, want)
+
+
+def _check_source(reader, src, tag, rng, **kw):
+    return _check_formats(reader, *src, tag, rng, **kw)
 
 
 @pytest.mark.gpu
@@ -427,144 +295,46 @@ def test_yuv422_to_bgr_padded_pitch_and_stride(env, fmt):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize('sd,count,min_ok', [('sample-images1', 81, 79), ('sample-images2', 223, 222)])
-def test_fixture_frames(env, sd, count, min_ok):
-    e = env[sd]
-    assert len(e['frames']) == count
-    rng = np.random.default_rng(count)
-    shapes = {}
-    for fr in e['frames']:
-        shapes.setdefault(fr.shape, []).append(fr)
-    ok = 0
-    for (shape, group) in shapes.items():
-        (Y, U, V) = bgr_to_yuv422(np.stack(group))
-        want = _check_formats(e['reader'], Y, U, V, '%s %s' % (sd, shape), rng)
-        ok += int((want['status'] == _hip.FRAME_OK).sum())
-    print('%s: %d of %d converted frames read OK' % (sd, ok, count))
-    assert ok >= min_ok, ok   # the comparison is one of readings, not of failures
-
-
-def _synth(frames, n, seed):
-    """n shifted + noisy fixture frames, every 9th a constant frame (Dials not found): as tests/test_pixel_formats.py."""
-    rng = np.random.default_rng(seed)
-    shapes = [f.shape for f in frames]
-    base = [f for f in frames if f.shape == max(set(shapes), key=shapes.count)]
-    out = np.empty((n,) + base[0].shape, np.uint8)
-    for i in range(n):
-        if i % 9 == 4:
-            out[i] = 128
-            continue
-        (dx, dy) = rng.integers(-8, 9, size=2)
-        img = np.roll(base[i % len(base)], (int(dy), int(dx)), axis=(0, 1)).astype(np.int16)
-        img += rng.integers(-2, 3, size=img.shape).astype(np.int16)
-        out[i] = np.clip(img, 0, 255).astype(np.uint8)
-    return out
+def test_fixture_frames(env, sd, count, min_ok):  # noqa: F811
+    fc.fixture_frames(F422, env[sd], sd, count, min_ok, _check_source)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize('kind,kernel', [('fast', 'mfma'), ('gen', 'gen'), ('dot4', 'dot4')])
-def test_each_match_kernel(env, monkeypatch, kind, kernel):
-    from meterelf_amd import MeterReader
-    e = env['sample-images1']
-    (Y, U, V) = bgr_to_yuv422(_synth(e['frames'], 256, 5))
-    monkeypatch.setenv('MELF_MATCH', kind)
-    r = MeterReader(e['params'])
-    try:
-        want = r.read_frames(yuv422_to_bgr(Y, U, V))
-        assert r.ctx.last_match()['kernel'] == kernel
-        assert (want['status'] == _hip.FRAME_DIALS_NOT_FOUND).sum() >= 28 and (want['status'] == _hip.FRAME_OK).sum() >= 128
-        rng = np.random.default_rng(7)
-        for fmt in FORMATS:
-            arr = conventional(Y, U, V, fmt, 6, rng)
-            v = _hip.yuv422_frames_view(arr, fmt)
-            assert not v.copied
-            assert r.ctx.process_yuv422(v.ptr, v.descriptor()).tobytes() == want.tobytes(), (kind, fmt, 'host')
-            assert r.ctx.last_match()['kernel'] == kernel
-            buf = DevBuf(v.ptr, v.extent)
-            try:
-                assert r.ctx.process_yuv422_dev(buf.d.value, v.descriptor()).tobytes() == want.tobytes(), (kind, fmt, 'device')
-            finally:
-                buf.free()
-            assert r.ctx.last_match()['kernel'] == kernel
-    finally:
-        r.close()
-
-
-def _params_with_rect(tmp_path, sd, rect, tag):
-    import yaml
-    from meterelf_amd import _params
-    src = os.path.join(GOLDEN, sd)
-    with open(os.path.join(src, 'params.yml')) as fp:
-        data = yaml.safe_load(fp)
-    data['meter_rect'] = {'top_left': [rect[0], rect[1]], 'bottom_right': [rect[2], rect[3]]}
-    d = tmp_path / tag
-    d.mkdir()
-    with open(d / 'params.yml', 'w') as fp:
-        yaml.safe_dump(data, fp)
-    shutil.copy(os.path.join(src, 'dials_gray.png'), d / 'dials_gray.png')
-    return _params.load(str(d / 'params.yml'))
+def test_each_match_kernel(env, monkeypatch, kind, kernel):  # noqa: F811
+    layout = fc.as_conventional(F422, lambda fmt: 6)
+    fc.each_match_kernel(env['sample-images1'], monkeypatch, kind, kernel, [(F422, FORMATS, layout)], n=256, seed=5, rng_seed=7,
+                         min_not_found=28, min_ok=128)
 
 
 @pytest.mark.gpu
-def test_odd_geometry(env, tmp_path):
+def test_odd_geometry(env, tmp_path):  # noqa: F811
     """meter_rect (50, 160)-(300, 410) moved to all four parities of (x0, y0), and given sizes of all four parities (the far edge
     of the crop odd or even whatever the origin); the frames are shifted by as much, so that the meter stays inside."""
-    from meterelf_amd import MeterReader
-    e = env['sample-images1']
-    src = _synth(e['frames'], 40, 3)
-    rng = np.random.default_rng(13)
     cases = ((0, 0, 0, 0), (1, 0, 0, 0), (0, 1, 0, 0), (1, 1, 0, 0),       # origins at the four parities of (x, y), even sizes
              (0, 0, -1, 0), (0, 0, 0, -1), (0, 0, -1, -1),                  # sizes at the other three parities: far edge odd
              (1, 1, -1, -1), (1, 0, 1, 1), (3, 5, 1, 1), (1, 2, 2, 1))      # odd origin with an even / odd far edge
-    for (k, (dx, dy, dw, dh)) in enumerate(cases):
-        params = _params_with_rect(tmp_path, 'sample-images1', (50 + dx, 160 + dy, 300 + dx + dw, 410 + dy + dh), 'odd%d' % k)
-        bgr = np.roll(src, (dy, dx), axis=(1, 2))
-        (Y, U, V) = bgr_to_yuv422(bgr)
-        r = MeterReader(params)
-        try:
-            want = _check_formats(r, Y, U, V, (dx, dy, dw, dh), rng, formats=(FORMATS[k % 3], FORMATS[(k + 1) % 3]))
-            assert (want['status'] == _hip.FRAME_OK).sum() > 20, (dx, dy, dw, dh)
-        finally:
-            r.close()
+    fc.odd_geometry(F422, env['sample-images1'], tmp_path, cases,
+                    lambda r, src, tag, rng, k: _check_source(r, src, tag, rng, formats=(FORMATS[k % 3], FORMATS[(k + 1) % 3])),
+                    n=40, seed=3, rng_seed=13, min_ok=20)
 
 
 @pytest.mark.gpu
-def test_frame_edges_and_batch_sizes(env):
+def test_frame_edges_and_batch_sizes(env):  # noqa: F811
     """meter_rect (50, 160)-(300, 410) reaching the right and bottom frame edges, and past them (numpy clamp), with an odd frame
     height, device buffers of exactly the descriptor's extent (every _read_both); batch sizes around the 32-frame group and
     above the 128 frames of a host-path chunk."""
     e = env['sample-images1']
-    reader = e['reader']
     rng = np.random.default_rng(11)
-    src = _synth(e['frames'], 131, 3)
-    for (H, W) in ((410, 300), (399, 290), (405, 298)):
-        (Y, U, V) = bgr_to_yuv422(np.ascontiguousarray(src[:12, :H, :W]))
-        want = _check_formats(reader, Y, U, V, (H, W), rng)
-        assert (want['status'] == _hip.FRAME_OK).sum() >= 6, (H, W)
-    (Y, U, V) = bgr_to_yuv422(src)
-    want = reader.read_frames(yuv422_to_bgr(Y, U, V))
-    assert (want['status'] == _hip.FRAME_OK).sum() > 80
-    for (k, n) in enumerate((1, 31, 32, 33, 131)):
-        _check_formats(reader, Y[:n], U[:n], V[:n], n, rng, formats=(FORMATS[k % 3],), want=want[:n])
+    src = fc.synth(e['frames'], 131, 3)
+    fc.frame_edges(F422, e['reader'], src, rng, 12, ((410, 300), (399, 290), (405, 298)), _check_source, min_ok=6)
+    fc.batch_sizes(F422, e['reader'], src, rng, (1, 31, 32, 33, 131), lambda k: (FORMATS[k % 3],), _check_source, min_ok=80)
 
 
 @pytest.mark.gpu
-def test_random_frames(env):
+def test_random_frames(env):  # noqa: F811
     """Uniform random Y, U, V bytes: every clamp of the conversion is hit, in every kernel that converts."""
-    e = env['sample-images1']
-    rng = np.random.default_rng(99)
-    (H, W) = e['frames'][2].shape[:2]
-    n = 40
-    (Y, U, V) = (rng.integers(0, 256, (n, H, W), dtype=np.uint8), rng.integers(0, 256, (n, H, W // 2), dtype=np.uint8),
-                 rng.integers(0, 256, (n, H, W // 2), dtype=np.uint8))
-    bgr = yuv422_to_bgr(Y, U, V)
-    assert (bgr == 0).any() and (bgr == 255).any()
-    # half of the frames carry a fixture's meter, so that the dial reader runs on them (random chroma under it)
-    (Yf, _, _) = bgr_to_yuv422(np.stack(e['frames'][2:2 + n // 2]))
-    Y[::2] = Yf
-    U[::2] = 128 + (U[::2].astype(np.int16) - 128) // 16
-    V[::2] = 128 + (V[::2].astype(np.int16) - 128) // 16
-    want = _check_formats(e['reader'], Y, U, V, 'random', rng)
-    assert (want['status'] != _hip.FRAME_DIALS_NOT_FOUND).sum() >= n // 4
+    fc.random_yuv_frames(F422, env['sample-images1'], _check_source, n=40, seed=99)
 
 
 @pytest.mark.gpu
@@ -608,51 +378,11 @@ def test_1080p_six_dials_uyvy_padded(env, tmp_path):
 
 
 @pytest.mark.gpu
-def test_resident_lanes_two_streams(env):
+def test_resident_lanes_two_streams(env):  # noqa: F811
     """melf_ctx_set_frames_resident(1) and two caller streams, formats alternating: every call's records equal a synchronous call's."""
-    from meterelf_amd import MeterReader
-    e = env['sample-images2']
-    hip = _hip_rt()
-    (Y, U, V) = bgr_to_yuv422(_synth(e['frames'], 96, 21))
-    rsz = _hip.RESULT_DTYPE.itemsize
-    r = MeterReader(e['params'])
-    bufs = []
-    streams = [C.c_void_p(), C.c_void_p()]
-    d_res = C.c_void_p()
-    try:
-        want = r.read_frames(yuv422_to_bgr(Y, U, V))
-        assert (want['status'] == _hip.FRAME_OK).sum() > 48
-        descs = []
-        keep = []
-        for (k, fmt) in enumerate(('yuyv', 'uyvy', 'yvyu', 'uyvy')):
-            (buf, desc) = pitched(Y, U, V, fmt, row_pad=4 * k, stride_pad=8 * k, rng=np.random.default_rng(k))
-            keep.append(buf)
-            bufs.append(DevBuf(buf.ctypes.data, buf.nbytes))
-            descs.append(desc)
-            # the synchronous call
-            assert r.ctx.process_yuv422_dev(bufs[-1].d.value, desc).tobytes() == want.tobytes(), fmt
-        for s in streams:
-            assert hip.hipStreamCreate(C.byref(s)) == 0
-        assert hip.hipMalloc(C.byref(d_res), C.c_size_t(8 * len(Y) * rsz)) == 0
-        r.ctx.set_frames_resident(True)
-        for i in range(8):
-            r.ctx.process_yuv422_dev(bufs[i % 4].d.value, descs[i % 4], d_results_ptr=d_res.value + i * len(Y) * rsz, want_host=False,
-                                     stream=streams[i % 2].value)
-        r.ctx.sync()
-        got = np.zeros(8 * len(Y), _hip.RESULT_DTYPE)
-        assert hip.hipMemcpy(C.c_void_p(got.ctypes.data), d_res, C.c_size_t(got.nbytes), 2) == 0
-        for i in range(8):
-            assert got[i * len(Y):(i + 1) * len(Y)].tobytes() == want.tobytes(), i
-        r.ctx.set_frames_resident(False)
-    finally:
-        r.close()
-        for b in bufs:
-            b.free()
-        if d_res.value:
-            hip.hipFree(d_res)
-        for s in streams:
-            if s.value:
-                hip.hipStreamDestroy(s)
+    fc.resident_lanes_two_streams(F422, env['sample-images2'], ('yuyv', 'uyvy', 'yvyu', 'uyvy'),
+                                  lambda k: dict(row_pad=4 * k, stride_pad=8 * k), n=96, seed=21, min_ok=48,
+                                  keep_host=True)
 
 
 @pytest.mark.gpu
@@ -669,7 +399,7 @@ def test_argument_errors_launch_nothing(env):
     buf = DevBuf(host.ctypes.data, host.nbytes)
     try:
         ctx.set_profiling(1)
-        before = {k: cnt for (k, (_ms, cnt)) in ctx.timings().items()}
+        before = fc.launch_counts(ctx)
         out = np.zeros(n, _hip.RESULT_DTYPE)
         bgr_out = np.zeros((n, H, W, 3), np.uint8)
         F = _hip.MelfYuv422Frames
@@ -708,10 +438,10 @@ def test_argument_errors_launch_nothing(env):
         assert L.melf_process_yuv422_dev(ctx._h, None, C.byref(empty), None, None, None) == 0
         assert L.melf_process_yuv422(ctx._h, None, C.byref(empty), None) == 0
         assert L.melf_yuv422_to_bgr(ctx._h, None, C.byref(empty), None) == 0
-        assert {k: cnt for (k, (_ms, cnt)) in ctx.timings().items()} == before
+        assert fc.launch_counts(ctx) == before
         # a good descriptor runs
         assert L.melf_process_yuv422_dev(ctx._h, C.c_void_p(buf.d.value), C.byref(good), None, _hip._ptr(out), None) == 0
-        assert {k: cnt for (k, (_ms, cnt)) in ctx.timings().items()} != before
+        assert fc.launch_counts(ctx) != before
         assert out.tobytes() == e['reader'].read_frames(yuv422_to_bgr(Y, U, V)).tobytes()
     finally:
         ctx.set_profiling(0)
@@ -721,74 +451,4 @@ def test_argument_errors_launch_nothing(env):
 @pytest.mark.gpu
 def test_torch_tensors_in_a_torch_process():
     """read_yuv422_frames with torch tensors, in a child process that imports torch first."""
-    env = dict(os.environ)
-    env['PYTHONPATH'] = ROOT + os.pathsep + env.get('PYTHONPATH', '')
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), 'torch'], env=env, cwd=ROOT, stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=900)
-    assert p.returncode == 0 and b'torch yuv422 path ok' in p.stdout, (p.returncode, p.stdout[-3000:], p.stderr[-3000:])
-
-
-def _torch_main():
-    import torch  # before the package loads the library: one HIP runtime in the process
-    from meterelf_amd import MeterReader, _params
-    from meterelf_amd._image import imread_bgr
-    params = _params.load(os.path.join(GOLDEN, 'sample-images1', 'params.yml'))
-    files = sorted(glob.glob(os.path.join(GOLDEN, 'sample-images1', '*.jpg')))
-    frames = [imread_bgr(f) for f in files]
-    (Y, U, V) = bgr_to_yuv422(_synth(frames, 128, 9))
-    reader = MeterReader(params, device=0)
-    dev = torch.device('cuda', 0)
-    want = reader.read_frames(yuv422_to_bgr(Y, U, V))
-    assert (want['status'] == _hip.FRAME_OK).sum() > 64
-    rsz = _hip.RESULT_DTYPE.itemsize
-    rng = np.random.default_rng(1)
-    W = Y.shape[2]
-    for fmt in FORMATS:
-        for pad in (0, 12):
-            arr = conventional(Y, U, V, fmt, pad, rng)
-            full = torch.from_numpy(arr.base if pad else arr).to(dev)
-            t = full[:, :, :W]
-            assert not _hip.yuv422_frames_view(t, fmt).copied
-            assert reader.read_yuv422_frames(t, fmt).tobytes() == want.tobytes(), (fmt, pad)
-            # host tensors take the host path
-            assert reader.read_yuv422_frames(torch.from_numpy(np.ascontiguousarray(arr)), fmt).tobytes() == want.tobytes(), (fmt, pad)
-            # out=: records into a device tensor on the current stream, nothing synchronised
-            out = torch.empty((len(Y), rsz), dtype=torch.uint8, device=dev)
-            assert reader.read_yuv422_frames(t, fmt, out=out) is out
-            torch.cuda.synchronize()
-            assert out.cpu().numpy().tobytes() == want.tobytes(), (fmt, pad, 'out')
-    # every other frame in place; a row pitch that is no multiple of 4 goes through one packed copy
-    t = torch.from_numpy(conventional(Y, U, V, 'uyvy')).to(dev)
-    assert not _hip.yuv422_frames_view(t[::2], 'uyvy').copied
-    assert reader.read_yuv422_frames(t[::2], 'uyvy').tobytes() == want[::2].tobytes()
-    wide = torch.zeros((len(Y), Y.shape[1], W + 1, 2), dtype=torch.uint8, device=dev)
-    wide[:, :, :W] = t
-    assert _hip.yuv422_frames_view(wide[:, :, :W], 'uyvy').copied
-    out = torch.empty((len(Y), rsz), dtype=torch.uint8, device=dev)
-    reader.read_yuv422_frames(wide[:, :, :W], 'uyvy', out=out)
-    torch.cuda.synchronize()
-    assert out.cpu().numpy().tobytes() == want.tobytes()
-    with pytest.raises(ValueError):
-        reader.read_yuv422_frames(t.cpu(), 'uyvy', out=out)   # out= takes device frames only
-    # resident frames, two caller streams, out= on each
-    reader.ctx.set_frames_resident(True)
-    (sa, sb) = (torch.cuda.Stream(dev), torch.cuda.Stream(dev))
-    outs = []
-    tn = torch.from_numpy(conventional(Y, U, V, 'yuyv', 4, rng).base).to(dev)[:, :, :W]
-    torch.cuda.synchronize()
-    for i in range(6):
-        with torch.cuda.stream(sa if i % 2 == 0 else sb):
-            o = torch.empty((len(Y), rsz), dtype=torch.uint8, device=dev)
-            reader.read_yuv422_frames(tn if i % 3 else t, 'yuyv' if i % 3 else 'uyvy', out=o)
-            outs.append(o)
-    torch.cuda.synchronize()
-    for o in outs:
-        assert o.cpu().numpy().tobytes() == want.tobytes()
-    reader.ctx.set_frames_resident(False)
-    reader.ctx.sync()
-    reader.close()
-    print('torch yuv422 path ok')
-
-
-if __name__ == '__main__' and sys.argv[1:] == ['torch']:
-    _torch_main()
+    fc.run_torch_child('yuv422')

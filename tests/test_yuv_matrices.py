@@ -11,16 +11,14 @@ below makes of it under the descriptor's matrix (include/meterelf_hip.h), >> ari
     G = clamp((yy + (1 << 19) + CGV * v + CGU * u) >> 20, 0, 255)
     B = clamp((yy + (1 << 19) + CBU * u)           >> 20, 0, 255)
 
-MATRIX below restates the table of offsets and coefficients, convert() the arithmetic: the expected side of every comparison.
-forward() (float64 RGB -> YUV per matrix and range, chroma means, round half up, clip) only makes test input from the BGR
-fixtures; nothing is compared against it.  test_yuv_frames.py and test_yuv422_frames.py keep pinning code 0 bit for bit, and code
+MATRIX of tests/frame_cases.py restates the table of offsets and coefficients, its yuv_to_bgr the arithmetic: the expected side of
+every comparison.  Its bgr_to_yuv (float64 RGB -> YUV per matrix and range from Kr and Kb, chroma means, round half up, clip) only
+makes test input from the BGR fixtures; nothing is compared against it.  test_yuv_frames.py and test_yuv422_frames.py keep pinning code 0 bit for bit, and code
 1 as a rejected descriptor.
 """
 import ctypes as C
 import functools
-import glob
 import os
-import shutil
 import subprocess
 import sys
 
@@ -34,17 +32,11 @@ if ROOT not in sys.path:
 
 from meterelf_amd import _hip  # noqa: E402
 
-# code: (YOFF, CY, CRV, CGV, CGU, CBU)
-MATRIX = {
-    0: (16, 1220542, 1673527, -852492, -409993, 2116026),
-    2: (0, 1048576, 1470104, -748826, -360853, 1858077),
-    3: (16, 1220945, 1879825, -558796, -223607, 2215014),
-    4: (0, 1048576, 1651297, -490864, -196424, 1945738),
-}
+from tests import frame_cases as fc  # noqa: E402
+from tests.frame_cases import F420, F422, MATRIX, STANDARD, DevBuf, env, packed422  # noqa: E402,F401
+
 NAMES = {'bt601': 0, 'bt601-full': 2, 'bt709': 3, 'bt709-full': 4}
 NEW = (2, 3, 4)
-# code: (Kr, Kb, limited range)
-STANDARD = {0: (0.299, 0.114, True), 2: (0.299, 0.114, False), 3: (0.2126, 0.0722, True), 4: (0.2126, 0.0722, False)}
 
 
 def exact_coefficients(code):
@@ -58,145 +50,26 @@ def exact_coefficients(code):
 
 
 # ------------------------------------------------------------------------------------------------- the conversion, restated ---
-def convert(Y, u, v, code):
-    """Y (uint8), u = U - 128 and v = V - 128 (int32, broadcastable to Y) -> (..., 3) uint8 BGR under matrix `code`."""
-    (yoff, cy, crv, cgv, cgu, cbu) = MATRIX[code]
-    yy = np.maximum(Y.astype(np.int32) - yoff, 0) * cy + (1 << 19)
-    out = np.empty(Y.shape + (3,), np.uint8)
-    out[..., 2] = np.clip((yy + crv * v) >> 20, 0, 255)
-    out[..., 1] = np.clip((yy + cgv * v + cgu * u) >> 20, 0, 255)
-    out[..., 0] = np.clip((yy + cbu * u) >> 20, 0, 255)
-    return out
-
-
 def yuv420_to_bgr(Y, U, V, code):
     """Y (..., H, W), U and V (..., H / 2, W / 2): the nearest chroma sample."""
-    u = np.repeat(np.repeat(U.astype(np.int32) - 128, 2, axis=-2), 2, axis=-1)
-    v = np.repeat(np.repeat(V.astype(np.int32) - 128, 2, axis=-2), 2, axis=-1)
-    return convert(Y, u, v, code)
+    return fc.yuv_to_bgr(Y, U, V, 1, 1, code)
 
 
 def yuv422_to_bgr(Y, U, V, code):
     """Y (..., H, W), U and V (..., H, W / 2): the two pixels of a macropixel share its chroma."""
-    return convert(Y, np.repeat(U.astype(np.int32) - 128, 2, axis=-1), np.repeat(V.astype(np.int32) - 128, 2, axis=-1), code)
-
-
-def forward(bgr, code):
-    """Test input only: (..., H, W, 3) BGR -> full-resolution float64 (y, u, v) of the standard and range of `code`."""
-    (kr, kb, limited) = STANDARD[code]
-    f = bgr.astype(np.float64)
-    (b, g, r) = (f[..., 0], f[..., 1], f[..., 2])
-    yl = kr * r + (1.0 - kr - kb) * g + kb * b
-    (pb, pr) = ((b - yl) / (2.0 * (1.0 - kb)), (r - yl) / (2.0 * (1.0 - kr)))
-    if limited:
-        return 16.0 + yl * 219.0 / 255.0, 128.0 + pb * 224.0 / 255.0, 128.0 + pr * 224.0 / 255.0
-    return yl, 128.0 + pb, 128.0 + pr
-
-
-def _q(p):
-    return np.clip(np.floor(p + 0.5), 0, 255).astype(np.uint8)
+    return fc.yuv_to_bgr(Y, U, V, 1, 0, code)
 
 
 def forward_both(bgr, code):
-    """Test input only: the 4:2:0 planes (2 x 2 chroma mean) and the 4:2:2 planes (pair mean) of the BGR frames, in chunks."""
-    (n, H, W) = bgr.shape[:3]
-    Y = np.empty((n, H, W), np.uint8)
-    (U0, V0) = (np.empty((n, H // 2, W // 2), np.uint8), np.empty((n, H // 2, W // 2), np.uint8))
-    (U2, V2) = (np.empty((n, H, W // 2), np.uint8), np.empty((n, H, W // 2), np.uint8))
-    for i in range(0, n, 16):
-        (y, u, v) = forward(bgr[i:i + 16], code)
-        Y[i:i + 16] = _q(y)
-        for (p, d0, d2) in ((u, U0, U2), (v, V0, V2)):
-            d0[i:i + 16] = _q((p[..., 0::2, 0::2] + p[..., 0::2, 1::2] + p[..., 1::2, 0::2] + p[..., 1::2, 1::2]) / 4.0)
-            d2[i:i + 16] = _q((p[..., 0::2] + p[..., 1::2]) / 2.0)
-    return (Y, U0, V0), (Y, U2, V2)
+    """Test input only: the 4:2:0 planes (2 x 2 chroma mean) and the 4:2:2 planes (pair mean) of the BGR frames."""
+    return fc.bgr_to_yuv(bgr, 1, 1, code), fc.bgr_to_yuv(bgr, 1, 0, code)
 
 
 @functools.lru_cache(maxsize=None)
 def table(code):
-    """convert() of all 2^24 triples: (2^24, 3) uint8 BGR at index Y << 16 | V << 8 | U."""
+    """The conversion of all 2^24 triples: (2^24, 3) uint8 BGR at index Y << 16 | V << 8 | U."""
     i = np.arange(1 << 24, dtype=np.uint32)
-    return convert((i >> 16).astype(np.uint8), (i & 255).astype(np.int32) - 128, ((i >> 8) & 255).astype(np.int32) - 128, code)
-
-
-# ------------------------------------------------------------------------------------------------ layouts (as the format tests) ---
-def nv12_or_i420(Y, U, V, fmt, pad=0, rng=None):
-    """The conventional (N, H * 3 // 2, W) array; pad > 0 (nv12): a [:, :, :W] view of an array with longer rows."""
-    rng = rng if rng is not None else np.random.default_rng(0)
-    (n, H, W) = Y.shape
-    full = rng.integers(0, 256, size=(n, H * 3 // 2, W + pad), dtype=np.uint8)
-    out = full[:, :, :W]
-    out[:, :H] = Y
-    if fmt == 'nv12':
-        out[:, H:, 0::2] = U
-        out[:, H:, 1::2] = V
-    else:
-        assert pad == 0 and fmt == 'i420'
-        q = H * W // 4
-        flat = out.reshape(n, -1)
-        flat[:, H * W:H * W + q] = U.reshape(n, -1)
-        flat[:, H * W + q:] = V.reshape(n, -1)
-    return out
-
-
-def pitched420(Y, U, V, fmt, code, y_pad=7, c_pad=5, gap=3, stride_pad=11, rng=None):
-    """A byte buffer of exactly the descriptor's extent with padded pitches: (buffer, MelfYuvFrames)."""
-    rng = rng if rng is not None else np.random.default_rng(0)
-    (n, H, W) = Y.shape
-    nv12 = fmt == 'nv12'
-    (yp, cw) = (W + y_pad, W if nv12 else W // 2)
-    cp = cw + c_pad
-    c0 = H * yp + gap
-    if nv12:
-        c0 += c0 & 1
-        (uo, vo, end) = (c0, c0 + 1, c0 + (H // 2 - 1) * cp + cw)
-    else:
-        (uo, vo) = (c0, c0 + (H // 2) * cp + gap)
-        end = vo + (H // 2 - 1) * cp + cw
-    fs = end + stride_pad
-    buf = rng.integers(0, 256, size=(n - 1) * fs + end, dtype=np.uint8)
-    for f in range(n):
-        o = f * fs
-        for y in range(H):
-            buf[o + y * yp:o + y * yp + W] = Y[f, y]
-        for y in range(H // 2):
-            if nv12:
-                buf[o + uo + y * cp:o + uo + y * cp + W:2] = U[f, y]
-                buf[o + vo + y * cp:o + vo + y * cp + W - 1:2] = V[f, y]
-            else:
-                buf[o + uo + y * cp:o + uo + y * cp + cw] = U[f, y]
-                buf[o + vo + y * cp:o + vo + y * cp + cw] = V[f, y]
-    return buf, _hip.MelfYuvFrames(_hip.YUV_CODES[fmt], code, n, H, W, 0, yp, cp, uo, vo, fs)
-
-
-def fill422(out, Y, U, V, fmt):
-    (yb, cb) = (1, 0) if fmt == 'uyvy' else (0, 1)
-    (first, second) = (V, U) if fmt == 'yvyu' else (U, V)
-    out[..., yb] = Y
-    out[..., 0::2, cb] = first
-    out[..., 1::2, cb] = second
-    return out
-
-
-def packed422(Y, U, V, fmt):
-    (n, H, W) = Y.shape
-    return fill422(np.empty((n, H, W, 2), np.uint8), Y, U, V, fmt)
-
-
-def pitched422(Y, U, V, fmt, code, row_pad=12, stride_pad=20, rng=None):
-    """A byte buffer of exactly the descriptor's extent with padded rows and frame stride: (buffer, MelfYuv422Frames)."""
-    rng = rng if rng is not None else np.random.default_rng(0)
-    (n, H, W) = Y.shape
-    rp = 2 * W + row_pad
-    end = (H - 1) * rp + 2 * W
-    fs = end + stride_pad
-    buf = rng.integers(0, 256, size=(n - 1) * fs + end, dtype=np.uint8)
-    assert buf.ctypes.data % 4 == 0
-    rows = packed422(Y, U, V, fmt).reshape(n, H, 2 * W)
-    for f in range(n):
-        for y in range(H):
-            buf[f * fs + y * rp:f * fs + y * rp + 2 * W] = rows[f, y]
-    return buf, _hip.MelfYuv422Frames(_hip.YUV422_CODES[fmt], code, n, H, W, 0, rp, fs)
+    return fc.yuv_to_bgr((i >> 16).astype(np.uint8), (i & 255).astype(np.uint8), ((i >> 8) & 255).astype(np.uint8), 0, 0, code)
 
 
 # ------------------------------------------------------------------------------------------------------------- CPU ---------
@@ -323,85 +196,26 @@ def test_views_carry_the_matrix():
 
 
 # ------------------------------------------------------------------------------------------------------------- GPU ---------
-@pytest.fixture(scope='module')
-def env():
-    if _hip.device_count() < 1:
-        pytest.fail('GPU tests need an MI355X: no HIP device visible (no CPU fallback exists)')
-    from meterelf_amd import MeterReader, _params
-    from meterelf_amd._image import imread_bgr
-    out = {}
-    for sd in ('sample-images1', 'sample-images2'):
-        params = _params.load(os.path.join(GOLDEN, sd, 'params.yml'))
-        frames = [imread_bgr(f) for f in sorted(glob.glob(os.path.join(GOLDEN, sd, '*.jpg')))]
-        out[sd] = dict(params=params, frames=frames, reader=MeterReader(params))
-    yield out
-    for e in out.values():
-        e['reader'].close()
-
-
-def _hip_rt():
-    from tests.helpers import hip_runtime
-    return hip_runtime()
-
-
-class DevBuf:
-    """Device copy of `nbytes` bytes at host address `ptr`, allocated to exactly that size."""
-
-    def __init__(self, ptr, nbytes):
-        self.hip = _hip_rt()
-        self.d = C.c_void_p()
-        assert self.hip.hipMalloc(C.byref(self.d), C.c_size_t(max(nbytes, 1))) == 0
-        assert self.hip.hipMemcpy(self.d, C.c_void_p(ptr), C.c_size_t(nbytes), 1) == 0
-
-    def free(self):
-        self.hip.hipFree(self.d)
-
-
-def _extent420(d):
-    last = max(d.u_offset, d.v_offset) + (d.H // 2 - 1) * d.c_pitch + (d.W - 1 if d.format == _hip.YUV_NV12 else d.W // 2)
-    return (d.n - 1) * d.frame_stride + last
-
-
-def _extent422(d):
-    return (d.n - 1) * d.frame_stride + (d.H - 1) * d.row_pitch + 2 * d.W
-
-
-def _read_both(ctx, ptr, desc, extent):
-    """Records of the host path and of the device path (a device buffer of exactly `extent` bytes)."""
-    p422 = isinstance(desc, _hip.MelfYuv422Frames)
-    assert extent == (_extent422(desc) if p422 else _extent420(desc))
-    host = (ctx.process_yuv422 if p422 else ctx.process_yuv)(ptr, desc)
-    buf = DevBuf(ptr, extent)
-    try:
-        dev = (ctx.process_yuv422_dev if p422 else ctx.process_yuv_dev)(buf.d.value, desc)
-    finally:
-        buf.free()
-    return host, dev
-
-
 def _check_layouts(reader, p420, p422, code, tag, rng, pitched=True):
     """NV12, I420 and YUYV under matrix `code`, conventional (and pitched), host and device, against read_frames of the restated
     conversion.  Returns (records of the 4:2:0 frames, records of the 4:2:2 frames)."""
     name = [k for (k, c) in NAMES.items() if c == code][0]
-    want0 = reader.read_frames(yuv420_to_bgr(*p420, code))
-    want2 = reader.read_frames(yuv422_to_bgr(*p422, code))
+    (f0, f2) = (fc.with_matrix(F420, code), fc.with_matrix(F422, code))
+    want0 = reader.read_frames(f0.bgr_of(*p420))
+    want2 = reader.read_frames(f2.bgr_of(*p422))
     for fmt in ('nv12', 'i420', 'yuyv'):
-        (planes, wb) = (p422, want2.tobytes()) if fmt == 'yuyv' else (p420, want0.tobytes())
-        if fmt == 'yuyv':
-            arr = packed422(*planes, fmt)
-            assert reader.read_yuv422_frames(arr, fmt, matrix=name).tobytes() == wb, (tag, fmt, 'reader')
-            v = _hip.yuv422_frames_view(arr, fmt, code)
-        else:
-            arr = nv12_or_i420(*planes, fmt, 10 if fmt == 'nv12' else 0, rng)
-            assert reader.read_yuv_frames(arr, fmt, matrix=name).tobytes() == wb, (tag, fmt, 'reader')
-            v = _hip.yuv_frames_view(arr, fmt, code)
+        (fam, planes, wb) = (f2, p422, want2.tobytes()) if fmt == 'yuyv' else (f0, p420, want0.tobytes())
+        arr = packed422(*planes, fmt) if fmt == 'yuyv' else fc.conventional420(*planes, fmt, 10 if fmt == 'nv12' else 0, rng)
+        assert getattr(reader, fam.read)(arr, fmt, matrix=name).tobytes() == wb, (tag, fmt, 'reader')
+        v = fam.view(arr, fmt)
         assert not v.copied and v.descriptor().matrix == code
-        (host, dev) = _read_both(reader.ctx, v.ptr, v.descriptor(), v.extent)
+        (host, dev) = fc.read_both(fam, reader, v.ptr, v.descriptor(), v.extent)
         assert host.tobytes() == wb, (tag, fmt, 'host')
         assert dev.tobytes() == wb, (tag, fmt, 'device')
         if pitched:
-            (buf, desc) = (pitched422 if fmt == 'yuyv' else pitched420)(*planes, fmt, code, rng=rng)
-            (host, dev) = _read_both(reader.ctx, buf.ctypes.data, desc, buf.nbytes)
+            (buf, desc) = fam.pitched(*planes, fmt, rng=rng, **fam.check_pitch(0))
+            assert desc.matrix == code
+            (host, dev) = fc.read_both(fam, reader, buf.ctypes.data, desc, buf.nbytes)
             assert host.tobytes() == wb, (tag, fmt, 'pitched host')
             assert dev.tobytes() == wb, (tag, fmt, 'pitched device')
     return want0, want2
@@ -450,7 +264,7 @@ def test_yuv_to_bgr_all_triples(env, code, fmt):
     """melf_yuv_to_bgr == the restatement for all 2^24 (Y, U, V) under each new matrix."""
     ctx = env['sample-images1']['reader'].ctx
     (Y, U, V, idx) = _triples420()
-    v = _hip.yuv_frames_view(nv12_or_i420(Y, U, V, fmt), fmt, code)
+    v = _hip.yuv_frames_view(fc.conventional420(Y, U, V, fmt), fmt, code)
     got = ctx.yuv_to_bgr(v.ptr, v.descriptor())
     want = table(code)[idx]
     if code == NEW[0] and fmt == 'nv12':   # the table is the restatement of the frame (once: the gather is the cheaper form)
@@ -499,48 +313,16 @@ def test_fixture_frames(env, code, sd, count):
     assert 4 * ok0 >= 3 * count and 4 * ok2 >= 3 * count, (ok0, ok2, count)
 
 
-def _synth(frames, n, seed):
-    """n shifted + noisy fixture frames, every 9th a constant frame (Dials not found): as tests/test_pixel_formats.py."""
-    rng = np.random.default_rng(seed)
-    shapes = [f.shape for f in frames]
-    base = [f for f in frames if f.shape == max(set(shapes), key=shapes.count)]
-    out = np.empty((n,) + base[0].shape, np.uint8)
-    for i in range(n):
-        if i % 9 == 4:
-            out[i] = 128
-            continue
-        (dx, dy) = rng.integers(-8, 9, size=2)
-        img = np.roll(base[i % len(base)], (int(dy), int(dx)), axis=(0, 1)).astype(np.int16)
-        img += rng.integers(-2, 3, size=img.shape).astype(np.int16)
-        out[i] = np.clip(img, 0, 255).astype(np.uint8)
-    return out
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize('kind,kernel', [('fast', 'mfma'), ('gen', 'gen'), ('dot4', 'dot4')])
 @pytest.mark.parametrize('code', NEW)
-def test_each_match_kernel(env, monkeypatch, code, kind, kernel):
+def test_each_match_kernel(env, monkeypatch, code, kind, kernel):  # noqa: F811
     """256 frames (the tuned matrix-core kernel's batch) with each match kernel forced: the prep kernels and the dot4 matcher
     convert under the matrix."""
-    from meterelf_amd import MeterReader
-    e = env['sample-images1']
-    (p420, p422) = forward_both(_synth(e['frames'], 256, 5), code)
-    monkeypatch.setenv('MELF_MATCH', kind)
-    r = MeterReader(e['params'])
-    try:
-        for (planes, fmts) in ((p420, ('nv12', 'i420')), (p422, ('yuyv',))):
-            p2 = fmts == ('yuyv',)
-            want = r.read_frames((yuv422_to_bgr if p2 else yuv420_to_bgr)(*planes, code))
-            assert r.ctx.last_match()['kernel'] == kernel
-            assert (want['status'] == _hip.FRAME_DIALS_NOT_FOUND).sum() >= 28 and (want['status'] == _hip.FRAME_OK).sum() >= 128
-            for fmt in fmts:
-                v = _hip.yuv422_frames_view(packed422(*planes, fmt), fmt, code) if p2 else _hip.yuv_frames_view(nv12_or_i420(*planes, fmt), fmt, code)
-                (host, dev) = _read_both(r.ctx, v.ptr, v.descriptor(), v.extent)
-                assert r.ctx.last_match()['kernel'] == kernel
-                assert host.tobytes() == want.tobytes(), (code, kind, fmt, 'host')
-                assert dev.tobytes() == want.tobytes(), (code, kind, fmt, 'device')
-    finally:
-        r.close()
+    (f0, f2) = (fc.with_matrix(F420, code), fc.with_matrix(F422, code))
+    groups = [(f0, ('nv12', 'i420'), fc.as_conventional(f0, lambda fmt: 0)), (f2, ('yuyv',), fc.as_conventional(f2, lambda fmt: 0))]
+    fc.each_match_kernel(env['sample-images1'], monkeypatch, kind, kernel, groups, n=256, seed=5, rng_seed=0, min_not_found=28,
+                         min_ok=128)
 
 
 @pytest.mark.gpu
@@ -552,7 +334,7 @@ def test_the_matrix_reaches_the_kernels(env):
     shapes = [f.shape for f in e['frames']]
     group = np.stack([f for f in e['frames'] if f.shape == max(set(shapes), key=shapes.count)])
     (p420, p422) = forward_both(group, 0)
-    nv12 = nv12_or_i420(*p420, 'nv12')
+    nv12 = fc.conventional420(*p420, 'nv12')
     yuyv = packed422(*p422, 'yuyv')
     for (arr, planes, conv, read) in ((nv12, p420, yuv420_to_bgr, reader.read_yuv_frames), (yuyv, p422, yuv422_to_bgr, reader.read_yuv422_frames)):
         recs = {}
@@ -562,30 +344,15 @@ def test_the_matrix_reaches_the_kernels(env):
         assert len(set(recs.values())) == len(recs)
 
 
-def _params_with_rect(tmp_path, sd, rect, tag):
-    import yaml
-    from meterelf_amd import _params
-    src = os.path.join(GOLDEN, sd)
-    with open(os.path.join(src, 'params.yml')) as fp:
-        data = yaml.safe_load(fp)
-    data['meter_rect'] = {'top_left': [rect[0], rect[1]], 'bottom_right': [rect[2], rect[3]]}
-    d = tmp_path / tag
-    d.mkdir()
-    with open(d / 'params.yml', 'w') as fp:
-        yaml.safe_dump(data, fp)
-    shutil.copy(os.path.join(src, 'dials_gray.png'), d / 'dials_gray.png')
-    return _params.load(str(d / 'params.yml'))
-
-
 @pytest.mark.gpu
 def test_odd_origin_and_frame_edges(env, tmp_path):
     """Under BT.709 limited: meter_rect (50, 160)-(300, 410) moved to an odd x0 and y0 (the frames shifted by as much), and
     reaching the right and bottom edge of 300 x 410 frames (the host staging path rounds the crop to whole chroma samples)."""
     from meterelf_amd import MeterReader
     e = env['sample-images1']
-    src = _synth(e['frames'], 40, 3)
+    src = fc.synth(e['frames'], 40, 3)
     rng = np.random.default_rng(13)
-    r = MeterReader(_params_with_rect(tmp_path, 'sample-images1', (53, 165, 304, 416), 'odd'))
+    r = MeterReader(fc.params_with_rect(tmp_path, 'sample-images1', (53, 165, 304, 416), 'odd'))
     try:
         (p420, p422) = forward_both(np.roll(src, (5, 3), axis=(1, 2)), 3)
         (w0, w2) = _check_layouts(r, p420, p422, 3, 'odd origin', rng)
@@ -598,57 +365,35 @@ def test_odd_origin_and_frame_edges(env, tmp_path):
 
 
 @pytest.mark.gpu
-def test_resident_lanes_two_streams_changing_matrix(env):
+def test_resident_lanes_two_streams_changing_matrix(env):  # noqa: F811
     """melf_ctx_set_frames_resident(1), two caller streams, a different matrix (and family) on consecutive calls of one context:
     every call's records equal a synchronous read of its own conversion."""
     from meterelf_amd import MeterReader
     e = env['sample-images2']
-    hip = _hip_rt()
-    src = _synth(e['frames'], 96, 21)
+    src = fc.synth(e['frames'], 96, 21)
     planes = {code: forward_both(src, code) for code in (0, 2, 3, 4)}   # every call's frames are encoded with its own matrix
-    n = len(src)
-    rsz = _hip.RESULT_DTYPE.itemsize
     r = MeterReader(e['params'])
     (bufs, keep, calls) = ([], [], [])
-    streams = [C.c_void_p(), C.c_void_p()]
-    d_res = C.c_void_p()
     try:
         for (k, (fmt, code)) in enumerate((('nv12', 2), ('yuyv', 3), ('i420', 4), ('nv12', 0), ('uyvy', 2), ('nv12', 3))):
             (p420, p422) = planes[code]
             if fmt in ('nv12', 'i420'):
-                (buf, desc) = pitched420(*p420, fmt, code, y_pad=4 * k, c_pad=2 * k, gap=k, stride_pad=k, rng=np.random.default_rng(k))
+                (buf, desc) = fc.pitched420(*p420, fmt, y_pad=4 * k, c_pad=2 * k, gap=k, stride_pad=k, rng=np.random.default_rng(k), matrix=code)
                 want = r.read_frames(yuv420_to_bgr(*p420, code))
+                fn = r.ctx.process_yuv_dev
             else:
-                (buf, desc) = pitched422(*p422, fmt, code, row_pad=4 * k, stride_pad=8 * k, rng=np.random.default_rng(k))
+                (buf, desc) = fc.pitched422(*p422, fmt, row_pad=4 * k, stride_pad=8 * k, rng=np.random.default_rng(k), matrix=code)
                 want = r.read_frames(yuv422_to_bgr(*p422, code))
+                fn = r.ctx.process_yuv422_dev
             assert (want['status'] == _hip.FRAME_OK).sum() > 48
             keep.append(buf)
             bufs.append(DevBuf(buf.ctypes.data, buf.nbytes))
-            calls.append((desc, want.tobytes()))
-        for s in streams:
-            assert hip.hipStreamCreate(C.byref(s)) == 0
-        rounds = 2 * len(calls)
-        assert hip.hipMalloc(C.byref(d_res), C.c_size_t(rounds * n * rsz)) == 0
-        r.ctx.set_frames_resident(True)
-        for i in range(rounds):
-            (desc, _w) = calls[i % len(calls)]
-            fn = r.ctx.process_yuv422_dev if isinstance(desc, _hip.MelfYuv422Frames) else r.ctx.process_yuv_dev
-            fn(bufs[i % len(calls)].d.value, desc, d_results_ptr=d_res.value + i * n * rsz, want_host=False, stream=streams[i % 2].value)
-        r.ctx.sync()
-        got = np.zeros(rounds * n, _hip.RESULT_DTYPE)
-        assert hip.hipMemcpy(C.c_void_p(got.ctypes.data), d_res, C.c_size_t(got.nbytes), 2) == 0
-        for i in range(rounds):
-            assert got[i * n:(i + 1) * n].tobytes() == calls[i % len(calls)][1], i
-        r.ctx.set_frames_resident(False)
+            calls.append((functools.partial(fn, bufs[-1].d.value, desc), want.tobytes()))
+        fc.resident_calls(r, len(src), calls, 2 * len(calls), lambda i: i % len(calls))
     finally:
         r.close()
         for b in bufs:
             b.free()
-        if d_res.value:
-            hip.hipFree(d_res)
-        for s in streams:
-            if s.value:
-                hip.hipStreamDestroy(s)
 
 
 @pytest.mark.gpu
@@ -659,12 +404,12 @@ def test_rejected_matrix_codes_launch_nothing(env):
     L = _hip.lib()
     (p420, p422) = forward_both(np.stack(e['frames'][2:6]), 3)
     (n, H, W) = p420[0].shape
-    a0 = nv12_or_i420(*p420, 'nv12')
+    a0 = fc.conventional420(*p420, 'nv12')
     a2 = packed422(*p422, 'yuyv')
     (b0, b2) = (DevBuf(a0.ctypes.data, a0.nbytes), DevBuf(a2.ctypes.data, a2.nbytes))
     try:
         ctx.set_profiling(1)
-        before = {k: cnt for (k, (_ms, cnt)) in ctx.timings().items()}
+        before = fc.launch_counts(ctx)
         out = np.zeros(n, _hip.RESULT_DTYPE)
         bgr_out = np.zeros((n, H, W, 3), np.uint8)
         for code in (1, 5, -1, 256):
@@ -679,14 +424,14 @@ def test_rejected_matrix_codes_launch_nothing(env):
                 assert rc == -1, code
                 msg = L.melf_last_error().decode()
                 assert 'matrix' in msg and all(s in msg for s in ('0', '2', '3', '4')), msg
-        assert {k: cnt for (k, (_ms, cnt)) in ctx.timings().items()} == before
+        assert fc.launch_counts(ctx) == before
         assert not out.tobytes().strip(b'\0') and not bgr_out.any()
         # every accepted code runs
         for code in (0, 2, 3, 4):
             f = _hip.MelfYuvFrames(_hip.YUV_NV12, code, n, H, W, 0, W, W, H * W, H * W + 1, H * W * 3 // 2)
             assert L.melf_process_yuv_dev(ctx._h, C.c_void_p(b0.d.value), C.byref(f), None, _hip._ptr(out), None) == 0
             assert out.tobytes() == e['reader'].read_frames(yuv420_to_bgr(*p420, code)).tobytes()
-        assert {k: cnt for (k, (_ms, cnt)) in ctx.timings().items()} != before
+        assert fc.launch_counts(ctx) != before
     finally:
         ctx.set_profiling(0)
         b0.free()
@@ -696,53 +441,5 @@ def test_rejected_matrix_codes_launch_nothing(env):
 @pytest.mark.gpu
 def test_torch_tensors_in_a_torch_process():
     """read_yuv_frames / read_yuv422_frames with matrix= on torch device tensors and out=, in a child process that imports torch
-    first (tests/test_pixel_formats.py says why)."""
-    env = dict(os.environ)
-    env['PYTHONPATH'] = ROOT + os.pathsep + env.get('PYTHONPATH', '')
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), 'torch'], env=env, cwd=ROOT, stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=900)
-    assert p.returncode == 0 and b'torch yuv matrix path ok' in p.stdout, (p.returncode, p.stdout[-3000:], p.stderr[-3000:])
-
-
-def _torch_main():
-    import torch  # before the package loads the library: one HIP runtime in the process
-    from meterelf_amd import MeterReader, _params
-    from meterelf_amd._image import imread_bgr
-    params = _params.load(os.path.join(GOLDEN, 'sample-images1', 'params.yml'))
-    frames = [imread_bgr(f) for f in sorted(glob.glob(os.path.join(GOLDEN, 'sample-images1', '*.jpg')))]
-    reader = MeterReader(params, device=0)
-    dev = torch.device('cuda', 0)
-    rsz = _hip.RESULT_DTYPE.itemsize
-    src = _synth(frames, 64, 9)
-    seen = set()
-    for (name, code) in (('bt709', 3), ('bt601-full', 2), ('bt709-full', 4)):
-        (p420, p422) = forward_both(src, 3)   # the same bytes under each matrix
-        (n, _H, W) = p420[0].shape
-        want0 = reader.read_frames(yuv420_to_bgr(*p420, code))
-        want2 = reader.read_frames(yuv422_to_bgr(*p422, code))
-        assert (want0['status'] == _hip.FRAME_OK).sum() > 32
-        seen.add(want0.tobytes())
-        full = torch.from_numpy(nv12_or_i420(*p420, 'nv12', 12).base).to(dev)
-        t = full[:, :, :W]
-        assert not _hip.yuv_frames_view(t, 'nv12', name).copied
-        assert reader.read_yuv_frames(t, 'nv12', matrix=name).tobytes() == want0.tobytes(), name
-        assert reader.read_yuv_frames(t, 'nv12', code).tobytes() == want0.tobytes(), name
-        out = torch.empty((n, rsz), dtype=torch.uint8, device=dev)
-        assert reader.read_yuv_frames(t, 'nv12', matrix=name, out=out) is out
-        torch.cuda.synchronize()
-        assert out.cpu().numpy().tobytes() == want0.tobytes(), (name, 'out')
-        t2 = torch.from_numpy(packed422(*p422, 'uyvy')).to(dev)
-        assert reader.read_yuv422_frames(t2, 'uyvy', matrix=name).tobytes() == want2.tobytes(), name
-        out2 = torch.empty((n, rsz), dtype=torch.uint8, device=dev)
-        assert reader.read_yuv422_frames(t2, 'uyvy', matrix=code, out=out2) is out2
-        torch.cuda.synchronize()
-        assert out2.cpu().numpy().tobytes() == want2.tobytes(), (name, 'out 4:2:2')
-        # host tensors take the host path
-        assert reader.read_yuv422_frames(t2.cpu(), 'uyvy', matrix=name).tobytes() == want2.tobytes(), name
-    assert len(seen) == 3
-    reader.close()
-    print('torch yuv matrix path ok')
-
-
-if __name__ == '__main__' and sys.argv[1:] == ['torch']:
-    _torch_main()
+    first (tests/frame_cases.py says why)."""
+    fc.run_torch_child('yuv_matrix')

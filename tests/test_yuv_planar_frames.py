@@ -4,13 +4,15 @@
 The contract (include/meterelf_hip.h): the records are byte-identical to melf_process_batch on the packed BGR frame that the
 header's integer conversion makes of each frame under the descriptor's matrix, with the NEAREST chroma sample: pixel (x, y) uses
 U[y >> sub_y][x >> sub_x] and V[..]; U of pixel (x, y) is the byte at frame + u_offset + (y >> sub_y) * c_pitch + (x >> sub_x) *
-c_step.  yuv_planar_to_bgr below restates that in numpy; every GPU test compares against read_frames of its output.
+c_step.  yuv_to_bgr of tests/frame_cases.py (yuv_planar_to_bgr here) restates that in numpy; every GPU test compares against
+read_frames of its output.
 
 The reference (meterelf/_image.py:46-55) has cv2.imread and nothing else: it never sees such frames.  These layouts are what the
 sources of the 'bt601-full' / 'bt709-full' matrices deliver (software MJPEG decoders: yuvj422p; screen capture: 4:4:4; V4L2 /
 Rockchip decoders: NV16; Android's camera: NV21).
 """
 import ctypes as C
+import functools
 import os
 import subprocess
 import sys
@@ -24,130 +26,16 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from meterelf_amd import _hip  # noqa: E402
-from tests.test_yuv_frames import (DevBuf, _hip_rt, _params_with_rect, _synth, conventional as conventional420,  # noqa: E402
-                                   env, yuv420_to_bgr)   # noqa: F401  (env: the module-scoped fixture of the YUV 4:2:0 tests)
+from tests import frame_cases as fc  # noqa: E402
+from tests.frame_cases import (DevBuf, conventional420, conventional_yuv_planar as conventional, env,  # noqa: E402,F401
+                               extent_yuv_planar as _desc_extent, pitched420, pitched_yuv_planar as pitched, rows_of)
 
-FORMATS = getattr(_hip, 'YUV_PLANAR_FORMATS', {})
+FORMATS = fc.YUV_PLANAR_FORMATS
 NAMES = ('i422', 'yv16', 'nv16', 'nv61', 'i444', 'yv24', 'nv24', 'nv42', 'i440', 'nv21', 'nv12', 'i420', 'yv12')
 SUBSAMPLINGS = {'422': (1, 0), '444': (0, 0), '440': (0, 1), '420': (1, 1)}
-# offset, CY, CRV, CGV, CGU, CBU of include/meterelf_hip.h's table, by matrix code
-MATRICES = {0: (16, 1220542, 1673527, -852492, -409993, 2116026), 2: (0, 1048576, 1470104, -748826, -360853, 1858077),
-            3: (16, 1220945, 1879825, -558796, -223607, 2215014), 4: (0, 1048576, 1651297, -490864, -196424, 1945738)}
-
-
-# ------------------------------------------------------------------------------------------------- the conversion, restated ---
-def yuv_planar_to_bgr(Y, U, V, sub_x, sub_y, matrix=0):
-    """Y (..., H, W), U and V (..., H >> sub_y, W >> sub_x) uint8 -> (..., H, W, 3) uint8 BGR: the header's integer arithmetic with
-    the nearest chroma sample."""
-    (yoff, cy, crv, cgv, cgu, cbu) = MATRICES[matrix]
-    yy = np.maximum(Y.astype(np.int64) - yoff, 0) * cy + (1 << 19)
-
-    def up(p):
-        p = p.astype(np.int64) - 128
-        if sub_y:
-            p = np.repeat(p, 2, axis=-2)
-        if sub_x:
-            p = np.repeat(p, 2, axis=-1)
-        return p
-    (u, v) = (up(U), up(V))
-    out = np.empty(Y.shape + (3,), np.uint8)
-    out[..., 2] = np.clip((yy + crv * v) >> 20, 0, 255)
-    out[..., 1] = np.clip((yy + cgv * v + cgu * u) >> 20, 0, 255)
-    out[..., 0] = np.clip((yy + cbu * u) >> 20, 0, 255)
-    return out
-
-
-def bgr_to_yuv(bgr, sub_x, sub_y):
-    """Test input only: (..., H, W, 3) BGR -> Y, U, V planes (float BT.601 limited range, chroma block mean, round half up)."""
-    f = bgr.astype(np.float64)
-    (b, g, r) = (f[..., 0], f[..., 1], f[..., 2])
-    y = 16.0 + (65.481 * r + 128.553 * g + 24.966 * b) / 255.0
-    u = 128.0 + (-37.797 * r - 74.203 * g + 112.0 * b) / 255.0
-    v = 128.0 + (112.0 * r - 93.786 * g - 18.214 * b) / 255.0
-
-    def mean(p):
-        if sub_y:
-            p = (p[..., 0::2, :] + p[..., 1::2, :]) / 2.0
-        if sub_x:
-            p = (p[..., 0::2] + p[..., 1::2]) / 2.0
-        return p
-
-    def q(p):
-        return np.clip(np.floor(p + 0.5), 0, 255).astype(np.uint8)
-    return q(y), q(mean(u)), q(mean(v))
-
-
-def rows_of(fmt, H):
-    (sx, sy, _step, _vf) = FORMATS[fmt]
-    return H + 2 * (H >> sy) // (1 << sx)
-
-
-def conventional(Y, U, V, fmt, pad=0, rng=None):
-    """The raw-video (N, rows, W) array of the planes in layout fmt; pad > 0: a [:, :, :W] view of an array whose rows are pad
-    bytes longer (random filling) -- only for the layouts whose chroma rows are whole rows of the array."""
-    rng = rng if rng is not None else np.random.default_rng(0)
-    (sx, sy, step, vfirst) = FORMATS[fmt]
-    (n, H, W) = Y.shape
-    (ch, cw) = (H >> sy, W >> sx)
-    rows = rows_of(fmt, H)
-    full = rng.integers(0, 256, size=(n, rows, W + pad), dtype=np.uint8)
-    out = full[:, :, :W]
-    out[:, :H] = Y
-    (first, second) = (V, U) if vfirst else (U, V)
-    if step == 2:
-        if cw * 2 == W:
-            out[:, H:, 0::2] = first
-            out[:, H:, 1::2] = second
-        else:   # 4:4:4: a chroma row is two rows of the array
-            assert pad == 0
-            c = out[:, H:].reshape(n, ch, 2 * cw)
-            c[:, :, 0::2] = first
-            c[:, :, 1::2] = second
-    elif cw == W:
-        out[:, H:H + ch] = first
-        out[:, H + ch:] = second
-    else:
-        assert pad == 0
-        flat = out.reshape(n, -1)
-        flat[:, H * W:H * W + ch * cw] = first.reshape(n, -1)
-        flat[:, H * W + ch * cw:] = second.reshape(n, -1)
-    return out
-
-
-def pitched(Y, U, V, fmt, y_pad=0, c_pad=0, gap=0, stride_pad=0, rng=None, matrix=0, lead=0):
-    """A byte buffer of exactly the descriptor's extent (+ lead bytes in front of the base) with padded pitches:
-    (buffer, MelfYuvPlanarFrames, base offset).  gap: bytes between the planes -- it sets the chroma planes' byte phase against Y."""
-    rng = rng if rng is not None else np.random.default_rng(0)
-    (sx, sy, step, vfirst) = FORMATS[fmt]
-    (n, H, W) = Y.shape
-    (ch, cw) = (H >> sy, (W >> sx) * step)
-    (yp, cp) = (W + y_pad, cw + c_pad)
-    c0 = H * yp - y_pad + gap
-    if step == 2:
-        (uo, vo) = (c0 + 1, c0) if vfirst else (c0, c0 + 1)
-        end = c0 + (ch - 1) * cp + cw
-    else:
-        c1 = c0 + (ch - 1) * cp + cw + gap
-        (uo, vo) = (c1, c0) if vfirst else (c0, c1)
-        end = c1 + (ch - 1) * cp + cw
-    fs = end + stride_pad
-    raw = rng.integers(0, 256, size=lead + (n - 1) * fs + end, dtype=np.uint8)
-    buf = raw[lead:]
-    for f in range(n):
-        o = f * fs
-        for y in range(H):
-            buf[o + y * yp:o + y * yp + W] = Y[f, y]
-        for y in range(ch):
-            buf[o + uo + y * cp:o + uo + y * cp + step * (cw // step - 1) + 1:step] = U[f, y]
-            buf[o + vo + y * cp:o + vo + y * cp + step * (cw // step - 1) + 1:step] = V[f, y]
-    desc = _hip.MelfYuvPlanarFrames(matrix, n, H, W, sx, sy, step, 0, yp, cp, uo, vo, fs)
-    return raw, desc, lead
-
-
-def _desc_extent(d):
-    ch = d.H >> d.sub_y
-    last = max(d.u_offset, d.v_offset) + (ch - 1) * d.c_pitch + ((d.W >> d.sub_x) - 1) * d.c_step + 1
-    return (d.n - 1) * d.frame_stride + last
+yuv_planar_to_bgr = fc.yuv_to_bgr   # (Y, U, V, sub_x, sub_y, matrix=0): the header's conversion, restated
+bgr_to_yuv = fc.bgr_to_yuv          # (bgr, sub_x, sub_y): test input only
+yuv420_to_bgr = fc.F420.bgr_of
 
 
 # ------------------------------------------------------------------------------------------------------------- CPU ---------
@@ -292,6 +180,8 @@ def test_read_yuv_frames_still_rejects_nv21():
 
 
 def test_restatement_equals_420_restatement():
+    """The 4:2:0 file's restatement is the shared yuv_to_bgr at (1, 1) since the two were made one function; what is left to
+    check is that the package's table gives nv12 that subsampling."""
     rng = np.random.default_rng(4)
     (Y, U, V) = (rng.integers(0, 256, (2, 12, 20), dtype=np.uint8), rng.integers(0, 256, (2, 6, 10), dtype=np.uint8),
                  rng.integers(0, 256, (2, 6, 10), dtype=np.uint8))
@@ -344,16 +234,7 @@ def test_kernels_metadata():
 
 
 # ------------------------------------------------------------------------------------------------------------- GPU ---------
-def _read_both(reader, ptr, desc, extent):
-    """Records of the host path and of the device path (a device buffer of exactly `extent` bytes)."""
-    assert extent == _desc_extent(desc)
-    host = reader.ctx.process_yuv_planar(ptr, desc)
-    buf = DevBuf(ptr, extent)
-    try:
-        dev = reader.ctx.process_yuv_planar_dev(buf.d.value, desc)
-    finally:
-        buf.free()
-    return host, dev
+_read_both = functools.partial(fc.read_both, fc.yuv_planar(1, 0))   # (the entry points are those of every subsampling)
 
 
 def _check_formats(reader, bgr, tag, rng, formats=NAMES, pitch=True):
@@ -476,7 +357,7 @@ def test_420_equals_existing_entry_points(env):
     cross-check); nv21 == nv12 of the swapped chroma."""
     e = env['sample-images1']
     reader = e['reader']
-    (Y, U, V) = bgr_to_yuv(_synth(e['frames'], 70, 3), 1, 1)
+    (Y, U, V) = bgr_to_yuv(fc.synth(e['frames'], 70, 3), 1, 1)
     want = reader.read_frames(yuv420_to_bgr(Y, U, V))
     assert (want['status'] == _hip.FRAME_OK).sum() > 40
     for fmt in ('nv12', 'i420', 'yv12'):
@@ -494,31 +375,13 @@ def test_420_equals_existing_entry_points(env):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize('kind,kernel', [('fast', 'mfma'), ('gen', 'gen'), ('dot4', 'dot4')])
-def test_each_match_kernel(env, monkeypatch, kind, kernel):
-    from meterelf_amd import MeterReader
-    e = env['sample-images1']
-    bgr = _synth(e['frames'], 256, 5)
-    monkeypatch.setenv('MELF_MATCH', kind)
-    r = MeterReader(e['params'])
-    try:
-        rng = np.random.default_rng(7)
-        for fmt in ('i422', 'nv42'):
-            (sx, sy, _step, _vf) = FORMATS[fmt]
-            (Y, U, V) = bgr_to_yuv(bgr, sx, sy)
-            want = r.read_frames(yuv_planar_to_bgr(Y, U, V, sx, sy))
-            assert r.ctx.last_match()['kernel'] == kernel
-            assert (want['status'] == _hip.FRAME_DIALS_NOT_FOUND).sum() >= 28 and (want['status'] == _hip.FRAME_OK).sum() >= 128
-            v = _hip.yuv_planar_frames_view(conventional(Y, U, V, fmt, 0, rng), fmt)
-            assert r.ctx.process_yuv_planar(v.ptr, v.descriptor()).tobytes() == want.tobytes(), (kind, fmt, 'host')
-            assert r.ctx.last_match()['kernel'] == kernel
-            buf = DevBuf(v.ptr, v.extent)
-            try:
-                assert r.ctx.process_yuv_planar_dev(buf.d.value, v.descriptor()).tobytes() == want.tobytes(), (kind, fmt, 'device')
-            finally:
-                buf.free()
-            assert r.ctx.last_match()['kernel'] == kernel
-    finally:
-        r.close()
+def test_each_match_kernel(env, monkeypatch, kind, kernel):  # noqa: F811
+    groups = []
+    for fmt in ('i422', 'nv42'):
+        fam = fc.yuv_planar(*FORMATS[fmt][:2])
+        groups.append((fam, (fmt,), fc.as_conventional(fam, lambda fmt: 0)))
+    fc.each_match_kernel(env['sample-images1'], monkeypatch, kind, kernel, groups, n=256, seed=5, rng_seed=7, min_not_found=28,
+                         min_ok=128)
 
 
 @pytest.mark.gpu
@@ -527,11 +390,11 @@ def test_odd_geometry(env, tmp_path, name):
     """meter_rect (50, 160)-(300, 410) at all four parities of origin and of size; the frames are shifted by as much."""
     from meterelf_amd import MeterReader
     e = env['sample-images1']
-    src = _synth(e['frames'], 24, 3)
+    src = fc.synth(e['frames'], 24, 3)
     rng = np.random.default_rng(13)
     formats = [f for f in NAMES if FORMATS[f][:2] == SUBSAMPLINGS[name] and f not in ('nv12', 'i420', 'yv12')]
     for (k, (dx, dy, dw, dh)) in enumerate(((1, 0, 0, 0), (0, 1, 0, 0), (1, 1, 0, 0), (0, 0, -1, 0), (0, 0, 0, -1), (1, 1, -1, -1))):
-        params = _params_with_rect(tmp_path, 'sample-images1', (50 + dx, 160 + dy, 300 + dx + dw, 410 + dy + dh), 'odd%d' % k)
+        params = fc.params_with_rect(tmp_path, 'sample-images1', (50 + dx, 160 + dy, 300 + dx + dw, 410 + dy + dh), 'odd%d' % k)
         r = MeterReader(params)
         try:
             wants = _check_formats(r, np.roll(src, (dy, dx), axis=(1, 2)), (dx, dy, dw, dh), rng, formats=formats, pitch=(k % 2 == 0))
@@ -547,7 +410,7 @@ def test_frame_edges_and_batch_sizes(env):
     e = env['sample-images1']
     reader = e['reader']
     rng = np.random.default_rng(11)
-    src = _synth(e['frames'], 131, 3)
+    src = fc.synth(e['frames'], 131, 3)
     one_each = ('i422', 'nv61', 'yv24', 'nv24', 'i440', 'nv21')
     for (H, W) in ((410, 300), (400, 290)):
         wants = _check_formats(reader, np.ascontiguousarray(src[:12, :H, :W]), (H, W), rng, formats=one_each)
@@ -564,7 +427,7 @@ def test_first_byte_and_byte_phases(env):
     e = env['sample-images1']
     reader = e['reader']
     rng = np.random.default_rng(17)
-    bgr = _synth(e['frames'], 33, 8)
+    bgr = fc.synth(e['frames'], 33, 8)
     for fmt in ('i422', 'nv16', 'i444', 'nv24'):
         (sx, sy, _step, _vf) = FORMATS[fmt]
         (Y, U, V) = bgr_to_yuv(bgr, sx, sy)
@@ -595,10 +458,10 @@ def test_crop_at_the_buffers_first_byte(env, tmp_path):
     from meterelf_amd import MeterReader
     e = env['sample-images1']
     rng = np.random.default_rng(23)
-    src = _synth(e['frames'], 40, 3)
+    src = fc.synth(e['frames'], 40, 3)
     for (k, (y1, x1)) in enumerate(((480, 640), (410, 300))):
         bgr = np.ascontiguousarray(src[:, 160:y1, 50:x1])
-        r = MeterReader(_params_with_rect(tmp_path, 'sample-images1', (0, 0, 250, 250), 'corner%d' % k))
+        r = MeterReader(fc.params_with_rect(tmp_path, 'sample-images1', (0, 0, 250, 250), 'corner%d' % k))
         try:
             for fmt in ('i422', 'nv16', 'i444', 'nv24'):
                 (sx, sy, _step, _vf) = FORMATS[fmt]
@@ -628,7 +491,7 @@ def test_host_staging_three_chunks(env, tmp_path):
     e = env['sample-images1']
     reader = e['reader']
     rng = np.random.default_rng(257)
-    bgr = np.ascontiguousarray(_synth(e['frames'], 257, 4)[:, :410, :300])
+    bgr = np.ascontiguousarray(fc.synth(e['frames'], 257, 4)[:, :410, :300])
     for fmt in ('i422', 'nv61', 'i444', 'nv24', 'i440', 'nv21'):
         (sx, sy, _step, _vf) = FORMATS[fmt]
         (Y, U, V) = bgr_to_yuv(bgr, sx, sy)
@@ -705,28 +568,23 @@ def test_1080p_six_dials_nv16_padded(env, tmp_path):
 
 
 @pytest.mark.gpu
-def test_resident_lanes_two_streams(env):
+def test_resident_lanes_two_streams(env):  # noqa: F811
     """melf_ctx_set_frames_resident(1) and two caller streams, the layout and the entry-point family changing from call to call:
     every call's records equal a synchronous call's."""
     from meterelf_amd import MeterReader
-    from tests.test_yuv_frames import pitched as pitched420
     e = env['sample-images2']
-    hip = _hip_rt()
-    bgr = _synth(e['frames'], 96, 21)
+    bgr = fc.synth(e['frames'], 96, 21)
     nf = len(bgr)
-    rsz = _hip.RESULT_DTYPE.itemsize
     r = MeterReader(e['params'])
     bufs = []
     keep = []
-    streams = [C.c_void_p(), C.c_void_p()]
-    d_res = C.c_void_p()
     try:
-        calls = []   # (entry, device buffer, descriptor, wanted bytes)
+        calls = []   # (entry point bound to its device buffer and descriptor, wanted bytes)
         for (k, fmt) in enumerate(('i422', 'nv24', 'nv12-old', 'nv61', 'i440', 'yv24', 'nv21', 'bgr')):
             if fmt == 'bgr':
                 want = r.read_frames(bgr)
                 bufs.append(DevBuf(bgr.ctypes.data, bgr.nbytes))
-                calls.append(('bgr', bufs[-1], None, want.tobytes()))
+                calls.append((functools.partial(r.ctx.process_batch_dev, bufs[-1].d.value, nf, bgr.shape[1], bgr.shape[2]), want.tobytes()))
                 continue
             if fmt == 'nv12-old':
                 (Y, U, V) = bgr_to_yuv(bgr, 1, 1)
@@ -734,7 +592,7 @@ def test_resident_lanes_two_streams(env):
                 (buf, desc) = pitched420(Y, U, V, 'nv12', y_pad=4, c_pad=2, gap=2, stride_pad=2, rng=np.random.default_rng(k))
                 keep.append(buf)
                 bufs.append(DevBuf(buf.ctypes.data, buf.nbytes))
-                calls.append(('yuv', bufs[-1], desc, want.tobytes()))
+                calls.append((functools.partial(r.ctx.process_yuv_dev, bufs[-1].d.value, desc), want.tobytes()))
                 continue
             (sx, sy, _step, _vf) = FORMATS[fmt]
             (Y, U, V) = bgr_to_yuv(bgr, sx, sy)
@@ -743,36 +601,12 @@ def test_resident_lanes_two_streams(env):
             (raw, desc, _lead) = pitched(Y, U, V, fmt, y_pad=k, c_pad=2 * k + 1, gap=k, stride_pad=k, rng=np.random.default_rng(k))
             keep.append(raw)
             bufs.append(DevBuf(raw.ctypes.data, raw.nbytes))
-            calls.append(('yuvp', bufs[-1], desc, want.tobytes()))
-        for s in streams:
-            assert hip.hipStreamCreate(C.byref(s)) == 0
-        rounds = 2 * len(calls)
-        assert hip.hipMalloc(C.byref(d_res), C.c_size_t(rounds * nf * rsz)) == 0
-        r.ctx.set_frames_resident(True)
-        for i in range(rounds):
-            (kind, buf, desc, _w) = calls[(3 * i) % len(calls)]
-            kw = dict(d_results_ptr=d_res.value + i * nf * rsz, want_host=False, stream=streams[i % 2].value)
-            if kind == 'bgr':
-                r.ctx.process_batch_dev(buf.d.value, nf, bgr.shape[1], bgr.shape[2], **kw)
-            elif kind == 'yuv':
-                r.ctx.process_yuv_dev(buf.d.value, desc, **kw)
-            else:
-                r.ctx.process_yuv_planar_dev(buf.d.value, desc, **kw)
-        r.ctx.sync()
-        got = np.zeros(rounds * nf, _hip.RESULT_DTYPE)
-        assert hip.hipMemcpy(C.c_void_p(got.ctypes.data), d_res, C.c_size_t(got.nbytes), 2) == 0
-        for i in range(rounds):
-            assert got[i * nf:(i + 1) * nf].tobytes() == calls[(3 * i) % len(calls)][3], i
-        r.ctx.set_frames_resident(False)
+            calls.append((functools.partial(r.ctx.process_yuv_planar_dev, bufs[-1].d.value, desc), want.tobytes()))
+        fc.resident_calls(r, nf, calls, 2 * len(calls), lambda i: (3 * i) % len(calls))
     finally:
         r.close()
         for b in bufs:
             b.free()
-        if d_res.value:
-            hip.hipFree(d_res)
-        for s in streams:
-            if s.value:
-                hip.hipStreamDestroy(s)
 
 
 @pytest.mark.gpu
@@ -786,7 +620,7 @@ def test_argument_errors_launch_nothing(env):
     buf = DevBuf(arr.ctypes.data, arr.nbytes)
     try:
         ctx.set_profiling(1)
-        before = {k: cnt for (k, (_ms, cnt)) in ctx.timings().items()}
+        before = fc.launch_counts(ctx)
         out = np.zeros(n, _hip.RESULT_DTYPE)
         bgr_out = np.zeros((n, H, W, 3), np.uint8)
         F = _hip.MelfYuvPlanarFrames
@@ -842,10 +676,10 @@ def test_argument_errors_launch_nothing(env):
         empty = D(n=0)
         assert L.melf_process_yuv_planar_dev(ctx._h, None, C.byref(empty), None, None, None) == 0             # n == 0 passes
         assert L.melf_process_yuv_planar(ctx._h, None, C.byref(empty), None) == 0
-        assert {k: cnt for (k, (_ms, cnt)) in ctx.timings().items()} == before
+        assert fc.launch_counts(ctx) == before
         # a good descriptor runs
         assert L.melf_process_yuv_planar_dev(ctx._h, C.c_void_p(buf.d.value), C.byref(good), None, _hip._ptr(out), None) == 0
-        assert {k: cnt for (k, (_ms, cnt)) in ctx.timings().items()} != before
+        assert fc.launch_counts(ctx) != before
         assert out.tobytes() == e['reader'].read_frames(yuv_planar_to_bgr(Y, U, V, 1, 0)).tobytes()
     finally:
         ctx.set_profiling(0)
@@ -855,63 +689,4 @@ def test_argument_errors_launch_nothing(env):
 @pytest.mark.gpu
 def test_torch_tensors_in_a_torch_process():
     """read_yuv_planar_frames with torch tensors, in a child process that imports torch first."""
-    env_ = dict(os.environ)
-    env_['PYTHONPATH'] = ROOT + os.pathsep + env_.get('PYTHONPATH', '')
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), 'torch'], env=env_, cwd=ROOT, stdout=subprocess.PIPE,
-                       stderr=subprocess.PIPE, timeout=900)
-    assert p.returncode == 0 and b'torch planar yuv path ok' in p.stdout, (p.returncode, p.stdout[-3000:], p.stderr[-3000:])
-
-
-def _torch_main():
-    import glob
-
-    import torch  # before the package loads the library: one HIP runtime in the process
-    from meterelf_amd import MeterReader, _params
-    from meterelf_amd._image import imread_bgr
-    params = _params.load(os.path.join(GOLDEN, 'sample-images1', 'params.yml'))
-    frames = [imread_bgr(f) for f in sorted(glob.glob(os.path.join(GOLDEN, 'sample-images1', '*.jpg')))]
-    bgr = _synth(frames, 96, 9)
-    reader = MeterReader(params, device=0)
-    dev = torch.device('cuda', 0)
-    rsz = _hip.RESULT_DTYPE.itemsize
-    rng = np.random.default_rng(1)
-    W = bgr.shape[2]
-    for fmt in ('i422', 'nv16', 'nv61', 'i444', 'nv24', 'i440', 'nv21'):
-        (sx, sy, step, _vf) = FORMATS[fmt]
-        (Y, U, V) = bgr_to_yuv(bgr, sx, sy)
-        want = reader.read_frames(yuv_planar_to_bgr(Y, U, V, sx, sy, 2))
-        assert (want['status'] == _hip.FRAME_OK).sum() > 48
-        for pad in ((0, 12) if (W >> sx) * step == W else (0,)):
-            arr = conventional(Y, U, V, fmt, pad, rng)
-            t = torch.from_numpy(arr.base if pad else arr).to(dev)[:, :, :W]
-            assert not _hip.yuv_planar_frames_view(t, fmt).copied
-            assert reader.read_yuv_planar_frames(t, fmt, 'bt601-full').tobytes() == want.tobytes(), (fmt, pad)
-            # host tensors take the host path
-            assert reader.read_yuv_planar_frames(torch.from_numpy(np.ascontiguousarray(arr)), fmt, 'bt601-full').tobytes() == want.tobytes(), (fmt, pad)
-            # out=: records into a device tensor on the current stream, nothing synchronised
-            out = torch.empty((len(Y), rsz), dtype=torch.uint8, device=dev)
-            assert reader.read_yuv_planar_frames(t, fmt, 'bt601-full', out=out) is out
-            torch.cuda.synchronize()
-            assert out.cpu().numpy().tobytes() == want.tobytes(), (fmt, pad, 'out')
-        if fmt == 'i444':
-            # the (N, 3, H, W) shape, every other frame, in place
-            t4 = torch.from_numpy(np.stack([Y, U, V], axis=1)).to(dev)
-            assert not _hip.yuv_planar_frames_view(t4[::2], fmt).copied
-            assert reader.read_yuv_planar_frames(t4[::2], fmt, 'bt601-full').tobytes() == want[::2].tobytes()
-        if fmt == 'i422':
-            # padded rows of a layout whose chroma rows are half rows: one packed copy, on the device
-            wide = torch.zeros((len(Y), 2 * Y.shape[1], W + 8), dtype=torch.uint8, device=dev)
-            wide[:, :, :W] = torch.from_numpy(conventional(Y, U, V, fmt)).to(dev)
-            assert _hip.yuv_planar_frames_view(wide[:, :, :W], fmt).copied
-            out = torch.empty((len(Y), rsz), dtype=torch.uint8, device=dev)
-            reader.read_yuv_planar_frames(wide[:, :, :W], fmt, 'bt601-full', out=out)
-            torch.cuda.synchronize()
-            assert out.cpu().numpy().tobytes() == want.tobytes()
-            with pytest.raises(ValueError):
-                reader.read_yuv_planar_frames(conventional(Y, U, V, fmt), fmt, out=out)   # out= with host frames
-    reader.close()
-    print('torch planar yuv path ok')
-
-
-if __name__ == '__main__' and len(sys.argv) > 1 and sys.argv[1] == 'torch':
-    _torch_main()
+    fc.run_torch_child('yuv_planar')

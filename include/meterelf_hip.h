@@ -202,8 +202,8 @@ int melf_process_frames_dev(melf_ctx* ctx, const void* d_frames, const melf_fram
  * triples differ from it at all under code 2, 1 315 under code 3, none under code 4).  Code 2 is the JFIF matrix but not
  * libjpeg's tables bit for bit: libjpeg rounds the chroma terms separately at 16 bits, and 8 332 triples differ by 1 (the JPEG
  * entry points below decode with libjpeg's own arithmetic and are not affected by any of this).
- * Out of scope: BT.2020, 10-bit formats, interpolated chroma, chroma siting, planes in separate allocations.  (4:2:2, 4:4:4 and 4:4:0
- * planes and NV21: melf_process_yuv_planar*, below.)
+ * Out of scope: BT.2020, interpolated chroma, chroma siting, planes in separate allocations.  (4:2:2, 4:4:4 and 4:4:0 planes and
+ * NV21: melf_process_yuv_planar*; 10-, 12- and 16-bit samples: melf_process_yuv16*, both below.)
  * Frame f starts at frames + f * frame_stride; its Y row y at + y * y_pitch (W bytes), its chroma row y >> 1 at
  * + u_offset / v_offset + (y >> 1) * c_pitch: NV12 W bytes U V U V .. (v_offset == u_offset + 1), I420 W / 2 bytes per plane.
  * YV12 is I420 with the two offsets exchanged.  The buffer must hold every plane of every frame up to the last sample of its
@@ -311,6 +311,62 @@ int melf_process_yuv_planar_dev(melf_ctx* ctx, const void* d_frames, const melf_
                                 melf_result* out_host, void* stream);
 /* Stage entry point (parity tests, and a debug view for callers): the conversion alone, n packed H x W x 3 BGR frames out. */
 int melf_yuv_planar_to_bgr(melf_ctx* ctx, const void* frames_host, const melf_yuv_planar_frames* f, uint8_t* bgr_out_host);
+
+/* ---- the same path for planar and semi-planar YUV frames of 10, 12 or 16 bits per sample: what a hardware HEVC / AV1 Main10
+ * decoder leaves (P010: semi-planar 4:2:0, the value in the high bits of a 16-bit word), ffmpeg's software decoders (yuv420p10le /
+ * I010: planar, the value in the low bits), capture cards (P210, P216) ----
+ * Samples are little-endian uint16.  A sample s is read as the 8-bit sample
+ *     s8 = min(s >> shift, 255)
+ * truncation, a pure selection of bits: for P010 (shift 8) it is the sample's high byte.  The clamp matters only for LSB-aligned
+ * data with out-of-spec high bits.  The records are byte-identical to melf_process_yuv_planar(_dev) on the 8-bit frame of the same
+ * geometry (sub_x 1, the same sub_y and planar / semi-planar form and order of U and V) whose samples are s8 -- and so, by that
+ * entry point's contract, to melf_process_batch(_dev) on the BGR frame the integer conversion above makes of it under the
+ * descriptor's matrix (the existing table, any of the four codes; 1 stays invalid).
+ *     chroma: the nearest sample, no interpolation: pixel (x, y) uses U[y >> sub_y][x >> 1], V[y >> sub_y][x >> 1]
+ * Neither that 8-bit frame nor a BGR frame is ever formed: the kernels read the 16-bit planes in place, and only the meter_rect
+ * crop of them.
+ * Frame f starts at frames + f * frame_stride (bytes); its Y row y at + y * y_pitch: W samples of 2 bytes; U of pixel (x, y) is
+ * the sample at byte + u_offset + (y >> sub_y) * c_pitch + (x >> 1) * c_step * 2, V the same from v_offset.
+ *     c_step   SAMPLES from one sample of a chroma plane to the next in its row: 1 planar, 2 semi-planar (U and V interleaved in
+ *              one plane: the two offsets are 2 bytes apart, and which is the lower says which sample of a pair comes first)
+ *     shift    low bits dropped, 0 .. 8:  8 for MSB-aligned and full 16-bit samples (P010, P012, P016, P210, P216, yuv420p16le,
+ *              yuv422p16le), 4 for 12 bits in the low bits (yuv420p12le, yuv422p12le), 2 for 10 bits in the low bits (I010 /
+ *              yuv420p10le, I210 / yuv422p10le)
+ * Alignment: the base, the offsets, the pitches and frame_stride are 2-byte aligned (whole samples), and need be no more than that.
+ * The buffer must hold every plane of every frame up to the last sample of its last row, and need hold nothing behind that nor
+ * before the base: no load of the kernels reaches outside (n - 1) * frame_stride + the last sample of the last frame, nor before
+ * the base.  MELF_ERR_INVALID (melf_last_error says which) before anything is launched or copied for: a NULL descriptor or NULL
+ * frames; reserved != 0; sub_y outside {0, 1}; c_step outside {1, 2}; shift outside 0 .. 8; c_step 2 with offsets that are not
+ * 2 bytes apart; an odd W, an odd H with sub_y; H or W <= 0, n < 0 (n == 0 passes); a negative offset; an unknown matrix; an odd
+ * base, y_pitch, c_pitch, u_offset, v_offset or frame_stride; y_pitch < 2 * W bytes; c_pitch smaller than a chroma row ((W >> 1) *
+ * c_step samples of 2 bytes); a pitch > 2^31 - 1; a chroma plane closer to the other than its span (overlapping) or starting
+ * inside the Y plane's span; a frame_stride smaller than the span of one frame.
+ * Out of scope: sub_x = 0 (4:4:4 / 4:4:0 at 16 bits); the packed 10-bit formats (Y210, v210); big-endian samples; BT.2020 (and
+ * any transfer function: the samples are taken as they are); rounding or dithering of the dropped bits. */
+typedef struct melf_yuv16_frames {
+    int32_t matrix;                             /* MELF_YUV_BT* as above (the four codes; 1 stays invalid) */
+    int32_t n, H, W;                            /* W even; H even if sub_y                                */
+    int32_t sub_y;                              /* 0: 4:2:2, 1: 4:2:0 (sub_x is 1: see scope)             */
+    int32_t c_step;                             /* SAMPLES from one sample of a chroma plane to the next
+                                                   in its row: 1 planar, 2 semi-planar                    */
+    int32_t shift;                              /* 0 .. 8: low bits dropped (8, 12-bit LSB: 4, 10-bit LSB: 2) */
+    int32_t reserved;                           /* 0                                                      */
+    int64_t y_pitch;                            /* BYTES between Y rows, even, >= 2 * W                   */
+    int64_t c_pitch;                            /* BYTES between chroma rows, even, >= W * c_step         */
+    int64_t u_offset, v_offset;                 /* BYTES, even, from a frame's first byte to its first
+                                                   U / V sample; c_step 2: |u_offset - v_offset| == 2     */
+    int64_t frame_stride;                       /* BYTES between frames, even                             */
+} melf_yuv16_frames;
+/* Host frames, as melf_process_yuv_planar: only the crop crosses PCIe, packed into the pinned staging buffers as a small frame of
+ * the same layout (16-bit samples as they are: the Y rows of the crop rounded out to whole chroma blocks and the chroma rows under
+ * them); no sample is reduced, converted or reordered on the CPU. */
+int melf_process_yuv16(melf_ctx* ctx, const void* frames_host, const melf_yuv16_frames* f, melf_result* out_host);
+/* Frames in HBM, exactly as melf_process_yuv_planar_dev: the same lanes, melf_ctx_set_frames_resident, caller streams, and NULL
+ * d_results / out_host semantics. */
+int melf_process_yuv16_dev(melf_ctx* ctx, const void* d_frames, const melf_yuv16_frames* f, void* d_results, melf_result* out_host,
+                           void* stream);
+/* Stage entry point (parity tests, and a debug view for callers): reduction and conversion alone, n packed H x W x 3 BGR frames out. */
+int melf_yuv16_to_bgr(melf_ctx* ctx, const void* frames_host, const melf_yuv16_frames* f, uint8_t* bgr_out_host);
 
 /* ---- the same path for planar, channels-first frames: (N, 3, H, W) uint8 as torch's decoders and pre-processing pipelines
  * hold them, ffmpeg's gbrp, rgb24 split into planes ----
@@ -532,10 +588,10 @@ typedef struct {
 int melf_ctx_last_match(const melf_ctx* ctx, melf_match_info* out);
 /* Which dial-reader kernel the context's most recent launch ran: the kernel family that reads the frames' layout and NR, the
  * window rows a lane requests up front -- one of 32, 40, 48, 52, 56, 64, the smallest that holds ws_max, the context's largest
- * dial window (2 R + 5 rows).  Twelve families times six NR: tests assert the pair, so that every instantiation production can
- * pick is known to have been the one a parity test launched.  family is -1 and nr 0 before the first launch; a call of more
- * frames than one launch takes reports its last piece.  Plain fields written by every launch, as for melf_ctx_fused_variant's
- * last_launch.  Every output pointer may be NULL. */
+ * dial window (2 R + 5 rows).  Twelve families (and the two of the 16-bit frames, below) times six NR: tests assert the pair, so
+ * that every instantiation production can pick is known to have been the one a parity test launched.  family is -1 and nr 0
+ * before the first launch; a call of more frames than one launch takes reports its last piece.  Plain fields written by every
+ * launch, as for melf_ctx_fused_variant's last_launch.  Every output pointer may be NULL. */
 enum { MELF_DIALS_HLS = 0,            /* k_dials<true>: packed HLS dials crops (melf_read_dials)            */
        MELF_DIALS_BGR = 1,            /* k_dials<false>: packed B G R                                       */
        MELF_DIALS_PACKED3 = 2,        /* k_needles<3>: packed R G B                                         */
@@ -549,6 +605,11 @@ enum { MELF_DIALS_HLS = 0,            /* k_dials<true>: packed HLS dials crops (
        MELF_DIALS_YP_SUB1_STEP2 = 10, /* k_yp_needle<1, 2>: ... sub_x 1, interleaved pairs                  */
        MELF_DIALS_PLANAR = 11,        /* k_planar_needle: melf_process_planes*                              */
        MELF_DIALS_FAMILIES = 12 };
+/* The families of the 16-bit frames (melf_process_yuv16*), also values of `family`.  An enum and a prefix of their own: the twelve
+ * MELF_DIALS_* names and MELF_DIALS_FAMILIES == 12 are what the instantiation tests of the 8-bit layouts enumerate and pin, and
+ * these kernels are enumerated by tests of their own; the values go on from 12 so that `family` stays one number space. */
+enum { MELF_DIALS16_STEP1 = 12,       /* k_y16_needle<1>: melf_process_yuv16*, planar                        */
+       MELF_DIALS16_STEP2 = 13 };     /* k_y16_needle<2>: ... interleaved pairs                              */
 int melf_ctx_last_dials(const melf_ctx* ctx, int* nr, int* family, int* ws_max);
 /* The tuned kernel's wave layout for a template / searched-image shape and a batch of n images, without a GPU or a
  * context (host logic; kernel = MELF_MATCH_KERNEL_MFMA when the shape belongs to the tuned kernel's class, else the

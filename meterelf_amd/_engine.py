@@ -224,6 +224,23 @@ class MeterReader:
         return self._read_view(v, out, lambda: self.ctx.process_yuv_planar(v.ptr, desc),
                                lambda **kw: self.ctx.process_yuv_planar_dev(v.ptr, desc, **kw))
 
+    def read_yuv16_frames(self, frames, pixel_format: str, matrix, out=None):
+        """Planar and semi-planar YUV frames of 10, 12 or 16 bits per sample -- 'p010' as a hardware HEVC / AV1 Main10 decoder leaves
+        a camera stream, 'i010' / 'yuv420p10le' as ffmpeg's software decoders do, 'p210' / 'p216' of capture cards, the 12- and 16-bit
+        and 4:2:2 siblings (_hip.YUV16_FORMATS) -- -> records, equal to read_yuv_planar_frames() of the 8-bit frames whose samples are
+        min(s >> shift, 255), the format's shift dropping the low bits (melf_process_yuv16*); the 16-bit planes are read in place, no
+        reduction or conversion pass.  matrix has no default: nearly all 10-bit material is 'bt709', and the wrong matrix raises no
+        error -- it shifts hue and lightness, which is what the dials are read from.  frames: the raw-video (N, rows, W) array of
+        uint16, rows = 3 H / 2 (4:2:0) or 2 H (4:2:2): a numpy array / torch CPU tensor (host path) or a torch tensor on this
+        reader's GPU (enqueued on torch.cuda.current_stream), torch.uint16 where the installed torch has it, or torch.int16 holding
+        the same bits; _hip.yuv16_frames_view says which layouts are read in place.  out: a uint8 device tensor (N,
+        RESULT_DTYPE.itemsize) on the same GPU that receives the records without synchronising the stream (device frames only);
+        returns it.  Otherwise returns the records."""
+        v = _hip.yuv16_frames_view(frames, pixel_format, matrix)
+        desc = v.descriptor()
+        return self._read_view(v, out, lambda: self.ctx.process_yuv16(v.ptr, desc),
+                               lambda **kw: self.ctx.process_yuv16_dev(v.ptr, desc, **kw))
+
     def read_planar_frames(self, frames, channel_order: str = 'rgb', out=None):
         """Planar, channels-first frames (N, 3, H, W) / (N, 4, H, W) uint8 -> records, equal to read_frames() of the packed BGR
         frames with the same samples (melf_process_planes*); the planes are read in place, no interleaved copy is made.  frames: a

@@ -118,6 +118,25 @@ YUV_PLANAR_FORMATS = {
 }
 
 
+class MelfYuv16Frames(C.Structure):
+    _fields_ = [('matrix', C.c_int32), ('n', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('sub_y', C.c_int32),
+                ('c_step', C.c_int32), ('shift', C.c_int32), ('reserved', C.c_int32), ('y_pitch', C.c_int64),
+                ('c_pitch', C.c_int64), ('u_offset', C.c_int64), ('v_offset', C.c_int64), ('frame_stride', C.c_int64)]
+
+
+# planar and semi-planar YUV layouts of 16-bit little-endian samples (melf_process_yuv16*) by name: (sub_y, c_step, V before U,
+# shift).  sub_y: log2 of the vertical chroma subsampling (the horizontal one is 2); c_step 1: U and V in planes of their own, 2:
+# interleaved pairs in one plane; shift: the low bits dropped from a sample -- 8 where the value sits in the high bits (the P0xx /
+# P2xx formats of hardware decoders) or fills the word, 16 - 8 - (16 - depth) = depth - 8 where it sits in the low bits.
+YUV16_FORMATS = {
+    'p010': (1, 2, False, 8), 'p012': (1, 2, False, 8), 'p016': (1, 2, False, 8),
+    'p210': (0, 2, False, 8), 'p216': (0, 2, False, 8),
+    'i010': (1, 1, False, 2), 'yuv420p10le': (1, 1, False, 2), 'i210': (0, 1, False, 2), 'yuv422p10le': (0, 1, False, 2),
+    'i012': (1, 1, False, 4), 'yuv420p12le': (1, 1, False, 4), 'i212': (0, 1, False, 4), 'yuv422p12le': (0, 1, False, 4),
+    'yuv420p16le': (1, 1, False, 8), 'yuv422p16le': (0, 1, False, 8),
+}
+
+
 class MelfPlanarFrames(C.Structure):
     _fields_ = [('n', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('reserved', C.c_int32), ('b_offset', C.c_int64),
                 ('g_offset', C.c_int64), ('r_offset', C.c_int64), ('row_pitch', C.c_int64), ('frame_stride', C.c_int64)]
@@ -142,6 +161,10 @@ class HipError(RuntimeError):
 DIALS_FAMILIES = ('hls', 'bgr', 'packed3', 'packed4', 'nv12', 'i420', 'p422', 'yp_sub0_step1', 'yp_sub0_step2', 'yp_sub1_step1',
                   'yp_sub1_step2', 'planar')
 
+# MELF_DIALS16_* of include/meterelf_hip.h, the families of the 16-bit frames: values 12, 13 of melf_ctx_last_dials' family.  A tuple
+# of their own, as the header keeps them in an enum of their own: DIALS_FAMILIES is the twelve the instantiation tests enumerate.
+DIALS16_FAMILIES = ('yuv16_step1', 'yuv16_step2')
+
 # every symbol include/meterelf_hip.h declares for the product library; DIAG_EXPORTS: what its `#ifdef MELF_DIAG` part adds (the
 # diagnostic build, make -C meterelf_amd/csrc diag, loaded through MELF_LIB_PATH)
 DIAG_EXPORTS = ['melf_stream_probe_dev']
@@ -152,6 +175,7 @@ EXPORTS = [
     'melf_process_frames', 'melf_process_frames_dev', 'melf_process_yuv', 'melf_process_yuv_dev', 'melf_yuv_to_bgr',
     'melf_process_yuv422', 'melf_process_yuv422_dev', 'melf_yuv422_to_bgr', 'melf_process_planes', 'melf_process_planes_dev',
     'melf_process_yuv_planar', 'melf_process_yuv_planar_dev', 'melf_yuv_planar_to_bgr',
+    'melf_process_yuv16', 'melf_process_yuv16_dev', 'melf_yuv16_to_bgr',
     'melf_bgr2hls', 'melf_hls_inrange_close', 'melf_hls_inrange_close_dev', 'melf_match_ccoeff',
     'melf_read_dials', 'melf_aligned_average', 'melf_inrange', 'melf_ctx_fused_table_ties', 'melf_ctx_fused_variant', 'melf_ctx_set_frames_resident', 'melf_ctx_last_match', 'melf_ctx_last_dials', 'melf_match_layout_query', 'melf_match_gen_plan_query', 'melf_ctx_set_profiling', 'melf_ctx_timings', 'melf_kernel_name',
     'melf_jpeg_probe', 'melf_jpeg_probe_batch', 'melf_jpeg_decode_batch', 'melf_jpeg_clean_segment', 'melf_jpeg_process_batch',
@@ -201,6 +225,9 @@ def lib():
     L.melf_process_yuv_planar.argtypes = [vp, vp, C.POINTER(MelfYuvPlanarFrames), vp]
     L.melf_process_yuv_planar_dev.argtypes = [vp, vp, C.POINTER(MelfYuvPlanarFrames), vp, vp, vp]
     L.melf_yuv_planar_to_bgr.argtypes = [vp, vp, C.POINTER(MelfYuvPlanarFrames), vp]
+    L.melf_process_yuv16.argtypes = [vp, vp, C.POINTER(MelfYuv16Frames), vp]
+    L.melf_process_yuv16_dev.argtypes = [vp, vp, C.POINTER(MelfYuv16Frames), vp, vp, vp]
+    L.melf_yuv16_to_bgr.argtypes = [vp, vp, C.POINTER(MelfYuv16Frames), vp]
     L.melf_process_planes.argtypes = [vp, vp, C.POINTER(MelfPlanarFrames), vp]
     L.melf_process_planes_dev.argtypes = [vp, vp, C.POINTER(MelfPlanarFrames), vp, vp, vp]
     L.melf_process_stream_dev.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, vp]
@@ -597,6 +624,103 @@ def yuv_planar_frames_view(frames, pixel_format='i422', matrix='bt601'):
                                int(extent), not ok, frames, mcode)
 
 
+class Yuv16FramesView(NamedTuple):
+    """How the kernels read a batch of 16-bit planar / semi-planar YUV frames in place (yuv16_frames_view)."""
+    ptr: int            # address of frame 0's first Y sample
+    on_device: bool     # True: a torch tensor on a GPU (ptr is a device address)
+    device: Optional[int]
+    n: int
+    H: int
+    W: int
+    sub_y: int          # log2 of the vertical chroma subsampling
+    c_step: int         # SAMPLES between the samples of a chroma plane: 1 planar, 2 semi-planar
+    shift: int          # low bits dropped from a sample
+    y_pitch: int        # BYTES between Y rows
+    c_pitch: int        # BYTES between chroma rows
+    u_offset: int       # BYTES from a frame's first byte to its first U / V sample
+    v_offset: int
+    frame_stride: int   # BYTES between frames
+    extent: int         # bytes read from ptr: every plane of every frame up to the last sample of its last row
+    copied: bool        # the layout could not be described and the frames were copied once to a packed array
+    array: object       # what ptr points into (the caller's array, or the copy): keep it alive while the call runs
+    matrix: int         # YUV_BT* code of the colour conversion
+
+    def descriptor(self):
+        return MelfYuv16Frames(self.matrix, self.n, self.H, self.W, self.sub_y, self.c_step, self.shift, 0, self.y_pitch,
+                               self.c_pitch, self.u_offset, self.v_offset, self.frame_stride)
+
+
+def reduce16(samples, shift):
+    """The 8-bit samples the kernels read 16-bit ones as: min(s >> shift, 255), uint8 (include/meterelf_hip.h)."""
+    return np.minimum(np.asarray(samples).view(np.uint16) >> np.uint16(shift), np.uint16(255)).astype(np.uint8)
+
+
+def _unwrap16(frames):
+    """_unwrap for arrays of 2-byte samples: a uint16 numpy array, or a torch tensor of torch.uint16 (where the installed torch has
+    it) or torch.int16 (the same bits); strides in BYTES.  Anything else: ValueError."""
+    if _is_torch(frames):
+        if str(frames.dtype) not in ('torch.uint16', 'torch.int16'):
+            raise ValueError('frames must be uint16 (or int16 holding the same bits), not %s' % frames.dtype)
+        on_device = frames.device.type == 'cuda'
+        return (frames, True, tuple(frames.shape), tuple(2 * st for st in frames.stride()),
+                frames.data_ptr(), on_device, frames.device.index if on_device else None)
+    frames = np.asarray(frames)
+    if frames.dtype != np.uint16:
+        raise ValueError('frames must be uint16, not %s' % frames.dtype)
+    return (frames, False, frames.shape, frames.strides, frames.ctypes.data, False, None)
+
+
+def yuv16_frames_view(frames, pixel_format, matrix):
+    """Describes the raw-video (N, rows, W) uint16 array of 16-bit planar / semi-planar YUV frames (numpy array, or torch tensor of
+    uint16 / int16) as melf_process_yuv16* read it.  pixel_format, a name of YUV16_FORMATS: 4:2:0 'p010', 'p012', 'p016' (semi-planar,
+    the value in the high bits), 'i010' / 'yuv420p10le', 'i012' / 'yuv420p12le', 'yuv420p16le' (planar, the value in the low bits)
+    with rows = 3 H / 2; 4:2:2 'p210', 'p216', 'i210' / 'yuv422p10le', 'i212' / 'yuv422p12le', 'yuv422p16le' with rows = 2 H.  Rows
+    0 .. H - 1 are Y; behind them the U plane and then the V plane, H >> sub_y rows of W / 2 samples each, or one plane of
+    interleaved U V pairs, W samples a row.  The frame stride is honoured in place (frames[::2], frames[a:b]), and so is a
+    row-padded view (frames[:, :, :w]) of the semi-planar formats, whose chroma row is one row of the array.  Anything else -- padded
+    rows of a planar format (its chroma rows are half rows of the array), an element stride other than 1, negative strides -- is
+    copied once to a packed array (Yuv16FramesView.copied).  matrix: a name of YUV_MATRIX_CODES or a code; there is no default:
+    nearly all 10-bit material is BT.709, and the wrong matrix raises no error.  Not 16-bit samples, a shape that is not that of the
+    format, an odd W (an odd H for 4:2:0), an unknown format or an unknown matrix: ValueError."""
+    mcode = yuv_matrix_code(matrix)
+    (frames, is_torch, shape, strides, ptr, on_device, device) = _unwrap16(frames)
+    fmt = str(pixel_format).lower()
+    if fmt not in YUV16_FORMATS:
+        raise ValueError('pixel_format %r is not a 16-bit planar / semi-planar YUV layout (%s)' % (pixel_format, ', '.join(YUV16_FORMATS)))
+    (sy, step, vfirst, shift) = YUV16_FORMATS[fmt]
+    blocks = 2 << sy                                  # pixels per chroma sample: rows = H * (blocks + 2) / blocks
+    bad = len(shape) != 3 or shape[1] == 0 or shape[2] == 0 or (shape[1] * blocks) % (blocks + 2) != 0
+    if not bad:
+        (n, rows, W) = shape
+        H = rows * blocks // (blocks + 2)
+        bad = W % 2 or (sy and H % 2)
+    if bad:
+        raise ValueError('%s frames must be (N, H * %d // %d, W) with an even W%s, not %s'
+                         % (fmt, blocks + 2, blocks, ' and an even H' * sy, shape))
+    (fs, rp, es) = strides
+    (cw, ch) = ((W >> 1) * step * 2, H >> sy)         # bytes of a chroma row (semi-planar: of both), chroma rows
+    if n == 1:
+        fs = rows * rp if rp > 0 else 0
+    whole_rows = step == 2                            # a chroma row is one row of the array: padded rows can be described
+    even = rp % 2 == 0 and fs % 2 == 0 and ptr % 2 == 0     # whole samples: odd byte strides or an odd base cannot be described
+    ok = es == 2 and even and 2 * W <= rp <= 2 ** 31 - 1 and fs >= (rows - 1) * rp + 2 * W and (whole_rows or rp == 2 * W)
+    if not ok:
+        (frames, ptr) = _packed_copy(frames, is_torch)
+        (rp, fs) = (2 * W, rows * 2 * W)
+    c_pitch = rp if whole_rows else cw
+    first = H * rp
+    if step == 2:
+        (u_off, v_off) = (first + 2, first) if vfirst else (first, first + 2)
+        last = first + (ch - 1) * c_pitch + cw
+    else:
+        second = first + ch * c_pitch
+        (u_off, v_off) = (second, first) if vfirst else (first, second)
+        last = second + (ch - 1) * c_pitch + cw
+    extent = (n - 1) * fs + last if n else 0
+    return Yuv16FramesView(int(ptr), on_device, device, n, H, W, sy, step, shift, int(rp), int(c_pitch), int(u_off), int(v_off), int(fs),
+                           int(extent), not ok, frames, mcode)
+
+
 class PlanarFramesView(NamedTuple):
     """How the kernels read a batch of planar (channels-first) frames in place (planar_frames_view)."""
     ptr: int            # address of frame 0's first plane
@@ -927,6 +1051,21 @@ class Context:
         check(self._L.melf_yuv_planar_to_bgr(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
         return out
 
+    def process_yuv16(self, frames_ptr, desc):
+        """Host 16-bit planar / semi-planar YUV frames (melf_process_yuv16; desc: a MelfYuv16Frames, e.g.
+        yuv16_frames_view(...).descriptor()) -> records."""
+        return self._host(self._L.melf_process_yuv16, frames_ptr, desc)
+
+    def process_yuv16_dev(self, d_frames_ptr, desc, d_results_ptr=None, want_host=True, stream=None):
+        """16-bit planar / semi-planar YUV frames in HBM (melf_process_yuv16_dev, as process_frames_dev).  Returns records when want_host."""
+        return self._dev(self._L.melf_process_yuv16_dev, d_frames_ptr, desc, d_results_ptr, want_host, stream)
+
+    def yuv16_to_bgr(self, frames_ptr, desc):
+        """Reduction and conversion alone (melf_yuv16_to_bgr): host 16-bit planar / semi-planar YUV frames -> (n, H, W, 3) BGR."""
+        out = np.empty((desc.n, desc.H, desc.W, 3), np.uint8)
+        check(self._L.melf_yuv16_to_bgr(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
+        return out
+
     def process_planes(self, frames_ptr, desc):
         """Host planar frames (melf_process_planes; desc: a MelfPlanarFrames, e.g. planar_frames_view(...).descriptor()) -> records."""
         return self._host(self._L.melf_process_planes, frames_ptr, desc)
@@ -1114,7 +1253,8 @@ class Context:
         None before the first launch), 'nr' (window rows a lane requests up front) and 'ws_max' (the context's largest window)."""
         (nr, fam, ws) = (C.c_int(0), C.c_int(0), C.c_int(0))
         check(self._L.melf_ctx_last_dials(self._h, C.byref(nr), C.byref(fam), C.byref(ws)))
-        return dict(family=DIALS_FAMILIES[fam.value] if fam.value >= 0 else None, nr=nr.value, ws_max=ws.value)
+        names = DIALS_FAMILIES + DIALS16_FAMILIES   # (the 16-bit families' values go on from the twelve's)
+        return dict(family=names[fam.value] if fam.value >= 0 else None, nr=nr.value, ws_max=ws.value)
 
     def set_profiling(self, on):
         check(self._L.melf_ctx_set_profiling(self._h, int(on)))  # False/0 off, True/1 every kernel, 2 only k_match

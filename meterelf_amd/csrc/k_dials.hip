@@ -278,6 +278,20 @@ __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_v
 #include "k_dials_body.inc"
 }
 
+// Planar / semi-planar YUV frames of 16-bit samples (melf_process_yuv16*): src describes the Y plane (strides in bytes), yuv the
+// chroma and the reduction to 8 bits.  One instantiation per CSTEP (samples between the samples of a chroma plane) and NR; sub_y,
+// shift, the order of a pair's samples and the matrix are runtime, wave-uniform values.
+template <int CSTEP, int NR>
+__global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_vgpr(DIALS_VGPRS))) void k_y16_needle(DialsSrc src, Yuv16Planes yuv, YuvMatrix ymat, melf_params P,
+                                                                const DialGeom* __restrict__ geom,
+                                                                const uint64_t* __restrict__ rowmasks,
+                                                                const MatchPartial* __restrict__ partials,
+                                                                int nparts, int rw, melf_result* __restrict__ results)
+{
+    using Src = DialYuv16<CSTEP>; const typename Src::Args sargs{yuv, ymat};
+#include "k_dials_body.inc"
+}
+
 // Planar frames (melf_process_planes*): the B, G and R planes at `planes` in a frame.  Past its loads the body is the one of 4-byte
 // B G R pixels.
 template <int NR>
@@ -322,7 +336,11 @@ DialsLaunch launch_dials(const DialsSrc& src, const FrameLayout& lay, int n, con
             const int swap_rb = pix == MELF_PIX_RGB || pix == MELF_PIX_RGBA;
             hipLaunchKernelGGL(kernel, grid, block, shmem, stream, src, P, d_geom, d_rowmasks, d_partials, nparts, rw, d_results, swap_rb);
         };
-        if (pix == PIX_YUVP) {
+        if (pix == PIX_YUV16) {
+            if (lay.y16.c_step == 1) { ran.family = MELF_DIALS16_STEP1; go(k_y16_needle<1, NR>, lay.y16, *lay.mx); }
+            else { ran.family = MELF_DIALS16_STEP2; go(k_y16_needle<2, NR>, lay.y16, *lay.mx); }
+        }
+        else if (pix == PIX_YUVP) {
             const YuvPlanarPlanes& yp = lay.yuvp;
             if (yp.sub_x == 0) {
                 if (yp.c_step == 1) { ran.family = MELF_DIALS_YP_SUB0_STEP1; go(k_yp_needle<0, 1, NR>, yp, *lay.mx); }

@@ -91,8 +91,10 @@
     constexpr int NG = NR / 4;
     static_assert(NR % 4 == 0, "window rows come in groups of four");
     const int rg = lane >> 4, pc = lane & 15;
-    const int npiece = (ws + 3) >> 2;   // wave-uniform: 12-byte pieces of a window row
-    auto W = FS.window(wx0, npiece, pc, th1, rs_u, P.tw);
+    // (EVEN_QUADS sources: the quads start qshift = 0 or 1 columns left of the window, wave-uniform; 0 and compiled out elsewhere)
+    const int qshift = Src::EVEN_QUADS ? FS.quad_shift(wx0) : 0;
+    const int npiece = Src::EVEN_QUADS ? (ws + qshift + 3) >> 2 : (ws + 3) >> 2;   // wave-uniform: 12-byte pieces of a window row
+    auto W = FS.window(Src::EVEN_QUADS ? wx0 - qshift : wx0, npiece, pc, th1, rs_u, P.tw);
     const bool quads = W.quads;   // wave-uniform; otherwise every pixel takes the exact path below
     u32x4v raw[NG];
     if (quads) {
@@ -171,8 +173,12 @@
         const uint32_t SLO = (uint32_t)max(los - 1, 0) * 0x00010001u, SHI = (uint32_t)(his + 1) * 0x00010001u;
         const int xleft = ws - 4 * pc;   // pixels j < xleft of this lane's four are window columns
         // the lanes whose pixel j is a window column, as wave masks: a pixel's candidacy is then ballot(test) & masks, scalar work
-        const uint64_t xm[4] = {__builtin_amdgcn_ballot_w64(0 < xleft), __builtin_amdgcn_ballot_w64(1 < xleft),
-                                __builtin_amdgcn_ballot_w64(2 < xleft), __builtin_amdgcn_ballot_w64(3 < xleft)};
+        uint64_t xm[4] = {__builtin_amdgcn_ballot_w64(0 < xleft), __builtin_amdgcn_ballot_w64(1 < xleft),
+                          __builtin_amdgcn_ballot_w64(2 < xleft), __builtin_amdgcn_ballot_w64(3 < xleft)};
+        if constexpr (Src::EVEN_QUADS) {   // pixel j is window column 4 pc + j - qshift
+#pragma unroll
+            for (int j = 0; j < 4; ++j) xm[j] = __builtin_amdgcn_ballot_w64((uint32_t)(4 * pc + j - qshift) < (uint32_t)ws);
+        }
         if (quads) {
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
@@ -211,7 +217,7 @@
                             const int slot = total + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(cb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cb, 0u));
                             const bool cand = (cb >> lane) & 1ull;
                             if (cand && slot < DIAL_LIST_CAP) {
-                                list_pos[slot] = (uint16_t)(y << 6 | (4 * pc + j));
+                                list_pos[slot] = (uint16_t)(y << 6 | (Src::EVEN_QUADS ? 4 * pc + j - qshift : 4 * pc + j));
                                 if constexpr (PB == 4)
                                     list_px[slot] = FS.bgr(j == 0 ? q4.x : (j == 1 ? q4.y : (j == 2 ? q4.z : q4.w)));
                                 else

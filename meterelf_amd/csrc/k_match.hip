@@ -18,6 +18,7 @@
 
 #include "melf_device.h"
 #include "melf_internal.h"
+#include "melf_y16_addr.h"
 
 namespace melf {
 
@@ -33,7 +34,9 @@ __device__ inline bool better(float v, int i, float bv, int bi)
 // YUV 4:2:2 frames (yuv: P422Sel, the byte permute to Y0 U Y1 V; a pixel's macropixel as one aligned dword load); 23 = planar
 // frames (melf_process_planes*; yuv: PlanarPlanes, where the B, G and R planes start in a frame; three byte loads per pixel);
 // 24 = planar / semi-planar YUV of any subsampling (melf_process_yuv_planar*; yuv: YuvPlanarPlanes; a Y byte and the chroma bytes
-// at (y >> sub_y, x >> sub_x) per pixel, byte loads: the shifts and the sample step are wave-uniform scalars).
+// at (y >> sub_y, x >> sub_x) per pixel, byte loads: the shifts and the sample step are wave-uniform scalars); 25 = 16-bit planar /
+// semi-planar YUV (melf_process_yuv16*; yuv: Yuv16Planes; a Y sample and the chroma samples at (y >> sub_y, x >> 1) per pixel, 2-byte
+// loads, each reduced to 8 bits by y16::reduce).
 struct NoYuv {};
 struct P422Sel { uint32_t sel; };
 template <int PX, class YUV = NoYuv>
@@ -67,6 +70,10 @@ __device__ __forceinline__ void match_tile(MatchSrc src, MatchGeom g, const uint
             urow = img + (size_t)yuv.u_off + (size_t)((src.y0 + y) >> yuv.sub_y) * (size_t)yuv.c_pitch;
             vrow = img + (size_t)yuv.v_off + (size_t)((src.y0 + y) >> yuv.sub_y) * (size_t)yuv.c_pitch;
         }
+        if constexpr (PX == 25) {
+            urow = img + (size_t)yuv.u_off;
+            vrow = img + (size_t)yuv.v_off;
+        }
         for (int c4 = lane; c4 < g.ldsw; c4 += 64) {
             uint32_t packed = 0;
             if (y < src.rows) {
@@ -83,6 +90,11 @@ __device__ __forceinline__ void match_tile(MatchSrc src, MatchGeom g, const uint
                             const int ci = ((src.x0 + x) >> yuv.sub_x) << (yuv.c_step - 1);
                             const YuvChroma c = yuv_chroma(urow[ci], vrow[ci], mx);
                             v = (uint32_t)yuv_lightness(prow[src.x0 + x], yuv_cmax(c), yuv_cmin(c), mx);
+                        } else if constexpr (PX == 25) {
+                            const size_t co = y16::px_c_off(src.y0 + y, yuv.sub_y, (size_t)yuv.c_pitch, src.x0 + x, yuv.c_step);
+                            const uint32_t sft = (uint32_t)yuv.shift;
+                            const YuvChroma c = yuv_chroma((int)y16::reduce(*(const uint16_t*)(urow + co), sft), (int)y16::reduce(*(const uint16_t*)(vrow + co), sft), mx);
+                            v = (uint32_t)yuv_lightness((int)y16::reduce(*(const uint16_t*)(prow + (size_t)(src.x0 + x) * 2), sft), yuv_cmax(c), yuv_cmin(c), mx);
                         } else if constexpr (PX == 22) {
                             const int fx = src.x0 + x;
                             const uint32_t m = __builtin_amdgcn_perm(0u, *(const uint32_t*)(prow + (size_t)(fx >> 1) * 4), yuv.sel);
@@ -229,6 +241,14 @@ __global__ __launch_bounds__(256) void k_yp_match(MatchSrc src, YuvPlanarPlanes 
     match_tile<24, YuvPlanarPlanes>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts, yuv, mx);
 }
 
+// 16-bit planar / semi-planar YUV (melf_process_yuv16*): the dot4 matcher with a Y sample and two chroma samples per pixel
+__global__ __launch_bounds__(256) void k_y16_match(MatchSrc src, Yuv16Planes yuv, YuvMatrix mx, MatchGeom g, const uint32_t* __restrict__ tplT,
+                                                   int rh, int rw, int nrb, float* __restrict__ result_map,
+                                                   MatchPartial* __restrict__ partials, int nparts)
+{
+    match_tile<25, Yuv16Planes>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts, yuv, mx);
+}
+
 int match_parts(const MatchGeom& g, int rows, int cols)
 {
     const int rh = rows - g.th + 1, rw = cols - g.tw + 1;
@@ -247,7 +267,10 @@ void launch_match(const MatchSrc& src, const FrameLayout& lay, int n, const Matc
     if (nparts_out) *nparts_out = nparts;
     const size_t shmem = (size_t)g.lds_rows * g.ldsw * sizeof(uint32_t);
     dim3 grid(nparts, n), block(256);
-    if (pix == PIX_YUVP)
+    if (pix == PIX_YUV16)
+        hipLaunchKernelGGL(k_y16_match, grid, block, shmem, stream, src, lay.y16, *lay.mx, g, d_tplT, rh, rw, nrb, d_result_map,
+                           d_partials, nparts);
+    else if (pix == PIX_YUVP)
         hipLaunchKernelGGL(k_yp_match, grid, block, shmem, stream, src, lay.yuvp, *lay.mx, g, d_tplT, rh, rw, nrb, d_result_map,
                            d_partials, nparts);
     else if (pix == PIX_PLANAR)

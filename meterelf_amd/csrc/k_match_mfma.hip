@@ -35,6 +35,7 @@
 #include <hip/hip_ext.h>
 
 #include "melf_internal.h"
+#include "melf_y16_addr.h"
 
 namespace melf {
 
@@ -146,6 +147,37 @@ __global__ __launch_bounds__(256) void k_yp_lplane(MatchSrc src, YuvPlanarPlanes
 #include "prep_lplane_body.inc"
 }
 #undef MELF_YUVP_BODY
+
+// NS consecutive 16-bit samples from byte o of the buffer at `base` (o and base 2-byte aligned; o - m >= 0: the caller has checked
+// it; m = the byte phase of base + o, 0 or 2), each reduced to 8 bits -- min(s >> shift, 255), two samples a dword by a packed 16-bit
+// shift and minimum -- and packed four to a dword: out holds the NS bytes from its byte 0 on.  The loads are load_window's.
+typedef unsigned short u16x2m __attribute__((ext_vector_type(2)));
+template <int NS>
+__device__ __forceinline__ void load_window16(const uint8_t* base, size_t o, uint32_t m, uint32_t shift, uint32_t (&out)[(NS + 3) / 4])
+{
+    constexpr int ND = (2 * NS + 3) / 4;   // dwords of two samples
+    uint32_t d[ND];
+    load_window<2 * NS>(base, o, m, d);
+    const u16x2m sh2 = {(unsigned short)shift, (unsigned short)shift}, top = {255, 255};
+#pragma unroll
+    for (int i = 0; i < ND; ++i)
+        d[i] = __builtin_bit_cast(uint32_t, __builtin_elementwise_min((u16x2m)(__builtin_bit_cast(u16x2m, d[i]) >> sh2), top));
+#pragma unroll
+    for (int i = 0; i < (NS + 3) / 4; ++i) out[i] = __builtin_amdgcn_perm(2 * i + 1 < ND ? d[2 * i + 1] : 0u, d[2 * i], 0x06040200u);
+}
+
+// Planar / semi-planar YUV frames of 16-bit samples (melf_process_yuv16*): src is the Y plane (strides in bytes), yuv the chroma and
+// the reduction.  One instantiation per CSTEP (samples between the samples of a chroma plane; 2: interleaved pairs); sub_y, shift
+// and the order of a pair's samples are runtime, wave-uniform values.  L straight from the reduced Y, U, V as in k_yp_lplane.
+#define MELF_Y16_BODY
+template <int CSTEP>
+__global__ __launch_bounds__(256) void k_y16_lplane(MatchSrc src, Yuv16Planes yuv, YuvMatrix mx, int nframes, int nkb, int rows_pad, int tw, int rwp, int pairs,
+                                                    int8_t* __restrict__ Lg, uint16_t* __restrict__ R)
+{
+    constexpr int PX = 25;
+#include "prep_lplane_body.inc"
+}
+#undef MELF_Y16_BODY
 
 // ---------------------------------------------------------------------------
 // k_match_mfma
@@ -849,9 +881,16 @@ void launch_match_prep(const MatchSrc& src, const FrameLayout& lay, int n, int g
         (void)hipFuncSetAttribute((const void*)k_yp_lplane<0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute((const void*)k_yp_lplane<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute((const void*)k_yp_lplane<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_y16_lplane<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_y16_lplane<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         attr_set[dev] = true;
     }
-    if (pix == PIX_YUVP) {
+    if (pix == PIX_YUV16) {
+        const Yuv16Planes& yp = lay.y16;
+        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, pre_bytes, stream, src, yp, *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r); };
+        if (yp.c_step == 1) go(k_y16_lplane<1>); else go(k_y16_lplane<2>);
+    }
+    else if (pix == PIX_YUVP) {
         const YuvPlanarPlanes& yp = lay.yuvp;
         auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, pre_bytes, stream, src, yp, *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r); };
         if (yp.sub_x == 0) { if (yp.c_step == 1) go(k_yp_lplane<0, 1>); else go(k_yp_lplane<0, 2>); }

@@ -7,6 +7,7 @@
 // Y, two 6-byte rows of B G R out.  A parity and debugging aid, not a hot path: the hot path never forms the BGR frame.
 #include "melf_device.h"
 #include "melf_internal.h"
+#include "melf_y16_addr.h"
 
 namespace melf {
 
@@ -103,6 +104,40 @@ void launch_yuvp_to_bgr(const uint8_t* d_src, int n, int H, int W, int y_pitch, 
         const int m = n - f0 < 65535 ? n - f0 : 65535;
         dim3 grid((W + 255) / 256, H < 65535 ? H : 65535, m), block(256);
         hipLaunchKernelGGL(k_yp_to_bgr, grid, block, 0, stream, d_src + (size_t)f0 * frame_stride, H, W, y_pitch, frame_stride, yp, mx,
+                           d_dst + (size_t)f0 * H * W * 3);
+    }
+}
+
+// 16-bit planar / semi-planar YUV -> BGR alone: the stage kernel behind melf_yuv16_to_bgr.  One thread per pixel: its Y sample and
+// the chroma samples at (y >> sub_y, x >> 1), 2-byte loads at the address formula of include/meterelf_hip.h as it stands, each
+// reduced to 8 bits (y16::reduce: the statement of min(s >> shift, 255) every reading kernel shares), three bytes out.  This kernel
+// pins the addressing, the reduction and the arithmetic for every sample value; like k_yuv2bgr it is no hot path.
+__global__ __launch_bounds__(256) void k_y16_to_bgr(const uint8_t* __restrict__ src, int H, int W, int y_pitch, size_t frame_stride,
+                                                    Yuv16Planes yp, YuvMatrix mx, uint8_t* __restrict__ dst)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.z;
+    if (x >= W) return;
+    const uint8_t* frame = src + (size_t)f * frame_stride;
+    const uint32_t sh = (uint32_t)yp.shift;
+    for (int y = blockIdx.y; y < H; y += gridDim.y) {
+        const size_t co = y16::px_c_off(y, yp.sub_y, (size_t)yp.c_pitch, x, yp.c_step);
+        const uint32_t u = *(const uint16_t*)(frame + (size_t)yp.u_off + co), v = *(const uint16_t*)(frame + (size_t)yp.v_off + co);
+        const uint32_t ys = *(const uint16_t*)(frame + y16::px_y_off(y, (size_t)y_pitch, x));
+        const YuvChroma c = yuv_chroma((int)y16::reduce(u, sh), (int)y16::reduce(v, sh), mx);
+        const uint32_t p = yuv_bgr((int)y16::reduce(ys, sh), c, mx);
+        uint8_t* o = dst + (((size_t)f * H + y) * (size_t)W + (size_t)x) * 3;
+        o[0] = (uint8_t)p; o[1] = (uint8_t)(p >> 8); o[2] = (uint8_t)(p >> 16);
+    }
+}
+
+void launch_y16_to_bgr(const uint8_t* d_src, int n, int H, int W, int y_pitch, size_t frame_stride, const Yuv16Planes& yp,
+                       const YuvMatrix& mx, uint8_t* d_dst, hipStream_t stream)
+{
+    // at most 65 535 frames per launch (grid z); a workgroup row takes every 65 535th image row (grid y)
+    for (int f0 = 0; f0 < n; f0 += 65535) {
+        const int m = n - f0 < 65535 ? n - f0 : 65535;
+        dim3 grid((W + 255) / 256, H < 65535 ? H : 65535, m), block(256);
+        hipLaunchKernelGGL(k_y16_to_bgr, grid, block, 0, stream, d_src + (size_t)f0 * frame_stride, H, W, y_pitch, frame_stride, yp, mx,
                            d_dst + (size_t)f0 * H * W * 3);
     }
 }

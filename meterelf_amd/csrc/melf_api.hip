@@ -1300,6 +1300,48 @@ static int check_yuv_planar(const melf_ctx* c, const void* frames, const melf_yu
     return MELF_SUCCESS;
 }
 
+// melf_yuv16_frames (melf_process_yuv16*, melf_yuv16_to_bgr): check_yuv_planar's cases for sub_x 1, restated in bytes and samples of
+// 2 bytes; base, frame_stride and row_stride (bytes) describe the Y plane; the extent reaches to the last sample of the last plane
+static int check_yuv16(const melf_ctx* c, const void* frames, const melf_yuv16_frames* f, FrameBatch* b)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    if (!f) return fail(MELF_ERR_INVALID, "16-bit YUV frame descriptor is NULL");
+    if (f->reserved != 0) return fail(MELF_ERR_INVALID, "reserved field of the 16-bit YUV frame descriptor is not 0");
+    if (f->sub_y != 0 && f->sub_y != 1) return fail(MELF_ERR_INVALID, "sub_y must be 0 or 1 (log2 of the vertical chroma subsampling)");
+    if (f->c_step != 1 && f->c_step != 2) return fail(MELF_ERR_INVALID, "c_step must be 1 (planar) or 2 (semi-planar) samples");
+    if (f->shift < 0 || f->shift > 8) return fail(MELF_ERR_INVALID, "shift must be 0 .. 8 (low bits dropped from a 16-bit sample)");
+    const YuvMatrix* mx = yuv_matrix(f->matrix);
+    if (!mx)
+        return fail(MELF_ERR_INVALID, "unknown YUV matrix (accepted: 0 BT.601 limited, 2 BT.601 full, 3 BT.709 limited, 4 BT.709 full)");
+    if (f->n < 0 || f->H <= 0 || f->W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
+    if (f->W & 1) return fail(MELF_ERR_INVALID, "horizontally subsampled chroma needs an even width");
+    if (f->sub_y && (f->H & 1)) return fail(MELF_ERR_INVALID, "vertically subsampled chroma (sub_y) needs an even height");
+    if (f->u_offset < 0 || f->v_offset < 0) return fail(MELF_ERR_INVALID, "negative chroma offset");
+    if ((f->y_pitch | f->c_pitch | f->u_offset | f->v_offset | f->frame_stride) & 1)
+        return fail(MELF_ERR_INVALID, "16-bit samples need an even y_pitch, c_pitch, u_offset, v_offset and frame_stride (bytes)");
+    const bool semi = f->c_step == 2;
+    if (semi && f->u_offset - f->v_offset != 2 && f->v_offset - f->u_offset != 2)
+        return fail(MELF_ERR_INVALID, "c_step 2 (semi-planar) needs u_offset and v_offset 2 bytes apart");
+    if (f->y_pitch < (int64_t)f->W * 2 || f->y_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "y_pitch smaller than a row of 2-byte samples (or too large)");
+    const int64_t cw = (int64_t)(f->W >> 1) * f->c_step * 2, ch = f->H >> f->sub_y;   // bytes of a chroma row (semi-planar: of both), rows
+    if (f->c_pitch < cw || f->c_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "c_pitch smaller than a chroma row of 2-byte samples (or too large)");
+    const int64_t y_end = (int64_t)(f->H - 1) * f->y_pitch + (int64_t)f->W * 2;
+    const int64_t c_lo = f->u_offset < f->v_offset ? f->u_offset : f->v_offset, c_hi = f->u_offset < f->v_offset ? f->v_offset : f->u_offset;
+    const int64_t c_len = (ch - 1) * f->c_pitch + (semi ? cw - 2 : cw);   // bytes from a plane's offset to the end of its last sample
+    if (c_hi > INT64_MAX - c_len) return fail(MELF_ERR_INVALID, "chroma offset too large");
+    if (c_lo < y_end) return fail(MELF_ERR_INVALID, "a chroma offset lies inside the Y plane's span (first to last sample): spans may not overlap");
+    if (!semi && c_hi - c_lo < c_len)
+        return fail(MELF_ERR_INVALID, "the spans (first to last sample) of the two chroma planes overlap: U and V rows sharing one pitch are not taken");
+    const int64_t c_end = c_hi + c_len;
+    if (f->frame_stride < c_end) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
+    const Yuv16Planes yp = {f->u_offset, f->v_offset, (int)f->c_pitch, f->sub_y, f->c_step, f->shift};
+    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->y_pitch, FrameLayout::yuv16(yp, *mx, (size_t)c_end)};
+    if (f->n == 0) return MELF_SUCCESS;
+    if (!frames) return fail(MELF_ERR_INVALID, "frames pointer is NULL");
+    if ((uintptr_t)frames & 1) return fail(MELF_ERR_INVALID, "16-bit samples need a 2-byte aligned base");
+    return MELF_SUCCESS;
+}
+
 // melf_planar_frames (melf_process_planes*): the extent reaches to the last sample of the frame's last plane
 static int check_planes(const melf_ctx* c, const void* frames, const melf_planar_frames* f, FrameBatch* b)
 {
@@ -1372,6 +1414,15 @@ extern "C" int melf_process_yuv_planar_dev(melf_ctx* c, const void* d_frames, co
 {
     FrameBatch b;
     if (int rc = check_yuv_planar(c, d_frames, f, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return batch_dev(c, d_frames, b, d_results, out_host, stream_);
+}
+
+extern "C" int melf_process_yuv16_dev(melf_ctx* c, const void* d_frames, const melf_yuv16_frames* f, void* d_results,
+                                      melf_result* out_host, void* stream_)
+{
+    FrameBatch b;
+    if (int rc = check_yuv16(c, d_frames, f, &b)) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return batch_dev(c, d_frames, b, d_results, out_host, stream_);
 }
@@ -1679,16 +1730,19 @@ static int host_p422(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& 
     });
 }
 
-// Planar / semi-planar YUV of any subsampling: the staged frame is a small frame of the same layout -- the same subsampling, sample
-// step and order of U and V --, the Y rows of the crop with its origin rounded down (and its far corner up) to whole chroma blocks
+// Planar / semi-planar YUV of any subsampling and sample size: the staged frame is a small frame of the same layout -- the same
+// subsampling, sample step and order of U and V, and for 16-bit samples the same shift, the samples copied as they are (nothing is
+// reduced on the CPU) --, the Y rows of the crop with its origin rounded down (and its far corner up) to whole chroma blocks
 // (1 << sub_x by 1 << sub_y) and the chroma rows under them; the kernels read it with the rectangle shifted by the rounding (0 or 1
 // pixel each way), under the caller's matrix.  Work items: the Y rows in blocks of 32, and the chroma rows as one more.
-static int host_yuv_planar(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host)
+// bps: bytes per sample; step: samples from one sample of a chroma plane to the next; u_off, v_off, c_pitch: the source's, in
+// bytes; layout(u_off, v_off, c_pitch, frame_stride): the small frame's FrameLayout, the source's with these four replaced.
+template <class MakeLayout>
+static int host_yuv_planes(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host, int bps, int sx, int sy,
+                           int step, int64_t u_off, int64_t v_off, int c_pitch, MakeLayout layout)
 {
     Crop cr;
     if (int rc = host_crop(c, b, out_host, &cr)) return rc;
-    const YuvPlanarPlanes src_planes = b.lay.yuvp;
-    const int sx = src_planes.sub_x, sy = src_planes.sub_y, step = src_planes.c_step;
     const bool semi = step == 2;
     const size_t y_pitch = (size_t)b.row_stride;
     const int bx = 1 << sx, by = 1 << sy;
@@ -1696,41 +1750,60 @@ static int host_yuv_planar(melf_ctx* c, const uint8_t* frames_host, const FrameB
     // the small frame (whole blocks, inside the frame: W and H are whole blocks)
     const int sw = ((cr.x1 + bx - 1) & ~(bx - 1)) - ex0, sh = ((cr.y1 + by - 1) & ~(by - 1)) - ey0;
     const int crows = sh >> sy;                                      // chroma rows of the small frame
-    const size_t ypitch = pitch64((size_t)sw);
-    const size_t cbytes = (size_t)(sw >> sx) * (size_t)step;         // bytes of a chroma row (semi-planar: of both)
+    const size_t ybytes = (size_t)sw * (size_t)bps, ypitch = pitch64(ybytes);
+    const size_t cbytes = (size_t)(sw >> sx) * (size_t)step * (size_t)bps;   // bytes of a chroma row (semi-planar: of both)
     const size_t cpitch = pitch64(cbytes);
     const size_t c0 = (size_t)sh * ypitch;                           // the first chroma byte of the small frame
-    const int64_t src_lo = src_planes.u_off < src_planes.v_off ? src_planes.u_off : src_planes.v_off;
-    YuvPlanarPlanes sp_planes = src_planes;
-    sp_planes.c_pitch = (int)cpitch;
-    if (semi) {
-        sp_planes.u_off = (int64_t)c0 + (src_planes.u_off - src_lo);
-        sp_planes.v_off = (int64_t)c0 + (src_planes.v_off - src_lo);
-    } else {
-        sp_planes.u_off = (int64_t)c0;
-        sp_planes.v_off = (int64_t)(c0 + (size_t)crows * cpitch);
-    }
+    const int64_t src_lo = u_off < v_off ? u_off : v_off;
+    const int64_t su_off = semi ? (int64_t)c0 + (u_off - src_lo) : (int64_t)c0;
+    const int64_t sv_off = semi ? (int64_t)c0 + (v_off - src_lo) : (int64_t)(c0 + (size_t)crows * cpitch);
     const size_t crop_stride = c0 + (size_t)crows * cpitch * (semi ? 1 : 2) + 128;
     const int rblocks = (sh + 31) / 32;
-    const StagePlan sp = {{0, sh, sw, crop_stride, (int)ypitch, FrameLayout::yuv_planar(sp_planes, *b.lay.mx, crop_stride)},
+    const StagePlan sp = {{0, sh, sw, crop_stride, (int)ypitch, layout(su_off, sv_off, (int)cpitch, crop_stride)},
                           {cr.x0 - ex0, cr.y0 - ey0, cr.x0 - ex0 + cr.cols, cr.y0 - ey0 + cr.rows}, rblocks + 1};
     return stage_host_frames(c, frames_host, b.n, b.frame_stride, sp, out_host, [=](const uint8_t* frame, uint8_t* small, int part) {
         if (part < rblocks) {
             const int r0 = part * 32, r1 = r0 + 32 < sh ? r0 + 32 : sh;
-            for (int y = r0; y < r1; ++y) memcpy(small + (size_t)y * ypitch, frame + (size_t)(ey0 + y) * y_pitch + ex0, (size_t)sw);
+            for (int y = r0; y < r1; ++y)
+                memcpy(small + (size_t)y * ypitch, frame + (size_t)(ey0 + y) * y_pitch + (size_t)ex0 * (size_t)bps, ybytes);
         } else {
-            const size_t cx = (size_t)(ex0 >> sx) * (size_t)step;
+            const size_t cx = (size_t)(ex0 >> sx) * (size_t)step * (size_t)bps;
             for (int y = 0; y < crows; ++y) {
-                const size_t so = (size_t)((ey0 >> sy) + y) * (size_t)src_planes.c_pitch + cx;
+                const size_t so = (size_t)((ey0 >> sy) + y) * (size_t)c_pitch + cx;
                 if (semi) {
                     memcpy(small + c0 + (size_t)y * cpitch, frame + (size_t)src_lo + so, cbytes);
                 } else {
-                    memcpy(small + (size_t)sp_planes.u_off + (size_t)y * cpitch, frame + (size_t)src_planes.u_off + so, cbytes);
-                    memcpy(small + (size_t)sp_planes.v_off + (size_t)y * cpitch, frame + (size_t)src_planes.v_off + so, cbytes);
+                    memcpy(small + (size_t)su_off + (size_t)y * cpitch, frame + (size_t)u_off + so, cbytes);
+                    memcpy(small + (size_t)sv_off + (size_t)y * cpitch, frame + (size_t)v_off + so, cbytes);
                 }
             }
         }
     });
+}
+
+static int host_yuv_planar(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host)
+{
+    const YuvPlanarPlanes src = b.lay.yuvp;
+    const YuvMatrix* mx = b.lay.mx;
+    return host_yuv_planes(c, frames_host, b, out_host, 1, src.sub_x, src.sub_y, src.c_step, src.u_off, src.v_off, src.c_pitch,
+                           [=](int64_t u_off, int64_t v_off, int c_pitch, size_t stride) {
+                               YuvPlanarPlanes p = src;
+                               p.u_off = u_off; p.v_off = v_off; p.c_pitch = c_pitch;
+                               return FrameLayout::yuv_planar(p, *mx, stride);
+                           });
+}
+
+// 16-bit samples: sub_x is 1, the sample 2 bytes.
+static int host_yuv16(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host)
+{
+    const Yuv16Planes src = b.lay.y16;
+    const YuvMatrix* mx = b.lay.mx;
+    return host_yuv_planes(c, frames_host, b, out_host, 2, 1, src.sub_y, src.c_step, src.u_off, src.v_off, src.c_pitch,
+                           [=](int64_t u_off, int64_t v_off, int c_pitch, size_t stride) {
+                               Yuv16Planes p = src;
+                               p.u_off = u_off; p.v_off = v_off; p.c_pitch = c_pitch;
+                               return FrameLayout::yuv16(p, *mx, stride);
+                           });
 }
 
 // Planar: the staged frame is a small planar frame, the crop's rows of the B, the G and the R plane, one plane after the other,
@@ -1797,6 +1870,14 @@ extern "C" int melf_process_yuv_planar(melf_ctx* c, const void* frames_host, con
     return host_yuv_planar(c, (const uint8_t*)frames_host, b, out_host);
 }
 
+extern "C" int melf_process_yuv16(melf_ctx* c, const void* frames_host, const melf_yuv16_frames* f, melf_result* out_host)
+{
+    FrameBatch b;
+    if (int rc = check_yuv16(c, frames_host, f, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return host_yuv16(c, (const uint8_t*)frames_host, b, out_host);
+}
+
 extern "C" int melf_process_planes(melf_ctx* c, const void* frames_host, const melf_planar_frames* f, melf_result* out_host)
 {
     FrameBatch b;
@@ -1806,7 +1887,7 @@ extern "C" int melf_process_planes(melf_ctx* c, const void* frames_host, const m
 }
 
 // ---------------------------------------------------------- stage entries ----
-// melf_yuv_to_bgr / melf_yuv422_to_bgr / melf_yuv_planar_to_bgr after their checks: the frames up, the conversion kernel alone, n packed H x W BGR frames down
+// melf_yuv_to_bgr / melf_yuv422_to_bgr / melf_yuv_planar_to_bgr / melf_yuv16_to_bgr after their checks: the frames up, the conversion kernel alone, n packed H x W BGR frames down
 static int to_bgr(melf_ctx* c, const void* frames_host, const FrameBatch& b, uint8_t* bgr_out_host)
 {
     if (!bgr_out_host) return fail(MELF_ERR_INVALID, "bgr_out_host is NULL");
@@ -1815,7 +1896,9 @@ static int to_bgr(melf_ctx* c, const void* frames_host, const FrameBatch& b, uin
     if (int rc = grow(&c->d_stage_in, &c->stage_in_cap, in_bytes)) return rc;
     if (int rc = grow(&c->d_stage_out, &c->stage_out_cap, out_bytes)) return rc;
     HIP_TRY(hipMemcpyAsync(c->d_stage_in, frames_host, in_bytes, hipMemcpyHostToDevice, c->stream));
-    if (b.lay.pix == PIX_YUVP)
+    if (b.lay.pix == PIX_YUV16)
+        launch_y16_to_bgr(c->d_stage_in, b.n, b.H, b.W, b.row_stride, b.frame_stride, b.lay.y16, *b.lay.mx, c->d_stage_out, c->stream);
+    else if (b.lay.pix == PIX_YUVP)
         launch_yuvp_to_bgr(c->d_stage_in, b.n, b.H, b.W, b.row_stride, b.frame_stride, b.lay.yuvp, *b.lay.mx, c->d_stage_out, c->stream);
     else if (pix_yuv(b.lay.pix))
         launch_yuv2bgr(c->d_stage_in, b.lay.pix, b.n, b.H, b.W, b.row_stride, b.frame_stride, b.lay.yuv, *b.lay.mx, c->d_stage_out, c->stream);
@@ -1839,6 +1922,14 @@ extern "C" int melf_yuv_planar_to_bgr(melf_ctx* c, const void* frames_host, cons
 {
     FrameBatch b;
     if (int rc = check_yuv_planar(c, frames_host, f, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return to_bgr(c, frames_host, b, bgr_out_host);
+}
+
+extern "C" int melf_yuv16_to_bgr(melf_ctx* c, const void* frames_host, const melf_yuv16_frames* f, uint8_t* bgr_out_host)
+{
+    FrameBatch b;
+    if (int rc = check_yuv16(c, frames_host, f, &b)) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return to_bgr(c, frames_host, b, bgr_out_host);
 }

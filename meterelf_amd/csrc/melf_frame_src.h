@@ -4,6 +4,7 @@
 #pragma once
 #include "melf_device.h"
 #include "melf_internal.h"
+#include "melf_y16_addr.h"
 
 namespace melf {
 
@@ -71,6 +72,10 @@ __device__ __forceinline__ PxColumn px_column_of(const uint8_t* col, const uint8
 //                       the caller made readable; otherwise nothing is requested and every pixel takes the exact path;
 //       .request(g, Y)  the lane's loads for crop row Y, its g-th: what goes into raw[g];
 //       .unpack(g, r)   raw[g] -> four B G R dwords (PB 4) or the 12 bytes (PB 3), where the prefilter picks them up.
+//   EVEN_QUADS  the lanes' quads must start at an even pixel of the frame (16-bit YUV: see DialYuv16).  The body then asks
+//       quad_shift(wx0), 0 or 1 and wave-uniform, starts the quads that many columns left of the window (window(wx0 - shift, ..) with
+//       npiece = (ws + shift + 3) / 4) and takes the lane's pixel j for window column 4 pc + j - shift.  False everywhere else, where
+//       the body is what it was.
 // th1 = P.th - 1 and rs_u = rstride, both made wave-uniform by the body.
 
 // Packed 3- and 4-byte pixels (PB; 4: base, rows and frames 4-byte aligned, the 4th byte ignored): k_dials (B G R, compile-time
@@ -85,6 +90,7 @@ template <int PB_, bool RT_ORDER, bool FROM_HLS_ = false>
 struct DialPacked {
     static constexpr int PB = PB_;
     static constexpr bool FROM_HLS = FROM_HLS_;
+    static constexpr bool EVEN_QUADS = false;
     struct Args { uint32_t bsel; };
     const DialsSrc& src;
     const uint32_t bsel, csel;   // csel: pixel -> B G R in bytes 0..2
@@ -93,6 +99,7 @@ struct DialPacked {
     __device__ __forceinline__ DialPacked(const DialsSrc& s, const Args& a, const melf_params& P, const uint8_t* frame, int mx, int my)
         : src(s), bsel(a.bsel), csel(a.bsel ? 0x0c000102u : 0x0c020100u), rstride(FROM_HLS ? (size_t)P.tw * 3 : (size_t)s.row_stride),
           origin(FROM_HLS ? frame : frame + (size_t)(s.y0 + my) * s.row_stride + (size_t)(s.x0 + mx) * PB) {}
+    __device__ __forceinline__ int quad_shift(int) const { return 0; }
     __device__ __forceinline__ uint32_t sb() const { return RT_ORDER ? bsel : 0u; }
     __device__ __forceinline__ uint32_t bgr(uint32_t px) const
     {
@@ -143,12 +150,14 @@ template <class Self>
 struct DialFrame {
     static constexpr int PB = 4;
     static constexpr bool FROM_HLS = false;
+    static constexpr bool EVEN_QUADS = false;
     const DialsSrc& src;
     const uint8_t* const frame;
     const size_t rstride;
     const int fx_m, fy_m;   // the match position in the frame
     __device__ __forceinline__ DialFrame(const DialsSrc& s, const uint8_t* frame_, int mx, int my)
         : src(s), frame(frame_), rstride((size_t)s.row_stride), fx_m(s.x0 + mx), fy_m(s.y0 + my) {}
+    __device__ __forceinline__ int quad_shift(int) const { return 0; }
     __device__ __forceinline__ uint32_t sb() const { return 0u; }
     __device__ __forceinline__ uint32_t bgr(uint32_t px) const { return px; }
     __device__ __forceinline__ int column(int X) const { return X; }
@@ -255,6 +264,97 @@ struct DialYuvPlanar : DialFrame<DialYuvPlanar<SUBX, CSTEP>> {
         const uint32_t cshift = SUBX ? (uint32_t)((fx0 >> 1) - cstart) * 8u * CSTEP : 0u;
         return Window{*this, quads, rs_u, fx0, cstart, cshift, (bool)(fx0 & 1), vfirst ? vplane : uplane,
                       vfirst ? 0x07050301u : 0x06040200u, vfirst ? 0x06040200u : 0x07050301u};
+    }
+};
+
+// Planar / semi-planar YUV frames of 16-bit samples (k_y16_needle, melf_process_yuv16*): src the Y plane (strides in bytes), `yuv` the
+// chroma and the reduction (Yuv16Planes), everything 2-byte aligned; CSTEP (1, 2, in samples) is compile-time, sub_y, shift and the
+// order of a pair's samples wave-uniform values.  A sibling of DialYuvPlanar, not a parameter of it: the samples' size changes every
+// load and the window's geometry.  Every sample is reduced to 8 bits where it is unpacked (y16::reduce, or the same as a packed
+// 16-bit shift and minimum on two samples), and leaves as the B G R dword the 8-bit source makes of the reduced samples.
+// The window: four Y samples are 8 bytes, and the body hands over 16 bytes per lane and row.  Two chroma pairs are 8 more (CSTEP 1:
+// a dword of each plane; CSTEP 2: 8 interleaved bytes), and two pairs lie under four pixels exactly when the first is EVEN in the
+// frame; from an odd pixel the four touch three pairs, 20 bytes.  So the quads always start even (EVEN_QUADS): when the window's
+// first column is odd in the frame -- match position + dial geometry + crop origin, wave-uniform -- they start one column to its
+// left and the body places the columns one further right.  Both parities run the same code at the same cost: no wave takes the
+// exact path for its parity.  The shift costs no load: ws = 2 R + 5 is odd, so the ws + 1 columns from the even pixel on fit the
+// (ws + 3) / 4 quads that hold ws.  What it does cost is the exact path for a window that starts at the DIALS crop's first column
+// (wx0 == 0) where that column is odd in the frame, (src.x0 + mx) & 1: its quads would start left of the dials crop's columns, as
+// for a window that leaves them anyway.  For a dial with wx0 == 0 that is every frame of one match parity, about half under jitter;
+// a dial with wx0 >= 1 never pays it.
+// All of a quad's samples are samples of the crop's rows (the four pixels lie inside the crop, the two pairs are theirs), so nothing
+// is read outside the planes, and no load has to be moved left at the crop's right edge: none reaches past the pixels' own pairs.
+template <int CSTEP>
+struct DialYuv16 : DialFrame<DialYuv16<CSTEP>> {
+    using Base = DialFrame<DialYuv16<CSTEP>>;
+    static constexpr bool EVEN_QUADS = true;
+    struct Args { const Yuv16Planes& yuv; const YuvMatrix& ymat; };
+    const YuvMatrix& ymat;
+    const int cp_u, sy_u;
+    const uint32_t sh_u;
+    const uint8_t *const uplane, *const vplane;
+    const bool vfirst;   // CSTEP 2: V before U in a pair (wave-uniform)
+    __device__ __forceinline__ DialYuv16(const DialsSrc& s, const Args& a, const melf_params&, const uint8_t* frame_, int mx, int my)
+        : Base(s, frame_, mx, my), ymat(a.ymat), cp_u(__builtin_amdgcn_readfirstlane(a.yuv.c_pitch)), sy_u(__builtin_amdgcn_readfirstlane(a.yuv.sub_y)),
+          sh_u((uint32_t)__builtin_amdgcn_readfirstlane(a.yuv.shift)), uplane(frame_ + (size_t)a.yuv.u_off), vplane(frame_ + (size_t)a.yuv.v_off),
+          vfirst(a.yuv.v_off < a.yuv.u_off) {}
+    __device__ __forceinline__ int quad_shift(int wx0) const { return __builtin_amdgcn_readfirstlane(y16::quad_shift(this->fx_m, wx0)); }
+    __device__ __forceinline__ uint32_t px(int X, int Y) const
+    {
+        const int fx = this->fx_m + X, fy = this->fy_m + Y;
+        const size_t co = y16::px_c_off(fy, sy_u, (size_t)cp_u, fx, CSTEP);
+        const uint32_t yv = *(const uint16_t*)(this->frame + y16::px_y_off(fy, this->rstride, fx));
+        const uint32_t u = *(const uint16_t*)(uplane + co), v = *(const uint16_t*)(vplane + co);
+        return yuv_bgr((int)y16::reduce(yv, sh_u), yuv_chroma<false>((int)y16::reduce(u, sh_u), (int)y16::reduce(v, sh_u), ymat), ymat);
+    }
+    // two 16-bit samples of a dword, each reduced to 8 bits in its half
+    __device__ __forceinline__ uint32_t reduce2(uint32_t d) const
+    {
+        typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+        const u16x2 s2 = {(unsigned short)sh_u, (unsigned short)sh_u}, top = {255, 255};
+        return __builtin_bit_cast(uint32_t, __builtin_elementwise_min((u16x2)(__builtin_bit_cast(u16x2, d) >> s2), top));
+    }
+    struct Window {
+        const DialYuv16& S;
+        bool quads;
+        int rs_u, fx0;           // the lane's first pixel in the frame (even)
+        const uint8_t* cplane;   // CSTEP 2: the interleaved plane
+        __device__ __forceinline__ u32x4v request(int, int Y) const   // {Y0 Y1, Y2 Y3, chroma, chroma}
+        {
+            const int fy = S.fy_m + Y;
+            uint32_t yd[2];
+            __builtin_memcpy(yd, S.frame + y16::dial_y_off(fy, (size_t)rs_u, fx0), y16::DIAL_Y_BYTES);
+            const size_t co = y16::dial_c_off(fy, S.sy_u, (size_t)S.cp_u, fx0, CSTEP);
+            if constexpr (CSTEP == 1) {
+                uint32_t ud, vd;
+                __builtin_memcpy(&ud, S.uplane + co, 4);
+                __builtin_memcpy(&vd, S.vplane + co, 4);
+                return u32x4v{yd[0], yd[1], ud, vd};
+            } else {
+                uint32_t cd[2];
+                __builtin_memcpy(cd, cplane + co, 8);
+                return u32x4v{yd[0], yd[1], cd[0], cd[1]};
+            }
+        }
+        __device__ __forceinline__ u32x4v unpack(int, const u32x4v r) const
+        {
+            const uint32_t y01 = S.reduce2(r.x), y23 = S.reduce2(r.y), ca = S.reduce2(r.z), cb = S.reduce2(r.w);
+            uint32_t u0, v0, u1, v1;   // the chroma of pixels 0, 1 and of pixels 2, 3
+            if constexpr (CSTEP == 1) {   // ca: U of the two pairs, cb: V
+                u0 = ca & 255u; u1 = ca >> 16; v0 = cb & 255u; v1 = cb >> 16;
+            } else {                      // ca: the first pair, cb: the second
+                const uint32_t f0 = ca & 255u, s0 = ca >> 16, f1 = cb & 255u, s1 = cb >> 16;
+                u0 = S.vfirst ? s0 : f0; v0 = S.vfirst ? f0 : s0; u1 = S.vfirst ? s1 : f1; v1 = S.vfirst ? f1 : s1;
+            }
+            const YuvChroma c0 = yuv_chroma<false>((int)u0, (int)v0, S.ymat), c1 = yuv_chroma<false>((int)u1, (int)v1, S.ymat);
+            return u32x4v{yuv_bgr((int)(y01 & 255u), c0, S.ymat), yuv_bgr((int)(y01 >> 16), c0, S.ymat), yuv_bgr((int)(y23 & 255u), c1, S.ymat),
+                          yuv_bgr((int)(y23 >> 16), c1, S.ymat)};
+        }
+    };
+    // wx0: the quads' first column (the window's, less quad_shift), npiece: their count
+    __device__ __forceinline__ Window window(int wx0, int npiece, int pc, int, int rs_u, int tw) const
+    {
+        return Window{*this, y16::quads_inside(wx0, npiece, tw), rs_u, y16::lane_fx0(this->fx_m, wx0, npiece, pc), vfirst ? vplane : uplane};
     }
 };
 

@@ -97,6 +97,20 @@ struct YuvPlanarPlanes {
     int sub_x, sub_y;      // log2 of the chroma subsampling, 0 or 1 each
     int c_step;            // bytes from one sample of a chroma plane to the next in its row: 1 planar, 2 semi-planar
 };
+// Planar and semi-planar YUV frames of 16-bit little-endian samples, chroma subsampled horizontally (melf_process_yuv16*): the
+// launch's pix.  The Y plane is described by base, frame_stride and row_stride of MatchSrc / DialsSrc in BYTES (all 2-byte aligned),
+// x0 and cols count pixels (samples); the chroma by Yuv16Planes: U of pixel (x, y) is the sample at byte frame + u_off + (y >> sub_y)
+// * c_pitch + (x >> 1) * c_step * 2, V the same from v_off.  A sample s is read as min(s >> shift, 255) (melf_y16_addr.h: reduce),
+// and from there on the arithmetic is that of PIX_YUVP.  A by-value kernel argument of its own; the hot kernels are instantiated
+// per c_step and take sub_y, shift and the order of a pair's samples as runtime, wave-uniform values.
+constexpr int PIX_YUV16 = 48;
+struct Yuv16Planes {
+    int64_t u_off, v_off;  // bytes from a frame's first byte to its first U / V sample
+    int c_pitch;           // bytes between chroma rows
+    int sub_y;             // log2 of the vertical chroma subsampling, 0 or 1
+    int c_step;            // samples from one sample of a chroma plane to the next in its row: 1 planar, 2 semi-planar
+    int shift;             // low bits dropped from a sample, 0 .. 8
+};
 
 // How the frames of one launch lie in memory, beside the base, the strides and the rectangle of MatchSrc / DialsSrc: the pixel
 // layout and what goes with it.  Host side only: the launchers hand the kernels the members by value.  Made by the makers below
@@ -105,9 +119,10 @@ struct FrameLayout {
     int pix;
     YuvPlanes yuv;         // pix_yuv(pix): the chroma planes
     PlanarPlanes planes;   // PIX_PLANAR: where the three planes start
-    const YuvMatrix* mx;   // pix_yuv(pix), pix_p422(pix), PIX_YUVP: the frames' colour conversion, never NULL there
+    const YuvMatrix* mx;   // pix_yuv(pix), pix_p422(pix), PIX_YUVP, PIX_YUV16: the frames' colour conversion, never NULL there
     size_t extent;         // bytes a kernel may read of the LAST frame, from its first byte (the others: frame_stride)
     YuvPlanarPlanes yuvp;  // PIX_YUVP: the chroma planes and their subsampling (mx: the conversion, as above)
+    Yuv16Planes y16;       // PIX_YUV16: the chroma planes of 16-bit samples and the reduction (mx: the conversion, as above)
 
     static FrameLayout packed(int pix /* MELF_PIX_* */, size_t extent) { return FrameLayout{pix, {}, {}, nullptr, extent}; }
     static FrameLayout yuv420(int pix /* PIX_NV12, PIX_I420 */, const YuvPlanes& yp, const YuvMatrix& mx, size_t extent)
@@ -121,6 +136,10 @@ struct FrameLayout {
     static FrameLayout yuv_planar(const YuvPlanarPlanes& yp, const YuvMatrix& mx, size_t extent)
     {
         return FrameLayout{PIX_YUVP, {}, {}, &mx, extent, yp};
+    }
+    static FrameLayout yuv16(const Yuv16Planes& yp, const YuvMatrix& mx, size_t extent)
+    {
+        return FrameLayout{PIX_YUV16, {}, {}, &mx, extent, {}, yp};
     }
     static FrameLayout planar(const PlanarPlanes& pl, size_t extent) { return FrameLayout{PIX_PLANAR, {}, pl, nullptr, extent}; }
     static FrameLayout plane(size_t extent) { return FrameLayout{PIX_PLANE, {}, {}, nullptr, extent}; }
@@ -276,6 +295,10 @@ void launch_yuv2bgr(const uint8_t* d_src, int pix, int n, int H, int W, int y_pi
 // the same for planar / semi-planar YUV of any subsampling (melf_yuv_planar_to_bgr): the Y plane at d_src (y_pitch, frame_stride)
 void launch_yuvp_to_bgr(const uint8_t* d_src, int n, int H, int W, int y_pitch, size_t frame_stride, const YuvPlanarPlanes& yp,
                         const YuvMatrix& mx, uint8_t* d_dst, hipStream_t stream);
+
+// the same for 16-bit planar / semi-planar YUV (melf_yuv16_to_bgr): y_pitch and frame_stride in bytes
+void launch_y16_to_bgr(const uint8_t* d_src, int n, int H, int W, int y_pitch, size_t frame_stride, const Yuv16Planes& yp,
+                       const YuvMatrix& mx, uint8_t* d_dst, hipStream_t stream);
 
 // the same for packed YUV 4:2:2 (melf_yuv422_to_bgr): n frames at d_src (row_pitch, frame_stride), pix PIX_YUYV / _UYVY / _YVYU
 void launch_p422_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int row_pitch, size_t frame_stride, const YuvMatrix& mx,

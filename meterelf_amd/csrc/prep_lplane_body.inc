@@ -23,6 +23,12 @@
 //       aligned dwords and v_alignbit, as for PX 23), CSTEP 2 twice as many interleaved bytes from the lower of the two offsets, one
 //       runtime v_perm_b32 per dword putting U before V.  sub_y is the scalar shift of the chroma row.  No window may start before
 //       the caller's base nor end behind the buffer, or the lane takes byte loads of the crop's own samples.
+//   With MELF_Y16_BODY defined instead (k_y16_lplane): PX 25 = planar / semi-planar YUV frames of 16-bit samples
+//       (melf_process_yuv16*), the chroma in `yuv` (Yuv16Planes), everything 2-byte aligned; CSTEP (1, 2, in samples) is compile-time.
+//       The even-pixel window is 34 Y samples (68 bytes) and the 17 chroma pairs under them (CSTEP 1: 34 bytes of each plane, CSTEP 2:
+//       68 interleaved bytes from the lower of the two offsets): aligned dwords and v_alignbit at the 2-byte phase (load_window16,
+//       k_match_mfma.hip), two samples a dword reduced to 8 bits by a packed 16-bit shift and minimum and packed four to a dword --
+//       from there on the arm is PX 24's.  Offsets, window lengths, rows_safe and the lane's own test: melf_y16_addr.h.
     constexpr int PB = PX == 4 ? 4 : 3;         // bytes per pixel of the frame reads
     constexpr int WIN = PX == 4 ? 128 : 100;    // bytes a lane's 32-pixel load window spans
     __shared__ __attribute__((aligned(16))) uint32_t tile[8 * 2 * 32 * 4];  // [kb][h][n][16 B], one chunk of 8 blocks
@@ -69,6 +75,16 @@
     const bool rows_safe = (yp_bm == 0 || (yp_first + yp_yrow + (size_t)yp_x0 >= 3 && yp_first + yp_c0 + yp_crow + (size_t)((yp_x0 >> SUBX) * CSTEP) >= 3)) &&
                            yp_last + yp_yrow + (size_t)yp_xlast + 40 <= src.readable &&
                            yp_last + (CSTEP == 2 ? yp_c0 : yp_c1) + yp_crow + (size_t)((yp_xlast >> SUBX) * CSTEP) + CWIN <= src.readable;
+#elif defined(MELF_Y16_BODY)
+    (void)PB; (void)WIN;
+    // (the same for the windows of a lane of these frames, at the buffer's first bytes as well as at its last: y16::prep_rows_safe)
+    constexpr int CB = 34 * CSTEP;                   // bytes of a chroma window
+    const int xodd = src.x0 & 1;
+    const bool yp_swap = yuv.v_off < yuv.u_off;      // CSTEP 2: V before U in a pair
+    const uint32_t y16_shift = (uint32_t)yuv.shift;
+    const y16::PrepRow prow16 = y16::prep_row((size_t)src.base, src.frame_stride, (size_t)src.row_stride, src.x0, src.y0, y, grp, nframes, nkb,
+                                              yuv.u_off, yuv.v_off, (size_t)yuv.c_pitch, yuv.sub_y);
+    const bool rows_safe = y16::prep_rows_safe(prow16, CSTEP, src.readable);
 #elif defined(MELF_PLANAR_BODY)
     (void)PB; (void)WIN;
     // (the same for the three 36-byte windows of a planar lane, and for their first dword: with a base that is not 4-byte aligned
@@ -261,6 +277,66 @@
                         const int ci = ((src.x0 + xbeg + k) >> SUBX) * CSTEP;
                         const YuvChroma c = yuv_chroma(pu[ci], pv[ci], mx);
                         const int L = yuv_lightness(py[k], yuv_cmax(c), yuv_cmin(c), mx);
+                        w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
+                    }
+                }
+            } else
+#elif defined(MELF_Y16_BODY)
+            if (PX == 25) {
+                const int xs = (src.x0 + xbeg) & ~1;   // the window's first pixel (even)
+                const size_t fo = (size_t)f * src.frame_stride;
+                const size_t yo = y16::prep_y_off(prow16, fo, xs);
+                const size_t uo = y16::prep_c_off(prow16, fo, CSTEP == 2 ? prow16.c0 : (size_t)yuv.u_off, xs, CSTEP);   // CSTEP 2: the interleaved window
+                const size_t vo = y16::prep_c_off(prow16, fo, (size_t)yuv.v_off, xs, CSTEP);                            // (CSTEP 1 only)
+                const uint32_t my = (prow16.bm + (uint32_t)yo) & 3u, mu = (prow16.bm + (uint32_t)uo) & 3u, mv = (prow16.bm + (uint32_t)vo) & 3u;
+                // the windows may reach past the crop and the row (never used: masked) but must stay inside the caller's buffer, at its
+                // first bytes as well as at its last
+                if (rows_safe || (y16::prep_window_ok(yo, my, y16::PREP_Y_BYTES, src.readable) && y16::prep_window_ok(uo, mu, CB, src.readable) &&
+                                  (CSTEP == 2 || y16::prep_window_ok(vo, mv, CB, src.readable)))) {
+                    uint32_t ya[9], ua[5], va[5];   // Y, U, V of the window reduced to 8 bits, a sample per byte
+                    load_window16<34>(src.base, yo, my, y16_shift, ya);
+                    if constexpr (CSTEP == 2) {
+                        uint32_t ca[9];             // first, second, first, second .. of the pairs, a sample per byte
+                        load_window16<34>(src.base, uo, mu, y16_shift, ca);
+                        // pairs -> U0 U1 V0 V1 per dword, then the U halves and the V halves of two dwords together
+                        const uint32_t sel = yp_swap ? 0x02000301u : 0x03010200u;
+#pragma unroll
+                        for (int i = 0; i < 9; ++i) ca[i] = __builtin_amdgcn_perm(0u, ca[i], sel);
+#pragma unroll
+                        for (int i = 0; i < 5; ++i) {
+                            const uint32_t lo = ca[2 * i], hi = 2 * i + 1 < 9 ? ca[2 * i + 1] : 0u;
+                            ua[i] = __builtin_amdgcn_perm(hi, lo, 0x05040100u);
+                            va[i] = __builtin_amdgcn_perm(hi, lo, 0x07060302u);
+                        }
+                    } else {
+                        load_window16<17>(src.base, uo, mu, y16_shift, ua);
+                        load_window16<17>(src.base, vo, mv, y16_shift, va);
+                    }
+                    uint32_t wl[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // L' of the window's 34 pixels
+#pragma unroll
+                    for (int j = 0; j < 17; ++j) {
+                        const int U = (int)((ua[j >> 2] >> ((j & 3) * 8)) & 255u), V = (int)((va[j >> 2] >> ((j & 3) * 8)) & 255u);
+                        const YuvChroma c = yuv_chroma(U, V, mx);
+                        const int cmax = yuv_cmax(c), cmin = yuv_cmin(c);
+#pragma unroll
+                        for (int q2 = 0; q2 < 2; ++q2) {
+                            const int k = 2 * j + q2;
+                            const int L = yuv_lightness((int)((ya[k >> 2] >> ((k & 3) * 8)) & 255u), cmax, cmin, mx);
+                            wl[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
+                        }
+                    }
+                    // the lane's 32 pixels start at byte xodd of the window
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) w[i] = __builtin_amdgcn_alignbit(wl[i + 1], wl[i], (uint32_t)xodd * 8u);
+                } else {  // first / last bytes of the frame buffer: 2-byte loads, the crop's own samples only
+                    const uint8_t* pf = src.base + fo;
+                    for (int k = 0; k < npx; ++k) {
+                        const int fx = src.x0 + xbeg + k;
+                        const size_t co = y16::px_c_off(src.y0 + y, yuv.sub_y, (size_t)yuv.c_pitch, fx, CSTEP);
+                        const YuvChroma c = yuv_chroma((int)y16::reduce(*(const uint16_t*)(pf + (size_t)yuv.u_off + co), y16_shift),
+                                                       (int)y16::reduce(*(const uint16_t*)(pf + (size_t)yuv.v_off + co), y16_shift), mx);
+                        const int L = yuv_lightness((int)y16::reduce(*(const uint16_t*)(pf + y16::px_y_off(src.y0 + y, (size_t)src.row_stride, fx)), y16_shift),
+                                                    yuv_cmax(c), yuv_cmin(c), mx);
                         w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
                     }
                 }

@@ -1,5 +1,5 @@
-"""What the frame-format rate tools share (pixel_format_rate, yuv_rate, yuv422_rate, yuv_matrix_rate, planar_rate, yuv_planar_rate):
-the arguments, the fixture and the synthetic frames, the encoding of those frames as YUV and the header's integer conversion back,
+"""What the frame-format rate tools share (pixel_format_rate, yuv_rate, yuv422_rate, yuv_matrix_rate, planar_rate, yuv_planar_rate,
+yuv16_rate): the arguments, the fixture and the synthetic frames, the encoding of those frames as YUV and the header's integer conversion back,
 the layout writers, and the measuring method.  A tool keeps its docstring, its rows, its own columns and its closing lines.
 
 The method is bench.py's (timed_steps): frames resident in HBM, --nbuf distinct batches in rotation (more than the Infinity Cache

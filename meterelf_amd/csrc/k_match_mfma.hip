@@ -36,6 +36,7 @@
 
 #include "melf_internal.h"
 #include "melf_y16_addr.h"
+#include "melf_prep_addr.h"
 
 namespace melf {
 
@@ -864,6 +865,13 @@ void launch_match_prep(const MatchSrc& src, const FrameLayout& lay, int n, int g
                        int8_t* d_lg, uint16_t* d_r, hipStream_t stream, int pairs)
 {
     const int pix = lay.pix;
+    // the source as the two arms without a test for their windows' first dword get it (melf_prep_addr.h: prep_window_readable), named
+    // where the kernel of that arm is picked
+    auto windows = [&](prep::Arm arm) {
+        MatchSrc s = src;
+        s.readable = prep::prep_window_readable(arm, (size_t)src.base & 3, src.x0, src.y0, src.readable);
+        return s;
+    };
     dim3 grid(rows_pad, groups), block(256);
     const size_t pre_bytes = (size_t)32 * (nkb * 32 + 8) * sizeof(int16_t);
     int dev = 0;
@@ -898,11 +906,11 @@ void launch_match_prep(const MatchSrc& src, const FrameLayout& lay, int n, int g
     }
     else if (pix == PIX_PLANAR) hipLaunchKernelGGL(k_planar_lplane, grid, block, pre_bytes, stream, src, lay.planes, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else if (pix_p422(pix)) hipLaunchKernelGGL(k_p422_lplane, grid, block, pre_bytes, stream, src, p422_sel(pix), *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
-    else if (pix == PIX_NV12) hipLaunchKernelGGL((k_lplane_yuv<false>), grid, block, pre_bytes, stream, src, lay.yuv, *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
-    else if (pix == PIX_I420) hipLaunchKernelGGL((k_lplane_yuv<true>), grid, block, pre_bytes, stream, src, lay.yuv, *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    else if (pix == PIX_NV12) hipLaunchKernelGGL((k_lplane_yuv<false>), grid, block, pre_bytes, stream, windows(prep::ARM_YUV420), lay.yuv, *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    else if (pix == PIX_I420) hipLaunchKernelGGL((k_lplane_yuv<true>), grid, block, pre_bytes, stream, windows(prep::ARM_YUV420), lay.yuv, *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else if (pix == PIX_PLANE) hipLaunchKernelGGL((k_prep_lplane<false>), grid, block, pre_bytes, stream, src, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else if (pix_bytes(pix) == 4) hipLaunchKernelGGL(k_lplane_px4, grid, block, pre_bytes, stream, src, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
-    else hipLaunchKernelGGL((k_prep_lplane<true>), grid, block, pre_bytes, stream, src, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    else hipLaunchKernelGGL((k_prep_lplane<true>), grid, block, pre_bytes, stream, windows(prep::ARM_PX3), n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
 }
 
 void launch_mfma_prep(const MatchSrc& src, const FrameLayout& lay, int n, const MfmaPlan& p, int th, int tw, int8_t* d_lg,

@@ -10,6 +10,21 @@ namespace melf {
 
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 
+// Host seams.  tests/frame_src_bounds_main.cpp compiles this header as plain C++ and runs the sources on the CPU against buffers of
+// exact extent; two constructs have no host form and are the device's own text only in the device compile (__HIP_DEVICE_COMPILE__):
+// the scalar-register constraint in load_px3_row, and the 16-byte load of a 4-byte-aligned address (load16), a plain dereference
+// on the device, bytes copied on the host (x86 faults on a 16-byte vector load that is not 16-byte aligned).
+__device__ __forceinline__ u32x4v load16(const void* p)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return *(const u32x4v*)p;
+#else
+    u32x4v v;
+    __builtin_memcpy(&v, p, 16);
+    return v;
+#endif
+}
+
 // ---- packed 3-byte pixels, one at a time ----------------------------------------------------------------------------------
 // Three bytes of a packed 3-channel pixel with ONE (unaligned) dword load instead of three byte loads: the
 // dword starts one byte early (so it never runs past the buffer's end) except at the buffer's very first pixel.
@@ -39,7 +54,9 @@ __device__ __forceinline__ PxColumn px_column(const uint8_t* col, const uint8_t*
 }
 __device__ __forceinline__ uint32_t load_px3_row(const PxColumn& c, size_t row_off)
 {
+#if defined(__HIP_DEVICE_COMPILE__)
     asm("" : "+s"(row_off));  // the offset stays a scalar product: otherwise the compiler folds it into one 64-bit vector multiply-add per row
+#endif
     uint32_t v;
     __builtin_memcpy(&v, c.first + row_off, 4);
     return v >> c.shift;
@@ -118,10 +135,10 @@ struct DialPacked {
         {
             const uint8_t* const a = lane0 + (size_t)Y * (size_t)rs_u;
             if constexpr (PB == 4) {
-                return *(const u32x4v*)a;
+                return load16(a);
             } else {
                 mshift |= ((uint32_t)(uintptr_t)a & 3u) << (2 * g);
-                return *(const u32x4v*)((uintptr_t)a & ~(uintptr_t)3);
+                return load16((const void*)((uintptr_t)a & ~(uintptr_t)3));
             }
         }
         // 3-byte pixels: the lane's 12 bytes  B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3
@@ -140,7 +157,7 @@ struct DialPacked {
         const uint8_t* const buf_end = src.base + src.readable;   // (not frames x stride: the last frame of a padded-stride buffer may end earlier)
         const bool quads = !FROM_HLS && ((uintptr_t)src.base & 3) == 0 && wx0 >= 0 && wx0 + 4 * npiece <= tw &&
                            origin + (size_t)th1 * rstride + (size_t)(wx0 + 4 * npiece) * PB + (PB == 4 ? 0 : 4) <= buf_end;
-        return Window{quads, origin + (size_t)(wx0 + 4 * min(pc, npiece - 1)) * PB, rs_u, 0u};
+        return Window{quads, origin + (ptrdiff_t)(wx0 + 4 * min(pc, npiece - 1)) * PB, rs_u, 0u};   // (signed: wx0 may be -1; unused then)
     }
 };
 

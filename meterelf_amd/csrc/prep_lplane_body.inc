@@ -29,8 +29,10 @@
 //       68 interleaved bytes from the lower of the two offsets): aligned dwords and v_alignbit at the 2-byte phase (load_window16,
 //       k_match_mfma.hip), two samples a dword reduced to 8 bits by a packed 16-bit shift and minimum and packed four to a dword --
 //       from there on the arm is PX 24's.  Offsets, window lengths, rows_safe and the lane's own test: melf_y16_addr.h.
-    constexpr int PB = PX == 4 ? 4 : 3;         // bytes per pixel of the frame reads
-    constexpr int WIN = PX == 4 ? 128 : 100;    // bytes a lane's 32-pixel load window spans
+// The 8-bit arms (PX 3, 4, 20 .. 24) compute their windows' offsets and lengths, rows_safe and the lane's own test with the functions
+// of melf_prep_addr.h, as PX 25 does with melf_y16_addr.h: tests/prep_bounds_main.cpp sweeps the same functions on the CPU.
+    constexpr int PB = prep::packed_pb(PX);     // bytes per pixel of the frame reads
+    constexpr int WIN = prep::packed_win(PX);   // bytes a lane's 32-pixel load window spans
     __shared__ __attribute__((aligned(16))) uint32_t tile[8 * 2 * 32 * 4];  // [kb][h][n][16 B], one chunk of 8 blocks
     extern __shared__ int16_t pre_dyn[];                                    // [32][nkb * 32 + 8]: inclusive prefix of L' per frame (mod 2^16)
     const int pstride = nkb * 32 + 8;
@@ -45,36 +47,32 @@
     (void)PB; (void)WIN;
     // (the same for the three windows of a YUV lane: 40 bytes from the Y sample and from the chroma samples of its even pixel)
     const int xodd = src.x0 & 1;
-    const size_t yuv_last = (size_t)min(grp * 32 + 31, nframes - 1) * src.frame_stride;
-    const size_t yuv_crow = (size_t)((src.y0 + y) >> 1) * (size_t)yuv.c_pitch;
-    const int yuv_xlast = (src.x0 & ~1) + 32 * (nkb - 1);
-    const bool rows_safe = yuv_last + (size_t)(src.y0 + y) * src.row_stride + (size_t)yuv_xlast + 40 <= src.readable &&
-                           yuv_last + (size_t)max(yuv.u_off, yuv.v_off) + yuv_crow + (size_t)(PX == 20 ? yuv_xlast : yuv_xlast >> 1) + 40 <= src.readable;
+    const size_t yuv_last = (size_t)prep::last_frame(grp, nframes) * src.frame_stride;
+    const size_t yuv_crow = prep::yuv420_crow(src.y0 + y, yuv.c_pitch);
+    const int yuv_xlast = prep::yuv420_xlast(src.x0, nkb);
+    const bool rows_safe = prep::yuv420_rows_safe(yuv_last, src.y0 + y, src.row_stride, yuv_xlast, yuv.u_off, yuv.v_off, yuv_crow, PX == 20, src.readable);
 #elif defined(MELF_P422_BODY)
     (void)PB; (void)WIN;
     // (the same for the 68-byte window of a 4:2:2 lane: 17 macropixels from the one of its even pixel)
     const int xodd = src.x0 & 1;
-    const bool rows_safe = (size_t)min(grp * 32 + 31, nframes - 1) * src.frame_stride + (size_t)(src.y0 + y) * src.row_stride +
-                           (size_t)((src.x0 & ~1) + 32 * (nkb - 1)) * 2 + 68 <= src.readable;
+    const bool rows_safe = prep::p422_rows_safe(grp, nframes, src.frame_stride, src.y0 + y, src.row_stride, src.x0, nkb, src.readable);
 #elif defined(MELF_YUVP_BODY)
     (void)PB; (void)WIN;
     // (the same for the windows of a lane of these frames: 40 bytes from the Y sample of its even pixel, CB + 3 bytes rounded up to
     // dwords from its first chroma sample in each plane (CSTEP 1) or in the interleaved plane (CSTEP 2) -- and for their first dword:
     // with a base that is not 4-byte aligned the aligned window of the buffer's very first samples would start before it)
-    constexpr int NC = 34 >> SUBX;                   // chroma samples under a window
-    constexpr int CB = NC * CSTEP;                   // bytes of a chroma window
-    constexpr int CWIN = (CB + 6) / 4 * 4;           // bytes its aligned dwords span
+    constexpr int NC = prep::yuvp_nc(SUBX);          // chroma samples under a window
+    constexpr int CB = prep::yuvp_cb(SUBX, CSTEP);   // bytes of a chroma window
+    constexpr int CWIN = prep::yuvp_cwin(SUBX, CSTEP);   // bytes its aligned dwords span
     const int xodd = src.x0 & 1;
     const uint32_t yp_bm = (uint32_t)((size_t)src.base & 3);
     const bool yp_swap = yuv.v_off < yuv.u_off;      // CSTEP 2: V before U in a pair (NV21, NV61, NV42)
     const size_t yp_c0 = (size_t)min(yuv.u_off, yuv.v_off), yp_c1 = (size_t)max(yuv.u_off, yuv.v_off);
-    const size_t yp_first = (size_t)grp * 32 * src.frame_stride, yp_last = (size_t)min(grp * 32 + 31, nframes - 1) * src.frame_stride;
+    const size_t yp_first = (size_t)grp * 32 * src.frame_stride, yp_last = (size_t)prep::last_frame(grp, nframes) * src.frame_stride;
     const size_t yp_yrow = (size_t)(src.y0 + y) * src.row_stride;
     const size_t yp_crow = (size_t)((src.y0 + y) >> yuv.sub_y) * (size_t)yuv.c_pitch;
     const int yp_x0 = src.x0 & ~1, yp_xlast = yp_x0 + 32 * (nkb - 1);
-    const bool rows_safe = (yp_bm == 0 || (yp_first + yp_yrow + (size_t)yp_x0 >= 3 && yp_first + yp_c0 + yp_crow + (size_t)((yp_x0 >> SUBX) * CSTEP) >= 3)) &&
-                           yp_last + yp_yrow + (size_t)yp_xlast + 40 <= src.readable &&
-                           yp_last + (CSTEP == 2 ? yp_c0 : yp_c1) + yp_crow + (size_t)((yp_xlast >> SUBX) * CSTEP) + CWIN <= src.readable;
+    const bool rows_safe = prep::yuvp_rows_safe(yp_bm, yp_first, yp_last, yp_yrow, yp_crow, yp_c0, yp_c1, yp_x0, yp_xlast, SUBX, CSTEP, CWIN, src.readable);
 #elif defined(MELF_Y16_BODY)
     (void)PB; (void)WIN;
     // (the same for the windows of a lane of these frames, at the buffer's first bytes as well as at its last: y16::prep_rows_safe)
@@ -90,13 +88,11 @@
     // (the same for the three 36-byte windows of a planar lane, and for their first dword: with a base that is not 4-byte aligned
     // the aligned window of the very first samples of the buffer would start before it)
     const uint32_t pl_bm = (uint32_t)((size_t)src.base & 3);
-    const size_t pl_row = (size_t)(src.y0 + y) * src.row_stride + (size_t)src.x0;
+    const size_t pl_row = prep::planar_row(src.y0 + y, src.row_stride, src.x0);
     const size_t pl_lo = (size_t)min(min(planes.b_off, planes.g_off), planes.r_off), pl_hi = (size_t)max(max(planes.b_off, planes.g_off), planes.r_off);
-    const bool rows_safe = (pl_bm == 0 || (size_t)grp * 32 * src.frame_stride + pl_lo + pl_row >= 3) &&
-                           (size_t)min(grp * 32 + 31, nframes - 1) * src.frame_stride + pl_hi + pl_row + (size_t)(32 * (nkb - 1)) + 36 <= src.readable;
+    const bool rows_safe = prep::planar_rows_safe(pl_bm, grp, nframes, src.frame_stride, pl_lo, pl_hi, pl_row, nkb, src.readable);
 #else
-    const bool rows_safe = (size_t)min(grp * 32 + 31, nframes - 1) * src.frame_stride + (size_t)(src.y0 + y) * src.row_stride +
-                           (size_t)(src.x0 + 32 * (nkb - 1)) * PB + WIN <= src.readable;
+    const bool rows_safe = prep::packed_rows_safe(grp, nframes, src.frame_stride, src.y0 + y, src.row_stride, src.x0, nkb, PB, WIN, src.readable);
 #endif
     u32x4m* out = (u32x4m*)(Lg + ((size_t)grp * rows_pad + y) * (size_t)nkb * 1024);
     for (int kc = 0; kc < nkb; kc += 8) {
@@ -112,12 +108,12 @@
                 constexpr bool NV12 = PX == 20;
                 const int xs = (src.x0 + xbeg) & ~1;   // the window's first pixel (even)
                 const size_t fo = (size_t)f * src.frame_stride;
-                const size_t yo = fo + (size_t)(src.y0 + y) * src.row_stride + (size_t)xs;
-                const size_t uo = fo + (size_t)yuv.u_off + yuv_crow + (size_t)(NV12 ? xs : xs >> 1);
-                const size_t vo = fo + (size_t)yuv.v_off + yuv_crow + (size_t)(xs >> 1);   // (I420 only)
+                const size_t yo = prep::yuv420_y_off(fo, src.y0 + y, src.row_stride, xs);
+                const size_t uo = prep::yuv420_c_off(fo, yuv.u_off, yuv_crow, xs, NV12);
+                const size_t vo = prep::yuv420_c_off(fo, yuv.v_off, yuv_crow, xs, false);   // (I420 only)
                 // 10 aligned dwords cover 34 bytes (+ 3 of misalignment), 6 the 17 bytes of an I420 chroma row's share; the windows
                 // may reach past the crop (never used: masked) but must stay inside the caller's buffer
-                if (rows_safe || (yo + 40 <= src.readable && uo + (NV12 ? 40 : 24) <= src.readable && (NV12 || vo + 24 <= src.readable))) {
+                if (rows_safe || prep::yuv420_lane_ok(yo, uo, vo, NV12, src.readable)) {
                     uint32_t ya[9], ua[9], va[5];
                     {
                         const uint8_t* p = src.base + yo;
@@ -191,9 +187,9 @@
 #elif defined(MELF_P422_BODY)
             if (PX == 22) {
                 const int xs = (src.x0 + xbeg) & ~1;   // the window's first pixel (even)
-                const size_t o = (size_t)xs * 2;
+                const size_t o = prep::p422_x_off(xs);
                 // the window may reach past the crop and the row (never used: masked) but must stay inside the caller's buffer
-                if (rows_safe || (size_t)f * src.frame_stride + (size_t)(src.y0 + y) * src.row_stride + o + 68 <= src.readable) {
+                if (rows_safe || prep::p422_lane_ok(f, src.frame_stride, src.y0 + y, src.row_stride, o, src.readable)) {
                     const u32x4a4* q = (const u32x4a4*)(prow + o);
                     u32x4a4 d[4];
 #pragma unroll
@@ -226,14 +222,13 @@
                 const int xs = (src.x0 + xbeg) & ~1;   // the window's first pixel (even)
                 const size_t fo = (size_t)f * src.frame_stride;
                 const size_t yo = fo + yp_yrow + (size_t)xs;
-                const size_t cx = (size_t)((xs >> SUBX) * CSTEP);
+                const size_t cx = prep::yuvp_cx(xs, SUBX, CSTEP);
                 const size_t uo = fo + (CSTEP == 2 ? yp_c0 : (size_t)yuv.u_off) + yp_crow + cx;   // CSTEP 2: the interleaved window
                 const size_t vo = fo + (size_t)yuv.v_off + yp_crow + cx;                          // (CSTEP 1 only)
                 const uint32_t my = (yp_bm + (uint32_t)yo) & 3u, mu = (yp_bm + (uint32_t)uo) & 3u, mv = (yp_bm + (uint32_t)vo) & 3u;
                 // the windows may reach past the crop and the row (never used: masked) but must stay inside the caller's buffer, at its
                 // first bytes as well as at its last
-                if (rows_safe || (yo >= my && uo >= mu && yo - my + 40 <= src.readable && uo - mu + CWIN <= src.readable &&
-                                  (CSTEP == 2 || (vo >= mv && vo - mv + CWIN <= src.readable)))) {
+                if (rows_safe || prep::yuvp_lane_ok(yo, my, uo, mu, vo, mv, CSTEP, CWIN, src.readable)) {
                     uint32_t ya[9], ua[(NC + 3) / 4], va[(NC + 3) / 4];   // Y, U, V of the window, a sample per byte
                     load_window<34>(src.base, yo, my, ya);
                     if constexpr (CSTEP == 2) {
@@ -344,13 +339,12 @@
 #elif defined(MELF_PLANAR_BODY)
             if (PX == 23) {
                 // the lane's first sample in each plane, from the caller's base, and its byte phase there
-                const size_t o = (size_t)f * src.frame_stride + (size_t)(src.y0 + y) * src.row_stride + (size_t)(src.x0 + xbeg);
+                const size_t o = prep::planar_lane_off(f, src.frame_stride, src.y0 + y, src.row_stride, src.x0 + xbeg);
                 const size_t ob = o + (size_t)planes.b_off, og = o + (size_t)planes.g_off, orr = o + (size_t)planes.r_off;
                 const uint32_t mb = (pl_bm + (uint32_t)ob) & 3u, mg = (pl_bm + (uint32_t)og) & 3u, mr = (pl_bm + (uint32_t)orr) & 3u;
                 // nine aligned dwords per plane cover its 32 bytes at any phase; the windows may reach past the crop and the row (never
                 // used: masked) but must stay inside the caller's buffer, at its first bytes as well as at its last
-                if (rows_safe || (ob >= mb && og >= mg && orr >= mr && ob - mb + 36 <= src.readable && og - mg + 36 <= src.readable &&
-                                  orr - mr + 36 <= src.readable)) {
+                if (rows_safe || prep::planar_lane_ok(ob, mb, og, mg, orr, mr, src.readable)) {
                     const uint32_t* qb = (const uint32_t*)(src.base + (ob - mb));
                     const uint32_t* qg = (const uint32_t*)(src.base + (og - mg));
                     const uint32_t* qr = (const uint32_t*)(src.base + (orr - mr));
@@ -380,12 +374,12 @@
             } else
 #endif
             if (PX == 3) {
-                const size_t o = (size_t)(src.x0 + xbeg) * 3;
+                const size_t o = prep::packed_x_off(src.x0 + xbeg, 3);
                 const uint8_t* p = prow + o;
                 const int mis = (int)((size_t)p & 3);
                 // 25 aligned dwords cover the 96 bytes of 32 pixels at any byte alignment; the window may
                 // reach past the crop (never used: masked) but must stay inside the caller's buffer
-                if (rows_safe || (size_t)f * src.frame_stride + (size_t)(src.y0 + y) * src.row_stride + o + 100 <= src.readable) {
+                if (rows_safe || prep::packed_lane_ok(f, src.frame_stride, src.y0 + y, src.row_stride, o, 100, src.readable)) {
                     const uint32_t* q = (const uint32_t*)(p - mis);
                     uint32_t d[25];
 #pragma unroll
@@ -410,10 +404,10 @@
                     }
                 }
             } else if (PX == 4) {
-                const size_t o = (size_t)(src.x0 + xbeg) * 4;
+                const size_t o = prep::packed_x_off(src.x0 + xbeg, 4);
                 const uint8_t* p = prow + o;
                 // (as above: the last block's window may reach past the crop, never past the caller's buffer)
-                if (rows_safe || (size_t)f * src.frame_stride + (size_t)(src.y0 + y) * src.row_stride + o + 128 <= src.readable) {
+                if (rows_safe || prep::packed_lane_ok(f, src.frame_stride, src.y0 + y, src.row_stride, o, 128, src.readable)) {
                     const u32x4a4* q = (const u32x4a4*)p;
                     u32x4a4 d[8];
 #pragma unroll

@@ -1,4 +1,4 @@
-"""What the frame-format tests share: the fixtures' readers, exact-extent device buffers, frame synthesis, the integer YUV -> BGR
+"""What the frame-format tests share: the fixtures' readers, device buffers of exact extent (DevBuf: two placements), frame synthesis, the integer YUV -> BGR
 conversion of include/meterelf_hip.h restated once, the layout builders of every family, a record per family that names its entry
 points, and the test bodies that are the same for every family once those names are given.
 
@@ -217,12 +217,31 @@ def to_layout(bgr, fmt, pad=0, rng=None, view3=False):
 
 
 def read_packed_dev(ctx, v, **kw):
-    """Packed pixels: the records of the device path for the view v of host frames (a device buffer of exactly its extent)."""
+    """Packed pixels: the records of the device path for the view v of host frames, from an allocation of its extent with the copy at
+    its start (the runtime rounds the allocation up to whole pages: what lies behind the copy is mapped; buffer_ends places copies
+    where the mapping ends)."""
     buf = DevBuf(v.ptr, v.extent)
     try:
         return ctx.process_frames_dev(buf.d.value, v.pixel_format, v.n, v.H, v.W, v.row_pitch, v.frame_stride, **kw)
     finally:
         buf.free()
+
+
+def pitched_packed(bgr, fmt, row_pad=0, rng=None):
+    """Packed pixels: a byte buffer of exactly the descriptor's extent, rows row_pad bytes longer than W pixels (a multiple of 4
+    for the 4-byte layouts), the frames back to back (frame_stride = one frame's extent: the last row unpadded), random filling:
+    (buffer, the arguments of process_frames_dev behind the pointer)."""
+    rng = rng if rng is not None else np.random.default_rng(0)
+    (n, H, W, _c) = bgr.shape
+    px = to_layout(bgr, fmt, 0, rng)[0]
+    ch = px.shape[-1]
+    assert ch == 3 or row_pad % 4 == 0
+    rp = W * ch + row_pad
+    fs = (H - 1) * rp + W * ch
+    buf = rng.integers(0, 256, size=n * fs, dtype=np.uint8)
+    for f in range(n):
+        np.lib.stride_tricks.as_strided(buf[f * fs:], shape=(H, W * ch), strides=(rp, 1))[...] = px[f].reshape(H, W * ch)
+    return buf, (getattr(_hip, 'PIX_' + fmt.upper()), n, H, W, rp, fs)
 
 
 def conventional420(Y, U, V, fmt, pad=0, rng=None):
@@ -512,7 +531,9 @@ def with_matrix(fam, code):
 
 # -------------------------------------------------------------------------------------------------------- shared bodies ---
 def read_both(fam, reader, ptr, desc, extent, phase=None):
-    """Records of the host path and of the device path (a device buffer of exactly `extent` bytes)."""
+    """Records of the host path and of the device path: a device copy of exactly `extent` bytes, placed by the family's devbuf -- plain
+    DevBuf: at the start of an allocation the runtime rounds up to whole pages, so a load past the extent stays inside mapped
+    memory; DevBuf.at_end: ending where the allocation ends (buffer_ends does that for every family)."""
     assert extent == fam.desc_extent(desc)
     host = getattr(reader.ctx, fam.host)(ptr, desc)
     buf = fam.devbuf(ptr, extent) if phase is None else fam.devbuf(ptr, extent, phase)
@@ -714,6 +735,126 @@ def resident_lanes_two_streams(fam, e, formats, pads_of, n, seed, min_ok, keep_h
         r.close()
         for b in bufs:
             b.free()
+
+
+MATCH_KINDS = (('fast', 'mfma'), ('gen', 'gen'), ('dot4', 'dot4'))   # MELF_MATCH, the kernel melf_ctx_last_match names
+ENDS_FRAMES = 33                                                       # a second frame group of one frame
+ENDS_CASES = (((410, 300), (0, 0)), ((412, 302), (1, 1)))              # frames cut to (H, W), meter_rect moved by (dx, dy)
+
+
+@functools.lru_cache(maxsize=None)
+def corner_frames(n=ENDS_FRAMES):
+    """(frames, mx, my): n same-sized sample-images1 frames that read OK, each rolled so that the dials template matches at the
+    bottom-right corner of the crop of meter_rect (50, 160)-(300, 410): match position (mx, my) = (crop_cols - tw, crop_rows - th).
+    Where the frames come from: the oracle's match positions of the fixture frames (no GPU)."""
+    from meterelf_amd._image import imread_bgr
+    from oracle import pyoracle as po
+    sd = os.path.join(GOLDEN, 'sample-images1')
+    op = po.Params(os.path.join(sd, 'params.yml'))
+    (th, tw) = op.template_size
+    (mx, my) = (250 - tw, 250 - th)
+    frames = [imread_bgr(f) for f in sorted(glob.glob(os.path.join(sd, '*.jpg')))]
+    shapes = [f.shape for f in frames]
+    same = np.stack([f for f in frames if f.shape == max(set(shapes), key=shapes.count)][:n + 12])
+    out = []
+    for (fr, o) in zip(same, po.process_frames(same, op)):
+        if o.status == 0 and len(out) < n:
+            out.append(np.roll(fr, (my - o.match_y, mx - o.match_x), axis=(0, 1)))
+    assert len(out) == n
+    out = np.stack(out)
+    out.setflags(write=False)
+    return out, mx, my
+
+
+def family_ends(fam, formats=None):
+    """buffer_ends' arguments for a Family: two pitched buffers per format, without padding and with the rows, pitches and gaps of
+    the family's check_pitch, neither with stride padding."""
+    def layouts(src, k, fmt, rng):
+        pads = dict(fam.check_pitch(k), stride_pad=0)
+        none = {key: (0, 0, 0) if isinstance(v, tuple) else 0 for (key, v) in pads.items()}
+        return [fam.pitched(*src, fmt, rng=rng, **kw) for kw in (none, pads)]
+    return dict(formats=formats or fam.formats, from_bgr=fam.from_bgr, bgr_of=fam.bgr_of, layouts=layouts,
+                read_dev=lambda ctx, d, desc: getattr(ctx, fam.dev)(d, desc),
+                nframes_stride=lambda desc: (desc.n, desc.frame_stride))
+
+
+def buffer_ends(monkeypatch, tmp_path, formats, from_bgr, bgr_of, layouts, read_dev, nframes_stride, phases_of):
+    """Device buffers that end where their allocation ends (DevBuf.at_end), at every base phase phases_of(fmt) the family's check
+    accepts, read through the device entry point: a load past the descriptor's extent leaves the mapping.  The frames
+    (corner_frames) are cut so that meter_rect ends on the frame's last row and column, (410, 300), or starts at an odd origin and
+    ends one pixel short of both, (412, 302) with the rect moved by (1, 1); the template matches at the crop's bottom-right corner
+    (asserted from the records), so the dial windows' last rows and columns are the crop's.  Buffers: layouts(src, k, fmt, rng), a
+    list of (byte buffer of exactly the extent, descriptor) without stride padding (asserted), for 1 and for 33 frames; the last
+    frame reads FRAME_OK (asserted).  Under each match kernel (MELF_MATCH fast, gen, dot4; melf_ctx_last_match asserted after
+    every call) the records equal, byte for byte, read_frames of the family's BGR frames under that kernel."""
+    from meterelf_amd import MeterReader
+    (base, mx, my) = corner_frames()
+    rng = np.random.default_rng(ENDS_FRAMES)
+    for (case, ((H, W), (dx, dy))) in enumerate(ENDS_CASES):
+        params = params_with_rect(tmp_path, 'sample-images1', (50 + dx, 160 + dy, 300 + dx, 410 + dy), 'ends%d' % case)
+        src = from_bgr(np.ascontiguousarray(np.roll(base, (dy, dx), axis=(1, 2))[:, :H, :W]))
+        readers = []
+        try:
+            for (kind, kernel) in MATCH_KINDS:
+                monkeypatch.setenv('MELF_MATCH', kind)
+                r = MeterReader(params)
+                want = r.read_frames(bgr_of(*src))
+                assert r.ctx.last_match()['kernel'] == kernel
+                assert [(int(x), int(y)) for (x, y) in zip(want['match_x'], want['match_y'])] == [(mx, my)] * ENDS_FRAMES, (H, W, kind)
+                assert int(want['status'][0]) == int(want['status'][-1]) == _hip.FRAME_OK, (H, W, kind)
+                readers.append((r, kernel, want))
+            for n in (1, ENDS_FRAMES):
+                for (k, fmt) in enumerate(formats):
+                    for (buf, desc) in layouts(tuple(p[:n] for p in src), k, fmt, rng):
+                        (dn, fs) = nframes_stride(desc)
+                        assert dn == n and buf.nbytes == n * fs, (fmt, 'stride padding')
+                        for phase in phases_of(fmt):
+                            d = DevBuf.at_end(buf.ctypes.data, buf.nbytes, phase)
+                            try:
+                                assert d.d.value % 4 == phase
+                                for (r, kernel, want) in readers:
+                                    got = read_dev(r.ctx, d.d.value, desc)
+                                    assert r.ctx.last_match()['kernel'] == kernel
+                                    assert got.tobytes() == want[:n].tobytes(), (H, W, n, fmt, phase, kernel)
+                            finally:
+                                d.free()
+        finally:
+            for (r, _k, _w) in readers:
+                r.close()
+
+
+def first_bytes(monkeypatch, tmp_path, formats, from_bgr, bgr_of, layouts, read_dev, x0s):
+    """A base that is not 4-byte aligned (phases 1 .. 3) and meter_rect in the frame's first row from column x0 of x0s.  For the
+    columns from which a window would reach the base's dword, launch_match_prep sends the whole launch down the prep kernel's
+    sample-by-sample path (melf_prep_addr.h: prep_window_readable); this test checks that the RECORDS of that path, and of the
+    window path at the columns next to it, are byte for byte those of read_frames of the family's BGR frames, under the two
+    matrix-core match kernels (they read what the prep kernel wrote), three frames.  It cannot see where a load starts: the bytes
+    before an unaligned base share a mapped dword with it.  That no window starts before the base is what
+    tests/prep_bounds_main.cpp sweeps, with the launcher's own function."""
+    from meterelf_amd import MeterReader
+    (base, _mx, _my) = corner_frames()
+    rng = np.random.default_rng(3)
+    for x0 in x0s:
+        params = params_with_rect(tmp_path, 'sample-images1', (x0, 0, x0 + 250, 250), 'first%d' % x0)
+        src = from_bgr(np.ascontiguousarray(np.roll(base[:3], (-160, x0 - 50), axis=(1, 2))[:, :252, :x0 + 252 - (x0 & 1)]))
+        for (kind, kernel) in MATCH_KINDS[:2]:
+            monkeypatch.setenv('MELF_MATCH', kind)
+            r = MeterReader(params)
+            try:
+                want = r.read_frames(bgr_of(*src))
+                assert (want['status'] == _hip.FRAME_OK).all(), (x0, kind)
+                for (k, fmt) in enumerate(formats):
+                    (buf, desc) = layouts(src, k, fmt, rng)[0]
+                    for phase in (1, 2, 3):
+                        d = DevBuf.at_end(buf.ctypes.data, buf.nbytes, phase)
+                        try:
+                            assert d.d.value % 4 == phase
+                            assert read_dev(r.ctx, d.d.value, desc).tobytes() == want.tobytes(), (x0, fmt, phase, kind)
+                            assert r.ctx.last_match()['kernel'] == kernel
+                        finally:
+                            d.free()
+            finally:
+                r.close()
 
 
 def launch_counts(ctx):

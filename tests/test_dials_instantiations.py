@@ -13,6 +13,12 @@ from ws_max, the context's largest dial window (2 R + 5 rows): 72 kernels.  The 
   (cstart / cshift of k_yneedle and k_yp_needle<1, *>, mstart / mshifted of k_p422_needle), every family, at both parities of
   the crop's origin.
 
+The loads themselves are checked on the CPU: tests/frame_src_bounds_main.cpp compiles melf_frame_src.h for the host and runs every
+source type against frames malloc'd to exactly their extent, under the host sanitizers (test_frame_src_bounds_sweep), and
+tests/prep_bounds_main.cpp sweeps the prep arms' address functions (melf_prep_addr.h, shared with the kernels) the same way
+(test_prep_bounds_sweep).  On the GPU the edge cases then
+run once more on frames cut to the crop's last row and column, every family's device copy ending where its allocation ends.
+
 CPU tests check the inputs: the oracle reads every frame at every geometry, the outer rows of each NR class carry part of the
 reading, the matches land where the edge cases need them, and the shifts the edge cases are there for do act.
 
@@ -25,6 +31,7 @@ import functools
 import glob
 import os
 import shutil
+import subprocess
 import sys
 import tempfile
 
@@ -352,6 +359,52 @@ def test_edge_geometries_reach_the_paths():
     assert seen_m == {(0, 1), (1, 1)}
 
 
+def rocm_clangxx():
+    """The ROCm tree's clang++ and include directory, from the hipcc meterelf_amd/csrc/Makefile builds with (HIPCC, else
+    /opt/rocm/bin/hipcc)."""
+    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+    rocm = os.path.dirname(os.path.dirname(os.path.realpath(shutil.which(hipcc) or hipcc)))
+    cxx = os.path.join(rocm, 'llvm', 'bin', 'clang++')
+    assert os.path.isfile(cxx), 'no clang++ beside %s (looked for %s): the dial sources cannot be compiled for the host' % (hipcc, cxx)
+    return cxx, os.path.join(rocm, 'include')
+
+
+def _build_and_run(tmp_path, cxx, src, name, extra, san):
+    """src as a stand-alone program, plain and under the host sanitizers `san`: both exit 0 and print `failures 0`.  Returns
+    the plain run's output."""
+    out = None
+    for (tag, flags) in (('plain', ['-O2']), ('san', ['-O1', '-g', '-fno-sanitize-recover=all'] + san)):
+        exe = str(tmp_path / (name + '_' + tag))
+        subprocess.check_call([cxx, '-std=c++17', '-Wall', '-Werror'] + extra + flags + ['-o', exe, src])
+        p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+        assert p.returncode == 0, (tag, p.stdout[-2000:], p.stderr[-4000:])
+        assert b'failures 0' in p.stdout, p.stdout
+        print(tag, p.stdout.decode().strip())
+        out = out or p.stdout.decode()
+    return out
+
+
+def test_frame_src_bounds_sweep(tmp_path):
+    """tests/frame_src_bounds_main.cpp: the dial sources of melf_frame_src.h, compiled for the host and run on frames malloc'd to
+    exactly the descriptor's extent, over the sweep the program's head lists: no load leaves the allocation (the sanitizer's red
+    zones), every unpacked pixel equals px of the same source and plain indexing of the planes, and every source type took the
+    window fetch, the exact path and -- where it has one -- the load moved left at the crop's right edge.  Only `alignment` is
+    dropped from the sanitizers: the sources load unaligned dwords on purpose."""
+    (cxx, inc) = rocm_clangxx()
+    out = _build_and_run(tmp_path, cxx, os.path.join(ROOT, 'tests', 'frame_src_bounds_main.cpp'), 'frame_src_bounds',
+                         ['-D__HIP_PLATFORM_AMD__', '-I' + inc], ['-fsanitize=address,undefined', '-fno-sanitize=alignment'])
+    assert out.count('windows: quads') == 15, out   # the fifteen source types
+
+
+def test_prep_bounds_sweep(tmp_path):
+    """tests/prep_bounds_main.cpp: every load of the prep kernels' 8-bit arms lies inside a buffer of exact extent, over the sweep
+    the program's head lists, and every arm took each of its three paths.  The addresses, spans and guards are those of
+    meterelf_amd/csrc/melf_prep_addr.h, the functions the kernels and the launcher compute them with."""
+    out = _build_and_run(tmp_path, os.environ.get('CXX', 'g++'), os.path.join(ROOT, 'tests', 'prep_bounds_main.cpp'), 'prep_bounds', [],
+                         ['-fsanitize=address,undefined'])
+    assert out.count('lanes: row-safe') == 10, out   # the ten arms
+
+
 # ------------------------------------------------------------------------------------------------------------- GPU ---------
 SEEN = set()       # (family, NR) pairs this module launched and asserted
 _SWEPT = {}        # r_max -> None, or the failure of its run
@@ -414,11 +467,17 @@ def _converted(bgr, key):
     return _CONVERTED[key]
 
 
-def _run_families(c, bgr, rng, families, want_match_x=None):
+def _run_families(c, bgr, rng, families, want_match_x=None, at_end=False):
     """Every family named, host and device path, byte for byte against read_frames of the packed BGR frames its conversion
-    defines; melf_ctx_last_dials after every call.  want_match_x: where the converted frames, too, have to match."""
+    defines; melf_ctx_last_dials after every call.  want_match_x: where the converted frames, too, have to match.  at_end: the
+    device path alone, every family's device copy ending where its allocation ends (frame_cases.DevBuf.at_end)."""
     ctx = c.ctx
     wants = {}
+    devbuf = fc.DevBuf.at_end if at_end else fc.DevBuf
+
+    def packed_dev(v):
+        return _dev(lambda: devbuf(v.ptr, v.extent),
+                    lambda d: ctx.process_frames_dev(d, v.pixel_format, v.n, v.H, v.W, v.row_pitch, v.frame_stride))
 
     def want_of(key):
         if key not in wants:
@@ -429,8 +488,9 @@ def _run_families(c, bgr, rng, families, want_match_x=None):
         return wants[key].tobytes()
 
     def check(family, fmt, wb, host, dev):
-        assert host().tobytes() == wb, (c.tag, fmt, 'host')
-        c.ran(family)
+        if not at_end:
+            assert host().tobytes() == wb, (c.tag, fmt, 'host')
+            c.ran(family)
         assert dev().tobytes() == wb, (c.tag, fmt, 'device')
         c.ran(family)
 
@@ -438,19 +498,19 @@ def _run_families(c, bgr, rng, families, want_match_x=None):
         if family in families:
             (arr, f) = fc.to_layout(bgr, fmt, 5, rng)
             check(family, fmt, want_of('bgr'), lambda: c.reader.read_frame_views(arr, f),
-                  lambda: fc.read_packed_dev(ctx, _hip.frames_view(arr, f)))
+                  lambda: packed_dev(_hip.frames_view(arr, f)))
     for fmt in ('nv12', 'i420'):
         if fmt in families:
             (Y, U, V, _b) = _converted(bgr, '420')
             v = _hip.yuv_frames_view(fc.conventional420(Y, U, V, fmt, 10 if fmt == 'nv12' else 0, rng), fmt)
             check(fmt, fmt, want_of('420'), lambda: ctx.process_yuv(v.ptr, v.descriptor()),
-                  lambda: _dev(lambda: fc.DevBuf(v.ptr, v.extent), lambda d: ctx.process_yuv_dev(d, v.descriptor())))
+                  lambda: _dev(lambda: devbuf(v.ptr, v.extent), lambda d: ctx.process_yuv_dev(d, v.descriptor())))
     if 'p422' in families:
         (Y, U, V, _b) = _converted(bgr, '422')
         for fmt in ('yuyv', 'uyvy'):
             v = _hip.yuv422_frames_view(fc.conventional422(Y, U, V, fmt, 6, rng), fmt)
             check('p422', fmt, want_of('422'), lambda: ctx.process_yuv422(v.ptr, v.descriptor()),
-                  lambda: _dev(lambda: fc.DevBuf(v.ptr, v.extent), lambda d: ctx.process_yuv422_dev(d, v.descriptor())))
+                  lambda: _dev(lambda: devbuf(v.ptr, v.extent), lambda d: ctx.process_yuv422_dev(d, v.descriptor())))
     for (fmt, family) in (('i422', 'yp_sub1_step1'), ('nv16', 'yp_sub1_step2'), ('i444', 'yp_sub0_step1'), ('nv24', 'yp_sub0_step2')):
         if family in families:
             (sx, sy, step, _vf) = fc.YUV_PLANAR_FORMATS[fmt]
@@ -461,7 +521,7 @@ def _run_families(c, bgr, rng, families, want_match_x=None):
             (Y, U, V, _b) = _converted(bgr, key)
             v = _hip.yuv_planar_frames_view(fc.conventional_yuv_planar(Y, U, V, fmt, 0, rng), fmt)
             check(family, fmt, want_of(key), lambda: ctx.process_yuv_planar(v.ptr, v.descriptor()),
-                  lambda: _dev(lambda: fc.DevBuf(v.ptr, v.extent), lambda d: ctx.process_yuv_planar_dev(d, v.descriptor())))
+                  lambda: _dev(lambda: devbuf(v.ptr, v.extent), lambda d: ctx.process_yuv_planar_dev(d, v.descriptor())))
     if 'planar' in families:
         v = _hip.planar_frames_view(fc.to_planes(bgr, 'rgb', rng), 'rgb')
         check('planar', 'rgb planes', want_of('bgr'), lambda: ctx.process_planes(v.ptr, v.descriptor()),
@@ -537,7 +597,10 @@ def test_every_family_at_every_window_class(r_max):
 @pytest.mark.parametrize('k', range(4))
 @pytest.mark.parametrize('kind', EDGE_KINDS)
 def test_crop_edge_paths(kind, k, x0):
-    """x0 = 51, the crop's origin at the other parity: the families that read chroma pairs."""
+    """x0 = 51, the crop's origin at the other parity: the families that read chroma pairs.  Then the same frames cut to the crop's
+    bottom row and right column (the width rounded up to even), every family's device copy ending where its allocation ends: the
+    last frame matches at the crop's last column (match_x = k), so its windows' last pieces -- the exact path of the window that
+    leaves the crop, the chroma and macropixel fetches moved left -- lie against the buffer's last bytes."""
     data = edge_data(kind, k, x0)
     bgr = edge_frames(k, x0)
     tag = '%s_k%d_x%d' % (kind, k, x0)
@@ -547,8 +610,12 @@ def test_crop_edge_paths(kind, k, x0):
         recs = c.read_bgr(bgr)
         _compare_records(recs, edge_oracle(kind, k, x0), tag=tag)
         assert [int(x) for x in recs['match_x']] == edge_match_x(k)
-        _run_families(c, bgr, np.random.default_rng(7 + k), [f for f in FAMILIES if x0 == RECT_X0 or f in SUBSAMPLED],
-                      want_match_x=edge_match_x(k))
+        families = [f for f in FAMILIES if x0 == RECT_X0 or f in SUBSAMPLED]
+        _run_families(c, bgr, np.random.default_rng(7 + k), families, want_match_x=edge_match_x(k))
+        x1 = data['meter_rect']['bottom_right'][0]
+        assert edge_match_x(k)[-1] == k == x1 - x0 - data['dials_template_size'][0]
+        cut = np.ascontiguousarray(bgr[:, :RECT_Y1, :(x1 + 1) & ~1])
+        _run_families(c, cut, np.random.default_rng(70 + k), families, want_match_x=edge_match_x(k), at_end=True)
     finally:
         c.close()
 

@@ -221,8 +221,9 @@ def test_1080p_six_dials_bgra_padded(env, tmp_path):
 
 @pytest.mark.gpu
 def test_frame_edges_and_batch_sizes(env):
-    """meter_rect (50, 160)-(300, 410) reaching the right and bottom frame edges, and past them (numpy clamp), device buffers of
-    exactly the descriptor's extent; batch sizes around the 32-frame group."""
+    """meter_rect (50, 160)-(300, 410) reaching the right and bottom frame edges, and past them (numpy clamp), device copies of
+    exactly the descriptor's extent at the start of their allocation (what lies behind them is mapped: test_buffer_ends places
+    them at its end); batch sizes around the 32-frame group."""
     e = env['sample-images1']
     reader = e['reader']
     rng = np.random.default_rng(11)
@@ -241,6 +242,28 @@ def test_frame_edges_and_batch_sizes(env):
             (arr, f) = to_layout(src[:n], fmt, 9, rng)
             assert reader.read_frame_views(arr, f).tobytes() == want, (n, fmt)
             assert _read_dev(reader.ctx, _hip.frames_view(arr, f)).tobytes() == want, (n, fmt)
+
+
+@pytest.mark.gpu
+def test_buffer_ends(env, monkeypatch, tmp_path):  # noqa: F811
+    """tests/frame_cases.py: buffer_ends -- pitched buffers of exactly the descriptor's extent that end where their allocation ends,
+    at every base phase the descriptor check accepts, the match at the crop's bottom-right corner, 1 and 33 frames, every match
+    kernel."""
+    def layouts(src, k, fmt, rng):
+        return [fc.pitched_packed(src[0], fmt, pad, rng) for pad in ((0, 12) if fmt in ('bgra', 'rgba') else (0, 7))]
+    fc.buffer_ends(monkeypatch, tmp_path, FORMATS, from_bgr=lambda bgr: (bgr,), bgr_of=lambda bgr: bgr,
+                   layouts=layouts, read_dev=lambda ctx, d, a: ctx.process_frames_dev(d, *a), nframes_stride=lambda a: (a[1], a[5]),
+                   phases_of=lambda fmt: (0,) if fmt in ('bgra', 'rgba') else (0, 1, 2, 3))
+
+
+@pytest.mark.gpu
+def test_first_bytes_unaligned_base(env, monkeypatch, tmp_path):  # noqa: F811
+    """tests/frame_cases.py: first_bytes -- a base at byte phases 1 .. 3 and the meter crop at the frame's first row and first
+    columns, where the launcher sends the prep kernel down its sample-by-sample path: the records are the BGR path's.  (Where the
+    loads start is swept on the CPU, tests/prep_bounds_main.cpp.)"""
+    fc.first_bytes(monkeypatch, tmp_path, ('bgr', 'rgb'), from_bgr=lambda bgr: (bgr,), bgr_of=lambda bgr: bgr,
+                   layouts=lambda src, k, fmt, rng: [fc.pitched_packed(src[0], fmt, 0, rng)],
+                   read_dev=lambda ctx, d, a: ctx.process_frames_dev(d, *a), x0s=(0, 1))
 
 
 @pytest.mark.gpu

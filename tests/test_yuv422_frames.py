@@ -21,8 +21,9 @@ CPU tests: the descriptor against the header, yuv422_frames_view's mapping of nu
 against hand-derived triples and byte positions, the new kernels' code-object notes.  GPU tests: the conversion kernel for all
 2^24 triples at both pixels of a macropixel, records against the BGR path of the converted frames on the fixtures, with every
 match kernel, at every parity of the crop, at the frame edges, at 1080p, over lanes and streams, with torch tensors (in a child
-process that imports torch first: tests/frame_cases.py says why).  Every device buffer has exactly the descriptor's
-extent: a load past it is a fault.
+process that imports torch first: tests/frame_cases.py says why).  Every device copy has exactly the descriptor's
+extent; test_buffer_ends places the copies where their allocation ends, so that a load past the extent leaves the mapping (the
+other tests' copies start their allocation, which the runtime rounds up to whole pages).
 """
 import ctypes as C
 import functools
@@ -322,13 +323,22 @@ def test_odd_geometry(env, tmp_path):  # noqa: F811
 @pytest.mark.gpu
 def test_frame_edges_and_batch_sizes(env):  # noqa: F811
     """meter_rect (50, 160)-(300, 410) reaching the right and bottom frame edges, and past them (numpy clamp), with an odd frame
-    height, device buffers of exactly the descriptor's extent (every _read_both); batch sizes around the 32-frame group and
-    above the 128 frames of a host-path chunk."""
+    height, device copies of exactly the descriptor's extent at the start of their allocation (every _read_both; what lies behind
+    them is mapped: test_buffer_ends places them at its end); batch sizes around the 32-frame group and above the 128 frames of a
+    host-path chunk."""
     e = env['sample-images1']
     rng = np.random.default_rng(11)
     src = fc.synth(e['frames'], 131, 3)
     fc.frame_edges(F422, e['reader'], src, rng, 12, ((410, 300), (399, 290), (405, 298)), _check_source, min_ok=6)
     fc.batch_sizes(F422, e['reader'], src, rng, (1, 31, 32, 33, 131), lambda k: (FORMATS[k % 3],), _check_source, min_ok=80)
+
+
+@pytest.mark.gpu
+def test_buffer_ends(env, monkeypatch, tmp_path):  # noqa: F811
+    """tests/frame_cases.py: buffer_ends -- pitched buffers of exactly the descriptor's extent that end where their allocation ends,
+    at every base phase the descriptor check accepts, the match at the crop's bottom-right corner, 1 and 33 frames, every match
+    kernel."""
+    fc.buffer_ends(monkeypatch, tmp_path, **fc.family_ends(F422), phases_of=lambda fmt: (0,))
 
 
 @pytest.mark.gpu

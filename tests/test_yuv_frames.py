@@ -246,13 +246,33 @@ def test_odd_geometry(env, tmp_path):  # noqa: F811
 
 @pytest.mark.gpu
 def test_frame_edges_and_batch_sizes(env):  # noqa: F811
-    """meter_rect (50, 160)-(300, 410) reaching the right and bottom frame edges, and past them (numpy clamp), device buffers of
-    exactly the descriptor's extent (every _read_both); batch sizes around the 32-frame group."""
+    """meter_rect (50, 160)-(300, 410) reaching the right and bottom frame edges, and past them (numpy clamp), device copies of
+    exactly the descriptor's extent at the start of their allocation (every _read_both; what lies behind them is mapped:
+    test_buffer_ends places them at its end); batch sizes around the 32-frame group."""
     e = env['sample-images1']
     rng = np.random.default_rng(11)
     src = fc.synth(e['frames'], 70, 3)
     fc.frame_edges(F420, e['reader'], src, rng, 12, ((410, 300), (400, 290)), _check_source, min_ok=6)
     fc.batch_sizes(F420, e['reader'], src, rng, (1, 31, 33, 70), lambda k: FORMATS, _check_source, min_ok=40)
+
+
+@pytest.mark.gpu
+def test_buffer_ends(env, monkeypatch, tmp_path):  # noqa: F811
+    """tests/frame_cases.py: buffer_ends -- pitched buffers of exactly the descriptor's extent that end where their allocation ends,
+    at every base phase the descriptor check accepts, the match at the crop's bottom-right corner, 1 and 33 frames, every match
+    kernel."""
+    fc.buffer_ends(monkeypatch, tmp_path, **fc.family_ends(F420, ('nv12', 'i420', 'yv12')),
+                   phases_of=lambda fmt: (0, 1, 2, 3))
+
+
+@pytest.mark.gpu
+def test_first_bytes_unaligned_base(env, monkeypatch, tmp_path):  # noqa: F811
+    """tests/frame_cases.py: first_bytes -- a base at byte phases 1 .. 3 and the meter crop at the frame's first row and first
+    columns, where the launcher sends the prep kernel down its sample-by-sample path: the records are the BGR path's.  (Where the
+    loads start is swept on the CPU, tests/prep_bounds_main.cpp.)"""
+    args = fc.family_ends(F420, ('nv12', 'i420', 'yv12'))
+    del args['nframes_stride']   # (buffer_ends' check of the frame stride)
+    fc.first_bytes(monkeypatch, tmp_path, **args, x0s=(0, 3, 4))
 
 
 @pytest.mark.gpu

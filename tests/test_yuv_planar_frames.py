@@ -405,8 +405,9 @@ def test_odd_geometry(env, tmp_path, name):
 
 @pytest.mark.gpu
 def test_frame_edges_and_batch_sizes(env):
-    """meter_rect reaching the right and bottom frame edges, and past them (numpy clamp); device buffers of exactly the
-    descriptor's extent; batch sizes around the 32-frame group and 131."""
+    """meter_rect reaching the right and bottom frame edges, and past them (numpy clamp); device copies of exactly the
+    descriptor's extent at the start of their allocation (what lies behind them is mapped: test_buffer_ends places them at its
+    end); batch sizes around the 32-frame group and 131."""
     e = env['sample-images1']
     reader = e['reader']
     rng = np.random.default_rng(11)
@@ -417,6 +418,17 @@ def test_frame_edges_and_batch_sizes(env):
         assert all((w['status'] == _hip.FRAME_OK).sum() >= 6 for w in wants.values()), (H, W)
     for n in (1, 31, 32, 33, 131):
         _check_formats(reader, src[:n], n, rng, formats=('yv16', 'nv16', 'i444', 'nv42') if n != 131 else ('i422', 'nv24'), pitch=n < 131)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', sorted(SUBSAMPLINGS))
+def test_buffer_ends(env, monkeypatch, tmp_path, name):
+    """tests/frame_cases.py: buffer_ends -- pitched buffers of exactly the descriptor's extent that end where their allocation ends,
+    at every base phase the descriptor check accepts, the match at the crop's bottom-right corner, 1 and 33 frames, every match
+    kernel; every format of one chroma subsampling per case."""
+    fam = fc.yuv_planar(*SUBSAMPLINGS[name])
+    assert sorted(f for s in SUBSAMPLINGS.values() for f in fc.yuv_planar(*s).formats) == sorted(NAMES)
+    fc.buffer_ends(monkeypatch, tmp_path, **fc.family_ends(fam), phases_of=lambda fmt: (0, 1, 2, 3))
 
 
 @pytest.mark.gpu

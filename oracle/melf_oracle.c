@@ -93,7 +93,14 @@ enum {
     ORC_OPT_L_INTEGER = 7,     /* 1: L = (max + min + 1) >> 1 instead of the float32 path                            */
     ORC_OPT_MINMAX_LAST = 8,   /* 1: minMaxLoc returns the last maximum in raster order instead of the first         */
     ORC_OPT_HUE_G_FIRST = 9,   /* 1: the hue sector test tries vmax == g before vmax == r                            */
-    ORC_OPT_COUNT = 10
+    /* the reference's own Python steps (meterelf/_reading.py) and inRange's closed bounds: mutants for tests/dial_scenes.py */
+    ORC_OPT_AREA_GE = 10,      /* 1: the largest contour is taken at area >= 100 instead of > 100                    */
+    ORC_OPT_NO_UNWRAP = 11,    /* 1: ring angles 0.75 or more above the smallest are not lowered by one turn         */
+    ORC_OPT_TRIM_CUT = 12,     /* 1: the trim cuts 2 from each end whenever there are 5 or more ring points          */
+    ORC_OPT_TRIM_KEY = 13,     /* 1: among equal angles the larger squared distance sorts first                      */
+    ORC_OPT_CARRY_HALF = 14,   /* 1: the digit carry thresholds are 0.5 / 0.5 instead of 0.55 / 0.45                 */
+    ORC_OPT_INRANGE_OPEN = 15, /* 1: inRange's bounds are exclusive                                                  */
+    ORC_OPT_COUNT = 16
 };
 static int g_opt[ORC_OPT_COUNT];
 #define g_hls_variant (g_opt[ORC_OPT_HLS_VARIANT])
@@ -343,8 +350,12 @@ ORC_API void orc_inrange(const uint8_t* hls, int rows, int cols, const int* lo, 
 {
     for (long p = 0; p < (long)rows * cols; ++p) {
         const uint8_t* v = hls + 3 * p;
-        out[p] = (v[0] >= lo[0] && v[0] <= hi[0] && v[1] >= lo[1] && v[1] <= hi[1] &&
-                  v[2] >= lo[2] && v[2] <= hi[2]) ? 255 : 0;
+        if (g_opt[ORC_OPT_INRANGE_OPEN])
+            out[p] = (v[0] > lo[0] && v[0] < hi[0] && v[1] > lo[1] && v[1] < hi[1] &&
+                      v[2] > lo[2] && v[2] < hi[2]) ? 255 : 0;
+        else
+            out[p] = (v[0] >= lo[0] && v[0] <= hi[0] && v[1] >= lo[1] && v[1] <= hi[1] &&
+                      v[2] >= lo[2] && v[2] <= hi[2]) ? 255 : 0;
     }
 }
 
@@ -624,11 +635,12 @@ ORC_API int orc_angle_by_vector(double x, double y, double* out)
 ORC_API double orc_value_by_positions(const double* r)
 {
     double r4 = r[0], r3 = r[1], r2 = r[2], r1 = r[3];
-    int d3 = (int)r3 + ((py_fmod(r3, 1.0) > 0.55 && r4 <= 2) ? 1 : 0) - ((py_fmod(r3, 1.0) < 0.45 && r4 >= 8) ? 1 : 0);
+    double up = g_opt[ORC_OPT_CARRY_HALF] ? 0.5 : 0.55, down = g_opt[ORC_OPT_CARRY_HALF] ? 0.5 : 0.45;
+    int d3 = (int)r3 + ((py_fmod(r3, 1.0) > up && r4 <= 2) ? 1 : 0) - ((py_fmod(r3, 1.0) < down && r4 >= 8) ? 1 : 0);
     d3 = ((d3 % 10) + 10) % 10;
-    int d2 = (int)r2 + ((py_fmod(r2, 1.0) > 0.55 && d3 <= 2) ? 1 : 0) - ((py_fmod(r2, 1.0) < 0.45 && d3 >= 8) ? 1 : 0);
+    int d2 = (int)r2 + ((py_fmod(r2, 1.0) > up && d3 <= 2) ? 1 : 0) - ((py_fmod(r2, 1.0) < down && d3 >= 8) ? 1 : 0);
     d2 = ((d2 % 10) + 10) % 10;
-    int d1 = (int)r1 + ((py_fmod(r1, 1.0) > 0.55 && d2 <= 2) ? 1 : 0) - ((py_fmod(r1, 1.0) < 0.45 && d2 >= 8) ? 1 : 0);
+    int d1 = (int)r1 + ((py_fmod(r1, 1.0) > up && d2 <= 2) ? 1 : 0) - ((py_fmod(r1, 1.0) < down && d2 >= 8) ? 1 : 0);
     d1 = ((d1 % 10) + 10) % 10;
     return (d1 * 100.0) + (d2 * 10.0) + (d3 * 1.0) + r4 / 10.0;
 }
@@ -641,8 +653,9 @@ static int cmp_ang_sq(const void* pa, const void* pb)
     const ang_sq* b = (const ang_sq*)pb;
     if (a->a < b->a) return -1;
     if (a->a > b->a) return 1;
-    if (a->d < b->d) return -1;
-    if (a->d > b->d) return 1;
+    int rev = g_opt[ORC_OPT_TRIM_KEY] ? -1 : 1;
+    if (a->d < b->d) return -rev;
+    if (a->d > b->d) return rev;
     return 0;
 }
 
@@ -695,7 +708,7 @@ static int read_one_dial(const uint8_t* dials_hls, int th, int tw, const orc_dia
         rc = 1;
         goto done;
     }
-    if (!(area > 100)) memcpy(needle, mde, n); /* needle_mask = needle_mask_de, _reading.py:147-148 */
+    if (!(area > 100 || (g_opt[ORC_OPT_AREA_GE] && area == 100))) memcpy(needle, mde, n); /* needle_mask = needle_mask_de, _reading.py:147-148 */
 
     /* momentum, _reading.py:32-41 ; find_non_zero is raster order */
     double mx = 0.0, my = 0.0;
@@ -746,11 +759,11 @@ static int read_one_dial(const uint8_t* dials_hls, int th, int tw, const orc_dia
     double min_angle = as[0].a;
     for (int k = 1; k < na; ++k)
         if (as[k].a < min_angle) min_angle = as[k].a;
-    for (int k = 0; k < na; ++k)
+    for (int k = 0; k < na && !g_opt[ORC_OPT_NO_UNWRAP]; ++k)
         if (!(fabs(as[k].a - min_angle) < 0.75)) as[k].a = as[k].a - 1;
     int b = 0, e = na;
     if (na >= 5) {
-        int cut = (na - 3) / 2 < 2 ? (na - 3) / 2 : 2;
+        int cut = (na - 3) / 2 < 2 && !g_opt[ORC_OPT_TRIM_CUT] ? (na - 3) / 2 : 2;
         qsort(as, na, sizeof(ang_sq), cmp_ang_sq);
         b = cut;
         e = na - cut;

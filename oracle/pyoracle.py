@@ -93,7 +93,8 @@ def _ptr(a):
 
 # audit switches of melf_oracle.c (ORC_OPT_*): value 0 is the restatement proper
 OPTIONS = ['hls_variant', 'contour_tie', 'mean_form', 'hls_round', 'area_rule', 'no_hole_fill', 'erode_border',
-           'l_integer', 'minmax_last', 'hue_g_first']
+           'l_integer', 'minmax_last', 'hue_g_first', 'area_ge', 'no_unwrap', 'trim_cut', 'trim_key', 'carry_half',
+           'inrange_open']
 
 
 def set_option(name, value):

@@ -13,6 +13,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
 
 
+def po_options():
+    from oracle import pyoracle as po
+    return po.OPTIONS
+
+
 def test_sensitivity_table_is_current():
     import oracle_sensitivity as osens
     rows = osens.audit()
@@ -27,6 +32,14 @@ def test_sensitivity_table_is_current():
     # ... and do NOT pin these: no fixture exercises them (documented as unpinned in DESIGN.md section 2)
     for k in ('hls_variant=1', 'hls_variant=2', 'contour_tie=1', 'mean_form=1', 'area_rule=1', 'erode_border=1', 'hue_g_first=1'):
         assert by[k]['golden_lines_changed'] == 0 and by[k]['records_changed'] == 0, k
+    # the reference's own Python steps and inRange's closed bounds (the mutants of tests/dial_scenes.py): the goldens pin the unwrap,
+    # the cut sizes, the carry thresholds and the bounds, and do not pin `> 100` against `>=` or the trim's second sort key
+    for k in ('no_unwrap=1', 'trim_cut=1', 'carry_half=1', 'inrange_open=1'):
+        assert by[k]['golden_lines_changed'] > 0, k
+    for k in ('area_ge=1', 'trim_key=1'):
+        assert by[k]['golden_lines_changed'] == 0, k
+    assert by['area_ge=1']['records_changed'] == 0 and by['trim_key=1']['records_changed'] > 0
+    assert len(rows) == len(osens.VARIANTS) == 17 and {r['switch'].split('=')[0] for r in rows} == set(po_options())
     # after the audit the oracle is back to the restatement proper
     from oracle import pyoracle as po
     import glob

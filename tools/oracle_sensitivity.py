@@ -27,7 +27,11 @@ from oracle import pyoracle as po  # noqa: E402
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
 NOISY = '20180814021310-00-e02.jpg'
 VARIANTS = [('hls_variant', 1), ('hls_variant', 2), ('contour_tie', 1), ('mean_form', 1), ('hls_round', 1), ('area_rule', 1),
-            ('no_hole_fill', 1), ('erode_border', 1), ('l_integer', 1), ('minmax_last', 1), ('hue_g_first', 1)]
+            ('no_hole_fill', 1), ('erode_border', 1), ('l_integer', 1), ('minmax_last', 1), ('hue_g_first', 1),
+            ('area_ge', 1), ('no_unwrap', 1), ('trim_cut', 1), ('trim_key', 1), ('carry_half', 1), ('inrange_open', 1)]
+# the switches that act after the template match: their runs re-read the dials of the unflipped run's matched crop
+DIAL_STAGE = {'contour_tie', 'area_rule', 'no_hole_fill', 'erode_border', 'area_ge', 'no_unwrap', 'trim_cut', 'trim_key', 'carry_half',
+              'inrange_open'}
 WHAT = {
     ('hls_variant', 1): 'BGR2HLS S formula: scalar-tail form `2 - vmax - vmin` for every pixel',
     ('hls_variant', 2): 'BGR2HLS S formula: SIMD form `2 - (vmax + vmin)` for every pixel (no scalar tail)',
@@ -40,6 +44,12 @@ WHAT = {
     ('l_integer', 1): 'L = (max + min + 1) >> 1 instead of the float32 path',
     ('minmax_last', 1): 'minMaxLoc returns the last maximum in raster order instead of the first',
     ('hue_g_first', 1): 'hue sector test tries vmax == g before vmax == r (differs on r == g ties)',
+    ('area_ge', 1): 'the largest contour is taken at contourArea >= 100 instead of > 100',
+    ('no_unwrap', 1): 'ring angles 0.75 turn or more above the smallest are not lowered by one turn',
+    ('trim_cut', 1): 'the trim cuts 2 ring points from each end whenever there are 5 or more (min(2, (n - 3) // 2) dropped)',
+    ('trim_key', 1): 'the trim sorts equal angles by the larger squared distance first',
+    ('carry_half', 1): 'digit carry thresholds 0.5 / 0.5 instead of 0.55 / 0.45',
+    ('inrange_open', 1): 'inRange with exclusive bounds',
 }
 
 
@@ -56,13 +66,29 @@ def load():
     return data
 
 
-def run(data):
-    """-> (lines that differ from the golden stdout, raw records)"""
+def run(data, matched=None):
+    """-> (lines that differ from the golden stdout, raw records).  matched: a dict that the unflipped run fills with every
+    frame's match and matched HLS crop, and from which the run of a DIAL_STAGE switch reads the dials alone (the same record as
+    the whole path gives: nothing before the dial stage looks at such a switch)."""
     bad = 0
     records = []
+    fill = matched is not None and not matched
     for (sd, (params, expected, crops)) in data.items():
+        (th, tw) = params.template_size
         for (name, crop) in crops:
-            res = po.process_crop(crop, params)
+            if matched and not fill:
+                (m, dials) = matched[(sd, name)]
+                if dials is None:
+                    res = m
+                else:
+                    res = po.read_dials(dials, params)
+                    (res.match_x, res.match_y, res.match_val) = (m.match_x, m.match_y, m.match_val)
+            else:
+                res = po.process_crop(crop, params)
+                if fill:
+                    hls = None if res.status == po.DIALS_NOT_FOUND else po.bgr2hls(crop, params.hue_shift)
+                    matched[(sd, name)] = (res, None if hls is None else
+                                           np.ascontiguousarray(hls[res.match_y:res.match_y + th, res.match_x:res.match_x + tw]))
             line = po.output_line(name, res, params).split(': ', 1)[1]
             exp = expected[name]
             if line != exp:
@@ -81,13 +107,14 @@ def audit():
     data = load()
     for name in po.OPTIONS:
         po.set_option(name, 0)
-    (base_bad, base) = run(data)
+    matched = {}
+    (base_bad, base) = run(data, matched)
     assert base_bad == 0, 'the unflipped oracle must reproduce all goldens'
     rows = []
     for (name, value) in VARIANTS:
         po.set_option(name, value)
         try:
-            (bad, recs) = run(data)
+            (bad, recs) = run(data, matched if name in DIAL_STAGE else None)
         finally:
             po.set_option(name, 0)
         changed = sum(1 for (a, b) in zip(base, recs) if a != b)

@@ -208,8 +208,8 @@ int melf_process_frames_dev(melf_ctx* ctx, const void* d_frames, const melf_fram
  * + u_offset / v_offset + (y >> 1) * c_pitch: NV12 W bytes U V U V .. (v_offset == u_offset + 1), I420 W / 2 bytes per plane.
  * YV12 is I420 with the two offsets exchanged.  The buffer must hold every plane of every frame up to the last sample of its
  * last row, and nothing behind that: no load of the kernels reaches past it.  Odd H or W, a pitch or stride too small, a chroma
- * plane that overlaps the Y plane, an unknown format or matrix or a NULL descriptor return MELF_ERR_INVALID before anything is
- * launched or copied. */
+ * plane that overlaps the Y plane or whose last sample lies beyond INT64_MAX, an unknown format or matrix or a NULL descriptor
+ * return MELF_ERR_INVALID before anything is launched or copied. */
 enum { MELF_YUV_NV12 = 0, MELF_YUV_I420 = 1 };
 enum { MELF_YUV_BT601_LIMITED = 0, MELF_YUV_BT601_FULL = 2, MELF_YUV_BT709_LIMITED = 3, MELF_YUV_BT709_FULL = 4 };
                                                 /* matrix; anything else, 1 included: MELF_ERR_INVALID    */

@@ -549,6 +549,44 @@ class YuvPlanarFramesView(NamedTuple):
                                    self.c_pitch, self.u_offset, self.v_offset, self.frame_stride)
 
 
+def _yuv_rows_layout(frames, is_torch, shape, strides, ptr, bps, sx, sy, step, vfirst, fmt, even_words):
+    """Rows of a raw-video (N, rows, W) array of bps-byte samples -> the planar YUV descriptor's numbers (yuv_planar_frames_view: bps 1;
+    yuv16_frames_view: bps 2, sx 1).  strides in bytes; step in samples.  Returns (frames, ptr, n, H, W, y_pitch, c_pitch, u_offset,
+    v_offset, frame_stride, extent, copied), frames and ptr those of the packed copy where the layout could not be described in place.
+    A shape that is not the format's: ValueError."""
+    blocks = (1 << sx) * (1 << sy)                    # pixels per chroma sample: rows = H * (blocks + 2) / blocks
+    bad = len(shape) != 3 or shape[1] == 0 or shape[2] == 0 or (shape[1] * blocks) % (blocks + 2) != 0
+    if not bad:
+        (n, rows, W) = shape
+        H = rows * blocks // (blocks + 2)
+        bad = (sx and W % 2) or (sy and H % 2)
+    if bad:
+        raise ValueError('%s frames must be (N, H * %d // %d, W)%s, not %s' % (fmt, blocks + 2, blocks, even_words, shape))
+    (fs, rp, es) = strides
+    (row, cw, ch) = (W * bps, (W >> sx) * step * bps, H >> sy)   # bytes of a Y row, of a chroma row (semi-planar: of both), chroma rows
+    if W == 1:
+        es = bps
+    if n == 1:
+        fs = rows * rp if rp > 0 else 0
+    whole_rows = cw == row                            # a chroma row is one row of the array: padded rows can be described
+    whole_samples = rp % bps == 0 and fs % bps == 0 and ptr % bps == 0   # odd byte strides or an odd base cannot be described
+    ok = es == bps and whole_samples and row <= rp <= 2 ** 31 - 1 and fs >= (rows - 1) * rp + row and (whole_rows or rp == row)
+    if not ok:
+        (frames, ptr) = _packed_copy(frames, is_torch)
+        (rp, fs) = (row, rows * row)
+    c_pitch = rp if whole_rows else cw
+    first = H * rp
+    if step == 2:
+        (u_off, v_off) = (first + bps, first) if vfirst else (first, first + bps)
+        last = first + (ch - 1) * c_pitch + cw
+    else:
+        second = first + ch * c_pitch
+        (u_off, v_off) = (second, first) if vfirst else (first, second)
+        last = second + (ch - 1) * c_pitch + cw
+    extent = (n - 1) * fs + last if n else 0
+    return (frames, int(ptr), n, H, W, int(rp), int(c_pitch), int(u_off), int(v_off), int(fs), int(extent), not ok)
+
+
 def yuv_planar_frames_view(frames, pixel_format='i422', matrix='bt601'):
     """Describes the raw-video (N, rows, W) uint8 array of planar / semi-planar YUV frames (numpy array or torch tensor) as
     melf_process_yuv_planar* read it.  pixel_format, a name of YUV_PLANAR_FORMATS: 4:2:2 'i422' (yuv422p / yuvj422p), 'yv16', 'nv16',
@@ -590,38 +628,9 @@ def yuv_planar_frames_view(frames, pixel_format='i422', matrix='bt601'):
         extent = (n - 1) * fs + 2 * ps + span if n else 0
         return YuvPlanarFramesView(int(ptr), on_device, device, n, H, W, 0, 0, 1, int(rp), int(rp), int(u_off), int(v_off), int(fs),
                                    int(extent), not ok, frames, mcode)
-    blocks = (1 << sx) * (1 << sy)                    # pixels per chroma sample: rows = H * (blocks + 2) / blocks
-    bad = len(shape) != 3 or shape[1] == 0 or shape[2] == 0 or (shape[1] * blocks) % (blocks + 2) != 0
-    if not bad:
-        (n, rows, W) = shape
-        H = rows * blocks // (blocks + 2)
-        bad = (sx and W % 2) or (sy and H % 2)
-    if bad:
-        raise ValueError('%s frames must be (N, H * %d // %d, W)%s, not %s'
-                         % (fmt, blocks + 2, blocks, ' with an even W' * sx + ' with an even H' * sy, shape))
-    (fs, rp, es) = strides
-    (cw, ch) = ((W >> sx) * step, H >> sy)            # bytes of a chroma row (semi-planar: of both), chroma rows
-    if W == 1:
-        es = 1
-    if n == 1:
-        fs = rows * rp if rp > 0 else 0
-    whole_rows = cw == W                              # a chroma row is one row of the array: padded rows can be described
-    ok = es == 1 and W <= rp <= 2 ** 31 - 1 and fs >= (rows - 1) * rp + W and (whole_rows or rp == W)
-    if not ok:
-        (frames, ptr) = _packed_copy(frames, is_torch)
-        (rp, fs) = (W, rows * W)
-    c_pitch = rp if whole_rows else cw
-    first = H * rp
-    if step == 2:
-        (u_off, v_off) = (first + 1, first) if vfirst else (first, first + 1)
-        last = first + (ch - 1) * c_pitch + cw
-    else:
-        second = first + ch * c_pitch
-        (u_off, v_off) = (second, first) if vfirst else (first, second)
-        last = second + (ch - 1) * c_pitch + cw
-    extent = (n - 1) * fs + last if n else 0
-    return YuvPlanarFramesView(int(ptr), on_device, device, n, H, W, sx, sy, step, int(rp), int(c_pitch), int(u_off), int(v_off), int(fs),
-                               int(extent), not ok, frames, mcode)
+    (frames, ptr, n, H, W, rp, c_pitch, u_off, v_off, fs, extent, copied) = _yuv_rows_layout(
+        frames, is_torch, shape, strides, ptr, 1, sx, sy, step, vfirst, fmt, ' with an even W' * sx + ' with an even H' * sy)
+    return YuvPlanarFramesView(ptr, on_device, device, n, H, W, sx, sy, step, rp, c_pitch, u_off, v_off, fs, extent, copied, frames, mcode)
 
 
 class Yuv16FramesView(NamedTuple):
@@ -688,37 +697,9 @@ def yuv16_frames_view(frames, pixel_format, matrix):
     if fmt not in YUV16_FORMATS:
         raise ValueError('pixel_format %r is not a 16-bit planar / semi-planar YUV layout (%s)' % (pixel_format, ', '.join(YUV16_FORMATS)))
     (sy, step, vfirst, shift) = YUV16_FORMATS[fmt]
-    blocks = 2 << sy                                  # pixels per chroma sample: rows = H * (blocks + 2) / blocks
-    bad = len(shape) != 3 or shape[1] == 0 or shape[2] == 0 or (shape[1] * blocks) % (blocks + 2) != 0
-    if not bad:
-        (n, rows, W) = shape
-        H = rows * blocks // (blocks + 2)
-        bad = W % 2 or (sy and H % 2)
-    if bad:
-        raise ValueError('%s frames must be (N, H * %d // %d, W) with an even W%s, not %s'
-                         % (fmt, blocks + 2, blocks, ' and an even H' * sy, shape))
-    (fs, rp, es) = strides
-    (cw, ch) = ((W >> 1) * step * 2, H >> sy)         # bytes of a chroma row (semi-planar: of both), chroma rows
-    if n == 1:
-        fs = rows * rp if rp > 0 else 0
-    whole_rows = step == 2                            # a chroma row is one row of the array: padded rows can be described
-    even = rp % 2 == 0 and fs % 2 == 0 and ptr % 2 == 0     # whole samples: odd byte strides or an odd base cannot be described
-    ok = es == 2 and even and 2 * W <= rp <= 2 ** 31 - 1 and fs >= (rows - 1) * rp + 2 * W and (whole_rows or rp == 2 * W)
-    if not ok:
-        (frames, ptr) = _packed_copy(frames, is_torch)
-        (rp, fs) = (2 * W, rows * 2 * W)
-    c_pitch = rp if whole_rows else cw
-    first = H * rp
-    if step == 2:
-        (u_off, v_off) = (first + 2, first) if vfirst else (first, first + 2)
-        last = first + (ch - 1) * c_pitch + cw
-    else:
-        second = first + ch * c_pitch
-        (u_off, v_off) = (second, first) if vfirst else (first, second)
-        last = second + (ch - 1) * c_pitch + cw
-    extent = (n - 1) * fs + last if n else 0
-    return Yuv16FramesView(int(ptr), on_device, device, n, H, W, sy, step, shift, int(rp), int(c_pitch), int(u_off), int(v_off), int(fs),
-                           int(extent), not ok, frames, mcode)
+    (frames, ptr, n, H, W, rp, c_pitch, u_off, v_off, fs, extent, copied) = _yuv_rows_layout(
+        frames, is_torch, shape, strides, ptr, 2, 1, sy, step, vfirst, fmt, ' with an even W' + ' and an even H' * sy)
+    return Yuv16FramesView(ptr, on_device, device, n, H, W, sy, step, shift, rp, c_pitch, u_off, v_off, fs, extent, copied, frames, mcode)
 
 
 class PlanarFramesView(NamedTuple):

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "melf_device.h"
+#include "melf_frame_checks.h"
 #include "melf_internal.h"
 #include "melf_threads.h"
 
@@ -1139,20 +1140,6 @@ static int run_match_impl(melf_ctx* c, const MatchSrc& ms, const FrameLayout& la
 // ------------------------------------------------------------ full path ----
 static const int MAX_FRAMES_PER_LAUNCH = 32768;
 
-// A batch of frames as an entry point's checks leave it: n frames of H x W pixels, frame_stride bytes apart, their rows (of the
-// packed pixels, of the Y plane, of every plane) row_stride bytes apart, everything else in the layout
-struct FrameBatch {
-    int n, H, W;
-    size_t frame_stride;
-    int row_stride;
-    FrameLayout lay;
-};
-// packed BGR frames with packed rows: melf_process_batch*, melf_process_stream_dev, the decoded JPEG frames
-static FrameBatch bgr_batch(int n, int H, int W, size_t frame_stride)
-{
-    return FrameBatch{n, H, W, frame_stride, W * 3, FrameLayout::packed(MELF_PIX_BGR, (size_t)H * W * 3)};
-}
-
 // The meter crop of H x W frames: r = {x0, y0, x1, y1} (NULL: the context's meter_rect) clamped to the frame as numpy slicing
 // img[y0:y1, x0:x1] clamps (meterelf/_image.py:54-55)
 struct Crop {
@@ -1178,196 +1165,12 @@ static int process_batch_on(melf_ctx* c, const void* d_frames, const FrameBatch&
 // the entry points on frames in HBM after their argument checks: the lane logic
 static int batch_dev(melf_ctx* c, const void* d_frames, const FrameBatch& b, void* d_results, melf_result* out_host, void* stream_);
 
-// The five descriptor checks (the C ABI's melf_*_frames): every entry point that takes the descriptor starts with its check, which
-// leaves the batch in *b; n == 0 passes whatever the frames pointer.
-
-// melf_frames (melf_process_frames*)
-static int check_frames(const melf_ctx* c, const void* frames, const melf_frames* f, FrameBatch* b)
+// The descriptor checks (melf_frame_checks.h) as every entry point that takes a descriptor starts with them: the context first, then
+// the check's message; the check leaves the batch in *b, and n == 0 passes whatever the frames pointer.
+static int checked(const melf_ctx* c, const char* msg)
 {
     if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    if (!f) return fail(MELF_ERR_INVALID, "frame descriptor is NULL");
-    if (f->pixel_format < MELF_PIX_BGR || f->pixel_format > MELF_PIX_RGBA) return fail(MELF_ERR_INVALID, "unknown pixel_format");
-    if (f->n < 0 || f->H <= 0 || f->W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
-    const int64_t bpp = pix_bytes(f->pixel_format);
-    if (f->row_pitch < (int64_t)f->W * bpp) return fail(MELF_ERR_INVALID, "row_pitch smaller than a row");
-    if (f->row_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "row_pitch too large");
-    const int64_t extent = (int64_t)(f->H - 1) * f->row_pitch + (int64_t)f->W * bpp;   // the last row of a pitched buffer needs no padding
-    if (f->frame_stride < extent) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
-    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch, FrameLayout::packed(f->pixel_format, (size_t)extent)};
-    if (f->n == 0) return MELF_SUCCESS;
-    if (!frames) return fail(MELF_ERR_INVALID, "frames pointer is NULL");
-    if (bpp == 4 && (((uintptr_t)frames | (uint64_t)f->row_pitch | (uint64_t)f->frame_stride) & 3))
-        return fail(MELF_ERR_INVALID, "4-byte pixel formats need a 4-byte aligned base, row_pitch and frame_stride");
-    return MELF_SUCCESS;
-}
-
-// melf_yuv_frames (melf_process_yuv*, melf_yuv_to_bgr): base, frame_stride and row_stride describe the Y plane; the extent reaches
-// to the last sample of the frame's last plane
-static int check_yuv(const melf_ctx* c, const void* frames, const melf_yuv_frames* f, FrameBatch* b)
-{
-    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    if (!f) return fail(MELF_ERR_INVALID, "YUV frame descriptor is NULL");
-    if (f->format != MELF_YUV_NV12 && f->format != MELF_YUV_I420) return fail(MELF_ERR_INVALID, "unknown YUV format");
-    const YuvMatrix* mx = yuv_matrix(f->matrix);
-    if (!mx)
-        return fail(MELF_ERR_INVALID, "unknown YUV matrix (accepted: 0 BT.601 limited, 2 BT.601 full, 3 BT.709 limited, 4 BT.709 full)");
-    if (f->n < 0 || f->H <= 0 || f->W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
-    if ((f->H | f->W) & 1) return fail(MELF_ERR_INVALID, "YUV 4:2:0 frames need an even height and width");
-    if (f->H > 131070) return fail(MELF_ERR_INVALID, "frame too high");
-    const bool nv12 = f->format == MELF_YUV_NV12;
-    const int64_t cw = nv12 ? f->W : f->W / 2;   // bytes of a chroma row
-    if (f->y_pitch < f->W || f->y_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "y_pitch smaller than a row (or too large)");
-    if (f->c_pitch < cw || f->c_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "c_pitch smaller than a chroma row (or too large)");
-    const int64_t y_end = (int64_t)(f->H - 1) * f->y_pitch + f->W;
-    const int64_t c_len = (int64_t)(f->H / 2 - 1) * f->c_pitch + (nv12 ? cw - 1 : cw);   // samples of one of U, V from its offset
-    if (f->u_offset < y_end || f->v_offset < y_end) return fail(MELF_ERR_INVALID, "a chroma plane overlaps the Y plane");
-    if (nv12 && (f->v_offset != f->u_offset + 1 || (f->u_offset & 1)))
-        return fail(MELF_ERR_INVALID, "NV12 needs v_offset == u_offset + 1 and an even u_offset");
-    const int64_t c_end = (f->u_offset > f->v_offset ? f->u_offset : f->v_offset) + c_len;
-    if (f->frame_stride < c_end) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
-    const YuvPlanes yp = {f->u_offset, f->v_offset, (int)f->c_pitch, 0};
-    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->y_pitch,
-                    FrameLayout::yuv420(nv12 ? PIX_NV12 : PIX_I420, yp, *mx, (size_t)c_end)};
-    if (f->n == 0) return MELF_SUCCESS;
-    if (!frames) return fail(MELF_ERR_INVALID, "frames pointer is NULL");
-    return MELF_SUCCESS;
-}
-
-// melf_yuv422_frames (melf_process_yuv422*, melf_yuv422_to_bgr)
-static int check_yuv422(const melf_ctx* c, const void* frames, const melf_yuv422_frames* f, FrameBatch* b)
-{
-    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    if (!f) return fail(MELF_ERR_INVALID, "YUV 4:2:2 frame descriptor is NULL");
-    if (f->format != MELF_YUV422_YUYV && f->format != MELF_YUV422_UYVY && f->format != MELF_YUV422_YVYU)
-        return fail(MELF_ERR_INVALID, "unknown YUV 4:2:2 format");
-    const YuvMatrix* mx = yuv_matrix(f->matrix);
-    if (!mx)
-        return fail(MELF_ERR_INVALID, "unknown YUV matrix (accepted: 0 BT.601 limited, 2 BT.601 full, 3 BT.709 limited, 4 BT.709 full)");
-    if (f->n < 0 || f->H <= 0 || f->W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
-    if (f->W & 1) return fail(MELF_ERR_INVALID, "YUV 4:2:2 frames need an even width");
-    if (f->row_pitch < (int64_t)f->W * 2) return fail(MELF_ERR_INVALID, "row_pitch smaller than a row");
-    if (f->row_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "row_pitch too large");
-    const int64_t extent = (int64_t)(f->H - 1) * f->row_pitch + (int64_t)f->W * 2;
-    if (f->frame_stride < extent) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
-    if (((uint64_t)f->row_pitch | (uint64_t)f->frame_stride) & 3)
-        return fail(MELF_ERR_INVALID, "YUV 4:2:2 frames need a 4-byte aligned row_pitch and frame_stride");
-    const int pix = f->format == MELF_YUV422_UYVY ? PIX_UYVY : (f->format == MELF_YUV422_YVYU ? PIX_YVYU : PIX_YUYV);
-    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch, FrameLayout::yuv422(pix, *mx, (size_t)extent)};
-    if (f->n == 0) return MELF_SUCCESS;
-    if (!frames) return fail(MELF_ERR_INVALID, "frames pointer is NULL");
-    if ((uintptr_t)frames & 3) return fail(MELF_ERR_INVALID, "YUV 4:2:2 frames need a 4-byte aligned base");
-    return MELF_SUCCESS;
-}
-
-// melf_yuv_planar_frames (melf_process_yuv_planar*, melf_yuv_planar_to_bgr): base, frame_stride and row_stride describe the Y plane;
-// the extent reaches to the last sample of the frame's last plane
-static int check_yuv_planar(const melf_ctx* c, const void* frames, const melf_yuv_planar_frames* f, FrameBatch* b)
-{
-    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    if (!f) return fail(MELF_ERR_INVALID, "planar YUV frame descriptor is NULL");
-    if (f->reserved != 0) return fail(MELF_ERR_INVALID, "reserved field of the planar YUV frame descriptor is not 0");
-    if ((f->sub_x != 0 && f->sub_x != 1) || (f->sub_y != 0 && f->sub_y != 1))
-        return fail(MELF_ERR_INVALID, "sub_x and sub_y must be 0 or 1 (log2 of the chroma subsampling)");
-    if (f->c_step != 1 && f->c_step != 2) return fail(MELF_ERR_INVALID, "c_step must be 1 (planar) or 2 (semi-planar)");
-    const YuvMatrix* mx = yuv_matrix(f->matrix);
-    if (!mx)
-        return fail(MELF_ERR_INVALID, "unknown YUV matrix (accepted: 0 BT.601 limited, 2 BT.601 full, 3 BT.709 limited, 4 BT.709 full)");
-    if (f->n < 0 || f->H <= 0 || f->W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
-    if (f->sub_x && (f->W & 1)) return fail(MELF_ERR_INVALID, "horizontally subsampled chroma (sub_x) needs an even width");
-    if (f->sub_y && (f->H & 1)) return fail(MELF_ERR_INVALID, "vertically subsampled chroma (sub_y) needs an even height");
-    if (f->u_offset < 0 || f->v_offset < 0) return fail(MELF_ERR_INVALID, "negative chroma offset");
-    const bool semi = f->c_step == 2;
-    if (semi && f->u_offset - f->v_offset != 1 && f->v_offset - f->u_offset != 1)
-        return fail(MELF_ERR_INVALID, "c_step 2 (semi-planar) needs adjacent u_offset and v_offset");
-    if (f->y_pitch < f->W || f->y_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "y_pitch smaller than a row (or too large)");
-    const int64_t cw = (int64_t)(f->W >> f->sub_x) * f->c_step, ch = f->H >> f->sub_y;   // bytes of a chroma row (semi-planar: of both), rows
-    if (f->c_pitch < cw || f->c_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "c_pitch smaller than a chroma row (or too large)");
-    const int64_t y_end = (int64_t)(f->H - 1) * f->y_pitch + f->W;
-    const int64_t c_lo = f->u_offset < f->v_offset ? f->u_offset : f->v_offset, c_hi = f->u_offset < f->v_offset ? f->v_offset : f->u_offset;
-    const int64_t c_len = (ch - 1) * f->c_pitch + (semi ? cw - 1 : cw);   // bytes from a plane's offset to its last sample
-    if (c_hi > INT64_MAX - c_len) return fail(MELF_ERR_INVALID, "chroma offset too large");
-    // (by spans, first to last sample: chroma kept inside the Y rows' padding, or U and V rows side by side in one pitch, do not
-    // overlap sample by sample but are not taken -- the header states the span rule)
-    if (c_lo < y_end) return fail(MELF_ERR_INVALID, "a chroma offset lies inside the Y plane's span (first to last sample): spans may not overlap");
-    if (!semi && c_hi - c_lo < c_len)
-        return fail(MELF_ERR_INVALID, "the spans (first to last sample) of the two chroma planes overlap: U and V rows sharing one pitch are not taken");
-    const int64_t c_end = c_hi + c_len;
-    if (f->frame_stride < c_end) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
-    const YuvPlanarPlanes yp = {f->u_offset, f->v_offset, (int)f->c_pitch, f->sub_x, f->sub_y, f->c_step};
-    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->y_pitch, FrameLayout::yuv_planar(yp, *mx, (size_t)c_end)};
-    if (f->n == 0) return MELF_SUCCESS;
-    if (!frames) return fail(MELF_ERR_INVALID, "frames pointer is NULL");
-    return MELF_SUCCESS;
-}
-
-// melf_yuv16_frames (melf_process_yuv16*, melf_yuv16_to_bgr): check_yuv_planar's cases for sub_x 1, restated in bytes and samples of
-// 2 bytes; base, frame_stride and row_stride (bytes) describe the Y plane; the extent reaches to the last sample of the last plane
-static int check_yuv16(const melf_ctx* c, const void* frames, const melf_yuv16_frames* f, FrameBatch* b)
-{
-    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    if (!f) return fail(MELF_ERR_INVALID, "16-bit YUV frame descriptor is NULL");
-    if (f->reserved != 0) return fail(MELF_ERR_INVALID, "reserved field of the 16-bit YUV frame descriptor is not 0");
-    if (f->sub_y != 0 && f->sub_y != 1) return fail(MELF_ERR_INVALID, "sub_y must be 0 or 1 (log2 of the vertical chroma subsampling)");
-    if (f->c_step != 1 && f->c_step != 2) return fail(MELF_ERR_INVALID, "c_step must be 1 (planar) or 2 (semi-planar) samples");
-    if (f->shift < 0 || f->shift > 8) return fail(MELF_ERR_INVALID, "shift must be 0 .. 8 (low bits dropped from a 16-bit sample)");
-    const YuvMatrix* mx = yuv_matrix(f->matrix);
-    if (!mx)
-        return fail(MELF_ERR_INVALID, "unknown YUV matrix (accepted: 0 BT.601 limited, 2 BT.601 full, 3 BT.709 limited, 4 BT.709 full)");
-    if (f->n < 0 || f->H <= 0 || f->W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
-    if (f->W & 1) return fail(MELF_ERR_INVALID, "horizontally subsampled chroma needs an even width");
-    if (f->sub_y && (f->H & 1)) return fail(MELF_ERR_INVALID, "vertically subsampled chroma (sub_y) needs an even height");
-    if (f->u_offset < 0 || f->v_offset < 0) return fail(MELF_ERR_INVALID, "negative chroma offset");
-    if ((f->y_pitch | f->c_pitch | f->u_offset | f->v_offset | f->frame_stride) & 1)
-        return fail(MELF_ERR_INVALID, "16-bit samples need an even y_pitch, c_pitch, u_offset, v_offset and frame_stride (bytes)");
-    const bool semi = f->c_step == 2;
-    if (semi && f->u_offset - f->v_offset != 2 && f->v_offset - f->u_offset != 2)
-        return fail(MELF_ERR_INVALID, "c_step 2 (semi-planar) needs u_offset and v_offset 2 bytes apart");
-    if (f->y_pitch < (int64_t)f->W * 2 || f->y_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "y_pitch smaller than a row of 2-byte samples (or too large)");
-    const int64_t cw = (int64_t)(f->W >> 1) * f->c_step * 2, ch = f->H >> f->sub_y;   // bytes of a chroma row (semi-planar: of both), rows
-    if (f->c_pitch < cw || f->c_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "c_pitch smaller than a chroma row of 2-byte samples (or too large)");
-    const int64_t y_end = (int64_t)(f->H - 1) * f->y_pitch + (int64_t)f->W * 2;
-    const int64_t c_lo = f->u_offset < f->v_offset ? f->u_offset : f->v_offset, c_hi = f->u_offset < f->v_offset ? f->v_offset : f->u_offset;
-    const int64_t c_len = (ch - 1) * f->c_pitch + (semi ? cw - 2 : cw);   // bytes from a plane's offset to the end of its last sample
-    if (c_hi > INT64_MAX - c_len) return fail(MELF_ERR_INVALID, "chroma offset too large");
-    if (c_lo < y_end) return fail(MELF_ERR_INVALID, "a chroma offset lies inside the Y plane's span (first to last sample): spans may not overlap");
-    if (!semi && c_hi - c_lo < c_len)
-        return fail(MELF_ERR_INVALID, "the spans (first to last sample) of the two chroma planes overlap: U and V rows sharing one pitch are not taken");
-    const int64_t c_end = c_hi + c_len;
-    if (f->frame_stride < c_end) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
-    const Yuv16Planes yp = {f->u_offset, f->v_offset, (int)f->c_pitch, f->sub_y, f->c_step, f->shift};
-    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->y_pitch, FrameLayout::yuv16(yp, *mx, (size_t)c_end)};
-    if (f->n == 0) return MELF_SUCCESS;
-    if (!frames) return fail(MELF_ERR_INVALID, "frames pointer is NULL");
-    if ((uintptr_t)frames & 1) return fail(MELF_ERR_INVALID, "16-bit samples need a 2-byte aligned base");
-    return MELF_SUCCESS;
-}
-
-// melf_planar_frames (melf_process_planes*): the extent reaches to the last sample of the frame's last plane
-static int check_planes(const melf_ctx* c, const void* frames, const melf_planar_frames* f, FrameBatch* b)
-{
-    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    if (!f) return fail(MELF_ERR_INVALID, "planar frame descriptor is NULL");
-    if (f->n < 0 || f->H <= 0 || f->W <= 0) return fail(MELF_ERR_INVALID, "bad batch shape");
-    if (f->reserved != 0) return fail(MELF_ERR_INVALID, "reserved field of the planar frame descriptor is not 0");
-    if (f->b_offset < 0 || f->g_offset < 0 || f->r_offset < 0) return fail(MELF_ERR_INVALID, "negative plane offset");
-    if (f->row_pitch < f->W) return fail(MELF_ERR_INVALID, "row_pitch smaller than a row");
-    if (f->row_pitch > INT32_MAX) return fail(MELF_ERR_INVALID, "row_pitch too large");
-    const int64_t span = (int64_t)(f->H - 1) * f->row_pitch + f->W;   // bytes of one plane, first to last sample
-    const int64_t off[3] = {f->b_offset, f->g_offset, f->r_offset};
-    int64_t hi = 0;
-    for (int a = 0; a < 3; ++a) {
-        if (off[a] > INT64_MAX - span) return fail(MELF_ERR_INVALID, "plane offset too large");
-        if (off[a] > hi) hi = off[a];
-        for (int k = a + 1; k < 3; ++k) {
-            const int64_t lo2 = off[a] < off[k] ? off[a] : off[k], hi2 = off[a] < off[k] ? off[k] : off[a];
-            if (hi2 - lo2 < span) return fail(MELF_ERR_INVALID, "two planes overlap");
-        }
-    }
-    if (f->frame_stride < hi + span) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
-    const PlanarPlanes pl = {f->b_offset, f->g_offset, f->r_offset};
-    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch, FrameLayout::planar(pl, (size_t)(hi + span))};
-    if (f->n == 0) return MELF_SUCCESS;
-    if (!frames) return fail(MELF_ERR_INVALID, "frames pointer is NULL");
+    if (msg) return fail(MELF_ERR_INVALID, msg);
     return MELF_SUCCESS;
 }
 
@@ -1386,7 +1189,7 @@ extern "C" int melf_process_frames_dev(melf_ctx* c, const void* d_frames, const 
                                        void* stream_)
 {
     FrameBatch b;
-    if (int rc = check_frames(c, d_frames, f, &b)) return rc;
+    if (int rc = checked(c, check_frames(d_frames, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return batch_dev(c, d_frames, b, d_results, out_host, stream_);
 }
@@ -1395,7 +1198,7 @@ extern "C" int melf_process_yuv_dev(melf_ctx* c, const void* d_frames, const mel
                                     void* stream_)
 {
     FrameBatch b;
-    if (int rc = check_yuv(c, d_frames, f, &b)) return rc;
+    if (int rc = checked(c, check_yuv(d_frames, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return batch_dev(c, d_frames, b, d_results, out_host, stream_);
 }
@@ -1404,7 +1207,7 @@ extern "C" int melf_process_yuv422_dev(melf_ctx* c, const void* d_frames, const 
                                        melf_result* out_host, void* stream_)
 {
     FrameBatch b;
-    if (int rc = check_yuv422(c, d_frames, f, &b)) return rc;
+    if (int rc = checked(c, check_yuv422(d_frames, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return batch_dev(c, d_frames, b, d_results, out_host, stream_);
 }
@@ -1413,7 +1216,7 @@ extern "C" int melf_process_yuv_planar_dev(melf_ctx* c, const void* d_frames, co
                                            melf_result* out_host, void* stream_)
 {
     FrameBatch b;
-    if (int rc = check_yuv_planar(c, d_frames, f, &b)) return rc;
+    if (int rc = checked(c, check_yuv_planar(d_frames, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return batch_dev(c, d_frames, b, d_results, out_host, stream_);
 }
@@ -1422,7 +1225,7 @@ extern "C" int melf_process_yuv16_dev(melf_ctx* c, const void* d_frames, const m
                                       melf_result* out_host, void* stream_)
 {
     FrameBatch b;
-    if (int rc = check_yuv16(c, d_frames, f, &b)) return rc;
+    if (int rc = checked(c, check_yuv16(d_frames, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return batch_dev(c, d_frames, b, d_results, out_host, stream_);
 }
@@ -1431,7 +1234,7 @@ extern "C" int melf_process_planes_dev(melf_ctx* c, const void* d_frames, const 
                                        melf_result* out_host, void* stream_)
 {
     FrameBatch b;
-    if (int rc = check_planes(c, d_frames, f, &b)) return rc;
+    if (int rc = checked(c, check_planes(d_frames, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return batch_dev(c, d_frames, b, d_results, out_host, stream_);
 }
@@ -1841,7 +1644,7 @@ extern "C" int melf_process_batch(melf_ctx* c, const uint8_t* frames_host, int n
 extern "C" int melf_process_frames(melf_ctx* c, const void* frames_host, const melf_frames* f, melf_result* out_host)
 {
     FrameBatch b;
-    if (int rc = check_frames(c, frames_host, f, &b)) return rc;
+    if (int rc = checked(c, check_frames(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return host_packed(c, (const uint8_t*)frames_host, b, out_host);
 }
@@ -1849,7 +1652,7 @@ extern "C" int melf_process_frames(melf_ctx* c, const void* frames_host, const m
 extern "C" int melf_process_yuv(melf_ctx* c, const void* frames_host, const melf_yuv_frames* f, melf_result* out_host)
 {
     FrameBatch b;
-    if (int rc = check_yuv(c, frames_host, f, &b)) return rc;
+    if (int rc = checked(c, check_yuv(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return host_yuv(c, (const uint8_t*)frames_host, b, out_host);
 }
@@ -1857,7 +1660,7 @@ extern "C" int melf_process_yuv(melf_ctx* c, const void* frames_host, const melf
 extern "C" int melf_process_yuv422(melf_ctx* c, const void* frames_host, const melf_yuv422_frames* f, melf_result* out_host)
 {
     FrameBatch b;
-    if (int rc = check_yuv422(c, frames_host, f, &b)) return rc;
+    if (int rc = checked(c, check_yuv422(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return host_p422(c, (const uint8_t*)frames_host, b, out_host);
 }
@@ -1865,7 +1668,7 @@ extern "C" int melf_process_yuv422(melf_ctx* c, const void* frames_host, const m
 extern "C" int melf_process_yuv_planar(melf_ctx* c, const void* frames_host, const melf_yuv_planar_frames* f, melf_result* out_host)
 {
     FrameBatch b;
-    if (int rc = check_yuv_planar(c, frames_host, f, &b)) return rc;
+    if (int rc = checked(c, check_yuv_planar(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return host_yuv_planar(c, (const uint8_t*)frames_host, b, out_host);
 }
@@ -1873,7 +1676,7 @@ extern "C" int melf_process_yuv_planar(melf_ctx* c, const void* frames_host, con
 extern "C" int melf_process_yuv16(melf_ctx* c, const void* frames_host, const melf_yuv16_frames* f, melf_result* out_host)
 {
     FrameBatch b;
-    if (int rc = check_yuv16(c, frames_host, f, &b)) return rc;
+    if (int rc = checked(c, check_yuv16(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return host_yuv16(c, (const uint8_t*)frames_host, b, out_host);
 }
@@ -1881,7 +1684,7 @@ extern "C" int melf_process_yuv16(melf_ctx* c, const void* frames_host, const me
 extern "C" int melf_process_planes(melf_ctx* c, const void* frames_host, const melf_planar_frames* f, melf_result* out_host)
 {
     FrameBatch b;
-    if (int rc = check_planes(c, frames_host, f, &b)) return rc;
+    if (int rc = checked(c, check_planes(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return host_planes(c, (const uint8_t*)frames_host, b, out_host);
 }
@@ -1913,7 +1716,7 @@ static int to_bgr(melf_ctx* c, const void* frames_host, const FrameBatch& b, uin
 extern "C" int melf_yuv422_to_bgr(melf_ctx* c, const void* frames_host, const melf_yuv422_frames* f, uint8_t* bgr_out_host)
 {
     FrameBatch b;
-    if (int rc = check_yuv422(c, frames_host, f, &b)) return rc;
+    if (int rc = checked(c, check_yuv422(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return to_bgr(c, frames_host, b, bgr_out_host);
 }
@@ -1921,7 +1724,7 @@ extern "C" int melf_yuv422_to_bgr(melf_ctx* c, const void* frames_host, const me
 extern "C" int melf_yuv_planar_to_bgr(melf_ctx* c, const void* frames_host, const melf_yuv_planar_frames* f, uint8_t* bgr_out_host)
 {
     FrameBatch b;
-    if (int rc = check_yuv_planar(c, frames_host, f, &b)) return rc;
+    if (int rc = checked(c, check_yuv_planar(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return to_bgr(c, frames_host, b, bgr_out_host);
 }
@@ -1929,7 +1732,7 @@ extern "C" int melf_yuv_planar_to_bgr(melf_ctx* c, const void* frames_host, cons
 extern "C" int melf_yuv16_to_bgr(melf_ctx* c, const void* frames_host, const melf_yuv16_frames* f, uint8_t* bgr_out_host)
 {
     FrameBatch b;
-    if (int rc = check_yuv16(c, frames_host, f, &b)) return rc;
+    if (int rc = checked(c, check_yuv16(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return to_bgr(c, frames_host, b, bgr_out_host);
 }
@@ -1937,7 +1740,7 @@ extern "C" int melf_yuv16_to_bgr(melf_ctx* c, const void* frames_host, const mel
 extern "C" int melf_yuv_to_bgr(melf_ctx* c, const void* frames_host, const melf_yuv_frames* f, uint8_t* bgr_out_host)
 {
     FrameBatch b;
-    if (int rc = check_yuv(c, frames_host, f, &b)) return rc;
+    if (int rc = checked(c, check_yuv(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return to_bgr(c, frames_host, b, bgr_out_host);
 }

@@ -1,0 +1,230 @@
+// The descriptor checks of the C ABI's melf_*_frames: every entry point that takes a descriptor starts with its check, which decides
+// what layouts are taken and leaves the batch -- with FrameLayout::extent, which becomes MatchSrc::readable / DialsSrc::readable -- in
+// *b.  Pure functions of the frames pointer (its NULL and alignment rules only) and the descriptor: no context, no HIP, nothing
+// global.  They return the error message, or nullptr when the descriptor is taken; n == 0 passes whatever the frames pointer.
+// melf_api.hip reports the message through fail(MELF_ERR_INVALID, ..); tests/frame_checks_main.cpp sweeps the checks on the CPU, and
+// the bounds programs beside it allocate what the checks accept.
+#pragma once
+#include "melf_frame_layout.h"
+
+namespace melf {
+
+// A batch of frames as an entry point's checks leave it: n frames of H x W pixels, frame_stride bytes apart, their rows (of the
+// packed pixels, of the Y plane, of every plane) row_stride bytes apart, everything else in the layout
+struct FrameBatch {
+    int n, H, W;
+    size_t frame_stride;
+    int row_stride;
+    FrameLayout lay;
+};
+// packed BGR frames with packed rows: melf_process_batch*, melf_process_stream_dev, the decoded JPEG frames
+inline FrameBatch bgr_batch(int n, int H, int W, size_t frame_stride)
+{
+    return FrameBatch{n, H, W, frame_stride, W * 3, FrameLayout::packed(MELF_PIX_BGR, (size_t)H * W * 3)};
+}
+
+// Bytes from a plane's first sample to the end of its last: `rows` rows pitch bytes apart (0 <= pitch <= INT32_MAX), each of
+// `samples` samples of bps bytes, `step` samples from one to the next (2: the other plane's samples lie between them).
+inline int64_t plane_span(int64_t rows, int64_t pitch, int64_t samples, int step, int bps)
+{
+    return (rows - 1) * pitch + ((samples - 1) * step + 1) * bps;
+}
+// The spans of a Y plane at offset 0 and two chroma planes behind it, in bytes of one frame.
+struct YuvSpans {
+    int64_t y_end;       // the Y plane, first to last sample
+    int64_t c_lo, c_hi;  // the lower and the higher of the two chroma offsets
+    int64_t c_len;       // from a chroma plane's offset to the end of its last sample
+    bool fits;           // c_hi + c_len is an int64_t
+    int64_t c_end;       // fits: c_hi + c_len, the extent of a frame
+};
+// (pitches already known to be 0 .. INT32_MAX: no product here leaves 63 bits)
+inline YuvSpans yuv_spans(int H, int W, int64_t y_pitch, int c_rows, int c_samples, int64_t c_pitch, int c_step, int bps, int64_t u_offset,
+                          int64_t v_offset)
+{
+    YuvSpans s;
+    s.y_end = plane_span(H, y_pitch, W, 1, bps);
+    s.c_lo = u_offset < v_offset ? u_offset : v_offset;
+    s.c_hi = u_offset < v_offset ? v_offset : u_offset;
+    s.c_len = plane_span(c_rows, c_pitch, c_samples, c_step, bps);
+    s.fits = s.c_hi <= INT64_MAX - s.c_len;
+    s.c_end = s.fits ? s.c_hi + s.c_len : 0;
+    return s;
+}
+// The span rules of melf_yuv_planar_frames and melf_yuv16_frames (offsets already known to be >= 0).  By spans, first to last
+// sample: chroma kept inside the Y rows' padding, or U and V rows side by side in one pitch, do not overlap sample by sample but are
+// not taken -- the header states the span rule.
+inline const char* yuv_spans_error(const YuvSpans& s, bool semi, int64_t frame_stride)
+{
+    if (!s.fits) return "chroma offset too large";
+    if (s.c_lo < s.y_end) return "a chroma offset lies inside the Y plane's span (first to last sample): spans may not overlap";
+    if (!semi && s.c_hi - s.c_lo < s.c_len)
+        return "the spans (first to last sample) of the two chroma planes overlap: U and V rows sharing one pitch are not taken";
+    if (frame_stride < s.c_end) return "frame_stride smaller than a frame";
+    return nullptr;
+}
+
+constexpr const char* UNKNOWN_YUV_MATRIX = "unknown YUV matrix (accepted: 0 BT.601 limited, 2 BT.601 full, 3 BT.709 limited, 4 BT.709 full)";
+
+// melf_frames (melf_process_frames*)
+inline const char* check_frames(const void* frames, const melf_frames* f, FrameBatch* b)
+{
+    if (!f) return "frame descriptor is NULL";
+    if (f->pixel_format < MELF_PIX_BGR || f->pixel_format > MELF_PIX_RGBA) return "unknown pixel_format";
+    if (f->n < 0 || f->H <= 0 || f->W <= 0) return "bad batch shape";
+    const int64_t bpp = pix_bytes(f->pixel_format);
+    if (f->row_pitch < (int64_t)f->W * bpp) return "row_pitch smaller than a row";
+    if (f->row_pitch > INT32_MAX) return "row_pitch too large";
+    const int64_t extent = plane_span(f->H, f->row_pitch, f->W, 1, (int)bpp);   // the last row of a pitched buffer needs no padding
+    if (f->frame_stride < extent) return "frame_stride smaller than a frame";
+    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch, FrameLayout::packed(f->pixel_format, (size_t)extent)};
+    if (f->n == 0) return nullptr;
+    if (!frames) return "frames pointer is NULL";
+    if (bpp == 4 && (((uintptr_t)frames | (uint64_t)f->row_pitch | (uint64_t)f->frame_stride) & 3))
+        return "4-byte pixel formats need a 4-byte aligned base, row_pitch and frame_stride";
+    return nullptr;
+}
+
+// melf_yuv_frames (melf_process_yuv*, melf_yuv_to_bgr): base, frame_stride and row_stride describe the Y plane; the extent reaches
+// to the last sample of the frame's last plane.  The spans are yuv_spans'; the rules are this descriptor's own: NV12's offsets, the
+// height limit, and no test of I420's U span against its V span.
+inline const char* check_yuv(const void* frames, const melf_yuv_frames* f, FrameBatch* b)
+{
+    if (!f) return "YUV frame descriptor is NULL";
+    if (f->format != MELF_YUV_NV12 && f->format != MELF_YUV_I420) return "unknown YUV format";
+    const YuvMatrix* mx = yuv_matrix(f->matrix);
+    if (!mx) return UNKNOWN_YUV_MATRIX;
+    if (f->n < 0 || f->H <= 0 || f->W <= 0) return "bad batch shape";
+    if ((f->H | f->W) & 1) return "YUV 4:2:0 frames need an even height and width";
+    if (f->H > 131070) return "frame too high";
+    const bool nv12 = f->format == MELF_YUV_NV12;
+    const int64_t cw = nv12 ? f->W : f->W / 2;   // bytes of a chroma row
+    if (f->y_pitch < f->W || f->y_pitch > INT32_MAX) return "y_pitch smaller than a row (or too large)";
+    if (f->c_pitch < cw || f->c_pitch > INT32_MAX) return "c_pitch smaller than a chroma row (or too large)";
+    const YuvSpans s = yuv_spans(f->H, f->W, f->y_pitch, f->H / 2, f->W / 2, f->c_pitch, nv12 ? 2 : 1, 1, f->u_offset, f->v_offset);
+    if (s.c_lo < s.y_end) return "a chroma plane overlaps the Y plane";
+    if (nv12 && (f->v_offset - f->u_offset != 1 || (f->u_offset & 1)))   // (both offsets >= y_end > 0 here: the difference cannot overflow)
+        return "NV12 needs v_offset == u_offset + 1 and an even u_offset";
+    if (!s.fits) return "chroma offset too large";
+    if (f->frame_stride < s.c_end) return "frame_stride smaller than a frame";
+    const YuvPlanes yp = {f->u_offset, f->v_offset, (int)f->c_pitch, 0};
+    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->y_pitch,
+                    FrameLayout::yuv420(nv12 ? PIX_NV12 : PIX_I420, yp, *mx, (size_t)s.c_end)};
+    if (f->n == 0) return nullptr;
+    if (!frames) return "frames pointer is NULL";
+    return nullptr;
+}
+
+// melf_yuv422_frames (melf_process_yuv422*, melf_yuv422_to_bgr)
+inline const char* check_yuv422(const void* frames, const melf_yuv422_frames* f, FrameBatch* b)
+{
+    if (!f) return "YUV 4:2:2 frame descriptor is NULL";
+    if (f->format != MELF_YUV422_YUYV && f->format != MELF_YUV422_UYVY && f->format != MELF_YUV422_YVYU) return "unknown YUV 4:2:2 format";
+    const YuvMatrix* mx = yuv_matrix(f->matrix);
+    if (!mx) return UNKNOWN_YUV_MATRIX;
+    if (f->n < 0 || f->H <= 0 || f->W <= 0) return "bad batch shape";
+    if (f->W & 1) return "YUV 4:2:2 frames need an even width";
+    if (f->row_pitch < (int64_t)f->W * 2) return "row_pitch smaller than a row";
+    if (f->row_pitch > INT32_MAX) return "row_pitch too large";
+    const int64_t extent = plane_span(f->H, f->row_pitch, f->W, 1, 2);
+    if (f->frame_stride < extent) return "frame_stride smaller than a frame";
+    if (((uint64_t)f->row_pitch | (uint64_t)f->frame_stride) & 3) return "YUV 4:2:2 frames need a 4-byte aligned row_pitch and frame_stride";
+    const int pix = f->format == MELF_YUV422_UYVY ? PIX_UYVY : (f->format == MELF_YUV422_YVYU ? PIX_YVYU : PIX_YUYV);
+    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch, FrameLayout::yuv422(pix, *mx, (size_t)extent)};
+    if (f->n == 0) return nullptr;
+    if (!frames) return "frames pointer is NULL";
+    if ((uintptr_t)frames & 3) return "YUV 4:2:2 frames need a 4-byte aligned base";
+    return nullptr;
+}
+
+// melf_yuv_planar_frames (melf_process_yuv_planar*, melf_yuv_planar_to_bgr): base, frame_stride and row_stride describe the Y plane;
+// the extent reaches to the last sample of the frame's last plane
+inline const char* check_yuv_planar(const void* frames, const melf_yuv_planar_frames* f, FrameBatch* b)
+{
+    if (!f) return "planar YUV frame descriptor is NULL";
+    if (f->reserved != 0) return "reserved field of the planar YUV frame descriptor is not 0";
+    if ((f->sub_x != 0 && f->sub_x != 1) || (f->sub_y != 0 && f->sub_y != 1))
+        return "sub_x and sub_y must be 0 or 1 (log2 of the chroma subsampling)";
+    if (f->c_step != 1 && f->c_step != 2) return "c_step must be 1 (planar) or 2 (semi-planar)";
+    const YuvMatrix* mx = yuv_matrix(f->matrix);
+    if (!mx) return UNKNOWN_YUV_MATRIX;
+    if (f->n < 0 || f->H <= 0 || f->W <= 0) return "bad batch shape";
+    if (f->sub_x && (f->W & 1)) return "horizontally subsampled chroma (sub_x) needs an even width";
+    if (f->sub_y && (f->H & 1)) return "vertically subsampled chroma (sub_y) needs an even height";
+    if (f->u_offset < 0 || f->v_offset < 0) return "negative chroma offset";
+    const bool semi = f->c_step == 2;
+    if (semi && f->u_offset - f->v_offset != 1 && f->v_offset - f->u_offset != 1)
+        return "c_step 2 (semi-planar) needs adjacent u_offset and v_offset";
+    if (f->y_pitch < f->W || f->y_pitch > INT32_MAX) return "y_pitch smaller than a row (or too large)";
+    const int cs = f->W >> f->sub_x, ch = f->H >> f->sub_y;   // samples of a chroma plane's row, rows
+    if (f->c_pitch < (int64_t)cs * f->c_step || f->c_pitch > INT32_MAX) return "c_pitch smaller than a chroma row (or too large)";
+    const YuvSpans s = yuv_spans(f->H, f->W, f->y_pitch, ch, cs, f->c_pitch, f->c_step, 1, f->u_offset, f->v_offset);
+    if (const char* msg = yuv_spans_error(s, semi, f->frame_stride)) return msg;
+    const YuvPlanarPlanes yp = {f->u_offset, f->v_offset, (int)f->c_pitch, f->sub_x, f->sub_y, f->c_step};
+    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->y_pitch, FrameLayout::yuv_planar(yp, *mx, (size_t)s.c_end)};
+    if (f->n == 0) return nullptr;
+    if (!frames) return "frames pointer is NULL";
+    return nullptr;
+}
+
+// melf_yuv16_frames (melf_process_yuv16*, melf_yuv16_to_bgr): samples of 2 bytes, sub_x 1; base, frame_stride and row_stride (bytes)
+// describe the Y plane; the extent reaches to the end of the last sample of the frame's last plane
+inline const char* check_yuv16(const void* frames, const melf_yuv16_frames* f, FrameBatch* b)
+{
+    if (!f) return "16-bit YUV frame descriptor is NULL";
+    if (f->reserved != 0) return "reserved field of the 16-bit YUV frame descriptor is not 0";
+    if (f->sub_y != 0 && f->sub_y != 1) return "sub_y must be 0 or 1 (log2 of the vertical chroma subsampling)";
+    if (f->c_step != 1 && f->c_step != 2) return "c_step must be 1 (planar) or 2 (semi-planar) samples";
+    if (f->shift < 0 || f->shift > 8) return "shift must be 0 .. 8 (low bits dropped from a 16-bit sample)";
+    const YuvMatrix* mx = yuv_matrix(f->matrix);
+    if (!mx) return UNKNOWN_YUV_MATRIX;
+    if (f->n < 0 || f->H <= 0 || f->W <= 0) return "bad batch shape";
+    if (f->W & 1) return "horizontally subsampled chroma needs an even width";
+    if (f->sub_y && (f->H & 1)) return "vertically subsampled chroma (sub_y) needs an even height";
+    if (f->u_offset < 0 || f->v_offset < 0) return "negative chroma offset";
+    if ((f->y_pitch | f->c_pitch | f->u_offset | f->v_offset | f->frame_stride) & 1)
+        return "16-bit samples need an even y_pitch, c_pitch, u_offset, v_offset and frame_stride (bytes)";
+    const bool semi = f->c_step == 2;
+    if (semi && f->u_offset - f->v_offset != 2 && f->v_offset - f->u_offset != 2)
+        return "c_step 2 (semi-planar) needs u_offset and v_offset 2 bytes apart";
+    if (f->y_pitch < (int64_t)f->W * 2 || f->y_pitch > INT32_MAX) return "y_pitch smaller than a row of 2-byte samples (or too large)";
+    const int cs = f->W >> 1, ch = f->H >> f->sub_y;   // samples of a chroma plane's row, rows
+    if (f->c_pitch < (int64_t)cs * f->c_step * 2 || f->c_pitch > INT32_MAX) return "c_pitch smaller than a chroma row of 2-byte samples (or too large)";
+    const YuvSpans s = yuv_spans(f->H, f->W, f->y_pitch, ch, cs, f->c_pitch, f->c_step, 2, f->u_offset, f->v_offset);
+    if (const char* msg = yuv_spans_error(s, semi, f->frame_stride)) return msg;
+    const Yuv16Planes yp = {f->u_offset, f->v_offset, (int)f->c_pitch, f->sub_y, f->c_step, f->shift};
+    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->y_pitch, FrameLayout::yuv16(yp, *mx, (size_t)s.c_end)};
+    if (f->n == 0) return nullptr;
+    if (!frames) return "frames pointer is NULL";
+    if ((uintptr_t)frames & 1) return "16-bit samples need a 2-byte aligned base";
+    return nullptr;
+}
+
+// melf_planar_frames (melf_process_planes*): the extent reaches to the last sample of the frame's last plane
+inline const char* check_planes(const void* frames, const melf_planar_frames* f, FrameBatch* b)
+{
+    if (!f) return "planar frame descriptor is NULL";
+    if (f->n < 0 || f->H <= 0 || f->W <= 0) return "bad batch shape";
+    if (f->reserved != 0) return "reserved field of the planar frame descriptor is not 0";
+    if (f->b_offset < 0 || f->g_offset < 0 || f->r_offset < 0) return "negative plane offset";
+    if (f->row_pitch < f->W) return "row_pitch smaller than a row";
+    if (f->row_pitch > INT32_MAX) return "row_pitch too large";
+    const int64_t span = plane_span(f->H, f->row_pitch, f->W, 1, 1);   // bytes of one plane, first to last sample
+    const int64_t off[3] = {f->b_offset, f->g_offset, f->r_offset};
+    int64_t hi = 0;
+    for (int a = 0; a < 3; ++a) {
+        if (off[a] > INT64_MAX - span) return "plane offset too large";
+        if (off[a] > hi) hi = off[a];
+        for (int k = a + 1; k < 3; ++k) {
+            const int64_t lo2 = off[a] < off[k] ? off[a] : off[k], hi2 = off[a] < off[k] ? off[k] : off[a];
+            if (hi2 - lo2 < span) return "two planes overlap";
+        }
+    }
+    if (f->frame_stride < hi + span) return "frame_stride smaller than a frame";
+    const PlanarPlanes pl = {f->b_offset, f->g_offset, f->r_offset};
+    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch, FrameLayout::planar(pl, (size_t)(hi + span))};
+    if (f->n == 0) return nullptr;
+    if (!frames) return "frames pointer is NULL";
+    return nullptr;
+}
+
+}  // namespace melf

@@ -118,6 +118,22 @@ def params_with_rect(tmp_path, sd, rect, tag):
     return _params.load(str(d / 'params.yml'))
 
 
+# ------------------------------------------------------------------------------------------------ stand-alone programs ---
+def build_and_run(tmp_path, cxx, src, name, extra, san):
+    """src as a stand-alone program, plain and under the host sanitizers `san`: both exit 0 and print `failures 0`.  Returns
+    the plain run's output."""
+    out = None
+    for (tag, flags) in (('plain', ['-O2']), ('san', ['-O1', '-g', '-fno-sanitize-recover=all'] + san)):
+        exe = str(tmp_path / (name + '_' + tag))
+        subprocess.check_call([cxx, '-std=c++17', '-Wall', '-Werror'] + extra + flags + ['-o', exe, src])
+        p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+        assert p.returncode == 0, (tag, p.stdout[-2000:], p.stderr[-4000:])
+        assert b'failures 0' in p.stdout, p.stdout
+        print(tag, p.stdout.decode().strip())
+        out = out or p.stdout.decode()
+    return out
+
+
 # ------------------------------------------------------------------------------------------------- the conversion, restated ---
 # matrix code: (YOFF, CY, CRV, CGV, CGU, CBU) of include/meterelf_hip.h's table
 MATRIX = {

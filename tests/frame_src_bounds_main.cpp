@@ -1,8 +1,9 @@
 // Stand-alone run of the dial reader's frame sources (meterelf_amd/csrc/melf_frame_src.h, the header the kernels compile) on the
 // CPU: every source type the dial kernels instantiate is built and driven the way k_dials_body.inc drives it -- px for the colour
 // core, column / col_px for the exact path, window / request / unpack for the window fetch -- on frames that are malloc'd to
-// exactly the extent the matching check_* of melf_api.hip accepts at its tightest: the last row unpadded, the planes back to back,
-// no stride padding behind the last frame.  The loads are the header's own, so under -fsanitize=address the allocation's red zones
+// exactly (n - 1) * frame_stride + extent as the family's check_* (meterelf_amd/csrc/melf_frame_checks.h, the function the entry
+// points call) leaves them for this program's descriptors: the last row unpadded, the planes back to back, at the tightest no stride
+// padding behind a frame.  A descriptor the check does not take ends the program.  The loads are the header's own, so under -fsanitize=address the allocation's red zones
 // are the bounds check: a load that starts before the buffer or ends behind it stops the program with the sanitizer's report.  A
 // sibling of y16_bounds_main.cpp, which sweeps the 16-bit family's address functions and asserts the bounds itself.
 // Built and run by tests/test_dials_instantiations.py (test_frame_src_bounds_sweep) with the ROCm tree's clang++ as a plain C++
@@ -65,6 +66,7 @@ static inline int min(int a, int b) { return a < b ? a : b; }
 }  // namespace melf
 
 #include "../meterelf_amd/csrc/melf_frame_src.h"
+#include "tight_frames.h"
 
 using namespace melf;
 
@@ -101,6 +103,27 @@ struct Buf {
     void release() { free(mem); mem = base = nullptr; }
     const uint8_t* frame(int f) const { return base + (size_t)f * frame_stride; }
 };
+
+// d through its check (tight_frames.h): the frames as the launchers would be handed them
+template <class D, class Check>
+static Buf checked_buf(const Check& check, D& d, int spad, size_t phase)
+{
+    FrameBatch fb = {};
+    const char* const msg = tight_frames(check, d, spad, phase, &fb);
+    if (msg) {
+        fprintf(stderr, "a descriptor of the sweep is not taken: %s (n %d H %d W %d)\nfailures 1\n", msg, d.n, d.H, d.W);
+        exit(1);
+    }
+    Buf b;
+    b.n = fb.n; b.H = fb.H; b.W = fb.W; b.phase = phase;
+    b.row_stride = fb.row_stride; b.frame_stride = fb.frame_stride; b.extent = fb.lay.extent;
+    const FrameLayout& lay = fb.lay;
+    if (lay.pix == PIX_PLANAR) { b.off[0] = lay.planes.b_off; b.off[1] = lay.planes.g_off; b.off[2] = lay.planes.r_off; }
+    else if (lay.pix == PIX_YUVP) { b.off[0] = lay.yuvp.u_off; b.off[1] = lay.yuvp.v_off; b.c_pitch = lay.yuvp.c_pitch; }
+    else if (lay.pix == PIX_YUV16) { b.off[0] = lay.y16.u_off; b.off[1] = lay.y16.v_off; b.c_pitch = lay.y16.c_pitch; }
+    else if (pix_yuv(lay.pix)) { b.off[0] = lay.yuv.u_off; b.off[1] = lay.yuv.v_off; b.c_pitch = lay.yuv.c_pitch; }
+    return b;
+}
 
 struct Crop { int x0, y0, rows, cols, tw, th; };
 struct Count {
@@ -289,16 +312,14 @@ struct PackedFam {
     int nphases = PB == 4 ? 1 : 4;
     Buf make(const Cfg& g) const
     {
-        Buf b;
-        b.n = g.n; b.H = g.H; b.W = g.W; b.phase = g.phase;
-        if (FROM_HLS) {   // melf_read_dials: n packed th x tw crops of three bytes a pixel
-            b.row_stride = g.tw * 3; b.extent = (size_t)g.th * b.row_stride; b.frame_stride = b.extent; b.phase = 0;
-        } else {
-            b.row_stride = g.W * PB + g.pad;
-            b.extent = (size_t)(g.H - 1) * b.row_stride + (size_t)g.W * PB;
-            b.frame_stride = b.extent + (size_t)g.spad;
+        if (FROM_HLS) {   // melf_read_dials: n packed th x tw crops of three bytes a pixel (no descriptor: the entry point's own arguments)
+            Buf b;
+            b.n = g.n; b.H = g.H; b.W = g.W; b.phase = 0;
+            b.row_stride = g.tw * 3; b.extent = (size_t)g.th * b.row_stride; b.frame_stride = b.extent;
+            return b;
         }
-        return b;
+        melf_frames d = {PB == 4 ? MELF_PIX_BGRA : MELF_PIX_BGR, g.n, g.H, g.W, (int64_t)g.W * PB + g.pad, 0};
+        return checked_buf(check_frames, d, g.spad, g.phase);
     }
     void run(Count& cnt, const Buf& b, const Cfg& g, const DialsSrc& ds, const melf_params& P, int f, int mx, int my, int wx0, int wy0, int ws) const
     {
@@ -315,21 +336,22 @@ struct PackedFam {
 
 // ---- planar / semi-planar 8-bit YUV (check_yuv, check_yuv_planar) -----------------------------------------------------------------
 // The Y plane, then the chroma: semi-planar one plane of pairs (either order), planar two planes back to back (either order).
-struct YuvGeom { int sub_x, sub_y, c_step; bool nv12_rule; };
+// f420: MELF_YUV_NV12 / MELF_YUV_I420 for melf_yuv_frames (NV12: an even u_offset), -1 for melf_yuv_planar_frames.  The caller's side of
+// the layout -- the pitches and where the chroma starts -- is written here; what a frame then spans is the check's.
+struct YuvGeom { int sub_x, sub_y, c_step, f420; };
 static Buf make_yuv(const Cfg& g, const YuvGeom& y, bool vfirst)
 {
-    Buf b;
-    b.n = g.n; b.H = g.H; b.W = g.W; b.phase = g.phase;
-    b.row_stride = g.W + g.pad;
     const int cw = (g.W >> y.sub_x) * y.c_step, ch = g.H >> y.sub_y;
-    b.c_pitch = cw + g.pad;
-    const int64_t y_end = (int64_t)(g.H - 1) * b.row_stride + g.W;
-    const int64_t c_len = (int64_t)(ch - 1) * b.c_pitch + (y.c_step == 2 ? cw - 1 : cw);
-    const int64_t lo = y.nv12_rule ? (y_end + 1) & ~(int64_t)1 : y_end, hi = y.c_step == 2 ? lo + 1 : lo + c_len;
-    b.off[0] = vfirst ? hi : lo; b.off[1] = vfirst ? lo : hi;
-    b.extent = (size_t)(hi + c_len);
-    b.frame_stride = b.extent + (size_t)g.spad;
-    return b;
+    const int64_t y_pitch = g.W + g.pad, c_pitch = cw + g.pad;
+    const int64_t y_end = (int64_t)(g.H - 1) * y_pitch + g.W, c_len = (int64_t)(ch - 1) * c_pitch + (y.c_step == 2 ? cw - 1 : cw);
+    const int64_t lo = y.f420 == MELF_YUV_NV12 ? (y_end + 1) & ~(int64_t)1 : y_end, hi = y.c_step == 2 ? lo + 1 : lo + c_len;
+    const int64_t u_off = vfirst ? hi : lo, v_off = vfirst ? lo : hi;
+    if (y.f420 >= 0) {
+        melf_yuv_frames d = {y.f420, MELF_YUV_BT601_LIMITED, g.n, g.H, g.W, 0, y_pitch, c_pitch, u_off, v_off, 0};
+        return checked_buf(check_yuv, d, g.spad, g.phase);
+    }
+    melf_yuv_planar_frames d = {MELF_YUV_BT601_LIMITED, g.n, g.H, g.W, y.sub_x, y.sub_y, y.c_step, 0, y_pitch, c_pitch, u_off, v_off, 0};
+    return checked_buf(check_yuv_planar, d, g.spad, g.phase);
 }
 static uint32_t ref_yuv(const Buf& b, const YuvGeom& y, const YuvMatrix& m, int fr, int fx, int fy)
 {
@@ -343,7 +365,7 @@ struct Yuv420Fam {
     bool even_w = true;
     const int* pads = PADS_BYTE; int npads = 4;
     const int* phases = PHASES_ANY; int nphases = 4;
-    YuvGeom yg{1, 1, PLANAR ? 1 : 2, !PLANAR};
+    YuvGeom yg{1, 1, PLANAR ? 1 : 2, PLANAR ? MELF_YUV_I420 : MELF_YUV_NV12};
     Buf make(const Cfg& g) const { return make_yuv(g, yg, PLANAR && (g.variant & 1)); }   // I420 / YV12; NV12: U first
     void run(Count& cnt, const Buf& b, const Cfg& g, const DialsSrc& ds, const melf_params& P, int f, int mx, int my, int wx0, int wy0, int ws) const
     {
@@ -360,10 +382,10 @@ struct YuvPlanarFam {
     bool even_w = SUBX == 1;
     const int* pads = PADS_BYTE; int npads = 4;
     const int* phases = PHASES_ANY; int nphases = 4;
-    Buf make(const Cfg& g) const { return make_yuv(g, YuvGeom{SUBX, (g.variant >> 3) & 1, CSTEP, false}, g.variant & 1); }
+    Buf make(const Cfg& g) const { return make_yuv(g, YuvGeom{SUBX, (g.variant >> 3) & 1, CSTEP, -1}, g.variant & 1); }
     void run(Count& cnt, const Buf& b, const Cfg& g, const DialsSrc& ds, const melf_params& P, int f, int mx, int my, int wx0, int wy0, int ws) const
     {
-        const YuvGeom yg{SUBX, (g.variant >> 3) & 1, CSTEP, false};
+        const YuvGeom yg{SUBX, (g.variant >> 3) & 1, CSTEP, -1};
         const YuvMatrix& m = MATRICES[(g.variant >> 1) & 3];
         const YuvPlanarPlanes yp = {b.off[0], b.off[1], b.c_pitch, SUBX, yg.sub_y, CSTEP};
         const typename Src::Args a{yp, m};
@@ -380,12 +402,8 @@ struct P422Fam {
     const int* phases = PHASES_NONE; int nphases = 1;
     Buf make(const Cfg& g) const
     {
-        Buf b;
-        b.n = g.n; b.H = g.H; b.W = g.W; b.phase = 0;
-        b.row_stride = g.W * 2 + g.pad;
-        b.extent = (size_t)(g.H - 1) * b.row_stride + (size_t)g.W * 2;
-        b.frame_stride = b.extent + (size_t)g.spad;
-        return b;
+        melf_yuv422_frames d = {MELF_YUV422_YUYV + g.variant % 3, MELF_YUV_BT601_LIMITED, g.n, g.H, g.W, 0, (int64_t)g.W * 2 + g.pad, 0};
+        return checked_buf(check_yuv422, d, g.spad, 0);
     }
     void run(Count& cnt, const Buf& b, const Cfg& g, const DialsSrc& ds, const melf_params& P, int f, int mx, int my, int wx0, int wy0, int ws) const
     {
@@ -410,14 +428,10 @@ struct PlanarRgbFam {
     Buf make(const Cfg& g) const
     {
         static const int order[3][3] = {{0, 1, 2}, {2, 1, 0}, {1, 2, 0}};   // B G R, R G B, and a rotation
-        Buf b;
-        b.n = g.n; b.H = g.H; b.W = g.W; b.phase = g.phase;
-        b.row_stride = g.W + g.pad;
-        const int64_t span = (int64_t)(g.H - 1) * b.row_stride + g.W;
-        for (int k = 0; k < 3; ++k) b.off[k] = order[g.variant % 3][k] * span;
-        b.extent = (size_t)(3 * span);
-        b.frame_stride = b.extent + (size_t)g.spad;
-        return b;
+        const int* const o = order[g.variant % 3];
+        const int64_t pitch = g.W + g.pad, span = (int64_t)(g.H - 1) * pitch + g.W;   // the caller's side: the three planes back to back
+        melf_planar_frames d = {g.n, g.H, g.W, 0, o[0] * span, o[1] * span, o[2] * span, pitch, 0};
+        return checked_buf(check_planes, d, g.spad, g.phase);
     }
     void run(Count& cnt, const Buf& b, const Cfg&, const DialsSrc& ds, const melf_params& P, int f, int mx, int my, int wx0, int wy0, int ws) const
     {
@@ -442,18 +456,12 @@ struct Yuv16Fam {
     {
         const int sub_y = (g.variant >> 3) & 1;
         const bool vfirst = g.variant & 1;
-        Buf b;
-        b.n = g.n; b.H = g.H; b.W = g.W; b.phase = g.phase;
-        b.row_stride = g.W * 2 + g.pad;
-        const int cw = (g.W >> 1) * CSTEP * 2, ch = g.H >> sub_y;
-        b.c_pitch = cw + g.pad;
-        const int64_t y_end = (int64_t)(g.H - 1) * b.row_stride + (int64_t)g.W * 2;
-        const int64_t c_len = (int64_t)(ch - 1) * b.c_pitch + (CSTEP == 2 ? cw - 2 : cw);
+        const int cw = (g.W >> 1) * CSTEP * 2, ch = g.H >> sub_y;   // the caller's side: the pitches, the planes back to back
+        const int64_t y_pitch = g.W * 2 + g.pad, c_pitch = cw + g.pad;
+        const int64_t y_end = (int64_t)(g.H - 1) * y_pitch + (int64_t)g.W * 2, c_len = (int64_t)(ch - 1) * c_pitch + (CSTEP == 2 ? cw - 2 : cw);
         const int64_t lo = y_end, hi = CSTEP == 2 ? lo + 2 : lo + c_len;
-        b.off[0] = vfirst ? hi : lo; b.off[1] = vfirst ? lo : hi;
-        b.extent = (size_t)(hi + c_len);
-        b.frame_stride = b.extent + (size_t)g.spad;
-        return b;
+        melf_yuv16_frames d = {MELF_YUV_BT601_LIMITED, g.n, g.H, g.W, sub_y, CSTEP, (g.variant >> 5) % 9, 0, y_pitch, c_pitch, vfirst ? hi : lo, vfirst ? lo : hi, 0};
+        return checked_buf(check_yuv16, d, g.spad, g.phase);
     }
     void run(Count& cnt, const Buf& b, const Cfg& g, const DialsSrc& ds, const melf_params& P, int f, int mx, int my, int wx0, int wy0, int ws) const
     {

@@ -1,8 +1,9 @@
 // Stand-alone sweep of the load addresses of the prep kernels' 8-bit arms (meterelf_amd/csrc/prep_lplane_body.inc: PX 3, 4, 20, 21,
 // 22, 23 and 24 in its four SUBX / CSTEP forms), on the CPU, against buffers of exact extent -- what y16_bounds_main.cpp's prep_case
-// does for PX 25.  Every load of every live lane must lie inside [base, base + readable), readable = (n - 1) * frame_stride + the
-// extent the family's check_* (melf_api.hip) accepts at its tightest: the last row unpadded, the planes back to back, no stride
-// padding behind the last frame; the aligned dword windows must start on a dword of the address space and hold the lane's samples.
+// does for PX 25.  Every load of every live lane must lie inside [base, base + readable), readable = (n - 1) * frame_stride + extent
+// as the family's check_* (meterelf_amd/csrc/melf_frame_checks.h, the function the entry points call) leaves them for this program's
+// descriptors: the last row unpadded, the planes back to back, the stride a frame and the swept padding.  A descriptor the check
+// does not take is a failure.  The aligned dword windows must start on a dword of the address space and hold the lane's samples.
 //
 // The arms compute their addresses with the functions of meterelf_amd/csrc/melf_prep_addr.h (rows_safe, the lane's own test, the
 // windows' offsets and spans, and the launcher's prep_window_readable), and this program calls the same functions: a change of the
@@ -25,6 +26,7 @@
 #include <stdlib.h>
 
 #include "../meterelf_amd/csrc/melf_prep_addr.h"
+#include "tight_frames.h"
 
 namespace prep = melf::prep;
 
@@ -252,41 +254,59 @@ static void yuvp_case(Arm& arm, const Frames& f, const Crop& c, int nkb, int sub
         });
 }
 
-// ---- the frames, as the checks accept them at their tightest -----------------------------------------------------------------------------
-static Frames packed_frames(int n, int H, int W, int PB, int pad, int spad, int phase)
+// ---- the frames: this program's descriptors, and what the family's check leaves of them ----------------------------------------------------
+// d through its check (tight_frames.h), as this program's Frames
+template <class D, class Check>
+static Frames checked_frames(const Check& check, D& d, int spad, int phase)
 {
+    melf::FrameBatch b = {};
+    const char* const msg = tight_frames(check, d, spad, (size_t)phase, &b);
+    if (msg && g_fail++ < 20) fprintf(stderr, "a descriptor of the sweep is not taken: %s (n %d H %d W %d)\n", msg, d.n, d.H, d.W);
     Frames f = {};
-    f.n = n; f.H = H; f.W = W; f.phase = phase;
-    f.row_stride = W * PB + pad;
-    f.extent = (int64_t)(H - 1) * f.row_stride + (int64_t)W * PB;
-    f.frame_stride = f.extent + spad;
+    f.n = b.n; f.H = b.H; f.W = b.W; f.phase = phase;
+    f.row_stride = b.row_stride; f.frame_stride = (int64_t)b.frame_stride; f.extent = (int64_t)b.lay.extent;
+    if (b.lay.pix == melf::PIX_PLANAR) {
+        f.off[0] = b.lay.planes.b_off; f.off[1] = b.lay.planes.g_off; f.off[2] = b.lay.planes.r_off;
+    } else if (b.lay.pix == melf::PIX_YUVP) {
+        f.off[0] = b.lay.yuvp.u_off; f.off[1] = b.lay.yuvp.v_off; f.c_pitch = b.lay.yuvp.c_pitch;
+    } else if (melf::pix_yuv(b.lay.pix)) {
+        f.off[0] = b.lay.yuv.u_off; f.off[1] = b.lay.yuv.v_off; f.c_pitch = b.lay.yuv.c_pitch;
+    }
     return f;
 }
-static Frames yuv_frames(int n, int H, int W, int sub_x, int sub_y, int c_step, bool nv12_rule, bool vfirst, int pad, int spad, int phase)
+static Frames packed_frames(int n, int H, int W, int PB, int pad, int spad, int phase)
 {
-    Frames f = {};
-    f.n = n; f.H = H; f.W = W; f.phase = phase;
-    f.row_stride = W + pad;
+    melf_frames d = {PB == 4 ? MELF_PIX_BGRA : MELF_PIX_BGR, n, H, W, (int64_t)W * PB + pad, 0};
+    return checked_frames(melf::check_frames, d, spad, phase);
+}
+static Frames p422_frames(int n, int H, int W, int pad, int spad)
+{
+    melf_yuv422_frames d = {MELF_YUV422_YUYV, MELF_YUV_BT601_LIMITED, n, H, W, 0, (int64_t)W * 2 + pad, 0};
+    return checked_frames(melf::check_yuv422, d, spad, 0);
+}
+// f420: MELF_YUV_NV12 / MELF_YUV_I420 for melf_yuv_frames (NV12: an even u_offset), -1 for melf_yuv_planar_frames.  The caller's side of
+// the layout -- the pitches, and the chroma right behind the Y plane's last sample, planar V right behind U's (or the reverse) -- is
+// written here; what a frame then spans is the check's.
+static Frames yuv_frames(int n, int H, int W, int sub_x, int sub_y, int c_step, int f420, bool vfirst, int pad, int spad, int phase)
+{
     const int cw = (W >> sub_x) * c_step, ch = H >> sub_y;
-    f.c_pitch = cw + pad;
-    const int64_t y_end = (int64_t)(H - 1) * f.row_stride + W, c_len = (int64_t)(ch - 1) * f.c_pitch + (c_step == 2 ? cw - 1 : cw);
-    const int64_t lo = nv12_rule ? (y_end + 1) & ~(int64_t)1 : y_end, hi = c_step == 2 ? lo + 1 : lo + c_len;
-    f.off[0] = vfirst ? hi : lo; f.off[1] = vfirst ? lo : hi;
-    f.extent = hi + c_len;
-    f.frame_stride = f.extent + spad;
-    return f;
+    const int64_t y_pitch = W + pad, c_pitch = cw + pad;
+    const int64_t y_end = (int64_t)(H - 1) * y_pitch + W, c_len = (int64_t)(ch - 1) * c_pitch + (c_step == 2 ? cw - 1 : cw);
+    const int64_t lo = f420 == MELF_YUV_NV12 ? (y_end + 1) & ~(int64_t)1 : y_end, hi = c_step == 2 ? lo + 1 : lo + c_len;
+    const int64_t u_off = vfirst ? hi : lo, v_off = vfirst ? lo : hi;
+    if (f420 >= 0) {
+        melf_yuv_frames d = {f420, MELF_YUV_BT601_LIMITED, n, H, W, 0, y_pitch, c_pitch, u_off, v_off, 0};
+        return checked_frames(melf::check_yuv, d, spad, phase);
+    }
+    melf_yuv_planar_frames d = {MELF_YUV_BT601_LIMITED, n, H, W, sub_x, sub_y, c_step, 0, y_pitch, c_pitch, u_off, v_off, 0};
+    return checked_frames(melf::check_yuv_planar, d, spad, phase);
 }
 static Frames planar_frames(int n, int H, int W, int order, int pad, int spad, int phase)
 {
     static const int orders[3][3] = {{0, 1, 2}, {2, 1, 0}, {1, 2, 0}};
-    Frames f = {};
-    f.n = n; f.H = H; f.W = W; f.phase = phase;
-    f.row_stride = W + pad;
-    const int64_t span = (int64_t)(H - 1) * f.row_stride + W;
-    for (int k = 0; k < 3; ++k) f.off[k] = orders[order][k] * span;
-    f.extent = 3 * span;
-    f.frame_stride = f.extent + spad;
-    return f;
+    const int64_t pitch = W + pad, span = (int64_t)(H - 1) * pitch + W;   // the caller's side: the three planes back to back
+    melf_planar_frames d = {n, H, W, 0, orders[order][0] * span, orders[order][1] * span, orders[order][2] * span, pitch, 0};
+    return checked_frames(melf::check_planes, d, spad, phase);
 }
 
 static Arm g_arms[11] = {{"PX 3", 0, 0, 0},          {"PX 4", 0, 0, 0},          {"PX 20 (NV12)", 0, 0, 0},   {"PX 21 (I420)", 0, 0, 0},
@@ -321,20 +341,20 @@ int main()
                                         packed_case<3>(g_arms[0], packed_frames(n, H, W, 3, pads_byte[pi], pads_byte[spad_i], ph), c, nkb);
                                         planar_case(g_arms[5], planar_frames(n, H, W, order, pads_byte[pi], pads_byte[spad_i], ph), c, nkb);
                                         for (int sub_y = 0; sub_y < 2; ++sub_y) {
-                                            yuvp_case<0, 1>(g_arms[6], yuv_frames(n, H, W, 0, sub_y, 1, false, vfirst, pads_byte[pi], pads_byte[spad_i], ph), c, nkb, sub_y);
-                                            yuvp_case<0, 2>(g_arms[7], yuv_frames(n, H, W, 0, sub_y, 2, false, vfirst, pads_byte[pi], pads_byte[spad_i], ph), c, nkb, sub_y);
+                                            yuvp_case<0, 1>(g_arms[6], yuv_frames(n, H, W, 0, sub_y, 1, -1, vfirst, pads_byte[pi], pads_byte[spad_i], ph), c, nkb, sub_y);
+                                            yuvp_case<0, 2>(g_arms[7], yuv_frames(n, H, W, 0, sub_y, 2, -1, vfirst, pads_byte[pi], pads_byte[spad_i], ph), c, nkb, sub_y);
                                         }
                                         if (W & 1) continue;   // horizontally subsampled chroma: an even width
-                                        yuv420_case<true>(g_arms[2], yuv_frames(n, H, W, 1, 1, 2, true, false, pads_byte[pi], pads_byte[spad_i], ph), c, nkb);
-                                        yuv420_case<false>(g_arms[3], yuv_frames(n, H, W, 1, 1, 1, false, vfirst, pads_byte[pi], pads_byte[spad_i], ph), c, nkb);
+                                        yuv420_case<true>(g_arms[2], yuv_frames(n, H, W, 1, 1, 2, MELF_YUV_NV12, false, pads_byte[pi], pads_byte[spad_i], ph), c, nkb);
+                                        yuv420_case<false>(g_arms[3], yuv_frames(n, H, W, 1, 1, 1, MELF_YUV_I420, vfirst, pads_byte[pi], pads_byte[spad_i], ph), c, nkb);
                                         for (int sub_y = 0; sub_y < 2; ++sub_y) {
-                                            yuvp_case<1, 1>(g_arms[8], yuv_frames(n, H, W, 1, sub_y, 1, false, vfirst, pads_byte[pi], pads_byte[spad_i], ph), c, nkb, sub_y);
-                                            yuvp_case<1, 2>(g_arms[9], yuv_frames(n, H, W, 1, sub_y, 2, false, vfirst, pads_byte[pi], pads_byte[spad_i], ph), c, nkb, sub_y);
+                                            yuvp_case<1, 1>(g_arms[8], yuv_frames(n, H, W, 1, sub_y, 1, -1, vfirst, pads_byte[pi], pads_byte[spad_i], ph), c, nkb, sub_y);
+                                            yuvp_case<1, 2>(g_arms[9], yuv_frames(n, H, W, 1, sub_y, 2, -1, vfirst, pads_byte[pi], pads_byte[spad_i], ph), c, nkb, sub_y);
                                         }
                                     }
                                     if (pi < 3) {   // everything 4-byte aligned: phase 0, pads of whole dwords
                                         packed_case<4>(g_arms[1], packed_frames(n, H, W, 4, pads_dword[pi], pads_dword[spad_i % 3], 0), c, nkb);
-                                        if (!(W & 1)) p422_case(g_arms[4], packed_frames(n, H, W, 2, pads_dword[pi], pads_dword[spad_i % 3], 0), c, nkb);
+                                        if (!(W & 1)) p422_case(g_arms[4], p422_frames(n, H, W, pads_dword[pi], pads_dword[spad_i % 3]), c, nkb);
                                     }
                                 }
                             }

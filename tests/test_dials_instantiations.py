@@ -31,7 +31,6 @@ import functools
 import glob
 import os
 import shutil
-import subprocess
 import sys
 import tempfile
 
@@ -369,21 +368,6 @@ def rocm_clangxx():
     return cxx, os.path.join(rocm, 'include')
 
 
-def _build_and_run(tmp_path, cxx, src, name, extra, san):
-    """src as a stand-alone program, plain and under the host sanitizers `san`: both exit 0 and print `failures 0`.  Returns
-    the plain run's output."""
-    out = None
-    for (tag, flags) in (('plain', ['-O2']), ('san', ['-O1', '-g', '-fno-sanitize-recover=all'] + san)):
-        exe = str(tmp_path / (name + '_' + tag))
-        subprocess.check_call([cxx, '-std=c++17', '-Wall', '-Werror'] + extra + flags + ['-o', exe, src])
-        p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
-        assert p.returncode == 0, (tag, p.stdout[-2000:], p.stderr[-4000:])
-        assert b'failures 0' in p.stdout, p.stdout
-        print(tag, p.stdout.decode().strip())
-        out = out or p.stdout.decode()
-    return out
-
-
 def test_frame_src_bounds_sweep(tmp_path):
     """tests/frame_src_bounds_main.cpp: the dial sources of melf_frame_src.h, compiled for the host and run on frames malloc'd to
     exactly the descriptor's extent, over the sweep the program's head lists: no load leaves the allocation (the sanitizer's red
@@ -391,8 +375,8 @@ def test_frame_src_bounds_sweep(tmp_path):
     window fetch, the exact path and -- where it has one -- the load moved left at the crop's right edge.  Only `alignment` is
     dropped from the sanitizers: the sources load unaligned dwords on purpose."""
     (cxx, inc) = rocm_clangxx()
-    out = _build_and_run(tmp_path, cxx, os.path.join(ROOT, 'tests', 'frame_src_bounds_main.cpp'), 'frame_src_bounds',
-                         ['-D__HIP_PLATFORM_AMD__', '-I' + inc], ['-fsanitize=address,undefined', '-fno-sanitize=alignment'])
+    out = fc.build_and_run(tmp_path, cxx, os.path.join(ROOT, 'tests', 'frame_src_bounds_main.cpp'), 'frame_src_bounds',
+                           ['-D__HIP_PLATFORM_AMD__', '-I' + inc], ['-fsanitize=address,undefined', '-fno-sanitize=alignment'])
     assert out.count('windows: quads') == 15, out   # the fifteen source types
 
 
@@ -400,8 +384,8 @@ def test_prep_bounds_sweep(tmp_path):
     """tests/prep_bounds_main.cpp: every load of the prep kernels' 8-bit arms lies inside a buffer of exact extent, over the sweep
     the program's head lists, and every arm took each of its three paths.  The addresses, spans and guards are those of
     meterelf_amd/csrc/melf_prep_addr.h, the functions the kernels and the launcher compute them with."""
-    out = _build_and_run(tmp_path, os.environ.get('CXX', 'g++'), os.path.join(ROOT, 'tests', 'prep_bounds_main.cpp'), 'prep_bounds', [],
-                         ['-fsanitize=address,undefined'])
+    out = fc.build_and_run(tmp_path, os.environ.get('CXX', 'g++'), os.path.join(ROOT, 'tests', 'prep_bounds_main.cpp'), 'prep_bounds', [],
+                           ['-fsanitize=address,undefined'])
     assert out.count('lanes: row-safe') == 10, out   # the ten arms
 
 

@@ -1,7 +1,8 @@
 // Stand-alone sweep of the address arithmetic of the 16-bit YUV kernels (meterelf_amd/csrc/melf_y16_addr.h: the functions the dial
 // source's window fetch and the prep arm compute their loads with), on the CPU: every load of every lane must lie inside
-// [base, base + extent) of a buffer of exact extent -- (n - 1) * frame_stride + the last sample of the last frame -- and start on
-// a sample; the aligned dword windows of the prep arm must start on a dword of the address space.  Built and run by
+// [base, base + readable) and start on a sample, readable = (n - 1) * frame_stride + extent as check_yuv16 (meterelf_amd/csrc/
+// melf_frame_checks.h, the function the entry points call) leaves them for this program's descriptors -- a descriptor it does not
+// take is a failure; the aligned dword windows of the prep arm must start on a dword of the address space.  Built and run by
 // tests/test_yuv16_frames.py (test_load_bounds_sweep) with the host compiler, plain and under -fsanitize=address,undefined.
 //
 // Swept: crop origin parities; crop widths 8 .. 72; pitches with 0, 2 and 6 bytes of padding; both c_step; both sub_y; base
@@ -12,10 +13,11 @@
 #include <stdlib.h>
 
 #include "../meterelf_amd/csrc/melf_y16_addr.h"
+#include "tight_frames.h"
 
 using namespace melf;
 
-struct Frames {            // what check_yuv16 (melf_api.hip) accepts, as tight as it accepts it
+struct Frames {            // what check_yuv16 leaves of a descriptor
     int n, H, W, sub_y, c_step;
     size_t y_pitch, c_pitch, frame_stride, extent;   // extent: of one frame, to the end of its last sample
     int64_t u_off, v_off;
@@ -23,24 +25,30 @@ struct Frames {            // what check_yuv16 (melf_api.hip) accepts, as tight 
     size_t readable() const { return (size_t)(n - 1) * frame_stride + extent; }
 };
 
+static long long g_loads = 0, g_fail = 0;
+// The caller's side of the layout -- the pitches, and the planes back to back with no byte between their spans -- is written here;
+// the stride is the smallest check_yuv16 takes and `pad` bytes, and what a frame spans is the check's.
 static Frames make_frames(int n, int H, int W, int sub_y, int c_step, int pad, bool vfirst, size_t phase)
 {
+    melf_yuv16_frames d = {};
+    d.matrix = MELF_YUV_BT601_LIMITED; d.n = n; d.H = H; d.W = W; d.sub_y = sub_y; d.c_step = c_step; d.shift = 8;
+    const int64_t cw = (int64_t)(W >> 1) * c_step * 2, ch = H >> sub_y;
+    d.y_pitch = (int64_t)W * 2 + pad;
+    d.c_pitch = cw + pad;
+    const int64_t y_end = (int64_t)(H - 1) * d.y_pitch + (int64_t)W * 2, c_len = (ch - 1) * d.c_pitch + (c_step == 2 ? cw - 2 : cw);
+    const int64_t lo = y_end, hi = c_step == 2 ? y_end + 2 : y_end + c_len;
+    d.u_offset = vfirst ? hi : lo;
+    d.v_offset = vfirst ? lo : hi;
+    FrameBatch b = {};
+    const char* const msg = tight_frames(check_yuv16, d, pad, phase, &b);
+    if (msg && g_fail++ < 20) fprintf(stderr, "a descriptor of the sweep is not taken: %s (n %d H %d W %d)\n", msg, n, H, W);
     Frames f;
-    f.n = n; f.H = H; f.W = W; f.sub_y = sub_y; f.c_step = c_step; f.phase = phase;
-    f.y_pitch = (size_t)W * 2 + (size_t)pad;
-    const size_t cw = (size_t)(W >> 1) * (size_t)c_step * 2, ch = (size_t)(H >> sub_y);
-    f.c_pitch = cw + (size_t)pad;
-    const size_t y_end = (size_t)(H - 1) * f.y_pitch + (size_t)W * 2;
-    const size_t c_len = (ch - 1) * f.c_pitch + (c_step == 2 ? cw - 2 : cw);
-    const size_t lo = y_end, hi = c_step == 2 ? y_end + 2 : y_end + c_len;   // the planes back to back, no byte between their spans
-    f.u_off = (int64_t)(vfirst ? hi : lo);
-    f.v_off = (int64_t)(vfirst ? lo : hi);
-    f.extent = hi + c_len;
-    f.frame_stride = f.extent + (size_t)pad;
+    f.n = b.n; f.H = b.H; f.W = b.W; f.sub_y = b.lay.y16.sub_y; f.c_step = b.lay.y16.c_step; f.phase = phase;
+    f.y_pitch = (size_t)b.row_stride; f.c_pitch = (size_t)b.lay.y16.c_pitch; f.frame_stride = b.frame_stride; f.extent = b.lay.extent;
+    f.u_off = b.lay.y16.u_off; f.v_off = b.lay.y16.v_off;
     return f;
 }
 
-static long long g_loads = 0, g_fail = 0;
 static void load(const Frames& f, size_t off, size_t len, size_t align, const char* what)
 {
     ++g_loads;

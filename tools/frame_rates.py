@@ -24,7 +24,7 @@ if ROOT not in sys.path:
 from meterelf_amd import _engine, _hip, _params  # noqa: E402
 from meterelf_amd._image import imread_bgr  # noqa: E402
 
-# matrix code: (YOFF, CY, CRV, CGV, CGU, CBU), YuvMatrix of meterelf_amd/csrc/melf_internal.h
+# matrix code: (YOFF, CY, CRV, CGV, CGU, CBU), YuvMatrix of meterelf_amd/csrc/melf_frame_layout.h
 MATRIX = {
     0: (16, 1220542, 1673527, -852492, -409993, 2116026),
     2: (0, 1048576, 1470104, -748826, -360853, 1858077),

@@ -341,8 +341,9 @@ int melf_yuv_planar_to_bgr(melf_ctx* ctx, const void* frames_host, const melf_yu
  * base, y_pitch, c_pitch, u_offset, v_offset or frame_stride; y_pitch < 2 * W bytes; c_pitch smaller than a chroma row ((W >> 1) *
  * c_step samples of 2 bytes); a pitch > 2^31 - 1; a chroma plane closer to the other than its span (overlapping) or starting
  * inside the Y plane's span; a frame_stride smaller than the span of one frame.
- * Out of scope: sub_x = 0 (4:4:4 / 4:4:0 at 16 bits); the packed 10-bit formats (Y210, v210); big-endian samples; BT.2020 (and
- * any transfer function: the samples are taken as they are); rounding or dithering of the dropped bits. */
+ * Out of scope: sub_x = 0 (4:4:4 / 4:4:0 at 16 bits); big-endian samples; BT.2020 (and any transfer function: the samples are
+ * taken as they are); rounding or dithering of the dropped bits.  (The packed 10-bit formats, v210 and Y210 / Y212 / Y216:
+ * melf_process_yuv422_10*, below.) */
 typedef struct melf_yuv16_frames {
     int32_t matrix;                             /* MELF_YUV_BT* as above (the four codes; 1 stays invalid) */
     int32_t n, H, W;                            /* W even; H even if sub_y                                */
@@ -367,6 +368,56 @@ int melf_process_yuv16_dev(melf_ctx* ctx, const void* d_frames, const melf_yuv16
                            void* stream);
 /* Stage entry point (parity tests, and a debug view for callers): reduction and conversion alone, n packed H x W x 3 BGR frames out. */
 int melf_yuv16_to_bgr(melf_ctx* ctx, const void* frames_host, const melf_yuv16_frames* f, uint8_t* bgr_out_host);
+
+/* ---- the same path for packed 10-bit YUV 4:2:2 frames: v210, the native 10-bit format of SDI / HDMI capture cards (DeckLink
+ * bmdFormat10BitYUV, AJA, ffmpeg's v210), and Y210 / Y212 / Y216, what hardware 4:2:2 10-bit decoders leave (D3D11, VAAPI, oneVPL) ----
+ * Every sample is read as an 8-bit sample s8 by truncation, a pure selection of bits, and the records are byte-identical to
+ * melf_process_yuv422(_dev) on the 8-bit YUYV frame with the same n, H, W and matrix whose samples are the s8 -- and so, by that
+ * entry point's contract, to melf_process_batch(_dev) on the BGR frame the integer conversion above makes of it under the
+ * descriptor's matrix (any of the four codes; 1 stays invalid).  Neither that 8-bit frame nor a BGR frame is ever formed: the
+ * kernels read the packed frames in place, and only the meter_rect crop of them.
+ *     chroma: the two pixels of a pair share its U and V; no interpolation, no vertical subsampling
+ * MELF_YUV422_10_V210: row y of frame f starts at frames + f * frame_stride + y * row_pitch and is ceil(W / 6) whole groups of 16
+ * bytes.  A group is four little-endian 32-bit words, each with three 10-bit fields at bits 0-9, 10-19 and 20-29; bits 30-31 are
+ * ignored, whatever they hold.  A group holds pixels 6 g .. 6 g + 5 as three pairs, pair q = pixels 6 g + 2 q and 6 g + 2 q + 1
+ * sharing U and V; its fields, as (word, bit offset):
+ *     pair   first Y   second Y   U        V
+ *     0      w0, 10    w1, 0      w0, 0    w0, 20
+ *     1      w1, 20    w2, 10     w1, 10   w2, 0
+ *     2      w3, 0     w3, 20     w2, 20   w3, 10
+ * (the twelve fields in order are U Y V Y U Y V Y U Y V Y).  s8 = (field >> 2) & 255.  Fields of pixels >= W in a row's last
+ * group are never looked at.  W is even, H any; row_pitch >= ceil(W / 6) * 16 (the conventional pitch is ((W + 47) / 48) * 128);
+ * the base, row_pitch and frame_stride are multiples of 16, so that a group is one aligned 16-byte load.  A frame extends over
+ * (H - 1) * row_pitch + ceil(W / 6) * 16 bytes.
+ * MELF_YUV422_10_Y210 (also Y212 and Y216): a row is W / 2 macropixels of four MSB-aligned little-endian 16-bit words Y0 U Y1 V,
+ * 8 bytes for two pixels.  s8 = s >> 8, the word's high byte: under truncation the three formats are one.  W is even;
+ * row_pitch >= 4 * W; the base, row_pitch and frame_stride are multiples of 8.  A frame extends over (H - 1) * row_pitch + 4 * W
+ * bytes.
+ * The buffer must hold (n - 1) * frame_stride + one frame's extent, and need hold nothing behind that nor before the base: no
+ * load of the kernels reaches outside.  MELF_ERR_INVALID (melf_last_error says which) before anything is launched or copied for:
+ * a NULL descriptor or NULL frames; an unknown format or matrix; reserved != 0; H or W <= 0, n < 0 (n == 0 passes); an odd W; a
+ * row_pitch smaller than a row or > 2^31 - 1; a frame_stride smaller than a frame; a misaligned base, row_pitch or frame_stride.
+ * Out of scope: big-endian and LSB-aligned Y21x; Y410 and other packed 4:4:4; the r210 RGB format; rounding or dithering of the
+ * dropped bits; BT.2020 and transfer functions; interpolated chroma. */
+enum { MELF_YUV422_10_V210 = 0, MELF_YUV422_10_Y210 = 1 };   /* Y210: also Y212, Y216 */
+typedef struct melf_yuv422_10_frames {
+    int32_t format, matrix;                     /* MELF_YUV422_10_*; matrix: MELF_YUV_BT* as above        */
+    int32_t n, H, W;                            /* W even, H any                                          */
+    int32_t reserved;                           /* 0                                                      */
+    int64_t row_pitch;                          /* bytes between rows: v210 >= ceil(W / 6) * 16 and a
+                                                   multiple of 16; Y210 >= 4 * W and a multiple of 8      */
+    int64_t frame_stride;                       /* bytes between frames, aligned like row_pitch           */
+} melf_yuv422_10_frames;
+/* Host frames, as melf_process_yuv422: only the crop crosses PCIe, packed into the pinned staging buffers as a small frame of the
+ * same format (its x origin rounded down and its far corner up to whole groups of 6 pixels (v210) or whole macropixels (Y210),
+ * the rows copied as they are); no sample is unpacked on the CPU. */
+int melf_process_yuv422_10(melf_ctx* ctx, const void* frames_host, const melf_yuv422_10_frames* f, melf_result* out_host);
+/* Frames in HBM, exactly as melf_process_yuv422_dev: the same lanes, melf_ctx_set_frames_resident, caller streams, and NULL
+ * d_results / out_host semantics. */
+int melf_process_yuv422_10_dev(melf_ctx* ctx, const void* d_frames, const melf_yuv422_10_frames* f, void* d_results,
+                               melf_result* out_host, void* stream);
+/* Stage entry point (parity tests, and a debug view for callers): unpacking and conversion alone, n packed H x W x 3 BGR frames out. */
+int melf_yuv422_10_to_bgr(melf_ctx* ctx, const void* frames_host, const melf_yuv422_10_frames* f, uint8_t* bgr_out_host);
 
 /* ---- the same path for planar, channels-first frames: (N, 3, H, W) uint8 as torch's decoders and pre-processing pipelines
  * hold them, ffmpeg's gbrp, rgb24 split into planes ----
@@ -588,7 +639,7 @@ typedef struct {
 int melf_ctx_last_match(const melf_ctx* ctx, melf_match_info* out);
 /* Which dial-reader kernel the context's most recent launch ran: the kernel family that reads the frames' layout and NR, the
  * window rows a lane requests up front -- one of 32, 40, 48, 52, 56, 64, the smallest that holds ws_max, the context's largest
- * dial window (2 R + 5 rows).  Twelve families (and the two of the 16-bit frames, below) times six NR: tests assert the pair, so
+ * dial window (2 R + 5 rows).  Twelve families (and the two of the 16-bit and the two of the packed 10-bit frames, below) times six NR: tests assert the pair, so
  * that every instantiation production can pick is known to have been the one a parity test launched.  family is -1 and nr 0
  * before the first launch; a call of more frames than one launch takes reports its last piece.  Plain fields written by every
  * launch, as for melf_ctx_fused_variant's last_launch.  Every output pointer may be NULL. */
@@ -610,6 +661,9 @@ enum { MELF_DIALS_HLS = 0,            /* k_dials<true>: packed HLS dials crops (
  * these kernels are enumerated by tests of their own; the values go on from 12 so that `family` stays one number space. */
 enum { MELF_DIALS16_STEP1 = 12,       /* k_y16_needle<1>: melf_process_yuv16*, planar                        */
        MELF_DIALS16_STEP2 = 13 };     /* k_y16_needle<2>: ... interleaved pairs                              */
+/* The families of the packed 10-bit 4:2:2 frames (melf_process_yuv422_10*), in the same way: an enum of their own that goes on. */
+enum { MELF_DIALS10_V210 = 14,        /* k_v210_needle: melf_process_yuv422_10*, MELF_YUV422_10_V210         */
+       MELF_DIALS10_Y210 = 15 };      /* k_y210_needle: ... MELF_YUV422_10_Y210                              */
 int melf_ctx_last_dials(const melf_ctx* ctx, int* nr, int* family, int* ws_max);
 /* The tuned kernel's wave layout for a template / searched-image shape and a batch of n images, without a GPU or a
  * context (host logic; kernel = MELF_MATCH_KERNEL_MFMA when the shape belongs to the tuned kernel's class, else the

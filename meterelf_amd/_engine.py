@@ -241,6 +241,21 @@ class MeterReader:
         return self._read_view(v, out, lambda: self.ctx.process_yuv16(v.ptr, desc),
                                lambda **kw: self.ctx.process_yuv16_dev(v.ptr, desc, **kw))
 
+    def read_yuv422_10_frames(self, frames, pixel_format: str, matrix, width=None, out=None):
+        """Packed 10-bit YUV 4:2:2 frames -- 'v210', the native 10-bit format of SDI / HDMI capture cards, or 'y210' / 'y212' / 'y216'
+        as hardware 4:2:2 10-bit decoders leave them (_hip.YUV422_10_FORMATS) -- -> records, equal to read_yuv422_frames() of the 8-bit
+        YUYV frames whose samples are the top 8 bits of each sample (melf_process_yuv422_10*); the packed frames are read in place, no
+        unpack pass.  matrix has no default, as for read_yuv16_frames.  frames: 'v210' (N, H, row_words) of uint32 with width= the
+        frames' width in pixels (required); 'y21x' (N, H, W, 2) of uint16: a numpy array / torch CPU tensor (host path) or a torch
+        tensor on this reader's GPU (enqueued on torch.cuda.current_stream), torch.int32 / torch.int16 holding the same bits where the
+        installed torch has no unsigned type; _hip.yuv422_10_frames_view says which layouts are read in place.  out: a uint8 device
+        tensor (N, RESULT_DTYPE.itemsize) on the same GPU that receives the records without synchronising the stream (device frames
+        only); returns it.  Otherwise returns the records."""
+        v = _hip.yuv422_10_frames_view(frames, pixel_format, matrix, width)
+        desc = v.descriptor()
+        return self._read_view(v, out, lambda: self.ctx.process_yuv422_10(v.ptr, desc),
+                               lambda **kw: self.ctx.process_yuv422_10_dev(v.ptr, desc, **kw))
+
     def read_planar_frames(self, frames, channel_order: str = 'rgb', out=None):
         """Planar, channels-first frames (N, 3, H, W) / (N, 4, H, W) uint8 -> records, equal to read_frames() of the packed BGR
         frames with the same samples (melf_process_planes*); the planes are read in place, no interleaved copy is made.  frames: a

@@ -137,6 +137,17 @@ YUV16_FORMATS = {
 }
 
 
+class MelfYuv422_10Frames(C.Structure):
+    _fields_ = [('format', C.c_int32), ('matrix', C.c_int32), ('n', C.c_int32), ('H', C.c_int32), ('W', C.c_int32),
+                ('reserved', C.c_int32), ('row_pitch', C.c_int64), ('frame_stride', C.c_int64)]
+
+
+# packed 10-bit YUV 4:2:2 layouts of melf_process_yuv422_10* (MELF_YUV422_10_*) by name: 'v210', six pixels in a 16-byte group of
+# four 32-bit words; 'y210' / 'y212' / 'y216', MSB-aligned 16-bit words Y0 U Y1 V, one format once the low bits are dropped
+(YUV422_10_V210, YUV422_10_Y210) = (0, 1)
+YUV422_10_FORMATS = {'v210': 0, 'y210': 1, 'y212': 1, 'y216': 1}
+
+
 class MelfPlanarFrames(C.Structure):
     _fields_ = [('n', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('reserved', C.c_int32), ('b_offset', C.c_int64),
                 ('g_offset', C.c_int64), ('r_offset', C.c_int64), ('row_pitch', C.c_int64), ('frame_stride', C.c_int64)]
@@ -165,6 +176,9 @@ DIALS_FAMILIES = ('hls', 'bgr', 'packed3', 'packed4', 'nv12', 'i420', 'p422', 'y
 # of their own, as the header keeps them in an enum of their own: DIALS_FAMILIES is the twelve the instantiation tests enumerate.
 DIALS16_FAMILIES = ('yuv16_step1', 'yuv16_step2')
 
+# MELF_DIALS10_* in the same way, the families of the packed 10-bit 4:2:2 frames: values 14, 15
+DIALS10_FAMILIES = ('v210', 'y210')
+
 # every symbol include/meterelf_hip.h declares for the product library; DIAG_EXPORTS: what its `#ifdef MELF_DIAG` part adds (the
 # diagnostic build, make -C meterelf_amd/csrc diag, loaded through MELF_LIB_PATH)
 DIAG_EXPORTS = ['melf_stream_probe_dev']
@@ -176,6 +190,7 @@ EXPORTS = [
     'melf_process_yuv422', 'melf_process_yuv422_dev', 'melf_yuv422_to_bgr', 'melf_process_planes', 'melf_process_planes_dev',
     'melf_process_yuv_planar', 'melf_process_yuv_planar_dev', 'melf_yuv_planar_to_bgr',
     'melf_process_yuv16', 'melf_process_yuv16_dev', 'melf_yuv16_to_bgr',
+    'melf_process_yuv422_10', 'melf_process_yuv422_10_dev', 'melf_yuv422_10_to_bgr',
     'melf_bgr2hls', 'melf_hls_inrange_close', 'melf_hls_inrange_close_dev', 'melf_match_ccoeff',
     'melf_read_dials', 'melf_aligned_average', 'melf_inrange', 'melf_ctx_fused_table_ties', 'melf_ctx_fused_variant', 'melf_ctx_set_frames_resident', 'melf_ctx_last_match', 'melf_ctx_last_dials', 'melf_match_layout_query', 'melf_match_gen_plan_query', 'melf_ctx_set_profiling', 'melf_ctx_timings', 'melf_kernel_name',
     'melf_jpeg_probe', 'melf_jpeg_probe_batch', 'melf_jpeg_decode_batch', 'melf_jpeg_clean_segment', 'melf_jpeg_process_batch',
@@ -228,6 +243,9 @@ def lib():
     L.melf_process_yuv16.argtypes = [vp, vp, C.POINTER(MelfYuv16Frames), vp]
     L.melf_process_yuv16_dev.argtypes = [vp, vp, C.POINTER(MelfYuv16Frames), vp, vp, vp]
     L.melf_yuv16_to_bgr.argtypes = [vp, vp, C.POINTER(MelfYuv16Frames), vp]
+    L.melf_process_yuv422_10.argtypes = [vp, vp, C.POINTER(MelfYuv422_10Frames), vp]
+    L.melf_process_yuv422_10_dev.argtypes = [vp, vp, C.POINTER(MelfYuv422_10Frames), vp, vp, vp]
+    L.melf_yuv422_10_to_bgr.argtypes = [vp, vp, C.POINTER(MelfYuv422_10Frames), vp]
     L.melf_process_planes.argtypes = [vp, vp, C.POINTER(MelfPlanarFrames), vp]
     L.melf_process_planes_dev.argtypes = [vp, vp, C.POINTER(MelfPlanarFrames), vp, vp, vp]
     L.melf_process_stream_dev.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, vp]
@@ -702,6 +720,101 @@ def yuv16_frames_view(frames, pixel_format, matrix):
     return Yuv16FramesView(ptr, on_device, device, n, H, W, sy, step, shift, rp, c_pitch, u_off, v_off, fs, extent, copied, frames, mcode)
 
 
+class Yuv422_10FramesView(NamedTuple):
+    """How the kernels read a batch of packed 10-bit YUV 4:2:2 frames in place (yuv422_10_frames_view)."""
+    ptr: int            # address of frame 0's first group / macropixel
+    on_device: bool     # True: a torch tensor on a GPU (ptr is a device address)
+    device: Optional[int]
+    format: int         # YUV422_10_V210 / YUV422_10_Y210
+    n: int
+    H: int
+    W: int
+    row_pitch: int      # bytes between rows
+    frame_stride: int   # bytes between frames
+    extent: int         # bytes read from ptr: (n - 1) * frame_stride + (H - 1) * row_pitch + a row's groups / macropixels
+    copied: bool        # the layout could not be described and the frames were copied once to a packed array
+    array: object       # what ptr points into (the caller's array, or the copy): keep it alive while the call runs
+    matrix: int         # YUV_BT* code of the colour conversion
+
+    def descriptor(self):
+        return MelfYuv422_10Frames(self.format, self.matrix, self.n, self.H, self.W, 0, self.row_pitch, self.frame_stride)
+
+
+def _unwrap32(frames):
+    """_unwrap for arrays of 4-byte words: a uint32 numpy array, or a torch tensor of torch.uint32 (where the installed torch has it)
+    or torch.int32 (the same bits); strides in BYTES.  Anything else: ValueError."""
+    if _is_torch(frames):
+        if str(frames.dtype) not in ('torch.uint32', 'torch.int32'):
+            raise ValueError('frames must be uint32 (or int32 holding the same bits), not %s' % frames.dtype)
+        on_device = frames.device.type == 'cuda'
+        return (frames, True, tuple(frames.shape), tuple(4 * st for st in frames.stride()),
+                frames.data_ptr(), on_device, frames.device.index if on_device else None)
+    frames = np.asarray(frames)
+    if frames.dtype != np.uint32:
+        raise ValueError('frames must be uint32, not %s' % frames.dtype)
+    return (frames, False, frames.shape, frames.strides, frames.ctypes.data, False, None)
+
+
+def v210_row_bytes(width):
+    """Bytes of a v210 row of `width` pixels: ceil(width / 6) whole groups of 16 bytes."""
+    return (width + 5) // 6 * 16
+
+
+def yuv422_10_frames_view(frames, pixel_format, matrix, width=None):
+    """Describes a batch of packed 10-bit YUV 4:2:2 frames (numpy array or torch tensor) as melf_process_yuv422_10* read it.
+    pixel_format, a name of YUV422_10_FORMATS.  'v210': frames are (N, H, row_words) of uint32 (torch: int32 holding the same
+    bits), a row being ceil(width / 6) groups of four words and whatever padding follows them (the conventional pitch is
+    ((width + 47) // 48) * 32 words); width, the frames' width in pixels, is required: the array does not say it.  'y210' / 'y212' /
+    'y216': frames are (N, H, W, 2) of uint16 (torch: int16 holding the same bits), the two words of pixel x being Y and, in turn,
+    U or V; width, if given, must be W.  The frame stride and the row stride are honoured in place (frames[a:b], frames[::2], padded
+    rows) where they are multiples of 16 (v210) / 8 (Y21x) bytes; any other layout -- an element stride, a row stride that is no such
+    multiple, negative strides -- is copied once to a packed array (Yuv422_10FramesView.copied).  matrix: a name of YUV_MATRIX_CODES
+    or a code; there is no default: nearly all 10-bit material is BT.709, and the wrong matrix raises no error.  A wrong dtype or
+    rank, an odd or missing width, rows shorter than the width's groups, a base that is not 16- (v210) / 8-byte (Y21x) aligned, an
+    unknown format or an unknown matrix: ValueError."""
+    mcode = yuv_matrix_code(matrix)
+    fmt = str(pixel_format).lower()
+    if fmt not in YUV422_10_FORMATS:
+        raise ValueError('pixel_format %r is not a packed 10-bit YUV 4:2:2 layout (%s)' % (pixel_format, ', '.join(YUV422_10_FORMATS)))
+    code = YUV422_10_FORMATS[fmt]
+    if code == YUV422_10_V210:
+        (frames, is_torch, shape, strides, ptr, on_device, device) = _unwrap32(frames)
+        if width is None:
+            raise ValueError('v210 frames need width=: the row of words does not say how many pixels it holds')
+        W = int(width)
+        if len(shape) != 3 or shape[1] == 0 or W <= 0 or W % 2 != 0:
+            raise ValueError('v210 frames must be (N, H, row_words) with an even width, not %s at width %r' % (shape, width))
+        (n, H, words) = shape
+        (row, align) = (v210_row_bytes(W), 16)
+        if words * 4 < row:
+            raise ValueError('v210 rows of %d words are shorter than the %d bytes of %d pixels' % (words, row, W))
+        (fs, rp, es) = strides
+        ok = es == 4
+    else:
+        (frames, is_torch, shape, strides, ptr, on_device, device) = _unwrap16(frames)
+        if len(shape) != 4 or shape[3] != 2 or shape[1] == 0 or shape[2] == 0 or shape[2] % 2 != 0 or (width is not None and int(width) != shape[2]):
+            raise ValueError('%s frames must be (N, H, W, 2) with an even W (and width, if given, W), not %s at width %r' % (fmt, shape, width))
+        (n, H, W, _two) = shape
+        (row, align) = (4 * W, 8)
+        (fs, rp, ps, es) = strides
+        ok = es == 2 and ps == 4
+    if ptr % align != 0:
+        raise ValueError('%s frames need a %d-byte aligned base' % (fmt, align))
+    # strides of dimensions of size 1 are never stepped over: make them what a packed array has
+    if H == 1:
+        rp = row
+    if n == 1:
+        fs = (H - 1) * rp + row if rp > 0 else 0
+    ok = ok and rp >= row and fs >= (H - 1) * rp + row and rp <= 2 ** 31 - 1 and (rp | fs) % align == 0
+    if not ok:
+        if code == YUV422_10_V210:
+            frames = frames[:, :, :row // 4]   # the groups alone: a packed row of them is a multiple of 16 bytes
+        (frames, ptr) = _packed_copy(frames, is_torch)
+        (rp, fs) = (row, H * row)
+    extent = (n - 1) * fs + (H - 1) * rp + row if n else 0
+    return Yuv422_10FramesView(int(ptr), on_device, device, code, n, H, W, int(rp), int(fs), int(extent), not ok, frames, mcode)
+
+
 class PlanarFramesView(NamedTuple):
     """How the kernels read a batch of planar (channels-first) frames in place (planar_frames_view)."""
     ptr: int            # address of frame 0's first plane
@@ -1047,6 +1160,21 @@ class Context:
         check(self._L.melf_yuv16_to_bgr(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
         return out
 
+    def process_yuv422_10(self, frames_ptr, desc):
+        """Host packed 10-bit YUV 4:2:2 frames (melf_process_yuv422_10; desc: a MelfYuv422_10Frames, e.g.
+        yuv422_10_frames_view(...).descriptor()) -> records."""
+        return self._host(self._L.melf_process_yuv422_10, frames_ptr, desc)
+
+    def process_yuv422_10_dev(self, d_frames_ptr, desc, d_results_ptr=None, want_host=True, stream=None):
+        """Packed 10-bit YUV 4:2:2 frames in HBM (melf_process_yuv422_10_dev, as process_frames_dev).  Returns records when want_host."""
+        return self._dev(self._L.melf_process_yuv422_10_dev, d_frames_ptr, desc, d_results_ptr, want_host, stream)
+
+    def yuv422_10_to_bgr(self, frames_ptr, desc):
+        """Unpacking and conversion alone (melf_yuv422_10_to_bgr): host packed 10-bit YUV 4:2:2 frames -> (n, H, W, 3) BGR."""
+        out = np.empty((desc.n, desc.H, desc.W, 3), np.uint8)
+        check(self._L.melf_yuv422_10_to_bgr(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
+        return out
+
     def process_planes(self, frames_ptr, desc):
         """Host planar frames (melf_process_planes; desc: a MelfPlanarFrames, e.g. planar_frames_view(...).descriptor()) -> records."""
         return self._host(self._L.melf_process_planes, frames_ptr, desc)
@@ -1234,7 +1362,7 @@ class Context:
         None before the first launch), 'nr' (window rows a lane requests up front) and 'ws_max' (the context's largest window)."""
         (nr, fam, ws) = (C.c_int(0), C.c_int(0), C.c_int(0))
         check(self._L.melf_ctx_last_dials(self._h, C.byref(nr), C.byref(fam), C.byref(ws)))
-        names = DIALS_FAMILIES + DIALS16_FAMILIES   # (the 16-bit families' values go on from the twelve's)
+        names = DIALS_FAMILIES + DIALS16_FAMILIES + DIALS10_FAMILIES   # (the later families' values go on from the twelve's)
         return dict(family=names[fam.value] if fam.value >= 0 else None, nr=nr.value, ws_max=ws.value)
 
     def set_profiling(self, on):

@@ -292,6 +292,30 @@ __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_v
 #include "k_dials_body.inc"
 }
 
+// Packed 10-bit YUV 4:2:2 frames (melf_process_yuv422_10*): v210, rows of whole 16-byte groups of six pixels, and Y210 / Y212 /
+// Y216, macropixels of four 16-bit words.  Nothing but the matrix travels with the frames; one instantiation per format and NR.
+template <int NR>
+__global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_vgpr(DIALS_VGPRS))) void k_v210_needle(DialsSrc src, YuvMatrix ymat, melf_params P,
+                                                                const DialGeom* __restrict__ geom,
+                                                                const uint64_t* __restrict__ rowmasks,
+                                                                const MatchPartial* __restrict__ partials,
+                                                                int nparts, int rw, melf_result* __restrict__ results)
+{
+    using Src = DialV210; const Src::Args sargs{ymat};
+#include "k_dials_body.inc"
+}
+
+template <int NR>
+__global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_vgpr(DIALS_VGPRS))) void k_y210_needle(DialsSrc src, YuvMatrix ymat, melf_params P,
+                                                                const DialGeom* __restrict__ geom,
+                                                                const uint64_t* __restrict__ rowmasks,
+                                                                const MatchPartial* __restrict__ partials,
+                                                                int nparts, int rw, melf_result* __restrict__ results)
+{
+    using Src = DialY210; const Src::Args sargs{ymat};
+#include "k_dials_body.inc"
+}
+
 // Planar frames (melf_process_planes*): the B, G and R planes at `planes` in a frame.  Past its loads the body is the one of 4-byte
 // B G R pixels.
 template <int NR>
@@ -350,6 +374,8 @@ DialsLaunch launch_dials(const DialsSrc& src, const FrameLayout& lay, int n, con
                 else { ran.family = MELF_DIALS_YP_SUB1_STEP2; go(k_yp_needle<1, 2, NR>, yp, *lay.mx); }
             }
         }
+        else if (pix == PIX_V210) { ran.family = MELF_DIALS10_V210; go(k_v210_needle<NR>, *lay.mx); }
+        else if (pix == PIX_Y210) { ran.family = MELF_DIALS10_Y210; go(k_y210_needle<NR>, *lay.mx); }
         else if (pix == PIX_PLANAR) { ran.family = MELF_DIALS_PLANAR; go(k_planar_needle<NR>, lay.planes); }
         else if (pix_p422(pix)) { ran.family = MELF_DIALS_P422; go(k_p422_needle<NR>, p422_sel(pix), *lay.mx); }
         else if (pix == PIX_NV12) { ran.family = MELF_DIALS_NV12; go(k_yneedle<false, NR>, lay.yuv, *lay.mx); }

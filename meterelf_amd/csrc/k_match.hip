@@ -19,6 +19,7 @@
 #include "melf_device.h"
 #include "melf_internal.h"
 #include "melf_y16_addr.h"
+#include "melf_p10_addr.h"
 
 namespace melf {
 
@@ -36,7 +37,8 @@ __device__ inline bool better(float v, int i, float bv, int bi)
 // 24 = planar / semi-planar YUV of any subsampling (melf_process_yuv_planar*; yuv: YuvPlanarPlanes; a Y byte and the chroma bytes
 // at (y >> sub_y, x >> sub_x) per pixel, byte loads: the shifts and the sample step are wave-uniform scalars); 25 = 16-bit planar /
 // semi-planar YUV (melf_process_yuv16*; yuv: Yuv16Planes; a Y sample and the chroma samples at (y >> sub_y, x >> 1) per pixel, 2-byte
-// loads, each reduced to 8 bits by y16::reduce).
+// loads, each reduced to 8 bits by y16::reduce); 26 / 27 = packed 10-bit YUV 4:2:2, v210 / Y210 (melf_process_yuv422_10*; no yuv: the
+// two words of the pixel's group / the two dwords of its macropixel, melf_p10_addr.h).
 struct NoYuv {};
 struct P422Sel { uint32_t sel; };
 template <int PX, class YUV = NoYuv>
@@ -95,6 +97,19 @@ __device__ __forceinline__ void match_tile(MatchSrc src, MatchGeom g, const uint
                             const uint32_t sft = (uint32_t)yuv.shift;
                             const YuvChroma c = yuv_chroma((int)y16::reduce(*(const uint16_t*)(urow + co), sft), (int)y16::reduce(*(const uint16_t*)(vrow + co), sft), mx);
                             v = (uint32_t)yuv_lightness((int)y16::reduce(*(const uint16_t*)(prow + (size_t)(src.x0 + x) * 2), sft), yuv_cmax(c), yuv_cmin(c), mx);
+                        } else if constexpr (PX == 26 || PX == 27) {
+                            const int fx = src.x0 + x;
+                            uint32_t s;
+                            if constexpr (PX == 26) {
+                                const uint32_t* w = (const uint32_t*)(img + p10::v210_px_off(src.y0 + y, (size_t)src.row_stride, fx));
+                                const int ph = p10::v210_phase(fx);
+                                s = p10::v210_px_yuv(w[0], w[1], ph >> 1, ph & 1);
+                            } else {
+                                const uint32_t* w = (const uint32_t*)(img + p10::y210_px_off(src.y0 + y, (size_t)src.row_stride, fx));
+                                s = p10::y210_px_yuv(w[0], w[1], fx & 1);
+                            }
+                            const YuvChroma c = yuv_chroma((int)((s >> 8) & 255u), (int)(s >> 16), mx);
+                            v = (uint32_t)yuv_lightness((int)(s & 255u), yuv_cmax(c), yuv_cmin(c), mx);
                         } else if constexpr (PX == 22) {
                             const int fx = src.x0 + x;
                             const uint32_t m = __builtin_amdgcn_perm(0u, *(const uint32_t*)(prow + (size_t)(fx >> 1) * 4), yuv.sel);
@@ -249,6 +264,21 @@ __global__ __launch_bounds__(256) void k_y16_match(MatchSrc src, Yuv16Planes yuv
     match_tile<25, Yuv16Planes>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts, yuv, mx);
 }
 
+// packed 10-bit YUV 4:2:2 (melf_process_yuv422_10*): the dot4 matcher with the pixel's two words (v210) / its macropixel (Y210)
+__global__ __launch_bounds__(256) void k_v210_match(MatchSrc src, YuvMatrix mx, MatchGeom g, const uint32_t* __restrict__ tplT,
+                                                    int rh, int rw, int nrb, float* __restrict__ result_map,
+                                                    MatchPartial* __restrict__ partials, int nparts)
+{
+    match_tile<26, NoYuv>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts, NoYuv{}, mx);
+}
+
+__global__ __launch_bounds__(256) void k_y210_match(MatchSrc src, YuvMatrix mx, MatchGeom g, const uint32_t* __restrict__ tplT,
+                                                    int rh, int rw, int nrb, float* __restrict__ result_map,
+                                                    MatchPartial* __restrict__ partials, int nparts)
+{
+    match_tile<27, NoYuv>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts, NoYuv{}, mx);
+}
+
 int match_parts(const MatchGeom& g, int rows, int cols)
 {
     const int rh = rows - g.th + 1, rw = cols - g.tw + 1;
@@ -273,6 +303,10 @@ void launch_match(const MatchSrc& src, const FrameLayout& lay, int n, const Matc
     else if (pix == PIX_YUVP)
         hipLaunchKernelGGL(k_yp_match, grid, block, shmem, stream, src, lay.yuvp, *lay.mx, g, d_tplT, rh, rw, nrb, d_result_map,
                            d_partials, nparts);
+    else if (pix == PIX_V210)
+        hipLaunchKernelGGL(k_v210_match, grid, block, shmem, stream, src, *lay.mx, g, d_tplT, rh, rw, nrb, d_result_map, d_partials, nparts);
+    else if (pix == PIX_Y210)
+        hipLaunchKernelGGL(k_y210_match, grid, block, shmem, stream, src, *lay.mx, g, d_tplT, rh, rw, nrb, d_result_map, d_partials, nparts);
     else if (pix == PIX_PLANAR)
         hipLaunchKernelGGL(k_planar_match, grid, block, shmem, stream, src, lay.planes, g, d_tplT, rh, rw, nrb, d_result_map,
                            d_partials, nparts);

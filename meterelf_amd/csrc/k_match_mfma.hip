@@ -36,6 +36,7 @@
 
 #include "melf_internal.h"
 #include "melf_y16_addr.h"
+#include "melf_p10_addr.h"
 #include "melf_prep_addr.h"
 
 namespace melf {
@@ -179,6 +180,25 @@ __global__ __launch_bounds__(256) void k_y16_lplane(MatchSrc src, Yuv16Planes yu
 #include "prep_lplane_body.inc"
 }
 #undef MELF_Y16_BODY
+
+// Packed 10-bit YUV 4:2:2 frames (melf_process_yuv422_10*): v210, six pixels in a 16-byte group, and Y210 / Y212 / Y216, two pixels
+// in a macropixel of four 16-bit words.  Every sample is taken as its top 8 bits; L straight from Y, U, V as in k_p422_lplane.
+#define MELF_V210_BODY
+__global__ __launch_bounds__(256) void k_v210_lplane(MatchSrc src, YuvMatrix mx, int nframes, int nkb, int rows_pad, int tw, int rwp, int pairs,
+                                                     int8_t* __restrict__ Lg, uint16_t* __restrict__ R)
+{
+    constexpr int PX = 26;
+#include "prep_lplane_body.inc"
+}
+#undef MELF_V210_BODY
+#define MELF_Y210_BODY
+__global__ __launch_bounds__(256) void k_y210_lplane(MatchSrc src, YuvMatrix mx, int nframes, int nkb, int rows_pad, int tw, int rwp, int pairs,
+                                                     int8_t* __restrict__ Lg, uint16_t* __restrict__ R)
+{
+    constexpr int PX = 27;
+#include "prep_lplane_body.inc"
+}
+#undef MELF_Y210_BODY
 
 // ---------------------------------------------------------------------------
 // k_match_mfma
@@ -891,9 +911,13 @@ void launch_match_prep(const MatchSrc& src, const FrameLayout& lay, int n, int g
         (void)hipFuncSetAttribute((const void*)k_yp_lplane<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute((const void*)k_y16_lplane<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute((const void*)k_y16_lplane<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_v210_lplane, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_y210_lplane, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         attr_set[dev] = true;
     }
-    if (pix == PIX_YUV16) {
+    if (pix == PIX_V210) hipLaunchKernelGGL(k_v210_lplane, grid, block, pre_bytes, stream, src, *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    else if (pix == PIX_Y210) hipLaunchKernelGGL(k_y210_lplane, grid, block, pre_bytes, stream, src, *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    else if (pix == PIX_YUV16) {
         const Yuv16Planes& yp = lay.y16;
         auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, pre_bytes, stream, src, yp, *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r); };
         if (yp.c_step == 1) go(k_y16_lplane<1>); else go(k_y16_lplane<2>);

@@ -8,6 +8,7 @@
 #include "melf_device.h"
 #include "melf_internal.h"
 #include "melf_y16_addr.h"
+#include "melf_p10_addr.h"
 
 namespace melf {
 
@@ -139,6 +140,57 @@ void launch_y16_to_bgr(const uint8_t* d_src, int n, int H, int W, int y_pitch, s
         dim3 grid((W + 255) / 256, H < 65535 ? H : 65535, m), block(256);
         hipLaunchKernelGGL(k_y16_to_bgr, grid, block, 0, stream, d_src + (size_t)f0 * frame_stride, H, W, y_pitch, frame_stride, yp, mx,
                            d_dst + (size_t)f0 * H * W * 3);
+    }
+}
+
+// Packed 10-bit YUV 4:2:2 -> BGR alone: the stage kernels behind melf_yuv422_10_to_bgr.  One thread per pixel: the two words of its
+// group that hold its three fields (v210) or the two dwords of its macropixel (Y210), at the offsets and with the bit selection of
+// melf_p10_addr.h that every reading kernel shares, three bytes out.  They pin the addressing, the selection and the arithmetic for
+// every sample value at every position of a group; like k_yuv2bgr no hot path.
+template <bool V210>
+__device__ __forceinline__ void p10_to_bgr(const uint8_t* __restrict__ src, int H, int W, int row_pitch, size_t frame_stride, const YuvMatrix& mx,
+                                           uint8_t* __restrict__ dst)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.z;
+    if (x >= W) return;
+    const uint8_t* frame = src + (size_t)f * frame_stride;
+    for (int y = blockIdx.y; y < H; y += gridDim.y) {
+        uint32_t s;
+        if constexpr (V210) {
+            const uint32_t* w = (const uint32_t*)(frame + p10::v210_px_off(y, (size_t)row_pitch, x));
+            const int ph = p10::v210_phase(x);
+            s = p10::v210_px_yuv(w[0], w[1], ph >> 1, ph & 1);
+        } else {
+            const uint32_t* w = (const uint32_t*)(frame + p10::y210_px_off(y, (size_t)row_pitch, x));
+            s = p10::y210_px_yuv(w[0], w[1], x & 1);
+        }
+        const uint32_t p = yuv_bgr((int)(s & 255u), yuv_chroma((int)((s >> 8) & 255u), (int)(s >> 16), mx), mx);
+        uint8_t* o = dst + (((size_t)f * H + y) * (size_t)W + (size_t)x) * 3;
+        o[0] = (uint8_t)p; o[1] = (uint8_t)(p >> 8); o[2] = (uint8_t)(p >> 16);
+    }
+}
+__global__ __launch_bounds__(256) void k_v210_to_bgr(const uint8_t* __restrict__ src, int H, int W, int row_pitch, size_t frame_stride, YuvMatrix mx,
+                                                     uint8_t* __restrict__ dst)
+{
+    p10_to_bgr<true>(src, H, W, row_pitch, frame_stride, mx, dst);
+}
+__global__ __launch_bounds__(256) void k_y210_to_bgr(const uint8_t* __restrict__ src, int H, int W, int row_pitch, size_t frame_stride, YuvMatrix mx,
+                                                     uint8_t* __restrict__ dst)
+{
+    p10_to_bgr<false>(src, H, W, row_pitch, frame_stride, mx, dst);
+}
+
+void launch_p10_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int row_pitch, size_t frame_stride, const YuvMatrix& mx,
+                       uint8_t* d_dst, hipStream_t stream)
+{
+    // at most 65 535 frames per launch (grid z); a workgroup row takes every 65 535th image row (grid y)
+    for (int f0 = 0; f0 < n; f0 += 65535) {
+        const int m = n - f0 < 65535 ? n - f0 : 65535;
+        dim3 grid((W + 255) / 256, H < 65535 ? H : 65535, m), block(256);
+        const uint8_t* s = d_src + (size_t)f0 * frame_stride;
+        uint8_t* d = d_dst + (size_t)f0 * H * W * 3;
+        if (pix == PIX_V210) hipLaunchKernelGGL(k_v210_to_bgr, grid, block, 0, stream, s, H, W, row_pitch, frame_stride, mx, d);
+        else hipLaunchKernelGGL(k_y210_to_bgr, grid, block, 0, stream, s, H, W, row_pitch, frame_stride, mx, d);
     }
 }
 

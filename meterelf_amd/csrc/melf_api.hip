@@ -1230,6 +1230,15 @@ extern "C" int melf_process_yuv16_dev(melf_ctx* c, const void* d_frames, const m
     return batch_dev(c, d_frames, b, d_results, out_host, stream_);
 }
 
+extern "C" int melf_process_yuv422_10_dev(melf_ctx* c, const void* d_frames, const melf_yuv422_10_frames* f, void* d_results,
+                                          melf_result* out_host, void* stream_)
+{
+    FrameBatch b;
+    if (int rc = checked(c, check_yuv422_10(d_frames, f, &b))) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return batch_dev(c, d_frames, b, d_results, out_host, stream_);
+}
+
 extern "C" int melf_process_planes_dev(melf_ctx* c, const void* d_frames, const melf_planar_frames* f, void* d_results,
                                        melf_result* out_host, void* stream_)
 {
@@ -1533,6 +1542,28 @@ static int host_p422(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& 
     });
 }
 
+// Packed 10-bit YUV 4:2:2 (v210, Y210): as host_p422, the staged frame a small frame of the same format, its x origin rounded down
+// and its far corner up to whole groups of 6 pixels (v210: rows hold whole groups, so the far corner stays inside the row) or whole
+// macropixels (Y210); the rows are copied as they are, no sample is unpacked on the CPU.  Work items: the rows in blocks of 32.
+static int host_yuv422_10(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host)
+{
+    Crop cr;
+    if (int rc = host_crop(c, b, out_host, &cr)) return rc;
+    const bool v210 = b.lay.pix == PIX_V210;
+    const int unit = v210 ? 6 : 2;
+    const int crows = cr.rows, y0 = cr.y0, ex0 = cr.x0 / unit * unit;
+    const int sw = (cr.x1 + unit - 1) / unit * unit - ex0;   // the small frame's width: whole groups / macropixels
+    const size_t row_pitch = (size_t)b.row_stride;
+    const size_t rbytes = v210 ? (size_t)(sw / 6) * 16 : (size_t)sw * 4, x_off = v210 ? (size_t)(ex0 / 6) * 16 : (size_t)ex0 * 4;
+    const size_t pitch = pitch64(rbytes);
+    const StagePlan sp = {{0, crows, sw, crows * pitch + 128, (int)pitch, FrameLayout::yuv422_10(b.lay.pix, *b.lay.mx, crows * pitch)},
+                          {cr.x0 - ex0, 0, cr.x0 - ex0 + cr.cols, crows}, (crows + 31) / 32};
+    return stage_host_frames(c, frames_host, b.n, b.frame_stride, sp, out_host, [=](const uint8_t* frame, uint8_t* small, int part) {
+        const int r0 = part * 32, r1 = r0 + 32 < crows ? r0 + 32 : crows;
+        for (int y = r0; y < r1; ++y) memcpy(small + (size_t)y * pitch, frame + (size_t)(y0 + y) * row_pitch + x_off, rbytes);
+    });
+}
+
 // Planar / semi-planar YUV of any subsampling and sample size: the staged frame is a small frame of the same layout -- the same
 // subsampling, sample step and order of U and V, and for 16-bit samples the same shift, the samples copied as they are (nothing is
 // reduced on the CPU) --, the Y rows of the crop with its origin rounded down (and its far corner up) to whole chroma blocks
@@ -1681,6 +1712,14 @@ extern "C" int melf_process_yuv16(melf_ctx* c, const void* frames_host, const me
     return host_yuv16(c, (const uint8_t*)frames_host, b, out_host);
 }
 
+extern "C" int melf_process_yuv422_10(melf_ctx* c, const void* frames_host, const melf_yuv422_10_frames* f, melf_result* out_host)
+{
+    FrameBatch b;
+    if (int rc = checked(c, check_yuv422_10(frames_host, f, &b))) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return host_yuv422_10(c, (const uint8_t*)frames_host, b, out_host);
+}
+
 extern "C" int melf_process_planes(melf_ctx* c, const void* frames_host, const melf_planar_frames* f, melf_result* out_host)
 {
     FrameBatch b;
@@ -1699,7 +1738,9 @@ static int to_bgr(melf_ctx* c, const void* frames_host, const FrameBatch& b, uin
     if (int rc = grow(&c->d_stage_in, &c->stage_in_cap, in_bytes)) return rc;
     if (int rc = grow(&c->d_stage_out, &c->stage_out_cap, out_bytes)) return rc;
     HIP_TRY(hipMemcpyAsync(c->d_stage_in, frames_host, in_bytes, hipMemcpyHostToDevice, c->stream));
-    if (b.lay.pix == PIX_YUV16)
+    if (pix_p10(b.lay.pix))
+        launch_p10_to_bgr(c->d_stage_in, b.lay.pix, b.n, b.H, b.W, b.row_stride, b.frame_stride, *b.lay.mx, c->d_stage_out, c->stream);
+    else if (b.lay.pix == PIX_YUV16)
         launch_y16_to_bgr(c->d_stage_in, b.n, b.H, b.W, b.row_stride, b.frame_stride, b.lay.y16, *b.lay.mx, c->d_stage_out, c->stream);
     else if (b.lay.pix == PIX_YUVP)
         launch_yuvp_to_bgr(c->d_stage_in, b.n, b.H, b.W, b.row_stride, b.frame_stride, b.lay.yuvp, *b.lay.mx, c->d_stage_out, c->stream);
@@ -1733,6 +1774,14 @@ extern "C" int melf_yuv16_to_bgr(melf_ctx* c, const void* frames_host, const mel
 {
     FrameBatch b;
     if (int rc = checked(c, check_yuv16(frames_host, f, &b))) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return to_bgr(c, frames_host, b, bgr_out_host);
+}
+
+extern "C" int melf_yuv422_10_to_bgr(melf_ctx* c, const void* frames_host, const melf_yuv422_10_frames* f, uint8_t* bgr_out_host)
+{
+    FrameBatch b;
+    if (int rc = checked(c, check_yuv422_10(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return to_bgr(c, frames_host, b, bgr_out_host);
 }

@@ -199,6 +199,53 @@ inline const char* check_yuv16(const void* frames, const melf_yuv16_frames* f, F
     return nullptr;
 }
 
+// melf_yuv422_10_frames (melf_process_yuv422_10*, melf_yuv422_10_to_bgr): v210 rows are whole 16-byte groups of six pixels, Y21x rows
+// macropixels of 8 bytes; the extent reaches to the end of the last row's last group / macropixel.  Its messages have names, in one
+// table: tests/p10_bounds_main.cpp sweeps this check and counts, through the table, that every one of them was produced
+// (tests/frame_checks_main.cpp does that for the six checks above, from their text).
+enum Yuv422_10Msg { P10_DESC_NULL, P10_FORMAT, P10_RESERVED, P10_SHAPE, P10_ODD_W, P10_PITCH_SMALL, P10_PITCH_LARGE, P10_STRIDE_SMALL,
+                    P10_V210_STRIDES, P10_Y210_STRIDES, P10_FRAMES_NULL, P10_V210_BASE, P10_Y210_BASE, P10_MESSAGES };
+constexpr const char* YUV422_10_MESSAGES[P10_MESSAGES] = {
+    "packed 10-bit YUV 4:2:2 frame descriptor is NULL",
+    "unknown packed 10-bit YUV 4:2:2 format",
+    "reserved field of the packed 10-bit YUV 4:2:2 frame descriptor is not 0",
+    "bad batch shape",
+    "YUV 4:2:2 frames need an even width",
+    "row_pitch smaller than a row",
+    "row_pitch too large",
+    "frame_stride smaller than a frame",
+    "v210 frames need a 16-byte aligned row_pitch and frame_stride",
+    "Y210 frames need an 8-byte aligned row_pitch and frame_stride",
+    "frames pointer is NULL",
+    "v210 frames need a 16-byte aligned base",
+    "Y210 frames need an 8-byte aligned base",
+};
+inline const char* check_yuv422_10(const void* frames, const melf_yuv422_10_frames* f, FrameBatch* b)
+{
+    const char* const* const msg = YUV422_10_MESSAGES;
+    if (!f) return msg[P10_DESC_NULL];
+    if (f->format != MELF_YUV422_10_V210 && f->format != MELF_YUV422_10_Y210) return msg[P10_FORMAT];
+    const YuvMatrix* mx = yuv_matrix(f->matrix);
+    if (!mx) return UNKNOWN_YUV_MATRIX;
+    if (f->reserved != 0) return msg[P10_RESERVED];
+    if (f->n < 0 || f->H <= 0 || f->W <= 0) return msg[P10_SHAPE];
+    if (f->W & 1) return msg[P10_ODD_W];
+    const bool v210 = f->format == MELF_YUV422_10_V210;
+    const int64_t row = v210 ? ((int64_t)f->W + 5) / 6 * 16 : (int64_t)f->W * 4;   // bytes of a row: whole groups / macropixels
+    if (f->row_pitch < row) return msg[P10_PITCH_SMALL];
+    if (f->row_pitch > INT32_MAX) return msg[P10_PITCH_LARGE];
+    const int64_t extent = (int64_t)(f->H - 1) * f->row_pitch + row;
+    if (f->frame_stride < extent) return msg[P10_STRIDE_SMALL];
+    const uint64_t amask = v210 ? 15 : 7;
+    if (((uint64_t)f->row_pitch | (uint64_t)f->frame_stride) & amask) return msg[v210 ? P10_V210_STRIDES : P10_Y210_STRIDES];
+    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch,
+                    FrameLayout::yuv422_10(v210 ? PIX_V210 : PIX_Y210, *mx, (size_t)extent)};
+    if (f->n == 0) return nullptr;
+    if (!frames) return msg[P10_FRAMES_NULL];
+    if ((uintptr_t)frames & amask) return msg[v210 ? P10_V210_BASE : P10_Y210_BASE];
+    return nullptr;
+}
+
 // melf_planar_frames (melf_process_planes*): the extent reaches to the last sample of the frame's last plane
 inline const char* check_planes(const void* frames, const melf_planar_frames* f, FrameBatch* b)
 {

@@ -100,6 +100,14 @@ struct Yuv16Planes {
     int c_step;            // samples from one sample of a chroma plane to the next in its row: 1 planar, 2 semi-planar
     int shift;             // low bits dropped from a sample, 0 .. 8
 };
+// Packed 10-bit YUV 4:2:2 frames (melf_process_yuv422_10*): the launch's pix.  PIX_V210: rows of whole 16-byte groups, four
+// little-endian words of three 10-bit fields each, six pixels a group in the order U Y V Y ..; base, frame_stride and row_stride
+// (bytes) are multiples of 16, so a group is one aligned 16-byte load.  PIX_Y210 (Y210, Y212, Y216): macropixels of four MSB-aligned
+// little-endian 16-bit words Y0 U Y1 V, 8 bytes for two pixels; base and strides are multiples of 8.  x0 and cols count pixels.  A
+// field / word is read as its top 8 bits (melf_p10_addr.h: field8, the high bytes), and from there on the arithmetic is that of the
+// packed 8-bit 4:2:2 frames.  Nothing travels with the pix but the matrix.
+constexpr int PIX_V210 = 56, PIX_Y210 = 57;
+inline bool pix_p10(int pix) { return pix == PIX_V210 || pix == PIX_Y210; }
 
 // How the frames of one launch lie in memory, beside the base, the strides and the rectangle of MatchSrc / DialsSrc: the pixel
 // layout and what goes with it.  Host side only: the launchers hand the kernels the members by value.  Made by the makers below
@@ -108,7 +116,7 @@ struct FrameLayout {
     int pix;
     YuvPlanes yuv;         // pix_yuv(pix): the chroma planes
     PlanarPlanes planes;   // PIX_PLANAR: where the three planes start
-    const YuvMatrix* mx;   // pix_yuv(pix), pix_p422(pix), PIX_YUVP, PIX_YUV16: the frames' colour conversion, never NULL there
+    const YuvMatrix* mx;   // pix_yuv(pix), pix_p422(pix), pix_p10(pix), PIX_YUVP, PIX_YUV16: the frames' colour conversion, never NULL there
     size_t extent;         // bytes a kernel may read of the LAST frame, from its first byte (the others: frame_stride)
     YuvPlanarPlanes yuvp;  // PIX_YUVP: the chroma planes and their subsampling (mx: the conversion, as above)
     Yuv16Planes y16;       // PIX_YUV16: the chroma planes of 16-bit samples and the reduction (mx: the conversion, as above)
@@ -129,6 +137,10 @@ struct FrameLayout {
     static FrameLayout yuv16(const Yuv16Planes& yp, const YuvMatrix& mx, size_t extent)
     {
         return FrameLayout{PIX_YUV16, {}, {}, &mx, extent, {}, yp};
+    }
+    static FrameLayout yuv422_10(int pix /* PIX_V210, PIX_Y210 */, const YuvMatrix& mx, size_t extent)
+    {
+        return FrameLayout{pix, {}, {}, &mx, extent};
     }
     static FrameLayout planar(const PlanarPlanes& pl, size_t extent) { return FrameLayout{PIX_PLANAR, {}, pl, nullptr, extent}; }
     static FrameLayout plane(size_t extent) { return FrameLayout{PIX_PLANE, {}, {}, nullptr, extent}; }

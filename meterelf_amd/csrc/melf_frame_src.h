@@ -5,6 +5,7 @@
 #include "melf_device.h"
 #include "melf_internal.h"
 #include "melf_y16_addr.h"
+#include "melf_p10_addr.h"
 
 namespace melf {
 
@@ -432,6 +433,107 @@ struct DialP422 : DialFrame<DialP422> {
         const int fx0 = lane_fx0(wx0, npiece, pc);
         const int mstart = min(fx0 >> 1, mlim - 3);
         return Window{*this, quads, rs_u, mstart, (fx0 >> 1) != mstart, (bool)(fx0 & 1)};
+    }
+};
+
+// Packed 10-bit YUV 4:2:2 frames (melf_process_yuv422_10*), both formats: every sample leaves its load as its top 8 bits, and from
+// Y0 U Y1 V on the arithmetic is DialP422's.  The quads start at an even pixel of the frame (EVEN_QUADS, as DialYuv16): four pixels
+// from an even one are two whole pairs, 16 bytes in either format.  Offsets and guards: melf_p10_addr.h.
+// What a pair's four samples make: two B G R dwords.
+__device__ __forceinline__ void p10_pair_bgr(uint32_t y0, uint32_t u, uint32_t y1, uint32_t v, const YuvMatrix& ymat, uint32_t& b0, uint32_t& b1)
+{
+    const YuvChroma c = yuv_chroma<false>((int)u, (int)v, ymat);
+    b0 = yuv_bgr((int)y0, c, ymat);
+    b1 = yuv_bgr((int)y1, c, ymat);
+}
+
+// v210 (k_v210_needle): rows of whole 16-byte groups, six pixels each, twelve 10-bit fields U Y V Y ...  One pixel: the two words
+// of its group that hold its three fields.  A lane's quad from the even pixel fx0, p = fx0 % 6: the aligned group (p 0, 2) or the
+// 16 bytes from its third word on (p 4), one load16; the twelve fields of the 16 bytes are extracted at fixed positions and the
+// quad's eight picked by p -- which differs from lane to lane -- with selects, so every register array is indexed by constants.
+struct DialV210 : DialFrame<DialV210> {
+    static constexpr bool EVEN_QUADS = true;
+    struct Args { const YuvMatrix& ymat; };
+    const YuvMatrix& ymat;
+    __device__ __forceinline__ DialV210(const DialsSrc& s, const Args& a, const melf_params&, const uint8_t* frame_, int mx, int my)
+        : DialFrame(s, frame_, mx, my), ymat(a.ymat) {}
+    __device__ __forceinline__ int quad_shift(int wx0) const { return __builtin_amdgcn_readfirstlane(p10::quad_shift(fx_m, wx0)); }
+    __device__ __forceinline__ uint32_t px(int X, int Y) const
+    {
+        const int fx = fx_m + X, fy = fy_m + Y;
+        const uint32_t* w = (const uint32_t*)(frame + p10::v210_px_off(fy, rstride, fx));
+        const int ph = p10::v210_phase(fx);
+        const uint32_t s = p10::v210_px_yuv(w[0], w[1], ph >> 1, ph & 1);
+        return yuv_bgr((int)(s & 255u), yuv_chroma<false>((int)((s >> 8) & 255u), (int)(s >> 16), ymat), ymat);
+    }
+    struct Window {
+        const DialV210& S;
+        bool quads;
+        int rs_u, fx0;   // the lane's first pixel in the frame (even)
+        int f0;          // the quad's first field among the twelve of the 16 bytes loaded: 0, 4 or 2
+        __device__ __forceinline__ u32x4v request(int, int Y) const { return load16(S.frame + p10::v210_dial_off(S.fy_m + Y, (size_t)rs_u, fx0)); }
+        __device__ __forceinline__ u32x4v unpack(int, const u32x4v r) const
+        {
+            uint32_t F[12];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) F[i] = p10::field8(r[p10::field_word(i)], p10::field_bit(i));
+            uint32_t q[8];   // U Y V Y U Y V Y of the quad
+#pragma unroll
+            for (int k = 0; k < 8; ++k) q[k] = f0 == 0 ? F[k] : (f0 == 4 ? F[k + 4] : F[k + 2]);
+            u32x4v o;
+            uint32_t b0, b1;
+            p10_pair_bgr(q[1], q[0], q[3], q[2], S.ymat, b0, b1);
+            o.x = b0; o.y = b1;
+            p10_pair_bgr(q[5], q[4], q[7], q[6], S.ymat, b0, b1);
+            o.z = b0; o.w = b1;
+            return o;
+        }
+    };
+    // wx0: the quads' first column (the window's, less quad_shift), npiece: their count
+    __device__ __forceinline__ Window window(int wx0, int npiece, int pc, int, int rs_u, int tw) const
+    {
+        const int fx0 = p10::lane_fx0(fx_m, wx0, npiece, pc);
+        return Window{*this, p10::quads_inside(wx0, npiece, tw), rs_u, fx0, p10::v210_dial_field0(p10::v210_phase(fx0))};
+    }
+};
+
+// Y210 / Y212 / Y216 (k_y210_needle): macropixels of four MSB-aligned 16-bit words Y0 U Y1 V.  One pixel: its macropixel, two
+// aligned dwords.  A lane's quad from an even pixel is two macropixels, one 16-byte load, 8-byte aligned; a byte permute per
+// macropixel picks the four high bytes.
+struct DialY210 : DialFrame<DialY210> {
+    static constexpr bool EVEN_QUADS = true;
+    struct Args { const YuvMatrix& ymat; };
+    const YuvMatrix& ymat;
+    __device__ __forceinline__ DialY210(const DialsSrc& s, const Args& a, const melf_params&, const uint8_t* frame_, int mx, int my)
+        : DialFrame(s, frame_, mx, my), ymat(a.ymat) {}
+    __device__ __forceinline__ int quad_shift(int wx0) const { return __builtin_amdgcn_readfirstlane(p10::quad_shift(fx_m, wx0)); }
+    __device__ __forceinline__ uint32_t px(int X, int Y) const
+    {
+        const int fx = fx_m + X, fy = fy_m + Y;
+        const uint32_t* w = (const uint32_t*)(frame + p10::y210_px_off(fy, rstride, fx));
+        const uint32_t s = p10::y210_px_yuv(w[0], w[1], fx & 1);
+        return yuv_bgr((int)(s & 255u), yuv_chroma<false>((int)((s >> 8) & 255u), (int)(s >> 16), ymat), ymat);
+    }
+    struct Window {
+        const DialY210& S;
+        bool quads;
+        int rs_u, fx0;   // the lane's first pixel in the frame (even)
+        __device__ __forceinline__ u32x4v request(int, int Y) const { return load16(S.frame + p10::y210_dial_off(S.fy_m + Y, (size_t)rs_u, fx0)); }
+        __device__ __forceinline__ u32x4v unpack(int, const u32x4v r) const
+        {
+            const uint32_t ma = __builtin_amdgcn_perm(r.y, r.x, 0x07050301u), mb = __builtin_amdgcn_perm(r.w, r.z, 0x07050301u);   // Y0 U Y1 V each
+            u32x4v o;
+            uint32_t b0, b1;
+            p10_pair_bgr(ma & 255u, (ma >> 8) & 255u, (ma >> 16) & 255u, ma >> 24, S.ymat, b0, b1);
+            o.x = b0; o.y = b1;
+            p10_pair_bgr(mb & 255u, (mb >> 8) & 255u, (mb >> 16) & 255u, mb >> 24, S.ymat, b0, b1);
+            o.z = b0; o.w = b1;
+            return o;
+        }
+    };
+    __device__ __forceinline__ Window window(int wx0, int npiece, int pc, int, int rs_u, int tw) const
+    {
+        return Window{*this, p10::quads_inside(wx0, npiece, tw), rs_u, p10::lane_fx0(fx_m, wx0, npiece, pc)};
     }
 };
 

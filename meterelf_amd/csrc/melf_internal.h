@@ -181,6 +181,10 @@ void launch_yuvp_to_bgr(const uint8_t* d_src, int n, int H, int W, int y_pitch, 
 void launch_y16_to_bgr(const uint8_t* d_src, int n, int H, int W, int y_pitch, size_t frame_stride, const Yuv16Planes& yp,
                        const YuvMatrix& mx, uint8_t* d_dst, hipStream_t stream);
 
+// the same for packed 10-bit YUV 4:2:2 (melf_yuv422_10_to_bgr): pix PIX_V210 / PIX_Y210
+void launch_p10_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int row_pitch, size_t frame_stride, const YuvMatrix& mx,
+                       uint8_t* d_dst, hipStream_t stream);
+
 // the same for packed YUV 4:2:2 (melf_yuv422_to_bgr): n frames at d_src (row_pitch, frame_stride), pix PIX_YUYV / _UYVY / _YVYU
 void launch_p422_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int row_pitch, size_t frame_stride, const YuvMatrix& mx,
                         uint8_t* d_dst, hipStream_t stream);

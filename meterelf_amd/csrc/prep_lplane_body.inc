@@ -29,6 +29,16 @@
 //       68 interleaved bytes from the lower of the two offsets): aligned dwords and v_alignbit at the 2-byte phase (load_window16,
 //       k_match_mfma.hip), two samples a dword reduced to 8 bits by a packed 16-bit shift and minimum and packed four to a dword --
 //       from there on the arm is PX 24's.  Offsets, window lengths, rows_safe and the lane's own test: melf_y16_addr.h.
+//   With MELF_V210_BODY defined instead (k_v210_lplane): PX 26 = v210 frames (melf_process_yuv422_10*), rows of whole 16-byte groups
+//       of six pixels, everything 16-byte aligned.  The even-pixel window of 34 pixels is 17 pairs from pair slot s = (xs / 2) % 3 of
+//       the window's first group, which differs from lane to lane (32 pixels advance the slot by one): up to seven aligned 16-byte
+//       loads, of which a lane makes those that hold its own pixels (the rest of the window reads as zero), all 21 pairs of the seven
+//       groups unpacked to Y0 U Y1 V at fixed positions and 17 picked by unrolled selects on s: every register array is indexed by
+//       constants.  From the 17 dwords on the arm is PX 22's.  No load can leave the crop's row: there is no per-pixel path.
+//   With MELF_Y210_BODY defined instead (k_y210_lplane): PX 27 = Y210 / Y212 / Y216 frames, macropixels of four 16-bit words, everything
+//       8-byte aligned.  The window is 17 macropixels, 34 aligned dwords as eight 16-byte loads and two dwords; one byte permute per
+//       macropixel picks the high bytes Y0 U Y1 V, and from there on the arm is PX 22's.  Offsets, rows_safe and the lane's own
+//       test of both arms: melf_p10_addr.h.
 // The 8-bit arms (PX 3, 4, 20 .. 24) compute their windows' offsets and lengths, rows_safe and the lane's own test with the functions
 // of melf_prep_addr.h, as PX 25 does with melf_y16_addr.h: tests/prep_bounds_main.cpp sweeps the same functions on the CPU.
     constexpr int PB = prep::packed_pb(PX);     // bytes per pixel of the frame reads
@@ -83,6 +93,17 @@
     const y16::PrepRow prow16 = y16::prep_row((size_t)src.base, src.frame_stride, (size_t)src.row_stride, src.x0, src.y0, y, grp, nframes, nkb,
                                               yuv.u_off, yuv.v_off, (size_t)yuv.c_pitch, yuv.sub_y);
     const bool rows_safe = y16::prep_rows_safe(prow16, CSTEP, src.readable);
+#elif defined(MELF_V210_BODY)
+    (void)PB; (void)WIN;
+    // (here: every live lane of the row holds pixels of the window's first six groups, which then are loaded without a test of
+    // the lane's own)
+    const int xodd = src.x0 & 1;
+    const bool rows_safe = p10::v210_rows_safe(src.x0, src.cols, nkb);
+#elif defined(MELF_Y210_BODY)
+    (void)PB; (void)WIN;
+    // (the same for the 136-byte window of a Y210 lane: 17 macropixels from the one of its even pixel)
+    const int xodd = src.x0 & 1;
+    const bool rows_safe = p10::y210_rows_safe(grp, nframes, src.frame_stride, src.y0 + y, (size_t)src.row_stride, src.x0, nkb, src.readable);
 #elif defined(MELF_PLANAR_BODY)
     (void)PB; (void)WIN;
     // (the same for the three 36-byte windows of a planar lane, and for their first dword: with a base that is not 4-byte aligned
@@ -332,6 +353,76 @@
                                                        (int)y16::reduce(*(const uint16_t*)(pf + (size_t)yuv.v_off + co), y16_shift), mx);
                         const int L = yuv_lightness((int)y16::reduce(*(const uint16_t*)(pf + y16::px_y_off(src.y0 + y, (size_t)src.row_stride, fx)), y16_shift),
                                                     yuv_cmax(c), yuv_cmin(c), mx);
+                        w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
+                    }
+                }
+            } else
+#elif defined(MELF_V210_BODY)
+            if (PX == 26) {
+                const int xs = (src.x0 + xbeg) & ~1;   // the window's first pixel (even)
+                const int cnt = p10::v210_prep_groups(xs, src.x0 + xbeg + npx);   // groups that hold the lane's own pixels
+                const int s = p10::v210_slot(xs);      // pair slot of the window's first pair in its group
+                const u32x4m* q = (const u32x4m*)(src.base + p10::v210_prep_off((size_t)f * src.frame_stride, src.y0 + y, (size_t)src.row_stride, xs));
+                u32x4m d[p10::V210_PREP_GROUPS];
+                d[0] = q[0];
+#pragma unroll
+                for (int i = 1; i < p10::V210_PREP_GROUPS; ++i) {
+                    d[i] = u32x4m{0u, 0u, 0u, 0u};
+                    if ((i < 6 && rows_safe) || i < cnt) d[i] = q[i];
+                }
+                uint32_t pr[3 * p10::V210_PREP_GROUPS];   // every pair of the groups as Y0 U Y1 V
+#pragma unroll
+                for (int i = 0; i < 3 * p10::V210_PREP_GROUPS; ++i) {
+                    const int g = i / 3, pq = i % 3;
+                    const int iu = p10::pair_u(pq), iv = p10::pair_v(pq), iy0 = p10::pair_y(pq, 0), iy1 = p10::pair_y(pq, 1);
+                    pr[i] = p10::field8(d[g][p10::field_word(iy0)], p10::field_bit(iy0)) | p10::field8(d[g][p10::field_word(iu)], p10::field_bit(iu)) << 8 |
+                            p10::field8(d[g][p10::field_word(iy1)], p10::field_bit(iy1)) << 16 | p10::field8(d[g][p10::field_word(iv)], p10::field_bit(iv)) << 24;
+                }
+                uint32_t wl[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // L' of the window's 34 pixels
+#pragma unroll
+                for (int j = 0; j < 17; ++j) {
+                    const uint32_t m = s == 0 ? pr[j] : (s == 1 ? pr[j + 1] : pr[j + 2]);   // Y0 U Y1 V
+                    const YuvChroma c = yuv_chroma((int)((m >> 8) & 255u), (int)(m >> 24), mx);
+                    const int cmax = yuv_cmax(c), cmin = yuv_cmin(c);
+                    const int L0 = yuv_lightness((int)(m & 255u), cmax, cmin, mx), L1 = yuv_lightness((int)((m >> 16) & 255u), cmax, cmin, mx);
+                    wl[j >> 1] |= ((uint32_t)((L0 - 128) & 255) | (uint32_t)((L1 - 128) & 255) << 8) << ((j & 1) * 16);
+                }
+                // the lane's 32 pixels start at byte xodd of the window
+#pragma unroll
+                for (int i = 0; i < 8; ++i) w[i] = __builtin_amdgcn_alignbit(wl[i + 1], wl[i], (uint32_t)xodd * 8u);
+            } else
+#elif defined(MELF_Y210_BODY)
+            if (PX == 27) {
+                const int xs = (src.x0 + xbeg) & ~1;   // the window's first pixel (even)
+                const size_t o = p10::y210_prep_off((size_t)f * src.frame_stride, src.y0 + y, (size_t)src.row_stride, xs);
+                // the window may reach past the crop and the row (never used: masked) but must stay inside the caller's buffer
+                if (rows_safe || p10::y210_lane_ok(o, src.readable)) {
+                    const u32x4a4* q = (const u32x4a4*)(src.base + o);
+                    u32x4a4 d[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) d[i] = q[i];
+                    const uint32_t d32 = ((const uint32_t*)(src.base + o))[32], d33 = ((const uint32_t*)(src.base + o))[33];
+                    uint32_t wl[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // L' of the window's 34 pixels
+#pragma unroll
+                    for (int j = 0; j < 17; ++j) {
+                        const uint32_t lo = j < 16 ? d[j >> 1][(j & 1) * 2] : d32, hi = j < 16 ? d[j >> 1][(j & 1) * 2 + 1] : d33;   // Y0 U, Y1 V
+                        const uint32_t m = __builtin_amdgcn_perm(hi, lo, 0x07050301u);   // the high bytes: Y0 U Y1 V
+                        const YuvChroma c = yuv_chroma((int)((m >> 8) & 255u), (int)(m >> 24), mx);
+                        const int cmax = yuv_cmax(c), cmin = yuv_cmin(c);
+                        const int L0 = yuv_lightness((int)(m & 255u), cmax, cmin, mx), L1 = yuv_lightness((int)((m >> 16) & 255u), cmax, cmin, mx);
+                        wl[j >> 1] |= ((uint32_t)((L0 - 128) & 255) | (uint32_t)((L1 - 128) & 255) << 8) << ((j & 1) * 16);
+                    }
+                    // the lane's 32 pixels start at byte xodd of the window
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) w[i] = __builtin_amdgcn_alignbit(wl[i + 1], wl[i], (uint32_t)xodd * 8u);
+                } else {  // last bytes of the frame buffer: one macropixel per pixel, inside the row
+                    const uint8_t* pf = src.base + (size_t)f * src.frame_stride;
+                    for (int k = 0; k < npx; ++k) {
+                        const int fx = src.x0 + xbeg + k;
+                        const uint32_t* mp = (const uint32_t*)(pf + p10::y210_px_off(src.y0 + y, (size_t)src.row_stride, fx));
+                        const uint32_t sv = p10::y210_px_yuv(mp[0], mp[1], fx & 1);
+                        const YuvChroma c = yuv_chroma((int)((sv >> 8) & 255u), (int)(sv >> 16), mx);
+                        const int L = yuv_lightness((int)(sv & 255u), yuv_cmax(c), yuv_cmin(c), mx);
                         w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
                     }
                 }

@@ -341,9 +341,10 @@ int melf_yuv_planar_to_bgr(melf_ctx* ctx, const void* frames_host, const melf_yu
  * base, y_pitch, c_pitch, u_offset, v_offset or frame_stride; y_pitch < 2 * W bytes; c_pitch smaller than a chroma row ((W >> 1) *
  * c_step samples of 2 bytes); a pitch > 2^31 - 1; a chroma plane closer to the other than its span (overlapping) or starting
  * inside the Y plane's span; a frame_stride smaller than the span of one frame.
- * Out of scope: sub_x = 0 (4:4:4 / 4:4:0 at 16 bits); big-endian samples; BT.2020 (and any transfer function: the samples are
- * taken as they are); rounding or dithering of the dropped bits.  (The packed 10-bit formats, v210 and Y210 / Y212 / Y216:
- * melf_process_yuv422_10*, below.) */
+ * Out of scope: sub_x = 0 (planar and semi-planar 4:4:4 / 4:4:0 at 16 bits: yuv444p10le, P410); big-endian samples; BT.2020 (and any
+ * transfer function: the samples are taken as they are); rounding or dithering of the dropped bits.  (The packed 10-bit formats,
+ * v210 and Y210 / Y212 / Y216: melf_process_yuv422_10*, below.  4:4:4 at 10 bits as one 32-bit word per pixel, Y410 / XV30:
+ * melf_process_packed32*, below.) */
 typedef struct melf_yuv16_frames {
     int32_t matrix;                             /* MELF_YUV_BT* as above (the four codes; 1 stays invalid) */
     int32_t n, H, W;                            /* W even; H even if sub_y                                */
@@ -397,8 +398,9 @@ int melf_yuv16_to_bgr(melf_ctx* ctx, const void* frames_host, const melf_yuv16_f
  * load of the kernels reaches outside.  MELF_ERR_INVALID (melf_last_error says which) before anything is launched or copied for:
  * a NULL descriptor or NULL frames; an unknown format or matrix; reserved != 0; H or W <= 0, n < 0 (n == 0 passes); an odd W; a
  * row_pitch smaller than a row or > 2^31 - 1; a frame_stride smaller than a frame; a misaligned base, row_pitch or frame_stride.
- * Out of scope: big-endian and LSB-aligned Y21x; Y410 and other packed 4:4:4; the r210 RGB format; rounding or dithering of the
- * dropped bits; BT.2020 and transfer functions; interpolated chroma. */
+ * Out of scope: big-endian and LSB-aligned Y21x; the big-endian r210 RGB format; rounding or dithering of the dropped bits; BT.2020
+ * and transfer functions; interpolated chroma.  (Y410 and the other 4:4:4 formats of one 32-bit word per pixel, X2RGB10 among
+ * them: melf_process_packed32*, below.) */
 enum { MELF_YUV422_10_V210 = 0, MELF_YUV422_10_Y210 = 1 };   /* Y210: also Y212, Y216 */
 typedef struct melf_yuv422_10_frames {
     int32_t format, matrix;                     /* MELF_YUV422_10_*; matrix: MELF_YUV_BT* as above        */
@@ -418,6 +420,61 @@ int melf_process_yuv422_10_dev(melf_ctx* ctx, const void* d_frames, const melf_y
                                melf_result* out_host, void* stream);
 /* Stage entry point (parity tests, and a debug view for callers): unpacking and conversion alone, n packed H x W x 3 BGR frames out. */
 int melf_yuv422_10_to_bgr(melf_ctx* ctx, const void* frames_host, const melf_yuv422_10_frames* f, uint8_t* bgr_out_host);
+
+/* ---- the same path for 4:4:4 frames of ONE 32-BIT WORD PER PIXEL: AYUV / VUYA (8-bit) and Y410 / XV30 (10-bit) as D3D11, VA-API and
+ * oneVPL deliver HEVC RExt, AV1 and VP9 4:4:4; XRGB2101010 / XBGR2101010 (R10G10B10A2) as DRM scan-out, DXGI desktop duplication and
+ * 10-bit camera ISPs deliver RGB ----
+ * A pixel is one little-endian 32-bit word.  It holds three 8-bit reads at bit positions pos[0..2], each a pure selection of bits:
+ *     s8_k = (word >> pos[k]) & 255
+ * For a 10-bit field at bit o, pos = o + 2: the field's top 8 bits, by truncation, as for v210 and P010.  For byte b, pos = 8 b.
+ * Every other bit of the word is ignored, whatever it holds: alpha / X bits and the low bits of 10-bit fields.
+ * MELF_P32_YUV: the reads are Y, U, V, and the records are byte-identical to melf_process_yuv_planar(_dev) on the 8-bit 4:4:4 planar
+ * frame (i444: sub_x = sub_y = 0) with the same n, H, W and matrix whose samples are the s8 -- and so, by that entry point's
+ * contract, to melf_process_batch(_dev) on the BGR frame the integer conversion above makes of it (any of the four matrix codes; 1
+ * stays invalid).  MELF_P32_RGB: the reads are R, G, B, and the records are byte-identical to melf_process_batch(_dev) on the packed
+ * BGR frame of the s8; nothing is converted and matrix must be 0.  Neither the 8-bit frame nor a BGR frame is ever formed: the
+ * kernels read the words in place, and only the meter_rect crop of them.
+ * The layouts by name, as drm_fourcc.h and ffmpeg's pixfmt.h state them (pos: Y, U, V / R, G, B):
+ *     name                                   colour  pos         the word
+ *     VUYA / VUYX                            YUV     16,  8,  0  bytes V U Y A in memory (what Microsoft and DRM call AYUV)
+ *     AYUV                                   YUV      8, 16, 24  bytes A Y U V in memory (ffmpeg's and GStreamer's byte order)
+ *     UYVA                                   YUV      8,  0, 16  bytes U Y V A in memory
+ *     Y410 / XV30                            YUV     12,  2, 22  U bits 0-9, Y 10-19, V 20-29, A 30-31
+ *     V30X                                   YUV     14,  4, 24  X bits 0-1, U 2-11, Y 12-21, V 22-31
+ *     X2RGB10 (XRGB2101010)                  RGB     22, 12,  2  B bits 0-9, G 10-19, R 20-29, X 30-31
+ *     X2BGR10 (XBGR2101010, R10G10B10A2)     RGB      2, 12, 22  R bits 0-9, G 10-19, B 20-29, X 30-31
+ * and any other layout three non-overlapping positions express.  Row y of frame f starts at frames + f * frame_stride + y *
+ * row_pitch and is W words; any W, any H.  The base, row_pitch and frame_stride are multiples of 4.  A frame extends over
+ * (H - 1) * row_pitch + 4 * W bytes; the buffer must hold (n - 1) * frame_stride + that extent, and need hold nothing behind that
+ * nor before the base: no load of the kernels reaches outside.  MELF_ERR_INVALID (melf_last_error says which) before anything is
+ * launched or copied for: a NULL descriptor or NULL frames; a colour outside the two codes; an unknown matrix for YUV, a non-zero
+ * matrix for RGB; a non-zero reserved field; a pos[k] outside 0 .. 24; two reads that overlap (|pos[i] - pos[j]| < 8); H or W <= 0,
+ * n < 0 (n == 0 passes); a row_pitch smaller than a row or > 2^31 - 1; a frame_stride smaller than a frame; a base, row_pitch or
+ * frame_stride that is not 4-byte aligned.
+ * Measured on one MI355X (1024-frame config-3 steps, profiles/packed32/packed32_rate.txt): Y410 in place 0.2614 ms a step, VUYA
+ * 0.2619, X2RGB10 0.2500 -- 1.05, 1.05 and 1.01 times BGRA through melf_process_frames (0.2484 ms), which moves the same bytes per
+ * pixel -- where unpacking every whole Y410 frame to three planes first and reading those takes 4.2432 ms, 16.2 times as long.
+ * Out of scope: 64-bit pixels (Y416, XV36 / XV48, RGBA64); planar and semi-planar 4:4:4 at 16 bits (yuv444p10le, P410: their quads
+ * are 24 - 32 bytes per lane and need a different window hand-over); big-endian r210; alpha; RGB565; rounding or dithering of the
+ * dropped bits; BT.2020 and transfer functions. */
+enum { MELF_P32_YUV = 0, MELF_P32_RGB = 1 };
+typedef struct melf_packed32_frames {
+    int32_t colour, matrix;                     /* MELF_P32_*; MELF_YUV_BT* for YUV, 0 for RGB            */
+    int32_t n, H, W;                            /* any W, any H                                           */
+    int32_t pos[3];                             /* 0 .. 24: low bit of the 8 bits read of Y,U,V / R,G,B   */
+    int64_t row_pitch;                          /* bytes, multiple of 4, >= 4 * W, <= 2^31 - 1            */
+    int64_t frame_stride;                       /* bytes, multiple of 4, >= (H - 1) * row_pitch + 4 * W   */
+    int32_t reserved, reserved2;                /* 0                                                      */
+} melf_packed32_frames;
+/* Host frames, as melf_process_yuv422_10: only the crop crosses PCIe, its rows copied as they are into the pinned staging buffers;
+ * no word is unpacked on the CPU. */
+int melf_process_packed32(melf_ctx* ctx, const void* frames_host, const melf_packed32_frames* f, melf_result* out_host);
+/* Frames in HBM, exactly as melf_process_yuv422_10_dev: the same lanes, melf_ctx_set_frames_resident, caller streams, and NULL
+ * d_results / out_host semantics. */
+int melf_process_packed32_dev(melf_ctx* ctx, const void* d_frames, const melf_packed32_frames* f, void* d_results,
+                              melf_result* out_host, void* stream);
+/* Stage entry point (parity tests, and a debug view for callers): unpacking and conversion alone, n packed H x W x 3 BGR frames out. */
+int melf_packed32_to_bgr(melf_ctx* ctx, const void* frames_host, const melf_packed32_frames* f, uint8_t* bgr_out_host);
 
 /* ---- the same path for planar, channels-first frames: (N, 3, H, W) uint8 as torch's decoders and pre-processing pipelines
  * hold them, ffmpeg's gbrp, rgb24 split into planes ----
@@ -639,7 +696,7 @@ typedef struct {
 int melf_ctx_last_match(const melf_ctx* ctx, melf_match_info* out);
 /* Which dial-reader kernel the context's most recent launch ran: the kernel family that reads the frames' layout and NR, the
  * window rows a lane requests up front -- one of 32, 40, 48, 52, 56, 64, the smallest that holds ws_max, the context's largest
- * dial window (2 R + 5 rows).  Twelve families (and the two of the 16-bit and the two of the packed 10-bit frames, below) times six NR: tests assert the pair, so
+ * dial window (2 R + 5 rows).  Twelve families (and the two each of the 16-bit, the packed 10-bit and the 32-bit packed frames, below) times six NR: tests assert the pair, so
  * that every instantiation production can pick is known to have been the one a parity test launched.  family is -1 and nr 0
  * before the first launch; a call of more frames than one launch takes reports its last piece.  Plain fields written by every
  * launch, as for melf_ctx_fused_variant's last_launch.  Every output pointer may be NULL. */
@@ -664,6 +721,9 @@ enum { MELF_DIALS16_STEP1 = 12,       /* k_y16_needle<1>: melf_process_yuv16*, p
 /* The families of the packed 10-bit 4:2:2 frames (melf_process_yuv422_10*), in the same way: an enum of their own that goes on. */
 enum { MELF_DIALS10_V210 = 14,        /* k_v210_needle: melf_process_yuv422_10*, MELF_YUV422_10_V210         */
        MELF_DIALS10_Y210 = 15 };      /* k_y210_needle: ... MELF_YUV422_10_Y210                              */
+/* The families of the 32-bit packed 4:4:4 frames (melf_process_packed32*), in the same way. */
+enum { MELF_DIALS32_YUV = 16,         /* k_p32_needle<true>: melf_process_packed32*, MELF_P32_YUV            */
+       MELF_DIALS32_RGB = 17 };       /* k_p32_needle<false>: ... MELF_P32_RGB                               */
 int melf_ctx_last_dials(const melf_ctx* ctx, int* nr, int* family, int* ws_max);
 /* The tuned kernel's wave layout for a template / searched-image shape and a batch of n images, without a GPU or a
  * context (host logic; kernel = MELF_MATCH_KERNEL_MFMA when the shape belongs to the tuned kernel's class, else the

@@ -256,6 +256,22 @@ class MeterReader:
         return self._read_view(v, out, lambda: self.ctx.process_yuv422_10(v.ptr, desc),
                                lambda **kw: self.ctx.process_yuv422_10_dev(v.ptr, desc, **kw))
 
+    def read_packed32_frames(self, frames, pixel_format: str, matrix=None, out=None):
+        """4:4:4 frames of one 32-bit word per pixel -- 'vuya' / 'ayuv' / 'uyva' (8-bit), 'y410' / 'xv30' / 'v30x' (10-bit YUV) as
+        hardware 4:4:4 decoders deliver them, 'x2rgb10' / 'x2bgr10' (10-bit RGB) as scan-out, desktop duplication and camera ISPs do
+        (_hip.PACKED32_FORMATS) -- -> records, equal to read_yuv_planar_frames() of the 8-bit 'i444' frames whose samples are the top
+        8 bits of each field (YUV), or to read_frames() of the BGR frames of those (RGB) (melf_process_packed32*); the words are read
+        in place, no unpack pass.  matrix is required for the YUV formats (no default, as for read_yuv16_frames) and must be None for
+        the RGB ones.  frames: (N, H, W) of uint32, or (N, H, W, 4) of uint8 for the byte formats: a numpy array / torch CPU tensor
+        (host path) or a torch tensor on this reader's GPU (enqueued on torch.cuda.current_stream), torch.int32 holding the same bits
+        where the installed torch has no unsigned type; _hip.packed32_frames_view says which layouts are read in place.  out: a uint8
+        device tensor (N, RESULT_DTYPE.itemsize) on the same GPU that receives the records without synchronising the stream (device
+        frames only); returns it.  Otherwise returns the records."""
+        v = _hip.packed32_frames_view(frames, pixel_format, matrix)
+        desc = v.descriptor()
+        return self._read_view(v, out, lambda: self.ctx.process_packed32(v.ptr, desc),
+                               lambda **kw: self.ctx.process_packed32_dev(v.ptr, desc, **kw))
+
     def read_planar_frames(self, frames, channel_order: str = 'rgb', out=None):
         """Planar, channels-first frames (N, 3, H, W) / (N, 4, H, W) uint8 -> records, equal to read_frames() of the packed BGR
         frames with the same samples (melf_process_planes*); the planes are read in place, no interleaved copy is made.  frames: a

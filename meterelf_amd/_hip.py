@@ -148,6 +148,31 @@ class MelfYuv422_10Frames(C.Structure):
 YUV422_10_FORMATS = {'v210': 0, 'y210': 1, 'y212': 1, 'y216': 1}
 
 
+class MelfPacked32Frames(C.Structure):
+    _fields_ = [('colour', C.c_int32), ('matrix', C.c_int32), ('n', C.c_int32), ('H', C.c_int32), ('W', C.c_int32),
+                ('pos', C.c_int32 * 3), ('row_pitch', C.c_int64), ('frame_stride', C.c_int64), ('reserved', C.c_int32),
+                ('reserved2', C.c_int32)]
+
+
+# 4:4:4 layouts of one little-endian 32-bit word per pixel (melf_process_packed32*) by name -> (colour, pos): colour MELF_P32_*,
+# pos the low bit of the 8 bits read of Y, U, V (P32_YUV) or of R, G, B (P32_RGB); a 10-bit field at bit o is read from o + 2, byte b
+# from 8 b.  The layouts are those of drm_fourcc.h and ffmpeg's pixfmt.h (include/meterelf_hip.h has the table):
+#   'vuya' / 'vuyx'  bytes V U Y A in memory (Microsoft's and DRM's AYUV)     'ayuv'  bytes A Y U V (ffmpeg, GStreamer)
+#   'uyva'           bytes U Y V A                                             'y410' / 'xv30'  U bits 0-9, Y 10-19, V 20-29
+#   'v30x'           U bits 2-11, Y 12-21, V 22-31
+#   'x2rgb10' / 'xrgb2101010'  B bits 0-9, G 10-19, R 20-29                   'x2bgr10' / 'xbgr2101010' / 'r10g10b10a2'  R in the low bits
+(P32_YUV, P32_RGB) = (0, 1)
+PACKED32_FORMATS = {
+    'vuya': (P32_YUV, (16, 8, 0)), 'vuyx': (P32_YUV, (16, 8, 0)),
+    'ayuv': (P32_YUV, (8, 16, 24)),
+    'uyva': (P32_YUV, (8, 0, 16)),
+    'y410': (P32_YUV, (12, 2, 22)), 'xv30': (P32_YUV, (12, 2, 22)),
+    'v30x': (P32_YUV, (14, 4, 24)),
+    'x2rgb10': (P32_RGB, (22, 12, 2)), 'xrgb2101010': (P32_RGB, (22, 12, 2)),
+    'x2bgr10': (P32_RGB, (2, 12, 22)), 'xbgr2101010': (P32_RGB, (2, 12, 22)), 'r10g10b10a2': (P32_RGB, (2, 12, 22)),
+}
+
+
 class MelfPlanarFrames(C.Structure):
     _fields_ = [('n', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('reserved', C.c_int32), ('b_offset', C.c_int64),
                 ('g_offset', C.c_int64), ('r_offset', C.c_int64), ('row_pitch', C.c_int64), ('frame_stride', C.c_int64)]
@@ -179,6 +204,9 @@ DIALS16_FAMILIES = ('yuv16_step1', 'yuv16_step2')
 # MELF_DIALS10_* in the same way, the families of the packed 10-bit 4:2:2 frames: values 14, 15
 DIALS10_FAMILIES = ('v210', 'y210')
 
+# MELF_DIALS32_* in the same way, the families of the 32-bit packed 4:4:4 frames: values 16, 17
+DIALS32_FAMILIES = ('p32yuv', 'p32rgb')
+
 # every symbol include/meterelf_hip.h declares for the product library; DIAG_EXPORTS: what its `#ifdef MELF_DIAG` part adds (the
 # diagnostic build, make -C meterelf_amd/csrc diag, loaded through MELF_LIB_PATH)
 DIAG_EXPORTS = ['melf_stream_probe_dev']
@@ -191,6 +219,7 @@ EXPORTS = [
     'melf_process_yuv_planar', 'melf_process_yuv_planar_dev', 'melf_yuv_planar_to_bgr',
     'melf_process_yuv16', 'melf_process_yuv16_dev', 'melf_yuv16_to_bgr',
     'melf_process_yuv422_10', 'melf_process_yuv422_10_dev', 'melf_yuv422_10_to_bgr',
+    'melf_process_packed32', 'melf_process_packed32_dev', 'melf_packed32_to_bgr',
     'melf_bgr2hls', 'melf_hls_inrange_close', 'melf_hls_inrange_close_dev', 'melf_match_ccoeff',
     'melf_read_dials', 'melf_aligned_average', 'melf_inrange', 'melf_ctx_fused_table_ties', 'melf_ctx_fused_variant', 'melf_ctx_set_frames_resident', 'melf_ctx_last_match', 'melf_ctx_last_dials', 'melf_match_layout_query', 'melf_match_gen_plan_query', 'melf_ctx_set_profiling', 'melf_ctx_timings', 'melf_kernel_name',
     'melf_jpeg_probe', 'melf_jpeg_probe_batch', 'melf_jpeg_decode_batch', 'melf_jpeg_clean_segment', 'melf_jpeg_process_batch',
@@ -246,6 +275,9 @@ def lib():
     L.melf_process_yuv422_10.argtypes = [vp, vp, C.POINTER(MelfYuv422_10Frames), vp]
     L.melf_process_yuv422_10_dev.argtypes = [vp, vp, C.POINTER(MelfYuv422_10Frames), vp, vp, vp]
     L.melf_yuv422_10_to_bgr.argtypes = [vp, vp, C.POINTER(MelfYuv422_10Frames), vp]
+    L.melf_process_packed32.argtypes = [vp, vp, C.POINTER(MelfPacked32Frames), vp]
+    L.melf_process_packed32_dev.argtypes = [vp, vp, C.POINTER(MelfPacked32Frames), vp, vp, vp]
+    L.melf_packed32_to_bgr.argtypes = [vp, vp, C.POINTER(MelfPacked32Frames), vp]
     L.melf_process_planes.argtypes = [vp, vp, C.POINTER(MelfPlanarFrames), vp]
     L.melf_process_planes_dev.argtypes = [vp, vp, C.POINTER(MelfPlanarFrames), vp, vp, vp]
     L.melf_process_stream_dev.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, vp]
@@ -815,6 +847,85 @@ def yuv422_10_frames_view(frames, pixel_format, matrix, width=None):
     return Yuv422_10FramesView(int(ptr), on_device, device, code, n, H, W, int(rp), int(fs), int(extent), not ok, frames, mcode)
 
 
+class Packed32FramesView(NamedTuple):
+    """How the kernels read a batch of 32-bit packed 4:4:4 frames in place (packed32_frames_view)."""
+    ptr: int            # address of frame 0's first word
+    on_device: bool     # True: a torch tensor on a GPU (ptr is a device address)
+    device: Optional[int]
+    colour: int         # P32_YUV / P32_RGB
+    pos: tuple          # low bit of the 8 bits read of Y, U, V / R, G, B
+    n: int
+    H: int
+    W: int
+    row_pitch: int      # bytes between rows
+    frame_stride: int   # bytes between frames
+    extent: int         # bytes read from ptr: (n - 1) * frame_stride + (H - 1) * row_pitch + 4 * W
+    copied: bool        # the layout could not be described and the frames were copied once to a packed array
+    array: object       # what ptr points into (the caller's array, or the copy): keep it alive while the call runs
+    matrix: int         # YUV_BT* code of the colour conversion; 0 for P32_RGB
+
+    def descriptor(self):
+        return MelfPacked32Frames(self.colour, self.matrix, self.n, self.H, self.W, (C.c_int32 * 3)(*self.pos), self.row_pitch,
+                                  self.frame_stride, 0, 0)
+
+
+def packed32_frames_view(frames, pixel_format, matrix=None):
+    """Describes a batch of 4:4:4 frames of one 32-bit word per pixel (numpy array or torch tensor) as melf_process_packed32* read
+    it.  pixel_format: a name of PACKED32_FORMATS.  frames: (N, H, W) of uint32 (torch: int32 holding the same bits), a little-endian
+    word per pixel; for the formats whose reads are whole bytes ('vuya', 'ayuv', 'uyva') also (N, H, W, 4) of uint8, the word's bytes
+    in memory order.  The frame stride and the row stride are honoured in place (frames[a:b], frames[::2], frames[:, :, :w], padded
+    rows) where the pixels are 4 bytes apart and the strides are multiples of 4; any other layout -- a pixel stride other than 4, a
+    byte stride other than 1, negative strides -- is copied once to a packed array (Packed32FramesView.copied).  matrix: a name of
+    YUV_MATRIX_CODES or a code for the YUV formats, where there is no default (None: ValueError) -- the wrong matrix raises no error;
+    it must be None for the RGB formats.  A wrong dtype or rank, a base that is not 4-byte aligned, an unknown format or matrix:
+    ValueError."""
+    fmt = str(pixel_format).lower()
+    if fmt not in PACKED32_FORMATS:
+        raise ValueError('pixel_format %r is not a 32-bit packed 4:4:4 layout (%s)' % (pixel_format, ', '.join(PACKED32_FORMATS)))
+    (colour, pos) = PACKED32_FORMATS[fmt]
+    if colour == P32_YUV:
+        if matrix is None:
+            raise ValueError('%s frames need matrix=: there is no default, and the wrong matrix raises no error' % fmt)
+        mcode = yuv_matrix_code(matrix)
+    else:
+        if matrix is not None:
+            raise ValueError('%s frames are RGB: matrix must be None, not %r' % (fmt, matrix))
+        mcode = 0
+    as_bytes = (frames.dim() if _is_torch(frames) else np.ndim(frames)) == 4
+    if as_bytes:
+        if any(p % 8 for p in pos):
+            raise ValueError('%s frames must be (N, H, W) of uint32: their reads are not whole bytes' % fmt)
+        (frames, is_torch, shape, strides, ptr, on_device, device) = _unwrap(frames)
+        if shape[3] != 4 or shape[1] == 0 or shape[2] == 0:
+            raise ValueError('%s frames of uint8 must be (N, H, W, 4), not %s' % (fmt, shape))
+        (n, H, W, _four) = shape
+        (fs, rp, ps, es) = strides
+        ok = es == 1
+    else:
+        (frames, is_torch, shape, strides, ptr, on_device, device) = _unwrap32(frames)
+        if len(shape) != 3 or shape[1] == 0 or shape[2] == 0:
+            raise ValueError('%s frames must be (N, H, W) of uint32, not %s' % (fmt, shape))
+        (n, H, W) = shape
+        (fs, rp, ps) = strides
+        ok = True
+    if ptr % 4 != 0:
+        raise ValueError('%s frames need a 4-byte aligned base' % fmt)
+    row = 4 * W
+    # strides of dimensions of size 1 are never stepped over: make them what a packed array has
+    if W == 1:
+        ps = 4
+    if H == 1:
+        rp = row
+    if n == 1:
+        fs = (H - 1) * rp + row if rp > 0 else 0
+    ok = ok and ps == 4 and rp >= row and fs >= (H - 1) * rp + row and rp <= 2 ** 31 - 1 and (rp | fs) % 4 == 0
+    if not ok:
+        (frames, ptr) = _packed_copy(frames, is_torch)
+        (rp, fs) = (row, H * row)
+    extent = (n - 1) * fs + (H - 1) * rp + row if n else 0
+    return Packed32FramesView(int(ptr), on_device, device, colour, tuple(pos), n, H, W, int(rp), int(fs), int(extent), not ok, frames, mcode)
+
+
 class PlanarFramesView(NamedTuple):
     """How the kernels read a batch of planar (channels-first) frames in place (planar_frames_view)."""
     ptr: int            # address of frame 0's first plane
@@ -1175,6 +1286,21 @@ class Context:
         check(self._L.melf_yuv422_10_to_bgr(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
         return out
 
+    def process_packed32(self, frames_ptr, desc):
+        """Host 32-bit packed 4:4:4 frames (melf_process_packed32; desc: a MelfPacked32Frames, e.g.
+        packed32_frames_view(...).descriptor()) -> records."""
+        return self._host(self._L.melf_process_packed32, frames_ptr, desc)
+
+    def process_packed32_dev(self, d_frames_ptr, desc, d_results_ptr=None, want_host=True, stream=None):
+        """32-bit packed 4:4:4 frames in HBM (melf_process_packed32_dev, as process_frames_dev).  Returns records when want_host."""
+        return self._dev(self._L.melf_process_packed32_dev, d_frames_ptr, desc, d_results_ptr, want_host, stream)
+
+    def packed32_to_bgr(self, frames_ptr, desc):
+        """Unpacking and conversion alone (melf_packed32_to_bgr): host 32-bit packed 4:4:4 frames -> (n, H, W, 3) BGR."""
+        out = np.empty((desc.n, desc.H, desc.W, 3), np.uint8)
+        check(self._L.melf_packed32_to_bgr(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
+        return out
+
     def process_planes(self, frames_ptr, desc):
         """Host planar frames (melf_process_planes; desc: a MelfPlanarFrames, e.g. planar_frames_view(...).descriptor()) -> records."""
         return self._host(self._L.melf_process_planes, frames_ptr, desc)
@@ -1362,7 +1488,7 @@ class Context:
         None before the first launch), 'nr' (window rows a lane requests up front) and 'ws_max' (the context's largest window)."""
         (nr, fam, ws) = (C.c_int(0), C.c_int(0), C.c_int(0))
         check(self._L.melf_ctx_last_dials(self._h, C.byref(nr), C.byref(fam), C.byref(ws)))
-        names = DIALS_FAMILIES + DIALS16_FAMILIES + DIALS10_FAMILIES   # (the later families' values go on from the twelve's)
+        names = DIALS_FAMILIES + DIALS16_FAMILIES + DIALS10_FAMILIES + DIALS32_FAMILIES   # (the later families' values go on from the twelve's)
         return dict(family=names[fam.value] if fam.value >= 0 else None, nr=nr.value, ws_max=ws.value)
 
     def set_profiling(self, on):

@@ -316,6 +316,20 @@ __global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_v
 #include "k_dials_body.inc"
 }
 
+// 32-bit packed 4:4:4 frames (melf_process_packed32*): one word per pixel, three 8-bit reads at the positions of `fields`; YUV: the
+// reads are Y, U, V under ymat, else R, G, B (ymat is not looked at).  The positions and the matrix are the same for every lane
+// (SGPRs), so that the formats of a colour kind share its NR instantiations.
+template <bool YUV, int NR>
+__global__ __launch_bounds__(64 * MELF_MAX_DIALS, 4) __attribute__((amdgpu_num_vgpr(DIALS_VGPRS))) void k_p32_needle(DialsSrc src, Packed32Fields fields, YuvMatrix ymat, melf_params P,
+                                                                const DialGeom* __restrict__ geom,
+                                                                const uint64_t* __restrict__ rowmasks,
+                                                                const MatchPartial* __restrict__ partials,
+                                                                int nparts, int rw, melf_result* __restrict__ results)
+{
+    using Src = DialWord32<YUV>; const typename Src::Args sargs{fields, ymat};
+#include "k_dials_body.inc"
+}
+
 // Planar frames (melf_process_planes*): the B, G and R planes at `planes` in a frame.  Past its loads the body is the one of 4-byte
 // B G R pixels.
 template <int NR>
@@ -376,6 +390,8 @@ DialsLaunch launch_dials(const DialsSrc& src, const FrameLayout& lay, int n, con
         }
         else if (pix == PIX_V210) { ran.family = MELF_DIALS10_V210; go(k_v210_needle<NR>, *lay.mx); }
         else if (pix == PIX_Y210) { ran.family = MELF_DIALS10_Y210; go(k_y210_needle<NR>, *lay.mx); }
+        else if (pix == PIX_P32_YUV) { ran.family = MELF_DIALS32_YUV; go(k_p32_needle<true, NR>, lay.p32, *lay.mx); }
+        else if (pix == PIX_P32_RGB) { ran.family = MELF_DIALS32_RGB; go(k_p32_needle<false, NR>, lay.p32, YuvMatrix{}); }
         else if (pix == PIX_PLANAR) { ran.family = MELF_DIALS_PLANAR; go(k_planar_needle<NR>, lay.planes); }
         else if (pix_p422(pix)) { ran.family = MELF_DIALS_P422; go(k_p422_needle<NR>, p422_sel(pix), *lay.mx); }
         else if (pix == PIX_NV12) { ran.family = MELF_DIALS_NV12; go(k_yneedle<false, NR>, lay.yuv, *lay.mx); }

@@ -20,6 +20,7 @@
 #include "melf_internal.h"
 #include "melf_y16_addr.h"
 #include "melf_p10_addr.h"
+#include "melf_p32_addr.h"
 
 namespace melf {
 
@@ -38,7 +39,8 @@ __device__ inline bool better(float v, int i, float bv, int bi)
 // at (y >> sub_y, x >> sub_x) per pixel, byte loads: the shifts and the sample step are wave-uniform scalars); 25 = 16-bit planar /
 // semi-planar YUV (melf_process_yuv16*; yuv: Yuv16Planes; a Y sample and the chroma samples at (y >> sub_y, x >> 1) per pixel, 2-byte
 // loads, each reduced to 8 bits by y16::reduce); 26 / 27 = packed 10-bit YUV 4:2:2, v210 / Y210 (melf_process_yuv422_10*; no yuv: the
-// two words of the pixel's group / the two dwords of its macropixel, melf_p10_addr.h).
+// two words of the pixel's group / the two dwords of its macropixel, melf_p10_addr.h); 28 / 29 = 32-bit packed 4:4:4, Y U V / R G B
+// (melf_process_packed32*; yuv: Packed32Fields, where the three reads sit; the pixel's word, one aligned dword, melf_p32_addr.h).
 struct NoYuv {};
 struct P422Sel { uint32_t sel; };
 template <int PX, class YUV = NoYuv>
@@ -110,6 +112,14 @@ __device__ __forceinline__ void match_tile(MatchSrc src, MatchGeom g, const uint
                             }
                             const YuvChroma c = yuv_chroma((int)((s >> 8) & 255u), (int)(s >> 16), mx);
                             v = (uint32_t)yuv_lightness((int)(s & 255u), yuv_cmax(c), yuv_cmin(c), mx);
+                        } else if constexpr (PX == 28 || PX == 29) {
+                            const uint32_t wd = *(const uint32_t*)(img + p32::px_off(src.y0 + y, (size_t)src.row_stride, src.x0 + x));
+                            if constexpr (PX == 28) {
+                                const YuvChroma c = yuv_chroma((int)p32::read8(wd, yuv.pos[1]), (int)p32::read8(wd, yuv.pos[2]), mx);
+                                v = (uint32_t)yuv_lightness((int)p32::read8(wd, yuv.pos[0]), yuv_cmax(c), yuv_cmin(c), mx);
+                            } else {
+                                v = (uint32_t)hls_lightness((int)p32::read8(wd, yuv.pos[2]), (int)p32::read8(wd, yuv.pos[1]), (int)p32::read8(wd, yuv.pos[0]));
+                            }
                         } else if constexpr (PX == 22) {
                             const int fx = src.x0 + x;
                             const uint32_t m = __builtin_amdgcn_perm(0u, *(const uint32_t*)(prow + (size_t)(fx >> 1) * 4), yuv.sel);
@@ -279,6 +289,16 @@ __global__ __launch_bounds__(256) void k_y210_match(MatchSrc src, YuvMatrix mx, 
     match_tile<27, NoYuv>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts, NoYuv{}, mx);
 }
 
+// 32-bit packed 4:4:4 (melf_process_packed32*): the dot4 matcher with the pixel's word, one aligned dword; YUV: the reads are Y, U, V
+// under mx, else R, G, B (mx is not looked at)
+template <bool YUV>
+__global__ __launch_bounds__(256) void k_p32_match(MatchSrc src, Packed32Fields fields, YuvMatrix mx, MatchGeom g, const uint32_t* __restrict__ tplT,
+                                                   int rh, int rw, int nrb, float* __restrict__ result_map,
+                                                   MatchPartial* __restrict__ partials, int nparts)
+{
+    match_tile<YUV ? 28 : 29, Packed32Fields>(src, g, tplT, rh, rw, nrb, result_map, partials, nparts, fields, mx);
+}
+
 int match_parts(const MatchGeom& g, int rows, int cols)
 {
     const int rh = rows - g.th + 1, rw = cols - g.tw + 1;
@@ -307,6 +327,10 @@ void launch_match(const MatchSrc& src, const FrameLayout& lay, int n, const Matc
         hipLaunchKernelGGL(k_v210_match, grid, block, shmem, stream, src, *lay.mx, g, d_tplT, rh, rw, nrb, d_result_map, d_partials, nparts);
     else if (pix == PIX_Y210)
         hipLaunchKernelGGL(k_y210_match, grid, block, shmem, stream, src, *lay.mx, g, d_tplT, rh, rw, nrb, d_result_map, d_partials, nparts);
+    else if (pix == PIX_P32_YUV)
+        hipLaunchKernelGGL(k_p32_match<true>, grid, block, shmem, stream, src, lay.p32, *lay.mx, g, d_tplT, rh, rw, nrb, d_result_map, d_partials, nparts);
+    else if (pix == PIX_P32_RGB)
+        hipLaunchKernelGGL(k_p32_match<false>, grid, block, shmem, stream, src, lay.p32, YuvMatrix{}, g, d_tplT, rh, rw, nrb, d_result_map, d_partials, nparts);
     else if (pix == PIX_PLANAR)
         hipLaunchKernelGGL(k_planar_match, grid, block, shmem, stream, src, lay.planes, g, d_tplT, rh, rw, nrb, d_result_map,
                            d_partials, nparts);

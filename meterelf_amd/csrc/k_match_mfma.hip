@@ -37,6 +37,7 @@
 #include "melf_internal.h"
 #include "melf_y16_addr.h"
 #include "melf_p10_addr.h"
+#include "melf_p32_addr.h"
 #include "melf_prep_addr.h"
 
 namespace melf {
@@ -199,6 +200,20 @@ __global__ __launch_bounds__(256) void k_y210_lplane(MatchSrc src, YuvMatrix mx,
 #include "prep_lplane_body.inc"
 }
 #undef MELF_Y210_BODY
+
+// 32-bit packed 4:4:4 frames (melf_process_packed32*): one word per pixel, k_lplane_px4's loads; the three reads of a word at the
+// positions of `fields`, the same for every lane (SGPRs).  YUV: the reads are Y, U, V and L comes straight from them under mx as in
+// k_yp_lplane<0, 1>; else they are R, G, B and L comes from the largest and the smallest as in k_lplane_px4 (mx is not looked at).
+// No BGR pixel is formed.
+#define MELF_P32_BODY
+template <bool YUV>
+__global__ __launch_bounds__(256) void k_p32_lplane(MatchSrc src, Packed32Fields fields, YuvMatrix mx, int nframes, int nkb, int rows_pad, int tw, int rwp, int pairs,
+                                                    int8_t* __restrict__ Lg, uint16_t* __restrict__ R)
+{
+    constexpr int PX = YUV ? 28 : 29;
+#include "prep_lplane_body.inc"
+}
+#undef MELF_P32_BODY
 
 // ---------------------------------------------------------------------------
 // k_match_mfma
@@ -913,9 +928,13 @@ void launch_match_prep(const MatchSrc& src, const FrameLayout& lay, int n, int g
         (void)hipFuncSetAttribute((const void*)k_y16_lplane<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute((const void*)k_v210_lplane, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         (void)hipFuncSetAttribute((const void*)k_y210_lplane, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_p32_lplane<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_p32_lplane<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
         attr_set[dev] = true;
     }
-    if (pix == PIX_V210) hipLaunchKernelGGL(k_v210_lplane, grid, block, pre_bytes, stream, src, *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    if (pix == PIX_P32_YUV) hipLaunchKernelGGL(k_p32_lplane<true>, grid, block, pre_bytes, stream, src, lay.p32, *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    else if (pix == PIX_P32_RGB) hipLaunchKernelGGL(k_p32_lplane<false>, grid, block, pre_bytes, stream, src, lay.p32, YuvMatrix{}, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
+    else if (pix == PIX_V210) hipLaunchKernelGGL(k_v210_lplane, grid, block, pre_bytes, stream, src, *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else if (pix == PIX_Y210) hipLaunchKernelGGL(k_y210_lplane, grid, block, pre_bytes, stream, src, *lay.mx, n, nkb, rows_pad, tw, rwp, pairs, d_lg, d_r);
     else if (pix == PIX_YUV16) {
         const Yuv16Planes& yp = lay.y16;

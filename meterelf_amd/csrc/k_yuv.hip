@@ -9,6 +9,7 @@
 #include "melf_internal.h"
 #include "melf_y16_addr.h"
 #include "melf_p10_addr.h"
+#include "melf_p32_addr.h"
 
 namespace melf {
 
@@ -191,6 +192,42 @@ void launch_p10_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int r
         uint8_t* d = d_dst + (size_t)f0 * H * W * 3;
         if (pix == PIX_V210) hipLaunchKernelGGL(k_v210_to_bgr, grid, block, 0, stream, s, H, W, row_pitch, frame_stride, mx, d);
         else hipLaunchKernelGGL(k_y210_to_bgr, grid, block, 0, stream, s, H, W, row_pitch, frame_stride, mx, d);
+    }
+}
+
+// 32-bit packed 4:4:4 -> BGR alone: the stage kernels behind melf_packed32_to_bgr.  One thread per pixel: its word, the three reads at
+// the positions every reading kernel takes (melf_p32_addr.h), YUV: the conversion under mx, else R G B as they are; three bytes out.
+// They pin the addressing and the selection for every value at every position; like k_yuv2bgr no hot path.
+template <bool YUV>
+__global__ __launch_bounds__(256) void k_p32_to_bgr(const uint8_t* __restrict__ src, int H, int W, int row_pitch, size_t frame_stride, Packed32Fields fields,
+                                                    YuvMatrix mx, uint8_t* __restrict__ dst)
+{
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.z;
+    if (x >= W) return;
+    const uint8_t* frame = src + (size_t)f * frame_stride;
+    for (int y = blockIdx.y; y < H; y += gridDim.y) {
+        const uint32_t wd = *(const uint32_t*)(frame + p32::px_off(y, (size_t)row_pitch, x));
+        uint32_t p;
+        if constexpr (YUV)
+            p = yuv_bgr((int)p32::read8(wd, fields.pos[0]), yuv_chroma((int)p32::read8(wd, fields.pos[1]), (int)p32::read8(wd, fields.pos[2]), mx), mx);
+        else
+            p = p32::rgb_bgr(wd, fields);
+        uint8_t* o = dst + (((size_t)f * H + y) * (size_t)W + (size_t)x) * 3;
+        o[0] = (uint8_t)p; o[1] = (uint8_t)(p >> 8); o[2] = (uint8_t)(p >> 16);
+    }
+}
+
+void launch_p32_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int row_pitch, size_t frame_stride, const Packed32Fields& fields,
+                       const YuvMatrix* mx, uint8_t* d_dst, hipStream_t stream)
+{
+    // at most 65 535 frames per launch (grid z); a workgroup row takes every 65 535th image row (grid y)
+    for (int f0 = 0; f0 < n; f0 += 65535) {
+        const int m = n - f0 < 65535 ? n - f0 : 65535;
+        dim3 grid((W + 255) / 256, H < 65535 ? H : 65535, m), block(256);
+        const uint8_t* s = d_src + (size_t)f0 * frame_stride;
+        uint8_t* d = d_dst + (size_t)f0 * H * W * 3;
+        if (pix == PIX_P32_YUV) hipLaunchKernelGGL(k_p32_to_bgr<true>, grid, block, 0, stream, s, H, W, row_pitch, frame_stride, fields, *mx, d);
+        else hipLaunchKernelGGL(k_p32_to_bgr<false>, grid, block, 0, stream, s, H, W, row_pitch, frame_stride, fields, YuvMatrix{}, d);
     }
 }
 

@@ -1239,6 +1239,15 @@ extern "C" int melf_process_yuv422_10_dev(melf_ctx* c, const void* d_frames, con
     return batch_dev(c, d_frames, b, d_results, out_host, stream_);
 }
 
+extern "C" int melf_process_packed32_dev(melf_ctx* c, const void* d_frames, const melf_packed32_frames* f, void* d_results,
+                                         melf_result* out_host, void* stream_)
+{
+    FrameBatch b;
+    if (int rc = checked(c, check_packed32(d_frames, f, &b))) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return batch_dev(c, d_frames, b, d_results, out_host, stream_);
+}
+
 extern "C" int melf_process_planes_dev(melf_ctx* c, const void* d_frames, const melf_planar_frames* f, void* d_results,
                                        melf_result* out_host, void* stream_)
 {
@@ -1564,6 +1573,24 @@ static int host_yuv422_10(melf_ctx* c, const uint8_t* frames_host, const FrameBa
     });
 }
 
+// 32-bit packed 4:4:4 (AYUV, Y410, X2RGB10 ..): the staged frame is the crop, its rows of words copied as they are at a 64-byte pitch
+// (4-byte aligned like the caller's), read under the same positions and matrix; no word is unpacked on the CPU.  Work items: the
+// rows in blocks of 32.
+static int host_packed32(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host)
+{
+    Crop cr;
+    if (int rc = host_crop(c, b, out_host, &cr)) return rc;
+    const int crows = cr.rows, y0 = cr.y0;
+    const size_t row_pitch = (size_t)b.row_stride, rbytes = (size_t)cr.cols * 4, x_off = (size_t)cr.x0 * 4;
+    const size_t pitch = pitch64(rbytes);
+    const StagePlan sp = {{0, crows, cr.cols, crows * pitch + 128, (int)pitch, FrameLayout::packed32(b.lay.pix, b.lay.p32, b.lay.mx, crows * pitch)},
+                          {0, 0, cr.cols, crows}, (crows + 31) / 32};
+    return stage_host_frames(c, frames_host, b.n, b.frame_stride, sp, out_host, [=](const uint8_t* frame, uint8_t* small, int part) {
+        const int r0 = part * 32, r1 = r0 + 32 < crows ? r0 + 32 : crows;
+        for (int y = r0; y < r1; ++y) memcpy(small + (size_t)y * pitch, frame + (size_t)(y0 + y) * row_pitch + x_off, rbytes);
+    });
+}
+
 // Planar / semi-planar YUV of any subsampling and sample size: the staged frame is a small frame of the same layout -- the same
 // subsampling, sample step and order of U and V, and for 16-bit samples the same shift, the samples copied as they are (nothing is
 // reduced on the CPU) --, the Y rows of the crop with its origin rounded down (and its far corner up) to whole chroma blocks
@@ -1720,6 +1747,14 @@ extern "C" int melf_process_yuv422_10(melf_ctx* c, const void* frames_host, cons
     return host_yuv422_10(c, (const uint8_t*)frames_host, b, out_host);
 }
 
+extern "C" int melf_process_packed32(melf_ctx* c, const void* frames_host, const melf_packed32_frames* f, melf_result* out_host)
+{
+    FrameBatch b;
+    if (int rc = checked(c, check_packed32(frames_host, f, &b))) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return host_packed32(c, (const uint8_t*)frames_host, b, out_host);
+}
+
 extern "C" int melf_process_planes(melf_ctx* c, const void* frames_host, const melf_planar_frames* f, melf_result* out_host)
 {
     FrameBatch b;
@@ -1729,7 +1764,7 @@ extern "C" int melf_process_planes(melf_ctx* c, const void* frames_host, const m
 }
 
 // ---------------------------------------------------------- stage entries ----
-// melf_yuv_to_bgr / melf_yuv422_to_bgr / melf_yuv_planar_to_bgr / melf_yuv16_to_bgr after their checks: the frames up, the conversion kernel alone, n packed H x W BGR frames down
+// melf_yuv_to_bgr / melf_yuv422_to_bgr / melf_yuv_planar_to_bgr / melf_yuv16_to_bgr / melf_yuv422_10_to_bgr / melf_packed32_to_bgr after their checks: the frames up, the conversion kernel alone, n packed H x W BGR frames down
 static int to_bgr(melf_ctx* c, const void* frames_host, const FrameBatch& b, uint8_t* bgr_out_host)
 {
     if (!bgr_out_host) return fail(MELF_ERR_INVALID, "bgr_out_host is NULL");
@@ -1738,7 +1773,9 @@ static int to_bgr(melf_ctx* c, const void* frames_host, const FrameBatch& b, uin
     if (int rc = grow(&c->d_stage_in, &c->stage_in_cap, in_bytes)) return rc;
     if (int rc = grow(&c->d_stage_out, &c->stage_out_cap, out_bytes)) return rc;
     HIP_TRY(hipMemcpyAsync(c->d_stage_in, frames_host, in_bytes, hipMemcpyHostToDevice, c->stream));
-    if (pix_p10(b.lay.pix))
+    if (pix_p32(b.lay.pix))
+        launch_p32_to_bgr(c->d_stage_in, b.lay.pix, b.n, b.H, b.W, b.row_stride, b.frame_stride, b.lay.p32, b.lay.mx, c->d_stage_out, c->stream);
+    else if (pix_p10(b.lay.pix))
         launch_p10_to_bgr(c->d_stage_in, b.lay.pix, b.n, b.H, b.W, b.row_stride, b.frame_stride, *b.lay.mx, c->d_stage_out, c->stream);
     else if (b.lay.pix == PIX_YUV16)
         launch_y16_to_bgr(c->d_stage_in, b.n, b.H, b.W, b.row_stride, b.frame_stride, b.lay.y16, *b.lay.mx, c->d_stage_out, c->stream);
@@ -1782,6 +1819,14 @@ extern "C" int melf_yuv422_10_to_bgr(melf_ctx* c, const void* frames_host, const
 {
     FrameBatch b;
     if (int rc = checked(c, check_yuv422_10(frames_host, f, &b))) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return to_bgr(c, frames_host, b, bgr_out_host);
+}
+
+extern "C" int melf_packed32_to_bgr(melf_ctx* c, const void* frames_host, const melf_packed32_frames* f, uint8_t* bgr_out_host)
+{
+    FrameBatch b;
+    if (int rc = checked(c, check_packed32(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return to_bgr(c, frames_host, b, bgr_out_host);
 }

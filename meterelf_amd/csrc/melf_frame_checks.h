@@ -246,6 +246,60 @@ inline const char* check_yuv422_10(const void* frames, const melf_yuv422_10_fram
     return nullptr;
 }
 
+// melf_packed32_frames (melf_process_packed32*, melf_packed32_to_bgr): one 32-bit word per pixel, three 8-bit reads at pos[0..2]; the
+// extent reaches to the end of the last row's last word.  Its messages have names, in one table, as YUV422_10_MESSAGES:
+// tests/p32_bounds_main.cpp sweeps this check and counts, through the table, that every one of them was produced.
+enum Packed32Msg { P32_DESC_NULL, P32_COLOUR, P32_MATRIX_YUV, P32_MATRIX_RGB, P32_RESERVED, P32_POS_RANGE, P32_POS_OVERLAP, P32_SHAPE,
+                   P32_PITCH_SMALL, P32_PITCH_LARGE, P32_STRIDE_SMALL, P32_STRIDES, P32_FRAMES_NULL, P32_BASE, P32_MESSAGES };
+constexpr const char* PACKED32_MESSAGES[P32_MESSAGES] = {
+    "32-bit packed frame descriptor is NULL",
+    "unknown colour of 32-bit packed frames (accepted: 0 YUV, 1 RGB)",
+    "unknown YUV matrix of 32-bit packed frames (accepted: 0 BT.601 limited, 2 BT.601 full, 3 BT.709 limited, 4 BT.709 full)",
+    "matrix of 32-bit packed RGB frames is not 0",
+    "reserved field of the 32-bit packed frame descriptor is not 0",
+    "a read position of 32-bit packed frames is outside 0 .. 24",
+    "two reads of 32-bit packed frames overlap (positions less than 8 bits apart)",
+    "bad batch shape of 32-bit packed frames",
+    "row_pitch of 32-bit packed frames smaller than a row",
+    "row_pitch of 32-bit packed frames too large",
+    "frame_stride of 32-bit packed frames smaller than a frame",
+    "32-bit packed frames need a 4-byte aligned row_pitch and frame_stride",
+    "frames pointer of 32-bit packed frames is NULL",
+    "32-bit packed frames need a 4-byte aligned base",
+};
+inline const char* check_packed32(const void* frames, const melf_packed32_frames* f, FrameBatch* b)
+{
+    const char* const* const msg = PACKED32_MESSAGES;
+    if (!f) return msg[P32_DESC_NULL];
+    if (f->colour != MELF_P32_YUV && f->colour != MELF_P32_RGB) return msg[P32_COLOUR];
+    const bool yuv = f->colour == MELF_P32_YUV;
+    const YuvMatrix* mx = yuv ? yuv_matrix(f->matrix) : nullptr;
+    if (yuv && !mx) return msg[P32_MATRIX_YUV];
+    if (!yuv && f->matrix != 0) return msg[P32_MATRIX_RGB];
+    if (f->reserved != 0 || f->reserved2 != 0) return msg[P32_RESERVED];
+    for (int k = 0; k < 3; ++k)
+        if (f->pos[k] < 0 || f->pos[k] > 24) return msg[P32_POS_RANGE];
+    for (int i = 0; i < 3; ++i)
+        for (int j = i + 1; j < 3; ++j) {
+            const int d = f->pos[i] - f->pos[j];
+            if (d > -8 && d < 8) return msg[P32_POS_OVERLAP];
+        }
+    if (f->n < 0 || f->H <= 0 || f->W <= 0) return msg[P32_SHAPE];
+    const int64_t row = (int64_t)f->W * 4;
+    if (f->row_pitch < row) return msg[P32_PITCH_SMALL];
+    if (f->row_pitch > INT32_MAX) return msg[P32_PITCH_LARGE];
+    const int64_t extent = (int64_t)(f->H - 1) * f->row_pitch + row;
+    if (f->frame_stride < extent) return msg[P32_STRIDE_SMALL];
+    if (((uint64_t)f->row_pitch | (uint64_t)f->frame_stride) & 3) return msg[P32_STRIDES];
+    const Packed32Fields fields = {{(uint32_t)f->pos[0], (uint32_t)f->pos[1], (uint32_t)f->pos[2]}};
+    *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch,
+                    FrameLayout::packed32(yuv ? PIX_P32_YUV : PIX_P32_RGB, fields, mx, (size_t)extent)};
+    if (f->n == 0) return nullptr;
+    if (!frames) return msg[P32_FRAMES_NULL];
+    if ((uintptr_t)frames & 3) return msg[P32_BASE];
+    return nullptr;
+}
+
 // melf_planar_frames (melf_process_planes*): the extent reaches to the last sample of the frame's last plane
 inline const char* check_planes(const void* frames, const melf_planar_frames* f, FrameBatch* b)
 {

@@ -108,6 +108,16 @@ struct Yuv16Planes {
 // packed 8-bit 4:2:2 frames.  Nothing travels with the pix but the matrix.
 constexpr int PIX_V210 = 56, PIX_Y210 = 57;
 inline bool pix_p10(int pix) { return pix == PIX_V210 || pix == PIX_Y210; }
+// 32-bit packed 4:4:4 frames (melf_process_packed32*: AYUV / VUYA, Y410, X2RGB10 ..): the launch's pix.  A pixel is one little-endian
+// 32-bit word; base, frame_stride and row_stride (bytes) are multiples of 4, x0 and cols count pixels.  The word holds three 8-bit
+// reads, read k = (word >> pos[k]) & 255 (Packed32Fields: the same for every lane, so the kernels keep it in SGPRs and a read is one
+// v_bfe_u32 with a scalar offset); every other bit is ignored.  PIX_P32_YUV: the reads are Y, U, V, converted under the matrix like
+// the samples of an 8-bit 4:4:4 frame; PIX_P32_RGB: they are R, G, B, and nothing is converted.
+constexpr int PIX_P32_YUV = 64, PIX_P32_RGB = 65;
+inline bool pix_p32(int pix) { return pix == PIX_P32_YUV || pix == PIX_P32_RGB; }
+struct Packed32Fields {
+    uint32_t pos[3];       // low bit of the 8 bits read of Y, U, V / R, G, B: 0 .. 24
+};
 
 // How the frames of one launch lie in memory, beside the base, the strides and the rectangle of MatchSrc / DialsSrc: the pixel
 // layout and what goes with it.  Host side only: the launchers hand the kernels the members by value.  Made by the makers below
@@ -116,10 +126,11 @@ struct FrameLayout {
     int pix;
     YuvPlanes yuv;         // pix_yuv(pix): the chroma planes
     PlanarPlanes planes;   // PIX_PLANAR: where the three planes start
-    const YuvMatrix* mx;   // pix_yuv(pix), pix_p422(pix), pix_p10(pix), PIX_YUVP, PIX_YUV16: the frames' colour conversion, never NULL there
+    const YuvMatrix* mx;   // pix_yuv(pix), pix_p422(pix), pix_p10(pix), PIX_YUVP, PIX_YUV16, PIX_P32_YUV: the frames' colour conversion, never NULL there
     size_t extent;         // bytes a kernel may read of the LAST frame, from its first byte (the others: frame_stride)
     YuvPlanarPlanes yuvp;  // PIX_YUVP: the chroma planes and their subsampling (mx: the conversion, as above)
     Yuv16Planes y16;       // PIX_YUV16: the chroma planes of 16-bit samples and the reduction (mx: the conversion, as above)
+    Packed32Fields p32;    // pix_p32(pix): where the three reads sit in a pixel's word (PIX_P32_YUV: mx the conversion; _RGB: mx NULL)
 
     static FrameLayout packed(int pix /* MELF_PIX_* */, size_t extent) { return FrameLayout{pix, {}, {}, nullptr, extent}; }
     static FrameLayout yuv420(int pix /* PIX_NV12, PIX_I420 */, const YuvPlanes& yp, const YuvMatrix& mx, size_t extent)
@@ -141,6 +152,11 @@ struct FrameLayout {
     static FrameLayout yuv422_10(int pix /* PIX_V210, PIX_Y210 */, const YuvMatrix& mx, size_t extent)
     {
         return FrameLayout{pix, {}, {}, &mx, extent};
+    }
+    static FrameLayout packed32(int pix /* PIX_P32_YUV, PIX_P32_RGB */, const Packed32Fields& fields, const YuvMatrix* mx /* NULL for _RGB */,
+                                size_t extent)
+    {
+        return FrameLayout{pix, {}, {}, mx, extent, {}, {}, fields};
     }
     static FrameLayout planar(const PlanarPlanes& pl, size_t extent) { return FrameLayout{PIX_PLANAR, {}, pl, nullptr, extent}; }
     static FrameLayout plane(size_t extent) { return FrameLayout{PIX_PLANE, {}, {}, nullptr, extent}; }

@@ -6,6 +6,7 @@
 #include "melf_internal.h"
 #include "melf_y16_addr.h"
 #include "melf_p10_addr.h"
+#include "melf_p32_addr.h"
 
 namespace melf {
 
@@ -534,6 +535,48 @@ struct DialY210 : DialFrame<DialY210> {
     __device__ __forceinline__ Window window(int wx0, int npiece, int pc, int, int rs_u, int tw) const
     {
         return Window{*this, p10::quads_inside(wx0, npiece, tw), rs_u, p10::lane_fx0(fx_m, wx0, npiece, pc)};
+    }
+};
+
+// 32-bit packed 4:4:4 frames (k_p32_needle, melf_process_packed32*): one little-endian word per pixel, base, rows and frames 4-byte
+// aligned; three 8-bit reads at the positions of `fields` (Packed32Fields, the same for every lane: scalar operands), YUV: Y, U, V
+// under the launch's matrix, else R, G, B.  One pixel: its word, one aligned dword.  A lane's four window pixels are their four
+// words, one 16-byte load from a 4-byte aligned address exactly as DialPacked<4>'s -- the four are pixels of the crop's rows when the
+// pieces lie inside the crop, so nothing is read outside a row, and no quad has to start at an even pixel.  unpack: three v_bfe_u32
+// per pixel, then yuv_chroma / yuv_bgr with one chroma per pixel as DialYuvPlanar<0, 1> (YUV), or two v_lshl_or_b32 into B G R.
+template <bool YUV>
+struct DialWord32 : DialFrame<DialWord32<YUV>> {
+    using Base = DialFrame<DialWord32<YUV>>;
+    struct Args { const Packed32Fields& fields; const YuvMatrix& ymat; };
+    const Packed32Fields& fields;
+    const YuvMatrix& ymat;   // (YUV only)
+    __device__ __forceinline__ DialWord32(const DialsSrc& s, const Args& a, const melf_params&, const uint8_t* frame_, int mx, int my)
+        : Base(s, frame_, mx, my), fields(a.fields), ymat(a.ymat) {}
+    // a word -> the B G R dword
+    __device__ __forceinline__ uint32_t word_bgr(uint32_t w) const
+    {
+        if constexpr (YUV)
+            return yuv_bgr((int)p32::read8(w, fields.pos[0]), yuv_chroma<false>((int)p32::read8(w, fields.pos[1]), (int)p32::read8(w, fields.pos[2]), ymat), ymat);
+        else
+            return p32::rgb_bgr(w, fields);
+    }
+    __device__ __forceinline__ uint32_t px(int X, int Y) const
+    {
+        return word_bgr(*(const uint32_t*)(this->frame + p32::px_off(this->fy_m + Y, this->rstride, this->fx_m + X)));
+    }
+    struct Window {
+        const DialWord32& S;
+        bool quads;
+        int rs_u, fx0;   // the lane's first pixel in the frame
+        __device__ __forceinline__ u32x4v request(int, int Y) const { return load16(S.frame + p32::dial_off(S.fy_m + Y, (size_t)rs_u, fx0)); }
+        __device__ __forceinline__ u32x4v unpack(int, const u32x4v r) const
+        {
+            return u32x4v{S.word_bgr(r.x), S.word_bgr(r.y), S.word_bgr(r.z), S.word_bgr(r.w)};
+        }
+    };
+    __device__ __forceinline__ Window window(int wx0, int npiece, int pc, int, int rs_u, int tw) const
+    {
+        return Window{*this, Base::pieces_inside(wx0, npiece, tw), rs_u, this->lane_fx0(wx0, npiece, pc)};
     }
 };
 

@@ -185,6 +185,10 @@ void launch_y16_to_bgr(const uint8_t* d_src, int n, int H, int W, int y_pitch, s
 void launch_p10_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int row_pitch, size_t frame_stride, const YuvMatrix& mx,
                        uint8_t* d_dst, hipStream_t stream);
 
+// the same for 32-bit packed 4:4:4 (melf_packed32_to_bgr): pix PIX_P32_YUV (mx: the conversion) / PIX_P32_RGB (mx NULL)
+void launch_p32_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int row_pitch, size_t frame_stride, const Packed32Fields& fields,
+                       const YuvMatrix* mx, uint8_t* d_dst, hipStream_t stream);
+
 // the same for packed YUV 4:2:2 (melf_yuv422_to_bgr): n frames at d_src (row_pitch, frame_stride), pix PIX_YUYV / _UYVY / _YVYU
 void launch_p422_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int row_pitch, size_t frame_stride, const YuvMatrix& mx,
                         uint8_t* d_dst, hipStream_t stream);

@@ -39,6 +39,11 @@
 //       8-byte aligned.  The window is 17 macropixels, 34 aligned dwords as eight 16-byte loads and two dwords; one byte permute per
 //       macropixel picks the high bytes Y0 U Y1 V, and from there on the arm is PX 22's.  Offsets, rows_safe and the lane's own
 //       test of both arms: melf_p10_addr.h.
+//   With MELF_P32_BODY defined instead (k_p32_lplane): PX 28 / 29 = 32-bit packed 4:4:4 frames (melf_process_packed32*), one word per
+//       pixel, everything 4-byte aligned, three 8-bit reads at the positions of `fields` (Packed32Fields: scalars).  The loads are
+//       PX 4's, taken from the same functions of melf_prep_addr.h: 32 pixels are 128 bytes, eight 16-byte loads, guarded like PX 4's
+//       (rows_safe per row, the lane's own test, one dword per pixel where both fail).  PX 28: the reads are Y, U, V, L straight from
+//       them (yuv_lightness, one chroma per pixel); PX 29: they are R, G, B, L from the largest and the smallest as for PX 4.
 // The 8-bit arms (PX 3, 4, 20 .. 24) compute their windows' offsets and lengths, rows_safe and the lane's own test with the functions
 // of melf_prep_addr.h, as PX 25 does with melf_y16_addr.h: tests/prep_bounds_main.cpp sweeps the same functions on the CPU.
     constexpr int PB = prep::packed_pb(PX);     // bytes per pixel of the frame reads
@@ -104,6 +109,10 @@
     // (the same for the 136-byte window of a Y210 lane: 17 macropixels from the one of its even pixel)
     const int xodd = src.x0 & 1;
     const bool rows_safe = p10::y210_rows_safe(grp, nframes, src.frame_stride, src.y0 + y, (size_t)src.row_stride, src.x0, nkb, src.readable);
+#elif defined(MELF_P32_BODY)
+    (void)PB; (void)WIN;
+    // (the same for the 128-byte window of a lane of 4-byte words: PX 4's test)
+    const bool rows_safe = prep::packed_rows_safe(grp, nframes, src.frame_stride, src.y0 + y, src.row_stride, src.x0, nkb, prep::packed_pb(4), prep::packed_win(4), src.readable);
 #elif defined(MELF_PLANAR_BODY)
     (void)PB; (void)WIN;
     // (the same for the three 36-byte windows of a planar lane, and for their first dword: with a base that is not 4-byte aligned
@@ -423,6 +432,42 @@
                         const uint32_t sv = p10::y210_px_yuv(mp[0], mp[1], fx & 1);
                         const YuvChroma c = yuv_chroma((int)((sv >> 8) & 255u), (int)(sv >> 16), mx);
                         const int L = yuv_lightness((int)(sv & 255u), yuv_cmax(c), yuv_cmin(c), mx);
+                        w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
+                    }
+                }
+            } else
+#elif defined(MELF_P32_BODY)
+            if (PX == 28 || PX == 29) {
+                const size_t o = prep::packed_x_off(src.x0 + xbeg, prep::packed_pb(4));
+                const uint8_t* p = prow + o;
+                // (as PX 4: the last block's window may reach past the crop, never past the caller's buffer)
+                if (rows_safe || prep::packed_lane_ok(f, src.frame_stride, src.y0 + y, src.row_stride, o, prep::packed_win(4), src.readable)) {
+                    const u32x4a4* q = (const u32x4a4*)p;
+                    u32x4a4 d[8];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) d[i] = q[i];
+#pragma unroll
+                    for (int k = 0; k < 32; ++k) {
+                        const uint32_t wd = d[k >> 2][k & 3];
+                        int L;
+                        if (PX == 28) {
+                            const YuvChroma c = yuv_chroma((int)p32::read8(wd, fields.pos[1]), (int)p32::read8(wd, fields.pos[2]), mx);
+                            L = yuv_lightness((int)p32::read8(wd, fields.pos[0]), yuv_cmax(c), yuv_cmin(c), mx);
+                        } else {
+                            L = hls_lightness_fast((int)p32::read8(wd, fields.pos[2]), (int)p32::read8(wd, fields.pos[1]), (int)p32::read8(wd, fields.pos[0]));
+                        }
+                        w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
+                    }
+                } else {  // last bytes of the frame buffer: one dword per pixel
+                    for (int k = 0; k < npx; ++k) {
+                        const uint32_t wd = ((const uint32_t*)p)[k];
+                        int L;
+                        if (PX == 28) {
+                            const YuvChroma c = yuv_chroma((int)p32::read8(wd, fields.pos[1]), (int)p32::read8(wd, fields.pos[2]), mx);
+                            L = yuv_lightness((int)p32::read8(wd, fields.pos[0]), yuv_cmax(c), yuv_cmin(c), mx);
+                        } else {
+                            L = hls_lightness((int)p32::read8(wd, fields.pos[2]), (int)p32::read8(wd, fields.pos[1]), (int)p32::read8(wd, fields.pos[0]));
+                        }
                         w[k >> 2] |= (uint32_t)((L - 128) & 255) << ((k & 3) * 8);
                     }
                 }

@@ -202,7 +202,8 @@ int melf_process_frames_dev(melf_ctx* ctx, const void* d_frames, const melf_fram
  * triples differ from it at all under code 2, 1 315 under code 3, none under code 4).  Code 2 is the JFIF matrix but not
  * libjpeg's tables bit for bit: libjpeg rounds the chroma terms separately at 16 bits, and 8 332 triples differ by 1 (the JPEG
  * entry points below decode with libjpeg's own arithmetic and are not affected by any of this).
- * Out of scope: BT.2020, interpolated chroma, chroma siting, planes in separate allocations.  (4:2:2, 4:4:4 and 4:4:0 planes and
+ * Out of scope: BT.2020, interpolated chroma, chroma siting, a frame's planes in separate allocations (frames in separate
+ * allocations: melf_process_frame_list*, below).  (4:2:2, 4:4:4 and 4:4:0 planes and
  * NV21: melf_process_yuv_planar*; 10-, 12- and 16-bit samples: melf_process_yuv16*, both below.)
  * Frame f starts at frames + f * frame_stride; its Y row y at + y * y_pitch (W bytes), its chroma row y >> 1 at
  * + u_offset / v_offset + (y >> 1) * c_pitch: NV12 W bytes U V U V .. (v_offset == u_offset + 1), I420 W / 2 bytes per plane.
@@ -508,6 +509,47 @@ int melf_process_planes(melf_ctx* ctx, const void* frames_host, const melf_plana
 int melf_process_planes_dev(melf_ctx* ctx, const void* d_frames, const melf_planar_frames* f, void* d_results, melf_result* out_host,
                             void* stream);
 
+/* ---- the same path for frames in SEPARATE ALLOCATIONS: the surfaces of a hardware decoder's pool (rocDecode, VA-API), a list of
+ * tensors from a video reader or torchvision.io.decode_jpeg(device=...), one V4L2 / DRM capture buffer per frame ----
+ * Every entry point above takes one base pointer and a frame_stride.  These two take, beside the descriptor of one of the eight
+ * families above, a HOST array of n frame pointers (device pointers for _dev, host pointers otherwise); the library copies the
+ * array before it returns, so the caller may free it at once.  Frames may alias or repeat: they are only read.
+ *     family   MELF_LIST_*: which descriptor `desc` points to
+ *     desc     the family's descriptor.  Its n is the length of the list; its frame_stride is not looked at.  Everything else is
+ *              checked as for a batch of one frame, and every pointer of the list against the family's NULL and alignment rules:
+ *              MELF_ERR_INVALID before anything is launched or copied, the message naming the offending frame's index.  n == 0
+ *              passes; an unknown family is MELF_ERR_INVALID.
+ *     frames   from each pointer one frame's extent must be readable -- (H - 1) * row_pitch + a row, or up to the last sample of
+ *              the frame's last plane, as the family states it for the last frame of a batch -- and nothing behind it nor before
+ *              the pointer is read: each frame may be the last thing in its mapping.
+ * The records are byte-identical to the family's melf_process_* / melf_process_*_dev call on one contiguous batch that holds the
+ * same frames in list order.
+ * How: no reading kernel takes a pointer table.  One kernel (k_gather_rows) first copies the rows of the meter_rect crop of every
+ * listed frame -- the rows as they are, the origin rounded to whole chroma blocks, macropixels or v210 groups where the format
+ * needs it, exactly the small staged frames the host-fed path packs on the CPU -- into a staged batch in HBM, which the unchanged
+ * kernels then read.  The price is one extra read and one extra write of the crop's bytes only (187 500 of a 640 x 480 BGR frame's
+ * 921 600), against the read and write of every whole frame that torch.stack or n hipMemcpy calls cost a caller before.  Measured
+ * on one MI355X, 1024-frame config-3 steps (profiles/frame_list/frame_list_rate.txt): see README.md, "Frames in separate
+ * allocations".
+ * The device call takes a lane as melf_process_frames_dev does.  The staged batch and the pointer table belong to the lane, so
+ * calls on two caller streams do not share them; lists longer than 1024 frames go through the lane's staging buffer in chunks of
+ * 1024.  The gather kernel is ordered after everything the caller's stream held at the call, also under
+ * melf_ctx_set_frames_resident (the promise there covers batches, not lists: a decoder may still be writing the frames; the call
+ * then runs on the lane's own stream and the caller's stream continues when it is done).  d_results / out_host / stream: as for
+ * melf_process_frames_dev.  The host call is melf_process_frames and its siblings with the i-th pointer as frame i.
+ * frames in separate allocations: melf_process_frame_list*; a frame's planes in separate allocations are still not there. */
+enum { MELF_LIST_FRAMES = 0,      /* desc: const melf_frames*            */
+       MELF_LIST_YUV = 1,         /* const melf_yuv_frames*              */
+       MELF_LIST_YUV422 = 2,      /* const melf_yuv422_frames*           */
+       MELF_LIST_YUV_PLANAR = 3,  /* const melf_yuv_planar_frames*       */
+       MELF_LIST_YUV16 = 4,       /* const melf_yuv16_frames*            */
+       MELF_LIST_YUV422_10 = 5,   /* const melf_yuv422_10_frames*        */
+       MELF_LIST_PACKED32 = 6,    /* const melf_packed32_frames*         */
+       MELF_LIST_PLANES = 7 };    /* const melf_planar_frames*           */
+int melf_process_frame_list_dev(melf_ctx* ctx, int family, const void* desc, const void* const* d_frames, void* d_results,
+                                melf_result* out_host, void* stream);
+int melf_process_frame_list(melf_ctx* ctx, int family, const void* desc, const void* const* frames_host, melf_result* out_host);
+
 /* ---- stage entry points (parity tests and roofline runs) ----------------- */
 
 /* convert_to_hls (meterelf/_utils.py:100-102): cvtColor(BGR2HLS_FULL) + uint8
@@ -536,6 +578,10 @@ int melf_hls_inrange_close_dev(melf_ctx* ctx, const void* d_frames, int n, int H
  * tables filled first); > 0: blocks of that many chunks from a work queue.  The launch
  * is timed like the fused kernel's (melf_ctx_set_profiling(1), entry MELF_K_STREAM_PROBE of melf_ctx_timings). */
 int melf_stream_probe_dev(melf_ctx* ctx, const void* d_in, size_t in_bytes, void* d_out, int chunks_per_block, void* stream);
+/* DIAGNOSTIC BUILD ONLY, measurement aid of tools/frame_list_rate.py: melf_process_frame_list_dev up to and including its gather
+ * kernel -- the checks, the lane, the pointer table, k_gather_rows into the lane's staged batch -- and nothing of the reading path.
+ * *bytes_moved (may be NULL): the bytes the gather read plus the bytes it wrote.  Timed as entry MELF_K_GATHER of melf_ctx_timings. */
+int melf_gather_frame_list_dev(melf_ctx* ctx, int family, const void* desc, const void* const* d_frames, void* stream, size_t* bytes_moved);
 #endif
 
 /* Number of entries of the fused stage's hue lookup table whose in-range answer
@@ -676,7 +722,8 @@ int melf_ctx_set_frames_resident(melf_ctx* ctx, int on);
  * by hipEvents on its stream; melf_ctx_timings drains them (synchronising) and
  * returns per-kernel accumulated milliseconds and launch counts. */
 enum { MELF_K_LPLANE = 0, MELF_K_MATCH = 1, MELF_K_DIALS = 2, MELF_K_FUSED_MASK = 3, MELF_K_HLS = 4,
-       MELF_K_JPEG_HUFF = 5, MELF_K_JPEG_IDCT = 6, MELF_K_JPEG_COLOR = 7, MELF_K_STREAM_PROBE = 8, MELF_K_COUNT = 9 };
+       MELF_K_JPEG_HUFF = 5, MELF_K_JPEG_IDCT = 6, MELF_K_JPEG_COLOR = 7, MELF_K_STREAM_PROBE = 8,
+       MELF_K_GATHER = 9 /* k_gather_rows: melf_process_frame_list_dev */, MELF_K_COUNT = 10 };
 /* Which kernel, in which layout, computed the template match (meterelf/_utils.py:91-97: ONE cv2.matchTemplate code
  * path in the reference; here the batch size and the crop shape select among three kernels and, for the tuned one,
  * among wave layouts) of the context's most recent call.  Tests assert it, so that a change of a dispatch threshold

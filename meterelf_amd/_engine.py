@@ -283,6 +283,64 @@ class MeterReader:
         desc = v.descriptor()
         return self._read_view(v, out, lambda: self.ctx.process_planes(v.ptr, desc), lambda **kw: self.ctx.process_planes_dev(v.ptr, desc, **kw))
 
+    # layout of read_frame_list: (the batch method's view function, whether it takes a matrix and with which default)
+    _LIST_VIEWS = {
+        'views': ('frames_view', None), 'yuv': ('yuv_frames_view', 'bt601'), 'yuv422': ('yuv422_frames_view', 'bt601'),
+        'yuv_planar': ('yuv_planar_frames_view', 'bt601'), 'yuv16': ('yuv16_frames_view', ''), 'yuv422_10': ('yuv422_10_frames_view', ''),
+        'packed32': ('packed32_frames_view', ''), 'planar': ('planar_frames_view', None),
+    }
+
+    def read_frame_list(self, frames, layout: str, pixel_format: str, matrix=None, width=None, out=None):
+        """Frames in separate allocations -- the surfaces of a decoder's pool, a list of tensors from a video reader -- -> records,
+        equal to the batch method's on one array holding the same frames in list order (melf_process_frame_list*), without the
+        torch.stack or the copies that would make that array: one kernel gathers the meter crop's rows of every frame, and only
+        those, into a staged batch which the reading kernels take.  layout names the family by its batch method: 'views'
+        (read_frame_views), 'yuv' (read_yuv_frames), 'yuv422', 'yuv_planar', 'yuv16', 'yuv422_10', 'packed32', 'planar'
+        (read_planar_frames; pixel_format is its channel_order); pixel_format, matrix and width are that method's, with its defaults.
+        frames: a sequence whose elements each have the shape of ONE frame of that method's array (the documented shape without
+        the leading N): numpy arrays / torch CPU tensors (host path), or torch tensors on this reader's GPU (enqueued on
+        torch.cuda.current_stream).  Every element is described by the method's _hip.*_frames_view as frame[None]; all must agree
+        in everything but the address.  ValueError: host and device elements mixed, an element on another device, elements that
+        differ (the message says which and in what), an element the view would have to copy (a layout the descriptor cannot
+        express).  out: as for the batch methods, a uint8 device tensor (len(frames), RESULT_DTYPE.itemsize)."""
+        if layout not in self._LIST_VIEWS:
+            raise ValueError('layout %r is none of %s' % (layout, ', '.join(sorted(self._LIST_VIEWS))))
+        (view_name, default_matrix) = self._LIST_VIEWS[layout]
+        args = [pixel_format]
+        if default_matrix is not None:
+            args.append(matrix if matrix is not None or default_matrix == '' else default_matrix)
+        elif matrix is not None:
+            raise ValueError('layout %r takes no matrix' % layout)
+        if layout == 'yuv422_10':
+            args.append(width)
+        elif width is not None:
+            raise ValueError('layout %r takes no width' % layout)
+        frames = list(frames)
+        views = []
+        for (i, f) in enumerate(frames):
+            if not (_hip._is_torch(f) or isinstance(f, np.ndarray)):
+                f = np.asarray(f)
+            v = getattr(_hip, view_name)(f[None], *args)
+            if v.copied:
+                raise ValueError('frame %d of the list has a layout the %r descriptor cannot express (it would have to be copied)' % (i, layout))
+            if views:
+                if v.on_device != views[0].on_device:
+                    raise ValueError('frame %d of the list is in %s memory, frame 0 in %s memory' % ((i,) + tuple(
+                        'device' if w.on_device else 'host' for w in (v, views[0]))))
+                for name in v._fields:
+                    if name not in ('ptr', 'array', 'on_device') and getattr(v, name) != getattr(views[0], name):
+                        raise ValueError('frame %d of the list differs from frame 0 in %s: %r, not %r' % (i, name, getattr(v, name), getattr(views[0], name)))
+            views.append(v)
+        n = len(views)
+        if n == 0:
+            return out if out is not None else np.zeros(0, _hip.RESULT_DTYPE)
+        v0 = views[0]
+        desc = v0.descriptor() if hasattr(v0, 'descriptor') else _hip.MelfFrames(v0.pixel_format, 1, v0.H, v0.W, v0.row_pitch, v0.frame_stride)
+        desc.n = n
+        ptrs = [v.ptr for v in views]
+        return self._read_view(v0._replace(n=n), out, lambda: self.ctx.process_frame_list(layout, desc, ptrs),
+                               lambda **kw: self.ctx.process_frame_list_dev(layout, desc, ptrs, **kw))
+
     def read_crops(self, crops: np.ndarray) -> np.ndarray:
         """Already meter_rect-cropped images (the reference's bgr_image injection)."""
         (_n, h, w, _c) = crops.shape

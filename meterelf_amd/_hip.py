@@ -26,7 +26,9 @@ FRAME_DIALS_NOT_FOUND = 1
 FRAME_NEEDLE_CONTOURS_NOT_FOUND = 2
 FRAME_ANGLE_UNDETERMINED = 3
 
-K_LPLANE, K_MATCH, K_DIALS, K_FUSED_MASK, K_HLS, K_JPEG_HUFF, K_JPEG_IDCT, K_JPEG_COLOR, K_STREAM_PROBE, K_COUNT = range(10)
+K_LPLANE, K_MATCH, K_DIALS, K_FUSED_MASK, K_HLS, K_JPEG_HUFF, K_JPEG_IDCT, K_JPEG_COLOR, K_STREAM_PROBE, K_GATHER, K_COUNT = range(11)
+# MELF_LIST_* of include/meterelf_hip.h: the family of a frame list's descriptor, by the name MeterReader.read_frame_list gives it
+LIST_FAMILIES = {'views': 0, 'yuv': 1, 'yuv422': 2, 'yuv_planar': 3, 'yuv16': 4, 'yuv422_10': 5, 'packed32': 6, 'planar': 7}
 JPEG_OK, JPEG_UNSUPPORTED, JPEG_CORRUPT, JPEG_SIZE_MISMATCH, JPEG_UNREADABLE = 0, 1, 2, 3, 4
 FILES_IN_FLIGHT_MAX = 3   # MELF_FILES_IN_FLIGHT_MAX (include/meterelf_hip.h); tests compare with melf_jpeg_files_in_flight_max()
 
@@ -209,7 +211,7 @@ DIALS32_FAMILIES = ('p32yuv', 'p32rgb')
 
 # every symbol include/meterelf_hip.h declares for the product library; DIAG_EXPORTS: what its `#ifdef MELF_DIAG` part adds (the
 # diagnostic build, make -C meterelf_amd/csrc diag, loaded through MELF_LIB_PATH)
-DIAG_EXPORTS = ['melf_stream_probe_dev']
+DIAG_EXPORTS = ['melf_stream_probe_dev', 'melf_gather_frame_list_dev']
 EXPORTS = [
     'melf_last_error', 'melf_abi_version', 'melf_device_count', 'melf_build_dial_masks',
     'melf_blob_size', 'melf_blob_pack', 'melf_blob_params', 'melf_ctx_create', 'melf_ctx_create_bcast', 'melf_ctx_destroy',
@@ -220,6 +222,7 @@ EXPORTS = [
     'melf_process_yuv16', 'melf_process_yuv16_dev', 'melf_yuv16_to_bgr',
     'melf_process_yuv422_10', 'melf_process_yuv422_10_dev', 'melf_yuv422_10_to_bgr',
     'melf_process_packed32', 'melf_process_packed32_dev', 'melf_packed32_to_bgr',
+    'melf_process_frame_list', 'melf_process_frame_list_dev',
     'melf_bgr2hls', 'melf_hls_inrange_close', 'melf_hls_inrange_close_dev', 'melf_match_ccoeff',
     'melf_read_dials', 'melf_aligned_average', 'melf_inrange', 'melf_ctx_fused_table_ties', 'melf_ctx_fused_variant', 'melf_ctx_set_frames_resident', 'melf_ctx_last_match', 'melf_ctx_last_dials', 'melf_match_layout_query', 'melf_match_gen_plan_query', 'melf_ctx_set_profiling', 'melf_ctx_timings', 'melf_kernel_name',
     'melf_jpeg_probe', 'melf_jpeg_probe_batch', 'melf_jpeg_decode_batch', 'melf_jpeg_clean_segment', 'melf_jpeg_process_batch',
@@ -280,6 +283,10 @@ def lib():
     L.melf_packed32_to_bgr.argtypes = [vp, vp, C.POINTER(MelfPacked32Frames), vp]
     L.melf_process_planes.argtypes = [vp, vp, C.POINTER(MelfPlanarFrames), vp]
     L.melf_process_planes_dev.argtypes = [vp, vp, C.POINTER(MelfPlanarFrames), vp, vp, vp]
+    L.melf_process_frame_list.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.melf_process_frame_list_dev.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    if hasattr(L, 'melf_gather_frame_list_dev'):   # the diagnostic build only
+        L.melf_gather_frame_list_dev.argtypes = [vp, C.c_int, vp, vp, vp, C.POINTER(C.c_size_t)]
     L.melf_process_stream_dev.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, vp]
     L.melf_bgr2hls.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp]
     L.melf_hls_inrange_close.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
@@ -1308,6 +1315,45 @@ class Context:
     def process_planes_dev(self, d_frames_ptr, desc, d_results_ptr=None, want_host=True, stream=None):
         """Planar frames in HBM (melf_process_planes_dev, as process_frames_dev).  Returns records when want_host."""
         return self._dev(self._L.melf_process_planes_dev, d_frames_ptr, desc, d_results_ptr, want_host, stream)
+
+    # --- frames in separate allocations ---
+    @staticmethod
+    def _pointer_table(ptrs, desc):
+        """The host array of frame pointers melf_process_frame_list* take (a NULL entry stays NULL: the library names it); a
+        ctypes array made by an earlier call is taken as it is.  The library reads desc.n entries: fewer is a ValueError."""
+        if len(ptrs) < desc.n:
+            raise ValueError('the descriptor counts %d frames, the list holds %d pointers' % (desc.n, len(ptrs)))
+        if isinstance(ptrs, C.Array):
+            return ptrs
+        return (C.c_void_p * len(ptrs))(*[int(p) or None for p in ptrs])
+
+    def process_frame_list(self, family, desc, frame_ptrs):
+        """Host frames in separate allocations (melf_process_frame_list) -> records.  family: LIST_FAMILIES' code or name; desc: the
+        family's descriptor, its n the length of the list (frame_stride is not looked at); frame_ptrs: the frames' addresses."""
+        family = LIST_FAMILIES.get(family, family)
+        out = np.zeros(max(desc.n, 0), RESULT_DTYPE)
+        check(self._L.melf_process_frame_list(self._h, family, C.byref(desc), self._pointer_table(frame_ptrs, desc), _ptr(out)))
+        return out
+
+    def process_frame_list_dev(self, family, desc, d_frame_ptrs, d_results_ptr=None, want_host=True, stream=None):
+        """Frames in separate allocations in HBM (melf_process_frame_list_dev, as process_frames_dev): d_frame_ptrs: their device
+        addresses (the library copies the table before it returns).  Returns records when want_host."""
+        family = LIST_FAMILIES.get(family, family)
+        out = np.zeros(max(desc.n, 0), RESULT_DTYPE) if want_host else None
+        check(self._L.melf_process_frame_list_dev(self._h, family, C.byref(desc), self._pointer_table(d_frame_ptrs, desc),
+                                                  C.c_void_p(d_results_ptr) if d_results_ptr else None, _ptr(out) if want_host else None,
+                                                  C.c_void_p(stream) if stream else None))
+        return out
+
+    def gather_frame_list_dev(self, family, desc, d_frame_ptrs, stream=None):
+        """The gather kernel of process_frame_list_dev alone (melf_gather_frame_list_dev: the diagnostic build only) -> the bytes it
+        read plus the bytes it wrote."""
+        if not hasattr(self._L, 'melf_gather_frame_list_dev'):
+            raise HipError('melf_gather_frame_list_dev is part of the diagnostic build only (make -C meterelf_amd/csrc diag; MELF_LIB_PATH)')
+        moved = C.c_size_t(0)
+        check(self._L.melf_gather_frame_list_dev(self._h, LIST_FAMILIES.get(family, family), C.byref(desc), self._pointer_table(d_frame_ptrs, desc),
+                                                 C.c_void_p(stream) if stream else None, C.byref(moved)))
+        return moved.value
 
     # --- stages ---
     def process_stream_dev(self, d_frames_ptr, nbatches, batch_stride, n, H, W, d_results_ptr, results_stride, frame_stride=None,

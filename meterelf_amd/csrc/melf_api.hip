@@ -24,6 +24,7 @@
 #include "melf_device.h"
 #include "melf_frame_checks.h"
 #include "melf_internal.h"
+#include "melf_stage_plan.h"
 #include "melf_threads.h"
 
 using namespace melf;
@@ -57,7 +58,7 @@ extern "C" int melf_device_count(int* count)
 extern "C" const char* melf_kernel_name(int k)
 {
     static const char* names[MELF_K_COUNT] = {"k_lplane", "k_match", "k_dials", "k_fused_mask", "k_bgr2hls",
-                                               "k_jpeg_huff", "k_jpeg_idct", "k_jpeg_color", "k_stream_probe"};
+                                               "k_jpeg_huff", "k_jpeg_idct", "k_jpeg_color", "k_stream_probe", "k_gather"};
     return (k >= 0 && k < MELF_K_COUNT) ? names[k] : "?";
 }
 
@@ -252,6 +253,12 @@ struct melf_ctx {
     int8_t* d_lg[NLANES] = {}; size_t lg_cap[NLANES] = {};
     uint16_t* d_rsum[NLANES] = {}; size_t rsum_cap[NLANES] = {};
     MatchPartial* d_lpart[NLANES] = {}; size_t lpart_cap[NLANES] = {};
+    // frame lists (melf_process_frame_list_dev): per lane the staged batch the gather kernel writes, the pointer table in HBM and
+    // its pinned host copy, and the event of the last upload from that copy (it is not rewritten before the upload has finished)
+    uint8_t* d_list_stage[NLANES] = {}; size_t list_stage_cap[NLANES] = {};
+    const void** d_list_tab[NLANES] = {}; size_t list_tab_cap[NLANES] = {};
+    const void** h_list_tab[NLANES] = {}; size_t h_list_tab_cap[NLANES] = {};
+    hipEvent_t ev_list_tab[NLANES] = {};
     uint32_t* d_fused_tables = nullptr;  // K1b lookup tables (built on the GPU at creation)
     int fused_ambiguous = 0;             // hue-table entries whose answer depends on float32 rounding of the triple
     int fused_active_sectors = 0;        // bit c: hue sector c (max = r/g/b) has in-range entries
@@ -773,6 +780,9 @@ extern "C" void melf_ctx_destroy(melf_ctx* c)
     }
     for (int l = 0; l < melf_ctx::NLANES; ++l) {
         hipFree(c->d_lg[l]); hipFree(c->d_rsum[l]); hipFree(c->d_lpart[l]);
+        hipFree(c->d_list_stage[l]); hipFree(c->d_list_tab[l]);
+        if (c->h_list_tab[l]) hipHostFree(c->h_list_tab[l]);
+        if (c->ev_list_tab[l]) hipEventDestroy(c->ev_list_tab[l]);
         if (c->lane_stream[l]) hipStreamDestroy(c->lane_stream[l]);
         if (c->ev_join[l]) hipEventDestroy(c->ev_join[l]);
     }
@@ -1140,19 +1150,12 @@ static int run_match_impl(melf_ctx* c, const MatchSrc& ms, const FrameLayout& la
 // ------------------------------------------------------------ full path ----
 static const int MAX_FRAMES_PER_LAUNCH = 32768;
 
-// The meter crop of H x W frames: r = {x0, y0, x1, y1} (NULL: the context's meter_rect) clamped to the frame as numpy slicing
-// img[y0:y1, x0:x1] clamps (meterelf/_image.py:54-55)
-struct Crop {
-    int x0, y0, x1, y1, rows, cols;
-};
+// The meter crop of H x W frames (Crop: melf_stage_plan.h): r = {x0, y0, x1, y1} (NULL: the context's meter_rect) clamped to the
+// frame as numpy slicing img[y0:y1, x0:x1] clamps (meterelf/_image.py:54-55)
 static int meter_crop(const melf_params& P, const int* r, int H, int W, Crop* cr)
 {
-    const int rx0 = r ? r[0] : P.rect_x0, ry0 = r ? r[1] : P.rect_y0;
-    const int rx1 = r ? r[2] : P.rect_x1, ry1 = r ? r[3] : P.rect_y1;
-    cr->x0 = rx0 < W ? rx0 : W; cr->x1 = rx1 < W ? rx1 : W;
-    cr->y0 = ry0 < H ? ry0 : H; cr->y1 = ry1 < H ? ry1 : H;
-    cr->rows = cr->y1 - cr->y0; cr->cols = cr->x1 - cr->x0;
-    if (cr->x0 < 0 || cr->y0 < 0 || cr->rows < P.th || cr->cols < P.tw)
+    const int rect[4] = {r ? r[0] : P.rect_x0, r ? r[1] : P.rect_y0, r ? r[2] : P.rect_x1, r ? r[3] : P.rect_y1};
+    if (!clamp_crop(rect, H, W, cr) || cr->rows < P.th || cr->cols < P.tw)
         return fail(MELF_ERR_INVALID, "meter_rect crop is smaller than the dials template (cv2.matchTemplate would assert)");
     return MELF_SUCCESS;
 }
@@ -1384,14 +1387,10 @@ extern "C" int melf_process_stream_dev(melf_ctx* c, const void* d_frames, int nb
 // frames are packed (on the host pool's threads) into one of two pinned staging buffers, copied by DMA on a copy
 // stream and processed on the context's stream, so that packing chunk k+1, the copy of chunk k and the kernels of
 // chunk k-1 overlap.  The kernels see the staged frames as frames of their own, with the rect where the plan says.
-// Every format goes this way (stage_host_frames); a format brings its plan and its packer: what a staged frame looks like, and
-// the rows of the caller's frame that go into it -- copied as they are, no byte is converted or reordered on the CPU.
-struct StagePlan {
-    FrameBatch staged;   // the staged frames as the kernels read them (n: set per chunk); frame_stride: bytes of a staged frame,
-                         // rows at a 64-byte pitch, + 128 spare bytes (the prep kernel's aligned windows reach past the last sample)
-    int rect[4];         // the meter crop inside a staged frame
-    int items;           // the packer's work items per frame
-};
+// Every format goes this way (stage_host_frames); a format brings its plan: what a staged frame looks like, and the rows of the
+// caller's frame that go into it -- copied as they are, no byte is converted or reordered on the CPU.  The plans (StagePlan: the
+// staged frame, the rectangle, the work items and the row runs) are melf_stage_plan.h's, one per family, shared with the frame
+// lists' gather kernel; host_frames below is the one packer.
 
 // What every host entry point needs after its descriptor's checks: somewhere for the records, and a meter crop the template fits
 static int host_crop(const melf_ctx* c, const FrameBatch& b, const melf_result* out_host, Crop* cr)
@@ -1400,11 +1399,20 @@ static int host_crop(const melf_ctx* c, const FrameBatch& b, const melf_result* 
     return meter_crop(c->P, nullptr, b.H, b.W, cr);
 }
 
-// pack(frame, staged, item): writes work item `item` (0 .. sp.items - 1) of the caller's frame at `frame` into its staged frame
-// at `staged`; runs on the host pool's threads.  A template parameter, so that the packer is inlined into the pool's work item.
-template <class Pack>
-static int stage_host_frames(melf_ctx* c, const uint8_t* frames_host, int n, size_t frame_stride, const StagePlan& sp,
-                             melf_result* out_host, const Pack& pack)
+// frame_at(i): the first byte of the caller's frame i -- base + i * frame_stride for a batch (Strided), the i-th pointer of a list
+// (Listed).  pack(frame, staged, item): writes work item `item` (0 .. sp.items - 1) of the caller's frame at `frame` into its staged
+// frame at `staged`; runs on the host pool's threads.  Template parameters, so that both are inlined into the pool's work item.
+struct Strided {
+    const uint8_t* base;
+    size_t frame_stride;
+    const uint8_t* operator()(int i) const { return base + (size_t)i * frame_stride; }
+};
+struct Listed {
+    const void* const* frames;
+    const uint8_t* operator()(int i) const { return (const uint8_t*)frames[i]; }
+};
+template <class FrameAt, class Pack>
+static int stage_host_frames(melf_ctx* c, const FrameAt& frame_at, int n, const StagePlan& sp, melf_result* out_host, const Pack& pack)
 {
     HIP_TRY(hipSetDevice(c->device));
     pool_use_device(c->device);
@@ -1440,7 +1448,7 @@ static int stage_host_frames(melf_ctx* c, const uint8_t* frames_host, int n, siz
         const int items = sp.items;   // of 32 rows or so: a chunk of 128 frames gives a 16-thread pool ~1000 of them
         host_pool().run(m * items, [&](int item) {
             const int i = item / items;
-            pack(frames_host + (size_t)(f0 + i) * frame_stride, pin + (size_t)i * crop_stride, item - i * items);
+            pack(frame_at(f0 + i), pin + (size_t)i * crop_stride, item - i * items);
         });
         pack_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count();
         uint8_t* d_chunk = c->d_crops + (size_t)f0 * crop_stride;
@@ -1460,233 +1468,52 @@ static int stage_host_frames(melf_ctx* c, const uint8_t* frames_host, int n, siz
     return MELF_SUCCESS;
 }
 
-static size_t pitch64(size_t row_bytes) { return (row_bytes + 63) & ~(size_t)63; }
-
-// The pixel layouts of melf_process_batch / melf_process_frames: the staged frame is the crop, its rows (cols * bytes per pixel, read
-// at the caller's row pitch) packed as they are
-static int host_packed(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host)
+// The host-fed path of every family: the family's plan (melf_stage_plan.h: stage_plan), and as the packer the plan's row runs, the
+// rows copied as they are in the plan's work items.  The pixel layouts of melf_process_batch / melf_process_frames keep a packer of
+// their own: crop rows at a 64-byte pitch, packed with streaming (non-temporal) 16-byte stores -- a plain memcpy into the staging
+// buffer reads every destination line before writing it, a third of the pack's memory traffic.  It copies the whole 64-byte pitch
+// from the source row (the tail bytes are never looked at) where that stays inside the frame's own extent, the row's bytes otherwise.
+template <class FrameAt>
+static int host_frames(melf_ctx* c, const FrameAt& frame_at, const FrameBatch& b, melf_result* out_host)
 {
     Crop cr;
     if (int rc = host_crop(c, b, out_host, &cr)) return rc;
-    const int pix = b.lay.pix, bpp = pix_bytes(pix), crows = cr.rows;
-    const size_t row_pitch = (size_t)b.row_stride, row_bytes = (size_t)cr.cols * bpp, x_off = (size_t)cr.x0 * bpp;
-    // crop rows at a 64-byte pitch, so that the host side can pack them with streaming (non-temporal) 16-byte stores:
-    // a plain memcpy into the staging buffer reads every destination line before writing it, a third of the pack's
-    // memory traffic
-    const size_t pitch = pitch64(row_bytes);
-    const StagePlan sp = {{0, crows, cr.cols, crows * pitch + 128, (int)pitch, FrameLayout::packed(pix, crows * pitch)},
-                          {0, 0, cr.cols, crows}, (crows + 31) / 32};
-    const uint8_t* frames_end = frames_host + (size_t)(b.n - 1) * b.frame_stride + b.lay.extent;
-    const int y0 = cr.y0;
-    return stage_host_frames(c, frames_host, b.n, b.frame_stride, sp, out_host, [=](const uint8_t* frame, uint8_t* staged, int part) {
-        const int r0 = part * 32, r1 = r0 + 32 < crows ? r0 + 32 : crows;
-        const uint8_t* src = frame + (size_t)(y0 + r0) * row_pitch + x_off;
-        uint8_t* dst = staged + (size_t)r0 * pitch;
-        for (int y = r0; y < r1; ++y, src += row_pitch, dst += pitch) {
-            if (src + pitch <= frames_end) {  // whole 64-byte pitch from the source row (the tail bytes are never looked at)
-                for (size_t o = 0; o < pitch; o += 16)
-                    _mm_stream_si128((__m128i*)(dst + o), _mm_loadu_si128((const __m128i*)(src + o)));
-            } else {
-                memcpy(dst, src, row_bytes);
-            }
-        }
-        _mm_sfence();
-    });
-}
-
-// YUV 4:2:0: the staged frame is a small frame of the same format, the Y rows of the crop with its origin rounded down (and its
-// far corner up) to even and the chroma rows under them; the kernels read it with the rectangle shifted by the rounding (0 or 1
-// pixel each way), under the caller's matrix.  Work items: the Y rows in blocks of 32, and the chroma rows as one more.
-static int host_yuv(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host)
-{
-    Crop cr;
-    if (int rc = host_crop(c, b, out_host, &cr)) return rc;
-    const bool nv12 = b.lay.pix == PIX_NV12;
-    const YuvPlanes src_planes = b.lay.yuv;
-    const size_t y_pitch = (size_t)b.row_stride;
-    const int ex0 = cr.x0 & ~1, ey0 = cr.y0 & ~1;
-    const int sw = ((cr.x1 + 1) & ~1) - ex0, sh = ((cr.y1 + 1) & ~1) - ey0;   // the small frame (even, inside the frame: H and W are even)
-    const size_t ypitch = pitch64((size_t)sw);
-    const size_t cbytes = nv12 ? (size_t)sw : (size_t)sw / 2;            // bytes of a chroma row
-    const size_t cpitch = pitch64(cbytes);
-    YuvPlanes sy;
-    sy.u_off = (int64_t)((size_t)sh * ypitch);
-    sy.v_off = nv12 ? sy.u_off + 1 : sy.u_off + (int64_t)((size_t)(sh / 2) * cpitch);
-    sy.c_pitch = (int)cpitch; sy.pad = 0;
-    const size_t crop_stride = (size_t)sh * ypitch + (size_t)(sh / 2) * cpitch * (nv12 ? 1 : 2) + 128;
-    const int rblocks = (sh + 31) / 32;
-    const StagePlan sp = {{0, sh, sw, crop_stride, (int)ypitch, FrameLayout::yuv420(b.lay.pix, sy, *b.lay.mx, crop_stride)},
-                          {cr.x0 - ex0, cr.y0 - ey0, cr.x0 - ex0 + cr.cols, cr.y0 - ey0 + cr.rows}, rblocks + 1};
-    return stage_host_frames(c, frames_host, b.n, b.frame_stride, sp, out_host, [=](const uint8_t* frame, uint8_t* small, int part) {
-        if (part < rblocks) {
-            const int r0 = part * 32, r1 = r0 + 32 < sh ? r0 + 32 : sh;
-            for (int y = r0; y < r1; ++y) memcpy(small + (size_t)y * ypitch, frame + (size_t)(ey0 + y) * y_pitch + ex0, (size_t)sw);
-        } else {
-            const size_t cx = nv12 ? (size_t)ex0 : (size_t)ex0 / 2;
-            for (int y = 0; y < sh / 2; ++y) {
-                const size_t so = (size_t)(ey0 / 2 + y) * (size_t)src_planes.c_pitch + cx;
-                memcpy(small + (size_t)sy.u_off + (size_t)y * cpitch, frame + (size_t)src_planes.u_off + so, cbytes);
-                if (!nv12) memcpy(small + (size_t)sy.v_off + (size_t)y * cpitch, frame + (size_t)src_planes.v_off + so, cbytes);
-            }
-        }
-    });
-}
-
-// Packed YUV 4:2:2: the staged frame is a small frame of the same format, the rows of the crop (no vertical rounding: every row
-// has its own chroma), its x origin rounded down and its far corner up to even, i.e. to whole macropixels; the kernels read it
-// with the rectangle shifted by the rounding (0 or 1 pixel), under the caller's matrix.  Work items: the rows in blocks of 32.
-static int host_p422(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host)
-{
-    Crop cr;
-    if (int rc = host_crop(c, b, out_host, &cr)) return rc;
-    const int crows = cr.rows, y0 = cr.y0, ex0 = cr.x0 & ~1;
-    const int sw = ((cr.x1 + 1) & ~1) - ex0;   // the small frame's width (even, inside the frame: W is even)
-    const size_t row_pitch = (size_t)b.row_stride, rbytes = (size_t)sw * 2;
-    const size_t pitch = pitch64(rbytes);
-    const StagePlan sp = {{0, crows, sw, crows * pitch + 128, (int)pitch, FrameLayout::yuv422(b.lay.pix, *b.lay.mx, crows * pitch)},
-                          {cr.x0 - ex0, 0, cr.x0 - ex0 + cr.cols, crows}, (crows + 31) / 32};
-    return stage_host_frames(c, frames_host, b.n, b.frame_stride, sp, out_host, [=](const uint8_t* frame, uint8_t* small, int part) {
-        const int r0 = part * 32, r1 = r0 + 32 < crows ? r0 + 32 : crows;
-        for (int y = r0; y < r1; ++y) memcpy(small + (size_t)y * pitch, frame + (size_t)(y0 + y) * row_pitch + (size_t)ex0 * 2, rbytes);
-    });
-}
-
-// Packed 10-bit YUV 4:2:2 (v210, Y210): as host_p422, the staged frame a small frame of the same format, its x origin rounded down
-// and its far corner up to whole groups of 6 pixels (v210: rows hold whole groups, so the far corner stays inside the row) or whole
-// macropixels (Y210); the rows are copied as they are, no sample is unpacked on the CPU.  Work items: the rows in blocks of 32.
-static int host_yuv422_10(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host)
-{
-    Crop cr;
-    if (int rc = host_crop(c, b, out_host, &cr)) return rc;
-    const bool v210 = b.lay.pix == PIX_V210;
-    const int unit = v210 ? 6 : 2;
-    const int crows = cr.rows, y0 = cr.y0, ex0 = cr.x0 / unit * unit;
-    const int sw = (cr.x1 + unit - 1) / unit * unit - ex0;   // the small frame's width: whole groups / macropixels
-    const size_t row_pitch = (size_t)b.row_stride;
-    const size_t rbytes = v210 ? (size_t)(sw / 6) * 16 : (size_t)sw * 4, x_off = v210 ? (size_t)(ex0 / 6) * 16 : (size_t)ex0 * 4;
-    const size_t pitch = pitch64(rbytes);
-    const StagePlan sp = {{0, crows, sw, crows * pitch + 128, (int)pitch, FrameLayout::yuv422_10(b.lay.pix, *b.lay.mx, crows * pitch)},
-                          {cr.x0 - ex0, 0, cr.x0 - ex0 + cr.cols, crows}, (crows + 31) / 32};
-    return stage_host_frames(c, frames_host, b.n, b.frame_stride, sp, out_host, [=](const uint8_t* frame, uint8_t* small, int part) {
-        const int r0 = part * 32, r1 = r0 + 32 < crows ? r0 + 32 : crows;
-        for (int y = r0; y < r1; ++y) memcpy(small + (size_t)y * pitch, frame + (size_t)(y0 + y) * row_pitch + x_off, rbytes);
-    });
-}
-
-// 32-bit packed 4:4:4 (AYUV, Y410, X2RGB10 ..): the staged frame is the crop, its rows of words copied as they are at a 64-byte pitch
-// (4-byte aligned like the caller's), read under the same positions and matrix; no word is unpacked on the CPU.  Work items: the
-// rows in blocks of 32.
-static int host_packed32(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host)
-{
-    Crop cr;
-    if (int rc = host_crop(c, b, out_host, &cr)) return rc;
-    const int crows = cr.rows, y0 = cr.y0;
-    const size_t row_pitch = (size_t)b.row_stride, rbytes = (size_t)cr.cols * 4, x_off = (size_t)cr.x0 * 4;
-    const size_t pitch = pitch64(rbytes);
-    const StagePlan sp = {{0, crows, cr.cols, crows * pitch + 128, (int)pitch, FrameLayout::packed32(b.lay.pix, b.lay.p32, b.lay.mx, crows * pitch)},
-                          {0, 0, cr.cols, crows}, (crows + 31) / 32};
-    return stage_host_frames(c, frames_host, b.n, b.frame_stride, sp, out_host, [=](const uint8_t* frame, uint8_t* small, int part) {
-        const int r0 = part * 32, r1 = r0 + 32 < crows ? r0 + 32 : crows;
-        for (int y = r0; y < r1; ++y) memcpy(small + (size_t)y * pitch, frame + (size_t)(y0 + y) * row_pitch + x_off, rbytes);
-    });
-}
-
-// Planar / semi-planar YUV of any subsampling and sample size: the staged frame is a small frame of the same layout -- the same
-// subsampling, sample step and order of U and V, and for 16-bit samples the same shift, the samples copied as they are (nothing is
-// reduced on the CPU) --, the Y rows of the crop with its origin rounded down (and its far corner up) to whole chroma blocks
-// (1 << sub_x by 1 << sub_y) and the chroma rows under them; the kernels read it with the rectangle shifted by the rounding (0 or 1
-// pixel each way), under the caller's matrix.  Work items: the Y rows in blocks of 32, and the chroma rows as one more.
-// bps: bytes per sample; step: samples from one sample of a chroma plane to the next; u_off, v_off, c_pitch: the source's, in
-// bytes; layout(u_off, v_off, c_pitch, frame_stride): the small frame's FrameLayout, the source's with these four replaced.
-template <class MakeLayout>
-static int host_yuv_planes(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host, int bps, int sx, int sy,
-                           int step, int64_t u_off, int64_t v_off, int c_pitch, MakeLayout layout)
-{
-    Crop cr;
-    if (int rc = host_crop(c, b, out_host, &cr)) return rc;
-    const bool semi = step == 2;
-    const size_t y_pitch = (size_t)b.row_stride;
-    const int bx = 1 << sx, by = 1 << sy;
-    const int ex0 = cr.x0 & ~(bx - 1), ey0 = cr.y0 & ~(by - 1);
-    // the small frame (whole blocks, inside the frame: W and H are whole blocks)
-    const int sw = ((cr.x1 + bx - 1) & ~(bx - 1)) - ex0, sh = ((cr.y1 + by - 1) & ~(by - 1)) - ey0;
-    const int crows = sh >> sy;                                      // chroma rows of the small frame
-    const size_t ybytes = (size_t)sw * (size_t)bps, ypitch = pitch64(ybytes);
-    const size_t cbytes = (size_t)(sw >> sx) * (size_t)step * (size_t)bps;   // bytes of a chroma row (semi-planar: of both)
-    const size_t cpitch = pitch64(cbytes);
-    const size_t c0 = (size_t)sh * ypitch;                           // the first chroma byte of the small frame
-    const int64_t src_lo = u_off < v_off ? u_off : v_off;
-    const int64_t su_off = semi ? (int64_t)c0 + (u_off - src_lo) : (int64_t)c0;
-    const int64_t sv_off = semi ? (int64_t)c0 + (v_off - src_lo) : (int64_t)(c0 + (size_t)crows * cpitch);
-    const size_t crop_stride = c0 + (size_t)crows * cpitch * (semi ? 1 : 2) + 128;
-    const int rblocks = (sh + 31) / 32;
-    const StagePlan sp = {{0, sh, sw, crop_stride, (int)ypitch, layout(su_off, sv_off, (int)cpitch, crop_stride)},
-                          {cr.x0 - ex0, cr.y0 - ey0, cr.x0 - ex0 + cr.cols, cr.y0 - ey0 + cr.rows}, rblocks + 1};
-    return stage_host_frames(c, frames_host, b.n, b.frame_stride, sp, out_host, [=](const uint8_t* frame, uint8_t* small, int part) {
-        if (part < rblocks) {
-            const int r0 = part * 32, r1 = r0 + 32 < sh ? r0 + 32 : sh;
-            for (int y = r0; y < r1; ++y)
-                memcpy(small + (size_t)y * ypitch, frame + (size_t)(ey0 + y) * y_pitch + (size_t)ex0 * (size_t)bps, ybytes);
-        } else {
-            const size_t cx = (size_t)(ex0 >> sx) * (size_t)step * (size_t)bps;
-            for (int y = 0; y < crows; ++y) {
-                const size_t so = (size_t)((ey0 >> sy) + y) * (size_t)c_pitch + cx;
-                if (semi) {
-                    memcpy(small + c0 + (size_t)y * cpitch, frame + (size_t)src_lo + so, cbytes);
+    const StagePlan sp = stage_plan(b, cr);
+    if (b.lay.pix >= MELF_PIX_BGR && b.lay.pix <= MELF_PIX_RGBA) {
+        const RowRun run = sp.runs.run[0];
+        const size_t extent = b.lay.extent, row_pitch = run.src_pitch, pitch = run.dst_pitch, row_bytes = run.row_bytes;
+        const int crows = (int)run.rows;
+        return stage_host_frames(c, frame_at, b.n, sp, out_host, [=](const uint8_t* frame, uint8_t* staged, int part) {
+            const int r0 = part * 32, r1 = r0 + 32 < crows ? r0 + 32 : crows;
+            const uint8_t* frame_end = frame + extent;
+            const uint8_t* src = frame + (size_t)run.src_off + (size_t)r0 * row_pitch;
+            uint8_t* dst = staged + (size_t)r0 * pitch;
+            for (int y = r0; y < r1; ++y, src += row_pitch, dst += pitch) {
+                if (src + pitch <= frame_end) {
+                    for (size_t o = 0; o < pitch; o += 16)
+                        _mm_stream_si128((__m128i*)(dst + o), _mm_loadu_si128((const __m128i*)(src + o)));
                 } else {
-                    memcpy(small + (size_t)su_off + (size_t)y * cpitch, frame + (size_t)u_off + so, cbytes);
-                    memcpy(small + (size_t)sv_off + (size_t)y * cpitch, frame + (size_t)v_off + so, cbytes);
+                    memcpy(dst, src, row_bytes);
                 }
             }
+            _mm_sfence();
+        });
+    }
+    return stage_host_frames(c, frame_at, b.n, sp, out_host, [=](const uint8_t* frame, uint8_t* staged, int item) {
+        int k0, k1;
+        uint32_t r0, r1;
+        stage_item(sp, item, &k0, &k1, &r0, &r1);
+        for (int k = k0; k < k1; ++k) {
+            const RowRun& run = sp.runs.run[k];
+            for (uint32_t y = r0; y < r1; ++y)
+                memcpy(staged + (size_t)run.dst_off + (size_t)y * run.dst_pitch, frame + (size_t)run.src_off + (size_t)y * run.src_pitch, run.row_bytes);
         }
     });
 }
-
-static int host_yuv_planar(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host)
+// a batch: frame i at frames_host + i * frame_stride
+static int host_batch(melf_ctx* c, const void* frames_host, const FrameBatch& b, melf_result* out_host)
 {
-    const YuvPlanarPlanes src = b.lay.yuvp;
-    const YuvMatrix* mx = b.lay.mx;
-    return host_yuv_planes(c, frames_host, b, out_host, 1, src.sub_x, src.sub_y, src.c_step, src.u_off, src.v_off, src.c_pitch,
-                           [=](int64_t u_off, int64_t v_off, int c_pitch, size_t stride) {
-                               YuvPlanarPlanes p = src;
-                               p.u_off = u_off; p.v_off = v_off; p.c_pitch = c_pitch;
-                               return FrameLayout::yuv_planar(p, *mx, stride);
-                           });
-}
-
-// 16-bit samples: sub_x is 1, the sample 2 bytes.
-static int host_yuv16(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host)
-{
-    const Yuv16Planes src = b.lay.y16;
-    const YuvMatrix* mx = b.lay.mx;
-    return host_yuv_planes(c, frames_host, b, out_host, 2, 1, src.sub_y, src.c_step, src.u_off, src.v_off, src.c_pitch,
-                           [=](int64_t u_off, int64_t v_off, int c_pitch, size_t stride) {
-                               Yuv16Planes p = src;
-                               p.u_off = u_off; p.v_off = v_off; p.c_pitch = c_pitch;
-                               return FrameLayout::yuv16(p, *mx, stride);
-                           });
-}
-
-// Planar: the staged frame is a small planar frame, the crop's rows of the B, the G and the R plane, one plane after the other,
-// which the kernels read with the rectangle at its origin.  Work items: the crop's rows of one plane in blocks of 32.
-static int host_planes(melf_ctx* c, const uint8_t* frames_host, const FrameBatch& b, melf_result* out_host)
-{
-    Crop cr;
-    if (int rc = host_crop(c, b, out_host, &cr)) return rc;
-    const int crows = cr.rows, ccols = cr.cols, x0 = cr.x0, y0 = cr.y0;
-    const size_t row_pitch = (size_t)b.row_stride, pitch = pitch64((size_t)ccols), plane = (size_t)crows * pitch;
-    const size_t crop_stride = 3 * plane + 128;
-    const PlanarPlanes in_frame = {0, (int64_t)plane, (int64_t)(2 * plane)};
-    const int rblocks = (crows + 31) / 32;
-    const StagePlan sp = {{0, crows, ccols, crop_stride, (int)pitch, FrameLayout::planar(in_frame, crop_stride)}, {0, 0, ccols, crows}, 3 * rblocks};
-    const int64_t src_off[3] = {b.lay.planes.b_off, b.lay.planes.g_off, b.lay.planes.r_off};
-    return stage_host_frames(c, frames_host, b.n, b.frame_stride, sp, out_host, [=](const uint8_t* frame, uint8_t* small, int item) {
-        const int p = item / rblocks, part = item - p * rblocks;
-        const uint8_t* src = frame + (size_t)src_off[p] + (size_t)x0;
-        uint8_t* dst = small + (size_t)p * plane;
-        const int r0 = part * 32, r1 = r0 + 32 < crows ? r0 + 32 : crows;
-        for (int y = r0; y < r1; ++y) memcpy(dst + (size_t)y * pitch, src + (size_t)(y0 + y) * row_pitch, (size_t)ccols);
-    });
+    return host_frames(c, Strided{(const uint8_t*)frames_host, b.frame_stride}, b, out_host);
 }
 
 extern "C" int melf_process_batch(melf_ctx* c, const uint8_t* frames_host, int n, int H, int W, size_t frame_stride,
@@ -1696,7 +1523,7 @@ extern "C" int melf_process_batch(melf_ctx* c, const uint8_t* frames_host, int n
     if (n == 0) return MELF_SUCCESS;
     if (!frames_host || !out_host || n < 0 || H <= 0 || W <= 0) return fail(MELF_ERR_INVALID, "bad argument");
     if (frame_stride < (size_t)H * W * 3) return fail(MELF_ERR_INVALID, "frame_stride smaller than a frame");
-    return host_packed(c, frames_host, bgr_batch(n, H, W, frame_stride), out_host);
+    return host_batch(c, frames_host, bgr_batch(n, H, W, frame_stride), out_host);
 }
 
 extern "C" int melf_process_frames(melf_ctx* c, const void* frames_host, const melf_frames* f, melf_result* out_host)
@@ -1704,7 +1531,7 @@ extern "C" int melf_process_frames(melf_ctx* c, const void* frames_host, const m
     FrameBatch b;
     if (int rc = checked(c, check_frames(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
-    return host_packed(c, (const uint8_t*)frames_host, b, out_host);
+    return host_batch(c, frames_host, b, out_host);
 }
 
 extern "C" int melf_process_yuv(melf_ctx* c, const void* frames_host, const melf_yuv_frames* f, melf_result* out_host)
@@ -1712,7 +1539,7 @@ extern "C" int melf_process_yuv(melf_ctx* c, const void* frames_host, const melf
     FrameBatch b;
     if (int rc = checked(c, check_yuv(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
-    return host_yuv(c, (const uint8_t*)frames_host, b, out_host);
+    return host_batch(c, frames_host, b, out_host);
 }
 
 extern "C" int melf_process_yuv422(melf_ctx* c, const void* frames_host, const melf_yuv422_frames* f, melf_result* out_host)
@@ -1720,7 +1547,7 @@ extern "C" int melf_process_yuv422(melf_ctx* c, const void* frames_host, const m
     FrameBatch b;
     if (int rc = checked(c, check_yuv422(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
-    return host_p422(c, (const uint8_t*)frames_host, b, out_host);
+    return host_batch(c, frames_host, b, out_host);
 }
 
 extern "C" int melf_process_yuv_planar(melf_ctx* c, const void* frames_host, const melf_yuv_planar_frames* f, melf_result* out_host)
@@ -1728,7 +1555,7 @@ extern "C" int melf_process_yuv_planar(melf_ctx* c, const void* frames_host, con
     FrameBatch b;
     if (int rc = checked(c, check_yuv_planar(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
-    return host_yuv_planar(c, (const uint8_t*)frames_host, b, out_host);
+    return host_batch(c, frames_host, b, out_host);
 }
 
 extern "C" int melf_process_yuv16(melf_ctx* c, const void* frames_host, const melf_yuv16_frames* f, melf_result* out_host)
@@ -1736,7 +1563,7 @@ extern "C" int melf_process_yuv16(melf_ctx* c, const void* frames_host, const me
     FrameBatch b;
     if (int rc = checked(c, check_yuv16(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
-    return host_yuv16(c, (const uint8_t*)frames_host, b, out_host);
+    return host_batch(c, frames_host, b, out_host);
 }
 
 extern "C" int melf_process_yuv422_10(melf_ctx* c, const void* frames_host, const melf_yuv422_10_frames* f, melf_result* out_host)
@@ -1744,7 +1571,7 @@ extern "C" int melf_process_yuv422_10(melf_ctx* c, const void* frames_host, cons
     FrameBatch b;
     if (int rc = checked(c, check_yuv422_10(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
-    return host_yuv422_10(c, (const uint8_t*)frames_host, b, out_host);
+    return host_batch(c, frames_host, b, out_host);
 }
 
 extern "C" int melf_process_packed32(melf_ctx* c, const void* frames_host, const melf_packed32_frames* f, melf_result* out_host)
@@ -1752,7 +1579,7 @@ extern "C" int melf_process_packed32(melf_ctx* c, const void* frames_host, const
     FrameBatch b;
     if (int rc = checked(c, check_packed32(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
-    return host_packed32(c, (const uint8_t*)frames_host, b, out_host);
+    return host_batch(c, frames_host, b, out_host);
 }
 
 extern "C" int melf_process_planes(melf_ctx* c, const void* frames_host, const melf_planar_frames* f, melf_result* out_host)
@@ -1760,8 +1587,164 @@ extern "C" int melf_process_planes(melf_ctx* c, const void* frames_host, const m
     FrameBatch b;
     if (int rc = checked(c, check_planes(frames_host, f, &b))) return rc;
     if (b.n == 0) return MELF_SUCCESS;
-    return host_planes(c, (const uint8_t*)frames_host, b, out_host);
+    return host_batch(c, frames_host, b, out_host);
 }
+
+// ------------------------------------------------------------ frame lists ----
+// Frames in separate allocations: a host array of n frame pointers beside the family's descriptor (n: the length of the list;
+// frame_stride is not looked at).  The device call gathers the crop's rows of every frame into a staged batch in HBM (k_gather_rows,
+// the device-side twin of stage_host_frames' packers: the same plan, the same row runs) and runs the unchanged reading path on it;
+// the host call is stage_host_frames with the i-th pointer as frame i.
+
+// The family's check on a list.  The descriptor as a one-frame batch, with a frame_stride that every check takes (a multiple of 16
+// no extent reaches), against a pointer that breaks no rule; then every pointer of the list for the check's NULL and alignment
+// rules, the message led by the frame's index.  *b: the one-frame batch with n the list's length (frame_stride means nothing).
+template <class Desc>
+static int check_list(const void* desc, const void* const* frames, const char* (*check)(const void*, const Desc*, FrameBatch*), FrameBatch* b)
+{
+    if (!desc) return fail(MELF_ERR_INVALID, check(nullptr, nullptr, b));
+    Desc one = *(const Desc*)desc;
+    const int n = one.n;
+    one.n = n > 0 ? 1 : n;
+    one.frame_stride = INT64_MAX & ~(int64_t)15;
+    if (const char* msg = check((const void*)(uintptr_t)64, &one, b)) return fail(MELF_ERR_INVALID, msg);
+    b->n = n;
+    if (n == 0) return MELF_SUCCESS;
+    if (!frames) return fail(MELF_ERR_INVALID, "the list's array of frame pointers is NULL");
+    FrameBatch scratch;
+    for (int i = 0; i < n; ++i)
+        if (const char* msg = check(frames[i], &one, &scratch)) return fail(MELF_ERR_INVALID, "frame " + std::to_string(i) + " of the list: " + msg);
+    return MELF_SUCCESS;
+}
+
+static int list_batch(const melf_ctx* c, int family, const void* desc, const void* const* frames, FrameBatch* b)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    switch (family) {
+    case MELF_LIST_FRAMES: return check_list<melf_frames>(desc, frames, check_frames, b);
+    case MELF_LIST_YUV: return check_list<melf_yuv_frames>(desc, frames, check_yuv, b);
+    case MELF_LIST_YUV422: return check_list<melf_yuv422_frames>(desc, frames, check_yuv422, b);
+    case MELF_LIST_YUV_PLANAR: return check_list<melf_yuv_planar_frames>(desc, frames, check_yuv_planar, b);
+    case MELF_LIST_YUV16: return check_list<melf_yuv16_frames>(desc, frames, check_yuv16, b);
+    case MELF_LIST_YUV422_10: return check_list<melf_yuv422_10_frames>(desc, frames, check_yuv422_10, b);
+    case MELF_LIST_PACKED32: return check_list<melf_packed32_frames>(desc, frames, check_packed32, b);
+    case MELF_LIST_PLANES: return check_list<melf_planar_frames>(desc, frames, check_planes, b);
+    default: return fail(MELF_ERR_INVALID, "unknown family of the frame list (accepted: MELF_LIST_FRAMES .. MELF_LIST_PLANES, 0 .. 7)");
+    }
+}
+
+// Frames of a list per gather launch and staged batch: a lane's staging buffer holds at most this many staged frames (1024 crops of
+// a 640 x 480 BGR frame: 197 MB), longer lists go through it chunk after chunk.  A multiple of the 32-frame match group.
+static const int LIST_CHUNK = 1024;
+
+// read: the reading path on the staged batch (melf_process_frame_list_dev); otherwise the gather alone (the diagnostic build's
+// melf_gather_frame_list_dev), *bytes_moved: what its kernels read and wrote
+static int frame_list_dev(melf_ctx* c, const FrameBatch& b, const void* const* d_frames, void* d_results, melf_result* out_host, void* stream_,
+                          bool read, size_t* bytes_moved)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    Crop cr;
+    if (int rc = meter_crop(c->P, nullptr, b.H, b.W, &cr)) return rc;
+    const StagePlan sp = stage_plan(b, cr);
+    const int n = b.n;
+    hipStream_t st = (hipStream_t)stream_;  // NULL = the null (legacy default) stream, as everywhere in HIP
+    melf_result* res_dev = (melf_result*)d_results;
+    if (read && !res_dev) {
+        if (int rc = grow(&c->d_results, &c->results_cap, (size_t)n)) return rc;
+        res_dev = c->d_results;
+    }
+    // The lane, as batch_dev picks it.  Resident mode promises nothing about the frames of a list -- a decoder may still be writing
+    // them --, so there the call runs on the lane's own stream, beside the other lane's kernels, but its gather (and with it
+    // everything behind it) waits for what the caller's stream held at the call; only the pointer table goes up before that.
+    const bool resident = c->frames_resident;
+    int lane = 0;
+    hipStream_t ws = st;
+    if (resident) {
+        lane = c->resident_next_lane;
+        c->resident_next_lane = (lane + 1) % melf_ctx::NLANES;
+        ws = c->lane_stream[lane];
+        if (int rc = claim_lane(c, lane, ws)) return rc;
+    } else if (int rc = acquire_lane(c, st, &lane)) {
+        return rc;
+    }
+    c->active_lane = lane;
+    // the lane's staged batch and pointer table (never the context's d_crops: two caller streams' calls run on two lanes at once)
+    const size_t stride = sp.staged.frame_stride;
+    const size_t cap = (size_t)(n < LIST_CHUNK ? n : LIST_CHUNK);
+    if (int rc = grow(&c->d_list_stage[lane], &c->list_stage_cap[lane], cap * stride)) return rc;
+    if (int rc = grow(&c->d_list_tab[lane], &c->list_tab_cap[lane], cap)) return rc;
+    if (!c->ev_list_tab[lane]) HIP_TRY(hipEventCreateWithFlags(&c->ev_list_tab[lane], hipEventDisableTiming));
+    if (c->h_list_tab_cap[lane] < cap) {
+        if (c->h_list_tab[lane]) { HIP_TRY(hipEventSynchronize(c->ev_list_tab[lane])); HIP_TRY(hipHostFree(c->h_list_tab[lane])); }
+        c->h_list_tab[lane] = nullptr;
+        c->h_list_tab_cap[lane] = 0;
+        HIP_TRY(hipHostMalloc((void**)&c->h_list_tab[lane], cap * sizeof(void*), hipHostMallocDefault));
+        c->h_list_tab_cap[lane] = cap;
+    }
+    FrameBatch staged = sp.staged;
+    for (int f0 = 0; f0 < n; f0 += LIST_CHUNK) {
+        const int m = n - f0 < LIST_CHUNK ? n - f0 : LIST_CHUNK;
+        HIP_TRY(hipEventSynchronize(c->ev_list_tab[lane]));   // the previous upload from the pinned table has finished
+        memcpy(c->h_list_tab[lane], d_frames + f0, (size_t)m * sizeof(void*));
+        HIP_TRY(hipMemcpyAsync(c->d_list_tab[lane], c->h_list_tab[lane], (size_t)m * sizeof(void*), hipMemcpyHostToDevice, ws));
+        HIP_TRY(hipEventRecord(c->ev_list_tab[lane], ws));
+        if (resident && f0 == 0) {
+            if (!c->ev_call[lane]) HIP_TRY(hipEventCreateWithFlags(&c->ev_call[lane], hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(c->ev_call[lane], st));
+            HIP_TRY(hipStreamWaitEvent(ws, c->ev_call[lane], 0));
+        }
+        {
+            KernelTimer t(c, MELF_K_GATHER, ws);
+            launch_gather_rows(c->d_list_tab[lane], m, sp.runs, c->d_list_stage[lane], stride, b.lay.extent, ws);
+        }
+        HIP_TRY(hipGetLastError());
+        if (!read) continue;
+        staged.n = m;
+        if (int rc = process_batch_on(c, c->d_list_stage[lane], staged, res_dev + f0, nullptr, ws, sp.rect)) return rc;
+    }
+    if (bytes_moved) {
+        size_t per_frame = 0;
+        for (int k = 0; k < sp.runs.count; ++k) per_frame += (size_t)sp.runs.run[k].rows * sp.runs.run[k].row_bytes;
+        *bytes_moved = 2 * per_frame * (size_t)n;
+    }
+    if (resident) {
+        HIP_TRY(hipEventRecord(c->ev_join[lane], ws));
+        HIP_TRY(hipStreamWaitEvent(st, c->ev_join[lane], 0));   // what the caller enqueues next sees the records
+    }
+    if (read && out_host) {
+        HIP_TRY(hipMemcpyAsync(out_host, res_dev, (size_t)n * sizeof(melf_result), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_process_frame_list_dev(melf_ctx* c, int family, const void* desc, const void* const* d_frames, void* d_results,
+                                           melf_result* out_host, void* stream_)
+{
+    FrameBatch b;
+    if (int rc = list_batch(c, family, desc, d_frames, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return frame_list_dev(c, b, d_frames, d_results, out_host, stream_, true, nullptr);
+}
+
+extern "C" int melf_process_frame_list(melf_ctx* c, int family, const void* desc, const void* const* frames_host, melf_result* out_host)
+{
+    FrameBatch b;
+    if (int rc = list_batch(c, family, desc, frames_host, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    return host_frames(c, Listed{frames_host}, b, out_host);
+}
+
+#ifdef MELF_DIAG   // measurement aid of the diagnostic build (tools/frame_list_rate.py): not an entry point of the product library
+extern "C" int melf_gather_frame_list_dev(melf_ctx* c, int family, const void* desc, const void* const* d_frames, void* stream_, size_t* bytes_moved)
+{
+    FrameBatch b;
+    if (int rc = list_batch(c, family, desc, d_frames, &b)) return rc;
+    if (bytes_moved) *bytes_moved = 0;
+    if (b.n == 0) return MELF_SUCCESS;
+    return frame_list_dev(c, b, d_frames, nullptr, nullptr, stream_, false, bytes_moved);
+}
+#endif
 
 // ---------------------------------------------------------- stage entries ----
 // melf_yuv_to_bgr / melf_yuv422_to_bgr / melf_yuv_planar_to_bgr / melf_yuv16_to_bgr / melf_yuv422_10_to_bgr / melf_packed32_to_bgr after their checks: the frames up, the conversion kernel alone, n packed H x W BGR frames down

@@ -193,6 +193,13 @@ void launch_p32_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int r
 void launch_p422_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int row_pitch, size_t frame_stride, const YuvMatrix& mx,
                         uint8_t* d_dst, hipStream_t stream);
 
+// ---- k_gather.hip: frames in separate allocations (melf_process_frame_list_dev) ----
+// Copies the row runs of a staging plan (melf_stage_plan.h: RowRuns) from each of the n frames d_frames[i] -- a DEVICE array of n
+// device pointers, `extent` bytes readable from each -- into the staged frame d_staged + i * staged_stride.  n <= 65535.
+struct RowRuns;
+void launch_gather_rows(const void* const* d_frames, int n, const RowRuns& runs, uint8_t* d_staged, size_t staged_stride, size_t extent,
+                        hipStream_t stream);
+
 // ---- calibration stage kernels ------------------------------------------------
 void launch_aligned_average(const uint8_t* d_frames, int n, size_t frame_stride, int row_stride, int x0, int y0, int rows,
                             int cols, const int32_t* d_mx, const int32_t* d_my, int ax, int ay, uint8_t* d_out,

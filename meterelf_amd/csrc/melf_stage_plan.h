@@ -1,0 +1,233 @@
+// The staging plans of the eight frame families: what the small staged frame of a format looks like -- the meter crop's rows, copied
+// as they are, its origin rounded to whole chroma blocks, macropixels or v210 groups where the format needs it -- and the row runs
+// that copy a caller's frame into it.  Pure host functions of a checked FrameBatch (melf_frame_checks.h) and the crop: no HIP, no
+// context.  Two users, one statement of a format's staged frame: the host-fed path (melf_api.hip: stage_host_frames packs the runs
+// on the CPU into pinned memory) and the frame lists (melf_process_frame_list*: k_gather_rows copies the runs of separately
+// allocated device frames into a staged batch in HBM).  The kernels then read the staged frames as frames of their own, with the
+// rectangle where the plan says.  tests/stage_runs_main.cpp sweeps the plans on the CPU.
+#pragma once
+#include "melf_frame_checks.h"
+
+namespace melf {
+
+// The meter crop of H x W frames: {x0, y0, x1, y1} clamped to the frame as numpy slicing img[y0:y1, x0:x1] clamps
+// (meterelf/_image.py:54-55)
+struct Crop {
+    int x0, y0, x1, y1, rows, cols;
+};
+// r = {x0, y0, x1, y1}; false: the clamped crop is empty or starts before the frame (the caller also wants it to hold the template)
+inline bool clamp_crop(const int* r, int H, int W, Crop* cr)
+{
+    cr->x0 = r[0] < W ? r[0] : W; cr->x1 = r[2] < W ? r[2] : W;
+    cr->y0 = r[1] < H ? r[1] : H; cr->y1 = r[3] < H ? r[3] : H;
+    cr->rows = cr->y1 - cr->y0; cr->cols = cr->x1 - cr->x0;
+    return cr->x0 >= 0 && cr->y0 >= 0 && cr->rows > 0 && cr->cols > 0;
+}
+
+// One run of rows: `rows` rows of row_bytes bytes, from frame + src_off + r * src_pitch to staged + dst_off + r * dst_pitch.  A
+// plane of the frame is one run (Y / U / V, Y / UV, B / G / R, or the one packed plane).  dst_off and dst_pitch are multiples of 64;
+// src_off and src_pitch have the alignment the family's check leaves the frame's base and pitches.  Every run reads from the one
+// frame pointer (a frame's planes in separate allocations would give each run a pointer slot of its own: not built).
+struct RowRun {
+    uint64_t src_off, dst_off;
+    uint32_t src_pitch, dst_pitch;
+    uint32_t row_bytes, rows;
+};
+constexpr int STAGE_MAX_RUNS = 3;
+struct RowRuns {
+    RowRun run[STAGE_MAX_RUNS];
+    int count;
+};
+
+struct StagePlan {
+    FrameBatch staged;   // the staged frames as the kernels read them (n: set per chunk); frame_stride: bytes of a staged frame,
+                         // rows at a 64-byte pitch, + 128 spare bytes (the prep kernel's aligned windows reach past the last sample)
+    int rect[4];         // the meter crop inside a staged frame
+    int items;           // the host packer's work items per frame: blocks of 32 rows (see stage_item)
+    RowRuns runs;        // the rows of the caller's frame that make a staged frame
+};
+
+inline size_t pitch64(size_t row_bytes) { return (row_bytes + 63) & ~(size_t)63; }
+inline RowRun row_run(size_t src_off, size_t src_pitch, size_t dst_off, size_t dst_pitch, size_t row_bytes, int rows)
+{
+    return RowRun{(uint64_t)src_off, (uint64_t)dst_off, (uint32_t)src_pitch, (uint32_t)dst_pitch, (uint32_t)row_bytes, (uint32_t)rows};
+}
+
+// One packed plane (the pixel layouts of melf_frames, packed 4:2:2, packed 10-bit 4:2:2, 32-bit packed 4:4:4): the staged frame is
+// the crop's rows from pixel ex0 on, sw pixels wide, unit_bytes per unit_px pixels, no vertical rounding.  Work items: the rows in
+// blocks of 32.
+inline StagePlan one_plane_plan(const FrameBatch& b, const Crop& cr, int ex0, int sw, int unit_px, int unit_bytes, const FrameLayout& lay_of_extent0)
+{
+    const int crows = cr.rows;
+    const size_t rbytes = (size_t)(sw / unit_px) * unit_bytes, x_off = (size_t)(ex0 / unit_px) * unit_bytes;
+    const size_t pitch = pitch64(rbytes);
+    FrameLayout lay = lay_of_extent0;
+    lay.extent = crows * pitch;
+    StagePlan sp = {{0, crows, sw, crows * pitch + 128, (int)pitch, lay}, {cr.x0 - ex0, 0, cr.x0 - ex0 + cr.cols, crows}, (crows + 31) / 32, {}};
+    sp.runs.count = 1;
+    sp.runs.run[0] = row_run((size_t)cr.y0 * (size_t)b.row_stride + x_off, (size_t)b.row_stride, 0, pitch, rbytes, crows);
+    return sp;
+}
+
+// The pixel layouts of melf_process_batch / melf_process_frames: the staged frame is the crop, its rows (cols * bytes per pixel, read
+// at the caller's row pitch) packed as they are at a 64-byte pitch
+inline StagePlan packed_plan(const FrameBatch& b, const Crop& cr)
+{
+    return one_plane_plan(b, cr, cr.x0, cr.cols, 1, pix_bytes(b.lay.pix), FrameLayout::packed(b.lay.pix, 0));
+}
+
+// Packed YUV 4:2:2: a small frame of the same format, the rows of the crop (every row has its own chroma), its x origin rounded down
+// and its far corner up to even, i.e. to whole macropixels (inside the frame: W is even); the kernels read it with the rectangle
+// shifted by the rounding (0 or 1 pixel), under the caller's matrix
+inline StagePlan p422_plan(const FrameBatch& b, const Crop& cr)
+{
+    const int ex0 = cr.x0 & ~1;
+    return one_plane_plan(b, cr, ex0, ((cr.x1 + 1) & ~1) - ex0, 2, 4, FrameLayout::yuv422(b.lay.pix, *b.lay.mx, 0));
+}
+
+// Packed 10-bit YUV 4:2:2 (v210, Y210): as p422_plan, the x origin rounded down and the far corner up to whole groups of 6 pixels
+// (v210: rows hold whole groups, so the far corner stays inside the row) or whole macropixels (Y210)
+inline StagePlan yuv422_10_plan(const FrameBatch& b, const Crop& cr)
+{
+    const bool v210 = b.lay.pix == PIX_V210;
+    const int unit = v210 ? 6 : 2;
+    const int ex0 = cr.x0 / unit * unit;
+    return one_plane_plan(b, cr, ex0, (cr.x1 + unit - 1) / unit * unit - ex0, unit, v210 ? 16 : 8, FrameLayout::yuv422_10(b.lay.pix, *b.lay.mx, 0));
+}
+
+// 32-bit packed 4:4:4 (AYUV, Y410, X2RGB10 ..): the staged frame is the crop, its rows of words at a 64-byte pitch (4-byte aligned
+// like the caller's), read under the same positions and matrix
+inline StagePlan packed32_plan(const FrameBatch& b, const Crop& cr)
+{
+    return one_plane_plan(b, cr, cr.x0, cr.cols, 1, 4, FrameLayout::packed32(b.lay.pix, b.lay.p32, b.lay.mx, 0));
+}
+
+// Planar / semi-planar YUV of any subsampling and sample size (4:2:0 of melf_yuv_frames, melf_yuv_planar_frames, melf_yuv16_frames):
+// a small frame of the same layout -- the same subsampling, sample step and order of U and V, and for 16-bit samples the same shift --,
+// the Y rows of the crop with its origin rounded down (and its far corner up) to whole chroma blocks (1 << sub_x by 1 << sub_y; inside
+// the frame: W and H are whole blocks) and the chroma rows under them; the kernels read it with the rectangle shifted by the rounding
+// (0 or 1 pixel each way), under the caller's matrix.  Semi-planar: the interleaved pairs are one run from the lower of the two
+// offsets.  Work items: the Y rows in blocks of 32, and the chroma rows as one more.
+// bps: bytes per sample; step: samples from one sample of a chroma plane to the next; u_off, v_off, c_pitch: the source's, in
+// bytes; layout(u_off, v_off, c_pitch, extent): the small frame's FrameLayout, the source's with these four replaced.
+template <class MakeLayout>
+inline StagePlan yuv_planes_plan(const FrameBatch& b, const Crop& cr, int bps, int sx, int sy, int step, int64_t u_off, int64_t v_off, int c_pitch,
+                                 MakeLayout layout)
+{
+    const bool semi = step == 2;
+    const size_t y_pitch = (size_t)b.row_stride;
+    const int bx = 1 << sx, by = 1 << sy;
+    const int ex0 = cr.x0 & ~(bx - 1), ey0 = cr.y0 & ~(by - 1);
+    const int sw = ((cr.x1 + bx - 1) & ~(bx - 1)) - ex0, sh = ((cr.y1 + by - 1) & ~(by - 1)) - ey0;
+    const int crows = sh >> sy;                                      // chroma rows of the small frame
+    const size_t ybytes = (size_t)sw * (size_t)bps, ypitch = pitch64(ybytes);
+    const size_t cbytes = (size_t)(sw >> sx) * (size_t)step * (size_t)bps;   // bytes of a chroma row (semi-planar: of both)
+    const size_t cpitch = pitch64(cbytes);
+    const size_t c0 = (size_t)sh * ypitch;                           // the first chroma byte of the small frame
+    const int64_t src_lo = u_off < v_off ? u_off : v_off;
+    const int64_t su_off = semi ? (int64_t)c0 + (u_off - src_lo) : (int64_t)c0;
+    const int64_t sv_off = semi ? (int64_t)c0 + (v_off - src_lo) : (int64_t)(c0 + (size_t)crows * cpitch);
+    const size_t crop_stride = c0 + (size_t)crows * cpitch * (semi ? 1 : 2) + 128;
+    StagePlan sp = {{0, sh, sw, crop_stride, (int)ypitch, layout(su_off, sv_off, (int)cpitch, crop_stride)},
+                    {cr.x0 - ex0, cr.y0 - ey0, cr.x0 - ex0 + cr.cols, cr.y0 - ey0 + cr.rows}, (sh + 31) / 32 + 1, {}};
+    const size_t cx = (size_t)(ex0 >> sx) * (size_t)step * (size_t)bps;
+    const size_t crow0 = (size_t)(ey0 >> sy) * (size_t)c_pitch + cx;
+    sp.runs.run[0] = row_run((size_t)ey0 * y_pitch + (size_t)ex0 * (size_t)bps, y_pitch, 0, ypitch, ybytes, sh);
+    if (semi) {
+        sp.runs.count = 2;
+        sp.runs.run[1] = row_run((size_t)src_lo + crow0, (size_t)c_pitch, c0, cpitch, cbytes, crows);
+    } else {
+        sp.runs.count = 3;
+        sp.runs.run[1] = row_run((size_t)u_off + crow0, (size_t)c_pitch, (size_t)su_off, cpitch, cbytes, crows);
+        sp.runs.run[2] = row_run((size_t)v_off + crow0, (size_t)c_pitch, (size_t)sv_off, cpitch, cbytes, crows);
+    }
+    return sp;
+}
+
+// YUV 4:2:0 of melf_yuv_frames (NV12: v_off == u_off + 1; I420 / YV12: two planes)
+inline StagePlan yuv420_plan(const FrameBatch& b, const Crop& cr)
+{
+    const int pix = b.lay.pix;
+    const YuvMatrix* mx = b.lay.mx;
+    const YuvPlanes src = b.lay.yuv;
+    return yuv_planes_plan(b, cr, 1, 1, 1, pix == PIX_NV12 ? 2 : 1, src.u_off, src.v_off, src.c_pitch,
+                           [=](int64_t u_off, int64_t v_off, int c_pitch, size_t stride) {
+                               const YuvPlanes p = {u_off, v_off, c_pitch, 0};
+                               return FrameLayout::yuv420(pix, p, *mx, stride);
+                           });
+}
+
+inline StagePlan yuv_planar_plan(const FrameBatch& b, const Crop& cr)
+{
+    const YuvPlanarPlanes src = b.lay.yuvp;
+    const YuvMatrix* mx = b.lay.mx;
+    return yuv_planes_plan(b, cr, 1, src.sub_x, src.sub_y, src.c_step, src.u_off, src.v_off, src.c_pitch,
+                           [=](int64_t u_off, int64_t v_off, int c_pitch, size_t stride) {
+                               YuvPlanarPlanes p = src;
+                               p.u_off = u_off; p.v_off = v_off; p.c_pitch = c_pitch;
+                               return FrameLayout::yuv_planar(p, *mx, stride);
+                           });
+}
+
+// 16-bit samples: sub_x is 1, the sample 2 bytes
+inline StagePlan yuv16_plan(const FrameBatch& b, const Crop& cr)
+{
+    const Yuv16Planes src = b.lay.y16;
+    const YuvMatrix* mx = b.lay.mx;
+    return yuv_planes_plan(b, cr, 2, 1, src.sub_y, src.c_step, src.u_off, src.v_off, src.c_pitch,
+                           [=](int64_t u_off, int64_t v_off, int c_pitch, size_t stride) {
+                               Yuv16Planes p = src;
+                               p.u_off = u_off; p.v_off = v_off; p.c_pitch = c_pitch;
+                               return FrameLayout::yuv16(p, *mx, stride);
+                           });
+}
+
+// Planar RGB: a small planar frame, the crop's rows of the B, the G and the R plane, one plane after the other, which the kernels
+// read with the rectangle at its origin.  Work items: the crop's rows of one plane in blocks of 32.
+inline StagePlan planar_plan(const FrameBatch& b, const Crop& cr)
+{
+    const int crows = cr.rows, ccols = cr.cols;
+    const size_t row_pitch = (size_t)b.row_stride, pitch = pitch64((size_t)ccols), plane = (size_t)crows * pitch;
+    const size_t crop_stride = 3 * plane + 128;
+    const PlanarPlanes in_frame = {0, (int64_t)plane, (int64_t)(2 * plane)};
+    const int rblocks = (crows + 31) / 32;
+    StagePlan sp = {{0, crows, ccols, crop_stride, (int)pitch, FrameLayout::planar(in_frame, crop_stride)}, {0, 0, ccols, crows}, 3 * rblocks, {}};
+    const int64_t src_off[3] = {b.lay.planes.b_off, b.lay.planes.g_off, b.lay.planes.r_off};
+    sp.runs.count = 3;
+    for (int p = 0; p < 3; ++p)
+        sp.runs.run[p] = row_run((size_t)src_off[p] + (size_t)cr.y0 * row_pitch + (size_t)cr.x0, row_pitch, (size_t)p * plane, pitch, (size_t)ccols, crows);
+    return sp;
+}
+
+// The plan of a checked batch of any family, by its layout's pix
+inline StagePlan stage_plan(const FrameBatch& b, const Crop& cr)
+{
+    const int pix = b.lay.pix;
+    if (pix_yuv(pix)) return yuv420_plan(b, cr);
+    if (pix_p422(pix)) return p422_plan(b, cr);
+    if (pix_p10(pix)) return yuv422_10_plan(b, cr);
+    if (pix_p32(pix)) return packed32_plan(b, cr);
+    if (pix == PIX_YUVP) return yuv_planar_plan(b, cr);
+    if (pix == PIX_YUV16) return yuv16_plan(b, cr);
+    if (pix == PIX_PLANAR) return planar_plan(b, cr);
+    return packed_plan(b, cr);
+}
+
+// Work item `item` (0 .. items - 1) of a plan as rows of its runs: the rows [*r0, *r1) of the runs [*k0, *k1).  Plans of one run
+// per 32-row block and run (packed: items == blocks; planar RGB: 3 x blocks) give one run's block; the YUV plans (items == the Y
+// blocks + 1) give a Y block, or as the last item every row of the chroma runs.
+inline void stage_item(const StagePlan& sp, int item, int* k0, int* k1, uint32_t* r0, uint32_t* r1)
+{
+    const RowRuns& rr = sp.runs;
+    const int rblocks = (int)((rr.run[0].rows + 31) / 32);
+    if (sp.items == rblocks + 1 && rr.count > 1 && item == rblocks) {
+        *k0 = 1; *k1 = rr.count; *r0 = 0; *r1 = rr.run[1].rows;
+        return;
+    }
+    const int k = item / rblocks, part = item - k * rblocks;
+    *k0 = k; *k1 = k + 1;
+    *r0 = (uint32_t)part * 32;
+    *r1 = *r0 + 32 < rr.run[k].rows ? *r0 + 32 : rr.run[k].rows;
+}
+
+}  // namespace melf

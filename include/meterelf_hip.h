@@ -202,8 +202,8 @@ int melf_process_frames_dev(melf_ctx* ctx, const void* d_frames, const melf_fram
  * triples differ from it at all under code 2, 1 315 under code 3, none under code 4).  Code 2 is the JFIF matrix but not
  * libjpeg's tables bit for bit: libjpeg rounds the chroma terms separately at 16 bits, and 8 332 triples differ by 1 (the JPEG
  * entry points below decode with libjpeg's own arithmetic and are not affected by any of this).
- * Out of scope: BT.2020, interpolated chroma, chroma siting, a frame's planes in separate allocations (frames in separate
- * allocations: melf_process_frame_list*, below).  (4:2:2, 4:4:4 and 4:4:0 planes and
+ * Out of scope: BT.2020, interpolated chroma, chroma siting.  (Frames in separate allocations: melf_process_frame_list*, a
+ * frame's planes in separate allocations: melf_process_plane_list*, both below.  4:2:2, 4:4:4 and 4:4:0 planes and
  * NV21: melf_process_yuv_planar*; 10-, 12- and 16-bit samples: melf_process_yuv16*, both below.)
  * Frame f starts at frames + f * frame_stride; its Y row y at + y * y_pitch (W bytes), its chroma row y >> 1 at
  * + u_offset / v_offset + (y >> 1) * c_pitch: NV12 W bytes U V U V .. (v_offset == u_offset + 1), I420 W / 2 bytes per plane.
@@ -537,7 +537,8 @@ int melf_process_planes_dev(melf_ctx* ctx, const void* d_frames, const melf_plan
  * melf_ctx_set_frames_resident (the promise there covers batches, not lists: a decoder may still be writing the frames; the call
  * then runs on the lane's own stream and the caller's stream continues when it is done).  d_results / out_host / stream: as for
  * melf_process_frames_dev.  The host call is melf_process_frames and its siblings with the i-th pointer as frame i.
- * frames in separate allocations: melf_process_frame_list*; a frame's planes in separate allocations are still not there. */
+ * frames in separate allocations: melf_process_frame_list*; a frame's planes in separate allocations are still not there.
+ * (Not in these two, that is, which take one pointer per frame: one pointer per PLANE is melf_process_plane_list*, below.) */
 enum { MELF_LIST_FRAMES = 0,      /* desc: const melf_frames*            */
        MELF_LIST_YUV = 1,         /* const melf_yuv_frames*              */
        MELF_LIST_YUV422 = 2,      /* const melf_yuv422_frames*           */
@@ -549,6 +550,49 @@ enum { MELF_LIST_FRAMES = 0,      /* desc: const melf_frames*            */
 int melf_process_frame_list_dev(melf_ctx* ctx, int family, const void* desc, const void* const* d_frames, void* d_results,
                                 melf_result* out_host, void* stream);
 int melf_process_frame_list(melf_ctx* ctx, int family, const void* desc, const void* const* frames_host, melf_result* out_host);
+
+/* ---- the same path for frames whose PLANES lie in separate allocations: libav's AVFrame (data[0..2] + linesize[0..2]), V4L2
+ * multi-planar capture (NV12M, YUV420M, NV16M: one buffer per plane), VA-API / DRM exports with one object per plane, a torch
+ * pipeline that holds (y, uv) or (r, g, b) as separate tensors ----
+ * The four families with more than one plane: MELF_LIST_YUV, MELF_LIST_YUV_PLANAR, MELF_LIST_YUV16, MELF_LIST_PLANES (the codes
+ * above).  The four one-plane families return MELF_ERR_INVALID (their frames go through melf_process_frame_list*), as does an
+ * unknown family.
+ *     planes   a HOST array of n * nplanes pointers, frame-major: planes[i * nplanes + k] is plane slot k of frame i (device pointers
+ *              for _dev, host pointers otherwise).  The library copies the array before it returns.  Slots of the YUV families:
+ *              0 = Y, 1 = the U plane or the one interleaved chroma plane, 2 = the V plane; of melf_planar_frames: 0 / 1 / 2 = B / G / R.
+ *     nplanes  what the descriptor implies, else MELF_ERR_INVALID: 2 for MELF_YUV_NV12 and for c_step == 2, 3 otherwise.
+ *     desc     the family's descriptor.  Its n is the length of the list; frame_stride is not looked at.  W, H, the pitches (one
+ *              y_pitch for all Y planes, one c_pitch for all chroma planes, one row_pitch for B, G and R), subsampling, shift,
+ *              matrix and reserved fields follow the family's rules exactly.  The plane offsets (u_offset / v_offset, b_ / g_ /
+ *              r_offset) count from the plane's OWN pointer: 0 for every plane of a planar layout; for a semi-planar layout {0,
+ *              bytes per sample} in the order that says which of U and V comes first ({u, v} = {0, 1}: NV12, NV16, NV24; {1, 0}:
+ *              NV21, NV61, NV42; {0, 2}: P010 ..; melf_yuv_frames' NV12 takes {0, 1} only); anything else is MELF_ERR_INVALID.
+ *     pointers every one is checked for NULL and for the family's alignment (2 bytes for melf_yuv16_frames, none otherwise), the
+ *              message naming the frame's and the plane's index; MELF_ERR_INVALID before anything is launched or copied.  n == 0
+ *              passes.
+ * Readable extent: from each plane pointer the bytes up to and including the last sample of that plane's last row -- Y: (H - 1) *
+ * y_pitch + W * bytes per sample; a chroma plane: (chroma rows - 1) * c_pitch + the bytes of a chroma row (of both samples for an
+ * interleaved plane); B / G / R: (H - 1) * row_pitch + W.  Nothing before a pointer or behind its extent is read: every plane may
+ * be the last thing in its mapping.  Planes and frames may alias or repeat: they are only read.
+ * The records are byte-identical to the family's melf_process_* / melf_process_*_dev call on one contiguous batch whose frames
+ * hold the same samples in list order.
+ * How: as the frame lists.  The library forms the canonical one-allocation descriptor of the same geometry (the planes back to
+ * back), runs the family's unchanged check and staging plan on it -- one row run per plane --, and one kernel (k_plane_rows, the
+ * sibling of k_gather_rows: one launch for all planes of a chunk, timed as MELF_K_GATHER) copies run k of every frame from the
+ * frame's k-th pointer into the lane's staged batch, which the unchanged kernels read.  Lanes, melf_ctx_set_frames_resident, caller
+ * streams, ordering (the copy waits for what the caller's stream held at the call), chunks of 1024 frames and the NULL d_results /
+ * out_host semantics are exactly melf_process_frame_list_dev's; the lane's pointer tables grow to 1024 * nplanes entries.  The host
+ * call packs each run's rows from that run's own plane on the host pool, as melf_process_frame_list does from the one frame.
+ * Measured on one MI355X, 1024-frame config-3 steps (profiles/plane_list/plane_list_rate.txt), NV12 / I420 / P010 / planar RGB:
+ * the plane list (c) takes 1.021 / 1.019 / 0.990 / 0.991 times the step of the frame list (b) of one-allocation frames holding the
+ * same samples (0.29 - 0.33 ms); concatenating each frame's planes into one allocation first (torch.cat per frame) and then the
+ * frame list (d) takes 18.4 / 21.7 / 16.7 / 18.7 times the plane list's step.
+ * Out of scope: planes of one frame with differing chroma pitches (U and V share c_pitch, B, G and R share row_pitch); a 4th
+ * plane; plane lists for melf_process_stream_dev, the fused full-frame mask, melf_aligned_average and the JPEG entry points. */
+int melf_process_plane_list_dev(melf_ctx* ctx, int family, const void* desc, const void* const* d_planes, int nplanes,
+                                void* d_results, melf_result* out_host, void* stream);
+int melf_process_plane_list(melf_ctx* ctx, int family, const void* desc, const void* const* planes_host, int nplanes,
+                            melf_result* out_host);
 
 /* ---- stage entry points (parity tests and roofline runs) ----------------- */
 
@@ -723,7 +767,7 @@ int melf_ctx_set_frames_resident(melf_ctx* ctx, int on);
  * returns per-kernel accumulated milliseconds and launch counts. */
 enum { MELF_K_LPLANE = 0, MELF_K_MATCH = 1, MELF_K_DIALS = 2, MELF_K_FUSED_MASK = 3, MELF_K_HLS = 4,
        MELF_K_JPEG_HUFF = 5, MELF_K_JPEG_IDCT = 6, MELF_K_JPEG_COLOR = 7, MELF_K_STREAM_PROBE = 8,
-       MELF_K_GATHER = 9 /* k_gather_rows: melf_process_frame_list_dev */, MELF_K_COUNT = 10 };
+       MELF_K_GATHER = 9 /* k_gather_rows: melf_process_frame_list_dev; k_plane_rows: melf_process_plane_list_dev */, MELF_K_COUNT = 10 };
 /* Which kernel, in which layout, computed the template match (meterelf/_utils.py:91-97: ONE cv2.matchTemplate code
  * path in the reference; here the batch size and the crop shape select among three kernels and, for the tuned one,
  * among wave layouts) of the context's most recent call.  Tests assert it, so that a change of a dispatch threshold

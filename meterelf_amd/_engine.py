@@ -4,7 +4,7 @@ One MeterReader owns one melf_ctx (one GPU).  Frames go in as uint8 BGR arrays
 (N, H, W, 3); records come back as a numpy structured array (_hip.RESULT_DTYPE)
 and are turned into the reference's dicts / exceptions by result_to_python().
 """
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -340,6 +340,132 @@ class MeterReader:
         ptrs = [v.ptr for v in views]
         return self._read_view(v0._replace(n=n), out, lambda: self.ctx.process_frame_list(layout, desc, ptrs),
                                lambda **kw: self.ctx.process_frame_list_dev(layout, desc, ptrs, **kw))
+
+    _PLANE_LAYOUTS = ('yuv', 'yuv_planar', 'yuv16', 'planar')
+
+    class _PlaneListView(NamedTuple):
+        """What _read_view looks at, for a list of planes"""
+        on_device: bool
+        device: Optional[int]
+        n: int
+        array: object
+        copied: bool = False
+
+    @staticmethod
+    def _plane_list_format(layout, pixel_format, matrix):
+        """(bytes per sample, sub_x, sub_y, interleaved, V first, shift, matrix code) of a format name of the layout's batch method"""
+        fmt = str(pixel_format).lower()
+        if layout == 'planar':
+            if matrix is not None:
+                raise ValueError("layout 'planar' takes no matrix")
+            if fmt not in ('rgb', 'bgr', 'gbr'):
+                raise ValueError("channel_order %r does not name three planes (rgb, bgr, gbr)" % (pixel_format,))
+            return (1, 0, 0, False, False, 0, 0)
+        if layout == 'yuv16':
+            mcode = _hip.yuv_matrix_code(matrix)
+            if fmt not in _hip.YUV16_FORMATS:
+                raise ValueError('pixel_format %r is not a 16-bit planar / semi-planar YUV layout (%s)' % (pixel_format, ', '.join(_hip.YUV16_FORMATS)))
+            (sy, step, vfirst, shift) = _hip.YUV16_FORMATS[fmt]
+            return (2, 1, sy, step == 2, vfirst, shift, mcode)
+        mcode = _hip.yuv_matrix_code('bt601' if matrix is None else matrix)
+        if layout == 'yuv':
+            if fmt not in _hip.YUV_CODES:
+                raise ValueError('pixel_format %r is not a YUV 4:2:0 layout (nv12, i420, yv12)' % (pixel_format,))
+            return (1, 1, 1, fmt == 'nv12', fmt == 'yv12', 0, mcode)
+        if fmt not in _hip.YUV_PLANAR_FORMATS:
+            raise ValueError('pixel_format %r is not a planar / semi-planar YUV layout (%s)' % (pixel_format, ', '.join(_hip.YUV_PLANAR_FORMATS)))
+        (sx, sy, step, vfirst) = _hip.YUV_PLANAR_FORMATS[fmt]
+        return (1, sx, sy, step == 2, vfirst, 0, mcode)
+
+    def read_plane_list(self, frames, layout: str, pixel_format: str, matrix=None, out=None):
+        """Frames whose PLANES lie in separate allocations -- libav's AVFrame (data[0..2], linesize[0..2]), V4L2 multi-planar capture
+        (NV12M: one buffer per plane), (y, uv) or (r, g, b) held as separate tensors -- -> records, equal to the batch method's on one
+        array holding the same samples in list order (melf_process_plane_list*), without concatenating any frame's planes: one kernel
+        gathers the meter crop's rows of every plane, and only those, into a staged batch which the reading kernels take.
+        layout: 'yuv' (read_yuv_frames), 'yuv_planar', 'yuv16' or 'planar' (read_planar_frames; pixel_format is its channel_order,
+        'rgb', 'bgr' or 'gbr'); pixel_format and matrix are that method's, with its defaults.
+        frames: a sequence of tuples of 2-D planes, in the order in which the format name stores them (cutting one frame of the batch
+        method's array at its plane boundaries yields the tuple): 'i420' (Y, U, V); 'yv12' / 'yv16' / 'yv24' (Y, V, U); 'nv12' /
+        'nv21' / 'p010' and the like (Y, C), C the interleaved plane of shape (Hc, Wc * 2) or (Hc, Wc, 2); 'planar': the three planes
+        in channel_order.  A plane is a numpy array / torch CPU tensor (host path) or a torch tensor on this reader's GPU (enqueued on
+        torch.cuda.current_stream): uint8, or uint16 / int16 for 'yuv16'; its elements contiguous along the last axis, any row stride.
+        All Y planes share one pitch, all chroma planes (U and V alike) another; R, G and B share theirs.  ValueError, naming frame,
+        plane and field: a wrong plane count, host and device planes mixed, a plane on another device, differing pitches or shapes,
+        shapes that are not the format's subsampling, a plane that would have to be copied.  out: as for the batch methods, a uint8
+        device tensor (len(frames), RESULT_DTYPE.itemsize)."""
+        if layout not in self._PLANE_LAYOUTS:
+            raise ValueError('layout %r is none of %s' % (layout, ', '.join(self._PLANE_LAYOUTS)))
+        (bps, sx, sy, semi, vfirst, shift, mcode) = self._plane_list_format(layout, pixel_format, matrix)
+        nplanes = 2 if semi else 3
+        frames = list(frames)
+        n = len(frames)
+        if n == 0:
+            return out if out is not None else np.zeros(0, _hip.RESULT_DTYPE)
+        # tuple position -> plane slot of the C ABI (Y, U or interleaved chroma, V; B, G, R)
+        if layout == 'planar':
+            order = str(pixel_format).lower()
+            slot_of = [('bgr').index(ch) for ch in order]
+        else:
+            slot_of = [0, 2, 1] if (vfirst and not semi) else list(range(nplanes))
+        pitch_name = ['row_pitch'] * 3 if layout == 'planar' else ['y_pitch', 'c_pitch', 'c_pitch']
+        first = None          # frame 0's views by slot
+        table = []
+        alive = []            # every plane's view (and with it the array its address points into, a converted one included)
+        for (i, planes) in enumerate(frames):
+            planes = tuple(planes) if isinstance(planes, (tuple, list)) else (planes,)
+            if len(planes) != nplanes:
+                raise ValueError('frame %d of the list has %d planes, %r / %r frames have %d' % (i, len(planes), layout, pixel_format, nplanes))
+            views = [None] * nplanes
+            for (k, p) in enumerate(planes):
+                if not (_hip._is_torch(p) or isinstance(p, np.ndarray)):
+                    p = np.asarray(p)
+                try:
+                    views[slot_of[k]] = (k, _hip.plane_view(p, bps))
+                except ValueError as e:
+                    raise ValueError('frame %d, plane %d of the list: %s' % (i, k, e)) from None
+            if first is None:
+                first = views
+                (H, W) = (first[0][1].rows, first[0][1].row_bytes // bps)
+                if (sx and W % 2) or (sy and H % 2):
+                    raise ValueError('frame 0, plane 0 of the list: shape (%d, %d) is odd where %r subsamples the chroma' % (H, W, pixel_format))
+                crows = H >> sy
+                cbytes = (W >> sx) * (2 if semi else 1) * bps
+                want_shape = [(H, W * bps)] + [(crows, cbytes)] * (nplanes - 1) if layout != 'planar' else [(H, W)] * 3
+            for (slot, (k, v)) in enumerate(views):
+                where = 'frame %d, plane %d of the list' % (i, k)
+                (k0, v0) = first[0]
+                if v.on_device != v0.on_device:
+                    raise ValueError('%s is in %s memory, frame 0, plane %d in %s memory' % (
+                        where, 'device' if v.on_device else 'host', k0, 'device' if v0.on_device else 'host'))
+                if v.device != v0.device:
+                    raise ValueError('%s is on cuda:%s, frame 0, plane %d on cuda:%s' % (where, v.device, k0, v0.device))
+                if (v.rows, v.row_bytes) != want_shape[slot]:
+                    raise ValueError('%s differs in shape: %d rows of %d bytes, not the %d rows of %d bytes that %r frames of %d x %d have' % (
+                        where, v.rows, v.row_bytes, want_shape[slot][0], want_shape[slot][1], pixel_format, W, H))
+                if not v.in_place:
+                    raise ValueError('%s has a layout the descriptor cannot express (it would have to be copied): its elements must be '
+                                     'contiguous along the last axis and its rows a non-negative stride apart' % where)
+                ref = first[1 if slot == 2 else slot][1] if layout != 'planar' else first[0][1]
+                if v.pitch != ref.pitch:
+                    raise ValueError('%s differs in %s: %d, not %d' % (where, pitch_name[slot], v.pitch, ref.pitch))
+                table.append(v.ptr)
+                alive.append(v)
+        (y_pitch, c_pitch) = (first[0][1].pitch, first[1][1].pitch)
+        if layout == 'planar':
+            desc = _hip.MelfPlanarFrames(n, H, W, 0, 0, 0, 0, y_pitch, 0)
+        else:
+            (u_off, v_off) = ((bps, 0) if vfirst else (0, bps)) if semi else (0, 0)
+            if layout == 'yuv':
+                desc = _hip.MelfYuvFrames(_hip.YUV_NV12 if semi else _hip.YUV_I420, mcode, n, H, W, 0, y_pitch, c_pitch, u_off, v_off, 0)
+            elif layout == 'yuv_planar':
+                desc = _hip.MelfYuvPlanarFrames(mcode, n, H, W, sx, sy, 2 if semi else 1, 0, y_pitch, c_pitch, u_off, v_off, 0)
+            else:
+                desc = _hip.MelfYuv16Frames(mcode, n, H, W, sy, 2 if semi else 1, shift, 0, y_pitch, c_pitch, u_off, v_off, 0)
+        v0 = first[0][1]
+        view = self._PlaneListView(v0.on_device, v0.device, n, v0.array)
+        # the closures hold `alive`: the table is addresses only, and what np.asarray made of an array-like has no other owner
+        return self._read_view(view, out, lambda alive=alive: self.ctx.process_plane_list(layout, desc, table, nplanes),
+                               lambda alive=alive, **kw: self.ctx.process_plane_list_dev(layout, desc, table, nplanes, **kw))
 
     def read_crops(self, crops: np.ndarray) -> np.ndarray:
         """Already meter_rect-cropped images (the reference's bgr_image injection)."""

@@ -222,7 +222,7 @@ EXPORTS = [
     'melf_process_yuv16', 'melf_process_yuv16_dev', 'melf_yuv16_to_bgr',
     'melf_process_yuv422_10', 'melf_process_yuv422_10_dev', 'melf_yuv422_10_to_bgr',
     'melf_process_packed32', 'melf_process_packed32_dev', 'melf_packed32_to_bgr',
-    'melf_process_frame_list', 'melf_process_frame_list_dev',
+    'melf_process_frame_list', 'melf_process_frame_list_dev', 'melf_process_plane_list', 'melf_process_plane_list_dev',
     'melf_bgr2hls', 'melf_hls_inrange_close', 'melf_hls_inrange_close_dev', 'melf_match_ccoeff',
     'melf_read_dials', 'melf_aligned_average', 'melf_inrange', 'melf_ctx_fused_table_ties', 'melf_ctx_fused_variant', 'melf_ctx_set_frames_resident', 'melf_ctx_last_match', 'melf_ctx_last_dials', 'melf_match_layout_query', 'melf_match_gen_plan_query', 'melf_ctx_set_profiling', 'melf_ctx_timings', 'melf_kernel_name',
     'melf_jpeg_probe', 'melf_jpeg_probe_batch', 'melf_jpeg_decode_batch', 'melf_jpeg_clean_segment', 'melf_jpeg_process_batch',
@@ -285,6 +285,8 @@ def lib():
     L.melf_process_planes_dev.argtypes = [vp, vp, C.POINTER(MelfPlanarFrames), vp, vp, vp]
     L.melf_process_frame_list.argtypes = [vp, C.c_int, vp, vp, vp]
     L.melf_process_frame_list_dev.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    L.melf_process_plane_list.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
+    L.melf_process_plane_list_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp]
     if hasattr(L, 'melf_gather_frame_list_dev'):   # the diagnostic build only
         L.melf_gather_frame_list_dev.argtypes = [vp, C.c_int, vp, vp, vp, C.POINTER(C.c_size_t)]
     L.melf_process_stream_dev.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, vp]
@@ -757,6 +759,36 @@ def yuv16_frames_view(frames, pixel_format, matrix):
     (frames, ptr, n, H, W, rp, c_pitch, u_off, v_off, fs, extent, copied) = _yuv_rows_layout(
         frames, is_torch, shape, strides, ptr, 2, 1, sy, step, vfirst, fmt, ' with an even W' + ' and an even H' * sy)
     return Yuv16FramesView(ptr, on_device, device, n, H, W, sy, step, shift, rp, c_pitch, u_off, v_off, fs, extent, copied, frames, mcode)
+
+
+class PlaneView(NamedTuple):
+    """One plane of one frame as melf_process_plane_list* read it (plane_view)."""
+    ptr: int            # address of the plane's first sample
+    on_device: bool     # True: a torch tensor on a GPU (ptr is a device address)
+    device: Optional[int]
+    rows: int
+    row_bytes: int      # bytes of a row's samples (an interleaved plane: of both)
+    pitch: int          # bytes between rows
+    in_place: bool      # False: the plane would have to be copied (an element stride other than 1, a negative or too small row stride)
+    array: object       # what ptr points into: keep it alive while the call runs
+
+
+def plane_view(plane, bps=1):
+    """Describes one plane -- a 2-D (rows, samples) array, or (rows, pairs, 2) for an interleaved chroma plane -- of bps-byte
+    samples (1: uint8; 2: uint16, or torch.int16 holding the same bits): a numpy array or torch tensor whose elements are contiguous
+    along the last axis (and the pairs along the last two), with any row stride.  Not that dtype or not 2-D / (.., .., 2): ValueError."""
+    (a, _is_t, shape, strides, ptr, on_device, device) = _unwrap(plane) if bps == 1 else _unwrap16(plane)
+    if not (len(shape) == 2 or (len(shape) == 3 and shape[2] == 2)) or 0 in shape:
+        raise ValueError('a plane must be (rows, samples) or, interleaved, (rows, pairs, 2), not %s' % (tuple(shape),))
+    rows = shape[0]
+    samples = shape[1] * (2 if len(shape) == 3 else 1)
+    row_bytes = samples * bps
+    contiguous = strides[-1] == bps or shape[-1] == 1
+    if len(shape) == 3:
+        contiguous = contiguous and (strides[1] == 2 * bps or shape[1] == 1)
+    pitch = strides[0] if rows > 1 else row_bytes   # the stride of a dimension of size 1 is never stepped over
+    in_place = bool(contiguous and row_bytes <= pitch <= 2 ** 31 - 1 and pitch % bps == 0)
+    return PlaneView(int(ptr), on_device, device, int(rows), int(row_bytes), int(pitch), in_place, a)
 
 
 class Yuv422_10FramesView(NamedTuple):
@@ -1341,6 +1373,41 @@ class Context:
         family = LIST_FAMILIES.get(family, family)
         out = np.zeros(max(desc.n, 0), RESULT_DTYPE) if want_host else None
         check(self._L.melf_process_frame_list_dev(self._h, family, C.byref(desc), self._pointer_table(d_frame_ptrs, desc),
+                                                  C.c_void_p(d_results_ptr) if d_results_ptr else None, _ptr(out) if want_host else None,
+                                                  C.c_void_p(stream) if stream else None))
+        return out
+
+    # --- a frame's planes in separate allocations ---
+    @staticmethod
+    def _plane_table(ptrs, desc, nplanes):
+        """The host array of plane pointers melf_process_plane_list* take, frame-major: ptrs is flat (n * nplanes addresses) or one
+        sequence of nplanes addresses per frame; a NULL entry stays NULL (the library names it).  Fewer than desc.n * nplanes: ValueError."""
+        if isinstance(ptrs, C.Array):
+            flat = ptrs
+        else:
+            flat = []
+            for p in ptrs:
+                flat.extend(p if isinstance(p, (tuple, list)) else (p,))
+        if nplanes > 0 and len(flat) < desc.n * nplanes:
+            raise ValueError('the descriptor counts %d frames of %d planes, the list holds %d pointers' % (desc.n, nplanes, len(flat)))
+        return flat if isinstance(flat, C.Array) else (C.c_void_p * len(flat))(*[int(p) or None for p in flat])
+
+    def process_plane_list(self, family, desc, plane_ptrs, nplanes):
+        """Host frames whose planes lie in separate allocations (melf_process_plane_list) -> records.  family: LIST_FAMILIES' code or
+        name ('yuv', 'yuv_planar', 'yuv16', 'planar'); desc: the family's descriptor, its n the length of the list, its plane offsets
+        counted from each plane's own pointer; plane_ptrs: n * nplanes addresses, frame-major (slots: Y, U or interleaved chroma, V;
+        B, G, R), flat or one tuple per frame."""
+        family = LIST_FAMILIES.get(family, family)
+        out = np.zeros(max(desc.n, 0), RESULT_DTYPE)
+        check(self._L.melf_process_plane_list(self._h, family, C.byref(desc), self._plane_table(plane_ptrs, desc, nplanes), nplanes, _ptr(out)))
+        return out
+
+    def process_plane_list_dev(self, family, desc, d_plane_ptrs, nplanes, d_results_ptr=None, want_host=True, stream=None):
+        """The same for planes in HBM (melf_process_plane_list_dev, as process_frame_list_dev): d_plane_ptrs: their device addresses
+        (the library copies the table before it returns).  Returns records when want_host."""
+        family = LIST_FAMILIES.get(family, family)
+        out = np.zeros(max(desc.n, 0), RESULT_DTYPE) if want_host else None
+        check(self._L.melf_process_plane_list_dev(self._h, family, C.byref(desc), self._plane_table(d_plane_ptrs, desc, nplanes), nplanes,
                                                   C.c_void_p(d_results_ptr) if d_results_ptr else None, _ptr(out) if want_host else None,
                                                   C.c_void_p(stream) if stream else None))
         return out

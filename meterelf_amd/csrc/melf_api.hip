@@ -1638,15 +1638,23 @@ static int list_batch(const melf_ctx* c, int family, const void* desc, const voi
 static const int LIST_CHUNK = 1024;
 
 // read: the reading path on the staged batch (melf_process_frame_list_dev); otherwise the gather alone (the diagnostic build's
-// melf_gather_frame_list_dev), *bytes_moved: what its kernels read and wrote
+// melf_gather_frame_list_dev), *bytes_moved: what its kernels read and wrote.  pl NULL: d_frames holds one pointer per frame
+// (k_gather_rows); otherwise pl->nplanes pointers per frame, frame-major, b the canonical batch of pl (melf_process_plane_list_dev:
+// k_plane_rows).
 static int frame_list_dev(melf_ctx* c, const FrameBatch& b, const void* const* d_frames, void* d_results, melf_result* out_host, void* stream_,
-                          bool read, size_t* bytes_moved)
+                          bool read, size_t* bytes_moved, const PlaneList* pl = nullptr)
 {
     HIP_TRY(hipSetDevice(c->device));
     Crop cr;
     if (int rc = meter_crop(c->P, nullptr, b.H, b.W, &cr)) return rc;
     const StagePlan sp = stage_plan(b, cr);
     const int n = b.n;
+    const size_t per_frame_ptrs = pl ? (size_t)pl->nplanes : 1;   // table entries per frame
+    PlaneSplit split = {};
+    if (pl) {
+        if (sp.runs.count != pl->nplanes) return fail(MELF_ERR_INVALID, "plane list: the plan's runs are not one per plane");
+        split = plane_split(sp.runs, *pl);
+    }
     hipStream_t st = (hipStream_t)stream_;  // NULL = the null (legacy default) stream, as everywhere in HIP
     melf_result* res_dev = (melf_result*)d_results;
     if (read && !res_dev) {
@@ -1672,21 +1680,22 @@ static int frame_list_dev(melf_ctx* c, const FrameBatch& b, const void* const* d
     const size_t stride = sp.staged.frame_stride;
     const size_t cap = (size_t)(n < LIST_CHUNK ? n : LIST_CHUNK);
     if (int rc = grow(&c->d_list_stage[lane], &c->list_stage_cap[lane], cap * stride)) return rc;
-    if (int rc = grow(&c->d_list_tab[lane], &c->list_tab_cap[lane], cap)) return rc;
+    const size_t tab_cap = cap * per_frame_ptrs;
+    if (int rc = grow(&c->d_list_tab[lane], &c->list_tab_cap[lane], tab_cap)) return rc;
     if (!c->ev_list_tab[lane]) HIP_TRY(hipEventCreateWithFlags(&c->ev_list_tab[lane], hipEventDisableTiming));
-    if (c->h_list_tab_cap[lane] < cap) {
+    if (c->h_list_tab_cap[lane] < tab_cap) {
         if (c->h_list_tab[lane]) { HIP_TRY(hipEventSynchronize(c->ev_list_tab[lane])); HIP_TRY(hipHostFree(c->h_list_tab[lane])); }
         c->h_list_tab[lane] = nullptr;
         c->h_list_tab_cap[lane] = 0;
-        HIP_TRY(hipHostMalloc((void**)&c->h_list_tab[lane], cap * sizeof(void*), hipHostMallocDefault));
-        c->h_list_tab_cap[lane] = cap;
+        HIP_TRY(hipHostMalloc((void**)&c->h_list_tab[lane], tab_cap * sizeof(void*), hipHostMallocDefault));
+        c->h_list_tab_cap[lane] = tab_cap;
     }
     FrameBatch staged = sp.staged;
     for (int f0 = 0; f0 < n; f0 += LIST_CHUNK) {
         const int m = n - f0 < LIST_CHUNK ? n - f0 : LIST_CHUNK;
         HIP_TRY(hipEventSynchronize(c->ev_list_tab[lane]));   // the previous upload from the pinned table has finished
-        memcpy(c->h_list_tab[lane], d_frames + f0, (size_t)m * sizeof(void*));
-        HIP_TRY(hipMemcpyAsync(c->d_list_tab[lane], c->h_list_tab[lane], (size_t)m * sizeof(void*), hipMemcpyHostToDevice, ws));
+        memcpy(c->h_list_tab[lane], d_frames + (size_t)f0 * per_frame_ptrs, (size_t)m * per_frame_ptrs * sizeof(void*));
+        HIP_TRY(hipMemcpyAsync(c->d_list_tab[lane], c->h_list_tab[lane], (size_t)m * per_frame_ptrs * sizeof(void*), hipMemcpyHostToDevice, ws));
         HIP_TRY(hipEventRecord(c->ev_list_tab[lane], ws));
         if (resident && f0 == 0) {
             if (!c->ev_call[lane]) HIP_TRY(hipEventCreateWithFlags(&c->ev_call[lane], hipEventDisableTiming));
@@ -1695,7 +1704,10 @@ static int frame_list_dev(melf_ctx* c, const FrameBatch& b, const void* const* d
         }
         {
             KernelTimer t(c, MELF_K_GATHER, ws);
-            launch_gather_rows(c->d_list_tab[lane], m, sp.runs, c->d_list_stage[lane], stride, b.lay.extent, ws);
+            if (pl)
+                launch_plane_rows(c->d_list_tab[lane], pl->nplanes, m, sp.runs, split, c->d_list_stage[lane], stride, ws);
+            else
+                launch_gather_rows(c->d_list_tab[lane], m, sp.runs, c->d_list_stage[lane], stride, b.lay.extent, ws);
         }
         HIP_TRY(hipGetLastError());
         if (!read) continue;
@@ -1733,6 +1745,66 @@ extern "C" int melf_process_frame_list(melf_ctx* c, int family, const void* desc
     if (int rc = list_batch(c, family, desc, frames_host, &b)) return rc;
     if (b.n == 0) return MELF_SUCCESS;
     return host_frames(c, Listed{frames_host}, b, out_host);
+}
+
+// ------------------------------------------------------------ plane lists ----
+// A frame's planes in separate allocations: nplanes pointers per frame beside the family's descriptor, whose plane offsets count
+// from each plane's own pointer.  plane_list_check (melf_stage_plan.h) makes the canonical one-allocation descriptor of the same
+// geometry and runs the family's check on it; the plan of that batch has one run per plane, and k_plane_rows / the host packer read
+// run k from plane slot k.  Everything else is the frame lists'.
+static int plane_list_batch(const melf_ctx* c, int family, const void* desc, const void* const* planes, int nplanes, PlaneList* pl)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    if (const char* msg = plane_list_check(family, desc, nplanes, pl)) return fail(MELF_ERR_INVALID, msg);
+    const int n = pl->batch.n;
+    if (n == 0) return MELF_SUCCESS;
+    if (!planes) return fail(MELF_ERR_INVALID, "the list's array of plane pointers is NULL");
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < nplanes; ++k) {
+            const void* p = planes[(size_t)i * nplanes + k];
+            const char* msg = !p ? "plane pointer is NULL" : ((uintptr_t)p & (pl->align - 1)) ? "16-bit samples need a 2-byte aligned plane pointer" : nullptr;
+            if (msg) return fail(MELF_ERR_INVALID, "frame " + std::to_string(i) + ", plane " + std::to_string(k) + " of the list: " + msg);
+        }
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_process_plane_list_dev(melf_ctx* c, int family, const void* desc, const void* const* d_planes, int nplanes, void* d_results,
+                                           melf_result* out_host, void* stream_)
+{
+    PlaneList pl;
+    if (int rc = plane_list_batch(c, family, desc, d_planes, nplanes, &pl)) return rc;
+    if (pl.batch.n == 0) return MELF_SUCCESS;
+    return frame_list_dev(c, pl.batch, d_planes, d_results, out_host, stream_, true, nullptr, &pl);
+}
+
+// frame i of a plane list: its nplanes pointers
+struct ListedPlanes {
+    const void* const* planes;
+    int nplanes;
+    const void* const* operator()(int i) const { return planes + (size_t)i * nplanes; }
+};
+extern "C" int melf_process_plane_list(melf_ctx* c, int family, const void* desc, const void* const* planes_host, int nplanes, melf_result* out_host)
+{
+    PlaneList pl;
+    if (int rc = plane_list_batch(c, family, desc, planes_host, nplanes, &pl)) return rc;
+    if (pl.batch.n == 0) return MELF_SUCCESS;
+    Crop cr;
+    if (int rc = host_crop(c, pl.batch, out_host, &cr)) return rc;
+    const StagePlan sp = stage_plan(pl.batch, cr);
+    if (sp.runs.count != pl.nplanes) return fail(MELF_ERR_INVALID, "plane list: the plan's runs are not one per plane");
+    const PlaneSplit split = plane_split(sp.runs, pl);
+    // host_frames' packer, each run's rows from that run's own plane
+    return stage_host_frames(c, ListedPlanes{planes_host, nplanes}, pl.batch.n, sp, out_host, [=](const void* const* planes, uint8_t* staged, int item) {
+        int k0, k1;
+        uint32_t r0, r1;
+        stage_item(sp, item, &k0, &k1, &r0, &r1);
+        for (int k = k0; k < k1; ++k) {
+            const RowRun& run = sp.runs.run[k];
+            const uint8_t* plane = (const uint8_t*)planes[k] + (size_t)split.src_off[k];
+            for (uint32_t y = r0; y < r1; ++y)
+                memcpy(staged + (size_t)run.dst_off + (size_t)y * run.dst_pitch, plane + (size_t)y * run.src_pitch, run.row_bytes);
+        }
+    });
 }
 
 #ifdef MELF_DIAG   // measurement aid of the diagnostic build (tools/frame_list_rate.py): not an entry point of the product library

@@ -2,6 +2,7 @@
 // destination row the source offset, the bytes it holds and the loads that fetch them.  Plain C++, the sibling of melf_prep_addr.h:
 // the kernel computes its addresses with these functions, and tests/stage_runs_main.cpp executes the same functions on the CPU
 // against frames of exact extent.  Source offsets count BYTES from a frame's pointer, destination offsets from its staged frame.
+// k_plane_rows, the same copy from one pointer per PLANE, adds wave_run and plane_rows (tests/plane_runs_main.cpp executes those).
 //
 // A destination row starts on a 64-byte boundary, so piece p of a row is the 16 aligned bytes [16 p, 16 p + 16) of it.  A piece that
 // lies wholly inside the row's bytes is one 16-byte load at whatever alignment the source row has; the last piece of a row whose
@@ -56,6 +57,31 @@ MELF_GATHER_FN WaveRows wave_rows(const RowRuns& rr, uint32_t w)
 #undef MELF_GATHER_SEL
     o.row0 = b * ROWS_PER_WAVE;
     o.nrows = o.run.rows - o.row0 < (uint32_t)ROWS_PER_WAVE ? o.run.rows - o.row0 : (uint32_t)ROWS_PER_WAVE;
+    return o;
+}
+
+// k_plane_rows (a frame's planes in separate allocations): the index of wave w's run -- the plane slot its rows are read from --, as
+// wave_rows finds it
+MELF_GATHER_FN uint32_t wave_run(const RowRuns& rr, uint32_t w)
+{
+    const uint32_t w0 = run_waves(rr.run[0]), w1 = rr.count > 1 ? run_waves(rr.run[1]) : 0;
+    return w < w0 ? 0u : (w < w0 + w1 ? 1u : 2u);
+}
+// ... and the wave's rows with the run's source offset counted from that plane's own pointer, of which `extent` bytes are readable
+// (PlaneSplit: melf_stage_plan.h); the same masks as wave_rows, for the same reason
+struct PlaneRows {
+    WaveRows wr;       // wr.run.src_off: from the pointer of plane slot k
+    uint32_t k;
+    uint64_t extent;   // of plane slot k
+};
+MELF_GATHER_FN PlaneRows plane_rows(const RowRuns& rr, const PlaneSplit& ps, uint32_t w)
+{
+    PlaneRows o;
+    o.wr = wave_rows(rr, w);
+    o.k = wave_run(rr, w);
+    const uint64_t m0 = 0 - (uint64_t)(o.k == 0), m1 = 0 - (uint64_t)(o.k == 1), m2 = 0 - (uint64_t)(o.k == 2);
+    o.wr.run.src_off = (ps.src_off[0] & m0) | (ps.src_off[1] & m1) | (ps.src_off[2] & m2);
+    o.extent = (ps.extent[0] & m0) | (ps.extent[1] & m1) | (ps.extent[2] & m2);
     return o;
 }
 

@@ -199,6 +199,12 @@ void launch_p422_to_bgr(const uint8_t* d_src, int pix, int n, int H, int W, int 
 struct RowRuns;
 void launch_gather_rows(const void* const* d_frames, int n, const RowRuns& runs, uint8_t* d_staged, size_t staged_stride, size_t extent,
                         hipStream_t stream);
+// The same for frames whose planes lie in separate allocations (melf_process_plane_list_dev): d_planes is a DEVICE array of
+// n * nplanes device pointers, frame-major; run k of the plan reads plane slot k at the offset and within the extent `split` gives
+// (melf_stage_plan.h: plane_split).  nplanes == runs.count.
+struct PlaneSplit;
+void launch_plane_rows(const void* const* d_planes, int nplanes, int n, const RowRuns& runs, const PlaneSplit& split, uint8_t* d_staged,
+                       size_t staged_stride, hipStream_t stream);
 
 // ---- calibration stage kernels ------------------------------------------------
 void launch_aligned_average(const uint8_t* d_frames, int n, size_t frame_stride, int row_stride, int x0, int y0, int rows,

@@ -4,7 +4,9 @@
 // context.  Two users, one statement of a format's staged frame: the host-fed path (melf_api.hip: stage_host_frames packs the runs
 // on the CPU into pinned memory) and the frame lists (melf_process_frame_list*: k_gather_rows copies the runs of separately
 // allocated device frames into a staged batch in HBM).  The kernels then read the staged frames as frames of their own, with the
-// rectangle where the plan says.  tests/stage_runs_main.cpp sweeps the plans on the CPU.
+// rectangle where the plan says.  tests/stage_runs_main.cpp sweeps the plans on the CPU.  The plane lists (melf_process_plane_list*:
+// one pointer per PLANE) take the same plans of a canonical one-allocation descriptor and split their runs by plane: the end of this
+// file; tests/plane_runs_main.cpp sweeps that.
 #pragma once
 #include "melf_frame_checks.h"
 
@@ -26,8 +28,9 @@ inline bool clamp_crop(const int* r, int H, int W, Crop* cr)
 
 // One run of rows: `rows` rows of row_bytes bytes, from frame + src_off + r * src_pitch to staged + dst_off + r * dst_pitch.  A
 // plane of the frame is one run (Y / U / V, Y / UV, B / G / R, or the one packed plane).  dst_off and dst_pitch are multiples of 64;
-// src_off and src_pitch have the alignment the family's check leaves the frame's base and pitches.  Every run reads from the one
-// frame pointer (a frame's planes in separate allocations would give each run a pointer slot of its own: not built).
+// src_off and src_pitch have the alignment the family's check leaves the frame's base and pitches.  Every run of a plan reads from
+// the one frame pointer; for a frame whose planes lie in separate allocations (melf_process_plane_list*) plane_split, at the end of
+// this file, gives each run a pointer slot of its own -- the run's index -- and its offset from that plane's pointer.
 struct RowRun {
     uint64_t src_off, dst_off;
     uint32_t src_pitch, dst_pitch;
@@ -228,6 +231,160 @@ inline void stage_item(const StagePlan& sp, int item, int* k0, int* k1, uint32_t
     *k0 = k; *k1 = k + 1;
     *r0 = (uint32_t)part * 32;
     *r1 = *r0 + 32 < rr.run[k].rows ? *r0 + 32 : rr.run[k].rows;
+}
+
+// ---- a frame's planes in separate allocations (melf_process_plane_list*) ----
+// The caller's descriptor gives the geometry of one frame whose planes each have a pointer of their own: the plane offsets in it
+// count from the plane's OWN pointer.  plane_list_check turns it into the canonical one-allocation descriptor of the same geometry --
+// the planes back to back, each from an even offset --, runs the family's unchanged check on that, and leaves the batch, the
+// canonical offset of every plane slot and the bytes readable from every plane's pointer.  The plan of that batch (stage_plan) has
+// one run per plane, run k reading plane slot k; plane_split restates the runs' source offsets from the planes' own pointers.
+// Slots: 0 = Y, 1 = the U plane or the one interleaved chroma plane, 2 = the V plane; melf_planar_frames: 0 / 1 / 2 = B / G / R.
+struct PlaneList {
+    FrameBatch batch;                      // the canonical one-allocation batch; n: the list's length
+    int nplanes;                           // pointers per frame: 2 (Y and interleaved chroma) or 3
+    unsigned align;                        // every plane pointer is a multiple of this: 2 for 16-bit samples, 1 otherwise
+    uint64_t offset[STAGE_MAX_RUNS];       // slot k's first byte in the canonical frame
+    uint64_t extent[STAGE_MAX_RUNS];       // bytes readable from slot k's pointer: (rows - 1) * pitch + the bytes of a row
+};
+// Run k of a plan as k_plane_rows and the host packer read it: from plane slot k, src_off[k] bytes behind that plane's pointer, of
+// which extent[k] bytes are readable
+struct PlaneSplit {
+    uint64_t src_off[STAGE_MAX_RUNS], extent[STAGE_MAX_RUNS];
+    int count;
+};
+inline PlaneSplit plane_split(const RowRuns& runs, const PlaneList& pl)
+{
+    PlaneSplit ps = {};
+    ps.count = runs.count;
+    for (int k = 0; k < STAGE_MAX_RUNS; ++k)
+        if (k < runs.count) {
+            ps.src_off[k] = runs.run[k].src_off - pl.offset[k];
+            ps.extent[k] = pl.extent[k];
+        }
+    return ps;
+}
+
+constexpr const char* PLANE_LIST_ONE_PLANE =
+    "frames of this family have one plane: a list of such frames goes through melf_process_frame_list*";
+constexpr const char* PLANE_LIST_UNKNOWN_FAMILY =
+    "unknown family of the plane list (accepted: MELF_LIST_YUV, MELF_LIST_YUV_PLANAR, MELF_LIST_YUV16, MELF_LIST_PLANES)";
+constexpr const char* PLANE_LIST_PLANAR_OFFSETS =
+    "plane offsets of a plane list count from the plane's own pointer: every offset of a planar layout must be 0";
+constexpr const char* PLANE_LIST_SEMI_OFFSETS =
+    "plane offsets of a plane list count from the plane's own pointer: a semi-planar layout needs {u_offset, v_offset} = {0, bytes "
+    "per sample} or the reverse";
+constexpr const char* PLANE_LIST_NPLANES =
+    "nplanes does not fit the descriptor: 2 for NV12 and c_step 2 (Y and the interleaved chroma plane), 3 otherwise";
+
+// The Y / chroma geometry of the three YUV descriptors -> the canonical offsets.  H, W, the pitches and the chroma shape are used
+// only where they are in range (the family's check, run on the result, rejects them otherwise, whatever the offsets): 0 elsewhere.
+struct PlaneGeom {
+    int64_t y_end, c0, c1, c_extent;
+};
+inline PlaneGeom yuv_plane_geom(int H, int W, int64_t y_pitch, int64_t c_pitch, int c_rows, int c_samples, int step, int bps)
+{
+    PlaneGeom g = {0, 0, 0, 0};
+    if (H <= 0 || W <= 0 || y_pitch < 0 || y_pitch > INT32_MAX || c_pitch < 0 || c_pitch > INT32_MAX || c_rows <= 0 || c_samples <= 0) return g;
+    g.y_end = plane_span(H, y_pitch, W, 1, bps);
+    g.c0 = (g.y_end + 1) & ~(int64_t)1;
+    g.c_extent = (int64_t)(c_rows - 1) * c_pitch + (int64_t)c_samples * step * bps;
+    g.c1 = g.c0 + ((g.c_extent + 1) & ~(int64_t)1);
+    return g;
+}
+// Fills the canonical offsets of a YUV descriptor copy *d (u_offset / v_offset, frame_stride, n) from the caller's; vfirst: V is the
+// first sample of an interleaved pair
+template <class Desc>
+inline void yuv_canonical(Desc* d, const PlaneGeom& g, bool semi, bool vfirst, int bps)
+{
+    d->u_offset = semi ? g.c0 + (vfirst ? bps : 0) : g.c0;
+    d->v_offset = semi ? g.c0 + (vfirst ? 0 : bps) : g.c1;
+    d->frame_stride = INT64_MAX & ~(int64_t)15;   // as the frame lists: a stride every check takes
+    d->n = d->n > 0 ? 1 : d->n;
+}
+inline void yuv_plane_slots(PlaneList* pl, const PlaneGeom& g, bool semi)
+{
+    pl->nplanes = semi ? 2 : 3;
+    pl->offset[0] = 0; pl->offset[1] = (uint64_t)g.c0; pl->offset[2] = semi ? 0 : (uint64_t)g.c1;
+    pl->extent[0] = (uint64_t)g.y_end; pl->extent[1] = (uint64_t)g.c_extent; pl->extent[2] = semi ? 0 : (uint64_t)g.c_extent;
+}
+
+// family: MELF_LIST_*; desc: the family's descriptor with the plane offsets counted from each plane's own pointer; nplanes: the
+// caller's.  Returns the error message, or nullptr with *pl filled (n == 0 passes).  The pointers themselves -- NULL, pl->align --
+// are the caller's to check: it knows their indices.
+inline const char* plane_list_check(int family, const void* desc, int nplanes, PlaneList* pl)
+{
+    const void* const base = (const void*)(uintptr_t)64;   // a pointer that breaks no family's rule
+    *pl = PlaneList{};
+    pl->align = 1;
+    switch (family) {
+    case MELF_LIST_FRAMES: case MELF_LIST_YUV422: case MELF_LIST_YUV422_10: case MELF_LIST_PACKED32: return PLANE_LIST_ONE_PLANE;
+    case MELF_LIST_YUV: {
+        if (!desc) return check_yuv(nullptr, nullptr, &pl->batch);
+        melf_yuv_frames d = *(const melf_yuv_frames*)desc;
+        const int n = d.n;
+        const bool semi = d.format == MELF_YUV_NV12;
+        const int64_t u = d.u_offset, v = d.v_offset;
+        const PlaneGeom g = yuv_plane_geom(d.H, d.W, d.y_pitch, d.c_pitch, d.H / 2, d.W / 2, semi ? 2 : 1, 1);
+        yuv_canonical(&d, g, semi, false, 1);
+        if (const char* msg = check_yuv(base, &d, &pl->batch)) return msg;
+        if (semi ? (u != 0 || v != 1) : (u != 0 || v != 0)) return semi ? PLANE_LIST_SEMI_OFFSETS : PLANE_LIST_PLANAR_OFFSETS;
+        yuv_plane_slots(pl, g, semi);
+        pl->batch.n = n;
+        break;
+    }
+    case MELF_LIST_YUV_PLANAR: {
+        if (!desc) return check_yuv_planar(nullptr, nullptr, &pl->batch);
+        melf_yuv_planar_frames d = *(const melf_yuv_planar_frames*)desc;
+        const int n = d.n;
+        const bool semi = d.c_step == 2, vfirst = d.v_offset < d.u_offset;
+        const int64_t u = d.u_offset, v = d.v_offset;
+        const bool subs = (d.sub_x == 0 || d.sub_x == 1) && (d.sub_y == 0 || d.sub_y == 1);
+        const PlaneGeom g = yuv_plane_geom(d.H, d.W, d.y_pitch, d.c_pitch, subs ? d.H >> d.sub_y : 0, subs ? d.W >> d.sub_x : 0, semi ? 2 : 1, 1);
+        yuv_canonical(&d, g, semi, vfirst, 1);
+        if (const char* msg = check_yuv_planar(base, &d, &pl->batch)) return msg;
+        if (semi ? !((u == 0 && v == 1) || (u == 1 && v == 0)) : (u != 0 || v != 0)) return semi ? PLANE_LIST_SEMI_OFFSETS : PLANE_LIST_PLANAR_OFFSETS;
+        yuv_plane_slots(pl, g, semi);
+        pl->batch.n = n;
+        break;
+    }
+    case MELF_LIST_YUV16: {
+        if (!desc) return check_yuv16(nullptr, nullptr, &pl->batch);
+        melf_yuv16_frames d = *(const melf_yuv16_frames*)desc;
+        const int n = d.n;
+        const bool semi = d.c_step == 2, vfirst = d.v_offset < d.u_offset;
+        const int64_t u = d.u_offset, v = d.v_offset;
+        const bool subs = d.sub_y == 0 || d.sub_y == 1;
+        const PlaneGeom g = yuv_plane_geom(d.H, d.W, d.y_pitch, d.c_pitch, subs ? d.H >> d.sub_y : 0, d.W >> 1, semi ? 2 : 1, 2);
+        yuv_canonical(&d, g, semi, vfirst, 2);
+        if (const char* msg = check_yuv16(base, &d, &pl->batch)) return msg;
+        if (semi ? !((u == 0 && v == 2) || (u == 2 && v == 0)) : (u != 0 || v != 0)) return semi ? PLANE_LIST_SEMI_OFFSETS : PLANE_LIST_PLANAR_OFFSETS;
+        yuv_plane_slots(pl, g, semi);
+        pl->align = 2;
+        pl->batch.n = n;
+        break;
+    }
+    case MELF_LIST_PLANES: {
+        if (!desc) return check_planes(nullptr, nullptr, &pl->batch);
+        melf_planar_frames d = *(const melf_planar_frames*)desc;
+        const int n = d.n;
+        const bool zero = d.b_offset == 0 && d.g_offset == 0 && d.r_offset == 0;
+        const bool in_range = d.H > 0 && d.W > 0 && d.row_pitch >= 0 && d.row_pitch <= INT32_MAX;
+        const int64_t span = in_range ? plane_span(d.H, d.row_pitch, d.W, 1, 1) : 0;
+        d.b_offset = 0; d.g_offset = span; d.r_offset = 2 * span;
+        d.frame_stride = INT64_MAX & ~(int64_t)15;
+        d.n = n > 0 ? 1 : n;
+        if (const char* msg = check_planes(base, &d, &pl->batch)) return msg;
+        if (!zero) return PLANE_LIST_PLANAR_OFFSETS;
+        pl->nplanes = 3;
+        for (int k = 0; k < 3; ++k) { pl->offset[k] = (uint64_t)(k * span); pl->extent[k] = (uint64_t)span; }
+        pl->batch.n = n;
+        break;
+    }
+    default: return PLANE_LIST_UNKNOWN_FAMILY;
+    }
+    if (nplanes != pl->nplanes) return PLANE_LIST_NPLANES;
+    return nullptr;
 }
 
 }  // namespace melf

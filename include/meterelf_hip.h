@@ -594,6 +594,75 @@ int melf_process_plane_list_dev(melf_ctx* ctx, int family, const void* desc, con
 int melf_process_plane_list(melf_ctx* ctx, int family, const void* desc, const void* const* planes_host, int nplanes,
                             melf_result* out_host);
 
+/* ---- the same path for frames that are stored ROTATED or MIRRORED: the raw frames of a camera mounted on its side (V4L2 buffers,
+ * decoder surfaces, tensors), phone and IP-camera video whose rotation sits in the container's display matrix while the hardware
+ * decoder leaves NV12 unrotated ----
+ * The reference reads every frame through cv2.imread, which applies the EXIF orientation tag: what it reads is upright.  These
+ * entry points take the stored batch and the orientation and read the frame a viewer shows, without forming it.
+ * Orientation codes are the EXIF / TIFF tag 0x0112 values.  With S the stored frame of H rows x W columns and O the oriented frame
+ * of H' x W' -- the frame a viewer shows and cv2.imread returns --:
+ *     code  name                     H' x W'   O[y][x] =
+ *     1     MELF_ORIENT_NORMAL       H x W     S[y][x]
+ *     2     MELF_ORIENT_MIRROR       H x W     S[y][W-1-x]
+ *     3     MELF_ORIENT_ROT180       H x W     S[H-1-y][W-1-x]
+ *     4     MELF_ORIENT_FLIP         H x W     S[H-1-y][x]
+ *     5     MELF_ORIENT_TRANSPOSE    W x H     S[x][y]
+ *     6     MELF_ORIENT_ROT90CW      W x H     S[H-1-x][y]
+ *     7     MELF_ORIENT_TRANSVERSE   W x H     S[H-1-x][W-1-y]
+ *     8     MELF_ORIENT_ROT90CCW     W x H     S[x][W-1-y]
+ * A video stream's "rotate by 90 / 180 / 270 degrees clockwise to display" is 6 / 3 / 8.
+ * For a layout with chroma planes every plane is oriented by the same formula on its own sample grid: for a chroma plane of
+ * (H >> sub_y) x (W >> sub_x) samples the formula applies with those dimensions, and an interleaved U/V pair moves as one element.
+ * Because H and W are whole chroma blocks this is the same as orienting the converted BGR frame -- for codes 2-4 under any
+ * subsampling, for codes 5-8 where sub_x == sub_y.
+ *     family       MELF_LIST_*: which descriptor `desc` points to
+ *     desc         that family's descriptor of the STORED batch: one base pointer, its own frame_stride, every rule of the family's
+ *                  check unchanged
+ *     orientation  1 .. 8
+ * meter_rect is taken on the ORIENTED frame, with the same clamping; H' x W' must hold the crop and the template exactly as the
+ * family's call requires of an upright frame, with the same error otherwise.
+ * The records are byte-identical to the family's own melf_process_* / melf_process_*_dev call on a contiguous batch holding the
+ * oriented frames O in the same layout.  Neither O nor any other whole frame is formed: only the source samples of the crop are
+ * read -- the crop rounded out to chroma blocks exactly as the family's staging plan rounds it --, and no load reaches outside
+ * [base, base + (n - 1) * frame_stride + one frame's extent).
+ * Families: MELF_LIST_FRAMES, MELF_LIST_PACKED32, MELF_LIST_PLANES and MELF_LIST_YUV take all eight codes; MELF_LIST_YUV_PLANAR all
+ * eight when sub_x == sub_y and 1-4 otherwise; MELF_LIST_YUV16 all eight when sub_y == 1 and 1-4 otherwise.  MELF_LIST_YUV422 and
+ * MELF_LIST_YUV422_10 return MELF_ERR_INVALID: a mirrored macropixel is not a permutation of equal-sized elements.  Also
+ * MELF_ERR_INVALID before anything is launched or copied, melf_last_error saying which: an orientation outside 1 .. 8, a NULL
+ * pointer, an unknown family.  n == 0 passes.
+ * How: code 1 calls the family's in-place entry point and nothing else.  For codes 2-8 one kernel (k_orient_tiles, timed as
+ * MELF_K_GATHER) writes the oriented crop of every frame into the lane's staged batch -- the same staged frame, rectangle and layout
+ * the family's staging plan gives for an upright frame of the oriented geometry --, which the unchanged kernels then read exactly as
+ * they read a frame list's.  A workgroup takes a tile of 64 x 64 elements (a Y, chroma, B / G / R sample; an interleaved pair; a
+ * 3- or 4-byte pixel; a 16-bit sample or pair), loads its source rectangle along the stored rows into LDS and writes the
+ * destination rows from there in aligned 16-byte pieces.  The price is one read and one write of the crop's bytes only (187 500 of a
+ * 640 x 480 BGR frame's 921 600), against the read and write of every whole frame that torch.rot90(frames, ..).contiguous() or
+ * flip costs a caller before.  Lanes, caller streams, melf_ctx_set_frames_resident, ordering, chunks of 1024 frames and the NULL
+ * d_results / out_host semantics are exactly melf_process_frame_list_dev's.  The host call packs the same staged frames on the host
+ * pool from the same address functions: only the crop crosses PCIe.
+ * Measured on one MI355X, 1024-frame config-3 steps (profiles/oriented/oriented_rate.txt), BGR under 3, BGR / BGRA / NV12 / P010
+ * under 6: the stored batch (b) takes 0.3353 / 0.3316 / 0.3551 / 0.2866 / 0.3269 ms a step, 1.43 / 1.41 / 1.44 / 1.21 / 1.28 times the
+ * upright batch in place (a); torch.rot90 / flip of the whole stored frames and then the batch read (c) takes 6.8 / 11.3 / 11.9 / 8.5 /
+ * 8.5 times the step of (b); k_orient_tiles takes 0.109 / 0.106 / 0.101 / 0.056 / 0.084 ms a launch, 1.30 / 1.26 / 0.95 / 1.28 / 1.17
+ * times the plain-copy kernel of a frame list (k_gather_rows) moving the same bytes in the same run.
+ * Out of scope: oriented frame lists and plane lists; the two packed 4:2:2 families; re-describing 4:2:2 as 4:4:0 (and back) under
+ * transposition; the JPEG entry points (melf_jpeg_probe still reports a file whose EXIF orientation is > 1 unsupported, and such a
+ * file takes the host branch); melf_process_stream_dev and the fused full-frame mask. */
+enum { MELF_ORIENT_NORMAL = 1, MELF_ORIENT_MIRROR = 2, MELF_ORIENT_ROT180 = 3, MELF_ORIENT_FLIP = 4, MELF_ORIENT_TRANSPOSE = 5,
+       MELF_ORIENT_ROT90CW = 6, MELF_ORIENT_TRANSVERSE = 7, MELF_ORIENT_ROT90CCW = 8 };
+int melf_process_oriented_dev(melf_ctx* ctx, int family, const void* desc, int orientation, const void* d_frames, void* d_results,
+                              melf_result* out_host, void* stream);
+int melf_process_oriented(melf_ctx* ctx, int family, const void* desc, int orientation, const void* frames_host, melf_result* out_host);
+/* Stage entry point (parity tests, debug view): the orientation alone.  The same kernel with the rectangle set to the whole oriented
+ * frame, for all eight codes; out receives n oriented frames of H' x W' in the family's layout at TIGHT pitches, one after the
+ * other, out_bytes >= n * one such frame.  The tight frame per family -- MELF_LIST_FRAMES: H' rows of W' pixels of 3 or 4 bytes;
+ * MELF_LIST_PACKED32: H' rows of W' words; MELF_LIST_PLANES: the B, the G and the R plane, H' x W' bytes each, in that order whatever
+ * the stored order; the YUV families: the Y plane, H' rows of W' samples, then for an interleaved layout the one chroma plane of
+ * (H' >> sub_y) rows of (W' >> sub_x) pairs in the stored order of a pair, for a planar layout the U plane and then the V plane,
+ * (H' >> sub_y) x (W' >> sub_x) samples each, whatever the stored order; samples of 2 bytes for MELF_LIST_YUV16. */
+int melf_orient_frames(melf_ctx* ctx, int family, const void* desc, int orientation, const void* frames_host, void* out_host,
+                       size_t out_bytes);
+
 /* ---- stage entry points (parity tests and roofline runs) ----------------- */
 
 /* convert_to_hls (meterelf/_utils.py:100-102): cvtColor(BGR2HLS_FULL) + uint8

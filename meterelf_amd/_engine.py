@@ -341,6 +341,44 @@ class MeterReader:
         return self._read_view(v0._replace(n=n), out, lambda: self.ctx.process_frame_list(layout, desc, ptrs),
                                lambda **kw: self.ctx.process_frame_list_dev(layout, desc, ptrs, **kw))
 
+    def read_oriented_frames(self, frames, layout: str, pixel_format: str, orientation, matrix=None, out=None):
+        """Frames that are stored rotated or mirrored -- the raw frames of a camera mounted on its side, video whose rotation sits
+        in the container's display matrix -- -> records, equal to the batch method's on the upright frames a viewer shows (what
+        cv2.imread makes of a file with that EXIF orientation), without the torch.rot90(frames, ..).contiguous() or flip that
+        would make them (melf_process_oriented*): one kernel writes the meter crop of every frame upright into a staged batch,
+        reading only the crop's samples.  frames: the STORED batch, in the shape the layout's own batch method documents; layout,
+        pixel_format and matrix resolve as in read_frame_list ('views', 'yuv', 'yuv_planar', 'yuv16', 'packed32', 'planar'; the
+        packed 4:2:2 layouts cannot be oriented in place).  orientation: the EXIF code 1 .. 8 or its name -- 'normal', 'mirror',
+        'rot180', 'flip', 'transpose', 'rot90cw', 'transverse', 'rot90ccw'; a stream's "rotate 90 / 180 / 270 degrees clockwise to
+        display" is 'rot90cw' / 'rot180' / 'rot90ccw'.  The meter_rect is taken on the upright frame.  numpy arrays / torch CPU
+        tensors take the host path, torch tensors on this reader's GPU are enqueued on torch.cuda.current_stream; out: as for the
+        batch methods.  ValueError: an unknown orientation, a layout or chroma subsampling that cannot be oriented (codes 5 .. 8
+        need sub_x == sub_y), a view that would have to copy."""
+        if layout not in self._LIST_VIEWS:
+            raise ValueError('layout %r is none of %s' % (layout, ', '.join(sorted(self._LIST_VIEWS))))
+        if layout in ('yuv422', 'yuv422_10'):
+            raise ValueError('layout %r cannot be oriented in place: a mirrored macropixel is not a permutation of equal-sized elements' % layout)
+        code = _hip.ORIENTATIONS.get(orientation.lower()) if isinstance(orientation, str) else orientation
+        if isinstance(code, bool) or not isinstance(code, (int, np.integer)) or not 1 <= code <= 8:
+            raise ValueError('orientation %r is none of 1 .. 8 or %s' % (orientation, ', '.join(_hip.ORIENTATIONS)))
+        code = int(code)
+        (view_name, default_matrix) = self._LIST_VIEWS[layout]
+        args = [pixel_format]
+        if default_matrix is not None:
+            args.append(matrix if matrix is not None or default_matrix == '' else default_matrix)
+        elif matrix is not None:
+            raise ValueError('layout %r takes no matrix' % layout)
+        v = getattr(_hip, view_name)(frames, *args)
+        if v.copied:
+            raise ValueError('the frames have a layout the %r descriptor cannot express (they would have to be copied)' % layout)
+        desc = v.descriptor() if hasattr(v, 'descriptor') else _hip.MelfFrames(v.pixel_format, v.n, v.H, v.W, v.row_pitch, v.frame_stride)
+        if code >= 5:
+            (sx, sy) = (getattr(desc, 'sub_x', 1), getattr(desc, 'sub_y', 1)) if layout in ('yuv_planar', 'yuv16') else (1, 1)
+            if sx != sy:
+                raise ValueError('orientation %r transposes the frame: %r chroma is not subsampled alike in both directions' % (orientation, pixel_format))
+        return self._read_view(v, out, lambda: self.ctx.process_oriented(layout, desc, code, v.ptr),
+                               lambda **kw: self.ctx.process_oriented_dev(layout, desc, code, v.ptr, **kw))
+
     _PLANE_LAYOUTS = ('yuv', 'yuv_planar', 'yuv16', 'planar')
 
     class _PlaneListView(NamedTuple):

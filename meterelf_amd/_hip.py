@@ -29,6 +29,8 @@ FRAME_ANGLE_UNDETERMINED = 3
 K_LPLANE, K_MATCH, K_DIALS, K_FUSED_MASK, K_HLS, K_JPEG_HUFF, K_JPEG_IDCT, K_JPEG_COLOR, K_STREAM_PROBE, K_GATHER, K_COUNT = range(11)
 # MELF_LIST_* of include/meterelf_hip.h: the family of a frame list's descriptor, by the name MeterReader.read_frame_list gives it
 LIST_FAMILIES = {'views': 0, 'yuv': 1, 'yuv422': 2, 'yuv_planar': 3, 'yuv16': 4, 'yuv422_10': 5, 'packed32': 6, 'planar': 7}
+# MELF_ORIENT_* of include/meterelf_hip.h (the EXIF / TIFF tag 0x0112 values), by the name MeterReader.read_oriented_frames takes
+ORIENTATIONS = {'normal': 1, 'mirror': 2, 'rot180': 3, 'flip': 4, 'transpose': 5, 'rot90cw': 6, 'transverse': 7, 'rot90ccw': 8}
 JPEG_OK, JPEG_UNSUPPORTED, JPEG_CORRUPT, JPEG_SIZE_MISMATCH, JPEG_UNREADABLE = 0, 1, 2, 3, 4
 FILES_IN_FLIGHT_MAX = 3   # MELF_FILES_IN_FLIGHT_MAX (include/meterelf_hip.h); tests compare with melf_jpeg_files_in_flight_max()
 
@@ -223,6 +225,7 @@ EXPORTS = [
     'melf_process_yuv422_10', 'melf_process_yuv422_10_dev', 'melf_yuv422_10_to_bgr',
     'melf_process_packed32', 'melf_process_packed32_dev', 'melf_packed32_to_bgr',
     'melf_process_frame_list', 'melf_process_frame_list_dev', 'melf_process_plane_list', 'melf_process_plane_list_dev',
+    'melf_process_oriented', 'melf_process_oriented_dev', 'melf_orient_frames',
     'melf_bgr2hls', 'melf_hls_inrange_close', 'melf_hls_inrange_close_dev', 'melf_match_ccoeff',
     'melf_read_dials', 'melf_aligned_average', 'melf_inrange', 'melf_ctx_fused_table_ties', 'melf_ctx_fused_variant', 'melf_ctx_set_frames_resident', 'melf_ctx_last_match', 'melf_ctx_last_dials', 'melf_match_layout_query', 'melf_match_gen_plan_query', 'melf_ctx_set_profiling', 'melf_ctx_timings', 'melf_kernel_name',
     'melf_jpeg_probe', 'melf_jpeg_probe_batch', 'melf_jpeg_decode_batch', 'melf_jpeg_clean_segment', 'melf_jpeg_process_batch',
@@ -287,6 +290,9 @@ def lib():
     L.melf_process_frame_list_dev.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     L.melf_process_plane_list.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
     L.melf_process_plane_list_dev.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp, vp]
+    L.melf_process_oriented.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp]
+    L.melf_process_oriented_dev.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
+    L.melf_orient_frames.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, C.c_size_t]
     if hasattr(L, 'melf_gather_frame_list_dev'):   # the diagnostic build only
         L.melf_gather_frame_list_dev.argtypes = [vp, C.c_int, vp, vp, vp, C.POINTER(C.c_size_t)]
     L.melf_process_stream_dev.argtypes = [vp, vp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, vp]
@@ -1410,6 +1416,31 @@ class Context:
         check(self._L.melf_process_plane_list_dev(self._h, family, C.byref(desc), self._plane_table(d_plane_ptrs, desc, nplanes), nplanes,
                                                   C.c_void_p(d_results_ptr) if d_results_ptr else None, _ptr(out) if want_host else None,
                                                   C.c_void_p(stream) if stream else None))
+        return out
+
+    # --- frames stored rotated or mirrored ---
+    def process_oriented(self, family, desc, orientation, frames_ptr):
+        """Host frames stored rotated or mirrored (melf_process_oriented) -> records.  family: LIST_FAMILIES' code or name; desc: the
+        family's descriptor of the STORED batch; orientation: ORIENTATIONS' code (1 .. 8) or name."""
+        out = np.zeros(max(desc.n, 0), RESULT_DTYPE)
+        check(self._L.melf_process_oriented(self._h, LIST_FAMILIES.get(family, family), C.byref(desc), ORIENTATIONS.get(orientation, orientation),
+                                            C.c_void_p(frames_ptr), _ptr(out)))
+        return out
+
+    def process_oriented_dev(self, family, desc, orientation, d_frames_ptr, d_results_ptr=None, want_host=True, stream=None):
+        """The same for a stored batch in HBM (melf_process_oriented_dev, as process_frames_dev).  Returns records when want_host."""
+        out = np.zeros(max(desc.n, 0), RESULT_DTYPE) if want_host else None
+        check(self._L.melf_process_oriented_dev(self._h, LIST_FAMILIES.get(family, family), C.byref(desc), ORIENTATIONS.get(orientation, orientation),
+                                                C.c_void_p(d_frames_ptr), C.c_void_p(d_results_ptr) if d_results_ptr else None,
+                                                _ptr(out) if want_host else None, C.c_void_p(stream) if stream else None))
+        return out
+
+    def orient_frames(self, family, desc, orientation, frames_ptr, out_bytes):
+        """The orientation alone (melf_orient_frames): host frames -> a uint8 array of out_bytes bytes holding desc.n oriented frames in
+        the family's layout at tight pitches (include/meterelf_hip.h states the tight frame per family)."""
+        out = np.zeros(out_bytes, np.uint8)
+        check(self._L.melf_orient_frames(self._h, LIST_FAMILIES.get(family, family), C.byref(desc), ORIENTATIONS.get(orientation, orientation),
+                                         C.c_void_p(frames_ptr), _ptr(out), out_bytes))
         return out
 
     def gather_frame_list_dev(self, family, desc, d_frame_ptrs, stream=None):

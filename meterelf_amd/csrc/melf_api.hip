@@ -24,6 +24,7 @@
 #include "melf_device.h"
 #include "melf_frame_checks.h"
 #include "melf_internal.h"
+#include "melf_orient_addr.h"
 #include "melf_stage_plan.h"
 #include "melf_threads.h"
 
@@ -1640,14 +1641,22 @@ static const int LIST_CHUNK = 1024;
 // read: the reading path on the staged batch (melf_process_frame_list_dev); otherwise the gather alone (the diagnostic build's
 // melf_gather_frame_list_dev), *bytes_moved: what its kernels read and wrote.  pl NULL: d_frames holds one pointer per frame
 // (k_gather_rows); otherwise pl->nplanes pointers per frame, frame-major, b the canonical batch of pl (melf_process_plane_list_dev:
-// k_plane_rows).
+// k_plane_rows).  op (melf_process_oriented_dev): no list at all -- d_frames is the base of ONE stored batch b, frame i at base + i *
+// b.frame_stride, its frames rotated or mirrored; the staged batch is op's (the plan of the oriented geometry) and k_orient_tiles
+// writes it, with no pointer table.  Everything else -- the lane, the ordering, the chunks, the records -- is the same flow.
 static int frame_list_dev(melf_ctx* c, const FrameBatch& b, const void* const* d_frames, void* d_results, melf_result* out_host, void* stream_,
-                          bool read, size_t* bytes_moved, const PlaneList* pl = nullptr)
+                          bool read, size_t* bytes_moved, const PlaneList* pl = nullptr, const orient::Plan* op = nullptr)
 {
     HIP_TRY(hipSetDevice(c->device));
-    Crop cr;
-    if (int rc = meter_crop(c->P, nullptr, b.H, b.W, &cr)) return rc;
-    const StagePlan sp = stage_plan(b, cr);
+    StagePlan plan;
+    if (op) {
+        plan = op->sp;
+    } else {
+        Crop cr;
+        if (int rc = meter_crop(c->P, nullptr, b.H, b.W, &cr)) return rc;
+        plan = stage_plan(b, cr);
+    }
+    const StagePlan& sp = plan;
     const int n = b.n;
     const size_t per_frame_ptrs = pl ? (size_t)pl->nplanes : 1;   // table entries per frame
     PlaneSplit split = {};
@@ -1680,9 +1689,9 @@ static int frame_list_dev(melf_ctx* c, const FrameBatch& b, const void* const* d
     const size_t stride = sp.staged.frame_stride;
     const size_t cap = (size_t)(n < LIST_CHUNK ? n : LIST_CHUNK);
     if (int rc = grow(&c->d_list_stage[lane], &c->list_stage_cap[lane], cap * stride)) return rc;
-    const size_t tab_cap = cap * per_frame_ptrs;
+    const size_t tab_cap = op ? 0 : cap * per_frame_ptrs;
     if (int rc = grow(&c->d_list_tab[lane], &c->list_tab_cap[lane], tab_cap)) return rc;
-    if (!c->ev_list_tab[lane]) HIP_TRY(hipEventCreateWithFlags(&c->ev_list_tab[lane], hipEventDisableTiming));
+    if (!op && !c->ev_list_tab[lane]) HIP_TRY(hipEventCreateWithFlags(&c->ev_list_tab[lane], hipEventDisableTiming));
     if (c->h_list_tab_cap[lane] < tab_cap) {
         if (c->h_list_tab[lane]) { HIP_TRY(hipEventSynchronize(c->ev_list_tab[lane])); HIP_TRY(hipHostFree(c->h_list_tab[lane])); }
         c->h_list_tab[lane] = nullptr;
@@ -1693,10 +1702,12 @@ static int frame_list_dev(melf_ctx* c, const FrameBatch& b, const void* const* d
     FrameBatch staged = sp.staged;
     for (int f0 = 0; f0 < n; f0 += LIST_CHUNK) {
         const int m = n - f0 < LIST_CHUNK ? n - f0 : LIST_CHUNK;
-        HIP_TRY(hipEventSynchronize(c->ev_list_tab[lane]));   // the previous upload from the pinned table has finished
-        memcpy(c->h_list_tab[lane], d_frames + (size_t)f0 * per_frame_ptrs, (size_t)m * per_frame_ptrs * sizeof(void*));
-        HIP_TRY(hipMemcpyAsync(c->d_list_tab[lane], c->h_list_tab[lane], (size_t)m * per_frame_ptrs * sizeof(void*), hipMemcpyHostToDevice, ws));
-        HIP_TRY(hipEventRecord(c->ev_list_tab[lane], ws));
+        if (!op) {
+            HIP_TRY(hipEventSynchronize(c->ev_list_tab[lane]));   // the previous upload from the pinned table has finished
+            memcpy(c->h_list_tab[lane], d_frames + (size_t)f0 * per_frame_ptrs, (size_t)m * per_frame_ptrs * sizeof(void*));
+            HIP_TRY(hipMemcpyAsync(c->d_list_tab[lane], c->h_list_tab[lane], (size_t)m * per_frame_ptrs * sizeof(void*), hipMemcpyHostToDevice, ws));
+            HIP_TRY(hipEventRecord(c->ev_list_tab[lane], ws));
+        }
         if (resident && f0 == 0) {
             if (!c->ev_call[lane]) HIP_TRY(hipEventCreateWithFlags(&c->ev_call[lane], hipEventDisableTiming));
             HIP_TRY(hipEventRecord(c->ev_call[lane], st));
@@ -1704,7 +1715,9 @@ static int frame_list_dev(melf_ctx* c, const FrameBatch& b, const void* const* d
         }
         {
             KernelTimer t(c, MELF_K_GATHER, ws);
-            if (pl)
+            if (op)
+                launch_orient_tiles((const uint8_t*)d_frames + (size_t)f0 * b.frame_stride, b.frame_stride, m, op->runs, c->d_list_stage[lane], stride, ws);
+            else if (pl)
                 launch_plane_rows(c->d_list_tab[lane], pl->nplanes, m, sp.runs, split, c->d_list_stage[lane], stride, ws);
             else
                 launch_gather_rows(c->d_list_tab[lane], m, sp.runs, c->d_list_stage[lane], stride, b.lay.extent, ws);
@@ -1805,6 +1818,111 @@ extern "C" int melf_process_plane_list(melf_ctx* c, int family, const void* desc
                 memcpy(staged + (size_t)run.dst_off + (size_t)y * run.dst_pitch, plane + (size_t)y * run.src_pitch, run.row_bytes);
         }
     });
+}
+
+// ------------------------------------------------------- oriented frames ----
+// One batch whose frames are stored rotated or mirrored (EXIF orientations 1-8): the family's descriptor of the STORED batch and
+// the orientation.  Code 1 is the family's own call.  Otherwise the plan is the family's plan of the ORIENTED geometry
+// (melf_orient_addr.h: oriented_plan), k_orient_tiles writes its staged frames from the stored ones -- the frame lists' flow with
+// another kernel in the gather's place --, and the host call packs the same staged frames element by element (elem_src_off).
+
+// The argument checks of the three entry points: the batch of the stored frames in *b (n == 0 passes whatever the pointer)
+static int oriented_batch_check(const melf_ctx* c, int family, const void* desc, int orientation, const void* frames, FrameBatch* b)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    if (orientation < MELF_ORIENT_NORMAL || orientation > MELF_ORIENT_ROT90CCW) return fail(MELF_ERR_INVALID, orient::ORIENT_RANGE);
+    const char* msg = nullptr;
+    switch (family) {
+    case MELF_LIST_FRAMES: msg = check_frames(frames, (const melf_frames*)desc, b); break;
+    case MELF_LIST_YUV: msg = check_yuv(frames, (const melf_yuv_frames*)desc, b); break;
+    case MELF_LIST_YUV_PLANAR: msg = check_yuv_planar(frames, (const melf_yuv_planar_frames*)desc, b); break;
+    case MELF_LIST_YUV16: msg = check_yuv16(frames, (const melf_yuv16_frames*)desc, b); break;
+    case MELF_LIST_PACKED32: msg = check_packed32(frames, (const melf_packed32_frames*)desc, b); break;
+    case MELF_LIST_PLANES: msg = check_planes(frames, (const melf_planar_frames*)desc, b); break;
+    case MELF_LIST_YUV422: case MELF_LIST_YUV422_10: return fail(MELF_ERR_INVALID, orient::ORIENT_PACKED422);
+    default: return fail(MELF_ERR_INVALID, "unknown family of the oriented frames (accepted: MELF_LIST_FRAMES, MELF_LIST_YUV, MELF_LIST_YUV_PLANAR, MELF_LIST_YUV16, MELF_LIST_PACKED32, MELF_LIST_PLANES)");
+    }
+    if (msg) return fail(MELF_ERR_INVALID, msg);
+    if (const char* why = orient::orientable(*b, orientation)) return fail(MELF_ERR_INVALID, why);
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_process_oriented_dev(melf_ctx* c, int family, const void* desc, int orientation, const void* d_frames, void* d_results,
+                                         melf_result* out_host, void* stream_)
+{
+    FrameBatch b;
+    if (int rc = oriented_batch_check(c, family, desc, orientation, d_frames, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    if (orientation == MELF_ORIENT_NORMAL) return batch_dev(c, d_frames, b, d_results, out_host, stream_);
+    Crop cr;
+    if (int rc = meter_crop(c->P, nullptr, orient::oriented_h(b, orientation), orient::oriented_w(b, orientation), &cr)) return rc;
+    const orient::Plan op = orient::oriented_plan(b, orientation, cr);
+    return frame_list_dev(c, b, (const void* const*)d_frames, d_results, out_host, stream_, true, nullptr, nullptr, &op);
+}
+
+extern "C" int melf_process_oriented(melf_ctx* c, int family, const void* desc, int orientation, const void* frames_host, melf_result* out_host)
+{
+    FrameBatch b;
+    if (int rc = oriented_batch_check(c, family, desc, orientation, frames_host, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    if (orientation == MELF_ORIENT_NORMAL) return host_batch(c, frames_host, b, out_host);
+    if (!out_host) return fail(MELF_ERR_INVALID, "out_host is NULL");
+    Crop cr;
+    if (int rc = meter_crop(c->P, nullptr, orient::oriented_h(b, orientation), orient::oriented_w(b, orientation), &cr)) return rc;
+    const orient::Plan op = orient::oriented_plan(b, orientation, cr);
+    return stage_host_frames(c, Strided{(const uint8_t*)frames_host, b.frame_stride}, b.n, op.sp, out_host, [=](const uint8_t* frame, uint8_t* staged, int item) {
+        int k0, k1;
+        uint32_t r0, r1;
+        stage_item(op.sp, item, &k0, &k1, &r0, &r1);
+        for (int k = k0; k < k1; ++k) {
+            const orient::Run& run = op.runs.run[k];
+            for (uint32_t y = r0; y < r1; ++y) {
+                uint8_t* row = staged + (size_t)run.dst_off + (size_t)y * run.dst_pitch;
+                for (uint32_t x = 0; x < run.cols; ++x)
+                    memcpy(row + (size_t)x * run.eb, frame + orient::elem_src_off(run, orientation, y, x), run.eb);
+            }
+        }
+    });
+}
+
+// Stage entry point: the kernel alone, the rectangle the whole oriented frame; the staged frames come back and their rows are packed
+// tight on the host, run after run
+extern "C" int melf_orient_frames(melf_ctx* c, int family, const void* desc, int orientation, const void* frames_host, void* out_host, size_t out_bytes)
+{
+    FrameBatch b;
+    if (int rc = oriented_batch_check(c, family, desc, orientation, frames_host, &b)) return rc;
+    if (b.n == 0) return MELF_SUCCESS;
+    if (!out_host) return fail(MELF_ERR_INVALID, "out_host is NULL");
+    const int H2 = orient::oriented_h(b, orientation), W2 = orient::oriented_w(b, orientation);
+    const int whole[4] = {0, 0, W2, H2};
+    Crop cr;
+    clamp_crop(whole, H2, W2, &cr);
+    const orient::Plan op = orient::oriented_plan(b, orientation, cr);
+    size_t tight = 0;
+    for (int k = 0; k < op.sp.runs.count; ++k) tight += (size_t)op.sp.runs.run[k].rows * op.sp.runs.run[k].row_bytes;
+    if (out_bytes / tight < (size_t)b.n) return fail(MELF_ERR_INVALID, "out_bytes smaller than n tight oriented frames");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t in_bytes = (size_t)(b.n - 1) * b.frame_stride + b.lay.extent, stride = op.sp.staged.frame_stride;
+    const int cap = b.n < LIST_CHUNK ? b.n : LIST_CHUNK;
+    if (int rc = grow(&c->d_stage_in, &c->stage_in_cap, in_bytes)) return rc;
+    if (int rc = grow(&c->d_stage_out, &c->stage_out_cap, (size_t)cap * stride)) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_stage_in, frames_host, in_bytes, hipMemcpyHostToDevice, c->stream));
+    std::vector<uint8_t> staged((size_t)cap * stride);
+    uint8_t* out = (uint8_t*)out_host;
+    for (int f0 = 0; f0 < b.n; f0 += LIST_CHUNK) {
+        const int m = b.n - f0 < LIST_CHUNK ? b.n - f0 : LIST_CHUNK;
+        launch_orient_tiles(c->d_stage_in + (size_t)f0 * b.frame_stride, b.frame_stride, m, op.runs, c->d_stage_out, stride, c->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(staged.data(), c->d_stage_out, (size_t)m * stride, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (int i = 0; i < m; ++i)
+            for (int k = 0; k < op.sp.runs.count; ++k) {
+                const RowRun& run = op.sp.runs.run[k];
+                for (uint32_t y = 0; y < run.rows; ++y, out += run.row_bytes)
+                    memcpy(out, staged.data() + (size_t)i * stride + (size_t)run.dst_off + (size_t)y * run.dst_pitch, run.row_bytes);
+            }
+    }
+    return MELF_SUCCESS;
 }
 
 #ifdef MELF_DIAG   // measurement aid of the diagnostic build (tools/frame_list_rate.py): not an entry point of the product library

@@ -206,6 +206,13 @@ struct PlaneSplit;
 void launch_plane_rows(const void* const* d_planes, int nplanes, int n, const RowRuns& runs, const PlaneSplit& split, uint8_t* d_staged,
                        size_t staged_stride, hipStream_t stream);
 
+// ---- k_orient.hip: frames stored rotated or mirrored (melf_process_oriented_dev, melf_orient_frames) ----
+// Writes the runs of an oriented plan (melf_orient_addr.h: orient::Runs) of each of the n stored frames d_frames + i * frame_stride
+// upright into the staged frame d_staged + i * staged_stride.  n <= 65535.
+namespace orient { struct Runs; }
+void launch_orient_tiles(const void* d_frames, size_t frame_stride, int n, const orient::Runs& runs, uint8_t* d_staged, size_t staged_stride,
+                         hipStream_t stream);
+
 // ---- calibration stage kernels ------------------------------------------------
 void launch_aligned_average(const uint8_t* d_frames, int n, size_t frame_stride, int row_stride, int x0, int y0, int rows,
                             int cols, const int32_t* d_mx, const int32_t* d_my, int ax, int ay, uint8_t* d_out,

@@ -646,8 +646,8 @@ int melf_process_plane_list(melf_ctx* ctx, int family, const void* desc, const v
  * 8.5 times the step of (b); k_orient_tiles takes 0.109 / 0.106 / 0.101 / 0.056 / 0.084 ms a launch, 1.30 / 1.26 / 0.95 / 1.28 / 1.17
  * times the plain-copy kernel of a frame list (k_gather_rows) moving the same bytes in the same run.
  * Out of scope: oriented frame lists and plane lists; the two packed 4:2:2 families; re-describing 4:2:2 as 4:4:0 (and back) under
- * transposition; the JPEG entry points (melf_jpeg_probe still reports a file whose EXIF orientation is > 1 unsupported, and such a
- * file takes the host branch); melf_process_stream_dev and the fused full-frame mask. */
+ * transposition; melf_process_stream_dev and the fused full-frame mask.  (JPEG FILES that carry an EXIF orientation are decoded
+ * upright by the JPEG entry points themselves once melf_ctx_set_jpeg_orientation is on: see "JPEG decode", below.) */
 enum { MELF_ORIENT_NORMAL = 1, MELF_ORIENT_MIRROR = 2, MELF_ORIENT_ROT180 = 3, MELF_ORIENT_FLIP = 4, MELF_ORIENT_TRANSPOSE = 5,
        MELF_ORIENT_ROT90CW = 6, MELF_ORIENT_TRANSVERSE = 7, MELF_ORIENT_ROT90CCW = 8 };
 int melf_process_oriented_dev(melf_ctx* ctx, int family, const void* desc, int orientation, const void* d_frames, void* d_results,
@@ -768,6 +768,43 @@ int melf_jpeg_probe(const uint8_t* data, size_t size, int32_t* H, int32_t* W, in
 /* The same check for n files at once (one call instead of n from a scripting host). */
 int melf_jpeg_probe_batch(const uint8_t* const* data, const size_t* sizes, int n, int32_t* H, int32_t* W,
                           int32_t* supported);
+
+/* ---- JPEG files with an EXIF orientation (tag 0x0112 in IFD0 of the first Exif APP1 segment): a camera mounted on its side, a phone ----
+ * cv2.imread applies the tag, so the reference reads such a file upright.  melf_jpeg_probe and melf_jpeg_probe_batch report a file
+ * whose tag is 2..8 unsupported (reason "EXIF orientation ..."), and by default every decode call below gives it status 1 for the
+ * caller's host decoder to decode and rotate; none of that changes.  melf_ctx_set_jpeg_orientation(ctx, 1) makes melf_jpeg_decode_batch,
+ * melf_jpeg_process_batch, melf_jpeg_process_files and melf_jpeg_process_files_begin / _end of that context take such a file, if the
+ * decoder takes it otherwise.  Off at context creation; with it off every JPEG entry point behaves exactly as before, status codes
+ * included.  Not while a _begin call is in flight.
+ * Semantics, bit for bit: with S the frame libjpeg(-turbo) decodes from the file -- ISLOW IDCT, fancy upsampling in STORED geometry
+ * (the chroma filter runs along the stored axes whatever the code), libjpeg's colour tables, exactly as for an upright file -- the
+ * frame produced is O[y][x] of the orientation table above ("stored ROTATED or MIRRORED"): decode first, permute afterwards, which is
+ * what cv2.imread and Pillow's exif_transpose do.  The caller's H and W, and H_used / W_used, are UPRIGHT sizes throughout: a file of
+ * stored size h x w counts as w x h under codes 5-8, and a file whose upright size is not H x W gets MELF_JPEG_SIZE_MISMATCH.  Upright
+ * and oriented files, and files of different codes, may share one call; frames and records come back in the caller's order.
+ * How: the entropy decoder, the IDCT and the chroma filter never see the orientation.  The files of a call are decoded code by code
+ * (scheduling only), each code on its own window of the stored frame -- the meter_rect taken back through the code, grown by one MCU
+ * on every side, aligned to 16 and clamped (melf_jpeg_orient_addr.h; for code 1 the window it always was) -- and one kernel
+ * (k_jpeg_color_exif, timed as MELF_K_JPEG_COLOR) converts a 64 x 64 tile of that window along the stored rows, parks it in LDS and
+ * writes the tile's rows of the upright frame.  O is never formed outside the window.  A call without an oriented file launches
+ * exactly what it launches with the switch off.
+ * Measured on one MI355X, 1024-file config-3 calls of melf_jpeg_process_batch (profiles/jpeg_orient/jpeg_orient_rate.txt): the
+ * fixture's content stored under orientation 6 / 3 takes 3.21 / 3.36 ms a call, 0.975 / 1.018 times the same content in upright files
+ * (3.30 ms; quality 95, 68 KB a file), where the host branch such files took before (Pillow decode + exif_transpose on 8 threads,
+ * then the batch read) takes 714 / 685 ms: 222 / 204 times as long.  The colour stage takes 0.815 / 0.803 ms a call against 0.193 ms
+ * for upright 4:2:0 files.  Upright files, this library against the one before the switch existed, same lease: 1.962 / 1.981 against
+ * 1.981 / 1.976 ms a call.
+ * Out of scope: a tag anywhere but IFD0 of the first Exif APP1 (a second Exif block that asks for a rotation sends the file to the
+ * host); progressive and multi-scan files, which stay unsupported with or without a tag; a 4:2:0 fast path for oriented files. */
+/* The header check that takes the tag: H and W are the STORED size, *orientation is 1..8 (1 when the tag is absent, unreadable or
+ * outside 1..8, which Pillow and cv2 leave alone too), *supported is what melf_jpeg_probe would answer if the file had no tag.  The
+ * upright size is W x H for codes 5-8. */
+int melf_jpeg_probe_oriented(const uint8_t* data, size_t size, int32_t* H, int32_t* W, int32_t* orientation, int32_t* supported);
+/* The same for n files at once (MeterReader.read_jpeg_files groups a list by upright size with it). */
+int melf_jpeg_probe_oriented_batch(const uint8_t* const* data, const size_t* sizes, int n, int32_t* H, int32_t* W, int32_t* orientation,
+                                   int32_t* supported);
+int melf_ctx_set_jpeg_orientation(melf_ctx* ctx, int on);
+int melf_ctx_get_jpeg_orientation(melf_ctx* ctx, int* on);
 
 /* Decodes n files of H x W pixels.  out: n*H*W*3 bytes, on the host (out_on_device = 0) or in HBM.
  * Synchronises the context's stream. */

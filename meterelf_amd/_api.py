@@ -21,7 +21,10 @@ device gets its own context from it.  With one device nothing changes (no thread
 cv2.imread of the reference (meterelf/_image.py:49): baseline JPEG files are read (on threads, inside the
 library) and decoded on the GPU (METERELF_DECODE=gpu, the default; bit-identical to libjpeg's defaults); any other file, and
 everything when METERELF_DECODE=host, is decoded on the host by Pillow on a small thread pool
-(METERELF_DECODE_THREADS, default min(8, cpu count); Pillow releases the GIL).
+(METERELF_DECODE_THREADS, default min(8, cpu count); Pillow releases the GIL).  cv2.imread applies the EXIF orientation tag: a
+JPEG file that carries one (a camera mounted on its side, a phone) is decoded on the GPU too and comes out upright, byte for byte
+the frame the host branch rotates (the readers are made with MeterReader's jpeg_orientation switch on);
+METERELF_JPEG_ORIENT=host sends such files through the host branch instead, as before the GPU took them.
 """
 import collections
 import hashlib
@@ -64,9 +67,23 @@ _ENV_IN_KEY = ('MELF_MATCH', 'MELF_MATCH_LAYOUT', 'MELF_GEN_SHAPE', 'MELF_FORCE_
                'MELF_IO_THREADS', 'MELF_HOST_THREADS', 'MELF_LIB_PATH')
 
 
+def _jpeg_orientation_on_gpu() -> bool:
+    """JPEG files with an EXIF orientation are decoded upright on the GPU; METERELF_JPEG_ORIENT=host leaves them to the host branch."""
+    return os.getenv('METERELF_JPEG_ORIENT', 'gpu') != 'host'
+
+
 def _reader_key(params, blob, device: int) -> bytes:
     env = ';'.join('%s=%s' % (k, os.environ[k]) for k in _ENV_IN_KEY if k in os.environ)
-    return hashlib.sha1(blob.tobytes() + repr(list(params.dial_names)).encode() + b'|dev%d|' % device + env.encode()).digest()
+    orient = b'|orient%d|' % _jpeg_orientation_on_gpu()   # a reader keeps the setting it was made with
+    return hashlib.sha1(blob.tobytes() + repr(list(params.dial_names)).encode() + b'|dev%d|' % device + orient + env.encode()).digest()
+
+
+def _with_jpeg_orientation(reader):
+    """Turns a new reader's switch on (MeterReader.set_jpeg_orientation) unless the host branch is asked for; a reader from the
+    cache has it already (the setting is part of its key)."""
+    if _jpeg_orientation_on_gpu() and hasattr(reader, 'set_jpeg_orientation') and not getattr(reader, 'jpeg_orientation', False):
+        reader.set_jpeg_orientation(True)
+    return reader
 
 
 def _acquire_reader(params, device: int = 0) -> MeterReader:
@@ -75,7 +92,7 @@ def _acquire_reader(params, device: int = 0) -> MeterReader:
     with _idle_lock:
         reader = _idle_readers.pop(key, None)
     if reader is None:
-        reader = MeterReader(params, device=device, blob=blob)
+        reader = _with_jpeg_orientation(MeterReader(params, device=device, blob=blob))
     reader._cache_key = key
     return reader
 
@@ -102,7 +119,7 @@ def _acquire_readers_bcast(params, devices: List[int]) -> Dict[int, MeterReader]
     if len(missing) == 1:     # one context to make: a plain upload (a communicator for a broadcast to oneself costs more than it moves)
         w = missing[0]
         try:
-            r = MeterReader(params, device=devices[w], blob=blob)
+            r = _with_jpeg_orientation(MeterReader(params, device=devices[w], blob=blob))
         except Exception:
             for r2 in out.values():
                 _release_reader(r2)
@@ -118,7 +135,7 @@ def _acquire_readers_bcast(params, devices: List[int]) -> Dict[int, MeterReader]
             return {}
         try:
             for (w, ctx) in zip(missing, ctxs):
-                r = MeterReader(params, device=devices[w], blob=blob, ctx=ctx)
+                r = _with_jpeg_orientation(MeterReader(params, device=devices[w], blob=blob, ctx=ctx))
                 r._cache_key = _reader_key(params, blob, devices[w])
                 out[w] = r
         except Exception:     # nothing of a half-made set survives: the workers start from scratch
@@ -285,7 +302,7 @@ def _process_chunks(params, chunks: Iterator[List[str]], device: int, gpu_decode
         chunk = next(chunks, None)
         while chunk is not None:
             if reader is None:
-                reader = _acquire_reader(params, device) if MeterReader is _REAL_READER else MeterReader(params, device=device)
+                reader = _acquire_reader(params, device) if MeterReader is _REAL_READER else _with_jpeg_orientation(MeterReader(params, device=device))
             assert len(reader.dial_names) == 4  # meterelf/_reading.py:166
             pipelined = gpu_decode and batch > 1 and hasattr(reader, 'read_jpeg_paths_begin')
             errors: Dict[int, ImageProcessingError] = {}

@@ -124,7 +124,10 @@ def records_to_items(records: np.ndarray, ok, dial_names: List[str], filenames: 
 
 
 class MeterReader:
-    def __init__(self, params: Params, device: int = 0, blob: Optional[np.ndarray] = None, ctx: Optional['_hip.Context'] = None) -> None:
+    def __init__(self, params: Params, device: int = 0, blob: Optional[np.ndarray] = None, ctx: Optional['_hip.Context'] = None,
+                 jpeg_orientation: bool = False) -> None:
+        """jpeg_orientation: the read_jpeg_* methods decode JPEG files that carry an EXIF orientation 2..8 on the GPU, upright (as
+        cv2.imread returns them), instead of leaving them to the caller's host decoder (None / ok false), which is the default."""
         self.params = params
         self.device = device
         self.dial_names = params.dial_names
@@ -133,6 +136,14 @@ class MeterReader:
         self._crop_ctx: Dict[Tuple[int, int], _hip.Context] = {}
         self._begun: list = []      # read_jpeg_paths_begin: path lists in flight, oldest first
         self._collected: list = []  # their results taken out of the library early (drain_jpeg_paths), oldest first
+        self.jpeg_orientation = False
+        if jpeg_orientation:
+            self.set_jpeg_orientation(True)
+
+    def set_jpeg_orientation(self, on: bool) -> None:
+        """The switch of the constructor's jpeg_orientation, on a reader with nothing in flight (melf_ctx_set_jpeg_orientation)."""
+        self.ctx.set_jpeg_orientation(on)
+        self.jpeg_orientation = bool(on)
 
     def close(self) -> None:
         self.ctx.close()
@@ -520,7 +531,11 @@ class MeterReader:
         decodes that one on the host."""
         out: List[Optional[np.void]] = [None] * len(files)
         groups: Dict[Tuple[int, int], List[int]] = {}
-        (hs, ws, oks) = _hip.jpeg_probe_batch(files)
+        if self.jpeg_orientation:    # by UPRIGHT size: what the library takes as H and W once the switch is on
+            (hs, ws, orient, oks) = _hip.jpeg_probe_oriented_batch(files)
+            (hs, ws) = (np.where(orient >= 5, ws, hs), np.where(orient >= 5, hs, ws))
+        else:
+            (hs, ws, oks) = _hip.jpeg_probe_batch(files)
         for i in np.flatnonzero(oks):
             groups.setdefault((int(hs[i]), int(ws[i])), []).append(int(i))
         for ((h, w), idxs) in groups.items():

@@ -230,6 +230,7 @@ EXPORTS = [
     'melf_read_dials', 'melf_aligned_average', 'melf_inrange', 'melf_ctx_fused_table_ties', 'melf_ctx_fused_variant', 'melf_ctx_set_frames_resident', 'melf_ctx_last_match', 'melf_ctx_last_dials', 'melf_match_layout_query', 'melf_match_gen_plan_query', 'melf_ctx_set_profiling', 'melf_ctx_timings', 'melf_kernel_name',
     'melf_jpeg_probe', 'melf_jpeg_probe_batch', 'melf_jpeg_decode_batch', 'melf_jpeg_clean_segment', 'melf_jpeg_process_batch',
     'melf_jpeg_process_files', 'melf_jpeg_process_files_begin', 'melf_jpeg_process_files_end', 'melf_jpeg_files_in_flight_max', 'melf_ctx_files_stats', 'melf_files_open_probe',
+    'melf_jpeg_probe_oriented', 'melf_jpeg_probe_oriented_batch', 'melf_ctx_set_jpeg_orientation', 'melf_ctx_get_jpeg_orientation',
 ]
 
 _lib = None
@@ -318,6 +319,10 @@ def lib():
     i32p = C.POINTER(C.c_int32)
     L.melf_jpeg_probe.argtypes = [vp, C.c_size_t, i32p, i32p, i32p]
     L.melf_jpeg_probe_batch.argtypes = [vp, vp, C.c_int, vp, vp, vp]
+    L.melf_jpeg_probe_oriented.argtypes = [vp, C.c_size_t, i32p, i32p, i32p, i32p]
+    L.melf_jpeg_probe_oriented_batch.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
+    L.melf_ctx_set_jpeg_orientation.argtypes = [vp, C.c_int]
+    L.melf_ctx_get_jpeg_orientation.argtypes = [vp, C.POINTER(C.c_int)]
     L.melf_jpeg_decode_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]
     L.melf_jpeg_process_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.melf_jpeg_process_files.argtypes = [vp, vp, C.c_int, i32p, i32p, vp, vp]
@@ -1045,6 +1050,31 @@ def jpeg_probe(data):
     return H.value, W.value, bool(ok.value), L.melf_last_error().decode()
 
 
+def jpeg_probe_oriented(data):
+    """(H, W, orientation, supported, reason) of a JPEG file's bytes, with the EXIF orientation taken instead of refused: H and W are
+    the STORED size, orientation is 1..8 (1 when the tag is absent or invalid), supported is what jpeg_probe would say of the file
+    without its tag.  The upright size is (W, H) for orientations 5-8.  Header parse only, no GPU."""
+    L = lib()
+    H, W, o, ok = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    if isinstance(data, np.ndarray):
+        p = _ptr(data)
+    else:
+        data = data if isinstance(data, bytes) else bytes(data)
+        p = C.cast(C.c_char_p(data), C.c_void_p)  # no copy: the bytes object outlives the call
+    check(L.melf_jpeg_probe_oriented(p, len(data), C.byref(H), C.byref(W), C.byref(o), C.byref(ok)))
+    return H.value, W.value, o.value, bool(ok.value), L.melf_last_error().decode()
+
+
+def jpeg_probe_oriented_batch(files):
+    """jpeg_probe_oriented of many files' bytes in one call: (H, W, orientation, supported) int32 arrays; H and W are STORED sizes."""
+    n = len(files)
+    (H, W, o, ok) = (np.zeros(n, np.int32), np.zeros(n, np.int32), np.ones(n, np.int32), np.zeros(n, np.int32))
+    if n:
+        (ptrs, sizes, keep) = _file_table(files)
+        check(lib().melf_jpeg_probe_oriented_batch(ptrs, sizes, n, _ptr(H), _ptr(W), _ptr(o), _ptr(ok)))
+    return H, W, o, ok
+
+
 def jpeg_probe_batch(files):
     """Header check of many files' bytes in one call: (H, W, supported) int32 arrays."""
     n = len(files)
@@ -1614,6 +1644,16 @@ class Context:
 
     def files_in_flight(self):
         return len(getattr(self, '_files_pending', None) or ())
+
+    def set_jpeg_orientation(self, on):
+        """JPEG files with an EXIF orientation 2..8 are decoded upright by the jpeg_* calls of this context instead of coming back
+        unsupported (melf_ctx_set_jpeg_orientation); H and W of those calls are then upright sizes.  Off by default."""
+        check(self._L.melf_ctx_set_jpeg_orientation(self._h, int(bool(on))))
+
+    def jpeg_orientation(self):
+        on = C.c_int(0)
+        check(self._L.melf_ctx_get_jpeg_orientation(self._h, C.byref(on)))
+        return bool(on.value)
 
     def set_frames_resident(self, on):
         """Promise that the frames of every process_batch_dev call are complete in HBM when the call is made: a call's prep

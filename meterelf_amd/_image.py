@@ -3,7 +3,9 @@
 Baseline JPEG files are decoded on the GPU (melf_jpeg_process_files, the default of get_meter_values); this module
 is the HOST decoder behind cv2.imread's other cases -- formats the GPU decoder does not take (PNG, progressive or
 CMYK JPEG ...), files it reports as corrupt, and METERELF_DECODE=host -- with Pillow's libjpeg-turbo (ISLOW IDCT +
-fancy upsampling, cv2's defaults).  Everything after the decode -- crop, HLS, dial finding -- happens on the GPU.
+fancy upsampling, cv2's defaults).  A baseline JPEG file with an EXIF orientation is decoded upright on the GPU as well (the bytes
+imread_bgr below returns for it); it comes here only under METERELF_JPEG_ORIENT=host, or from a MeterReader made without
+jpeg_orientation.  Everything after the decode -- crop, HLS, dial finding -- happens on the GPU.
 """
 from typing import Optional
 

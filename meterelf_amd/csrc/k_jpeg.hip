@@ -19,7 +19,10 @@
 //          k_jpeg_huff_rst  streams with restart intervals: one lane per interval, no speculation needed
 //   J2     k_jpeg_idct      one thread per 8x8 block: dequantise + ISLOW IDCT -> u8 planes
 //   J3     k_jpeg_color420  8 pixels per thread: fancy upsample + YCC->BGR -> NHWC frame (k_jpeg_color: other modes)
+//          k_jpeg_color_exif  files with an EXIF orientation 2-8 (when the caller asked for them): the same conversion in
+//                           stored geometry, each pixel written where the upright frame has it
 #include "melf_internal.h"
+#include "melf_jpeg_orient_addr.h"
 #include "melf_threads.h"
 
 #include <emmintrin.h>
@@ -57,7 +60,8 @@ struct JpegHeader {
     bool qt_set[4] = {false, false, false, false};
     HuffSpec dc[2], ac[2];
     size_t scan_begin = 0;
-    bool saw_jfif = false, saw_adobe = false;
+    bool saw_jfif = false, saw_adobe = false, saw_exif = false;
+    int orient = 1;             // EXIF orientation of the first Exif APP1 (1 when absent, unreadable or outside 1..8)
     int adobe_transform = 0;
     const char* why = nullptr;  // non-NULL: a valid-looking file this decoder does not handle
 };
@@ -109,7 +113,8 @@ static const char* huff_spec_flaw(const HuffSpec& t, const bool dc)
     return nullptr;
 }
 
-static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h)
+// take_orient: a file with an orientation tag 2..8 is one for the GPU (h.orient says which); otherwise it is unsupported, as ever.
+static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h, const bool take_orient = false)
 {
     for (int i = 0; i < 2; ++i) { h.dc[i].set = false; h.ac[i].set = false; }
     if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return -1;
@@ -185,10 +190,15 @@ static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h)
             case 0xE0:
                 if (len >= 5 && !memcmp(s, "JFIF\0", 5)) h.saw_jfif = true;
                 break;
-            case 0xE1:  // APP1: cv2.imread (3.4) applies the EXIF orientation tag; the kernels do not rotate, so a file
-                        // that asks for it goes to the caller's host decoder (which does: meterelf_amd/_image.py)
-                if (len >= 14 && !memcmp(s, "Exif\0\0", 6) && exif_orientation(s + 6, len - 6) > 1)
-                    h.why = "EXIF orientation other than top-left (decoded and rotated on the host)";
+            case 0xE1:  // APP1: cv2.imread (3.4) applies the EXIF orientation tag.  Unless the caller takes oriented files
+                        // (k_jpeg_color_exif), a file that asks for it goes to the caller's host decoder (which rotates:
+                        // meterelf_amd/_image.py).  Only the first Exif block counts; a later one that asks again is left to the host.
+                if (len >= 14 && !memcmp(s, "Exif\0\0", 6)) {
+                    const int o = exif_orientation(s + 6, len - 6);
+                    if (o > 1 && (!take_orient || h.saw_exif)) h.why = "EXIF orientation other than top-left (decoded and rotated on the host)";
+                    else if (o > 1) h.orient = o;
+                    h.saw_exif = true;
+                }
                 break;
             case 0xEE:
                 if (len >= 12 && !memcmp(s, "Adobe", 5)) { h.saw_adobe = true; h.adobe_transform = s[11]; }
@@ -250,6 +260,44 @@ int jpeg_probe(const uint8_t* data, size_t size, int* H, int* W, int* supported,
     return 0;
 }
 
+// The same with the orientation taken: the STORED size, the code, and whether the decoder takes the file apart from its tag.
+int jpeg_probe_oriented(const uint8_t* data, size_t size, int* H, int* W, int* orientation, int* supported, std::string* why)
+{
+    JpegHeader h;
+    if (parse_headers(data, size, h, true) != 0) {
+        *H = *W = 0; *supported = 0; *orientation = 1;
+        if (why) *why = "not a JPEG file or truncated headers";
+        return 0;
+    }
+    *H = h.H; *W = h.W; *orientation = h.orient; *supported = h.why ? 0 : 1;
+    if (why) *why = h.why ? h.why : "";
+    return 0;
+}
+
+// The orientation alone (1..8), from a walk over the marker segments in front of the frame header: what parse_headers records,
+// for a caller that orders a call's files before they are parsed.
+int jpeg_file_orientation(const uint8_t* d, size_t n)
+{
+    if (!d || n < 4 || d[0] != 0xFF || d[1] != 0xD8) return 1;
+    size_t i = 2;
+    for (;;) {
+        while (i < n && d[i] != 0xFF) ++i;
+        while (i < n && d[i] == 0xFF) ++i;
+        if (i >= n) return 1;
+        const int m = d[i++];
+        if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
+        if (m == 0xD9 || m == 0xDA || (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC)) return 1;
+        if (i + 2 > n) return 1;
+        const int L = be16(d + i);
+        if (L < 2 || i + L > n) return 1;
+        if (m == 0xE1 && L - 2 >= 14 && !memcmp(d + i + 2, "Exif\0\0", 6)) {
+            const int o = exif_orientation(d + i + 8, L - 8);
+            return o > 1 ? o : 1;
+        }
+        i += L;
+    }
+}
+
 // ------------------------------------------------------------ device-side records ----
 struct JpegImageDev {
     uint32_t scan_off, scan_len;  // clean entropy-coded bytes (no stuffing, no markers) in the scan area
@@ -260,7 +308,8 @@ struct JpegImageDev {
     uint16_t restart_interval;
     uint8_t ncomp, hs0, vs0, ok;
     uint8_t tq[3], td[3], ta[3];
-    uint8_t pad[3];
+    uint8_t orient;               // EXIF orientation the colour stage applies (1..8); the other stages work in stored geometry
+    uint8_t pad[2];
     uint32_t rst_off, rst_cnt;    // restart intervals: table of their byte offsets in the clean scan (relative to the
                                   // scan area), number of intervals
     // Filled by the host; scan_len and rst_cnt (and the bytes they describe) by k_jpeg_clean on the GPU (round 4):
@@ -1431,6 +1480,40 @@ __global__ __launch_bounds__(256) void k_jpeg_color420(const JpegImageDev* __res
     }
 }
 
+// One pixel of any sampling the decoder takes, as 0x00RRGGBB: the general colour stage, shared by the upright kernel below and by
+// the oriented one.  H and W are the STORED frame's (the chroma planes' sizes and border rules follow from them).
+struct PlaneSrc {
+    const uint8_t *Y, *Cb, *Cr;
+    int ys, cs, cw, ch;
+    int mode;   // 0 grey, 1 4:4:4, 2 4:2:2 (h2v1), 3 4:2:0 (h2v2)
+};
+__device__ __forceinline__ PlaneSrc plane_src(const JpegImageDev& I, const uint8_t* planes, int H, int W)
+{
+    PlaneSrc s;
+    s.Y = planes + I.plane_off[0];
+    s.ys = I.blocks_x[0] * 8;
+    s.mode = I.ncomp == 1 ? 0 : (I.hs0 == 2 && I.vs0 == 2) ? 3 : I.hs0 == 2 ? 2 : 1;
+    s.Cb = s.Cr = s.Y;
+    s.cs = s.cw = s.ch = 0;
+    if (I.ncomp != 1) {
+        s.Cb = planes + I.plane_off[1];
+        s.Cr = planes + I.plane_off[2];
+        s.cs = I.blocks_x[1] * 8;
+        s.cw = (W + I.hs0 - 1) / I.hs0; s.ch = (H + I.vs0 - 1) / I.vs0;
+    }
+    return s;
+}
+__device__ __forceinline__ uint32_t plane_bgr(const PlaneSrc& s, int x, int y)
+{
+    const int yy = s.Y[(size_t)y * s.ys + x];
+    if (s.mode == 0) return (uint32_t)yy | ((uint32_t)yy << 8) | ((uint32_t)yy << 16);
+    int cb, cr;
+    if (s.mode == 3) { cb = chroma_h2v2(s.Cb, s.cs, s.cw, s.ch, x, y); cr = chroma_h2v2(s.Cr, s.cs, s.cw, s.ch, x, y); }
+    else if (s.mode == 2) { cb = chroma_h2v1(s.Cb, s.cs, s.cw, x, y); cr = chroma_h2v1(s.Cr, s.cs, s.cw, x, y); }
+    else { cb = s.Cb[(size_t)y * s.cs + x]; cr = s.Cr[(size_t)y * s.cs + x]; }
+    return ycc_to_bgr(yy, cb, cr);
+}
+
 __global__ __launch_bounds__(256) void k_jpeg_color(const JpegImageDev* __restrict__ imgs, const int32_t* __restrict__ status,
                                                     const uint8_t* __restrict__ planes, int H, int W,
                                                     uint8_t* __restrict__ frames, int fast420, JpegWindow win)
@@ -1446,25 +1529,9 @@ __global__ __launch_bounds__(256) void k_jpeg_color(const JpegImageDev* __restri
         for (int k = 0; k < npx * 3; ++k) out[k] = 0;
         return;
     }
-    const uint8_t* Y = planes + I.plane_off[0];
-    const int ys = I.blocks_x[0] * 8;
+    const PlaneSrc src = plane_src(I, planes, H, W);
     uint32_t px[4] = {0, 0, 0, 0};
-    if (I.ncomp == 1) {
-        for (int k = 0; k < npx; ++k) { const uint32_t v = Y[(size_t)y * ys + x0 + k]; px[k] = v | (v << 8) | (v << 16); }
-    } else {
-        const uint8_t* Cb = planes + I.plane_off[1];
-        const uint8_t* Cr = planes + I.plane_off[2];
-        const int cs = I.blocks_x[1] * 8;
-        const int cw = (W + I.hs0 - 1) / I.hs0, ch = (H + I.vs0 - 1) / I.vs0;
-        for (int k = 0; k < npx; ++k) {
-            const int x = x0 + k;
-            int cb, cr;
-            if (I.hs0 == 2 && I.vs0 == 2) { cb = chroma_h2v2(Cb, cs, cw, ch, x, y); cr = chroma_h2v2(Cr, cs, cw, ch, x, y); }
-            else if (I.hs0 == 2) { cb = chroma_h2v1(Cb, cs, cw, x, y); cr = chroma_h2v1(Cr, cs, cw, x, y); }
-            else { cb = Cb[(size_t)y * cs + x]; cr = Cr[(size_t)y * cs + x]; }
-            px[k] = ycc_to_bgr(Y[(size_t)y * ys + x], cb, cr);
-        }
-    }
+    for (int k = 0; k < npx; ++k) px[k] = plane_bgr(src, x0 + k, y);
     if (npx == 4 && ((W * 3) & 3) == 0) {  // 12 bytes, dword aligned
         uint32_t* o = (uint32_t*)out;
         o[0] = px[0] | (px[1] << 24);
@@ -1472,6 +1539,73 @@ __global__ __launch_bounds__(256) void k_jpeg_color(const JpegImageDev* __restri
         o[2] = (px[2] >> 16) | (px[3] << 8);
     } else {
         for (int k = 0; k < npx; ++k) { out[3 * k] = px[k] & 255; out[3 * k + 1] = (px[k] >> 8) & 255; out[3 * k + 2] = (px[k] >> 16) & 255; }
+    }
+}
+
+// Colour stage of the files stored under an EXIF orientation 2-8 (every sampling, any size).  Decode first, permute afterwards, as
+// cv2.imread does: the conversion above runs in STORED geometry (Hs x Ws, the chroma filter along the stored axes), and each pixel
+// is written where the upright frame has it (melf_jpeg_orient_addr.h); the frames are n x H' x W' x 3 with H' x W' = Ws x Hs for
+// codes 5-8.  Built like k_orient_tiles: a workgroup takes a tile of OT x OT pixels of the stored window, every thread converts
+// pixels along the stored rows (the plane reads of a wave are contiguous) and parks them as one dword each in LDS; after the
+// barrier the workgroup writes the tile's rows of the UPRIGHT frame, consecutive lanes consecutive dwords of a row.
+// OT = 64, not 32: an upright row of a tile is then 192 contiguous bytes instead of 96 (the store side is what the kernel is bound
+// by: W' * 3 has no alignment, so every row has ragged ends, and they are a 6th of the row's dwords at 32 and a 12th at 64), and the
+// tile's 16.3 KiB of LDS still leave room for 9 workgroups on a CU, more than the 8 its wave slots hold at 256 threads.
+// Row pitch 65 dwords: the transposed read (codes 5-8) walks a tile column, 65 dwords apart, i.e. one bank further per pixel (LDS
+// dword reads bank over 32 dwords per 32-lane half); the row-wise write and the untransposed read are contiguous anyway.
+// Bounds: win lies inside the stored frame (jpeg_orient::window clamps it), so sx < Ws <= 8 * blocks_x and sy < Hs <= 8 * blocks_y:
+// no load leaves the file's own planes (the chroma filter clamps its neighbours itself); and the stored pixel (sx, sy) of the frame
+// goes to one pixel (x, y) of H' x W': no store leaves bytes [0, H' * W' * 3) of the file's frame.
+constexpr int OT = 64, OT_PITCH = OT + 1;
+__global__ __launch_bounds__(256) void k_jpeg_color_exif(const JpegImageDev* __restrict__ imgs, const int32_t* __restrict__ status,
+                                                             const uint8_t* __restrict__ planes, int Hs, int Ws, int code,
+                                                             uint8_t* __restrict__ frames, JpegWindow win)
+{
+    __shared__ uint32_t tile[OT * OT_PITCH];
+    const int img = blockIdx.y;
+    const int tiles_x = (win.x1 - win.x0 + OT - 1) / OT;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int sx0 = win.x0 + tx * OT, sy0 = win.y0 + ty * OT;
+    const int tw = min(OT, win.x1 - sx0), th = min(OT, win.y1 - sy0);
+    if (tw <= 0 || th <= 0) return;   // uniform: a launch with more tiles than the window has
+    const JpegImageDev& I = imgs[img];
+    if (I.ok && status[img] == 0) {
+        const PlaneSrc src = plane_src(I, planes, Hs, Ws);
+        for (int i = threadIdx.x; i < th * OT; i += 256) {
+            const int ly = i / OT, lx = i % OT;
+            if (lx < tw) tile[ly * OT_PITCH + lx] = plane_bgr(src, sx0 + lx, sy0 + ly);
+        }
+    } else {   // not decoded, or failed in the entropy decoder: zeros over its oriented window
+        for (int i = threadIdx.x; i < th * OT; i += 256) tile[(i / OT) * OT_PITCH + i % OT] = 0;
+    }
+    __syncthreads();
+    // the tile in the upright frame: nr rows of nc pixels from (x0, y0); element e of row r sits at tile[base + r * sr + e * se]
+    const bool t = jpeg_orient::transposed(code), fx = jpeg_orient::flips_x(code), fy = jpeg_orient::flips_y(code);
+    const int u0 = fx ? Ws - sx0 - tw : sx0, v0 = fy ? Hs - sy0 - th : sy0;
+    const int step_x = fx ? -1 : 1, step_y = fy ? -OT_PITCH : OT_PITCH;
+    const int base = (fx ? tw - 1 : 0) + (fy ? (th - 1) * OT_PITCH : 0);
+    const int nr = t ? tw : th, nc = t ? th : tw, x0 = t ? v0 : u0, y0 = t ? u0 : v0;
+    const int sr = t ? step_x : step_y, se = t ? step_y : step_x;
+    const int Hup = t ? Ws : Hs, Wup = t ? Hs : Ws;
+    uint8_t* const out = frames + (size_t)img * Hup * Wup * 3;
+    const int nb = nc * 3;              // bytes of a row of the tile
+    const int slots = (nb + 6) / 4;     // aligned dwords a row can touch, whatever its first byte's alignment
+    for (int i = threadIdx.x; i < nr * slots; i += 256) {
+        const int r = i / slots, k = i - r * slots;
+        uint8_t* const row = out + ((size_t)(y0 + r) * Wup + x0) * 3;
+        const int j0 = 4 * k - (int)((uintptr_t)row & 3);   // the slot's first byte, counted from the row's first
+        if (j0 >= nb) continue;
+        const int li = base + r * sr;
+        if (j0 >= 0 && j0 + 4 <= nb) {   // a whole dword of the row: the bytes of two neighbouring pixels
+            const int e = j0 / 3, q = j0 - 3 * e;
+            const uint64_t two = (uint64_t)tile[li + e * se] | ((uint64_t)tile[li + min(e + 1, nc - 1) * se] << 24);
+            *(uint32_t*)(row + j0) = (uint32_t)(two >> (8 * q));
+        } else {                         // a ragged end: byte stores
+            for (int b = max(j0, 0); b < min(j0 + 4, nb); ++b) {
+                const int e = b / 3, q = b - 3 * e;
+                row[b] = (uint8_t)(tile[li + e * se] >> (8 * q));
+            }
+        }
     }
 }
 
@@ -1501,6 +1635,14 @@ struct JpegWorkspace {
     int n_par = 0, n_seq = 0;   // images for the segment-parallel / the restart-interval Huffman kernel
     int n_420 = 0;              // three-component 4:2:0 images (fast colour kernel)
     size_t max_par_scan = 0;    // longest clean scan among the former (bytes)
+    // The batch as runs of consecutive files of one orientation code: J1..J3 are launched once per run, on the run's window of
+    // the stored frame.  A batch without oriented files is one run of code 1 whose counts are the five above.
+    struct Run {
+        int first, n, code;
+        int n_par, n_seq, n_420, max_blocks;
+        size_t max_par_scan;
+    };
+    std::vector<Run> runs;
 };
 
 void jpeg_workspace_free(JpegWorkspace* w)
@@ -1561,22 +1703,26 @@ void jpeg_parsed_resize(JpegParsed* p, int n)   // keeps what it has allocated: 
     if ((int)p->hdr.size() < n) p->hdr.resize(n);
     if (!p->slow.empty() && p->slow.size() < (size_t)n * 4) p->slow.resize((size_t)n * 4);
 }
-void jpeg_parse_one(JpegParsed* p, int i, const uint8_t* data, size_t size, int* H, int* W, int* supported)
+// take_orient: files with an orientation tag are taken, and H, W are then the UPRIGHT size (what a caller groups files by).
+void jpeg_parse_one(JpegParsed* p, int i, const uint8_t* data, size_t size, int* H, int* W, int* supported, bool take_orient)
 {
     JpegHeader& h = p->hdr[i];
     h = JpegHeader();   // the object may be a previous call's
-    if (!data || parse_headers(data, size, h) != 0) { *H = *W = 0; *supported = 0; return; }
-    *H = h.H; *W = h.W; *supported = h.why ? 0 : 1;
+    if (!data || parse_headers(data, size, h, take_orient) != 0) { *H = *W = 0; *supported = 0; return; }
+    *H = jpeg_orient::swapped_h(h.orient, h.H, h.W); *W = jpeg_orient::swapped_w(h.orient, h.H, h.W); *supported = h.why ? 0 : 1;
     if (!h.why && !p->slow.empty()) build_slow4(h, p->slow.data() + (size_t)i * 4);
 }
 void jpeg_parsed_free(JpegParsed* p) { delete p; }
+int jpeg_parsed_orientation(const JpegParsed* p, int i) { return p->hdr[i].orient; }
 
 // Host half of a batch: parse every file (unless `parsed` holds the headers already: files first .. first + n - 1 of that
 // pass, host_status filled), lay the batch out, fill the pinned stage buffer.
 // host_status[i]: 0 = handed to the GPU, 1 = valid but unsupported, 2 = unreadable, 3 = other size.
+// take_orient: files with an EXIF orientation 2..8 are handed to the GPU too; H and W are the UPRIGHT size, which such a file's
+// stored size gives after the swap its code asks for, and everything laid out here for it follows its STORED size.
 int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const size_t* sizes, int n, int H, int W,
                        int32_t* host_status, std::string* err, const JpegParsed* parsed, int first, const int* pidx,
-                       const uint8_t* pin_base, size_t pin_len)
+                       const uint8_t* pin_base, size_t pin_len, bool take_orient)
 {
     if (!*pws) *pws = new JpegWorkspace();
     JpegWorkspace* w = *pws;
@@ -1590,9 +1736,9 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
         own.resize(n);
         par_for([&](int i) {
             JpegHeader& h = own[i];
-            if (!data[i] || parse_headers(data[i], sizes[i], h) != 0) { host_status[i] = 2; return; }
+            if (!data[i] || parse_headers(data[i], sizes[i], h, take_orient) != 0) { host_status[i] = 2; return; }
             if (h.why) { host_status[i] = 1; return; }
-            if (h.H != H || h.W != W) { host_status[i] = 3; return; }
+            if (jpeg_orient::swapped_h(h.orient, h.H, h.W) != H || jpeg_orient::swapped_w(h.orient, h.H, h.W) != W) { host_status[i] = 3; return; }
             host_status[i] = 0;
         });
     }
@@ -1628,10 +1774,11 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
         if (host_status[i] != 0) continue;
         const JpegHeader& h = hbase[hidx(i)];
         r.ok = 1;
+        r.orient = (uint8_t)h.orient;
         r.ncomp = (uint8_t)h.ncomp; r.hs0 = (uint8_t)h.hs[0]; r.vs0 = (uint8_t)h.vs[0];
         r.restart_interval = (uint16_t)h.restart_interval;
-        r.mcus_x = (uint16_t)((W + 8 * h.hs[0] - 1) / (8 * h.hs[0]));
-        r.mcus_y = (uint16_t)((H + 8 * h.vs[0] - 1) / (8 * h.vs[0]));
+        r.mcus_x = (uint16_t)((h.W + 8 * h.hs[0] - 1) / (8 * h.hs[0]));   // the stored size: (W, H), swapped for codes 5-8
+        r.mcus_y = (uint16_t)((h.H + 8 * h.vs[0] - 1) / (8 * h.vs[0]));
         int blocks = 0;
         for (int c = 0; c < h.ncomp; ++c) {
             r.tq[c] = (uint8_t)h.tq[c]; r.td[c] = (uint8_t)h.td[c]; r.ta[c] = (uint8_t)h.ta[c];
@@ -1741,10 +1888,19 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
     else par_for(fill);
     w->n_par = w->n_seq = w->n_420 = 0;
     w->max_par_scan = 0;
+    w->runs.clear();
     for (int i = 0; i < n; ++i) {
-        if (rec[i].ok == 1) { ++w->n_par; w->max_par_scan = std::max(w->max_par_scan, (size_t)rec[i].raw_len); }
-        else if (rec[i].ok == 2) ++w->n_seq;
-        if (rec[i].ok && rec[i].ncomp == 3 && rec[i].hs0 == 2 && rec[i].vs0 == 2) ++w->n_420;
+        // a file that is not decoded (zeros over the window) belongs to the run it stands in
+        const int code = rec[i].ok ? rec[i].orient : (w->runs.empty() ? 1 : w->runs.back().code);
+        if (w->runs.empty() || w->runs.back().code != code) w->runs.push_back({i, 0, code, 0, 0, 0, 0, 0});
+        JpegWorkspace::Run& run = w->runs.back();
+        ++run.n;
+        if (rec[i].ok == 1) { ++w->n_par; ++run.n_par; w->max_par_scan = std::max(w->max_par_scan, (size_t)rec[i].raw_len); run.max_par_scan = std::max(run.max_par_scan, (size_t)rec[i].raw_len); }
+        else if (rec[i].ok == 2) { ++w->n_seq; ++run.n_seq; }
+        if (rec[i].ok && rec[i].ncomp == 3 && rec[i].hs0 == 2 && rec[i].vs0 == 2) { ++w->n_420; ++run.n_420; }
+        int blocks = 0;
+        for (int c = 0; c < rec[i].ncomp; ++c) blocks += (int)rec[i].blocks_x[c] * rec[i].blocks_y[c];
+        run.max_blocks = std::max(run.max_blocks, blocks);   // (a record that was not laid out has no components)
     }
     memcpy(base + w->off_imgs, rec.data(), (size_t)n * sizeof(JpegImageDev));
     if (trace) {
@@ -1782,51 +1938,81 @@ int jpeg_upload_batch(JpegWorkspace* w, int n, hipStream_t copy_stream, std::str
 int jpeg_decode_batch_kernels(JpegWorkspace* w, int n, int H, int W, uint8_t* d_frames, hipStream_t stream, std::string* err,
                               void (*timer)(void*, int, int), void* timer_arg, const int* rect)
 {
-    // window: the caller's rectangle grown by one MCU (chroma filter context) and aligned to 16, or the frame
-    JpegWindow win = {0, 0, W, H};
-    if (rect) {
-        win.x0 = std::max(0, (rect[0] - 16) & ~15); win.y0 = std::max(0, (rect[1] - 16) & ~15);
-        win.x1 = std::min(W, (rect[2] + 16 + 15) & ~15); win.y1 = std::min(H, (rect[3] + 16 + 15) & ~15);
-        if (win.x1 <= win.x0 || win.y1 <= win.y0) win = {0, 0, W, H};
+    // Per run of one orientation code: the caller's rectangle, taken back to the stored frame, grown by one MCU (chroma filter
+    // context) and aligned to 16, or the frame (melf_jpeg_orient_addr.h).  A kernel of a run gets the run's first file as its file 0.
+    struct RunGeo { int Hs, Ws; JpegWindow win; };
+    std::vector<RunGeo> geo;
+    for (const JpegWorkspace::Run& r : w->runs) {
+        const int Hs = jpeg_orient::swapped_h(r.code, H, W), Ws = jpeg_orient::swapped_w(r.code, H, W);
+        const jpeg_orient::Window ow = jpeg_orient::window(rect, r.code, Hs, Ws);
+        geo.push_back({Hs, Ws, {ow.x0, ow.y0, ow.x1, ow.y1}});
     }
-    const int win_w = win.x1 - win.x0, win_h = win.y1 - win.y0;
     JTRY(hipMemsetAsync(w->d_status, 0, (size_t)n * sizeof(int32_t), stream));
-    const JpegImageDev* imgs = (const JpegImageDev*)(w->d_stage + w->off_imgs);
-    const uint16_t* qt = (const uint16_t*)(w->d_stage + w->off_qt);
-    const HuffSlow* slow = (const HuffSlow*)(w->d_stage + w->off_slow);
+    const JpegImageDev* const imgs0 = (const JpegImageDev*)(w->d_stage + w->off_imgs);
+    const uint16_t* const qt0 = (const uint16_t*)(w->d_stage + w->off_qt);
+    const HuffSlow* const slow0 = (const HuffSlow*)(w->d_stage + w->off_slow);
     const uint8_t* scan = w->d_stage + w->off_scan;
+    const size_t nruns = w->runs.size();
     if (timer) timer(timer_arg, 0, 0);
     if (w->n_par + w->n_seq > 0)   // J0: stuffing, fill bytes and restart markers out of the uploaded segments
         hipLaunchKernelGGL(k_jpeg_clean, dim3(n), dim3(CLEAN_T), 0, stream, (JpegImageDev*)(w->d_stage + w->off_imgs), w->d_raw, w->d_stage + w->off_scan);
-    if (w->n_par > 0) {  // one workgroup per image, one lane per stream segment
-        // 512 lanes per image; a batch with a scan too long for 512 segments of the length the kernel can address takes 1024
-        if (w->max_par_scan > JPEG_MAX_PAR_SCAN / 2)
-            hipLaunchKernelGGL(k_jpeg_huff<1024>, dim3(n), dim3(1024), 0, stream, imgs, slow, scan, w->d_coefs, w->d_status, win);
-        else
-            hipLaunchKernelGGL(k_jpeg_huff<512>, dim3(n), dim3(512), 0, stream, imgs, slow, scan, w->d_coefs, w->d_status, win);
-    }
-    if (w->n_seq > 0) {  // streams with restart intervals: one lane per interval
-        hipLaunchKernelGGL(k_jpeg_huff_rst<256>, dim3(n), dim3(256), 0, stream, imgs, slow, scan, w->d_coefs, w->d_status, win);
+    for (size_t q = 0; q < nruns; ++q) {
+        const JpegWorkspace::Run& r = w->runs[q];
+        const JpegWindow win = geo[q].win;
+        const JpegImageDev* imgs = imgs0 + r.first;
+        const HuffSlow* slow = slow0 + (size_t)r.first * 4;
+        int32_t* status = w->d_status + r.first;
+        if (r.n_par > 0) {  // one workgroup per image, one lane per stream segment
+            // 512 lanes per image; a batch with a scan too long for 512 segments of the length the kernel can address takes 1024
+            if (r.max_par_scan > JPEG_MAX_PAR_SCAN / 2)
+                hipLaunchKernelGGL(k_jpeg_huff<1024>, dim3(r.n), dim3(1024), 0, stream, imgs, slow, scan, w->d_coefs, status, win);
+            else
+                hipLaunchKernelGGL(k_jpeg_huff<512>, dim3(r.n), dim3(512), 0, stream, imgs, slow, scan, w->d_coefs, status, win);
+        }
+        if (r.n_seq > 0) {  // streams with restart intervals: one lane per interval
+            hipLaunchKernelGGL(k_jpeg_huff_rst<256>, dim3(r.n), dim3(256), 0, stream, imgs, slow, scan, w->d_coefs, status, win);
+        }
     }
     if (timer) timer(timer_arg, 0, 1);
     JTRY(hipGetLastError());
     if (w->max_blocks > 0) {
         if (timer) timer(timer_arg, 1, 0);
-        // at most (window / 8)^2 luma blocks + two chroma planes of up to the same count (4:4:4)
-        const int wblocks = 3 * ((win_w + 15) / 8 + 2) * ((win_h + 15) / 8 + 2);
-        const int nblk = std::min(w->max_blocks, wblocks);
-        hipLaunchKernelGGL(k_jpeg_idct, dim3((nblk + 255) / 256, n), dim3(256), 0, stream, imgs, qt, w->d_coefs, w->d_status, w->d_planes, win);
+        for (size_t q = 0; q < nruns; ++q) {
+            const JpegWorkspace::Run& r = w->runs[q];
+            if (r.max_blocks <= 0) continue;
+            const JpegWindow win = geo[q].win;
+            const int win_w = win.x1 - win.x0, win_h = win.y1 - win.y0;
+            // at most (window / 8)^2 luma blocks + two chroma planes of up to the same count (4:4:4)
+            const int wblocks = 3 * ((win_w + 15) / 8 + 2) * ((win_h + 15) / 8 + 2);
+            const int nblk = std::min(r.max_blocks, wblocks);
+            hipLaunchKernelGGL(k_jpeg_idct, dim3((nblk + 255) / 256, r.n), dim3(256), 0, stream, imgs0 + r.first, qt0 + (size_t)r.first * 256, w->d_coefs,
+                               w->d_status + r.first, w->d_planes, win);
+        }
         if (timer) timer(timer_arg, 1, 1);
         JTRY(hipGetLastError());
     }
     if (timer) timer(timer_arg, 2, 0);
-    const int fast420 = (W % 8 == 0 && w->n_420 > 0) ? 1 : 0;
-    if (fast420) {
-        const int items = ((win_w + 7) / 8) * ((win_h + 1) / 2);   // 8 pixels x 2 rows each
-        hipLaunchKernelGGL(k_jpeg_color420, dim3((items + 255) / 256, n), dim3(256), 0, stream, imgs, w->d_status, w->d_planes, H, W, d_frames, win);
+    for (size_t q = 0; q < nruns; ++q) {
+        const JpegWorkspace::Run& r = w->runs[q];
+        const JpegWindow win = geo[q].win;
+        const int win_w = win.x1 - win.x0, win_h = win.y1 - win.y0;
+        const JpegImageDev* imgs = imgs0 + r.first;
+        const int32_t* status = w->d_status + r.first;
+        uint8_t* frames = d_frames + (size_t)r.first * H * W * 3;
+        if (r.code != 1) {   // every sampling through the one oriented kernel
+            const int tiles = ((win_w + OT - 1) / OT) * ((win_h + OT - 1) / OT);
+            hipLaunchKernelGGL(k_jpeg_color_exif, dim3(tiles, r.n), dim3(256), 0, stream, imgs, status, w->d_planes, geo[q].Hs, geo[q].Ws, r.code,
+                               frames, win);
+            continue;
+        }
+        const int fast420 = (W % 8 == 0 && r.n_420 > 0) ? 1 : 0;
+        if (fast420) {
+            const int items = ((win_w + 7) / 8) * ((win_h + 1) / 2);   // 8 pixels x 2 rows each
+            hipLaunchKernelGGL(k_jpeg_color420, dim3((items + 255) / 256, r.n), dim3(256), 0, stream, imgs, status, w->d_planes, H, W, frames, win);
+        }
+        if (!fast420 || r.n_420 < r.n)
+            hipLaunchKernelGGL(k_jpeg_color, dim3((win_w + 1023) / 1024, win_h, r.n), dim3(256), 0, stream, imgs, status, w->d_planes, H, W, frames, fast420, win);
     }
-    if (!fast420 || w->n_420 < n)
-        hipLaunchKernelGGL(k_jpeg_color, dim3((win_w + 1023) / 1024, win_h, n), dim3(256), 0, stream, imgs, w->d_status, w->d_planes, H, W, d_frames, fast420, win);
     if (timer) timer(timer_arg, 2, 1);
     JTRY(hipGetLastError());
     return MELF_SUCCESS;

@@ -283,6 +283,7 @@ struct melf_ctx {
     uint8_t* d_stage_out = nullptr;
     size_t stage_out_cap = 0;
     JpegWorkspace* jpeg = nullptr;     // created by the first JPEG batch
+    bool jpeg_orient = false;          // melf_ctx_set_jpeg_orientation: files with an EXIF orientation 2..8 are decoded, not refused
     // pipelined JPEG path (melf_jpeg_process_batch): a second workspace and decode stream, so that the host prepares chunk
     // k + 1 and its upload runs while chunk k decodes; per-chunk events; the files' decode status in pinned memory
     static const int NJ = 4;           // workspaces in the ring (a 1024-file call in 256-file chunks never waits for one)
@@ -872,6 +873,21 @@ extern "C" int melf_ctx_set_frames_resident(melf_ctx* c, int on)
 {
     if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
     c->frames_resident = on != 0;
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_ctx_set_jpeg_orientation(melf_ctx* c, int on)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    if (!c->files_jobs.empty()) return fail(MELF_ERR_INVALID, "melf_ctx_set_jpeg_orientation while a melf_jpeg_process_files_begin call is in flight");
+    c->jpeg_orient = on != 0;
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_ctx_get_jpeg_orientation(melf_ctx* c, int* on)
+{
+    if (!c || !on) return fail(MELF_ERR_INVALID, "bad argument");
+    *on = c->jpeg_orient ? 1 : 0;
     return MELF_SUCCESS;
 }
 
@@ -2231,6 +2247,29 @@ extern "C" int melf_jpeg_probe(const uint8_t* data, size_t size, int32_t* H, int
     return MELF_SUCCESS;
 }
 
+extern "C" int melf_jpeg_probe_oriented(const uint8_t* data, size_t size, int32_t* H, int32_t* W, int32_t* orientation, int32_t* supported)
+{
+    if (!data || !H || !W || !orientation || !supported) return fail(MELF_ERR_INVALID, "bad argument");
+    int h = 0, w = 0, o = 1, ok = 0;
+    std::string why;
+    jpeg_probe_oriented(data, size, &h, &w, &o, &ok, &why);
+    *H = h; *W = w; *orientation = o; *supported = ok;
+    g_err = why;
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_jpeg_probe_oriented_batch(const uint8_t* const* data, const size_t* sizes, int n, int32_t* H, int32_t* W,
+                                              int32_t* orientation, int32_t* supported)
+{
+    if (n < 0 || (n > 0 && (!data || !sizes || !H || !W || !orientation || !supported))) return fail(MELF_ERR_INVALID, "bad argument");
+    for (int i = 0; i < n; ++i) {
+        int h = 0, w = 0, o = 1, ok = 0;
+        if (data[i] && sizes[i]) jpeg_probe_oriented(data[i], sizes[i], &h, &w, &o, &ok, nullptr);
+        H[i] = h; W[i] = w; orientation[i] = o; supported[i] = ok;
+    }
+    return MELF_SUCCESS;
+}
+
 extern "C" int melf_jpeg_probe_batch(const uint8_t* const* data, const size_t* sizes, int n, int32_t* H, int32_t* W,
                                      int32_t* supported)
 {
@@ -2273,7 +2312,7 @@ int jpeg_decode_to_device(melf_ctx* c, const uint8_t* const* data, const size_t*
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<int32_t> hstat(n);
     std::string err;
-    if (int rc = jpeg_prepare_batch(&c->jpeg, data, sizes, n, H, W, hstat.data(), &err)) return fail(rc, err);
+    if (int rc = jpeg_prepare_batch(&c->jpeg, data, sizes, n, H, W, hstat.data(), &err, nullptr, 0, nullptr, nullptr, 0, c->jpeg_orient)) return fail(rc, err);
     const auto t1 = std::chrono::steady_clock::now();
     std::vector<int32_t> dstat(n);
     JpegTimers t{c, c->stream, {}, {false, false, false}};
@@ -2409,8 +2448,8 @@ static int jpeg_decode_pipelined(melf_ctx* c, const uint8_t* const* data, const 
         if (seq >= (uint64_t)NJ) HIP_TRY(hipEventSynchronize(c->ev_jup[b]));
         if (trace) tt[1] = trace_clock_ms(std::chrono::steady_clock::now());
         if (int rc = src ? jpeg_prepare_batch(ws[b], data + f0, sizes + f0, m, H, W, hstat.data() + f0, &err, src->parsed, f0, src->index,
-                                              src->pin_base, src->pin_len)
-                         : jpeg_prepare_batch(ws[b], data + f0, sizes + f0, m, H, W, hstat.data() + f0, &err))
+                                              src->pin_base, src->pin_len, c->jpeg_orient)
+                         : jpeg_prepare_batch(ws[b], data + f0, sizes + f0, m, H, W, hstat.data() + f0, &err, nullptr, 0, nullptr, nullptr, 0, c->jpeg_orient))
             return fail(rc, err);
         if (trace) tt[2] = trace_clock_ms(std::chrono::steady_clock::now());
         // ... and the kernels that last read its device buffers before the upload overwrites them
@@ -2465,31 +2504,31 @@ static int jpeg_process_batch_from(melf_ctx* c, const uint8_t* const* data, cons
     // the reading path only looks at the meter_rect crop: IDCT and colour conversion are limited to it
     const int rect[4] = {c->P.rect_x0, c->P.rect_y0, c->P.rect_x1, c->P.rect_y1};
     if (!overlapped) HIP_TRY(hipStreamSynchronize(c->stream));   // a caller's earlier work on the context's stream
-    if (n <= 64) {
-        if (overlapped) HIP_TRY(hipDeviceSynchronize());   // the one-piece path shares its buffers with every call: alone on the GPU
-        if (int rc = grow(&c->d_stage_in, &c->stage_in_cap, bytes)) return rc;
-        if (int rc = jpeg_decode_to_device(c, data, sizes, n, H, W, c->d_stage_in, status, rect)) return rc;
-        return melf_process_batch_dev(c, c->d_stage_in, n, H, W, (size_t)H * W * 3, nullptr, out_host, c->stream);
-    }
-    static const bool trace = diag_env("MELF_JPEG_TRACE") != nullptr;
-    const auto tc0 = std::chrono::steady_clock::now();
-    // Files with very few bits per block (a dark, flat frame: "DC difference 0, end of block" and nothing else) keep the
-    // Huffman kernel's wrongly-phased decoders in step with their garbage, so the truth crawls one segment per round and
-    // the image's workgroup runs ~3x as long as a normal one -- and with it the whole chunk's kernel.  They go FIRST, in a
-    // chunk of their own: its kernel then runs beside the other chunks' preparation and kernels.  Scheduling only: the
-    // records come back in the caller's order.
+    // Files with an EXIF orientation (melf_ctx_set_jpeg_orientation): the decode kernels are launched once per run of files of one
+    // code (each code has its own window of the stored frame), so the call's files are ordered code by code.  Scheduling only,
+    // like the sparse files below: the records go back in the caller's order.  Without such a file nothing is reordered for it.
     std::vector<int> perm;
     std::vector<const uint8_t*> pdata;
     std::vector<size_t> psizes;
     std::vector<int> pindex;
     JpegSource psrc;
-    int nsparse = 0;
-    const double blocks = ((H + 7) / 8) * (double)((W + 7) / 8) * 1.5;
-    for (int i = 0; i < n; ++i) nsparse += (double)sizes[i] * 8.0 < 12.0 * blocks ? 1 : 0;
-    if (nsparse > 0 && nsparse < n) {
+    std::vector<uint8_t> code;
+    bool oriented = false;
+    if (c->jpeg_orient) {
+        code.resize(n);
+        for (int i = 0; i < n; ++i) {
+            code[i] = (uint8_t)(src ? jpeg_parsed_orientation(src->parsed, src->index ? src->index[i] : i) : jpeg_file_orientation(data[i], sizes[i]));
+            oriented = oriented || code[i] != 1;
+        }
+    }
+    // perm[k]: the caller's index of the file decoded k-th -- `first` files (by `is_first`) in front, each part code by code
+    auto reorder = [&](const std::function<bool(int)>& is_first) {
         perm.resize(n); pdata.resize(n); psizes.resize(n);
-        int a = 0, b = nsparse;
-        for (int i = 0; i < n; ++i) perm[(double)sizes[i] * 8.0 < 12.0 * blocks ? a++ : b++] = i;
+        for (int i = 0; i < n; ++i) perm[i] = i;
+        std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) {
+            const int ka = (is_first(a) ? 0 : 16) + (oriented ? code[a] : 0), kb = (is_first(b) ? 0 : 16) + (oriented ? code[b] : 0);
+            return ka < kb;
+        });
         for (int i = 0; i < n; ++i) { pdata[i] = data[perm[i]]; psizes[i] = sizes[perm[i]]; }
         data = pdata.data();
         sizes = psizes.data();
@@ -2499,9 +2538,37 @@ static int jpeg_process_batch_from(melf_ctx* c, const uint8_t* const* data, cons
             psrc = {src->parsed, pindex.data(), src->pin_base, src->pin_len};
             src = &psrc;
         }
-    } else {
-        nsparse = 0;
+    };
+    if (n <= 64) {
+        if (overlapped) HIP_TRY(hipDeviceSynchronize());   // the one-piece path shares its buffers with every call: alone on the GPU
+        if (int rc = grow(&c->d_stage_in, &c->stage_in_cap, bytes)) return rc;
+        if (!oriented) {
+            if (int rc = jpeg_decode_to_device(c, data, sizes, n, H, W, c->d_stage_in, status, rect)) return rc;
+            return melf_process_batch_dev(c, c->d_stage_in, n, H, W, (size_t)H * W * 3, nullptr, out_host, c->stream);
+        }
+        reorder([](int) { return false; });
+        std::vector<int32_t> pstatus(n);
+        std::vector<melf_result> pout(n);
+        if (int rc = jpeg_decode_to_device(c, data, sizes, n, H, W, c->d_stage_in, pstatus.data(), rect)) return rc;
+        if (int rc = melf_process_batch_dev(c, c->d_stage_in, n, H, W, (size_t)H * W * 3, nullptr, pout.data(), c->stream)) return rc;
+        for (int i = 0; i < n; ++i) { status[perm[i]] = pstatus[i]; out_host[perm[i]] = pout[i]; }
+        return MELF_SUCCESS;
     }
+    static const bool trace = diag_env("MELF_JPEG_TRACE") != nullptr;
+    const auto tc0 = std::chrono::steady_clock::now();
+    // Files with very few bits per block (a dark, flat frame: "DC difference 0, end of block" and nothing else) keep the
+    // Huffman kernel's wrongly-phased decoders in step with their garbage, so the truth crawls one segment per round and
+    // the image's workgroup runs ~3x as long as a normal one -- and with it the whole chunk's kernel.  They go FIRST, in a
+    // chunk of their own: its kernel then runs beside the other chunks' preparation and kernels.  Scheduling only: the
+    // records come back in the caller's order.
+    int nsparse = 0;
+    const double blocks = ((H + 7) / 8) * (double)((W + 7) / 8) * 1.5;
+    const size_t* const sizes0 = sizes;
+    auto sparse = [&](int i) { return (double)sizes0[i] * 8.0 < 12.0 * blocks; };
+    for (int i = 0; i < n; ++i) nsparse += sparse(i) ? 1 : 0;
+    if (nsparse == n) nsparse = 0;
+    if (nsparse > 0) reorder(sparse);
+    else if (oriented) reorder([](int) { return false; });
     std::vector<int32_t> hstat;
     // the reading path: ONE pass over all n frames behind the last chunk (the tuned match kernel in its full-batch layout)
     if (int rc = grow(&c->d_jframes[cs], &c->jframes_cap[cs], bytes)) return rc;
@@ -2629,6 +2696,7 @@ static int jpeg_files_read(melf_ctx* c, int slot, const char* const* paths, int 
     const auto t_arena = std::chrono::steady_clock::now();
     std::atomic<size_t> bump{0};
     std::atomic<int> spilled{0};
+    const bool take_orient = c->jpeg_orient;   // hs / ws are then the files' UPRIGHT sizes: stage 2 groups by them
     auto read_all = [](int fd, uint8_t* dst, size_t sz) {
         size_t got = 0;
         while (got < sz) {
@@ -2668,7 +2736,7 @@ static int jpeg_files_read(melf_ctx* c, int slot, const char* const* paths, int 
         R.where[i] = base + o;
         // header and Huffman decode data right here, while the file's first lines are in this core's cache: the decode stage
         // then has nothing to compute per file
-        jpeg_parse_one(R.parsed, i, base + o, sz, &hs[i], &ws[i], &oks[i]);
+        jpeg_parse_one(R.parsed, i, base + o, sz, &hs[i], &ws[i], &oks[i], take_orient);
     });
     const auto t_read = std::chrono::steady_clock::now();
     c->file_arena_per_file[slot] = std::max<size_t>(bump.load() / (size_t)n, 4096);
@@ -2691,7 +2759,7 @@ static int jpeg_files_read(melf_ctx* c, int slot, const char* const* paths, int 
             if (got != len[i]) return;
             status[i] = MELF_JPEG_OK;
             R.where[i] = dst;
-            jpeg_parse_one(R.parsed, i, dst, len[i], &hs[i], &ws[i], &oks[i]);
+            jpeg_parse_one(R.parsed, i, dst, len[i], &hs[i], &ws[i], &oks[i], take_orient);
         });
     }
     if (trace) {

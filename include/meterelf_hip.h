@@ -795,7 +795,8 @@ int melf_jpeg_probe_batch(const uint8_t* const* data, const size_t* sizes, int n
  * for upright 4:2:0 files.  Upright files, this library against the one before the switch existed, same lease: 1.962 / 1.981 against
  * 1.981 / 1.976 ms a call.
  * Out of scope: a tag anywhere but IFD0 of the first Exif APP1 (a second Exif block that asks for a rotation sends the file to the
- * host); progressive and multi-scan files, which stay unsupported with or without a tag; a 4:2:0 fast path for oriented files. */
+ * host); progressive files unless melf_ctx_set_jpeg_progressive is on too (below), and multi-scan sequential files, which stay
+ * unsupported with or without a tag; a 4:2:0 fast path for oriented files. */
 /* The header check that takes the tag: H and W are the STORED size, *orientation is 1..8 (1 when the tag is absent, unreadable or
  * outside 1..8, which Pillow and cv2 leave alone too), *supported is what melf_jpeg_probe would answer if the file had no tag.  The
  * upright size is W x H for codes 5-8. */
@@ -805,6 +806,54 @@ int melf_jpeg_probe_oriented_batch(const uint8_t* const* data, const size_t* siz
                                    int32_t* supported);
 int melf_ctx_set_jpeg_orientation(melf_ctx* ctx, int on);
 int melf_ctx_get_jpeg_orientation(melf_ctx* ctx, int* on);
+
+/* ---- Progressive JPEG files (SOF2): phones, web exporters, jpegtran -progressive, cameras' "optimised" mode ----
+ * melf_jpeg_probe and the probes above report such a file unsupported (reason "... progressive ..."), and by default every decode call
+ * gives it status 1 for the caller's host decoder; none of that changes.  melf_ctx_set_jpeg_progressive(ctx, 1) makes
+ * melf_jpeg_decode_batch, melf_jpeg_process_batch, melf_jpeg_process_files and melf_jpeg_process_files_begin / _end of that context take
+ * progressive files of the subset below.  Off at context creation; with it off every JPEG entry point behaves exactly as before,
+ * status codes and melf_last_error texts included.  Not while a _begin call is in flight.  Independent of the orientation switch: a
+ * progressive file with an EXIF orientation 2..8 is taken when both are on.
+ * Taken: SOF2 with 8-bit samples; components, sampling, JFIF / Adobe / component-id and empty-image rules exactly as for baseline
+ * files; at most MELF_JPEG_PROG_SCANS_MAX scans, each well formed (Ss = 0 implies Se = 0, a DC scan of 1..ncomp components in frame
+ * order; Ss > 0 implies one component and Ss <= Se <= 63; Ah = 0 or Al = Ah - 1; Al <= 13) and consistent (a first scan covers only
+ * coefficients not sent before, a refinement only coefficients whose precision is Ah, a component's AC scans follow its first DC
+ * scan: libjpeg only warns about an inconsistent script, here it is unsupported); after the last scan EVERY coefficient of every
+ * component at full precision -- libjpeg smooths blocks whose AC precision is incomplete, and then the pixels are no longer those of
+ * the coefficient blocks, so a file that ends early in its script or never sends some band is unsupported; Huffman table ids 0..3,
+ * redefined between scans at will (a scan uses the tables in force at its SOS; a table it needs must exist and pass libjpeg's checks;
+ * a DC refinement needs none); quantisation tables as in force at the first SOS (a DQT behind it: unsupported); DRI, also between
+ * scans (the interval counts the MCUs of the scan it applies to -- single blocks in a non-interleaved scan); bytes behind EOI are
+ * ignored.  Entropy-coded data that run out before a scan's blocks are done, an RSTn out of sequence or a Huffman code that does not
+ * exist give MELF_JPEG_CORRUPT and a zero-filled frame, and so does a file whose bytes end inside a scan.  The 4 MB limit of
+ * restart-less baseline scans does not apply.
+ * Semantics, bit for bit: the frame libjpeg(-turbo) decodes from the file with its defaults.  Every scan is accumulated into the
+ * coefficient blocks (k_jpeg_prog_scan, melf_jpeg_prog.h; timed as MELF_K_JPEG_HUFF): one wave per (file, scan, restart interval),
+ * one launch per LEVEL of scans -- a scan's level is one more than the highest level of the earlier scans that send a coefficient it
+ * sends too, so the scans of a level touch no common coefficient and run side by side (libjpeg's default colour script of ten
+ * scans has three levels) --, then the baseline decoder's IDCT, upsampling, colour and orientation stages run unchanged, on the
+ * window they always ran on; the coefficient area of a progressive file is zeroed and decoded whole.  The host walks a progressive
+ * file's entropy-coded bytes once, to find its scans and restart intervals; a call without a progressive file launches what it
+ * launched before.
+ * Measured on one MI355X, melf_jpeg_process_batch on the 640 x 480 fixture frames re-saved progressive at quality 95 (50 KB a file):
+ * 256 / 1024 files a call take 150 / 305 ms (1.7 K / 3.4 K files/s) without restart markers, where a scan is ONE sequential chain on
+ * one lane, and 31 / 111 ms (8.3 K / 9.3 K files/s) with a restart interval of one MCU row; the host branch such files took reads
+ * 1.4 - 1.5 K files/s.  A call of 512 baseline + 512 progressive files takes 161 ms.  The baseline files' own rate is unchanged.
+ * What a call pays is the LATENCY of one file's chain, not a rate: a 256-file call with 1 / 8 / 32 / 128 / 256 restart-less
+ * progressive files among baseline ones takes 116 / 121 / 125 / 129 / 137 ms, where Pillow on 8 threads for those files plus the GPU
+ * call for the rest takes 4 / 15 / 43 / 140 / 282 ms (profiles/jpeg_prog/jpeg_prog_rate.txt): the switch pays from about half a chunk
+ * of progressive files on, or for files with restart markers.  That is why it is opt-in everywhere, get_meter_values included
+ * (METERELF_JPEG_PROGRESSIVE=gpu). */
+#define MELF_JPEG_PROG_SCANS_MAX 32
+enum { MELF_JPEG_TAKE_ORIENTED = 1, MELF_JPEG_TAKE_PROGRESSIVE = 2 };
+int melf_ctx_set_jpeg_progressive(melf_ctx* ctx, int on);
+int melf_ctx_get_jpeg_progressive(melf_ctx* ctx, int* on);
+/* The header check with switches: *supported is what the decode calls of a context with the switches `flags` (MELF_JPEG_TAKE_*) on
+ * would answer from the headers; H and W are the STORED size, *orientation the EXIF code 1..8 whether or not oriented files are
+ * taken.  With flags 0 this is melf_jpeg_probe plus the orientation code.  melf_last_error holds the reason of a refusal. */
+int melf_jpeg_probe_flags(const uint8_t* data, size_t size, int flags, int32_t* H, int32_t* W, int32_t* orientation, int32_t* supported);
+int melf_jpeg_probe_flags_batch(const uint8_t* const* data, const size_t* sizes, int n, int flags, int32_t* H, int32_t* W,
+                                int32_t* orientation, int32_t* supported);
 
 /* Decodes n files of H x W pixels.  out: n*H*W*3 bytes, on the host (out_on_device = 0) or in HBM.
  * Synchronises the context's stream. */

@@ -24,7 +24,12 @@ everything when METERELF_DECODE=host, is decoded on the host by Pillow on a smal
 (METERELF_DECODE_THREADS, default min(8, cpu count); Pillow releases the GIL).  cv2.imread applies the EXIF orientation tag: a
 JPEG file that carries one (a camera mounted on its side, a phone) is decoded on the GPU too and comes out upright, byte for byte
 the frame the host branch rotates (the readers are made with MeterReader's jpeg_orientation switch on);
-METERELF_JPEG_ORIENT=host sends such files through the host branch instead, as before the GPU took them.
+METERELF_JPEG_ORIENT=host sends such files through the host branch instead, as before the GPU took them.  Progressive JPEG files
+(phones, web exporters) go through the host branch (METERELF_JPEG_PROGRESSIVE=host, the default); METERELF_JPEG_PROGRESSIVE=gpu
+decodes them on the GPU (MeterReader's jpeg_progressive switch; one that the GPU decoder does not take -- an incomplete or
+inconsistent scan script -- still goes to the host).  The default follows the measurement (profiles/jpeg_prog/jpeg_prog_rate.txt): a
+progressive scan without restart markers is one sequential chain on the GPU, so a chunk takes the time of its slowest file's chain
+however few progressive files it holds, and only lists made mostly of progressive files, or of files with restart markers, gain.
 """
 import collections
 import hashlib
@@ -72,17 +77,24 @@ def _jpeg_orientation_on_gpu() -> bool:
     return os.getenv('METERELF_JPEG_ORIENT', 'gpu') != 'host'
 
 
+def _jpeg_progressive_on_gpu() -> bool:
+    """METERELF_JPEG_PROGRESSIVE=gpu decodes progressive JPEG files on the GPU; 'host' (the default) leaves them to the host branch."""
+    return os.getenv('METERELF_JPEG_PROGRESSIVE', 'host') == 'gpu'
+
+
 def _reader_key(params, blob, device: int) -> bytes:
     env = ';'.join('%s=%s' % (k, os.environ[k]) for k in _ENV_IN_KEY if k in os.environ)
-    orient = b'|orient%d|' % _jpeg_orientation_on_gpu()   # a reader keeps the setting it was made with
+    orient = b'|orient%d|prog%d|' % (_jpeg_orientation_on_gpu(), _jpeg_progressive_on_gpu())   # a reader keeps the settings it was made with
     return hashlib.sha1(blob.tobytes() + repr(list(params.dial_names)).encode() + b'|dev%d|' % device + orient + env.encode()).digest()
 
 
 def _with_jpeg_orientation(reader):
-    """Turns a new reader's switch on (MeterReader.set_jpeg_orientation) unless the host branch is asked for; a reader from the
-    cache has it already (the setting is part of its key)."""
+    """Turns a new reader's switches on (MeterReader.set_jpeg_orientation, set_jpeg_progressive) unless the host branch is asked for;
+    a reader from the cache has them already (the settings are part of its key)."""
     if _jpeg_orientation_on_gpu() and hasattr(reader, 'set_jpeg_orientation') and not getattr(reader, 'jpeg_orientation', False):
         reader.set_jpeg_orientation(True)
+    if _jpeg_progressive_on_gpu() and hasattr(reader, 'set_jpeg_progressive') and not getattr(reader, 'jpeg_progressive', False):
+        reader.set_jpeg_progressive(True)
     return reader
 
 

@@ -231,6 +231,7 @@ EXPORTS = [
     'melf_jpeg_probe', 'melf_jpeg_probe_batch', 'melf_jpeg_decode_batch', 'melf_jpeg_clean_segment', 'melf_jpeg_process_batch',
     'melf_jpeg_process_files', 'melf_jpeg_process_files_begin', 'melf_jpeg_process_files_end', 'melf_jpeg_files_in_flight_max', 'melf_ctx_files_stats', 'melf_files_open_probe',
     'melf_jpeg_probe_oriented', 'melf_jpeg_probe_oriented_batch', 'melf_ctx_set_jpeg_orientation', 'melf_ctx_get_jpeg_orientation',
+    'melf_jpeg_probe_flags', 'melf_jpeg_probe_flags_batch', 'melf_ctx_set_jpeg_progressive', 'melf_ctx_get_jpeg_progressive',
 ]
 
 _lib = None
@@ -323,6 +324,10 @@ def lib():
     L.melf_jpeg_probe_oriented_batch.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
     L.melf_ctx_set_jpeg_orientation.argtypes = [vp, C.c_int]
     L.melf_ctx_get_jpeg_orientation.argtypes = [vp, C.POINTER(C.c_int)]
+    L.melf_jpeg_probe_flags.argtypes = [vp, C.c_size_t, C.c_int, i32p, i32p, i32p, i32p]
+    L.melf_jpeg_probe_flags_batch.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.melf_ctx_set_jpeg_progressive.argtypes = [vp, C.c_int]
+    L.melf_ctx_get_jpeg_progressive.argtypes = [vp, C.POINTER(C.c_int)]
     L.melf_jpeg_decode_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]
     L.melf_jpeg_process_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.melf_jpeg_process_files.argtypes = [vp, vp, C.c_int, i32p, i32p, vp, vp]
@@ -1075,6 +1080,35 @@ def jpeg_probe_oriented_batch(files):
     return H, W, o, ok
 
 
+JPEG_TAKE_ORIENTED = 1      # MELF_JPEG_TAKE_*: the switches a probe answers for
+JPEG_TAKE_PROGRESSIVE = 2
+
+
+def jpeg_probe_flags(data, flags):
+    """(H, W, orientation, supported, reason) of a JPEG file's bytes as the decode calls of a context with the switches `flags`
+    (JPEG_TAKE_ORIENTED | JPEG_TAKE_PROGRESSIVE) on answer from the headers: H and W are the STORED size, orientation is the EXIF code
+    1..8 whether or not oriented files are taken.  With flags 0: jpeg_probe plus the orientation.  Header parse only, no GPU."""
+    L = lib()
+    H, W, o, ok = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    if isinstance(data, np.ndarray):
+        p = _ptr(data)
+    else:
+        data = data if isinstance(data, bytes) else bytes(data)
+        p = C.cast(C.c_char_p(data), C.c_void_p)  # no copy: the bytes object outlives the call
+    check(L.melf_jpeg_probe_flags(p, len(data), int(flags), C.byref(H), C.byref(W), C.byref(o), C.byref(ok)))
+    return H.value, W.value, o.value, bool(ok.value), L.melf_last_error().decode()
+
+
+def jpeg_probe_flags_batch(files, flags):
+    """jpeg_probe_flags of many files' bytes in one call: (H, W, orientation, supported) int32 arrays; H and W are STORED sizes."""
+    n = len(files)
+    (H, W, o, ok) = (np.zeros(n, np.int32), np.zeros(n, np.int32), np.ones(n, np.int32), np.zeros(n, np.int32))
+    if n:
+        (ptrs, sizes, keep) = _file_table(files)
+        check(lib().melf_jpeg_probe_flags_batch(ptrs, sizes, n, int(flags), _ptr(H), _ptr(W), _ptr(o), _ptr(ok)))
+    return H, W, o, ok
+
+
 def jpeg_probe_batch(files):
     """Header check of many files' bytes in one call: (H, W, supported) int32 arrays."""
     n = len(files)
@@ -1653,6 +1687,16 @@ class Context:
     def jpeg_orientation(self):
         on = C.c_int(0)
         check(self._L.melf_ctx_get_jpeg_orientation(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def set_jpeg_progressive(self, on):
+        """Progressive JPEG files (SOF2) of the subset include/meterelf_hip.h states are decoded by the jpeg_* calls of this context
+        instead of coming back unsupported (melf_ctx_set_jpeg_progressive).  Off by default."""
+        check(self._L.melf_ctx_set_jpeg_progressive(self._h, int(bool(on))))
+
+    def jpeg_progressive(self):
+        on = C.c_int(0)
+        check(self._L.melf_ctx_get_jpeg_progressive(self._h, C.byref(on)))
         return bool(on.value)
 
     def set_frames_resident(self, on):

@@ -17,12 +17,16 @@
 //   J1     k_jpeg_huff      one workgroup per image, one lane per bit-stream segment (speculative decode until
 //                           the segments' exit states reach a fixed point) -> int16 coefficient blocks in decode order
 //          k_jpeg_huff_rst  streams with restart intervals: one lane per interval, no speculation needed
+//          k_jpeg_prog_scan progressive files (SOF2), for a caller that asked for them (melf_ctx_set_jpeg_progressive): every scan
+//                           accumulated into the same coefficient blocks, one wave per (file, scan, restart interval), one launch
+//                           per level of scans that depend on each other (melf_jpeg_prog.h); J2 and J3 then run as for any file
 //   J2     k_jpeg_idct      one thread per 8x8 block: dequantise + ISLOW IDCT -> u8 planes
 //   J3     k_jpeg_color420  8 pixels per thread: fancy upsample + YCC->BGR -> NHWC frame (k_jpeg_color: other modes)
 //          k_jpeg_color_exif  files with an EXIF orientation 2-8 (when the caller asked for them): the same conversion in
 //                           stored geometry, each pixel written where the upright frame has it
 #include "melf_internal.h"
 #include "melf_jpeg_orient_addr.h"
+#include "melf_jpeg_prog.h"
 #include "melf_threads.h"
 
 #include <emmintrin.h>
@@ -58,13 +62,21 @@ struct JpegHeader {
     int restart_interval = 0;
     uint16_t qt[4][64];
     bool qt_set[4] = {false, false, false, false};
-    HuffSpec dc[2], ac[2];
+    HuffSpec dc[4], ac[4];      // ids 2 and 3: progressive files only
     size_t scan_begin = 0;
     bool saw_jfif = false, saw_adobe = false, saw_exif = false;
     int orient = 1;             // EXIF orientation of the first Exif APP1 (1 when absent, unreadable or outside 1..8)
+    int orient_tag = 1;         // the same whether or not the caller takes oriented files
     int adobe_transform = 0;
     const char* why = nullptr;  // non-NULL: a valid-looking file this decoder does not handle
+    // A progressive file (SOF2) that is taken: its scans (byte offsets relative to scan_begin, the first scan's first byte), the
+    // distinct Huffman tables they use, and where their restart intervals begin
+    bool progressive = false;
+    std::vector<jpeg_prog::Scan> pscans;
+    std::vector<jpeg_prog::Huff> ptabs;
+    std::vector<uint32_t> prst;
 };
+constexpr int TAKE_ORIENTED = 1, TAKE_PROGRESSIVE = 2;   // MELF_JPEG_TAKE_*: what a caller's switches make the parser accept
 
 static inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
 
@@ -113,27 +125,126 @@ static const char* huff_spec_flaw(const HuffSpec& t, const bool dc)
     return nullptr;
 }
 
-// take_orient: a file with an orientation tag 2..8 is one for the GPU (h.orient says which); otherwise it is unsupported, as ever.
-static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h, const bool take_orient = false)
+// The rules on the frame header that do not depend on the kind of scan: sets h.why, and makes a greyscale frame 1x1.
+static void frame_rules(JpegHeader& h)
 {
-    for (int i = 0; i < 2; ++i) { h.dc[i].set = false; h.ac[i].set = false; }
+    if (h.H <= 0 || h.W <= 0) { h.why = "empty image"; return; }
+    if (h.ncomp == 3) {
+        if (h.saw_adobe && h.adobe_transform != 1) h.why = "Adobe marker says the data are not YCbCr";
+        else if (!h.saw_jfif && !h.saw_adobe && h.id[0] == 'R' && h.id[1] == 'G' && h.id[2] == 'B') h.why = "RGB component ids";
+        else if (h.hs[1] != 1 || h.vs[1] != 1 || h.hs[2] != 1 || h.vs[2] != 1) h.why = "subsampled chroma with sampling factors above 1";
+        else if (!((h.hs[0] == 1 && h.vs[0] == 1) || (h.hs[0] == 2 && h.vs[0] == 1) || (h.hs[0] == 2 && h.vs[0] == 2)))
+            h.why = "luma sampling other than 1x1, 2x1, 2x2";
+    } else {
+        h.hs[0] = h.vs[0] = 1;  // a single-component scan is never interleaved: one block per MCU
+    }
+}
+
+struct HuffSlow;
+static void build_huff(const HuffSpec& t, HuffSlow* slow);
+
+// What the parser keeps while it goes through a progressive file's scans (T.81 G.1.1.1.1 and libjpeg's progressive decoder).
+struct ProgState {
+    int8_t bits[3][64];   // per coefficient: -1 = not sent yet, else the precision (Al) it has been brought to
+    int dc_idx[4], ac_idx[4];   // where table id t, as defined now, stands in h.ptabs (-1: not built)
+    bool started = false;
+    ProgState() { memset(bits, -1, sizeof(bits)); for (int t = 0; t < 4; ++t) dc_idx[t] = ac_idx[t] = -1; }
+};
+static jpeg_prog::File prog_file_geometry(const JpegHeader& h)
+{
+    jpeg_prog::File f;
+    memset(&f, 0, sizeof(f));
+    f.ncomp = (uint8_t)h.ncomp; f.hs0 = (uint8_t)h.hs[0]; f.vs0 = (uint8_t)h.vs[0];
+    f.mcus_x = (uint16_t)((h.W + 8 * h.hs[0] - 1) / (8 * h.hs[0]));
+    f.mcus_y = (uint16_t)((h.H + 8 * h.vs[0] - 1) / (8 * h.vs[0]));
+    f.rbx0 = (uint16_t)((h.W + 7) / 8); f.rby0 = (uint16_t)((h.H + 7) / 8);
+    f.rbxc = (uint16_t)(((h.W + h.hs[0] - 1) / h.hs[0] + 7) / 8); f.rbyc = (uint16_t)(((h.H + h.vs[0] - 1) / h.vs[0] + 7) / 8);
+    return f;
+}
+// One SOS of a progressive file (s: its parameters): the scan's record, or why the file is not taken.
+static const char* prog_scan_header(JpegHeader& h, ProgState& ps, const uint8_t* s, jpeg_prog::Scan& sc)
+{
+    memset(&sc, 0, sizeof(sc));
+    sc.ac_tab = jpeg_prog::NO_TABLE;
+    for (int k = 0; k < 3; ++k) sc.dc_tab[k] = jpeg_prog::NO_TABLE;
+    const int ns = s[0];
+    if (ns < 1 || ns > h.ncomp) return "progressive scan with a component count outside 1..components of the frame";
+    const uint8_t* e = s + 1 + 2 * ns;
+    const int Ss = e[0], Se = e[1], Ah = e[2] >> 4, Al = e[2] & 15;
+    if (Ss == 0 ? Se != 0 : (ns != 1 || Se < Ss || Se > 63)) return "progressive scan whose band is not DC alone or Ss <= Se <= 63 of one component";
+    if (Ah != 0 && Al != Ah - 1) return "progressive scan whose Al is not Ah - 1";
+    if (Al > 13) return "progressive scan with Al above 13";
+    sc.ns = (uint8_t)ns; sc.Ss = (uint8_t)Ss; sc.Se = (uint8_t)Se; sc.Ah = (uint8_t)Ah; sc.Al = (uint8_t)Al;
+    sc.restart_interval = (uint16_t)h.restart_interval;
+    int prev = -1;
+    for (int k = 0; k < ns; ++k) {
+        const int cid = s[1 + 2 * k];
+        int c = -1;
+        for (int q = 0; q < h.ncomp; ++q) if (h.id[q] == cid) c = q;
+        if (c <= prev) return "progressive scan whose components are not in the frame header's order";
+        prev = c;
+        sc.comp[k] = (uint8_t)c;
+        const int td = s[2 + 2 * k] >> 4, ta = s[2 + 2 * k] & 15;
+        if (td > 3 || ta > 3) return "Huffman table id above 3";
+        if (Ss > 0 && ps.bits[c][0] < 0) return "inconsistent progression: an AC scan before the component's first DC scan";
+        for (int z = Ss; z <= Se; ++z) {
+            if (Ah == 0 ? ps.bits[c][z] >= 0 : ps.bits[c][z] != Ah)
+                return Ah == 0 ? "inconsistent progression: a first scan over coefficients already sent"
+                               : "inconsistent progression: a refinement of coefficients whose precision is not Ah";
+            ps.bits[c][z] = (int8_t)Al;
+        }
+        // the tables in force now: a DC first scan decodes with its DC tables, every AC scan with its AC table
+        const bool need_dc = Ss == 0 && Ah == 0, need_ac = Ss > 0;
+        if (need_dc || need_ac) {
+            const HuffSpec& t = need_dc ? h.dc[td] : h.ac[ta];
+            int& idx = need_dc ? ps.dc_idx[td] : ps.ac_idx[ta];
+            if (!t.set) return "missing Huffman table";
+            if (idx < 0) {
+                if (const char* flaw = huff_spec_flaw(t, need_dc)) return flaw;
+                if (h.ptabs.size() >= 255) return "too many Huffman tables";
+                idx = (int)h.ptabs.size();
+                h.ptabs.emplace_back();
+                build_huff(t, (HuffSlow*)&h.ptabs.back());
+            }
+            if (need_dc) sc.dc_tab[k] = (uint8_t)idx; else sc.ac_tab = (uint8_t)idx;
+        }
+    }
+    return nullptr;
+}
+
+// take: TAKE_ORIENTED -- a file with an orientation tag 2..8 is one for the GPU (h.orient says which); TAKE_PROGRESSIVE -- so is a
+// progressive file of the subset include/meterelf_hip.h states (h.progressive, h.pscans).  Otherwise they are unsupported, as ever.
+static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h, const int take = 0)
+{
+    const bool take_orient = (take & TAKE_ORIENTED) != 0, take_prog = (take & TAKE_PROGRESSIVE) != 0;
+    for (int i = 0; i < 4; ++i) { h.dc[i].set = false; h.ac[i].set = false; }
     if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return -1;
     size_t i = 2;
-    bool have_sof = false;
+    bool have_sof = false, high_table = false;
+    ProgState ps;
     for (;;) {
         while (i < n && d[i] != 0xFF) ++i;  // tolerate garbage between segments like libjpeg's next_marker
         while (i < n && d[i] == 0xFF) ++i;
         if (i >= n) return -1;
         const int m = d[i++];
         if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;  // parameterless
-        if (m == 0xD9) return -1;                                           // EOI before SOS
+        if (m == 0xD9) {
+            if (h.progressive && ps.started) goto prog_done;
+            return -1;                                                      // EOI before SOS
+        }
         if (i + 2 > n) return -1;
         const int L = be16(d + i);
         if (L < 2 || i + L > n) return -1;
         const uint8_t* s = d + i + 2;
         const int len = L - 2;
+        // One frame header per file: once a progressive frame is taken, any further SOFn (libjpeg: "duplicate SOF") makes the file
+        // unsupported -- the rules on the frame were applied to the first one, and the scans recorded so far rest on its geometry.
+        if (h.progressive && m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
+            h.why = "second frame header in a progressive file (libjpeg rejects it)";
+            return 0;
+        }
         switch (m) {
-            case 0xC0: case 0xC1: {  // baseline / extended sequential, Huffman
+            case 0xC0: case 0xC1: sof_taken: {  // baseline / extended sequential, Huffman -- and progressive, where the caller takes it
                 if (len < 6) return -1;
                 if (s[0] != 8) { h.why = "sample precision is not 8 bits"; }
                 h.H = be16(s + 1); h.W = be16(s + 3); h.ncomp = s[5];
@@ -143,13 +254,19 @@ static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h, const bool t
                     h.id[c] = s[6 + 3 * c]; h.hs[c] = s[7 + 3 * c] >> 4; h.vs[c] = s[7 + 3 * c] & 15; h.tq[c] = s[8 + 3 * c] & 3;
                 }
                 have_sof = true;
+                if (m == 0xC2) h.progressive = true;
+                else if (high_table) h.why = "Huffman table id above 1";
                 break;
             }
-            case 0xC2: case 0xC3: case 0xC5: case 0xC6: case 0xC7: case 0xC9: case 0xCA: case 0xCB: case 0xCD: case 0xCE: case 0xCF:
+            case 0xC2:
+                if (take_prog && !have_sof) goto sof_taken;
+                // fallthrough
+            case 0xC3: case 0xC5: case 0xC6: case 0xC7: case 0xC9: case 0xCA: case 0xCB: case 0xCD: case 0xCE: case 0xCF:
                 h.why = "not a baseline sequential Huffman JPEG (progressive / lossless / arithmetic)";
                 if (len >= 6) { h.H = be16(s + 1); h.W = be16(s + 3); }
                 return 0;
             case 0xDB: {  // DQT
+                if (ps.started) { h.why = "quantisation table defined after the first scan of a progressive file"; return 0; }
                 int o = 0;
                 while (o < len) {
                     const int pq = s[o] >> 4, tq = s[o] & 15;
@@ -172,7 +289,10 @@ static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h, const bool t
                     int total = 0;
                     for (int l = 1; l <= 16; ++l) total += s[o + l];
                     if (total > 256 || o + 17 + total > len || tc > 1) return -1;
-                    if (th > 1) { h.why = "Huffman table id above 1"; o += 17 + total; continue; }
+                    // ids 2 and 3 are a progressive file's to use; anywhere else they make the file unsupported, as ever
+                    if (th > 3 || (th > 1 && !take_prog)) { h.why = "Huffman table id above 1"; o += 17 + total; continue; }
+                    if (th > 1 && !h.progressive) { if (have_sof) h.why = "Huffman table id above 1"; else high_table = true; }
+                    (tc ? ps.ac_idx[th] : ps.dc_idx[th]) = -1;   // a scan after this one builds the new definition
                     HuffSpec& t = tc ? h.ac[th] : h.dc[th];
                     t.bits[0] = 0;
                     for (int l = 1; l <= 16; ++l) t.bits[l] = s[o + l];
@@ -195,6 +315,7 @@ static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h, const bool t
                         // meterelf_amd/_image.py).  Only the first Exif block counts; a later one that asks again is left to the host.
                 if (len >= 14 && !memcmp(s, "Exif\0\0", 6)) {
                     const int o = exif_orientation(s + 6, len - 6);
+                    if (o > 1 && !h.saw_exif) h.orient_tag = o;
                     if (o > 1 && (!take_orient || h.saw_exif)) h.why = "EXIF orientation other than top-left (decoded and rotated on the host)";
                     else if (o > 1) h.orient = o;
                     h.saw_exif = true;
@@ -208,6 +329,41 @@ static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h, const bool t
                 if (len < 1) return -1;
                 const int ns = s[0];
                 if (len < 1 + 2 * ns + 3) return -1;
+                if (h.progressive) {
+                    if (h.why) return 0;   // refused by a segment between the scans: no further scan is looked at
+                    if (!ps.started) {   // the frame must be one for the decoder before any scan byte is looked at
+                        if (!h.why) frame_rules(h);
+                        for (int c = 0; c < h.ncomp && !h.why; ++c)
+                            if (!h.qt_set[h.tq[c]]) h.why = "missing quantisation table";
+                        if (h.why) return 0;
+                        h.scan_begin = i + L;
+                        ps.started = true;
+                    }
+                    if (h.pscans.size() >= (size_t)MELF_JPEG_PROG_SCANS_MAX) { h.why = "progressive file with more scans than MELF_JPEG_PROG_SCANS_MAX"; return 0; }
+                    jpeg_prog::Scan sc;
+                    if (const char* flaw = prog_scan_header(h, ps, s, sc)) { h.why = flaw; return 0; }
+                    // the scan's bytes, once: where it ends and where its restart intervals begin
+                    const jpeg_prog::File geo = prog_file_geometry(h);
+                    const uint32_t expected = jpeg_prog::scan_intervals(geo, sc);
+                    sc.off = (uint32_t)(i + L - h.scan_begin);
+                    sc.rst_first = (uint32_t)h.prst.size();
+                    h.prst.resize(h.prst.size() + expected);
+                    uint32_t found = 0;
+                    const size_t end = jpeg_prog::walk_scan(d, i + L, n, h.prst.data() + sc.rst_first, expected, &found);
+                    if (end >= n) return -1;   // the data end inside a scan: a truncated file
+                    sc.len = (uint32_t)(end - (i + L));
+                    sc.rst_count = found;
+                    for (uint32_t k = found; k < expected; ++k) h.prst[sc.rst_first + k] = 0;
+                    for (const jpeg_prog::Scan& t : h.pscans) {   // the level: behind every earlier scan that touches a coefficient of this one
+                        bool shared = false;
+                        for (int a = 0; a < sc.ns; ++a)
+                            for (int b = 0; b < t.ns; ++b) shared = shared || sc.comp[a] == t.comp[b];
+                        if (shared && sc.Ss <= t.Se && t.Ss <= sc.Se && t.level + 1 > sc.level) sc.level = (uint8_t)(t.level + 1);
+                    }
+                    h.pscans.push_back(sc);
+                    i = end;
+                    continue;
+                }
                 if (ns != h.ncomp) { h.why = "more than one scan (non-interleaved components)"; return 0; }
                 for (int k = 0; k < ns; ++k) {
                     const int cid = s[1 + 2 * k];
@@ -226,18 +382,17 @@ static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h, const bool t
         }
         i += L;
     }
+prog_done:
+    // libjpeg smooths blocks whose AC coefficients have not reached full precision (jdcoefct's block smoothing): the pixels are
+    // those of the coefficient blocks only when every scan of the script has arrived
+    for (int c = 0; c < h.ncomp; ++c)
+        for (int z = 0; z < 64; ++z)
+            if (ps.bits[c][z] != 0) { h.why = "progressive script incomplete: not every coefficient reaches full precision (libjpeg smooths such blocks)"; return 0; }
+    return 0;
 done:
     if (h.why) return 0;
-    if (h.H <= 0 || h.W <= 0) { h.why = "empty image"; return 0; }
-    if (h.ncomp == 3) {
-        if (h.saw_adobe && h.adobe_transform != 1) h.why = "Adobe marker says the data are not YCbCr";
-        else if (!h.saw_jfif && !h.saw_adobe && h.id[0] == 'R' && h.id[1] == 'G' && h.id[2] == 'B') h.why = "RGB component ids";
-        else if (h.hs[1] != 1 || h.vs[1] != 1 || h.hs[2] != 1 || h.vs[2] != 1) h.why = "subsampled chroma with sampling factors above 1";
-        else if (!((h.hs[0] == 1 && h.vs[0] == 1) || (h.hs[0] == 2 && h.vs[0] == 1) || (h.hs[0] == 2 && h.vs[0] == 2)))
-            h.why = "luma sampling other than 1x1, 2x1, 2x2";
-    } else {
-        h.hs[0] = h.vs[0] = 1;  // a single-component scan is never interleaved: one block per MCU
-    }
+    frame_rules(h);
+    if (h.H <= 0 || h.W <= 0) return 0;
     for (int c = 0; c < h.ncomp && !h.why; ++c) {
         if (!h.qt_set[h.tq[c]]) h.why = "missing quantisation table";
         else if (!h.dc[h.td[c]].set || !h.ac[h.ta[c]].set) h.why = "missing Huffman table";
@@ -264,7 +419,7 @@ int jpeg_probe(const uint8_t* data, size_t size, int* H, int* W, int* supported,
 int jpeg_probe_oriented(const uint8_t* data, size_t size, int* H, int* W, int* orientation, int* supported, std::string* why)
 {
     JpegHeader h;
-    if (parse_headers(data, size, h, true) != 0) {
+    if (parse_headers(data, size, h, TAKE_ORIENTED) != 0) {
         *H = *W = 0; *supported = 0; *orientation = 1;
         if (why) *why = "not a JPEG file or truncated headers";
         return 0;
@@ -274,10 +429,26 @@ int jpeg_probe_oriented(const uint8_t* data, size_t size, int* H, int* W, int* o
     return 0;
 }
 
+// What the decode calls of a context with the switches `flags` (MELF_JPEG_TAKE_*) answer from the headers.  The orientation code is
+// reported whether or not files that carry one are taken.
+int jpeg_probe_flags(const uint8_t* data, size_t size, int flags, int* H, int* W, int* orientation, int* supported, std::string* why)
+{
+    JpegHeader h;
+    if (parse_headers(data, size, h, flags & (TAKE_ORIENTED | TAKE_PROGRESSIVE)) != 0) {
+        *H = *W = 0; *supported = 0; *orientation = 1;
+        if (why) *why = "not a JPEG file or truncated headers";
+        return 0;
+    }
+    *H = h.H; *W = h.W; *orientation = h.orient_tag; *supported = h.why ? 0 : 1;
+    if (why) *why = h.why ? h.why : "";
+    return 0;
+}
+
 // The orientation alone (1..8), from a walk over the marker segments in front of the frame header: what parse_headers records,
 // for a caller that orders a call's files before they are parsed.
-int jpeg_file_orientation(const uint8_t* d, size_t n)
+int jpeg_file_orientation(const uint8_t* d, size_t n, int* progressive)
 {
+    if (progressive) *progressive = 0;
     if (!d || n < 4 || d[0] != 0xFF || d[1] != 0xD8) return 1;
     size_t i = 2;
     for (;;) {
@@ -286,6 +457,7 @@ int jpeg_file_orientation(const uint8_t* d, size_t n)
         if (i >= n) return 1;
         const int m = d[i++];
         if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
+        if (m == 0xC2 && progressive) *progressive = 1;
         if (m == 0xD9 || m == 0xDA || (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC)) return 1;
         if (i + 2 > n) return 1;
         const int L = be16(d + i);
@@ -330,6 +502,8 @@ struct HuffSlow {  // canonical decode data (JPEG spec F.2.2.3) for code lengths
 };
 constexpr int SLOW_DW = 96;
 static_assert(sizeof(HuffSlow) == SLOW_DW * 4, "HuffSlow is copied to LDS as dwords");
+static_assert(sizeof(jpeg_prog::Huff) == sizeof(HuffSlow) && offsetof(jpeg_prog::Huff, valoff) == offsetof(HuffSlow, valoff) &&
+              offsetof(jpeg_prog::Huff, huffval) == offsetof(HuffSlow, huffval), "melf_jpeg_prog.h restates HuffSlow");
 
 static void build_huff(const HuffSpec& t, HuffSlow* slow)
 {
@@ -1277,6 +1451,64 @@ __global__ __launch_bounds__(T) void k_jpeg_huff_rst(const JpegImageDev* __restr
     if (tid == 0) status[img] = anybad ? 2 : 0;
 }
 
+// ------------------------------------------------- J1, progressive files: one scan ----
+// The scans of one LEVEL of every progressive file of a run (melf_jpeg_prog.h has the decoder and what it rests on).  One wave per
+// work item (file, scan, restart interval of that scan); an item whose file has no such scan, whose scan is of another level, or
+// whose file an earlier level found corrupt, leaves at once.  A scan's level is one more than the highest level among the earlier
+// scans of its file that send a coefficient it sends too (same component, overlapping band): levels are launched in order, one
+// launch each, so a scan finds what the scans it builds on left, and the scans of a level -- the first DC scan and the first AC
+// scans of all bands and components, say -- run side by side.  Inside a launch no wave waits for another: the intervals of a
+// scan touch different blocks, the scans of a level different coefficients.  The wave brings the records, the scan's tables and
+// their first-level lookup tables into LDS together; the decode itself is one sequential chain (a bit position that depends on
+// every symbol before it) and runs on the first lane, which is why melf_jpeg_prog.h keeps memory out of that chain.
+__global__ __launch_bounds__(64) void k_jpeg_prog_scan(const jpeg_prog::File* __restrict__ files, const jpeg_prog::Scan* __restrict__ scans,
+                                                       const jpeg_prog::Huff* __restrict__ tabs, const uint32_t* __restrict__ rst,
+                                                       const uint8_t* __restrict__ raw, int16_t* __restrict__ coefs,
+                                                       int32_t* __restrict__ status, const int level)
+{
+    __shared__ uint32_t sl[4 * SLOW_DW];
+    __shared__ uint16_t look[4 * jpeg_prog::LOOK_N];
+    __shared__ uint8_t nat[64];
+    __shared__ __attribute__((aligned(16))) int16_t stage[64];
+    __shared__ uint32_t recs[(sizeof(jpeg_prog::File) + sizeof(jpeg_prog::Scan)) / 4];
+    const int img = blockIdx.y, lane = threadIdx.x, s = blockIdx.z;
+    if ((uint32_t)s >= files[img].scan_count || scans[files[img].scan_first + (uint32_t)s].level != level || status[img] != 0) return;
+    {   // the two records, so that the decoder's loops read them from LDS (nothing it stores can alias them there)
+        constexpr int FD = sizeof(jpeg_prog::File) / 4, SD = sizeof(jpeg_prog::Scan) / 4;
+        if (lane < FD) recs[lane] = ((const uint32_t*)(files + img))[lane];
+        else if (lane < FD + SD) recs[lane] = ((const uint32_t*)(scans + files[img].scan_first + (uint32_t)s))[lane - FD];
+    }
+    __syncthreads();
+    const jpeg_prog::File& F = *(const jpeg_prog::File*)recs;
+    const jpeg_prog::Scan& sc = *(const jpeg_prog::Scan*)(recs + sizeof(jpeg_prog::File) / 4);
+    const uint32_t expected = jpeg_prog::scan_intervals(F, sc), it = blockIdx.x;
+    if (sc.rst_count != expected) {   // restart markers missing or surplus
+        if (it == 0 && lane == 0) status[img] = 2;
+        return;
+    }
+    if (it >= expected) return;
+    for (int i = lane; i < 4 * SLOW_DW; i += 64) {
+        const int t = i / SLOW_DW;
+        const int id = t < 3 ? sc.dc_tab[t] : sc.ac_tab;
+        sl[i] = id == jpeg_prog::NO_TABLE ? 0u : ((const uint32_t*)(tabs + F.tab_first + id))[i - t * SLOW_DW];
+    }
+    nat[lane] = c_zz2nat[lane];
+    __syncthreads();
+    for (int i = lane; i < 4 * jpeg_prog::LOOK_N; i += 64)
+        look[i] = jpeg_prog::look_entry((const jpeg_prog::Huff*)sl + i / jpeg_prog::LOOK_N, (uint32_t)(i % jpeg_prog::LOOK_N));
+    __syncthreads();
+    if (lane != 0) return;
+    const uint8_t* d = raw + F.raw_off + sc.off;
+    const uint32_t begin = rst[F.rst_first + sc.rst_first + it];
+    const uint32_t units = jpeg_prog::scan_units(F, sc);
+    const uint32_t u0 = sc.restart_interval ? it * sc.restart_interval : 0u;
+    const uint32_t nu = sc.restart_interval ? min(units - u0, (uint32_t)sc.restart_interval) : units;
+    int bad = begin > sc.len || (it > 0 && (begin < 2 || d[begin - 1] != 0xD0u + ((it - 1u) & 7u)));   // an RSTn out of sequence
+    if (!bad)
+        bad = jpeg_prog::decode_interval(F, sc, d, begin, sc.len, u0, nu, (const jpeg_prog::Huff*)sl, look, nat, coefs + (size_t)F.coef_first * 64, stage);
+    if (bad) status[img] = 2;
+}
+
 // ------------------------------------------------------------------ J2: IDCT ----
 // The "accurate integer" inverse DCT (libjpeg jidctint: Loeffler-Ligtenberg-Moschytz, 13-bit
 // constants, 2 extra bits kept between the passes).  Every shift below is part of the result.
@@ -1629,6 +1861,7 @@ struct JpegWorkspace {
     size_t status_cap = 0;
     // layout of the current batch inside the stage buffers
     size_t off_imgs = 0, off_qt = 0, off_slow = 0, off_scan = 0, total = 0;   // total: what is uploaded (records + tables)
+    size_t off_pfile = 0, off_pscan = 0, off_ptab = 0, off_prst = 0;          // progressive files: their records, scans, tables, intervals
     size_t scan_bytes = 0;      // device-only scan area behind them
     size_t coef_elems = 0, plane_bytes = 0;
     int max_blocks = 0;
@@ -1637,10 +1870,16 @@ struct JpegWorkspace {
     size_t max_par_scan = 0;    // longest clean scan among the former (bytes)
     // The batch as runs of consecutive files of one orientation code: J1..J3 are launched once per run, on the run's window of
     // the stored frame.  A batch without oriented files is one run of code 1 whose counts are the five above.
+    // A run of progressive files (prog) is decoded level by level (k_jpeg_prog_scan): prog_items[l] = the most restart intervals any
+    // scan of level l of its files has, prog_scans the most scans of a file; its files' coefficient blocks (prog_coef0, prog_coefs of them, in blocks) are zeroed in front of the first scan.
     struct Run {
         int first, n, code;
         int n_par, n_seq, n_420, max_blocks;
         size_t max_par_scan;
+        bool prog = false;
+        size_t prog_coef0 = 0, prog_coefs = 0;
+        std::vector<uint32_t> prog_items;
+        uint32_t prog_scans = 0;
     };
     std::vector<Run> runs;
 };
@@ -1704,16 +1943,17 @@ void jpeg_parsed_resize(JpegParsed* p, int n)   // keeps what it has allocated: 
     if (!p->slow.empty() && p->slow.size() < (size_t)n * 4) p->slow.resize((size_t)n * 4);
 }
 // take_orient: files with an orientation tag are taken, and H, W are then the UPRIGHT size (what a caller groups files by).
-void jpeg_parse_one(JpegParsed* p, int i, const uint8_t* data, size_t size, int* H, int* W, int* supported, bool take_orient)
+void jpeg_parse_one(JpegParsed* p, int i, const uint8_t* data, size_t size, int* H, int* W, int* supported, int take)
 {
     JpegHeader& h = p->hdr[i];
     h = JpegHeader();   // the object may be a previous call's
-    if (!data || parse_headers(data, size, h, take_orient) != 0) { *H = *W = 0; *supported = 0; return; }
+    if (!data || parse_headers(data, size, h, take) != 0) { h.progressive = false; *H = *W = 0; *supported = 0; return; }
     *H = jpeg_orient::swapped_h(h.orient, h.H, h.W); *W = jpeg_orient::swapped_w(h.orient, h.H, h.W); *supported = h.why ? 0 : 1;
-    if (!h.why && !p->slow.empty()) build_slow4(h, p->slow.data() + (size_t)i * 4);
+    if (!h.why && !h.progressive && !p->slow.empty()) build_slow4(h, p->slow.data() + (size_t)i * 4);   // (a progressive file's tables go with its scans)
 }
 void jpeg_parsed_free(JpegParsed* p) { delete p; }
 int jpeg_parsed_orientation(const JpegParsed* p, int i) { return p->hdr[i].orient; }
+int jpeg_parsed_progressive(const JpegParsed* p, int i) { return p->hdr[i].progressive ? 1 : 0; }
 
 // Host half of a batch: parse every file (unless `parsed` holds the headers already: files first .. first + n - 1 of that
 // pass, host_status filled), lay the batch out, fill the pinned stage buffer.
@@ -1722,7 +1962,7 @@ int jpeg_parsed_orientation(const JpegParsed* p, int i) { return p->hdr[i].orien
 // stored size gives after the swap its code asks for, and everything laid out here for it follows its STORED size.
 int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const size_t* sizes, int n, int H, int W,
                        int32_t* host_status, std::string* err, const JpegParsed* parsed, int first, const int* pidx,
-                       const uint8_t* pin_base, size_t pin_len, bool take_orient)
+                       const uint8_t* pin_base, size_t pin_len, int take)
 {
     if (!*pws) *pws = new JpegWorkspace();
     JpegWorkspace* w = *pws;
@@ -1736,7 +1976,7 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
         own.resize(n);
         par_for([&](int i) {
             JpegHeader& h = own[i];
-            if (!data[i] || parse_headers(data[i], sizes[i], h, take_orient) != 0) { host_status[i] = 2; return; }
+            if (!data[i] || parse_headers(data[i], sizes[i], h, take) != 0) { host_status[i] = 2; return; }
             if (h.why) { host_status[i] = 1; return; }
             if (jpeg_orient::swapped_h(h.orient, h.H, h.W) != H || jpeg_orient::swapped_w(h.orient, h.H, h.W) != W) { host_status[i] = 3; return; }
             host_status[i] = 0;
@@ -1766,6 +2006,10 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
     size_t coef_blocks = 0, plane_bytes = 0;
     int max_blocks = 0;
     std::vector<JpegImageDev> rec(n);
+    std::vector<jpeg_prog::File> pfile;   // one per file once the batch has a progressive file
+    size_t pscans = 0, ptabs = 0, prsts = 0;
+    for (int i = 0; i < n; ++i)
+        if (host_status[i] == 0 && hbase[hidx(i)].progressive) { pfile.resize(n); memset(pfile.data(), 0, (size_t)n * sizeof(jpeg_prog::File)); break; }
     for (int i = 0; i < n; ++i) {
         JpegImageDev& r = rec[i];
         memset(&r, 0, sizeof(r));
@@ -1773,6 +2017,14 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
         raw_off[i + 1] = raw_off[i];
         if (host_status[i] != 0) continue;
         const JpegHeader& h = hbase[hidx(i)];
+        if (h.progressive) {
+            jpeg_prog::File& f = pfile[i];
+            f = prog_file_geometry(h);
+            f.scan_first = (uint32_t)pscans; f.scan_count = (uint32_t)h.pscans.size();
+            f.tab_first = (uint32_t)ptabs; f.rst_first = (uint32_t)prsts;
+            f.coef_first = (uint32_t)coef_blocks;
+            pscans += h.pscans.size(); ptabs += h.ptabs.size(); prsts += h.prst.size();
+        }
         r.ok = 1;
         r.orient = (uint8_t)h.orient;
         r.ncomp = (uint8_t)h.ncomp; r.hs0 = (uint8_t)h.hs[0]; r.vs0 = (uint8_t)h.vs[0];
@@ -1796,8 +2048,9 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
         r.raw_off = direct ? (uint32_t)(data[i] + h.scan_begin - span_lo) : (uint32_t)raw_off[i];
         r.raw_len = (uint32_t)raw_len;
         raw_off[i + 1] = raw_off[i] + align_up(raw_len + 32, 64);   // k_jpeg_clean reads up to 20 bytes past the end
-        size_t region = align_up(raw_len + 128, 64);
-        if (h.restart_interval) {  // room for the table of interval offsets behind the scan
+        // (a progressive file is decoded from its raw bytes: no clean scan, no restart table in the scan area)
+        size_t region = h.progressive ? 128 : align_up(raw_len + 128, 64);
+        if (h.restart_interval && !h.progressive) {  // room for the table of interval offsets behind the scan
             const size_t mcus = (size_t)r.mcus_x * r.mcus_y;
             r.rst_cnt = (uint32_t)((mcus + h.restart_interval - 1) / h.restart_interval);  // expected; replaced by the number found
             r.rst_off = (uint32_t)region;                                                   // relative for now
@@ -1812,7 +2065,11 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
     w->off_imgs = 0;
     w->off_qt = align_up(w->off_imgs + (size_t)n * sizeof(JpegImageDev), 256);
     w->off_slow = align_up(w->off_qt + (size_t)n * 4 * 64 * sizeof(uint16_t), 256);
-    w->off_scan = align_up(w->off_slow + (size_t)n * 4 * sizeof(HuffSlow), 256);
+    w->off_pfile = align_up(w->off_slow + (size_t)n * 4 * sizeof(HuffSlow), 256);
+    w->off_pscan = align_up(w->off_pfile + pfile.size() * sizeof(jpeg_prog::File), 256);
+    w->off_ptab = align_up(w->off_pscan + pscans * sizeof(jpeg_prog::Scan), 256);
+    w->off_prst = align_up(w->off_ptab + ptabs * sizeof(jpeg_prog::Huff), 256);
+    w->off_scan = align_up(w->off_prst + prsts * sizeof(uint32_t), 256);
     w->total = w->off_scan;                 // uploaded: records + tables
     w->scan_bytes = scan_off[n] + 64;       // device only
     w->raw_total = direct ? (size_t)(span_hi - span_lo) + 64 : raw_off[n] + 64;
@@ -1856,7 +2113,8 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
         for (int t = 0; t < 4; ++t) {
             if (h.qt_set[t]) memcpy(qt + t * 64, h.qt[t], 128); else memset(qt + t * 64, 0, 128);
         }
-        if (tables_ready) memcpy(slow, parsed->slow.data() + (size_t)hidx(i) * 4, 4 * sizeof(HuffSlow));
+        if (h.progressive) memset(slow, 0, 4 * sizeof(HuffSlow));   // its tables go with its scans, below
+        else if (tables_ready) memcpy(slow, parsed->slow.data() + (size_t)hidx(i) * 4, 4 * sizeof(HuffSlow));
         else build_slow4(h, slow);
         // the entropy-coded segment as it is: stuffing, fill bytes and restart markers are taken out on the GPU (k_jpeg_clean),
         // which also writes the clean length and the restart table (r.rst_cnt: the EXPECTED number of intervals until then)
@@ -1875,6 +2133,20 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
         r.scan_len = 0;
         if (h.restart_interval) r.rst_off = (uint32_t)(scan_off[i] + r.rst_off);
         r.ok = h.restart_interval != 0 ? 2 : 1;
+        if (h.progressive) {
+            // The baseline kernels must pass this file by: ok = 3 is neither k_jpeg_huff's nor k_jpeg_huff_rst's, and with no raw
+            // bytes in the record k_jpeg_clean only zeroes the file's 128 bytes of the scan area.  Where the bytes are says the
+            // progressive record; the scans' records, tables and interval tables are copied as the parser left them.
+            jpeg_prog::File& f = pfile[i];
+            f.raw_off = r.raw_off; f.raw_len = r.raw_len;
+            r.raw_len = 0; r.restart_interval = 0; r.rst_off = 0; r.rst_cnt = 0;
+            r.scan_cap = (uint32_t)(scan_off[i + 1] - scan_off[i]);
+            r.ok = 3;
+            memcpy((jpeg_prog::Scan*)(base + w->off_pscan) + f.scan_first, h.pscans.data(), h.pscans.size() * sizeof(jpeg_prog::Scan));
+            memcpy((jpeg_prog::Huff*)(base + w->off_ptab) + f.tab_first, h.ptabs.data(), h.ptabs.size() * sizeof(jpeg_prog::Huff));
+            memcpy((uint32_t*)(base + w->off_prst) + f.rst_first, h.prst.data(), h.prst.size() * sizeof(uint32_t));
+            return;
+        }
         // longer than 1024 lanes x the segment length k_jpeg_huff can address (the raw length: the clean one is only known on
         // the GPU and at most 1/128 shorter)
         if (!h.restart_interval && r.raw_len > JPEG_MAX_PAR_SCAN) {
@@ -1892,9 +2164,24 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
     for (int i = 0; i < n; ++i) {
         // a file that is not decoded (zeros over the window) belongs to the run it stands in
         const int code = rec[i].ok ? rec[i].orient : (w->runs.empty() ? 1 : w->runs.back().code);
-        if (w->runs.empty() || w->runs.back().code != code) w->runs.push_back({i, 0, code, 0, 0, 0, 0, 0});
+        const bool prog = rec[i].ok ? rec[i].ok == 3 : (w->runs.empty() ? false : w->runs.back().prog);
+        if (w->runs.empty() || w->runs.back().code != code || w->runs.back().prog != prog) {
+            w->runs.push_back({i, 0, code, 0, 0, 0, 0, 0});
+            w->runs.back().prog = prog;
+        }
         JpegWorkspace::Run& run = w->runs.back();
         ++run.n;
+        if (rec[i].ok == 3) {
+            const jpeg_prog::File& f = pfile[i];
+            const JpegHeader& h = hbase[hidx(i)];
+            if (run.prog_coefs == 0) run.prog_coef0 = f.coef_first;
+            run.prog_coefs = f.coef_first + jpeg_prog::area_blocks(f) - run.prog_coef0;   // files lie in the area in batch order
+            run.prog_scans = std::max(run.prog_scans, (uint32_t)h.pscans.size());
+            for (const jpeg_prog::Scan& t : h.pscans) {
+                if (run.prog_items.size() <= t.level) run.prog_items.resize((size_t)t.level + 1, 0);
+                run.prog_items[t.level] = std::max(run.prog_items[t.level], jpeg_prog::scan_intervals(f, t));
+            }
+        }
         if (rec[i].ok == 1) { ++w->n_par; ++run.n_par; w->max_par_scan = std::max(w->max_par_scan, (size_t)rec[i].raw_len); run.max_par_scan = std::max(run.max_par_scan, (size_t)rec[i].raw_len); }
         else if (rec[i].ok == 2) { ++w->n_seq; ++run.n_seq; }
         if (rec[i].ok && rec[i].ncomp == 3 && rec[i].hs0 == 2 && rec[i].vs0 == 2) { ++w->n_420; ++run.n_420; }
@@ -1903,6 +2190,7 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
         run.max_blocks = std::max(run.max_blocks, blocks);   // (a record that was not laid out has no components)
     }
     memcpy(base + w->off_imgs, rec.data(), (size_t)n * sizeof(JpegImageDev));
+    if (!pfile.empty()) memcpy(base + w->off_pfile, pfile.data(), (size_t)n * sizeof(jpeg_prog::File));
     if (trace) {
         const auto tp3 = std::chrono::steady_clock::now();
         auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -1971,6 +2259,17 @@ int jpeg_decode_batch_kernels(JpegWorkspace* w, int n, int H, int W, uint8_t* d_
         }
         if (r.n_seq > 0) {  // streams with restart intervals: one lane per interval
             hipLaunchKernelGGL(k_jpeg_huff_rst<256>, dim3(r.n), dim3(256), 0, stream, imgs, slow, scan, w->d_coefs, status, win);
+        }
+        if (r.prog && !r.prog_items.empty()) {
+            // Progressive files: the WHOLE coefficient area zeroed (a refinement scan reads one bit for every coefficient that is
+            // non-zero, in every block of the image: where the stream goes depends on blocks outside the window too), then level
+            // after level of scans.  IDCT and colour run on the window, as for every file.
+            JTRY(hipMemsetAsync(w->d_coefs + r.prog_coef0 * 64, 0, r.prog_coefs * 64 * sizeof(int16_t), stream));
+            const jpeg_prog::File* pf = (const jpeg_prog::File*)(w->d_stage + w->off_pfile) + r.first;
+            for (size_t sidx = 0; sidx < r.prog_items.size(); ++sidx)
+                hipLaunchKernelGGL(k_jpeg_prog_scan, dim3(r.prog_items[sidx], r.n, r.prog_scans), dim3(64), 0, stream, pf,
+                                   (const jpeg_prog::Scan*)(w->d_stage + w->off_pscan), (const jpeg_prog::Huff*)(w->d_stage + w->off_ptab),
+                                   (const uint32_t*)(w->d_stage + w->off_prst), w->d_raw, w->d_coefs, status, (int)sidx);
         }
     }
     if (timer) timer(timer_arg, 0, 1);

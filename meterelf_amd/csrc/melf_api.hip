@@ -283,6 +283,8 @@ struct melf_ctx {
     uint8_t* d_stage_out = nullptr;
     size_t stage_out_cap = 0;
     JpegWorkspace* jpeg = nullptr;     // created by the first JPEG batch
+    bool jpeg_prog = false;            // melf_ctx_set_jpeg_progressive: progressive files of the header's subset are decoded, not refused
+    int jpeg_take() const { return (jpeg_orient ? MELF_JPEG_TAKE_ORIENTED : 0) | (jpeg_prog ? MELF_JPEG_TAKE_PROGRESSIVE : 0); }
     bool jpeg_orient = false;          // melf_ctx_set_jpeg_orientation: files with an EXIF orientation 2..8 are decoded, not refused
     // pipelined JPEG path (melf_jpeg_process_batch): a second workspace and decode stream, so that the host prepares chunk
     // k + 1 and its upload runs while chunk k decodes; per-chunk events; the files' decode status in pinned memory
@@ -888,6 +890,21 @@ extern "C" int melf_ctx_get_jpeg_orientation(melf_ctx* c, int* on)
 {
     if (!c || !on) return fail(MELF_ERR_INVALID, "bad argument");
     *on = c->jpeg_orient ? 1 : 0;
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_ctx_set_jpeg_progressive(melf_ctx* c, int on)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    if (!c->files_jobs.empty()) return fail(MELF_ERR_INVALID, "melf_ctx_set_jpeg_progressive while a melf_jpeg_process_files_begin call is in flight");
+    c->jpeg_prog = on != 0;
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_ctx_get_jpeg_progressive(melf_ctx* c, int* on)
+{
+    if (!c || !on) return fail(MELF_ERR_INVALID, "bad argument");
+    *on = c->jpeg_prog ? 1 : 0;
     return MELF_SUCCESS;
 }
 
@@ -2270,6 +2287,31 @@ extern "C" int melf_jpeg_probe_oriented_batch(const uint8_t* const* data, const 
     return MELF_SUCCESS;
 }
 
+extern "C" int melf_jpeg_probe_flags(const uint8_t* data, size_t size, int flags, int32_t* H, int32_t* W, int32_t* orientation, int32_t* supported)
+{
+    if (!data || !H || !W || !orientation || !supported || (flags & ~(MELF_JPEG_TAKE_ORIENTED | MELF_JPEG_TAKE_PROGRESSIVE)))
+        return fail(MELF_ERR_INVALID, "bad argument");
+    int h = 0, w = 0, o = 1, ok = 0;
+    std::string why;
+    jpeg_probe_flags(data, size, flags, &h, &w, &o, &ok, &why);
+    *H = h; *W = w; *orientation = o; *supported = ok;
+    g_err = why;
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_jpeg_probe_flags_batch(const uint8_t* const* data, const size_t* sizes, int n, int flags, int32_t* H, int32_t* W,
+                                           int32_t* orientation, int32_t* supported)
+{
+    if (n < 0 || (n > 0 && (!data || !sizes || !H || !W || !orientation || !supported)) || (flags & ~(MELF_JPEG_TAKE_ORIENTED | MELF_JPEG_TAKE_PROGRESSIVE)))
+        return fail(MELF_ERR_INVALID, "bad argument");
+    for (int i = 0; i < n; ++i) {
+        int h = 0, w = 0, o = 1, ok = 0;
+        if (data[i] && sizes[i]) jpeg_probe_flags(data[i], sizes[i], flags, &h, &w, &o, &ok, nullptr);
+        H[i] = h; W[i] = w; orientation[i] = o; supported[i] = ok;
+    }
+    return MELF_SUCCESS;
+}
+
 extern "C" int melf_jpeg_probe_batch(const uint8_t* const* data, const size_t* sizes, int n, int32_t* H, int32_t* W,
                                      int32_t* supported)
 {
@@ -2312,7 +2354,7 @@ int jpeg_decode_to_device(melf_ctx* c, const uint8_t* const* data, const size_t*
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<int32_t> hstat(n);
     std::string err;
-    if (int rc = jpeg_prepare_batch(&c->jpeg, data, sizes, n, H, W, hstat.data(), &err, nullptr, 0, nullptr, nullptr, 0, c->jpeg_orient)) return fail(rc, err);
+    if (int rc = jpeg_prepare_batch(&c->jpeg, data, sizes, n, H, W, hstat.data(), &err, nullptr, 0, nullptr, nullptr, 0, c->jpeg_take())) return fail(rc, err);
     const auto t1 = std::chrono::steady_clock::now();
     std::vector<int32_t> dstat(n);
     JpegTimers t{c, c->stream, {}, {false, false, false}};
@@ -2448,8 +2490,8 @@ static int jpeg_decode_pipelined(melf_ctx* c, const uint8_t* const* data, const 
         if (seq >= (uint64_t)NJ) HIP_TRY(hipEventSynchronize(c->ev_jup[b]));
         if (trace) tt[1] = trace_clock_ms(std::chrono::steady_clock::now());
         if (int rc = src ? jpeg_prepare_batch(ws[b], data + f0, sizes + f0, m, H, W, hstat.data() + f0, &err, src->parsed, f0, src->index,
-                                              src->pin_base, src->pin_len, c->jpeg_orient)
-                         : jpeg_prepare_batch(ws[b], data + f0, sizes + f0, m, H, W, hstat.data() + f0, &err, nullptr, 0, nullptr, nullptr, 0, c->jpeg_orient))
+                                              src->pin_base, src->pin_len, c->jpeg_take())
+                         : jpeg_prepare_batch(ws[b], data + f0, sizes + f0, m, H, W, hstat.data() + f0, &err, nullptr, 0, nullptr, nullptr, 0, c->jpeg_take()))
             return fail(rc, err);
         if (trace) tt[2] = trace_clock_ms(std::chrono::steady_clock::now());
         // ... and the kernels that last read its device buffers before the upload overwrites them
@@ -2514,10 +2556,18 @@ static int jpeg_process_batch_from(melf_ctx* c, const uint8_t* const* data, cons
     JpegSource psrc;
     std::vector<uint8_t> code;
     bool oriented = false;
-    if (c->jpeg_orient) {
+    if (c->jpeg_orient || c->jpeg_prog) {   // progressive files (melf_ctx_set_jpeg_progressive) form runs of their own too: 16 + their code
         code.resize(n);
         for (int i = 0; i < n; ++i) {
-            code[i] = (uint8_t)(src ? jpeg_parsed_orientation(src->parsed, src->index ? src->index[i] : i) : jpeg_file_orientation(data[i], sizes[i]));
+            int prog = 0, o = 1;
+            if (src) {
+                const int q = src->index ? src->index[i] : i;
+                o = jpeg_parsed_orientation(src->parsed, q);
+                prog = jpeg_parsed_progressive(src->parsed, q);
+            } else {
+                o = jpeg_file_orientation(data[i], sizes[i], &prog);
+            }
+            code[i] = (uint8_t)((c->jpeg_orient ? o : 1) + (c->jpeg_prog && prog ? 16 : 0));
             oriented = oriented || code[i] != 1;
         }
     }
@@ -2526,7 +2576,7 @@ static int jpeg_process_batch_from(melf_ctx* c, const uint8_t* const* data, cons
         perm.resize(n); pdata.resize(n); psizes.resize(n);
         for (int i = 0; i < n; ++i) perm[i] = i;
         std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) {
-            const int ka = (is_first(a) ? 0 : 16) + (oriented ? code[a] : 0), kb = (is_first(b) ? 0 : 16) + (oriented ? code[b] : 0);
+            const int ka = (is_first(a) ? 0 : 64) + (oriented ? code[a] : 0), kb = (is_first(b) ? 0 : 64) + (oriented ? code[b] : 0);
             return ka < kb;
         });
         for (int i = 0; i < n; ++i) { pdata[i] = data[perm[i]]; psizes[i] = sizes[perm[i]]; }
@@ -2696,7 +2746,7 @@ static int jpeg_files_read(melf_ctx* c, int slot, const char* const* paths, int 
     const auto t_arena = std::chrono::steady_clock::now();
     std::atomic<size_t> bump{0};
     std::atomic<int> spilled{0};
-    const bool take_orient = c->jpeg_orient;   // hs / ws are then the files' UPRIGHT sizes: stage 2 groups by them
+    const int take_orient = c->jpeg_take();    // (orientation: hs / ws are then the files' UPRIGHT sizes: stage 2 groups by them)
     auto read_all = [](int fd, uint8_t* dst, size_t sz) {
         size_t got = 0;
         while (got < sz) {

@@ -225,7 +225,9 @@ int jpeg_probe(const uint8_t* data, size_t size, int* H, int* W, int* supported,
 // EXIF orientation (melf_ctx_set_jpeg_orientation): the probe that takes the tag (stored size, code 1..8, supported apart from the
 // tag), and the tag alone from a walk over the segments in front of the frame header
 int jpeg_probe_oriented(const uint8_t* data, size_t size, int* H, int* W, int* orientation, int* supported, std::string* why);
-int jpeg_file_orientation(const uint8_t* data, size_t size);
+int jpeg_file_orientation(const uint8_t* data, size_t size, int* progressive = nullptr);   // *progressive: the frame header is SOF2
+// What the decode calls answer from the headers with the switches `flags` (MELF_JPEG_TAKE_ORIENTED | MELF_JPEG_TAKE_PROGRESSIVE) on
+int jpeg_probe_flags(const uint8_t* data, size_t size, int flags, int* H, int* W, int* orientation, int* supported, std::string* why);
 // Headers (and, when asked for, the Huffman decode data built from them) of n files, parsed file by file, from any thread (one
 // thread per index): the file-name entry points parse a file right after reading it, on the thread that read it, and build its
 // decode tables there too
@@ -233,9 +235,11 @@ struct JpegParsed;
 JpegParsed* jpeg_parsed_new(int n, bool with_tables);
 void jpeg_parsed_resize(JpegParsed* p, int n);   // room for n files; nothing is cleared (jpeg_parse_one resets its entry)
 // take_orient: a file with an orientation tag 2..8 is supported, and H, W are its UPRIGHT size
-void jpeg_parse_one(JpegParsed* p, int i, const uint8_t* data, size_t size, int* H, int* W, int* supported, bool take_orient = false);
+// (take: MELF_JPEG_TAKE_* flags; with MELF_JPEG_TAKE_PROGRESSIVE progressive files of the header's subset are supported too)
+void jpeg_parse_one(JpegParsed* p, int i, const uint8_t* data, size_t size, int* H, int* W, int* supported, int take = 0);
 void jpeg_parsed_free(JpegParsed* p);
 int jpeg_parsed_orientation(const JpegParsed* p, int i);
+int jpeg_parsed_progressive(const JpegParsed* p, int i);
 // parsed: headers made earlier -- of file pidx[first + j] for the batch's file j (pidx NULL: of file first + j); host_status is
 // then the caller's.  pin_base / pin_len: a pinned host buffer the files' bytes may already lie in (the file-name entry points
 // read into one): a batch whose files all do is uploaded from there, no byte of it is copied on the host.
@@ -243,7 +247,7 @@ int jpeg_parsed_orientation(const JpegParsed* p, int i);
 // parsed with the same setting.
 int jpeg_prepare_batch(JpegWorkspace** ws, const uint8_t* const* data, const size_t* sizes, int n, int H, int W,
                        int32_t* host_status, std::string* err, const JpegParsed* parsed = nullptr, int first = 0,
-                       const int* pidx = nullptr, const uint8_t* pin_base = nullptr, size_t pin_len = 0, bool take_orient = false);
+                       const int* pidx = nullptr, const uint8_t* pin_base = nullptr, size_t pin_len = 0, int take = 0);
 int jpeg_launch_batch(JpegWorkspace* ws, int n, int H, int W, uint8_t* d_frames, int32_t* status_out_host,
                       hipStream_t stream, std::string* err, void (*timer)(void*, int, int), void* timer_arg,
                       const int* rect /* x0, y0, x1, y1: only this part of each frame is needed; NULL = all */);

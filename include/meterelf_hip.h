@@ -845,9 +845,46 @@ int melf_ctx_get_jpeg_orientation(melf_ctx* ctx, int* on);
  * of progressive files on, or for files with restart markers.  That is why it is opt-in everywhere, get_meter_values included
  * (METERELF_JPEG_PROGRESSIVE=gpu). */
 #define MELF_JPEG_PROG_SCANS_MAX 32
-enum { MELF_JPEG_TAKE_ORIENTED = 1, MELF_JPEG_TAKE_PROGRESSIVE = 2 };
+enum { MELF_JPEG_TAKE_ORIENTED = 1, MELF_JPEG_TAKE_PROGRESSIVE = 2, MELF_JPEG_TAKE_SAMPLINGS = 4 };
 int melf_ctx_set_jpeg_progressive(melf_ctx* ctx, int on);
 int melf_ctx_get_jpeg_progressive(melf_ctx* ctx, int* on);
+
+/* ---- YCbCr 4:4:0 and 4:1:1 JPEG files ----
+ * 4:4:0 (luma 1x2, chroma 1x1) is what a lossless 90-degree rotation (jpegtran -rotate, exiftran, gallery apps) makes of a 4:2:2 file,
+ * the layout of ESP32-CAM-class and many MJPEG / UVC cameras; 4:1:1 (luma 4x1, chroma 1x1) is written by DV-derived and older
+ * IP-camera / capture-card encoders.  Every probe reports such a file unsupported (reason "luma sampling other than 1x1, 2x1, 2x2"),
+ * and by default every decode call gives it status 1 for the caller's host decoder; none of that changes.
+ * melf_ctx_set_jpeg_samplings(ctx, 1) makes melf_jpeg_decode_batch, melf_jpeg_process_batch, melf_jpeg_process_files and
+ * melf_jpeg_process_files_begin / _end of that context take them.  Off at context creation; with it off every JPEG entry point
+ * behaves exactly as before, status codes, probe answers and melf_last_error texts included.  Not while a _begin call is in flight.
+ * Independent of the other two switches: a progressive 4:4:0 file with an EXIF orientation is taken when all three are on.
+ * Taken: three-component YCbCr files whose luma sampling is 1x2 or 4x1 and whose chroma sampling is 1x1, baseline or (with that
+ * switch) progressive, under every other rule of the decoder as it stands.  An MCU is then 8 x 16 pixels and 4 blocks, or 32 x 8
+ * pixels and 6 blocks.
+ * Semantics, bit for bit: the frame libjpeg(-turbo) decodes from the file with its defaults.  With P a chroma plane of
+ * ch = ceil(H / 2) real rows (4:4:0) or cw = ceil(W / 4) real columns (4:1:1):
+ *     4:4:0 ("h1v2 fancy"), output row y, cy = y >> 1:
+ *         even y   (3 * P[cy][x] + P[max(cy - 1, 0)][x] + 1) >> 2
+ *         odd y    (3 * P[cy][x] + P[min(cy + 1, ch - 1)][x] + 2) >> 2
+ *       the neighbour clamped to the REAL rows, not the MCU-padded ones; no narrow-image fallback (libjpeg has one for h2v1 / h2v2 only)
+ *     4:1:1: plain replication, P[y][x >> 2], no filter
+ * and everything else is the existing pipeline: the ISLOW IDCT and libjpeg's colour tables.
+ * How: the entropy decoders, the IDCT and the progressive decoder were general in the luma factors already; the general colour kernels
+ * (k_jpeg_color, k_jpeg_color_exif) get the two upsamplers.  The decode window stays the one it was (16 pixels of margin, 16-aligned):
+ * every stage rounds it outwards to the file's own MCUs, so a 32-wide MCU the window cuts is decoded whole.  Files of the four older
+ * samplings launch exactly what they launched, k_jpeg_color420 included.
+ * Measured on one MI355X, 1024-file config-3 calls of melf_jpeg_process_batch on fixture frames re-encoded with the same tables
+ * (profiles/jpeg_sampling/jpeg_sampling_rate.txt): 4:4:0 / 4:1:1 files take 2.34 / 2.58 ms
+ * a call (439 K / 396 K files/s), 0.929 / 1.028 times the same frames as 4:2:2 files (2.51 ms; the nearest sibling: the same colour
+ * kernel), where the host branch such files took before (Pillow on 8 threads, then the batch read) takes 655 / 630 ms: 281 / 244
+ * times as long.  Per call, summed over its chunks: Huffman 1.75 / 2.64 ms (4:2:2: 1.84), IDCT 0.20 / 0.19 (0.20), colour 0.70 / 0.68
+ * (0.94; the 4:2:0 fast path: 0.16).  The fixture's own 4:2:0 files, this library against the one before the switch existed, same
+ * lease, taking turns: 1.987 / 2.055 against 2.039 / 2.048 ms a call, 0.992 on the medians, inside either's spread.
+ * Out of scope: 4:1:0 (luma 4x2, 10 blocks an MCU) and anything with more than 6 blocks an MCU; chroma factors other than 1x1,
+ * including the "2x2 / 1x2 / 1x2" spelling of 4:2:2; RGB / CMYK / Adobe-transform-0 files; multi-scan sequential files; a packed
+ * fast path like k_jpeg_color420 for the new layouts. */
+int melf_ctx_set_jpeg_samplings(melf_ctx* ctx, int on);
+int melf_ctx_get_jpeg_samplings(melf_ctx* ctx, int* on);
 /* The header check with switches: *supported is what the decode calls of a context with the switches `flags` (MELF_JPEG_TAKE_*) on
  * would answer from the headers; H and W are the STORED size, *orientation the EXIF code 1..8 whether or not oriented files are
  * taken.  With flags 0 this is melf_jpeg_probe plus the orientation code.  melf_last_error holds the reason of a refusal. */

@@ -30,6 +30,9 @@ decodes them on the GPU (MeterReader's jpeg_progressive switch; one that the GPU
 inconsistent scan script -- still goes to the host).  The default follows the measurement (profiles/jpeg_prog/jpeg_prog_rate.txt): a
 progressive scan without restart markers is one sequential chain on the GPU, so a chunk takes the time of its slowest file's chain
 however few progressive files it holds, and only lists made mostly of progressive files, or of files with restart markers, gain.
+YCbCr 4:4:0 and 4:1:1 files (a losslessly rotated 4:2:2 file; DV-derived encoders) are decoded on the GPU, byte for byte the frame the
+host branch decodes (MeterReader's jpeg_samplings switch; they cost no latency, unlike progressive files);
+METERELF_JPEG_SAMPLING=host sends them through the host branch instead, as before the GPU took them.
 """
 import collections
 import hashlib
@@ -82,19 +85,26 @@ def _jpeg_progressive_on_gpu() -> bool:
     return os.getenv('METERELF_JPEG_PROGRESSIVE', 'host') == 'gpu'
 
 
+def _jpeg_samplings_on_gpu() -> bool:
+    """4:4:0 and 4:1:1 JPEG files are decoded on the GPU; METERELF_JPEG_SAMPLING=host leaves them to the host branch."""
+    return os.getenv('METERELF_JPEG_SAMPLING', 'gpu') != 'host'
+
+
 def _reader_key(params, blob, device: int) -> bytes:
     env = ';'.join('%s=%s' % (k, os.environ[k]) for k in _ENV_IN_KEY if k in os.environ)
-    orient = b'|orient%d|prog%d|' % (_jpeg_orientation_on_gpu(), _jpeg_progressive_on_gpu())   # a reader keeps the settings it was made with
+    orient = b'|orient%d|prog%d|samp%d|' % (_jpeg_orientation_on_gpu(), _jpeg_progressive_on_gpu(), _jpeg_samplings_on_gpu())   # a reader keeps the settings it was made with
     return hashlib.sha1(blob.tobytes() + repr(list(params.dial_names)).encode() + b'|dev%d|' % device + orient + env.encode()).digest()
 
 
 def _with_jpeg_orientation(reader):
-    """Turns a new reader's switches on (MeterReader.set_jpeg_orientation, set_jpeg_progressive) unless the host branch is asked for;
+    """Turns a new reader's switches on (MeterReader.set_jpeg_orientation, set_jpeg_progressive, set_jpeg_samplings) unless the host branch is asked for;
     a reader from the cache has them already (the settings are part of its key)."""
     if _jpeg_orientation_on_gpu() and hasattr(reader, 'set_jpeg_orientation') and not getattr(reader, 'jpeg_orientation', False):
         reader.set_jpeg_orientation(True)
     if _jpeg_progressive_on_gpu() and hasattr(reader, 'set_jpeg_progressive') and not getattr(reader, 'jpeg_progressive', False):
         reader.set_jpeg_progressive(True)
+    if _jpeg_samplings_on_gpu() and hasattr(reader, 'set_jpeg_samplings') and not getattr(reader, 'jpeg_samplings', False):
+        reader.set_jpeg_samplings(True)
     return reader
 
 

@@ -125,8 +125,10 @@ def records_to_items(records: np.ndarray, ok, dial_names: List[str], filenames: 
 
 class MeterReader:
     def __init__(self, params: Params, device: int = 0, blob: Optional[np.ndarray] = None, ctx: Optional['_hip.Context'] = None,
-                 jpeg_orientation: bool = False, jpeg_progressive: bool = False) -> None:
-        """jpeg_progressive: the read_jpeg_* methods decode progressive JPEG files (the subset include/meterelf_hip.h states) on the
+                 jpeg_orientation: bool = False, jpeg_progressive: bool = False, jpeg_samplings: bool = False) -> None:
+        """jpeg_samplings: the read_jpeg_* methods decode YCbCr 4:4:0 and 4:1:1 JPEG files (a losslessly rotated 4:2:2 file; DV-derived
+        encoders) on the GPU, byte for byte like libjpeg, instead of leaving them to the caller's host decoder, which is the default.
+        jpeg_progressive: the read_jpeg_* methods decode progressive JPEG files (the subset include/meterelf_hip.h states) on the
         GPU instead of leaving them to the caller's host decoder, which is the default.
         jpeg_orientation: the read_jpeg_* methods decode JPEG files that carry an EXIF orientation 2..8 on the GPU, upright (as
         cv2.imread returns them), instead of leaving them to the caller's host decoder (None / ok false), which is the default."""
@@ -144,6 +146,14 @@ class MeterReader:
         self.jpeg_progressive = False
         if jpeg_progressive:
             self.set_jpeg_progressive(True)
+        self.jpeg_samplings = False
+        if jpeg_samplings:
+            self.set_jpeg_samplings(True)
+
+    def set_jpeg_samplings(self, on: bool) -> None:
+        """The switch of the constructor's jpeg_samplings, on a reader with nothing in flight (melf_ctx_set_jpeg_samplings)."""
+        self.ctx.set_jpeg_samplings(on)
+        self.jpeg_samplings = bool(on)
 
     def set_jpeg_progressive(self, on: bool) -> None:
         """The switch of the constructor's jpeg_progressive, on a reader with nothing in flight (melf_ctx_set_jpeg_progressive)."""
@@ -541,8 +551,9 @@ class MeterReader:
         decodes that one on the host."""
         out: List[Optional[np.void]] = [None] * len(files)
         groups: Dict[Tuple[int, int], List[int]] = {}
-        if self.jpeg_orientation or self.jpeg_progressive:   # what the context's switches make the library take
-            flags = (_hip.JPEG_TAKE_ORIENTED if self.jpeg_orientation else 0) | (_hip.JPEG_TAKE_PROGRESSIVE if self.jpeg_progressive else 0)
+        if self.jpeg_orientation or self.jpeg_progressive or self.jpeg_samplings:   # what the context's switches make the library take
+            flags = (_hip.JPEG_TAKE_ORIENTED if self.jpeg_orientation else 0) | (_hip.JPEG_TAKE_PROGRESSIVE if self.jpeg_progressive else 0) | \
+                    (_hip.JPEG_TAKE_SAMPLINGS if self.jpeg_samplings else 0)
             (hs, ws, orient, oks) = _hip.jpeg_probe_flags_batch(files, flags)
             if self.jpeg_orientation:    # by UPRIGHT size: what the library takes as H and W once that switch is on
                 (hs, ws) = (np.where(orient >= 5, ws, hs), np.where(orient >= 5, hs, ws))

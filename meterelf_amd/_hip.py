@@ -232,6 +232,7 @@ EXPORTS = [
     'melf_jpeg_process_files', 'melf_jpeg_process_files_begin', 'melf_jpeg_process_files_end', 'melf_jpeg_files_in_flight_max', 'melf_ctx_files_stats', 'melf_files_open_probe',
     'melf_jpeg_probe_oriented', 'melf_jpeg_probe_oriented_batch', 'melf_ctx_set_jpeg_orientation', 'melf_ctx_get_jpeg_orientation',
     'melf_jpeg_probe_flags', 'melf_jpeg_probe_flags_batch', 'melf_ctx_set_jpeg_progressive', 'melf_ctx_get_jpeg_progressive',
+    'melf_ctx_set_jpeg_samplings', 'melf_ctx_get_jpeg_samplings',
 ]
 
 _lib = None
@@ -328,6 +329,8 @@ def lib():
     L.melf_jpeg_probe_flags_batch.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     L.melf_ctx_set_jpeg_progressive.argtypes = [vp, C.c_int]
     L.melf_ctx_get_jpeg_progressive.argtypes = [vp, C.POINTER(C.c_int)]
+    L.melf_ctx_set_jpeg_samplings.argtypes = [vp, C.c_int]
+    L.melf_ctx_get_jpeg_samplings.argtypes = [vp, C.POINTER(C.c_int)]
     L.melf_jpeg_decode_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]
     L.melf_jpeg_process_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.melf_jpeg_process_files.argtypes = [vp, vp, C.c_int, i32p, i32p, vp, vp]
@@ -1082,11 +1085,12 @@ def jpeg_probe_oriented_batch(files):
 
 JPEG_TAKE_ORIENTED = 1      # MELF_JPEG_TAKE_*: the switches a probe answers for
 JPEG_TAKE_PROGRESSIVE = 2
+JPEG_TAKE_SAMPLINGS = 4     # 4:4:0 and 4:1:1 files (melf_ctx_set_jpeg_samplings)
 
 
 def jpeg_probe_flags(data, flags):
     """(H, W, orientation, supported, reason) of a JPEG file's bytes as the decode calls of a context with the switches `flags`
-    (JPEG_TAKE_ORIENTED | JPEG_TAKE_PROGRESSIVE) on answer from the headers: H and W are the STORED size, orientation is the EXIF code
+    (JPEG_TAKE_ORIENTED | JPEG_TAKE_PROGRESSIVE | JPEG_TAKE_SAMPLINGS) on answer from the headers: H and W are the STORED size, orientation is the EXIF code
     1..8 whether or not oriented files are taken.  With flags 0: jpeg_probe plus the orientation.  Header parse only, no GPU."""
     L = lib()
     H, W, o, ok = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
@@ -1697,6 +1701,16 @@ class Context:
     def jpeg_progressive(self):
         on = C.c_int(0)
         check(self._L.melf_ctx_get_jpeg_progressive(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def set_jpeg_samplings(self, on):
+        """YCbCr 4:4:0 (luma 1x2) and 4:1:1 (luma 4x1) JPEG files are decoded by the jpeg_* calls of this context instead of coming
+        back unsupported (melf_ctx_set_jpeg_samplings).  Off by default."""
+        check(self._L.melf_ctx_set_jpeg_samplings(self._h, int(bool(on))))
+
+    def jpeg_samplings(self):
+        on = C.c_int(0)
+        check(self._L.melf_ctx_get_jpeg_samplings(self._h, C.byref(on)))
         return bool(on.value)
 
     def set_frames_resident(self, on):

@@ -1,6 +1,7 @@
 // Baseline JPEG decode on the GPU: replaces the host decode behind
 // cv2.imread (meterelf/_image.py:49) for the files the meter cameras write -- baseline sequential
-// DCT, 8 bit, Huffman, one interleaved scan, YCbCr 4:2:0 / 4:2:2 / 4:4:4 or greyscale.  Within that: SOF0 or SOF1, Huffman
+// DCT, 8 bit, Huffman, one interleaved scan, YCbCr 4:2:0 / 4:2:2 / 4:4:4 or greyscale (and 4:4:0 / 4:1:1 for a caller that asked for
+// them: melf_ctx_set_jpeg_samplings).  Within that: SOF0 or SOF1, Huffman
 // table ids 0 and 1 in any assignment to the components, quantisation tables 0..3 with 8- or 16-bit entries, any component
 // ids, any order and packing of the header segments.  Everything else is reported unsupported (the caller's host decoder
 // takes it), including a file that refers to a Huffman table it does not define (libjpeg-turbo falls back to the Annex K
@@ -76,7 +77,7 @@ struct JpegHeader {
     std::vector<jpeg_prog::Huff> ptabs;
     std::vector<uint32_t> prst;
 };
-constexpr int TAKE_ORIENTED = 1, TAKE_PROGRESSIVE = 2;   // MELF_JPEG_TAKE_*: what a caller's switches make the parser accept
+constexpr int TAKE_ORIENTED = 1, TAKE_PROGRESSIVE = 2, TAKE_SAMPLINGS = 4;   // MELF_JPEG_TAKE_*: what a caller's switches make the parser accept
 
 static inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
 
@@ -126,15 +127,19 @@ static const char* huff_spec_flaw(const HuffSpec& t, const bool dc)
 }
 
 // The rules on the frame header that do not depend on the kind of scan: sets h.why, and makes a greyscale frame 1x1.
-static void frame_rules(JpegHeader& h)
+// take_samp (TAKE_SAMPLINGS): luma 1x2 (4:4:0) and 4x1 (4:1:1) are taken too; 4:1:0 (4x2) has 10 blocks an MCU, McuLayout packs 6.
+static void frame_rules(JpegHeader& h, const bool take_samp)
 {
     if (h.H <= 0 || h.W <= 0) { h.why = "empty image"; return; }
     if (h.ncomp == 3) {
         if (h.saw_adobe && h.adobe_transform != 1) h.why = "Adobe marker says the data are not YCbCr";
         else if (!h.saw_jfif && !h.saw_adobe && h.id[0] == 'R' && h.id[1] == 'G' && h.id[2] == 'B') h.why = "RGB component ids";
         else if (h.hs[1] != 1 || h.vs[1] != 1 || h.hs[2] != 1 || h.vs[2] != 1) h.why = "subsampled chroma with sampling factors above 1";
-        else if (!((h.hs[0] == 1 && h.vs[0] == 1) || (h.hs[0] == 2 && h.vs[0] == 1) || (h.hs[0] == 2 && h.vs[0] == 2)))
-            h.why = "luma sampling other than 1x1, 2x1, 2x2";
+        else if (!((h.hs[0] == 1 && h.vs[0] == 1) || (h.hs[0] == 2 && h.vs[0] == 1) || (h.hs[0] == 2 && h.vs[0] == 2))) {
+            if (!take_samp) h.why = "luma sampling other than 1x1, 2x1, 2x2";
+            else if (h.hs[0] == 4 && h.vs[0] == 2) h.why = "4:1:0 (luma sampling 4x2): more than 6 blocks an MCU";
+            else if (!((h.hs[0] == 1 && h.vs[0] == 2) || (h.hs[0] == 4 && h.vs[0] == 1))) h.why = "luma sampling other than 1x1, 2x1, 2x2, 1x2, 4x1";
+        }
     } else {
         h.hs[0] = h.vs[0] = 1;  // a single-component scan is never interleaved: one block per MCU
     }
@@ -213,10 +218,11 @@ static const char* prog_scan_header(JpegHeader& h, ProgState& ps, const uint8_t*
 }
 
 // take: TAKE_ORIENTED -- a file with an orientation tag 2..8 is one for the GPU (h.orient says which); TAKE_PROGRESSIVE -- so is a
-// progressive file of the subset include/meterelf_hip.h states (h.progressive, h.pscans).  Otherwise they are unsupported, as ever.
+// progressive file of the subset include/meterelf_hip.h states (h.progressive, h.pscans); TAKE_SAMPLINGS -- and a 4:4:0 or 4:1:1
+// file (frame_rules).  Otherwise they are unsupported, as ever.
 static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h, const int take = 0)
 {
-    const bool take_orient = (take & TAKE_ORIENTED) != 0, take_prog = (take & TAKE_PROGRESSIVE) != 0;
+    const bool take_orient = (take & TAKE_ORIENTED) != 0, take_prog = (take & TAKE_PROGRESSIVE) != 0, take_samp = (take & TAKE_SAMPLINGS) != 0;
     for (int i = 0; i < 4; ++i) { h.dc[i].set = false; h.ac[i].set = false; }
     if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return -1;
     size_t i = 2;
@@ -332,7 +338,7 @@ static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h, const int ta
                 if (h.progressive) {
                     if (h.why) return 0;   // refused by a segment between the scans: no further scan is looked at
                     if (!ps.started) {   // the frame must be one for the decoder before any scan byte is looked at
-                        if (!h.why) frame_rules(h);
+                        if (!h.why) frame_rules(h, take_samp);
                         for (int c = 0; c < h.ncomp && !h.why; ++c)
                             if (!h.qt_set[h.tq[c]]) h.why = "missing quantisation table";
                         if (h.why) return 0;
@@ -391,7 +397,7 @@ prog_done:
     return 0;
 done:
     if (h.why) return 0;
-    frame_rules(h);
+    frame_rules(h, take_samp);
     if (h.H <= 0 || h.W <= 0) return 0;
     for (int c = 0; c < h.ncomp && !h.why; ++c) {
         if (!h.qt_set[h.tq[c]]) h.why = "missing quantisation table";
@@ -434,7 +440,7 @@ int jpeg_probe_oriented(const uint8_t* data, size_t size, int* H, int* W, int* o
 int jpeg_probe_flags(const uint8_t* data, size_t size, int flags, int* H, int* W, int* orientation, int* supported, std::string* why)
 {
     JpegHeader h;
-    if (parse_headers(data, size, h, flags & (TAKE_ORIENTED | TAKE_PROGRESSIVE)) != 0) {
+    if (parse_headers(data, size, h, flags & (TAKE_ORIENTED | TAKE_PROGRESSIVE | TAKE_SAMPLINGS)) != 0) {
         *H = *W = 0; *supported = 0; *orientation = 1;
         if (why) *why = "not a JPEG file or truncated headers";
         return 0;
@@ -772,10 +778,17 @@ constexpr size_t JPEG_MAX_PAR_SCAN = 4000000;
 constexpr uint32_t TAB_MASK = (1u << TAB_BITS) - 1u;
 
 // Per-MCU-position tables packed into registers: 1 bit of DC table id, 1 bit of AC table id and 2 bits
-// of component per block position (an MCU has at most 6 blocks here).
+// of component per block position (an MCU has at most 6 blocks here: 4:2:0 and 4:1:1 have 6, 4:2:2 and 4:4:0 have 4).
 // The pixel window the decoder produces (x0, y0 multiples of 16): the whole frame, or -- when the caller only
-// reads the meter_rect crop -- that crop plus one MCU of context for the chroma filter.  Coefficients outside it
+// reads the meter_rect crop -- that crop plus 16 pixels of context for the chroma filter.  Coefficients outside it
 // are neither zeroed nor stored, J2 / J3 do not run there.
+// The window is in PIXELS and knows nothing of the file's MCU (a run's files may differ in sampling).  Every stage turns it into
+// the file's own MCUs the same way -- floor(x0 / mw) .. ceil(x1 / mw), floor(y0 / mh) .. ceil(y1 / mh) with mw x mh = 8 hs0 x 8 vs0:
+// jpeg_zero_window for J1, k_jpeg_idct for J2 -- so the MCUs that are zeroed, stored and inverse-transformed are exactly those that
+// hold a pixel of the window, whatever the MCU: 8 x 8, 16 x 8, 16 x 16, and 8 x 16 (4:4:0) and 32 x 8 (4:1:1) just the same.  For the
+// MCUs up to 16 x 16 the 16-aligned origin is an MCU corner; for a 32-wide MCU x0 may lie 16 pixels inside its first MCU, which is
+// then decoded whole (16 more columns than asked for, never fewer).  What the 16 pixels of margin are for is the chroma filter's
+// reach, at most one chroma sample = 2 luma pixels in the filtered direction (4:1:1 is not filtered at all); it is not an MCU count.
 struct JpegWindow {
     int x0, y0, x1, y1;
 };
@@ -1134,6 +1147,7 @@ __device__ __forceinline__ McuWindow jpeg_zero_window(const JpegImageDev* R, con
     McuWindow m;
     m.mx0 = win.x0 / mwid; m.mx1 = min((win.x1 + mwid - 1) / mwid, (int)R->mcus_x);
     m.my0 = win.y0 / mhei; m.my1 = min((win.y1 + mhei - 1) / mhei, (int)R->mcus_y);
+    // (floor and ceiling in the file's own MCU, 8 x 16 and 32 x 8 included: 0 <= mx0 < mx1 <= mcus_x because 0 <= x0 < x1 <= W, same for y)
     // decode order: the window's MCUs of one MCU row are one run of bpm * 128 bytes each
     const int bpm = ncomp == 1 ? 1 : hs0 * vs0 + 2;
     const int run16 = (m.mx1 - m.mx0) * bpm * 8, rows = m.my1 - m.my0;  // uint4s per row of MCUs
@@ -1228,6 +1242,9 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_num_sgpr(80))) void k_jpeg
     // margin of one and a half MCU rows, and CHECKED against the exact counts once the rounds are over: if the settled
     // prefix does not reach the window's end after all, the rounds go on over every segment.  What is given up: a stream
     // damaged only BEHIND the window is no longer reported corrupt (libjpeg would decode the window just the same).
+    // All of it counts in BLOCKS of the file's own MCU row (mcus_x * bpm), so it holds for every MCU shape: a 4:1:1 row is
+    // ceil(W / 32) MCUs of 6 blocks and 8 pixels tall, a 4:4:0 row ceil(W / 8) MCUs of 4 blocks and 16 tall; the margin is an
+    // estimate's slack, the exact check behind the rounds is what the result rests on.
     const int wend = min(total_blocks, mwin.my1 * mcus_x * L.bpm);   // first block behind the window
     int cut = nseg - 1;                                               // last segment the rounds have to settle
     if (wend < total_blocks) {
@@ -1548,7 +1565,10 @@ __global__ __launch_bounds__(256) void k_jpeg_idct(const JpegImageDev* __restric
     const int img = blockIdx.y;
     const JpegImageDev& I = imgs[img];   // a reference: a local copy indexed by the component lives in scratch
     if (!I.ok || status[img] != 0) return;
-    // blocks of the MCUs that overlap the pixel window (16-aligned, so whole MCUs in every sampling mode)
+    // blocks of the MCUs that overlap the pixel window: floor / ceiling in the file's own MCU, the very MCUs jpeg_zero_window gave
+    // the Huffman stage (the window's origin is 16-aligned: an MCU corner for MCUs up to 16 x 16, and for the 32 x 8 MCU of 4:1:1
+    // possibly the middle of one, which the floor takes whole).  Stores: bx < blocks_x[c], by < blocks_y[c] since mx1 <= mcus_x,
+    // my1 <= mcus_y, so a block's 8 x 8 samples lie inside the component's plane of blocks_x * 8 x blocks_y * 8 bytes.
     const int mw = 8 * I.hs0, mh = 8 * I.vs0;
     const int mx0 = win.x0 / mw, mx1 = min((win.x1 + mw - 1) / mw, (int)I.mcus_x);
     const int my0 = win.y0 / mh, my1 = min((win.y1 + mh - 1) / mh, (int)I.mcus_y);
@@ -1617,6 +1637,15 @@ __device__ __forceinline__ int chroma_h2v1(const uint8_t* P, int stride, int cw,
     if (cw <= 2) return v;
     if (x & 1) return cx == cw - 1 ? v : (3 * v + row[cx + 1] + 2) >> 2;
     return cx == 0 ? v : (3 * v + row[cx - 1] + 1) >> 2;
+}
+// 4:4:0 (libjpeg's h1v2 fancy upsampling): the triangle filter down the columns only, 3/4 the nearer chroma row + 1/4 the further one,
+// rounding 1 for the even and 2 for the odd output row; the missing neighbour at the top and bottom is the edge row itself, the last
+// REAL row (ch = ceil(H / 2)), not the MCU padding.  No narrow-image fallback: libjpeg has that for the horizontal filters only.
+__device__ __forceinline__ int chroma_h1v2(const uint8_t* P, int stride, int ch, int x, int y)
+{
+    const int cy = y >> 1;
+    const int fy = (y & 1) ? min(cy + 1, ch - 1) : max(cy - 1, 0);
+    return (3 * P[(size_t)cy * stride + x] + P[(size_t)fy * stride + x] + 1 + (y & 1)) >> 2;
 }
 
 // YCbCr -> RGB with libjpeg's 16-bit fixed-point tables (jdcolor): the rounding term sits in the
@@ -1717,14 +1746,25 @@ __global__ __launch_bounds__(256) void k_jpeg_color420(const JpegImageDev* __res
 struct PlaneSrc {
     const uint8_t *Y, *Cb, *Cr;
     int ys, cs, cw, ch;
-    int mode;   // 0 grey, 1 4:4:4, 2 4:2:2 (h2v1), 3 4:2:0 (h2v2)
+    int mode;   // 0 grey, 1 4:4:4, 2 4:2:2 (h2v1), 3 4:2:0 (h2v2), 4 4:4:0 (h1v2), 5 4:1:1 (h4v1: plain replication)
 };
+// Bounds of the two chroma reads melf_ctx_set_jpeg_samplings adds, for a pixel (x, y) of the window, 0 <= x < W, 0 <= y < H (the
+// window lies inside the stored frame), in a chroma plane of cs = 8 * blocks_x[1] bytes a row and 8 * blocks_y[1] rows:
+//   4:1:1  column x >> 2 <= (W - 1) / 4 < cw = ceil(W / 4) <= 8 * ceil(W / 32) = 8 * blocks_x[1], row y < H <= 8 * blocks_y[1].  The
+//          sample's MCU is the one that holds pixel (x, y) (an MCU is 32 pixels = 8 chroma columns wide), so it overlaps the window
+//          and was inverse-transformed for every window (k_jpeg_idct takes every MCU that holds a pixel of it).
+//   4:4:0  column x < W <= 8 * blocks_x[1]; rows cy = y >> 1 <= (H - 1) / 2 < ch = ceil(H / 2) <= 8 * blocks_y[1], and cy - 1, cy + 1
+//          clamped to [0, ch): inside the plane whatever the window.  Row cy is in the MCU of pixel (x, y); rows cy +- 1 are luma rows
+//          y - 2 .. y + 3, so for the pixels a caller reads (at least 16 rows inside the window, or at a frame edge, where the clamp
+//          applies) they are rows of the window and their MCU rows were inverse-transformed.  The window's own outermost two rows
+//          may filter with a row from outside it -- memory of this file's plane, never read by the caller -- exactly as the first and
+//          last rows of a 4:2:0 window always have.
 __device__ __forceinline__ PlaneSrc plane_src(const JpegImageDev& I, const uint8_t* planes, int H, int W)
 {
     PlaneSrc s;
     s.Y = planes + I.plane_off[0];
     s.ys = I.blocks_x[0] * 8;
-    s.mode = I.ncomp == 1 ? 0 : (I.hs0 == 2 && I.vs0 == 2) ? 3 : I.hs0 == 2 ? 2 : 1;
+    s.mode = I.ncomp == 1 ? 0 : (I.hs0 == 2 && I.vs0 == 2) ? 3 : I.hs0 == 2 ? 2 : I.vs0 == 2 ? 4 : I.hs0 == 4 ? 5 : 1;
     s.Cb = s.Cr = s.Y;
     s.cs = s.cw = s.ch = 0;
     if (I.ncomp != 1) {
@@ -1742,6 +1782,8 @@ __device__ __forceinline__ uint32_t plane_bgr(const PlaneSrc& s, int x, int y)
     int cb, cr;
     if (s.mode == 3) { cb = chroma_h2v2(s.Cb, s.cs, s.cw, s.ch, x, y); cr = chroma_h2v2(s.Cr, s.cs, s.cw, s.ch, x, y); }
     else if (s.mode == 2) { cb = chroma_h2v1(s.Cb, s.cs, s.cw, x, y); cr = chroma_h2v1(s.Cr, s.cs, s.cw, x, y); }
+    else if (s.mode == 4) { cb = chroma_h1v2(s.Cb, s.cs, s.ch, x, y); cr = chroma_h1v2(s.Cr, s.cs, s.ch, x, y); }
+    else if (s.mode == 5) { cb = s.Cb[(size_t)y * s.cs + (x >> 2)]; cr = s.Cr[(size_t)y * s.cs + (x >> 2)]; }
     else { cb = s.Cb[(size_t)y * s.cs + x]; cr = s.Cr[(size_t)y * s.cs + x]; }
     return ycc_to_bgr(yy, cb, cr);
 }
@@ -2281,7 +2323,10 @@ int jpeg_decode_batch_kernels(JpegWorkspace* w, int n, int H, int W, uint8_t* d_
             if (r.max_blocks <= 0) continue;
             const JpegWindow win = geo[q].win;
             const int win_w = win.x1 - win.x0, win_h = win.y1 - win.y0;
-            // at most (window / 8)^2 luma blocks + two chroma planes of up to the same count (4:4:4)
+            // at most (window / 8)^2 luma blocks + two chroma planes of up to the same count (4:4:4).  A 32-wide MCU (4:1:1) can add
+            // up to 16 columns on EACH side of the 16-aligned window: w0 <= win_w / 8 + 6 luma blocks a row against the
+            // win_w / 8 + 3 allowed for here, but its two chroma planes are a quarter of the luma each, 1.5 w0 h0 blocks in all, and
+            // 1.5 (win_w / 8 + 6) <= 3 (win_w / 8 + 3); h0 = ceil(win_h / 8) as ever.  4:4:0 has MCUs of 8 x 16: nothing new.
             const int wblocks = 3 * ((win_w + 15) / 8 + 2) * ((win_h + 15) / 8 + 2);
             const int nblk = std::min(r.max_blocks, wblocks);
             hipLaunchKernelGGL(k_jpeg_idct, dim3((nblk + 255) / 256, r.n), dim3(256), 0, stream, imgs0 + r.first, qt0 + (size_t)r.first * 256, w->d_coefs,

@@ -16,7 +16,13 @@
 namespace melf {
 namespace jpeg_orient {
 
-constexpr int MCU = 16;   // the largest MCU edge (4:2:0): window margin and alignment
+// Window margin and alignment, in pixels: the MCU edge of 4:2:0, and what the window has always been cut with.  It is NOT the largest
+// MCU edge of every file the decoder takes: a 4:1:1 MCU is 32 x 8, a 4:4:0 MCU 8 x 16 (melf_ctx_set_jpeg_samplings).  The window
+// stays as it is for them, bit for bit, because nothing below needs the MCU: the MARGIN is the chroma filter's reach -- one chroma
+// sample, i.e. 2 pixels along a filtered axis (4:4:0 filters down the columns, 4:1:1 not at all), 16 covers it -- and the ALIGNMENT
+// is the 4:2:0 colour kernel's (8 pixels, even rows).  The decode stages take the window in pixels and round it outwards to each
+// file's own MCUs themselves (k_jpeg.hip, JpegWindow), so a 32-wide MCU that the window cuts in the middle is decoded whole.
+constexpr int MCU = 16;
 
 struct Window { int x0, y0, x1, y1; };   // pixels of the stored frame, [x0, x1) x [y0, y1)
 

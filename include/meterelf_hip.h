@@ -795,7 +795,7 @@ int melf_jpeg_probe_batch(const uint8_t* const* data, const size_t* sizes, int n
  * for upright 4:2:0 files.  Upright files, this library against the one before the switch existed, same lease: 1.962 / 1.981 against
  * 1.981 / 1.976 ms a call.
  * Out of scope: a tag anywhere but IFD0 of the first Exif APP1 (a second Exif block that asks for a rotation sends the file to the
- * host); progressive files unless melf_ctx_set_jpeg_progressive is on too (below), and multi-scan sequential files, which stay
+ * host); progressive files unless melf_ctx_set_jpeg_progressive is on too (below), and multi-scan sequential files, which (unless melf_ctx_set_jpeg_multiscan is on, below) stay
  * unsupported with or without a tag; a 4:2:0 fast path for oriented files. */
 /* The header check that takes the tag: H and W are the STORED size, *orientation is 1..8 (1 when the tag is absent, unreadable or
  * outside 1..8, which Pillow and cv2 leave alone too), *supported is what melf_jpeg_probe would answer if the file had no tag.  The
@@ -845,7 +845,9 @@ int melf_ctx_get_jpeg_orientation(melf_ctx* ctx, int* on);
  * of progressive files on, or for files with restart markers.  That is why it is opt-in everywhere, get_meter_values included
  * (METERELF_JPEG_PROGRESSIVE=gpu). */
 #define MELF_JPEG_PROG_SCANS_MAX 32
-enum { MELF_JPEG_TAKE_ORIENTED = 1, MELF_JPEG_TAKE_PROGRESSIVE = 2, MELF_JPEG_TAKE_SAMPLINGS = 4 };
+/* (8 is no switch: a probe with that bit is a bad argument, as it has been since the flags word had three bits) */
+enum { MELF_JPEG_TAKE_ORIENTED = 1, MELF_JPEG_TAKE_PROGRESSIVE = 2, MELF_JPEG_TAKE_SAMPLINGS = 4, MELF_JPEG_TAKE_DEFAULT_TABLES = 16,
+       MELF_JPEG_TAKE_MULTISCAN = 32 };
 int melf_ctx_set_jpeg_progressive(melf_ctx* ctx, int on);
 int melf_ctx_get_jpeg_progressive(melf_ctx* ctx, int* on);
 
@@ -881,10 +883,72 @@ int melf_ctx_get_jpeg_progressive(melf_ctx* ctx, int* on);
  * (0.94; the 4:2:0 fast path: 0.16).  The fixture's own 4:2:0 files, this library against the one before the switch existed, same
  * lease, taking turns: 1.987 / 2.055 against 2.039 / 2.048 ms a call, 0.992 on the medians, inside either's spread.
  * Out of scope: 4:1:0 (luma 4x2, 10 blocks an MCU) and anything with more than 6 blocks an MCU; chroma factors other than 1x1,
- * including the "2x2 / 1x2 / 1x2" spelling of 4:2:2; RGB / CMYK / Adobe-transform-0 files; multi-scan sequential files; a packed
+ * including the "2x2 / 1x2 / 1x2" spelling of 4:2:2; RGB / CMYK / Adobe-transform-0 files; multi-scan sequential files (melf_ctx_set_jpeg_multiscan, below); a packed
  * fast path like k_jpeg_color420 for the new layouts. */
 int melf_ctx_set_jpeg_samplings(melf_ctx* ctx, int on);
 int melf_ctx_get_jpeg_samplings(melf_ctx* ctx, int* on);
+
+/* ---- Multi-scan sequential JPEG files ----
+ * A sequential file (SOF0 / SOF1) may send its three components in three scans of one component each instead of one interleaved
+ * scan (jpegtran -scans, some camera firmwares and hardware encoders).  Every probe reports such a file unsupported (reason "more than
+ * one scan (non-interleaved components)"), and by default every decode call gives it status 1 for the caller's host decoder; none of
+ * that changes.  melf_ctx_set_jpeg_multiscan(ctx, 1) makes melf_jpeg_decode_batch, melf_jpeg_process_batch, melf_jpeg_process_files and
+ * melf_jpeg_process_files_begin / _end of that context take them.  Off at context creation; with it off every JPEG entry point
+ * behaves exactly as before, status codes, probe answers and melf_last_error texts included.  Not while a _begin call is in flight.
+ * Independent of the other switches: a 4:4:0 multi-scan file with an EXIF orientation is taken when the three are on.
+ * Taken: SOF0 or SOF1, 8 bit, three components, YCbCr of any sampling the context takes otherwise; exactly three scans of one
+ * component each, every component once, in any order, each with Ss = 0, Se = 63, Ah = Al = 0.  Between the scans: DHT with ids 0-3
+ * (a scan uses the tables in force at its own SOS; a redefinition between scans is legal; every table a scan uses must exist and pass
+ * libjpeg's checks), DRI (the interval counts the blocks of the scan it applies to), COM and APPn.
+ * Unsupported, each with a reason of its own: a scan of two components, a component sent twice, a file that ends (EOI) before every
+ * component has had its scan, a DQT or a frame header behind the first SOS, anything behind the third scan other than EOI (bytes behind
+ * EOI are ignored, as ever).  A file whose bytes end inside a scan is MELF_JPEG_CORRUPT, as a truncated file ever was.
+ * Semantics, bit for bit: the frame libjpeg(-turbo) decodes with its defaults.  libjpeg smooths only progressive files, so that is the
+ * frame of the interleaved file that holds the same coefficient blocks.  Corruption in any scan (the data run out, restart markers
+ * missing or surplus, a code that does not exist) gives the file MELF_JPEG_CORRUPT and a zero-filled frame; its neighbours are unaffected.
+ * How: a non-interleaved scan of a component is, bit for bit, the entropy-coded segment of a greyscale file of the component's size
+ * (ceil(W hs_c / hs_max) x ceil(H vs_c / vs_max)): one block an MCU, the REAL blocks in raster order, its own DC predictor, restart
+ * interval and tables.  Each scan therefore goes through k_jpeg_clean, k_jpeg_huff and k_jpeg_huff_rst unchanged as a one-component
+ * record of its own, with a snapshot of its two tables, and writes the component's blocks into an area of its own; k_jpeg_idct reads a
+ * marked file's blocks from those areas and leaves the MCU-padding blocks, which no scan sends and no pixel reads, flat.  Unlike
+ * progressive files these keep the segment-parallel decoder and pay no chain latency.  The scans' records are launched in groups of one
+ * window: a chroma scan's window is the file's window divided by the sampling factors and rounded outwards to MCUs, not a subset of
+ * the luma window (meterelf_amd/csrc/melf_jpeg_scans.h).  Each scan has the 1024-segment / 4 MB allowance of a file's one scan.  The
+ * host walks these files' entropy-coded bytes once, to find the second and third SOS; a call without such a file launches exactly what
+ * it launched before.
+ * Measured on one MI355X, 1024-file config-3 calls of melf_jpeg_process_batch on fixture frames written as interleaved files, as their
+ * multi-scan twins and as their twins without DHT segments (profiles/jpeg_scans/jpeg_scans_rate.txt): multi-scan 4:2:0 / 4:2:2 files
+ * take 2.56 / 2.92 ms a call (401 K / 350 K files/s), 1.148 / 1.192 times their interleaved twins (2.23 / 2.45 ms), where the host branch
+ * such files took before (Pillow on 8 threads, then the batch read) takes 567 ms: 222 times as long.  Per call, summed over its chunks:
+ * Huffman 1.18 / 1.61 ms (twins: 1.99 / 1.72), IDCT 0.13 / 0.18 (0.18 / 0.21), colour 0.16 / 0.75 (0.20 / 1.09); what a call pays above
+ * its twin is launches (one more Huffman launch per group, four records a file through k_jpeg_clean) and the host's walk, not kernel
+ * time.  A 256-file call with ONE multi-scan file among baseline files takes 1.22 ms, the same call with that file through the host
+ * branch 2.85 ms: that is why get_meter_values turns the switch on (METERELF_JPEG_MULTISCAN=host restores the host branch).  The
+ * fixture's own 4:2:0 files, this library against the one before the switch existed, same lease, taking turns: 2.133 / 2.047 against
+ * 2.007 / 2.068 ms a call, 1.023 on the medians with 4 - 5 % between either library's own turns; eight more alternating turns gave
+ * 2.19 / 2.06 / 2.06 / 2.09 against 2.03 / 2.10 / 2.12 / 2.10 ms, 0.987 on the medians: no difference beyond the turns' own spread.
+ * Out of scope: partially interleaved scripts (Y, then CbCr together), 4:1:0 and chroma factors above 1, RGB / CMYK files, a DQT
+ * between scans. */
+int melf_ctx_set_jpeg_multiscan(melf_ctx* ctx, int on);
+int melf_ctx_get_jpeg_multiscan(melf_ctx* ctx, int* on);
+
+/* ---- JPEG files without their Huffman tables (Motion-JPEG frames) ----
+ * Frames of UVC webcams, ESP32-class boards and AVI MJPG streams come without a DHT segment: Motion-JPEG leaves the tables to the
+ * decoder, and libjpeg-turbo (so cv2.imread and Pillow) installs the ones ITU-T T.81 Annex K.3 prints.  Every probe reports such a
+ * file unsupported (reason "missing Huffman table"), and by default every decode call gives it status 1 for the caller's host decoder;
+ * none of that changes.  melf_ctx_set_jpeg_default_tables(ctx, 1) makes the decode calls of that context take them.  Off at context
+ * creation; with it off every JPEG entry point behaves exactly as before.  Not while a _begin call is in flight.  Independent of the
+ * other switches.
+ * Semantics, exactly libjpeg-turbo's std_huff_tables: when the Huffman decoder starts -- behind the headers up to the first SOS -- each
+ * of the slots DC 0, AC 0, DC 1 and AC 1 that no DHT has defined receives the Annex K table for it, luminance for id 0 and
+ * chrominance for id 1.  Slots 2 and 3 receive nothing.  A file without any DHT and a file that defines only some of the four are
+ * both covered; for a multi-scan file the fill happens once, before the first scan.  Progressive files are not covered and keep their
+ * answer.  Host code only (meterelf_amd/csrc/melf_jpeg_std_tables.h): the files go through the pipeline as it stands, at their twins'
+ * rate (profiles/jpeg_scans/jpeg_scans_rate.txt: 2.22 / 2.38 ms a 1024-file call of 4:2:0 / 4:2:2 files without DHT, 0.996 / 0.972 times
+ * the same files with their tables, where the host branch takes 593 ms, 268 times as long).  get_meter_values turns the switch on;
+ * METERELF_JPEG_TABLES=host restores the host branch. */
+int melf_ctx_set_jpeg_default_tables(melf_ctx* ctx, int on);
+int melf_ctx_get_jpeg_default_tables(melf_ctx* ctx, int* on);
 /* The header check with switches: *supported is what the decode calls of a context with the switches `flags` (MELF_JPEG_TAKE_*) on
  * would answer from the headers; H and W are the STORED size, *orientation the EXIF code 1..8 whether or not oriented files are
  * taken.  With flags 0 this is melf_jpeg_probe plus the orientation code.  melf_last_error holds the reason of a refusal. */

@@ -33,6 +33,11 @@ however few progressive files it holds, and only lists made mostly of progressiv
 YCbCr 4:4:0 and 4:1:1 files (a losslessly rotated 4:2:2 file; DV-derived encoders) are decoded on the GPU, byte for byte the frame the
 host branch decodes (MeterReader's jpeg_samplings switch; they cost no latency, unlike progressive files);
 METERELF_JPEG_SAMPLING=host sends them through the host branch instead, as before the GPU took them.
+Files that leave Huffman tables out (Motion-JPEG frames of UVC webcams and AVI MJPG streams carry no DHT segment) are decoded on the GPU
+with the T.81 Annex K tables, as libjpeg-turbo decodes them (MeterReader's jpeg_default_tables switch); METERELF_JPEG_TABLES=host sends
+them through the host branch instead.  Sequential files sent as three one-component scans are decoded on the GPU as well
+(MeterReader's jpeg_multiscan switch; they keep the segment-parallel decoder and cost no latency, unlike progressive files);
+METERELF_JPEG_MULTISCAN=host sends them through the host branch instead.
 """
 import collections
 import hashlib
@@ -90,14 +95,29 @@ def _jpeg_samplings_on_gpu() -> bool:
     return os.getenv('METERELF_JPEG_SAMPLING', 'gpu') != 'host'
 
 
+def _jpeg_multiscan_on_gpu() -> bool:
+    """Sequential JPEG files of three one-component scans are decoded on the GPU; METERELF_JPEG_MULTISCAN=host leaves them to the host
+    branch.  On by default because one such file in a 256-file call costs less on the GPU than through the host branch
+    (profiles/jpeg_scans/jpeg_scans_rate.txt: 1.22 against 2.85 ms a call)."""
+    return os.getenv('METERELF_JPEG_MULTISCAN', 'gpu') != 'host'
+
+
+def _jpeg_default_tables_on_gpu() -> bool:
+    """JPEG files that leave Huffman tables out (Motion-JPEG frames) are decoded on the GPU with the Annex K tables;
+    METERELF_JPEG_TABLES=host leaves them to the host branch."""
+    return os.getenv('METERELF_JPEG_TABLES', 'gpu') != 'host'
+
+
 def _reader_key(params, blob, device: int) -> bytes:
     env = ';'.join('%s=%s' % (k, os.environ[k]) for k in _ENV_IN_KEY if k in os.environ)
-    orient = b'|orient%d|prog%d|samp%d|' % (_jpeg_orientation_on_gpu(), _jpeg_progressive_on_gpu(), _jpeg_samplings_on_gpu())   # a reader keeps the settings it was made with
+    orient = b'|orient%d|prog%d|samp%d|scans%d|tabs%d|' % (_jpeg_orientation_on_gpu(), _jpeg_progressive_on_gpu(), _jpeg_samplings_on_gpu(),
+                                                          _jpeg_multiscan_on_gpu(), _jpeg_default_tables_on_gpu())   # a reader keeps the settings it was made with
     return hashlib.sha1(blob.tobytes() + repr(list(params.dial_names)).encode() + b'|dev%d|' % device + orient + env.encode()).digest()
 
 
 def _with_jpeg_orientation(reader):
-    """Turns a new reader's switches on (MeterReader.set_jpeg_orientation, set_jpeg_progressive, set_jpeg_samplings) unless the host branch is asked for;
+    """Turns a new reader's switches on (MeterReader.set_jpeg_orientation, set_jpeg_progressive, set_jpeg_samplings, set_jpeg_multiscan,
+    set_jpeg_default_tables) unless the host branch is asked for;
     a reader from the cache has them already (the settings are part of its key)."""
     if _jpeg_orientation_on_gpu() and hasattr(reader, 'set_jpeg_orientation') and not getattr(reader, 'jpeg_orientation', False):
         reader.set_jpeg_orientation(True)
@@ -105,6 +125,10 @@ def _with_jpeg_orientation(reader):
         reader.set_jpeg_progressive(True)
     if _jpeg_samplings_on_gpu() and hasattr(reader, 'set_jpeg_samplings') and not getattr(reader, 'jpeg_samplings', False):
         reader.set_jpeg_samplings(True)
+    if _jpeg_multiscan_on_gpu() and hasattr(reader, 'set_jpeg_multiscan') and not getattr(reader, 'jpeg_multiscan', False):
+        reader.set_jpeg_multiscan(True)
+    if _jpeg_default_tables_on_gpu() and hasattr(reader, 'set_jpeg_default_tables') and not getattr(reader, 'jpeg_default_tables', False):
+        reader.set_jpeg_default_tables(True)
     return reader
 
 

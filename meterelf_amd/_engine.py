@@ -125,8 +125,14 @@ def records_to_items(records: np.ndarray, ok, dial_names: List[str], filenames: 
 
 class MeterReader:
     def __init__(self, params: Params, device: int = 0, blob: Optional[np.ndarray] = None, ctx: Optional['_hip.Context'] = None,
-                 jpeg_orientation: bool = False, jpeg_progressive: bool = False, jpeg_samplings: bool = False) -> None:
-        """jpeg_samplings: the read_jpeg_* methods decode YCbCr 4:4:0 and 4:1:1 JPEG files (a losslessly rotated 4:2:2 file; DV-derived
+                 jpeg_orientation: bool = False, jpeg_progressive: bool = False, jpeg_samplings: bool = False,
+                 jpeg_multiscan: bool = False, jpeg_default_tables: bool = False) -> None:
+        """jpeg_default_tables: the read_jpeg_* methods decode sequential JPEG files that leave Huffman tables 0 / 1 out (Motion-JPEG frames of
+        UVC webcams and AVI MJPG streams: no DHT segment) with the T.81 Annex K tables, as libjpeg-turbo does, instead of leaving them to
+        the caller's host decoder, which is the default.
+        jpeg_multiscan: the read_jpeg_* methods decode sequential JPEG files sent as three scans of one component each on the GPU, byte
+        for byte like libjpeg, instead of leaving them to the caller's host decoder, which is the default.
+        jpeg_samplings: the read_jpeg_* methods decode YCbCr 4:4:0 and 4:1:1 JPEG files (a losslessly rotated 4:2:2 file; DV-derived
         encoders) on the GPU, byte for byte like libjpeg, instead of leaving them to the caller's host decoder, which is the default.
         jpeg_progressive: the read_jpeg_* methods decode progressive JPEG files (the subset include/meterelf_hip.h states) on the
         GPU instead of leaving them to the caller's host decoder, which is the default.
@@ -149,6 +155,22 @@ class MeterReader:
         self.jpeg_samplings = False
         if jpeg_samplings:
             self.set_jpeg_samplings(True)
+        self.jpeg_multiscan = False
+        if jpeg_multiscan:
+            self.set_jpeg_multiscan(True)
+        self.jpeg_default_tables = False
+        if jpeg_default_tables:
+            self.set_jpeg_default_tables(True)
+
+    def set_jpeg_multiscan(self, on: bool) -> None:
+        """The switch of the constructor's jpeg_multiscan, on a reader with nothing in flight (melf_ctx_set_jpeg_multiscan)."""
+        self.ctx.set_jpeg_multiscan(on)
+        self.jpeg_multiscan = bool(on)
+
+    def set_jpeg_default_tables(self, on: bool) -> None:
+        """The switch of the constructor's jpeg_default_tables, on a reader with nothing in flight (melf_ctx_set_jpeg_default_tables)."""
+        self.ctx.set_jpeg_default_tables(on)
+        self.jpeg_default_tables = bool(on)
 
     def set_jpeg_samplings(self, on: bool) -> None:
         """The switch of the constructor's jpeg_samplings, on a reader with nothing in flight (melf_ctx_set_jpeg_samplings)."""
@@ -551,9 +573,10 @@ class MeterReader:
         decodes that one on the host."""
         out: List[Optional[np.void]] = [None] * len(files)
         groups: Dict[Tuple[int, int], List[int]] = {}
-        if self.jpeg_orientation or self.jpeg_progressive or self.jpeg_samplings:   # what the context's switches make the library take
+        if self.jpeg_orientation or self.jpeg_progressive or self.jpeg_samplings or self.jpeg_multiscan or self.jpeg_default_tables:   # what the context's switches make the library take
             flags = (_hip.JPEG_TAKE_ORIENTED if self.jpeg_orientation else 0) | (_hip.JPEG_TAKE_PROGRESSIVE if self.jpeg_progressive else 0) | \
-                    (_hip.JPEG_TAKE_SAMPLINGS if self.jpeg_samplings else 0)
+                    (_hip.JPEG_TAKE_SAMPLINGS if self.jpeg_samplings else 0) | (_hip.JPEG_TAKE_MULTISCAN if self.jpeg_multiscan else 0) | \
+                    (_hip.JPEG_TAKE_DEFAULT_TABLES if self.jpeg_default_tables else 0)
             (hs, ws, orient, oks) = _hip.jpeg_probe_flags_batch(files, flags)
             if self.jpeg_orientation:    # by UPRIGHT size: what the library takes as H and W once that switch is on
                 (hs, ws) = (np.where(orient >= 5, ws, hs), np.where(orient >= 5, hs, ws))

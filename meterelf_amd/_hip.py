@@ -233,6 +233,7 @@ EXPORTS = [
     'melf_jpeg_probe_oriented', 'melf_jpeg_probe_oriented_batch', 'melf_ctx_set_jpeg_orientation', 'melf_ctx_get_jpeg_orientation',
     'melf_jpeg_probe_flags', 'melf_jpeg_probe_flags_batch', 'melf_ctx_set_jpeg_progressive', 'melf_ctx_get_jpeg_progressive',
     'melf_ctx_set_jpeg_samplings', 'melf_ctx_get_jpeg_samplings',
+    'melf_ctx_set_jpeg_multiscan', 'melf_ctx_get_jpeg_multiscan', 'melf_ctx_set_jpeg_default_tables', 'melf_ctx_get_jpeg_default_tables',
 ]
 
 _lib = None
@@ -331,6 +332,10 @@ def lib():
     L.melf_ctx_get_jpeg_progressive.argtypes = [vp, C.POINTER(C.c_int)]
     L.melf_ctx_set_jpeg_samplings.argtypes = [vp, C.c_int]
     L.melf_ctx_get_jpeg_samplings.argtypes = [vp, C.POINTER(C.c_int)]
+    L.melf_ctx_set_jpeg_multiscan.argtypes = [vp, C.c_int]
+    L.melf_ctx_get_jpeg_multiscan.argtypes = [vp, C.POINTER(C.c_int)]
+    L.melf_ctx_set_jpeg_default_tables.argtypes = [vp, C.c_int]
+    L.melf_ctx_get_jpeg_default_tables.argtypes = [vp, C.POINTER(C.c_int)]
     L.melf_jpeg_decode_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]
     L.melf_jpeg_process_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.melf_jpeg_process_files.argtypes = [vp, vp, C.c_int, i32p, i32p, vp, vp]
@@ -1086,11 +1091,13 @@ def jpeg_probe_oriented_batch(files):
 JPEG_TAKE_ORIENTED = 1      # MELF_JPEG_TAKE_*: the switches a probe answers for
 JPEG_TAKE_PROGRESSIVE = 2
 JPEG_TAKE_SAMPLINGS = 4     # 4:4:0 and 4:1:1 files (melf_ctx_set_jpeg_samplings)
+JPEG_TAKE_MULTISCAN = 32    # sequential files of three one-component scans (melf_ctx_set_jpeg_multiscan)
+JPEG_TAKE_DEFAULT_TABLES = 16   # sequential files that leave Huffman tables 0 / 1 out: Motion-JPEG frames (melf_ctx_set_jpeg_default_tables)
 
 
 def jpeg_probe_flags(data, flags):
     """(H, W, orientation, supported, reason) of a JPEG file's bytes as the decode calls of a context with the switches `flags`
-    (JPEG_TAKE_ORIENTED | JPEG_TAKE_PROGRESSIVE | JPEG_TAKE_SAMPLINGS) on answer from the headers: H and W are the STORED size, orientation is the EXIF code
+    (JPEG_TAKE_ORIENTED | JPEG_TAKE_PROGRESSIVE | JPEG_TAKE_SAMPLINGS | JPEG_TAKE_MULTISCAN | JPEG_TAKE_DEFAULT_TABLES) on answer from the headers: H and W are the STORED size, orientation is the EXIF code
     1..8 whether or not oriented files are taken.  With flags 0: jpeg_probe plus the orientation.  Header parse only, no GPU."""
     L = lib()
     H, W, o, ok = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
@@ -1711,6 +1718,26 @@ class Context:
     def jpeg_samplings(self):
         on = C.c_int(0)
         check(self._L.melf_ctx_get_jpeg_samplings(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def set_jpeg_multiscan(self, on):
+        """Sequential JPEG files sent as three scans of one component each are decoded by the jpeg_* calls of this context instead
+        of coming back unsupported (melf_ctx_set_jpeg_multiscan).  Off by default."""
+        check(self._L.melf_ctx_set_jpeg_multiscan(self._h, int(bool(on))))
+
+    def jpeg_multiscan(self):
+        on = C.c_int(0)
+        check(self._L.melf_ctx_get_jpeg_multiscan(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def set_jpeg_default_tables(self, on):
+        """Sequential JPEG files that leave Huffman tables 0 / 1 out (Motion-JPEG frames: no DHT segment) are decoded with the
+        T.81 Annex K tables, as libjpeg-turbo does, instead of coming back unsupported (melf_ctx_set_jpeg_default_tables).  Off by default."""
+        check(self._L.melf_ctx_set_jpeg_default_tables(self._h, int(bool(on))))
+
+    def jpeg_default_tables(self):
+        on = C.c_int(0)
+        check(self._L.melf_ctx_get_jpeg_default_tables(self._h, C.byref(on)))
         return bool(on.value)
 
     def set_frames_resident(self, on):

@@ -1,11 +1,12 @@
 // Baseline JPEG decode on the GPU: replaces the host decode behind
 // cv2.imread (meterelf/_image.py:49) for the files the meter cameras write -- baseline sequential
 // DCT, 8 bit, Huffman, one interleaved scan, YCbCr 4:2:0 / 4:2:2 / 4:4:4 or greyscale (and 4:4:0 / 4:1:1 for a caller that asked for
-// them: melf_ctx_set_jpeg_samplings).  Within that: SOF0 or SOF1, Huffman
+// them: melf_ctx_set_jpeg_samplings; and three scans of one component each instead of the interleaved one for a caller that asked
+// for those: melf_ctx_set_jpeg_multiscan, melf_jpeg_scans.h).  Within that: SOF0 or SOF1, Huffman
 // table ids 0 and 1 in any assignment to the components, quantisation tables 0..3 with 8- or 16-bit entries, any component
 // ids, any order and packing of the header segments.  Everything else is reported unsupported (the caller's host decoder
 // takes it), including a file that refers to a Huffman table it does not define (libjpeg-turbo falls back to the Annex K
-// tables there) or to one libjpeg rejects (over-subscribed, using the all-ones code, a DC category above 15).
+// tables there, and so does the parser for a caller that asked for it: melf_ctx_set_jpeg_default_tables) or to one libjpeg rejects (over-subscribed, using the all-ones code, a DC category above 15).
 //
 // The result must be the bytes libjpeg(-turbo) produces with its defaults (what cv2.imread and
 // Pillow both use): JDCT_ISLOW inverse DCT, "fancy" triangle-filter chroma upsampling, the
@@ -21,6 +22,8 @@
 //          k_jpeg_prog_scan progressive files (SOF2), for a caller that asked for them (melf_ctx_set_jpeg_progressive): every scan
 //                           accumulated into the same coefficient blocks, one wave per (file, scan, restart interval), one launch
 //                           per level of scans that depend on each other (melf_jpeg_prog.h); J2 and J3 then run as for any file
+//          (multi-scan sequential files: each scan is a one-component record of its own through k_jpeg_clean and the two kernels above,
+//          k_jpeg_scan_status then gives the file the worst of its scans' statuses)
 //   J2     k_jpeg_idct      one thread per 8x8 block: dequantise + ISLOW IDCT -> u8 planes
 //   J3     k_jpeg_color420  8 pixels per thread: fancy upsample + YCC->BGR -> NHWC frame (k_jpeg_color: other modes)
 //          k_jpeg_color_exif  files with an EXIF orientation 2-8 (when the caller asked for them): the same conversion in
@@ -28,6 +31,8 @@
 #include "melf_internal.h"
 #include "melf_jpeg_orient_addr.h"
 #include "melf_jpeg_prog.h"
+#include "melf_jpeg_scans.h"
+#include "melf_jpeg_std_tables.h"
 #include "melf_threads.h"
 
 #include <emmintrin.h>
@@ -76,8 +81,13 @@ struct JpegHeader {
     std::vector<jpeg_prog::Scan> pscans;
     std::vector<jpeg_prog::Huff> ptabs;
     std::vector<uint32_t> prst;
+    // A multi-scan sequential file that is taken (melf_jpeg_scans.h): per COMPONENT its scan -- the tables in force at its SOS, its
+    // restart interval (in blocks of the component), and its entropy-coded bytes (offset relative to scan_begin, up to the next marker)
+    struct MScan { HuffSpec dc, ac; int restart_interval; size_t off, len; };
+    bool multiscan = false;
+    std::vector<MScan> ms;      // three, once multiscan
 };
-constexpr int TAKE_ORIENTED = 1, TAKE_PROGRESSIVE = 2, TAKE_SAMPLINGS = 4;   // MELF_JPEG_TAKE_*: what a caller's switches make the parser accept
+constexpr int TAKE_ORIENTED = 1, TAKE_PROGRESSIVE = 2, TAKE_SAMPLINGS = 4, TAKE_DEFAULT_TABLES = 16, TAKE_MULTISCAN = 32;   // MELF_JPEG_TAKE_*: what a caller's switches make the parser accept
 
 static inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
 
@@ -143,6 +153,24 @@ static void frame_rules(JpegHeader& h, const bool take_samp)
     } else {
         h.hs[0] = h.vs[0] = 1;  // a single-component scan is never interleaved: one block per MCU
     }
+}
+
+// libjpeg-turbo's std_huff_tables, for a caller that asked for it (TAKE_DEFAULT_TABLES): when the Huffman decoder starts -- behind the
+// headers up to the first SOS -- each of the slots DC 0, AC 0, DC 1, AC 1 that no DHT has defined receives the table Annex K.3 prints
+// for it (melf_jpeg_std_tables.h).  Slots 2 and 3 receive nothing; a slot a DHT defined keeps its definition, flawed or not.
+static void install_std_tables(JpegHeader& h)
+{
+    for (int cls = 0; cls < 2; ++cls)
+        for (int id = 0; id < 2; ++id) {
+            HuffSpec& t = cls ? h.ac[id] : h.dc[id];
+            if (t.set) continue;
+            const jpeg_std::Table& k = jpeg_std::TABLES[cls][id];
+            t.bits[0] = 0;
+            memcpy(t.bits + 1, k.counts, 16);
+            memcpy(t.vals, k.vals, (size_t)k.nvals);
+            t.nvals = k.nvals;
+            t.set = true;
+        }
 }
 
 struct HuffSlow;
@@ -219,10 +247,13 @@ static const char* prog_scan_header(JpegHeader& h, ProgState& ps, const uint8_t*
 
 // take: TAKE_ORIENTED -- a file with an orientation tag 2..8 is one for the GPU (h.orient says which); TAKE_PROGRESSIVE -- so is a
 // progressive file of the subset include/meterelf_hip.h states (h.progressive, h.pscans); TAKE_SAMPLINGS -- and a 4:4:0 or 4:1:1
-// file (frame_rules).  Otherwise they are unsupported, as ever.
+// file (frame_rules); TAKE_DEFAULT_TABLES -- and a sequential file that leaves Huffman tables 0 / 1 out (install_std_tables).  Otherwise
+// they are unsupported, as ever.
 static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h, const int take = 0)
 {
     const bool take_orient = (take & TAKE_ORIENTED) != 0, take_prog = (take & TAKE_PROGRESSIVE) != 0, take_samp = (take & TAKE_SAMPLINGS) != 0;
+    const bool take_multi = (take & TAKE_MULTISCAN) != 0;
+    unsigned ms_seen = 0;   // multi-scan sequential file: the components that have had their scan
     for (int i = 0; i < 4; ++i) { h.dc[i].set = false; h.ac[i].set = false; }
     if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return -1;
     size_t i = 2;
@@ -236,6 +267,7 @@ static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h, const int ta
         if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;  // parameterless
         if (m == 0xD9) {
             if (h.progressive && ps.started) goto prog_done;
+            if (h.multiscan) { h.why = "sequential file that ends before every component has had its scan"; return 0; }
             return -1;                                                      // EOI before SOS
         }
         if (i + 2 > n) return -1;
@@ -249,6 +281,11 @@ static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h, const int ta
             h.why = "second frame header in a progressive file (libjpeg rejects it)";
             return 0;
         }
+        if (h.multiscan) {   // between the scans of a multi-scan sequential file: DHT and DRI count, COM and APPn are passed by
+            if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) { h.why = "second frame header behind a scan (libjpeg rejects it)"; return 0; }
+            if (m == 0xDB) { h.why = "quantisation table defined after the first scan of a multi-scan file"; return 0; }
+            if ((m >= 0xE0 && m <= 0xEF) || m == 0xFE) { i += L; continue; }
+        }
         switch (m) {
             case 0xC0: case 0xC1: sof_taken: {  // baseline / extended sequential, Huffman -- and progressive, where the caller takes it
                 if (len < 6) return -1;
@@ -261,7 +298,7 @@ static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h, const int ta
                 }
                 have_sof = true;
                 if (m == 0xC2) h.progressive = true;
-                else if (high_table) h.why = "Huffman table id above 1";
+                else if (high_table && !take_multi) h.why = "Huffman table id above 1";   // (take_multi: decided at the first SOS)
                 break;
             }
             case 0xC2:
@@ -296,8 +333,8 @@ static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h, const int ta
                     for (int l = 1; l <= 16; ++l) total += s[o + l];
                     if (total > 256 || o + 17 + total > len || tc > 1) return -1;
                     // ids 2 and 3 are a progressive file's to use; anywhere else they make the file unsupported, as ever
-                    if (th > 3 || (th > 1 && !take_prog)) { h.why = "Huffman table id above 1"; o += 17 + total; continue; }
-                    if (th > 1 && !h.progressive) { if (have_sof) h.why = "Huffman table id above 1"; else high_table = true; }
+                    if (th > 3 || (th > 1 && !take_prog && !take_multi)) { h.why = "Huffman table id above 1"; o += 17 + total; continue; }
+                    if (th > 1 && !h.progressive) { if (have_sof && !take_multi) h.why = "Huffman table id above 1"; else high_table = true; }
                     (tc ? ps.ac_idx[th] : ps.dc_idx[th]) = -1;   // a scan after this one builds the new definition
                     HuffSpec& t = tc ? h.ac[th] : h.dc[th];
                     t.bits[0] = 0;
@@ -370,7 +407,48 @@ static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h, const int ta
                     i = end;
                     continue;
                 }
+                if (h.multiscan || (take_multi && h.ncomp == 3 && (ns == 1 || ns == 2))) {
+                    // A sequential file that sends its components in scans of their own (melf_jpeg_scans.h).  Ids 2 and 3 and
+                    // redefinitions between the scans are free: every scan keeps a snapshot of the two tables in force at its SOS.
+                    if (h.why) return 0;
+                    if (!h.multiscan) {   // the frame must be one for the decoder before any scan byte is looked at
+                        frame_rules(h, take_samp);
+                        for (int c = 0; c < h.ncomp && !h.why; ++c)
+                            if (!h.qt_set[h.tq[c]]) h.why = "missing quantisation table";
+                        if (h.why) return 0;
+                        if (take & TAKE_DEFAULT_TABLES) install_std_tables(h);   // once, before the first scan, as libjpeg does
+                        h.scan_begin = i + L;
+                        h.multiscan = true;
+                        h.ms.assign(3, JpegHeader::MScan());
+                    }
+                    int c = -1;
+                    for (int q = 0; q < h.ncomp; ++q) if (h.id[q] == s[1]) c = q;
+                    const uint8_t* e = s + 1 + 2 * ns;
+                    if (const char* flaw = jpeg_scans::scan_rule(ns, c, ms_seen, e[0], e[1], e[2])) { h.why = flaw; return 0; }
+                    const int td = s[2] >> 4, ta = s[2] & 15;
+                    if (td > 3 || ta > 3) { h.why = "Huffman table id above 3"; return 0; }
+                    if (!h.dc[td].set || !h.ac[ta].set) { h.why = "missing Huffman table"; return 0; }
+                    if (const char* flaw = huff_spec_flaw(h.dc[td], true)) { h.why = flaw; return 0; }
+                    if (const char* flaw = huff_spec_flaw(h.ac[ta], false)) { h.why = flaw; return 0; }
+                    JpegHeader::MScan& sc = h.ms[c];
+                    sc.dc = h.dc[td]; sc.ac = h.ac[ta];
+                    sc.restart_interval = h.restart_interval;
+                    sc.off = i + L - h.scan_begin;
+                    uint32_t found = 0;
+                    const size_t end = jpeg_prog::walk_scan(d, i + L, n, nullptr, 0, &found);   // the one pass over these files' bytes
+                    if (end >= n) return -1;   // the data end inside a scan: a truncated file
+                    sc.len = end - (i + L);
+                    ms_seen |= 1u << c;
+                    i = end;
+                    if (ms_seen != 7u) continue;
+                    size_t j = end;   // behind the third scan: EOI (what lies behind that is ignored, as ever)
+                    while (j < n && d[j] == 0xFF) ++j;
+                    if (j >= n) return -1;
+                    if (d[j] != 0xD9) h.why = "segment behind the third scan of a multi-scan file other than EOI";
+                    return 0;
+                }
                 if (ns != h.ncomp) { h.why = "more than one scan (non-interleaved components)"; return 0; }
+                if (take_multi && high_table && !h.why) h.why = "Huffman table id above 1";
                 for (int k = 0; k < ns; ++k) {
                     const int cid = s[1 + 2 * k];
                     int c = -1;
@@ -399,6 +477,7 @@ done:
     if (h.why) return 0;
     frame_rules(h, take_samp);
     if (h.H <= 0 || h.W <= 0) return 0;
+    if (take & TAKE_DEFAULT_TABLES) install_std_tables(h);
     for (int c = 0; c < h.ncomp && !h.why; ++c) {
         if (!h.qt_set[h.tq[c]]) h.why = "missing quantisation table";
         else if (!h.dc[h.td[c]].set || !h.ac[h.ta[c]].set) h.why = "missing Huffman table";
@@ -440,7 +519,7 @@ int jpeg_probe_oriented(const uint8_t* data, size_t size, int* H, int* W, int* o
 int jpeg_probe_flags(const uint8_t* data, size_t size, int flags, int* H, int* W, int* orientation, int* supported, std::string* why)
 {
     JpegHeader h;
-    if (parse_headers(data, size, h, flags & (TAKE_ORIENTED | TAKE_PROGRESSIVE | TAKE_SAMPLINGS)) != 0) {
+    if (parse_headers(data, size, h, flags & (TAKE_ORIENTED | TAKE_PROGRESSIVE | TAKE_SAMPLINGS | TAKE_MULTISCAN | TAKE_DEFAULT_TABLES)) != 0) {
         *H = *W = 0; *supported = 0; *orientation = 1;
         if (why) *why = "not a JPEG file or truncated headers";
         return 0;
@@ -487,9 +566,12 @@ struct JpegImageDev {
     uint8_t ncomp, hs0, vs0, ok;
     uint8_t tq[3], td[3], ta[3];
     uint8_t orient;               // EXIF orientation the colour stage applies (1..8); the other stages work in stored geometry
-    uint8_t pad[2];
+    uint8_t planar;               // a multi-scan sequential file (ok = 4): every component's blocks in an area of its own, coef_blk[c], the
+                                  // REAL blocks in raster order, written by the one-component records of its scans (melf_jpeg_scans.h)
+    uint8_t pad[1];
     uint32_t rst_off, rst_cnt;    // restart intervals: table of their byte offsets in the clean scan (relative to the
-                                  // scan area), number of intervals
+                                  // scan area), number of intervals.  A planar file's record has no scan of its own and keeps its
+                                  // real block grids here: rst_off = luma, rst_cnt = chroma, columns | rows << 16
     // Filled by the host; scan_len and rst_cnt (and the bytes they describe) by k_jpeg_clean on the GPU (round 4):
     uint32_t scan_cap;            // bytes of the scan area reserved for this file's clean scan (zero-filled behind scan_len)
     uint32_t raw_off, raw_len;    // the file's entropy-coded segment as it is in the file (stuffing, fill bytes, RSTn, EOI and
@@ -1586,6 +1668,20 @@ __global__ __launch_bounds__(256) void k_jpeg_idct(const JpegImageDev* __restric
     const int mcu = (by / fy) * I.mcus_x + bx / fx;
     const int inb = c == 0 ? (by % fy) * I.hs0 + bx % fx : I.hs0 * I.vs0 + c - 1;
     const int16_t* src = coefs + ((size_t)I.coef_blk[0] + (size_t)mcu * bpm + inb) * 64;
+    if (I.planar) {
+        // a multi-scan file: the component's real blocks in raster order in its own area.  No scan sends the MCU-padding blocks:
+        // they come out as zero blocks (flat 128), and no pixel of the frame reads them
+        const uint32_t grid = c == 0 ? I.rst_off : I.rst_cnt;
+        const int rbx = (int)(grid & 0xffffu), rby = (int)(grid >> 16);
+        if (bx >= rbx || by >= rby) {
+            const int pstride = I.blocks_x[c] * 8;
+            uint8_t* pad = planes + I.plane_off[c] + (size_t)(by * 8) * pstride + bx * 8;
+#pragma unroll
+            for (int y = 0; y < 8; ++y) *(uint2*)(pad + (size_t)y * pstride) = make_uint2(0x80808080u, 0x80808080u);
+            return;
+        }
+        src = coefs + ((size_t)I.coef_blk[c] + (size_t)by * rbx + bx) * 64;
+    }
     const uint16_t* q = g_qt + ((size_t)img * 4 + I.tq[c]) * 64;
     int ws[64];
     // pass 1: columns
@@ -1613,6 +1709,16 @@ __global__ __launch_bounds__(256) void k_jpeg_idct(const JpegImageDev* __restric
         }
         *(uint2*)(dst + (size_t)y * stride) = make_uint2(lo, hi);
     }
+}
+
+// A multi-scan file's status is the worst of its scans' statuses (0 or 2 each): map holds, per such file, the index of its record and
+// of its three scans' records.  Runs behind the scans' Huffman kernels; the IDCT and colour stages read the file's combined status.
+__global__ __launch_bounds__(64) void k_jpeg_scan_status(const uint32_t* __restrict__ map, const int files, int32_t* __restrict__ status)
+{
+    const int f = blockIdx.x * 64 + threadIdx.x;
+    if (f >= files) return;
+    const uint32_t* m = map + 4 * (size_t)f;
+    status[m[0]] = max(status[m[1]], max(status[m[2]], status[m[3]]));
 }
 
 // ------------------------------------------------------ J3: upsample + colour ----
@@ -1924,6 +2030,19 @@ struct JpegWorkspace {
         uint32_t prog_scans = 0;
     };
     std::vector<Run> runs;
+    // Multi-scan sequential files (melf_jpeg_scans.h): their scans are one-component records of their own behind the batch's n file
+    // records (n_scan_recs of them, with tables and clean-scan regions of their own), grouped by what fixes a scan's window -- the
+    // file's orientation code and sampling, and whether the component is luma or chroma -- each group one launch of the Huffman kernels
+    // on its own window.  ms_files: such files in the batch; off_msmap: per file the indices of its record and of its three scans'
+    // records (k_jpeg_scan_status).  A batch without such a file has none of this and launches what it launched before.
+    struct ScanGroup {
+        int first, n, code, hs0, vs0, chroma;   // first: index among the scan records
+        int n_par, n_seq;
+        size_t max_par_scan;
+    };
+    std::vector<ScanGroup> scan_groups;
+    int n_scan_recs = 0, ms_files = 0;
+    size_t off_msmap = 0;
 };
 
 void jpeg_workspace_free(JpegWorkspace* w)
@@ -2048,6 +2167,7 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
     size_t coef_blocks = 0, plane_bytes = 0;
     int max_blocks = 0;
     std::vector<JpegImageDev> rec(n);
+    std::vector<int> ms_files;            // multi-scan sequential files handed to the GPU
     std::vector<jpeg_prog::File> pfile;   // one per file once the batch has a progressive file
     size_t pscans = 0, ptabs = 0, prsts = 0;
     for (int i = 0; i < n; ++i)
@@ -2059,6 +2179,12 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
         raw_off[i + 1] = raw_off[i];
         if (host_status[i] != 0) continue;
         const JpegHeader& h = hbase[hidx(i)];
+        if (h.multiscan) {   // each scan has the 1024-segment allowance of a file's one scan
+            for (const JpegHeader::MScan& sc : h.ms)
+                if (!sc.restart_interval && sc.len > JPEG_MAX_PAR_SCAN) host_status[i] = 1;   // valid, but for the host decoder
+            if (host_status[i] != 0) continue;
+            ms_files.push_back(i);
+        }
         if (h.progressive) {
             jpeg_prog::File& f = pfile[i];
             f = prog_file_geometry(h);
@@ -2091,8 +2217,8 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
         r.raw_len = (uint32_t)raw_len;
         raw_off[i + 1] = raw_off[i] + align_up(raw_len + 32, 64);   // k_jpeg_clean reads up to 20 bytes past the end
         // (a progressive file is decoded from its raw bytes: no clean scan, no restart table in the scan area)
-        size_t region = h.progressive ? 128 : align_up(raw_len + 128, 64);
-        if (h.restart_interval && !h.progressive) {  // room for the table of interval offsets behind the scan
+        size_t region = (h.progressive || h.multiscan) ? 128 : align_up(raw_len + 128, 64);
+        if (h.restart_interval && !h.progressive && !h.multiscan) {  // room for the table of interval offsets behind the scan
             const size_t mcus = (size_t)r.mcus_x * r.mcus_y;
             r.rst_cnt = (uint32_t)((mcus + h.restart_interval - 1) / h.restart_interval);  // expected; replaced by the number found
             r.rst_off = (uint32_t)region;                                                   // relative for now
@@ -2100,20 +2226,69 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
         }
         scan_off[i + 1] = scan_off[i] + region;
     }
-    if (coef_blocks >= (1ull << 32) / 64 || plane_bytes >= (1ull << 32) || scan_off[n] >= (1ull << 32) || raw_off[n] >= (1ull << 32)) {
+    // The scans of the multi-scan files: one-component records behind the n file records, in groups of one window
+    struct ScanEntry { int file, comp; uint32_t key; };
+    std::vector<ScanEntry> ms_scans;
+    for (const int i : ms_files)
+        for (int c = 0; c < 3; ++c)
+            ms_scans.push_back({i, c, (uint32_t)rec[i].orient << 16 | (uint32_t)rec[i].hs0 << 8 | (uint32_t)rec[i].vs0 << 4 | (c ? 1u : 0u)});
+    std::stable_sort(ms_scans.begin(), ms_scans.end(), [](const ScanEntry& a, const ScanEntry& b) { return a.key < b.key; });
+    const int extra = (int)ms_scans.size();
+    w->scan_groups.clear();
+    w->n_scan_recs = extra;
+    w->ms_files = (int)ms_files.size();
+    if (extra) {
+        rec.resize((size_t)n + extra);
+        scan_off.resize((size_t)n + extra + 1);
+        for (int k = 0; k < extra; ++k) {
+            const ScanEntry& se = ms_scans[k];
+            const JpegHeader& h = hbase[hidx(se.file)];
+            const JpegHeader::MScan& sc = h.ms[se.comp];
+            const jpeg_scans::Comp comp = jpeg_scans::component(h.W, h.H, h.hs[0], h.vs[0], se.comp);
+            JpegImageDev& r = rec[(size_t)n + k];
+            memset(&r, 0, sizeof(r));
+            r.ok = sc.restart_interval ? 2 : 1;
+            r.orient = 1;
+            r.ncomp = 1; r.hs0 = 1; r.vs0 = 1;
+            r.restart_interval = (uint16_t)sc.restart_interval;
+            r.mcus_x = r.blocks_x[0] = (uint16_t)comp.rbx;   // one block is an MCU: the component's real blocks in raster order
+            r.mcus_y = r.blocks_y[0] = (uint16_t)comp.rby;
+            r.coef_blk[0] = rec[se.file].coef_blk[se.comp];
+            r.raw_off = rec[se.file].raw_off + (uint32_t)sc.off;   // inside the file's bytes, which are uploaded once
+            r.raw_len = (uint32_t)sc.len;
+            size_t region = align_up(sc.len + 128, 64);
+            r.scan_cap = (uint32_t)region;
+            r.scan_off = (uint32_t)scan_off[(size_t)n + k];
+            if (sc.restart_interval) {
+                const size_t blocks = (size_t)comp.rbx * comp.rby;
+                r.rst_cnt = (uint32_t)((blocks + sc.restart_interval - 1) / sc.restart_interval);   // expected; replaced by the number found
+                r.rst_off = (uint32_t)(scan_off[(size_t)n + k] + region);
+                region += align_up(((size_t)r.rst_cnt + 1) * sizeof(uint32_t), 64);
+            }
+            scan_off[(size_t)n + k + 1] = scan_off[(size_t)n + k] + region;
+            if (w->scan_groups.empty() || ms_scans[k - 1].key != se.key)
+                w->scan_groups.push_back({k, 0, (int)rec[se.file].orient, (int)rec[se.file].hs0, (int)rec[se.file].vs0, se.comp ? 1 : 0, 0, 0, 0});
+            JpegWorkspace::ScanGroup& g = w->scan_groups.back();
+            ++g.n;
+            if (r.ok == 1) { ++g.n_par; g.max_par_scan = std::max(g.max_par_scan, sc.len); } else ++g.n_seq;
+        }
+    }
+    const size_t nrec = (size_t)n + extra;
+    if (coef_blocks >= (1ull << 32) / 64 || plane_bytes >= (1ull << 32) || scan_off[nrec] >= (1ull << 32) || raw_off[n] >= (1ull << 32)) {
         if (err) *err = "JPEG batch too large for 32-bit offsets; decode in smaller batches";
         return MELF_ERR_TOO_LARGE;
     }
     w->off_imgs = 0;
-    w->off_qt = align_up(w->off_imgs + (size_t)n * sizeof(JpegImageDev), 256);
+    w->off_qt = align_up(w->off_imgs + nrec * sizeof(JpegImageDev), 256);
     w->off_slow = align_up(w->off_qt + (size_t)n * 4 * 64 * sizeof(uint16_t), 256);
-    w->off_pfile = align_up(w->off_slow + (size_t)n * 4 * sizeof(HuffSlow), 256);
+    w->off_pfile = align_up(w->off_slow + nrec * 4 * sizeof(HuffSlow), 256);
     w->off_pscan = align_up(w->off_pfile + pfile.size() * sizeof(jpeg_prog::File), 256);
     w->off_ptab = align_up(w->off_pscan + pscans * sizeof(jpeg_prog::Scan), 256);
     w->off_prst = align_up(w->off_ptab + ptabs * sizeof(jpeg_prog::Huff), 256);
-    w->off_scan = align_up(w->off_prst + prsts * sizeof(uint32_t), 256);
+    w->off_msmap = align_up(w->off_prst + prsts * sizeof(uint32_t), 256);
+    w->off_scan = align_up(w->off_msmap + ms_files.size() * 4 * sizeof(uint32_t), 256);
     w->total = w->off_scan;                 // uploaded: records + tables
-    w->scan_bytes = scan_off[n] + 64;       // device only
+    w->scan_bytes = scan_off[nrec] + 64;    // device only
     w->raw_total = direct ? (size_t)(span_hi - span_lo) + 64 : raw_off[n] + 64;
     if (w->raw_total >= (1ull << 32)) {
         if (err) *err = "JPEG batch too large for 32-bit offsets; decode in smaller batches";
@@ -2155,7 +2330,7 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
         for (int t = 0; t < 4; ++t) {
             if (h.qt_set[t]) memcpy(qt + t * 64, h.qt[t], 128); else memset(qt + t * 64, 0, 128);
         }
-        if (h.progressive) memset(slow, 0, 4 * sizeof(HuffSlow));   // its tables go with its scans, below
+        if (h.progressive || h.multiscan) memset(slow, 0, 4 * sizeof(HuffSlow));   // its tables go with its scans, below
         else if (tables_ready) memcpy(slow, parsed->slow.data() + (size_t)hidx(i) * 4, 4 * sizeof(HuffSlow));
         else build_slow4(h, slow);
         // the entropy-coded segment as it is: stuffing, fill bytes and restart markers are taken out on the GPU (k_jpeg_clean),
@@ -2175,6 +2350,19 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
         r.scan_len = 0;
         if (h.restart_interval) r.rst_off = (uint32_t)(scan_off[i] + r.rst_off);
         r.ok = h.restart_interval != 0 ? 2 : 1;
+        if (h.multiscan) {
+            // The Huffman kernels pass this record by (ok = 4) and k_jpeg_clean only zeroes its 128 bytes of the scan area: the file's
+            // scans have records of their own.  What the record keeps is what J2 and J3 need: geometry, quantisation, the planar mark
+            // and the real block grids.
+            const jpeg_scans::Comp y = jpeg_scans::component(h.W, h.H, h.hs[0], h.vs[0], 0), cc = jpeg_scans::component(h.W, h.H, h.hs[0], h.vs[0], 1);
+            r.raw_len = 0; r.restart_interval = 0;
+            r.rst_off = (uint32_t)y.rbx | (uint32_t)y.rby << 16;
+            r.rst_cnt = (uint32_t)cc.rbx | (uint32_t)cc.rby << 16;
+            r.scan_cap = (uint32_t)(scan_off[i + 1] - scan_off[i]);
+            r.ok = 4;
+            r.planar = 1;
+            return;
+        }
         if (h.progressive) {
             // The baseline kernels must pass this file by: ok = 3 is neither k_jpeg_huff's nor k_jpeg_huff_rst's, and with no raw
             // bytes in the record k_jpeg_clean only zeroes the file's 128 bytes of the scan area.  Where the bytes are says the
@@ -2231,7 +2419,20 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
         for (int c = 0; c < rec[i].ncomp; ++c) blocks += (int)rec[i].blocks_x[c] * rec[i].blocks_y[c];
         run.max_blocks = std::max(run.max_blocks, blocks);   // (a record that was not laid out has no components)
     }
-    memcpy(base + w->off_imgs, rec.data(), (size_t)n * sizeof(JpegImageDev));
+    for (int k = 0; k < extra; ++k) {   // a scan's two tables, as they were at its SOS, in the slots DC 0 and AC 0 of its record
+        const JpegHeader::MScan& sc = hbase[hidx(ms_scans[k].file)].ms[ms_scans[k].comp];
+        HuffSlow* slow = (HuffSlow*)(base + w->off_slow) + ((size_t)n + k) * 4;
+        memset(slow, 0, 4 * sizeof(HuffSlow));
+        build_huff(sc.dc, slow);
+        build_huff(sc.ac, slow + 2);
+    }
+    for (size_t f = 0; f < ms_files.size(); ++f) {
+        uint32_t* m = (uint32_t*)(base + w->off_msmap) + 4 * f;
+        m[0] = (uint32_t)ms_files[f];
+        for (int k = 0; k < extra; ++k)
+            if (ms_scans[k].file == ms_files[f]) m[1 + ms_scans[k].comp] = (uint32_t)(n + k);
+    }
+    memcpy(base + w->off_imgs, rec.data(), nrec * sizeof(JpegImageDev));
     if (!pfile.empty()) memcpy(base + w->off_pfile, pfile.data(), (size_t)n * sizeof(jpeg_prog::File));
     if (trace) {
         const auto tp3 = std::chrono::steady_clock::now();
@@ -2259,7 +2460,7 @@ int jpeg_upload_batch(JpegWorkspace* w, int n, hipStream_t copy_stream, std::str
     JTRY(grow_dev(&w->d_raw, &w->d_raw_cap, w->raw_total));
     JTRY(grow_dev(&w->d_coefs, &w->coef_cap, w->coef_elems + 64));
     JTRY(grow_dev(&w->d_planes, &w->plane_cap, w->plane_bytes + 64));
-    JTRY(grow_dev(&w->d_status, &w->status_cap, (size_t)n));
+    JTRY(grow_dev(&w->d_status, &w->status_cap, (size_t)n + w->n_scan_recs));
     JTRY(hipMemcpyAsync(w->d_stage, w->h_stage, w->total, hipMemcpyHostToDevice, copy_stream));
     JTRY(hipMemcpyAsync(w->d_raw, w->raw_src, w->raw_total, hipMemcpyHostToDevice, copy_stream));
     return MELF_SUCCESS;
@@ -2277,15 +2478,15 @@ int jpeg_decode_batch_kernels(JpegWorkspace* w, int n, int H, int W, uint8_t* d_
         const jpeg_orient::Window ow = jpeg_orient::window(rect, r.code, Hs, Ws);
         geo.push_back({Hs, Ws, {ow.x0, ow.y0, ow.x1, ow.y1}});
     }
-    JTRY(hipMemsetAsync(w->d_status, 0, (size_t)n * sizeof(int32_t), stream));
+    JTRY(hipMemsetAsync(w->d_status, 0, ((size_t)n + w->n_scan_recs) * sizeof(int32_t), stream));
     const JpegImageDev* const imgs0 = (const JpegImageDev*)(w->d_stage + w->off_imgs);
     const uint16_t* const qt0 = (const uint16_t*)(w->d_stage + w->off_qt);
     const HuffSlow* const slow0 = (const HuffSlow*)(w->d_stage + w->off_slow);
     const uint8_t* scan = w->d_stage + w->off_scan;
     const size_t nruns = w->runs.size();
     if (timer) timer(timer_arg, 0, 0);
-    if (w->n_par + w->n_seq > 0)   // J0: stuffing, fill bytes and restart markers out of the uploaded segments
-        hipLaunchKernelGGL(k_jpeg_clean, dim3(n), dim3(CLEAN_T), 0, stream, (JpegImageDev*)(w->d_stage + w->off_imgs), w->d_raw, w->d_stage + w->off_scan);
+    if (w->n_par + w->n_seq + w->n_scan_recs > 0)   // J0: stuffing, fill bytes and restart markers out of the uploaded segments
+        hipLaunchKernelGGL(k_jpeg_clean, dim3(n + w->n_scan_recs), dim3(CLEAN_T), 0, stream, (JpegImageDev*)(w->d_stage + w->off_imgs), w->d_raw, w->d_stage + w->off_scan);
     for (size_t q = 0; q < nruns; ++q) {
         const JpegWorkspace::Run& r = w->runs[q];
         const JpegWindow win = geo[q].win;
@@ -2314,6 +2515,28 @@ int jpeg_decode_batch_kernels(JpegWorkspace* w, int n, int H, int W, uint8_t* d_
                                    (const uint32_t*)(w->d_stage + w->off_prst), w->d_raw, w->d_coefs, status, (int)sidx);
         }
     }
+    // The scans of multi-scan files, group by group: a group's records share the window its component class has in its files
+    // (melf_jpeg_scans.h), the way a run's files share theirs.  Then every such file's status from its scans'.
+    for (const JpegWorkspace::ScanGroup& g : w->scan_groups) {
+        const int Hs = jpeg_orient::swapped_h(g.code, H, W), Ws = jpeg_orient::swapped_w(g.code, H, W);
+        const jpeg_orient::Window ow = jpeg_orient::window(rect, g.code, Hs, Ws);
+        const jpeg_scans::Window sw = jpeg_scans::scan_window({ow.x0, ow.y0, ow.x1, ow.y1}, Ws, Hs, g.hs0, g.vs0, g.chroma);
+        const JpegWindow win = {sw.x0, sw.y0, sw.x1, sw.y1};
+        const JpegImageDev* imgs = imgs0 + n + g.first;
+        const HuffSlow* slow = slow0 + ((size_t)n + g.first) * 4;
+        int32_t* status = w->d_status + n + g.first;
+        if (g.n_par > 0) {
+            if (g.max_par_scan > JPEG_MAX_PAR_SCAN / 2)
+                hipLaunchKernelGGL(k_jpeg_huff<1024>, dim3(g.n), dim3(1024), 0, stream, imgs, slow, scan, w->d_coefs, status, win);
+            else
+                hipLaunchKernelGGL(k_jpeg_huff<512>, dim3(g.n), dim3(512), 0, stream, imgs, slow, scan, w->d_coefs, status, win);
+        }
+        if (g.n_seq > 0)
+            hipLaunchKernelGGL(k_jpeg_huff_rst<256>, dim3(g.n), dim3(256), 0, stream, imgs, slow, scan, w->d_coefs, status, win);
+    }
+    if (w->ms_files > 0)
+        hipLaunchKernelGGL(k_jpeg_scan_status, dim3((w->ms_files + 63) / 64), dim3(64), 0, stream, (const uint32_t*)(w->d_stage + w->off_msmap),
+                           w->ms_files, w->d_status);
     if (timer) timer(timer_arg, 0, 1);
     JTRY(hipGetLastError());
     if (w->max_blocks > 0) {

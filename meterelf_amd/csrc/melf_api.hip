@@ -285,7 +285,13 @@ struct melf_ctx {
     JpegWorkspace* jpeg = nullptr;     // created by the first JPEG batch
     bool jpeg_prog = false;            // melf_ctx_set_jpeg_progressive: progressive files of the header's subset are decoded, not refused
     bool jpeg_samp = false;            // melf_ctx_set_jpeg_samplings: 4:4:0 and 4:1:1 files are decoded, not refused
-    int jpeg_take() const { return (jpeg_orient ? MELF_JPEG_TAKE_ORIENTED : 0) | (jpeg_prog ? MELF_JPEG_TAKE_PROGRESSIVE : 0) | (jpeg_samp ? MELF_JPEG_TAKE_SAMPLINGS : 0); }
+    bool jpeg_multi = false;           // melf_ctx_set_jpeg_multiscan: sequential files of three one-component scans are decoded, not refused
+    bool jpeg_std_tabs = false;        // melf_ctx_set_jpeg_default_tables: a sequential file that leaves Huffman tables 0 / 1 out gets the Annex K ones
+    int jpeg_take() const
+    {
+        return (jpeg_orient ? MELF_JPEG_TAKE_ORIENTED : 0) | (jpeg_prog ? MELF_JPEG_TAKE_PROGRESSIVE : 0) | (jpeg_samp ? MELF_JPEG_TAKE_SAMPLINGS : 0) |
+               (jpeg_multi ? MELF_JPEG_TAKE_MULTISCAN : 0) | (jpeg_std_tabs ? MELF_JPEG_TAKE_DEFAULT_TABLES : 0);
+    }
     bool jpeg_orient = false;          // melf_ctx_set_jpeg_orientation: files with an EXIF orientation 2..8 are decoded, not refused
     // pipelined JPEG path (melf_jpeg_process_batch): a second workspace and decode stream, so that the host prepares chunk
     // k + 1 and its upload runs while chunk k decodes; per-chunk events; the files' decode status in pinned memory
@@ -921,6 +927,36 @@ extern "C" int melf_ctx_get_jpeg_samplings(melf_ctx* c, int* on)
 {
     if (!c || !on) return fail(MELF_ERR_INVALID, "bad argument");
     *on = c->jpeg_samp ? 1 : 0;
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_ctx_set_jpeg_multiscan(melf_ctx* c, int on)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    if (!c->files_jobs.empty()) return fail(MELF_ERR_INVALID, "melf_ctx_set_jpeg_multiscan while a melf_jpeg_process_files_begin call is in flight");
+    c->jpeg_multi = on != 0;
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_ctx_get_jpeg_multiscan(melf_ctx* c, int* on)
+{
+    if (!c || !on) return fail(MELF_ERR_INVALID, "bad argument");
+    *on = c->jpeg_multi ? 1 : 0;
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_ctx_set_jpeg_default_tables(melf_ctx* c, int on)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    if (!c->files_jobs.empty()) return fail(MELF_ERR_INVALID, "melf_ctx_set_jpeg_default_tables while a melf_jpeg_process_files_begin call is in flight");
+    c->jpeg_std_tabs = on != 0;
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_ctx_get_jpeg_default_tables(melf_ctx* c, int* on)
+{
+    if (!c || !on) return fail(MELF_ERR_INVALID, "bad argument");
+    *on = c->jpeg_std_tabs ? 1 : 0;
     return MELF_SUCCESS;
 }
 
@@ -2305,7 +2341,7 @@ extern "C" int melf_jpeg_probe_oriented_batch(const uint8_t* const* data, const 
 
 extern "C" int melf_jpeg_probe_flags(const uint8_t* data, size_t size, int flags, int32_t* H, int32_t* W, int32_t* orientation, int32_t* supported)
 {
-    if (!data || !H || !W || !orientation || !supported || (flags & ~(MELF_JPEG_TAKE_ORIENTED | MELF_JPEG_TAKE_PROGRESSIVE | MELF_JPEG_TAKE_SAMPLINGS)))
+    if (!data || !H || !W || !orientation || !supported || (flags & ~(MELF_JPEG_TAKE_ORIENTED | MELF_JPEG_TAKE_PROGRESSIVE | MELF_JPEG_TAKE_SAMPLINGS | MELF_JPEG_TAKE_MULTISCAN | MELF_JPEG_TAKE_DEFAULT_TABLES)))
         return fail(MELF_ERR_INVALID, "bad argument");
     int h = 0, w = 0, o = 1, ok = 0;
     std::string why;
@@ -2318,7 +2354,7 @@ extern "C" int melf_jpeg_probe_flags(const uint8_t* data, size_t size, int flags
 extern "C" int melf_jpeg_probe_flags_batch(const uint8_t* const* data, const size_t* sizes, int n, int flags, int32_t* H, int32_t* W,
                                            int32_t* orientation, int32_t* supported)
 {
-    if (n < 0 || (n > 0 && (!data || !sizes || !H || !W || !orientation || !supported)) || (flags & ~(MELF_JPEG_TAKE_ORIENTED | MELF_JPEG_TAKE_PROGRESSIVE | MELF_JPEG_TAKE_SAMPLINGS)))
+    if (n < 0 || (n > 0 && (!data || !sizes || !H || !W || !orientation || !supported)) || (flags & ~(MELF_JPEG_TAKE_ORIENTED | MELF_JPEG_TAKE_PROGRESSIVE | MELF_JPEG_TAKE_SAMPLINGS | MELF_JPEG_TAKE_MULTISCAN | MELF_JPEG_TAKE_DEFAULT_TABLES)))
         return fail(MELF_ERR_INVALID, "bad argument");
     for (int i = 0; i < n; ++i) {
         int h = 0, w = 0, o = 1, ok = 0;

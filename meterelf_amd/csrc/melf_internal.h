@@ -226,7 +226,7 @@ int jpeg_probe(const uint8_t* data, size_t size, int* H, int* W, int* supported,
 // tag), and the tag alone from a walk over the segments in front of the frame header
 int jpeg_probe_oriented(const uint8_t* data, size_t size, int* H, int* W, int* orientation, int* supported, std::string* why);
 int jpeg_file_orientation(const uint8_t* data, size_t size, int* progressive = nullptr);   // *progressive: the frame header is SOF2
-// What the decode calls answer from the headers with the switches `flags` (MELF_JPEG_TAKE_ORIENTED | MELF_JPEG_TAKE_PROGRESSIVE | MELF_JPEG_TAKE_SAMPLINGS) on
+// What the decode calls answer from the headers with the switches `flags` (MELF_JPEG_TAKE_* of include/meterelf_hip.h) on
 int jpeg_probe_flags(const uint8_t* data, size_t size, int flags, int* H, int* W, int* orientation, int* supported, std::string* why);
 // Headers (and, when asked for, the Huffman decode data built from them) of n files, parsed file by file, from any thread (one
 // thread per index): the file-name entry points parse a file right after reading it, on the thread that read it, and build its
@@ -236,7 +236,8 @@ JpegParsed* jpeg_parsed_new(int n, bool with_tables);
 void jpeg_parsed_resize(JpegParsed* p, int n);   // room for n files; nothing is cleared (jpeg_parse_one resets its entry)
 // take_orient: a file with an orientation tag 2..8 is supported, and H, W are its UPRIGHT size
 // (take: MELF_JPEG_TAKE_* flags; with MELF_JPEG_TAKE_PROGRESSIVE progressive files of the header's subset are supported too, with
-// MELF_JPEG_TAKE_SAMPLINGS 4:4:0 and 4:1:1 files)
+// MELF_JPEG_TAKE_SAMPLINGS 4:4:0 and 4:1:1 files, with MELF_JPEG_TAKE_MULTISCAN sequential files of three one-component scans, with
+// MELF_JPEG_TAKE_DEFAULT_TABLES sequential files that leave Huffman tables 0 / 1 out)
 void jpeg_parse_one(JpegParsed* p, int i, const uint8_t* data, size_t size, int* H, int* W, int* supported, int take = 0);
 void jpeg_parsed_free(JpegParsed* p);
 int jpeg_parsed_orientation(const JpegParsed* p, int i);

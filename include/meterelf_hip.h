@@ -949,6 +949,44 @@ int melf_ctx_get_jpeg_multiscan(melf_ctx* ctx, int* on);
  * METERELF_JPEG_TABLES=host restores the host branch. */
 int melf_ctx_set_jpeg_default_tables(melf_ctx* ctx, int on);
 int melf_ctx_get_jpeg_default_tables(melf_ctx* ctx, int* on);
+
+/* ---- JPEG files that end early ----
+ * A snapshot read while the camera software is still writing it, an upload that lost its connection, an MJPEG frame clipped by the
+ * transport: a baseline file whose bytes stop inside the scan.  libjpeg(-turbo), so cv2.imread and Pillow, reads such a file: its data
+ * source answers the end of the bytes with a fake EOI, the decoder goes on over zero bits, and warns.  By default every decode call
+ * gives such a file MELF_JPEG_CORRUPT and a zero frame; none of that changes.  melf_ctx_set_jpeg_truncated(ctx, 1) makes
+ * melf_jpeg_decode_batch, melf_jpeg_process_batch, melf_jpeg_process_files and melf_jpeg_process_files_begin / _end of that context give
+ * status 0 and libjpeg's frame to a sequential single-scan file (SOF0 / SOF1) the decoder takes otherwise whose scan ends, before its
+ * last block, at the end of the bytes or at an EOI.  Off at context creation; with it off every entry point behaves exactly as
+ * before, status codes, melf_last_error texts and launches included.  Not while a _begin call is in flight.  Independent of the other
+ * five switches.  No probe knows the switch: truncation does not show in the headers.
+ * The rule, bit for bit libjpeg's.  Let the stream be the entropy-coded bytes without stuffing and markers, followed by an endless run
+ * of zero bits, decoded MCU by MCU as ever.  The cut MCU is the MCU during whose decode a bit behind the real bytes is first required,
+ * by a Huffman code or by the value bits behind it; it is decoded completely, from the zero bits, and is the last one decoded.  Every
+ * block of every later MCU is all zero, DC included (no predictor is applied): mid grey.  IDCT, upsampling and colour conversion run
+ * unchanged; the chroma filter blends across the boundary as anywhere.  A stream that ends exactly on an MCU boundary with MCUs still
+ * owing makes the next MCU the cut MCU, decoded entirely from zeros.  With restart intervals: every interval before the last one found
+ * must be complete; the last one found may be short, or empty; if it is complete and intervals are owing, the first MCU of the next
+ * interval, predictors reset, is the cut MCU; intervals never reached stay zero.
+ * Exactness holds where libjpeg's range limit is a plain clamp.  The zero-decoded MCU is garbage (with the Annex K tables a luma block of
+ * 63 AC coefficients of -1) and can leave that range with coarse quantisation tables; the pixels of the cut MCU, and those whose chroma
+ * filter reads it, are then unspecified -- no fault, no access out of bounds -- and every other pixel is still exact.
+ * Still MELF_JPEG_CORRUPT, with or without the switch: a scan that ends at a marker other than EOI, a Huffman code that does not exist,
+ * a restart interval that runs out of data but is not the last one found, surplus RSTn, a progressive file that ends inside a scan
+ * (libjpeg smooths it), a multi-scan file that ends inside a scan or before its third scan, a file cut inside its headers.
+ * A file cut behind the meter_rect window plus its margin was always read by melf_jpeg_process_batch (the window-limited decode never
+ * looks behind the window); that path is untouched and such a file is not counted below.
+ * How: k_jpeg_clean records what ended the scan.  With the switch on, k_jpeg_huff and k_jpeg_huff_rst report a file that holds no
+ * impossible code but runs out of data with a status value of their own (the IDCT and colour stages treat it as 0; the host maps it to
+ * 0 and counts it), k_jpeg_huff leaving the exact entry states of its last two segments.  k_jpeg_cut_tail, one wave per file, which a
+ * file that is not cut leaves at once, walks on from there over the masked stream (meterelf_amd/csrc/melf_jpeg_cut.h: the zeros are
+ * produced, not read), writes the cut MCU's blocks inside the window, zeroes the blocks behind it that the segment decoders' 32 bits
+ * of over-run may have completed, and settles the status.
+ * melf_ctx_jpeg_truncated_files: the files this context's calls completed under the rule since the last reset (what libjpeg's
+ * warning would have told the caller); reset != 0 zeroes the count. */
+int melf_ctx_set_jpeg_truncated(melf_ctx* ctx, int on);
+int melf_ctx_get_jpeg_truncated(melf_ctx* ctx, int* on);
+int melf_ctx_jpeg_truncated_files(const melf_ctx* ctx, int64_t* files, int reset);
 /* The header check with switches: *supported is what the decode calls of a context with the switches `flags` (MELF_JPEG_TAKE_*) on
  * would answer from the headers; H and W are the STORED size, *orientation the EXIF code 1..8 whether or not oriented files are
  * taken.  With flags 0 this is melf_jpeg_probe plus the orientation code.  melf_last_error holds the reason of a refusal. */

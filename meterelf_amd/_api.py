@@ -38,6 +38,9 @@ with the T.81 Annex K tables, as libjpeg-turbo decodes them (MeterReader's jpeg_
 them through the host branch instead.  Sequential files sent as three one-component scans are decoded on the GPU as well
 (MeterReader's jpeg_multiscan switch; they keep the segment-parallel decoder and cost no latency, unlike progressive files);
 METERELF_JPEG_MULTISCAN=host sends them through the host branch instead.
+A baseline file whose bytes stop inside the scan (a snapshot still being written, an upload that lost its connection) is completed on the
+GPU as libjpeg completes it, byte for byte the frame the host branch decodes (MeterReader's jpeg_truncated switch);
+METERELF_JPEG_TRUNCATED=host sends such files through the host branch instead, as before the GPU took them.
 """
 import collections
 import hashlib
@@ -102,6 +105,12 @@ def _jpeg_multiscan_on_gpu() -> bool:
     return os.getenv('METERELF_JPEG_MULTISCAN', 'gpu') != 'host'
 
 
+def _jpeg_truncated_on_gpu() -> bool:
+    """Baseline JPEG files that end inside their scan are completed on the GPU; METERELF_JPEG_TRUNCATED=host leaves them to the host
+    branch."""
+    return os.getenv('METERELF_JPEG_TRUNCATED', 'gpu') != 'host'
+
+
 def _jpeg_default_tables_on_gpu() -> bool:
     """JPEG files that leave Huffman tables out (Motion-JPEG frames) are decoded on the GPU with the Annex K tables;
     METERELF_JPEG_TABLES=host leaves them to the host branch."""
@@ -110,14 +119,15 @@ def _jpeg_default_tables_on_gpu() -> bool:
 
 def _reader_key(params, blob, device: int) -> bytes:
     env = ';'.join('%s=%s' % (k, os.environ[k]) for k in _ENV_IN_KEY if k in os.environ)
-    orient = b'|orient%d|prog%d|samp%d|scans%d|tabs%d|' % (_jpeg_orientation_on_gpu(), _jpeg_progressive_on_gpu(), _jpeg_samplings_on_gpu(),
-                                                          _jpeg_multiscan_on_gpu(), _jpeg_default_tables_on_gpu())   # a reader keeps the settings it was made with
+    orient = b'|orient%d|prog%d|samp%d|scans%d|tabs%d|cut%d|' % (_jpeg_orientation_on_gpu(), _jpeg_progressive_on_gpu(), _jpeg_samplings_on_gpu(),
+                                                                _jpeg_multiscan_on_gpu(), _jpeg_default_tables_on_gpu(),
+                                                                _jpeg_truncated_on_gpu())   # a reader keeps the settings it was made with
     return hashlib.sha1(blob.tobytes() + repr(list(params.dial_names)).encode() + b'|dev%d|' % device + orient + env.encode()).digest()
 
 
 def _with_jpeg_orientation(reader):
     """Turns a new reader's switches on (MeterReader.set_jpeg_orientation, set_jpeg_progressive, set_jpeg_samplings, set_jpeg_multiscan,
-    set_jpeg_default_tables) unless the host branch is asked for;
+    set_jpeg_default_tables, set_jpeg_truncated) unless the host branch is asked for;
     a reader from the cache has them already (the settings are part of its key)."""
     if _jpeg_orientation_on_gpu() and hasattr(reader, 'set_jpeg_orientation') and not getattr(reader, 'jpeg_orientation', False):
         reader.set_jpeg_orientation(True)
@@ -129,6 +139,8 @@ def _with_jpeg_orientation(reader):
         reader.set_jpeg_multiscan(True)
     if _jpeg_default_tables_on_gpu() and hasattr(reader, 'set_jpeg_default_tables') and not getattr(reader, 'jpeg_default_tables', False):
         reader.set_jpeg_default_tables(True)
+    if _jpeg_truncated_on_gpu() and hasattr(reader, 'set_jpeg_truncated') and not getattr(reader, 'jpeg_truncated', False):
+        reader.set_jpeg_truncated(True)
     return reader
 
 

@@ -126,8 +126,11 @@ def records_to_items(records: np.ndarray, ok, dial_names: List[str], filenames: 
 class MeterReader:
     def __init__(self, params: Params, device: int = 0, blob: Optional[np.ndarray] = None, ctx: Optional['_hip.Context'] = None,
                  jpeg_orientation: bool = False, jpeg_progressive: bool = False, jpeg_samplings: bool = False,
-                 jpeg_multiscan: bool = False, jpeg_default_tables: bool = False) -> None:
-        """jpeg_default_tables: the read_jpeg_* methods decode sequential JPEG files that leave Huffman tables 0 / 1 out (Motion-JPEG frames of
+                 jpeg_multiscan: bool = False, jpeg_default_tables: bool = False, jpeg_truncated: bool = False) -> None:
+        """jpeg_truncated: the read_jpeg_* methods complete a baseline JPEG file whose bytes stop inside the scan (a snapshot still being
+        written, an upload that lost its connection) as libjpeg does -- the MCU in progress from zero bits, mid grey behind it -- instead
+        of handing it back as undecodable, which is the default.
+        jpeg_default_tables: the read_jpeg_* methods decode sequential JPEG files that leave Huffman tables 0 / 1 out (Motion-JPEG frames of
         UVC webcams and AVI MJPG streams: no DHT segment) with the T.81 Annex K tables, as libjpeg-turbo does, instead of leaving them to
         the caller's host decoder, which is the default.
         jpeg_multiscan: the read_jpeg_* methods decode sequential JPEG files sent as three scans of one component each on the GPU, byte
@@ -161,6 +164,14 @@ class MeterReader:
         self.jpeg_default_tables = False
         if jpeg_default_tables:
             self.set_jpeg_default_tables(True)
+        self.jpeg_truncated = False
+        if jpeg_truncated:
+            self.set_jpeg_truncated(True)
+
+    def set_jpeg_truncated(self, on: bool) -> None:
+        """The switch of the constructor's jpeg_truncated, on a reader with nothing in flight (melf_ctx_set_jpeg_truncated)."""
+        self.ctx.set_jpeg_truncated(on)
+        self.jpeg_truncated = bool(on)
 
     def set_jpeg_multiscan(self, on: bool) -> None:
         """The switch of the constructor's jpeg_multiscan, on a reader with nothing in flight (melf_ctx_set_jpeg_multiscan)."""

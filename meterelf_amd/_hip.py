@@ -234,6 +234,7 @@ EXPORTS = [
     'melf_jpeg_probe_flags', 'melf_jpeg_probe_flags_batch', 'melf_ctx_set_jpeg_progressive', 'melf_ctx_get_jpeg_progressive',
     'melf_ctx_set_jpeg_samplings', 'melf_ctx_get_jpeg_samplings',
     'melf_ctx_set_jpeg_multiscan', 'melf_ctx_get_jpeg_multiscan', 'melf_ctx_set_jpeg_default_tables', 'melf_ctx_get_jpeg_default_tables',
+    'melf_ctx_set_jpeg_truncated', 'melf_ctx_get_jpeg_truncated', 'melf_ctx_jpeg_truncated_files',
 ]
 
 _lib = None
@@ -336,6 +337,10 @@ def lib():
     L.melf_ctx_get_jpeg_multiscan.argtypes = [vp, C.POINTER(C.c_int)]
     L.melf_ctx_set_jpeg_default_tables.argtypes = [vp, C.c_int]
     L.melf_ctx_get_jpeg_default_tables.argtypes = [vp, C.POINTER(C.c_int)]
+    if hasattr(L, 'melf_ctx_set_jpeg_truncated'):   # (tools/jpeg_cut_rate.py loads the library from before the switch through MELF_LIB_PATH)
+        L.melf_ctx_set_jpeg_truncated.argtypes = [vp, C.c_int]
+        L.melf_ctx_get_jpeg_truncated.argtypes = [vp, C.POINTER(C.c_int)]
+        L.melf_ctx_jpeg_truncated_files.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
     L.melf_jpeg_decode_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]
     L.melf_jpeg_process_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.melf_jpeg_process_files.argtypes = [vp, vp, C.c_int, i32p, i32p, vp, vp]
@@ -1739,6 +1744,23 @@ class Context:
         on = C.c_int(0)
         check(self._L.melf_ctx_get_jpeg_default_tables(self._h, C.byref(on)))
         return bool(on.value)
+
+    def set_jpeg_truncated(self, on):
+        """Baseline JPEG files whose bytes stop inside the scan are completed by the jpeg_* calls of this context as libjpeg completes
+        them -- the cut MCU from zero bits, mid grey behind it -- instead of coming back corrupt (melf_ctx_set_jpeg_truncated).  Off by
+        default."""
+        check(self._L.melf_ctx_set_jpeg_truncated(self._h, int(bool(on))))
+
+    def jpeg_truncated(self):
+        on = C.c_int(0)
+        check(self._L.melf_ctx_get_jpeg_truncated(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def jpeg_truncated_files(self, reset=False):
+        """Files this context's calls completed under that rule since the last reset (melf_ctx_jpeg_truncated_files)."""
+        n = C.c_int64(0)
+        check(self._L.melf_ctx_jpeg_truncated_files(self._h, C.byref(n), int(bool(reset))))
+        return int(n.value)
 
     def set_frames_resident(self, on):
         """Promise that the frames of every process_batch_dev call are complete in HBM when the call is made: a call's prep

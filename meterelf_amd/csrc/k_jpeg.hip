@@ -29,6 +29,7 @@
 //          k_jpeg_color_exif  files with an EXIF orientation 2-8 (when the caller asked for them): the same conversion in
 //                           stored geometry, each pixel written where the upright frame has it
 #include "melf_internal.h"
+#include "melf_jpeg_cut.h"
 #include "melf_jpeg_orient_addr.h"
 #include "melf_jpeg_prog.h"
 #include "melf_jpeg_scans.h"
@@ -88,6 +89,7 @@ struct JpegHeader {
     std::vector<MScan> ms;      // three, once multiscan
 };
 constexpr int TAKE_ORIENTED = 1, TAKE_PROGRESSIVE = 2, TAKE_SAMPLINGS = 4, TAKE_DEFAULT_TABLES = 16, TAKE_MULTISCAN = 32;   // MELF_JPEG_TAKE_*: what a caller's switches make the parser accept
+constexpr int TAKE_TRUNCATED = JPEG_TAKE_TRUNCATED_INTERNAL;   // not a probe flag (the headers do not show a cut): melf_ctx_set_jpeg_truncated, for the Huffman stage alone
 
 static inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
 
@@ -568,7 +570,7 @@ struct JpegImageDev {
     uint8_t orient;               // EXIF orientation the colour stage applies (1..8); the other stages work in stored geometry
     uint8_t planar;               // a multi-scan sequential file (ok = 4): every component's blocks in an area of its own, coef_blk[c], the
                                   // REAL blocks in raster order, written by the one-component records of its scans (melf_jpeg_scans.h)
-    uint8_t pad[1];
+    uint8_t end_marker;           // written by k_jpeg_clean: the byte behind the FF that ended the scan (D9 = EOI), 0 when the bytes ended first
     uint32_t rst_off, rst_cnt;    // restart intervals: table of their byte offsets in the clean scan (relative to the
                                   // scan area), number of intervals.  A planar file's record has no scan of its own and keeps its
                                   // real block grids here: rst_off = luma, rst_cnt = chroma, columns | rows << 16
@@ -642,6 +644,7 @@ __global__ __launch_bounds__(CLEAN_T) void k_jpeg_clean(JpegImageDev* __restrict
     const int rst_cap = has_rst ? (int)R->rst_cnt + 1 : 0;   // the host left the EXPECTED number of intervals here
     int o_base = 0, r_base = 0;   // clean bytes written, restart markers seen, before this round
     bool ended = false;
+    int endpos = -1;   // where the FF that ended the scan stands (uniform), -1: none, the bytes ended first
     for (int base = 0; base < n && !ended; base += CLEAN_T * 16) {
         if (tid == 0) s_end = INT_MAX;
         const int my = base + tid * 16;
@@ -679,7 +682,9 @@ __global__ __launch_bounds__(CLEAN_T) void k_jpeg_clean(JpegImageDev* __restrict
         __syncthreads();
         if (endmask) atomicMin(&s_end, my + (int)__builtin_ctz(endmask));
         __syncthreads();
-        const int end = min(s_end, n);
+        const int se = s_end;
+        const int end = min(se, n);
+        if (se != INT_MAX) endpos = se;
         const int live = end - my;
         const uint32_t Lm = live >= 16 ? 0xFFFFu : (live > 0 ? (1u << live) - 1u : 0u);
         // kept: a stuffed FF (FF 00), and every other byte that is not the second byte of a stuffed pair or of a marker
@@ -757,6 +762,7 @@ __global__ __launch_bounds__(CLEAN_T) void k_jpeg_clean(JpegImageDev* __restrict
     for (int i = o_base + tid; i < cap; i += CLEAN_T) out[i] = 0;
     if (tid == 0) {
         R->scan_len = (uint32_t)o_base;
+        R->end_marker = endpos >= 0 && endpos + 1 < n ? s[endpos + 1] : (uint8_t)0;   // (never 00: FF 00 is a stuffed FF)
         if (has_rst) {
             rst[0] = 0;
             R->rst_cnt = (uint32_t)(r_base + 1);
@@ -1245,13 +1251,29 @@ __device__ __forceinline__ McuWindow jpeg_zero_window(const JpegImageDev* R, con
 #define JSTAMP(k) do { } while (0)
 #endif
 
+// Files that end early (melf_ctx_set_jpeg_truncated, melf_jpeg_cut.h).  The Huffman kernels of a context that takes such files get a
+// table of two JpegCutRec per file (NULL otherwise: everything as ever).  A file whose stream holds no impossible code but runs
+// out before the frame's last block is then not reported corrupt: its status becomes JPEG_ST_CUT, and k_jpeg_cut_tail, one wave per
+// file behind the Huffman kernels, finishes the cut MCU from an exact decoder state, zeroes what lies behind it and settles the status
+// (JPEG_ST_CUT stays for a file completed under the rule -- J2 and J3 treat it as 0, the host maps it to 0 and counts it -- and 2
+// for one that is corrupt after all).  k_jpeg_huff leaves that state: the entry states of its last two segments (block index and
+// DC predictors included), of which the tail takes the later one that does not lie behind the stream's last real bit.
+// k_jpeg_huff_rst needs no record: the last interval found starts in a known state.
+struct JpegCutRec {
+    uint32_t p;           // bit position
+    int32_t nb;           // block in decode order
+    int32_t blk_k;        // block within the MCU << 8 | coefficient index
+    int32_t pred[3];      // DC predictors there
+};
+__device__ __forceinline__ bool jpeg_status_ok(const int32_t st) { return st == 0 || st == JPEG_ST_CUT; }
+
 // At most 80 SGPRs per wave, VCC and the other implicit ones included: one more 16-register granule and a SIMD holds
 // 7 waves instead of 8, i.e. three workgroups of 512 per CU instead of four and a 1024-image batch in two passes
 // (measured in round 2: 73 -> 75 numbered SGPRs took the kernel from 1.07 to 1.47 ms with the same cycles per workgroup).
 template <int T>
 __global__ __launch_bounds__(T) __attribute__((amdgpu_num_sgpr(80))) void k_jpeg_huff(const JpegImageDev* __restrict__ imgs, const HuffSlow* __restrict__ g_slow,
                                                  const uint8_t* __restrict__ scan, int16_t* __restrict__ coefs,
-                                                 int32_t* __restrict__ status, JpegWindow win)
+                                                 int32_t* __restrict__ status, JpegWindow win, JpegCutRec* __restrict__ cutrec)
 {
     __shared__ uint32_t tab[4 << TAB_BITS];
     __shared__ uint32_t longtab[2 * LONG_N];
@@ -1430,6 +1452,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_num_sgpr(80))) void k_jpeg
     __syncthreads();
     }
     const bool limited = cut < nseg - 1;
+    if (tid == 0) wcount[0] = nseg;   // (free since the rounds ended; read at the kernel's end, barriers in between)
     const SegState entry = {n_p[tid], (int)(n_s[tid] >> 8), (int)(n_s[tid] & 255u)};
     const uint32_t p_end = min((uint32_t)(tid + 1) * S, bits + 32u);
     JSTAMP(4);
@@ -1444,6 +1467,10 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_num_sgpr(80))) void k_jpeg
         SegState st = entry;
         int n2;
         jpeg_decode_segment(W, tab, longtab, slow, nat, L, st, p_end, n2, nb_in, total_blocks, q0, q1, q2, ndc, mcus_x, cp, bad);
+        // where the frame's last block ended, if this segment completed it (e_p is free since the rounds ended): behind the
+        // stream's end when it was completed on the zero bits of the scan area's padding alone -- a file that ends early all
+        // the same, which a caller that takes such files is told about (at the kernel's end)
+        e_p[tid] = nb_in + n2 >= total_blocks ? st.p : 0u;
     }
     const int64_t dsum = (int64_t)q0 + ((int64_t)q1 << 16) + ((int64_t)q2 << 32);
     sc_d[tid] = dsum;
@@ -1500,7 +1527,24 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_num_sgpr(80))) void k_jpeg
 #endif
     // the whole scan settled: it must hold every block of the frame; a window-limited decode: the settled prefix reached the
     // window's end (checked above) and the segments it decoded were consistent
-    if (tid == 0) status[img] = (anybad || (!limited && done_blocks < total_blocks)) ? 2 : 0;
+    int32_t st = (anybad || (!limited && done_blocks < total_blocks)) ? 2 : 0;
+    // (uniform conditions: the barrier inside is reached by all threads or by none)
+    if (cutrec != nullptr && !anybad && !limited && (st != 0 || __syncthreads_or(ran && e_p[tid] > R->scan_len * 8u))) {
+        // no impossible code, but the stream runs out before the frame's last block (or holds it only thanks to the zero padding):
+        // a cut file for k_jpeg_cut_tail.  The entry
+        // states of the last two segments (exact: the rounds settled them), with the block and the predictors there -- all of it
+        // still in LDS (the prefix sums are inclusive: segment j's first block and predictors are its predecessor's sums), so
+        // that nothing of this lives in a register while the decoders run
+        const int j = wcount[0] - 2 + tid;
+        if (tid < 2 && j >= 0) {
+            JpegCutRec r;
+            r.p = n_p[j]; r.blk_k = (int32_t)n_s[j]; r.nb = j > 0 ? sc_n[j - 1] : 0;
+            unpack_dsum(j > 0 ? sc_d[j - 1] : (int64_t)0, r.pred[0], r.pred[1], r.pred[2]);
+            cutrec[2 * img + tid] = r;
+        }
+        st = JPEG_ST_CUT;
+    }
+    if (tid == 0) status[img] = st;
 }
 
 // Streams with restart intervals need no speculation: every interval starts byte aligned with the DC
@@ -1509,7 +1553,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_num_sgpr(80))) void k_jpeg
 template <int T>
 __global__ __launch_bounds__(T) void k_jpeg_huff_rst(const JpegImageDev* __restrict__ imgs, const HuffSlow* __restrict__ g_slow,
                                                      const uint8_t* __restrict__ scan, int16_t* __restrict__ coefs,
-                                                     int32_t* __restrict__ status, JpegWindow win)
+                                                     int32_t* __restrict__ status, JpegWindow win, const int take_cut)
 {
     __shared__ uint32_t tab[4 << TAB_BITS];
     __shared__ uint32_t longtab[2 * LONG_N];
@@ -1535,19 +1579,123 @@ __global__ __launch_bounds__(T) void k_jpeg_huff_rst(const JpegImageDev* __restr
     const int per_interval = (int)R->restart_interval * L.bpm;
     const int nint = (int)R->rst_cnt;
     const int expected = (total_blocks + per_interval - 1) / per_interval;
-    const uint32_t bits = R->scan_len * 8u;
+    const uint32_t p_stop = R->scan_len * 8u + 32u;   // where a walk stops at the latest: 32 bits into the zero padding
     const CoefBlocks cp = {coefs + (size_t)R->coef_blk[0] * 64, mwin};
     __syncthreads();
-    int bad = nint != expected ? 1 : 0;  // markers missing or surplus: corrupt stream
+    // markers missing or surplus: corrupt stream -- unless the caller takes files that end early (take_cut): then intervals may be
+    // missing at the end, and the last one found may be short; both are bit 1 of `bad`, for k_jpeg_cut_tail to settle
+    int bad = nint == expected ? 0 : (take_cut && nint < expected ? 2 : 1);
     for (int it = tid; it < min(nint, expected); it += T) {
         SegState st = {rst[it] * 8u, 0, 0};
         const int nb0 = it * per_interval, nb1 = min(nb0 + per_interval, total_blocks);
         int n2, ndc, q0 = 0, q1 = 0, q2 = 0;  // every interval starts with zero predictors
-        jpeg_decode_segment(W, tab, longtab, slow, nat, L, st, bits + 32u, n2, nb0, nb1, q0, q1, q2, ndc, mcus_x, cp, bad);
-        if (n2 < nb1 - nb0) bad = 1;  // ran out of data before the interval's last block
+        jpeg_decode_segment(W, tab, longtab, slow, nat, L, st, p_stop, n2, nb0, nb1, q0, q1, q2, ndc, mcus_x, cp, bad);
+        if (n2 < nb1 - nb0) bad |= take_cut && it == nint - 1 ? 2 : 1;  // ran out of data before the interval's last block
+        else if (take_cut && it == nint - 1 && st.p + 32u > p_stop) bad |= 2;   // complete, but only on zero bits behind the stream's end
     }
-    const int anybad = __syncthreads_or(bad);
-    if (tid == 0) status[img] = anybad ? 2 : 0;
+    // (the barrier tells whether ANY lane's value is non-zero, not which bits: a second one, for the files that need it, tells corrupt from cut)
+    const int any = __syncthreads_or(bad);
+    const int anybad = any ? __syncthreads_or(bad & 1) : 0;
+    if (tid == 0) status[img] = anybad ? 2 : any ? JPEG_ST_CUT : 0;
+}
+
+// ------------------------------------------------- J1, files that end early: the cut MCU ----
+// One wave per file behind the Huffman kernels of a run; a file that is not cut (status other than JPEG_ST_CUT) leaves at once.
+// The first lane walks on from an exact state (melf_jpeg_cut.h: finish) over the MASKED stream -- the real bits, then zeros that are
+// produced, not read -- and stores the coefficients of the blocks inside the window exactly as the output pass would have (the blocks
+// the Huffman kernel already wrote there hold the same values: it decoded the same bits followed by the scan area's zero padding).
+// Then the wave zeroes the 64 blocks behind the cut MCU: the Huffman kernels stop at bits + 32, not at bits, so a segment's walk
+// may have completed blocks of LATER MCUs on zero bits -- fewer than 32 of them, since a symbol ends below bits + 63 and a block
+// takes two bits at the least.  Blocks further on were zeroed by jpeg_zero_window and never written.
+// Bounds: a block index nb < total_blocks is stored only when its MCU lies inside the window, as coef_block_ptr has it.
+// Refused here (status 2): a scan ended by a marker other than EOI, an impossible code met on the way, a state that does not reach
+// the stream's end.
+static_assert(sizeof(jpeg_cut::Huff) == sizeof(HuffSlow) && offsetof(jpeg_cut::Huff, valoff) == offsetof(HuffSlow, valoff) &&
+              offsetof(jpeg_cut::Huff, huffval) == offsetof(HuffSlow, huffval), "melf_jpeg_cut.h restates HuffSlow");
+__global__ __launch_bounds__(64) void k_jpeg_cut_tail(const JpegImageDev* __restrict__ imgs, const HuffSlow* __restrict__ g_slow,
+                                                      const uint8_t* __restrict__ scan, int16_t* __restrict__ coefs,
+                                                      int32_t* __restrict__ status, const JpegCutRec* __restrict__ cutrec, JpegWindow win)
+{
+    __shared__ uint32_t sl[4 * SLOW_DW];
+    __shared__ uint8_t nat[64];
+    __shared__ int s_res[2];
+    const int img = blockIdx.x, lane = threadIdx.x;
+    if (status[img] != JPEG_ST_CUT) return;
+    const JpegImageDev* R = imgs + img;
+    {
+        const uint32_t* ssrc = (const uint32_t*)(g_slow + (size_t)img * 4);
+        for (int i = lane; i < 4 * SLOW_DW; i += 64) sl[i] = ssrc[i];
+        nat[lane] = c_zz2nat[lane];
+    }
+    __syncthreads();
+    const int hs0 = R->hs0, vs0 = R->vs0, ncomp = R->ncomp, mcus_x = R->mcus_x;
+    const int mwid = 8 * hs0, mhei = 8 * vs0;
+    const int bpm = ncomp == 1 ? 1 : hs0 * vs0 + 2;
+    const int total_blocks = mcus_x * (int)R->mcus_y * bpm;
+    // the window in MCUs, as jpeg_zero_window gave it to the Huffman kernels
+    const int mx0 = win.x0 / mwid, mx1 = min((win.x1 + mwid - 1) / mwid, mcus_x);
+    const int my0 = win.y0 / mhei, my1 = min((win.y1 + mhei - 1) / mhei, (int)R->mcus_y);
+    int16_t* const base = coefs + (size_t)R->coef_blk[0] * 64;
+    auto inside = [&](const int32_t nb) {
+        const int mcu = nb / bpm, my = mcu / mcus_x, mx = mcu - my * mcus_x;
+        return nb < total_blocks && mx >= mx0 && mx < mx1 && my >= my0 && my < my1;
+    };
+    if (lane == 0) {
+        int res = jpeg_cut::INVALID_CODE;
+        jpeg_cut::State st = {0u, 0, 0, 0, 0, 0, 0};
+        const uint32_t m = R->end_marker;
+        if (m == 0u || m == 0xD9u) {   // the bytes ended, or EOI: what libjpeg's data source ends a short scan with
+            jpeg_cut::Layout L = {bpm, 0u, 0u, 0u};
+            for (int b = 0; b < bpm; ++b) {
+                const int c = b < bpm - 2 || ncomp == 1 ? 0 : 1 + b - (bpm - 2);
+                L.comp_bits |= (uint32_t)c << (2 * b);
+                L.dc_bits |= (uint32_t)(R->td[c] & 1) << b;
+                L.ac_bits |= (uint32_t)(R->ta[c] & 1) << b;
+            }
+            const uint8_t* s = scan + R->scan_off;
+            const uint32_t bits = R->scan_len * 8u;
+            const jpeg_cut::Huff* tabs = (const jpeg_cut::Huff*)sl;
+            auto sink = [&](const int32_t nb, const int idx, const int v) {
+                if (inside(nb)) base[(size_t)nb * 64 + idx] = (int16_t)v;
+            };
+            if (R->ok == 1) {
+                // the later of the two states k_jpeg_huff left that is not behind the stream's end (a slot it did not write
+                // holds zeros: the state at the stream's first bit)
+                JpegCutRec r = cutrec[2 * img + 1];
+                if (r.p > bits) r = cutrec[2 * img];
+                if (r.p <= bits) {
+                    st = {r.p, r.blk_k >> 8, r.blk_k & 255, r.nb, r.pred[0], r.pred[1], r.pred[2]};
+                    res = jpeg_cut::finish(s, bits, tabs, nat, L, st, total_blocks, sink);
+                }
+            } else {
+                // restart intervals: the last one found from its first bit; if it turns out complete and intervals are still
+                // owing, the first MCU of the next one, from zero bits
+                const uint32_t* rst = (const uint32_t*)(scan + R->rst_off);
+                const int per_interval = (int)R->restart_interval * bpm;
+                const int nint = (int)R->rst_cnt, expected = (total_blocks + per_interval - 1) / per_interval;
+                if (nint >= 1 && nint <= expected && rst[nint - 1] * 8u <= bits) {
+                    st = {rst[nint - 1] * 8u, 0, 0, (nint - 1) * per_interval, 0, 0, 0};
+                    res = jpeg_cut::finish(s, bits, tabs, nat, L, st, min(st.nb + per_interval, total_blocks), sink);
+                    if (res == jpeg_cut::NOT_CUT && nint < expected) {
+                        st = {bits, 0, 0, nint * per_interval, 0, 0, 0};
+                        res = jpeg_cut::finish(s, bits, tabs, nat, L, st, min(st.nb + per_interval, total_blocks), sink);
+                    }
+                }
+            }
+        }
+        s_res[0] = res;
+        s_res[1] = st.nb;
+    }
+    __syncthreads();
+    if (s_res[0] != jpeg_cut::CUT) {
+        if (lane == 0) status[img] = 2;
+        return;
+    }
+    const int32_t after = s_res[1];
+    for (int i = lane; i < 64 * 8; i += 64) {
+        const int32_t nb = after + (i >> 3);
+        if (inside(nb)) ((uint4*)(base + (size_t)nb * 64))[i & 7] = make_uint4(0u, 0u, 0u, 0u);
+    }
 }
 
 // ------------------------------------------------- J1, progressive files: one scan ----
@@ -1646,7 +1794,7 @@ __global__ __launch_bounds__(256) void k_jpeg_idct(const JpegImageDev* __restric
 {
     const int img = blockIdx.y;
     const JpegImageDev& I = imgs[img];   // a reference: a local copy indexed by the component lives in scratch
-    if (!I.ok || status[img] != 0) return;
+    if (!I.ok || !jpeg_status_ok(status[img])) return;
     // blocks of the MCUs that overlap the pixel window: floor / ceiling in the file's own MCU, the very MCUs jpeg_zero_window gave
     // the Huffman stage (the window's origin is 16-aligned: an MCU corner for MCUs up to 16 x 16, and for the 32 x 8 MCU of 4:1:1
     // possibly the middle of one, which the floor takes whole).  Stores: bx < blocks_x[c], by < blocks_y[c] since mx1 <= mcus_x,
@@ -1788,7 +1936,7 @@ __global__ __launch_bounds__(256) void k_jpeg_color420(const JpegImageDev* __res
     const JpegImageDev* R = &rec;
     if (!(rec.ok && rec.ncomp == 3 && rec.hs0 == 2 && rec.vs0 == 2)) return;  // the generic kernel's image
     uint8_t* const orow = frames + ((size_t)img * H + y) * W * 3 + (size_t)g * 24;
-    if (st != 0) {  // failed in the entropy decoder: zero frame
+    if (!jpeg_status_ok(st)) {  // failed in the entropy decoder: zero frame
         uint2* z = (uint2*)orow;
         z[0] = z[1] = z[2] = make_uint2(0u, 0u);
         if (two) {
@@ -1905,7 +2053,7 @@ __global__ __launch_bounds__(256) void k_jpeg_color(const JpegImageDev* __restri
     if (fast420 && I.ok && I.ncomp == 3 && I.hs0 == 2 && I.vs0 == 2) return;  // k_jpeg_color420 did it
     uint8_t* out = frames + ((size_t)img * H + y) * W * 3 + (size_t)x0 * 3;
     const int npx = min(4, W - x0);
-    if (!I.ok || status[img] != 0) {
+    if (!I.ok || !jpeg_status_ok(status[img])) {
         for (int k = 0; k < npx * 3; ++k) out[k] = 0;
         return;
     }
@@ -1949,7 +2097,7 @@ __global__ __launch_bounds__(256) void k_jpeg_color_exif(const JpegImageDev* __r
     const int tw = min(OT, win.x1 - sx0), th = min(OT, win.y1 - sy0);
     if (tw <= 0 || th <= 0) return;   // uniform: a launch with more tiles than the window has
     const JpegImageDev& I = imgs[img];
-    if (I.ok && status[img] == 0) {
+    if (I.ok && jpeg_status_ok(status[img])) {
         const PlaneSrc src = plane_src(I, planes, Hs, Ws);
         for (int i = threadIdx.x; i < th * OT; i += 256) {
             const int ly = i / OT, lx = i % OT;
@@ -2007,6 +2155,9 @@ struct JpegWorkspace {
     size_t plane_cap = 0;
     int32_t* d_status = nullptr;
     size_t status_cap = 0;
+    bool cut = false;            // the batch's context takes files that end early (TAKE_TRUNCATED): the Huffman kernels leave states
+    uint8_t* d_cut = nullptr;    // in two JpegCutRec per file here, and k_jpeg_cut_tail runs behind them
+    size_t cut_cap = 0;
     // layout of the current batch inside the stage buffers
     size_t off_imgs = 0, off_qt = 0, off_slow = 0, off_scan = 0, total = 0;   // total: what is uploaded (records + tables)
     size_t off_pfile = 0, off_pscan = 0, off_ptab = 0, off_prst = 0;          // progressive files: their records, scans, tables, intervals
@@ -2055,6 +2206,7 @@ void jpeg_workspace_free(JpegWorkspace* w)
     if (w->d_coefs) (void)hipFree(w->d_coefs);
     if (w->d_planes) (void)hipFree(w->d_planes);
     if (w->d_status) (void)hipFree(w->d_status);
+    if (w->d_cut) (void)hipFree(w->d_cut);
     delete w;
 }
 
@@ -2127,6 +2279,7 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
 {
     if (!*pws) *pws = new JpegWorkspace();
     JpegWorkspace* w = *pws;
+    w->cut = (take & TAKE_TRUNCATED) != 0;
     static const bool trace = diag_env("MELF_JPEG_TRACE") != nullptr;
     const auto tp0 = std::chrono::steady_clock::now();
     std::vector<JpegHeader> own;
@@ -2461,6 +2614,7 @@ int jpeg_upload_batch(JpegWorkspace* w, int n, hipStream_t copy_stream, std::str
     JTRY(grow_dev(&w->d_coefs, &w->coef_cap, w->coef_elems + 64));
     JTRY(grow_dev(&w->d_planes, &w->plane_cap, w->plane_bytes + 64));
     JTRY(grow_dev(&w->d_status, &w->status_cap, (size_t)n + w->n_scan_recs));
+    if (w->cut) JTRY(grow_dev(&w->d_cut, &w->cut_cap, (size_t)n * 2 * sizeof(JpegCutRec)));
     JTRY(hipMemcpyAsync(w->d_stage, w->h_stage, w->total, hipMemcpyHostToDevice, copy_stream));
     JTRY(hipMemcpyAsync(w->d_raw, w->raw_src, w->raw_total, hipMemcpyHostToDevice, copy_stream));
     return MELF_SUCCESS;
@@ -2484,6 +2638,9 @@ int jpeg_decode_batch_kernels(JpegWorkspace* w, int n, int H, int W, uint8_t* d_
     const HuffSlow* const slow0 = (const HuffSlow*)(w->d_stage + w->off_slow);
     const uint8_t* scan = w->d_stage + w->off_scan;
     const size_t nruns = w->runs.size();
+    // files that end early: a state k_jpeg_huff does not write reads as zeros, the state at the stream's first bit
+    JpegCutRec* const cut0 = w->cut && w->n_par + w->n_seq > 0 ? (JpegCutRec*)w->d_cut : nullptr;
+    if (cut0 && w->n_par > 0) JTRY(hipMemsetAsync(cut0, 0, (size_t)n * 2 * sizeof(JpegCutRec), stream));
     if (timer) timer(timer_arg, 0, 0);
     if (w->n_par + w->n_seq + w->n_scan_recs > 0)   // J0: stuffing, fill bytes and restart markers out of the uploaded segments
         hipLaunchKernelGGL(k_jpeg_clean, dim3(n + w->n_scan_recs), dim3(CLEAN_T), 0, stream, (JpegImageDev*)(w->d_stage + w->off_imgs), w->d_raw, w->d_stage + w->off_scan);
@@ -2493,16 +2650,19 @@ int jpeg_decode_batch_kernels(JpegWorkspace* w, int n, int H, int W, uint8_t* d_
         const JpegImageDev* imgs = imgs0 + r.first;
         const HuffSlow* slow = slow0 + (size_t)r.first * 4;
         int32_t* status = w->d_status + r.first;
+        JpegCutRec* const cutrec = cut0 ? cut0 + 2 * (size_t)r.first : nullptr;
         if (r.n_par > 0) {  // one workgroup per image, one lane per stream segment
             // 512 lanes per image; a batch with a scan too long for 512 segments of the length the kernel can address takes 1024
             if (r.max_par_scan > JPEG_MAX_PAR_SCAN / 2)
-                hipLaunchKernelGGL(k_jpeg_huff<1024>, dim3(r.n), dim3(1024), 0, stream, imgs, slow, scan, w->d_coefs, status, win);
+                hipLaunchKernelGGL(k_jpeg_huff<1024>, dim3(r.n), dim3(1024), 0, stream, imgs, slow, scan, w->d_coefs, status, win, cutrec);
             else
-                hipLaunchKernelGGL(k_jpeg_huff<512>, dim3(r.n), dim3(512), 0, stream, imgs, slow, scan, w->d_coefs, status, win);
+                hipLaunchKernelGGL(k_jpeg_huff<512>, dim3(r.n), dim3(512), 0, stream, imgs, slow, scan, w->d_coefs, status, win, cutrec);
         }
         if (r.n_seq > 0) {  // streams with restart intervals: one lane per interval
-            hipLaunchKernelGGL(k_jpeg_huff_rst<256>, dim3(r.n), dim3(256), 0, stream, imgs, slow, scan, w->d_coefs, status, win);
+            hipLaunchKernelGGL(k_jpeg_huff_rst<256>, dim3(r.n), dim3(256), 0, stream, imgs, slow, scan, w->d_coefs, status, win, cutrec ? 1 : 0);
         }
+        if (cutrec && r.n_par + r.n_seq > 0)   // one wave per file; a file that is not cut leaves at once
+            hipLaunchKernelGGL(k_jpeg_cut_tail, dim3(r.n), dim3(64), 0, stream, imgs, slow, scan, w->d_coefs, status, cutrec, win);
         if (r.prog && !r.prog_items.empty()) {
             // Progressive files: the WHOLE coefficient area zeroed (a refinement scan reads one bit for every coefficient that is
             // non-zero, in every block of the image: where the stream goes depends on blocks outside the window too), then level
@@ -2527,12 +2687,12 @@ int jpeg_decode_batch_kernels(JpegWorkspace* w, int n, int H, int W, uint8_t* d_
         int32_t* status = w->d_status + n + g.first;
         if (g.n_par > 0) {
             if (g.max_par_scan > JPEG_MAX_PAR_SCAN / 2)
-                hipLaunchKernelGGL(k_jpeg_huff<1024>, dim3(g.n), dim3(1024), 0, stream, imgs, slow, scan, w->d_coefs, status, win);
+                hipLaunchKernelGGL(k_jpeg_huff<1024>, dim3(g.n), dim3(1024), 0, stream, imgs, slow, scan, w->d_coefs, status, win, (JpegCutRec*)nullptr);
             else
-                hipLaunchKernelGGL(k_jpeg_huff<512>, dim3(g.n), dim3(512), 0, stream, imgs, slow, scan, w->d_coefs, status, win);
+                hipLaunchKernelGGL(k_jpeg_huff<512>, dim3(g.n), dim3(512), 0, stream, imgs, slow, scan, w->d_coefs, status, win, (JpegCutRec*)nullptr);
         }
-        if (g.n_seq > 0)
-            hipLaunchKernelGGL(k_jpeg_huff_rst<256>, dim3(g.n), dim3(256), 0, stream, imgs, slow, scan, w->d_coefs, status, win);
+        if (g.n_seq > 0)   // (a multi-scan file that ends inside a scan stays corrupt: no states, no tail)
+            hipLaunchKernelGGL(k_jpeg_huff_rst<256>, dim3(g.n), dim3(256), 0, stream, imgs, slow, scan, w->d_coefs, status, win, 0);
     }
     if (w->ms_files > 0)
         hipLaunchKernelGGL(k_jpeg_scan_status, dim3((w->ms_files + 63) / 64), dim3(64), 0, stream, (const uint32_t*)(w->d_stage + w->off_msmap),

@@ -12,6 +12,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -287,10 +288,20 @@ struct melf_ctx {
     bool jpeg_samp = false;            // melf_ctx_set_jpeg_samplings: 4:4:0 and 4:1:1 files are decoded, not refused
     bool jpeg_multi = false;           // melf_ctx_set_jpeg_multiscan: sequential files of three one-component scans are decoded, not refused
     bool jpeg_std_tabs = false;        // melf_ctx_set_jpeg_default_tables: a sequential file that leaves Huffman tables 0 / 1 out gets the Annex K ones
+    bool jpeg_cut = false;             // melf_ctx_set_jpeg_truncated: a baseline file that ends inside its scan is completed as libjpeg completes it, not refused
+    std::atomic<int64_t> jpeg_cut_files{0};   // files completed that way since the last reset (melf_ctx_jpeg_truncated_files)
+    // a file's status from the parser's and the Huffman stage's: JPEG_ST_CUT is a file completed under the rule -- 0, and counted
+    int32_t jpeg_file_status(const int32_t host, const int32_t dev)
+    {
+        if (host) return host;
+        if (dev == JPEG_ST_CUT) { jpeg_cut_files.fetch_add(1, std::memory_order_relaxed); return MELF_JPEG_OK; }
+        return dev ? MELF_JPEG_CORRUPT : MELF_JPEG_OK;
+    }
     int jpeg_take() const
     {
         return (jpeg_orient ? MELF_JPEG_TAKE_ORIENTED : 0) | (jpeg_prog ? MELF_JPEG_TAKE_PROGRESSIVE : 0) | (jpeg_samp ? MELF_JPEG_TAKE_SAMPLINGS : 0) |
-               (jpeg_multi ? MELF_JPEG_TAKE_MULTISCAN : 0) | (jpeg_std_tabs ? MELF_JPEG_TAKE_DEFAULT_TABLES : 0);
+               (jpeg_multi ? MELF_JPEG_TAKE_MULTISCAN : 0) | (jpeg_std_tabs ? MELF_JPEG_TAKE_DEFAULT_TABLES : 0) |
+               (jpeg_cut ? JPEG_TAKE_TRUNCATED_INTERNAL : 0);
     }
     bool jpeg_orient = false;          // melf_ctx_set_jpeg_orientation: files with an EXIF orientation 2..8 are decoded, not refused
     // pipelined JPEG path (melf_jpeg_process_batch): a second workspace and decode stream, so that the host prepares chunk
@@ -957,6 +968,29 @@ extern "C" int melf_ctx_get_jpeg_default_tables(melf_ctx* c, int* on)
 {
     if (!c || !on) return fail(MELF_ERR_INVALID, "bad argument");
     *on = c->jpeg_std_tabs ? 1 : 0;
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_ctx_set_jpeg_truncated(melf_ctx* c, int on)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    if (!c->files_jobs.empty()) return fail(MELF_ERR_INVALID, "melf_ctx_set_jpeg_truncated while a melf_jpeg_process_files_begin call is in flight");
+    c->jpeg_cut = on != 0;
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_ctx_get_jpeg_truncated(melf_ctx* c, int* on)
+{
+    if (!c || !on) return fail(MELF_ERR_INVALID, "bad argument");
+    *on = c->jpeg_cut ? 1 : 0;
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_ctx_jpeg_truncated_files(const melf_ctx* c, int64_t* files, int reset)
+{
+    if (!c || !files) return fail(MELF_ERR_INVALID, "bad argument");
+    std::atomic<int64_t>& n = const_cast<melf_ctx*>(c)->jpeg_cut_files;
+    *files = reset ? n.exchange(0) : n.load();
     return MELF_SUCCESS;
 }
 
@@ -2416,7 +2450,7 @@ int jpeg_decode_to_device(melf_ctx* c, const uint8_t* const* data, const size_t*
         fprintf(stderr, "[melf jpeg] n=%d host prepare %.2f ms, H2D + kernels + status %.2f ms\n", n,
                 std::chrono::duration<double, std::milli>(t1 - t0).count(), std::chrono::duration<double, std::milli>(t2 - t1).count());
     }
-    for (int i = 0; i < n; ++i) status[i] = hstat[i] ? hstat[i] : (dstat[i] ? MELF_JPEG_CORRUPT : MELF_JPEG_OK);
+    for (int i = 0; i < n; ++i) status[i] = c->jpeg_file_status(hstat[i], dstat[i]);
     return MELF_SUCCESS;
 }
 }  // namespace
@@ -2715,7 +2749,7 @@ static int jpeg_process_batch_from(melf_ctx* c, const uint8_t* const* data, cons
     }
     for (int i = 0; i < n; ++i) {
         const int o = perm.empty() ? i : perm[i];
-        status[o] = hstat[i] ? hstat[i] : (c->h_jstatus[cs][i] ? MELF_JPEG_CORRUPT : MELF_JPEG_OK);
+        status[o] = c->jpeg_file_status(hstat[i], c->h_jstatus[cs][i]);
         out_host[o] = recs[i];
     }
     return MELF_SUCCESS;

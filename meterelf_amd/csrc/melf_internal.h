@@ -257,6 +257,11 @@ int jpeg_upload_batch(JpegWorkspace* ws, int n, hipStream_t copy_stream, std::st
 int jpeg_decode_batch_kernels(JpegWorkspace* ws, int n, int H, int W, uint8_t* d_frames, hipStream_t stream, std::string* err,
                               void (*timer)(void*, int, int), void* timer_arg, const int* rect);
 const int32_t* jpeg_device_status(const JpegWorkspace* ws);
+// Files that end early (melf_ctx_set_jpeg_truncated).  The switch travels with the MELF_JPEG_TAKE_* flags of a batch as a bit of its own
+// that no probe takes (truncation does not show in the headers); the Huffman stage reports a file it completed under the rule of
+// melf_jpeg_cut.h with JPEG_ST_CUT in the device status array, which the later stages treat as 0 and the host maps to 0 and counts.
+constexpr int JPEG_TAKE_TRUNCATED_INTERNAL = 256;
+constexpr int32_t JPEG_ST_CUT = 3;
 void jpeg_workspace_free(JpegWorkspace* ws);
 
 }  // namespace melf

@@ -83,64 +83,43 @@ _ENV_IN_KEY = ('MELF_MATCH', 'MELF_MATCH_LAYOUT', 'MELF_GEN_SHAPE', 'MELF_FORCE_
                'MELF_IO_THREADS', 'MELF_HOST_THREADS', 'MELF_LIB_PATH')
 
 
-def _jpeg_orientation_on_gpu() -> bool:
-    """JPEG files with an EXIF orientation are decoded upright on the GPU; METERELF_JPEG_ORIENT=host leaves them to the host branch."""
-    return os.getenv('METERELF_JPEG_ORIENT', 'gpu') != 'host'
+# The JPEG switches get_meter_values makes its readers with: (MeterReader switch, environment variable, its default, the switch's tag in
+# the reader cache's key).  VARIABLE=gpu: such files are decoded on the GPU; VARIABLE=host: they are left to the host branch.
+#   jpeg_orientation     files with an EXIF orientation 2..8, decoded upright
+#   jpeg_progressive     progressive files -- 'host' by default: they cost latency on the GPU
+#   jpeg_samplings       4:4:0 and 4:1:1 files
+#   jpeg_multiscan       sequential files of three one-component scans -- on by default because one such file in a 256-file call costs
+#                        less on the GPU than through the host branch (profiles/jpeg_scans/jpeg_scans_rate.txt: 1.22 against 2.85 ms a call)
+#   jpeg_default_tables  files that leave Huffman tables out (Motion-JPEG frames), decoded with the Annex K tables
+#   jpeg_truncated       baseline files that end inside their scan, completed as libjpeg completes them
+JPEG_SWITCH_ENV = (
+    ('jpeg_orientation', 'METERELF_JPEG_ORIENT', 'gpu', b'orient'),
+    ('jpeg_progressive', 'METERELF_JPEG_PROGRESSIVE', 'host', b'prog'),
+    ('jpeg_samplings', 'METERELF_JPEG_SAMPLING', 'gpu', b'samp'),
+    ('jpeg_multiscan', 'METERELF_JPEG_MULTISCAN', 'gpu', b'scans'),
+    ('jpeg_default_tables', 'METERELF_JPEG_TABLES', 'gpu', b'tabs'),
+    ('jpeg_truncated', 'METERELF_JPEG_TRUNCATED', 'gpu', b'cut'),
+)
 
 
-def _jpeg_progressive_on_gpu() -> bool:
-    """METERELF_JPEG_PROGRESSIVE=gpu decodes progressive JPEG files on the GPU; 'host' (the default) leaves them to the host branch."""
-    return os.getenv('METERELF_JPEG_PROGRESSIVE', 'host') == 'gpu'
-
-
-def _jpeg_samplings_on_gpu() -> bool:
-    """4:4:0 and 4:1:1 JPEG files are decoded on the GPU; METERELF_JPEG_SAMPLING=host leaves them to the host branch."""
-    return os.getenv('METERELF_JPEG_SAMPLING', 'gpu') != 'host'
-
-
-def _jpeg_multiscan_on_gpu() -> bool:
-    """Sequential JPEG files of three one-component scans are decoded on the GPU; METERELF_JPEG_MULTISCAN=host leaves them to the host
-    branch.  On by default because one such file in a 256-file call costs less on the GPU than through the host branch
-    (profiles/jpeg_scans/jpeg_scans_rate.txt: 1.22 against 2.85 ms a call)."""
-    return os.getenv('METERELF_JPEG_MULTISCAN', 'gpu') != 'host'
-
-
-def _jpeg_truncated_on_gpu() -> bool:
-    """Baseline JPEG files that end inside their scan are completed on the GPU; METERELF_JPEG_TRUNCATED=host leaves them to the host
-    branch."""
-    return os.getenv('METERELF_JPEG_TRUNCATED', 'gpu') != 'host'
-
-
-def _jpeg_default_tables_on_gpu() -> bool:
-    """JPEG files that leave Huffman tables out (Motion-JPEG frames) are decoded on the GPU with the Annex K tables;
-    METERELF_JPEG_TABLES=host leaves them to the host branch."""
-    return os.getenv('METERELF_JPEG_TABLES', 'gpu') != 'host'
+def _jpeg_on_gpu(switch: str) -> bool:
+    """Whether get_meter_values' readers have the MeterReader switch on: its variable's word, else its default's."""
+    (var, default) = next((v, d) for (name, v, d, _tag) in JPEG_SWITCH_ENV if name == switch)
+    return {'gpu': True, 'host': False}.get(os.getenv(var), default == 'gpu')
 
 
 def _reader_key(params, blob, device: int) -> bytes:
     env = ';'.join('%s=%s' % (k, os.environ[k]) for k in _ENV_IN_KEY if k in os.environ)
-    orient = b'|orient%d|prog%d|samp%d|scans%d|tabs%d|cut%d|' % (_jpeg_orientation_on_gpu(), _jpeg_progressive_on_gpu(), _jpeg_samplings_on_gpu(),
-                                                                _jpeg_multiscan_on_gpu(), _jpeg_default_tables_on_gpu(),
-                                                                _jpeg_truncated_on_gpu())   # a reader keeps the settings it was made with
+    orient = b'|' + b''.join(b'%s%d|' % (tag, _jpeg_on_gpu(name)) for (name, _var, _default, tag) in JPEG_SWITCH_ENV)   # a reader keeps the settings it was made with
     return hashlib.sha1(blob.tobytes() + repr(list(params.dial_names)).encode() + b'|dev%d|' % device + orient + env.encode()).digest()
 
 
 def _with_jpeg_orientation(reader):
-    """Turns a new reader's switches on (MeterReader.set_jpeg_orientation, set_jpeg_progressive, set_jpeg_samplings, set_jpeg_multiscan,
-    set_jpeg_default_tables, set_jpeg_truncated) unless the host branch is asked for;
-    a reader from the cache has them already (the settings are part of its key)."""
-    if _jpeg_orientation_on_gpu() and hasattr(reader, 'set_jpeg_orientation') and not getattr(reader, 'jpeg_orientation', False):
-        reader.set_jpeg_orientation(True)
-    if _jpeg_progressive_on_gpu() and hasattr(reader, 'set_jpeg_progressive') and not getattr(reader, 'jpeg_progressive', False):
-        reader.set_jpeg_progressive(True)
-    if _jpeg_samplings_on_gpu() and hasattr(reader, 'set_jpeg_samplings') and not getattr(reader, 'jpeg_samplings', False):
-        reader.set_jpeg_samplings(True)
-    if _jpeg_multiscan_on_gpu() and hasattr(reader, 'set_jpeg_multiscan') and not getattr(reader, 'jpeg_multiscan', False):
-        reader.set_jpeg_multiscan(True)
-    if _jpeg_default_tables_on_gpu() and hasattr(reader, 'set_jpeg_default_tables') and not getattr(reader, 'jpeg_default_tables', False):
-        reader.set_jpeg_default_tables(True)
-    if _jpeg_truncated_on_gpu() and hasattr(reader, 'set_jpeg_truncated') and not getattr(reader, 'jpeg_truncated', False):
-        reader.set_jpeg_truncated(True)
+    """Turns a new reader's switches on (MeterReader.set_jpeg_orientation and the others of JPEG_SWITCH_ENV) unless the host branch is
+    asked for; a reader from the cache has them already (the settings are part of its key)."""
+    for (name, _var, _default, _tag) in JPEG_SWITCH_ENV:
+        if _jpeg_on_gpu(name) and hasattr(reader, 'set_' + name) and not getattr(reader, name, False):
+            getattr(reader, 'set_' + name)(True)
     return reader
 
 

@@ -149,54 +149,40 @@ class MeterReader:
         self._crop_ctx: Dict[Tuple[int, int], _hip.Context] = {}
         self._begun: list = []      # read_jpeg_paths_begin: path lists in flight, oldest first
         self._collected: list = []  # their results taken out of the library early (drain_jpeg_paths), oldest first
-        self.jpeg_orientation = False
-        if jpeg_orientation:
-            self.set_jpeg_orientation(True)
-        self.jpeg_progressive = False
-        if jpeg_progressive:
-            self.set_jpeg_progressive(True)
-        self.jpeg_samplings = False
-        if jpeg_samplings:
-            self.set_jpeg_samplings(True)
-        self.jpeg_multiscan = False
-        if jpeg_multiscan:
-            self.set_jpeg_multiscan(True)
-        self.jpeg_default_tables = False
-        if jpeg_default_tables:
-            self.set_jpeg_default_tables(True)
-        self.jpeg_truncated = False
-        if jpeg_truncated:
-            self.set_jpeg_truncated(True)
+        asked = dict(jpeg_orientation=jpeg_orientation, jpeg_progressive=jpeg_progressive, jpeg_samplings=jpeg_samplings,
+                     jpeg_multiscan=jpeg_multiscan, jpeg_default_tables=jpeg_default_tables, jpeg_truncated=jpeg_truncated)
+        for (name, _flag, _doc) in _hip.JPEG_SWITCHES:      # the attribute jpeg_<switch>: what the context was last told
+            setattr(self, name, False)
+            if asked[name]:
+                self._set_jpeg_switch(name, True)
+
+    def _set_jpeg_switch(self, name: str, on: bool) -> None:
+        getattr(self.ctx, 'set_' + name)(on)
+        setattr(self, name, bool(on))
 
     def set_jpeg_truncated(self, on: bool) -> None:
         """The switch of the constructor's jpeg_truncated, on a reader with nothing in flight (melf_ctx_set_jpeg_truncated)."""
-        self.ctx.set_jpeg_truncated(on)
-        self.jpeg_truncated = bool(on)
+        self._set_jpeg_switch('jpeg_truncated', on)
 
     def set_jpeg_multiscan(self, on: bool) -> None:
         """The switch of the constructor's jpeg_multiscan, on a reader with nothing in flight (melf_ctx_set_jpeg_multiscan)."""
-        self.ctx.set_jpeg_multiscan(on)
-        self.jpeg_multiscan = bool(on)
+        self._set_jpeg_switch('jpeg_multiscan', on)
 
     def set_jpeg_default_tables(self, on: bool) -> None:
         """The switch of the constructor's jpeg_default_tables, on a reader with nothing in flight (melf_ctx_set_jpeg_default_tables)."""
-        self.ctx.set_jpeg_default_tables(on)
-        self.jpeg_default_tables = bool(on)
+        self._set_jpeg_switch('jpeg_default_tables', on)
 
     def set_jpeg_samplings(self, on: bool) -> None:
         """The switch of the constructor's jpeg_samplings, on a reader with nothing in flight (melf_ctx_set_jpeg_samplings)."""
-        self.ctx.set_jpeg_samplings(on)
-        self.jpeg_samplings = bool(on)
+        self._set_jpeg_switch('jpeg_samplings', on)
 
     def set_jpeg_progressive(self, on: bool) -> None:
         """The switch of the constructor's jpeg_progressive, on a reader with nothing in flight (melf_ctx_set_jpeg_progressive)."""
-        self.ctx.set_jpeg_progressive(on)
-        self.jpeg_progressive = bool(on)
+        self._set_jpeg_switch('jpeg_progressive', on)
 
     def set_jpeg_orientation(self, on: bool) -> None:
         """The switch of the constructor's jpeg_orientation, on a reader with nothing in flight (melf_ctx_set_jpeg_orientation)."""
-        self.ctx.set_jpeg_orientation(on)
-        self.jpeg_orientation = bool(on)
+        self._set_jpeg_switch('jpeg_orientation', on)
 
     def close(self) -> None:
         self.ctx.close()
@@ -584,10 +570,8 @@ class MeterReader:
         decodes that one on the host."""
         out: List[Optional[np.void]] = [None] * len(files)
         groups: Dict[Tuple[int, int], List[int]] = {}
-        if self.jpeg_orientation or self.jpeg_progressive or self.jpeg_samplings or self.jpeg_multiscan or self.jpeg_default_tables:   # what the context's switches make the library take
-            flags = (_hip.JPEG_TAKE_ORIENTED if self.jpeg_orientation else 0) | (_hip.JPEG_TAKE_PROGRESSIVE if self.jpeg_progressive else 0) | \
-                    (_hip.JPEG_TAKE_SAMPLINGS if self.jpeg_samplings else 0) | (_hip.JPEG_TAKE_MULTISCAN if self.jpeg_multiscan else 0) | \
-                    (_hip.JPEG_TAKE_DEFAULT_TABLES if self.jpeg_default_tables else 0)
+        flags = sum(flag for (name, flag, _doc) in _hip.JPEG_SWITCHES if flag and getattr(self, name))   # what the context's switches make the library take
+        if flags:
             (hs, ws, orient, oks) = _hip.jpeg_probe_flags_batch(files, flags)
             if self.jpeg_orientation:    # by UPRIGHT size: what the library takes as H and W once that switch is on
                 (hs, ws) = (np.where(orient >= 5, ws, hs), np.where(orient >= 5, hs, ws))

@@ -325,21 +325,13 @@ def lib():
     L.melf_jpeg_probe_batch.argtypes = [vp, vp, C.c_int, vp, vp, vp]
     L.melf_jpeg_probe_oriented.argtypes = [vp, C.c_size_t, i32p, i32p, i32p, i32p]
     L.melf_jpeg_probe_oriented_batch.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
-    L.melf_ctx_set_jpeg_orientation.argtypes = [vp, C.c_int]
-    L.melf_ctx_get_jpeg_orientation.argtypes = [vp, C.POINTER(C.c_int)]
     L.melf_jpeg_probe_flags.argtypes = [vp, C.c_size_t, C.c_int, i32p, i32p, i32p, i32p]
     L.melf_jpeg_probe_flags_batch.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
-    L.melf_ctx_set_jpeg_progressive.argtypes = [vp, C.c_int]
-    L.melf_ctx_get_jpeg_progressive.argtypes = [vp, C.POINTER(C.c_int)]
-    L.melf_ctx_set_jpeg_samplings.argtypes = [vp, C.c_int]
-    L.melf_ctx_get_jpeg_samplings.argtypes = [vp, C.POINTER(C.c_int)]
-    L.melf_ctx_set_jpeg_multiscan.argtypes = [vp, C.c_int]
-    L.melf_ctx_get_jpeg_multiscan.argtypes = [vp, C.POINTER(C.c_int)]
-    L.melf_ctx_set_jpeg_default_tables.argtypes = [vp, C.c_int]
-    L.melf_ctx_get_jpeg_default_tables.argtypes = [vp, C.POINTER(C.c_int)]
-    if hasattr(L, 'melf_ctx_set_jpeg_truncated'):   # (tools/jpeg_cut_rate.py loads the library from before the switch through MELF_LIB_PATH)
-        L.melf_ctx_set_jpeg_truncated.argtypes = [vp, C.c_int]
-        L.melf_ctx_get_jpeg_truncated.argtypes = [vp, C.POINTER(C.c_int)]
+    for (name, _flag, _doc) in JPEG_SWITCHES:
+        if hasattr(L, 'melf_ctx_set_' + name):   # (tools/jpeg_cut_rate.py loads the library from before melf_ctx_set_jpeg_truncated through MELF_LIB_PATH)
+            getattr(L, 'melf_ctx_set_' + name).argtypes = [vp, C.c_int]
+            getattr(L, 'melf_ctx_get_' + name).argtypes = [vp, C.POINTER(C.c_int)]
+    if hasattr(L, 'melf_ctx_set_jpeg_truncated'):
         L.melf_ctx_jpeg_truncated_files.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
     L.melf_jpeg_decode_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]
     L.melf_jpeg_process_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]
@@ -1099,6 +1091,31 @@ JPEG_TAKE_SAMPLINGS = 4     # 4:4:0 and 4:1:1 files (melf_ctx_set_jpeg_samplings
 JPEG_TAKE_MULTISCAN = 32    # sequential files of three one-component scans (melf_ctx_set_jpeg_multiscan)
 JPEG_TAKE_DEFAULT_TABLES = 16   # sequential files that leave Huffman tables 0 / 1 out: Motion-JPEG frames (melf_ctx_set_jpeg_default_tables)
 
+# The JPEG switches of a context, one entry each: (name, the MELF_JPEG_TAKE_* flag a probe answers for it with -- None: no probe does --,
+# what the switch does).  The library has melf_ctx_set_<name> / melf_ctx_get_<name>, Context has set_<name>(on) / <name>(), MeterReader
+# the keyword argument, the attribute <name> and set_<name>(on); a new switch is a new entry here (and its line in _api.JPEG_SWITCH_ENV).
+JPEG_SWITCHES = (
+    ('jpeg_orientation', JPEG_TAKE_ORIENTED,
+     """JPEG files with an EXIF orientation 2..8 are decoded upright by the jpeg_* calls of this context instead of coming back
+     unsupported (melf_ctx_set_jpeg_orientation); H and W of those calls are then upright sizes.  Off by default."""),
+    ('jpeg_progressive', JPEG_TAKE_PROGRESSIVE,
+     """Progressive JPEG files (SOF2) of the subset include/meterelf_hip.h states are decoded by the jpeg_* calls of this context
+     instead of coming back unsupported (melf_ctx_set_jpeg_progressive).  Off by default."""),
+    ('jpeg_samplings', JPEG_TAKE_SAMPLINGS,
+     """YCbCr 4:4:0 (luma 1x2) and 4:1:1 (luma 4x1) JPEG files are decoded by the jpeg_* calls of this context instead of coming
+     back unsupported (melf_ctx_set_jpeg_samplings).  Off by default."""),
+    ('jpeg_multiscan', JPEG_TAKE_MULTISCAN,
+     """Sequential JPEG files sent as three scans of one component each are decoded by the jpeg_* calls of this context instead
+     of coming back unsupported (melf_ctx_set_jpeg_multiscan).  Off by default."""),
+    ('jpeg_default_tables', JPEG_TAKE_DEFAULT_TABLES,
+     """Sequential JPEG files that leave Huffman tables 0 / 1 out (Motion-JPEG frames: no DHT segment) are decoded with the
+     T.81 Annex K tables, as libjpeg-turbo does, instead of coming back unsupported (melf_ctx_set_jpeg_default_tables).  Off by default."""),
+    ('jpeg_truncated', None,       # deliberately no probe flag: the headers do not show that a file ends early
+     """Baseline JPEG files whose bytes stop inside the scan are completed by the jpeg_* calls of this context as libjpeg completes
+     them -- the cut MCU from zero bits, mid grey behind it -- instead of coming back corrupt (melf_ctx_set_jpeg_truncated).  Off by
+     default."""),
+)
+
 
 def jpeg_probe_flags(data, flags):
     """(H, W, orientation, supported, reason) of a JPEG file's bytes as the decode calls of a context with the switches `flags`
@@ -1695,66 +1712,7 @@ class Context:
     def files_in_flight(self):
         return len(getattr(self, '_files_pending', None) or ())
 
-    def set_jpeg_orientation(self, on):
-        """JPEG files with an EXIF orientation 2..8 are decoded upright by the jpeg_* calls of this context instead of coming back
-        unsupported (melf_ctx_set_jpeg_orientation); H and W of those calls are then upright sizes.  Off by default."""
-        check(self._L.melf_ctx_set_jpeg_orientation(self._h, int(bool(on))))
-
-    def jpeg_orientation(self):
-        on = C.c_int(0)
-        check(self._L.melf_ctx_get_jpeg_orientation(self._h, C.byref(on)))
-        return bool(on.value)
-
-    def set_jpeg_progressive(self, on):
-        """Progressive JPEG files (SOF2) of the subset include/meterelf_hip.h states are decoded by the jpeg_* calls of this context
-        instead of coming back unsupported (melf_ctx_set_jpeg_progressive).  Off by default."""
-        check(self._L.melf_ctx_set_jpeg_progressive(self._h, int(bool(on))))
-
-    def jpeg_progressive(self):
-        on = C.c_int(0)
-        check(self._L.melf_ctx_get_jpeg_progressive(self._h, C.byref(on)))
-        return bool(on.value)
-
-    def set_jpeg_samplings(self, on):
-        """YCbCr 4:4:0 (luma 1x2) and 4:1:1 (luma 4x1) JPEG files are decoded by the jpeg_* calls of this context instead of coming
-        back unsupported (melf_ctx_set_jpeg_samplings).  Off by default."""
-        check(self._L.melf_ctx_set_jpeg_samplings(self._h, int(bool(on))))
-
-    def jpeg_samplings(self):
-        on = C.c_int(0)
-        check(self._L.melf_ctx_get_jpeg_samplings(self._h, C.byref(on)))
-        return bool(on.value)
-
-    def set_jpeg_multiscan(self, on):
-        """Sequential JPEG files sent as three scans of one component each are decoded by the jpeg_* calls of this context instead
-        of coming back unsupported (melf_ctx_set_jpeg_multiscan).  Off by default."""
-        check(self._L.melf_ctx_set_jpeg_multiscan(self._h, int(bool(on))))
-
-    def jpeg_multiscan(self):
-        on = C.c_int(0)
-        check(self._L.melf_ctx_get_jpeg_multiscan(self._h, C.byref(on)))
-        return bool(on.value)
-
-    def set_jpeg_default_tables(self, on):
-        """Sequential JPEG files that leave Huffman tables 0 / 1 out (Motion-JPEG frames: no DHT segment) are decoded with the
-        T.81 Annex K tables, as libjpeg-turbo does, instead of coming back unsupported (melf_ctx_set_jpeg_default_tables).  Off by default."""
-        check(self._L.melf_ctx_set_jpeg_default_tables(self._h, int(bool(on))))
-
-    def jpeg_default_tables(self):
-        on = C.c_int(0)
-        check(self._L.melf_ctx_get_jpeg_default_tables(self._h, C.byref(on)))
-        return bool(on.value)
-
-    def set_jpeg_truncated(self, on):
-        """Baseline JPEG files whose bytes stop inside the scan are completed by the jpeg_* calls of this context as libjpeg completes
-        them -- the cut MCU from zero bits, mid grey behind it -- instead of coming back corrupt (melf_ctx_set_jpeg_truncated).  Off by
-        default."""
-        check(self._L.melf_ctx_set_jpeg_truncated(self._h, int(bool(on))))
-
-    def jpeg_truncated(self):
-        on = C.c_int(0)
-        check(self._L.melf_ctx_get_jpeg_truncated(self._h, C.byref(on)))
-        return bool(on.value)
+    # set_jpeg_orientation(on) / jpeg_orientation() and so on, one pair per entry of JPEG_SWITCHES: _add_jpeg_switch below the class
 
     def jpeg_truncated_files(self, reset=False):
         """Files this context's calls completed under that rule since the last reset (melf_ctx_jpeg_truncated_files)."""
@@ -1797,3 +1755,21 @@ class Context:
         cnt = np.zeros(K_COUNT, np.int64)
         check(self._L.melf_ctx_timings(self._h, _ptr(ms), _ptr(cnt)))
         return {self._L.melf_kernel_name(k).decode(): (float(ms[k]), int(cnt[k])) for k in range(K_COUNT)}
+
+
+def _add_jpeg_switch(name, doc):
+    def set_switch(self, on):
+        check(getattr(self._L, 'melf_ctx_set_' + name)(self._h, int(bool(on))))
+
+    def get_switch(self):
+        on = C.c_int(0)
+        check(getattr(self._L, 'melf_ctx_get_' + name)(self._h, C.byref(on)))
+        return bool(on.value)
+    set_switch.__doc__ = doc
+    (set_switch.__name__, get_switch.__name__) = ('set_' + name, name)
+    setattr(Context, 'set_' + name, set_switch)
+    setattr(Context, name, get_switch)
+
+
+for (_name, _flag, _doc) in JPEG_SWITCHES:
+    _add_jpeg_switch(_name, _doc)

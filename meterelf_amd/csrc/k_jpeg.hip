@@ -14,7 +14,7 @@
 // the algorithm descriptions in the libjpeg documentation (jidctint / jdsample / jdcolor) and
 // pinned bit-for-bit against Pillow on the reference's 304 fixture files plus synthetic files.
 //
-//   host   parse markers, canonical Huffman data, strip byte stuffing / RSTn markers (recording where the
+//   host   parse markers (melf_jpeg_parse.h), canonical Huffman data, strip byte stuffing / RSTn markers (recording where the
 //          restart intervals begin)
 //   J1     k_jpeg_huff      one workgroup per image, one lane per bit-stream segment (speculative decode until
 //                           the segments' exit states reach a fixed point) -> int16 coefficient blocks in decode order
@@ -31,9 +31,9 @@
 #include "melf_internal.h"
 #include "melf_jpeg_cut.h"
 #include "melf_jpeg_orient_addr.h"
+#include "melf_jpeg_parse.h"
 #include "melf_jpeg_prog.h"
 #include "melf_jpeg_scans.h"
-#include "melf_jpeg_std_tables.h"
 #include "melf_threads.h"
 
 #include <emmintrin.h>
@@ -49,513 +49,6 @@
 #include <vector>
 
 namespace melf {
-
-// ------------------------------------------------------------------ host: parsing ----
-static const uint8_t ZIGZAG_TO_NATURAL[64] = {
-    0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-    41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-    30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-struct HuffSpec {
-    uint8_t bits[17];  // bits[l] = number of codes of length l
-    uint8_t vals[256];
-    int nvals;
-    bool set;
-};
-
-struct JpegHeader {
-    int H = 0, W = 0, ncomp = 0;
-    int id[3] = {0, 0, 0}, hs[3] = {1, 1, 1}, vs[3] = {1, 1, 1}, tq[3] = {0, 0, 0}, td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
-    int restart_interval = 0;
-    uint16_t qt[4][64];
-    bool qt_set[4] = {false, false, false, false};
-    HuffSpec dc[4], ac[4];      // ids 2 and 3: progressive files only
-    size_t scan_begin = 0;
-    bool saw_jfif = false, saw_adobe = false, saw_exif = false;
-    int orient = 1;             // EXIF orientation of the first Exif APP1 (1 when absent, unreadable or outside 1..8)
-    int orient_tag = 1;         // the same whether or not the caller takes oriented files
-    int adobe_transform = 0;
-    const char* why = nullptr;  // non-NULL: a valid-looking file this decoder does not handle
-    // A progressive file (SOF2) that is taken: its scans (byte offsets relative to scan_begin, the first scan's first byte), the
-    // distinct Huffman tables they use, and where their restart intervals begin
-    bool progressive = false;
-    std::vector<jpeg_prog::Scan> pscans;
-    std::vector<jpeg_prog::Huff> ptabs;
-    std::vector<uint32_t> prst;
-    // A multi-scan sequential file that is taken (melf_jpeg_scans.h): per COMPONENT its scan -- the tables in force at its SOS, its
-    // restart interval (in blocks of the component), and its entropy-coded bytes (offset relative to scan_begin, up to the next marker)
-    struct MScan { HuffSpec dc, ac; int restart_interval; size_t off, len; };
-    bool multiscan = false;
-    std::vector<MScan> ms;      // three, once multiscan
-};
-constexpr int TAKE_ORIENTED = 1, TAKE_PROGRESSIVE = 2, TAKE_SAMPLINGS = 4, TAKE_DEFAULT_TABLES = 16, TAKE_MULTISCAN = 32;   // MELF_JPEG_TAKE_*: what a caller's switches make the parser accept
-constexpr int TAKE_TRUNCATED = JPEG_TAKE_TRUNCATED_INTERNAL;   // not a probe flag (the headers do not show a cut): melf_ctx_set_jpeg_truncated, for the Huffman stage alone
-
-static inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
-
-// Returns 0 = parsed (check h.why for "unsupported"), -1 = not a JPEG / truncated headers.
-// The orientation tag (0x0112) of IFD0 of an EXIF block (TIFF header at `t`): 1..8, or 0 when absent / unreadable.
-static int exif_orientation(const uint8_t* t, int n)
-{
-    if (n < 8) return 0;
-    const bool le = t[0] == 'I' && t[1] == 'I';
-    if (!le && !(t[0] == 'M' && t[1] == 'M')) return 0;
-    auto u16 = [&](int o) { return le ? (t[o] | t[o + 1] << 8) : (t[o] << 8 | t[o + 1]); };
-    auto u32 = [&](int o) { return le ? ((uint32_t)t[o] | (uint32_t)t[o + 1] << 8 | (uint32_t)t[o + 2] << 16 | (uint32_t)t[o + 3] << 24)
-                                      : ((uint32_t)t[o] << 24 | (uint32_t)t[o + 1] << 16 | (uint32_t)t[o + 2] << 8 | (uint32_t)t[o + 3]); };
-    if (u16(2) != 42) return 0;
-    const uint32_t ifd = u32(4);
-    if (ifd > (uint32_t)n - 2) return 0;
-    const int cnt = u16((int)ifd);
-    for (int k = 0; k < cnt; ++k) {
-        const long e = (long)ifd + 2 + 12L * k;
-        if (e + 12 > n) return 0;
-        if (u16((int)e) == 0x0112) {
-            const int v = u16((int)e + 8);   // type SHORT, count 1: the value sits in the first two bytes of the value field
-            return (v >= 1 && v <= 8) ? v : 0;
-        }
-    }
-    return 0;
-}
-
-// What libjpeg checks when it builds the decoding table of a Huffman table the scan refers to (jdhuff, derived tables): the
-// canonical code counter must stay below 2^l after the codes of every length l in use -- an over-subscribed code set fails
-// that, and so does a complete one, whose last code is all ones -- and a DC table may only hold the categories 0..15.  A
-// table that fails makes libjpeg refuse the file; the kernels would decode something from it, so it is refused here too.
-static const char* huff_spec_flaw(const HuffSpec& t, const bool dc)
-{
-    int last = 0;
-    for (int l = 1; l <= 16; ++l) if (t.bits[l]) last = l;
-    long code = 0;
-    for (int l = 1; l <= last; ++l) {
-        code += t.bits[l];
-        if (code >= (1L << l)) return "Huffman table over-subscribed or using the all-ones code (libjpeg rejects it)";
-        code <<= 1;
-    }
-    if (dc)
-        for (int i = 0; i < t.nvals; ++i)
-            if (t.vals[i] > 15) return "DC Huffman table with a category above 15 (libjpeg rejects it)";
-    return nullptr;
-}
-
-// The rules on the frame header that do not depend on the kind of scan: sets h.why, and makes a greyscale frame 1x1.
-// take_samp (TAKE_SAMPLINGS): luma 1x2 (4:4:0) and 4x1 (4:1:1) are taken too; 4:1:0 (4x2) has 10 blocks an MCU, McuLayout packs 6.
-static void frame_rules(JpegHeader& h, const bool take_samp)
-{
-    if (h.H <= 0 || h.W <= 0) { h.why = "empty image"; return; }
-    if (h.ncomp == 3) {
-        if (h.saw_adobe && h.adobe_transform != 1) h.why = "Adobe marker says the data are not YCbCr";
-        else if (!h.saw_jfif && !h.saw_adobe && h.id[0] == 'R' && h.id[1] == 'G' && h.id[2] == 'B') h.why = "RGB component ids";
-        else if (h.hs[1] != 1 || h.vs[1] != 1 || h.hs[2] != 1 || h.vs[2] != 1) h.why = "subsampled chroma with sampling factors above 1";
-        else if (!((h.hs[0] == 1 && h.vs[0] == 1) || (h.hs[0] == 2 && h.vs[0] == 1) || (h.hs[0] == 2 && h.vs[0] == 2))) {
-            if (!take_samp) h.why = "luma sampling other than 1x1, 2x1, 2x2";
-            else if (h.hs[0] == 4 && h.vs[0] == 2) h.why = "4:1:0 (luma sampling 4x2): more than 6 blocks an MCU";
-            else if (!((h.hs[0] == 1 && h.vs[0] == 2) || (h.hs[0] == 4 && h.vs[0] == 1))) h.why = "luma sampling other than 1x1, 2x1, 2x2, 1x2, 4x1";
-        }
-    } else {
-        h.hs[0] = h.vs[0] = 1;  // a single-component scan is never interleaved: one block per MCU
-    }
-}
-
-// libjpeg-turbo's std_huff_tables, for a caller that asked for it (TAKE_DEFAULT_TABLES): when the Huffman decoder starts -- behind the
-// headers up to the first SOS -- each of the slots DC 0, AC 0, DC 1, AC 1 that no DHT has defined receives the table Annex K.3 prints
-// for it (melf_jpeg_std_tables.h).  Slots 2 and 3 receive nothing; a slot a DHT defined keeps its definition, flawed or not.
-static void install_std_tables(JpegHeader& h)
-{
-    for (int cls = 0; cls < 2; ++cls)
-        for (int id = 0; id < 2; ++id) {
-            HuffSpec& t = cls ? h.ac[id] : h.dc[id];
-            if (t.set) continue;
-            const jpeg_std::Table& k = jpeg_std::TABLES[cls][id];
-            t.bits[0] = 0;
-            memcpy(t.bits + 1, k.counts, 16);
-            memcpy(t.vals, k.vals, (size_t)k.nvals);
-            t.nvals = k.nvals;
-            t.set = true;
-        }
-}
-
-struct HuffSlow;
-static void build_huff(const HuffSpec& t, HuffSlow* slow);
-
-// What the parser keeps while it goes through a progressive file's scans (T.81 G.1.1.1.1 and libjpeg's progressive decoder).
-struct ProgState {
-    int8_t bits[3][64];   // per coefficient: -1 = not sent yet, else the precision (Al) it has been brought to
-    int dc_idx[4], ac_idx[4];   // where table id t, as defined now, stands in h.ptabs (-1: not built)
-    bool started = false;
-    ProgState() { memset(bits, -1, sizeof(bits)); for (int t = 0; t < 4; ++t) dc_idx[t] = ac_idx[t] = -1; }
-};
-static jpeg_prog::File prog_file_geometry(const JpegHeader& h)
-{
-    jpeg_prog::File f;
-    memset(&f, 0, sizeof(f));
-    f.ncomp = (uint8_t)h.ncomp; f.hs0 = (uint8_t)h.hs[0]; f.vs0 = (uint8_t)h.vs[0];
-    f.mcus_x = (uint16_t)((h.W + 8 * h.hs[0] - 1) / (8 * h.hs[0]));
-    f.mcus_y = (uint16_t)((h.H + 8 * h.vs[0] - 1) / (8 * h.vs[0]));
-    f.rbx0 = (uint16_t)((h.W + 7) / 8); f.rby0 = (uint16_t)((h.H + 7) / 8);
-    f.rbxc = (uint16_t)(((h.W + h.hs[0] - 1) / h.hs[0] + 7) / 8); f.rbyc = (uint16_t)(((h.H + h.vs[0] - 1) / h.vs[0] + 7) / 8);
-    return f;
-}
-// One SOS of a progressive file (s: its parameters): the scan's record, or why the file is not taken.
-static const char* prog_scan_header(JpegHeader& h, ProgState& ps, const uint8_t* s, jpeg_prog::Scan& sc)
-{
-    memset(&sc, 0, sizeof(sc));
-    sc.ac_tab = jpeg_prog::NO_TABLE;
-    for (int k = 0; k < 3; ++k) sc.dc_tab[k] = jpeg_prog::NO_TABLE;
-    const int ns = s[0];
-    if (ns < 1 || ns > h.ncomp) return "progressive scan with a component count outside 1..components of the frame";
-    const uint8_t* e = s + 1 + 2 * ns;
-    const int Ss = e[0], Se = e[1], Ah = e[2] >> 4, Al = e[2] & 15;
-    if (Ss == 0 ? Se != 0 : (ns != 1 || Se < Ss || Se > 63)) return "progressive scan whose band is not DC alone or Ss <= Se <= 63 of one component";
-    if (Ah != 0 && Al != Ah - 1) return "progressive scan whose Al is not Ah - 1";
-    if (Al > 13) return "progressive scan with Al above 13";
-    sc.ns = (uint8_t)ns; sc.Ss = (uint8_t)Ss; sc.Se = (uint8_t)Se; sc.Ah = (uint8_t)Ah; sc.Al = (uint8_t)Al;
-    sc.restart_interval = (uint16_t)h.restart_interval;
-    int prev = -1;
-    for (int k = 0; k < ns; ++k) {
-        const int cid = s[1 + 2 * k];
-        int c = -1;
-        for (int q = 0; q < h.ncomp; ++q) if (h.id[q] == cid) c = q;
-        if (c <= prev) return "progressive scan whose components are not in the frame header's order";
-        prev = c;
-        sc.comp[k] = (uint8_t)c;
-        const int td = s[2 + 2 * k] >> 4, ta = s[2 + 2 * k] & 15;
-        if (td > 3 || ta > 3) return "Huffman table id above 3";
-        if (Ss > 0 && ps.bits[c][0] < 0) return "inconsistent progression: an AC scan before the component's first DC scan";
-        for (int z = Ss; z <= Se; ++z) {
-            if (Ah == 0 ? ps.bits[c][z] >= 0 : ps.bits[c][z] != Ah)
-                return Ah == 0 ? "inconsistent progression: a first scan over coefficients already sent"
-                               : "inconsistent progression: a refinement of coefficients whose precision is not Ah";
-            ps.bits[c][z] = (int8_t)Al;
-        }
-        // the tables in force now: a DC first scan decodes with its DC tables, every AC scan with its AC table
-        const bool need_dc = Ss == 0 && Ah == 0, need_ac = Ss > 0;
-        if (need_dc || need_ac) {
-            const HuffSpec& t = need_dc ? h.dc[td] : h.ac[ta];
-            int& idx = need_dc ? ps.dc_idx[td] : ps.ac_idx[ta];
-            if (!t.set) return "missing Huffman table";
-            if (idx < 0) {
-                if (const char* flaw = huff_spec_flaw(t, need_dc)) return flaw;
-                if (h.ptabs.size() >= 255) return "too many Huffman tables";
-                idx = (int)h.ptabs.size();
-                h.ptabs.emplace_back();
-                build_huff(t, (HuffSlow*)&h.ptabs.back());
-            }
-            if (need_dc) sc.dc_tab[k] = (uint8_t)idx; else sc.ac_tab = (uint8_t)idx;
-        }
-    }
-    return nullptr;
-}
-
-// take: TAKE_ORIENTED -- a file with an orientation tag 2..8 is one for the GPU (h.orient says which); TAKE_PROGRESSIVE -- so is a
-// progressive file of the subset include/meterelf_hip.h states (h.progressive, h.pscans); TAKE_SAMPLINGS -- and a 4:4:0 or 4:1:1
-// file (frame_rules); TAKE_DEFAULT_TABLES -- and a sequential file that leaves Huffman tables 0 / 1 out (install_std_tables).  Otherwise
-// they are unsupported, as ever.
-static int parse_headers(const uint8_t* d, size_t n, JpegHeader& h, const int take = 0)
-{
-    const bool take_orient = (take & TAKE_ORIENTED) != 0, take_prog = (take & TAKE_PROGRESSIVE) != 0, take_samp = (take & TAKE_SAMPLINGS) != 0;
-    const bool take_multi = (take & TAKE_MULTISCAN) != 0;
-    unsigned ms_seen = 0;   // multi-scan sequential file: the components that have had their scan
-    for (int i = 0; i < 4; ++i) { h.dc[i].set = false; h.ac[i].set = false; }
-    if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return -1;
-    size_t i = 2;
-    bool have_sof = false, high_table = false;
-    ProgState ps;
-    for (;;) {
-        while (i < n && d[i] != 0xFF) ++i;  // tolerate garbage between segments like libjpeg's next_marker
-        while (i < n && d[i] == 0xFF) ++i;
-        if (i >= n) return -1;
-        const int m = d[i++];
-        if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;  // parameterless
-        if (m == 0xD9) {
-            if (h.progressive && ps.started) goto prog_done;
-            if (h.multiscan) { h.why = "sequential file that ends before every component has had its scan"; return 0; }
-            return -1;                                                      // EOI before SOS
-        }
-        if (i + 2 > n) return -1;
-        const int L = be16(d + i);
-        if (L < 2 || i + L > n) return -1;
-        const uint8_t* s = d + i + 2;
-        const int len = L - 2;
-        // One frame header per file: once a progressive frame is taken, any further SOFn (libjpeg: "duplicate SOF") makes the file
-        // unsupported -- the rules on the frame were applied to the first one, and the scans recorded so far rest on its geometry.
-        if (h.progressive && m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
-            h.why = "second frame header in a progressive file (libjpeg rejects it)";
-            return 0;
-        }
-        if (h.multiscan) {   // between the scans of a multi-scan sequential file: DHT and DRI count, COM and APPn are passed by
-            if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) { h.why = "second frame header behind a scan (libjpeg rejects it)"; return 0; }
-            if (m == 0xDB) { h.why = "quantisation table defined after the first scan of a multi-scan file"; return 0; }
-            if ((m >= 0xE0 && m <= 0xEF) || m == 0xFE) { i += L; continue; }
-        }
-        switch (m) {
-            case 0xC0: case 0xC1: sof_taken: {  // baseline / extended sequential, Huffman -- and progressive, where the caller takes it
-                if (len < 6) return -1;
-                if (s[0] != 8) { h.why = "sample precision is not 8 bits"; }
-                h.H = be16(s + 1); h.W = be16(s + 3); h.ncomp = s[5];
-                if (h.ncomp != 1 && h.ncomp != 3) { h.why = "neither greyscale nor three components"; h.ncomp = h.ncomp > 3 ? 3 : h.ncomp; }
-                if (len < 6 + 3 * (int)s[5]) return -1;
-                for (int c = 0; c < h.ncomp; ++c) {
-                    h.id[c] = s[6 + 3 * c]; h.hs[c] = s[7 + 3 * c] >> 4; h.vs[c] = s[7 + 3 * c] & 15; h.tq[c] = s[8 + 3 * c] & 3;
-                }
-                have_sof = true;
-                if (m == 0xC2) h.progressive = true;
-                else if (high_table && !take_multi) h.why = "Huffman table id above 1";   // (take_multi: decided at the first SOS)
-                break;
-            }
-            case 0xC2:
-                if (take_prog && !have_sof) goto sof_taken;
-                // fallthrough
-            case 0xC3: case 0xC5: case 0xC6: case 0xC7: case 0xC9: case 0xCA: case 0xCB: case 0xCD: case 0xCE: case 0xCF:
-                h.why = "not a baseline sequential Huffman JPEG (progressive / lossless / arithmetic)";
-                if (len >= 6) { h.H = be16(s + 1); h.W = be16(s + 3); }
-                return 0;
-            case 0xDB: {  // DQT
-                if (ps.started) { h.why = "quantisation table defined after the first scan of a progressive file"; return 0; }
-                int o = 0;
-                while (o < len) {
-                    const int pq = s[o] >> 4, tq = s[o] & 15;
-                    ++o;
-                    if (tq > 3 || o + (pq ? 128 : 64) > len) return -1;
-                    for (int k = 0; k < 64; ++k) {
-                        const int v = pq ? be16(s + o + 2 * k) : s[o + k];
-                        h.qt[tq][ZIGZAG_TO_NATURAL[k]] = (uint16_t)v;
-                    }
-                    h.qt_set[tq] = true;
-                    o += pq ? 128 : 64;
-                }
-                break;
-            }
-            case 0xC4: {  // DHT
-                int o = 0;
-                while (o < len) {
-                    if (o + 17 > len) return -1;
-                    const int tc = s[o] >> 4, th = s[o] & 15;
-                    int total = 0;
-                    for (int l = 1; l <= 16; ++l) total += s[o + l];
-                    if (total > 256 || o + 17 + total > len || tc > 1) return -1;
-                    // ids 2 and 3 are a progressive file's to use; anywhere else they make the file unsupported, as ever
-                    if (th > 3 || (th > 1 && !take_prog && !take_multi)) { h.why = "Huffman table id above 1"; o += 17 + total; continue; }
-                    if (th > 1 && !h.progressive) { if (have_sof && !take_multi) h.why = "Huffman table id above 1"; else high_table = true; }
-                    (tc ? ps.ac_idx[th] : ps.dc_idx[th]) = -1;   // a scan after this one builds the new definition
-                    HuffSpec& t = tc ? h.ac[th] : h.dc[th];
-                    t.bits[0] = 0;
-                    for (int l = 1; l <= 16; ++l) t.bits[l] = s[o + l];
-                    memcpy(t.vals, s + o + 17, total);
-                    t.nvals = total;
-                    t.set = true;
-                    o += 17 + total;
-                }
-                break;
-            }
-            case 0xDD:
-                if (len < 2) return -1;
-                h.restart_interval = be16(s);
-                break;
-            case 0xE0:
-                if (len >= 5 && !memcmp(s, "JFIF\0", 5)) h.saw_jfif = true;
-                break;
-            case 0xE1:  // APP1: cv2.imread (3.4) applies the EXIF orientation tag.  Unless the caller takes oriented files
-                        // (k_jpeg_color_exif), a file that asks for it goes to the caller's host decoder (which rotates:
-                        // meterelf_amd/_image.py).  Only the first Exif block counts; a later one that asks again is left to the host.
-                if (len >= 14 && !memcmp(s, "Exif\0\0", 6)) {
-                    const int o = exif_orientation(s + 6, len - 6);
-                    if (o > 1 && !h.saw_exif) h.orient_tag = o;
-                    if (o > 1 && (!take_orient || h.saw_exif)) h.why = "EXIF orientation other than top-left (decoded and rotated on the host)";
-                    else if (o > 1) h.orient = o;
-                    h.saw_exif = true;
-                }
-                break;
-            case 0xEE:
-                if (len >= 12 && !memcmp(s, "Adobe", 5)) { h.saw_adobe = true; h.adobe_transform = s[11]; }
-                break;
-            case 0xDA: {  // SOS
-                if (!have_sof) return -1;
-                if (len < 1) return -1;
-                const int ns = s[0];
-                if (len < 1 + 2 * ns + 3) return -1;
-                if (h.progressive) {
-                    if (h.why) return 0;   // refused by a segment between the scans: no further scan is looked at
-                    if (!ps.started) {   // the frame must be one for the decoder before any scan byte is looked at
-                        if (!h.why) frame_rules(h, take_samp);
-                        for (int c = 0; c < h.ncomp && !h.why; ++c)
-                            if (!h.qt_set[h.tq[c]]) h.why = "missing quantisation table";
-                        if (h.why) return 0;
-                        h.scan_begin = i + L;
-                        ps.started = true;
-                    }
-                    if (h.pscans.size() >= (size_t)MELF_JPEG_PROG_SCANS_MAX) { h.why = "progressive file with more scans than MELF_JPEG_PROG_SCANS_MAX"; return 0; }
-                    jpeg_prog::Scan sc;
-                    if (const char* flaw = prog_scan_header(h, ps, s, sc)) { h.why = flaw; return 0; }
-                    // the scan's bytes, once: where it ends and where its restart intervals begin
-                    const jpeg_prog::File geo = prog_file_geometry(h);
-                    const uint32_t expected = jpeg_prog::scan_intervals(geo, sc);
-                    sc.off = (uint32_t)(i + L - h.scan_begin);
-                    sc.rst_first = (uint32_t)h.prst.size();
-                    h.prst.resize(h.prst.size() + expected);
-                    uint32_t found = 0;
-                    const size_t end = jpeg_prog::walk_scan(d, i + L, n, h.prst.data() + sc.rst_first, expected, &found);
-                    if (end >= n) return -1;   // the data end inside a scan: a truncated file
-                    sc.len = (uint32_t)(end - (i + L));
-                    sc.rst_count = found;
-                    for (uint32_t k = found; k < expected; ++k) h.prst[sc.rst_first + k] = 0;
-                    for (const jpeg_prog::Scan& t : h.pscans) {   // the level: behind every earlier scan that touches a coefficient of this one
-                        bool shared = false;
-                        for (int a = 0; a < sc.ns; ++a)
-                            for (int b = 0; b < t.ns; ++b) shared = shared || sc.comp[a] == t.comp[b];
-                        if (shared && sc.Ss <= t.Se && t.Ss <= sc.Se && t.level + 1 > sc.level) sc.level = (uint8_t)(t.level + 1);
-                    }
-                    h.pscans.push_back(sc);
-                    i = end;
-                    continue;
-                }
-                if (h.multiscan || (take_multi && h.ncomp == 3 && (ns == 1 || ns == 2))) {
-                    // A sequential file that sends its components in scans of their own (melf_jpeg_scans.h).  Ids 2 and 3 and
-                    // redefinitions between the scans are free: every scan keeps a snapshot of the two tables in force at its SOS.
-                    if (h.why) return 0;
-                    if (!h.multiscan) {   // the frame must be one for the decoder before any scan byte is looked at
-                        frame_rules(h, take_samp);
-                        for (int c = 0; c < h.ncomp && !h.why; ++c)
-                            if (!h.qt_set[h.tq[c]]) h.why = "missing quantisation table";
-                        if (h.why) return 0;
-                        if (take & TAKE_DEFAULT_TABLES) install_std_tables(h);   // once, before the first scan, as libjpeg does
-                        h.scan_begin = i + L;
-                        h.multiscan = true;
-                        h.ms.assign(3, JpegHeader::MScan());
-                    }
-                    int c = -1;
-                    for (int q = 0; q < h.ncomp; ++q) if (h.id[q] == s[1]) c = q;
-                    const uint8_t* e = s + 1 + 2 * ns;
-                    if (const char* flaw = jpeg_scans::scan_rule(ns, c, ms_seen, e[0], e[1], e[2])) { h.why = flaw; return 0; }
-                    const int td = s[2] >> 4, ta = s[2] & 15;
-                    if (td > 3 || ta > 3) { h.why = "Huffman table id above 3"; return 0; }
-                    if (!h.dc[td].set || !h.ac[ta].set) { h.why = "missing Huffman table"; return 0; }
-                    if (const char* flaw = huff_spec_flaw(h.dc[td], true)) { h.why = flaw; return 0; }
-                    if (const char* flaw = huff_spec_flaw(h.ac[ta], false)) { h.why = flaw; return 0; }
-                    JpegHeader::MScan& sc = h.ms[c];
-                    sc.dc = h.dc[td]; sc.ac = h.ac[ta];
-                    sc.restart_interval = h.restart_interval;
-                    sc.off = i + L - h.scan_begin;
-                    uint32_t found = 0;
-                    const size_t end = jpeg_prog::walk_scan(d, i + L, n, nullptr, 0, &found);   // the one pass over these files' bytes
-                    if (end >= n) return -1;   // the data end inside a scan: a truncated file
-                    sc.len = end - (i + L);
-                    ms_seen |= 1u << c;
-                    i = end;
-                    if (ms_seen != 7u) continue;
-                    size_t j = end;   // behind the third scan: EOI (what lies behind that is ignored, as ever)
-                    while (j < n && d[j] == 0xFF) ++j;
-                    if (j >= n) return -1;
-                    if (d[j] != 0xD9) h.why = "segment behind the third scan of a multi-scan file other than EOI";
-                    return 0;
-                }
-                if (ns != h.ncomp) { h.why = "more than one scan (non-interleaved components)"; return 0; }
-                if (take_multi && high_table && !h.why) h.why = "Huffman table id above 1";
-                for (int k = 0; k < ns; ++k) {
-                    const int cid = s[1 + 2 * k];
-                    int c = -1;
-                    for (int q = 0; q < h.ncomp; ++q) if (h.id[q] == cid) c = q;
-                    if (c != k) { h.why = "scan component order differs from the frame header"; return 0; }
-                    h.td[c] = s[2 + 2 * k] >> 4; h.ta[c] = s[2 + 2 * k] & 15;
-                    if (h.td[c] > 1 || h.ta[c] > 1) h.why = "Huffman table id above 1";
-                }
-                const uint8_t* e = s + 1 + 2 * ns;
-                if (e[0] != 0 || e[1] != 63 || e[2] != 0) { h.why = "not a full sequential scan"; return 0; }
-                h.scan_begin = i + L;
-                goto done;
-            }
-            default: break;
-        }
-        i += L;
-    }
-prog_done:
-    // libjpeg smooths blocks whose AC coefficients have not reached full precision (jdcoefct's block smoothing): the pixels are
-    // those of the coefficient blocks only when every scan of the script has arrived
-    for (int c = 0; c < h.ncomp; ++c)
-        for (int z = 0; z < 64; ++z)
-            if (ps.bits[c][z] != 0) { h.why = "progressive script incomplete: not every coefficient reaches full precision (libjpeg smooths such blocks)"; return 0; }
-    return 0;
-done:
-    if (h.why) return 0;
-    frame_rules(h, take_samp);
-    if (h.H <= 0 || h.W <= 0) return 0;
-    if (take & TAKE_DEFAULT_TABLES) install_std_tables(h);
-    for (int c = 0; c < h.ncomp && !h.why; ++c) {
-        if (!h.qt_set[h.tq[c]]) h.why = "missing quantisation table";
-        else if (!h.dc[h.td[c]].set || !h.ac[h.ta[c]].set) h.why = "missing Huffman table";
-        else if (const char* flaw = huff_spec_flaw(h.dc[h.td[c]], true)) h.why = flaw;
-        else if (const char* flaw_ac = huff_spec_flaw(h.ac[h.ta[c]], false)) h.why = flaw_ac;
-    }
-    return 0;
-}
-
-int jpeg_probe(const uint8_t* data, size_t size, int* H, int* W, int* supported, std::string* why)
-{
-    JpegHeader h;
-    if (parse_headers(data, size, h) != 0) {
-        *H = *W = 0; *supported = 0;
-        if (why) *why = "not a JPEG file or truncated headers";
-        return 0;
-    }
-    *H = h.H; *W = h.W; *supported = h.why ? 0 : 1;
-    if (why) *why = h.why ? h.why : "";
-    return 0;
-}
-
-// The same with the orientation taken: the STORED size, the code, and whether the decoder takes the file apart from its tag.
-int jpeg_probe_oriented(const uint8_t* data, size_t size, int* H, int* W, int* orientation, int* supported, std::string* why)
-{
-    JpegHeader h;
-    if (parse_headers(data, size, h, TAKE_ORIENTED) != 0) {
-        *H = *W = 0; *supported = 0; *orientation = 1;
-        if (why) *why = "not a JPEG file or truncated headers";
-        return 0;
-    }
-    *H = h.H; *W = h.W; *orientation = h.orient; *supported = h.why ? 0 : 1;
-    if (why) *why = h.why ? h.why : "";
-    return 0;
-}
-
-// What the decode calls of a context with the switches `flags` (MELF_JPEG_TAKE_*) answer from the headers.  The orientation code is
-// reported whether or not files that carry one are taken.
-int jpeg_probe_flags(const uint8_t* data, size_t size, int flags, int* H, int* W, int* orientation, int* supported, std::string* why)
-{
-    JpegHeader h;
-    if (parse_headers(data, size, h, flags & (TAKE_ORIENTED | TAKE_PROGRESSIVE | TAKE_SAMPLINGS | TAKE_MULTISCAN | TAKE_DEFAULT_TABLES)) != 0) {
-        *H = *W = 0; *supported = 0; *orientation = 1;
-        if (why) *why = "not a JPEG file or truncated headers";
-        return 0;
-    }
-    *H = h.H; *W = h.W; *orientation = h.orient_tag; *supported = h.why ? 0 : 1;
-    if (why) *why = h.why ? h.why : "";
-    return 0;
-}
-
-// The orientation alone (1..8), from a walk over the marker segments in front of the frame header: what parse_headers records,
-// for a caller that orders a call's files before they are parsed.
-int jpeg_file_orientation(const uint8_t* d, size_t n, int* progressive)
-{
-    if (progressive) *progressive = 0;
-    if (!d || n < 4 || d[0] != 0xFF || d[1] != 0xD8) return 1;
-    size_t i = 2;
-    for (;;) {
-        while (i < n && d[i] != 0xFF) ++i;
-        while (i < n && d[i] == 0xFF) ++i;
-        if (i >= n) return 1;
-        const int m = d[i++];
-        if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
-        if (m == 0xC2 && progressive) *progressive = 1;
-        if (m == 0xD9 || m == 0xDA || (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC)) return 1;
-        if (i + 2 > n) return 1;
-        const int L = be16(d + i);
-        if (L < 2 || i + L > n) return 1;
-        if (m == 0xE1 && L - 2 >= 14 && !memcmp(d + i + 2, "Exif\0\0", 6)) {
-            const int o = exif_orientation(d + i + 8, L - 8);
-            return o > 1 ? o : 1;
-        }
-        i += L;
-    }
-}
 
 // ------------------------------------------------------------ device-side records ----
 struct JpegImageDev {
@@ -580,34 +73,6 @@ struct JpegImageDev {
                                   // whatever follows), in the raw area
 };
 static_assert(sizeof(JpegImageDev) % 4 == 0, "record must stay dword aligned");
-
-struct HuffSlow {  // canonical decode data (JPEG spec F.2.2.3) for code lengths 1..16
-    // limit[l - 1]: the canonical code counter after the codes of length l (one past the largest code of
-    // length l, carried over from shorter lengths if there is none).  A bit window's l-bit prefix is
-    // below limit[l - 1] exactly for l >= the code's length, so the length is 1 + the number of l with
-    // prefix >= limit[l - 1]: independent compares, no data-dependent loop.
-    uint32_t limit[16];
-    int32_t valoff[16];  // huffval index of the first code of length l, minus that code
-    uint8_t huffval[256];
-};
-constexpr int SLOW_DW = 96;
-static_assert(sizeof(HuffSlow) == SLOW_DW * 4, "HuffSlow is copied to LDS as dwords");
-static_assert(sizeof(jpeg_prog::Huff) == sizeof(HuffSlow) && offsetof(jpeg_prog::Huff, valoff) == offsetof(HuffSlow, valoff) &&
-              offsetof(jpeg_prog::Huff, huffval) == offsetof(HuffSlow, huffval), "melf_jpeg_prog.h restates HuffSlow");
-
-static void build_huff(const HuffSpec& t, HuffSlow* slow)
-{
-    memset(slow, 0, sizeof(*slow));
-    memcpy(slow->huffval, t.vals, t.nvals);
-    int code = 0, p = 0;
-    for (int l = 1; l <= 16; ++l) {
-        slow->valoff[l - 1] = p - code;
-        p += t.bits[l];
-        code += t.bits[l];
-        slow->limit[l - 1] = (uint32_t)code;
-        code <<= 1;
-    }
-}
 
 // ------------------------------------------------------------ J0: scan cleaning ----
 // The entropy-coded segment without byte stuffing (FF 00 -> FF), fill bytes and RSTn markers, up to the first other marker

@@ -25,6 +25,7 @@
 #include "melf_device.h"
 #include "melf_frame_checks.h"
 #include "melf_internal.h"
+#include "melf_jpeg_parse.h"
 #include "melf_orient_addr.h"
 #include "melf_stage_plan.h"
 #include "melf_threads.h"
@@ -284,11 +285,12 @@ struct melf_ctx {
     uint8_t* d_stage_out = nullptr;
     size_t stage_out_cap = 0;
     JpegWorkspace* jpeg = nullptr;     // created by the first JPEG batch
-    bool jpeg_prog = false;            // melf_ctx_set_jpeg_progressive: progressive files of the header's subset are decoded, not refused
-    bool jpeg_samp = false;            // melf_ctx_set_jpeg_samplings: 4:4:0 and 4:1:1 files are decoded, not refused
-    bool jpeg_multi = false;           // melf_ctx_set_jpeg_multiscan: sequential files of three one-component scans are decoded, not refused
-    bool jpeg_std_tabs = false;        // melf_ctx_set_jpeg_default_tables: a sequential file that leaves Huffman tables 0 / 1 out gets the Annex K ones
-    bool jpeg_cut = false;             // melf_ctx_set_jpeg_truncated: a baseline file that ends inside its scan is completed as libjpeg completes it, not refused
+    // The JPEG switches, one bit each (melf_ctx_set_jpeg_*): what the context's decode calls take instead of refusing it.
+    // MELF_JPEG_TAKE_ORIENTED: files with an EXIF orientation 2..8; _PROGRESSIVE: progressive files of the header's subset; _SAMPLINGS:
+    // 4:4:0 and 4:1:1 files; _MULTISCAN: sequential files of three one-component scans; _DEFAULT_TABLES: a sequential file that leaves
+    // Huffman tables 0 / 1 out gets the Annex K ones; JPEG_TAKE_TRUNCATED_INTERNAL: a baseline file that ends inside its scan is
+    // completed as libjpeg completes it
+    int jpeg_take_bits = 0;
     std::atomic<int64_t> jpeg_cut_files{0};   // files completed that way since the last reset (melf_ctx_jpeg_truncated_files)
     // a file's status from the parser's and the Huffman stage's: JPEG_ST_CUT is a file completed under the rule -- 0, and counted
     int32_t jpeg_file_status(const int32_t host, const int32_t dev)
@@ -297,13 +299,7 @@ struct melf_ctx {
         if (dev == JPEG_ST_CUT) { jpeg_cut_files.fetch_add(1, std::memory_order_relaxed); return MELF_JPEG_OK; }
         return dev ? MELF_JPEG_CORRUPT : MELF_JPEG_OK;
     }
-    int jpeg_take() const
-    {
-        return (jpeg_orient ? MELF_JPEG_TAKE_ORIENTED : 0) | (jpeg_prog ? MELF_JPEG_TAKE_PROGRESSIVE : 0) | (jpeg_samp ? MELF_JPEG_TAKE_SAMPLINGS : 0) |
-               (jpeg_multi ? MELF_JPEG_TAKE_MULTISCAN : 0) | (jpeg_std_tabs ? MELF_JPEG_TAKE_DEFAULT_TABLES : 0) |
-               (jpeg_cut ? JPEG_TAKE_TRUNCATED_INTERNAL : 0);
-    }
-    bool jpeg_orient = false;          // melf_ctx_set_jpeg_orientation: files with an EXIF orientation 2..8 are decoded, not refused
+    int jpeg_take() const { return jpeg_take_bits; }
     // pipelined JPEG path (melf_jpeg_process_batch): a second workspace and decode stream, so that the host prepares chunk
     // k + 1 and its upload runs while chunk k decodes; per-chunk events; the files' decode status in pinned memory
     static const int NJ = 4;           // workspaces in the ring (a 1024-file call in 256-file chunks never waits for one)
@@ -896,95 +892,32 @@ extern "C" int melf_ctx_set_frames_resident(melf_ctx* c, int on)
     return MELF_SUCCESS;
 }
 
-extern "C" int melf_ctx_set_jpeg_orientation(melf_ctx* c, int on)
+// The JPEG switches (melf_ctx::jpeg_take_bits): `who` is the exported function, for the message.
+static int set_jpeg_switch(melf_ctx* c, const int bit, const int on, const char* who)
 {
     if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    if (!c->files_jobs.empty()) return fail(MELF_ERR_INVALID, "melf_ctx_set_jpeg_orientation while a melf_jpeg_process_files_begin call is in flight");
-    c->jpeg_orient = on != 0;
+    if (!c->files_jobs.empty()) return fail(MELF_ERR_INVALID, std::string(who) + " while a melf_jpeg_process_files_begin call is in flight");
+    c->jpeg_take_bits = on ? c->jpeg_take_bits | bit : c->jpeg_take_bits & ~bit;
     return MELF_SUCCESS;
 }
-
-extern "C" int melf_ctx_get_jpeg_orientation(melf_ctx* c, int* on)
+static int get_jpeg_switch(const melf_ctx* c, const int bit, int* on)
 {
     if (!c || !on) return fail(MELF_ERR_INVALID, "bad argument");
-    *on = c->jpeg_orient ? 1 : 0;
+    *on = c->jpeg_take_bits & bit ? 1 : 0;
     return MELF_SUCCESS;
 }
-
-extern "C" int melf_ctx_set_jpeg_progressive(melf_ctx* c, int on)
-{
-    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    if (!c->files_jobs.empty()) return fail(MELF_ERR_INVALID, "melf_ctx_set_jpeg_progressive while a melf_jpeg_process_files_begin call is in flight");
-    c->jpeg_prog = on != 0;
-    return MELF_SUCCESS;
-}
-
-extern "C" int melf_ctx_get_jpeg_progressive(melf_ctx* c, int* on)
-{
-    if (!c || !on) return fail(MELF_ERR_INVALID, "bad argument");
-    *on = c->jpeg_prog ? 1 : 0;
-    return MELF_SUCCESS;
-}
-
-extern "C" int melf_ctx_set_jpeg_samplings(melf_ctx* c, int on)
-{
-    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    if (!c->files_jobs.empty()) return fail(MELF_ERR_INVALID, "melf_ctx_set_jpeg_samplings while a melf_jpeg_process_files_begin call is in flight");
-    c->jpeg_samp = on != 0;
-    return MELF_SUCCESS;
-}
-
-extern "C" int melf_ctx_get_jpeg_samplings(melf_ctx* c, int* on)
-{
-    if (!c || !on) return fail(MELF_ERR_INVALID, "bad argument");
-    *on = c->jpeg_samp ? 1 : 0;
-    return MELF_SUCCESS;
-}
-
-extern "C" int melf_ctx_set_jpeg_multiscan(melf_ctx* c, int on)
-{
-    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    if (!c->files_jobs.empty()) return fail(MELF_ERR_INVALID, "melf_ctx_set_jpeg_multiscan while a melf_jpeg_process_files_begin call is in flight");
-    c->jpeg_multi = on != 0;
-    return MELF_SUCCESS;
-}
-
-extern "C" int melf_ctx_get_jpeg_multiscan(melf_ctx* c, int* on)
-{
-    if (!c || !on) return fail(MELF_ERR_INVALID, "bad argument");
-    *on = c->jpeg_multi ? 1 : 0;
-    return MELF_SUCCESS;
-}
-
-extern "C" int melf_ctx_set_jpeg_default_tables(melf_ctx* c, int on)
-{
-    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    if (!c->files_jobs.empty()) return fail(MELF_ERR_INVALID, "melf_ctx_set_jpeg_default_tables while a melf_jpeg_process_files_begin call is in flight");
-    c->jpeg_std_tabs = on != 0;
-    return MELF_SUCCESS;
-}
-
-extern "C" int melf_ctx_get_jpeg_default_tables(melf_ctx* c, int* on)
-{
-    if (!c || !on) return fail(MELF_ERR_INVALID, "bad argument");
-    *on = c->jpeg_std_tabs ? 1 : 0;
-    return MELF_SUCCESS;
-}
-
-extern "C" int melf_ctx_set_jpeg_truncated(melf_ctx* c, int on)
-{
-    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
-    if (!c->files_jobs.empty()) return fail(MELF_ERR_INVALID, "melf_ctx_set_jpeg_truncated while a melf_jpeg_process_files_begin call is in flight");
-    c->jpeg_cut = on != 0;
-    return MELF_SUCCESS;
-}
-
-extern "C" int melf_ctx_get_jpeg_truncated(melf_ctx* c, int* on)
-{
-    if (!c || !on) return fail(MELF_ERR_INVALID, "bad argument");
-    *on = c->jpeg_cut ? 1 : 0;
-    return MELF_SUCCESS;
-}
+extern "C" int melf_ctx_set_jpeg_orientation(melf_ctx* c, int on) { return set_jpeg_switch(c, MELF_JPEG_TAKE_ORIENTED, on, __func__); }
+extern "C" int melf_ctx_get_jpeg_orientation(melf_ctx* c, int* on) { return get_jpeg_switch(c, MELF_JPEG_TAKE_ORIENTED, on); }
+extern "C" int melf_ctx_set_jpeg_progressive(melf_ctx* c, int on) { return set_jpeg_switch(c, MELF_JPEG_TAKE_PROGRESSIVE, on, __func__); }
+extern "C" int melf_ctx_get_jpeg_progressive(melf_ctx* c, int* on) { return get_jpeg_switch(c, MELF_JPEG_TAKE_PROGRESSIVE, on); }
+extern "C" int melf_ctx_set_jpeg_samplings(melf_ctx* c, int on) { return set_jpeg_switch(c, MELF_JPEG_TAKE_SAMPLINGS, on, __func__); }
+extern "C" int melf_ctx_get_jpeg_samplings(melf_ctx* c, int* on) { return get_jpeg_switch(c, MELF_JPEG_TAKE_SAMPLINGS, on); }
+extern "C" int melf_ctx_set_jpeg_multiscan(melf_ctx* c, int on) { return set_jpeg_switch(c, MELF_JPEG_TAKE_MULTISCAN, on, __func__); }
+extern "C" int melf_ctx_get_jpeg_multiscan(melf_ctx* c, int* on) { return get_jpeg_switch(c, MELF_JPEG_TAKE_MULTISCAN, on); }
+extern "C" int melf_ctx_set_jpeg_default_tables(melf_ctx* c, int on) { return set_jpeg_switch(c, MELF_JPEG_TAKE_DEFAULT_TABLES, on, __func__); }
+extern "C" int melf_ctx_get_jpeg_default_tables(melf_ctx* c, int* on) { return get_jpeg_switch(c, MELF_JPEG_TAKE_DEFAULT_TABLES, on); }
+extern "C" int melf_ctx_set_jpeg_truncated(melf_ctx* c, int on) { return set_jpeg_switch(c, JPEG_TAKE_TRUNCATED_INTERNAL, on, __func__); }
+extern "C" int melf_ctx_get_jpeg_truncated(melf_ctx* c, int* on) { return get_jpeg_switch(c, JPEG_TAKE_TRUNCATED_INTERNAL, on); }
 
 extern "C" int melf_ctx_jpeg_truncated_files(const melf_ctx* c, int64_t* files, int reset)
 {
@@ -2339,75 +2272,68 @@ extern "C" int melf_inrange(melf_ctx* c, const uint8_t* img_host, int rows, int 
 }
 
 // ------------------------------------------------------------ JPEG decode ----
+// The six probes: one file (its reason goes to the thread's error text) or a batch of them (a NULL or empty entry answers 0 x 0,
+// orientation 1, unsupported); `orientation` is NULL in the forms that do not report one, report_tag as jpeg_probe_flags has it.
+static int probe_file(const uint8_t* data, size_t size, int flags, bool report_tag, int32_t* H, int32_t* W, int32_t* orientation, int32_t* supported)
+{
+    int h = 0, w = 0, o = 1, ok = 0;
+    std::string why;
+    jpeg_probe_flags(data, size, flags, report_tag, &h, &w, &o, &ok, &why);
+    *H = h; *W = w; *supported = ok;
+    if (orientation) *orientation = o;
+    g_err = why;
+    return MELF_SUCCESS;
+}
+static int probe_batch(const uint8_t* const* data, const size_t* sizes, int n, int flags, bool report_tag, int32_t* H, int32_t* W,
+                       int32_t* orientation, int32_t* supported)
+{
+    for (int i = 0; i < n; ++i) {
+        int h = 0, w = 0, o = 1, ok = 0;
+        if (data[i] && sizes[i]) jpeg_probe_flags(data[i], sizes[i], flags, report_tag, &h, &w, &o, &ok, nullptr);
+        H[i] = h; W[i] = w; supported[i] = ok;
+        if (orientation) orientation[i] = o;
+    }
+    return MELF_SUCCESS;
+}
+
 extern "C" int melf_jpeg_probe(const uint8_t* data, size_t size, int32_t* H, int32_t* W, int32_t* supported)
 {
     if (!data || !H || !W || !supported) return fail(MELF_ERR_INVALID, "bad argument");
-    int h = 0, w = 0, ok = 0;
-    std::string why;
-    jpeg_probe(data, size, &h, &w, &ok, &why);
-    *H = h; *W = w; *supported = ok;
-    g_err = why;
-    return MELF_SUCCESS;
+    return probe_file(data, size, 0, false, H, W, nullptr, supported);
 }
 
 extern "C" int melf_jpeg_probe_oriented(const uint8_t* data, size_t size, int32_t* H, int32_t* W, int32_t* orientation, int32_t* supported)
 {
     if (!data || !H || !W || !orientation || !supported) return fail(MELF_ERR_INVALID, "bad argument");
-    int h = 0, w = 0, o = 1, ok = 0;
-    std::string why;
-    jpeg_probe_oriented(data, size, &h, &w, &o, &ok, &why);
-    *H = h; *W = w; *orientation = o; *supported = ok;
-    g_err = why;
-    return MELF_SUCCESS;
+    return probe_file(data, size, TAKE_ORIENTED, false, H, W, orientation, supported);
 }
 
 extern "C" int melf_jpeg_probe_oriented_batch(const uint8_t* const* data, const size_t* sizes, int n, int32_t* H, int32_t* W,
                                               int32_t* orientation, int32_t* supported)
 {
     if (n < 0 || (n > 0 && (!data || !sizes || !H || !W || !orientation || !supported))) return fail(MELF_ERR_INVALID, "bad argument");
-    for (int i = 0; i < n; ++i) {
-        int h = 0, w = 0, o = 1, ok = 0;
-        if (data[i] && sizes[i]) jpeg_probe_oriented(data[i], sizes[i], &h, &w, &o, &ok, nullptr);
-        H[i] = h; W[i] = w; orientation[i] = o; supported[i] = ok;
-    }
-    return MELF_SUCCESS;
+    return probe_batch(data, sizes, n, TAKE_ORIENTED, false, H, W, orientation, supported);
 }
 
 extern "C" int melf_jpeg_probe_flags(const uint8_t* data, size_t size, int flags, int32_t* H, int32_t* W, int32_t* orientation, int32_t* supported)
 {
-    if (!data || !H || !W || !orientation || !supported || (flags & ~(MELF_JPEG_TAKE_ORIENTED | MELF_JPEG_TAKE_PROGRESSIVE | MELF_JPEG_TAKE_SAMPLINGS | MELF_JPEG_TAKE_MULTISCAN | MELF_JPEG_TAKE_DEFAULT_TABLES)))
-        return fail(MELF_ERR_INVALID, "bad argument");
-    int h = 0, w = 0, o = 1, ok = 0;
-    std::string why;
-    jpeg_probe_flags(data, size, flags, &h, &w, &o, &ok, &why);
-    *H = h; *W = w; *orientation = o; *supported = ok;
-    g_err = why;
-    return MELF_SUCCESS;
+    if (!data || !H || !W || !orientation || !supported || (flags & ~TAKE_PROBE_FLAGS)) return fail(MELF_ERR_INVALID, "bad argument");
+    return probe_file(data, size, flags, true, H, W, orientation, supported);
 }
 
 extern "C" int melf_jpeg_probe_flags_batch(const uint8_t* const* data, const size_t* sizes, int n, int flags, int32_t* H, int32_t* W,
                                            int32_t* orientation, int32_t* supported)
 {
-    if (n < 0 || (n > 0 && (!data || !sizes || !H || !W || !orientation || !supported)) || (flags & ~(MELF_JPEG_TAKE_ORIENTED | MELF_JPEG_TAKE_PROGRESSIVE | MELF_JPEG_TAKE_SAMPLINGS | MELF_JPEG_TAKE_MULTISCAN | MELF_JPEG_TAKE_DEFAULT_TABLES)))
+    if (n < 0 || (n > 0 && (!data || !sizes || !H || !W || !orientation || !supported)) || (flags & ~TAKE_PROBE_FLAGS))
         return fail(MELF_ERR_INVALID, "bad argument");
-    for (int i = 0; i < n; ++i) {
-        int h = 0, w = 0, o = 1, ok = 0;
-        if (data[i] && sizes[i]) jpeg_probe_flags(data[i], sizes[i], flags, &h, &w, &o, &ok, nullptr);
-        H[i] = h; W[i] = w; orientation[i] = o; supported[i] = ok;
-    }
-    return MELF_SUCCESS;
+    return probe_batch(data, sizes, n, flags, true, H, W, orientation, supported);
 }
 
 extern "C" int melf_jpeg_probe_batch(const uint8_t* const* data, const size_t* sizes, int n, int32_t* H, int32_t* W,
                                      int32_t* supported)
 {
     if (n < 0 || (n > 0 && (!data || !sizes || !H || !W || !supported))) return fail(MELF_ERR_INVALID, "bad argument");
-    for (int i = 0; i < n; ++i) {
-        int h = 0, w = 0, ok = 0;
-        if (data[i] && sizes[i]) jpeg_probe(data[i], sizes[i], &h, &w, &ok, nullptr);
-        H[i] = h; W[i] = w; supported[i] = ok;
-    }
-    return MELF_SUCCESS;
+    return probe_batch(data, sizes, n, 0, false, H, W, nullptr, supported);
 }
 
 namespace {
@@ -2642,7 +2568,8 @@ static int jpeg_process_batch_from(melf_ctx* c, const uint8_t* const* data, cons
     JpegSource psrc;
     std::vector<uint8_t> code;
     bool oriented = false;
-    if (c->jpeg_orient || c->jpeg_prog) {   // progressive files (melf_ctx_set_jpeg_progressive) form runs of their own too: 16 + their code
+    const bool take_orient = (c->jpeg_take_bits & MELF_JPEG_TAKE_ORIENTED) != 0, take_prog = (c->jpeg_take_bits & MELF_JPEG_TAKE_PROGRESSIVE) != 0;
+    if (take_orient || take_prog) {   // progressive files (melf_ctx_set_jpeg_progressive) form runs of their own too: 16 + their code
         code.resize(n);
         for (int i = 0; i < n; ++i) {
             int prog = 0, o = 1;
@@ -2653,7 +2580,7 @@ static int jpeg_process_batch_from(melf_ctx* c, const uint8_t* const* data, cons
             } else {
                 o = jpeg_file_orientation(data[i], sizes[i], &prog);
             }
-            code[i] = (uint8_t)((c->jpeg_orient ? o : 1) + (c->jpeg_prog && prog ? 16 : 0));
+            code[i] = (uint8_t)((take_orient ? o : 1) + (take_prog && prog ? 16 : 0));
             oriented = oriented || code[i] != 1;
         }
     }

@@ -221,13 +221,7 @@ void launch_inrange3(const uint8_t* d_img, int npx, const int lo[3], const int h
 
 // ---- k_jpeg.hip: baseline JPEG decode ----
 struct JpegWorkspace;
-int jpeg_probe(const uint8_t* data, size_t size, int* H, int* W, int* supported, std::string* why);
-// EXIF orientation (melf_ctx_set_jpeg_orientation): the probe that takes the tag (stored size, code 1..8, supported apart from the
-// tag), and the tag alone from a walk over the segments in front of the frame header
-int jpeg_probe_oriented(const uint8_t* data, size_t size, int* H, int* W, int* orientation, int* supported, std::string* why);
-int jpeg_file_orientation(const uint8_t* data, size_t size, int* progressive = nullptr);   // *progressive: the frame header is SOF2
-// What the decode calls answer from the headers with the switches `flags` (MELF_JPEG_TAKE_* of include/meterelf_hip.h) on
-int jpeg_probe_flags(const uint8_t* data, size_t size, int flags, int* H, int* W, int* orientation, int* supported, std::string* why);
+// (the header parser, the probes and jpeg_file_orientation: melf_jpeg_parse.h, host-only and inline)
 // Headers (and, when asked for, the Huffman decode data built from them) of n files, parsed file by file, from any thread (one
 // thread per index): the file-name entry points parse a file right after reading it, on the thread that read it, and build its
 // decode tables there too
@@ -258,9 +252,8 @@ int jpeg_decode_batch_kernels(JpegWorkspace* ws, int n, int H, int W, uint8_t* d
                               void (*timer)(void*, int, int), void* timer_arg, const int* rect);
 const int32_t* jpeg_device_status(const JpegWorkspace* ws);
 // Files that end early (melf_ctx_set_jpeg_truncated).  The switch travels with the MELF_JPEG_TAKE_* flags of a batch as a bit of its own
-// that no probe takes (truncation does not show in the headers); the Huffman stage reports a file it completed under the rule of
+// (JPEG_TAKE_TRUNCATED_INTERNAL, melf_jpeg_parse.h); the Huffman stage reports a file it completed under the rule of
 // melf_jpeg_cut.h with JPEG_ST_CUT in the device status array, which the later stages treat as 0 and the host maps to 0 and counts.
-constexpr int JPEG_TAKE_TRUNCATED_INTERNAL = 256;
 constexpr int32_t JPEG_ST_CUT = 3;
 void jpeg_workspace_free(JpegWorkspace* ws);
 

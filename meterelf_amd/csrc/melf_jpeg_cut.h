@@ -30,7 +30,7 @@
 namespace melf {
 namespace jpeg_cut {
 
-struct Huff {   // restates HuffSlow (k_jpeg.hip): canonical decode data for code lengths 1..16
+struct Huff {   // restates HuffSlow (melf_jpeg_parse.h): canonical decode data for code lengths 1..16
     uint32_t limit[16];
     int32_t valoff[16];
     uint8_t huffval[256];

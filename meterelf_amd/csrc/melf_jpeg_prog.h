@@ -47,7 +47,7 @@ namespace jpeg_prog {
 
 constexpr int NO_TABLE = 255;
 
-// Canonical Huffman decode data (T.81 F.2.2.3), the layout of k_jpeg.hip's HuffSlow: limit[l - 1] is the code counter after the
+// Canonical Huffman decode data (T.81 F.2.2.3), the layout of melf_jpeg_parse.h's HuffSlow: limit[l - 1] is the code counter after the
 // codes of length l (one past the largest l-bit code), valoff[l - 1] the value index of the first l-bit code minus that code.
 struct Huff {
     uint32_t limit[16];

@@ -371,7 +371,7 @@ def reencode(p, grids):
 
 # ------------------------------------------------------------------ the host program's cases ----
 def huff_slow(spec):
-    """build_huff of k_jpeg.hip: (limit[16], valoff[16], huffval[256])."""
+    """build_huff of melf_jpeg_parse.h: (limit[16], valoff[16], huffval[256])."""
     (limit, valoff) = ([], [])
     (code, k) = (0, 0)
     for l in range(1, 17):

@@ -164,12 +164,12 @@ def test_get_meter_values_asks_for_the_switch_unless_the_host_is_asked_for(monke
         def set_jpeg_default_tables(self, on):
             self.jpeg_default_tables = bool(on)
     monkeypatch.delenv('METERELF_JPEG_TABLES', raising=False)
-    assert _api._jpeg_default_tables_on_gpu() and _api._with_jpeg_orientation(Reader()).jpeg_default_tables
+    assert _api._jpeg_on_gpu('jpeg_default_tables') and _api._with_jpeg_orientation(Reader()).jpeg_default_tables
     params = _params.load(PFILE)
     blob = _engine.make_blob(params)
     k_gpu = _api._reader_key(params, blob, 0)
     monkeypatch.setenv('METERELF_JPEG_TABLES', 'host')
-    assert not _api._jpeg_default_tables_on_gpu() and not _api._with_jpeg_orientation(Reader()).jpeg_default_tables
+    assert not _api._jpeg_on_gpu('jpeg_default_tables') and not _api._with_jpeg_orientation(Reader()).jpeg_default_tables
     assert _api._reader_key(params, blob, 0) != k_gpu                  # a reader made under one setting is never handed out under the other
     monkeypatch.setenv('METERELF_JPEG_TABLES', 'gpu')
     assert _api._reader_key(params, blob, 0) == k_gpu

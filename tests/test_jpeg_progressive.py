@@ -335,11 +335,11 @@ def test_get_meter_values_leaves_progressive_files_to_the_host_unless_asked(monk
         def set_jpeg_orientation(self, on):
             self.jpeg_orientation = bool(on)
     monkeypatch.delenv('METERELF_JPEG_PROGRESSIVE', raising=False)
-    assert not _api._jpeg_progressive_on_gpu() and not _api._with_jpeg_orientation(Reader()).jpeg_progressive
+    assert not _api._jpeg_on_gpu('jpeg_progressive') and not _api._with_jpeg_orientation(Reader()).jpeg_progressive
     monkeypatch.setenv('METERELF_JPEG_PROGRESSIVE', 'host')
     assert not _api._with_jpeg_orientation(Reader()).jpeg_progressive
     monkeypatch.setenv('METERELF_JPEG_PROGRESSIVE', 'gpu')
-    assert _api._jpeg_progressive_on_gpu() and _api._with_jpeg_orientation(Reader()).jpeg_progressive
+    assert _api._jpeg_on_gpu('jpeg_progressive') and _api._with_jpeg_orientation(Reader()).jpeg_progressive
 
 
 def test_probe_survives_mutated_progressive_headers():

@@ -176,12 +176,12 @@ def test_get_meter_values_asks_for_the_switch_unless_the_host_is_asked_for(monke
         def set_jpeg_samplings(self, on):
             self.jpeg_samplings = bool(on)
     monkeypatch.delenv('METERELF_JPEG_SAMPLING', raising=False)
-    assert _api._jpeg_samplings_on_gpu() and _api._with_jpeg_orientation(Reader()).jpeg_samplings
+    assert _api._jpeg_on_gpu('jpeg_samplings') and _api._with_jpeg_orientation(Reader()).jpeg_samplings
     params = _params.load(PFILES['sample-images1'])
     blob = _engine.make_blob(params)
     k_gpu = _api._reader_key(params, blob, 0)
     monkeypatch.setenv('METERELF_JPEG_SAMPLING', 'host')
-    assert not _api._jpeg_samplings_on_gpu() and not _api._with_jpeg_orientation(Reader()).jpeg_samplings
+    assert not _api._jpeg_on_gpu('jpeg_samplings') and not _api._with_jpeg_orientation(Reader()).jpeg_samplings
     assert _api._reader_key(params, blob, 0) != k_gpu                  # a reader made under one setting is never handed out under the other
     monkeypatch.setenv('METERELF_JPEG_SAMPLING', 'gpu')
     assert _api._reader_key(params, blob, 0) == k_gpu

@@ -196,14 +196,14 @@ def test_get_meter_values_asks_for_the_switch_unless_the_host_is_asked_for(monke
     params = _params.load(PFILE)
     blob = _engine.make_blob(params)
     k_default = _api._reader_key(params, blob, 0)
-    default_on = _api._jpeg_multiscan_on_gpu()
+    default_on = _api._jpeg_on_gpu('jpeg_multiscan')
     assert default_on
     assert _api._with_jpeg_orientation(Reader()).jpeg_multiscan == default_on
     monkeypatch.setenv('METERELF_JPEG_MULTISCAN', 'host')
-    assert not _api._jpeg_multiscan_on_gpu() and not _api._with_jpeg_orientation(Reader()).jpeg_multiscan
+    assert not _api._jpeg_on_gpu('jpeg_multiscan') and not _api._with_jpeg_orientation(Reader()).jpeg_multiscan
     k_host = _api._reader_key(params, blob, 0)
     monkeypatch.setenv('METERELF_JPEG_MULTISCAN', 'gpu')
-    assert _api._jpeg_multiscan_on_gpu() and _api._with_jpeg_orientation(Reader()).jpeg_multiscan
+    assert _api._jpeg_on_gpu('jpeg_multiscan') and _api._with_jpeg_orientation(Reader()).jpeg_multiscan
     assert _api._reader_key(params, blob, 0) != k_host                 # a reader made under one setting is never handed out under the other
     assert k_default == (_api._reader_key(params, blob, 0) if default_on else k_host)
 

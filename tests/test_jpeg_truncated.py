@@ -167,12 +167,12 @@ def test_get_meter_values_asks_for_the_switch_unless_the_host_is_asked_for(monke
     params = _params.load(PFILE)
     blob = _engine.make_blob(params)
     k_default = _api._reader_key(params, blob, 0)
-    assert _api._jpeg_truncated_on_gpu() and _api._with_jpeg_orientation(Reader()).jpeg_truncated
+    assert _api._jpeg_on_gpu('jpeg_truncated') and _api._with_jpeg_orientation(Reader()).jpeg_truncated
     monkeypatch.setenv('METERELF_JPEG_TRUNCATED', 'host')
-    assert not _api._jpeg_truncated_on_gpu() and not _api._with_jpeg_orientation(Reader()).jpeg_truncated
+    assert not _api._jpeg_on_gpu('jpeg_truncated') and not _api._with_jpeg_orientation(Reader()).jpeg_truncated
     k_host = _api._reader_key(params, blob, 0)
     monkeypatch.setenv('METERELF_JPEG_TRUNCATED', 'gpu')
-    assert _api._jpeg_truncated_on_gpu() and _api._with_jpeg_orientation(Reader()).jpeg_truncated
+    assert _api._jpeg_on_gpu('jpeg_truncated') and _api._with_jpeg_orientation(Reader()).jpeg_truncated
     assert _api._reader_key(params, blob, 0) != k_host and k_default != k_host
 
 

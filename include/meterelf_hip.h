@@ -757,7 +757,8 @@ int melf_process_stream_dev(melf_ctx* ctx, const void* d_frames, int nbatches, s
  * defaults (ISLOW IDCT, fancy upsampling), i.e. what cv2.imread returns: H x W x 3 BGR u8.
  * Per-file status: 0 decoded, 1 valid JPEG outside that subset (decode it on the host instead) -- also a file
  * WITHOUT restart markers whose entropy-coded data exceed 4 MB (the segment-parallel Huffman kernel addresses
- * 1024 segments of at most 32 000 bits; melf_jpeg_probe cannot tell, the decode calls report it) --,
+ * 1024 segments of at most 32 000 bits; melf_jpeg_probe cannot tell, the decode calls report it), unless
+ * melf_ctx_set_jpeg_long_scans is on (below): such a file is then decoded on the GPU as well --,
  * 2 unreadable / corrupt, 3 its size is not H x W.  Frames with a non-zero status are zero-filled. */
 enum { MELF_JPEG_OK = 0, MELF_JPEG_UNSUPPORTED = 1, MELF_JPEG_CORRUPT = 2, MELF_JPEG_SIZE_MISMATCH = 3,
        MELF_JPEG_UNREADABLE = 4 /* melf_jpeg_process_files: the file could not be opened or read */ };
@@ -826,7 +827,7 @@ int melf_ctx_get_jpeg_orientation(melf_ctx* ctx, int* on);
  * scans (the interval counts the MCUs of the scan it applies to -- single blocks in a non-interleaved scan); bytes behind EOI are
  * ignored.  Entropy-coded data that run out before a scan's blocks are done, an RSTn out of sequence or a Huffman code that does not
  * exist give MELF_JPEG_CORRUPT and a zero-filled frame, and so does a file whose bytes end inside a scan.  The 4 MB limit of
- * restart-less baseline scans does not apply.
+ * restart-less baseline scans (lifted for those by melf_ctx_set_jpeg_long_scans, below) never applied to progressive files.
  * Semantics, bit for bit: the frame libjpeg(-turbo) decodes from the file with its defaults.  Every scan is accumulated into the
  * coefficient blocks (k_jpeg_prog_scan, melf_jpeg_prog.h; timed as MELF_K_JPEG_HUFF): one wave per (file, scan, restart interval),
  * one launch per LEVEL of scans -- a scan's level is one more than the highest level of the earlier scans that send a coefficient it
@@ -987,6 +988,38 @@ int melf_ctx_get_jpeg_default_tables(melf_ctx* ctx, int* on);
 int melf_ctx_set_jpeg_truncated(melf_ctx* ctx, int on);
 int melf_ctx_get_jpeg_truncated(melf_ctx* ctx, int* on);
 int melf_ctx_jpeg_truncated_files(const melf_ctx* ctx, int64_t* files, int reset);
+
+/* ---- Baseline JPEG files with scans beyond 4 MB: 12 MP and larger snapshots at high quality ----
+ * k_jpeg_huff gives each of its 1024 lanes one segment of at most 32 000 bits of the stream, so by default a file WITHOUT restart
+ * markers whose entropy-coded data exceed 4 MB gets status 1 from every decode call; none of that changes.
+ * melf_ctx_set_jpeg_long_scans(ctx, 1, 0) makes melf_jpeg_decode_batch, melf_jpeg_process_batch, melf_jpeg_process_files and
+ * melf_jpeg_process_files_begin / _end of that context decode such a file on the GPU, byte for byte like libjpeg, up to 532 774 904
+ * bytes of entropy-coded data (where 32-bit bit positions end: meterelf_amd/csrc/melf_jpeg_long.h has the derivation); longer scans
+ * keep status 1.  Off at context creation; with it off every JPEG entry point behaves exactly as before, status codes, melf_last_error
+ * texts and launches included.  Not while a _begin call is in flight.  Independent of the other switches; no probe knows it (whether
+ * a scan is long does not show in what the probes report).
+ * How: such a file's record is of a kind of its own, which k_jpeg_huff and k_jpeg_huff_rst pass by, and k_jpeg_chapters (timed as
+ * MELF_K_JPEG_HUFF; launched only for runs of files that hold one) cuts its scan into consecutive chapters of 1024 segments and takes
+ * them in order, each through k_jpeg_huff's three phases.  The first segment of a chapter starts from the settled exit state of the
+ * chapter before, which is exact; the block count and the DC predictors carry over.  The loop ends after the chapter that holds the end
+ * of the meter_rect window (melf_jpeg_process_batch and the file-name calls), or after the last chapter.
+ * chapter_bytes = 0 is production: scans up to 4 MB take the ordinary kernels as ever, longer ones chapters of 4 091 904 bytes (999
+ * dwords a segment, the most the kernel addresses).  chapter_bytes > 0 is for tests and tuning: every restart-less baseline scan
+ * longer than one chapter takes k_jpeg_chapters, with chapters of that length rounded up to 4096 x an odd number of bytes, at least
+ * 36 864 and at most the production length; melf_ctx_get_jpeg_long_scans returns the chapter length in force (4 091 904 in production).  (What the
+ * host compares is the scan's length in the file, stuffing and EOI included; the chapters count the clean bytes.)
+ * chapter_bytes < 0, or a NULL context: MELF_ERR_INVALID.
+ * Measured on one MI355X (profiles/jpeg_long/jpeg_long_rate.txt; noise at quality 100, 4:4:4): melf_jpeg_process_batch on 64 / 256 files
+ * of 4.9 MB (two chapters) takes 18.4 / 111 ms a call, on 64 / 256 files of 10.5 MB (three chapters) 29.9 / 277 ms -- 10.8 / 16.6 and
+ * 12.6 / 18.4 ms of that in k_jpeg_chapters, the rest the staging copy and upload of 0.3 - 2.7 GB -- where the host branch such files
+ * took (Pillow on 8 threads, then the batch read) takes 257 / 955 and 628 / 2141 ms.  A 256-name list of 640 x 480 camera files with
+ * 1 / 8 / 32 files of 4.9 MB among them takes 9.3 / 11.8 / 19.4 ms against 22.5 / 32.3 / 121 ms with those files through the host
+ * branch.  Files the ordinary kernels take run at the rate they had (2.03 against 2.10 ms a 1024-file call, inside the spread).
+ * Out of scope: files with restart intervals and progressive files, which have no such limit; a component scan beyond 4 MB of a
+ * multi-scan file, which stays status 1; a long file that runs out of data is MELF_JPEG_CORRUPT whether or not
+ * melf_ctx_set_jpeg_truncated is on. */
+int melf_ctx_set_jpeg_long_scans(melf_ctx* ctx, int on, int chapter_bytes);
+int melf_ctx_get_jpeg_long_scans(melf_ctx* ctx, int* on, int* chapter_bytes);
 /* The header check with switches: *supported is what the decode calls of a context with the switches `flags` (MELF_JPEG_TAKE_*) on
  * would answer from the headers; H and W are the STORED size, *orientation the EXIF code 1..8 whether or not oriented files are
  * taken.  With flags 0 this is melf_jpeg_probe plus the orientation code.  melf_last_error holds the reason of a refusal. */

@@ -41,6 +41,10 @@ METERELF_JPEG_MULTISCAN=host sends them through the host branch instead.
 A baseline file whose bytes stop inside the scan (a snapshot still being written, an upload that lost its connection) is completed on the
 GPU as libjpeg completes it, byte for byte the frame the host branch decodes (MeterReader's jpeg_truncated switch);
 METERELF_JPEG_TRUNCATED=host sends such files through the host branch instead, as before the GPU took them.
+A baseline file without restart markers whose entropy-coded data exceed 4 MB (12 MP and larger snapshots at high quality) is decoded on
+the GPU chapter by chapter (MeterReader's jpeg_long_scans switch); METERELF_JPEG_LONG=host sends such files through the host branch
+instead, as before the GPU took them.  The default follows the measurement (profiles/jpeg_long/jpeg_long_rate.txt): a 256-name list with
+one 4.9 MB file among camera files takes 9.3 ms on the GPU against 22.5 ms with that file through the host branch.
 """
 import collections
 import hashlib
@@ -92,6 +96,9 @@ _ENV_IN_KEY = ('MELF_MATCH', 'MELF_MATCH_LAYOUT', 'MELF_GEN_SHAPE', 'MELF_FORCE_
 #                        less on the GPU than through the host branch (profiles/jpeg_scans/jpeg_scans_rate.txt: 1.22 against 2.85 ms a call)
 #   jpeg_default_tables  files that leave Huffman tables out (Motion-JPEG frames), decoded with the Annex K tables
 #   jpeg_truncated       baseline files that end inside their scan, completed as libjpeg completes them
+#   jpeg_long_scans      baseline files without restart markers whose scan exceeds 4 MB, decoded chapter by chapter -- on by default because
+#                        one such file in a 256-name list costs less on the GPU than through the host branch
+#                        (profiles/jpeg_long/jpeg_long_rate.txt: 9.3 against 22.5 ms), the rule jpeg_multiscan was decided by
 JPEG_SWITCH_ENV = (
     ('jpeg_orientation', 'METERELF_JPEG_ORIENT', 'gpu', b'orient'),
     ('jpeg_progressive', 'METERELF_JPEG_PROGRESSIVE', 'host', b'prog'),
@@ -99,6 +106,7 @@ JPEG_SWITCH_ENV = (
     ('jpeg_multiscan', 'METERELF_JPEG_MULTISCAN', 'gpu', b'scans'),
     ('jpeg_default_tables', 'METERELF_JPEG_TABLES', 'gpu', b'tabs'),
     ('jpeg_truncated', 'METERELF_JPEG_TRUNCATED', 'gpu', b'cut'),
+    ('jpeg_long_scans', 'METERELF_JPEG_LONG', 'gpu', b'long'),
 )
 
 

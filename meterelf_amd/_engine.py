@@ -126,8 +126,12 @@ def records_to_items(records: np.ndarray, ok, dial_names: List[str], filenames: 
 class MeterReader:
     def __init__(self, params: Params, device: int = 0, blob: Optional[np.ndarray] = None, ctx: Optional['_hip.Context'] = None,
                  jpeg_orientation: bool = False, jpeg_progressive: bool = False, jpeg_samplings: bool = False,
-                 jpeg_multiscan: bool = False, jpeg_default_tables: bool = False, jpeg_truncated: bool = False) -> None:
-        """jpeg_truncated: the read_jpeg_* methods complete a baseline JPEG file whose bytes stop inside the scan (a snapshot still being
+                 jpeg_multiscan: bool = False, jpeg_default_tables: bool = False, jpeg_truncated: bool = False,
+                 jpeg_long_scans: bool = False) -> None:
+        """jpeg_long_scans: the read_jpeg_* methods decode baseline JPEG files without restart markers whose entropy-coded data exceed 4 MB
+        (12 MP and larger snapshots at high quality) on the GPU, chapter by chapter, byte for byte like libjpeg, instead of leaving them
+        to the caller's host decoder, which is the default.
+        jpeg_truncated: the read_jpeg_* methods complete a baseline JPEG file whose bytes stop inside the scan (a snapshot still being
         written, an upload that lost its connection) as libjpeg does -- the MCU in progress from zero bits, mid grey behind it -- instead
         of handing it back as undecodable, which is the default.
         jpeg_default_tables: the read_jpeg_* methods decode sequential JPEG files that leave Huffman tables 0 / 1 out (Motion-JPEG frames of
@@ -150,7 +154,8 @@ class MeterReader:
         self._begun: list = []      # read_jpeg_paths_begin: path lists in flight, oldest first
         self._collected: list = []  # their results taken out of the library early (drain_jpeg_paths), oldest first
         asked = dict(jpeg_orientation=jpeg_orientation, jpeg_progressive=jpeg_progressive, jpeg_samplings=jpeg_samplings,
-                     jpeg_multiscan=jpeg_multiscan, jpeg_default_tables=jpeg_default_tables, jpeg_truncated=jpeg_truncated)
+                     jpeg_multiscan=jpeg_multiscan, jpeg_default_tables=jpeg_default_tables, jpeg_truncated=jpeg_truncated,
+                     jpeg_long_scans=jpeg_long_scans)
         for (name, _flag, _doc) in _hip.JPEG_SWITCHES:      # the attribute jpeg_<switch>: what the context was last told
             setattr(self, name, False)
             if asked[name]:
@@ -159,6 +164,12 @@ class MeterReader:
     def _set_jpeg_switch(self, name: str, on: bool) -> None:
         getattr(self.ctx, 'set_' + name)(on)
         setattr(self, name, bool(on))
+
+    def set_jpeg_long_scans(self, on: bool, chapter_bytes: int = 0) -> None:
+        """The switch of the constructor's jpeg_long_scans, on a reader with nothing in flight (melf_ctx_set_jpeg_long_scans);
+        chapter_bytes > 0, for tests and tuning, chooses the chapter length."""
+        self.ctx.set_jpeg_long_scans(on, chapter_bytes)
+        self.jpeg_long_scans = bool(on)
 
     def set_jpeg_truncated(self, on: bool) -> None:
         """The switch of the constructor's jpeg_truncated, on a reader with nothing in flight (melf_ctx_set_jpeg_truncated)."""

@@ -235,6 +235,7 @@ EXPORTS = [
     'melf_ctx_set_jpeg_samplings', 'melf_ctx_get_jpeg_samplings',
     'melf_ctx_set_jpeg_multiscan', 'melf_ctx_get_jpeg_multiscan', 'melf_ctx_set_jpeg_default_tables', 'melf_ctx_get_jpeg_default_tables',
     'melf_ctx_set_jpeg_truncated', 'melf_ctx_get_jpeg_truncated', 'melf_ctx_jpeg_truncated_files',
+    'melf_ctx_set_jpeg_long_scans', 'melf_ctx_get_jpeg_long_scans',
 ]
 
 _lib = None
@@ -328,9 +329,12 @@ def lib():
     L.melf_jpeg_probe_flags.argtypes = [vp, C.c_size_t, C.c_int, i32p, i32p, i32p, i32p]
     L.melf_jpeg_probe_flags_batch.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     for (name, _flag, _doc) in JPEG_SWITCHES:
-        if hasattr(L, 'melf_ctx_set_' + name):   # (tools/jpeg_cut_rate.py loads the library from before melf_ctx_set_jpeg_truncated through MELF_LIB_PATH)
+        if name != 'jpeg_long_scans' and hasattr(L, 'melf_ctx_set_' + name):   # (tools/jpeg_cut_rate.py loads the library from before melf_ctx_set_jpeg_truncated through MELF_LIB_PATH)
             getattr(L, 'melf_ctx_set_' + name).argtypes = [vp, C.c_int]
             getattr(L, 'melf_ctx_get_' + name).argtypes = [vp, C.POINTER(C.c_int)]
+    if hasattr(L, 'melf_ctx_set_jpeg_long_scans'):   # (the one switch with a second argument: the chapter length)
+        L.melf_ctx_set_jpeg_long_scans.argtypes = [vp, C.c_int, C.c_int]
+        L.melf_ctx_get_jpeg_long_scans.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     if hasattr(L, 'melf_ctx_set_jpeg_truncated'):
         L.melf_ctx_jpeg_truncated_files.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
     L.melf_jpeg_decode_batch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp]
@@ -1114,6 +1118,12 @@ JPEG_SWITCHES = (
      """Baseline JPEG files whose bytes stop inside the scan are completed by the jpeg_* calls of this context as libjpeg completes
      them -- the cut MCU from zero bits, mid grey behind it -- instead of coming back corrupt (melf_ctx_set_jpeg_truncated).  Off by
      default."""),
+    ('jpeg_long_scans', None,      # no probe flag either: whether a scan is long does not show in what a probe reports
+     """Baseline JPEG files without restart markers whose entropy-coded data exceed 4 MB (12 MP snapshots at high quality) are
+     decoded by the jpeg_* calls of this context, chapter by chapter, instead of coming back unsupported
+     (melf_ctx_set_jpeg_long_scans).  chapter_bytes: 0 = production (scans up to 4 MB take the ordinary kernels, longer ones the
+     longest chapters the kernel addresses); > 0, for tests and tuning: every restart-less baseline scan longer than one chapter
+     takes the chapter kernel, with chapters of that length rounded up to what the segment rule gives.  Off by default."""),
 )
 
 
@@ -1773,3 +1783,28 @@ def _add_jpeg_switch(name, doc):
 
 for (_name, _flag, _doc) in JPEG_SWITCHES:
     _add_jpeg_switch(_name, _doc)
+
+
+def _set_jpeg_long_scans(self, on, chapter_bytes=0):
+    check(self._L.melf_ctx_set_jpeg_long_scans(self._h, int(bool(on)), int(chapter_bytes)))
+
+
+def _jpeg_long_scans(self):
+    (on, k) = (C.c_int(0), C.c_int(0))
+    check(self._L.melf_ctx_get_jpeg_long_scans(self._h, C.byref(on), C.byref(k)))
+    return bool(on.value)
+
+
+def _jpeg_long_chapter_bytes(self):
+    """The chapter length in force (melf_ctx_get_jpeg_long_scans): 4 091 904 in production."""
+    (on, k) = (C.c_int(0), C.c_int(0))
+    check(self._L.melf_ctx_get_jpeg_long_scans(self._h, C.byref(on), C.byref(k)))
+    return int(k.value)
+
+
+# the one switch with a second argument replaces the generic pair
+_set_jpeg_long_scans.__doc__ = JPEG_SWITCHES[-1][2]
+(_set_jpeg_long_scans.__name__, _jpeg_long_scans.__name__, _jpeg_long_chapter_bytes.__name__) = ('set_jpeg_long_scans', 'jpeg_long_scans', 'jpeg_long_chapter_bytes')
+Context.set_jpeg_long_scans = _set_jpeg_long_scans
+Context.jpeg_long_scans = _jpeg_long_scans
+Context.jpeg_long_chapter_bytes = _jpeg_long_chapter_bytes

@@ -30,6 +30,7 @@
 //                           stored geometry, each pixel written where the upright frame has it
 #include "melf_internal.h"
 #include "melf_jpeg_cut.h"
+#include "melf_jpeg_long.h"
 #include "melf_jpeg_orient_addr.h"
 #include "melf_jpeg_parse.h"
 #include "melf_jpeg_prog.h"
@@ -326,7 +327,8 @@ constexpr uint32_t SYM_MASK = 0x007f001fu;  // bits | adv << 16 of the first sym
 constexpr int TAB_BITS = 10;
 constexpr int LONG_N = 512;  // entries of the long-code table per AC table
 // k_jpeg_huff keeps bit positions inside a segment in 16 bits: segments of at most 32 000 bits, i.e. scans of at most
-// 4 MB with 1024 lanes (2 MB with the usual 512); larger baseline files without restart markers go to the host decoder
+// 4 MB with 1024 lanes (2 MB with the usual 512); larger baseline files without restart markers go to the host decoder,
+// or, in a context with melf_ctx_set_jpeg_long_scans, to k_jpeg_chapters
 constexpr size_t JPEG_MAX_PAR_SCAN = 4000000;
 constexpr uint32_t TAB_MASK = (1u << TAB_BITS) - 1u;
 
@@ -1012,6 +1014,184 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_num_sgpr(80))) void k_jpeg
     if (tid == 0) status[img] = st;
 }
 
+// Scans longer than T segments of the length k_jpeg_huff can address (melf_ctx_set_jpeg_long_scans; records with ok = 5): the scan in
+// CHAPTERS of T segments of S = 32 seg_dw bits (melf_jpeg_long.h has the plan and its bounds).  One workgroup still owns one file and
+// works through the chapters in order; a chapter takes k_jpeg_huff's three phases -- the speculative state-only pass over its
+// segments, the synchronisation rounds, the output pass with the DC prefix sum and fix-up -- with the same two segment decoders.
+// What carries over from chapter to chapter (uniform values, every lane reads them from the LDS arrays before the chapter's last barrier):
+//   c_p, c_s     the entry state of the next chapter's first segment: the settled exit state of this chapter's last one, so it is
+//                EXACT (chapter 0: the stream's first bit).  Segment 0 of a chapter therefore never sees a new entry, after round r
+//                segments 0..r are settled, and the rounds of a chapter end after at most nseg - 1 of them;
+//   c_nb         blocks completed so far: a segment's first block is c_nb + the exclusive prefix of the chapter's counts;
+//   c_pr0..2     the DC predictors: the carried ones + the inclusive end of the chapter's DC-difference sums.
+// The loop ends after the chapter in which the completed blocks reach the window's end (wend), or after the last chapter.  Chapters in
+// front of the window run all three phases (the predictors and block counts come from them); coef_block_ptr filters their stores as
+// ever.  Inside a chapter every segment is settled: no estimated cut.  Loop bounds: nchap chapters, nseg + 1 rounds per chapter.
+// No workgroup waits for another and nothing waits on memory.  A file that runs out of data is corrupt here (no JpegCutRec, no tail).
+template <int T>
+__global__ __launch_bounds__(T) void k_jpeg_chapters(const JpegImageDev* __restrict__ imgs, const HuffSlow* __restrict__ g_slow,
+                                                      const uint8_t* __restrict__ scan, int16_t* __restrict__ coefs,
+                                                      int32_t* __restrict__ status, JpegWindow win, const uint32_t seg_dw)
+{
+    static_assert(T == (int)jpeg_long::T, "the plan's segments per chapter");
+    __shared__ uint32_t tab[4 << TAB_BITS];
+    __shared__ uint32_t longtab[2 * LONG_N];
+    __shared__ uint32_t slow[4 * SLOW_DW];
+    __shared__ uint8_t nat[64];
+    __shared__ uint32_t e_p[T], e_s[T];  // exit state of each segment of the chapter: bit position, blk << 8 | k
+    __shared__ uint32_t n_p[T], n_s[T];  // entry state its last decode started from
+    __shared__ int sc_n[T];              // blocks completed in the segment (then: prefix sums)
+    __shared__ int64_t sc_d[T];          // packed DC-difference sums of the output pass (then: prefix sums)
+    __shared__ uint16_t todo[T];         // segments to decode again this round, compacted
+    __shared__ int wcount[T / 64];
+    const int tid = threadIdx.x;
+    const int img = blockIdx.x;
+    const JpegImageDev* R = imgs + img;
+    if (R->ok != 5) return;
+    const uint32_t* W = (const uint32_t*)(scan + R->scan_off);  // zero-padded by 128 bytes
+    const McuWindow mwin = jpeg_zero_window<T>(R, win, coefs, tid);
+    const uint32_t scan_len = R->scan_len;
+    if (!jpeg_long::taken(scan_len) || seg_dw < jpeg_long::MIN_SEG_DWORDS || seg_dw > jpeg_long::MAX_SEG_DWORDS) {  // (the host sends neither)
+        if (tid == 0) status[img] = 2;
+        return;
+    }
+    const uint32_t bits = scan_len * 8u;
+    const uint32_t S = 32u * seg_dw;
+    const uint32_t nchap = jpeg_long::chapters(bits, seg_dw);
+    {
+        const uint32_t* ssrc = (const uint32_t*)(g_slow + (size_t)img * 4);
+        for (int i = tid; i < 4 * SLOW_DW; i += T) slow[i] = ssrc[i];
+        for (int i = tid; i < 64; i += T) nat[i] = c_zz2nat[i];
+    }
+    __syncthreads();
+    const McuLayout L = jpeg_mcu_layout(R);
+    jpeg_build_tables<T>(tab, longtab, slow, L, tid);
+    const int mcus_x = R->mcus_x;
+    const int total_blocks = mcus_x * (int)R->mcus_y * L.bpm;
+    const CoefBlocks cp = {coefs + (size_t)R->coef_blk[0] * 64, mwin};
+    const int wend = min(total_blocks, mwin.my1 * mcus_x * L.bpm);   // first block behind the window (the frame's end when all is wanted)
+    __syncthreads();
+
+    uint32_t c_p = 0, c_s = 0;
+    int c_nb = 0, c_pr0 = 0, c_pr1 = 0, c_pr2 = 0;
+    int bad = 0, anybad = 0;
+    for (uint32_t chap = 0; chap < nchap; ++chap) {
+        const jpeg_long::Chapter C = jpeg_long::chapter(bits, seg_dw, chap);
+        const int nseg = (int)C.nseg;
+        const bool mine = tid < nseg;
+        const uint32_t p_end = jpeg_long::seg_end(bits, seg_dw, C.bit0, (uint32_t)tid);
+        {   // speculative pass: segment 0 from the carried state, the others from a guess
+            SegState ex = {C.bit0 + (uint32_t)tid * S, 0, 0};
+            if (tid == 0) { ex.p = c_p; ex.blk = (int)(c_s >> 8); ex.k = (int)(c_s & 255u); }
+            n_p[tid] = ex.p;
+            n_s[tid] = (uint32_t)(ex.blk << 8 | ex.k);
+            int nblk = 0;
+            if (mine) jpeg_state_segment(W, tab, longtab, slow, L, ex, p_end, nblk);
+            e_p[tid] = ex.p;
+            e_s[tid] = (uint32_t)(ex.blk << 8 | ex.k);
+            sc_n[tid] = mine ? nblk : 0;
+        }
+        __syncthreads();
+        int round = 0;
+        for (; round <= nseg; ++round) {
+            uint32_t np = 0, ns = 0;
+            if (tid > 0) { np = e_p[tid - 1]; ns = e_s[tid - 1]; }
+            const bool ch = mine && tid > 0 && (np != n_p[tid] || ns != n_s[tid]);
+            const uint64_t bal = __ballot(ch);
+            const int wave = tid >> 6, lane = tid & 63;
+            if (lane == 0) wcount[wave] = __popcll(bal);
+            __syncthreads();
+            int before = 0, total = 0;
+#pragma unroll
+            for (int w = 0; w < T / 64; ++w) {
+                const int c = wcount[w];
+                before += w < wave ? c : 0;
+                total += c;
+            }
+            if (total == 0) break;
+            if (ch) {
+                const int pos = before + __popcll(bal & ((1ull << lane) - 1ull));
+                todo[pos] = (uint16_t)tid;
+                n_p[tid] = np;
+                n_s[tid] = ns;
+            }
+            __syncthreads();
+            for (int q = tid; q < total; q += T) {
+                const int i = todo[q];
+                SegState ex = {n_p[i], (int)(n_s[i] >> 8), (int)(n_s[i] & 255u)};
+                int nblk;
+                jpeg_state_segment(W, tab, longtab, slow, L, ex, jpeg_long::seg_end(bits, seg_dw, C.bit0, (uint32_t)i), nblk);
+                e_p[i] = ex.p;  // nobody reads exit states before the next barrier
+                e_s[i] = (uint32_t)(ex.blk << 8 | ex.k);
+                sc_n[i] = nblk;
+            }
+            __syncthreads();
+        }
+        if (round > nseg) bad = 1;   // (cannot happen: see above; the bound is what ends the loop whatever the stream holds)
+        // exclusive prefix over the segments: blocks completed
+        const int nblk = sc_n[tid];
+        __syncthreads();
+        for (int off = 1; off < T; off <<= 1) {
+            const int a = tid >= off ? sc_n[tid - off] : 0;
+            __syncthreads();
+            sc_n[tid] += a;
+            __syncthreads();
+        }
+        const SegState entry = {n_p[tid], (int)(n_s[tid] >> 8), (int)(n_s[tid] & 255u)};
+        const int nb_in = c_nb + sc_n[tid] - nblk;
+        // output pass: DC predictors starting at zero in every segment, then the prefix sum of the segments' DC-difference sums
+        const bool ran = mine && nb_in < wend;
+        int q0 = 0, q1 = 0, q2 = 0, ndc = 0;
+        if (ran) {
+            if (entry.blk != nb_in % L.bpm) bad = 1;  // the propagated state and the block count disagree: corrupt stream
+            SegState st = entry;
+            int n2;
+            jpeg_decode_segment(W, tab, longtab, slow, nat, L, st, p_end, n2, nb_in, total_blocks, q0, q1, q2, ndc, mcus_x, cp, bad);
+        }
+        const int64_t dsum = (int64_t)q0 + ((int64_t)q1 << 16) + ((int64_t)q2 << 32);
+        sc_d[tid] = dsum;
+        __syncthreads();
+        for (int off = 1; off < T; off <<= 1) {
+            const int64_t b = tid >= off ? sc_d[tid - off] : 0;
+            __syncthreads();
+            sc_d[tid] += b;
+            __syncthreads();
+        }
+        if (ran && ndc > 0) {
+            int pr0, pr1, pr2;
+            unpack_dsum(sc_d[tid] - dsum, pr0, pr1, pr2);  // the chapter's differences in front of the segment
+            pr0 += c_pr0; pr1 += c_pr1; pr2 += c_pr2;      // the predictors at the segment's entry
+            if ((pr0 | pr1 | pr2) != 0) {
+                const int b0 = nb_in + (entry.k != 0 ? 1 : 0);   // the first block that BEGINS here
+                const int mcu = b0 / L.bpm;
+                int blk = b0 - mcu * L.bpm, my = mcu / mcus_x, mx = mcu - (mcu / mcus_x) * mcus_x;
+                for (int i = 0; i < ndc; ++i) {
+                    int16_t* cb = coef_block_ptr(cp, mx, my, b0 + i);
+                    const int comp = (int)((L.comp_bits >> (2 * blk)) & 3u);
+                    if (cb) cb[0] = (int16_t)(cb[0] + (comp == 0 ? pr0 : comp == 1 ? pr1 : pr2));
+                    if (++blk == L.bpm) {
+                        blk = 0;
+                        if (++mx == mcus_x) { mx = 0; ++my; }
+                    }
+                }
+            }
+        }
+        // what the next chapter starts from (read before the barrier; the arrays are rewritten behind it)
+        c_p = e_p[nseg - 1];
+        c_s = e_s[nseg - 1];
+        c_nb += sc_n[T - 1];
+        {
+            int d0, d1, d2;
+            unpack_dsum(sc_d[T - 1], d0, d1, d2);
+            c_pr0 += d0; c_pr1 += d1; c_pr2 += d2;
+        }
+        anybad = __syncthreads_or(bad);
+        if (anybad || c_nb >= wend) break;
+    }
+    // an impossible code or an inconsistent state on the way, or the stream ran out before the window's (the frame's) last block
+    if (tid == 0) status[img] = (anybad || c_nb < wend) ? 2 : 0;
+}
+
 // Streams with restart intervals need no speculation: every interval starts byte aligned with the DC
 // predictors at zero.  One workgroup per image, lanes stride over the intervals (the host recorded where
 // each begins while stripping the markers) and write their coefficients directly.
@@ -1631,6 +1811,8 @@ struct JpegWorkspace {
     int max_blocks = 0;
     int n_par = 0, n_seq = 0;   // images for the segment-parallel / the restart-interval Huffman kernel
     int n_420 = 0;              // three-component 4:2:0 images (fast colour kernel)
+    int n_long = 0;             // images for k_jpeg_chapters (melf_ctx_set_jpeg_long_scans)
+    uint32_t long_dw = 0;       // its segment length in dwords (melf_jpeg_long.h)
     size_t max_par_scan = 0;    // longest clean scan among the former (bytes)
     // The batch as runs of consecutive files of one orientation code: J1..J3 are launched once per run, on the run's window of
     // the stored frame.  A batch without oriented files is one run of code 1 whose counts are the five above.
@@ -1644,6 +1826,7 @@ struct JpegWorkspace {
         size_t prog_coef0 = 0, prog_coefs = 0;
         std::vector<uint32_t> prog_items;
         uint32_t prog_scans = 0;
+        int n_long = 0;   // files for k_jpeg_chapters (ok = 5)
     };
     std::vector<Run> runs;
     // Multi-scan sequential files (melf_jpeg_scans.h): their scans are one-component records of their own behind the batch's n file
@@ -1745,6 +1928,12 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
     if (!*pws) *pws = new JpegWorkspace();
     JpegWorkspace* w = *pws;
     w->cut = (take & TAKE_TRUNCATED) != 0;
+    // long scans (melf_ctx_set_jpeg_long_scans): the segment length of the chapters, and from which raw length on a restart-less
+    // baseline scan is k_jpeg_chapters's -- beyond what k_jpeg_huff addresses, or beyond one chapter where the caller chose a length
+    const bool long_on = (take & TAKE_LONG) != 0;
+    const uint32_t long_choice = ((uint32_t)take >> JPEG_TAKE_LONG_DW_SHIFT) & JPEG_TAKE_LONG_DW_MASK;
+    w->long_dw = long_choice ? long_choice : jpeg_long::MAX_SEG_DWORDS;
+    const size_t long_from = long_choice ? jpeg_long::chapter_bytes(long_choice) : JPEG_MAX_PAR_SCAN;
     static const bool trace = diag_env("MELF_JPEG_TRACE") != nullptr;
     const auto tp0 = std::chrono::steady_clock::now();
     std::vector<JpegHeader> own;
@@ -1997,16 +2186,21 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
         }
         // longer than 1024 lanes x the segment length k_jpeg_huff can address (the raw length: the clean one is only known on
         // the GPU and at most 1/128 shorter)
-        if (!h.restart_interval && r.raw_len > JPEG_MAX_PAR_SCAN) {
-            r.ok = 0;
-            host_status[i] = 1;  // valid, but for the host decoder
+        if (!h.restart_interval && (r.raw_len > JPEG_MAX_PAR_SCAN || (long_on && r.raw_len > long_from))) {
+            // with melf_ctx_set_jpeg_long_scans: a record kind of its own (ok = 5: k_jpeg_chapters's), up to the longest scan
+            // 32-bit bit positions address (melf_jpeg_long.h)
+            if (long_on && jpeg_long::taken(r.raw_len)) r.ok = 5;
+            else {
+                r.ok = 0;
+                host_status[i] = 1;  // valid, but for the host decoder
+            }
         }
     };
     // nothing but two small copies per file left to do: not worth waking the pool (whose threads the file reads of the next
     // call are using)
     if (direct && tables_ready) { for (int i = 0; i < n; ++i) fill(i); }
     else par_for(fill);
-    w->n_par = w->n_seq = w->n_420 = 0;
+    w->n_par = w->n_seq = w->n_420 = w->n_long = 0;
     w->max_par_scan = 0;
     w->runs.clear();
     for (int i = 0; i < n; ++i) {
@@ -2032,6 +2226,7 @@ int jpeg_prepare_batch(JpegWorkspace** pws, const uint8_t* const* data, const si
         }
         if (rec[i].ok == 1) { ++w->n_par; ++run.n_par; w->max_par_scan = std::max(w->max_par_scan, (size_t)rec[i].raw_len); run.max_par_scan = std::max(run.max_par_scan, (size_t)rec[i].raw_len); }
         else if (rec[i].ok == 2) { ++w->n_seq; ++run.n_seq; }
+        else if (rec[i].ok == 5) { ++w->n_long; ++run.n_long; }
         if (rec[i].ok && rec[i].ncomp == 3 && rec[i].hs0 == 2 && rec[i].vs0 == 2) { ++w->n_420; ++run.n_420; }
         int blocks = 0;
         for (int c = 0; c < rec[i].ncomp; ++c) blocks += (int)rec[i].blocks_x[c] * rec[i].blocks_y[c];
@@ -2107,7 +2302,7 @@ int jpeg_decode_batch_kernels(JpegWorkspace* w, int n, int H, int W, uint8_t* d_
     JpegCutRec* const cut0 = w->cut && w->n_par + w->n_seq > 0 ? (JpegCutRec*)w->d_cut : nullptr;
     if (cut0 && w->n_par > 0) JTRY(hipMemsetAsync(cut0, 0, (size_t)n * 2 * sizeof(JpegCutRec), stream));
     if (timer) timer(timer_arg, 0, 0);
-    if (w->n_par + w->n_seq + w->n_scan_recs > 0)   // J0: stuffing, fill bytes and restart markers out of the uploaded segments
+    if (w->n_par + w->n_seq + w->n_long + w->n_scan_recs > 0)   // J0: stuffing, fill bytes and restart markers out of the uploaded segments
         hipLaunchKernelGGL(k_jpeg_clean, dim3(n + w->n_scan_recs), dim3(CLEAN_T), 0, stream, (JpegImageDev*)(w->d_stage + w->off_imgs), w->d_raw, w->d_stage + w->off_scan);
     for (size_t q = 0; q < nruns; ++q) {
         const JpegWorkspace::Run& r = w->runs[q];
@@ -2126,6 +2321,8 @@ int jpeg_decode_batch_kernels(JpegWorkspace* w, int n, int H, int W, uint8_t* d_
         if (r.n_seq > 0) {  // streams with restart intervals: one lane per interval
             hipLaunchKernelGGL(k_jpeg_huff_rst<256>, dim3(r.n), dim3(256), 0, stream, imgs, slow, scan, w->d_coefs, status, win, cutrec ? 1 : 0);
         }
+        if (r.n_long > 0)   // scans beyond k_jpeg_huff's reach, chapter by chapter (only runs that hold one)
+            hipLaunchKernelGGL(k_jpeg_chapters<1024>, dim3(r.n), dim3(1024), 0, stream, imgs, slow, scan, w->d_coefs, status, win, w->long_dw);
         if (cutrec && r.n_par + r.n_seq > 0)   // one wave per file; a file that is not cut leaves at once
             hipLaunchKernelGGL(k_jpeg_cut_tail, dim3(r.n), dim3(64), 0, stream, imgs, slow, scan, w->d_coefs, status, cutrec, win);
         if (r.prog && !r.prog_items.empty()) {

@@ -25,6 +25,7 @@
 #include "melf_device.h"
 #include "melf_frame_checks.h"
 #include "melf_internal.h"
+#include "melf_jpeg_long.h"
 #include "melf_jpeg_parse.h"
 #include "melf_orient_addr.h"
 #include "melf_stage_plan.h"
@@ -918,6 +919,24 @@ extern "C" int melf_ctx_set_jpeg_default_tables(melf_ctx* c, int on) { return se
 extern "C" int melf_ctx_get_jpeg_default_tables(melf_ctx* c, int* on) { return get_jpeg_switch(c, MELF_JPEG_TAKE_DEFAULT_TABLES, on); }
 extern "C" int melf_ctx_set_jpeg_truncated(melf_ctx* c, int on) { return set_jpeg_switch(c, JPEG_TAKE_TRUNCATED_INTERNAL, on, __func__); }
 extern "C" int melf_ctx_get_jpeg_truncated(melf_ctx* c, int* on) { return get_jpeg_switch(c, JPEG_TAKE_TRUNCATED_INTERNAL, on); }
+
+// Long scans: the switch's bit and, beside it, the chapters' segment length in dwords where the caller chose one (melf_jpeg_long.h)
+extern "C" int melf_ctx_set_jpeg_long_scans(melf_ctx* c, int on, int chapter_bytes)
+{
+    if (c && chapter_bytes < 0) return fail(MELF_ERR_INVALID, "melf_ctx_set_jpeg_long_scans: chapter_bytes is negative");
+    if (int rc = set_jpeg_switch(c, JPEG_TAKE_LONG_INTERNAL, on, __func__)) return rc;
+    const int dw = chapter_bytes > 0 ? (int)jpeg_long::seg_dwords((uint64_t)chapter_bytes) : 0;
+    c->jpeg_take_bits = (c->jpeg_take_bits & ~((int)JPEG_TAKE_LONG_DW_MASK << JPEG_TAKE_LONG_DW_SHIFT)) | dw << JPEG_TAKE_LONG_DW_SHIFT;
+    return MELF_SUCCESS;
+}
+extern "C" int melf_ctx_get_jpeg_long_scans(melf_ctx* c, int* on, int* chapter_bytes)
+{
+    if (!chapter_bytes) return fail(MELF_ERR_INVALID, "bad argument");
+    if (int rc = get_jpeg_switch(c, JPEG_TAKE_LONG_INTERNAL, on)) return rc;
+    const uint32_t dw = ((uint32_t)c->jpeg_take_bits >> JPEG_TAKE_LONG_DW_SHIFT) & JPEG_TAKE_LONG_DW_MASK;
+    *chapter_bytes = (int)jpeg_long::chapter_bytes(dw ? dw : jpeg_long::MAX_SEG_DWORDS);
+    return MELF_SUCCESS;
+}
 
 extern "C" int melf_ctx_jpeg_truncated_files(const melf_ctx* c, int64_t* files, int reset)
 {

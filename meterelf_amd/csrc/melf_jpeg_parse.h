@@ -76,6 +76,13 @@ constexpr int TAKE_PROBE_FLAGS = TAKE_ORIENTED | TAKE_PROGRESSIVE | TAKE_SAMPLIN
 constexpr int JPEG_TAKE_TRUNCATED_INTERNAL = 256;
 constexpr int TAKE_TRUNCATED = JPEG_TAKE_TRUNCATED_INTERNAL;
 static_assert((TAKE_PROBE_FLAGS & TAKE_TRUNCATED) == 0 && TAKE_PROBE_FLAGS == 55, "the switches' bits");
+// Long scans (melf_ctx_set_jpeg_long_scans): an internal bit too -- whether a scan is long does not show in what a probe reports -- and
+// beside it the segment length a caller chose for the chapters, in dwords (melf_jpeg_long.h; 0: the production length).
+constexpr int JPEG_TAKE_LONG_INTERNAL = 512;
+constexpr int TAKE_LONG = JPEG_TAKE_LONG_INTERNAL;
+constexpr int JPEG_TAKE_LONG_DW_SHIFT = 16;
+constexpr uint32_t JPEG_TAKE_LONG_DW_MASK = 1023u;
+static_assert((TAKE_PROBE_FLAGS & TAKE_LONG) == 0 && (TAKE_TRUNCATED & TAKE_LONG) == 0, "the switches' bits");
 
 // What the parser keeps while it goes through a progressive file's scans (T.81 G.1.1.1.1 and libjpeg's progressive decoder).
 struct ProgState {

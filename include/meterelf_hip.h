@@ -509,6 +509,78 @@ int melf_process_planes(melf_ctx* ctx, const void* frames_host, const melf_plana
 int melf_process_planes_dev(melf_ctx* ctx, const void* d_frames, const melf_planar_frames* f, void* d_results, melf_result* out_host,
                             void* stream);
 
+/* ---- the same path for RGB frames of WIDE samples: 16-bit words (RGB16 / BGR12 of machine-vision SDKs, ffmpeg's rgb48le, bgra64le,
+ * gbrp10le / gbrp12le / gbrp16le, decoded 16-bit PNG and TIFF) and floating point (float16, bfloat16, float32 images of a torch
+ * program, (N, 3, H, W) or (N, H, W, 3), often still under a Normalize(mean, std)) ----
+ * A sample of channel c becomes one byte, and from there on the frame is an 8-bit frame of the same geometry:
+ *     MELF_WIDE_U16   little-endian 16-bit word s:   min(s >> shift, 255), shift 0 .. 8: the rule of melf_process_yuv16
+ *     MELF_WIDE_F16, MELF_WIDE_BF16, MELF_WIDE_F32:
+ *         x = the sample widened to float32 (exact; bfloat16 is its bits << 16)
+ *         t = x * scale[c]      rounded to float32
+ *         q = t + offset[c]     rounded to float32 -- two roundings, never a fused multiply-add
+ *         r = rintf(q) (ties to even: what torch.round and np.rint do) under MELF_ROUND_NEAREST, floorf(q) under MELF_ROUND_FLOOR
+ *         the byte is 0 if r is NaN or r < 0, 255 if r > 255, otherwise r: -inf gives 0, +inf 255
+ * numpy reproduces it exactly in float32 (x * s, then + o; np.rint / np.floor; NaN to 0; clip).  scale and offset are three float32
+ * each, in B, G, R order whatever the order of the frames' channels; they must be finite, |scale| <= 2^24 (under that bound the
+ * byte does not depend on whether denormals are flushed).  They are not looked at for MELF_WIDE_U16, nor is shift for the others.
+ *     scale = 255, offset = 0, nearest           x.mul(255).round().clamp(0, 255) of a [0, 1] image
+ *     scale = std * 255, offset = mean * 255     the same of an image under Normalize(mean, std)
+ *     scale = 255.999, floor                     torchvision's convert_image_dtype
+ *     scale = 255, floor                         .mul(255).byte() for in-range values
+ * The wrong choice raises no error: it moves samples by one, and with them what the dials are read from -- as the wrong matrix does
+ * for YUV frames.
+ * The records are byte-identical to melf_process_frames(_dev) (packed) / melf_process_planes(_dev) (planar) on the 8-bit frames of
+ * those bytes.  A narrowing kernel (k_narrow_rows, timed as MELF_K_GATHER: one launch per chunk of 1024 frames) reads the meter_rect
+ * crop of every frame in place -- 2 or 4 bytes a sample, no other byte of a frame -- and writes the crop's bytes into the lane's
+ * staged batch, the staged frames of melf_process_frame_list_dev; the unchanged kernels read those.
+ *     layout MELF_WIDE_PACKED   pixel_format MELF_PIX_*: 3 or 4 samples a pixel in that order; the 4th sample is never converted.
+ *                               Row y of frame f at frames + f * frame_stride + y * row_pitch.  The offsets are not looked at.
+ *     layout MELF_WIDE_PLANAR   b_offset / g_offset / r_offset, row_pitch, frame_stride exactly as in melf_planar_frames (a 4th
+ *                               plane is never touched); pixel_format is not looked at.
+ * Everything is in BYTES and a multiple of the sample size (2, float32: 4), the base included; no larger alignment is needed: a
+ * torch view x[:, :, y0:, x0:] passes.  The buffer must hold every sample of every named plane / pixel of every frame and nothing
+ * more: no load reaches behind the last sample of a row, outside a frame's extent or before the base.  MELF_ERR_INVALID
+ * (melf_last_error says which) before anything is launched or copied for: a NULL descriptor or NULL frames; an unknown sample_type,
+ * layout, pixel_format (packed) or rounding; shift outside 0 .. 8; reserved or reserved2 != 0; a scale or offset that is not
+ * finite, |scale| > 2^24; H or W <= 0, n < 0 (n == 0 passes); a negative plane offset; a base, offset, row_pitch or frame_stride
+ * that is no multiple of the sample size; row_pitch smaller than a row or > 2^31 - 1; planes closer together than the span of one
+ * (overlapping); a frame_stride smaller than the span of a frame.
+ * Measured at 1024-frame steps of 640 x 480 frames, buffers in rotation beyond the cache (profiles/wide_frames/wide_rate.txt): the
+ * wide batch takes 1.54 - 2.00 times the 8-bit batch of the same samples in place (16-bit words 1.75 packed / 1.54 planar, float16
+ * 1.85 / 1.62, float32 2.00 / 1.77), where torch's conversion of every whole frame to uint8 followed by that 8-bit read takes 5.1 -
+ * 13.1 times the wide batch; k_narrow_rows alone takes 0.16 - 0.28 ms a launch.
+ * Out of scope: big-endian samples; wide frames in the frame lists, plane lists and oriented calls; wide YUV beyond
+ * melf_process_yuv16*. */
+enum { MELF_WIDE_U16 = 0, MELF_WIDE_F16 = 1, MELF_WIDE_BF16 = 2, MELF_WIDE_F32 = 3 };
+enum { MELF_WIDE_PACKED = 0, MELF_WIDE_PLANAR = 1 };
+enum { MELF_ROUND_NEAREST = 0, MELF_ROUND_FLOOR = 1 };
+typedef struct melf_wide_frames {
+    int32_t sample_type;                        /* MELF_WIDE_*                                            */
+    int32_t layout;                             /* MELF_WIDE_PACKED / MELF_WIDE_PLANAR                    */
+    int32_t pixel_format;                       /* packed: MELF_PIX_*                                     */
+    int32_t shift;                              /* MELF_WIDE_U16: 0 .. 8, low bits dropped                */
+    int32_t rounding;                           /* MELF_ROUND_*                                           */
+    int32_t reserved;                           /* 0                                                      */
+    float scale[3], offset[3];                  /* B, G, R; the float types                               */
+    int32_t n, H, W;
+    int32_t reserved2;                          /* 0                                                      */
+    int64_t b_offset, g_offset, r_offset;       /* planar: BYTES from a frame's first byte to the first
+                                                   sample of its B / G / R plane, >= 0                    */
+    int64_t row_pitch;                          /* BYTES between rows (planar: of a plane)                */
+    int64_t frame_stride;                       /* BYTES between frames                                   */
+} melf_wide_frames;
+/* Host frames: only the crop crosses PCIe, and as bytes -- the host threads narrow the crop's rows (the same rule, from the same
+ * header, meterelf_amd/csrc/melf_narrow.h) while they pack them into the pinned staging buffers. */
+int melf_process_wide(melf_ctx* ctx, const void* frames_host, const melf_wide_frames* f, melf_result* out_host);
+/* Frames in HBM, with the lanes, caller streams and NULL d_results / out_host semantics of melf_process_frames_dev; under
+ * melf_ctx_set_frames_resident the narrowing waits for what the caller's stream held at the call, as the gather of
+ * melf_process_frame_list_dev does. */
+int melf_process_wide_dev(melf_ctx* ctx, const void* d_frames, const melf_wide_frames* f, void* d_results, melf_result* out_host,
+                          void* stream);
+/* Stage entry point (parity tests, and a debug view for callers): the narrowing alone, through the GPU kernel, n packed H x W x 3 BGR
+ * frames out. */
+int melf_wide_to_bgr(melf_ctx* ctx, const void* frames_host, const melf_wide_frames* f, uint8_t* bgr_out_host);
+
 /* ---- the same path for frames in SEPARATE ALLOCATIONS: the surfaces of a hardware decoder's pool (rocDecode, VA-API), a list of
  * tensors from a video reader or torchvision.io.decode_jpeg(device=...), one V4L2 / DRM capture buffer per frame ----
  * Every entry point above takes one base pointer and a frame_stride.  These two take, beside the descriptor of one of the eight
@@ -1094,7 +1166,8 @@ int melf_ctx_set_frames_resident(melf_ctx* ctx, int on);
  * returns per-kernel accumulated milliseconds and launch counts. */
 enum { MELF_K_LPLANE = 0, MELF_K_MATCH = 1, MELF_K_DIALS = 2, MELF_K_FUSED_MASK = 3, MELF_K_HLS = 4,
        MELF_K_JPEG_HUFF = 5, MELF_K_JPEG_IDCT = 6, MELF_K_JPEG_COLOR = 7, MELF_K_STREAM_PROBE = 8,
-       MELF_K_GATHER = 9 /* k_gather_rows: melf_process_frame_list_dev; k_plane_rows: melf_process_plane_list_dev */, MELF_K_COUNT = 10 };
+       MELF_K_GATHER = 9 /* k_gather_rows: melf_process_frame_list_dev; k_plane_rows: melf_process_plane_list_dev; k_orient_tiles:
+                            melf_process_oriented_dev; k_narrow_rows: melf_process_wide_dev */, MELF_K_COUNT = 10 };
 /* Which kernel, in which layout, computed the template match (meterelf/_utils.py:91-97: ONE cv2.matchTemplate code
  * path in the reference; here the batch size and the crop shape select among three kernels and, for the tuned one,
  * among wave layouts) of the context's most recent call.  Tests assert it, so that a change of a dispatch threshold

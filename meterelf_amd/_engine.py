@@ -344,6 +344,28 @@ class MeterReader:
         desc = v.descriptor()
         return self._read_view(v, out, lambda: self.ctx.process_planes(v.ptr, desc), lambda **kw: self.ctx.process_planes_dev(v.ptr, desc, **kw))
 
+    def read_wide_frames(self, frames, layout: str, channel_order: str = 'rgb', scale=None, offset=None, rounding: str = 'nearest',
+                         shift=None, out=None):
+        """RGB frames of wide samples -- uint16 (RGB16 / BGR12 of machine-vision SDKs, ffmpeg's rgb48le / gbrp10le .., decoded 16-bit
+        PNG and TIFF) or float16, bfloat16, float32 (the image tensors of a torch program, often still under a Normalize(mean, std))
+        -- -> records, equal to read_frame_views() (layout 'hwc': (N, H, W, C)) or read_planar_frames() (layout 'chw': (N, C, H, W))
+        of the 8-bit frames whose samples are the narrowed ones (melf_process_wide*; _hip.narrow_wide restates the rule in numpy);
+        only the meter_rect crop of the wide frames is read, in place, and no 8-bit frame is formed.  Integer frames: shift is required
+        and has no default -- min(s >> shift, 255): 8 for full 16-bit and MSB-aligned samples, 4 for 12 bits and 2 for 10 bits in the
+        low bits; torch.int16 holding the same bits is taken.  Float frames: shift must be None; the byte is
+        round(x * scale + offset) in float32, two roundings, clipped to 0 .. 255 (NaN: 0); scale and offset a scalar or three values
+        in the order of channel_order, defaults 255 and 0; scale = std * 255, offset = mean * 255 undoes a Normalize; rounding
+        'nearest' (ties to even, torch.round) or 'floor' (with scale 255.999: torchvision's convert_image_dtype; with 255:
+        .mul(255).byte()).  The wrong choice raises no error: it moves samples by one, and with them what the dials are read from.
+        frames: a numpy array / torch CPU tensor (host path: the host threads narrow the crop while they stage it) or a torch tensor
+        on this reader's GPU (enqueued on torch.cuda.current_stream); strided views -- a channel slice of a 4-channel tensor, a
+        spatial crop -- are read in place when their strides fit (_hip.wide_frames_view), anything else is a ValueError before the
+        library is called.  out: a uint8 device tensor (N, RESULT_DTYPE.itemsize) on the same GPU that receives the records without
+        synchronising the stream (device frames only); returns it.  Otherwise returns the records."""
+        v = _hip.wide_frames_view(frames, layout, channel_order, scale, offset, rounding, shift)
+        desc = v.descriptor()
+        return self._read_view(v, out, lambda: self.ctx.process_wide(v.ptr, desc), lambda **kw: self.ctx.process_wide_dev(v.ptr, desc, **kw))
+
     # layout of read_frame_list: (the batch method's view function, whether it takes a matrix and with which default)
     _LIST_VIEWS = {
         'views': ('frames_view', None), 'yuv': ('yuv_frames_view', 'bt601'), 'yuv422': ('yuv422_frames_view', 'bt601'),

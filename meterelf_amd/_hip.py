@@ -185,6 +185,24 @@ class MelfPlanarFrames(C.Structure):
 # plane orders of planar_frames_view: the planes present in an (N, C, H, W) array, in the array's order; 'a' / 'x' is never read
 PLANAR_ORDERS = ('rgb', 'bgr', 'gbr', 'rgba', 'rgbx', 'bgra', 'bgrx')
 
+
+class MelfWideFrames(C.Structure):
+    _fields_ = [('sample_type', C.c_int32), ('layout', C.c_int32), ('pixel_format', C.c_int32), ('shift', C.c_int32),
+                ('rounding', C.c_int32), ('reserved', C.c_int32), ('scale', C.c_float * 3), ('offset', C.c_float * 3),
+                ('n', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('reserved2', C.c_int32), ('b_offset', C.c_int64),
+                ('g_offset', C.c_int64), ('r_offset', C.c_int64), ('row_pitch', C.c_int64), ('frame_stride', C.c_int64)]
+
+
+# RGB frames of wide samples (melf_process_wide*): MELF_WIDE_* by dtype name, the layouts, the roundings; channel orders of
+# wide_frames_view by layout -- 'hwc': the samples of a pixel, 'chw': the planes present, in the array's order ('a' / 'x' is never read)
+(WIDE_U16, WIDE_F16, WIDE_BF16, WIDE_F32) = (0, 1, 2, 3)
+(WIDE_PACKED, WIDE_PLANAR) = (0, 1)
+(ROUND_NEAREST, ROUND_FLOOR) = (0, 1)
+WIDE_TYPES = {'uint16': WIDE_U16, 'int16': WIDE_U16, 'float16': WIDE_F16, 'bfloat16': WIDE_BF16, 'float32': WIDE_F32}
+WIDE_SAMPLE_BYTES = {WIDE_U16: 2, WIDE_F16: 2, WIDE_BF16: 2, WIDE_F32: 4}
+WIDE_ROUNDINGS = {'nearest': ROUND_NEAREST, 'floor': ROUND_FLOOR}
+WIDE_PACKED_ORDERS = ('rgb', 'bgr', 'rgba', 'rgbx', 'bgra', 'bgrx')
+
 MATCH_KERNEL_NAMES = ('dot4', 'mfma', 'gen')
 
 RESULT_DTYPE = np.dtype([('status', '<i4'), ('match_x', '<i4'), ('match_y', '<i4'), ('failed_dial', '<i4'),
@@ -226,6 +244,7 @@ EXPORTS = [
     'melf_process_packed32', 'melf_process_packed32_dev', 'melf_packed32_to_bgr',
     'melf_process_frame_list', 'melf_process_frame_list_dev', 'melf_process_plane_list', 'melf_process_plane_list_dev',
     'melf_process_oriented', 'melf_process_oriented_dev', 'melf_orient_frames',
+    'melf_process_wide', 'melf_process_wide_dev', 'melf_wide_to_bgr',
     'melf_bgr2hls', 'melf_hls_inrange_close', 'melf_hls_inrange_close_dev', 'melf_match_ccoeff',
     'melf_read_dials', 'melf_aligned_average', 'melf_inrange', 'melf_ctx_fused_table_ties', 'melf_ctx_fused_variant', 'melf_ctx_set_frames_resident', 'melf_ctx_last_match', 'melf_ctx_last_dials', 'melf_match_layout_query', 'melf_match_gen_plan_query', 'melf_ctx_set_profiling', 'melf_ctx_timings', 'melf_kernel_name',
     'melf_jpeg_probe', 'melf_jpeg_probe_batch', 'melf_jpeg_decode_batch', 'melf_jpeg_clean_segment', 'melf_jpeg_process_batch',
@@ -292,6 +311,9 @@ def lib():
     L.melf_packed32_to_bgr.argtypes = [vp, vp, C.POINTER(MelfPacked32Frames), vp]
     L.melf_process_planes.argtypes = [vp, vp, C.POINTER(MelfPlanarFrames), vp]
     L.melf_process_planes_dev.argtypes = [vp, vp, C.POINTER(MelfPlanarFrames), vp, vp, vp]
+    L.melf_process_wide.argtypes = [vp, vp, C.POINTER(MelfWideFrames), vp]
+    L.melf_process_wide_dev.argtypes = [vp, vp, C.POINTER(MelfWideFrames), vp, vp, vp]
+    L.melf_wide_to_bgr.argtypes = [vp, vp, C.POINTER(MelfWideFrames), vp]
     L.melf_process_frame_list.argtypes = [vp, C.c_int, vp, vp, vp]
     L.melf_process_frame_list_dev.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     L.melf_process_plane_list.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
@@ -1051,6 +1073,155 @@ def planar_frames_view(frames, channel_order='rgb'):
                             not ok, frames)
 
 
+class WideFramesView(NamedTuple):
+    """How melf_process_wide* read a batch of RGB frames of wide samples in place (wide_frames_view)."""
+    ptr: int            # address of frame 0's first sample (planar: of the lowest named plane's)
+    on_device: bool     # True: a torch tensor on a GPU (ptr is a device address)
+    device: Optional[int]
+    sample_type: int    # WIDE_*
+    layout: int         # WIDE_PACKED / WIDE_PLANAR
+    pixel_format: int   # packed: PIX_*
+    shift: int
+    rounding: int       # ROUND_*
+    scale: tuple        # B, G, R
+    offset: tuple
+    n: int
+    H: int
+    W: int
+    b_offset: int       # planar: bytes from ptr to the first sample of frame 0's B / G / R plane
+    g_offset: int
+    r_offset: int
+    row_pitch: int      # bytes between rows
+    frame_stride: int   # bytes between frames
+    extent: int         # bytes read from ptr
+    copied: bool        # always False: a layout that cannot be described is a ValueError, not a copy
+    array: object       # what ptr points into: keep it alive while the call runs
+
+    def descriptor(self):
+        return MelfWideFrames(self.sample_type, self.layout, self.pixel_format, self.shift, self.rounding, 0, (C.c_float * 3)(*self.scale),
+                              (C.c_float * 3)(*self.offset), self.n, self.H, self.W, 0, self.b_offset, self.g_offset, self.r_offset,
+                              self.row_pitch, self.frame_stride)
+
+
+def narrow_wide(samples, scale=255.0, offset=0.0, rounding='nearest', shift=None):
+    """The bytes melf_process_wide* read wide samples as, in numpy, exactly (include/meterelf_hip.h): uint16: min(s >> shift, 255);
+    float16 / float32 (bfloat16: pass its values as float32): float32 x * scale, then + offset -- two roundings --, np.rint or
+    np.floor, NaN to 0, clipped to 0 .. 255.  scale / offset broadcast against the samples."""
+    a = np.asarray(samples)
+    if a.dtype == np.uint16:
+        return np.minimum(a >> np.uint16(shift), np.uint16(255)).astype(np.uint8)
+    with np.errstate(all='ignore'):
+        q = a.astype(np.float32) * np.asarray(scale, np.float32) + np.asarray(offset, np.float32)
+        r = np.floor(q) if rounding == 'floor' else np.rint(q)
+        return np.clip(np.where(np.isnan(r), np.float32(0), r), 0, 255).astype(np.uint8)
+
+
+def _three(value, order, default, what):
+    """scale / offset of wide_frames_view: a scalar or three values in the order of the frames' channels -> (B, G, R) floats"""
+    if value is None:
+        value = default
+    v = np.asarray(value, np.float64).reshape(-1)
+    if v.size not in (1, 3):
+        raise ValueError('%s must be a scalar or three values, not %r' % (what, value))
+    v = np.broadcast_to(v, (3,)).astype(np.float32)
+    out = tuple(float(v[order.index(ch)]) for ch in 'bgr')
+    if not all(np.isfinite(out)) or (what == 'scale' and max(abs(x) for x in out) > 2.0 ** 24):
+        raise ValueError('%s must be finite%s, not %r' % (what, ', |scale| <= 2^24' if what == 'scale' else '', value))
+    return out
+
+
+def wide_frames_view(frames, layout, channel_order='rgb', scale=None, offset=None, rounding='nearest', shift=None):
+    """Describes RGB frames of wide samples as melf_process_wide* read them: layout 'hwc' (N, H, W, C) or 'chw' (N, C, H, W), C = 3
+    or 4, of uint16 (torch: uint16, or int16 holding the same bits), float16, bfloat16 (torch only) or float32; a numpy array or a
+    torch tensor on the CPU or a GPU.  channel_order names the channels present in the array's order: 'rgb', 'bgr', 'rgba' / 'rgbx',
+    'bgra' / 'bgrx', and for 'chw' also 'gbr' (the 4th is never converted).  Integer frames need shift (0 .. 8: the low bits dropped,
+    8 for full 16-bit and MSB-aligned samples, 4 / 2 for 12 / 10 bits in the low bits) and take no scale, offset or rounding; float
+    frames take no shift; scale / offset: a scalar or three values in the order of channel_order, defaults 255 and 0; rounding
+    'nearest' or 'floor' (include/meterelf_hip.h has the rule; the wrong choice raises no error and moves samples by one).
+    Strided views are taken in place when their strides fit the descriptor: unit stride along a pixel's samples ('hwc', pixels 3 or 4
+    samples apart: x[..., :3] of a 4-channel tensor is read as the 4-sample format) or along W ('chw'), non-negative row, plane and
+    frame strides that keep rows, planes and frames apart -- a channel slice x[:, :3], a spatial crop x[:, :, y0:, x0:], x[::2].
+    Anything else is a ValueError: nothing is copied."""
+    lay = str(layout).lower()
+    if lay not in ('chw', 'hwc'):
+        raise ValueError("layout %r is not 'chw' or 'hwc'" % (layout,))
+    is_torch = _is_torch(frames)
+    if not is_torch:
+        frames = np.asarray(frames)
+    tname = str(frames.dtype).replace('torch.', '')
+    if tname not in WIDE_TYPES or (not is_torch and tname in ('int16', 'bfloat16')):
+        raise ValueError('wide frames must be uint16, float16, bfloat16 or float32, not %s' % frames.dtype)
+    stype = WIDE_TYPES[tname]
+    ss = WIDE_SAMPLE_BYTES[stype]
+    if is_torch:
+        on_device = frames.device.type == 'cuda'
+        (shape, strides, ptr, device) = (tuple(frames.shape), tuple(ss * st for st in frames.stride()), frames.data_ptr(),
+                                         frames.device.index if on_device else None)
+    else:
+        (shape, strides, ptr, on_device, device) = (frames.shape, frames.strides, frames.ctypes.data, False, None)
+    order = str(channel_order).lower()
+    orders = WIDE_PACKED_ORDERS if lay == 'hwc' else PLANAR_ORDERS
+    if order not in orders:
+        raise ValueError('channel_order %r is not one of %s' % (channel_order, ', '.join(orders)))
+    ci = 3 if lay == 'hwc' else 1
+    if len(shape) != 4 or shape[ci] not in (3, 4) or 0 in shape[1:]:
+        raise ValueError('wide %s frames must be %s with C = 3 or 4, not %s' % (lay, '(N, H, W, C)' if lay == 'hwc' else '(N, C, H, W)', shape,))
+    if shape[ci] != len(order):
+        raise ValueError('channel_order %r does not name the %d channels of the frames' % (channel_order, shape[ci]))
+    if stype == WIDE_U16:
+        if shift is None or int(shift) != shift or not 0 <= shift <= 8:
+            raise ValueError('integer frames need shift = 0 .. 8 (the low bits dropped: 8 for 16-bit, 4 for 12-bit, 2 for 10-bit samples), not %r' % (shift,))
+        if scale is not None or offset is not None or str(rounding).lower() != 'nearest':
+            raise ValueError('integer frames take no scale, offset or rounding')
+    elif shift is not None:
+        raise ValueError('float frames take no shift')
+    if str(rounding).lower() not in WIDE_ROUNDINGS:
+        raise ValueError("rounding %r is not 'nearest' or 'floor'" % (rounding,))
+    rgb3 = order[:3]
+    (sc, of) = (_three(scale, rgb3, 255.0, 'scale'), _three(offset, rgb3, 0.0, 'offset'))
+    n = shape[0]
+    (b_off, g_off, r_off, code) = (0, 0, 0, 0)
+    if lay == 'hwc':
+        (_n, H, W, ch) = shape
+        (fs, rp, ps, cs) = strides
+        if ch == 3 and W > 1 and ps == 4 * ss:
+            ch = 4                                   # a 3-channel view of 4-sample pixels: read the 4-sample format
+        code = PIX_CODES[rgb3 + ('a' if ch == 4 else '')]
+        if W == 1:
+            ps = ch * ss
+        if H == 1:
+            rp = W * ch * ss
+        span = (H - 1) * rp + W * ch * ss
+        if n == 1:
+            fs = span
+        ok = cs == ss and ps == ch * ss and W * ch * ss <= rp <= 2 ** 31 - 1 and fs >= span
+        if ok and n and ch == 4 and shape[3] == 3:
+            # the unconverted 4th sample of the last pixel lies behind the view's own samples: it must belong to the same memory
+            (lo, hi) = _owner_span(frames, is_torch)
+            ok = lo <= ptr and ptr + (n - 1) * fs + span <= hi
+    else:
+        (_n, _c, H, W) = shape
+        (fs, ps, rp, es) = strides
+        (ib, ig, ir) = (order.index('b'), order.index('g'), order.index('r'))
+        if W == 1:
+            es = ss
+        if H == 1:
+            rp = W * ss
+        span = (H - 1) * rp + W * ss
+        if n == 1:
+            fs = max(ib, ig, ir) * ps + span if ps >= 0 else 0
+        ok = es == ss and W * ss <= rp <= 2 ** 31 - 1 and ps >= span and fs >= max(ib, ig, ir) * ps + span
+        (b_off, g_off, r_off) = (ib * ps, ig * ps, ir * ps)
+        span = max(ib, ig, ir) * ps + span
+    if not ok or (ptr | rp | fs | b_off | g_off | r_off) % ss:
+        raise ValueError('the strides %s (bytes) of these %s frames do not fit melf_wide_frames: they are not read in place, and nothing is '
+                         'copied' % (strides, lay))
+    extent = (n - 1) * fs + span if n else 0
+    return WideFramesView(int(ptr), on_device, device, stype, WIDE_PLANAR if lay == 'chw' else WIDE_PACKED, code, int(shift or 0),
+                          WIDE_ROUNDINGS[str(rounding).lower()], sc, of, n, H, W, int(b_off), int(g_off), int(r_off), int(rp), int(fs),
+                          int(extent), False, frames)
+
+
 def jpeg_probe(data):
     """(H, W, supported, reason) of a JPEG file's bytes; header parse only, no GPU."""
     L = lib()
@@ -1460,6 +1631,21 @@ class Context:
     def process_planes_dev(self, d_frames_ptr, desc, d_results_ptr=None, want_host=True, stream=None):
         """Planar frames in HBM (melf_process_planes_dev, as process_frames_dev).  Returns records when want_host."""
         return self._dev(self._L.melf_process_planes_dev, d_frames_ptr, desc, d_results_ptr, want_host, stream)
+
+    def process_wide(self, frames_ptr, desc):
+        """Host RGB frames of wide samples (melf_process_wide; desc: a MelfWideFrames, e.g. wide_frames_view(...).descriptor()) ->
+        records."""
+        return self._host(self._L.melf_process_wide, frames_ptr, desc)
+
+    def process_wide_dev(self, d_frames_ptr, desc, d_results_ptr=None, want_host=True, stream=None):
+        """RGB frames of wide samples in HBM (melf_process_wide_dev, as process_frames_dev).  Returns records when want_host."""
+        return self._dev(self._L.melf_process_wide_dev, d_frames_ptr, desc, d_results_ptr, want_host, stream)
+
+    def wide_to_bgr(self, frames_ptr, desc):
+        """The narrowing alone, through the GPU kernel (melf_wide_to_bgr): host frames of wide samples -> (n, H, W, 3) BGR."""
+        out = np.empty((desc.n, desc.H, desc.W, 3), np.uint8)
+        check(self._L.melf_wide_to_bgr(self._h, C.c_void_p(frames_ptr), C.byref(desc), _ptr(out)))
+        return out
 
     # --- frames in separate allocations ---
     @staticmethod

@@ -27,6 +27,7 @@
 #include "melf_internal.h"
 #include "melf_jpeg_long.h"
 #include "melf_jpeg_parse.h"
+#include "melf_narrow_addr.h"
 #include "melf_orient_addr.h"
 #include "melf_stage_plan.h"
 #include "melf_threads.h"
@@ -1714,9 +1715,13 @@ static const int LIST_CHUNK = 1024;
 // (k_gather_rows); otherwise pl->nplanes pointers per frame, frame-major, b the canonical batch of pl (melf_process_plane_list_dev:
 // k_plane_rows).  op (melf_process_oriented_dev): no list at all -- d_frames is the base of ONE stored batch b, frame i at base + i *
 // b.frame_stride, its frames rotated or mirrored; the staged batch is op's (the plan of the oriented geometry) and k_orient_tiles
-// writes it, with no pointer table.  Everything else -- the lane, the ordering, the chunks, the records -- is the same flow.
+// writes it, with no pointer table.  wd (melf_process_wide_dev): no list either -- d_frames is the base of ONE batch of wide samples,
+// b its 8-bit batch of the same geometry (wd->b: everything in samples), frame i at base + i * b.frame_stride * wd->ss bytes; the
+// staged batch is that 8-bit batch's, and k_narrow_rows writes it.  Everything else -- the lane, the ordering, the chunks, the
+// records -- is the same flow.
 static int frame_list_dev(melf_ctx* c, const FrameBatch& b, const void* const* d_frames, void* d_results, melf_result* out_host, void* stream_,
-                          bool read, size_t* bytes_moved, const PlaneList* pl = nullptr, const orient::Plan* op = nullptr)
+                          bool read, size_t* bytes_moved, const PlaneList* pl = nullptr, const orient::Plan* op = nullptr,
+                          const WideBatch* wd = nullptr)
 {
     HIP_TRY(hipSetDevice(c->device));
     StagePlan plan;
@@ -1760,9 +1765,10 @@ static int frame_list_dev(melf_ctx* c, const FrameBatch& b, const void* const* d
     const size_t stride = sp.staged.frame_stride;
     const size_t cap = (size_t)(n < LIST_CHUNK ? n : LIST_CHUNK);
     if (int rc = grow(&c->d_list_stage[lane], &c->list_stage_cap[lane], cap * stride)) return rc;
-    const size_t tab_cap = op ? 0 : cap * per_frame_ptrs;
+    const bool table = !op && !wd;   // the call has a pointer table
+    const size_t tab_cap = table ? cap * per_frame_ptrs : 0;
     if (int rc = grow(&c->d_list_tab[lane], &c->list_tab_cap[lane], tab_cap)) return rc;
-    if (!op && !c->ev_list_tab[lane]) HIP_TRY(hipEventCreateWithFlags(&c->ev_list_tab[lane], hipEventDisableTiming));
+    if (table && !c->ev_list_tab[lane]) HIP_TRY(hipEventCreateWithFlags(&c->ev_list_tab[lane], hipEventDisableTiming));
     if (c->h_list_tab_cap[lane] < tab_cap) {
         if (c->h_list_tab[lane]) { HIP_TRY(hipEventSynchronize(c->ev_list_tab[lane])); HIP_TRY(hipHostFree(c->h_list_tab[lane])); }
         c->h_list_tab[lane] = nullptr;
@@ -1773,7 +1779,7 @@ static int frame_list_dev(melf_ctx* c, const FrameBatch& b, const void* const* d
     FrameBatch staged = sp.staged;
     for (int f0 = 0; f0 < n; f0 += LIST_CHUNK) {
         const int m = n - f0 < LIST_CHUNK ? n - f0 : LIST_CHUNK;
-        if (!op) {
+        if (table) {
             HIP_TRY(hipEventSynchronize(c->ev_list_tab[lane]));   // the previous upload from the pinned table has finished
             memcpy(c->h_list_tab[lane], d_frames + (size_t)f0 * per_frame_ptrs, (size_t)m * per_frame_ptrs * sizeof(void*));
             HIP_TRY(hipMemcpyAsync(c->d_list_tab[lane], c->h_list_tab[lane], (size_t)m * per_frame_ptrs * sizeof(void*), hipMemcpyHostToDevice, ws));
@@ -1786,7 +1792,10 @@ static int frame_list_dev(melf_ctx* c, const FrameBatch& b, const void* const* d
         }
         {
             KernelTimer t(c, MELF_K_GATHER, ws);
-            if (op)
+            if (wd)
+                launch_narrow_rows((const uint8_t*)d_frames + (size_t)f0 * b.frame_stride * wd->ss, b.frame_stride * wd->ss, m, sp.runs, wd->rule,
+                                   c->d_list_stage[lane], stride, b.lay.extent, ws);
+            else if (op)
                 launch_orient_tiles((const uint8_t*)d_frames + (size_t)f0 * b.frame_stride, b.frame_stride, m, op->runs, c->d_list_stage[lane], stride, ws);
             else if (pl)
                 launch_plane_rows(c->d_list_tab[lane], pl->nplanes, m, sp.runs, split, c->d_list_stage[lane], stride, ws);
@@ -2006,6 +2015,77 @@ extern "C" int melf_gather_frame_list_dev(melf_ctx* c, int family, const void* d
     return frame_list_dev(c, b, d_frames, nullptr, nullptr, stream_, false, bytes_moved);
 }
 #endif
+
+// ------------------------------------------------------------ wide frames ----
+// RGB frames of 16-bit or floating-point samples.  check_wide leaves the 8-bit batch of the same geometry (in samples) and the rule;
+// that batch's plan is the staged frame, its runs times the sample size the source's.  On the device k_narrow_rows writes the staged
+// batch -- the frame lists' flow with another kernel in the gather's place --; the host call narrows with the same header function
+// while it packs (melf_narrow_addr.h: pack_item), so that one byte per sample crosses PCIe.
+extern "C" int melf_process_wide_dev(melf_ctx* c, const void* d_frames, const melf_wide_frames* f, void* d_results, melf_result* out_host,
+                                     void* stream_)
+{
+    WideBatch wb;
+    if (int rc = checked(c, check_wide(d_frames, f, &wb))) return rc;
+    if (wb.b.n == 0) return MELF_SUCCESS;
+    return frame_list_dev(c, wb.b, (const void* const*)d_frames, d_results, out_host, stream_, true, nullptr, nullptr, nullptr, &wb);
+}
+
+extern "C" int melf_process_wide(melf_ctx* c, const void* frames_host, const melf_wide_frames* f, melf_result* out_host)
+{
+    WideBatch wb;
+    if (int rc = checked(c, check_wide(frames_host, f, &wb))) return rc;
+    if (wb.b.n == 0) return MELF_SUCCESS;
+    Crop cr;
+    if (int rc = host_crop(c, wb.b, out_host, &cr)) return rc;
+    const StagePlan sp = narrow::wide_plan(wb, cr);
+    const narrow::Rule rule = wb.rule;
+    const int ss = wb.ss;
+    return stage_host_frames(c, Strided{(const uint8_t*)frames_host, wb.b.frame_stride * (size_t)ss}, wb.b.n, sp, out_host,
+                             [=](const uint8_t* frame, uint8_t* staged, int item) { narrow::pack_item(frame, staged, item, sp, rule, ss); });
+}
+
+// Stage entry point: the kernel alone, the rectangle the whole frame; the staged frames come back and the host writes them out as
+// packed BGR (a packed staged pixel through its format's order; the staged planes are B, G, R)
+extern "C" int melf_wide_to_bgr(melf_ctx* c, const void* frames_host, const melf_wide_frames* f, uint8_t* bgr_out_host)
+{
+    WideBatch wb;
+    if (int rc = checked(c, check_wide(frames_host, f, &wb))) return rc;
+    const FrameBatch& b = wb.b;
+    if (b.n == 0) return MELF_SUCCESS;
+    if (!bgr_out_host) return fail(MELF_ERR_INVALID, "bgr_out_host is NULL");
+    const int whole[4] = {0, 0, b.W, b.H};
+    Crop cr;
+    clamp_crop(whole, b.H, b.W, &cr);
+    const StagePlan sp = narrow::wide_plan(wb, cr);
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t fs = b.frame_stride * (size_t)wb.ss, in_bytes = (size_t)(b.n - 1) * fs + b.lay.extent * (size_t)wb.ss;
+    const size_t stride = sp.staged.frame_stride;
+    const int cap = b.n < LIST_CHUNK ? b.n : LIST_CHUNK;
+    if (int rc = grow(&c->d_stage_in, &c->stage_in_cap, in_bytes)) return rc;
+    if (int rc = grow(&c->d_stage_out, &c->stage_out_cap, (size_t)cap * stride)) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_stage_in, frames_host, in_bytes, hipMemcpyHostToDevice, c->stream));
+    std::vector<uint8_t> staged((size_t)cap * stride);
+    const bool planar = b.lay.pix == PIX_PLANAR;
+    const int ch = planar ? 1 : pix_bytes(b.lay.pix);
+    const bool rgb = b.lay.pix == MELF_PIX_RGB || b.lay.pix == MELF_PIX_RGBA;
+    uint8_t* out = bgr_out_host;
+    for (int f0 = 0; f0 < b.n; f0 += LIST_CHUNK) {
+        const int m = b.n - f0 < LIST_CHUNK ? b.n - f0 : LIST_CHUNK;
+        launch_narrow_rows(c->d_stage_in + (size_t)f0 * fs, fs, m, sp.runs, wb.rule, c->d_stage_out, stride, b.lay.extent, c->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(staged.data(), c->d_stage_out, (size_t)m * stride, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (int i = 0; i < m; ++i)
+            for (int y = 0; y < b.H; ++y)
+                for (int x = 0; x < b.W; ++x, out += 3)
+                    for (int k = 0; k < 3; ++k) {   // channel k of B, G, R
+                        const RowRun& run = sp.runs.run[planar ? k : 0];
+                        const size_t at = planar ? (size_t)x : (size_t)x * ch + (rgb ? 2 - k : k);
+                        out[k] = staged[(size_t)i * stride + (size_t)run.dst_off + (size_t)y * run.dst_pitch + at];
+                    }
+    }
+    return MELF_SUCCESS;
+}
 
 // ---------------------------------------------------------- stage entries ----
 // melf_yuv_to_bgr / melf_yuv422_to_bgr / melf_yuv_planar_to_bgr / melf_yuv16_to_bgr / melf_yuv422_10_to_bgr / melf_packed32_to_bgr after their checks: the frames up, the conversion kernel alone, n packed H x W BGR frames down

@@ -6,6 +6,7 @@
 // the bounds programs beside it allocate what the checks accept.
 #pragma once
 #include "melf_frame_layout.h"
+#include "melf_narrow.h"
 
 namespace melf {
 
@@ -325,6 +326,95 @@ inline const char* check_planes(const void* frames, const melf_planar_frames* f,
     *b = FrameBatch{f->n, f->H, f->W, (size_t)f->frame_stride, (int)f->row_pitch, FrameLayout::planar(pl, (size_t)(hi + span))};
     if (f->n == 0) return nullptr;
     if (!frames) return "frames pointer is NULL";
+    return nullptr;
+}
+
+// melf_wide_frames (melf_process_wide*, melf_wide_to_bgr): RGB frames of 16-bit or floating-point samples.  The check leaves the
+// 8-bit batch OF THE SAME GEOMETRY -- every offset, pitch, stride and the extent counted in SAMPLES, which the alignment rule makes
+// whole numbers --, a packed batch of the descriptor's pixel format or a planar one: its staging plan (melf_stage_plan.h) is the
+// staged frame the narrowing writes, and its runs times the sample size are the source's (melf_narrow_addr.h).  And the rule
+// (melf_narrow.h), scale and offset laid out by position.  Its messages have names, in one table, as PACKED32_MESSAGES:
+// tests/wide_checks_main.cpp sweeps this check and counts, through the table, that every one of them was produced.
+struct WideBatch {
+    FrameBatch b;         // in samples; b.lay: packed(pixel_format) or planar
+    narrow::Rule rule;
+    int ss;               // bytes of a sample: frame f starts at frames + f * b.frame_stride * ss
+};
+enum WideMsg { WIDE_DESC_NULL, WIDE_TYPE, WIDE_LAYOUT, WIDE_FORMAT, WIDE_ROUNDING, WIDE_SHIFT, WIDE_RESERVED, WIDE_COEF, WIDE_SHAPE,
+               WIDE_NEG_OFFSET, WIDE_ALIGN, WIDE_PITCH_SMALL, WIDE_PITCH_LARGE, WIDE_OFFSET_LARGE, WIDE_OVERLAP, WIDE_STRIDE_SMALL,
+               WIDE_FRAMES_NULL, WIDE_BASE, WIDE_MSGS };
+constexpr const char* WIDE_MESSAGES[WIDE_MSGS] = {
+    "wide frame descriptor is NULL",
+    "unknown sample_type of wide frames (accepted: 0 u16, 1 f16, 2 bf16, 3 f32)",
+    "unknown layout of wide frames (accepted: 0 packed, 1 planar)",
+    "unknown pixel_format of packed wide frames",
+    "unknown rounding of wide frames (accepted: 0 nearest, 1 floor)",
+    "shift of wide frames must be 0 .. 8 (low bits dropped from a 16-bit sample)",
+    "reserved field of the wide frame descriptor is not 0",
+    "scale and offset of wide frames must be finite, |scale| <= 2^24",
+    "bad batch shape of wide frames",
+    "negative plane offset of wide frames",
+    "wide frames need offsets, a row_pitch and a frame_stride that are multiples of the sample size",
+    "row_pitch of wide frames smaller than a row",
+    "row_pitch of wide frames too large",
+    "plane offset of wide frames too large",
+    "two planes of wide frames overlap",
+    "frame_stride of wide frames smaller than a frame",
+    "frames pointer of wide frames is NULL",
+    "wide frames need a base that is a multiple of the sample size",
+};
+inline const char* check_wide(const void* frames, const melf_wide_frames* f, WideBatch* wb)
+{
+    const char* const* const msg = WIDE_MESSAGES;
+    if (!f) return msg[WIDE_DESC_NULL];
+    if (f->sample_type < MELF_WIDE_U16 || f->sample_type > MELF_WIDE_F32) return msg[WIDE_TYPE];
+    if (f->layout != MELF_WIDE_PACKED && f->layout != MELF_WIDE_PLANAR) return msg[WIDE_LAYOUT];
+    const bool planar = f->layout == MELF_WIDE_PLANAR;
+    if (!planar && (f->pixel_format < MELF_PIX_BGR || f->pixel_format > MELF_PIX_RGBA)) return msg[WIDE_FORMAT];
+    if (f->rounding != MELF_ROUND_NEAREST && f->rounding != MELF_ROUND_FLOOR) return msg[WIDE_ROUNDING];
+    if (f->shift < 0 || f->shift > 8) return msg[WIDE_SHIFT];
+    if (f->reserved != 0 || f->reserved2 != 0) return msg[WIDE_RESERVED];
+    for (int k = 0; k < 3; ++k)
+        if (!(fabsf(f->scale[k]) <= 16777216.0f) || !(fabsf(f->offset[k]) <= 3.402823466e38f)) return msg[WIDE_COEF];   // (NaN fails both)
+    if (f->n < 0 || f->H <= 0 || f->W <= 0) return msg[WIDE_SHAPE];
+    if (planar && (f->b_offset < 0 || f->g_offset < 0 || f->r_offset < 0)) return msg[WIDE_NEG_OFFSET];
+    const int ss = narrow::sample_bytes(f->sample_type);
+    const int ch = planar ? 1 : pix_bytes(f->pixel_format);   // samples of a pixel in one row
+    const uint64_t amask = (uint64_t)ss - 1;
+    if (((uint64_t)f->row_pitch | (uint64_t)f->frame_stride) & amask) return msg[WIDE_ALIGN];
+    if (planar && (((uint64_t)f->b_offset | (uint64_t)f->g_offset | (uint64_t)f->r_offset) & amask)) return msg[WIDE_ALIGN];
+    if (f->row_pitch < (int64_t)f->W * ch * ss) return msg[WIDE_PITCH_SMALL];
+    if (f->row_pitch > INT32_MAX) return msg[WIDE_PITCH_LARGE];
+    const int64_t span = plane_span(f->H, f->row_pitch, f->W, 1, ch * ss);   // bytes of the packed plane / of one plane
+    int64_t hi = 0;
+    if (planar) {
+        const int64_t off[3] = {f->b_offset, f->g_offset, f->r_offset};
+        for (int a = 0; a < 3; ++a) {
+            if (off[a] > INT64_MAX - span) return msg[WIDE_OFFSET_LARGE];
+            if (off[a] > hi) hi = off[a];
+            for (int k = a + 1; k < 3; ++k) {
+                const int64_t lo2 = off[a] < off[k] ? off[a] : off[k], hi2 = off[a] < off[k] ? off[k] : off[a];
+                if (hi2 - lo2 < span) return msg[WIDE_OVERLAP];
+            }
+        }
+    }
+    if (f->frame_stride < hi + span) return msg[WIDE_STRIDE_SMALL];
+    const size_t extent = (size_t)((hi + span) / ss);
+    const PlanarPlanes pl = {f->b_offset / ss, f->g_offset / ss, f->r_offset / ss};
+    wb->b = FrameBatch{f->n, f->H, f->W, (size_t)(f->frame_stride / ss), (int)(f->row_pitch / ss),
+                       planar ? FrameLayout::planar(pl, extent) : FrameLayout::packed(f->pixel_format, extent)};
+    wb->ss = ss;
+    narrow::Rule& r = wb->rule;
+    r = narrow::Rule{};
+    r.type = f->sample_type; r.shift = f->shift; r.floor_ = f->rounding == MELF_ROUND_FLOOR; r.channels = ch;
+    const bool rgb = !planar && (f->pixel_format == MELF_PIX_RGB || f->pixel_format == MELF_PIX_RGBA);
+    for (int p = 0; p < 3; ++p) {   // position p holds channel p (B G R ..; the planes of the staged frame) or 2 - p (R G B ..)
+        r.scale[p] = f->scale[rgb ? 2 - p : p];
+        r.offset[p] = f->offset[rgb ? 2 - p : p];
+    }
+    if (f->n == 0) return nullptr;
+    if (!frames) return msg[WIDE_FRAMES_NULL];
+    if ((uintptr_t)frames & amask) return msg[WIDE_BASE];
     return nullptr;
 }
 

@@ -213,6 +213,14 @@ namespace orient { struct Runs; }
 void launch_orient_tiles(const void* d_frames, size_t frame_stride, int n, const orient::Runs& runs, uint8_t* d_staged, size_t staged_stride,
                          hipStream_t stream);
 
+// ---- k_narrow.hip: frames of wide samples (melf_process_wide_dev, melf_wide_to_bgr) ----
+// Narrows the runs of a wide batch's plan (melf_narrow_addr.h: the runs count SAMPLES of the source) of each of the n frames d_frames
+// + i * frame_stride (bytes) into the staged frame d_staged + i * staged_stride, under `rule` (melf_narrow.h); `extent` samples of
+// a frame are readable.  n <= 65535.
+namespace narrow { struct Rule; }
+void launch_narrow_rows(const void* d_frames, size_t frame_stride, int n, const RowRuns& runs, const narrow::Rule& rule, uint8_t* d_staged,
+                        size_t staged_stride, size_t extent, hipStream_t stream);
+
 // ---- calibration stage kernels ------------------------------------------------
 void launch_aligned_average(const uint8_t* d_frames, int n, size_t frame_stride, int row_stride, int x0, int y0, int rows,
                             int cols, const int32_t* d_mx, const int32_t* d_my, int ax, int ay, uint8_t* d_out,

@@ -1,9 +1,14 @@
 // K2 -- cv2.matchTemplate(L, template, TM_CCOEFF) + cv2.minMaxLoc
 // (reference: meterelf/_utils.py:91-97, called from meterelf/_image.py:57-66).
 //
-// Exact integer formulation: cc[y,x] = sum_ij T[i,j] * I[y+i,x+j] in u32 (max
-// 119*188*255^2 < 2^31), window sum in u32, then OpenCV's own post-pass
+// Exact integer formulation: cc[y,x] = sum_ij T[i,j] * I[y+i,x+j] in u32, window
+// sum in u32, then OpenCV's own post-pass
 //   R = float32( double(cc) - double(winsum) * mean(T) ).
+// cc < 2^32, UNSIGNED: it passes 2^31 on bright frames for templates beyond 33 026
+// pixels.  Nothing in this kernel bounds th * tw; the context's rule for the LDS
+// tile below (setup_device_tables: (17 + ceil(tw / 4)) * (43 + th) * 4 <= 64 KiB)
+// does -- it admits at most 159 x 256 = 40 704 pixels, cc <= 2.65e9 -- and that is
+// what keeps the u32 accumulator from wrapping (tests/test_match_limits.py).
 // OpenCV reaches cc through a float32 DFT; the exact value is what that
 // approximates.
 //

@@ -560,9 +560,10 @@ __device__ __forceinline__ void match_wave(const int8_t* __restrict__ Lg, const 
     // ---- epilogue: exact u8 correlation, OpenCV's float post-pass, first-max reduction ----
     const int n = lane & 31, hh = lane >> 5;
     const int f = grp * 32 + n;
-    // cc = sum T*L is below 2^31 (119*188*255^2 at most for templates this kernel takes), so the three terms
-    // can be added modulo 2^32 and converted with one cvt_f64_u32 (an int64 -> double conversion is four
-    // instructions, two of them quarter rate).  A lane visits its elements in increasing raster index, so the
+    // cc = sum T*L is below 2^32 (mfma_match_ok: th * tw * 255^2 < 2^32; a context's templates reach 2.6e9, beyond 2^31,
+    // on bright frames: tests/test_match_limits.py), so the three terms can be added modulo 2^32 and converted UNSIGNED
+    // with one cvt_f64_u32 (an int64 -> double conversion is four instructions, two of them quarter rate; a signed
+    // conversion would be wrong from 2^31 on).  A lane visits its elements in increasing raster index, so the
     // first maximum is "strictly greater wins".  One map row at a time: a row's window sums and its accumulators
     // (which leave the accumulator file for the vector ALU) stay within the registers the main loop needs anyway.
     const bool lane_ok = f < g.nframes;

@@ -219,24 +219,42 @@ ORC_API void orc_match_ccoeff(const uint8_t* img, int rows, int cols, long strid
             integ[(long)(y + 1) * (cols + 1) + x + 1] = integ[(long)y * (cols + 1) + x + 1] + rs;
         }
     }
-    int32_t* acc = (int32_t*)malloc(sizeof(int32_t) * rw);
+    /* cc <= th * tw * 255^2.  Where that fits 32 unsigned bits (every template the GPU library admits: up to
+     * 2.65e9, beyond 2^31) the sum runs in uint32_t, which the compiler vectorises; a larger template takes the
+     * int64_t loop.  Either way cc is exact and converts to double without loss. */
+    const int wide = (long)th * tw * 65025L >= (1L << 32);
+    uint32_t* acc = (uint32_t*)malloc(sizeof(uint32_t) * rw);
+    int64_t* acc64 = wide ? (int64_t*)malloc(sizeof(int64_t) * rw) : NULL;
     float best = 0.f;
     int bx = -1, by = -1;
     for (int y = 0; y < rh; ++y) {
-        memset(acc, 0, sizeof(int32_t) * rw);
-        for (int i = 0; i < th; ++i) {
-            const uint8_t* irow = img + (long)(y + i) * stride;
-            const uint8_t* trow = tpl + (long)i * tw;
-            for (int j = 0; j < tw; ++j) {
-                int32_t t = trow[j];
-                const uint8_t* ip = irow + j;
-                for (int x = 0; x < rw; ++x) acc[x] += t * (int32_t)ip[x];
+        if (wide) {
+            memset(acc64, 0, sizeof(int64_t) * rw);
+            for (int i = 0; i < th; ++i) {
+                const uint8_t* irow = img + (long)(y + i) * stride;
+                const uint8_t* trow = tpl + (long)i * tw;
+                for (int j = 0; j < tw; ++j) {
+                    int64_t t = trow[j];
+                    const uint8_t* ip = irow + j;
+                    for (int x = 0; x < rw; ++x) acc64[x] += t * (int64_t)ip[x];
+                }
+            }
+        } else {
+            memset(acc, 0, sizeof(uint32_t) * rw);
+            for (int i = 0; i < th; ++i) {
+                const uint8_t* irow = img + (long)(y + i) * stride;
+                const uint8_t* trow = tpl + (long)i * tw;
+                for (int j = 0; j < tw; ++j) {
+                    uint32_t t = trow[j];
+                    const uint8_t* ip = irow + j;
+                    for (int x = 0; x < rw; ++x) acc[x] += t * (uint32_t)ip[x];
+                }
             }
         }
         for (int x = 0; x < rw; ++x) {
             long ws = integ[(long)(y + th) * (cols + 1) + x + tw] - integ[(long)y * (cols + 1) + x + tw]
                     - integ[(long)(y + th) * (cols + 1) + x] + integ[(long)y * (cols + 1) + x];
-            double num = (double)acc[x];
+            double num = wide ? (double)acc64[x] : (double)acc[x];   /* unsigned 32-bit -> double */
             num -= (double)ws * tmean;
             float r = (float)num;
             if (result) result[(long)y * rw + x] = r;
@@ -245,6 +263,7 @@ ORC_API void orc_match_ccoeff(const uint8_t* img, int rows, int cols, long strid
         }
     }
     free(acc);
+    free(acc64);
     free(integ);
     *max_val = best; *max_x = bx; *max_y = by;
 }

@@ -760,8 +760,9 @@ def test_host_fed_batches_crop_upload(env):
     assert again.tobytes() == recs[5:40].tobytes()
 
 
-def _reader_with_template(tmp_path, tpl):
-    """A MeterReader whose dials template is `tpl` (the match stage does not look at the dials)."""
+def _reader_with_template(tmp_path, tpl, **settings):
+    """A MeterReader whose dials template is `tpl` (the match stage does not look at the dials); `settings` replace top-level
+    entries of the params file (meter_rect, dials_template_match_threshold), which is left at tmp_path / 'params.yml'."""
     import yaml
     from PIL import Image
     from meterelf_amd import MeterReader, _params
@@ -769,6 +770,7 @@ def _reader_with_template(tmp_path, tpl):
     with open(os.path.join(GOLDEN, 'sample-images1', 'params.yml')) as fp:
         data = yaml.safe_load(fp)
     data['dials_template_size'] = [tw, th]
+    data.update(settings)
     small = min(th, tw) < 52
     for nd in data['needle_data']:
         if small:   # dials that fit a tiny template: radius round(2 / 2) + 0 + 2 - 1 = 2

@@ -150,10 +150,13 @@ def test_gen_planner_invariants_every_batch_size():
 
 
 @pytest.mark.parametrize('th,tw,rows,cols', [(9, 11, 9, 11), (9, 11, 40, 75), (40, 64, 250, 250), (119, 256, 300, 468), (60, 100, 135, 231),
-                                             (119, 188, 130, 1000), (31, 33, 62, 97)], ids=lambda v: str(v))
+                                             (119, 188, 130, 1000), (31, 33, 62, 97),
+                                             (209, 190, 231, 250), (209, 190, 231, 215), (159, 256, 175, 288), (291, 128, 300, 161)],
+                         ids=lambda v: str(v))
 def test_gen_planner_invariants_other_shapes(th, tw, rows, cols):
     """The same invariants for other templates and maps: 1 x 1 map, 1-4 remainder columns, several V-form row blocks, two
-    column blocks per tile, templates up to 256 columns."""
+    column blocks per tile, templates up to 256 columns; and the largest templates a context accepts (about 40 000 pixels:
+    tests/test_match_limits.py runs them)."""
     for n in (1, 32, 33, 100, 512, 1024, 3000):
         _check_gen_plan(th, tw, rows, cols, n)
 
@@ -167,6 +170,20 @@ def test_planner_other_shapes():
     assert _hip.match_layout_query(119, 188, 135, 400, 64)['kernel'] == 'gen'
     assert _hip.match_layout_query(40, 64, 250, 250, 64)['kernel'] == 'gen'
     assert _hip.match_layout_query(119, 300, 250, 400, 64)['kernel'] == 'dot4'
+    # the largest templates a context accepts (tests/test_match_limits.py): 209 x 190 is in the tuned kernel's class, with two column
+    # blocks and with one, in a layout that covers the 23 map rows whatever the batch size; the other two are the general kernel's
+    for n in (1, 40, 512, 1024, 3000):
+        for (cols, nxb) in ((250, 2), (215, 1)):
+            d = _hip.match_layout_query(209, 190, 231, cols, n)
+            (rb, na, npairs, ks) = (d['rows_per_wave'], d['full_waves'], d['pair_waves'] // 2, d['k_slices'])
+            assert d['kernel'] == 'mfma' and (nxb == 2 or npairs == 0), (n, cols, d)
+            covered = rb * na + (2 * rb + 1) * npairs
+            assert 23 <= covered < 23 + 2 * rb + 1, (n, cols, d)
+            sl = d['th_pad'] // ks
+            assert d['th_pad'] >= 209 and d['th_pad'] == sl * ks and sl % (rb + 1) == 0 and (npairs == 0 or sl % (rb + 2) == 0)
+            assert d['rows_pad'] >= covered + d['th_pad'] + 1
+        assert _hip.match_layout_query(159, 256, 175, 288, n)['kernel'] == 'gen'
+        assert _hip.match_layout_query(291, 128, 300, 161, n)['kernel'] == 'gen'
 
 
 # ------------------------------------------------------------------ GPU ----

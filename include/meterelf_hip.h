@@ -549,8 +549,9 @@ int melf_process_planes_dev(melf_ctx* ctx, const void* d_frames, const melf_plan
  * wide batch takes 1.54 - 2.00 times the 8-bit batch of the same samples in place (16-bit words 1.75 packed / 1.54 planar, float16
  * 1.85 / 1.62, float32 2.00 / 1.77), where torch's conversion of every whole frame to uint8 followed by that 8-bit read takes 5.1 -
  * 13.1 times the wide batch; k_narrow_rows alone takes 0.16 - 0.28 ms a launch.
- * Out of scope: big-endian samples; wide frames in the frame lists, plane lists and oriented calls; wide YUV beyond
- * melf_process_yuv16*. */
+ * Wide frames in separate allocations, and wide planes in separate allocations: melf_process_wide_list* and
+ * melf_process_wide_plane_list*, below.
+ * Out of scope: big-endian samples; wide frames in the oriented calls; wide YUV beyond melf_process_yuv16*. */
 enum { MELF_WIDE_U16 = 0, MELF_WIDE_F16 = 1, MELF_WIDE_BF16 = 2, MELF_WIDE_F32 = 3 };
 enum { MELF_WIDE_PACKED = 0, MELF_WIDE_PLANAR = 1 };
 enum { MELF_ROUND_NEAREST = 0, MELF_ROUND_FLOOR = 1 };
@@ -580,6 +581,55 @@ int melf_process_wide_dev(melf_ctx* ctx, const void* d_frames, const melf_wide_f
 /* Stage entry point (parity tests, and a debug view for callers): the narrowing alone, through the GPU kernel, n packed H x W x 3 BGR
  * frames out. */
 int melf_wide_to_bgr(melf_ctx* ctx, const void* frames_host, const melf_wide_frames* f, uint8_t* bgr_out_host);
+
+/* ---- wide frames in SEPARATE ALLOCATIONS: one (H, W, 3) uint16 array per decoded 16-bit PNG or TIFF, one RGB16 buffer per frame of
+ * a machine-vision SDK, a list of float16 / float32 (3, H, W) tensors from a torch Dataset or a video reader; and wide planar frames
+ * whose PLANES lie in separate allocations: libav's gbrp10le / gbrp12le / gbrp16le AVFrame with its three plane pointers ----
+ * melf_wide_frames beside a HOST array of pointers (device pointers for _dev, host pointers otherwise), as melf_process_frame_list*
+ * and melf_process_plane_list* take the 8-bit descriptors; the library copies the array before it returns.  These entry points take
+ * the wide descriptor directly: there is no MELF_LIST_* code for it.
+ *   Frame list (melf_process_wide_list*): either layout.  n is the list's length; frame_stride is not looked at; everything else is
+ *     checked as for a batch of one frame, with melf_process_wide's messages.  Every pointer is checked for NULL and for alignment to
+ *     the sample size, the message led by "frame i of the list:".  From each pointer one frame's extent is readable -- up to the last
+ *     sample of the frame's last row (packed) or of its last plane (planar) -- and nothing behind it nor before the pointer is read.
+ *     Frames may alias or repeat.
+ *   Plane list (melf_process_wide_plane_list*): MELF_WIDE_PLANAR only, nplanes == 3, planes[i * 3 + k] plane slot k of frame i, slots
+ *     0 / 1 / 2 = B / G / R as for melf_planar_frames plane lists.  b_offset, g_offset and r_offset count from each plane's own
+ *     pointer and must be 0; there is one row_pitch for the three planes.  A packed descriptor is MELF_ERR_INVALID (the message names
+ *     melf_process_wide_list), as is any other nplanes.  From each plane pointer (H - 1) * row_pitch + W * sample size bytes are
+ *     readable, and nothing more.  Every pointer is checked for NULL and alignment to the sample size, the message led by "frame i,
+ *     plane k of the list:".  Planes may alias or repeat.
+ * The records are byte-identical to melf_process_wide(_dev) on one contiguous batch holding the same samples in list order.
+ * Everything else is melf_process_frame_list_dev's: the lanes and caller streams; under melf_ctx_set_frames_resident the narrowing
+ * waits for what the caller's stream held at the call; lists longer than 1024 frames go through the lane's staging buffer in chunks
+ * of 1024; the NULL d_results / out_host semantics; n == 0 passes; nothing is launched or copied for a rejected call.  Two siblings
+ * of k_narrow_rows with its launch shape and its conversion code take the source pointer of a wave from the table in HBM
+ * (k_narrow_list_rows: frames[f]; k_narrow_plane_rows: planes[f * 3 + k], the piece tested against that plane's own extent), timed
+ * as MELF_K_GATHER, one launch per chunk.  The host calls narrow while they pack, from the i-th pointer(s) as frame i: one byte per
+ * sample crosses PCIe.
+ * Measured at 1024-frame config-3 steps of 640 x 480 frames, buffers in rotation beyond the cache
+ * (profiles/wide_list/wide_list_rate.txt), 16-bit words / float16 / float32: the frame list (b) takes 0.990 / 0.982 / 0.972 (packed) and
+ * 0.990 / 0.990 / 0.990 (planar) times the step of the wide batch in place (a) -- it moves the same bytes; 0.40 - 0.50 ms --, the
+ * plane list (c) 1.019 / 1.017 / 1.018 times the frame list, and torch.stack of the listed frames followed by the batch read (d)
+ * 4.02 / 3.93 / 4.15 (packed) and 4.19 / 4.04 / 4.26 (planar) times the frame list; torch.stack of the listed planes and the batch
+ * read takes 4.12 / 3.97 / 4.25 times the plane list.  The batch path itself runs as before: melf_process_wide_dev under the parent
+ * commit's library and under this one, in the same session, differ by -0.9 .. +0.1 %, inside the spread of the parent's own turns.
+ * Out of scope: big-endian samples (rgb48be, raw PNG / PPM words: melf_wide_frames has no free field left -- sample_type 4 and non-zero
+ * reserved fields are rejected --, so they need a descriptor revision and an ABI bump); wide frames in melf_process_oriented* (its
+ * kernel would have to narrow elements of 6 - 16 bytes through LDS: another kernel); a 4th plane; planes with differing pitches. */
+int melf_process_wide_list_dev(melf_ctx* ctx, const melf_wide_frames* f, const void* const* d_frames, void* d_results,
+                               melf_result* out_host, void* stream);
+int melf_process_wide_list(melf_ctx* ctx, const melf_wide_frames* f, const void* const* frames_host, melf_result* out_host);
+int melf_process_wide_plane_list_dev(melf_ctx* ctx, const melf_wide_frames* f, const void* const* d_planes, int nplanes, void* d_results,
+                                     melf_result* out_host, void* stream);
+int melf_process_wide_plane_list(melf_ctx* ctx, const melf_wide_frames* f, const void* const* planes_host, int nplanes,
+                                 melf_result* out_host);
+/* Stage entry point (parity tests, and a debug view for callers): the narrowing alone through the list kernels.  ptrs_host: n host
+ * pointers, one per frame (nplanes == 0), or n * 3, one per plane (nplanes == 3), checked as above.  The library uploads every listed
+ * frame or plane into a device allocation OF ITS OWN, of exactly its readable extent, runs the list kernel with the rectangle set to
+ * the whole frame and returns n packed H x W x 3 BGR frames, as melf_wide_to_bgr does for a batch.  The allocations are temporary
+ * and are freed before it returns.  n <= 1024. */
+int melf_wide_list_to_bgr(melf_ctx* ctx, const melf_wide_frames* f, const void* const* ptrs_host, int nplanes, uint8_t* bgr_out_host);
 
 /* ---- the same path for frames in SEPARATE ALLOCATIONS: the surfaces of a hardware decoder's pool (rocDecode, VA-API), a list of
  * tensors from a video reader or torchvision.io.decode_jpeg(device=...), one V4L2 / DRM capture buffer per frame ----
@@ -1167,7 +1217,8 @@ int melf_ctx_set_frames_resident(melf_ctx* ctx, int on);
 enum { MELF_K_LPLANE = 0, MELF_K_MATCH = 1, MELF_K_DIALS = 2, MELF_K_FUSED_MASK = 3, MELF_K_HLS = 4,
        MELF_K_JPEG_HUFF = 5, MELF_K_JPEG_IDCT = 6, MELF_K_JPEG_COLOR = 7, MELF_K_STREAM_PROBE = 8,
        MELF_K_GATHER = 9 /* k_gather_rows: melf_process_frame_list_dev; k_plane_rows: melf_process_plane_list_dev; k_orient_tiles:
-                            melf_process_oriented_dev; k_narrow_rows: melf_process_wide_dev */, MELF_K_COUNT = 10 };
+                            melf_process_oriented_dev; k_narrow_rows: melf_process_wide_dev; k_narrow_list_rows / k_narrow_plane_rows:
+                            melf_process_wide_list_dev / melf_process_wide_plane_list_dev */, MELF_K_COUNT = 10 };
 /* Which kernel, in which layout, computed the template match (meterelf/_utils.py:91-97: ONE cv2.matchTemplate code
  * path in the reference; here the batch size and the crop shape select among three kernels and, for the tuned one,
  * among wave layouts) of the context's most recent call.  Tests assert it, so that a change of a dispatch threshold

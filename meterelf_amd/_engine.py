@@ -588,6 +588,140 @@ class MeterReader:
         return self._read_view(view, out, lambda alive=alive: self.ctx.process_plane_list(layout, desc, table, nplanes),
                                lambda alive=alive, **kw: self.ctx.process_plane_list_dev(layout, desc, table, nplanes, **kw))
 
+    def read_wide_frame_list(self, frames, layout: str, channel_order: str = 'rgb', scale=None, offset=None, rounding: str = 'nearest',
+                             shift=None, out=None):
+        """Frames of wide samples in separate allocations -- one (H, W, 3) uint16 array per decoded 16-bit PNG or TIFF, one RGB16
+        buffer per frame of a camera SDK, a list of float16 / float32 (3, H, W) tensors from a Dataset or a video reader -- ->
+        records, equal to read_wide_frames() on one array holding the same frames in list order (melf_process_wide_list*), without
+        the torch.stack that would make that array: the narrowing kernel takes each frame's address from a table and reads only its
+        meter crop.  frames: a sequence whose elements are each ONE frame, (H, W, C) for layout 'hwc', (C, H, W) for 'chw': numpy
+        arrays / torch CPU tensors (host path), or torch tensors on this reader's GPU (enqueued on torch.cuda.current_stream).
+        channel_order, scale, offset, rounding and shift are read_wide_frames'.  Every element is described by
+        _hip.wide_frames_view as frame[None]; all must agree in everything but the address.  ValueError: host and device elements
+        mixed, an element on another device, elements that differ (the message says which and in what), an element whose strides
+        the descriptor cannot express (nothing is copied).  out: as for the batch methods, a uint8 device tensor (len(frames),
+        RESULT_DTYPE.itemsize)."""
+        frames = list(frames)
+        views = []
+        for (i, f) in enumerate(frames):
+            if not (_hip._is_torch(f) or isinstance(f, np.ndarray)):
+                f = np.asarray(f)
+            if f.ndim != 3:
+                raise ValueError('frame %d of the list must be one frame, %s, not of shape %s' % (
+                    i, '(C, H, W)' if str(layout).lower() == 'chw' else '(H, W, C)', tuple(f.shape)))
+            try:
+                v = _hip.wide_frames_view(f[None], layout, channel_order, scale, offset, rounding, shift)
+            except ValueError as e:
+                raise ValueError('frame %d of the list: %s' % (i, e)) from None
+            if views:
+                if v.on_device != views[0].on_device:
+                    raise ValueError('frame %d of the list is in %s memory, frame 0 in %s memory' % ((i,) + tuple(
+                        'device' if w.on_device else 'host' for w in (v, views[0]))))
+                for name in v._fields:
+                    if name not in ('ptr', 'array', 'on_device') and getattr(v, name) != getattr(views[0], name):
+                        raise ValueError('frame %d of the list differs from frame 0 in %s: %r, not %r' % (i, name, getattr(v, name), getattr(views[0], name)))
+            views.append(v)
+        n = len(views)
+        if n == 0:
+            return out if out is not None else np.zeros(0, _hip.RESULT_DTYPE)
+        desc = views[0].descriptor()
+        desc.n = n
+        ptrs = [v.ptr for v in views]
+        # the closures hold `views`: the table is addresses only, and what np.asarray made of an array-like has no other owner
+        return self._read_view(views[0]._replace(n=n), out, lambda views=views: self.ctx.process_wide_list(desc, ptrs),
+                               lambda views=views, **kw: self.ctx.process_wide_list_dev(desc, ptrs, **kw))
+
+    def read_wide_plane_list(self, frames, channel_order: str = 'rgb', scale=None, offset=None, rounding: str = 'nearest', shift=None,
+                             out=None):
+        """Planar frames of wide samples whose PLANES lie in separate allocations -- libav's gbrp10le / gbrp12le / gbrp16le AVFrame
+        (data[0..2], linesize[0..2]: channel_order 'gbr'), (r, g, b) held as separate float tensors -- -> records, equal to
+        read_wide_frames(layout='chw') on one array holding the same samples in list order (melf_process_wide_plane_list*), without
+        stacking any frame's planes.  frames: a sequence of 3-tuples of 2-D (H, W) planes in the order channel_order names them
+        ('rgb', 'bgr' or 'gbr'): numpy arrays / torch CPU tensors (host path) or torch tensors on this reader's GPU (enqueued on
+        torch.cuda.current_stream), of uint16 (torch: or int16 holding the same bits), float16, bfloat16 or float32, their samples
+        contiguous along W, any row stride; all planes share dtype, shape and row stride.  scale / offset: a scalar or three values
+        in the order of channel_order; they, rounding and shift are read_wide_frames'.  ValueError, naming frame and plane: a wrong
+        plane count, host and device planes mixed, a plane on another device, differing dtype, shape or row stride, a plane whose
+        strides the descriptor cannot express (nothing is copied).  out: as for the batch methods, a uint8 device tensor
+        (len(frames), RESULT_DTYPE.itemsize)."""
+        order = str(channel_order).lower()
+        if order not in ('rgb', 'bgr', 'gbr'):
+            raise ValueError('channel_order %r does not name three planes (rgb, bgr, gbr)' % (channel_order,))
+        frames = list(frames)
+        n = len(frames)
+        if n == 0:
+            return out if out is not None else np.zeros(0, _hip.RESULT_DTYPE)
+        slot_of = ['bgr'.index(ch) for ch in order]   # tuple position -> plane slot of the C ABI (B, G, R)
+        first = None      # frame 0, plane 0: (its view, its dtype)
+        table = []
+        alive = []        # every plane's view (and with it the array its address points into, a converted one included)
+        for (i, planes) in enumerate(frames):
+            planes = tuple(planes) if isinstance(planes, (tuple, list)) else (planes,)
+            if len(planes) != 3:
+                raise ValueError('frame %d of the list has %d planes, wide planar frames have 3' % (i, len(planes)))
+            slots = [None] * 3
+            for (k, p) in enumerate(planes):
+                where = 'frame %d, plane %d of the list' % (i, k)
+                if not (_hip._is_torch(p) or isinstance(p, np.ndarray)):
+                    p = np.asarray(p)
+                if p.ndim != 2:
+                    raise ValueError('%s must be a 2-D (H, W) plane, not of shape %s' % (where, tuple(p.shape)))
+                try:
+                    v = self._wide_plane_view(p, scale, offset, rounding, shift, order)
+                except ValueError as e:
+                    raise ValueError('%s: %s' % (where, e)) from None
+                if first is None:
+                    first = (v, str(p.dtype))
+                else:
+                    (v0, dt0) = first
+                    if v.on_device != v0.on_device:
+                        raise ValueError('%s is in %s memory, frame 0, plane 0 in %s memory' % (
+                            where, 'device' if v.on_device else 'host', 'device' if v0.on_device else 'host'))
+                    if v.device != v0.device:
+                        raise ValueError('%s is on cuda:%s, frame 0, plane 0 on cuda:%s' % (where, v.device, v0.device))
+                    for (name, a, b) in (('dtype', str(p.dtype), dt0), ('shape', (v.H, v.W), (v0.H, v0.W)), ('row_pitch', v.row_pitch, v0.row_pitch)):
+                        if a != b:
+                            raise ValueError('%s differs from frame 0, plane 0 in %s: %r, not %r' % (where, name, a, b))
+                slots[slot_of[k]] = v.ptr
+                alive.append(v)
+            table.extend(slots)
+        v0 = first[0]
+        desc = v0._replace(n=n, b_offset=0, g_offset=0, r_offset=0, frame_stride=0).descriptor()
+        view = self._PlaneListView(v0.on_device, v0.device, n, v0.array)
+        return self._read_view(view, out, lambda alive=alive: self.ctx.process_wide_plane_list(desc, table, 3),
+                               lambda alive=alive, **kw: self.ctx.process_wide_plane_list_dev(desc, table, 3, **kw))
+
+    @staticmethod
+    def _wide_plane_view(plane, scale, offset, rounding, shift, order):
+        """One 2-D plane of wide samples as a WideFramesView of layout 'chw' (n = 1; its plane offsets mean nothing): the sample
+        type, H, W, row_pitch and the address are the plane's; the rule and its argument checks are wide_frames_view's, taken from
+        a one-pixel stand-in of the same dtype and channel order.  A plane the descriptor cannot express is a ValueError."""
+        is_torch = _hip._is_torch(plane)
+        tname = str(plane.dtype).replace('torch.', '')
+        if tname not in _hip.WIDE_TYPES or (not is_torch and tname in ('int16', 'bfloat16')):
+            raise ValueError('wide frames must be uint16, float16, bfloat16 or float32, not %s' % plane.dtype)
+        ss = _hip.WIDE_SAMPLE_BYTES[_hip.WIDE_TYPES[tname]]
+        (H, W) = tuple(plane.shape)
+        if H == 0 or W == 0:
+            raise ValueError('a plane must be (H, W) with H, W > 0, not %s' % ((H, W),))
+        strides = tuple(ss * st for st in plane.stride()) if is_torch else plane.strides
+        (rp, es) = strides
+        # strides of dimensions of size 1 are never stepped over: make them what a packed plane has
+        if W == 1:
+            es = ss
+        if H == 1:
+            rp = W * ss
+        ptr = plane.data_ptr() if is_torch else plane.ctypes.data
+        if es != ss or not W * ss <= rp <= 2 ** 31 - 1 or (ptr | rp) % ss:
+            raise ValueError('the strides %s (bytes) of this plane do not fit melf_wide_frames: it is not read in place, and nothing is '
+                             'copied' % (strides,))
+        # (a numpy stand-in also for torch's own types: integer samples take the checks of uint16, float samples those of float16)
+        stand_in = np.zeros((1, 3, 1, 1), np.uint16 if _hip.WIDE_TYPES[tname] == _hip.WIDE_U16 else np.float16)
+        rule = _hip.wide_frames_view(stand_in, 'chw', order, scale, offset, rounding, shift)
+        on_device = is_torch and plane.device.type == 'cuda'
+        return rule._replace(ptr=int(ptr), on_device=on_device, device=plane.device.index if on_device else None,
+                             sample_type=_hip.WIDE_TYPES[tname], H=H, W=W, row_pitch=int(rp), array=plane)
+
     def read_crops(self, crops: np.ndarray) -> np.ndarray:
         """Already meter_rect-cropped images (the reference's bgr_image injection)."""
         (_n, h, w, _c) = crops.shape

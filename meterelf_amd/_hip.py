@@ -245,6 +245,8 @@ EXPORTS = [
     'melf_process_frame_list', 'melf_process_frame_list_dev', 'melf_process_plane_list', 'melf_process_plane_list_dev',
     'melf_process_oriented', 'melf_process_oriented_dev', 'melf_orient_frames',
     'melf_process_wide', 'melf_process_wide_dev', 'melf_wide_to_bgr',
+    'melf_process_wide_list', 'melf_process_wide_list_dev', 'melf_process_wide_plane_list', 'melf_process_wide_plane_list_dev',
+    'melf_wide_list_to_bgr',
     'melf_bgr2hls', 'melf_hls_inrange_close', 'melf_hls_inrange_close_dev', 'melf_match_ccoeff',
     'melf_read_dials', 'melf_aligned_average', 'melf_inrange', 'melf_ctx_fused_table_ties', 'melf_ctx_fused_variant', 'melf_ctx_set_frames_resident', 'melf_ctx_last_match', 'melf_ctx_last_dials', 'melf_match_layout_query', 'melf_match_gen_plan_query', 'melf_ctx_set_profiling', 'melf_ctx_timings', 'melf_kernel_name',
     'melf_jpeg_probe', 'melf_jpeg_probe_batch', 'melf_jpeg_decode_batch', 'melf_jpeg_clean_segment', 'melf_jpeg_process_batch',
@@ -314,6 +316,12 @@ def lib():
     L.melf_process_wide.argtypes = [vp, vp, C.POINTER(MelfWideFrames), vp]
     L.melf_process_wide_dev.argtypes = [vp, vp, C.POINTER(MelfWideFrames), vp, vp, vp]
     L.melf_wide_to_bgr.argtypes = [vp, vp, C.POINTER(MelfWideFrames), vp]
+    if hasattr(L, 'melf_process_wide_list'):   # (tools/wide_rate.py loads the library from before the wide lists through MELF_LIB_PATH)
+        L.melf_process_wide_list.argtypes = [vp, C.POINTER(MelfWideFrames), vp, vp]
+        L.melf_process_wide_list_dev.argtypes = [vp, C.POINTER(MelfWideFrames), vp, vp, vp, vp]
+        L.melf_process_wide_plane_list.argtypes = [vp, C.POINTER(MelfWideFrames), vp, C.c_int, vp]
+        L.melf_process_wide_plane_list_dev.argtypes = [vp, C.POINTER(MelfWideFrames), vp, C.c_int, vp, vp, vp]
+        L.melf_wide_list_to_bgr.argtypes = [vp, C.POINTER(MelfWideFrames), vp, C.c_int, vp]
     L.melf_process_frame_list.argtypes = [vp, C.c_int, vp, vp, vp]
     L.melf_process_frame_list_dev.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
     L.melf_process_plane_list.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp]
@@ -1709,6 +1717,46 @@ class Context:
         check(self._L.melf_process_plane_list_dev(self._h, family, C.byref(desc), self._plane_table(d_plane_ptrs, desc, nplanes), nplanes,
                                                   C.c_void_p(d_results_ptr) if d_results_ptr else None, _ptr(out) if want_host else None,
                                                   C.c_void_p(stream) if stream else None))
+        return out
+
+    # --- wide frames, and wide planes, in separate allocations ---
+    def process_wide_list(self, desc, frame_ptrs):
+        """Host frames of wide samples in separate allocations (melf_process_wide_list) -> records.  desc: a MelfWideFrames, its n the
+        length of the list (frame_stride is not looked at); frame_ptrs: the frames' addresses."""
+        out = np.zeros(max(desc.n, 0), RESULT_DTYPE)
+        check(self._L.melf_process_wide_list(self._h, C.byref(desc), self._pointer_table(frame_ptrs, desc), _ptr(out)))
+        return out
+
+    def process_wide_list_dev(self, desc, d_frame_ptrs, d_results_ptr=None, want_host=True, stream=None):
+        """The same for frames in HBM (melf_process_wide_list_dev, as process_frame_list_dev).  Returns records when want_host."""
+        out = np.zeros(max(desc.n, 0), RESULT_DTYPE) if want_host else None
+        check(self._L.melf_process_wide_list_dev(self._h, C.byref(desc), self._pointer_table(d_frame_ptrs, desc),
+                                                 C.c_void_p(d_results_ptr) if d_results_ptr else None, _ptr(out) if want_host else None,
+                                                 C.c_void_p(stream) if stream else None))
+        return out
+
+    def process_wide_plane_list(self, desc, plane_ptrs, nplanes=3):
+        """Host planar frames of wide samples whose planes lie in separate allocations (melf_process_wide_plane_list) -> records.  desc:
+        a planar MelfWideFrames, its n the length of the list, its plane offsets 0; plane_ptrs: n * 3 addresses, frame-major (B, G,
+        R), flat or one tuple per frame."""
+        out = np.zeros(max(desc.n, 0), RESULT_DTYPE)
+        check(self._L.melf_process_wide_plane_list(self._h, C.byref(desc), self._plane_table(plane_ptrs, desc, nplanes), nplanes, _ptr(out)))
+        return out
+
+    def process_wide_plane_list_dev(self, desc, d_plane_ptrs, nplanes=3, d_results_ptr=None, want_host=True, stream=None):
+        """The same for planes in HBM (melf_process_wide_plane_list_dev, as process_plane_list_dev).  Returns records when want_host."""
+        out = np.zeros(max(desc.n, 0), RESULT_DTYPE) if want_host else None
+        check(self._L.melf_process_wide_plane_list_dev(self._h, C.byref(desc), self._plane_table(d_plane_ptrs, desc, nplanes), nplanes,
+                                                       C.c_void_p(d_results_ptr) if d_results_ptr else None, _ptr(out) if want_host else None,
+                                                       C.c_void_p(stream) if stream else None))
+        return out
+
+    def wide_list_to_bgr(self, desc, ptrs, nplanes=0):
+        """The narrowing alone, through the list kernels (melf_wide_list_to_bgr): host addresses of desc.n frames (nplanes 0) or of
+        desc.n * 3 planes (nplanes 3), each uploaded into a device allocation of exactly its readable extent -> (n, H, W, 3) BGR."""
+        out = np.empty((max(desc.n, 0), desc.H, desc.W, 3), np.uint8)
+        table = self._plane_table(ptrs, desc, nplanes) if nplanes else self._pointer_table(ptrs, desc)
+        check(self._L.melf_wide_list_to_bgr(self._h, C.byref(desc), table, nplanes, _ptr(out)))
         return out
 
     # --- frames stored rotated or mirrored ---

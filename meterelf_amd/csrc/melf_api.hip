@@ -1718,10 +1718,12 @@ static const int LIST_CHUNK = 1024;
 // writes it, with no pointer table.  wd (melf_process_wide_dev): no list either -- d_frames is the base of ONE batch of wide samples,
 // b its 8-bit batch of the same geometry (wd->b: everything in samples), frame i at base + i * b.frame_stride * wd->ss bytes; the
 // staged batch is that 8-bit batch's, and k_narrow_rows writes it.  Everything else -- the lane, the ordering, the chunks, the
-// records -- is the same flow.
+// records -- is the same flow.  wd with wd_table (melf_process_wide_list_dev, melf_process_wide_plane_list_dev): both at once --
+// d_frames is a pointer table as for a list, of wide frames (k_narrow_list_rows) or, with pl, of their planes (k_narrow_plane_rows;
+// pl in samples: check_wide_plane_list).
 static int frame_list_dev(melf_ctx* c, const FrameBatch& b, const void* const* d_frames, void* d_results, melf_result* out_host, void* stream_,
                           bool read, size_t* bytes_moved, const PlaneList* pl = nullptr, const orient::Plan* op = nullptr,
-                          const WideBatch* wd = nullptr)
+                          const WideBatch* wd = nullptr, bool wd_table = false)
 {
     HIP_TRY(hipSetDevice(c->device));
     StagePlan plan;
@@ -1765,7 +1767,7 @@ static int frame_list_dev(melf_ctx* c, const FrameBatch& b, const void* const* d
     const size_t stride = sp.staged.frame_stride;
     const size_t cap = (size_t)(n < LIST_CHUNK ? n : LIST_CHUNK);
     if (int rc = grow(&c->d_list_stage[lane], &c->list_stage_cap[lane], cap * stride)) return rc;
-    const bool table = !op && !wd;   // the call has a pointer table
+    const bool table = !op && (!wd || wd_table);   // the call has a pointer table
     const size_t tab_cap = table ? cap * per_frame_ptrs : 0;
     if (int rc = grow(&c->d_list_tab[lane], &c->list_tab_cap[lane], tab_cap)) return rc;
     if (table && !c->ev_list_tab[lane]) HIP_TRY(hipEventCreateWithFlags(&c->ev_list_tab[lane], hipEventDisableTiming));
@@ -1792,7 +1794,11 @@ static int frame_list_dev(melf_ctx* c, const FrameBatch& b, const void* const* d
         }
         {
             KernelTimer t(c, MELF_K_GATHER, ws);
-            if (wd)
+            if (wd && table && pl)
+                launch_narrow_plane_rows(c->d_list_tab[lane], m, sp.runs, split, wd->rule, c->d_list_stage[lane], stride, ws);
+            else if (wd && table)
+                launch_narrow_list_rows(c->d_list_tab[lane], m, sp.runs, wd->rule, c->d_list_stage[lane], stride, b.lay.extent, ws);
+            else if (wd)
                 launch_narrow_rows((const uint8_t*)d_frames + (size_t)f0 * b.frame_stride * wd->ss, b.frame_stride * wd->ss, m, sp.runs, wd->rule,
                                    c->d_list_stage[lane], stride, b.lay.extent, ws);
             else if (op)
@@ -2044,8 +2050,26 @@ extern "C" int melf_process_wide(melf_ctx* c, const void* frames_host, const mel
                              [=](const uint8_t* frame, uint8_t* staged, int item) { narrow::pack_item(frame, staged, item, sp, rule, ss); });
 }
 
+// m staged frames of a whole-frame plan (`stride` bytes apart) -> m packed H x W x 3 BGR frames at out: a packed staged pixel through
+// its format's order; the staged planes are B, G, R.  Returns the end of what it wrote.
+static uint8_t* staged_to_bgr(const uint8_t* staged, size_t stride, int m, const FrameBatch& b, const StagePlan& sp, uint8_t* out)
+{
+    const bool planar = b.lay.pix == PIX_PLANAR;
+    const int ch = planar ? 1 : pix_bytes(b.lay.pix);
+    const bool rgb = b.lay.pix == MELF_PIX_RGB || b.lay.pix == MELF_PIX_RGBA;
+    for (int i = 0; i < m; ++i)
+        for (int y = 0; y < b.H; ++y)
+            for (int x = 0; x < b.W; ++x, out += 3)
+                for (int k = 0; k < 3; ++k) {   // channel k of B, G, R
+                    const RowRun& run = sp.runs.run[planar ? k : 0];
+                    const size_t at = planar ? (size_t)x : (size_t)x * ch + (rgb ? 2 - k : k);
+                    out[k] = staged[(size_t)i * stride + (size_t)run.dst_off + (size_t)y * run.dst_pitch + at];
+                }
+    return out;
+}
+
 // Stage entry point: the kernel alone, the rectangle the whole frame; the staged frames come back and the host writes them out as
-// packed BGR (a packed staged pixel through its format's order; the staged planes are B, G, R)
+// packed BGR
 extern "C" int melf_wide_to_bgr(melf_ctx* c, const void* frames_host, const melf_wide_frames* f, uint8_t* bgr_out_host)
 {
     WideBatch wb;
@@ -2065,9 +2089,6 @@ extern "C" int melf_wide_to_bgr(melf_ctx* c, const void* frames_host, const melf
     if (int rc = grow(&c->d_stage_out, &c->stage_out_cap, (size_t)cap * stride)) return rc;
     HIP_TRY(hipMemcpyAsync(c->d_stage_in, frames_host, in_bytes, hipMemcpyHostToDevice, c->stream));
     std::vector<uint8_t> staged((size_t)cap * stride);
-    const bool planar = b.lay.pix == PIX_PLANAR;
-    const int ch = planar ? 1 : pix_bytes(b.lay.pix);
-    const bool rgb = b.lay.pix == MELF_PIX_RGB || b.lay.pix == MELF_PIX_RGBA;
     uint8_t* out = bgr_out_host;
     for (int f0 = 0; f0 < b.n; f0 += LIST_CHUNK) {
         const int m = b.n - f0 < LIST_CHUNK ? b.n - f0 : LIST_CHUNK;
@@ -2075,15 +2096,132 @@ extern "C" int melf_wide_to_bgr(melf_ctx* c, const void* frames_host, const melf
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(staged.data(), c->d_stage_out, (size_t)m * stride, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
-        for (int i = 0; i < m; ++i)
-            for (int y = 0; y < b.H; ++y)
-                for (int x = 0; x < b.W; ++x, out += 3)
-                    for (int k = 0; k < 3; ++k) {   // channel k of B, G, R
-                        const RowRun& run = sp.runs.run[planar ? k : 0];
-                        const size_t at = planar ? (size_t)x : (size_t)x * ch + (rgb ? 2 - k : k);
-                        out[k] = staged[(size_t)i * stride + (size_t)run.dst_off + (size_t)y * run.dst_pitch + at];
-                    }
+        out = staged_to_bgr(staged.data(), stride, m, b, sp, out);
     }
+    return MELF_SUCCESS;
+}
+
+// ------------------------------------------------------- wide frame lists ----
+// Wide frames in separate allocations, and wide planar frames whose planes are: the wide descriptor beside a host array of pointers,
+// with entry points of their own (no MELF_LIST_* code: the 8-bit lists' family switch stays as it is).  check_wide_list /
+// check_wide_plane_list (host-only headers) run the unchanged check_wide on the one-frame descriptor; the device calls are
+// frame_list_dev with the wide batch AND a pointer table -- k_narrow_list_rows / k_narrow_plane_rows in the gather's place --, the
+// host calls stage_host_frames with the i-th pointer(s) as frame i, narrowing while they pack.
+static int wide_list_batch(const melf_ctx* c, const melf_wide_frames* f, const void* const* frames, WideBatch* wb)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    int bad;
+    if (const char* msg = check_wide_list(f, frames, wb, &bad))
+        return bad < 0 ? fail(MELF_ERR_INVALID, msg) : fail(MELF_ERR_INVALID, "frame " + std::to_string(bad) + " of the list: " + msg);
+    return MELF_SUCCESS;
+}
+static int wide_plane_list_batch(const melf_ctx* c, const melf_wide_frames* f, const void* const* planes, int nplanes, WidePlaneList* w)
+{
+    if (!c) return fail(MELF_ERR_INVALID, "ctx is NULL");
+    int bf, bp;
+    if (const char* msg = check_wide_plane_list(f, planes, nplanes, w, &bf, &bp))
+        return bf < 0 ? fail(MELF_ERR_INVALID, msg)
+                      : fail(MELF_ERR_INVALID, "frame " + std::to_string(bf) + ", plane " + std::to_string(bp) + " of the list: " + msg);
+    return MELF_SUCCESS;
+}
+
+extern "C" int melf_process_wide_list_dev(melf_ctx* c, const melf_wide_frames* f, const void* const* d_frames, void* d_results,
+                                          melf_result* out_host, void* stream_)
+{
+    WideBatch wb;
+    if (int rc = wide_list_batch(c, f, d_frames, &wb)) return rc;
+    if (wb.b.n == 0) return MELF_SUCCESS;
+    return frame_list_dev(c, wb.b, d_frames, d_results, out_host, stream_, true, nullptr, nullptr, nullptr, &wb, true);
+}
+
+extern "C" int melf_process_wide_list(melf_ctx* c, const melf_wide_frames* f, const void* const* frames_host, melf_result* out_host)
+{
+    WideBatch wb;
+    if (int rc = wide_list_batch(c, f, frames_host, &wb)) return rc;
+    if (wb.b.n == 0) return MELF_SUCCESS;
+    Crop cr;
+    if (int rc = host_crop(c, wb.b, out_host, &cr)) return rc;
+    const StagePlan sp = narrow::wide_plan(wb, cr);
+    const narrow::Rule rule = wb.rule;
+    const int ss = wb.ss;
+    return stage_host_frames(c, Listed{frames_host}, wb.b.n, sp, out_host,
+                             [=](const uint8_t* frame, uint8_t* staged, int item) { narrow::pack_item(frame, staged, item, sp, rule, ss); });
+}
+
+extern "C" int melf_process_wide_plane_list_dev(melf_ctx* c, const melf_wide_frames* f, const void* const* d_planes, int nplanes,
+                                                void* d_results, melf_result* out_host, void* stream_)
+{
+    WidePlaneList w;
+    if (int rc = wide_plane_list_batch(c, f, d_planes, nplanes, &w)) return rc;
+    if (w.wb.b.n == 0) return MELF_SUCCESS;
+    return frame_list_dev(c, w.wb.b, d_planes, d_results, out_host, stream_, true, nullptr, &w.pl, nullptr, &w.wb, true);
+}
+
+extern "C" int melf_process_wide_plane_list(melf_ctx* c, const melf_wide_frames* f, const void* const* planes_host, int nplanes,
+                                            melf_result* out_host)
+{
+    WidePlaneList w;
+    if (int rc = wide_plane_list_batch(c, f, planes_host, nplanes, &w)) return rc;
+    if (w.wb.b.n == 0) return MELF_SUCCESS;
+    Crop cr;
+    if (int rc = host_crop(c, w.wb.b, out_host, &cr)) return rc;
+    const StagePlan sp = narrow::wide_plan(w.wb, cr);
+    const PlaneSplit split = narrow::wide_plane_split(sp.runs, w.pl);
+    const narrow::Rule rule = w.wb.rule;
+    const int ss = w.wb.ss;
+    return stage_host_frames(c, ListedPlanes{planes_host, 3}, w.wb.b.n, sp, out_host, [=](const void* const* planes, uint8_t* staged, int item) {
+        narrow::pack_item(planes, staged, item, sp, split, rule, ss);
+    });
+}
+
+// Stage entry point of the two list kernels: every listed frame (nplanes == 0) or plane (nplanes == 3) goes up into a device
+// allocation of its own, of exactly its readable extent -- a kernel that read one sample behind it would leave the allocation --, the
+// list kernel runs with the rectangle the whole frame, and the staged frames come back as packed BGR.  The allocations live for
+// the call only.
+extern "C" int melf_wide_list_to_bgr(melf_ctx* c, const melf_wide_frames* f, const void* const* ptrs_host, int nplanes, uint8_t* bgr_out_host)
+{
+    WidePlaneList w;
+    const bool by_plane = nplanes != 0;
+    if (int rc = by_plane ? wide_plane_list_batch(c, f, ptrs_host, nplanes, &w) : wide_list_batch(c, f, ptrs_host, &w.wb)) return rc;
+    const WideBatch& wb = w.wb;
+    const FrameBatch& b = wb.b;
+    if (b.n == 0) return MELF_SUCCESS;
+    if (b.n > LIST_CHUNK) return fail(MELF_ERR_INVALID, "melf_wide_list_to_bgr takes at most 1024 frames");
+    if (!bgr_out_host) return fail(MELF_ERR_INVALID, "bgr_out_host is NULL");
+    const int whole[4] = {0, 0, b.W, b.H};
+    Crop cr;
+    clamp_crop(whole, b.H, b.W, &cr);
+    const StagePlan sp = narrow::wide_plan(wb, cr);
+    const PlaneSplit split = by_plane ? narrow::wide_plane_split(sp.runs, w.pl) : PlaneSplit{};
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t count = (size_t)b.n * (by_plane ? 3 : 1), stride = sp.staged.frame_stride;
+    const size_t bytes_each = (by_plane ? (size_t)w.pl.extent[0] : b.lay.extent) * (size_t)wb.ss;   // the readable extent of a frame / plane
+    std::vector<void*> dev(count + 1, nullptr);   // the frames' or planes' own allocations, and the pointer table behind them
+    hipError_t err = hipSuccess;
+    for (size_t i = 0; i < count && err == hipSuccess; ++i) {
+        err = hipMalloc(&dev[i], bytes_each);
+        if (err == hipSuccess) err = hipMemcpyAsync(dev[i], ptrs_host[i], bytes_each, hipMemcpyHostToDevice, c->stream);
+    }
+    if (err == hipSuccess) err = hipMalloc(&dev[count], count * sizeof(void*));
+    if (err == hipSuccess) err = hipMemcpyAsync(dev[count], dev.data(), count * sizeof(void*), hipMemcpyHostToDevice, c->stream);
+    std::vector<uint8_t> staged((size_t)b.n * stride);
+    int rc = MELF_SUCCESS;
+    if (err == hipSuccess) rc = grow(&c->d_stage_out, &c->stage_out_cap, (size_t)b.n * stride);
+    if (err == hipSuccess && rc == MELF_SUCCESS) {
+        if (by_plane)
+            launch_narrow_plane_rows((const void* const*)dev[count], b.n, sp.runs, split, wb.rule, c->d_stage_out, stride, c->stream);
+        else
+            launch_narrow_list_rows((const void* const*)dev[count], b.n, sp.runs, wb.rule, c->d_stage_out, stride, b.lay.extent, c->stream);
+        err = hipGetLastError();
+        if (err == hipSuccess) err = hipMemcpyAsync(staged.data(), c->d_stage_out, (size_t)b.n * stride, hipMemcpyDeviceToHost, c->stream);
+    }
+    const hipError_t sync_err = hipStreamSynchronize(c->stream);   // before the allocations go, whatever happened
+    if (err == hipSuccess) err = sync_err;
+    for (void* p : dev)
+        if (p) (void)hipFree(p);
+    if (rc != MELF_SUCCESS) return rc;
+    HIP_TRY(err);
+    staged_to_bgr(staged.data(), stride, b.n, b, sp, bgr_out_host);
     return MELF_SUCCESS;
 }
 

@@ -418,4 +418,42 @@ inline const char* check_wide(const void* frames, const melf_wide_frames* f, Wid
     return nullptr;
 }
 
+// melf_wide_frames beside a list of frame pointers (melf_process_wide_list*, melf_wide_list_to_bgr): the descriptor through check_wide
+// as a one-frame batch -- with a frame_stride that it takes, a multiple of 16 no extent reaches, against a pointer that breaks no
+// rule --, its messages WIDE_MESSAGES' own; then the array and every pointer of the list, whose messages have a table of their own.
+// *wb: the one-frame batch with n the list's length (frame_stride means nothing).  *bad: -1, or the index of the frame the message
+// is about, which the caller puts in front of it ("frame i of the list: ").  tests/wide_list_main.cpp sweeps this check and counts,
+// through the table, that every message was produced.
+enum WideListMsg { WLIST_TABLE_NULL, WLIST_PTR_NULL, WLIST_PTR_ALIGN, WLIST_MSGS };
+constexpr const char* WIDE_LIST_MESSAGES[WLIST_MSGS] = {
+    "the wide list's array of frame pointers is NULL",
+    "frame pointer of wide frames is NULL",
+    "wide frames need frame pointers that are multiples of the sample size",
+};
+// the descriptor as a one-frame batch: what the two list checks share (n: the caller's, put back by them)
+inline melf_wide_frames wide_one_frame(const melf_wide_frames& f)
+{
+    melf_wide_frames one = f;
+    one.n = f.n > 0 ? 1 : f.n;
+    one.frame_stride = INT64_MAX & ~(int64_t)15;
+    return one;
+}
+inline const char* check_wide_list(const melf_wide_frames* f, const void* const* frames, WideBatch* wb, int* bad)
+{
+    *bad = -1;
+    if (!f) return check_wide(nullptr, nullptr, wb);
+    const melf_wide_frames one = wide_one_frame(*f);
+    if (const char* msg = check_wide((const void*)(uintptr_t)64, &one, wb)) return msg;
+    wb->b.n = f->n;
+    if (f->n == 0) return nullptr;
+    if (!frames) return WIDE_LIST_MESSAGES[WLIST_TABLE_NULL];
+    for (int i = 0; i < f->n; ++i) {
+        *bad = i;
+        if (!frames[i]) return WIDE_LIST_MESSAGES[WLIST_PTR_NULL];
+        if ((uintptr_t)frames[i] & ((uintptr_t)wb->ss - 1)) return WIDE_LIST_MESSAGES[WLIST_PTR_ALIGN];
+    }
+    *bad = -1;
+    return nullptr;
+}
+
 }  // namespace melf

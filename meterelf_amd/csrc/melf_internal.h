@@ -220,6 +220,12 @@ void launch_orient_tiles(const void* d_frames, size_t frame_stride, int n, const
 namespace narrow { struct Rule; }
 void launch_narrow_rows(const void* d_frames, size_t frame_stride, int n, const RowRuns& runs, const narrow::Rule& rule, uint8_t* d_staged,
                         size_t staged_stride, size_t extent, hipStream_t stream);
+// The same from a DEVICE array of n frame pointers (melf_process_wide_list_dev; `extent` samples are readable from each), and from a
+// device array of n * 3 plane pointers, frame-major (melf_process_wide_plane_list_dev; split in samples: narrow::wide_plane_split).
+void launch_narrow_list_rows(const void* const* d_frames, int n, const RowRuns& runs, const narrow::Rule& rule, uint8_t* d_staged,
+                             size_t staged_stride, size_t extent, hipStream_t stream);
+void launch_narrow_plane_rows(const void* const* d_planes, int n, const RowRuns& runs, const PlaneSplit& split, const narrow::Rule& rule,
+                              uint8_t* d_staged, size_t staged_stride, hipStream_t stream);
 
 // ---- calibration stage kernels ------------------------------------------------
 void launch_aligned_average(const uint8_t* d_frames, int n, size_t frame_stride, int row_stride, int x0, int y0, int rows,

@@ -1,7 +1,8 @@
-// Address arithmetic of k_narrow_rows (k_narrow.hip) and of the host packer of melf_process_wide: which samples of a wide frame
-// (melf_process_wide*: 16-bit or floating-point samples, melf_narrow.h narrows one) make which 16-byte piece of the staged frame.
+// Address arithmetic of k_narrow_rows and its two list siblings (k_narrow.hip) and of the host packers of melf_process_wide*: which
+// samples of a wide frame (16-bit or floating-point samples, melf_narrow.h narrows one) make which 16-byte piece of the staged frame.
 // Plain C++, the sibling of melf_gather_addr.h, on which it stands: tests/wide_narrow_main.cpp executes the same functions on the CPU
-// against frames of exact extent.
+// against frames of exact extent, tests/wide_list_main.cpp against listed frames and planes of exact extent (the end of this file:
+// a wide frame's planes in separate allocations).
 //
 // The staged frame is the one the plan of the 8-bit batch of the same geometry gives (check_wide leaves that batch, every offset
 // and pitch counted in SAMPLES): packed_plan / planar_plan of melf_stage_plan.h.  A staged byte is one narrowed sample, so a run's
@@ -48,20 +49,44 @@ MELF_GATHER_FN uint32_t piece_phase(uint32_t piece, uint32_t channels) { return 
 
 // The host packer of melf_process_wide: work item `item` of the plan (stage_item: a block of 32 rows of one run) of the caller's frame
 // at `frame` into its staged frame at `staged`, piece by piece as the kernel does it, every sample narrowed on the way
+// rows [r0, r1) of run k (run.src_off: samples from src)
+inline void pack_run_rows(const uint8_t* src, uint8_t* staged, const RowRun& run, int k, uint32_t r0, uint32_t r1, const Rule& rule, int ss)
+{
+    const uint32_t ppr = gather::row_pieces(run.row_bytes);
+    for (uint32_t y = r0; y < r1; ++y)
+        for (uint32_t p = 0; p < ppr; ++p) {
+            const Samples s = samples_of(run, y, p);
+            narrow_samples(staged + s.dst_off, src + s.sample * (uint64_t)ss, s.count, s.j0, (uint32_t)k, rule);
+        }
+}
 inline void pack_item(const uint8_t* frame, uint8_t* staged, int item, const StagePlan& sp, const Rule& rule, int ss)
 {
     int k0, k1;
     uint32_t r0, r1;
     stage_item(sp, item, &k0, &k1, &r0, &r1);
-    for (int k = k0; k < k1; ++k) {
-        const RowRun& run = sp.runs.run[k];
-        const uint32_t ppr = gather::row_pieces(run.row_bytes);
-        for (uint32_t y = r0; y < r1; ++y)
-            for (uint32_t p = 0; p < ppr; ++p) {
-                const Samples s = samples_of(run, y, p);
-                narrow_samples(staged + s.dst_off, frame + s.sample * (uint64_t)ss, s.count, s.j0, (uint32_t)k, rule);
-            }
-    }
+    for (int k = k0; k < k1; ++k) pack_run_rows(frame, staged, sp.runs.run[k], k, r0, r1, rule, ss);
+}
+
+// ---- a wide frame's planes in separate allocations (melf_process_wide_plane_list*, k_narrow_plane_rows) ----
+// The PlaneSplit of a wide plane list, in SAMPLES: check_wide_plane_list (melf_stage_plan.h) leaves the canonical batch and its
+// PlaneList in samples, so run k of the plan starts src_off[k] samples behind plane slot k's own pointer, of which extent[k] samples
+// are readable.  The kernel takes a wave's rows through gather::plane_rows of this split and tests every piece with
+// samples_readable against that plane's extent.
+inline PlaneSplit wide_plane_split(const RowRuns& runs, const PlaneList& pl_in_samples) { return plane_split(runs, pl_in_samples); }
+// run k of the plan as it is read from plane slot k's pointer
+MELF_GATHER_FN RowRun plane_run(const RowRun& run, const PlaneSplit& split, int k)
+{
+    RowRun r = run;
+    r.src_off = split.src_off[k];
+    return r;
+}
+// The host packer's plane-list form: run k from planes[k] (the frame's three pointers, B / G / R)
+inline void pack_item(const void* const* planes, uint8_t* staged, int item, const StagePlan& sp, const PlaneSplit& split, const Rule& rule, int ss)
+{
+    int k0, k1;
+    uint32_t r0, r1;
+    stage_item(sp, item, &k0, &k1, &r0, &r1);
+    for (int k = k0; k < k1; ++k) pack_run_rows((const uint8_t*)planes[k], staged, plane_run(sp.runs.run[k], split, k), k, r0, r1, rule, ss);
 }
 
 }  // namespace narrow

@@ -387,4 +387,63 @@ inline const char* plane_list_check(int family, const void* desc, int nplanes, P
     return nullptr;
 }
 
+// ---- planar frames of WIDE samples whose planes lie in separate allocations (melf_process_wide_plane_list*) ----
+// The wide descriptor in the plane lists' way: MELF_WIDE_PLANAR only, b_ / g_ / r_offset counted from each plane's own pointer (0),
+// three pointers per frame, slots 0 / 1 / 2 = B / G / R.  The canonical one-allocation descriptor -- the planes back to back -- goes
+// through the unchanged check_wide (its messages WIDE_MESSAGES' own), which leaves the batch IN SAMPLES; so the PlaneList is in
+// samples too: offset[k] and extent[k] count samples, plane_split of the batch's plan gives run k's first sample from plane slot k's
+// pointer and the samples readable from it, and align is the sample size in bytes.  What is particular to the list has a message
+// table of its own; tests/wide_list_main.cpp sweeps the check and counts, through the table, that every message was produced.
+struct WidePlaneList {
+    WideBatch wb;    // wb.b == pl.batch: the canonical batch, n the list's length
+    PlaneList pl;
+};
+enum WidePlaneListMsg { WPLIST_PACKED, WPLIST_OFFSETS, WPLIST_NPLANES, WPLIST_TABLE_NULL, WPLIST_PTR_NULL, WPLIST_PTR_ALIGN, WPLIST_MSGS };
+constexpr const char* WIDE_PLANE_LIST_MESSAGES[WPLIST_MSGS] = {
+    "a plane list of wide frames takes MELF_WIDE_PLANAR only: packed wide frames in separate allocations go through melf_process_wide_list*",
+    "plane offsets of a wide plane list count from the plane's own pointer: b_offset, g_offset and r_offset must be 0",
+    "nplanes of a wide plane list must be 3 (B, G, R)",
+    "the wide list's array of plane pointers is NULL",
+    "plane pointer of wide frames is NULL",
+    "wide frames need plane pointers that are multiples of the sample size",
+};
+// planes: n * nplanes pointers, frame-major.  Returns the message, or nullptr with *w filled (n == 0 passes).  *bad_frame, *bad_plane:
+// -1, or the indices of the pointer the message is about ("frame i, plane k of the list: ").
+inline const char* check_wide_plane_list(const melf_wide_frames* f, const void* const* planes, int nplanes, WidePlaneList* w, int* bad_frame,
+                                         int* bad_plane)
+{
+    *bad_frame = *bad_plane = -1;
+    *w = WidePlaneList{};
+    if (!f) return check_wide(nullptr, nullptr, &w->wb);
+    melf_wide_frames d = wide_one_frame(*f);
+    const bool planar = d.layout == MELF_WIDE_PLANAR;
+    const bool zero = d.b_offset == 0 && d.g_offset == 0 && d.r_offset == 0;
+    const bool typed = d.sample_type >= MELF_WIDE_U16 && d.sample_type <= MELF_WIDE_F32;
+    const bool in_range = typed && d.H > 0 && d.W > 0 && d.row_pitch >= 0 && d.row_pitch <= INT32_MAX;
+    const int64_t span = in_range ? plane_span(d.H, d.row_pitch, d.W, 1, narrow::sample_bytes(d.sample_type)) : 0;   // bytes
+    if (planar) { d.b_offset = 0; d.g_offset = span; d.r_offset = 2 * span; }
+    if (const char* msg = check_wide((const void*)(uintptr_t)64, &d, &w->wb)) return msg;
+    if (!planar) return WIDE_PLANE_LIST_MESSAGES[WPLIST_PACKED];
+    if (!zero) return WIDE_PLANE_LIST_MESSAGES[WPLIST_OFFSETS];
+    if (nplanes != 3) return WIDE_PLANE_LIST_MESSAGES[WPLIST_NPLANES];
+    const int ss = w->wb.ss;
+    w->wb.b.n = f->n;
+    PlaneList& pl = w->pl;
+    pl.batch = w->wb.b;
+    pl.nplanes = 3;
+    pl.align = (unsigned)ss;
+    for (int k = 0; k < 3; ++k) { pl.offset[k] = (uint64_t)(k * (span / ss)); pl.extent[k] = (uint64_t)(span / ss); }
+    if (f->n == 0) return nullptr;
+    if (!planes) return WIDE_PLANE_LIST_MESSAGES[WPLIST_TABLE_NULL];
+    for (int i = 0; i < f->n; ++i)
+        for (int k = 0; k < 3; ++k) {
+            const void* p = planes[(size_t)i * 3 + k];
+            *bad_frame = i; *bad_plane = k;
+            if (!p) return WIDE_PLANE_LIST_MESSAGES[WPLIST_PTR_NULL];
+            if ((uintptr_t)p & ((uintptr_t)ss - 1)) return WIDE_PLANE_LIST_MESSAGES[WPLIST_PTR_ALIGN];
+        }
+    *bad_frame = *bad_plane = -1;
+    return nullptr;
+}
+
 }  // namespace melf

@@ -24,6 +24,25 @@
  * concurrently on the GPU, a third stream (or a call that needs the lane
  * another stream used last) is ordered behind that stream's work by an event.
  * Two batches' kernels never run against the same buffers at once.
+ *
+ * Stream order of the _dev entry points (tests/test_stream_order.py holds the library to it):
+ * - Without melf_ctx_set_frames_resident every command of a call -- a list's pointer-table upload, the gather / narrowing /
+ *   orienting kernel, prep, match and the kernel that writes the records -- is enqueued on `stream`; melf_process_stream_dev
+ *   enqueues on the two lanes' own streams, which first wait for everything `stream` held at the call, and `stream` then waits
+ *   for both.  The call waits for everything the caller's stream held at the call; what the caller enqueues on `stream` afterwards
+ *   is ordered behind the whole call: it sees the records and may overwrite the frames and the records.
+ * - With it, a contiguous batch (melf_process_batch_dev and the descriptor families' _dev calls): the caller's one promise is that
+ *   the frames are complete at the call.  Prep and match run on a lane's own stream and wait for nothing of `stream`; the kernel
+ *   that writes the records waits for everything `stream` held at the call; `stream` then waits for the end of the call.
+ * - With it, the list flow (frame lists, plane lists, wide frames, wide lists, oriented frames): no promise.  Only the pointer
+ *   table goes up at once; the gather / narrowing / orienting kernel and all behind it wait for everything `stream` held at the
+ *   call; `stream` then waits for the end of the call.  melf_process_stream_dev and melf_hls_inrange_close_dev do not look at the
+ *   mode (the mask is one kernel on `stream`).
+ * - A call that gets a lane another stream used last -- a third caller stream, a call after a switch of the mode -- waits for
+ *   everything that stream held.
+ * The host waits in three cases only: out_host is given (the call synchronises `stream`); a work buffer of the lane has to grow
+ * (the first call of a larger shape on that lane: the device is drained); a list call with a pointer table waits until the
+ * previous upload of that lane's table has finished.
  */
 #ifndef METERELF_HIP_H
 #define METERELF_HIP_H

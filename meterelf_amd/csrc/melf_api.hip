@@ -364,8 +364,8 @@ struct melf_ctx {
     bool frames_resident = false;
     int resident_next_lane = 0;
     hipEvent_t ev_call[NLANES] = {};     // caller-stream position at the time of a call (waited for by its dials kernel)
-    hipStream_t order_stream = nullptr;  // during a resident-mode call: the caller's stream (NULL stream: see order_null)
-    bool order_valid = false;
+    hipStream_t order_stream = nullptr;  // during a resident-mode batch call: the caller's stream (NULL is the null stream, a stream
+    bool order_valid = false;            // like any other: order_valid, not the handle, says that process_batch_on has to wait for it)
     hipStream_t lane_owner[NLANES] = {};
     bool lane_owned[NLANES] = {};
     uint64_t lane_used[NLANES] = {};

@@ -245,6 +245,21 @@ def read_dials(dials_hls, params):
     return res
 
 
+def read_dials_batch(crops_hls, params):
+    """read_dials of every crop of (N, th, tw, 3), the parameters and masks made once.  Returns a list of OrcResult."""
+    cp = params.c_params()
+    masks = params.masks()
+    order = params.name_order()
+    out = []
+    for crop in crops_hls:
+        crop = np.ascontiguousarray(crop)
+        res = OrcResult()
+        res.failed_dial = -1
+        lib().orc_read_dials(_ptr(crop), C.byref(cp), _ptr(masks), _ptr(order), C.byref(res))
+        out.append(res)
+    return out
+
+
 def process_crop(crop_bgr, params):
     crop_bgr = np.ascontiguousarray(crop_bgr)
     h, w, _ = crop_bgr.shape
